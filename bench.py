@@ -10,6 +10,11 @@ A step = one kk_forward over one batch (the whole acoustic path incl. duration p
 are REALISED are pinned to 5 frames per token so every rank does identical work: T = 130, F = 650,
 390 000 samples = 16.25 s per utterance).  Inputs (ids, style rows, weights) are resident in HBM before the
 timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything else the line can carry:
+the same K steps one batch (csm: one job) in flight, the per-kernel brackets and roofline figures, the B = 1 latency, the
+CPU baseline and, with --quantized, the other quantisation kernel.  `--dump-outputs DIR` writes what the last timed step
+returned (rank 0's view) as DIR/<name>.npy in float32 / float64; the inputs are seeded, so two builds compare output for output.
 """
 import argparse
 import ctypes
@@ -35,6 +40,34 @@ SR = 24000
 PEAK_TFLOPS = {"f32": 157.3, "bf16": 2500.0}
 PEAK_HBM_GBS = 8000.0
 PEAK_FP8_TFLOPS = 5000.0  # dense block-scaled fp8 (MI355X_MICROARCH.md)
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs: all files together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 kept, everything else (integer codes, durations) as float64, which holds
+    them exactly.  If the arrays exceed DUMP_BUDGET_BYTES, the largest keeps a fixed seeded sample of its rows (leading axis), whose
+    indices go to <name>_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for k, v in arrays.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu()
+            v = (v.float() if v.is_floating_point() and v.dtype != torch.float64 else v).numpy()
+        v = np.asarray(v)
+        out[k] = v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_BUDGET_BYTES:
+        big = max(out, key=lambda k: out[k].nbytes)
+        a = out[big]
+        row = a.nbytes // a.shape[0]
+        keep = (DUMP_BUDGET_BYTES - (total - a.nbytes) - 8 * a.shape[0] - 256 * (len(out) + 1)) // row  # (+ the .npy headers)
+        if keep < 1:
+            raise SystemExit(f"bench.py: --dump-outputs cannot fit one row of {big} in {DUMP_BUDGET_BYTES} bytes")
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], int(keep), replace=False))
+        out[big] = np.ascontiguousarray(a[rows])
+        out[big + "_rows"] = rows.astype(np.float64)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def cpu_baseline(cfg, w, utt, ref_s):
@@ -132,10 +165,17 @@ def main():
                          "10 s reference-audio prompt (125 Mimi frames) + 64 text ids, 125 frames generated greedily, Mimi decode included; a step is one "
                          "whole generation.")
     ap.add_argument("--dry-run", action="store_true", help="launcher rehearsal on CPU (gloo): rendezvous, barrier, MAX reduction, rank 0's line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: one batch / job in flight, per-kernel brackets and roofline, B = 1 latency, "
+                         "CPU baseline, the other quantisation kernel (--quantized), the CSM frame step (--config csm)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: become the launcher.  Nothing in this process has touched (or will touch) a GPU.
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -157,12 +197,13 @@ def main():
             dist_mod.destroy_process_group()
         return
     out = bench_kokoro(args, rank, world)
-    if args.quantized:  # (every rank: the second configuration has the same collectives)
+    if args.quantized:
+        out["quantization_kernel"] = args.quantization_kernel
+    if args.quantized and args.full:  # (every rank: the second configuration has the same collectives)
         # config 5 reports BOTH arithmetic choices for the quantised layer set: the default ("exact": dequantised weights, bf16 activations -- the
         # reference's semantics) is `value`; the opt-in fp8 kernels (or vice versa with --quantization-kernel mxfp8) ride along
         other = "mxfp8" if args.quantization_kernel == "exact" else "exact"
         alt = bench_kokoro(args, rank, world, quantization_kernel=other, brief=True)
-        out["quantization_kernel"] = args.quantization_kernel
         out["other_quantization_kernel"] = {"kernel": other, "value": alt["value"], "ms_per_step": alt["ms_per_step"],
                                             "note": "mxfp8 = e4m3 weights AND activations on v_mfma_scale_f32_32x32x64_f8f6f4 (opt-in, narrower than the reference's arithmetic)"}
     if rank == 0:
@@ -214,11 +255,15 @@ def bench_csm(args, rank, world):
         prompts = models[k].prompt_frames_batch(ctx, texts, 0, voice_match=False)  # the B reference clips in one Mimi.encode call
         return models[k].generate_batch(prompts, max_audio_length_ms=80 * FRAMES, temperature=0.0, stop_on_eos=False), prompts[0][0].shape[0]
 
+    last = {}  # the result of step n - 1 of the latest run_steps (--dump-outputs)
+
     def run_steps(n, jobs):
         """n steps over `jobs` jobs in flight (threads pull step numbers from one counter; a thread's launches go to its own stream)."""
         if jobs == 1:
-            for _ in range(n):
-                step(0)
+            for i in range(n):
+                r = step(0)
+                if i == n - 1:
+                    last["res"] = r[0]
             return
         import threading
 
@@ -231,7 +276,10 @@ def bench_csm(args, rank, world):
                         if left[0] <= 0:
                             break
                         left[0] -= 1
-                    step(k)
+                        i = n - 1 - left[0]
+                    r = step(k)
+                    if i == n - 1:
+                        last["res"] = r[0]
                 streams[k].synchronize()
 
         th = [threading.Thread(target=worker, args=(k,)) for k in range(jobs)]
@@ -255,29 +303,34 @@ def bench_csm(args, rank, world):
     run_steps(args.steps, NS)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # the last step's batch: every stream's waveform (all FRAMES long: EOS is ignored) and its codes
+        r = last["res"]
+        dump_outputs(args.dump_outputs, {"audio": torch.stack(r.audio), "codes": r.codes, "frames": np.asarray(r.frames)})
     dt_one = None
-    if NS > 1:  # the same K steps with one job in flight, for reference
+    if NS > 1 and args.full:  # the same K steps with one job in flight, for reference
         barrier()
         t1 = time.perf_counter()
         run_steps(args.steps, 1)
         barrier()
         dt_one = time.perf_counter() - t1
-    # the frame step on its own, HIP events on the stream the frames are launched on (torch's current stream): FRAMES single-token frames
     csm = model.model
     n = cfg["audio_num_codebooks"]
-    tok = torch.zeros((B, 1, n + 1), dtype=torch.int32, device=csm.device)
-    msk = torch.zeros((B, 1, n + 1), dtype=torch.float32, device=csm.device)
-    msk[:, 0, :n] = 1
-    for _ in range(3):
-        codes = csm.generate_frame(tok, msk)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    nfr = 50
-    e0.record()
-    for _ in range(nfr):
-        codes = csm.generate_frame(tok, msk)
-    e1.record()
-    torch.cuda.synchronize()
-    ms_frame = e0.elapsed_time(e1) / nfr
+    ms_frame = None
+    if args.full:
+        # the frame step on its own, HIP events on the stream the frames are launched on (torch's current stream): FRAMES single-token frames
+        tok = torch.zeros((B, 1, n + 1), dtype=torch.int32, device=csm.device)
+        msk = torch.zeros((B, 1, n + 1), dtype=torch.float32, device=csm.device)
+        msk[:, 0, :n] = 1
+        for _ in range(3):
+            codes = csm.generate_frame(tok, msk)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        nfr = 50
+        e0.record()
+        for _ in range(nfr):
+            codes = csm.generate_frame(tok, msk)
+        e1.record()
+        torch.cuda.synchronize()
+        ms_frame = e0.elapsed_time(e1) / nfr
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=csm.device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -303,15 +356,17 @@ def bench_csm(args, rank, world):
                                f"audio ({S - N_TEXT} Mimi frames incl. the EOS frame) + {N_TEXT} text ids = {S} positions, {FRAMES} frames ({FRAMES * 0.08:.0f} s) "
                                f"generated per stream, Mimi.decode included; replicas x{world}" + (f"; {NS} such jobs in flight per GPU (own stream, thread, KV caches; one copy of the weights)" if NS > 1 else ""),
                    "global_batch": B * world, "parallelism": f"replicas x{world}"},
-        "ms_per_frame": ms_frame, "frames_per_step": FRAMES, "jobs_in_flight": NS,
-        "ms_per_step_one_job_in_flight": (dt_one / args.steps * 1e3) if dt_one is not None else None,
-        "roofline": {"bound": "hbm", "kernel": "CSM frame step (six launches per Llama layer, Linears on gemvm_kernel (matrix cores); 16 + 31 x 4 layer passes)",
-                     "achieved": bytes_frame / (ms_frame * 1e-3) / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                     "frac": bytes_frame / (ms_frame * 1e-3) / 1e9 / PEAK_HBM_GBS, "traffic": None,
-                     "bytes_per_frame": bytes_frame, "note": "algorithmic bytes = every Linear matrix a frame multiplies by, in bf16; one launch = one frame step "
-                     "(hipGraph replay), duration from HIP events on the launch stream over 50 frames"},
+        "frames_per_step": FRAMES, "jobs_in_flight": NS,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        out["ms_per_frame"] = ms_frame
+        out["ms_per_step_one_job_in_flight"] = (dt_one / args.steps * 1e3) if dt_one is not None else None
+        out["roofline"] = {"bound": "hbm", "kernel": "CSM frame step (six launches per Llama layer, Linears on gemvm_kernel (matrix cores); 16 + 31 x 4 layer passes)",
+                           "achieved": bytes_frame / (ms_frame * 1e-3) / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                           "frac": bytes_frame / (ms_frame * 1e-3) / 1e9 / PEAK_HBM_GBS, "traffic": None,
+                           "bytes_per_frame": bytes_frame, "note": "algorithmic bytes = every Linear matrix a frame multiplies by, in bf16; one launch = one frame step "
+                           "(hipGraph replay), duration from HIP events on the launch stream over 50 frames"}
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_csm(cfg, w, mcfg, mw, res, S)
     return out
 
@@ -421,9 +476,10 @@ def bench_kokoro(args, rank, world, quantization_kernel=None, brief=False):
             if pending[j] is not None:
                 pending[j].wait()  # the batch that used this buffer last has left it
                 pending[j] = None
-            engs[k].forward(ids, lens, ref_s, speed, Fmax, forced_dur=forced, noise_mode=_lib.NOISE_PHILOX, seed=1000 + i, out=wavs[j])
+            res = engs[k].forward(ids, lens, ref_s, speed, Fmax, forced_dur=forced, noise_mode=_lib.NOISE_PHILOX, seed=1000 + i, out=wavs[j])
             if world > 1:
                 pending[j] = gather_waveforms(wavs[j], gathered[j], dist, async_op=True)
+        return res
 
     def drain():
         for j in range(nbuf):
@@ -450,11 +506,17 @@ def bench_kokoro(args, rank, world, quantization_kernel=None, brief=False):
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(nwarm + i)
+        res = step(nwarm + i)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and not brief:
+        # what the caller of the last step receives: the waveforms (all shards, gathered, with N > 1), the predicted durations and frame counts
+        wav_last, pred_last, nfr_last = res
+        if world > 1:
+            wav_last = gathered[(nwarm + args.steps - 1) % nbuf]
+        dump_outputs(args.dump_outputs, {"waveforms": wav_last, "pred_dur": pred_last, "n_frames": nfr_last})
     dt_one = None
-    if NS > 1 and not brief:  # the same K steps strictly one after the other (engine 0, one stream), for reference
+    if NS > 1 and not brief and args.full:  # the same K steps strictly one after the other (engine 0, one stream), for reference
         for i in range(2 * nbuf):
             step(i, single=True)  # (engine 0 captures its graph for every output buffer)
         barrier()
@@ -464,7 +526,7 @@ def bench_kokoro(args, rank, world, quantization_kernel=None, brief=False):
         barrier()
         dt_one = time.perf_counter() - t1
     prof, dt_prof = None, None
-    if not args.no_profile and not brief:
+    if args.full and not args.no_profile and not brief:
         eng.profile_begin()  # forwards with an open profile run eagerly
         barrier()
         t1 = time.perf_counter()
@@ -476,7 +538,7 @@ def bench_kokoro(args, rank, world, quantization_kernel=None, brief=False):
 
     # p50 per-utterance latency (second half of BASELINE.json's metric): B = 1, same shapes, after the timed region
     p50_ms = None
-    if rank == 0 and not args.no_latency and not brief:
+    if rank == 0 and args.full and not args.no_latency and not brief:
         i1, l1, T1 = eng.pack_ids(utts[:1])
         r1, s1, f1 = ref_s[:1].contiguous(), speed[:1].contiguous(), forced[:1].contiguous()
         w1 = torch.empty((1, 600 * Fmax), dtype=torch.float32, device=dev)
@@ -560,7 +622,7 @@ def bench_kokoro(args, rank, world, quantization_kernel=None, brief=False):
             tot = sum(v["ms"] for v in prof.values())
             out["kernel_ms_per_step"] = {k: round(v["ms"] / args.steps, 3) for k, v in prof.items() if v["launches"]}
             out["kernel_ms_per_step"]["_sum_bracketed"] = round(tot / args.steps, 3)
-        if world == 1 and not args.no_cpu_baseline and not brief:
+        if world == 1 and args.full and not args.no_cpu_baseline and not brief:
             out["cpu_baseline"] = cpu_baseline(cfg, P.synth_checkpoint(cfg, 0), utts[0], ref_np[0:1])
     del eng, engs
     torch.cuda.empty_cache()

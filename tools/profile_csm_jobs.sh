@@ -6,7 +6,7 @@ out=$root/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 cd $root
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -o k -- python3 bench.py --config csm --steps 4 --warmup 1 --no-cpu-baseline > $out/bench.json 2> $out/kt.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -o k -- python3 bench.py --full --config csm --steps 4 --warmup 1 --no-cpu-baseline > $out/bench.json 2> $out/kt.err
 f=$(find $out/kt -name '*kernel_stats.csv' | head -1)
 python3 - $f > $out/kernel_stats.txt <<'PY'
 import csv, sys
