@@ -328,9 +328,6 @@ int kk_csm_generate_frame(kk_csm* m, void* stream, int B, int S, const int32_t* 
  * hipGraphLaunch (the backbone position is a device counter, so the captured step is position-independent); results are unchanged */
 int kk_csm_set_graph_mode(kk_csm* m, int on);
 int kk_csm_debug_logits(kk_csm* m, void* stream, int B, float* dst); /* logits of the last frame, [n_cb][B][audio_vocab] */
-/* TIMING ONLY (results are wrong while a bit is set): kernel classes of the single-token step that are not launched; process-wide.
-   bit 0 q|k|v, 1 attention, 2 o, 3 gate|up, 4 down, 5 split-K combine, 6 heads, 7 sampler, 8 projection (tools/csm_skip_sweep.py) */
-int kk_csm_debug_skip(int mask);
 /* In-kernel wall-clock marks (100 MHz counter) of the single-token step's instrumented kernels, 8 uint64 per launch in launch order:
    class id, earliest workgroup start, latest workgroup end, workgroup 0 after its input loads, then workgroup 0's own start, shader-clock
    count at start, end, shader-clock count at end (core clock = cycles / wall x 100 MHz).  buf: device memory for `capacity`

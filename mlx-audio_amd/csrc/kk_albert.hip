@@ -313,9 +313,7 @@ int kk_launch_attention(const KKAttnArgs& a, int B, int dtype, hipStream_t st) {
     attr_once.done();
   }
   dim3 grid(a.heads, B, kk_cdiv(a.Tmax, QT));
-  static int no_mfma = -1;
-  if (no_mfma < 0) no_mfma = getenv("KK_ATTN_VALU") ? 1 : 0;  // A/B switch: the fp32 VALU kernel also handles bf16 tensors
-  if (dtype == KK_BF16 && !no_mfma && a.ld % 8 == 0 && a.ldo % 8 == 0 && a.hs % 8 == 0 && !(((uintptr_t)a.qkv | (uintptr_t)a.out) & 15)) {
+  if (dtype == KK_BF16 && a.ld % 8 == 0 && a.ldo % 8 == 0 && a.hs % 8 == 0 && !(((uintptr_t)a.qkv | (uintptr_t)a.out) & 15)) {
     hipLaunchKernelGGL(attention_mfma_kernel, grid, dim3(64), 0, st, a);
     KK_CHECK_LAUNCH();
     return 0;

@@ -268,25 +268,6 @@ bool kk_mfma_eligible(int Cin, int Cout, int Kw, int mode, int stride, int dil) 
   return halo <= MAX_HALO;
 }
 
-// rows of the output tile a launch with Q rows per phase uses (128 or 192); also the statistics tile size
-int kk_mfma_tile_rows(int Q) {
-  static int forced = -1;
-  if (forced < 0) {
-    const char* e = getenv("KK_MFMA_BM");
-    forced = e ? atoi(e) : 0;
-  }
-  if (forced == 128 || forced == 192) return forced;
-  (void)Q;
-  // measured (tools/bench_conv.py): 192 rows (3 MFMA row blocks per wave, 250 VGPRs, 73 KB LDS -> still two workgroups per CU)
-  // streams a third less W per MFMA than 128 and is 8-10 % faster on every shape; a 256-row variant spilled and was slower
-  return 192;
-}
-
-int kk_mfma_stat_tile_rows(const KKMfmaArgs& a, int out_dtype) {
-  (void)out_dtype;
-  return kk_mfma_tile_rows(a.Q);
-}
-
 int kk_launch_conv_mfma(const KKMfmaArgs& a, int B, int out_dtype, hipStream_t st) {
   if (a.Q <= 0 || B <= 0) return 0;
   if (a.CinP % CK != 0 || a.CoutP % BN != 0) return kk_fail("conv_mfma: CinP must be a multiple of 64 and CoutP of 128");
@@ -295,21 +276,15 @@ int kk_launch_conv_mfma(const KKMfmaArgs& a, int B, int out_dtype, hipStream_t s
     return kk_fail("conv_mfma: pointers must be 16-byte aligned");
   if (a.ldx < a.CinP) return kk_fail("conv_mfma: input pitch smaller than the padded channel count");
   if (a.nrm_a && (a.nrm_stride % 4 != 0 || a.nrm_stride < a.CinP)) return kk_fail("conv_mfma: bad AdaIN parameter pitch");
-  const int rows = kk_mfma_tile_rows(a.Q);
   const int nrm = a.nrm_a == nullptr ? 0 : (a.nrm_act == KK_ACT_SNAKE ? 1 : 2);
   if (nrm == 1 && a.nrm_C % 4 != 0) return kk_fail("conv_mfma: the fused Snake input needs a channel count that is a multiple of 4");
   KKMfmaArgs g = a;
   if (nrm == 2 && a.nrm_act != KK_ACT_LRELU) g.nrm_slope = 1.0f;  // plain AdaIN: identity activation
   if (out_dtype != KK_BF16) {
     if (nrm) return kk_fail("conv_mfma: fused AdaIN input needs a bf16 output");
-    return rows == 192 ? launch_one<float, 96, 0>(g, B, st) : launch_one<float, 64, 0>(g, B, st);
+    return launch_one<float, KK_MFMA_TILE_ROWS / 2, 0>(g, B, st);
   }
-  if (rows == 192) {
-    if (nrm == 1) return launch_one<bf16_t, 96, 1>(g, B, st);
-    if (nrm == 2) return launch_one<bf16_t, 96, 2>(g, B, st);
-    return launch_one<bf16_t, 96, 0>(g, B, st);
-  }
-  if (nrm == 1) return launch_one<bf16_t, 64, 1>(g, B, st);
-  if (nrm == 2) return launch_one<bf16_t, 64, 2>(g, B, st);
-  return launch_one<bf16_t, 64, 0>(g, B, st);
+  if (nrm == 1) return launch_one<bf16_t, KK_MFMA_TILE_ROWS / 2, 1>(g, B, st);
+  if (nrm == 2) return launch_one<bf16_t, KK_MFMA_TILE_ROWS / 2, 2>(g, B, st);
+  return launch_one<bf16_t, KK_MFMA_TILE_ROWS / 2, 0>(g, B, st);
 }

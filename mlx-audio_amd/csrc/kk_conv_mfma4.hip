@@ -80,10 +80,9 @@ union U32x8 {
 };
 
 // NRM: 0 = raw input, 1 = AdaIN + Snake while staging, 2 = AdaIN + LeakyReLU(nrm_slope; 1 = identity) while staging
-// WM = 96: 192-row tile, 2 workgroups per CU (230-256 VGPRs).  WM = 64: 128-row tile, 3 workgroups per CU (<= 168 VGPRs, 32 KB LDS): more
-// W traffic per MFMA, but a third workgroup to cover the serial prologue / slab staging / epilogue phases of the other two.
+// WM = 96: 192-row tile (KK_MFMA_TILE_ROWS), 2 workgroups per CU (230-256 VGPRs)
 template <typename TO, int WM, int NRM>
-__global__ __launch_bounds__(256, (WM == 96 ? 2 : 3)) __attribute__((amdgpu_waves_per_eu((WM == 96 ? 2 : 3), (WM == 96 ? 2 : 3)))) void conv_mfma4_kernel(KKMfmaArgs a) {
+__global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_mfma4_kernel(KKMfmaArgs a) {
   constexpr int BM = 2 * WM, MI = WM / 32;
   (void)MI;
   using G = Geo<BM>;
@@ -105,14 +104,11 @@ __global__ __launch_bounds__(256, (WM == 96 ? 2 : 3)) __attribute__((amdgpu_wave
     int lid = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
     const int per = total / 8, rem = total - per * 8;
     const int xcd = lid & 7, idx = lid >> 3;
-    if (!(a.dbg & 4)) lid = xcd * per + (xcd < rem ? xcd : rem) + idx;  // dbg bit 2 (KK_MFMA_NOXCD=1): the dispatcher's own order, for A/B timing
-    else { by = blockIdx.y; bx = blockIdx.x; bz = blockIdx.z; }
-    if (!(a.dbg & 4)) {
-      by = lid % gy;  // column blocks innermost
-      const int t = lid / gy;
-      bx = t % gx;
-      bz = t / gx;
-    }
+    lid = xcd * per + (xcd < rem ? xcd : rem) + idx;
+    by = lid % gy;  // column blocks innermost
+    const int t = lid / gy;
+    bx = t % gx;
+    bz = t / gx;
   }
   const int b = bz / nphase, phase = bz - b * nphase;
   const int q0 = bx * BM, n0 = by * BN;
@@ -305,11 +301,7 @@ int launch_one(const KKMfmaArgs& a, int B, hipStream_t st) {
   }
   const int nphase = a.mode == KK_CONVT ? a.stride : 1;
   dim3 grid(kk_cdiv(a.Q, 2 * WM), a.CoutP / BN, B * nphase);
-  static int noxcd = -1;
-  if (noxcd < 0) noxcd = getenv("KK_MFMA_NOXCD") ? 1 : 0;
-  KKMfmaArgs a2 = a;
-  if (noxcd) a2.dbg |= 4;
-  hipLaunchKernelGGL((conv_mfma4_kernel<TO, WM, NRM>), grid, dim3(256), G::LDS_BYTES, st, a2);
+  hipLaunchKernelGGL((conv_mfma4_kernel<TO, WM, NRM>), grid, dim3(256), G::LDS_BYTES, st, a);
   KK_CHECK_LAUNCH();
   return 0;
 }
@@ -370,11 +362,6 @@ int kk_launch_conv_mfma4(const KKMfmaArgs& a, int B, int out_dtype, hipStream_t 
   KKMfmaArgs g = a;
   if (nrm == 2 && a.nrm_act != KK_ACT_LRELU) g.nrm_slope = 1.0f;  // plain AdaIN: identity activation
   if (out_dtype != KK_BF16) return kk_fail("conv_mfma4: bf16 output only");
-  if (kk_mfma_tile_rows(a.Q) == 128) {
-    if (nrm == 1) return launch_one<bf16_t, 64, 1>(g, B, st);
-    if (nrm == 2) return launch_one<bf16_t, 64, 2>(g, B, st);
-    return launch_one<bf16_t, 64, 0>(g, B, st);
-  }
   if (nrm == 1) return launch_one<bf16_t, 96, 1>(g, B, st);
   if (nrm == 2) return launch_one<bf16_t, 96, 2>(g, B, st);
   return launch_one<bf16_t, 96, 0>(g, B, st);

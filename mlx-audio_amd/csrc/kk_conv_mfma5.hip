@@ -195,7 +195,7 @@ __global__ __launch_bounds__(512, 2) void conv_mfma5_kernel(KKMfmaArgs a, int B)
     const int kofs = 8 * (lane >> 5);
 #endif
     KK_BAR5();  // [P] slab 0 of the first tile is in LDS (and s_lout is written)
-    if (!(a.dbg & 16)) __builtin_amdgcn_s_setprio(3);  // beside a service wave on the same SIMD, the MFMA wave's LDS reads / weight loads issue first
+    __builtin_amdgcn_s_setprio(3);  // beside a service wave on the same SIMD, the MFMA wave's LDS reads / weight loads issue first
     const unsigned long long trm0 = TR5_NOW();
     (void)trm0;
 #ifdef KK_MFMA16
@@ -654,12 +654,12 @@ __global__ __launch_bounds__(512, 2) void conv_mfma5_kernel(KKMfmaArgs a, int B)
     load_x(s2, c2, XL, xkL);
     if (!stage2) xkL = 0;
     const unsigned long long t1 = TR5_NOW();
-    if (have_prev && c >= act0 && !(a.dbg & 4)) {  // (its residual rows were requested a slab period ago)
+    if (have_prev && c >= act0) {  // (its residual rows were requested a slab period ago)
       epi_compute(prev, (c - act0) * TPP);
       if (tail && a.stat_part) stats_to_lds();
     }
     const unsigned long long t2 = TR5_NOW();
-    if (stage1 && !(a.dbg & 8)) transform_x(c1, XT, xkT, slab_inside(s1, c1));
+    if (stage1) transform_x(c1, XT, xkT, slab_inside(s1, c1));
     // request the residual rows of the NEXT period's epilogue share: of `prev` inside a tile, of `cur` (the next `prev`) at its end
     {
       const int tb = tail ? 0 : (c + 1 >= act0 ? (c + 1 - act0) * TPP : 0);
@@ -750,12 +750,6 @@ int kk_launch_conv_mfma5(const KKMfmaArgs& a, int B, int out_dtype, hipStream_t 
   const int nrm = a.nrm_a == nullptr ? 0 : (a.nrm_act == KK_ACT_SNAKE ? 1 : 2);
   KKMfmaArgs g = a;
   if (nrm == 2 && a.nrm_act != KK_ACT_LRELU) g.nrm_slope = 1.0f;  // plain AdaIN: identity activation
-  static int dbg = -1;
-  if (dbg < 0) {
-    const char* e = getenv("KK_MFMA5_DBG");  // timing experiments only (wrong results): 2 no X loads, 4 no epilogue, 8 no transform
-    dbg = e ? atoi(e) : 0;
-  }
-  g.dbg = dbg;
   if (nrm == 1) return launch5n<1>(g, B, st);
   if (nrm == 2) return launch5n<2>(g, B, st);
   return launch5n<0>(g, B, st);

@@ -27,18 +27,13 @@ struct Lin {  // generic-kernel pack [1][Cin][ldw]
   size_t off = 0;
   int Cin = 0, Cout = 0, ldw = 0;
   const float* w = nullptr;
-  // bf16 weight mode (kk_csm_set_weight_dtype): the same matrix as bf16 in COLUMN-BLOCK order for the fused GEMV of the single-token
-  // steps: [Cout / CB][Cin][CB] with CB = 8 * oct columns per workgroup, so a workgroup streams one contiguous region
-  size_t boff = 0;
-  const uint16_t* wb = nullptr;
-  int oct = 0;  // 0 = no block pack (K not a multiple of 64)
-  // the same bf16 matrix in FRAGMENT order for the matrix-core GEMV (gemvm_kernel): [Cout / (16 nsub)][Cin / 32][nsub][64 lanes][8]: a wave
+  // bf16 weight mode (kk_csm_set_weight_dtype): the same matrix as bf16 in FRAGMENT order for the matrix-core GEMV (gemvm_kernel) of the
+  // single-token steps and the prompt GEMM (gemmp_kernel): [Cout / (16 nsub)][Cin / 32][nsub][64 lanes][8]: a wave
   // load of 1 KiB is one 32 x 16 B operand of v_mfma_f32_16x16x32_bf16 (lane L: k = 32 c + 8 (L / 16) + j, n = 16 s + L % 16)
   size_t moff = 0;
   const uint16_t* wm = nullptr;
   int nsub = 0;  // 0 = no fragment pack (K not a multiple of 32)
   int ks = 1;    // split-K slices of a deep projection (K >= 4096): partial tiles + combine
-  int cached = 0;  // 1: plain (cacheable) weight loads instead of nontemporal ones
 };
 struct Vec {
   size_t off = 0;
@@ -99,15 +94,6 @@ namespace {
 
 int rup(int v, int m) { return (v + m - 1) / m * m; }
 
-// kk_csm_debug_skip (TIMING ONLY, wrong results): kernel classes of the single-token step that are not launched -- bit 0 q|k|v, 1 attention,
-// 2 o, 3 gate|up, 4 down, 5 split-K combine, 6 heads, 7 sampler, 8 projection: the in-situ cost of a class is the frame time it removes
-int g_skip = 0;
-// A/B switches consulted on the launch path (environment, read once): bit 0 KK_CSM_PROMPT_F32, 1 KK_CSM_OLD_ATTN, 2 KK_CSM_NO_PROJ_TABLE
-int ab_switches() {
-  static int v = -1;
-  if (v < 0) v = (getenv("KK_CSM_PROMPT_F32") ? 1 : 0) | (getenv("KK_CSM_OLD_ATTN") ? 2 : 0) | (getenv("KK_CSM_NO_PROJ_TABLE") ? 4 : 0);
-  return v;
-}
 // kk_csm_debug_timestamps: in-kernel wall-clock marks (100 MHz) of the instrumented kernels, 8 words per launch in launch order:
 // [class id, earliest workgroup start, latest workgroup end, workgroup 0 after its input loads, workgroup 0's start / shader clock at start / end / shader
 // clock at end]; null in production
@@ -322,7 +308,7 @@ __global__ __launch_bounds__(128) void attn_cache_kernel(const float* qkv, int S
 
 // attn_step_kernel (round 3): the single-token attention over a SHORT cache (max_pos <= 64: the depth decoder's 33 positions, small test
 // stacks) as ONE memory round trip.  attn_cache_kernel walks the keys in dependent steps (a thread per key with 2 x 16 loads, then the
-// values 4 keys at a time): 7.6 us per launch in the frame (tools/csm_skip_sweep.py), 124 launches.  Here a workgroup owns one (item, kv
+// values 4 keys at a time): 7.6 us per launch in the frame (frame time with it not launched), 124 launches.  Here a workgroup owns one (item, kv
 // head) and its G = H / KV query heads: every cached K and V row, the new q / k / v and the RoPE row are requested at once, land in LDS
 // (K rows padded to hd + 4 floats: a lane per key reads 16-byte pieces without bank conflicts), and scores, softmax (a lane per key, one
 // wave per head) and the weighted sum run out of LDS.  RoPE of q / k and the cache append are fused as in attn_cache_kernel<true>.
@@ -967,24 +953,12 @@ __global__ __launch_bounds__(256) void skinny_reduce_kernel(const float* part, i
 
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
-// Fused GEMV of the single-token steps (bf16 weight mode): out[m][n] = sum_k f(x)[m][k] W[k][n] for M <= 16 rows, with NO split-K through
-// HBM and no separate reduce / norm / activation launches -- a Llama layer is five launches (qkv, attention, o, gate|up, down).
-//   * a workgroup owns CB = 8 * OCT output columns for ALL of K; the weights are packed [N / CB][K][CB] (bf16), so it streams one contiguous
-//     region: lane = (k-sub, column octet) takes 16 bytes = 8 columns of one k row, a wave instruction covers 64 / OCT consecutive k rows
-//     (1 KiB contiguous), U of them in flight per thread; OCT = 1 for the narrow matrices (>= 128 workgroups even for N = 1024), 8 for gate|up;
-//   * the input rows live in LDS as xs[row quad][k][4] fp32, staged per 1024-row K chunk with the PROLOGUE applied on the way in:
-//       PRO 0 plain rows; PRO 1 RMSNorm(x) * w (every workgroup recomputes the row norms: M x K floats from L2, against its own 16-256 KB of
-//       weights); PRO 2 silu(gate) * up of a gate|up pair; PRO 3 rows gathered from the audio embedding table by code (the depth decoder's
-//       input `curr`, sesame.py:373-392), for two-row items the first row from x;
-//   * a weight meets all rows in packed fp32 FMAs (accumulators acc[8 columns][MT / 2 row pairs]); per lane the k order is fixed by the
-//     layout, so a row's bits do not depend on its batch neighbours or on MT;
-//   * the lanes' / waves' partial sums meet in LDS in a fixed order; EPI 1 adds the residual (h += ...) in place.
 // h[m][n] += sum over the K slices of a split-K launch (slice order): the combine of the deep down projections
 __global__ __launch_bounds__(256) void combine_slices_kernel(const float* part, int KS, long long pss, long long n, float* h, unsigned long long* ts) {
   ts_begin(ts, 2);
   const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
   if (e >= n) return;
-  // all slices are requested at once (a plain loop is KS dependent L2 round trips); KS <= 16 (gemv_slices)
+  // all slices are requested at once (a plain loop is KS dependent L2 round trips); KS <= 16 (Lin::ks)
   float v[16];
 #pragma unroll
   for (int ks = 0; ks < 16; ++ks) v[ks] = part[(long long)(ks < KS ? ks : 0) * pss + e];
@@ -995,417 +969,6 @@ __global__ __launch_bounds__(256) void combine_slices_kernel(const float* part, 
   h[e] = h0 + t;
   ts_end(ts);
 }
-
-// sum over the 32 lanes of a half wave (butterfly)
-__device__ __forceinline__ float q32_sum(float v) {
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// 16-byte weight load that is not kept in the caches (a frame reads every matrix once; MI355X_MICROARCH.md nt-weights: -5 ... -10 % per layer)
-__device__ __forceinline__ uint4 ld_w_nt(const uint4* p, int dbg = 0) {
-  if (dbg & 8) return make_uint4(0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u);
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4 v = __builtin_nontemporal_load((const u32x4*)p);
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-// NPRE: weight loads a wave keeps in flight (requested BEFORE the prologue, then a ring in the main loop).  Round 2 had 8 before the prologue
-// and groups of FG_U = 4 afterwards, each group an exposed HBM round trip: 16-32 KB outstanding per CU, gate|up 33.5 MB in 16 us = 2.1 TB/s.
-template <int MT, int OCT, int PRO, int EPI, int NPRE>
-__global__ __launch_bounds__(256) void fused_gemv_kernel(FGArgs a) {
-  constexpr int CB = 8 * OCT, KSUB = 64 / OCT, MP = MT / 2, NQ = MT / 4, OUT = CB * 8;
-  constexpr int KCH = 16384 / MT;           // k rows staged at a time: xs is 64 KB (2048 rows for 8 input rows, 1024 for 16)
-  constexpr int NH = (PRO == 2 && KCH / 4 / 256 >= 2) ? 2 : 1;  // the gated prologue holds two values per item: two half passes where there is more than one quad per thread
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* xs = sm;                                   // [NQ][KCH][4]
-  float* red = sm;                                  // [4 waves][KSUB][OUT] (aliases xs after the main loop)
-  float* red2 = sm + 4 * KSUB * OUT;                // [4][OUT]
-  float* rs = red2 + 4 * OUT;                       // [16] row scales (PRO 1)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int oct = lane % OCT, ksub = lane / OCT;
-  const int nb = blockIdx.x;
-  const int K = a.K, M = a.M;
-  // split-K (gridDim.y > 1, the deep down projections): this workgroup owns k rows [k_lo, k_hi) and writes a partial tile
-  const int Kper = K / gridDim.y, k_lo = blockIdx.y * Kper, k_hi = k_lo + Kper;
-  const uint4* wblk = (const uint4*)(a.w + (long long)nb * K * CB) + oct;  // row k of the block at + k * OCT uint4
-  // ---- the first NPRE weight loads of this wave go out before anything else: they do not depend on the input rows
-  uint4 wpre[NPRE];
-  {
-    const int kn0 = min(KCH, k_hi - k_lo), nL0 = kn0 / KSUB;
-#pragma unroll
-    for (int i = 0; i < NPRE; ++i) {
-      const int L = wave + 4 * i;
-      wpre[i] = ld_w_nt(wblk + (long long)(k_lo + (L < nL0 ? L : wave % nL0) * KSUB + ksub) * OCT, a.dbg);
-    }
-  }
-  // input row m of this launch as an element offset from its base (PRO 3: an item's last row comes from the audio embedding table,
-  // sesame.py:373-392, its other rows from x)
-  int rowoff[MT];
-  bool rowemb[MT];
-#pragma unroll
-  for (int m = 0; m < MT; ++m) {
-    const int mm = m < M ? m : 0;
-    rowemb[m] = false;
-    if (PRO == 3) {
-      const int item = mm / a.rows, r = mm - item * a.rows;
-      rowemb[m] = r == a.rows - 1;
-      rowoff[m] = rowemb[m] ? (clamp_id(a.codes[(long long)item * a.cstride], a.V) + a.cb * a.V) * K : (int)(item * a.xrs);
-    } else {
-      rowoff[m] = (int)(mm * a.xrs);
-    }
-  }
-  auto rowptr = [&](int m) __attribute__((always_inline)) -> const float* { return (PRO == 3 && rowemb[m] ? a.emb : a.x) + rowoff[m]; };
-  if (PRO == 1 && K > KCH) {  // rows longer than a chunk (16 input rows of the backbone): the row scales need their own pass
-    float ssr[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m) ssr[m] = 0.f;
-    const int n4 = K >> 2;
-    for (int c0 = tid; c0 < n4; c0 += 256 * 2) {
-      float4 v[2][MT];
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int m = 0; m < MT; ++m) v[i][m] = *((const float4*)rowptr(m) + (c0 + 256 * i < n4 ? c0 + 256 * i : c0));
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const float live = c0 + 256 * i < n4 ? 1.0f : 0.0f;
-#pragma unroll
-        for (int m = 0; m < MT; ++m) ssr[m] += live * (((v[i][m].x * v[i][m].x + v[i][m].y * v[i][m].y) + v[i][m].z * v[i][m].z) + v[i][m].w * v[i][m].w);
-      }
-    }
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-      float t = ssr[m];
-      for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-      if (lane == 0) red2[wave * 16 + m] = t;
-    }
-    __syncthreads();
-    if (tid < MT) rs[tid] = 1.0f / sqrtf((((red2[tid] + red2[16 + tid]) + red2[32 + tid]) + red2[48 + tid]) / (float)K + a.eps);
-  }
-  float ssq[MT];  // PRO 1 with the whole row in one chunk: sums of squares of this thread's share of every input row
-#pragma unroll
-  for (int m = 0; m < MT; ++m) ssq[m] = 0.f;
-  sk2f acc[8][MP];
-#pragma unroll
-  for (int c = 0; c < 8; ++c)
-#pragma unroll
-    for (int i = 0; i < MP; ++i) acc[c][i] = sk2f{0.f, 0.f};
-  for (int kc = k_lo; kc < k_hi; kc += KCH) {
-    const int kn = min(KCH, k_hi - kc);
-    __syncthreads();  // (the previous chunk's readers are done)
-    // ---- stage the chunk (round 3: 16-byte loads): thread t takes the k QUADS t, t + 256, ... of EVERY input row (one float4 per row, coalesced
-    // along k; round 2 read single floats, half of them clamped duplicates) and writes one 16-byte LDS store per (k, row quad).  With the norm
-    // prologue and the whole row in this chunk the row scale is NOT on the way in: x * w is staged, the sums of squares stay in registers through
-    // the main loop and rms^-1 multiplies the finished dot products (defer_rs): no reduction + two barriers ahead of the weight stream.
-    const bool defer_rs = PRO == 1 && K <= KCH;
-    if (!(a.dbg & 1))
-#pragma unroll
-    for (int hh = 0; hh < NH; ++hh) {
-      constexpr int NI4 = KCH / 4 / 256 / NH;  // k quads per thread and pass
-      float4 g[NI4][MT], u[PRO == 2 ? NI4 : 1][MT], nw4[PRO == 1 ? NI4 : 1];
-      const int nq = kn >> 2;
-#pragma unroll
-      for (int i = 0; i < NI4; ++i) {
-        const int k4 = tid + 256 * (hh * NI4 + i);
-        const int kk = kc + 4 * (k4 < nq ? k4 : tid % nq);
-        if (PRO == 1) nw4[i] = *(const float4*)(a.nw + kk);
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-          g[i][m] = *(const float4*)(rowptr(m) + kk);
-          if (PRO == 2) u[i][m] = *(const float4*)(rowptr(m) + K + kk);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < NI4; ++i) {
-        const int k4 = tid + 256 * (hh * NI4 + i);
-        if (k4 < nq) {
-#pragma unroll
-          for (int m = 0; m < MT; ++m) {
-            float4 t = g[i][m];
-            if (PRO == 2) {
-              const float4 uu = u[i][m];
-              t.x = t.x / (1.0f + expf(-t.x)) * uu.x; t.y = t.y / (1.0f + expf(-t.y)) * uu.y;
-              t.z = t.z / (1.0f + expf(-t.z)) * uu.z; t.w = t.w / (1.0f + expf(-t.w)) * uu.w;
-            } else if (PRO == 1) {
-              if (defer_rs) {
-                ssq[m] = __builtin_fmaf(t.x, t.x, ssq[m]); ssq[m] = __builtin_fmaf(t.y, t.y, ssq[m]);
-                ssq[m] = __builtin_fmaf(t.z, t.z, ssq[m]); ssq[m] = __builtin_fmaf(t.w, t.w, ssq[m]);
-                t.x *= nw4[i].x; t.y *= nw4[i].y; t.z *= nw4[i].z; t.w *= nw4[i].w;
-              } else {
-                const float r = rs[m];
-                t.x = t.x * r * nw4[i].x; t.y = t.y * r * nw4[i].y; t.z = t.z * r * nw4[i].z; t.w = t.w * r * nw4[i].w;
-              }
-            }
-            if (m >= M) t = make_float4(0.f, 0.f, 0.f, 0.f);
-            g[i][m] = t;
-          }
-#pragma unroll
-          for (int q = 0; q < NQ; ++q) {
-            float* d = xs + ((long long)q * KCH + 4 * k4) * 4;
-            *(float4*)(d) = make_float4(g[i][4 * q].x, g[i][4 * q + 1].x, g[i][4 * q + 2].x, g[i][4 * q + 3].x);
-            *(float4*)(d + 4) = make_float4(g[i][4 * q].y, g[i][4 * q + 1].y, g[i][4 * q + 2].y, g[i][4 * q + 3].y);
-            *(float4*)(d + 8) = make_float4(g[i][4 * q].z, g[i][4 * q + 1].z, g[i][4 * q + 2].z, g[i][4 * q + 3].z);
-            *(float4*)(d + 12) = make_float4(g[i][4 * q].w, g[i][4 * q + 1].w, g[i][4 * q + 2].w, g[i][4 * q + 3].w);
-          }
-        }
-      }
-    }
-    __syncthreads();
-    const int nL = kn / KSUB;  // wave loads in this chunk; wave w takes L = w, w + 4, ...
-    auto fma_row = [&](const uint4& wq, int kl, float live) __attribute__((always_inline)) {
-      if (a.dbg & 2) { acc[0][0].x += __uint_as_float(wq.x ^ wq.y ^ wq.z ^ wq.w) * live; return; }
-      sk2f xv[MP];
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) {
-        const float4 t = *(const float4*)(xs + ((long long)q * KCH + kl) * 4);
-        xv[2 * q] = sk2f{t.x, t.y};
-        xv[2 * q + 1] = sk2f{t.z, t.w};
-      }
-      const unsigned wd[4] = {wq.x, wq.y, wq.z, wq.w};
-#pragma unroll
-      for (int c2 = 0; c2 < 4; ++c2) {
-        const float w0 = __uint_as_float(wd[c2] << 16) * live, w1 = __uint_as_float(wd[c2] & 0xffff0000u) * live;
-#pragma unroll
-        for (int mp = 0; mp < MP; ++mp) {
-          acc[2 * c2][mp] = __builtin_elementwise_fma(xv[mp], sk2f{w0, w0}, acc[2 * c2][mp]);
-          acc[2 * c2 + 1][mp] = __builtin_elementwise_fma(xv[mp], sk2f{w1, w1}, acc[2 * c2 + 1][mp]);
-        }
-      }
-    };
-    // The weight stream of this wave is a RING of NPRE loads in flight (round 3): slot i holds wave load L0 + 4 i; it is refilled with load
-    // L0 + 4 (i + NPRE) right before its value is used, so NPRE x 1 KiB per wave (64 KiB per CU at NPRE = 16) stay outstanding for the whole
-    // chunk -- vmcnt retires in order, hipcc waits for exactly the oldest.  The first chunk's ring was requested before the prologue (wpre).
-    if (kc != k_lo) {
-#pragma unroll
-      for (int i = 0; i < NPRE; ++i) {
-        const int L = wave + 4 * i;
-        wpre[i] = ld_w_nt(wblk + (long long)(kc + (L < nL ? L : wave % nL) * KSUB + ksub) * OCT, a.dbg);
-      }
-    }
-    int L0 = wave;
-    for (; L0 + 4 * NPRE < nL; L0 += 4 * NPRE) {  // every slot of this round has a successor (clamped in the last round of a ragged count)
-#pragma unroll
-      for (int i = 0; i < NPRE; ++i) {
-        const int L = L0 + 4 * i, Ln = L + 4 * NPRE;
-        const uint4 wq = wpre[i];
-        wpre[i] = ld_w_nt(wblk + (long long)(kc + (Ln < nL ? Ln : L) * KSUB + ksub) * OCT, a.dbg);
-        fma_row(wq, L * KSUB + ksub, 1.0f);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NPRE; ++i) {  // the last ring-full: nothing left to request
-      const int L = L0 + 4 * i;
-      fma_row(wpre[i], (L < nL ? L : wave % nL) * KSUB + ksub, L < nL ? 1.0f : 0.0f);
-    }
-  }
-  if (a.dbg & 4) {  // (timing only)
-    if (acc[0][0].x == 123.456f) a.out[tid] = acc[1][1].y;
-    return;
-  }
-  // deferred RMSNorm scale: the waves' sums of squares -> LDS (visible behind the barriers below), applied to the finished dot products
-  const bool defer_rs_out = PRO == 1 && K <= KCH;
-  float* rsp = rs + 16;  // [4 waves][16]
-  if (defer_rs_out) {
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-      float t = ssq[m];
-      for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-      if (lane == 0) rsp[wave * 16 + m] = t;
-    }
-  }
-  // ---- reduction over the lanes that share columns (k-sub) and the 4 waves, 8 rows per pass; output o = mloc * CB + column
-#pragma unroll
-  for (int mh = 0; mh < MT / 8; ++mh) {
-    __syncthreads();  // the chunk (or the previous pass) is no longer read
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float* d = red + ((long long)(wave * KSUB + ksub)) * OUT + oct * 8 + c;
-        d[(2 * i) * CB] = acc[c][4 * mh + i].x;
-        d[(2 * i + 1) * CB] = acc[c][4 * mh + i].y;
-      }
-    __syncthreads();
-    for (int pr = tid; pr < 4 * OUT; pr += 256) {  // (wave q, output o): the q-th wave's KSUB lanes in k-sub order
-      const int q = pr / OUT, o = pr - q * OUT;
-      const float* sp = red + (long long)q * KSUB * OUT + o;
-      float t = 0.f;
-#pragma unroll 8
-      for (int ks = 0; ks < KSUB; ++ks) t += sp[(long long)ks * OUT];
-      red2[pr] = t;
-    }
-    __syncthreads();
-    for (int o = tid; o < OUT; o += 256) {
-      const int mloc = o / CB, col = o - mloc * CB;
-      const int m = 8 * mh + mloc, n = nb * CB + col;
-      if (m < M && n < a.N) {
-        float t = ((red2[o] + red2[OUT + o]) + red2[2 * OUT + o]) + red2[3 * OUT + o];  // wave order
-        if (defer_rs_out) t *= 1.0f / sqrtf((((rsp[m] + rsp[16 + m]) + rsp[32 + m]) + rsp[48 + m]) / (float)K + a.eps);
-        if (EPI == 1) t += a.res[(long long)m * a.rrs + n];
-        if (EPI == 2) a.out[(long long)blockIdx.y * a.pss + (long long)m * a.ors + n] = t;  // K slice blockIdx.y of a split-K launch
-        else a.out[(long long)m * a.ors + n] = t;
-      }
-    }
-  }
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------------------------------
-// gemv8_kernel (round 3): the same product for M <= 8 rows and a single K chunk (K per slice <= 2048, a multiple of 128) in COMPACT code.
-// What the phase ablation of fused_gemv_kernel showed (KK_CSM_DBG): with the input staging, the FMAs, the reduction AND the
-// weight loads all switched off a frame still took 6.1 of 9.6 ms -- ~6 us per launch of an empty kernel -- and the time followed the
-// amount of straight-line CODE on the executed path, not the work: the kernels are 16-38 KB of fully unrolled instructions that run
-// once per launch, i.e. a launch is bound by instruction fetch from a cold instruction cache.  This kernel keeps the arithmetic and its
-// order (a row's bits are those of fused_gemv_kernel up to where the RMSNorm scale is applied) and shrinks the code:
-//   * staging: thread (row = tid / 32, lane32) takes the k quads lane32, lane32 + 32, ... of ONE row (8 float4 in flight per pass) instead of
-//     one column of every row; sums of squares stay per row half-wave (5 shuffle steps once, not 6 per row); fast exp / reciprocal in SwiGLU;
-//   * weight stream: ring of 8 loads per wave, a ROLLED loop over rounds of 8 (use + refill), then one use-only round;
-//   * the RMSNorm scale multiplies the finished dot products (no reduction + barriers ahead of the weight stream).
-template <int OCT, int PRO, int EPI>
-__global__ __launch_bounds__(256) void gemv8_kernel(FGArgs a) {
-  constexpr int CB = 8 * OCT, KSUB = 64 / OCT, OUT = CB * 8, KCH = 2048, RING = 8;
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* xs = sm;                     // [8 rows][KCH] row-major: staged by conflict-free 16-byte stores, read as 8 broadcast words per k
-  float* red = sm;                    // [4 waves][KSUB][OUT] (aliases xs after the main loop)
-  float* red2 = sm + 4 * KSUB * OUT;  // [4][OUT]
-  float* rsq = red2 + 4 * OUT;        // [8] sums of squares of the input rows (PRO 1)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int oct = lane % OCT, ksub = lane / OCT;
-  const int nb = blockIdx.x, K = a.K, M = a.M;
-  const int Kper = K / gridDim.y, k_lo = blockIdx.y * Kper;
-  const int nL = Kper / KSUB;  // wave loads of this workgroup; wave w takes L = w, w + 4, ...
-  const uint4* wblk = (const uint4*)(a.w + (long long)nb * K * CB) + oct + (long long)k_lo * OCT;  // row k of the slice at + k * OCT uint4
-  // ---- the ring's first loads go out before anything else
-  uint4 ring[RING];
-#pragma unroll
-  for (int i = 0; i < RING; ++i) {
-    const int L = wave + 4 * i;
-    ring[i] = ld_w_nt(wblk + (long long)((L < nL ? L : wave % nL) * KSUB + ksub) * OCT, a.dbg);
-  }
-  // ---- stage the input rows
-  {
-    const int m = tid >> 5, l32 = tid & 31, mm = m < M ? m : 0;
-    const float* row;
-    if (PRO == 3) {  // an item's last row comes from the audio embedding table (sesame.py:373-392), its other rows from x
-      const int item = mm / a.rows, r = mm - item * a.rows;
-      row = r == a.rows - 1 ? a.emb + (long long)(clamp_id(a.codes[(long long)item * a.cstride], a.V) + a.cb * a.V) * K : a.x + (long long)item * a.xrs;
-    } else {
-      row = a.x + (long long)mm * a.xrs;
-    }
-    float ssq = 0.f;
-    float* dst = xs + (long long)m * KCH;
-    const int nq = Kper >> 2;  // k quads of the slice: a multiple of 32 (launcher)
-    for (int j0 = 0; j0 < nq; j0 += 32 * 8) {  // 8 quads per thread in flight (K = 1024: one pass)
-      float4 g[8], u[PRO == 2 ? 8 : 1], nw[PRO == 1 ? 8 : 1];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int q = j0 + l32 + 32 * j, qc = q < nq ? q : l32;
-        g[j] = *(const float4*)(row + k_lo + 4 * qc);
-        if (PRO == 2) u[j] = *(const float4*)(row + K + k_lo + 4 * qc);
-        if (PRO == 1) nw[j] = *(const float4*)(a.nw + k_lo + 4 * qc);
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int q = j0 + l32 + 32 * j;
-        float4 t = g[j];
-        if (PRO == 2) {  // silu(gate) * up
-          t.x = t.x * __builtin_amdgcn_rcpf(1.0f + __expf(-t.x)) * u[j].x; t.y = t.y * __builtin_amdgcn_rcpf(1.0f + __expf(-t.y)) * u[j].y;
-          t.z = t.z * __builtin_amdgcn_rcpf(1.0f + __expf(-t.z)) * u[j].z; t.w = t.w * __builtin_amdgcn_rcpf(1.0f + __expf(-t.w)) * u[j].w;
-        } else if (PRO == 1) {
-          const float live = q < nq ? 1.0f : 0.0f;  // (a clamped duplicate of a ragged pass does not count)
-          ssq = __builtin_fmaf(t.x * live, t.x, ssq); ssq = __builtin_fmaf(t.y * live, t.y, ssq);
-          ssq = __builtin_fmaf(t.z * live, t.z, ssq); ssq = __builtin_fmaf(t.w * live, t.w, ssq);
-          t.x *= nw[j].x; t.y *= nw[j].y; t.z *= nw[j].z; t.w *= nw[j].w;
-        }
-        if (m >= M) t = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (q < nq) *(float4*)(dst + 4 * q) = t;
-      }
-    }
-    if (PRO == 1) {
-      ssq = q32_sum(ssq);
-      if (l32 == 0) rsq[m] = ssq;  // (its own LDS words: visible behind the barriers below)
-    }
-  }
-  sk2f acc[8][4];
-#pragma unroll
-  for (int c = 0; c < 8; ++c)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acc[c][i] = sk2f{0.f, 0.f};
-  __syncthreads();
-  auto fma_row = [&](const uint4& wq, int kl, float live) __attribute__((always_inline)) {
-    const float* xp = xs + kl;
-    const sk2f xv[4] = {sk2f{xp[0], xp[KCH]}, sk2f{xp[2 * KCH], xp[3 * KCH]}, sk2f{xp[4 * KCH], xp[5 * KCH]}, sk2f{xp[6 * KCH], xp[7 * KCH]}};
-    const unsigned wd[4] = {wq.x, wq.y, wq.z, wq.w};
-#pragma unroll
-    for (int c2 = 0; c2 < 4; ++c2) {
-      const float w0 = __uint_as_float(wd[c2] << 16) * live, w1 = __uint_as_float(wd[c2] & 0xffff0000u) * live;
-#pragma unroll
-      for (int mp = 0; mp < 4; ++mp) {
-        acc[2 * c2][mp] = __builtin_elementwise_fma(xv[mp], sk2f{w0, w0}, acc[2 * c2][mp]);
-        acc[2 * c2 + 1][mp] = __builtin_elementwise_fma(xv[mp], sk2f{w1, w1}, acc[2 * c2 + 1][mp]);
-      }
-    }
-  };
-  int L0 = wave;
-#pragma unroll 1
-  for (; L0 + 4 * RING < nL; L0 += 4 * RING) {  // every slot of this round has a successor (clamped in the last round of a ragged count)
-#pragma unroll
-    for (int i = 0; i < RING; ++i) {
-      const int L = L0 + 4 * i, Ln = L + 4 * RING;
-      const uint4 wq = ring[i];
-      ring[i] = ld_w_nt(wblk + (long long)((Ln < nL ? Ln : L) * KSUB + ksub) * OCT, a.dbg);
-      fma_row(wq, L * KSUB + ksub, 1.0f);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < RING; ++i) {  // the last ring-full: nothing left to request
-    const int L = L0 + 4 * i;
-    fma_row(ring[i], (L < nL ? L : wave % nL) * KSUB + ksub, L < nL ? 1.0f : 0.0f);
-  }
-  // ---- reduction over the lanes that share columns (k-sub) and the 4 waves; output o = m * CB + column
-  __syncthreads();  // xs is no longer read
-#pragma unroll
-  for (int c = 0; c < 8; ++c)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float* d = red + ((long long)(wave * KSUB + ksub)) * OUT + oct * 8 + c;
-      d[(2 * i) * CB] = acc[c][i].x;
-      d[(2 * i + 1) * CB] = acc[c][i].y;
-    }
-  __syncthreads();
-  for (int pr = tid; pr < 4 * OUT; pr += 256) {  // (wave q, output o): the q-th wave's KSUB lanes in k-sub order
-    const int q = pr / OUT, o = pr - q * OUT;
-    const float* sp = red + (long long)q * KSUB * OUT + o;
-    float t = 0.f;
-#pragma unroll 8
-    for (int ks = 0; ks < KSUB; ++ks) t += sp[(long long)ks * OUT];
-    red2[pr] = t;
-  }
-  __syncthreads();
-  for (int o = tid; o < OUT; o += 256) {
-    const int m = o / CB, col = o - m * CB, n = nb * CB + col;
-    if (m < M && n < a.N) {
-      float t = ((red2[o] + red2[OUT + o]) + red2[2 * OUT + o]) + red2[3 * OUT + o];  // wave order
-      if (PRO == 1) t *= 1.0f / sqrtf(rsq[m] / (float)K + a.eps);
-      if (EPI == 1) t += a.res[(long long)m * a.rrs + n];
-      if (EPI == 2) a.out[(long long)blockIdx.y * a.pss + (long long)m * a.ors + n] = t;  // K slice blockIdx.y of a split-K launch
-      else a.out[(long long)m * a.ors + n] = t;
-    }
-  }
-}
-template <int OCT>
-static size_t g8_lds_bytes() {
-  constexpr size_t xsb = (size_t)65536, redb = (size_t)4 * (64 / OCT) * (8 * OCT * 8) * 4;
-  return (xsb > redb ? xsb : redb) + (size_t)4 * (8 * OCT * 8) * 4 + 64;
-}
-
-template <int MT, int OCT>
-static size_t fg_lds_bytes() {
-  constexpr size_t xsb = (size_t)65536, redb = (size_t)4 * (64 / OCT) * (8 * OCT * 8) * 4;
-  return (xsb > redb ? xsb : redb) + (size_t)4 * (8 * OCT * 8) * 4 + 64 + 256;  // + rs [16] + the waves' sums of squares [4][16]
-}
-
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // gemmp_kernel (round 3): the PROMPT block's Linear layers (M = B x S rows, hundreds to thousands) on the matrix cores, from the same bf16
@@ -1423,8 +986,10 @@ struct GPArgs {
   const float* res; long long rrs;
   float* out; long long ors;
 };
-template <int RT, int KC>  // RT row tiles of 16 per workgroup (4: one per wave, 8: two per wave); KC 32-row K chunks per barrier (1 or 2)
 __global__ __launch_bounds__(256) void gemmp_kernel(GPArgs a) {
+  // RT row tiles of 16 per workgroup (one per wave), KC 32-row K chunks per barrier.  Measured, prefill of 190 positions, RT x KC: 30.7 / 31.1 /
+  // 33.9 / 36.3 ms for 4 x 2 / 4 x 1 / 8 x 2 / 8 x 1 -- the split arithmetic redone per column tile, not the tile shape, is what is left
+  constexpr int RT = 4, KC = 2;
   constexpr int NIT = RT / 4;      // row tiles per wave
   constexpr int NLD = RT / 2;      // float4 loads per thread and chunk: (16 RT rows) x (8 quads of 4 k) / 256 threads
   constexpr int KOP = 384, FRAGB = 4 * KOP;  // k-octet pitch in bytes (256 of data: the two k octets a wave's 8-byte writes touch share no bank), fragment bytes
@@ -1536,29 +1101,15 @@ __global__ __launch_bounds__(256) void gemmp_kernel(GPArgs a) {
       }
     }
 }
-// one launch of the prompt GEMM: KK_CSM_GEMM = "RT,KC" picks the tile for A/B runs
+// one launch of the prompt GEMM (64-row tiles)
 int launch_gemmp(const GPArgs& g, hipStream_t st) {
-  static int rt = 0, kc = 0;
-  if (!rt) {
-    const char* e = getenv("KK_CSM_GEMM");
-    rt = 4; kc = 2;  // (measured level: prefill of 190 positions 30.7 / 31.1 / 33.9 / 36.3 ms for 4,2 / 4,1 / 8,2 / 8,1 -- the split arithmetic redone per column tile, not the tile shape, is what is left)
-    if (e && e[0] && e[1] == ',' && e[2]) { rt = e[0] == '4' ? 4 : 8; kc = e[2] == '1' ? 1 : 2; }
+  const size_t lds = (size_t)2 * 2 * 4 * 3 * 1536;  // [2 buffers][KC chunks][RT row tiles][3 terms][1536-byte fragments]
+  static KKDevOnce attr;
+  if (attr.first()) {
+    (void)hipFuncSetAttribute((const void*)gemmp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr.done();
   }
-#define GP_GO(RT, KC)                                                                                                                   \
-  do {                                                                                                                                   \
-    const size_t lds = (size_t)2 * KC * RT * 3 * 1536;                                                                                   \
-    static KKDevOnce attr;                                                                                                               \
-    if (attr.first()) {                                                                                                                  \
-      (void)hipFuncSetAttribute((const void*)gemmp_kernel<RT, KC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                \
-      attr.done();                                                                                                                       \
-    }                                                                                                                                    \
-    hipLaunchKernelGGL((gemmp_kernel<RT, KC>), dim3((g.N + 63) / 64, (g.M + 16 * RT - 1) / (16 * RT)), dim3(256), lds, st, g);           \
-  } while (0)
-  if (rt == 4 && kc == 1) GP_GO(4, 1);
-  else if (rt == 4) GP_GO(4, 2);
-  else if (kc == 1) GP_GO(8, 1);
-  else GP_GO(8, 2);
-#undef GP_GO
+  hipLaunchKernelGGL(gemmp_kernel, dim3((g.N + 63) / 64, (g.M + 63) / 64), dim3(256), lds, st, g);
   KK_CHECK_LAUNCH();
   return 0;
 }
@@ -1622,8 +1173,7 @@ struct Packer {
     }
     if (m->wdt == KK_BF16) {
       // bf16 weight mode: the matrix IS its bf16 rounding everywhere (the fp32 pack the multi-token prompt block reads holds the rounded
-      // values too, so a prompt block and single-token steps multiply by identical weights); lossless for a bf16 checkpoint.  The bf16
-      // copy is laid out for the fused GEMV: [Cout / CB][Cin][CB], CB = 8 * oct columns per workgroup (fused_gemv_kernel).
+      // values too, so a prompt block and single-token steps multiply by identical weights); lossless for a bf16 checkpoint.
       float* dst = &m->pack[l.off];
       for (size_t e = 0; e < (size_t)I * l.ldw; ++e) {
         uint32_t u;
@@ -1632,28 +1182,14 @@ struct Packer {
         u &= 0xFFFF0000u;
         memcpy(&dst[e], &u, 4);
       }
-      // the round-2 / round-3a column-block pack (fused_gemv_kernel, gemv8_kernel) is built only for the A/B runs that ask for those kernels
-      if (I % 64 == 0 && (getenv("KK_CSM_NO_MFMA") || getenv("KK_CSM_OLD") || I % 32 != 0)) {
-        l.oct = (O >= 8192 || I >= 4096) ? 8 : 1;  // wide (gate|up) and deep (down) matrices: 64 columns per workgroup
-        const int CB = 8 * l.oct, nblk = (O + CB - 1) / CB;
-        l.boff = m->packb.size();
-        m->packb.resize(l.boff + (size_t)nblk * I * CB, 0);
-        uint16_t* db = &m->packb[l.boff];
-        for (int i = 0; i < I; ++i)
-          for (int o = 0; o < O; ++o) {
-            uint32_t u;
-            memcpy(&u, &dst[(size_t)i * l.ldw + o], 4);
-            db[((size_t)(o / CB) * I + i) * CB + o % CB] = (uint16_t)(u >> 16);
-          }
-      }
-      if (I % 32 == 0 && !getenv("KK_CSM_NO_MFMA")) {
+      if (I % 32 == 0) {
         // fragment pack of gemvm_kernel.  Split-K for the deep projections (K >= 4096 in slices of 1024 rows), then the widest column
-        // block (16 * nsub) that still gives ~200 workgroups; both depend on the matrix only, never on the batch.
+        // block (16 * nsub) that still gives ~200 workgroups; both depend on the matrix only, never on the batch.  (Measured: 2 instead
+        // of 4 sub-blocks for gate|up, i.e. 32-column blocks and more workgroups, cost +0.09 ms per frame.)
         l.ks = (I >= 4096 && I % 1024 == 0) ? (I / 1024 > 16 ? 16 : I / 1024) : 1;
         while (l.ks > 1 && (I % l.ks != 0 || (I / l.ks) % 32 != 0)) --l.ks;
         const int nb16 = (O + 15) / 16;
         l.nsub = nb16 * l.ks / 4 >= 192 ? 4 : (nb16 * l.ks / 2 >= 192 ? 2 : 1);
-        if (const char* e = getenv("KK_CSM_NSUB_MAX")) { const int mx = atoi(e); if (mx >= 1 && l.nsub > mx) l.nsub = mx; }  // (A/B: narrower column blocks = more workgroups; measured: 2 instead of 4 sub-blocks for gate|up costs +0.09 ms per frame)
         const int CBm = 16 * l.nsub, nblk = (O + CBm - 1) / CBm, nchunk = I / 32;
         l.moff = m->packb.size();
         m->packb.resize(l.moff + (size_t)nblk * I * CBm, 0);
@@ -1722,7 +1258,6 @@ void pack_stack(Packer& P, const std::string& name, Stack& st, int max_pos) {
 
 void resolve(kk_csm* m, Lin& l) {
   l.w = m->dev + l.off;
-  l.wb = (m->devb && l.oct) ? m->devb + l.boff : nullptr;
   l.wm = (m->devb && l.nsub) ? m->devb + l.moff : nullptr;
 }
 void resolve(kk_csm* m, Vec& v) { v.p = v.n ? m->dev + v.off : nullptr; }
@@ -1748,14 +1283,10 @@ struct Run {
     return (float*)(base + off);
   }
   // out[b][row][:] = W x[b][row][:] (+ res); x rows: `rows` per item at pitch `xbs` elements between items
-  // `gated`: x is [.. rows][2 * Cin] = gate | up and the input of the product is silu(gate) * up (skinny bf16 path only; callers check
-  // can_gate() first and run the stand-alone swiglu kernel otherwise).  `nw` / `xn`: RMSNorm of the result rows, launched right behind.
-  bool can_gate(const Lin& w, int rows) const { (void)w; (void)rows; return false; }  // (the gated form lives in the fused GEMV now)
-  int lin(const Lin& w, const float* x, long long xbs, int rows, float* out, long long obs, const float* res, bool gated = false,
-          const float* nw = nullptr, float* xn = nullptr, float eps = 0.f) {
+  // `nw` / `xn`: RMSNorm of the result rows, launched right behind.
+  int lin(const Lin& w, const float* x, long long xbs, int rows, float* out, long long obs, const float* res, const float* nw = nullptr,
+          float* xn = nullptr, float eps = 0.f) {
     if (dry) return 0;
-    if (gated && !(can_gate(w, rows) && xbs == (long long)rows * 2 * w.Cin && obs == (long long)rows * w.Cout)) return kk_fail("kk_csm: internal: gated input");
-    if (gated) xbs = (long long)rows * w.Cin;
     KKConvArgs a;
     memset(&a, 0, sizeof a);
     a.x = x; a.xbs = xbs; a.ldx = w.Cin; a.w = w.w; a.ldw = w.ldw;
@@ -1778,7 +1309,7 @@ struct Run {
       if ((size_t)KS * SK_MAXM * w.Cout <= skinny_floats) {
         for (int m0 = 0; m0 < Mtot; m0 += SK_MAXM) {
           const int M = Mtot - m0 < SK_MAXM ? Mtot - m0 : SK_MAXM;
-          const float* xin = x + (size_t)m0 * (gated ? 2 : 1) * w.Cin;
+          const float* xin = x + (size_t)m0 * w.Cin;
           const dim3 g(nblk, KS), t(256);
 #define SK_GO(MT) hipLaunchKernelGGL((skinny_gemm_kernel<MT, false, false>), g, t, 0, st, xin, M, w.Cin, (const void*)w.w, w.ldw, w.Cout, kchunk, skinny_scratch)
           // MT depends on the rows per launch only through "fits in 8": a row's arithmetic is the same in both instantiations
@@ -1797,8 +1328,8 @@ struct Run {
         return 0;
       }
     }
-    if (xbs == (long long)rows * w.Cin && obs == (long long)rows * w.Cout && w.wm && w.nsub && !gated && rows > 2 && !(ab_switches() & 1)) {
-      // the prompt block in bf16 weight mode: matrix cores (gemmp_kernel); KK_CSM_PROMPT_F32=1 keeps the round-2 generic fp32 kernel (A/B).
+    if (xbs == (long long)rows * w.Cin && obs == (long long)rows * w.Cout && w.wm && w.nsub && rows > 2) {
+      // the prompt block in bf16 weight mode: matrix cores (gemmp_kernel); without a fragment pack, the generic fp32 kernel below.
       // The choice depends on the rows PER ITEM only, never on B: a stream's bits do not depend on its batch.
       GPArgs g;
       memset(&g, 0, sizeof g);
@@ -1828,20 +1359,9 @@ struct Run {
   }
 };
 
-// fused GEMV launcher: `a` carries everything but the weights; rows in chunks of 16 (PRO 3: `rows` rows per item, chunk = whole items)
-// split-K slices of a deep projection (K >= 4096 on 64-column blocks): enough workgroups to fill the chip; depends on the matrix only
-int gemv_slices(const Lin& w) {
-  if (w.nsub) return w.ks;
-  if (w.oct != 8 || w.Cin < 4096) return 1;
-  const int nblk = (w.Cout + 63) / 64;
-  int ks = 256 / nblk;
-  if (ks > 16) ks = 16;
-  while (ks > 1 && (w.Cin % ks != 0 || (w.Cin / ks) % 32 != 0)) --ks;
-  return ks < 1 ? 1 : ks;
-}
 // the matrix-core GEMV: one launch for all rows (grid z = 8-row chunks); KS must be the pack's w.ks
 int launch_gemvm(const Lin& w, int pro, int epi, FGArgs a, int Mtot, hipStream_t st) {
-  a.w = w.wm; a.K = w.Cin; a.N = w.Cout; a.M = Mtot; a.dbg = w.cached; a.kper = w.Cin / w.ks;
+  a.w = w.wm; a.K = w.Cin; a.N = w.Cout; a.M = Mtot; a.kper = w.Cin / w.ks;
   a.ts = ts_slot(); a.ts_id = (w.Cout << 4) | (pro << 2) | epi;
   const int CB = 16 * w.nsub, nblk = (w.Cout + CB - 1) / CB, kper = w.Cin / w.ks;
   const size_t lds = gm_lds_bytes(w.nsub, kper);
@@ -1882,97 +1402,11 @@ int launch_gemvm(const Lin& w, int pro, int epi, FGArgs a, int Mtot, hipStream_t
   return 0;
 }
 
-int launch_gemv(const Lin& w, int pro, int epi, FGArgs a, int Mtot, hipStream_t st, int KS = 1) {
-  if (w.wm && w.nsub) {
-    if (KS != w.ks || (epi == 2) != (w.ks > 1)) return kk_fail("kk_csm: internal: split-K form");
-    return launch_gemvm(w, pro, epi, a, Mtot, st);
-  }
-  if (!w.wb || !w.oct) return kk_fail("kk_csm: internal: fused GEMV without a block pack");
-  a.w = w.wb; a.K = w.Cin; a.N = w.Cout;
-  {
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = getenv("KK_CSM_DBG"); dbg = e ? atoi(e) : 0; }
-    a.dbg = dbg;
-  }
-  const int CB = 8 * w.oct, nblk = (w.Cout + CB - 1) / CB;
-  if ((epi == 2) != (KS > 1 || epi == 2)) return kk_fail("kk_csm: internal: split-K form");
-  for (int m0 = 0; m0 < Mtot; m0 += 16) {
-    FGArgs g = a;
-    g.M = Mtot - m0 < 16 ? Mtot - m0 : 16;
-    if (pro == 3) {
-      const int item0 = m0 / a.rows;
-      g.x = a.x + (long long)item0 * a.xrs;
-      g.codes = a.codes + (long long)item0 * a.cstride;
-    } else {
-      g.x = a.x + (long long)m0 * a.xrs;
-    }
-    if (a.res) g.res = a.res + (long long)m0 * a.rrs;
-    g.out = a.out + (long long)m0 * a.ors;
-#define FG_GO1(MT, OCT, PRO, EPI, NPRE)                                                                                                 \
-  do {                                                                                                                                   \
-    static KKDevOnce attr;                                                                                                               \
-    const size_t lds_ = (fg_lds_bytes<MT, OCT>());                                                                                       \
-    if (attr.first()) {                                                                                                                  \
-      (void)hipFuncSetAttribute((const void*)fused_gemv_kernel<MT, OCT, PRO, EPI, NPRE>, hipFuncAttributeMaxDynamicSharedMemorySize,    \
-                                (int)lds_);                                                                                              \
-      attr.done();                                                                                                                       \
-    }                                                                                                                                    \
-    hipLaunchKernelGGL((fused_gemv_kernel<MT, OCT, PRO, EPI, NPRE>), dim3(nblk, KS), dim3(256), lds_, st, g);                               \
-  } while (0)
-#define FG_GO(MT, OCT, PRO, EPI) FG_GO1(MT, OCT, PRO, EPI, (OCT == 8 && MT == 8 ? 16 : 8))  /* (16 rows x 16 in flight would spill) */
-#define FG_PE(MT, OCT)                                                      \
-  do {                                                                       \
-    if (pro == 1 && epi == 0) FG_GO(MT, OCT, 1, 0);                          \
-    else if (pro == 0 && epi == 1) FG_GO(MT, OCT, 0, 1);                     \
-    else if (pro == 2 && epi == 1) FG_GO(MT, OCT, 2, 1);                     \
-    else if (pro == 2 && epi == 2) FG_GO(MT, OCT, 2, 2);                     \
-    else if (pro == 3 && epi == 0) FG_GO(MT, OCT, 3, 0);                     \
-    else if (pro == 0 && epi == 0) FG_GO(MT, OCT, 0, 0);                     \
-    else return kk_fail("kk_csm: internal: fused GEMV form");                \
-  } while (0)
-    // M <= 8 rows and one K chunk: the compact kernel (gemv8_kernel); KK_CSM_OLD=1 keeps the round-2 kernel for A/B timing
-    static int old_kernel = -1, g8_mask = 0xFF;
-    if (old_kernel < 0) {
-      old_kernel = getenv("KK_CSM_OLD") ? 1 : 0;
-      if (getenv("KK_CSM_G8_MASK")) g8_mask = atoi(getenv("KK_CSM_G8_MASK"));  // (debugging: bit p = prologue p on the compact kernel; bit 4 + oct/8)
-    }
-    const int kper = a.K / KS;
-    if (!old_kernel && ((g8_mask >> pro) & 1) && ((g8_mask >> (4 + (w.oct == 8 ? 1 : 0))) & 1) && g.M <= 8 && kper <= 2048 && kper % 128 == 0) {
-#define G8_GO(OCT, PRO, EPI)                                                                                                             \
-  do {                                                                                                                                   \
-    static KKDevOnce attr;                                                                                                               \
-    const size_t lds_ = (g8_lds_bytes<OCT>());                                                                                           \
-    if (attr.first()) {                                                                                                                  \
-      (void)hipFuncSetAttribute((const void*)gemv8_kernel<OCT, PRO, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_);        \
-      attr.done();                                                                                                                       \
-    }                                                                                                                                    \
-    hipLaunchKernelGGL((gemv8_kernel<OCT, PRO, EPI>), dim3(nblk, KS), dim3(256), lds_, st, g);                                           \
-  } while (0)
-#define G8_PE(OCT)                                                          \
-  do {                                                                       \
-    if (pro == 1 && epi == 0) G8_GO(OCT, 1, 0);                              \
-    else if (pro == 0 && epi == 1) G8_GO(OCT, 0, 1);                         \
-    else if (pro == 2 && epi == 1) G8_GO(OCT, 2, 1);                         \
-    else if (pro == 2 && epi == 2) G8_GO(OCT, 2, 2);                         \
-    else if (pro == 3 && epi == 0) G8_GO(OCT, 3, 0);                         \
-    else if (pro == 0 && epi == 0) G8_GO(OCT, 0, 0);                         \
-    else return kk_fail("kk_csm: internal: fused GEMV form");                \
-  } while (0)
-      if (w.oct == 8) G8_PE(8); else G8_PE(1);
-#undef G8_PE
-#undef G8_GO
-      KK_CHECK_LAUNCH();
-      continue;
-    }
-    // MT depends on the rows per launch only through "fits in 8": a row's arithmetic is the same in both instantiations
-    if (g.M <= 8) { if (w.oct == 8) FG_PE(8, 8); else FG_PE(8, 1); }
-    else { if (w.oct == 8) FG_PE(16, 8); else FG_PE(16, 1); }
-#undef FG_PE
-#undef FG_GO
-#undef FG_GO1
-    KK_CHECK_LAUNCH();
-  }
-  return 0;
+// the single-token GEMV of a bf16 matrix: `a` carries everything but the weights; KS = w.ks split-K slices (epi 2) or one (any other epi)
+int launch_gemv(const Lin& w, int pro, int epi, FGArgs a, int Mtot, hipStream_t st) {
+  if (!w.wm || !w.nsub) return kk_fail("kk_csm: internal: GEMV without a fragment pack");
+  if ((epi == 2) != (w.ks > 1)) return kk_fail("kk_csm: internal: split-K form");
+  return launch_gemvm(w, pro, epi, a, Mtot, st);
 }
 
 #define CS_TRY(x)          \
@@ -2017,22 +1451,18 @@ int stack_forward(Run& r, Stack& st, float* h, int S, int offset, float* out) {
       }
     }
     // h += o(att); x = RMSNorm(h) (post_attention_layernorm)
-    CS_TRY(r.lin(L.o, att, (long long)S * H * hd, S, h, (long long)S * D, h, false, L.n2.p, x, a.rms_eps));
+    CS_TRY(r.lin(L.o, att, (long long)S * H * hd, S, h, (long long)S * D, h, L.n2.p, x, a.rms_eps));
     CS_TRY(r.lin(L.gu, x, (long long)S * D, S, gu, (long long)S * 2 * I, nullptr));
     // h += down(silu(gate) * up); then the NEXT consumer's norm: the next layer's input_layernorm -> x, or the stack's final norm -> out
     const bool lastl = l + 1 == a.num_layers;
     const float* nw = lastl ? st.norm.p : st.layers[l + 1].n1.p;
     float* xn = lastl ? out : x;
-    if (r.can_gate(L.down, S)) {  // bf16 weight mode, single-token step: SwiGLU is applied while the down projection stages its input
-      CS_TRY(r.lin(L.down, gu, (long long)S * 2 * I, S, h, (long long)S * D, h, true, nw, xn, a.rms_eps));
-    } else {
-      if (!r.dry) {
-        const long long n = (long long)B * S * I;
-        hipLaunchKernelGGL(swiglu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r.st, gu, I, n, act);
-        KK_CHECK_LAUNCH();
-      }
-      CS_TRY(r.lin(L.down, act, (long long)S * I, S, h, (long long)S * D, h, false, nw, xn, a.rms_eps));
+    if (!r.dry) {
+      const long long n = (long long)B * S * I;
+      hipLaunchKernelGGL(swiglu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r.st, gu, I, n, act);
+      KK_CHECK_LAUNCH();
     }
+    CS_TRY(r.lin(L.down, act, (long long)S * I, S, h, (long long)S * D, h, nw, xn, a.rms_eps));
   }
   return 0;
 }
@@ -2043,7 +1473,7 @@ int stack_forward(Run& r, Stack& st, float* h, int S, int offset, float* out) {
 bool stack_can_step(const Stack& st) {
   for (const auto& L : st.layers)
     for (const Lin* w : {&L.qkv, &L.o, &L.gu, &L.down})
-      if (!(w->wm || w->wb)) return false;
+      if (!w->wm) return false;
   return !st.layers.empty();
 }
 // `gather` (optional): layer 0 reads its input rows from a table by code instead of from h, and writes them to h (FGArgs codes / cstride / cb / V / emb)
@@ -2067,9 +1497,8 @@ int stack_step(Run& r, Stack& st, float* h, int rows, int offset, const FGArgs* 
     memset(&g, 0, sizeof g);
     g.x = h; g.xrs = D; g.nw = L.n1.p; g.eps = a.rms_eps; g.out = qkv; g.ors = W;
     if (l == 0 && gather) { g.codes = gather->codes; g.cstride = gather->cstride; g.cb = gather->cb; g.V = gather->V; g.emb = gather->emb; g.gather_out = h; }
-    if (!(g_skip & 1)) CS_TRY(launch_gemv(L.qkv, 1, 0, g, M, r.st));
-    if (g_skip & 2) {
-    } else if (rows == 1 && st.max_pos <= 64 && H / KV <= 8 && !(ab_switches() & 2)) {
+    CS_TRY(launch_gemv(L.qkv, 1, 0, g, M, r.st));
+    if (rows == 1 && st.max_pos <= 64 && H / KV <= 8) {
       const size_t lds = attn_step_lds_bytes(st.max_pos, hd, H / KV);
       static KKDevOnce attr;
       if (attr.first()) {
@@ -2084,7 +1513,7 @@ int stack_step(Run& r, Stack& st, float* h, int rows, int offset, const FGArgs* 
         hipLaunchKernelGGL(attn_step_kernel<64>, dim3(KV, B), dim3(256), lds, r.st, qkv, H, KV, st.pos_dev, st.pos_dev ? 0 : offset, kc, vc, st.max_pos,
                            1.0f / sqrtf((float)hd), att, st.rope.p, st.pad_dev, ts_slot());
       KK_CHECK_LAUNCH();
-    } else if (rows == 1 && H / KV <= 8 && !(ab_switches() & 2)) {
+    } else if (rows == 1 && H / KV <= 8) {
       const size_t lds = attn_decode_lds_bytes(hd, H / KV);
       static KKDevOnce attr;
       if (attr.first()) {
@@ -2123,23 +1552,21 @@ int stack_step(Run& r, Stack& st, float* h, int rows, int offset, const FGArgs* 
     }
     memset(&g, 0, sizeof g);
     g.x = att; g.xrs = (long long)H * hd; g.res = h; g.rrs = D; g.out = h; g.ors = D;
-    if (!(g_skip & 4)) CS_TRY(launch_gemv(L.o, 0, 1, g, M, r.st));
+    CS_TRY(launch_gemv(L.o, 0, 1, g, M, r.st));
     memset(&g, 0, sizeof g);
     g.x = h; g.xrs = D; g.nw = L.n2.p; g.eps = a.rms_eps; g.out = gu; g.ors = 2 * I;
-    if (!(g_skip & 8)) CS_TRY(launch_gemv(L.gu, 1, 0, g, M, r.st));
+    CS_TRY(launch_gemv(L.gu, 1, 0, g, M, r.st));
     memset(&g, 0, sizeof g);
-    const int KS = gemv_slices(L.down);
+    const int KS = L.down.ks;
     if (KS > 1) {  // deep projection: K slices over workgroups, then one small combine (h += sum of the slices)
       g.x = gu; g.xrs = 2 * I; g.out = part; g.ors = D; g.pss = (long long)M * D;
-      if (!(g_skip & 16)) CS_TRY(launch_gemv(L.down, 2, 2, g, M, r.st, KS));
+      CS_TRY(launch_gemv(L.down, 2, 2, g, M, r.st));
       const long long n = (long long)M * D;
-      if (!(g_skip & 32)) {
-        hipLaunchKernelGGL(combine_slices_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r.st, part, KS, n, n, h, ts_slot());
-        KK_CHECK_LAUNCH();
-      }
+      hipLaunchKernelGGL(combine_slices_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r.st, part, KS, n, n, h, ts_slot());
+      KK_CHECK_LAUNCH();
     } else {
       g.x = gu; g.xrs = 2 * I; g.res = h; g.rrs = D; g.out = h; g.ors = D;
-      if (!(g_skip & 16)) CS_TRY(launch_gemv(L.down, 2, 1, g, M, r.st));
+      CS_TRY(launch_gemv(L.down, 2, 1, g, M, r.st));
     }
   }
   return 0;
@@ -2168,9 +1595,9 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, float temp, i
   }
   const size_t inner = r.used;
   // bf16 weight mode: single-token frames (and every depth-decoder step) run on the fused five-launch layers
-  const bool fast = m->wdt == KK_BF16 && stack_can_step(m->bb) && stack_can_step(m->dec) && (m->proj.wm || m->proj.wb) && (m->c0_head.wm || m->c0_head.wb);
+  const bool fast = m->wdt == KK_BF16 && stack_can_step(m->bb) && stack_can_step(m->dec) && m->proj.wm && m->c0_head.wm;
   bool heads_fast = fast;
-  for (const auto& l : m->audio_head) heads_fast = heads_fast && (l.wm || l.wb);
+  for (const auto& l : m->audio_head) heads_fast = heads_fast && l.wm;
   const float* last_h;   // the backbone's final-normed last position of every item
   long long last_rs;     // its item pitch
   if (fast && heads_fast && S == 1) {
@@ -2194,8 +1621,8 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, float temp, i
       FGArgs g;
       memset(&g, 0, sizeof g);
       g.x = last_h; g.xrs = last_rs; g.out = logits; g.ors = V;
-      if (!(g_skip & 64)) CS_TRY(launch_gemv(m->c0_head, 0, 0, g, B, r.st));
-      if (!(g_skip & 128)) CS_TRY(launch_sample(logits, V, temp, top_k, uniforms, ncb, codes, ncb, B, r.st));
+      CS_TRY(launch_gemv(m->c0_head, 0, 0, g, B, r.st));
+      CS_TRY(launch_sample(logits, V, temp, top_k, uniforms, ncb, codes, ncb, B, r.st));
     }
     int rows = 2, dpos = 0;
     for (int i = 1; i < ncb; ++i) {
@@ -2203,7 +1630,7 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, float temp, i
       // curr = [last_h, embed(0, c0)] for the first step, [embed(i-1, c_{i-1})] afterwards (sesame.py:373-392): gathered by the projection's prologue
       // later steps (one row per item): the projection of an embedding row is a row of the table built at finalize -- no launch; the decoder's first
       // kernel gathers it and materialises the residual stream
-      const bool tabled = rows == 1 && m->proj_table && m->dec.layers[0].qkv.wm && !(ab_switches() & 4);
+      const bool tabled = rows == 1 && m->proj_table && m->dec.layers[0].qkv.wm;
       FGArgs gat;
       memset(&gat, 0, sizeof gat);
       gat.codes = codes + (i - 1); gat.cstride = ncb; gat.cb = i - 1; gat.V = V; gat.emb = m->proj_table;
@@ -2212,7 +1639,7 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, float temp, i
         memset(&g, 0, sizeof g);
         g.x = last_h; g.xrs = last_rs; g.codes = codes + (i - 1); g.cstride = ncb; g.cb = i - 1; g.V = V; g.rows = rows; g.emb = m->audio_emb.p;
         g.out = pin; g.ors = Dd;
-        if (!(g_skip & 256)) CS_TRY(launch_gemv(m->proj, 3, 0, g, B * rows, r.st));
+        CS_TRY(launch_gemv(m->proj, 3, 0, g, B * rows, r.st));
       }
       CS_TRY(stack_step(r, m->dec, pin, rows, dpos, tabled ? &gat : nullptr));
       if (r.used > peak) peak = r.used;
@@ -2222,8 +1649,8 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, float temp, i
         FGArgs g;
         memset(&g, 0, sizeof g);
         g.x = pin + (size_t)(rows - 1) * Dd; g.xrs = (long long)rows * Dd; g.nw = m->dec.norm.p; g.eps = c.decoder.rms_eps; g.out = logits; g.ors = V;
-        if (!(g_skip & 64)) CS_TRY(launch_gemv(m->audio_head[i - 1], 1, 0, g, B, r.st));
-        if (!(g_skip & 128)) CS_TRY(launch_sample(logits, V, temp, top_k, uniforms ? uniforms + i : nullptr, ncb, codes + i, ncb, B, r.st));
+        CS_TRY(launch_gemv(m->audio_head[i - 1], 1, 0, g, B, r.st));
+        CS_TRY(launch_sample(logits, V, temp, top_k, uniforms ? uniforms + i : nullptr, ncb, codes + i, ncb, B, r.st));
       }
       rows = 1;
     }
@@ -2393,17 +1820,6 @@ extern "C" int kk_csm_finalize(kk_csm* m, void* stream) {
       for (int i = 0; i < ncb - 1; ++i) m->audio_head[i] = P.linear({}, {V}, Dd, ah->data() + (size_t)i * Dd * V);  // [Dd][V] used as x @ W
   }
   if (!P.err.empty()) return kk_fail(("kk_csm_finalize: " + P.err).c_str());
-  {  // KK_CSM_NT (A/B, measured equal within noise: 5.62 ms per frame each): "all" (default) nontemporal weight loads everywhere, "none" plain loads, "bb": the backbone
-    // streams and the depth decoder (222 MB re-read 31 times per frame, inside the reach of the 256-MB memory-side cache) is cacheable
-    const char* e = getenv("KK_CSM_NT");
-    const std::string mode = e ? e : "all";
-    const int dec_cached = mode != "all", bb_cached = mode == "none";
-    for (auto& L : m->dec.layers) L.qkv.cached = L.o.cached = L.gu.cached = L.down.cached = dec_cached;
-    for (auto& L : m->bb.layers) L.qkv.cached = L.o.cached = L.gu.cached = L.down.cached = bb_cached;
-    for (auto& l : m->audio_head) l.cached = dec_cached;
-    m->proj.cached = dec_cached;
-    m->c0_head.cached = bb_cached;
-  }
   if (hipMalloc((void**)&m->dev, m->pack.size() * sizeof(float)) != hipSuccess) return kk_fail("kk_csm_finalize: hipMalloc failed");
   if (hipMemcpyAsync(m->dev, m->pack.data(), m->pack.size() * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess)
     return kk_fail("kk_csm_finalize: upload failed");
@@ -2527,7 +1943,7 @@ extern "C" int kk_csm_generate_frame(kk_csm* m, void* stream, int B, int S, cons
     memcpy(&tbits, &temperature, 4);
     const std::vector<unsigned long long> key = {(unsigned long long)B, (unsigned long long)(uintptr_t)tokens, (unsigned long long)(uintptr_t)tokens_mask,
         (unsigned long long)tbits, (unsigned long long)top_k, (unsigned long long)(uintptr_t)uniforms, (unsigned long long)(uintptr_t)workspace,
-        (unsigned long long)workspace_bytes, (unsigned long long)(uintptr_t)codes_out, (unsigned long long)g_skip, (unsigned long long)(uintptr_t)g_ts};
+        (unsigned long long)workspace_bytes, (unsigned long long)(uintptr_t)codes_out, (unsigned long long)(uintptr_t)g_ts};
     kk_csm::GraphEntry* ge = nullptr;
     for (auto& g : m->graphs)
       if (g.key == key) ge = &g;
@@ -2577,11 +1993,6 @@ extern "C" int kk_csm_debug_timestamps(unsigned long long* buf, int capacity) {
   g_ts = buf;
   g_ts_cap = buf ? capacity : 0;
   g_ts_next = 0;
-  return 0;
-}
-
-extern "C" int kk_csm_debug_skip(int mask) {
-  g_skip = mask & 0xffff;
   return 0;
 }
 

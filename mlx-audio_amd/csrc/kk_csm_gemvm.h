@@ -55,7 +55,6 @@ struct FGArgs {
   const float* res; long long rrs;  // EPI 1
   float* out; long long ors;
   long long pss;                    // EPI 2: floats between the partial tiles of consecutive K slices
-  int dbg;                          // gemvm_kernel: bit 0 = plain instead of nontemporal weight loads (KK_CSM_NT); the round-2 kernels: KK_CSM_DBG phase switches
   float* gather_out;                // PRO 1 with `codes`: row m is emb[(codes[m * cstride] + cb * V)] (K floats, no x); column block 0 also writes the raw rows here (pitch K)
   unsigned long long* ts; int ts_id;  // kk_csm_debug_timestamps (null in production)
 };
@@ -63,7 +62,8 @@ struct FGArgs {
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // gemvm_kernel (round 3): the single-token product on the MATRIX CORES, with every weight byte of the workgroup requested up front.
-// What the per-kernel times of gemv8_kernel showed (profiles/r03_b_csm_bf16w_kernel_stats.csv): 15.5 us for gate|up (33.5 MB: 2.2 TB/s),
+// What the per-kernel times of gemv8_kernel, the vector-ALU GEMV this kernel replaced (since removed), showed
+// (profiles/r03_b_csm_bf16w_kernel_stats.csv): 15.5 us for gate|up (33.5 MB: 2.2 TB/s),
 // 8.7 us for q|k|v (3 MB), 7.3 us for o (2 MB), while a chain of EMPTY kernels costs 1.55 us per launch in graph replay
 // (tools/gridbar/launchfloor.hip): a frame is bound by the latency INSIDE its kernels.  gemv8 keeps 8 loads x 4 waves = 32 KB in flight
 // per CU, so gate|up's 128 KB per workgroup are four exposed HBM round trips, and its 64 fp32 accumulators per lane (8 columns x 8 rows)
@@ -136,20 +136,13 @@ __global__ __launch_bounds__(512) void gemvm_kernel(FGArgs a) {
     }
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_sched_barrier(0);
-  if (a.dbg & 1) {  // matrices that are re-read within the reach of the memory-side cache (the depth decoder: 222 MB, 31 times per frame): plain loads
+  // the first round is PLAIN loads, the refills below nontemporal ones: with this round nontemporal too, the CSM frame bench step
+  // (B = 8) took 380 instead of 357 ms
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int c = wave + 8 * j, cc = c < nch ? c : nch - 1;
+  for (int j = 0; j < 4; ++j) {
+    const int c = wave + 8 * j, cc = c < nch ? c : nch - 1;
 #pragma unroll
-      for (int s = 0; s < NSUB; ++s) ring[j][s] = *(wblk + (long long)(cc * NSUB + s) * 64);
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int c = wave + 8 * j, cc = c < nch ? c : nch - 1;
-#pragma unroll
-      for (int s = 0; s < NSUB; ++s) ring[j][s] = __builtin_nontemporal_load(wblk + (long long)(cc * NSUB + s) * 64);
-    }
+    for (int s = 0; s < NSUB; ++s) ring[j][s] = *(wblk + (long long)(cc * NSUB + s) * 64);
   }
   __builtin_amdgcn_sched_barrier(0);  // (the scheduler otherwise issues most of the weight loads BEHIND the split arithmetic to save registers)
   // ---- prologue, exact three-way bf16 split, fragment order

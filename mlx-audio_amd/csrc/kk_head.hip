@@ -35,7 +35,7 @@ constexpr int HD_NKS = HD_C / 16;    // k-steps per tap
 constexpr int HD_NIT = HD_K * HD_NKS;
 constexpr int HD_YLD = 23;           // fp32 pitch of the frame-major exchange tile (odd: conflict-free rows)
 constexpr int HD_EX_BYTES = 4 * 3 * 15 * 4;  // y[5..19] of the last three frames of every wave
-template <int ROWS>  // frames per workgroup (256: one frame per thread; 128: half the threads idle in the frame phase, but 4 workgroups per CU)
+template <int ROWS>  // frames per workgroup: 256, one frame per thread (128 -- half the threads idle in the frame phase, but 4 workgroups per CU -- was not kept)
 struct HeadGeo {
   static constexpr int HB = ROWS - 3;  // hop blocks produced per workgroup
   static constexpr int XROWS = ROWS + HD_K - 1;
@@ -48,7 +48,7 @@ struct HeadGeo {
 constexpr int HD_WIT = HD_NIT / 4;   // k-steps (weight fragments) per wave
 
 template <int HD_ROWS>
-__global__ __launch_bounds__(256, (HD_ROWS == 256 ? 2 : 3)) void conv_post_istft_kernel(KKHeadArgs a) {
+__global__ __launch_bounds__(256, 2) void conv_post_istft_kernel(KKHeadArgs a) {
   using G = HeadGeo<HD_ROWS>;
   constexpr int HD_HB = G::HB, HD_XROWS = G::XROWS, HD_XREG = G::XREG;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -90,7 +90,6 @@ __global__ __launch_bounds__(256, (HD_ROWS == 256 ? 2 : 3)) void conv_post_istft
       const int r = id >> 4, c8 = (id & 15) * 8;
       int row = f0 - 6 + r;
       row = row < 0 ? 0 : (row > hi ? hi : row);
-      if (a.dbg & 4) row &= 63;  // timing experiment: the slab comes from the first 64 rows (cache resident)
       xr[i] = *(const uint4*)(xb + (long long)row * a.ldx + c8);
     }
     asm volatile("" ::: "memory");
@@ -198,7 +197,7 @@ __global__ __launch_bounds__(256, (HD_ROWS == 256 ? 2 : 3)) void conv_post_istft
   __syncthreads();
   // ---- thread t = frame f0 - 3 + t
   const int f = f0 - 3 + tid;
-  const bool act = tid < HD_ROWS;  // (ROWS = 128: waves 2, 3 only keep the barriers company from here on)
+  const bool act = tid < HD_ROWS;
   const bool fv = act && f >= 0 && f < Tf;
   const int tq = act ? tid : 0;
   float in[22];
@@ -210,12 +209,7 @@ __global__ __launch_bounds__(256, (HD_ROWS == 256 ? 2 : 3)) void conv_post_istft
     for (int k = 0; k < 22; ++k) cr[k] = (bf16_t)in[k];
   }
   float y[20];
-  if (a.dbg & 2) {  // timing experiment: no frame arithmetic
-#pragma unroll
-    for (int o = 0; o < 20; ++o) y[o] = in[o];
-  } else {
-    kk_istft::frame_fast(in, fv ? 1.0f : 0.0f, y);
-  }
+  kk_istft::frame_fast(in, fv ? 1.0f : 0.0f, y);
   if (lane >= 61 && act) {
 #pragma unroll
     for (int k = 0; k < 15; ++k) Ex[(wave * 3 + (lane - 61)) * 15 + k] = y[5 + k];
@@ -292,21 +286,10 @@ int kk_launch_conv_post_istft(const KKHeadArgs& a, int B, hipStream_t st) {
   static KKDevOnce attr_once;
   if (attr_once.first()) {
     (void)hipFuncSetAttribute((const void*)conv_post_istft_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, HeadGeo<256>::LDS);
-    (void)hipFuncSetAttribute((const void*)conv_post_istft_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, HeadGeo<128>::LDS);
     attr_once.done();
   }
-  static int rows = -1;
-  if (rows < 0) {
-    const char* e = getenv("KK_HEAD_ROWS");  // A/B switch
-    rows = e ? atoi(e) : 256;
-  }
-  if (rows == 128) {
-    dim3 grid(kk_cdiv(a.Tfmax + 3, HeadGeo<128>::HB), B);
-    hipLaunchKernelGGL(conv_post_istft_kernel<128>, grid, dim3(256), HeadGeo<128>::LDS, st, a);
-  } else {
-    dim3 grid(kk_cdiv(a.Tfmax + 3, HeadGeo<256>::HB), B);
-    hipLaunchKernelGGL(conv_post_istft_kernel<256>, grid, dim3(256), HeadGeo<256>::LDS, st, a);
-  }
+  dim3 grid(kk_cdiv(a.Tfmax + 3, HeadGeo<256>::HB), B);
+  hipLaunchKernelGGL(conv_post_istft_kernel<256>, grid, dim3(256), HeadGeo<256>::LDS, st, a);
   KK_CHECK_LAUNCH();
   return 0;
 }

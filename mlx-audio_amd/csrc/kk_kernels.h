@@ -29,7 +29,6 @@ struct KKMfmaArgs {
   int accumulate, act;
   float act_slope;
   int in_act;  // variant 4 only: KK_ACT_ELU = elu(x, 1) applied to the input while it is staged (Mimi SEANet); 0 = leaky-relu(in_slope)
-  int dbg;  // timing experiments only (KK_MFMA_DBG): bit0 skip W reloads, bit1 skip X reloads
   // fused input transform (AdaIN apply + activation while staging X):  y = act(x * nrm_a[b][c] + nrm_b[b][c])
   const float* nrm_a;  // [B][nrm_stride], zero for pad channels; null = no transform
   const float* nrm_b;
@@ -70,7 +69,10 @@ __host__ __device__ inline long long kk_linear_pack_index(int o, int i, int K) {
 }
 int kk_launch_linear_rows_mfma(const KKLinMfmaArgs& a, hipStream_t st);
 bool kk_mfma_eligible(int Cin, int Cout, int Kw, int mode, int stride, int dil);
-int kk_mfma_tile_rows(int Q);  // 128 or 256 output rows per workgroup for a launch covering Q rows per phase
+// output rows per workgroup of variants 2 / 4 (also their statistics tile).  Measured (tools/bench_conv.py): 192 rows (3 MFMA row blocks per
+// wave, 250 VGPRs, 73 KB LDS -> still two workgroups per CU) streams a third less W per MFMA than 128 and is 8-10 % faster on every shape;
+// a 256-row variant spilled and was slower
+constexpr int KK_MFMA_TILE_ROWS = 192;
 int kk_launch_conv_mfma(const KKMfmaArgs& a, int B, int out_dtype, hipStream_t st);
 // variant 4 (kk_conv_mfma4.hip): W fragments straight from global memory into the MFMA operand registers; 192-row tiles, bf16 out
 int kk_launch_conv_mfma4(const KKMfmaArgs& a, int B, int out_dtype, hipStream_t st);
@@ -79,8 +81,6 @@ bool kk_mfma5_eligible(const KKMfmaArgs& a, int out_dtype);
 int kk_launch_conv_mfma5(const KKMfmaArgs& a, int B, int out_dtype, hipStream_t st);
 long long kk_mfma4_pack_index(int tap, int cout, int k, int CoutP, int CinP);
 int kk_launch_pack_w_frag(const void* w, void* wf, int Kw, int CoutP, int CinP, hipStream_t st);
-// rows per statistics tile of the kernel kk_launch_conv_mfma will pick for these arguments
-int kk_mfma_stat_tile_rows(const KKMfmaArgs& a, int out_dtype);
 
 // ---- normalisation family (kk_norm.hip)
 struct KKStatsArgs {
@@ -265,7 +265,6 @@ struct KKHeadArgs {
   long long cp_bs;
   int cp_ld;
   float hann_per[20];  // periodic Hann (utils.py:121), for the partial window sums at utterance edges
-  int dbg;             // timing experiments only (KK_HEAD_DBG): bit 0 one k-step, bit 1 no frame arithmetic, bit 2 cache-resident input
 };
 bool kk_head_eligible(int Cin, int Cout, int Kw, int n_fft, int hop);
 long long kk_head_pack_index(int tap, int cout, int cin);

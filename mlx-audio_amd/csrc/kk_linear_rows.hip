@@ -108,9 +108,7 @@ __global__ __launch_bounds__(256) void linear_rows_mfma_kernel(KKLinMfmaArgs a) 
 int kk_launch_linear_rows_mfma(const KKLinMfmaArgs& a, hipStream_t st) {
   if (a.K % 32 || a.N % 2 || a.rows < 1 || a.items < 1) return kk_fail("linear_rows_mfma: bad shape");
   const int M = a.flat ? a.items * a.rows : a.rows;
-  static int wide = -1;
-  if (wide < 0) wide = getenv("KK_LINROWS_WIDE") ? 1 : 0;  // (A/B: 64 columns per wave at every size)
-  if (M <= 256 && !wide) {
+  if (M <= 256) {
     const dim3 grid((a.N + 31) / 32, (M + 63) / 64, a.flat ? 1 : a.items);
     hipLaunchKernelGGL((linear_rows_mfma_kernel<2, 1, 12>), grid, dim3(256), 0, st, a);
   } else {  // (a 64-row x 64-column wave, <4, 4, 4>, was measured for full batches too: 40.7 vs 39.9 ms per B = 32 step against the tiled kernel -- the caller keeps that one above ~1000 rows)

@@ -62,11 +62,8 @@ int kk_launch_lstm(const KKLstmArgs& a, int B, int dtype, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// bf16 mode, H = 256: Wh stays ON CHIP for the whole sequence.  Thread g owns gate row g (256 weights, bf16):
-// the first 192 live in 96 VGPRs (packed pairs), the last 64 in a 144-byte-pitched LDS row (conflict-free b128 reads).
-// h is kept in LDS as 128 packed bf16 pairs that every lane reads as broadcasts; one v_dot2c_f32_bf16 per weight pair.
-// Per step: 2 x 128 dot2 + 32 broadcast reads + 2 x 8 row reads per lane, one barrier -- no L2 weight traffic at all (the
-// generic kernel above re-streams 1 MiB of fp32 Wh per step and direction).
+// bf16 mode, H = 256: Wh stays ON CHIP for the whole sequence (the generic kernel above re-streams 1 MiB of fp32 Wh per step and
+// direction); h is kept in LDS as packed bf16 pairs, one v_dot2c_f32_bf16 per weight pair.
 // ------------------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -76,107 +73,27 @@ __device__ __forceinline__ float dot2(unsigned w, unsigned h, float acc) {
   return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, w), __builtin_bit_cast(bf16x2_t, h), acc, false);
 }
 
-constexpr int LH = 256, LG = 1024, KR = 192, KL = 64, LWLD = 72;  // LDS row pitch in bf16 elements (144 B)
-constexpr int LSTM_LDS = LG * LWLD * 2 + 2 * 128 * 4;
+constexpr int LH = 256, LG = 1024;
 
-// 512 threads, each owning TWO gate rows: 2 x 96 weight registers fit the 256-VGPR budget of two waves per SIMD without spilling, and
-// every broadcast read of h feeds two dot products.
-// Round 3 (VERDICT next #10): a step was ~4000 cycles for 2048 cycles of dot products -- the rest were the exchange of the 1024 gate
-// values through LDS with its own barrier, a second barrier behind the state update of 256 threads, and precise expf / tanhf.  Now the
-// four gates of hidden unit j live in ONE LANE PAIR (lane 2j: rows i_j, f_j; lane 2j + 1: rows g_j, o_j), so the gates meet in two DPP
-// exchanges instead of LDS + barrier, both lanes carry c_j and h_j, and h goes into a double-buffered packed-bf16 vector: ONE barrier
-// per step.  Activations: sigmoid(x) = rcp(1 + exp(-x)), tanh(x) = 1 - 2 rcp(1 + exp(2x)) on v_exp_f32 / v_rcp_f32 (1e-6 absolute,
-// far inside the bf16 rounding of h that this mode applies every step anyway).
+// Round 3 (VERDICT next #10): the first on-chip form (512 threads, each owning two gate rows of 256 k) took ~4000 cycles per step for
+// 2048 cycles of dot products -- the rest were the exchange of the 1024 gate values through LDS with its own barrier, a second barrier
+// behind the state update of 256 threads, and precise expf / tanhf.  The four gates of hidden unit j live in ONE LANE PAIR (rows i_j, f_j
+// on the even lane, g_j, o_j on the odd one), so the gates meet in two DPP exchanges instead of LDS + barrier, both lanes carry c_j and
+// h_j, and h goes into a double-buffered packed-bf16 vector: ONE barrier per step.  Activations: sigmoid(x) = rcp(1 + exp(-x)),
+// tanh(x) = 1 - 2 rcp(1 + exp(2x)) on v_exp_f32 / v_rcp_f32 (1e-6 absolute, far inside the bf16 rounding of h that this mode applies
+// every step anyway).
 __device__ __forceinline__ float sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ __forceinline__ float tanh_fast(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
 
-template <typename T>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void lstm_h256_bf16_kernel(KKLstmArgs a, const bf16_t* whb) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
-  bf16_t* wl = (bf16_t*)lsm;                              // [1024][72]
-  unsigned* hb = (unsigned*)(lsm + LG * LWLD * 2);        // [2][128] packed (h[2k], h[2k+1]), double-buffered over the steps
-  const int b = blockIdx.x, dir = blockIdx.y, t0 = threadIdx.x;
-  const int j = t0 >> 1, odd = t0 & 1;
-  const int g0 = odd ? 2 * LH + j : j, g1 = odd ? 3 * LH + j : LH + j;  // even lane: i_j, f_j; odd lane: g_j, o_j
-  const int L = kk_len(a.len, b);
-  const bf16_t* wrow0 = whb + ((long long)dir * LG + g0) * LH;
-  const bf16_t* wrow1 = whb + ((long long)dir * LG + g1) * LH;
-  unsigned wa[KR / 2], wb[KR / 2];
-#pragma unroll
-  for (int q = 0; q < KR / 8; ++q) {
-    const uint4 v = *(const uint4*)(wrow0 + q * 8);
-    wa[4 * q] = v.x; wa[4 * q + 1] = v.y; wa[4 * q + 2] = v.z; wa[4 * q + 3] = v.w;
-    const uint4 u = *(const uint4*)(wrow1 + q * 8);
-    wb[4 * q] = u.x; wb[4 * q + 1] = u.y; wb[4 * q + 2] = u.z; wb[4 * q + 3] = u.w;
-  }
-#pragma unroll
-  for (int q = 0; q < KL / 8; ++q) {
-    *(uint4*)(wl + g0 * LWLD + q * 8) = *(const uint4*)(wrow0 + KR + q * 8);
-    *(uint4*)(wl + g1 * LWLD + q * 8) = *(const uint4*)(wrow1 + KR + q * 8);
-  }
-  if (t0 < 256) hb[t0] = 0u;
-  const float* xp = a.xproj + (long long)b * a.Lmax * 2 * LG + (long long)dir * LG;
-  T* ob = (T*)a.out + (long long)b * a.obs + dir * LH;
-  float c = 0.f;
-  const long long tfirst = dir ? L - 1 : 0;
-  float xn0 = L > 0 ? xp[tfirst * 2 * LG + g0] : 0.f, xn1 = L > 0 ? xp[tfirst * 2 * LG + g1] : 0.f;
-  __syncthreads();
-  for (int step = 0; step < L; ++step) {
-    const int t = dir ? (L - 1 - step) : step;
-    const unsigned* hc = hb + (step & 1) * 128;
-    unsigned* hnx = hb + ((step + 1) & 1) * 128;
-    float acc0 = xn0, acc1 = xn1;
-    if (step + 1 < L) {  // prefetch the next step's input projection
-      const long long tn = dir ? t - 1 : t + 1;
-      xn0 = xp[tn * 2 * LG + g0];
-      xn1 = xp[tn * 2 * LG + g1];
-    }
-#pragma unroll
-    for (int q = 0; q < KR / 8; ++q) {
-      const uint4 hv = *(const uint4*)(hc + 4 * q);
-      acc0 = dot2(wa[4 * q], hv.x, acc0);     acc1 = dot2(wb[4 * q], hv.x, acc1);
-      acc0 = dot2(wa[4 * q + 1], hv.y, acc0); acc1 = dot2(wb[4 * q + 1], hv.y, acc1);
-      acc0 = dot2(wa[4 * q + 2], hv.z, acc0); acc1 = dot2(wb[4 * q + 2], hv.z, acc1);
-      acc0 = dot2(wa[4 * q + 3], hv.w, acc0); acc1 = dot2(wb[4 * q + 3], hv.w, acc1);
-    }
-#pragma unroll
-    for (int q = 0; q < KL / 8; ++q) {
-      const uint4 hv = *(const uint4*)(hc + KR / 2 + 4 * q);
-      const uint4 w0 = *(const uint4*)(wl + g0 * LWLD + q * 8);
-      const uint4 w1 = *(const uint4*)(wl + g1 * LWLD + q * 8);
-      acc0 = dot2(w0.x, hv.x, acc0); acc1 = dot2(w1.x, hv.x, acc1);
-      acc0 = dot2(w0.y, hv.y, acc0); acc1 = dot2(w1.y, hv.y, acc1);
-      acc0 = dot2(w0.z, hv.z, acc0); acc1 = dot2(w1.z, hv.z, acc1);
-      acc0 = dot2(w0.w, hv.w, acc0); acc1 = dot2(w1.w, hv.w, acc1);
-    }
-    // even lane: acc0 = i, acc1 = f; odd lane: acc0 = g, acc1 = o.  tanh(x) = 2 sigmoid(2x) - 1: one code path for both lanes
-    const float sc = odd ? 2.0f : 1.0f;
-    float a0 = sigmoid_fast(acc0 * sc);
-    a0 = odd ? 2.0f * a0 - 1.0f : a0;
-    const float a1 = sigmoid_fast(acc1);
-    const float p0 = __shfl_xor(a0, 1), p1 = __shfl_xor(a1, 1);    // the pair's other two gates
-    c = (odd ? p1 : a1) * c + a0 * p0;  // f c + i g (modules.py:179-186); both lanes of the pair carry the unit's state
-    const float h = (odd ? a1 : p1) * tanh_fast(c);
-    const float hn = __shfl_down(h, 2);  // unit j + 1 (lanes = 0 mod 4 pack a pair; their partner lane + 2 is in the same wave)
-    if ((t0 & 3) == 0) {
-      const bf16x2_t p = {(bf16_t)h, (bf16_t)hn};
-      hnx[t0 >> 2] = __builtin_bit_cast(unsigned, p);
-    }
-    if (!odd) kk_st(ob + (long long)t * a.ldo + j, h);
-    __syncthreads();
-  }
-  if (t0 < LH)
-    for (int t = L; t < a.Lmax; ++t) kk_st(ob + (long long)t * a.ldo + t0, 0.f);
-}
-
-// Round 3, second form (lstm_h256_bf16_rs_kernel): the step above is LDS-bound, not VALU-bound -- per CU and step 8 waves x (32 broadcast reads of h +
-// 16 reads of the weight tails) x 8 cycles = 3072 LDS cycles beside 2528 VALU cycles per SIMD.  Here a lane owns 16 ROWS x 32 K instead of 2 rows x 256 k:
+// lstm_h256_bf16_rs_kernel: the lane-pair step with 2 rows x 256 k per lane (since removed) was LDS-bound, not VALU-bound -- per CU and
+// step 8 waves x (32 broadcast reads of h + 16 reads of the weight tails) x 8 cycles = 3072 LDS cycles beside 2528 VALU cycles per SIMD.
+// Here a lane owns 16 ROWS x 32 K:
 // lane = (row group rg = tid / 8, k group kg = tid % 8); it reads only ITS 16 packed pairs of h (4 reads instead of 32), multiplies them into 16 partial
 // sums (12 pairs of every row in registers, 4 in LDS at a conflict-free [row][thread] layout), and the eight partial sums of a row meet in a
 // REDUCE-SCATTER over DPP adds (row_half_mirror, then quad_perm xor 2, xor 1: 8 + 4 + 2 exchanges; the rows sit in the lane's registers in the order
 // the exchange wants, so no selects), after which lane kg holds local rows 2 kg, 2 kg + 1.
-// The group's 16 rows are ordered (unit, gate), so those are (i, f) of unit kg / 2 for an even lane and (g, o) for its odd neighbour: the lane-pair state
-// update, the packed double-buffered h and the single barrier per step are the ones of the kernel above.  20 LDS reads per wave and step instead of 48.
+// The group's 16 rows are ordered (unit, gate), so those are (i, f) of unit kg / 2 for an even lane and (g, o) for its odd neighbour: the lane-pair
+// state update, the packed double-buffered h and the single barrier per step.  20 LDS reads per wave and step instead of 48.
 __device__ __forceinline__ float dpp_half_mirror(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, false)); }
 __device__ __forceinline__ float dpp_xor2(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, false)); }
 __device__ __forceinline__ float dpp_xor1(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false)); }
@@ -270,24 +187,15 @@ int kk_launch_lstm_h256_bf16(const KKLstmArgs& a, const void* whb, int B, int dt
   if (a.H != LH) return kk_fail("lstm_h256_bf16: H must be 256");
   static KKDevOnce attr_once;
   if (attr_once.first()) {
-    (void)hipFuncSetAttribute((const void*)lstm_h256_bf16_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, LSTM_LDS);
-    (void)hipFuncSetAttribute((const void*)lstm_h256_bf16_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, LSTM_LDS);
     (void)hipFuncSetAttribute((const void*)lstm_h256_bf16_rs_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS);
     (void)hipFuncSetAttribute((const void*)lstm_h256_bf16_rs_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS);
     attr_once.done();
   }
-  static int pair_form = -1;
-  if (pair_form < 0) pair_form = getenv("KK_LSTM_PAIR") ? 1 : 0;  // (A/B: the 2-rows-per-lane form)
   dim3 grid(B, 2);
-  if (!pair_form) {
-    if (dtype == KK_F32)
-      hipLaunchKernelGGL(lstm_h256_bf16_rs_kernel<float>, grid, dim3(512), RS_LDS, st, a, (const bf16_t*)whb);
-    else
-      hipLaunchKernelGGL(lstm_h256_bf16_rs_kernel<bf16_t>, grid, dim3(512), RS_LDS, st, a, (const bf16_t*)whb);
-  } else if (dtype == KK_F32)
-    hipLaunchKernelGGL(lstm_h256_bf16_kernel<float>, grid, dim3(512), LSTM_LDS, st, a, (const bf16_t*)whb);
+  if (dtype == KK_F32)
+    hipLaunchKernelGGL(lstm_h256_bf16_rs_kernel<float>, grid, dim3(512), RS_LDS, st, a, (const bf16_t*)whb);
   else
-    hipLaunchKernelGGL(lstm_h256_bf16_kernel<bf16_t>, grid, dim3(512), LSTM_LDS, st, a, (const bf16_t*)whb);
+    hipLaunchKernelGGL(lstm_h256_bf16_rs_kernel<bf16_t>, grid, dim3(512), RS_LDS, st, a, (const bf16_t*)whb);
   KK_CHECK_LAUNCH();
   return 0;
 }

@@ -164,6 +164,7 @@ struct kk_context {
   std::map<std::string, const float*> dbg_over;
 
   // optional per-kernel-class timing (kk_profile_*): HIP events around every launch of a class
+  int flags = 0;               // the word kk_debug_force_generic received: the booleans below are its bits, the kk_forward graph key holds it whole
   bool force_generic = false;  // tests: run the bf16 mode without the MFMA kernel
   bool no_fusion = false;      // tests: MFMA convs but stand-alone statistics / AdaIN kernels
   bool prof_on = false;
@@ -191,7 +192,7 @@ struct kk_context {
   hipStream_t side_stream = nullptr;
   hipEvent_t side_fork[2] = {nullptr, nullptr}, side_join[2] = {nullptr, nullptr};
   bool no_side = false;  // debug bit 8 of kk_debug_force_generic: everything on the caller's stream
-  int linrows_mode = 0;  // debug bits 9 / 10: the streaming Linear kernel never / at every size (default: up to KK_LINROWS_MAX rows in flight)
+  int linrows_mode = 0;  // debug bits 9 / 10: the streaming Linear kernel never / at every size (default: up to 1024 rows in flight)
   struct ProfRec { int cls; double flops; double bytes; };
   std::vector<ProfRec> prof_rec;
 };
@@ -237,7 +238,6 @@ extern "C" int kk_context_create(kk_model* m, kk_context** out) {
     kk_context_destroy(cx);
     return kk_fail("kk_context_create: hipStreamCreate / hipEventCreate failed");
   }
-  if (getenv("KK_NO_SIDE")) cx->no_side = true;  // (A/B timing / debugging: no side stream)
   *out = cx;
   return 0;
 }
@@ -875,20 +875,12 @@ struct Ctx {
   // the branch read its inputs early), and a blocking side stream would serialise with stream 0 anyway.  A capture runs on the model's own stream,
   // so a replayed graph has the branches whatever stream it is launched on.
   bool side_on() const { return !dry && !cx->no_side && cx->side_stream && st != nullptr; }
-  static int side_mask() {  // (debugging: KK_SIDE_MASK bit k enables branch k; default both)
-    static int v = -1;
-    if (v < 0) {
-      const char* e = getenv("KK_SIDE_MASK");
-      v = e ? atoi(e) : 3;
-    }
-    return v;
-  }
   int fork_point(int k) {
-    if (!side_on() || !(side_mask() & (1 << k))) return 0;
+    if (!side_on()) return 0;
     return hipEventRecord(cx->side_fork[k], st) == hipSuccess ? 0 : kk_fail("kk_forward: hipEventRecord failed");
   }
   int begin_side(int k) {
-    if (!side_on() || !(side_mask() & (1 << k))) return 0;
+    if (!side_on()) return 0;
     if (hipStreamWaitEvent(cx->side_stream, cx->side_fork[k], 0) != hipSuccess) return kk_fail("kk_forward: hipStreamWaitEvent failed");
     main_st = st;
     st = cx->side_stream;
@@ -902,7 +894,7 @@ struct Ctx {
     return e == hipSuccess ? 0 : kk_fail("kk_forward: hipEventRecord failed");
   }
   int join_side(int k) {
-    if (!side_on() || !(side_mask() & (1 << k))) return 0;
+    if (!side_on()) return 0;
     return hipStreamWaitEvent(st, cx->side_join[k], 0) == hipSuccess ? 0 : kk_fail("kk_forward: hipStreamWaitEvent failed");
   }
   char* base;
@@ -988,9 +980,7 @@ struct Ctx {
     // latency-bound case (B = 1: 37 -> ~10 us per launch); from ~1000 rows on the tiled kernel's operand reuse wins (B = 32: the streaming form costs 4 % of the
     // step).  Both kernels feed the SAME matrix instruction the same operands in the same K order and share the epilogue arithmetic, so their results are
     // bit-identical (tests/test_gpu_forward.py::test_streaming_linear_equals_tiled_bitexact) and the choice by size does not touch batch invariance.
-    static int linrows_max = -1;
-    if (linrows_max < 0) { const char* e = getenv("KK_LINROWS_MAX"); linrows_max = e ? atoi(e) : 1024; }
-    const bool lr_size_ok = cx->linrows_mode == 1 || (cx->linrows_mode == 0 && (long long)B * Q <= linrows_max);
+    const bool lr_size_ok = cx->linrows_mode == 1 || (cx->linrows_mode == 0 && (long long)B * Q <= 1024);
     if (lr_size_ok && w.wl && w.Kw == 1 && can_mfma(w, x, out, o) && out.dtype == KK_BF16 && o.mode == KK_CONV && o.stride == 1 && o.pad == 0 && o.dil == 1 &&
         o.in_shift == 0 && !o.nrm_a && !o.want_stats && !o.res && !o.accumulate && o.in_slope == 1.f && o.scale == 1.f && o.post_slope == 1.f &&
         (o.act == KK_ACT_NONE || o.act == KK_ACT_GELU) && Q == x.rows && Q == out.rows && lin.len == lout.len && lin.mul == lout.mul && lin.add == lout.add &&
@@ -1018,7 +1008,7 @@ struct Ctx {
       g.Q = Q; g.Lo_rows = out.rows; g.lin = lin; g.lout = lout; g.in_slope = o.in_slope; g.scale = o.scale; g.accumulate = o.accumulate;
       g.act = o.act; g.act_slope = o.act_slope; g.post_slope = o.post_slope;
       if (o.want_stats) {
-        last_ntiles = kk_cdiv(Q, kk_mfma_stat_tile_rows(g, out.dtype)) * (o.mode == KK_CONVT ? o.stride : 1);
+        last_ntiles = kk_cdiv(Q, KK_MFMA_TILE_ROWS) * (o.mode == KK_CONVT ? o.stride : 1);
         if ((size_t)B * last_ntiles * 2 * w.Cout > fz_part_floats) return kk_fail("internal: statistics scratch too small");
         g.stat_part = fz_part;
         g.stat_ntiles = last_ntiles;
@@ -1029,20 +1019,12 @@ struct Ctx {
       // variant 5 (wave-specialised, persistent) takes the stride-1 convolutions; the polyphase transposed ones stay on variant 4
       // measured per shape: 3-9 % faster than variant 4 on the 11-tap layers, level on 7 taps, 10-25 % slower on 3 taps; round 3 (16x16x32
       // MFMA in both): also 2 % faster on the 7-tap layers of stage 0 (256 channels = 4 slabs per tile: more periods to spread the service work over)
-      static int v5_min_taps = -1;
-      if (v5_min_taps < 0) {
-        const char* e = getenv("KK_V5_MIN_TAPS");  // (experiments)
-        v5_min_taps = e ? atoi(e) : 9;
-      }
-      const bool v5 = v4 && cx->v5_mode != 2 && (cx->v5_mode == 1 || g.Kw >= v5_min_taps || (g.Kw >= v5_min_taps - 2 && g.CinP >= 256)) && B <= 256 && kk_mfma_tile_rows(Q) == 192 &&
-                      kk_mfma5_eligible(g, out.dtype);
+      const bool v5 = v4 && cx->v5_mode != 2 && (cx->v5_mode == 1 || g.Kw >= 9 || (g.Kw >= 7 && g.CinP >= 256)) && B <= 256 && kk_mfma5_eligible(g, out.dtype);
       // Linear layers over short utterances (Albert, T = 130 rows per item): the rows of a dense [B][T][C] tensor as ONE flat item, so that the
       // 192-row tiles run across utterance boundaries (32 x 130 rows = 22 tiles instead of 32).  k = 1, so rows do not interact; input rows past
       // an utterance's length are zeros already and the epilogue stores zeros there (KKMfmaArgs::flat_T).
       int Bl = B;
-      static int no_flat = -1;
-      if (no_flat < 0) no_flat = getenv("KK_NO_FLAT") ? 1 : 0;  // (A/B timing)
-      if (!no_flat && !v5 && B > 1 && w.Kw == 1 && o.mode == KK_CONV && o.stride == 1 && o.pad == 0 && o.dil == 1 && o.in_shift == 0 && !o.nrm_a && !o.want_stats &&
+      if (!v5 && B > 1 && w.Kw == 1 && o.mode == KK_CONV && o.stride == 1 && o.pad == 0 && o.dil == 1 && o.in_shift == 0 && !o.nrm_a && !o.want_stats &&
           Q == x.rows && Q == out.rows && Q % 192 != 0 && x.bs == (long long)x.rows * x.ld && out.bs == (long long)out.rows * out.ld &&
           (!o.res || (o.res->rows == out.rows && o.res->bs == (long long)o.res->rows * o.res->ld)) && (long long)B * Q < (1ll << 30)) {
         g.flat_T = Q;
@@ -1568,8 +1550,7 @@ int run_audio(Ctx& c, int Tmax, const int* lens, const float* ref_s, const int* 
   // The fused head will run (bf16 mode) and nobody looks at gen_stage1 / overrides a stage: the LeakyReLU(0.01) that conv_post applies to its
   // input (istftnet.py:797) moves into the epilogue of the conv that finishes the generator's last stage, and the head's slab staging --
   // a quarter of its vector instructions (profiles/r03_head_pmc.json) -- becomes a copy.
-  const bool post_lrelu = m->head_wf && !cx->no_head_fusion && !cx->force_generic && !cx->no_fusion && c.adt == KK_BF16 && !cx->keep_debug && cx->dbg_over.empty() &&
-                          !getenv("KK_NO_POST_LRELU");
+  const bool post_lrelu = m->head_wf && !cx->no_head_fusion && !cx->force_generic && !cx->no_fusion && c.adt == KK_BF16 && !cx->keep_debug && cx->dbg_over.empty();
   Buf cur = gx;           // input of ups[i]
   KKLen lcur = l2;
   int Lcur = L2;
@@ -1772,8 +1753,7 @@ extern "C" int kk_forward(kk_context* cx, void* stream, int B, int Tmax, const i
       (unsigned long long)(uintptr_t)ref_s, (unsigned long long)(uintptr_t)speed, (unsigned long long)(uintptr_t)forced_dur,
       (unsigned long long)(uintptr_t)sine_noise, (unsigned long long)(uintptr_t)workspace, (unsigned long long)workspace_bytes,
       (unsigned long long)(uintptr_t)wav_out, (unsigned long long)(uintptr_t)pred_dur_out, (unsigned long long)(uintptr_t)nframes_out,
-      (unsigned long long)cx->force_generic, (unsigned long long)cx->no_fusion, (unsigned long long)cx->no_v4,
-      (unsigned long long)cx->no_head_fusion, (unsigned long long)cx->keep_debug, (unsigned long long)cx->v5_mode, (unsigned long long)cx->no_side};
+      (unsigned long long)(unsigned)cx->flags};
   kk_context::GraphEntry* ge = nullptr;
   for (auto& g : cx->graphs)
     if (g.key == key) ge = &g;
@@ -1888,7 +1868,7 @@ extern "C" int kk_op_conv1d_bf16_fused(void* stream, int B, const void* x, int l
   g.in_slope = 1.f; g.scale = scale;
   g.nrm_a = nrm_a; g.nrm_b = nrm_b; g.nrm_stride = nrm_stride; g.nrm_act = nrm_act; g.nrm_slope = nrm_slope; g.nrm_alpha = nrm_alpha; g.nrm_C = Cin;
   g.stat_part = stat_part;
-  g.stat_ntiles = kk_cdiv(L_rows, kk_mfma_stat_tile_rows(g, KK_BF16));
+  g.stat_ntiles = kk_cdiv(L_rows, KK_MFMA_TILE_ROWS);
   if (stat_ntiles_out) *stat_ntiles_out = g.stat_ntiles;
   if (!kk_mfma_eligible(CinP, Cout, Kw, KK_CONV, 1, dil)) return kk_fail("kk_op_conv1d_bf16_fused: shape not eligible for the MFMA kernel");
   if (g_op_wfrag) {
@@ -2012,7 +1992,6 @@ extern "C" int kk_op_conv_post_istft(void* stream, int B, const void* x, int ldx
   h.len_frames = len_frames; h.Tfmax = Tf_rows; h.wav = wav; h.wbs = (long long)5 * (Tf_rows - 1);
   h.cp_out = (bf16_t*)cp_out; h.cp_bs = (long long)Tf_rows * cp_ld; h.cp_ld = cp_ld;
   for (int n = 0; n < 20; ++n) h.hann_per[n] = (float)(0.5 * (1.0 - cos(2.0 * 3.14159265358979323846 * n / 20.0)));
-  if (const char* e = getenv("KK_HEAD_DBG")) h.dbg = atoi(e);  // timing experiments (tools/bench_head.py)
   return kk_launch_conv_post_istft(h, B, (hipStream_t)stream);
 }
 
@@ -2041,6 +2020,7 @@ extern "C" int kk_debug_override(kk_context* cx, const char* name, const float* 
 }
 extern "C" void kk_debug_force_generic(kk_context* cx, int on) {
   if (!cx) return;
+  cx->flags = on;
   cx->force_generic = (on & 1) != 0;  // bit 0: no MFMA kernel at all
   cx->no_fusion = (on & 2) != 0;      // bit 1: MFMA convs, but stand-alone statistics / AdaIN kernels
   cx->no_v4 = (on & 4) != 0;          // bit 2: the LDS-staged MFMA kernel (variant 2) instead of variant 4

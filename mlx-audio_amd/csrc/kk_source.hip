@@ -194,156 +194,15 @@ __global__ __launch_bounds__(256) void stft20_kernel(const float* hs, int Nmax, 
   }
 }
 
-// ------------------------------------------------------------------ iSTFT head
-// HBM-bound by design: 22 inputs and 5 fp32 outputs per frame column (64 B with bf16 input).
-//   phase 0  the workgroup's [255 frames][ldx] input tile is ONE contiguous span: coalesced 16-byte loads into LDS
-//   phase 1  one thread per frame: exp / sin / sincos, then the 20-point inverse real DFT using the o <-> 20-o symmetry
-//            (cos terms even, sin terms odd: 11 x 18 FMAs instead of 20 x 18), x periodic Hann -> LDS
-//   phase 2  one thread per hop block: <= 4 overlapping frames added in ascending frame order (the reference's
-//            scatter-add order, utils.py:138-147), divided by the window sum accumulated in the same order
-//   phase 3  the 1260 output samples of the workgroup leave as coalesced 8-byte stores
-// 252 hop blocks + 3 halo frames = 255 frames: ONE frame per thread in phase 1 (with 256 + 3 the second trip of the frame loop
-// ran a full pass for three frames and doubled the kernel's VALU time); 252 * 5 samples keeps every workgroup's first sample even
-constexpr int IH_FR = 252;  // hop-blocks per workgroup
-constexpr int IH_NF = IH_FR + 3;
-
-template <typename T, bool FAST>
-__global__ __launch_bounds__(256) void istft_head_kernel(const T* x, long long xbs, int ldx, const int* len_frames, int Tfmax, float* wav,
-                                                         long long wbs, int stage_off, Tables tb) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char ism[];
-  // LDS: [ input tile [255][ldx]  ALIASED WITH  ys [255][21] fp32 ] [ stage [252][5] fp32 ] -- the tile is dead once every
-  // thread holds its frame's 22 spectrum values in registers (barrier), so 26.5 KB (bf16 input) per workgroup instead of 34 KB:
-  // 6 workgroups per CU instead of 4 to hide the tile-load latency
-  float* ys = (float*)ism;   // [255][21]
-  unsigned char* tile = ism;  // [255][ldx]
-  const int b = blockIdx.y, tid = threadIdx.x;
-  const int Tf = len_frames ? len_frames[b] : Tfmax;
-  const int g0 = blockIdx.x * IH_FR;  // first hop-block of this workgroup
-  const int f0 = g0 - 3;              // first frame of the tile
-  const T* xb = x + (long long)b * xbs;
-  const int row_bytes = ldx * (int)sizeof(T);
-  // ---- phase 0: coalesced tile load (frames clamped into [0, Tfmax): out-of-range frames are masked in phase 1)
-  {
-    const int fa = f0 < 0 ? 0 : f0;
-    const int fb = min(f0 + IH_NF, Tfmax);
-    const long long bytes = (long long)(fb - fa) * row_bytes;
-    const unsigned char* src = (const unsigned char*)(xb + (long long)fa * ldx);
-    unsigned char* dst = tile + (long long)(fa - f0) * row_bytes;
-    if (bytes > 0) {
-      if ((((uintptr_t)src) & 15) == 0 && (row_bytes & 15) == 0) {
-        for (long long o = (long long)tid * 16; o < bytes; o += 256 * 16) *(uint4*)(dst + o) = *(const uint4*)(src + o);
-      } else {
-        for (long long o = (long long)tid * sizeof(T); o < bytes; o += 256 * sizeof(T)) *(T*)(dst + o) = *(const T*)(src + o);
-      }
-    }
-  }
-  __syncthreads();
-  // ---- phase 1: windowed inverse real DFT of frames f0 .. f0+254
-  {
-    const int i = tid;  // IH_NF = 255 frames <= 256 threads
-    const int f = f0 + i;
-    float* yo = ys + i * 21;
-    const bool fv = i < IH_NF && f >= 0 && f < Tf;
-    float re[11], im[11];
-    if (fv) {
-      const T* xr = (const T*)(tile + (long long)i * row_bytes);
-#pragma unroll
-      for (int k = 0; k < 11; ++k) {
-        const float lm = kk_ld(xr + k), pr = kk_ld(xr + 11 + k);
-        const float mag = FAST ? __expf(lm) : expf(lm);
-        const float ph = FAST ? __sinf(pr) : sinf(pr);
-        float s, c;
-        if (FAST) __sincosf(ph, &s, &c); else sincosf(ph, &s, &c);
-        re[k] = mag * c;
-        im[k] = mag * s;
-      }
-    }
-    __syncthreads();  // every thread has read its row: ys may now overwrite the tile
-    if (fv) {
-      // x[o] = (re0 + (-1)^o re10 + 2 (C[o] - S[o])) / 20,  x[20-o] = (.. + 2 (C[o] + S[o])) / 20  with
-      //   C[o] = sum_k re[k] cos(2 pi k o / 20),  S[o] = sum_k im[k] sin(2 pi k o / 20),  k = 1..9.
-      // Even / odd k split: cos(2 pi k (10-o)/20) = (-1)^k cos(..o..), sin(2 pi k (10-o)/20) = -(-1)^k sin(..o..), so
-      // o and 10-o share their partial sums: 6 x 18 FMAs instead of 11 x 18.
-#pragma unroll
-      for (int o = 0; o <= 5; ++o) {
-        float Ce = 0.f, Co = 0.f, Se = 0.f, So = 0.f;
-#pragma unroll
-        for (int k = 1; k < 10; ++k) {
-          const int m = (k * o) % 20;
-          if (k & 1) {
-            Co = __builtin_fmaf(re[k], tb.cs[m], Co);
-            So = __builtin_fmaf(im[k], tb.sn[m], So);
-          } else {
-            Ce = __builtin_fmaf(re[k], tb.cs[m], Ce);
-            Se = __builtin_fmaf(im[k], tb.sn[m], Se);
-          }
-        }
-        {
-          const float C = Ce + Co, S = Se + So;
-          const float dc = re[0] + ((o & 1) ? -re[10] : re[10]);
-          yo[o] = (dc + 2.0f * (C - S)) * 0.05f * tb.hann_per[o];
-          if (o > 0) yo[20 - o] = (dc + 2.0f * (C + S)) * 0.05f * tb.hann_per[20 - o];
-        }
-        if (o < 5) {
-          const int p = 10 - o;
-          const float C = Ce - Co, S = So - Se;
-          const float dc = re[0] + ((p & 1) ? -re[10] : re[10]);
-          yo[p] = (dc + 2.0f * (C - S)) * 0.05f * tb.hann_per[p];
-          if (p < 10) yo[20 - p] = (dc + 2.0f * (C + S)) * 0.05f * tb.hann_per[20 - p];
-        }
-      }
-    } else if (i < IH_NF) {
-#pragma unroll
-      for (int o = 0; o < 20; ++o) yo[o] = 0.f;
-    }
-  }
-  __syncthreads();
-  // ---- phase 2: overlap-add in ascending frame order, normalise by the window sum, trim 10 | 10
-  float* stage = (float*)(ism + stage_off);  // [252][5]
-  const int g = g0 + tid;
-  const int nout = Tf > 0 ? 5 * (Tf - 1) : 0;
-#pragma unroll
-  for (int r = 0; r < 5; ++r) {
-    if (tid >= IH_FR) break;
-    const int n = 5 * g + r - 10;
-    float v = 0.f;
-    if (n >= 0 && n < nout) {
-      float acc = 0.f, ws = 0.f;
-#pragma unroll
-      for (int j = 3; j >= 0; --j) {
-        const int f = g - j;
-        if (f >= 0 && f < Tf) {
-          acc += ys[(tid + 3 - j) * 21 + 5 * j + r];
-          ws += tb.hann_per[5 * j + r];
-        }
-      }
-      v = ws != 0.f ? (FAST ? acc * __builtin_amdgcn_rcpf(ws) : acc / ws) : acc;
-    }
-    stage[tid * 5 + r] = v;
-  }
-  __syncthreads();
-  // ---- phase 3: samples n0 .. n0+1259 (n0 = 5*g0 - 10, even) as float2 stores
-  float* wb = wav + (long long)b * wbs;
-  const long long n0 = 5LL * g0 - 10;
-  const long long ntot = 5LL * (Tfmax - 1);
-  for (int e = tid; e < IH_FR * 5 / 2; e += 256) {
-    const long long n = n0 + 2 * e;
-    const float2 v = *(const float2*)(stage + 2 * e);
-    if (n >= 0 && n + 1 < ntot && ((((uintptr_t)(wb + n)) & 7) == 0)) {
-      *(float2*)(wb + n) = v;
-    } else {
-      if (n >= 0 && n < ntot) wb[n] = v.x;
-      if (n + 1 >= 0 && n + 1 < ntot) wb[n + 1] = v.y;
-    }
-  }
-}
-
 // ------------------------------------------------------------------ iSTFT head, wave-local form (no LDS, no barriers)
+// HBM-bound by design: 22 inputs and 5 fp32 outputs per frame column (64 B with bf16 input).  Per frame: exp / sin / sincos,
+// then the 20-point inverse real DFT using the o <-> 20-o symmetry (cos terms even, sin terms odd: 11 x 18 FMAs instead of 20 x 18),
+// x periodic Hann; per hop block: <= 4 overlapping frames added in ascending frame order (the reference's scatter-add order,
+// utils.py:138-147), divided by the window sum accumulated in the same order.
 // Lane l of a wave owns frame f = gw0 - 3 + l; the <= 4 frames that overlap hop block g = f live in lanes l-3 .. l, so the
 // overlap-add is 15 __shfl_up and lanes 3..63 each produce the 5 samples of their hop block (61 hop blocks per wave; the 3
 // halo frames per wave are recomputed, 5 %).  Occupancy is then bounded by VGPRs alone (8 waves per SIMD), which is what this
-// transcendental-bound kernel needs to hide its input latency.  Same arithmetic and the same ascending-frame summation order
-// as the tiled kernel above (the reference's scatter-add order, utils.py:138-147).
+// transcendental-bound kernel needs to hide its input latency (the LDS-tiled form it replaced staged 255 frames per workgroup).
 constexpr int IW_HB = 61;  // hop blocks per wave
 
 template <typename T, bool FAST>
@@ -547,11 +406,7 @@ int kk_launch_istft_head(const void* x, long long xbs, int ldx, const int* len_f
                          int dtype, int fast, hipStream_t st) {
   if (B <= 0 || Tfmax <= 0) return 0;
   if (ldx < 22 || ldx > 64) return kk_fail("istft_head: input pitch must be in [22, 64]");
-  static int tiled = -1;
-  if (tiled < 0) tiled = getenv("KK_ISTFT_TILED") ? 1 : 0;  // A/B switch: the LDS-tiled kernel
-  static int oldfast = -1;
-  if (oldfast < 0) oldfast = getenv("KK_ISTFT_OLDFAST") ? 1 : 0;  // A/B switch: the generic wave kernel's FAST instantiation
-  if (!tiled && fast && !oldfast && 5LL * Tfmax < 0x7fffffffLL) {
+  if (fast && 5LL * Tfmax < 0x7fffffffLL) {  // (5 Tfmax >= 2^31 samples: the generic wave kernel's FAST form below)
     dim3 gw(kk_cdiv(Tfmax + 3, 4 * IW_HB), B);
     if (dtype == KK_F32)
       hipLaunchKernelGGL((istft_head_wave_fast_kernel<float>), gw, dim3(256), 0, st, (const float*)x, xbs, ldx, len_frames, Tfmax, wav, wbs, g_tables);
@@ -560,35 +415,13 @@ int kk_launch_istft_head(const void* x, long long xbs, int ldx, const int* len_f
     KK_CHECK_LAUNCH();
     return 0;
   }
-  if (!tiled) {
-    dim3 gw(kk_cdiv(Tfmax + 3, 4 * IW_HB), B);
-    if (dtype == KK_F32) {
-      if (fast) hipLaunchKernelGGL((istft_head_wave_kernel<float, true>), gw, dim3(256), 0, st, (const float*)x, xbs, ldx, len_frames, Tfmax, wav, wbs, g_tables);
-      else hipLaunchKernelGGL((istft_head_wave_kernel<float, false>), gw, dim3(256), 0, st, (const float*)x, xbs, ldx, len_frames, Tfmax, wav, wbs, g_tables);
-    } else {
-      if (fast) hipLaunchKernelGGL((istft_head_wave_kernel<bf16_t, true>), gw, dim3(256), 0, st, (const bf16_t*)x, xbs, ldx, len_frames, Tfmax, wav, wbs, g_tables);
-      else hipLaunchKernelGGL((istft_head_wave_kernel<bf16_t, false>), gw, dim3(256), 0, st, (const bf16_t*)x, xbs, ldx, len_frames, Tfmax, wav, wbs, g_tables);
-    }
-    KK_CHECK_LAUNCH();
-    return 0;
-  }
-  dim3 grid(kk_cdiv(Tfmax + 3, IH_FR), B);
-  const size_t esz = dtype == KK_F32 ? 4 : 2;
-  size_t front = (size_t)IH_NF * ldx * esz;  // input tile, aliased with ys
-  if (front < (size_t)IH_NF * 21 * 4) front = (size_t)IH_NF * 21 * 4;
-  front = (front + 15) & ~(size_t)15;
-  const int soff = (int)front;
-  const size_t lds = front + (size_t)IH_FR * 5 * 4;
+  dim3 gw(kk_cdiv(Tfmax + 3, 4 * IW_HB), B);
   if (dtype == KK_F32) {
-    if (fast)
-      hipLaunchKernelGGL((istft_head_kernel<float, true>), grid, dim3(256), lds, st, (const float*)x, xbs, ldx, len_frames, Tfmax, wav, wbs, soff, g_tables);
-    else
-      hipLaunchKernelGGL((istft_head_kernel<float, false>), grid, dim3(256), lds, st, (const float*)x, xbs, ldx, len_frames, Tfmax, wav, wbs, soff, g_tables);
+    if (fast) hipLaunchKernelGGL((istft_head_wave_kernel<float, true>), gw, dim3(256), 0, st, (const float*)x, xbs, ldx, len_frames, Tfmax, wav, wbs, g_tables);
+    else hipLaunchKernelGGL((istft_head_wave_kernel<float, false>), gw, dim3(256), 0, st, (const float*)x, xbs, ldx, len_frames, Tfmax, wav, wbs, g_tables);
   } else {
-    if (fast)
-      hipLaunchKernelGGL((istft_head_kernel<bf16_t, true>), grid, dim3(256), lds, st, (const bf16_t*)x, xbs, ldx, len_frames, Tfmax, wav, wbs, soff, g_tables);
-    else
-      hipLaunchKernelGGL((istft_head_kernel<bf16_t, false>), grid, dim3(256), lds, st, (const bf16_t*)x, xbs, ldx, len_frames, Tfmax, wav, wbs, soff, g_tables);
+    if (fast) hipLaunchKernelGGL((istft_head_wave_kernel<bf16_t, true>), gw, dim3(256), 0, st, (const bf16_t*)x, xbs, ldx, len_frames, Tfmax, wav, wbs, g_tables);
+    else hipLaunchKernelGGL((istft_head_wave_kernel<bf16_t, false>), gw, dim3(256), 0, st, (const bf16_t*)x, xbs, ldx, len_frames, Tfmax, wav, wbs, g_tables);
   }
   KK_CHECK_LAUNCH();
   return 0;

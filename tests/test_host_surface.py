@@ -28,6 +28,18 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert set(_lib.SIGNATURES) <= declared
 
 
+def test_library_reads_no_environment_switches():
+    # the library is steered through its C ABI only: a switch read from the environment escapes the graph caches' keys and every test
+    found = []
+    for sub in ("mlx-audio_amd/csrc", "include"):
+        for dirpath, _, files in os.walk(os.path.join(ROOT, sub)):
+            for f in files:
+                if f.endswith((".hip", ".h", ".hpp", ".cpp", ".cc", ".c", ".inc")):
+                    p = os.path.join(dirpath, f)
+                    found += [f"{os.path.relpath(p, ROOT)}:{i}" for i, line in enumerate(open(p), 1) if "getenv" in line]
+    assert not found, found
+
+
 def test_kk_create_rejects_bad_configs_without_a_gpu():
     from mlx_audio_amd.engine import make_kk_config
 

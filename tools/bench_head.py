@@ -1,5 +1,6 @@
 """Micro-benchmark of the fused vocoder head (kk_head.hip) at the bench shape: B = 32 x 78 001 frames x 128 channels.
-KK_HEAD_ROWS=128|256 picks the tile; KK_HEAD_DBG bits are timing ablations (wrong results): 1 one k-step, 2 no frame arithmetic, 4 cached input."""
+python tools/bench_head.py [--slope S]   (the input LeakyReLU slope, default 0.01; 1 = the head staging raw rows)"""
+import argparse
 import ctypes as C
 import json
 import os
@@ -11,6 +12,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from mlx_audio_amd import _lib  # noqa: E402
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--slope", type=float, default=0.01)
+slope = ap.parse_args().slope
 lib = _lib.load()
 P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
 st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -24,7 +28,7 @@ wav = torch.empty(B, 5 * (Tf - 1), device="cuda")
 
 
 def call():
-    assert lib.kk_op_conv_post_istft(st(), B, P(x), Cn, Tf, None, P(wf), P(bias), C.c_float(float(os.environ.get("KK_HEAD_SLOPE", "0.01"))), P(wav), None, 0) == 0, lib.kk_last_error()
+    assert lib.kk_op_conv_post_istft(st(), B, P(x), Cn, Tf, None, P(wf), P(bias), C.c_float(slope), P(wav), None, 0) == 0, lib.kk_last_error()
 
 
 for _ in range(3):
@@ -38,5 +42,5 @@ e1.record()
 torch.cuda.synchronize()
 us = e0.elapsed_time(e1) / 20 * 1e3
 by = B * Tf * (Cn * 2 + 20)
-print(json.dumps({"rows": os.environ.get("KK_HEAD_ROWS", "256"), "dbg": os.environ.get("KK_HEAD_DBG", "0"), "us": round(us, 1), "GBs": round(by / us / 1e3, 1),
+print(json.dumps({"slope": slope, "us": round(us, 1), "GBs": round(by / us / 1e3, 1),
                   "frac_of_8TBs": round(by / us / 1e3 / 8000, 3)}))
