@@ -89,6 +89,7 @@ union U32x8 {
 template <typename TO, int WM, int NRM>
 __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_mfma_kernel(KKMfmaArgs a) {
   constexpr int BM = 2 * WM, MI = WM / 32;
+  constexpr bool ACC16 = false;  // 32 x 32 accumulator blocks (kk_conv_mfma_epilogue.h)
   using G = Geo<BM>;
   constexpr int XREG = G::XREG;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -199,7 +200,6 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
           acc[mi][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, b1, acc[mi][1], 0, 0, 0);
         }
       }
-#ifndef KK_MFMA_NO_SGB
       // prescribe the issue order: the fragments of k-step ks+1 are read from LDS WHILE the MFMAs of k-step ks run.  Left to
       // itself hipcc issues all 4 k-steps' ds_reads first and the 24 MFMAs after them, and the waves of a CU then fall into
       // lock step (everyone reads LDS, then everyone computes): measured 2860 cycles per iteration = LDS time + MFMA time.
@@ -217,7 +217,6 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         }
         __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
       }
-#endif
       if (it + 1 < nit) {
         const unsigned long long ta = TR_NOW();
         store_w((it & 1) ? Ws0 : Ws1);  // buffer last read in iteration it-1; every wave has passed that barrier

@@ -2,7 +2,8 @@
 // kk_conv_mfma4.hip (variant 4): accumulators -> fp32 LDS tile (one wave row group per pass) -> coalesced 16-byte rows with bias /
 // activation / residual / scale / accumulate / length mask, per-tile column statistics of the stored values.  ONE copy for both kernels.
 // Names taken from the including scope: a, b, bx (row-tile index), phase, nphase, q0, n0, tid, lane, wave, wr, wc, acc, Cs, red (via smem),
-// tile_live, Lout, TO, WM, MI, BM, G, NRM, v2f / fma2 / gelu_exact (kk_conv_mfma_shared.h).
+// tile_live, Lout, TO, WM, BM, G, NRM, ACC16 (accumulator layout: true = (WM / 16) x 4 blocks of 16 x 16 as in variant 4, false =
+// (WM / 32) x 2 blocks of 32 x 32 as in variant 2), v2f / fma2 / gelu_exact (kk_conv_mfma_shared.h).
   // ---- epilogue: per 128 rows, accumulators -> fp32 LDS tile -> coalesced rows --------------------------------------
   TO* ob = (TO*)a.out + (long long)b * a.obs;
   const TO* rb = a.res ? (const TO*)a.res + (long long)b * a.rbs : nullptr;
@@ -42,28 +43,29 @@
       if (pass > 0) __syncthreads();  // previous pass's readers are done with Cs
       // rows [RPP*pass, RPP*pass + RPP) of the block tile: tall tiles -> wave row `pass`; 128-row tile -> both wave rows
       if (wr == pass) {
-#ifdef KK_EPI_ACC16
-        // 16 x 16 blocks (v_mfma_f32_16x16x32_bf16): lane l holds rows 4 * (l / 16) .. + 3 of column l % 16
+        if constexpr (ACC16) {
+          // 16 x 16 blocks (v_mfma_f32_16x16x32_bf16): lane l holds rows 4 * (l / 16) .. + 3 of column l % 16
 #pragma unroll
-        for (int mi = 0; mi < WM / 16; ++mi)
+          for (int mi = 0; mi < WM / 16; ++mi)
 #pragma unroll
-          for (int ni = 0; ni < 4; ++ni) {
-            const int col = wc * 64 + ni * 16 + (lane & 15);
-            const int rbase = mi * 16 + 4 * (lane >> 4);
+            for (int ni = 0; ni < 4; ++ni) {
+              const int col = wc * 64 + ni * 16 + (lane & 15);
+              const int rbase = mi * 16 + 4 * (lane >> 4);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) Cs[(rbase + r) * CLD + col] = acc[mi][ni][r];
-          }
-#else
+              for (int r = 0; r < 4; ++r) Cs[(rbase + r) * CLD + col] = acc[mi][ni][r];
+            }
+        } else {
+          // 32 x 32 blocks (v_mfma_f32_32x32x16_bf16): lane l holds rows 8 * (r / 4) + 4 * (l / 32) + r % 4 of column l % 32
 #pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
+          for (int mi = 0; mi < WM / 32; ++mi)
 #pragma unroll
-          for (int ni = 0; ni < 2; ++ni) {
-            const int col = wc * 64 + ni * 32 + (lane & 31);
-            const int rbase = mi * 32 + 4 * (lane >> 5);
+            for (int ni = 0; ni < 2; ++ni) {
+              const int col = wc * 64 + ni * 32 + (lane & 31);
+              const int rbase = mi * 32 + 4 * (lane >> 5);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) Cs[(rbase + (r & 3) + 8 * (r >> 2)) * CLD + col] = acc[mi][ni][r];
-          }
-#endif
+              for (int r = 0; r < 16; ++r) Cs[(rbase + (r & 3) + 8 * (r >> 2)) * CLD + col] = acc[mi][ni][r];
+            }
+        }
       }
       __syncthreads();
     }

@@ -2,17 +2,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-// Matrix-instruction shape of variants 4 / 5: v_mfma_f32_16x16x32_bf16 (default) or, with -DKK_MFMA32, the round-2 v_mfma_f32_32x32x16_bf16.
-// KK_XLD = elements per LDS row of the X slab: 160 B keeps the 16-row fragments' ds_read_b128 conflict-free (see kk_conv_mfma4.hip), 144 B the 32-row ones.
-#if !defined(KK_MFMA32) && !defined(KK_EXP_MFMA16)
-#define KK_MFMA16 1
-#endif
-#ifdef KK_MFMA16
-#define KK_XLD 80
-#else
-#define KK_XLD 72
-#endif
-
 namespace {
 // Two floats WITHOUT the packed-f32 instructions (v_pk_fma_f32 ...): beside another wave's MFMAs on the same SIMD the packed forms run at
 // about half rate (variant 5's service waves showed it first; 2-6 % per fused launch of variant 4).  The files that include this are built
@@ -27,34 +16,41 @@ __device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return v2f{__builtin_
 // nn.gelu (exact erf form, modules.py / transformer feed-forward)
 __device__ __forceinline__ float gelu_exact(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 
-// KK_MFMA32(acc, a, b, ks): one v_mfma_f32_32x32x16_bf16.  -DKK_EXP_MFMA16 (build.py --exp16; TIMING ONLY, WRONG RESULTS): the same
-// operands through TWO v_mfma_f32_16x16x32_bf16 on quarter accumulators -- equal cycles, FLOPs, register and LDS traffic -- to measure what the
-// other MFMA shape does to the clock the chip holds (MI355X_MICROARCH.md, DVFS give-back item 7) before re-laying the kernels out for it.
 typedef float kk_f32x4 __attribute__((ext_vector_type(4)));
-typedef float kk_f32x8 __attribute__((ext_vector_type(8)));
-typedef float kk_f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 kk_bf16x8 __attribute__((ext_vector_type(8)));
-#ifdef KK_EXP_MFMA16
-#define KK_MFMA_PER 2
-template <int KS>
-__device__ __forceinline__ kk_f32x16 kk_mfma32(kk_bf16x8 a, kk_bf16x8 b, kk_f32x16 c) {
-  kk_f32x4 p0 = __builtin_shufflevector(c, c, 0, 1, 2, 3), p1 = __builtin_shufflevector(c, c, 4, 5, 6, 7);
-  kk_f32x4 p2 = __builtin_shufflevector(c, c, 8, 9, 10, 11), p3 = __builtin_shufflevector(c, c, 12, 13, 14, 15);
-  if (KS & 1) {
-    p2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, p2, 0, 0, 0);
-    p3 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, p3, 0, 0, 0);
-  } else {
-    p0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, p0, 0, 0, 0);
-    p1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, p1, 0, 0, 0);
+
+// One (tap, slab) iteration of the main loop of variants 4 / 5 on v_mfma_f32_16x16x32_bf16: two k-steps of 32 channels, the B fragments in
+// named registers [ks][ni] (fragment order, kk_mfma4_pack_index).  Per k-step this wave's 4 B fragments (4 x 16 columns) stay in registers
+// while the MI16 A fragments stream through from the X slab in LDS; the B registers are refilled from fn (the next iteration's fragments)
+// as soon as their MFMAs are issued.  Issue order: the A fragment of row block mi + 1 is read from LDS while the 4 MFMAs of row block mi
+// run, and the four global loads that refill a k-step's B registers go out right behind that k-step's MFMAs.
+// Names taken from the including scope: acc (kk_f32x4 [MI16][4]), xa (this lane's row and k-group at the tap's row shift), fn, MI16, XLD.
+// Macros, not functions: an always_inline function of the same body changes the kernels' register allocation.
+#define KK_MFMA_KSTEP(KS, B0, B1, B2, B3)                                                                                                  \
+  {                                                                                                                                          \
+    const kk_bf16x8 b0 = __builtin_bit_cast(kk_bf16x8, B0), b1 = __builtin_bit_cast(kk_bf16x8, B1);                                          \
+    const kk_bf16x8 b2 = __builtin_bit_cast(kk_bf16x8, B2), b3 = __builtin_bit_cast(kk_bf16x8, B3);                                          \
+    _Pragma("unroll") for (int mi = 0; mi < MI16; ++mi) {                                                                                    \
+      const kk_bf16x8 av = *(const kk_bf16x8*)(xa + mi * 16 * XLD + (KS) * 32);                                                              \
+      acc[mi][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, b0, acc[mi][0], 0, 0, 0);                                                     \
+      acc[mi][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, b1, acc[mi][1], 0, 0, 0);                                                     \
+      acc[mi][2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, b2, acc[mi][2], 0, 0, 0);                                                     \
+      acc[mi][3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, b3, acc[mi][3], 0, 0, 0);                                                     \
+    }                                                                                                                                        \
+    B0 = fn[((KS) * 4 + 0) * 64];                                                                                                            \
+    B1 = fn[((KS) * 4 + 1) * 64];                                                                                                            \
+    B2 = fn[((KS) * 4 + 2) * 64];                                                                                                            \
+    B3 = fn[((KS) * 4 + 3) * 64];                                                                                                            \
   }
-  const kk_f32x8 lo = __builtin_shufflevector(p0, p1, 0, 1, 2, 3, 4, 5, 6, 7), hi = __builtin_shufflevector(p2, p3, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
-}
-#else
-#define KK_MFMA_PER 1
-template <int KS>
-__device__ __forceinline__ kk_f32x16 kk_mfma32(kk_bf16x8 a, kk_bf16x8 b, kk_f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-#endif
+#define KK_MFMA_ITER(Q00, Q01, Q02, Q03, Q10, Q11, Q12, Q13)                                                                               \
+  KK_MFMA_KSTEP(0, Q00, Q01, Q02, Q03)                                                                                                     \
+  KK_MFMA_KSTEP(1, Q10, Q11, Q12, Q13)                                                                                                     \
+  __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                                                                                         \
+  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                                                         \
+    _Pragma("unroll") for (int j = 0; j < MI16; ++j) {                                                                                       \
+      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                                                                                     \
+      if (ks * MI16 + j + 2 < 2 * MI16) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                                   \
+    }                                                                                                                                        \
+    __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);                                                                                       \
+  }
 }  // namespace

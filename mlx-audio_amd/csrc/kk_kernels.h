@@ -79,7 +79,19 @@ int kk_launch_conv_mfma4(const KKMfmaArgs& a, int B, int out_dtype, hipStream_t 
 // variant 5 (kk_conv_mfma5.hip): wave-specialised persistent kernel (4 MFMA waves + 4 service waves per CU) for stride-1 convolutions
 bool kk_mfma5_eligible(const KKMfmaArgs& a, int out_dtype);
 int kk_launch_conv_mfma5(const KKMfmaArgs& a, int B, int out_dtype, hipStream_t st);
-long long kk_mfma4_pack_index(int tap, int cout, int k, int CoutP, int CinP);
+// element index of W[tap][cout][k] in the fragment-order weight pack of variants 4 / 5: [tap][n block (128 columns)][chunk (64 k)]
+// [wc (2 x 64 columns)][ks (2 x 32 k)][ni (4 x 16 columns)][lane = k-group * 16 + column][8]: one 1 KiB v_mfma_f32_16x16x32_bf16 B fragment
+// per (wc, ks, ni).  The host packers call the function; the device re-layout (kk_launch_pack_w_frag) expands the macro in place, because
+// a call compiles that kernel to different code (the function is optimised on its own before it is inlined).
+#define KK_MFMA4_PACK_INDEX(tap, cout, k, CoutP, CinP)                                                              \
+  ({                                                                                                                \
+    const int nbk = (cout) / 128, cr = (cout) % 128, chunk = (k) / 64, kr = (k) % 64;                               \
+    const long long blk = ((long long)(tap) * ((CoutP) / 128) + nbk) * ((CinP) / 64) + chunk;                       \
+    const int wc = cr / 64, ni = (cr % 64) / 16, ks = kr / 32, kq = (kr % 32) / 8, j = kr % 8;                      \
+    const int lane = kq * 16 + (cr % 16);                                                                           \
+    blk * (128 * 64) + ((long long)(((wc * 2 + ks) * 4 + ni) * 64 + lane)) * 8 + j;                                 \
+  })
+inline long long kk_mfma4_pack_index(int tap, int cout, int k, int CoutP, int CinP) { return KK_MFMA4_PACK_INDEX(tap, cout, k, CoutP, CinP); }
 int kk_launch_pack_w_frag(const void* w, void* wf, int Kw, int CoutP, int CinP, hipStream_t st);
 
 // ---- normalisation family (kk_norm.hip)

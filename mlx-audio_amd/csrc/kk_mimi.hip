@@ -25,6 +25,7 @@
 #include "../../include/kokoro_hip.h"
 #include "kk_common.h"
 #include "kk_kernels.h"
+#include "kk_host.h"
 
 namespace {
 
@@ -366,13 +367,6 @@ __global__ __launch_bounds__(256) void elu_rows_kernel(const float* x, long long
 
 // ------------------------------------------------------------------------------------------------------------- host
 int rup(int v, int m) { return (v + m - 1) / m * m; }
-uint16_t f32_to_bf16_rne(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
 
 struct Packer {
   kk_mimi* m;
@@ -472,7 +466,6 @@ struct Run {
   bool dry;
   bool oom = false;
   int adt = -1;  // activation dtype of this run (-1: the model's)
-  bool no_lin_rows = false;  // (A/B: the generic conv kernel for the few-row layers too)
   float* elu_tmp = nullptr;  // dense scratch for an ELU'd input of the few-rows kernel (streaming steps allocate it)
   size_t elu_floats = 0;
   void* raw(size_t bytes) {
@@ -512,7 +505,7 @@ struct Run {
     // few rows per item (the streaming steps): the weight-streaming kernel instead of the 64-row conv tile.  Chosen by the rows per ITEM,
     // never by B (batch invariance).  Forms: linear; causal conv over contiguous rows (pad 0, stride 1, pitch == Cin); transposed conv k = 2 s.
     {
-      const bool f32io = x.dtype == KK_F32 && out.dtype == KK_F32 && dil == 1 && pad == 0 && w.Cout >= 32 && !no_lin_rows &&
+      const bool f32io = x.dtype == KK_F32 && out.dtype == KK_F32 && dil == 1 && pad == 0 && w.Cout >= 32 &&
                          (act_ == KK_ACT_NONE || act_ == KK_ACT_GELU_TANH) && (in_act == 0 || (in_act == KK_ACT_ELU && elu_tmp));
       const bool lin = f32io && !transposed && stride == 1 && x.ld == w.Cin && x.rows == out.rows + w.K - 1 && out.rows <= LR_MAX_ROWS;
       const bool ctr = f32io && transposed && w.K == 2 * stride && x.ld == w.Cin && out.rows == x.rows * stride && x.rows >= 2 &&

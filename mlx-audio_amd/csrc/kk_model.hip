@@ -14,6 +14,7 @@
 #include "../../include/kokoro_hip.h"
 #include "kk_common.h"
 #include "kk_kernels.h"
+#include "kk_host.h"
 
 // ------------------------------------------------------------------------------------------------
 // error plumbing
@@ -283,14 +284,6 @@ static float f16_to_f32(uint16_t h) {
   float r;
   memcpy(&r, &u, 4);
   return r;
-}
-
-static uint16_t f32_to_bf16_rne(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN stays NaN
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
 }
 
 static std::string normalise_name(const std::string& in) {

@@ -40,6 +40,25 @@ def test_library_reads_no_environment_switches():
     assert not found, found
 
 
+def test_library_has_no_compile_time_switches():
+    # one shipped form per kernel: the only macros the sources test are the ABI header's guard, C++ detection and two instrumentation
+    # builds (build.py --trace; tools/gridbar/gemvm_bench.hip), so no alternative form can sit uncompiled next to the product one
+    allowed = {"__cplusplus", "KOKORO_HIP_H", "KK_MFMA_TRACE", "KK_TS_PER_WG"}
+    tested = set()
+    for sub in ("mlx-audio_amd/csrc", "include"):
+        for dirpath, _, files in os.walk(os.path.join(ROOT, sub)):
+            for f in files:
+                if f.endswith((".hip", ".h", ".hpp", ".cpp", ".cc", ".c", ".inc")):
+                    for line in open(os.path.join(dirpath, f)):
+                        m = re.match(r"\s*#\s*(ifdef|ifndef|if|elif)\b(.*)", line)
+                        if m:  # every name in the condition, defined(X) included
+                            tested |= set(re.findall(r"[A-Za-z_]\w*", m.group(2).split("//")[0].split("/*")[0])) - {"defined"}
+    assert tested <= allowed, sorted(tested - allowed)
+    # build.py builds the product library and the --trace side build, nothing else
+    src = open(os.path.join(ROOT, "mlx-audio_amd", "build.py")).read()
+    assert set(re.findall(r"""["'](--[a-z][\w-]*)["']""", src)) <= {"--trace", "--force"}
+
+
 def test_kk_create_rejects_bad_configs_without_a_gpu():
     from mlx_audio_amd.engine import make_kk_config
 
