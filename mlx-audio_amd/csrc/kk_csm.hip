@@ -17,7 +17,7 @@
 
 #include "../../include/kokoro_hip.h"
 #include "kk_common.h"
-#include "kk_kernels.h"
+#include "kk_host.h"
 
 namespace {
 
@@ -35,19 +35,14 @@ struct Lin {  // generic-kernel pack [1][Cin][ldw]
   int nsub = 0;  // 0 = no fragment pack (K not a multiple of 32)
   int ks = 1;    // split-K slices of a deep projection (K >= 4096): partial tiles + combine
 };
-struct Vec {
-  size_t off = 0;
-  size_t n = 0;
-  const float* p = nullptr;
-};
 struct LlamaLayer {
   Lin qkv, o, gu, down;
-  Vec n1, n2;
+  ArenaVec n1, n2;
 };
 struct Stack {
   kk_llama_args a;
   std::vector<LlamaLayer> layers;
-  Vec norm, rope;  // rope: [max_pos][hd/2][2] cos, sin
+  ArenaVec norm, rope;  // rope: [max_pos][hd/2][2] cos, sin
   float* kc = nullptr;  // [layers][maxB][max_pos][KV*hd]
   float* vc = nullptr;
   int max_pos = 0, offset = 0;
@@ -59,30 +54,21 @@ struct Stack {
 
 struct kk_csm {
   kk_csm_config cfg;
-  std::map<std::string, std::vector<float>> host;
-  std::vector<float> pack;
-  float* dev = nullptr;
+  WeightArena arena;  // fp32 parameters; arena.dev is shared by kk_csm_share copies
   bool finalized = false;
   int wdt = KK_F32;              // weight storage of the single-token steps (KK_F32 / KK_BF16)
   std::vector<uint16_t> packb;   // host staging of the bf16 copies
   uint16_t* devb = nullptr;
   Stack bb, dec;
-  Vec text_emb, audio_emb;
+  ArenaVec text_emb, audio_emb;
   Lin proj, c0_head;
   std::vector<Lin> audio_head;
   int max_batch = 0;
   float* dbg_logits = nullptr;  // [n_cb][maxB][V] of the last frame
   float* proj_table = nullptr;  // bf16 weight mode: projection(audio_embeddings) [n_cb * V][decoder hidden], computed once at finalize (weights: shared by kk_csm_share)
   // graph replay of the single-token frame step (kk_csm_set_graph_mode)
-  struct GraphEntry {
-    std::vector<unsigned long long> key;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    int seen = 0;
-  };
   bool graph_mode = false;
-  std::vector<GraphEntry> graphs;
-  hipStream_t cap_stream = nullptr;
+  GraphCache graphs{8};  // a kk_csm_share copy starts with an empty cache
   // kk_csm_reset_caches / kk_csm_set_padding take no stream: what they change on the device is applied on the NEXT frame's stream (a
   // synchronous hipMemset / hipMemcpy here would touch the legacy stream and break another thread's graph capture)
   bool reset_pending = false, pad_pending = false;
@@ -91,8 +77,6 @@ struct kk_csm {
 };
 
 namespace {
-
-int rup(int v, int m) { return (v + m - 1) / m * m; }
 
 // kk_csm_debug_timestamps: in-kernel wall-clock marks (100 MHz) of the instrumented kernels, 8 words per launch in launch order:
 // [class id, earliest workgroup start, latest workgroup end, workgroup 0 after its input loads, workgroup 0's start / shader clock at start / end / shader
@@ -1115,34 +1099,13 @@ int launch_gemmp(const GPArgs& g, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------------------- host
+// host tensors are erased as soon as they are packed: peak host memory stays near one copy of the 1.6 B parameters
 struct Packer {
   kk_csm* m;
-  std::string err;
-  size_t alloc(size_t n) {
-    const size_t off = (m->pack.size() + 63) & ~(size_t)63;
-    m->pack.resize(off + n, 0.f);
-    return off;
-  }
-  const std::vector<float>* get(const std::string& name, size_t n) {
-    auto it = m->host.find(name);
-    if (it == m->host.end()) {
-      if (err.empty()) err = "missing parameter: " + name;
-      return nullptr;
-    }
-    if (it->second.size() != n) {
-      if (err.empty()) err = "unexpected size for " + name;
-      return nullptr;
-    }
-    return &it->second;
-  }
-  Vec vec(const std::string& name, size_t n) {
-    Vec r;
-    const std::vector<float>* v = get(name, n);
-    if (!v) return r;
-    r.n = n;
-    r.off = alloc(n);
-    memcpy(&m->pack[r.off], v->data(), n * 4);
-    m->host.erase(name);
+  WeightArena& a;  // m->arena
+  ArenaVec vec(const std::string& name, size_t n) {
+    const ArenaVec r = a.vec(name, n);
+    a.host.erase(name);
     return r;
   }
   // nn.Linear weights [O_i][I] stacked along the output axis -> one [I][ldw] pack; `transposed_src`: the source is [I][O] (audio_head)
@@ -1151,30 +1114,30 @@ struct Packer {
     int O = 0;
     for (int o : outs) O += o;
     l.Cin = I; l.Cout = O; l.ldw = rup(O, 64);
-    l.off = alloc((size_t)I * l.ldw);
+    l.off = a.alloc((size_t)I * l.ldw);
     int base = 0;
     for (size_t k = 0; k < outs.size(); ++k) {
       const float* src = raw;
       if (!raw) {
-        const std::vector<float>* w = get(names[k], (size_t)outs[k] * I);
+        const HostTensor* w = a.get(names[k], (size_t)outs[k] * I);
         if (!w) return l;
-        src = w->data();
+        src = w->d.data();
       }
-      float* dst = &m->pack[l.off];
+      float* dst = &a.pack[l.off];
       if (raw) {  // [I][O]
         for (int i = 0; i < I; ++i)
           for (int o = 0; o < outs[k]; ++o) dst[(size_t)i * l.ldw + base + o] = src[(size_t)i * outs[k] + o];
       } else {
         for (int o = 0; o < outs[k]; ++o)
           for (int i = 0; i < I; ++i) dst[(size_t)i * l.ldw + base + o] = src[(size_t)o * I + i];
-        m->host.erase(names[k]);
+        a.host.erase(names[k]);
       }
       base += outs[k];
     }
     if (m->wdt == KK_BF16) {
       // bf16 weight mode: the matrix IS its bf16 rounding everywhere (the fp32 pack the multi-token prompt block reads holds the rounded
       // values too, so a prompt block and single-token steps multiply by identical weights); lossless for a bf16 checkpoint.
-      float* dst = &m->pack[l.off];
+      float* dst = &a.pack[l.off];
       for (size_t e = 0; e < (size_t)I * l.ldw; ++e) {
         uint32_t u;
         memcpy(&u, &dst[e], 4);
@@ -1246,8 +1209,8 @@ void pack_stack(Packer& P, const std::string& name, Stack& st, int max_pos) {
   llama3_theta(a, th);
   st.max_pos = max_pos;
   st.rope.n = (size_t)max_pos * (hd / 2) * 2;
-  st.rope.off = P.alloc(st.rope.n);
-  float* r = &P.m->pack[st.rope.off];
+  st.rope.off = P.a.alloc(st.rope.n);
+  float* r = &P.a.pack[st.rope.off];
   for (int pos = 0; pos < max_pos; ++pos)
     for (int i = 0; i < hd / 2; ++i) {
       const float ang = (float)pos * th[i];  // einsum in float32 (attention.py:56-58)
@@ -1257,31 +1220,25 @@ void pack_stack(Packer& P, const std::string& name, Stack& st, int max_pos) {
 }
 
 void resolve(kk_csm* m, Lin& l) {
-  l.w = m->dev + l.off;
+  l.w = m->arena.dev + l.off;
   l.wm = (m->devb && l.nsub) ? m->devb + l.moff : nullptr;
 }
-void resolve(kk_csm* m, Vec& v) { v.p = v.n ? m->dev + v.off : nullptr; }
+void resolve(kk_csm* m, ArenaVec& v) { m->arena.resolve(v); }
 void resolve(kk_csm* m, Stack& st) {
   for (auto& L : st.layers) { resolve(m, L.qkv); resolve(m, L.o); resolve(m, L.gu); resolve(m, L.down); resolve(m, L.n1); resolve(m, L.n2); }
   resolve(m, st.norm); resolve(m, st.rope);
 }
 
-struct Run {
+struct Run : Workspace {
   kk_csm* m;
   hipStream_t st;
   int B;
-  char* base;
-  size_t cap, used;
-  bool dry, oom;
   float* skinny_scratch = nullptr;  // partial sums of the skinny GEMM
   size_t skinny_floats = 0;
-  float* f32(size_t n) {
-    const size_t off = (used + 255) & ~(size_t)255;
-    used = off + n * 4;
-    if (dry) return nullptr;
-    if (used > cap) { oom = true; return nullptr; }
-    return (float*)(base + off);
+  Run(kk_csm* m_, hipStream_t st_, int B_, void* ws, size_t ws_bytes) : m(m_), st(st_), B(B_) {
+    base = (char*)ws; cap = ws_bytes; dry = ws == nullptr;
   }
+  float* f32(size_t n) { return (float*)raw(n * 4); }
   // out[b][row][:] = W x[b][row][:] (+ res); x rows: `rows` per item at pitch `xbs` elements between items
   // `nw` / `xn`: RMSNorm of the result rows, launched right behind.
   int lin(const Lin& w, const float* x, long long xbs, int rows, float* out, long long obs, const float* res, const float* nw = nullptr,
@@ -1409,12 +1366,6 @@ int launch_gemv(const Lin& w, int pro, int epi, FGArgs a, int Mtot, hipStream_t 
   return launch_gemvm(w, pro, epi, a, Mtot, st);
 }
 
-#define CS_TRY(x)          \
-  do {                     \
-    const int rc__ = (x);  \
-    if (rc__ != 0) return rc__; \
-  } while (0)
-
 // h [B][S][D] (updated in place) -> out [B][S][D] = final norm; appends S positions to the stack's cache at st.offset
 int stack_forward(Run& r, Stack& st, float* h, int S, int offset, float* out) {
   const kk_llama_args& a = st.a;
@@ -1436,7 +1387,7 @@ int stack_forward(Run& r, Stack& st, float* h, int S, int offset, float* out) {
     const LlamaLayer& L = st.layers[l];
     float* kc = st.kc + (size_t)l * r.m->max_batch * st.max_pos * KV * hd;
     float* vc = st.vc + (size_t)l * r.m->max_batch * st.max_pos * KV * hd;
-    CS_TRY(r.lin(L.qkv, x, (long long)S * D, S, qkv, (long long)S * W, nullptr));
+    KK_TRY(r.lin(L.qkv, x, (long long)S * D, S, qkv, (long long)S * W, nullptr));
     if (!r.dry) {
       if (S == 1) {  // single-token step: RoPE + cache append inside the attention kernel
         hipLaunchKernelGGL(attn_cache_kernel<true>, dim3(S, H, B), dim3(128), attn_lds_bytes(st.max_pos, hd), r.st, qkv, S, H, KV, hd, st.pos_dev,
@@ -1451,8 +1402,8 @@ int stack_forward(Run& r, Stack& st, float* h, int S, int offset, float* out) {
       }
     }
     // h += o(att); x = RMSNorm(h) (post_attention_layernorm)
-    CS_TRY(r.lin(L.o, att, (long long)S * H * hd, S, h, (long long)S * D, h, L.n2.p, x, a.rms_eps));
-    CS_TRY(r.lin(L.gu, x, (long long)S * D, S, gu, (long long)S * 2 * I, nullptr));
+    KK_TRY(r.lin(L.o, att, (long long)S * H * hd, S, h, (long long)S * D, h, L.n2.p, x, a.rms_eps));
+    KK_TRY(r.lin(L.gu, x, (long long)S * D, S, gu, (long long)S * 2 * I, nullptr));
     // h += down(silu(gate) * up); then the NEXT consumer's norm: the next layer's input_layernorm -> x, or the stack's final norm -> out
     const bool lastl = l + 1 == a.num_layers;
     const float* nw = lastl ? st.norm.p : st.layers[l + 1].n1.p;
@@ -1462,7 +1413,7 @@ int stack_forward(Run& r, Stack& st, float* h, int S, int offset, float* out) {
       hipLaunchKernelGGL(swiglu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r.st, gu, I, n, act);
       KK_CHECK_LAUNCH();
     }
-    CS_TRY(r.lin(L.down, act, (long long)S * I, S, h, (long long)S * D, h, nw, xn, a.rms_eps));
+    KK_TRY(r.lin(L.down, act, (long long)S * I, S, h, (long long)S * D, h, nw, xn, a.rms_eps));
   }
   return 0;
 }
@@ -1497,7 +1448,7 @@ int stack_step(Run& r, Stack& st, float* h, int rows, int offset, const FGArgs* 
     memset(&g, 0, sizeof g);
     g.x = h; g.xrs = D; g.nw = L.n1.p; g.eps = a.rms_eps; g.out = qkv; g.ors = W;
     if (l == 0 && gather) { g.codes = gather->codes; g.cstride = gather->cstride; g.cb = gather->cb; g.V = gather->V; g.emb = gather->emb; g.gather_out = h; }
-    CS_TRY(launch_gemv(L.qkv, 1, 0, g, M, r.st));
+    KK_TRY(launch_gemv(L.qkv, 1, 0, g, M, r.st));
     if (rows == 1 && st.max_pos <= 64 && H / KV <= 8) {
       const size_t lds = attn_step_lds_bytes(st.max_pos, hd, H / KV);
       static KKDevOnce attr;
@@ -1552,21 +1503,21 @@ int stack_step(Run& r, Stack& st, float* h, int rows, int offset, const FGArgs* 
     }
     memset(&g, 0, sizeof g);
     g.x = att; g.xrs = (long long)H * hd; g.res = h; g.rrs = D; g.out = h; g.ors = D;
-    CS_TRY(launch_gemv(L.o, 0, 1, g, M, r.st));
+    KK_TRY(launch_gemv(L.o, 0, 1, g, M, r.st));
     memset(&g, 0, sizeof g);
     g.x = h; g.xrs = D; g.nw = L.n2.p; g.eps = a.rms_eps; g.out = gu; g.ors = 2 * I;
-    CS_TRY(launch_gemv(L.gu, 1, 0, g, M, r.st));
+    KK_TRY(launch_gemv(L.gu, 1, 0, g, M, r.st));
     memset(&g, 0, sizeof g);
     const int KS = L.down.ks;
     if (KS > 1) {  // deep projection: K slices over workgroups, then one small combine (h += sum of the slices)
       g.x = gu; g.xrs = 2 * I; g.out = part; g.ors = D; g.pss = (long long)M * D;
-      CS_TRY(launch_gemv(L.down, 2, 2, g, M, r.st));
+      KK_TRY(launch_gemv(L.down, 2, 2, g, M, r.st));
       const long long n = (long long)M * D;
       hipLaunchKernelGGL(combine_slices_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r.st, part, KS, n, n, h, ts_slot());
       KK_CHECK_LAUNCH();
     } else {
       g.x = gu; g.xrs = 2 * I; g.res = h; g.rrs = D; g.out = h; g.ors = D;
-      CS_TRY(launch_gemv(L.down, 2, 1, g, M, r.st));
+      KK_TRY(launch_gemv(L.down, 2, 1, g, M, r.st));
     }
   }
   return 0;
@@ -1601,14 +1552,14 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, float temp, i
   const float* last_h;   // the backbone's final-normed last position of every item
   long long last_rs;     // its item pitch
   if (fast && heads_fast && S == 1) {
-    CS_TRY(stack_step(r, m->bb, h, 1, m->bb.offset));
+    KK_TRY(stack_step(r, m->bb, h, 1, m->bb.offset));
     if (!r.dry) {
       hipLaunchKernelGGL(rmsnorm_kernel, dim3(B), dim3(256), 0, r.st, h, m->bb.norm.p, D, c.backbone.rms_eps, hn);
       KK_CHECK_LAUNCH();
     }
     last_h = hn; last_rs = D;
   } else {
-    CS_TRY(stack_forward(r, m->bb, h, S, m->bb.offset, hn));
+    KK_TRY(stack_forward(r, m->bb, h, S, m->bb.offset, hn));
     last_h = hn ? hn + (size_t)(S - 1) * D : nullptr;  // row S-1 of every item (pitch S*D)
     last_rs = (long long)S * D;
   }
@@ -1621,8 +1572,8 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, float temp, i
       FGArgs g;
       memset(&g, 0, sizeof g);
       g.x = last_h; g.xrs = last_rs; g.out = logits; g.ors = V;
-      CS_TRY(launch_gemv(m->c0_head, 0, 0, g, B, r.st));
-      CS_TRY(launch_sample(logits, V, temp, top_k, uniforms, ncb, codes, ncb, B, r.st));
+      KK_TRY(launch_gemv(m->c0_head, 0, 0, g, B, r.st));
+      KK_TRY(launch_sample(logits, V, temp, top_k, uniforms, ncb, codes, ncb, B, r.st));
     }
     int rows = 2, dpos = 0;
     for (int i = 1; i < ncb; ++i) {
@@ -1639,9 +1590,9 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, float temp, i
         memset(&g, 0, sizeof g);
         g.x = last_h; g.xrs = last_rs; g.codes = codes + (i - 1); g.cstride = ncb; g.cb = i - 1; g.V = V; g.rows = rows; g.emb = m->audio_emb.p;
         g.out = pin; g.ors = Dd;
-        CS_TRY(launch_gemv(m->proj, 3, 0, g, B * rows, r.st));
+        KK_TRY(launch_gemv(m->proj, 3, 0, g, B * rows, r.st));
       }
-      CS_TRY(stack_step(r, m->dec, pin, rows, dpos, tabled ? &gat : nullptr));
+      KK_TRY(stack_step(r, m->dec, pin, rows, dpos, tabled ? &gat : nullptr));
       if (r.used > peak) peak = r.used;
       dpos += rows;
       if (!r.dry) {
@@ -1649,15 +1600,15 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, float temp, i
         FGArgs g;
         memset(&g, 0, sizeof g);
         g.x = pin + (size_t)(rows - 1) * Dd; g.xrs = (long long)rows * Dd; g.nw = m->dec.norm.p; g.eps = c.decoder.rms_eps; g.out = logits; g.ors = V;
-        CS_TRY(launch_gemv(m->audio_head[i - 1], 1, 0, g, B, r.st));
-        CS_TRY(launch_sample(logits, V, temp, top_k, uniforms ? uniforms + i : nullptr, ncb, codes + i, ncb, B, r.st));
+        KK_TRY(launch_gemv(m->audio_head[i - 1], 1, 0, g, B, r.st));
+        KK_TRY(launch_sample(logits, V, temp, top_k, uniforms ? uniforms + i : nullptr, ncb, codes + i, ncb, B, r.st));
       }
       rows = 1;
     }
   } else {
-  CS_TRY(r.lin(m->c0_head, last_h, last_rs, 1, logits, V, nullptr));
+  KK_TRY(r.lin(m->c0_head, last_h, last_rs, 1, logits, V, nullptr));
   if (!r.dry) {
-    CS_TRY(launch_sample(logits, V, temp, top_k, uniforms, ncb, codes, ncb, B, r.st));
+    KK_TRY(launch_sample(logits, V, temp, top_k, uniforms, ncb, codes, ncb, B, r.st));
     // curr = [last_h, embed_audio(0, c0)]
     hipLaunchKernelGGL(copy_rows_kernel, dim3(B), dim3(256), 0, r.st, last_h, last_rs, curr, (long long)2 * D, D);
     KK_CHECK_LAUNCH();
@@ -1667,15 +1618,15 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, float temp, i
   int rows = 2, dpos = 0;
   for (int i = 1; i < ncb; ++i) {
     r.used = inner;
-    CS_TRY(r.lin(m->proj, curr, (long long)rows * D, rows, pin, (long long)rows * Dd, nullptr));
-    CS_TRY(stack_forward(r, m->dec, pin, rows, dpos, dn));
+    KK_TRY(r.lin(m->proj, curr, (long long)rows * D, rows, pin, (long long)rows * Dd, nullptr));
+    KK_TRY(stack_forward(r, m->dec, pin, rows, dpos, dn));
     if (r.used > peak) peak = r.used;
     dpos += rows;
     const float* dl = dn ? dn + (size_t)(rows - 1) * Dd : nullptr;
     if (!r.dry && m->dbg_logits) logits = m->dbg_logits + (size_t)i * m->max_batch * V;
-    CS_TRY(r.lin(m->audio_head[i - 1], dl, (long long)rows * Dd, 1, logits, V, nullptr));
+    KK_TRY(r.lin(m->audio_head[i - 1], dl, (long long)rows * Dd, 1, logits, V, nullptr));
     if (!r.dry) {
-      CS_TRY(launch_sample(logits, V, temp, top_k, uniforms ? uniforms + i : nullptr, ncb, codes + i, ncb, B, r.st));
+      KK_TRY(launch_sample(logits, V, temp, top_k, uniforms ? uniforms + i : nullptr, ncb, codes + i, ncb, B, r.st));
       hipLaunchKernelGGL(embed_audio_kernel, dim3(B), dim3(256), 0, r.st, codes + i, ncb, m->audio_emb.p, i, V, D, curr, 1, 0);
       KK_CHECK_LAUNCH();
     }
@@ -1727,8 +1678,8 @@ extern "C" int kk_csm_create(const kk_csm_config* cfg, kk_csm** out) {
   if (!cfg || !out) return kk_fail("kk_csm_create: null argument");
   if (cfg->audio_num_codebooks < 1 || cfg->audio_vocab_size < 1 || cfg->audio_vocab_size > 8192 || cfg->text_vocab_size < 1 || cfg->max_seq_len < 2)
     return kk_fail("kk_csm_create: bad configuration");
-  CS_TRY(check_llama(cfg->backbone));
-  CS_TRY(check_llama(cfg->decoder));
+  KK_TRY(check_llama(cfg->backbone));
+  KK_TRY(check_llama(cfg->decoder));
   kk_csm* m = new kk_csm();
   m->cfg = *cfg;
   m->bb.a = cfg->backbone;
@@ -1752,17 +1703,15 @@ extern "C" int kk_csm_share(const kk_csm* m, kk_csm** out) {
   }
   c->max_batch = 0;
   c->dbg_logits = nullptr;
-  c->graphs.clear();
   c->reset_pending = c->pad_pending = false;
   c->pad_host.clear();
-  c->cap_stream = nullptr;
   *out = c;
   return 0;
 }
 
 extern "C" void kk_csm_destroy(kk_csm* m) {
   if (!m) return;
-  if (m->dev && !m->weights_of) (void)hipFree(m->dev);
+  if (m->arena.dev && !m->weights_of) (void)hipFree(m->arena.dev);
   if (m->devb && !m->weights_of) (void)hipFree(m->devb);
   if (m->proj_table && !m->weights_of) (void)hipFree(m->proj_table);
   for (Stack* s : {&m->bb, &m->dec}) {
@@ -1772,11 +1721,7 @@ extern "C" void kk_csm_destroy(kk_csm* m) {
   if (m->dbg_logits) (void)hipFree(m->dbg_logits);
   if (m->bb.pos_dev) (void)hipFree(m->bb.pos_dev);
   if (m->bb.pad_dev) (void)hipFree(m->bb.pad_dev);
-  for (auto& g : m->graphs) {
-    if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    if (g.graph) (void)hipGraphDestroy(g.graph);
-  }
-  if (m->cap_stream) (void)hipStreamDestroy(m->cap_stream);
+  m->graphs.clear();
   delete m;
 }
 
@@ -1797,7 +1742,9 @@ extern "C" int kk_csm_load_tensor(kk_csm* m, const char* name, const int64_t* sh
   if (m->finalized) return kk_fail("kk_csm_load_tensor: model already finalized");
   size_t n = 1;
   for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
-  m->host[name].assign(data, data + n);
+  HostTensor& t = m->arena.host[name];
+  t.d.assign(data, data + n);
+  t.shape.assign(shape, shape + ndim);
   return 0;
 }
 
@@ -1805,7 +1752,7 @@ extern "C" int kk_csm_finalize(kk_csm* m, void* stream) {
   if (!m) return kk_fail("kk_csm_finalize: null model");
   if (m->finalized) return kk_fail("kk_csm_finalize: already finalized");
   const kk_csm_config& c = m->cfg;
-  Packer P{m, ""};
+  Packer P{m, m->arena};
   const int D = c.backbone.hidden, Dd = c.decoder.hidden, V = c.audio_vocab_size, ncb = c.audio_num_codebooks;
   pack_stack(P, "backbone", m->bb, c.max_seq_len);
   pack_stack(P, "decoder", m->dec, ncb + 1);
@@ -1815,20 +1762,13 @@ extern "C" int kk_csm_finalize(kk_csm* m, void* stream) {
   m->c0_head = P.linear({"codebook0_head.weight"}, {V}, D);
   m->audio_head.resize(ncb > 1 ? ncb - 1 : 0);
   if (ncb > 1) {
-    const std::vector<float>* ah = P.get("audio_head", (size_t)(ncb - 1) * Dd * V);
+    const HostTensor* ah = P.a.get("audio_head", (size_t)(ncb - 1) * Dd * V);
     if (ah)
-      for (int i = 0; i < ncb - 1; ++i) m->audio_head[i] = P.linear({}, {V}, Dd, ah->data() + (size_t)i * Dd * V);  // [Dd][V] used as x @ W
+      for (int i = 0; i < ncb - 1; ++i) m->audio_head[i] = P.linear({}, {V}, Dd, ah->d.data() + (size_t)i * Dd * V);  // [Dd][V] used as x @ W
   }
-  if (!P.err.empty()) return kk_fail(("kk_csm_finalize: " + P.err).c_str());
-  if (hipMalloc((void**)&m->dev, m->pack.size() * sizeof(float)) != hipSuccess) return kk_fail("kk_csm_finalize: hipMalloc failed");
-  if (hipMemcpyAsync(m->dev, m->pack.data(), m->pack.size() * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess)
-    return kk_fail("kk_csm_finalize: upload failed");
-  if (!m->packb.empty()) {
-    if (hipMalloc((void**)&m->devb, m->packb.size() * 2) != hipSuccess) return kk_fail("kk_csm_finalize: hipMalloc failed");
-    if (hipMemcpyAsync(m->devb, m->packb.data(), m->packb.size() * 2, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess)
-      return kk_fail("kk_csm_finalize: upload failed");
-  }
-  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return kk_fail("kk_csm_finalize: stream sync failed");
+  if (!P.a.err.empty()) return kk_failf("kk_csm_finalize: %s", P.a.err.c_str());
+  KK_TRY(m->arena.upload((hipStream_t)stream, "kk_csm_finalize"));
+  if (!m->packb.empty()) KK_TRY(kk_upload(m->packb, &m->devb, (hipStream_t)stream, "kk_csm_finalize"));
   resolve(m, m->bb); resolve(m, m->audio_emb); resolve(m, m->proj);
   if (m->proj.wm && ncb > 1) {
     // projection(audio_embeddings): every input the depth decoder's later steps can see (sesame.py:373-392: curr_h = projection(embed(c_{i-1})))
@@ -1841,9 +1781,6 @@ extern "C" int kk_csm_finalize(kk_csm* m, void* stream) {
   }
   resolve(m, m->bb); resolve(m, m->dec); resolve(m, m->text_emb); resolve(m, m->audio_emb); resolve(m, m->proj); resolve(m, m->c0_head);
   for (auto& l : m->audio_head) resolve(m, l);
-  m->host.clear();
-  std::vector<float>().swap(m->pack);
-  std::vector<uint16_t>().swap(m->packb);
   m->finalized = true;
   return 0;
 }
@@ -1853,10 +1790,6 @@ extern "C" int kk_csm_setup_caches(kk_csm* m, int max_batch) {
   if (!m || !m->finalized || max_batch < 1) return kk_fail("kk_csm_setup_caches: bad argument");
   // captured frame steps have the OLD cache / logits pointers baked in: drop every graph before the buffers they point at are freed
   // (a replay after a second setup_caches would read and write freed memory)
-  for (auto& g : m->graphs) {
-    if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    if (g.graph) (void)hipGraphDestroy(g.graph);
-  }
   m->graphs.clear();
   (void)hipDeviceSynchronize();  // nothing in flight may still use the caches about to be freed
   for (Stack* s : {&m->bb, &m->dec}) {
@@ -1906,7 +1839,7 @@ extern "C" int kk_csm_position(const kk_csm* m) { return m ? m->bb.offset : -1; 
 
 extern "C" size_t kk_csm_workspace_bytes(kk_csm* m, int B, int S) {
   if (!m || !m->finalized || B <= 0 || S <= 0) return 0;
-  Run r{m, nullptr, B, nullptr, 0, 0, true, false};
+  Run r(m, nullptr, B, nullptr, 0);
   if (run_frame(r, S, nullptr, nullptr, 0.f, 1, nullptr, nullptr) != 0) return 0;
   return r.used + 256;
 }
@@ -1931,7 +1864,7 @@ extern "C" int kk_csm_generate_frame(kk_csm* m, void* stream, int B, int S, cons
     m->pad_pending = false;
   }
   auto eager = [&](void* on_stream) -> int {
-    Run r{m, (hipStream_t)on_stream, B, (char*)workspace, workspace_bytes, 0, false, false};
+    Run r(m, (hipStream_t)on_stream, B, workspace, workspace_bytes);
     return run_frame(r, S, tokens, tokens_mask, temperature, top_k, uniforms, codes_out);
   };
   int rc;
@@ -1944,46 +1877,10 @@ extern "C" int kk_csm_generate_frame(kk_csm* m, void* stream, int B, int S, cons
     const std::vector<unsigned long long> key = {(unsigned long long)B, (unsigned long long)(uintptr_t)tokens, (unsigned long long)(uintptr_t)tokens_mask,
         (unsigned long long)tbits, (unsigned long long)top_k, (unsigned long long)(uintptr_t)uniforms, (unsigned long long)(uintptr_t)workspace,
         (unsigned long long)workspace_bytes, (unsigned long long)(uintptr_t)codes_out, (unsigned long long)(uintptr_t)g_ts};
-    kk_csm::GraphEntry* ge = nullptr;
-    for (auto& g : m->graphs)
-      if (g.key == key) ge = &g;
-    if (!ge) {
-      if (m->graphs.size() >= 8) {
-        if (m->graphs.front().exec) (void)hipGraphExecDestroy(m->graphs.front().exec);
-        if (m->graphs.front().graph) (void)hipGraphDestroy(m->graphs.front().graph);
-        m->graphs.erase(m->graphs.begin());
-      }
-      m->graphs.emplace_back();
-      ge = &m->graphs.back();
-      ge->key = key;
-    }
-    if (ge->seen == 0) {
-      ge->seen = 1;
-      rc = eager(stream);
-    } else {
-      rc = 0;
-      if (ge->seen == 1) {
-        if (!m->cap_stream && hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking) != hipSuccess) return kk_fail("kk_csm: hipStreamCreate failed");
-        if (hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return kk_fail("kk_csm: hipStreamBeginCapture failed");
-        rc = eager((void*)m->cap_stream);
-        hipGraph_t g = nullptr;
-        const hipError_t e = hipStreamEndCapture(m->cap_stream, &g);
-        if (rc != 0) {
-          if (g) (void)hipGraphDestroy(g);
-          return rc;
-        }
-        if (e != hipSuccess || !g) return kk_fail("kk_csm: hipStreamEndCapture failed");
-        hipGraphExec_t ex = nullptr;
-        if (hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) != hipSuccess) {
-          (void)hipGraphDestroy(g);
-          return kk_fail("kk_csm: hipGraphInstantiate failed");
-        }
-        ge->graph = g;
-        ge->exec = ex;
-        ge->seen = 2;
-      }
-      if (hipGraphLaunch(ge->exec, (hipStream_t)stream) != hipSuccess) return kk_fail("kk_csm: hipGraphLaunch failed");
-    }
+    hipGraphExec_t ex = nullptr;
+    rc = m->graphs.run(key, (hipStream_t)stream, [&](hipStream_t on_stream, bool) { return eager((void*)on_stream); }, &ex, "kk_csm");
+    if (rc != 0) return rc;
+    if (ex && hipGraphLaunch(ex, (hipStream_t)stream) != hipSuccess) return kk_fail("kk_csm: hipGraphLaunch failed");
   }
   if (rc == 0) m->bb.offset += S;
   return rc;

@@ -37,38 +37,25 @@ struct PackedConv {  // generic-kernel pack [K][Cin][ldw] fp32 (+ bias); bf16 mo
   const float* b = nullptr;  // [CoutP] when mfma (zero padded), else [Cout]
   const bf16_t* wf = nullptr;
 };
-struct PackedVec {
-  size_t off = 0;
-  int n = 0;
-  const float* p = nullptr;
-};
 struct MimiLayer {
-  PackedVec n1w, n1b, n2w, n2b;
+  ArenaVec n1w, n1b, n2w, n2b;
   PackedConv in_proj, out_proj, lin1, lin2;  // out_proj / lin2 carry the LayerScale
 };
 struct SeaLayer {
   PackedConv up, b0, b1;
   int ratio = 1;
 };
-struct DebugBuf {
-  const void* p;
-  int rows, C, ld;
-  long long bs;
-  int B, dtype;
-};
 
 }  // namespace
 
 struct kk_mimi {
   kk_mimi_config cfg;
-  std::map<std::string, std::vector<float>> host;
-  std::vector<float> pack;
-  float* dev = nullptr;
+  WeightArena arena;
   bool finalized = false;
   int adt = KK_F32;  // activation dtype: KK_F32 (parity path) or KK_BF16 (MFMA convolutions, bf16 activations)
-  PackedVec codebooks;  // [nq][bins][qdim]
-  PackedVec inv_freq;   // [32]
-  PackedVec up_w;       // [2*stride][dim]
+  ArenaVec codebooks;  // [nq][bins][qdim]
+  ArenaVec inv_freq;   // [32]
+  ArenaVec up_w;       // [2*stride][dim]
   PackedConv proj_first, proj_rest, init_conv, final_conv;
   std::vector<MimiLayer> layers;
   std::vector<SeaLayer> sea;
@@ -78,8 +65,8 @@ struct kk_mimi {
   std::vector<SeaLayer> enc_sea;  // up = the strided down-sampling conv here
   std::vector<MimiLayer> enc_layers;
   std::vector<PackedConv> cb_dot;  // per code book: E^T as a 1x1 conv qdim -> bins (the x.e term of the distance)
-  PackedVec c2;                    // [nq][bins] |e|^2 / 2
-  std::map<std::string, DebugBuf> dbg;  // debug notes of the LAST call (any thread); dbg_mu makes concurrent callers of one codec safe
+  ArenaVec c2;                    // [nq][bins] |e|^2 / 2
+  DebugNotes dbg;  // debug notes of the LAST call (any thread); dbg_mu makes concurrent callers of one codec safe
   std::mutex dbg_mu;
 };
 
@@ -366,50 +353,22 @@ __global__ __launch_bounds__(256) void elu_rows_kernel(const float* x, long long
 }
 
 // ------------------------------------------------------------------------------------------------------------- host
-int rup(int v, int m) { return (v + m - 1) / m * m; }
-
 struct Packer {
   kk_mimi* m;
-  std::string err;
-  size_t alloc(size_t n) {
-    const size_t off = (m->pack.size() + 63) & ~(size_t)63;
-    m->pack.resize(off + n, 0.f);
-    return off;
-  }
-  const std::vector<float>* get(const std::string& name, size_t n) {
-    auto it = m->host.find(name);
-    if (it == m->host.end()) {
-      if (err.empty()) err = "missing parameter: " + name;
-      return nullptr;
-    }
-    if (it->second.size() != n) {
-      if (err.empty()) err = "unexpected size for " + name;
-      return nullptr;
-    }
-    return &it->second;
-  }
-  PackedVec vec(const std::string& name, size_t n) {
-    PackedVec r;
-    const std::vector<float>* v = get(name, n);
-    if (!v) return r;
-    r.n = (int)n;
-    r.off = alloc(n);
-    memcpy(&m->pack[r.off], v->data(), n * 4);
-    return r;
-  }
+  WeightArena& a;  // m->arena
   // MLX conv / conv-transpose weight [O][K][I] (+ bias [O]) -> [K][I][ldw]; `row_scale` (LayerScale) multiplies output row o
-  PackedConv conv(const std::string& wname, const std::string& bname, int O, int K, int I, const std::vector<float>* row_scale = nullptr) {
+  PackedConv conv(const std::string& wname, const std::string& bname, int O, int K, int I, const HostTensor* row_scale = nullptr) {
     PackedConv c;
-    const std::vector<float>* w = get(wname, (size_t)O * K * I);
+    const HostTensor* w = a.get(wname, (size_t)O * K * I);
     if (!w) return c;
     c.Cin = I; c.Cout = O; c.K = K; c.ldw = rup(O, 64);
-    c.w_off = alloc((size_t)K * I * c.ldw);
-    float* dst = &m->pack[c.w_off];
+    c.w_off = a.alloc((size_t)K * I * c.ldw);
+    float* dst = &a.pack[c.w_off];
     for (int o = 0; o < O; ++o)
       for (int k = 0; k < K; ++k)
         for (int i = 0; i < I; ++i) {
-          float v = (*w)[((size_t)o * K + k) * I + i];
-          if (row_scale) v *= (*row_scale)[o];
+          float v = w->d[((size_t)o * K + k) * I + i];
+          if (row_scale) v *= row_scale->d[o];
           dst[((size_t)k * I + i) * c.ldw + o] = v;
         }
     // bf16 mode: the same weights in MFMA fragment order for the variant-4 kernel (needs Cout % 8 == 0, >= 16 channels both ways)
@@ -418,25 +377,24 @@ struct Packer {
       c.CinP = rup(I, 64);
       c.CoutP = rup(O, 128);
       const size_t nel = (size_t)K * c.CoutP * c.CinP;
-      c.wf_off = alloc((nel + 1) / 2);
-      w = get(wname, (size_t)O * K * I);  // (alloc may have moved nothing here, but keep the pointer fresh)
-      uint16_t* dfr = (uint16_t*)&m->pack[c.wf_off];
+      c.wf_off = a.alloc((nel + 1) / 2);
+      uint16_t* dfr = (uint16_t*)&a.pack[c.wf_off];
       for (int o = 0; o < O; ++o)
         for (int k = 0; k < K; ++k)
           for (int i = 0; i < I; ++i) {
-            float v = (*w)[((size_t)o * K + k) * I + i];
-            if (row_scale) v *= (*row_scale)[o];
+            float v = w->d[((size_t)o * K + k) * I + i];
+            if (row_scale) v *= row_scale->d[o];
             dfr[kk_mfma4_pack_index(k, o, i, c.CoutP, c.CinP)] = f32_to_bf16_rne(v);
           }
     }
     const int nb = c.mfma ? c.CoutP : O;
     if (!bname.empty() || c.mfma) {
       c.has_bias = true;
-      c.b_off = alloc(nb);  // zero filled
+      c.b_off = a.alloc(nb);  // zero filled
       if (!bname.empty()) {
-        const std::vector<float>* b = get(bname, (size_t)O);
+        const HostTensor* b = a.get(bname, (size_t)O);
         if (!b) return c;
-        memcpy(&m->pack[c.b_off], b->data(), (size_t)O * 4);
+        memcpy(&a.pack[c.b_off], b->d.data(), (size_t)O * 4);
       }
     }
     return c;
@@ -444,11 +402,11 @@ struct Packer {
 };
 
 void resolve(kk_mimi* m, PackedConv& c) {
-  c.w = m->dev + c.w_off;
-  c.b = c.has_bias ? m->dev + c.b_off : nullptr;
-  c.wf = c.mfma ? (const bf16_t*)(m->dev + c.wf_off) : nullptr;
+  c.w = m->arena.dev + c.w_off;
+  c.b = c.has_bias ? m->arena.dev + c.b_off : nullptr;
+  c.wf = c.mfma ? (const bf16_t*)(m->arena.dev + c.wf_off) : nullptr;
 }
-void resolve(kk_mimi* m, PackedVec& v) { v.p = v.n ? m->dev + v.off : nullptr; }
+void resolve(kk_mimi* m, ArenaVec& v) { m->arena.resolve(v); }
 
 struct Act {  // an activation tensor [B][rows][ld], C valid channels
   void* p = nullptr;
@@ -457,23 +415,15 @@ struct Act {  // an activation tensor [B][rows][ld], C valid channels
   long long bs() const { return bstride ? bstride : (long long)rows * ld; }
 };
 
-struct Run {
+struct Run : Workspace {
   kk_mimi* m;
   hipStream_t st;
   int B;
-  char* base;
-  size_t cap, used;
-  bool dry;
-  bool oom = false;
   int adt = -1;  // activation dtype of this run (-1: the model's)
   float* elu_tmp = nullptr;  // dense scratch for an ELU'd input of the few-rows kernel (streaming steps allocate it)
   size_t elu_floats = 0;
-  void* raw(size_t bytes) {
-    const size_t off = (used + 255) & ~(size_t)255;
-    used = off + bytes;
-    if (dry) return nullptr;
-    if (used > cap) { oom = true; return nullptr; }
-    return base + off;
+  Run(kk_mimi* m_, hipStream_t st_, int B_, void* ws, size_t ws_bytes) : m(m_), st(st_), B(B_) {
+    base = (char*)ws; cap = ws_bytes; dry = ws == nullptr;
   }
   // bf16 tensors get a pitch that is a multiple of 64 so any of them can feed the MFMA kernel (pad channels are never read as
   // data: the kernel masks channels >= Cin)
@@ -559,16 +509,11 @@ struct Run {
   void note(const char* name, const Act& t) {
     if (!dry) {
       std::lock_guard<std::mutex> lk(m->dbg_mu);
-      m->dbg[name] = DebugBuf{t.p, t.rows, t.C, t.ld, t.bs(), B, t.dtype};
+      m->dbg.map[name] = DebugNote{t.p, t.ld, t.bs(), t.rows, t.C, t.dtype, B};
     }
   }
 };
 
-#define MM_TRY(x)        \
-  do {                   \
-    const int rc__ = (x); \
-    if (rc__ != 0) return rc__; \
-  } while (0)
 
 // x [B][T][D] updated in place by the layers (transformer.py:137-177); n, qkv, att, hbuf are scratch of the same row count
 int run_transformer(Run& r, const std::vector<MimiLayer>& layers, Act& x, Act& n, Act& qkv, Act& att, Act& hbuf) {
@@ -578,8 +523,8 @@ int run_transformer(Run& r, const std::vector<MimiLayer>& layers, Act& x, Act& n
   const bool bf = x.dtype == KK_BF16;
   for (size_t l = 0; l < layers.size(); ++l) {
     const MimiLayer& L = layers[l];
-    MM_TRY(r.layernorm(x, n, L.n1w.p, L.n1b.p));
-    MM_TRY(r.conv(L.in_proj, n, qkv, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
+    KK_TRY(r.layernorm(x, n, L.n1w.p, L.n1b.p));
+    KK_TRY(r.conv(L.in_proj, n, qkv, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
     if (!r.dry) {
       if (bf)
         hipLaunchKernelGGL(rope_kernel<bf16_t>, dim3(T, B), dim3(256), 0, r.st, (bf16_t*)qkv.p, m->inv_freq.p, T, D, qkv.ld, D / c.num_heads);
@@ -590,12 +535,12 @@ int run_transformer(Run& r, const std::vector<MimiLayer>& layers, Act& x, Act& n
       memset(&a, 0, sizeof a);
       a.qkv = qkv.p; a.bs = qkv.bs(); a.ld = qkv.ld; a.out = att.p; a.obs = att.bs(); a.ldo = att.ld;
       a.heads = c.num_heads; a.hs = D; a.Tmax = T; a.len = KKLen{nullptr, 0, T}; a.scale = 1.0f / sqrtf((float)(D / c.num_heads));
-      MM_TRY(kk_launch_attention(a, B, qkv.dtype, r.st));
+      KK_TRY(kk_launch_attention(a, B, qkv.dtype, r.st));
     }
-    MM_TRY(r.conv(L.out_proj, att, x, 0, 1, false, 1, 0, KK_ACT_NONE, &x, 0));  // x += ls1 * (W att)
-    MM_TRY(r.layernorm(x, n, L.n2w.p, L.n2b.p));
-    MM_TRY(r.conv(L.lin1, n, hbuf, 0, 1, false, 1, 0, KK_ACT_GELU_TANH, nullptr, 0));
-    MM_TRY(r.conv(L.lin2, hbuf, x, 0, 1, false, 1, 0, KK_ACT_NONE, &x, 0));     // x += ls2 * (W2 gelu(W1 n))
+    KK_TRY(r.conv(L.out_proj, att, x, 0, 1, false, 1, 0, KK_ACT_NONE, &x, 0));  // x += ls1 * (W att)
+    KK_TRY(r.layernorm(x, n, L.n2w.p, L.n2b.p));
+    KK_TRY(r.conv(L.lin1, n, hbuf, 0, 1, false, 1, 0, KK_ACT_GELU_TANH, nullptr, 0));
+    KK_TRY(r.conv(L.lin2, hbuf, x, 0, 1, false, 1, 0, KK_ACT_NONE, &x, 0));     // x += ls2 * (W2 gelu(W1 n))
   }
   return 0;
 }
@@ -608,16 +553,16 @@ int run_seanet(Run& r, const Act& x, float* pcm, const char* who) {
   (void)who;
   Act y = r.act(T, m->init_conv.Cout);
   if (r.oom) return kk_fail("kk_mimi_decode: workspace too small");
-  MM_TRY(r.conv(m->init_conv, x, y, (c.ksize - 1), 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
+  KK_TRY(r.conv(m->init_conv, x, y, (c.ksize - 1), 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
   static const char* lname[8] = {"layer0", "layer1", "layer2", "layer3", "layer4", "layer5", "layer6", "layer7"};
   for (size_t l = 0; l < m->sea.size(); ++l) {
     const SeaLayer& S = m->sea[l];
     const int Lo = y.rows * S.ratio, Co = S.up.Cout;
     Act u = r.act(Lo, Co), hb = r.act(Lo, S.b0.Cout), o = r.act(Lo, Co);
     if (r.oom) return kk_fail("kk_mimi_decode: workspace too small");
-    MM_TRY(r.conv(S.up, y, u, 0, 1, true, S.ratio, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
-    MM_TRY(r.conv(S.b0, u, hb, (c.residual_ksize - 1), 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
-    MM_TRY(r.conv(S.b1, hb, o, 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, &u, 0));
+    KK_TRY(r.conv(S.up, y, u, 0, 1, true, S.ratio, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
+    KK_TRY(r.conv(S.b0, u, hb, (c.residual_ksize - 1), 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
+    KK_TRY(r.conv(S.b1, hb, o, 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, &u, 0));
     r.note(l < 8 ? lname[l] : "layerN", o);
     y = o;
   }
@@ -639,7 +584,7 @@ int run_seanet(Run& r, const Act& x, float* pcm, const char* who) {
     }
     return 0;
   }
-  MM_TRY(r.conv(m->final_conv, y, out, (c.last_ksize - 1), 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
+  KK_TRY(r.conv(m->final_conv, y, out, (c.last_ksize - 1), 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
   return 0;
 }
 
@@ -660,8 +605,8 @@ int run_decode(Run& r, int Nf, const int* codes, float* pcm) {
     }
     KK_CHECK_LAUNCH();
   }
-  MM_TRY(r.conv(m->proj_first, q1, x0, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
-  if (c.nq > 1) MM_TRY(r.conv(m->proj_rest, q2, x0, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 1));
+  KK_TRY(r.conv(m->proj_first, q1, x0, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
+  if (c.nq > 1) KK_TRY(r.conv(m->proj_rest, q2, x0, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 1));
   r.note("quantized", x0);
   if (!r.dry) {
     if (bf)
@@ -674,7 +619,7 @@ int run_decode(Run& r, int Nf, const int* codes, float* pcm) {
   }
   r.note("upsampled", xu);
   // ---- transformer
-  MM_TRY(run_transformer(r, m->layers, x, n, qkv, att, hbuf));
+  KK_TRY(run_transformer(r, m->layers, x, n, qkv, att, hbuf));
   r.note("transformer", x);
   // ---- SEANet decoder
   return run_seanet(r, x, pcm, "kk_mimi_decode");
@@ -777,16 +722,16 @@ int run_transformer_step(Run& r, kk_mimi_stream* s, const std::vector<MimiLayer>
     const MimiLayer& L = layers[l];
     float* kcl = s->kc + (size_t)l * s->max_batch * s->max_pos * D;
     float* vcl = s->vc + (size_t)l * s->max_batch * s->max_pos * D;
-    MM_TRY(r.layernorm(x, n, L.n1w.p, L.n1b.p));
-    MM_TRY(r.conv(L.in_proj, n, qkv, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
+    KK_TRY(r.layernorm(x, n, L.n1w.p, L.n1b.p));
+    KK_TRY(r.conv(L.in_proj, n, qkv, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
     if (!r.dry) {
-      MM_TRY(kk_launch_rope_append((float*)qkv.p, T, H, H, hd, s->rope, s->pos, kcl, vcl, s->max_pos, B, r.st));
-      MM_TRY(kk_launch_attn_cache((const float*)qkv.p, T, H, H, hd, s->pos, kcl, vcl, s->max_pos, 1.0f / sqrtf((float)hd), (float*)att.p, 0, s->context, B, r.st));
+      KK_TRY(kk_launch_rope_append((float*)qkv.p, T, H, H, hd, s->rope, s->pos, kcl, vcl, s->max_pos, B, r.st));
+      KK_TRY(kk_launch_attn_cache((const float*)qkv.p, T, H, H, hd, s->pos, kcl, vcl, s->max_pos, 1.0f / sqrtf((float)hd), (float*)att.p, 0, s->context, B, r.st));
     }
-    MM_TRY(r.conv(L.out_proj, att, x, 0, 1, false, 1, 0, KK_ACT_NONE, &x, 0));
-    MM_TRY(r.layernorm(x, n, L.n2w.p, L.n2b.p));
-    MM_TRY(r.conv(L.lin1, n, hbuf, 0, 1, false, 1, 0, KK_ACT_GELU_TANH, nullptr, 0));
-    MM_TRY(r.conv(L.lin2, hbuf, x, 0, 1, false, 1, 0, KK_ACT_NONE, &x, 0));
+    KK_TRY(r.conv(L.out_proj, att, x, 0, 1, false, 1, 0, KK_ACT_NONE, &x, 0));
+    KK_TRY(r.layernorm(x, n, L.n2w.p, L.n2b.p));
+    KK_TRY(r.conv(L.lin1, n, hbuf, 0, 1, false, 1, 0, KK_ACT_GELU_TANH, nullptr, 0));
+    KK_TRY(r.conv(L.lin2, hbuf, x, 0, 1, false, 1, 0, KK_ACT_NONE, &x, 0));
   }
   return 0;
 }
@@ -894,32 +839,32 @@ int run_decode_step(Run& r, kk_mimi_stream* s, const int* codes, float* pcm_out)
   stream_elu_scratch(r, s);
   if (r.oom) return kk_fail("kk_mimi_decode_step: workspace too small");
   if (!r.dry && s->pos + F * us > s->max_pos) return kk_fail("kk_mimi_decode_step: the stream is longer than max_frames (kk_mimi_stream_create)");
-  MM_TRY(stream_begin(r, s));
+  KK_TRY(stream_begin(r, s));
   // ---- quantizer.decode of the new frames, straight behind the previous one
   Act xq = s->resample.fresh();
   if (!r.dry) {
     hipLaunchKernelGGL(rvq_sum_kernel<float>, dim3(F, B), dim3(256), 0, r.st, codes, m->codebooks.p, c.nq, c.bins, Q, F, q1.ld, (float*)q1.p, (float*)q2.p);
     KK_CHECK_LAUNCH();
   }
-  MM_TRY(r.conv(m->proj_first, q1, xq, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
-  if (c.nq > 1) MM_TRY(r.conv(m->proj_rest, q2, xq, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 1));
+  KK_TRY(r.conv(m->proj_first, q1, xq, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
+  if (c.nq > 1) KK_TRY(r.conv(m->proj_rest, q2, xq, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 1));
   // ---- upsample.step: the depthwise transposed conv over [previous | new]; its first `us` rows repeat the last step's
   if (!r.dry) {
     const Act w = s->resample.all();
     hipLaunchKernelGGL(upsample_dw_kernel<float>, dim3((F + 1) * us, B), dim3(256), 0, r.st, (const float*)w.p, w.bs(), m->up_w.p, D, w.ld, F + 1, us, (float*)xu.p);
     KK_CHECK_LAUNCH();
   }
-  MM_TRY(copy_rows(r, xu, us, x, F * us));
-  MM_TRY(copy_rows(r, x, 0, xup, F * us));  // debug hook: the transformer updates x in place
-  if (!r.dry) MM_TRY(state_shift(s->resample, B, r.st));
+  KK_TRY(copy_rows(r, xu, us, x, F * us));
+  KK_TRY(copy_rows(r, x, 0, xup, F * us));  // debug hook: the transformer updates x in place
+  if (!r.dry) KK_TRY(state_shift(s->resample, B, r.st));
   r.note("upsampled", xup);
   // ---- decoder_transformer with the KV caches
-  MM_TRY(run_transformer_step(r, s, m->layers, x, n, qkv, att, hbuf));
+  KK_TRY(run_transformer_step(r, s, m->layers, x, n, qkv, att, hbuf));
   r.note("transformer", x);
   // ---- decoder.step (seanet.py:228-283 through each module's step)
-  MM_TRY(copy_rows(r, x, 0, s->first.fresh(), F * us));
-  MM_TRY(r.conv(m->init_conv, s->first.all(), s->up[0].fresh(), 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
-  if (!r.dry) MM_TRY(state_shift(s->first, B, r.st));
+  KK_TRY(copy_rows(r, x, 0, s->first.fresh(), F * us));
+  KK_TRY(r.conv(m->init_conv, s->first.all(), s->up[0].fresh(), 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
+  if (!r.dry) KK_TRY(state_shift(s->first, B, r.st));
   static const char* lname[8] = {"layer0", "layer1", "layer2", "layer3", "layer4", "layer5", "layer6", "layer7"};
   for (size_t l = 0; l < m->sea.size(); ++l) {
     const SeaLayer& S = m->sea[l];
@@ -928,20 +873,20 @@ int run_decode_step(Run& r, kk_mimi_stream* s, const int* codes, float* pcm_out)
     const StateBuf& nextb = l + 1 < m->sea.size() ? s->up[l + 1] : s->last;
     Act full = r.act((U.n + 1) * S.ratio, S.up.Cout), hb = r.act(Bk.n, S.b0.Cout);
     if (r.oom) return kk_fail("kk_mimi_decode_step: workspace too small");
-    MM_TRY(r.conv(S.up, U.all(), full, 0, 1, true, S.ratio, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
-    MM_TRY(copy_rows(r, full, S.ratio, Bk.fresh(), Bk.n));
-    if (!r.dry) MM_TRY(state_shift(U, B, r.st));
-    MM_TRY(r.conv(S.b0, Bk.all(), hb, 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
+    KK_TRY(r.conv(S.up, U.all(), full, 0, 1, true, S.ratio, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
+    KK_TRY(copy_rows(r, full, S.ratio, Bk.fresh(), Bk.n));
+    if (!r.dry) KK_TRY(state_shift(U, B, r.st));
+    KK_TRY(r.conv(S.b0, Bk.all(), hb, 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
     const Act skip = Bk.fresh();
-    MM_TRY(r.conv(S.b1, hb, nextb.fresh(), 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, &skip, 0));
-    if (!r.dry) MM_TRY(state_shift(Bk, B, r.st));
+    KK_TRY(r.conv(S.b1, hb, nextb.fresh(), 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, &skip, 0));
+    if (!r.dry) KK_TRY(state_shift(Bk, B, r.st));
     r.note(l < 8 ? lname[l] : "layerN", nextb.fresh());
   }
   Act out;
   out.p = pcm_out; out.rows = s->last.n; out.C = 1; out.ld = 1; out.dtype = KK_F32;
-  MM_TRY(r.conv(m->final_conv, s->last.all(), out, 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
+  KK_TRY(r.conv(m->final_conv, s->last.all(), out, 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
   if (!r.dry) {
-    MM_TRY(state_shift(s->last, B, r.st));
+    KK_TRY(state_shift(s->last, B, r.st));
     s->pos += F * us;
     s->frames += F;
     s->fresh = false;
@@ -958,12 +903,12 @@ int run_encode_step(Run& r, kk_mimi_stream* s, const float* pcm, int* codes) {
   if (!r.dry && s->pos + T > s->max_pos) return kk_fail("kk_mimi_encode_step: the stream is longer than max_frames (kk_mimi_encode_stream_create)");
   stream_elu_scratch(r, s);
   if (r.oom) return kk_fail("kk_mimi_encode_step: workspace too small");
-  MM_TRY(stream_begin(r, s));
+  KK_TRY(stream_begin(r, s));
   Act in;
   in.p = const_cast<float*>(pcm); in.rows = N; in.C = 1; in.ld = 1; in.dtype = KK_F32;
-  MM_TRY(copy_rows(r, in, 0, s->first.fresh(), N));
-  MM_TRY(r.conv(m->enc_init, s->first.all(), s->blk[0].fresh(), 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
-  if (!r.dry) MM_TRY(state_shift(s->first, B, r.st));
+  KK_TRY(copy_rows(r, in, 0, s->first.fresh(), N));
+  KK_TRY(r.conv(m->enc_init, s->first.all(), s->blk[0].fresh(), 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
+  if (!r.dry) KK_TRY(state_shift(s->first, B, r.st));
   for (size_t l = 0; l < m->enc_sea.size(); ++l) {
     const SeaLayer& S = m->enc_sea[l];
     const StateBuf& Bk = s->blk[l];
@@ -971,35 +916,35 @@ int run_encode_step(Run& r, kk_mimi_stream* s, const float* pcm, int* codes) {
     const StateBuf& nextb = l + 1 < m->enc_sea.size() ? s->blk[l + 1] : s->last;
     Act hb = r.act(Bk.n, S.b0.Cout);
     if (r.oom) return kk_fail("kk_mimi_encode_step: workspace too small");
-    MM_TRY(r.conv(S.b0, Bk.all(), hb, 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
+    KK_TRY(r.conv(S.b0, Bk.all(), hb, 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
     const Act skip = Bk.fresh();
-    MM_TRY(r.conv(S.b1, hb, Dn.fresh(), 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, &skip, 0));
-    if (!r.dry) MM_TRY(state_shift(Bk, B, r.st));
-    MM_TRY(r.conv(S.up, Dn.all(), nextb.fresh(), 0, 1, false, S.ratio, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
-    if (!r.dry) MM_TRY(state_shift(Dn, B, r.st));
+    KK_TRY(r.conv(S.b1, hb, Dn.fresh(), 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, &skip, 0));
+    if (!r.dry) KK_TRY(state_shift(Bk, B, r.st));
+    KK_TRY(r.conv(S.up, Dn.all(), nextb.fresh(), 0, 1, false, S.ratio, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
+    if (!r.dry) KK_TRY(state_shift(Dn, B, r.st));
   }
   Act x = r.act(T, D), n = r.act(T, D), qkv = r.act(T, 3 * D), att = r.act(T, D), hbuf = r.act(T, c.dim_feedforward);
   Act xd = r.act(F, D), res = r.act(F, Q), dots = r.act(F, c.bins), xs = r.act(T, D);
   if (r.oom) return kk_fail("kk_mimi_encode_step: workspace too small");
-  MM_TRY(r.conv(m->enc_final, s->last.all(), xs, 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
-  if (!r.dry) MM_TRY(state_shift(s->last, B, r.st));
+  KK_TRY(r.conv(m->enc_final, s->last.all(), xs, 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
+  if (!r.dry) KK_TRY(state_shift(s->last, B, r.st));
   r.note("seanet", xs);
-  MM_TRY(copy_rows(r, xs, 0, x, T));  // (the transformer updates x in place; xs stays for the debug hook)
-  MM_TRY(run_transformer_step(r, s, m->enc_layers, x, n, qkv, att, hbuf));
+  KK_TRY(copy_rows(r, xs, 0, x, T));  // (the transformer updates x in place; xs stays for the debug hook)
+  KK_TRY(run_transformer_step(r, s, m->enc_layers, x, n, qkv, att, hbuf));
   r.note("transformer", x);
   // downsample.step: conv k = 2 us, stride us, 'edge' left padding on the first step
-  MM_TRY(copy_rows(r, x, 0, s->resample.fresh(), T));
+  KK_TRY(copy_rows(r, x, 0, s->resample.fresh(), T));
   if (!r.dry && s->fresh) {
     hipLaunchKernelGGL(state_edge_fill_kernel, dim3(B), dim3(256), 0, r.st, s->resample.p, s->resample.S, s->resample.n, s->resample.C, s->resample.pitch());
     KK_CHECK_LAUNCH();
   }
-  MM_TRY(r.conv(m->enc_down, s->resample.all(), xd, 0, 1, false, us, 0, KK_ACT_NONE, nullptr, 0));
-  if (!r.dry) MM_TRY(state_shift(s->resample, B, r.st));
+  KK_TRY(r.conv(m->enc_down, s->resample.all(), xd, 0, 1, false, us, 0, KK_ACT_NONE, nullptr, 0));
+  if (!r.dry) KK_TRY(state_shift(s->resample, B, r.st));
   r.note("downsampled", xd);
   for (int i = 0; i < c.nq; ++i) {  // split RVQ search, as in run_encode
-    if (i == 0) MM_TRY(r.conv(m->inproj_first, xd, res, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
-    if (i == 1) MM_TRY(r.conv(m->inproj_rest, xd, res, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
-    MM_TRY(r.conv(m->cb_dot[i], res, dots, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
+    if (i == 0) KK_TRY(r.conv(m->inproj_first, xd, res, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
+    if (i == 1) KK_TRY(r.conv(m->inproj_rest, xd, res, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
+    KK_TRY(r.conv(m->cb_dot[i], res, dots, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
     if (!r.dry) {
       hipLaunchKernelGGL(rvq_argmin_kernel, dim3(F, B), dim3(256), 0, r.st, (const float*)dots.p, m->c2.p + (size_t)i * c.bins,
                          m->codebooks.p + (size_t)i * c.bins * Q, c.bins, Q, F, c.nq, i, (float*)res.p, codes);
@@ -1030,28 +975,28 @@ int run_encode(Run& r, int N, const float* pcm, int* codes) {
   x.p = const_cast<float*>(pcm); x.rows = N; x.C = 1; x.ld = 1; x.dtype = KK_F32;
   Act y = r.act(N, m->enc_init.Cout);
   if (r.oom) return kk_fail("kk_mimi_encode: workspace too small");
-  MM_TRY(r.conv(m->enc_init, x, y, c.ksize - 1, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
+  KK_TRY(r.conv(m->enc_init, x, y, c.ksize - 1, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
   for (size_t l = 0; l < m->enc_sea.size(); ++l) {
     const SeaLayer& S = m->enc_sea[l];
     Act hb = r.act(y.rows, S.b0.Cout), o = r.act(y.rows, y.C);
     const int Lo = kk_cdiv(y.rows, S.ratio);
     Act d = r.act(Lo, S.up.Cout);
     if (r.oom) return kk_fail("kk_mimi_encode: workspace too small");
-    MM_TRY(r.conv(S.b0, y, hb, c.residual_ksize - 1, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
-    MM_TRY(r.conv(S.b1, hb, o, 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, &y, 0));
+    KK_TRY(r.conv(S.b0, y, hb, c.residual_ksize - 1, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
+    KK_TRY(r.conv(S.b1, hb, o, 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, &y, 0));
     // causal strided conv: left pad k - stride, the right "extra padding" (conv.py:200-209) is the kernel's implicit zero rows
-    MM_TRY(r.conv(S.up, o, d, S.up.K - S.ratio, 1, false, S.ratio, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
+    KK_TRY(r.conv(S.up, o, d, S.up.K - S.ratio, 1, false, S.ratio, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
     y = d;
   }
   const int T = y.rows;
   Act xe = r.act(T, D), n = r.act(T, D), qkv = r.act(T, 3 * D), att = r.act(T, D), hbuf = r.act(T, c.dim_feedforward);
   if (r.oom) return kk_fail("kk_mimi_encode: workspace too small");
-  MM_TRY(r.conv(m->enc_final, y, xe, c.last_ksize - 1, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
+  KK_TRY(r.conv(m->enc_final, y, xe, c.last_ksize - 1, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
   r.note("seanet", xe);
   Act xt = r.act(T, D);
   if (r.oom) return kk_fail("kk_mimi_encode: workspace too small");
   if (!r.dry && hipMemcpyAsync(xt.p, xe.p, (size_t)B * T * D * 4, hipMemcpyDeviceToDevice, r.st) != hipSuccess) return kk_fail("kk_mimi_encode: copy failed");
-  MM_TRY(run_transformer(r, m->enc_layers, xt, n, qkv, att, hbuf));
+  KK_TRY(run_transformer(r, m->enc_layers, xt, n, qkv, att, hbuf));
   r.note("transformer", xt);
   // resampler: conv k = 2 s, stride s, 'edge' padding on both sides (ConvDownsample1d, conv.py:350-367)
   const int s = c.upsample_stride, k = 2 * s, Nf = kk_cdiv(T, s);
@@ -1062,13 +1007,13 @@ int run_encode(Run& r, int N, const float* pcm, int* codes) {
     hipLaunchKernelGGL(edge_pad_kernel, dim3(Lp, B), dim3(256), 0, r.st, (const float*)xt.p, T, D, left, Lp, (float*)xp.p);
     KK_CHECK_LAUNCH();
   }
-  MM_TRY(r.conv(m->enc_down, xp, xd, 0, 1, false, s, 0, KK_ACT_NONE, nullptr, 0));
+  KK_TRY(r.conv(m->enc_down, xp, xd, 0, 1, false, s, 0, KK_ACT_NONE, nullptr, 0));
   r.note("downsampled", xd);
   // split RVQ search (quantization.py:128-133,170-176): first code book on its own projection, the other nq-1 on the second
   for (int i = 0; i < c.nq; ++i) {
-    if (i == 0) MM_TRY(r.conv(m->inproj_first, xd, res, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
-    if (i == 1) MM_TRY(r.conv(m->inproj_rest, xd, res, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
-    MM_TRY(r.conv(m->cb_dot[i], res, dots, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
+    if (i == 0) KK_TRY(r.conv(m->inproj_first, xd, res, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
+    if (i == 1) KK_TRY(r.conv(m->inproj_rest, xd, res, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
+    KK_TRY(r.conv(m->cb_dot[i], res, dots, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
     if (!r.dry) {
       hipLaunchKernelGGL(rvq_argmin_kernel, dim3(Nf, B), dim3(256), 0, r.st, (const float*)dots.p, m->c2.p + (size_t)i * c.bins,
                          m->codebooks.p + (size_t)i * c.bins * Q, c.bins, Q, Nf, c.nq, i, (float*)res.p, codes);
@@ -1091,7 +1036,7 @@ int check_cfg(const kk_mimi_config& c) {
 
 extern "C" int kk_mimi_create(const kk_mimi_config* cfg, kk_mimi** out) {
   if (!cfg || !out) return kk_fail("kk_mimi_create: null argument");
-  MM_TRY(check_cfg(*cfg));
+  KK_TRY(check_cfg(*cfg));
   kk_mimi* m = new kk_mimi();
   m->cfg = *cfg;
   m->adt = cfg->compute_dtype == KK_BF16 ? KK_BF16 : KK_F32;
@@ -1101,7 +1046,7 @@ extern "C" int kk_mimi_create(const kk_mimi_config* cfg, kk_mimi** out) {
 
 extern "C" void kk_mimi_destroy(kk_mimi* m) {
   if (!m) return;
-  if (m->dev) (void)hipFree(m->dev);
+  if (m->arena.dev) (void)hipFree(m->arena.dev);
   delete m;
 }
 
@@ -1110,7 +1055,9 @@ extern "C" int kk_mimi_load_tensor(kk_mimi* m, const char* name, const int64_t* 
   if (m->finalized) return kk_fail("kk_mimi_load_tensor: model already finalized");
   size_t n = 1;
   for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
-  m->host[name].assign(data, data + n);
+  HostTensor& t = m->arena.host[name];
+  t.d.assign(data, data + n);
+  t.shape.assign(shape, shape + ndim);
   return 0;
 }
 
@@ -1118,45 +1065,43 @@ extern "C" int kk_mimi_finalize(kk_mimi* m, void* stream) {
   if (!m) return kk_fail("kk_mimi_finalize: null model");
   if (m->finalized) return kk_fail("kk_mimi_finalize: already finalized");
   const kk_mimi_config& c = m->cfg;
-  Packer P{m, ""};
+  Packer P{m, m->arena};
   const int D = c.dim, Q = c.qdim;
   // code books: embedding = embedding_sum / max(cluster_usage, 1e-5), first | rest
   {
     m->codebooks.n = c.nq * c.bins * Q;
-    m->codebooks.off = P.alloc((size_t)m->codebooks.n);
+    m->codebooks.off = P.a.alloc(m->codebooks.n);
     for (int i = 0; i < c.nq; ++i) {
       const std::string p = std::string("quantizer.") + (i == 0 ? "rvq_first" : "rvq_rest") + ".vq.layers." + std::to_string(i == 0 ? 0 : i - 1) + ".codebook";
-      const std::vector<float>* es = P.get(p + ".embedding_sum", (size_t)c.bins * Q);
-      const std::vector<float>* cu = P.get(p + ".cluster_usage", (size_t)c.bins);
+      const HostTensor* es = P.a.get(p + ".embedding_sum", (size_t)c.bins * Q);
+      const HostTensor* cu = P.a.get(p + ".cluster_usage", (size_t)c.bins);
       if (!es || !cu) break;
-      float* dst = &m->pack[m->codebooks.off + (size_t)i * c.bins * Q];
+      float* dst = &P.a.pack[m->codebooks.off + (size_t)i * c.bins * Q];
       for (int r = 0; r < c.bins; ++r) {
-        const float u = (*cu)[r] > 1e-5f ? (*cu)[r] : 1e-5f;
-        for (int q = 0; q < Q; ++q) dst[(size_t)r * Q + q] = (*es)[(size_t)r * Q + q] / u;
+        const float u = cu->d[r] > 1e-5f ? cu->d[r] : 1e-5f;
+        for (int q = 0; q < Q; ++q) dst[(size_t)r * Q + q] = es->d[(size_t)r * Q + q] / u;
       }
     }
   }
   m->proj_first = P.conv("quantizer.rvq_first.output_proj.weight", "", D, 1, Q);
   if (c.nq > 1) m->proj_rest = P.conv("quantizer.rvq_rest.output_proj.weight", "", D, 1, Q);
-  m->up_w = P.vec("upsample.convtr.convtr.convtr.weight", (size_t)2 * c.upsample_stride * D);  // [1][2s][D] == [2s][D]
+  m->up_w = P.a.vec("upsample.convtr.convtr.convtr.weight", (size_t)2 * c.upsample_stride * D);  // [1][2s][D] == [2s][D]
   {
     const int half = 32;
     std::vector<float> f(half);
     for (int i = 0; i < half; ++i) f[i] = (float)pow((double)c.rope_base, -(double)i / (double)half);
-    m->inv_freq.n = half;
-    m->inv_freq.off = P.alloc(half);
-    memcpy(&m->pack[m->inv_freq.off], f.data(), half * 4);
+    m->inv_freq = P.a.put(f.data(), half);
   }
   auto pack_transformer = [&](const std::string& stack, std::vector<MimiLayer>& layers) {
     layers.resize(c.num_layers);
     for (int l = 0; l < c.num_layers; ++l) {
       const std::string p = stack + ".transformer.layers." + std::to_string(l);
       MimiLayer& L = layers[l];
-      L.n1w = P.vec(p + ".norm1.weight", D); L.n1b = P.vec(p + ".norm1.bias", D);
-      L.n2w = P.vec(p + ".norm2.weight", D); L.n2b = P.vec(p + ".norm2.bias", D);
+      L.n1w = P.a.vec(p + ".norm1.weight", D); L.n1b = P.a.vec(p + ".norm1.bias", D);
+      L.n2w = P.a.vec(p + ".norm2.weight", D); L.n2b = P.a.vec(p + ".norm2.bias", D);
       L.in_proj = P.conv(p + ".self_attn.in_proj.weight", "", 3 * D, 1, D);
-      const std::vector<float>* s1 = P.get(p + ".layer_scale_1.scale", D);
-      const std::vector<float>* s2 = P.get(p + ".layer_scale_2.scale", D);
+      const HostTensor* s1 = P.a.get(p + ".layer_scale_1.scale", D);
+      const HostTensor* s2 = P.a.get(p + ".layer_scale_2.scale", D);
       L.out_proj = P.conv(p + ".self_attn.out_proj.weight", "", D, 1, D, s1);
       L.lin1 = P.conv(p + ".gating.linear1.weight", "", c.dim_feedforward, 1, D);
       L.lin2 = P.conv(p + ".gating.linear2.weight", "", D, 1, c.dim_feedforward, s2);
@@ -1164,7 +1109,7 @@ extern "C" int kk_mimi_finalize(kk_mimi* m, void* stream) {
   };
   pack_transformer("decoder_transformer", m->layers);
   // ---- encode side, when the checkpoint has it
-  m->has_encoder = m->host.count("encoder.init_conv1d.conv.conv.weight") != 0;
+  m->has_encoder = m->arena.host.count("encoder.init_conv1d.conv.conv.weight") != 0;
   if (m->has_encoder) {
     const int saved = m->adt;
     m->adt = KK_F32;  // the encoder runs on the fp32 kernels only: no fragment packs
@@ -1188,15 +1133,15 @@ extern "C" int kk_mimi_finalize(kk_mimi* m, void* stream) {
     pack_transformer("encoder_transformer", m->enc_layers);
     // distance tables: c2 = |e|^2 / 2 and E^T as a 1x1 conv (quantization.py:27-28,35-39)
     m->c2.n = c.nq * c.bins;
-    m->c2.off = P.alloc((size_t)m->c2.n);
+    m->c2.off = P.a.alloc(m->c2.n);
     m->cb_dot.resize(c.nq);
     for (int i = 0; i < c.nq; ++i) {
       PackedConv& cd = m->cb_dot[i];
       cd.Cin = Q; cd.Cout = c.bins; cd.K = 1; cd.ldw = rup(c.bins, 64);
-      cd.w_off = P.alloc((size_t)Q * cd.ldw);
-      const float* E = &m->pack[m->codebooks.off + (size_t)i * c.bins * Q];
-      float* dst = &m->pack[cd.w_off];
-      float* c2 = &m->pack[m->c2.off + (size_t)i * c.bins];
+      cd.w_off = P.a.alloc((size_t)Q * cd.ldw);
+      const float* E = &P.a.pack[m->codebooks.off + (size_t)i * c.bins * Q];
+      float* dst = &P.a.pack[cd.w_off];
+      float* c2 = &P.a.pack[m->c2.off + (size_t)i * c.bins];
       for (int r = 0; r < c.bins; ++r) {
         float ss = 0.f;
         for (int q = 0; q < Q; ++q) {
@@ -1223,11 +1168,8 @@ extern "C" int kk_mimi_finalize(kk_mimi* m, void* stream) {
     mult /= 2;
   }
   m->final_conv = P.conv("decoder.final_conv1d.conv.conv.weight", "decoder.final_conv1d.conv.conv.bias", 1, c.last_ksize, c.nfilters);
-  if (!P.err.empty()) return kk_fail(("kk_mimi_finalize: " + P.err).c_str());
-  if (hipMalloc((void**)&m->dev, m->pack.size() * sizeof(float)) != hipSuccess) return kk_fail("kk_mimi_finalize: hipMalloc failed");
-  if (hipMemcpyAsync(m->dev, m->pack.data(), m->pack.size() * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess)
-    return kk_fail("kk_mimi_finalize: upload failed");
-  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return kk_fail("kk_mimi_finalize: stream sync failed");
+  if (!P.a.err.empty()) return kk_failf("kk_mimi_finalize: %s", P.a.err.c_str());
+  KK_TRY(m->arena.upload((hipStream_t)stream, "kk_mimi_finalize"));
   resolve(m, m->codebooks); resolve(m, m->inv_freq); resolve(m, m->up_w);
   resolve(m, m->proj_first); resolve(m, m->proj_rest); resolve(m, m->init_conv); resolve(m, m->final_conv);
   for (auto& L : m->layers) {
@@ -1245,8 +1187,6 @@ extern "C" int kk_mimi_finalize(kk_mimi* m, void* stream) {
     }
     for (auto& cd : m->cb_dot) resolve(m, cd);
   }
-  m->host.clear();
-  std::vector<float>().swap(m->pack);
   m->finalized = true;
   return 0;
 }
@@ -1260,7 +1200,7 @@ extern "C" int64_t kk_mimi_samples_per_frame(const kk_mimi* m) {
 
 extern "C" size_t kk_mimi_workspace_bytes(kk_mimi* m, int B, int Nf) {
   if (!m || !m->finalized || B <= 0 || Nf <= 0) return 0;
-  Run r{m, nullptr, B, nullptr, 0, 0, true, false};
+  Run r(m, nullptr, B, nullptr, 0);
   if (run_decode(r, Nf, nullptr, nullptr) != 0) return 0;
   return r.used + 256;
 }
@@ -1270,28 +1210,24 @@ extern "C" int kk_mimi_decode(kk_mimi* m, void* stream, int B, int Nf, const int
   if (!m || !m->finalized) return kk_fail("kk_mimi_decode: model not finalized");
   if (B <= 0 || Nf <= 0 || !codes || !workspace || !pcm_out) return kk_fail("kk_mimi_decode: bad argument");
   if (workspace_bytes < kk_mimi_workspace_bytes(m, B, Nf)) return kk_fail("kk_mimi_decode: workspace too small");
-  { std::lock_guard<std::mutex> lk(m->dbg_mu); m->dbg.clear(); }
-  Run r{m, (hipStream_t)stream, B, (char*)workspace, workspace_bytes, 0, false, false};
+  { std::lock_guard<std::mutex> lk(m->dbg_mu); m->dbg.map.clear(); }
+  Run r(m, (hipStream_t)stream, B, workspace, workspace_bytes);
   return run_decode(r, Nf, codes, pcm_out);
 }
 
 // ---- streaming (Mimi.decode_step / encode_step / MimiStreamingDecoder, mimi.py:156-168,264-306)
-static int kk_fail(const char* who, const char* what) {
-  std::string msg = std::string(who) + what;
-  return kk_fail(msg.c_str());
-}
 static int stream_create(kk_mimi* m, bool encoder, int max_batch, int max_frames, int chunk_frames, kk_mimi_stream** out, const char* who) {
-  if (!m || !m->finalized || !out || max_batch < 1 || max_frames < 1 || chunk_frames < 1 || chunk_frames > max_frames) return kk_fail(who, ": bad argument");
-  if (encoder && !m->has_encoder) return kk_fail(who, ": the checkpoint held no encoder.* parameters");
+  if (!m || !m->finalized || !out || max_batch < 1 || max_frames < 1 || chunk_frames < 1 || chunk_frames > max_frames) return kk_failf("%s: bad argument", who);
+  if (encoder && !m->has_encoder) return kk_failf("%s: the checkpoint held no encoder.* parameters", who);
   const kk_mimi_config& c = m->cfg;
   const int hd = c.dim / c.num_heads;
-  if (hd != 64 && hd != 128) return kk_fail(who, ": head size must be 64 or 128");
+  if (hd != 64 && hd != 128) return kk_failf("%s: head size must be 64 or 128", who);
   for (int l = 0; l < c.n_ratios; ++l) {
     const SeaLayer& L = encoder ? m->enc_sea[l] : m->sea[l];
-    if (L.up.K != 2 * L.ratio) return kk_fail(who, ": (transposed) conv kernel must be twice its stride");
+    if (L.up.K != 2 * L.ratio) return kk_failf("%s: (transposed) conv kernel must be twice its stride", who);
   }
   kk_mimi_stream* s = new (std::nothrow) kk_mimi_stream();
-  if (!s) return kk_fail(who, ": out of memory");
+  if (!s) return kk_failf("%s: out of memory", who);
   s->m = m; s->max_batch = max_batch; s->max_pos = max_frames * c.upsample_stride; s->encoder = encoder; s->chunk = s->max_chunk = chunk_frames;
   const size_t D = c.dim, nl = encoder ? m->enc_layers.size() : m->layers.size(), kvn = nl * max_batch * s->max_pos * D * 4;
   std::vector<float> tab((size_t)s->max_pos * (hd / 2) * 2);
@@ -1306,7 +1242,7 @@ static int stream_create(kk_mimi* m, bool encoder, int max_batch, int max_frames
       hipMalloc((void**)&s->vc, kvn ? kvn : 4) != hipSuccess || hipMalloc((void**)&s->rope, tab.size() * 4) != hipSuccess ||
       hipMemcpy(s->rope, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
     kk_mimi_stream_destroy(s);
-    return kk_fail(who, ": hipMalloc failed");
+    return kk_failf("%s: hipMalloc failed", who);
   }
   (void)stream_layout(s, s->pool);
   *out = s;
@@ -1354,7 +1290,7 @@ extern "C" int kk_mimi_stream_set_context(kk_mimi_stream* s, int context) {
 }
 extern "C" size_t kk_mimi_stream_workspace_bytes(kk_mimi_stream* s, int B) {
   if (!s || B < 1 || B > s->max_batch) return 0;
-  Run r{s->m, nullptr, B, nullptr, 0, 0, true, false};
+  Run r(s->m, nullptr, B, nullptr, 0);
   r.adt = KK_F32;
   const int cur = s->chunk;
   stream_set_rows(s, s->max_chunk);  // sized for the largest step: one workspace serves every step size
@@ -1364,28 +1300,28 @@ extern "C" size_t kk_mimi_stream_workspace_bytes(kk_mimi_stream* s, int B) {
   return r.used + 256;
 }
 static int step_check(kk_mimi_stream* s, bool encoder, int B, const void* in, void* workspace, size_t workspace_bytes, void* out, const char* who) {
-  if (!s || !in || !workspace || !out || B < 1 || B > s->max_batch) return kk_fail(who, ": bad argument");
-  if (s->encoder != encoder) return kk_fail(who, ": the stream was created for the other direction");
-  if (s->frames > 0 && B != s->B) return kk_fail(who, ": the batch size of a stream is fixed until it is reset");
-  if (workspace_bytes < kk_mimi_stream_workspace_bytes(s, B)) return kk_fail(who, ": workspace too small");
+  if (!s || !in || !workspace || !out || B < 1 || B > s->max_batch) return kk_failf("%s: bad argument", who);
+  if (s->encoder != encoder) return kk_failf("%s: the stream was created for the other direction", who);
+  if (s->frames > 0 && B != s->B) return kk_failf("%s: the batch size of a stream is fixed until it is reset", who);
+  if (workspace_bytes < kk_mimi_stream_workspace_bytes(s, B)) return kk_failf("%s: workspace too small", who);
   return 0;
 }
 // chunk frames of codes [B][nq][chunk] int32 -> pcm [B][chunk * samples_per_frame] float32; the stream's state lives in `s`
 // (library-owned device memory).  B is fixed by the first step after create / reset.  fp32 kernels.
 extern "C" int kk_mimi_decode_step(kk_mimi_stream* s, void* stream, int B, const int32_t* codes, void* workspace, size_t workspace_bytes, float* pcm_out) {
-  MM_TRY(step_check(s, false, B, codes, workspace, workspace_bytes, pcm_out, "kk_mimi_decode_step"));
+  KK_TRY(step_check(s, false, B, codes, workspace, workspace_bytes, pcm_out, "kk_mimi_decode_step"));
   s->B = B;
-  { std::lock_guard<std::mutex> lk(s->m->dbg_mu); s->m->dbg.clear(); }
-  Run r{s->m, (hipStream_t)stream, B, (char*)workspace, workspace_bytes, 0, false, false};
+  { std::lock_guard<std::mutex> lk(s->m->dbg_mu); s->m->dbg.map.clear(); }
+  Run r(s->m, (hipStream_t)stream, B, workspace, workspace_bytes);
   r.adt = KK_F32;
   return run_decode_step(r, s, codes, pcm_out);
 }
 // Mimi.encode_step (mimi.py:156-161): pcm [B][chunk * samples_per_frame] float32 -> codes [B][nq][chunk] int32
 extern "C" int kk_mimi_encode_step(kk_mimi_stream* s, void* stream, int B, const float* pcm, void* workspace, size_t workspace_bytes, int32_t* codes_out) {
-  MM_TRY(step_check(s, true, B, pcm, workspace, workspace_bytes, codes_out, "kk_mimi_encode_step"));
+  KK_TRY(step_check(s, true, B, pcm, workspace, workspace_bytes, codes_out, "kk_mimi_encode_step"));
   s->B = B;
-  { std::lock_guard<std::mutex> lk(s->m->dbg_mu); s->m->dbg.clear(); }
-  Run r{s->m, (hipStream_t)stream, B, (char*)workspace, workspace_bytes, 0, false, false};
+  { std::lock_guard<std::mutex> lk(s->m->dbg_mu); s->m->dbg.map.clear(); }
+  Run r(s->m, (hipStream_t)stream, B, workspace, workspace_bytes);
   r.adt = KK_F32;
   return run_encode_step(r, s, pcm, codes_out);
 }
@@ -1394,7 +1330,7 @@ extern "C" int kk_mimi_encode_frames(const kk_mimi* m, int N) { return (m && N >
 
 extern "C" size_t kk_mimi_encode_workspace_bytes(kk_mimi* m, int B, int N) {
   if (!m || !m->finalized || !m->has_encoder || B <= 0 || N <= 0) return 0;
-  Run r{m, nullptr, B, nullptr, 0, 0, true, false};
+  Run r(m, nullptr, B, nullptr, 0);
   if (run_encode(r, N, nullptr, nullptr) != 0) return 0;
   return r.used + 256;
 }
@@ -1405,8 +1341,8 @@ extern "C" int kk_mimi_encode(kk_mimi* m, void* stream, int B, int N, const floa
   if (!m->has_encoder) return kk_fail("kk_mimi_encode: the checkpoint held no encoder.* parameters");
   if (B <= 0 || N <= 0 || !pcm || !workspace || !codes_out) return kk_fail("kk_mimi_encode: bad argument");
   if (workspace_bytes < kk_mimi_encode_workspace_bytes(m, B, N)) return kk_fail("kk_mimi_encode: workspace too small");
-  { std::lock_guard<std::mutex> lk(m->dbg_mu); m->dbg.clear(); }
-  Run r{m, (hipStream_t)stream, B, (char*)workspace, workspace_bytes, 0, false, false};
+  { std::lock_guard<std::mutex> lk(m->dbg_mu); m->dbg.map.clear(); }
+  Run r(m, (hipStream_t)stream, B, workspace, workspace_bytes);
   return run_encode(r, N, pcm, codes_out);
 }
 
@@ -1414,19 +1350,10 @@ extern "C" int kk_mimi_encode(kk_mimi* m, void* stream, int B, int N, const floa
 extern "C" int kk_mimi_debug_info(kk_mimi* m, const char* name, int64_t* rows, int64_t* channels) {
   if (!m || !name) return kk_fail("kk_mimi_debug_info: bad argument");
   std::lock_guard<std::mutex> lk(m->dbg_mu);
-  auto it = m->dbg.find(name);
-  if (it == m->dbg.end()) return kk_fail("kk_mimi_debug_info: unknown stage");
-  if (rows) *rows = it->second.rows;
-  if (channels) *channels = it->second.C;
-  return 0;
+  return m->dbg.info("kk_mimi_debug_info", name, rows, channels);
 }
 extern "C" int kk_mimi_debug_fetch(kk_mimi* m, void* stream, const char* name, float* dst) {
   if (!m || !name || !dst) return kk_fail("kk_mimi_debug_fetch: bad argument");
   std::lock_guard<std::mutex> lk(m->dbg_mu);
-  auto it = m->dbg.find(name);
-  if (it == m->dbg.end()) return kk_fail("kk_mimi_debug_fetch: unknown stage");
-  const DebugBuf& d = it->second;
-  // any dtype / pitch -> dense fp32 [B][rows][C]
-  if (kk_launch_convert(d.p, d.dtype, d.bs, d.ld, dst, KK_F32, (long long)d.rows * d.C, d.C, d.C, d.rows, d.B, (hipStream_t)stream) != 0) return -1;
-  return 0;
+  return m->dbg.fetch("kk_mimi_debug_fetch", name, (hipStream_t)stream, dst);
 }

@@ -27,29 +27,13 @@ int kk_fail(const char* msg) {
   g_err = msg ? msg : "unknown error";
   return -1;
 }
-static int failf(const char* fmt, const std::string& a) {
-  char buf[512];
-  snprintf(buf, sizeof buf, fmt, a.c_str());
-  return kk_fail(buf);
-}
 extern "C" const char* kk_last_error(void) { return g_err.c_str(); }
 extern "C" int kk_abi_version(void) { return KK_ABI_VERSION; }
-
-#define KK_TRY(x)            \
-  do {                       \
-    int rc__ = (x);          \
-    if (rc__ != 0) return rc__; \
-  } while (0)
 
 // ------------------------------------------------------------------------------------------------
 // model structures
 // ------------------------------------------------------------------------------------------------
 namespace {
-
-struct HostTensor {
-  std::vector<float> d;
-  std::vector<int64_t> shape;
-};
 
 struct ConvW {  // packed [Kw][Cin][ldw] fp32 + bias
   size_t w_off = 0, b_off = 0;
@@ -71,14 +55,9 @@ struct ConvW {  // packed [Kw][Cin][ldw] fp32 + bias
   const uint4* q8 = nullptr;
   const unsigned char* s8 = nullptr;
 };
-struct VecW {
-  size_t off = 0;
-  int n = 0;
-  const float* p = nullptr;
-};
 struct LstmW {
   ConvW in;  // [1][I][8H], bias = b_ih + b_hh, columns dir*4H + gate row
-  VecW whT;  // [2][H][4H]
+  ArenaVec whT;  // [2][H][4H]
   int H = 0;
   // bf16 mode, H = 256: Wh as bf16 [2][4H][H] for the on-chip recurrence kernel
   bool has_whb = false;
@@ -94,53 +73,44 @@ struct ResBlk1d {  // AdainResBlk1d, istftnet.py:825-899
   bool up = false, learned = false;
   AdainRef n1, n2;
   ConvW conv1, conv2, sc;
-  VecW pool_w, pool_b;
+  ArenaVec pool_w, pool_b;
 };
 struct ResBlock1 {  // AdaINResBlock1, istftnet.py:341-396
   int C = 0, k = 0;
   int dil[3] = {1, 3, 5};
   ConvW c1[3], c2[3];
   AdainRef a1[3], a2[3];
-  VecW al1[3], al2[3];
-};
-
-struct DebugEntry {
-  void* p;
-  int ld;
-  long long bs;
-  int rows, C, dtype, B;
+  ArenaVec al1[3], al2[3];
 };
 
 }  // namespace
 
 struct kk_model {
   kk_config cfg;
-  std::map<std::string, HostTensor> host;
+  WeightArena arena;  // the packed fp32 parameters (host staging until kk_finalize, then the device copy)
   bool finalized = false;
-  std::vector<float> pack;  // host staging of all packed fp32 parameters
-  float* dev = nullptr;     // device copy of `pack`
   int adt = KK_F32;         // activation dtype
 
   // Albert
-  VecW emb_word, emb_pos, emb_type, emb_ln_w, emb_ln_b;
+  ArenaVec emb_word, emb_pos, emb_type, emb_ln_w, emb_ln_b;
   ConvW map_in, qkv, att_dense, ffn, ffn_out, bert_encoder;
-  VecW att_ln_w, att_ln_b, full_ln_w, full_ln_b;
+  ArenaVec att_ln_w, att_ln_b, full_ln_w, full_ln_b;
   // predictor
   std::vector<LstmW> dur_lstms;
   std::vector<AdainRef> dur_adaln;
   LstmW pred_lstm, shared_lstm, text_lstm;
-  VecW dur_W, dur_b;
+  ArenaVec dur_W, dur_b;
   ResBlk1d f0blk[3], nblk[3];
   ConvW f0_proj, n_proj;
   // text encoder
-  VecW te_emb;
+  ArenaVec te_emb;
   std::vector<ConvW> te_cnn;
-  std::vector<VecW> te_ln_w, te_ln_b;
+  std::vector<ArenaVec> te_ln_w, te_ln_b;
   // decoder
   ResBlk1d enc, dec[4];
   ConvW f0_conv, n_conv, asr_res;
   // generator
-  VecW lin_w;
+  ArenaVec lin_w;
   float lin_b = 0.f;
   ConvW noise_conv[4], ups[4], conv_post;
   ConvW noise_conv_rows[4];  // bf16 mode: the strided noise convs re-expressed as stride-1 convs over row groups (Packer::strided_rows)
@@ -148,7 +118,7 @@ struct kk_model {
   ResBlock1 noise_res[4];
   std::vector<ResBlock1> resblocks;
   // style projections (all AdaIN / AdaLN fc's), one matrix per style half
-  VecW sp_wT, sp_b, sd_wT, sd_b;  // prosody half (ref_s[128:]) / decoder half (ref_s[:128])
+  ArenaVec sp_wT, sp_b, sd_wT, sd_b;  // prosody half (ref_s[128:]) / decoder half (ref_s[:128])
   int Np = 0, Nd = 0;
 
   size_t head_wf_off = 0;       // conv_post in the fused head's fragment order (bf16), 0 = not eligible
@@ -161,7 +131,7 @@ struct kk_model {
 // one stream / thread at a time ("a kk_model is immutable after finalize and may be shared by threads using distinct streams + workspaces").
 struct kk_context {
   kk_model* m = nullptr;
-  std::map<std::string, DebugEntry> dbg;
+  DebugNotes dbg;
   std::map<std::string, const float*> dbg_over;
 
   // optional per-kernel-class timing (kk_profile_*): HIP events around every launch of a class
@@ -171,14 +141,8 @@ struct kk_context {
   bool prof_on = false;
   std::vector<hipEvent_t> prof_ev;  // pairs
   // graph replay of kk_forward (kk_set_graph_mode): one instantiated hipGraph per distinct argument tuple
-  struct GraphEntry {
-    std::vector<unsigned long long> key;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    int seen = 0;  // 1 = ran eagerly once (first-launch attribute calls are done), 2 = captured
-  };
   bool graph_mode = false;
-  std::vector<GraphEntry> graphs;
+  GraphCache graphs{16};
   unsigned long long* seed_dev = nullptr;  // the Philox seed of a replayed forward
   bool capturing = false;
   bool no_v4 = false;
@@ -187,7 +151,6 @@ struct kk_context {
                                 // (tests / A-B), 2 = never
   bool no_head_fusion = false;  // tests / A-B: stand-alone conv_post + iSTFT head kernels instead of the fused head (kk_head.hip)
   bool keep_debug = false;      // tests: also materialise the tensors fused kernels skip (conv_post)
-  hipStream_t cap_stream = nullptr;
   // side stream of a forward: branches that do not depend on each other (TextEncoder beside Albert / the duration stack; the harmonic source
   // beside the decoder) run concurrently -- the B = 1 latency is a chain of small kernels.  Fork / join through events, also inside a capture.
   hipStream_t side_stream = nullptr;
@@ -220,7 +183,7 @@ extern "C" int kk_create(const kk_config* cfg, kk_model** out) {
 
 extern "C" void kk_destroy(kk_model* m) {
   if (!m) return;
-  if (m->dev) (void)hipFree(m->dev);
+  if (m->arena.dev) (void)hipFree(m->arena.dev);
   delete m;
 }
 
@@ -246,12 +209,8 @@ extern "C" int kk_context_create(kk_model* m, kk_context** out) {
 extern "C" void kk_context_destroy(kk_context* cx) {
   if (!cx) return;
   for (hipEvent_t e : cx->prof_ev) (void)hipEventDestroy(e);
-  for (auto& g : cx->graphs) {
-    if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    if (g.graph) (void)hipGraphDestroy(g.graph);
-  }
+  cx->graphs.clear();
   if (cx->seed_dev) (void)hipFree(cx->seed_dev);
-  if (cx->cap_stream) (void)hipStreamDestroy(cx->cap_stream);
   if (cx->side_stream) (void)hipStreamDestroy(cx->side_stream);
   for (int i = 0; i < 2; ++i) {
     if (cx->side_fork[i]) (void)hipEventDestroy(cx->side_fork[i]);
@@ -321,7 +280,7 @@ extern "C" int kk_load_tensor(kk_model* m, const char* name, int dtype, const in
   else if (dtype == KK_DTYPE_BF16) for (size_t i = 0; i < n; ++i) t.d[i] = bf16_to_f32(((const uint16_t*)data)[i]);
   else if (dtype == KK_DTYPE_F16) for (size_t i = 0; i < n; ++i) t.d[i] = f16_to_f32(((const uint16_t*)data)[i]);
   else return kk_fail("kk_load_tensor: dtype must be F32, BF16 or F16");
-  m->host[nm] = std::move(t);
+  m->arena.host[nm] = std::move(t);
   return 0;
 }
 
@@ -332,24 +291,11 @@ namespace {
 
 struct Packer {
   kk_model* m;
-  std::string err;
-  bool ok() const { return err.empty(); }
-  size_t alloc(size_t n) {
-    size_t off = (m->pack.size() + 63) & ~(size_t)63;  // 256-byte alignment
-    m->pack.resize(off + n, 0.f);
-    return off;
-  }
-  const HostTensor* get(const std::string& name) {
-    auto it = m->host.find(name);
-    if (it == m->host.end()) {
-      if (err.empty()) err = "missing parameter: " + name;
-      return nullptr;
-    }
-    return &it->second;
-  }
+  WeightArena& a;  // m->arena
+  bool ok() const { return a.err.empty(); }
   // 3-D conv weight in MLX layout [A][K][C]; accepts the PyTorch layout [A][C][K] as well.
   bool conv3(const std::string& name, int A, int K, int C, std::vector<float>& out) {
-    const HostTensor* t = get(name);
+    const HostTensor* t = a.get(name, (size_t)A * K * C);
     if (!t) return false;
     out.assign((size_t)A * K * C, 0.f);
     if (t->shape.size() == 3 && t->shape[0] == A && t->shape[1] == K && t->shape[2] == C) {
@@ -362,36 +308,20 @@ struct Packer {
           for (int k = 0; k < K; ++k) out[((size_t)a * K + k) * C + c] = t->d[((size_t)a * C + c) * K + k];
       return true;
     }
-    if (err.empty()) err = "unexpected shape for " + name;
+    if (a.err.empty()) a.err = "unexpected shape for " + name;
     return false;
   }
-  bool vec(const std::string& name, size_t n, std::vector<float>& out) {
-    const HostTensor* t = get(name);
-    if (!t) return false;
-    if (t->d.size() != n) {
-      if (err.empty()) err = "unexpected size for " + name;
-      return false;
-    }
-    out = t->d;
-    return true;
+  bool read(const std::string& name, size_t n, std::vector<float>& out) {
+    const HostTensor* t = a.get(name, n);
+    if (t) out = t->d;
+    return t != nullptr;
   }
-  VecW put(const std::vector<float>& v) {
-    VecW r;
-    r.n = (int)v.size();
-    r.off = alloc(v.size());
-    memcpy(&m->pack[r.off], v.data(), v.size() * 4);
-    return r;
-  }
-  VecW put_named(const std::string& name, size_t n) {
-    std::vector<float> v;
-    if (!vec(name, n, v)) return VecW();
-    return put(v);
-  }
+  ArenaVec put(const std::vector<float>& v) { return a.put(v.data(), v.size()); }
   // weight_norm (istftnet.py:53-93 with dim=0): per leading index a, w = g[a] * v[a] / (||v[a]||_2 + 1e-7)
   bool folded(const std::string& prefix, int A, int K, int C, std::vector<float>& w) {
     std::vector<float> g;
     if (!conv3(prefix + ".weight_v", A, K, C, w)) return false;
-    if (!vec(prefix + ".weight_g", (size_t)A, g)) return false;
+    if (!read(prefix + ".weight_g", (size_t)A, g)) return false;
     for (int a = 0; a < A; ++a) {
       float ss = 0.f;
       float* row = &w[(size_t)a * K * C];
@@ -410,10 +340,10 @@ struct Packer {
     c.CinP = kk_cdiv(I, 64) * 64;
     c.CoutP = kk_cdiv(O, 128) * 128;
     const size_t nel = (size_t)K * c.CoutP * c.CinP;
-    c.wb_off = alloc((nel + 1) / 2);  // resize() zero-fills
-    c.wf_off = alloc((nel + 1) / 2);  // (may move the staging vector: take the pointers afterwards)
-    uint16_t* dst = (uint16_t*)&m->pack[c.wb_off];
-    uint16_t* dfr = (uint16_t*)&m->pack[c.wf_off];
+    c.wb_off = a.alloc((nel + 1) / 2);  // resize() zero-fills
+    c.wf_off = a.alloc((nel + 1) / 2);  // (may move the staging vector: take the pointers afterwards)
+    uint16_t* dst = (uint16_t*)&a.pack[c.wb_off];
+    uint16_t* dfr = (uint16_t*)&a.pack[c.wf_off];
     for (int o = 0; o < O; ++o)
       for (int k = 0; k < K; ++k)
         for (int i = 0; i < I; ++i) {
@@ -423,8 +353,8 @@ struct Packer {
         }
     if (K == 1 && I % 32 == 0) {  // Linear layers: the streaming kernel's pack (columns padded to 16 with zeros)
       const size_t nl = (size_t)kk_cdiv(O, 16) * 16 * I;
-      c.wl_off = alloc((nl + 1) / 2);
-      uint16_t* dl = (uint16_t*)&m->pack[c.wl_off];
+      c.wl_off = a.alloc((nl + 1) / 2);
+      uint16_t* dl = (uint16_t*)&a.pack[c.wl_off];
       for (int o = 0; o < O; ++o)
         for (int i = 0; i < I; ++i) dl[kk_linear_pack_index(o, i, I)] = f32_to_bf16_rne(wsrc[(size_t)o * I + i]);
     }
@@ -434,17 +364,17 @@ struct Packer {
   void pack_fp8(ConvW& c, const std::vector<float>& wsrc, int O, int I) {
     if (!m->q_group || m->adt != KK_BF16 || !kk_mxfp8_eligible(I, O) || I % m->q_group) return;
     const size_t qb = kk_mxfp8_q_bytes(O, I), sb = kk_mxfp8_s_bytes(O, I);
-    c.q8_off = alloc((qb + 3) / 4);
-    c.s8_off = alloc((sb + 3) / 4);
-    if (kk_mxfp8_pack_weight_host(wsrc.data(), O, I, m->q_group, (unsigned char*)&m->pack[c.q8_off], (unsigned char*)&m->pack[c.s8_off]) == 0)
+    c.q8_off = a.alloc((qb + 3) / 4);
+    c.s8_off = a.alloc((sb + 3) / 4);
+    if (kk_mxfp8_pack_weight_host(wsrc.data(), O, I, m->q_group, (unsigned char*)&a.pack[c.q8_off], (unsigned char*)&a.pack[c.s8_off]) == 0)
       c.fp8 = true;
   }
   // pack a conv weight given as wsrc[o][k][i] into [k][i][ldw]
   ConvW pack_oki(const std::vector<float>& wsrc, int O, int K, int I, const std::vector<float>* bias) {
     ConvW c;
     c.Cin = I; c.Cout = O; c.Kw = K; c.ldw = kk_cdiv(O, 64) * 64;
-    c.w_off = alloc((size_t)K * I * c.ldw);
-    float* dst = &m->pack[c.w_off];
+    c.w_off = a.alloc((size_t)K * I * c.ldw);
+    float* dst = &a.pack[c.w_off];
     for (int o = 0; o < O; ++o)
       for (int k = 0; k < K; ++k)
         for (int i = 0; i < I; ++i) dst[((size_t)k * I + i) * c.ldw + o] = wsrc[((size_t)o * K + k) * I + i];
@@ -452,8 +382,8 @@ struct Packer {
     if (bias) {
       c.has_bias = true;
       const int nb = c.mfma ? c.CoutP : O;
-      c.b_off = alloc(nb);
-      memcpy(&m->pack[c.b_off], bias->data(), (size_t)O * 4);
+      c.b_off = a.alloc(nb);
+      memcpy(&a.pack[c.b_off], bias->data(), (size_t)O * 4);
     }
     return c;
   }
@@ -461,7 +391,7 @@ struct Packer {
   ConvW convw(const std::string& prefix, int O, int K, int I, bool bias) {
     std::vector<float> w, b;
     if (!folded(prefix, O, K, I, w)) return ConvW();
-    if (bias && !vec(prefix + ".bias", (size_t)O, b)) return ConvW();
+    if (bias && !read(prefix + ".bias", (size_t)O, b)) return ConvW();
     return pack_oki(w, O, K, I, bias ? &b : nullptr);
   }
   // ConvWeighted used as conv_transpose1d (Generator.ups, istftnet.py:725-734,161-166): weight_v [Cin][K][Cout], norm over
@@ -469,7 +399,7 @@ struct Packer {
   ConvW convw_t(const std::string& prefix, int Cin, int K, int Cout) {
     std::vector<float> w, b;
     if (!folded(prefix, Cin, K, Cout, w)) return ConvW();
-    if (!vec(prefix + ".bias", (size_t)Cout, b)) return ConvW();
+    if (!read(prefix + ".bias", (size_t)Cout, b)) return ConvW();
     // re-index [i][k][o] as [o][k][i]: the packed forms ([k][i][o] fp32, [k][o][i] bf16) are the same for both kinds of conv
     std::vector<float> woki((size_t)Cout * K * Cin);
     for (int i = 0; i < Cin; ++i)
@@ -481,7 +411,7 @@ struct Packer {
   ConvW conv_plain(const std::string& prefix, int O, int K, int I) {
     std::vector<float> w, b;
     if (!conv3(prefix + ".weight", O, K, I, w)) return ConvW();
-    if (!vec(prefix + ".bias", (size_t)O, b)) return ConvW();
+    if (!read(prefix + ".bias", (size_t)O, b)) return ConvW();
     return pack_oki(w, O, K, I, &b);
   }
   // A strided conv (stride s, kernel K, padding pad) over rows of pitch `ld` reads, for output row q, the input rows
@@ -494,7 +424,7 @@ struct Packer {
     if (m->adt != KK_BF16) return c;
     std::vector<float> w, b;
     if (!conv3(prefix + ".weight", O, K, I, w)) return ConvW();
-    if (!vec(prefix + ".bias", (size_t)O, b)) return ConvW();
+    if (!read(prefix + ".bias", (size_t)O, b)) return ConvW();
     auto fdiv = [](int a, int d) { return a >= 0 ? a / d : -((-a + d - 1) / d); };
     const int tmin = fdiv(-pad, s), tmax = fdiv(K - 1 - pad, s);
     const int K2 = tmax - tmin + 1, I2 = s * ld;
@@ -505,10 +435,10 @@ struct Packer {
     c.CinP = kk_cdiv(I2, 64) * 64;
     c.CoutP = kk_cdiv(O, 128) * 128;
     const size_t nel = (size_t)K2 * c.CoutP * c.CinP;
-    c.wb_off = alloc((nel + 1) / 2);
-    c.wf_off = alloc((nel + 1) / 2);
-    uint16_t* dst = (uint16_t*)&m->pack[c.wb_off];
-    uint16_t* dfr = (uint16_t*)&m->pack[c.wf_off];
+    c.wb_off = a.alloc((nel + 1) / 2);
+    c.wf_off = a.alloc((nel + 1) / 2);
+    uint16_t* dst = (uint16_t*)&a.pack[c.wb_off];
+    uint16_t* dfr = (uint16_t*)&a.pack[c.wf_off];
     for (int o = 0; o < O; ++o)
       for (int t = 0; t < K; ++t) {
         const int tau = fdiv(t - pad, s), j = (t - pad) - tau * s;
@@ -519,15 +449,15 @@ struct Packer {
         }
       }
     c.has_bias = true;
-    c.b_off = alloc(c.CoutP);
-    memcpy(&m->pack[c.b_off], b.data(), (size_t)O * 4);
+    c.b_off = a.alloc(c.CoutP);
+    memcpy(&a.pack[c.b_off], b.data(), (size_t)O * 4);
     return c;
   }
   // nn.Linear: weight [O][I], bias [O]
   ConvW linear(const std::string& prefix, int O, int I, bool quantised = false) {
     std::vector<float> w, b;
-    if (!vec(prefix + ".weight", (size_t)O * I, w)) return ConvW();
-    if (!vec(prefix + ".bias", (size_t)O, b)) return ConvW();
+    if (!read(prefix + ".weight", (size_t)O * I, w)) return ConvW();
+    if (!read(prefix + ".bias", (size_t)O, b)) return ConvW();
     ConvW c = pack_oki(w, O, 1, I, &b);
     if (quantised) pack_fp8(c, w, O, I);
     return c;
@@ -540,10 +470,10 @@ struct Packer {
     const char* dirs[2] = {"forward", "backward"};
     for (int d = 0; d < 2; ++d) {
       std::vector<float> wx, wh, bi, bh;
-      if (!vec(prefix + ".Wx_" + dirs[d], (size_t)G * I, wx)) return l;
-      if (!vec(prefix + ".Wh_" + dirs[d], (size_t)G * H, wh)) return l;
-      if (!vec(prefix + ".bias_ih_" + dirs[d], (size_t)G, bi)) return l;
-      if (!vec(prefix + ".bias_hh_" + dirs[d], (size_t)G, bh)) return l;
+      if (!read(prefix + ".Wx_" + dirs[d], (size_t)G * I, wx)) return l;
+      if (!read(prefix + ".Wh_" + dirs[d], (size_t)G * H, wh)) return l;
+      if (!read(prefix + ".bias_ih_" + dirs[d], (size_t)G, bi)) return l;
+      if (!read(prefix + ".bias_hh_" + dirs[d], (size_t)G, bh)) return l;
       memcpy(&w[(size_t)d * G * I], wx.data(), wx.size() * 4);
       for (int g = 0; g < G; ++g) b[(size_t)d * G + g] = bi[g] + bh[g];  // mx.addmm(b_ih + b_hh, ...) modules.py:156-158
       for (int g = 0; g < G; ++g)
@@ -553,8 +483,8 @@ struct Packer {
     l.whT = put(whT);
     if (m->adt == KK_BF16 && H == 256) {
       l.has_whb = true;
-      l.whb_off = alloc(((size_t)2 * G * H + 1) / 2);
-      uint16_t* dst = (uint16_t*)&m->pack[l.whb_off];
+      l.whb_off = a.alloc(((size_t)2 * G * H + 1) / 2);
+      uint16_t* dst = (uint16_t*)&a.pack[l.whb_off];
       for (int d = 0; d < 2; ++d)
         for (int g = 0; g < G; ++g)
           for (int j = 0; j < H; ++j) dst[((size_t)d * G + g) * H + j] = f32_to_bf16_rne(whT[((size_t)d * H + j) * G + g]);
@@ -574,7 +504,7 @@ struct StyleBuilder {  // concatenates every `fc` of one style half into wT [128
     items.emplace_back(prefix, C);
     return r;
   }
-  bool build(Packer& P, VecW& wT, VecW& bias, int& N) {
+  bool build(Packer& P, ArenaVec& wT, ArenaVec& bias, int& N) {
     size_t n = 0;
     for (auto& it : items) n += 2 * (size_t)it.second;
     N = (int)n;
@@ -583,8 +513,8 @@ struct StyleBuilder {  // concatenates every `fc` of one style half into wT [128
     for (auto& it : items) {
       const int C2 = 2 * it.second;
       std::vector<float> w, b;
-      if (!P.vec(it.first + ".fc.weight", (size_t)C2 * 128, w)) return false;
-      if (!P.vec(it.first + ".fc.bias", (size_t)C2, b)) return false;
+      if (!P.read(it.first + ".fc.weight", (size_t)C2 * 128, w)) return false;
+      if (!P.read(it.first + ".fc.bias", (size_t)C2, b)) return false;
       for (int o = 0; o < C2; ++o) {
         Bv[off + o] = b[o];
         for (int j = 0; j < 128; ++j) W[(size_t)j * n + off + o] = w[(size_t)o * 128 + j];
@@ -607,7 +537,7 @@ ResBlk1d build_resblk1d(Packer& P, StyleBuilder& S, const std::string& p, int Ci
   if (r.learned) r.sc = P.convw(p + ".conv1x1", Cout, 1, Cin, false);
   if (up) {
     std::vector<float> w, b;
-    if (P.folded(p + ".pool", Cin, 3, 1, w) && P.vec(p + ".pool.bias", (size_t)Cin, b)) {
+    if (P.folded(p + ".pool", Cin, 3, 1, w) && P.read(p + ".pool.bias", (size_t)Cin, b)) {
       r.pool_w = P.put(w);  // [C][3]
       r.pool_b = P.put(b);
     }
@@ -625,26 +555,26 @@ ResBlock1 build_resblock1(Packer& P, StyleBuilder& S, const std::string& p, int 
     r.c2[j] = P.convw(p + ".convs2." + js, C, k, C, true);
     r.a1[j] = S.add(p + ".adain1." + js, C);
     r.a2[j] = S.add(p + ".adain2." + js, C);
-    r.al1[j] = P.put_named(p + ".alpha1." + js, (size_t)C);
-    r.al2[j] = P.put_named(p + ".alpha2." + js, (size_t)C);
+    r.al1[j] = P.a.vec(p + ".alpha1." + js, (size_t)C);
+    r.al2[j] = P.a.vec(p + ".alpha2." + js, (size_t)C);
   }
   return r;
 }
 
 void resolve(kk_model* m, ConvW& c) {
-  c.w = m->dev + c.w_off;
-  c.b = c.has_bias ? m->dev + c.b_off : nullptr;
-  c.wb = c.mfma ? (const bf16_t*)(m->dev + c.wb_off) : nullptr;
-  c.wf = c.mfma ? (const bf16_t*)(m->dev + c.wf_off) : nullptr;
-  c.wl = (c.mfma && c.wl_off) ? (const bf16_t*)(m->dev + c.wl_off) : nullptr;
-  c.q8 = c.fp8 ? (const uint4*)(m->dev + c.q8_off) : nullptr;
-  c.s8 = c.fp8 ? (const unsigned char*)(m->dev + c.s8_off) : nullptr;
+  c.w = m->arena.dev + c.w_off;
+  c.b = c.has_bias ? m->arena.dev + c.b_off : nullptr;
+  c.wb = c.mfma ? (const bf16_t*)(m->arena.dev + c.wb_off) : nullptr;
+  c.wf = c.mfma ? (const bf16_t*)(m->arena.dev + c.wf_off) : nullptr;
+  c.wl = (c.mfma && c.wl_off) ? (const bf16_t*)(m->arena.dev + c.wl_off) : nullptr;
+  c.q8 = c.fp8 ? (const uint4*)(m->arena.dev + c.q8_off) : nullptr;
+  c.s8 = c.fp8 ? (const unsigned char*)(m->arena.dev + c.s8_off) : nullptr;
 }
-void resolve(kk_model* m, VecW& v) { v.p = v.n ? m->dev + v.off : nullptr; }
+void resolve(kk_model* m, ArenaVec& v) { m->arena.resolve(v); }
 void resolve(kk_model* m, LstmW& l) {
   resolve(m, l.in);
   resolve(m, l.whT);
-  l.whb = l.has_whb ? (const void*)(m->dev + l.whb_off) : nullptr;
+  l.whb = l.has_whb ? (const void*)(m->arena.dev + l.whb_off) : nullptr;
 }
 void resolve(kk_model* m, ResBlk1d& r) {
   resolve(m, r.conv1); resolve(m, r.conv2);
@@ -663,15 +593,15 @@ extern "C" int kk_finalize(kk_model* m, void* stream) {
   if (!m) return kk_fail("kk_finalize: null model");
   if (m->finalized) return 0;
   const kk_config& c = m->cfg;
-  Packer P{m, ""};
+  Packer P{m, m->arena};
   StyleBuilder SP, SD;
   const int H = c.hidden_dim, S = c.style_dim, hs = c.plbert_hidden, E = c.plbert_embedding, DH = c.decoder_hidden;
   // ---- Albert (modules.py:438-649)
-  m->emb_word = P.put_named("bert.embeddings.word_embeddings.weight", (size_t)c.n_token * E);
-  m->emb_pos = P.put_named("bert.embeddings.position_embeddings.weight", (size_t)c.plbert_max_pos * E);
-  m->emb_type = P.put_named("bert.embeddings.token_type_embeddings.weight", (size_t)2 * E);
-  m->emb_ln_w = P.put_named("bert.embeddings.LayerNorm.weight", E);
-  m->emb_ln_b = P.put_named("bert.embeddings.LayerNorm.bias", E);
+  m->emb_word = P.a.vec("bert.embeddings.word_embeddings.weight", (size_t)c.n_token * E);
+  m->emb_pos = P.a.vec("bert.embeddings.position_embeddings.weight", (size_t)c.plbert_max_pos * E);
+  m->emb_type = P.a.vec("bert.embeddings.token_type_embeddings.weight", (size_t)2 * E);
+  m->emb_ln_w = P.a.vec("bert.embeddings.LayerNorm.weight", E);
+  m->emb_ln_b = P.a.vec("bert.embeddings.LayerNorm.bias", E);
   m->map_in = P.linear("bert.encoder.embedding_hidden_mapping_in", hs, E, true);
   const std::string lp = "bert.encoder.albert_layer_groups.0.albert_layers.0.";
   {
@@ -679,7 +609,7 @@ extern "C" int kk_finalize(kk_model* m, void* stream) {
     const char* nm[3] = {"query", "key", "value"};
     for (int i = 0; i < 3; ++i) {
       std::vector<float> wi, bi;
-      if (P.vec(lp + "attention." + nm[i] + ".weight", (size_t)hs * hs, wi) && P.vec(lp + "attention." + nm[i] + ".bias", hs, bi)) {
+      if (P.read(lp + "attention." + nm[i] + ".weight", (size_t)hs * hs, wi) && P.read(lp + "attention." + nm[i] + ".bias", hs, bi)) {
         memcpy(&w[(size_t)i * hs * hs], wi.data(), wi.size() * 4);
         memcpy(&b[(size_t)i * hs], bi.data(), bi.size() * 4);
       }
@@ -688,10 +618,10 @@ extern "C" int kk_finalize(kk_model* m, void* stream) {
     P.pack_fp8(m->qkv, w, 3 * hs, hs);
   }
   m->att_dense = P.linear(lp + "attention.dense", hs, hs, true);
-  m->att_ln_w = P.put_named(lp + "attention.LayerNorm.weight", hs);
-  m->att_ln_b = P.put_named(lp + "attention.LayerNorm.bias", hs);
-  m->full_ln_w = P.put_named(lp + "full_layer_layer_norm.weight", hs);
-  m->full_ln_b = P.put_named(lp + "full_layer_layer_norm.bias", hs);
+  m->att_ln_w = P.a.vec(lp + "attention.LayerNorm.weight", hs);
+  m->att_ln_b = P.a.vec(lp + "attention.LayerNorm.bias", hs);
+  m->full_ln_w = P.a.vec(lp + "full_layer_layer_norm.weight", hs);
+  m->full_ln_b = P.a.vec(lp + "full_layer_layer_norm.bias", hs);
   m->ffn = P.linear(lp + "ffn", c.plbert_intermediate, hs, true);
   m->ffn_out = P.linear(lp + "ffn_output", hs, c.plbert_intermediate, true);
   m->bert_encoder = P.linear("bert_encoder", H, hs, true);
@@ -704,13 +634,13 @@ extern "C" int kk_finalize(kk_model* m, void* stream) {
   m->shared_lstm = P.lstm("predictor.shared", H + S, H / 2);
   {  // stored transposed [H][max_dur]: the duration kernel's lanes (one per output bin) then read consecutive addresses
     std::vector<float> wd, wt((size_t)c.max_dur * H);
-    if (P.vec("predictor.duration_proj.linear_layer.weight", (size_t)c.max_dur * H, wd)) {
+    if (P.read("predictor.duration_proj.linear_layer.weight", (size_t)c.max_dur * H, wd)) {
       for (int o = 0; o < c.max_dur; ++o)
         for (int i = 0; i < H; ++i) wt[(size_t)i * c.max_dur + o] = wd[(size_t)o * H + i];
       m->dur_W = P.put(wt);
     }
   }
-  m->dur_b = P.put_named("predictor.duration_proj.linear_layer.bias", c.max_dur);
+  m->dur_b = P.a.vec("predictor.duration_proj.linear_layer.bias", c.max_dur);
   for (int which = 0; which < 2; ++which) {
     const std::string nm = which == 0 ? "predictor.F0" : "predictor.N";
     ResBlk1d* blk = which == 0 ? m->f0blk : m->nblk;
@@ -720,12 +650,12 @@ extern "C" int kk_finalize(kk_model* m, void* stream) {
     (which == 0 ? m->f0_proj : m->n_proj) = P.conv_plain(nm + "_proj", 1, 1, H / 2);
   }
   // ---- text encoder (modules.py:21-39)
-  m->te_emb = P.put_named("text_encoder.embedding.weight", (size_t)c.n_token * H);
+  m->te_emb = P.a.vec("text_encoder.embedding.weight", (size_t)c.n_token * H);
   for (int i = 0; i < c.n_layer; ++i) {
     const std::string is = std::to_string(i);
     m->te_cnn.push_back(P.convw("text_encoder.cnn." + is + ".0", H, c.text_encoder_kernel_size, H, true));
-    m->te_ln_w.push_back(P.put_named("text_encoder.cnn." + is + ".1.weight", H));
-    m->te_ln_b.push_back(P.put_named("text_encoder.cnn." + is + ".1.bias", H));
+    m->te_ln_w.push_back(P.a.vec("text_encoder.cnn." + is + ".1.weight", H));
+    m->te_ln_b.push_back(P.a.vec("text_encoder.cnn." + is + ".1.bias", H));
   }
   m->text_lstm = P.lstm("text_encoder.lstm", H, H / 2);
   // ---- decoder (istftnet.py:902-945)
@@ -739,7 +669,7 @@ extern "C" int kk_finalize(kk_model* m, void* stream) {
   const std::string g = "decoder.generator.";
   {
     std::vector<float> lw, lb;
-    if (P.vec(g + "m_source.l_linear.weight", 9, lw) && P.vec(g + "m_source.l_linear.bias", 1, lb)) {
+    if (P.read(g + "m_source.l_linear.weight", 9, lw) && P.read(g + "m_source.l_linear.bias", 1, lb)) {
       m->lin_w = P.put(lw);
       m->lin_b = lb[0];
     }
@@ -769,9 +699,9 @@ extern "C" int kk_finalize(kk_model* m, void* stream) {
       kk_head_eligible(m->conv_post.Cin, m->conv_post.Cout, m->conv_post.Kw, c.gen_istft_n_fft, c.gen_istft_hop_size)) {
     // the fused head (kk_head.hip) reads conv_post in its own fragment order: the same bf16 values as the MFMA pack
     const ConvW& cp = m->conv_post;
-    m->head_wf_off = P.alloc((kk_head_pack_elems() + 1) / 2);  // zero-filled: output columns 22..31 are padding
-    const uint16_t* src = (const uint16_t*)&m->pack[cp.wb_off];
-    uint16_t* dst = (uint16_t*)&m->pack[m->head_wf_off];
+    m->head_wf_off = P.a.alloc((kk_head_pack_elems() + 1) / 2);  // zero-filled: output columns 22..31 are padding
+    const uint16_t* src = (const uint16_t*)&P.a.pack[cp.wb_off];
+    uint16_t* dst = (uint16_t*)&P.a.pack[m->head_wf_off];
     for (int t = 0; t < cp.Kw; ++t)
       for (int o = 0; o < cp.Cout; ++o)
         for (int i = 0; i < cp.Cin; ++i) dst[kk_head_pack_index(t, o, i)] = src[((size_t)t * cp.CoutP + o) * cp.CinP + i];
@@ -780,20 +710,17 @@ extern "C" int kk_finalize(kk_model* m, void* stream) {
     SP.build(P, m->sp_wT, m->sp_b, m->Np);
     SD.build(P, m->sd_wT, m->sd_b, m->Nd);
   }
-  if (!P.ok()) return failf("kk_finalize: %s", P.err);
+  if (!P.ok()) return kk_failf("kk_finalize: %s", P.a.err.c_str());
 
   // ---- upload and resolve device pointers
-  if (hipMalloc((void**)&m->dev, m->pack.size() * sizeof(float)) != hipSuccess) return kk_fail("kk_finalize: hipMalloc failed");
-  if (hipMemcpyAsync(m->dev, m->pack.data(), m->pack.size() * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess)
-    return kk_fail("kk_finalize: upload failed");
-  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return kk_fail("kk_finalize: stream sync failed");
-  VecW* vecs[] = {&m->emb_word, &m->emb_pos, &m->emb_type, &m->emb_ln_w, &m->emb_ln_b, &m->att_ln_w, &m->att_ln_b, &m->full_ln_w,
+  KK_TRY(m->arena.upload((hipStream_t)stream, "kk_finalize"));
+  ArenaVec* vecs[] = {&m->emb_word, &m->emb_pos, &m->emb_type, &m->emb_ln_w, &m->emb_ln_b, &m->att_ln_w, &m->att_ln_b, &m->full_ln_w,
                   &m->full_ln_b, &m->dur_W, &m->dur_b, &m->te_emb, &m->lin_w, &m->sp_wT, &m->sp_b, &m->sd_wT, &m->sd_b};
-  for (VecW* v : vecs) resolve(m, *v);
+  for (ArenaVec* v : vecs) resolve(m, *v);
   ConvW* convs[] = {&m->map_in, &m->qkv, &m->att_dense, &m->ffn, &m->ffn_out, &m->bert_encoder, &m->f0_proj, &m->n_proj,
                     &m->f0_conv, &m->n_conv, &m->asr_res, &m->conv_post};
   for (ConvW* cw : convs) resolve(m, *cw);
-  m->head_wf = m->head_wf_off ? (const bf16_t*)(m->dev + m->head_wf_off) : nullptr;
+  m->head_wf = m->head_wf_off ? (const bf16_t*)(m->arena.dev + m->head_wf_off) : nullptr;
   for (auto& l : m->dur_lstms) resolve(m, l);
   resolve(m, m->pred_lstm); resolve(m, m->shared_lstm); resolve(m, m->text_lstm);
   for (int i = 0; i < 3; ++i) { resolve(m, m->f0blk[i]); resolve(m, m->nblk[i]); }
@@ -804,9 +731,6 @@ extern "C" int kk_finalize(kk_model* m, void* stream) {
   for (int i = 0; i < 4; ++i) resolve(m, m->dec[i]);
   for (int i = 0; i < c.n_upsamples; ++i) { resolve(m, m->noise_conv[i]); resolve(m, m->noise_conv_rows[i]); resolve(m, m->ups[i]); resolve(m, m->noise_res[i]); }
   for (auto& r : m->resblocks) resolve(m, r);
-  m->host.clear();
-  m->pack.clear();
-  m->pack.shrink_to_fit();
   m->finalized = true;
   return 0;
 }
@@ -856,12 +780,11 @@ struct ConvOpt {
   float post_slope = 1.f;   // MFMA variants 4 / 5: LeakyReLU(post_slope) of the FINAL stored value (after residual, scale, accumulate); 1 = none
 };
 
-struct Ctx {
+struct Ctx : Workspace {  // Workspace::raw never runs past `cap`: every entry point checks the workspace size up front
   kk_model* m;
   kk_context* cx = nullptr;  // the switches it carries shape the allocation plan too, so even a dry run has one
   hipStream_t st;
   hipStream_t main_st = nullptr;  // the caller's (or the capture) stream while a branch runs on the side stream
-  bool dry;
   // side branch k: fork_point(k) marks where its inputs are ready on the main stream; begin_side(k) ... end_side(k) brackets its launches
   // (they go to the model's side stream); join_side(k) makes the main stream wait for it.  All no-ops in a dry run / with the debug switch.
   // Not on the legacy NULL stream: an event recorded on / waited for by stream 0 did not order it against a non-blocking stream here (measured:
@@ -890,16 +813,9 @@ struct Ctx {
     if (!side_on()) return 0;
     return hipStreamWaitEvent(st, cx->side_join[k], 0) == hipSuccess ? 0 : kk_fail("kk_forward: hipStreamWaitEvent failed");
   }
-  char* base;
-  size_t cap, used = 0;
   int B;
   int adt;
 
-  void* raw(size_t bytes) {
-    const size_t off = (used + 255) & ~(size_t)255;
-    used = off + bytes;
-    return base ? base + off : nullptr;
-  }
   Buf act(int rows, int ld, int dtype = -1) {
     Buf b;
     b.dtype = dtype < 0 ? adt : dtype;
@@ -933,7 +849,7 @@ struct Ctx {
     auto it = cx->dbg_over.find(name);
     if (it != cx->dbg_over.end())
       KK_TRY(kk_launch_convert(it->second, KK_F32, (long long)b.rows * C, C, b.p, b.dtype, b.bs, b.ld, C, b.rows, B, st));
-    cx->dbg[name] = DebugEntry{b.p, b.ld, b.bs, b.rows, C, b.dtype, B};
+    cx->dbg.map[name] = DebugNote{b.p, b.ld, b.bs, b.rows, C, b.dtype, B};
     return 0;
   }
 
@@ -1077,7 +993,7 @@ struct Ctx {
     a.C = C; a.len = len; a.partial = fz_part; a.nchunk = last_ntiles; a.mean = mean; a.rstd = rstd; a.eps = 1e-5f; a.fused = 1;
     if (gb) {
       fz_flip ^= 1;
-      a.gb = gb; a.gbs = gbs; a.pa = fz_pa[fz_flip]; a.pb = fz_pb[fz_flip]; a.pstride = fz_stride; a.Cp = rup64(C);
+      a.gb = gb; a.gbs = gbs; a.pa = fz_pa[fz_flip]; a.pb = fz_pb[fz_flip]; a.pstride = fz_stride; a.Cp = rup(C, 64);
       *pa = a.pa; *pb = a.pb;
     }
     return kk_launch_norm_finalize(a, B, st);
@@ -1089,11 +1005,10 @@ struct Ctx {
     memset(&a, 0, sizeof a);
     fz_flip ^= 1;
     a.C = C; a.len = len; a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd); a.fused = 2; a.gb = gb; a.gbs = gbs;
-    a.pa = fz_pa[fz_flip]; a.pb = fz_pb[fz_flip]; a.pstride = fz_stride; a.Cp = rup64(C);
+    a.pa = fz_pa[fz_flip]; a.pb = fz_pb[fz_flip]; a.pstride = fz_stride; a.Cp = rup(C, 64);
     *pa = a.pa; *pb = a.pb;
     return kk_launch_norm_finalize(a, B, st);
   }
-  static int rup64(int v) { return (v + 63) / 64 * 64; }
 
   // scratch for instance-norm statistics, sized for the largest request seen in the dry run
   float* st_partial = nullptr;
@@ -1164,7 +1079,6 @@ struct Ctx {
   }
 };
 
-static int rup(int v, int m) { return (v + m - 1) / m * m; }
 
 // AdainResBlk1d (istftnet.py:825-899).  x: [B][Lmax_in][>=Cin]; out: channel slice receiving Cout channels at Lout rows.
 int run_resblk1d(Ctx& c, const ResBlk1d& r, const Buf& x, KKLen lin, int Lmax_in, const Buf& out, const float* style, int gbs,
@@ -1654,8 +1568,8 @@ int run_audio(Ctx& c, int Tmax, const int* lens, const float* ref_s, const int* 
 
 int check_common(kk_model* m, int B, int Tmax, const char* who) {
   if (!m) return kk_fail("null model");
-  if (!m->finalized) return failf("%s: kk_finalize has not been called", who);
-  if (B <= 0 || Tmax <= 0 || Tmax > 512 || Tmax > m->cfg.plbert_max_pos) return failf("%s: need 0 < B, 0 < Tmax <= 512 (kokoro.py:131-134)", who);
+  if (!m->finalized) return kk_failf("%s: kk_finalize has not been called", who);
+  if (B <= 0 || Tmax <= 0 || Tmax > 512 || Tmax > m->cfg.plbert_max_pos) return kk_failf("%s: need 0 < B, 0 < Tmax <= 512 (kokoro.py:131-134)", who);
   return 0;
 }
 
@@ -1747,53 +1661,19 @@ extern "C" int kk_forward(kk_context* cx, void* stream, int B, int Tmax, const i
       (unsigned long long)(uintptr_t)sine_noise, (unsigned long long)(uintptr_t)workspace, (unsigned long long)workspace_bytes,
       (unsigned long long)(uintptr_t)wav_out, (unsigned long long)(uintptr_t)pred_dur_out, (unsigned long long)(uintptr_t)nframes_out,
       (unsigned long long)(unsigned)cx->flags};
-  kk_context::GraphEntry* ge = nullptr;
-  for (auto& g : cx->graphs)
-    if (g.key == key) ge = &g;
-  if (!ge) {
-    if (cx->graphs.size() >= 16) {  // drop the oldest entry
-      if (cx->graphs.front().exec) (void)hipGraphExecDestroy(cx->graphs.front().exec);
-      if (cx->graphs.front().graph) (void)hipGraphDestroy(cx->graphs.front().graph);
-      cx->graphs.erase(cx->graphs.begin());
-    }
-    cx->graphs.emplace_back();
-    ge = &cx->graphs.back();
-    ge->key = key;
-  }
-  if (ge->seen == 0) {  // first sight of this argument tuple: run eagerly (one-time attribute calls must not land in a capture)
-    ge->seen = 1;
-    return eager(stream);
-  }
+  // the seed is the one by-value argument that changes between replays: a captured forward reads it from device memory
   if (!cx->seed_dev && hipMalloc((void**)&cx->seed_dev, 8) != hipSuccess) return kk_fail("kk_forward: hipMalloc(seed) failed");
-  if (ge->seen == 1) {
-    // capture on a private stream (the caller's may be the legacy default stream, which cannot be captured); nothing runs
-    // during capture, and the instantiated graph is launched on the caller's stream
-    if (!cx->cap_stream && hipStreamCreateWithFlags(&cx->cap_stream, hipStreamNonBlocking) != hipSuccess)
-      return kk_fail("kk_forward: hipStreamCreate failed");
-    if (hipStreamBeginCapture(cx->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess)
-      return kk_fail("kk_forward: hipStreamBeginCapture failed");
-    cx->capturing = true;
-    const int rc = eager((void*)cx->cap_stream);
+  auto work = [&](hipStream_t on_stream, bool capturing) -> int {
+    cx->capturing = capturing;
+    const int rc = eager((void*)on_stream);
     cx->capturing = false;
-    hipGraph_t g = nullptr;
-    const hipError_t e = hipStreamEndCapture(cx->cap_stream, &g);
-    if (rc != 0) {
-      if (g) (void)hipGraphDestroy(g);
-      return rc;
-    }
-    if (e != hipSuccess || !g) return kk_fail("kk_forward: hipStreamEndCapture failed");
-    hipGraphExec_t ex = nullptr;
-    if (hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) != hipSuccess) {
-      (void)hipGraphDestroy(g);
-      return kk_fail("kk_forward: hipGraphInstantiate failed");
-    }
-    ge->graph = g;
-    ge->exec = ex;
-    ge->seen = 2;
-  }
-  // the seed is the one by-value argument that changes between replays: it travels through device memory
+    return rc;
+  };
+  hipGraphExec_t ex = nullptr;
+  KK_TRY(cx->graphs.run(key, st, work, &ex, "kk_forward"));
+  if (!ex) return 0;  // ran eagerly
   KK_TRY(kk_launch_set_u64(cx->seed_dev, seed, st));
-  if (hipGraphLaunch(ge->exec, st) != hipSuccess) return kk_fail("kk_forward: hipGraphLaunch failed");
+  if (hipGraphLaunch(ex, st) != hipSuccess) return kk_fail("kk_forward: hipGraphLaunch failed");
   return 0;
 }
 
@@ -1993,18 +1873,11 @@ extern "C" int kk_op_conv_post_istft(void* stream, int B, const void* x, int ldx
 // ------------------------------------------------------------------------------------------------
 extern "C" int kk_debug_info(kk_context* cx, const char* name, int64_t* rows, int64_t* channels) {
   if (!cx || !name) return kk_fail("kk_debug_info: null argument");
-  auto it = cx->dbg.find(name);
-  if (it == cx->dbg.end()) return failf("kk_debug_info: no intermediate named %s in the last forward", name);
-  if (rows) *rows = it->second.rows;
-  if (channels) *channels = it->second.C;
-  return 0;
+  return cx->dbg.info("kk_debug_info", name, rows, channels);
 }
 extern "C" int kk_debug_fetch(kk_context* cx, void* stream, const char* name, float* dst) {
   if (!cx || !name || !dst) return kk_fail("kk_debug_fetch: null argument");
-  auto it = cx->dbg.find(name);
-  if (it == cx->dbg.end()) return failf("kk_debug_fetch: no intermediate named %s in the last forward", name);
-  const DebugEntry& e = it->second;
-  return kk_launch_convert(e.p, e.dtype, e.bs, e.ld, dst, KK_F32, (long long)e.rows * e.C, e.C, e.C, e.rows, e.B, (hipStream_t)stream);
+  return cx->dbg.fetch("kk_debug_fetch", name, (hipStream_t)stream, dst);
 }
 extern "C" int kk_debug_override(kk_context* cx, const char* name, const float* src) {
   if (!cx || !name || !src) return kk_fail("kk_debug_override: null argument");
@@ -2078,7 +1951,7 @@ extern "C" int kk_op_pack_w_frag(void* stream, const void* w_bf16, void* w_frag,
 extern "C" void kk_debug_clear(kk_context* cx) {
   if (!cx) return;
   cx->dbg_over.clear();
-  cx->dbg.clear();
+  cx->dbg.map.clear();
 }
 
 // ------------------------------------------------------------------------------------------------
