@@ -337,6 +337,32 @@ int kk_csm_debug_timestamps(unsigned long long* buf, int capacity);
 /* the sampler of generate_frame on its own (mlx_lm make_sampler(temp, top_k), sesame.py:335-336,719): logits [B][V] -> codes [B];
  * uniforms [B] or NULL (argmax).  Radix select of the top_k set + one-wave sort; V <= 8192. */
 int kk_op_csm_sample(void* stream, int B, int V, const float* logits, float temperature, int top_k, const float* uniforms, int32_t* codes_out);
+/* The kernels of the frame step on their own (tests), each through the launcher the frame runs.  Fragment pack of the bf16 weights (host):
+ * kk_csm_frag_choice gives the split-K slices and 16-column sub-blocks per block the generator picks for a K x N matrix (nsub = 0: no pack;
+ * split_ok: the matrix is a down projection, the one launched split-K); kk_csm_frag_pack lays w [K][N] fp32 out as bf16 (round to nearest
+ * even) [ceil(N / (16 nsub))][K / 32][nsub][64][8], lane L of chunk c, sub-block s = k 32 c + 8 (L / 16) + j, column 16 s + L % 16. */
+int kk_csm_frag_choice(int K, int N, int split_ok, int32_t* ks, int32_t* nsub);
+int kk_csm_frag_pack(const float* w, int K, int N, int nsub, uint16_t* out);
+/* Single-token GEMV on the matrix cores, out[m] = prologue(x[m]) W (+ res[m]): pro 0 plain, 1 RMSNorm with nw / eps (codes: rows gathered from
+ * emb, also written to gather_out), 2 silu(gate) * up of [gate | up] rows, 3 every `rows`-th row from emb by code (items of 1 or 2 rows); epi 0
+ * store, 1 + res; ks > 1 (epi 2): split-K, out[M][N] += the sum of the slices (part: ks M N floats).  Device pointers, row pitches in floats. */
+int kk_op_csm_gemv(void* stream, int pro, int epi, int ks, int nsub, int K, int N, int M, const void* w_frag, const float* x, long long xrs,
+                   const float* nw, float eps, const int32_t* codes, int cstride, int cb, int V, int rows, const float* emb, float* gather_out,
+                   const float* res, long long rrs, float* out, long long ors, float* part);
+/* the prompt block's GEMM: out[m] = x[m] W (+ res[m]) on a fragment pack */
+int kk_op_csm_gemm_prompt(void* stream, int K, int N, int M, int nsub, const void* w_frag, const float* x, long long xrs, const float* res,
+                          long long rrs, float* out, long long ors);
+/* fp32-weight skinny GEMM of the single-token steps: out[M][N] = x[M][K] w[K][ldw] (+ res); scratch: K slices x 16 x N floats */
+int kk_op_csm_linear_skinny(void* stream, int K, int N, int M, const float* w, int ldw, const float* x, const float* res, float* out, float* scratch,
+                            size_t scratch_floats);
+/* one new position per item: qkv [B][(H + 2 KV) hd], caches [B][max_pos][KV hd], rope [max_pos][hd / 2][2] cos | sin, pad [B] or NULL;
+ * RoPE + append at slot `offset`, causal GQA attention over slots >= pad[b] -> out [B][H hd].  form 0: the step's choice, 1 short-cache
+ * kernel (max_pos <= 64), 2 long-cache kernel + merge of its key splits (part: 8 B H (hd + 2) floats), 3 the general cache kernel */
+int kk_op_csm_attn_single(void* stream, int form, int B, int H, int KV, int hd, const float* qkv, float* kc, float* vc, int max_pos, int offset,
+                          const float* rope, const int32_t* pad, float* out, float* part);
+/* a block of S new positions per item: RoPE (q in place) + append at slots offset .. offset + S - 1, then causal attention -> out [B][S][H hd] */
+int kk_op_csm_attn_prompt(void* stream, int B, int S, int H, int KV, int hd, float* qkv, float* kc, float* vc, int max_pos, int offset, const float* rope,
+                          const int32_t* pad, float* out);
 
 #ifdef __cplusplus
 }

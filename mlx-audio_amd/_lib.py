@@ -100,6 +100,13 @@ SIGNATURES = {
     "kk_csm_debug_logits": (_i, [_vp, _vp, _i, _vp]),
     "kk_csm_debug_timestamps": (_i, [_vp, _i]),
     "kk_op_csm_sample": (_i, [_vp, _i, _i, _vp, _f, _i, _vp, _vp]),
+    "kk_csm_frag_choice": (_i, [_i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "kk_csm_frag_pack": (_i, [_vp, _i, _i, _i, _vp]),
+    "kk_op_csm_gemv": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, C.c_longlong, _vp, _f, _vp, _i, _i, _i, _i, _vp, _vp, _vp, C.c_longlong, _vp, C.c_longlong, _vp]),
+    "kk_op_csm_gemm_prompt": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong]),
+    "kk_op_csm_linear_skinny": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz]),
+    "kk_op_csm_attn_single": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "kk_op_csm_attn_prompt": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "kk_mimi_create": (_i, [C.POINTER(KKMimiConfig), C.POINTER(_vp)]),
     "kk_mimi_destroy": (None, [_vp]),
     "kk_mimi_load_tensor": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), _i, _vp]),

@@ -596,6 +596,13 @@ __global__ __launch_bounds__(HD) void attn_merge_kernel(const float* part, int H
   out[((long long)b * H + h) * HD + e] = den > 0.f ? num / den : 0.f;  // (no key at all: zero, as in the unsplit form)
 }
 #undef KK_LOAD_CHUNK
+// key splits of attn_decode_kernel: one per 2 chunks of the longest cache, at most 8 (the backbone's 2048 positions: 8 splits of 2 chunks;
+// short test stacks: 1-2)
+static int attn_nsplit(int max_pos, int hd) {
+  const int CHk = 8192 / hd, nchunks = (max_pos + CHk - 1) / CHk;
+  const int nsplit = (nchunks + 1) / 2;
+  return nsplit < 1 ? 1 : (nsplit > 8 ? 8 : nsplit);
+}
 static size_t attn_decode_lds_bytes(int hd, int G) {
   const size_t CH = 8192 / hd;
   return (CH * (hd + 4) + CH * hd + (size_t)G * hd + (size_t)G * CH + 2 * hd + 24) * 4;
@@ -1099,6 +1106,48 @@ int launch_gemmp(const GPArgs& g, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------------------- host
+// fp32 bits -> bf16 bits, round to nearest even (a NaN is truncated)
+static inline uint32_t bf16_round(uint32_t u) {
+  if ((u & 0x7FFFFFFFu) <= 0x7F800000u) u += 0x7FFFu + ((u >> 16) & 1u);
+  return u >> 16;
+}
+
+// The fragment pack of a K x N matrix: *nsub = 0 if it gets none.  Split-K for the deep projections (K >= 4096 in slices of 1024 rows), then
+// the widest column block (16 * nsub) that still gives ~200 workgroups; both depend on the matrix only, never on the batch.  (Measured: 2
+// instead of 4 sub-blocks for gate|up, i.e. 32-column blocks and more workgroups, cost +0.09 ms per frame.)  Only packs the GEMV can run:
+// split-K only where the step launches the matrix in that form (`split_ok`: the down projections), and a K slice too long for the launcher
+// takes more slices there, or leaves the matrix without a pack elsewhere (its stack then runs on the fp32 path, stack_can_step).
+static void frag_choice(int K, int N, bool split_ok, int* ks_out, int* nsub_out) {
+  *ks_out = 1; *nsub_out = 0;
+  if (K < 32 || K % 32 != 0 || N < 1) return;
+  int ks = 1;
+  if (split_ok) {
+    ks = (K >= 4096 && K % 1024 == 0) ? (K / 1024 > 16 ? 16 : K / 1024) : 1;
+    while (ks > 1 && (K % ks != 0 || (K / ks) % 32 != 0)) --ks;
+    for (int s = ks; !gm_slice_fits(4, K / ks) && s <= 16; ++s)
+      if (K % s == 0 && (K / s) % 32 == 0) ks = s;
+  }
+  if (!gm_slice_fits(4, K / ks)) return;
+  const int nb16 = (N + 15) / 16;
+  *ks_out = ks;
+  *nsub_out = nb16 * ks / 4 >= 192 ? 4 : (nb16 * ks / 2 >= 192 ? 2 : 1);
+}
+static size_t frag_elems(int K, int N, int nsub) { return (size_t)((N + 16 * nsub - 1) / (16 * nsub)) * K * 16 * nsub; }
+// w [K][ldw] fp32 -> out [N / (16 nsub)][K / 32][nsub][64 lanes][8] bf16 (RNE): lane L of chunk c, sub-block s holds k = 32 c + 8 (L / 16) + j,
+// n = 16 s + L % 16 of its column block; the columns that pad N to whole blocks are zero
+static void frag_pack(const float* w, int K, int N, long long ldw, int nsub, uint16_t* out) {
+  const int CBm = 16 * nsub, nblk = (N + CBm - 1) / CBm, nchunk = K / 32;
+  for (int i = 0; i < K; ++i) {
+    const int c = i >> 5, kq = (i & 31) >> 3, j = i & 7;
+    for (int o = 0; o < nblk * CBm; ++o) {
+      uint32_t u = 0;
+      if (o < N) memcpy(&u, &w[(size_t)i * ldw + o], 4);
+      const int nbk = o / CBm, sb = (o % CBm) >> 4, L = kq * 16 + (o & 15);
+      out[((((size_t)nbk * nchunk + c) * nsub + sb) * 64 + L) * 8 + j] = (uint16_t)bf16_round(u);
+    }
+  }
+}
+
 // host tensors are erased as soon as they are packed: peak host memory stays near one copy of the 1.6 B parameters
 struct Packer {
   kk_csm* m;
@@ -1108,8 +1157,9 @@ struct Packer {
     a.host.erase(name);
     return r;
   }
-  // nn.Linear weights [O_i][I] stacked along the output axis -> one [I][ldw] pack; `transposed_src`: the source is [I][O] (audio_head)
-  Lin linear(const std::vector<std::string>& names, const std::vector<int>& outs, int I, const float* raw = nullptr) {
+  // nn.Linear weights [O_i][I] stacked along the output axis -> one [I][ldw] pack; `raw`: the source is [I][O] (audio_head);
+  // `split_ok`: the single-token step launches this matrix in the split-K form too (the down projections)
+  Lin linear(const std::vector<std::string>& names, const std::vector<int>& outs, int I, const float* raw = nullptr, bool split_ok = false) {
     Lin l;
     int O = 0;
     for (int o : outs) O += o;
@@ -1141,31 +1191,16 @@ struct Packer {
       for (size_t e = 0; e < (size_t)I * l.ldw; ++e) {
         uint32_t u;
         memcpy(&u, &dst[e], 4);
-        if ((u & 0x7FFFFFFFu) <= 0x7F800000u) u += 0x7FFFu + ((u >> 16) & 1u);
-        u &= 0xFFFF0000u;
+        u = bf16_round(u) << 16;
         memcpy(&dst[e], &u, 4);
       }
-      if (I % 32 == 0) {
-        // fragment pack of gemvm_kernel.  Split-K for the deep projections (K >= 4096 in slices of 1024 rows), then the widest column
-        // block (16 * nsub) that still gives ~200 workgroups; both depend on the matrix only, never on the batch.  (Measured: 2 instead
-        // of 4 sub-blocks for gate|up, i.e. 32-column blocks and more workgroups, cost +0.09 ms per frame.)
-        l.ks = (I >= 4096 && I % 1024 == 0) ? (I / 1024 > 16 ? 16 : I / 1024) : 1;
-        while (l.ks > 1 && (I % l.ks != 0 || (I / l.ks) % 32 != 0)) --l.ks;
-        const int nb16 = (O + 15) / 16;
-        l.nsub = nb16 * l.ks / 4 >= 192 ? 4 : (nb16 * l.ks / 2 >= 192 ? 2 : 1);
-        const int CBm = 16 * l.nsub, nblk = (O + CBm - 1) / CBm, nchunk = I / 32;
+      int ks = 1, nsub = 0;
+      frag_choice(I, O, split_ok, &ks, &nsub);
+      if (nsub) {
+        l.ks = ks; l.nsub = nsub;
         l.moff = m->packb.size();
-        m->packb.resize(l.moff + (size_t)nblk * I * CBm, 0);
-        uint16_t* dm = &m->packb[l.moff];
-        for (int i = 0; i < I; ++i) {
-          const int c = i >> 5, kq = (i & 31) >> 3, j = i & 7;
-          for (int o = 0; o < O; ++o) {
-            uint32_t u;
-            memcpy(&u, &dst[(size_t)i * l.ldw + o], 4);
-            const int nbk = o / CBm, sb = (o % CBm) >> 4, L = kq * 16 + (o & 15);
-            dm[((((size_t)nbk * nchunk + c) * l.nsub + sb) * 64 + L) * 8 + j] = (uint16_t)(u >> 16);
-          }
-        }
+        m->packb.resize(l.moff + frag_elems(I, O, nsub));
+        frag_pack(dst, I, O, l.ldw, nsub, &m->packb[l.moff]);
       }
     }
     return l;
@@ -1202,7 +1237,7 @@ void pack_stack(Packer& P, const std::string& name, Stack& st, int max_pos) {
     L.qkv = P.linear({p + ".self_attn.q_proj.weight", p + ".self_attn.k_proj.weight", p + ".self_attn.v_proj.weight"}, {H * hd, KV * hd, KV * hd}, D);
     L.o = P.linear({p + ".self_attn.o_proj.weight"}, {D}, H * hd);
     L.gu = P.linear({p + ".mlp.gate_proj.weight", p + ".mlp.up_proj.weight"}, {I, I}, D);
-    L.down = P.linear({p + ".mlp.down_proj.weight"}, {D}, I);
+    L.down = P.linear({p + ".mlp.down_proj.weight"}, {D}, I, nullptr, true);
   }
   st.norm = P.vec(name + ".norm.weight", D);
   std::vector<float> th;
@@ -1227,6 +1262,39 @@ void resolve(kk_csm* m, ArenaVec& v) { m->arena.resolve(v); }
 void resolve(kk_csm* m, Stack& st) {
   for (auto& L : st.layers) { resolve(m, L.qkv); resolve(m, L.o); resolve(m, L.gu); resolve(m, L.down); resolve(m, L.n1); resolve(m, L.n2); }
   resolve(m, st.norm); resolve(m, st.rope);
+}
+
+// The skinny GEMM's K slices (fp32 weights, single-token steps): ~4 workgroups per CU (measured: fewer, longer slices are slower -- the kernel is
+// latency-bound); depends on the matrix only
+static void skinny_plan(int K, int N, int* KS_out, int* kchunk_out) {
+  const int nblk256 = kk_cdiv(N, 256);
+  int KS = 1024 / nblk256;
+  int maxks = kk_cdiv(K, 32);
+  if (maxks > 128) maxks = 128;  // deep, narrow matrices (down projections: K = 8192, N = 1024 / 2048) need the slices to fill the chip
+  KS = KS < 1 ? 1 : (KS > maxks ? maxks : KS);
+  const int kchunk = kk_cdiv(kk_cdiv(K, KS), 32) * 32;
+  *KS_out = kk_cdiv(K, kchunk);
+  *kchunk_out = kchunk;
+}
+// out[m][:] = x[m] W (+ res[m]) for Mtot contiguous rows, in launches of <= 16 rows; part: KS * 16 * N floats
+static int launch_skinny(const float* x, int Mtot, int K, int N, const float* w, int ldw, int KS, int kchunk, const float* res, float* out, float* part,
+                         hipStream_t st) {
+  const int nblk = kk_cdiv(N, 256);
+  for (int m0 = 0; m0 < Mtot; m0 += SK_MAXM) {
+    const int M = Mtot - m0 < SK_MAXM ? Mtot - m0 : SK_MAXM;
+    const float* xin = x + (size_t)m0 * K;
+    const dim3 g(nblk, KS), t(256);
+#define SK_GO(MT) hipLaunchKernelGGL((skinny_gemm_kernel<MT, false, false>), g, t, 0, st, xin, M, K, (const void*)w, ldw, N, kchunk, part)
+    // MT depends on the rows per launch only through "fits in 8": a row's arithmetic is the same in both instantiations
+    if (M <= 8) SK_GO(8); else SK_GO(16);
+#undef SK_GO
+    KK_CHECK_LAUNCH();
+    const float* resp = res ? res + (size_t)m0 * N : nullptr;
+    float* outp = out + (size_t)m0 * N;
+    hipLaunchKernelGGL(skinny_reduce_kernel, dim3((unsigned)(((long long)M * N + 255) / 256)), dim3(256), 0, st, part, KS, M, N, resp, outp);
+    KK_CHECK_LAUNCH();
+  }
+  return 0;
 }
 
 struct Run : Workspace {
@@ -1256,28 +1324,11 @@ struct Run : Workspace {
     if (xbs == (long long)rows * w.Cin && obs == (long long)rows * w.Cout && rows <= 2 && skinny_scratch) {
       // single-token steps (and the decoder's 2-token first step): the HBM-bound skinny GEMM (every CU streams a slice of W once for up
       // to 16 rows).  The choice depends on the rows PER ITEM only, never on B, so a stream's bits do not depend on its batch.
-      const int Mtot = B * rows, nblk256 = kk_cdiv(w.Cout, 256), nblk = nblk256;
-      int KS = 1024 / nblk256;  // ~4 workgroups per CU (measured: fewer, longer slices are slower -- the kernel is latency-bound)
-      int maxks = kk_cdiv(w.Cin, 32);
-      if (maxks > 128) maxks = 128;  // deep, narrow matrices (down projections: K = 8192, N = 1024 / 2048) need the slices to fill the chip
-      KS = KS < 1 ? 1 : (KS > maxks ? maxks : KS);
-      const int kchunk = kk_cdiv(kk_cdiv(w.Cin, KS), 32) * 32;
-      KS = kk_cdiv(w.Cin, kchunk);
+      const int Mtot = B * rows;
+      int KS, kchunk;
+      skinny_plan(w.Cin, w.Cout, &KS, &kchunk);
       if ((size_t)KS * SK_MAXM * w.Cout <= skinny_floats) {
-        for (int m0 = 0; m0 < Mtot; m0 += SK_MAXM) {
-          const int M = Mtot - m0 < SK_MAXM ? Mtot - m0 : SK_MAXM;
-          const float* xin = x + (size_t)m0 * w.Cin;
-          const dim3 g(nblk, KS), t(256);
-#define SK_GO(MT) hipLaunchKernelGGL((skinny_gemm_kernel<MT, false, false>), g, t, 0, st, xin, M, w.Cin, (const void*)w.w, w.ldw, w.Cout, kchunk, skinny_scratch)
-          // MT depends on the rows per launch only through "fits in 8": a row's arithmetic is the same in both instantiations
-          if (M <= 8) SK_GO(8); else SK_GO(16);
-#undef SK_GO
-          KK_CHECK_LAUNCH();
-          const float* resp = res ? res + (size_t)m0 * w.Cout : nullptr;
-          float* outp = out + (size_t)m0 * w.Cout;
-          hipLaunchKernelGGL(skinny_reduce_kernel, dim3((unsigned)(((long long)M * w.Cout + 255) / 256)), dim3(256), 0, st, skinny_scratch, KS, M, w.Cout, resp, outp);
-          KK_CHECK_LAUNCH();
-        }
+        KK_TRY(launch_skinny(x, Mtot, w.Cin, w.Cout, w.w, w.ldw, KS, kchunk, res, out, skinny_scratch, st));
         if (xn) {  // (one workgroup per row summing the slices AND normalising was tried: 17-38 us against 5 + 5 for the two launches)
           hipLaunchKernelGGL(rmsnorm_kernel, dim3(Mtot), dim3(256), 0, st, out, nw, w.Cout, eps, xn);
           KK_CHECK_LAUNCH();
@@ -1322,8 +1373,9 @@ int launch_gemvm(const Lin& w, int pro, int epi, FGArgs a, int Mtot, hipStream_t
   a.ts = ts_slot(); a.ts_id = (w.Cout << 4) | (pro << 2) | epi;
   const int CB = 16 * w.nsub, nblk = (w.Cout + CB - 1) / CB, kper = w.Cin / w.ks;
   const size_t lds = gm_lds_bytes(w.nsub, kper);
-  if (lds > 160 * 1024 || kper / 32 > 96) return kk_fail("kk_csm: internal: matrix-core GEMV: K slice too long for LDS");
-  if (pro == 3 && 8 % a.rows != 0) return kk_fail("kk_csm: internal: matrix-core GEMV: item rows");
+  if (!gm_slice_fits(w.nsub, kper)) return kk_fail("kk_csm: internal: matrix-core GEMV: K slice too long for LDS");
+  // PRO 3 reads an item's non-last rows from ONE x row per item (x + item * xrs): items of 1 or 2 rows only (the depth decoder's first step)
+  if (pro == 3 && a.rows != 1 && a.rows != 2) return kk_fail("kk_csm: internal: matrix-core GEMV: item rows");
   const dim3 grid(nblk, w.ks, (Mtot + 7) / 8);
   const int rounds = (kper / 32 + 31) / 32;  // straight-line rounds of 4 chunks x 8 waves (K slice <= 1024: one)
 #define GM_GO1(NSUB, PRO, EPI, RD)                                                                                                       \
@@ -1366,6 +1418,86 @@ int launch_gemv(const Lin& w, int pro, int epi, FGArgs a, int Mtot, hipStream_t 
   return launch_gemvm(w, pro, epi, a, Mtot, st);
 }
 
+// h[m][:] += x[m] W for M rows of N = w.Cout contiguous floats: EPI 1 in place, or for a split-K pack (w.ks > 1) the slices of an EPI 2 launch
+// into `part` ([ks][M][N]) and one combine (h += sum of the slices, slice order)
+int gemv_accumulate(const Lin& w, int pro, FGArgs g, int M, float* h, float* part, hipStream_t st) {
+  if (w.ks > 1) {  // deep projection: K slices over workgroups, then one small combine
+    g.out = part; g.ors = w.Cout; g.pss = (long long)M * w.Cout;
+    KK_TRY(launch_gemv(w, pro, 2, g, M, st));
+    const long long n = (long long)M * w.Cout;
+    hipLaunchKernelGGL(combine_slices_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, w.ks, n, n, h, ts_slot());
+    KK_CHECK_LAUNCH();
+    return 0;
+  }
+  g.res = h; g.rrs = w.Cout; g.out = h; g.ors = w.Cout;
+  return launch_gemv(w, pro, 1, g, M, st);
+}
+
+// The attention of one new position per item (qkv [B][(H + 2 KV) hd]) over a cache of max_pos slots, RoPE of q / the new key and the cache
+// append at slot offset (+ *pos_dev) inside.  `form`: ATTN_AUTO = the single-token step's choice -- attn_step_kernel for a short cache,
+// attn_decode_kernel (+ attn_merge_kernel over its key splits) for a long one, attn_cache_kernel<true> past G = 8 --, or a forced one.
+// attp: the key-split partials, 8 B H (hd + 2) floats.
+enum { ATTN_AUTO = 0, ATTN_STEP = 1, ATTN_DECODE = 2, ATTN_CACHE = 3 };
+int attn_single(int form, const float* qkv, int B, int H, int KV, int hd, const int* pos_dev, int offset, float* kc, float* vc, int max_pos,
+                const float* rope, const int* pad, float* att, float* attp, hipStream_t st) {
+  const int G = H / KV;
+  if (form == ATTN_AUTO) form = G > 8 ? ATTN_CACHE : (max_pos <= 64 ? ATTN_STEP : ATTN_DECODE);
+  if (form == ATTN_STEP) {
+    const size_t lds = attn_step_lds_bytes(max_pos, hd, G);
+    static KKDevOnce attr;
+    if (attr.first()) {
+      (void)hipFuncSetAttribute((const void*)attn_step_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_step_lds_bytes(64, 128, 8));
+      (void)hipFuncSetAttribute((const void*)attn_step_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_step_lds_bytes(64, 64, 8));
+      attr.done();
+    }
+    if (hd == 128)
+      hipLaunchKernelGGL(attn_step_kernel<128>, dim3(KV, B), dim3(256), lds, st, qkv, H, KV, pos_dev, offset, kc, vc, max_pos, 1.0f / sqrtf((float)hd), att, rope,
+                         pad, ts_slot());
+    else
+      hipLaunchKernelGGL(attn_step_kernel<64>, dim3(KV, B), dim3(256), lds, st, qkv, H, KV, pos_dev, offset, kc, vc, max_pos, 1.0f / sqrtf((float)hd), att, rope,
+                         pad, ts_slot());
+    KK_CHECK_LAUNCH();
+  } else if (form == ATTN_DECODE) {
+    const size_t lds = attn_decode_lds_bytes(hd, G);
+    static KKDevOnce attr;
+    if (attr.first()) {
+      (void)hipFuncSetAttribute((const void*)attn_decode_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_decode_lds_bytes(128, 8));
+      (void)hipFuncSetAttribute((const void*)attn_decode_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_decode_lds_bytes(64, 8));
+      attr.done();
+    }
+    const int nsplit = attn_nsplit(max_pos, hd);
+    if (nsplit > 1 && !attp) return kk_fail("kk_csm: internal: attention partials");
+    if (hd == 128)
+      hipLaunchKernelGGL(attn_decode_kernel<128>, dim3(KV, B, nsplit), dim3(256), lds, st, qkv, H, KV, pos_dev, offset, kc, vc, max_pos, 1.0f / sqrtf((float)hd),
+                         att, rope, pad, nsplit, attp);
+    else
+      hipLaunchKernelGGL(attn_decode_kernel<64>, dim3(KV, B, nsplit), dim3(256), lds, st, qkv, H, KV, pos_dev, offset, kc, vc, max_pos, 1.0f / sqrtf((float)hd),
+                         att, rope, pad, nsplit, attp);
+    KK_CHECK_LAUNCH();
+    if (nsplit > 1) {
+      if (hd == 128) hipLaunchKernelGGL(attn_merge_kernel<128>, dim3(H, B), dim3(128), 0, st, attp, H, G, nsplit, att);
+      else hipLaunchKernelGGL(attn_merge_kernel<64>, dim3(H, B), dim3(64), 0, st, attp, H, G, nsplit, att);
+    }
+    KK_CHECK_LAUNCH();
+  } else {
+    hipLaunchKernelGGL(attn_cache_kernel<true>, dim3(1, H, B), dim3(128), attn_lds_bytes(max_pos, hd), st, qkv, 1, H, KV, hd, pos_dev, offset, kc, vc, max_pos,
+                       1.0f / sqrtf((float)hd), att, 1, -1, rope, pad);
+    KK_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+// A block of S > 1 new positions per item: RoPE (q in place in qkv) + cache append, then causal attention of the block over the cache
+int attn_prompt(float* qkv, int B, int S, int H, int KV, int hd, const int* pos_dev, int offset, float* kc, float* vc, int max_pos, const float* rope,
+                const int* pad, float* att, hipStream_t st) {
+  hipLaunchKernelGGL(rope_append_kernel, dim3(S, B), dim3(256), 0, st, qkv, S, H, KV, hd, rope, pos_dev, offset, kc, vc, max_pos, pad);
+  KK_CHECK_LAUNCH();
+  hipLaunchKernelGGL(attn_cache_kernel<false>, dim3(S, H, B), dim3(128), attn_lds_bytes(max_pos, hd), st, qkv, S, H, KV, hd, pos_dev, offset, kc, vc, max_pos,
+                     1.0f / sqrtf((float)hd), att, 1, -1, (const float*)nullptr, pad);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
 // h [B][S][D] (updated in place) -> out [B][S][D] = final norm; appends S positions to the stack's cache at st.offset
 int stack_forward(Run& r, Stack& st, float* h, int S, int offset, float* out) {
   const kk_llama_args& a = st.a;
@@ -1389,17 +1521,10 @@ int stack_forward(Run& r, Stack& st, float* h, int S, int offset, float* out) {
     float* vc = st.vc + (size_t)l * r.m->max_batch * st.max_pos * KV * hd;
     KK_TRY(r.lin(L.qkv, x, (long long)S * D, S, qkv, (long long)S * W, nullptr));
     if (!r.dry) {
-      if (S == 1) {  // single-token step: RoPE + cache append inside the attention kernel
-        hipLaunchKernelGGL(attn_cache_kernel<true>, dim3(S, H, B), dim3(128), attn_lds_bytes(st.max_pos, hd), r.st, qkv, S, H, KV, hd, st.pos_dev,
-                           st.pos_dev ? 0 : offset, kc, vc, st.max_pos, 1.0f / sqrtf((float)hd), att, 1, -1, st.rope.p, st.pad_dev);
-        KK_CHECK_LAUNCH();
-      } else {
-        hipLaunchKernelGGL(rope_append_kernel, dim3(S, B), dim3(256), 0, r.st, qkv, S, H, KV, hd, st.rope.p, st.pos_dev, st.pos_dev ? 0 : offset, kc, vc, st.max_pos, st.pad_dev);
-        KK_CHECK_LAUNCH();
-        hipLaunchKernelGGL(attn_cache_kernel<false>, dim3(S, H, B), dim3(128), attn_lds_bytes(st.max_pos, hd), r.st, qkv, S, H, KV, hd, st.pos_dev,
-                           st.pos_dev ? 0 : offset, kc, vc, st.max_pos, 1.0f / sqrtf((float)hd), att, 1, -1, (const float*)nullptr, st.pad_dev);
-        KK_CHECK_LAUNCH();
-      }
+      if (S == 1)  // single-token step: RoPE + cache append inside the attention kernel
+        KK_TRY(attn_single(ATTN_CACHE, qkv, B, H, KV, hd, st.pos_dev, st.pos_dev ? 0 : offset, kc, vc, st.max_pos, st.rope.p, st.pad_dev, att, nullptr, r.st));
+      else
+        KK_TRY(attn_prompt(qkv, B, S, H, KV, hd, st.pos_dev, st.pos_dev ? 0 : offset, kc, vc, st.max_pos, st.rope.p, st.pad_dev, att, r.st));
     }
     // h += o(att); x = RMSNorm(h) (post_attention_layernorm)
     KK_TRY(r.lin(L.o, att, (long long)S * H * hd, S, h, (long long)S * D, h, L.n2.p, x, a.rms_eps));
@@ -1449,58 +1574,8 @@ int stack_step(Run& r, Stack& st, float* h, int rows, int offset, const FGArgs* 
     g.x = h; g.xrs = D; g.nw = L.n1.p; g.eps = a.rms_eps; g.out = qkv; g.ors = W;
     if (l == 0 && gather) { g.codes = gather->codes; g.cstride = gather->cstride; g.cb = gather->cb; g.V = gather->V; g.emb = gather->emb; g.gather_out = h; }
     KK_TRY(launch_gemv(L.qkv, 1, 0, g, M, r.st));
-    if (rows == 1 && st.max_pos <= 64 && H / KV <= 8) {
-      const size_t lds = attn_step_lds_bytes(st.max_pos, hd, H / KV);
-      static KKDevOnce attr;
-      if (attr.first()) {
-        (void)hipFuncSetAttribute((const void*)attn_step_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_step_lds_bytes(64, 128, 8));
-        (void)hipFuncSetAttribute((const void*)attn_step_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_step_lds_bytes(64, 64, 8));
-        attr.done();
-      }
-      if (hd == 128)
-        hipLaunchKernelGGL(attn_step_kernel<128>, dim3(KV, B), dim3(256), lds, r.st, qkv, H, KV, st.pos_dev, st.pos_dev ? 0 : offset, kc, vc, st.max_pos,
-                           1.0f / sqrtf((float)hd), att, st.rope.p, st.pad_dev, ts_slot());
-      else
-        hipLaunchKernelGGL(attn_step_kernel<64>, dim3(KV, B), dim3(256), lds, r.st, qkv, H, KV, st.pos_dev, st.pos_dev ? 0 : offset, kc, vc, st.max_pos,
-                           1.0f / sqrtf((float)hd), att, st.rope.p, st.pad_dev, ts_slot());
-      KK_CHECK_LAUNCH();
-    } else if (rows == 1 && H / KV <= 8) {
-      const size_t lds = attn_decode_lds_bytes(hd, H / KV);
-      static KKDevOnce attr;
-      if (attr.first()) {
-        (void)hipFuncSetAttribute((const void*)attn_decode_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_decode_lds_bytes(128, 8));
-        (void)hipFuncSetAttribute((const void*)attn_decode_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_decode_lds_bytes(64, 8));
-        attr.done();
-      }
-      // key splits: one per 2 chunks of the longest cache, at most 8 (the backbone's 2048 positions: 8 splits of 2 chunks; short test stacks: 1-2)
-      const int CHk = 8192 / hd, nchunks = (st.max_pos + CHk - 1) / CHk;
-      int nsplit = (nchunks + 1) / 2;
-      nsplit = nsplit < 1 ? 1 : (nsplit > 8 ? 8 : nsplit);
-      if (nsplit > 1 && !attp) return kk_fail("kk_csm: internal: attention partials");
-      if (hd == 128)
-        hipLaunchKernelGGL(attn_decode_kernel<128>, dim3(KV, B, nsplit), dim3(256), lds, r.st, qkv, H, KV, st.pos_dev, st.pos_dev ? 0 : offset, kc, vc, st.max_pos,
-                           1.0f / sqrtf((float)hd), att, st.rope.p, st.pad_dev, nsplit, attp);
-      else
-        hipLaunchKernelGGL(attn_decode_kernel<64>, dim3(KV, B, nsplit), dim3(256), lds, r.st, qkv, H, KV, st.pos_dev, st.pos_dev ? 0 : offset, kc, vc, st.max_pos,
-                           1.0f / sqrtf((float)hd), att, st.rope.p, st.pad_dev, nsplit, attp);
-      KK_CHECK_LAUNCH();
-      if (nsplit > 1) {
-        if (hd == 128) hipLaunchKernelGGL(attn_merge_kernel<128>, dim3(H, B), dim3(128), 0, r.st, attp, H, H / KV, nsplit, att);
-        else hipLaunchKernelGGL(attn_merge_kernel<64>, dim3(H, B), dim3(64), 0, r.st, attp, H, H / KV, nsplit, att);
-      }
-      KK_CHECK_LAUNCH();
-    } else if (rows == 1) {
-      hipLaunchKernelGGL(attn_cache_kernel<true>, dim3(1, H, B), dim3(128), attn_lds_bytes(st.max_pos, hd), r.st, qkv, 1, H, KV, hd, st.pos_dev,
-                         st.pos_dev ? 0 : offset, kc, vc, st.max_pos, 1.0f / sqrtf((float)hd), att, 1, -1, st.rope.p, st.pad_dev);
-      KK_CHECK_LAUNCH();
-    } else {
-      hipLaunchKernelGGL(rope_append_kernel, dim3(rows, B), dim3(256), 0, r.st, qkv, rows, H, KV, hd, st.rope.p, st.pos_dev, st.pos_dev ? 0 : offset, kc, vc,
-                         st.max_pos, st.pad_dev);
-      KK_CHECK_LAUNCH();
-      hipLaunchKernelGGL(attn_cache_kernel<false>, dim3(rows, H, B), dim3(128), attn_lds_bytes(st.max_pos, hd), r.st, qkv, rows, H, KV, hd, st.pos_dev,
-                         st.pos_dev ? 0 : offset, kc, vc, st.max_pos, 1.0f / sqrtf((float)hd), att, 1, -1, (const float*)nullptr, st.pad_dev);
-      KK_CHECK_LAUNCH();
-    }
+    if (rows == 1) KK_TRY(attn_single(ATTN_AUTO, qkv, B, H, KV, hd, st.pos_dev, st.pos_dev ? 0 : offset, kc, vc, st.max_pos, st.rope.p, st.pad_dev, att, attp, r.st));
+    else KK_TRY(attn_prompt(qkv, B, rows, H, KV, hd, st.pos_dev, st.pos_dev ? 0 : offset, kc, vc, st.max_pos, st.rope.p, st.pad_dev, att, r.st));
     memset(&g, 0, sizeof g);
     g.x = att; g.xrs = (long long)H * hd; g.res = h; g.rrs = D; g.out = h; g.ors = D;
     KK_TRY(launch_gemv(L.o, 0, 1, g, M, r.st));
@@ -1508,17 +1583,8 @@ int stack_step(Run& r, Stack& st, float* h, int rows, int offset, const FGArgs* 
     g.x = h; g.xrs = D; g.nw = L.n2.p; g.eps = a.rms_eps; g.out = gu; g.ors = 2 * I;
     KK_TRY(launch_gemv(L.gu, 1, 0, g, M, r.st));
     memset(&g, 0, sizeof g);
-    const int KS = L.down.ks;
-    if (KS > 1) {  // deep projection: K slices over workgroups, then one small combine (h += sum of the slices)
-      g.x = gu; g.xrs = 2 * I; g.out = part; g.ors = D; g.pss = (long long)M * D;
-      KK_TRY(launch_gemv(L.down, 2, 2, g, M, r.st));
-      const long long n = (long long)M * D;
-      hipLaunchKernelGGL(combine_slices_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r.st, part, KS, n, n, h, ts_slot());
-      KK_CHECK_LAUNCH();
-    } else {
-      g.x = gu; g.xrs = 2 * I; g.res = h; g.rrs = D; g.out = h; g.ors = D;
-      KK_TRY(launch_gemv(L.down, 2, 1, g, M, r.st));
-    }
+    g.x = gu; g.xrs = 2 * I;
+    KK_TRY(gemv_accumulate(L.down, 2, g, M, h, part, r.st));
   }
   return 0;
 }
@@ -1672,6 +1738,87 @@ int kk_launch_attn_cache(const float* qkv, int S, int H, int KV, int hd, int off
 extern "C" int kk_op_csm_sample(void* stream, int B, int V, const float* logits, float temperature, int top_k, const float* uniforms, int32_t* codes_out) {
   if (!logits || !codes_out || B < 1 || V < 1) return kk_fail("kk_op_csm_sample: bad argument");
   return launch_sample(logits, V, temperature, top_k, uniforms, 1, codes_out, 1, B, (hipStream_t)stream);
+}
+
+// ---- the kernels of the frame step on their own (tests): each entry point runs the launcher the frame runs, on caller-owned buffers
+extern "C" int kk_csm_frag_choice(int K, int N, int split_ok, int32_t* ks, int32_t* nsub) {
+  if (!ks || !nsub) return kk_fail("kk_csm_frag_choice: null argument");
+  int k = 1, s = 0;
+  frag_choice(K, N, split_ok != 0, &k, &s);
+  *ks = k; *nsub = s;
+  return 0;
+}
+
+extern "C" int kk_csm_frag_pack(const float* w, int K, int N, int nsub, uint16_t* out) {
+  if (!w || !out || K < 32 || K % 32 != 0 || N < 1 || (nsub != 1 && nsub != 2 && nsub != 4)) return kk_fail("kk_csm_frag_pack: bad argument");
+  frag_pack(w, K, N, N, nsub, out);
+  return 0;
+}
+
+extern "C" int kk_op_csm_gemv(void* stream, int pro, int epi, int ks, int nsub, int K, int N, int M, const void* w_frag, const float* x, long long xrs,
+                              const float* nw, float eps, const int32_t* codes, int cstride, int cb, int V, int rows, const float* emb, float* gather_out,
+                              const float* res, long long rrs, float* out, long long ors, float* part) {
+  if (!w_frag || !out || M < 1 || N < 1 || K < 32 || K % 32 != 0 || (nsub != 1 && nsub != 2 && nsub != 4)) return kk_fail("kk_op_csm_gemv: bad argument");
+  if (ks < 1 || ks > 16 || K % ks != 0 || (K / ks) % 32 != 0 || !gm_slice_fits(nsub, K / ks)) return kk_fail("kk_op_csm_gemv: K slices do not fit this K");
+  if (pro < 0 || pro > 3 || epi < 0 || epi > 2 || (epi == 2) != (ks > 1)) return kk_fail("kk_op_csm_gemv: form");
+  const bool gathered = (pro == 1 && codes) || pro == 3;
+  if ((!x && !(pro == 1 && codes)) || (x && (xrs < (pro == 2 ? 2LL * K : (long long)K) || xrs % 4 != 0))) return kk_fail("kk_op_csm_gemv: input rows");
+  if (gathered && (!codes || !emb || V < 1 || cb < 0 || cstride < 1)) return kk_fail("kk_op_csm_gemv: gathered rows");
+  if (pro == 1 && !nw) return kk_fail("kk_op_csm_gemv: norm weight");
+  if (epi == 1 && (!res || rrs < N)) return kk_fail("kk_op_csm_gemv: residual");
+  if (ors < N || (epi == 2 && (ors != N || res || !part))) return kk_fail("kk_op_csm_gemv: output");
+  Lin w;
+  w.Cin = K; w.Cout = N; w.wm = (const uint16_t*)w_frag; w.nsub = nsub; w.ks = ks;
+  FGArgs g;
+  memset(&g, 0, sizeof g);
+  g.x = x; g.xrs = xrs; g.nw = nw; g.eps = eps;
+  g.codes = codes; g.cstride = cstride; g.cb = cb; g.V = V; g.rows = rows; g.emb = emb; g.gather_out = gather_out;
+  g.res = res; g.rrs = rrs; g.out = out; g.ors = ors;
+  if (ks > 1) return gemv_accumulate(w, pro, g, M, out, part, (hipStream_t)stream);
+  return launch_gemv(w, pro, epi, g, M, (hipStream_t)stream);
+}
+
+extern "C" int kk_op_csm_gemm_prompt(void* stream, int K, int N, int M, int nsub, const void* w_frag, const float* x, long long xrs, const float* res,
+                                     long long rrs, float* out, long long ors) {
+  if (!w_frag || !x || !out || M < 1 || N < 1 || K < 32 || K % 32 != 0 || (nsub != 1 && nsub != 2 && nsub != 4) || xrs < K || xrs % 4 != 0 || ors < N ||
+      (res && rrs < N))
+    return kk_fail("kk_op_csm_gemm_prompt: bad argument");
+  GPArgs g;
+  memset(&g, 0, sizeof g);
+  g.x = x; g.xrs = xrs; g.w = (const uint16_t*)w_frag; g.K = K; g.N = N; g.M = M; g.nsub = nsub;
+  g.res = res; g.rrs = rrs; g.out = out; g.ors = ors;
+  return launch_gemmp(g, (hipStream_t)stream);
+}
+
+extern "C" int kk_op_csm_linear_skinny(void* stream, int K, int N, int M, const float* w, int ldw, const float* x, const float* res, float* out, float* scratch,
+                                       size_t scratch_floats) {
+  if (!w || !x || !out || !scratch || K < 1 || N < 1 || M < 1 || ldw < N) return kk_fail("kk_op_csm_linear_skinny: bad argument");
+  int KS, kchunk;
+  skinny_plan(K, N, &KS, &kchunk);
+  if ((size_t)KS * SK_MAXM * N > scratch_floats) return kk_failf("kk_op_csm_linear_skinny: scratch needs %zu floats", (size_t)KS * SK_MAXM * N);
+  return launch_skinny(x, M, K, N, w, ldw, KS, kchunk, res, out, scratch, (hipStream_t)stream);
+}
+
+extern "C" int kk_op_csm_attn_single(void* stream, int form, int B, int H, int KV, int hd, const float* qkv, float* kc, float* vc, int max_pos, int offset,
+                                     const float* rope, const int32_t* pad, float* out, float* part) {
+  if (!qkv || !kc || !vc || !rope || !out || B < 1 || H < 1 || KV < 1 || H % KV != 0 || offset < 0 || offset >= max_pos || form < 0 || form > 3)
+    return kk_fail("kk_op_csm_attn_single: bad argument");
+  if (hd != 64 && hd != 128) return kk_fail("kk_op_csm_attn_single: head_dim must be 64 or 128");
+  const int G = H / KV;
+  if (form == ATTN_AUTO) form = G > 8 ? ATTN_CACHE : (max_pos <= 64 ? ATTN_STEP : ATTN_DECODE);
+  if (form == ATTN_STEP && (max_pos > 64 || G > 8)) return kk_fail("kk_op_csm_attn_single: the short-cache kernel needs max_pos <= 64 and G <= 8");
+  if (form == ATTN_DECODE && (G > 8 || (attn_nsplit(max_pos, hd) > 1 && !part))) return kk_fail("kk_op_csm_attn_single: the long-cache kernel needs G <= 8 and partials");
+  if (form == ATTN_CACHE && attn_lds_bytes(max_pos, hd) > 64 * 1024) return kk_fail("kk_op_csm_attn_single: cache too long");
+  return attn_single(form, qkv, B, H, KV, hd, nullptr, offset, kc, vc, max_pos, rope, pad, out, part, (hipStream_t)stream);
+}
+
+extern "C" int kk_op_csm_attn_prompt(void* stream, int B, int S, int H, int KV, int hd, float* qkv, float* kc, float* vc, int max_pos, int offset, const float* rope,
+                                     const int32_t* pad, float* out) {
+  if (!qkv || !kc || !vc || !rope || !out || B < 1 || S < 1 || H < 1 || KV < 1 || H % KV != 0 || offset < 0 || offset + S > max_pos)
+    return kk_fail("kk_op_csm_attn_prompt: bad argument");
+  if (hd != 64 && hd != 128) return kk_fail("kk_op_csm_attn_prompt: head_dim must be 64 or 128");
+  if (attn_lds_bytes(max_pos, hd) > 64 * 1024) return kk_fail("kk_op_csm_attn_prompt: cache too long");
+  return attn_prompt(qkv, B, S, H, KV, hd, nullptr, offset, kc, vc, max_pos, rope, pad, out, (hipStream_t)stream);
 }
 
 extern "C" int kk_csm_create(const kk_csm_config* cfg, kk_csm** out) {

@@ -259,4 +259,6 @@ static size_t gm_lds_bytes(int nsub, int kper) {
   const size_t xb = (size_t)(kper / 32 + 1) * 2304, rb = (size_t)nsub * 4096;
   return (xb > rb ? xb : rb) + 256;
 }
+// a K slice of `kper` rows fits the launcher's limits: 160 KiB of LDS (kper <= 2240) and at most 3 straight-line rounds (kper <= 3072)
+static bool gm_slice_fits(int nsub, int kper) { return gm_lds_bytes(nsub, kper) <= 160 * 1024 && kper / 32 <= 96; }
 

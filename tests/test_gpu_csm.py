@@ -257,6 +257,43 @@ def test_csm_full_width_layers_split_k_and_wide_blocks_match_oracle():
         prev = ref
 
 
+def test_csm_hidden_2304_has_no_gemv_pack_and_runs_on_the_fp32_path():
+    """A backbone of hidden 2304 in bf16 weight mode: a K slice of 2304 rows does not fit the matrix-core GEMV's LDS and q|k|v, gate|up and the
+    projection are not launched split-K, so those matrices get no fragment pack (kk_csm_frag_choice) and the frames run on the fp32-weight path
+    instead of failing at frame time.  Prompt and two single-token frames against the fp32 oracle on a bf16 checkpoint: logits within 2e-4 of
+    their range, every code equal."""
+    from mlx_audio_amd.csm import SesameModel
+
+    cfg = P.csm_tiny_config()
+    cfg = dict(cfg, backbone=dict(cfg["backbone"], num_layers=1, hidden=2304, intermediate=512))
+    w = _as_bf16_checkpoint(P.csm_synth_checkpoint(cfg, 12))
+    rng = np.random.default_rng(51)
+    B, n = 2, cfg["audio_num_codebooks"]
+    orc = C.CsmOracle(w, cfg)
+    model = SesameModel(cfg, w, weight_dtype="bfloat16")
+    model.setup_caches(B)
+    tok, msk = _prompt(cfg, rng, B, 6, 3)
+    prev = None
+    for step in range(3):
+        if step == 0:
+            t_in, m_in, temp, u = tok, msk, 0.0, None
+        else:
+            t_in = np.zeros((B, 1, n + 1), np.int64)
+            t_in[:, 0, :n] = prev
+            m_in = np.zeros((B, 1, n + 1), np.float32)
+            m_in[:, 0, :n] = 1
+            temp, u = (0.9, rng.uniform(size=(B, n)).astype(np.float32)) if step == 1 else (0.0, None)
+        trace = {}
+        ref = orc.generate_frame(t_in, m_in, temp=temp, top_k=10, uniforms=u, trace=trace)
+        got = model.generate_frame(torch.tensor(t_in), torch.tensor(m_in), temperature=temp, top_k=10, uniforms=None if u is None else torch.tensor(u))
+        torch.cuda.synchronize()
+        e = err_stats(model.debug_logits().cpu().numpy(), np.stack([trace["c0_logits"]] + trace["ci_logits"], 0))
+        report(f"csm/hidden2304/frame{step}/logits", **e)
+        assert e["rel_max"] < 2e-4, (step, e)
+        np.testing.assert_array_equal(got.cpu().numpy(), ref)
+        prev = ref
+
+
 def test_csm_long_cache_single_token_attention_across_chunks():
     """The backbone's single-token attention over a cache longer than one chunk (attn_decode_kernel: 128 keys per chunk at head_dim 64, online
     softmax across chunks): a 125-position prompt, then six frames whose key counts run 126 .. 131 -- the new key in the last slot of a chunk, alone
