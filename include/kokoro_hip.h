@@ -30,6 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
+#define KK_ABI_MINOR 1   /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -132,6 +133,7 @@ int kk_quantized_layers(const kk_model* m);
 
 const char* kk_last_error(void);
 int kk_abi_version(void);
+int kk_abi_minor(void);
 
 /* ---- single-kernel entry points (used by the parity tests; same kernels kk_forward launches) ---- */
 
@@ -304,6 +306,30 @@ int kk_csm_load_tensor(kk_csm* m, const char* name, const int64_t* shape, int nd
  * bf16 checkpoints load_model keeps in their own dtype, tts/utils.py:217-262), 2-byte weight stream in the single-token steps with
  * SwiGLU applied while the down projection stages its input; activations, accumulation, KV cache, logits stay fp32.  Before finalize. */
 int kk_csm_set_weight_dtype(kk_csm* m, int dtype);
+/* A quantised nn.Linear / nn.Embedding of an MLX affine-quantised checkpoint (tts/utils.py:241-260; ABI minor 1): shape [O, I] of the
+ * DEquantised matrix, words uint32 [O][I bits / 32] (value j of a word in bits [j bits, (j + 1) bits)), scales / biases fp32 [O][I / group_size];
+ * w = scales * q + biases per group.  Host data, copied; before finalize; a name loaded both ways keeps the later call.  bits 2, 4 or 8.
+ * kk_csm_finalize then decides ONCE for the whole model: PACKED storage -- every Linear of the frame step (q|k|v, o, gate|up, down of both
+ * stacks, projection, codebook0_head) stays quantised in device memory and is decoded to bf16 inside the matrix-core kernels, as
+ * bf16_rne(fp32(q) * scale + bias) (fp32 multiply, fp32 add: the bf16 rounding of the dequantised matrix, so the frames carry the bits of bf16
+ * weight mode on the dequantised checkpoint), with no fp32 and no bf16 copy -- if all of them arrived quantised with bits 4 or 8, one (bits,
+ * group_size) per stacked matrix, group_size a multiple of 32 that divides I, and every one gets a fragment pack (kk_csm_frag_choice); otherwise
+ * the whole checkpoint is dequantised on the host and runs in bf16 weight mode.  Embedding tables are always dequantised into their fp32 tables. */
+int kk_csm_load_quantized(kk_csm* m, const char* name, const int64_t* shape, const uint32_t* words, const float* scales, const float* biases,
+                          int group_size, int bits);
+/* what kk_csm_finalize decided: one of KK_CSM_WEIGHTS_F32 / BF16 / Q8 / Q4, | KK_CSM_WEIGHTS_MIXED (packed, some Linears 8-bit and some 4-bit),
+ * | KK_CSM_WEIGHTS_DEQUANTIZED (a quantised checkpoint that fell back to host dequantisation; kk_csm_weight_fallback_reason says why); < 0: error */
+#define KK_CSM_WEIGHTS_F32 0
+#define KK_CSM_WEIGHTS_BF16 1
+#define KK_CSM_WEIGHTS_Q8 2
+#define KK_CSM_WEIGHTS_Q4 3
+#define KK_CSM_WEIGHTS_MIXED 0x100
+#define KK_CSM_WEIGHTS_DEQUANTIZED 0x200
+int kk_csm_weight_format(const kk_csm* m);
+const char* kk_csm_weight_fallback_reason(const kk_csm* m);
+/* device bytes held for the Linear matrices (fp32 copies, bf16 / quantised fragment packs, pairs) and for all weights (+ norms, embedding
+ * tables, RoPE tables, the projection table) */
+int kk_csm_weight_bytes(const kk_csm* m, size_t* linear_bytes, size_t* total_bytes);
 int kk_csm_finalize(kk_csm* m, void* stream);
 /* A second generator on the SAME device weights (immutable after kk_csm_finalize): own KV caches, positions, logits and graph cache, for another
    stream / thread in flight; `m` must outlive it; kk_csm_setup_caches before its first frame.  (The reference's SesameModel owns its caches,
@@ -343,12 +369,25 @@ int kk_op_csm_sample(void* stream, int B, int V, const float* logits, float temp
  * even) [ceil(N / (16 nsub))][K / 32][nsub][64][8], lane L of chunk c, sub-block s = k 32 c + 8 (L / 16) + j, column 16 s + L % 16. */
 int kk_csm_frag_choice(int K, int N, int split_ok, int32_t* ks, int32_t* nsub);
 int kk_csm_frag_pack(const float* w, int K, int N, int nsub, uint16_t* out);
+/* Quantised fragment pack (host) of one nn.Linear triplet, words [N][K bits / 32], scales / biases [N][K / group_size] (bits 4 or 8, group_size a
+ * multiple of 32 dividing K): q_out = the integers in the fragment order above, a lane's 8 values in 8 bytes (8-bit) or 4 bytes (4-bit), value j in
+ * bits [j bits, (j + 1) bits); pairs_out = float2 (scale, bias) [ceil(N / (16 nsub))][K / group_size][nsub][16 columns].  Padding columns: all zero
+ * (they decode to +0).  kk_csm_qfrag_bytes: K Npad bits / 8 and Npad (K / group_size) 8 bytes, Npad = N rounded up to 16 nsub. */
+int kk_csm_qfrag_bytes(int K, int N, int nsub, int group_size, int bits, size_t* q_bytes, size_t* pair_bytes);
+int kk_csm_qfrag_pack(const uint32_t* words, const float* scales, const float* biases, int K, int N, int nsub, int group_size, int bits, void* q_out,
+                      float* pairs_out);
 /* Single-token GEMV on the matrix cores, out[m] = prologue(x[m]) W (+ res[m]): pro 0 plain, 1 RMSNorm with nw / eps (codes: rows gathered from
  * emb, also written to gather_out), 2 silu(gate) * up of [gate | up] rows, 3 every `rows`-th row from emb by code (items of 1 or 2 rows); epi 0
  * store, 1 + res; ks > 1 (epi 2): split-K, out[M][N] += the sum of the slices (part: ks M N floats).  Device pointers, row pitches in floats. */
 int kk_op_csm_gemv(void* stream, int pro, int epi, int ks, int nsub, int K, int N, int M, const void* w_frag, const float* x, long long xrs,
                    const float* nw, float eps, const int32_t* codes, int cstride, int cb, int V, int rows, const float* emb, float* gather_out,
                    const float* res, long long rrs, float* out, long long ors, float* part);
+/* kk_op_csm_gemv on a quantised fragment pack + pairs (device): bit-identical to kk_op_csm_gemv on the bf16 pack of the dequantised matrix */
+int kk_op_csm_gemv_q(void* stream, int pro, int epi, int ks, int nsub, int K, int N, int M, const void* q_frag, const void* pairs, int group_size, int bits,
+                     const float* x, long long xrs, const float* nw, float eps, const int32_t* codes, int cstride, int cb, int V, int rows, const float* emb,
+                     float* gather_out, const float* res, long long rrs, float* out, long long ors, float* part);
+int kk_op_csm_gemm_prompt_q(void* stream, int K, int N, int M, int nsub, const void* q_frag, const void* pairs, int group_size, int bits, const float* x,
+                            long long xrs, const float* res, long long rrs, float* out, long long ors);
 /* the prompt block's GEMM: out[m] = x[m] W (+ res[m]) on a fragment pack */
 int kk_op_csm_gemm_prompt(void* stream, int K, int N, int M, int nsub, const void* w_frag, const float* x, long long xrs, const float* res,
                           long long rrs, float* out, long long ors);

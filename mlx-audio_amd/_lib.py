@@ -9,6 +9,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libkokoro_hip.so")
 
 KK_F32, KK_BF16, KK_I32, KK_F16 = 0, 1, 2, 3
+CSM_WEIGHTS = {0: "f32", 1: "bf16", 2: "q8", 3: "q4"}  # kk_csm_weight_format
+CSM_WEIGHTS_MIXED, CSM_WEIGHTS_DEQUANTIZED = 0x100, 0x200
 NOISE_ZERO, NOISE_INJECTED, NOISE_PHILOX = 0, 1, 2
 ACT_NONE, ACT_LRELU, ACT_GELU, ACT_SNAKE = 0, 1, 2, 3
 
@@ -64,6 +66,7 @@ SIGNATURES = {
     "kk_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _u64, _vp, _sz, _vp, _vp, _vp]),
     "kk_last_error": (C.c_char_p, []),
     "kk_abi_version": (_i, []),
+    "kk_abi_minor": (_i, []),
     "kk_op_conv1d": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _vp, _i, _f, _i, _vp, _i, _i, _vp, _i, _i]),
     "kk_op_conv1d_bf16": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _vp, _i, _f, _i, _vp, _i, _i, _vp, _i]),
     "kk_op_conv1d_bf16_fused": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _vp, _vp, _i, _f,
@@ -88,6 +91,10 @@ SIGNATURES = {
     "kk_csm_destroy": (None, [_vp]),
     "kk_csm_load_tensor": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), _i, _vp]),
     "kk_csm_set_weight_dtype": (_i, [_vp, _i]),
+    "kk_csm_load_quantized": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), _vp, _vp, _vp, _i, _i]),
+    "kk_csm_weight_format": (_i, [_vp]),
+    "kk_csm_weight_fallback_reason": (C.c_char_p, [_vp]),
+    "kk_csm_weight_bytes": (_i, [_vp, C.POINTER(_sz), C.POINTER(_sz)]),
     "kk_csm_finalize": (_i, [_vp, _vp]),
     "kk_csm_share": (_i, [_vp, C.POINTER(_vp)]),
     "kk_csm_setup_caches": (_i, [_vp, _i]),
@@ -102,6 +109,11 @@ SIGNATURES = {
     "kk_op_csm_sample": (_i, [_vp, _i, _i, _vp, _f, _i, _vp, _vp]),
     "kk_csm_frag_choice": (_i, [_i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "kk_csm_frag_pack": (_i, [_vp, _i, _i, _i, _vp]),
+    "kk_csm_qfrag_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(_sz), C.POINTER(_sz)]),
+    "kk_csm_qfrag_pack": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "kk_op_csm_gemv_q": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, C.c_longlong, _vp, _f, _vp, _i, _i, _i, _i, _vp, _vp, _vp, C.c_longlong, _vp,
+                              C.c_longlong, _vp]),
+    "kk_op_csm_gemm_prompt_q": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong]),
     "kk_op_csm_gemv": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, C.c_longlong, _vp, _f, _vp, _i, _i, _i, _i, _vp, _vp, _vp, C.c_longlong, _vp, C.c_longlong, _vp]),
     "kk_op_csm_gemm_prompt": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong]),
     "kk_op_csm_linear_skinny": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz]),
@@ -174,7 +186,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 1:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

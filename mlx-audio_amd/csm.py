@@ -23,7 +23,18 @@ def _llama_args(d: dict) -> _lib.KKLlamaArgs:
 
 
 class SesameModel:
-    def __init__(self, cfg: dict, weights: Optional[Dict[str, np.ndarray]] = None, device: str = "cuda:0", weight_dtype: str = "float32"):
+    def __init__(self, cfg: dict, weights: Optional[Dict[str, np.ndarray]] = None, device: str = "cuda:0", weight_dtype: str = "float32",
+                 quantization: Optional[dict] = None, weight_storage: str = "packed"):
+        """quantization: config["quantization"] of an MLX affine-quantised checkpoint ({"group_size", "bits"} + per-layer overrides); `weights`
+        then holds `{p}.weight` (uint32) / `{p}.scales` / `{p}.biases` triplets.  weight_storage "packed" (default): the Linears stay quantised
+        in device memory and are decoded inside the matrix-core kernels (kk_csm_load_quantized) -- the bits of bf16 weight mode on the
+        dequantised checkpoint; where the library cannot do that for the whole model it dequantises on the host (`weight_fallback` says
+        why).  "dequantized": dequantise here and run bf16 weight mode."""
+        if weight_storage not in ("packed", "dequantized"):
+            raise ValueError(f"weight_storage must be 'packed' or 'dequantized', not {weight_storage!r}")
+        self.quantization, self.weight_storage = quantization, weight_storage
+        if quantization is not None:
+            weight_dtype = "bfloat16"  # the arithmetic of a quantised checkpoint: fp32 on the bf16 rounding of scale * q + bias
         self.cfg = cfg
         self.lib = _lib.load()
         if not torch.cuda.is_available():
@@ -76,7 +87,24 @@ class SesameModel:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def load_weights(self, weights: Dict[str, np.ndarray]) -> "SesameModel":
+        triplets = {}
+        if self.quantization is not None:
+            from .quant import dequantize_affine, split_triplets
+
+            q = self.quantization
+            per_layer = {k: v for k, v in q.items() if k not in ("group_size", "bits")}
+            weights, triplets = split_triplets(weights, int(q["group_size"]), int(q["bits"]), per_layer)
+            if self.weight_storage == "dequantized":
+                weights = dict(weights, **{k: dequantize_affine(*t) for k, t in triplets.items()})
+                triplets = {}
         with torch.cuda.device(self.device):
+            for name, (words, scales, biases, group, bits) in triplets.items():
+                O, I = words.shape[0], words.shape[1] * (32 // bits)
+                if scales.shape != (O, I // group) or biases.shape != scales.shape:
+                    raise ValueError(f"{name}: scales / biases {scales.shape} do not match [{O}, {I}] at group size {group}")
+                shp = (C.c_int64 * 2)(O, I)
+                check(self.lib.kk_csm_load_quantized(self._h, name.encode(), shp, words.ctypes.data_as(C.c_void_p), scales.ctypes.data_as(C.c_void_p),
+                                                     biases.ctypes.data_as(C.c_void_p), group, bits), "kk_csm_load_quantized")
             for name, arr in weights.items():
                 a = np.ascontiguousarray(np.asarray(arr, np.float32))
                 shp = (C.c_int64 * a.ndim)(*a.shape)
@@ -84,6 +112,29 @@ class SesameModel:
             check(self.lib.kk_csm_finalize(self._h, self._stream()), "kk_csm_finalize")
         self._final = True
         return self
+
+    @property
+    def weight_format(self) -> str:
+        """kk_csm_weight_format: "f32", "bf16", "q8", "q4" ("q8+q4": packed, per-layer overrides mix the two)."""
+        f = int(self.lib.kk_csm_weight_format(self._h))
+        if f < 0:
+            check(1, "kk_csm_weight_format")
+        return "q8+q4" if f & _lib.CSM_WEIGHTS_MIXED else _lib.CSM_WEIGHTS[f & 0xFF]
+
+    @property
+    def weight_fallback(self) -> Optional[str]:
+        """None, or why a quantised checkpoint was dequantised on the host instead of staying packed."""
+        f = int(self.lib.kk_csm_weight_format(self._h))
+        if f < 0 or not f & _lib.CSM_WEIGHTS_DEQUANTIZED:
+            return None
+        return (self.lib.kk_csm_weight_fallback_reason(self._h) or b"").decode() or "fell back to dequantised"
+
+    @property
+    def weight_bytes(self) -> Dict[str, int]:
+        """kk_csm_weight_bytes: device bytes held for the Linear matrices / for all weights."""
+        lin, tot = C.c_size_t(0), C.c_size_t(0)
+        check(self.lib.kk_csm_weight_bytes(self._h, C.byref(lin), C.byref(tot)), "kk_csm_weight_bytes")
+        return {"linear": int(lin.value), "total": int(tot.value)}
 
     # ---- sesame.py:320-345
     def setup_caches(self, max_batch_size: int) -> None:

@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -32,8 +33,20 @@ struct Lin {  // generic-kernel pack [1][Cin][ldw]
   // load of 1 KiB is one 32 x 16 B operand of v_mfma_f32_16x16x32_bf16 (lane L: k = 32 c + 8 (L / 16) + j, n = 16 s + L % 16)
   size_t moff = 0;
   const uint16_t* wm = nullptr;
+  bool has_f32 = true;
   int nsub = 0;  // 0 = no fragment pack (K not a multiple of 32)
   int ks = 1;    // split-K slices of a deep projection (K >= 4096): partial tiles + combine
+  // packed storage of a quantised checkpoint (kk_csm_load_quantized): `wm` points at the quantised fragment pack instead (kk_csm_gemvm.h,
+  // KK_WF_Q8 / KK_WF_Q4), `wp` at its (scale, bias) pairs; such a matrix has NO fp32 copy (w == nullptr) and no bf16 one
+  int fmt = KK_WF_BF16, group = 0;
+  size_t qoff = 0, poff = 0;  // byte offsets into kk_csm::packq
+  const float2* wp = nullptr;
+};
+// a quantised nn.Linear / nn.Embedding as the checkpoint holds it (host, until finalize)
+struct QHost {
+  int O = 0, I = 0, group = 0, bits = 0;
+  std::vector<uint32_t> words;       // [O][I * bits / 32]
+  std::vector<float> scales, biases; // [O][I / group]
 };
 struct LlamaLayer {
   Lin qkv, o, gu, down;
@@ -59,6 +72,15 @@ struct kk_csm {
   int wdt = KK_F32;              // weight storage of the single-token steps (KK_F32 / KK_BF16)
   std::vector<uint16_t> packb;   // host staging of the bf16 copies
   uint16_t* devb = nullptr;
+  // quantised checkpoint: tensors as loaded; the packed Linears' integer fragment packs + pairs (bytes; shared like devb)
+  std::map<std::string, QHost> qhost;
+  std::vector<uint8_t> packq;
+  uint8_t* devq = nullptr;
+  bool packed = false;           // kk_csm_finalize's all-or-nothing decision: every Linear of the fast path runs from its quantised pack
+  bool q_fallback = false;       // a quantised checkpoint that was dequantised on the host instead (bf16 weight mode)
+  std::string q_reason;          // why
+  int n_q8 = 0, n_q4 = 0;        // packed Linears per format
+  size_t linear_bytes = 0, table_bytes = 0, total_bytes = 0;  // device bytes of the Linears' storage / of the projection table
   Stack bb, dec;
   ArenaVec text_emb, audio_emb;
   Lin proj, c0_head;
@@ -73,7 +95,7 @@ struct kk_csm {
   // synchronous hipMemset / hipMemcpy here would touch the legacy stream and break another thread's graph capture)
   bool reset_pending = false, pad_pending = false;
   std::vector<int32_t> pad_host;
-  const kk_csm* weights_of = nullptr;  // kk_csm_share: `dev` / `devb` belong to that generator (immutable after finalize), not to this one
+  const kk_csm* weights_of = nullptr;  // kk_csm_share: `dev` / `devb` / `devq` belong to that generator (immutable after finalize), not to this one
 };
 
 namespace {
@@ -972,11 +994,15 @@ __global__ __launch_bounds__(256) void combine_slices_kernel(const float* part, 
 // row's result depends on nothing but its own input row: the prompt block is batch-invariant.
 struct GPArgs {
   const float* x; long long xrs;
-  const uint16_t* w;
+  const void* w;
   int K, N, M, nsub;
   const float* res; long long rrs;
   float* out; long long ors;
+  const float2* wp; int gmagic, fmt;  // quantised fragment packs (kk_csm_gemvm.h): pairs, wf_group_magic(group), KK_WF_*
 };
+// FMT: the B fragments arrive as bf16, or as the quantised integers + one (scale, bias) pair per lane, decoded to bf16 in registers ahead of a
+// chunk's matrix instructions (every wave decodes the four fragments it multiplies)
+template <int FMT>
 __global__ __launch_bounds__(256) void gemmp_kernel(GPArgs a) {
   // RT row tiles of 16 per workgroup (one per wave), KC 32-row K chunks per barrier.  Measured, prefill of 190 positions, RT x KC: 30.7 / 31.1 /
   // 33.9 / 36.3 ms for 4 x 2 / 4 x 1 / 8 x 2 / 8 x 1 -- the split arithmetic redone per column tile, not the tile shape, is what is left
@@ -988,16 +1014,20 @@ __global__ __launch_bounds__(256) void gemmp_kernel(GPArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char abuf[];  // [2 buffers][KC chunks][CHB]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m0 = blockIdx.y * (16 * RT), sb0 = blockIdx.x * 4, nch = a.K >> 5;
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  typedef typename WFrag<FMT>::Q u32x4;  // (a lane's fragment: 16 bytes of bf16, or 8 / 4 bytes of integers)
   // B fragment of (chunk c, global sub-block sb): block sb / nsub, sub sb % nsub of the pack [block][chunk][sub][lane]
   const int nsbt = (a.N + 15) >> 4;
   const u32x4* bp[4];
+  const float2* pp[4];  // pairs of (group g, sub-block sb): [block][group][sub][16 columns]
+  const int ngrp = FMT == KK_WF_BF16 ? 0 : wf_group(nch, a.gmagic);
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
     const int sb = sb0 + s < nsbt ? sb0 + s : nsbt - 1;  // (a sub-block past the end repeats the last one; its columns are not stored)
     bp[s] = (const u32x4*)a.w + ((long long)(sb / a.nsub) * nch * a.nsub + sb % a.nsub) * 64 + lane;
+    pp[s] = FMT == KK_WF_BF16 ? nullptr : a.wp + ((long long)(sb / a.nsub) * ngrp * a.nsub + sb % a.nsub) * 16 + (lane & 15);
   }
   const long long bstep = (long long)a.nsub * 64;  // per chunk
+  const long long pstep = (long long)a.nsub * 16;  // per group
   // A staging: thread (row tid / 8 + 32 it, quad tid % 8) takes 4 consecutive k of its row: the 8 lanes of a row read one whole 128-byte line
   // (a thread per (row, k octet) read 64 different lines per wave instruction: the first form of this kernel was bound by exactly that)
   const int aq = tid & 7, ar0 = tid >> 3;
@@ -1011,8 +1041,9 @@ __global__ __launch_bounds__(256) void gemmp_kernel(GPArgs a) {
   }
   float4 g[KC][NLD];
   u32x4 b[KC][4], bn[KC][4];
+  float2 pb[FMT == KK_WF_BF16 ? 1 : KC][4] = {}, pbn[FMT == KK_WF_BF16 ? 1 : KC][4] = {};
   // (a chunk index past the end is clamped: the loads stay unconditional, the extra operands are never multiplied)
-  auto load_ab = [&](int c0, u32x4 (&bd)[KC][4]) __attribute__((always_inline)) {
+  auto load_ab = [&](int c0, u32x4 (&bd)[KC][4], float2 (&pd)[FMT == KK_WF_BF16 ? 1 : KC][4]) __attribute__((always_inline)) {
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
       const int c = c0 + kc < nch ? c0 + kc : nch - 1;
@@ -1020,6 +1051,11 @@ __global__ __launch_bounds__(256) void gemmp_kernel(GPArgs a) {
       for (int it = 0; it < NLD; ++it) g[kc][it] = *(const float4*)(arow[it] + 32 * c);
 #pragma unroll
       for (int s = 0; s < 4; ++s) bd[kc][s] = *(bp[s] + (long long)c * bstep);
+      if constexpr (FMT != KK_WF_BF16) {
+        const int gq = wf_group(c, a.gmagic);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) pd[kc][s] = *(pp[s] + (long long)gq * pstep);
+      }
     }
   };
   auto store_a = [&](int buf) __attribute__((always_inline)) {
@@ -1049,23 +1085,26 @@ __global__ __launch_bounds__(256) void gemmp_kernel(GPArgs a) {
   for (int mi = 0; mi < NIT; ++mi)
 #pragma unroll
     for (int s = 0; s < 4; ++s) acc[mi][s] = kk_f32x4{0.f, 0.f, 0.f, 0.f};
-  load_ab(0, b);
+  load_ab(0, b, pb);
   store_a(0);
   __syncthreads();
   const int rdoff = (lane >> 4) * KOP + (lane & 15) * 16;
   int buf = 0;
   for (int c = 0; c < nch; c += KC, buf ^= 1) {
-    load_ab(c + KC, bn);  // the next step's operands: in flight under this step's matrix instructions
+    load_ab(c + KC, bn, pbn);  // the next step's operands: in flight under this step's matrix instructions
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
       if (c + kc < nch) {
+        kk_bf16x8 bf[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) bf[s] = wf_decode(b[kc][s], pb[FMT == KK_WF_BF16 ? 0 : kc][s]);
 #pragma unroll
         for (int mi = 0; mi < NIT; ++mi)
 #pragma unroll
           for (int t = 0; t < 3; ++t) {
             const kk_bf16x8 af = *(const kk_bf16x8*)(abuf + (buf * KC + kc) * CHB + ((NIT * wave + mi) * 3 + t) * FRAGB + rdoff);
 #pragma unroll
-            for (int s = 0; s < 4; ++s) acc[mi][s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, __builtin_bit_cast(kk_bf16x8, b[kc][s]), acc[mi][s], 0, 0, 0);
+            for (int s = 0; s < 4; ++s) acc[mi][s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf[s], acc[mi][s], 0, 0, 0);
           }
       }
     }
@@ -1074,6 +1113,12 @@ __global__ __launch_bounds__(256) void gemmp_kernel(GPArgs a) {
     for (int kc = 0; kc < KC; ++kc)
 #pragma unroll
       for (int s = 0; s < 4; ++s) b[kc][s] = bn[kc][s];
+    if constexpr (FMT != KK_WF_BF16) {
+#pragma unroll
+      for (int kc = 0; kc < KC; ++kc)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) pb[kc][s] = pbn[kc][s];
+    }
     __syncthreads();
   }
 #pragma unroll
@@ -1097,12 +1142,22 @@ int launch_gemmp(const GPArgs& g, hipStream_t st) {
   const size_t lds = (size_t)2 * 2 * 4 * 3 * 1536;  // [2 buffers][KC chunks][RT row tiles][3 terms][1536-byte fragments]
   static KKDevOnce attr;
   if (attr.first()) {
-    (void)hipFuncSetAttribute((const void*)gemmp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)gemmp_kernel<KK_WF_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)gemmp_kernel<KK_WF_Q8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)gemmp_kernel<KK_WF_Q4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr.done();
   }
-  hipLaunchKernelGGL(gemmp_kernel, dim3((g.N + 63) / 64, (g.M + 63) / 64), dim3(256), lds, st, g);
+  if (g.fmt != KK_WF_BF16 && !g.wp) return kk_fail("kk_csm: internal: quantised prompt GEMM without pairs");
+  const dim3 grid((g.N + 63) / 64, (g.M + 63) / 64);
+  if (g.fmt == KK_WF_Q8) hipLaunchKernelGGL(gemmp_kernel<KK_WF_Q8>, grid, dim3(256), lds, st, g);
+  else if (g.fmt == KK_WF_Q4) hipLaunchKernelGGL(gemmp_kernel<KK_WF_Q4>, grid, dim3(256), lds, st, g);
+  else hipLaunchKernelGGL(gemmp_kernel<KK_WF_BF16>, grid, dim3(256), lds, st, g);
   KK_CHECK_LAUNCH();
   return 0;
+}
+// the prompt GEMM of a packed matrix (bf16 or quantised fragments)
+static void gemmp_weights(GPArgs& g, const Lin& w) {
+  g.w = w.wm; g.nsub = w.nsub; g.fmt = w.fmt; g.wp = w.wp; g.gmagic = w.fmt != KK_WF_BF16 ? wf_group_magic(w.group) : 0;
 }
 
 // ------------------------------------------------------------------------------------------------------------- host
@@ -1148,6 +1203,47 @@ static void frag_pack(const float* w, int K, int N, long long ldw, int nsub, uin
   }
 }
 
+// ---- quantised fragment packs (kk_csm_gemvm.h: KK_WF_Q8 / KK_WF_Q4)
+static size_t qfrag_q_bytes(int K, int N, int nsub, int bits) { return frag_elems(K, N, nsub) * (size_t)bits / 8; }
+static size_t qfrag_pair_bytes(int K, int N, int nsub, int group) { return frag_elems(K, N, nsub) / (size_t)group * 8; }
+// One nn.Linear part (words [O][K bits / 32], scales / biases [O][K / group]: output column n0 + o) into the packs of a K x N matrix; `q` and
+// `pairs` must be zero-filled before the first part (the columns that pad N to whole blocks stay q = 0, scale = bias = 0: they decode to +0).
+//   q:     [N / (16 nsub)][K / 32][nsub][64 lanes] x 8 values of `bits` bits, value j in bits [j bits, (j + 1) bits) of the lane's 8 / 4 bytes
+//          (lane L: k = 32 c + 8 (L / 16) + j, n = 16 s + L % 16, as in frag_pack)
+//   pairs: [N / (16 nsub)][K / group][nsub][16 columns] float2 (scale, bias)
+static void qfrag_pack_part(const uint32_t* words, const float* scales, const float* biases, int O, int n0, int K, int nsub, int group, int bits, uint8_t* q,
+                            float* pairs) {
+  const int CBm = 16 * nsub, nchunk = K / 32, ngrp = K / group, per = 32 / bits, wpr = K / per;
+  const uint32_t mask = (1u << bits) - 1u;
+  for (int o = 0; o < O; ++o) {
+    const int n = n0 + o, nbk = n / CBm, sb = (n % CBm) >> 4;
+    for (int g = 0; g < ngrp; ++g) {
+      float* pr = pairs + ((((size_t)nbk * ngrp + g) * nsub + sb) * 16 + (n & 15)) * 2;
+      pr[0] = scales[(size_t)o * ngrp + g];
+      pr[1] = biases[(size_t)o * ngrp + g];
+    }
+    for (int i = 0; i < K; ++i) {
+      const uint32_t v = (words[(size_t)o * wpr + i / per] >> ((i % per) * bits)) & mask;
+      const int c = i >> 5, L = ((i & 31) >> 3) * 16 + (n & 15), j = i & 7;
+      const size_t lane = (((size_t)nbk * nchunk + c) * nsub + sb) * 64 + L;
+      if (bits == 8) q[lane * 8 + j] = (uint8_t)v;
+      else q[lane * 4 + (j >> 1)] |= (uint8_t)(v << (4 * (j & 1)));
+    }
+  }
+}
+// the checkpoint's own arithmetic on the host: w = fp32(q) * scale + bias, two roundings (quant.dequantize_affine)
+static void dequantize_host(const QHost& t, std::vector<float>& out) {
+  const int per = 32 / t.bits, wpr = t.I / per, ngrp = t.I / t.group;
+  const uint32_t mask = (1u << t.bits) - 1u;
+  out.resize((size_t)t.O * t.I);
+  for (int o = 0; o < t.O; ++o)
+    for (int i = 0; i < t.I; ++i) {
+      const float qf = (float)((t.words[(size_t)o * wpr + i / per] >> ((i % per) * t.bits)) & mask);
+      volatile float prod = qf * t.scales[(size_t)o * ngrp + i / t.group];  // (rounded to fp32 before the add whatever the compiler's contraction rule)
+      out[(size_t)o * t.I + i] = prod + t.biases[(size_t)o * ngrp + i / t.group];
+    }
+}
+
 // host tensors are erased as soon as they are packed: peak host memory stays near one copy of the 1.6 B parameters
 struct Packer {
   kk_csm* m;
@@ -1159,12 +1255,18 @@ struct Packer {
   }
   // nn.Linear weights [O_i][I] stacked along the output axis -> one [I][ldw] pack; `raw`: the source is [I][O] (audio_head);
   // `split_ok`: the single-token step launches this matrix in the split-K form too (the down projections)
-  Lin linear(const std::vector<std::string>& names, const std::vector<int>& outs, int I, const float* raw = nullptr, bool split_ok = false) {
+  // `keep_f32` = false (packed storage: the audio heads): the fp32 matrix is staged in a scratch vector and only its bf16 pack is kept
+  Lin linear(const std::vector<std::string>& names, const std::vector<int>& outs, int I, const float* raw = nullptr, bool split_ok = false,
+             bool keep_f32 = true) {
     Lin l;
     int O = 0;
     for (int o : outs) O += o;
     l.Cin = I; l.Cout = O; l.ldw = rup(O, 64);
-    l.off = a.alloc((size_t)I * l.ldw);
+    std::vector<float> scratch;
+    if (keep_f32) l.off = a.alloc((size_t)I * l.ldw);
+    else scratch.assign((size_t)I * l.ldw, 0.f);
+    l.has_f32 = keep_f32;
+    if (keep_f32) m->linear_bytes += (size_t)I * l.ldw * 4;
     int base = 0;
     for (size_t k = 0; k < outs.size(); ++k) {
       const float* src = raw;
@@ -1173,7 +1275,7 @@ struct Packer {
         if (!w) return l;
         src = w->d.data();
       }
-      float* dst = &a.pack[l.off];
+      float* dst = keep_f32 ? &a.pack[l.off] : scratch.data();
       if (raw) {  // [I][O]
         for (int i = 0; i < I; ++i)
           for (int o = 0; o < outs[k]; ++o) dst[(size_t)i * l.ldw + base + o] = src[(size_t)i * outs[k] + o];
@@ -1187,7 +1289,7 @@ struct Packer {
     if (m->wdt == KK_BF16) {
       // bf16 weight mode: the matrix IS its bf16 rounding everywhere (the fp32 pack the multi-token prompt block reads holds the rounded
       // values too, so a prompt block and single-token steps multiply by identical weights); lossless for a bf16 checkpoint.
-      float* dst = &a.pack[l.off];
+      float* dst = keep_f32 ? &a.pack[l.off] : scratch.data();
       for (size_t e = 0; e < (size_t)I * l.ldw; ++e) {
         uint32_t u;
         memcpy(&u, &dst[e], 4);
@@ -1201,11 +1303,93 @@ struct Packer {
         l.moff = m->packb.size();
         m->packb.resize(l.moff + frag_elems(I, O, nsub));
         frag_pack(dst, I, O, l.ldw, nsub, &m->packb[l.moff]);
+        m->linear_bytes += frag_elems(I, O, nsub) * 2;
       }
     }
     return l;
   }
+  // the same stacked matrix from QUANTISED parts (kk_csm_load_quantized; csm_can_pack has checked them): integer fragment pack + pairs, nothing else
+  Lin qlinear(const std::vector<std::string>& names, const std::vector<int>& outs, int I, bool split_ok = false) {
+    Lin l;
+    int O = 0;
+    for (int o : outs) O += o;
+    l.Cin = I; l.Cout = O; l.ldw = rup(O, 64);
+    l.has_f32 = false;
+    const QHost& first = m->qhost.at(names[0]);
+    l.fmt = first.bits == 8 ? KK_WF_Q8 : KK_WF_Q4;
+    l.group = first.group;
+    frag_choice(I, O, split_ok, &l.ks, &l.nsub);
+    const size_t qb = qfrag_q_bytes(I, O, l.nsub, first.bits), pb = qfrag_pair_bytes(I, O, l.nsub, l.group);
+    l.qoff = (m->packq.size() + 255) & ~(size_t)255;
+    l.poff = (l.qoff + qb + 255) & ~(size_t)255;
+    m->packq.resize(l.poff + pb, 0);
+    int base = 0;
+    for (size_t k = 0; k < outs.size(); ++k) {
+      const QHost& t = m->qhost.at(names[k]);
+      qfrag_pack_part(t.words.data(), t.scales.data(), t.biases.data(), outs[k], base, I, l.nsub, l.group, t.bits, &m->packq[l.qoff],
+                      (float*)&m->packq[l.poff]);
+      m->qhost.erase(names[k]);
+      base += outs[k];
+    }
+    m->linear_bytes += qb + pb;
+    (l.fmt == KK_WF_Q8 ? m->n_q8 : m->n_q4) += 1;
+    return l;
+  }
+  Lin any_linear(const std::vector<std::string>& names, const std::vector<int>& outs, int I, bool split_ok = false) {
+    return m->packed ? qlinear(names, outs, I, split_ok) : linear(names, outs, I, nullptr, split_ok);
+  }
 };
+
+// The Linears of the frame step, as pack_stack / kk_csm_finalize stack them: (names, output widths, K, split-K allowed)
+struct LinSpec {
+  std::vector<std::string> names;
+  std::vector<int> outs;
+  int I;
+  bool split_ok;
+};
+static void stack_specs(const std::string& name, const kk_llama_args& a, std::vector<LinSpec>& v) {
+  const int H = a.num_heads, KV = a.num_kv_heads, hd = a.head_dim, D = a.hidden, I = a.intermediate;
+  for (int i = 0; i < a.num_layers; ++i) {
+    const std::string p = name + ".layers." + std::to_string(i);
+    v.push_back({{p + ".self_attn.q_proj.weight", p + ".self_attn.k_proj.weight", p + ".self_attn.v_proj.weight"}, {H * hd, KV * hd, KV * hd}, D, false});
+    v.push_back({{p + ".self_attn.o_proj.weight"}, {D}, H * hd, false});
+    v.push_back({{p + ".mlp.gate_proj.weight", p + ".mlp.up_proj.weight"}, {I, I}, D, false});
+    v.push_back({{p + ".mlp.down_proj.weight"}, {D}, I, true});
+  }
+}
+// Packed storage is all or nothing (a packed matrix has no fp32 copy for the fallback kernels): every Linear the fast frame path multiplies by
+// must arrive quantised in a form the kernels decode and get a fragment pack, and so must the bf16 audio heads.  Empty result = yes; else why not.
+static std::string csm_can_pack(const kk_csm* m) {
+  const kk_csm_config& c = m->cfg;
+  std::vector<LinSpec> v;
+  stack_specs("backbone", c.backbone, v);
+  stack_specs("decoder", c.decoder, v);
+  v.push_back({{"projection.weight"}, {c.decoder.hidden}, c.backbone.hidden, false});
+  v.push_back({{"codebook0_head.weight"}, {c.audio_vocab_size}, c.backbone.hidden, false});
+  for (const LinSpec& s : v) {
+    int O = 0, bits = 0, group = 0;
+    for (size_t k = 0; k < s.names.size(); ++k) {
+      auto it = m->qhost.find(s.names[k]);
+      if (it == m->qhost.end()) return s.names[k] + " is not quantised";
+      const QHost& t = it->second;
+      if (t.O != s.outs[k] || t.I != s.I) return "unexpected shape for " + s.names[k];
+      if (k == 0) { bits = t.bits; group = t.group; }
+      if (t.bits != bits || t.group != group) return s.names[k] + ": the parts of a stacked matrix differ in bits / group size";
+      O += s.outs[k];
+    }
+    if (bits != 4 && bits != 8) return s.names[0] + ": " + std::to_string(bits) + " bits (the kernels decode 4 and 8)";
+    if (!wf_group_ok(s.I, group)) return s.names[0] + ": group size " + std::to_string(group) + " (a multiple of 32 that divides K)";
+    int ks = 1, nsub = 0;
+    frag_choice(s.I, O, s.split_ok, &ks, &nsub);
+    if (!nsub) return s.names[0] + ": no fragment pack for K = " + std::to_string(s.I);
+  }
+  if (c.audio_num_codebooks > 1) {
+    int ks = 1, nsub = 0;
+    frag_choice(c.decoder.hidden, c.audio_vocab_size, false, &ks, &nsub);
+    if (!nsub) return "audio_head: no fragment pack";
+  }
+  return "";
+}
 
 void llama3_theta(const kk_llama_args& a, std::vector<float>& th) {  // attention.py:33-82, float32 like the reference
   const int half = a.head_dim / 2;
@@ -1234,10 +1418,10 @@ void pack_stack(Packer& P, const std::string& name, Stack& st, int max_pos) {
     LlamaLayer& L = st.layers[i];
     L.n1 = P.vec(p + ".input_layernorm.weight", D);
     L.n2 = P.vec(p + ".post_attention_layernorm.weight", D);
-    L.qkv = P.linear({p + ".self_attn.q_proj.weight", p + ".self_attn.k_proj.weight", p + ".self_attn.v_proj.weight"}, {H * hd, KV * hd, KV * hd}, D);
-    L.o = P.linear({p + ".self_attn.o_proj.weight"}, {D}, H * hd);
-    L.gu = P.linear({p + ".mlp.gate_proj.weight", p + ".mlp.up_proj.weight"}, {I, I}, D);
-    L.down = P.linear({p + ".mlp.down_proj.weight"}, {D}, I, nullptr, true);
+    L.qkv = P.any_linear({p + ".self_attn.q_proj.weight", p + ".self_attn.k_proj.weight", p + ".self_attn.v_proj.weight"}, {H * hd, KV * hd, KV * hd}, D);
+    L.o = P.any_linear({p + ".self_attn.o_proj.weight"}, {D}, H * hd);
+    L.gu = P.any_linear({p + ".mlp.gate_proj.weight", p + ".mlp.up_proj.weight"}, {I, I}, D);
+    L.down = P.any_linear({p + ".mlp.down_proj.weight"}, {D}, I, true);
   }
   st.norm = P.vec(name + ".norm.weight", D);
   std::vector<float> th;
@@ -1255,7 +1439,12 @@ void pack_stack(Packer& P, const std::string& name, Stack& st, int max_pos) {
 }
 
 void resolve(kk_csm* m, Lin& l) {
-  l.w = m->arena.dev + l.off;
+  l.w = l.has_f32 ? m->arena.dev + l.off : nullptr;
+  if (l.fmt != KK_WF_BF16) {
+    l.wm = m->devq ? (const uint16_t*)(m->devq + l.qoff) : nullptr;
+    l.wp = m->devq ? (const float2*)(m->devq + l.poff) : nullptr;
+    return;
+  }
   l.wm = (m->devb && l.nsub) ? m->devb + l.moff : nullptr;
 }
 void resolve(kk_csm* m, ArenaVec& v) { m->arena.resolve(v); }
@@ -1321,7 +1510,7 @@ struct Run : Workspace {
     a.Q = rows; a.Lo_rows = rows; a.lin = KKLen{nullptr, 0, rows}; a.lout = KKLen{nullptr, 0, rows};
     a.in_slope = 1.f; a.scale = 1.f;
     int nb = B;
-    if (xbs == (long long)rows * w.Cin && obs == (long long)rows * w.Cout && rows <= 2 && skinny_scratch) {
+    if (xbs == (long long)rows * w.Cin && obs == (long long)rows * w.Cout && rows <= 2 && skinny_scratch && w.w) {
       // single-token steps (and the decoder's 2-token first step): the HBM-bound skinny GEMM (every CU streams a slice of W once for up
       // to 16 rows).  The choice depends on the rows PER ITEM only, never on B, so a stream's bits do not depend on its batch.
       const int Mtot = B * rows;
@@ -1336,12 +1525,14 @@ struct Run : Workspace {
         return 0;
       }
     }
-    if (xbs == (long long)rows * w.Cin && obs == (long long)rows * w.Cout && w.wm && w.nsub && rows > 2) {
+    if (xbs == (long long)rows * w.Cin && obs == (long long)rows * w.Cout && w.wm && w.nsub && (rows > 2 || !w.w)) {
       // the prompt block in bf16 weight mode: matrix cores (gemmp_kernel); without a fragment pack, the generic fp32 kernel below.
-      // The choice depends on the rows PER ITEM only, never on B: a stream's bits do not depend on its batch.
+      // The choice depends on the rows PER ITEM only, never on B: a stream's bits do not depend on its batch.  (A packed quantised matrix has
+      // no fp32 copy for the skinny GEMM: its one- and two-row blocks come here too.)
       GPArgs g;
       memset(&g, 0, sizeof g);
-      g.x = x; g.xrs = w.Cin; g.w = w.wm; g.K = w.Cin; g.N = w.Cout; g.M = B * rows; g.nsub = w.nsub;
+      g.x = x; g.xrs = w.Cin; g.K = w.Cin; g.N = w.Cout; g.M = B * rows;
+      gemmp_weights(g, w);
       g.res = res; g.rrs = w.Cout; g.out = out; g.ors = w.Cout;
       { const int rc_ = launch_gemmp(g, st); if (rc_ != 0) return rc_; }
       if (xn) {
@@ -1350,6 +1541,7 @@ struct Run : Workspace {
       }
       return 0;
     }
+    if (!w.w) return kk_fail("kk_csm: internal: a packed matrix has no fp32 copy for the generic kernel");
     if (xbs == (long long)rows * w.Cin && obs == (long long)rows * w.Cout) {
       // items are contiguous: one launch over B*rows rows, so a weight tile is read once for the whole batch (single-token steps would
       // otherwise re-read every matrix once per item)
@@ -1370,6 +1562,8 @@ struct Run : Workspace {
 // the matrix-core GEMV: one launch for all rows (grid z = 8-row chunks); KS must be the pack's w.ks
 int launch_gemvm(const Lin& w, int pro, int epi, FGArgs a, int Mtot, hipStream_t st) {
   a.w = w.wm; a.K = w.Cin; a.N = w.Cout; a.M = Mtot; a.kper = w.Cin / w.ks;
+  a.wp = w.wp; a.gmagic = w.fmt != KK_WF_BF16 ? wf_group_magic(w.group) : 0;
+  if (w.fmt != KK_WF_BF16 && (!w.wp || !wf_group_ok(w.Cin, w.group))) return kk_fail("kk_csm: internal: quantised GEMV without pairs / group size");
   a.ts = ts_slot(); a.ts_id = (w.Cout << 4) | (pro << 2) | epi;
   const int CB = 16 * w.nsub, nblk = (w.Cout + CB - 1) / CB, kper = w.Cin / w.ks;
   const size_t lds = gm_lds_bytes(w.nsub, kper);
@@ -1378,14 +1572,20 @@ int launch_gemvm(const Lin& w, int pro, int epi, FGArgs a, int Mtot, hipStream_t
   if (pro == 3 && a.rows != 1 && a.rows != 2) return kk_fail("kk_csm: internal: matrix-core GEMV: item rows");
   const dim3 grid(nblk, w.ks, (Mtot + 7) / 8);
   const int rounds = (kper / 32 + 31) / 32;  // straight-line rounds of 4 chunks x 8 waves (K slice <= 1024: one)
-#define GM_GO1(NSUB, PRO, EPI, RD)                                                                                                       \
-  do {                                                                                                                                   \
-    static KKDevOnce attr;                                                                                                               \
-    if (attr.first()) {                                                                                                                  \
-      (void)hipFuncSetAttribute((const void*)gemvm_kernel<NSUB, PRO, EPI, RD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);  \
-      attr.done();                                                                                                                       \
-    }                                                                                                                                    \
-    hipLaunchKernelGGL((gemvm_kernel<NSUB, PRO, EPI, RD>), grid, dim3(512), lds, st, a);                                                 \
+#define GM_GO2(FMT, NSUB, PRO, EPI, RD)                                                                                                       \
+  do {                                                                                                                                        \
+    static KKDevOnce attr;                                                                                                                    \
+    if (attr.first()) {                                                                                                                       \
+      (void)hipFuncSetAttribute((const void*)gemvm_kernel<FMT, NSUB, PRO, EPI, RD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);  \
+      attr.done();                                                                                                                            \
+    }                                                                                                                                         \
+    hipLaunchKernelGGL((gemvm_kernel<FMT, NSUB, PRO, EPI, RD>), grid, dim3(512), lds, st, a);                                                 \
+  } while (0)
+#define GM_GO1(NSUB, PRO, EPI, RD)                                          \
+  do {                                                                      \
+    if (w.fmt == KK_WF_Q8) GM_GO2(KK_WF_Q8, NSUB, PRO, EPI, RD);            \
+    else if (w.fmt == KK_WF_Q4) GM_GO2(KK_WF_Q4, NSUB, PRO, EPI, RD);       \
+    else GM_GO2(KK_WF_BF16, NSUB, PRO, EPI, RD);                            \
   } while (0)
 #define GM_GO(NSUB, PRO, EPI)                                              \
   do {                                                                      \
@@ -1407,6 +1607,7 @@ int launch_gemvm(const Lin& w, int pro, int epi, FGArgs a, int Mtot, hipStream_t
 #undef GM_PE
 #undef GM_GO
 #undef GM_GO1
+#undef GM_GO2
   KK_CHECK_LAUNCH();
   return 0;
 }
@@ -1755,9 +1956,53 @@ extern "C" int kk_csm_frag_pack(const float* w, int K, int N, int nsub, uint16_t
   return 0;
 }
 
+extern "C" int kk_csm_qfrag_bytes(int K, int N, int nsub, int group_size, int bits, size_t* q_bytes, size_t* pair_bytes) {
+  if (K < 32 || K % 32 != 0 || N < 1 || (nsub != 1 && nsub != 2 && nsub != 4) || (bits != 4 && bits != 8) || !wf_group_ok(K, group_size))
+    return kk_fail("kk_csm_qfrag_bytes: bad argument");
+  if (q_bytes) *q_bytes = qfrag_q_bytes(K, N, nsub, bits);
+  if (pair_bytes) *pair_bytes = qfrag_pair_bytes(K, N, nsub, group_size);
+  return 0;
+}
+
+extern "C" int kk_csm_qfrag_pack(const uint32_t* words, const float* scales, const float* biases, int K, int N, int nsub, int group_size, int bits,
+                                 void* q_out, float* pairs_out) {
+  if (!words || !scales || !biases || !q_out || !pairs_out || K < 32 || K % 32 != 0 || N < 1 || (nsub != 1 && nsub != 2 && nsub != 4) ||
+      (bits != 4 && bits != 8) || !wf_group_ok(K, group_size))
+    return kk_fail("kk_csm_qfrag_pack: bad argument");
+  memset(q_out, 0, qfrag_q_bytes(K, N, nsub, bits));
+  memset(pairs_out, 0, qfrag_pair_bytes(K, N, nsub, group_size));
+  qfrag_pack_part(words, scales, biases, N, 0, K, nsub, group_size, bits, (uint8_t*)q_out, pairs_out);
+  return 0;
+}
+
+static int op_csm_gemv(const char* who, Lin& w, void* stream, int pro, int epi, int ks, int nsub, int K, int N, int M, const float* x, long long xrs,
+                       const float* nw, float eps, const int32_t* codes, int cstride, int cb, int V, int rows, const float* emb, float* gather_out,
+                       const float* res, long long rrs, float* out, long long ors, float* part);
+
 extern "C" int kk_op_csm_gemv(void* stream, int pro, int epi, int ks, int nsub, int K, int N, int M, const void* w_frag, const float* x, long long xrs,
                               const float* nw, float eps, const int32_t* codes, int cstride, int cb, int V, int rows, const float* emb, float* gather_out,
                               const float* res, long long rrs, float* out, long long ors, float* part) {
+  Lin w;
+  w.wm = (const uint16_t*)w_frag;
+  return op_csm_gemv("kk_op_csm_gemv", w, stream, pro, epi, ks, nsub, K, N, M, x, xrs, nw, eps, codes, cstride, cb, V, rows, emb, gather_out, res, rrs, out, ors,
+                     part);
+}
+
+extern "C" int kk_op_csm_gemv_q(void* stream, int pro, int epi, int ks, int nsub, int K, int N, int M, const void* q_frag, const void* pairs, int group_size,
+                                int bits, const float* x, long long xrs, const float* nw, float eps, const int32_t* codes, int cstride, int cb, int V, int rows,
+                                const float* emb, float* gather_out, const float* res, long long rrs, float* out, long long ors, float* part) {
+  if (!pairs || (bits != 4 && bits != 8) || K < 32 || !wf_group_ok(K, group_size)) return kk_fail("kk_op_csm_gemv_q: pairs / bits / group size");
+  Lin w;
+  w.wm = (const uint16_t*)q_frag; w.wp = (const float2*)pairs; w.fmt = bits == 8 ? KK_WF_Q8 : KK_WF_Q4; w.group = group_size;
+  return op_csm_gemv("kk_op_csm_gemv_q", w, stream, pro, epi, ks, nsub, K, N, M, x, xrs, nw, eps, codes, cstride, cb, V, rows, emb, gather_out, res, rrs, out,
+                     ors, part);
+}
+
+static int op_csm_gemv(const char* who, Lin& w, void* stream, int pro, int epi, int ks, int nsub, int K, int N, int M, const float* x, long long xrs,
+                       const float* nw, float eps, const int32_t* codes, int cstride, int cb, int V, int rows, const float* emb, float* gather_out,
+                       const float* res, long long rrs, float* out, long long ors, float* part) {
+  (void)who;
+  const void* w_frag = w.wm;
   if (!w_frag || !out || M < 1 || N < 1 || K < 32 || K % 32 != 0 || (nsub != 1 && nsub != 2 && nsub != 4)) return kk_fail("kk_op_csm_gemv: bad argument");
   if (ks < 1 || ks > 16 || K % ks != 0 || (K / ks) % 32 != 0 || !gm_slice_fits(nsub, K / ks)) return kk_fail("kk_op_csm_gemv: K slices do not fit this K");
   if (pro < 0 || pro > 3 || epi < 0 || epi > 2 || (epi == 2) != (ks > 1)) return kk_fail("kk_op_csm_gemv: form");
@@ -1767,8 +2012,7 @@ extern "C" int kk_op_csm_gemv(void* stream, int pro, int epi, int ks, int nsub, 
   if (pro == 1 && !nw) return kk_fail("kk_op_csm_gemv: norm weight");
   if (epi == 1 && (!res || rrs < N)) return kk_fail("kk_op_csm_gemv: residual");
   if (ors < N || (epi == 2 && (ors != N || res || !part))) return kk_fail("kk_op_csm_gemv: output");
-  Lin w;
-  w.Cin = K; w.Cout = N; w.wm = (const uint16_t*)w_frag; w.nsub = nsub; w.ks = ks;
+  w.Cin = K; w.Cout = N; w.nsub = nsub; w.ks = ks;
   FGArgs g;
   memset(&g, 0, sizeof g);
   g.x = x; g.xrs = xrs; g.nw = nw; g.eps = eps;
@@ -1785,7 +2029,20 @@ extern "C" int kk_op_csm_gemm_prompt(void* stream, int K, int N, int M, int nsub
     return kk_fail("kk_op_csm_gemm_prompt: bad argument");
   GPArgs g;
   memset(&g, 0, sizeof g);
-  g.x = x; g.xrs = xrs; g.w = (const uint16_t*)w_frag; g.K = K; g.N = N; g.M = M; g.nsub = nsub;
+  g.x = x; g.xrs = xrs; g.w = w_frag; g.K = K; g.N = N; g.M = M; g.nsub = nsub;
+  g.res = res; g.rrs = rrs; g.out = out; g.ors = ors;
+  return launch_gemmp(g, (hipStream_t)stream);
+}
+
+extern "C" int kk_op_csm_gemm_prompt_q(void* stream, int K, int N, int M, int nsub, const void* q_frag, const void* pairs, int group_size, int bits,
+                                       const float* x, long long xrs, const float* res, long long rrs, float* out, long long ors) {
+  if (!q_frag || !pairs || !x || !out || M < 1 || N < 1 || K < 32 || K % 32 != 0 || (nsub != 1 && nsub != 2 && nsub != 4) || xrs < K || xrs % 4 != 0 || ors < N ||
+      (res && rrs < N) || (bits != 4 && bits != 8) || !wf_group_ok(K, group_size))
+    return kk_fail("kk_op_csm_gemm_prompt_q: bad argument");
+  GPArgs g;
+  memset(&g, 0, sizeof g);
+  g.x = x; g.xrs = xrs; g.w = q_frag; g.K = K; g.N = N; g.M = M; g.nsub = nsub;
+  g.wp = (const float2*)pairs; g.gmagic = wf_group_magic(group_size); g.fmt = bits == 8 ? KK_WF_Q8 : KK_WF_Q4;
   g.res = res; g.rrs = rrs; g.out = out; g.ors = ors;
   return launch_gemmp(g, (hipStream_t)stream);
 }
@@ -1860,6 +2117,7 @@ extern "C" void kk_csm_destroy(kk_csm* m) {
   if (!m) return;
   if (m->arena.dev && !m->weights_of) (void)hipFree(m->arena.dev);
   if (m->devb && !m->weights_of) (void)hipFree(m->devb);
+  if (m->devq && !m->weights_of) (void)hipFree(m->devq);
   if (m->proj_table && !m->weights_of) (void)hipFree(m->proj_table);
   for (Stack* s : {&m->bb, &m->dec}) {
     if (s->kc) (void)hipFree(s->kc);
@@ -1892,6 +2150,7 @@ extern "C" int kk_csm_load_tensor(kk_csm* m, const char* name, const int64_t* sh
   HostTensor& t = m->arena.host[name];
   t.d.assign(data, data + n);
   t.shape.assign(shape, shape + ndim);
+  m->qhost.erase(name);
   return 0;
 }
 
@@ -1901,21 +2160,49 @@ extern "C" int kk_csm_finalize(kk_csm* m, void* stream) {
   const kk_csm_config& c = m->cfg;
   Packer P{m, m->arena};
   const int D = c.backbone.hidden, Dd = c.decoder.hidden, V = c.audio_vocab_size, ncb = c.audio_num_codebooks;
+  if (!m->qhost.empty()) {
+    // A quantised checkpoint.  Packed storage if the whole fast path can run from quantised packs (csm_can_pack), else today's arithmetic on the
+    // dequantised weights: bf16 weight mode either way.  Whatever is not a packed Linear (the embedding tables; everything on the fallback) is
+    // dequantised here, by the checkpoint's own rule, and then treated as a float tensor of that name.
+    m->q_reason = csm_can_pack(m);
+    m->packed = m->q_reason.empty();
+    m->q_fallback = !m->packed;
+    m->wdt = KK_BF16;
+    std::set<std::string> keep;
+    if (m->packed) {
+      std::vector<LinSpec> v;
+      stack_specs("backbone", c.backbone, v);
+      stack_specs("decoder", c.decoder, v);
+      for (const LinSpec& sp : v) keep.insert(sp.names.begin(), sp.names.end());
+      keep.insert("projection.weight");
+      keep.insert("codebook0_head.weight");
+    }
+    for (auto it = m->qhost.begin(); it != m->qhost.end();) {
+      if (keep.count(it->first)) { ++it; continue; }
+      HostTensor& t = m->arena.host[it->first];
+      dequantize_host(it->second, t.d);
+      t.shape = {it->second.O, it->second.I};
+      it = m->qhost.erase(it);
+    }
+  }
   pack_stack(P, "backbone", m->bb, c.max_seq_len);
   pack_stack(P, "decoder", m->dec, ncb + 1);
   m->text_emb = P.vec("text_embeddings.weight", (size_t)c.text_vocab_size * D);
   m->audio_emb = P.vec("audio_embeddings.weight", (size_t)V * ncb * D);
-  m->proj = P.linear({"projection.weight"}, {Dd}, D);
-  m->c0_head = P.linear({"codebook0_head.weight"}, {V}, D);
+  m->proj = P.any_linear({"projection.weight"}, {Dd}, D);
+  m->c0_head = P.any_linear({"codebook0_head.weight"}, {V}, D);
   m->audio_head.resize(ncb > 1 ? ncb - 1 : 0);
   if (ncb > 1) {
     const HostTensor* ah = P.a.get("audio_head", (size_t)(ncb - 1) * Dd * V);
     if (ah)
-      for (int i = 0; i < ncb - 1; ++i) m->audio_head[i] = P.linear({}, {V}, Dd, ah->d.data() + (size_t)i * Dd * V);  // [Dd][V] used as x @ W
+      for (int i = 0; i < ncb - 1; ++i) m->audio_head[i] = P.linear({}, {V}, Dd, ah->d.data() + (size_t)i * Dd * V, false, !m->packed);  // [Dd][V] used as x @ W
   }
   if (!P.a.err.empty()) return kk_failf("kk_csm_finalize: %s", P.a.err.c_str());
+  m->qhost.clear();
+  m->total_bytes = m->arena.pack.size() * 4 + m->packb.size() * 2 + m->packq.size();
   KK_TRY(m->arena.upload((hipStream_t)stream, "kk_csm_finalize"));
   if (!m->packb.empty()) KK_TRY(kk_upload(m->packb, &m->devb, (hipStream_t)stream, "kk_csm_finalize"));
+  if (!m->packq.empty()) KK_TRY(kk_upload(m->packq, &m->devq, (hipStream_t)stream, "kk_csm_finalize"));
   resolve(m, m->bb); resolve(m, m->audio_emb); resolve(m, m->proj);
   if (m->proj.wm && ncb > 1) {
     // projection(audio_embeddings): every input the depth decoder's later steps can see (sesame.py:373-392: curr_h = projection(embed(c_{i-1})))
@@ -1923,12 +2210,52 @@ extern "C" int kk_csm_finalize(kk_csm* m, void* stream) {
     if (hipMalloc((void**)&m->proj_table, rows * Dd * sizeof(float)) != hipSuccess) return kk_fail("kk_csm_finalize: hipMalloc failed");
     GPArgs g;
     memset(&g, 0, sizeof g);
-    g.x = m->audio_emb.p; g.xrs = D; g.w = m->proj.wm; g.K = D; g.N = Dd; g.M = (int)rows; g.nsub = m->proj.nsub; g.out = m->proj_table; g.ors = Dd;
+    g.x = m->audio_emb.p; g.xrs = D; g.K = D; g.N = Dd; g.M = (int)rows; g.out = m->proj_table; g.ors = Dd;
+    gemmp_weights(g, m->proj);
+    m->table_bytes = rows * Dd * sizeof(float);
+    m->total_bytes += m->table_bytes;
     if (launch_gemmp(g, (hipStream_t)stream) != 0 || hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return kk_fail("kk_csm_finalize: projection table failed");
   }
   resolve(m, m->bb); resolve(m, m->dec); resolve(m, m->text_emb); resolve(m, m->audio_emb); resolve(m, m->proj); resolve(m, m->c0_head);
   for (auto& l : m->audio_head) resolve(m, l);
+  if (m->packed) {  // the decision above promised the fast path: never a frame that could reach a matrix without its fp32 copy
+    bool ok = stack_can_step(m->bb) && stack_can_step(m->dec) && m->proj.wm && m->c0_head.wm;
+    for (const auto& l : m->audio_head) ok = ok && l.wm;
+    if (!ok) return kk_fail("kk_csm_finalize: internal: packed storage without a complete fast path");
+  }
   m->finalized = true;
+  return 0;
+}
+
+extern "C" int kk_csm_load_quantized(kk_csm* m, const char* name, const int64_t* shape, const uint32_t* words, const float* scales, const float* biases,
+                                     int group_size, int bits) {
+  if (!m || !name || !shape || !words || !scales || !biases) return kk_fail("kk_csm_load_quantized: bad argument");
+  if (m->finalized) return kk_fail("kk_csm_load_quantized: model already finalized");
+  if (bits != 2 && bits != 4 && bits != 8) return kk_fail("kk_csm_load_quantized: bits must be 2, 4 or 8 (values of a word in bits [j bits, (j + 1) bits))");
+  const int64_t O = shape[0], I = shape[1];
+  if (O < 1 || I < 1 || O > (1 << 30) || I > (1 << 30) || group_size < 1 || I % group_size != 0 || (I * bits) % 32 != 0)
+    return kk_failf("kk_csm_load_quantized: %s: shape / group size", name);
+  QHost& t = m->qhost[name];
+  t.O = (int)O; t.I = (int)I; t.group = group_size; t.bits = bits;
+  t.words.assign(words, words + (size_t)O * (size_t)(I * bits / 32));
+  t.scales.assign(scales, scales + (size_t)O * (size_t)(I / group_size));
+  t.biases.assign(biases, biases + (size_t)O * (size_t)(I / group_size));
+  m->arena.host.erase(name);
+  return 0;
+}
+
+extern "C" int kk_csm_weight_format(const kk_csm* m) {
+  if (!m || !m->finalized) { kk_fail("kk_csm_weight_format: needs a finalized generator"); return -1; }
+  if (m->packed) return (m->n_q8 ? KK_CSM_WEIGHTS_Q8 : KK_CSM_WEIGHTS_Q4) | (m->n_q8 && m->n_q4 ? KK_CSM_WEIGHTS_MIXED : 0);
+  return (m->wdt == KK_BF16 ? KK_CSM_WEIGHTS_BF16 : KK_CSM_WEIGHTS_F32) | (m->q_fallback ? KK_CSM_WEIGHTS_DEQUANTIZED : 0);
+}
+
+extern "C" const char* kk_csm_weight_fallback_reason(const kk_csm* m) { return m ? m->q_reason.c_str() : ""; }
+
+extern "C" int kk_csm_weight_bytes(const kk_csm* m, size_t* linear_bytes, size_t* total_bytes) {
+  if (!m || !m->finalized) return kk_fail("kk_csm_weight_bytes: needs a finalized generator");
+  if (linear_bytes) *linear_bytes = m->linear_bytes;
+  if (total_bytes) *total_bytes = m->total_bytes;
   return 0;
 }
 

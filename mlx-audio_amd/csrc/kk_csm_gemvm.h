@@ -6,6 +6,39 @@
 
 typedef float kk_f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 kk_bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned kk_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned kk_u32x2 __attribute__((ext_vector_type(2)));
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// Weight formats of the fragment pack (template parameter FMT of gemvm_kernel / gemmp_kernel).  KK_WF_BF16: a lane's 8 values of a fragment as
+// 8 bf16 (16 bytes).  KK_WF_Q8 / KK_WF_Q4: the MLX affine-quantised checkpoint's integers, 8 bytes / 8 nibbles (value j in bits [j bits, (j + 1) bits))
+// in the SAME fragment order [block][chunk][sub-block][lane], plus one (scale, bias) pair per column and quantisation group in
+// [block][K / group][sub-block][16 columns] float2: a lane's 8 values lie in one 32-row chunk, hence in one group (group % 32 == 0).  The lane
+// decodes them in registers to  bf16_rne(fp32(q) * scale + bias)  -- fp32 multiply, then fp32 add, no fma -- which is the bf16 rounding of the
+// dequantised matrix, i.e. bit for bit the fragment the bf16 pack of that matrix holds; everything behind the B operand is shared.
+enum { KK_WF_BF16 = 0, KK_WF_Q8 = 1, KK_WF_Q4 = 2 };
+template <int FMT> struct WFrag;
+template <> struct WFrag<KK_WF_BF16> { typedef kk_u32x4 Q; };
+template <> struct WFrag<KK_WF_Q8> { typedef kk_u32x2 Q; };
+template <> struct WFrag<KK_WF_Q4> { typedef unsigned Q; };
+__device__ __forceinline__ kk_bf16x8 wf_decode(kk_u32x4 q, float2) { return __builtin_bit_cast(kk_bf16x8, q); }
+__device__ __forceinline__ kk_bf16x8 wf_decode(kk_u32x2 q, float2 sb) {
+  kk_bf16x8 v;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = (__bf16)__fadd_rn(__fmul_rn((float)((q[j >> 2] >> (8 * (j & 3))) & 0xffu), sb.x), sb.y);
+  return v;
+}
+__device__ __forceinline__ kk_bf16x8 wf_decode(unsigned q, float2 sb) {
+  kk_bf16x8 v;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = (__bf16)__fadd_rn(__fmul_rn((float)((q >> (4 * j)) & 0xfu), sb.x), sb.y);
+  return v;
+}
+// quantisation group of 32-row chunk c: c / (group / 32) as a multiply and shift (gmagic = ceil(2^20 / (group / 32)); exact while
+// chunks x (group / 32) < 2^20, which wf_group_magic's callers check)
+__device__ __forceinline__ int wf_group(int c, int gmagic) { return (int)(((unsigned)c * (unsigned)gmagic) >> 20); }
+static int wf_group_magic(int group) { return (int)(((1u << 20) + (unsigned)(group / 32) - 1) / (unsigned)(group / 32)); }
+static bool wf_group_ok(int K, int group) { return group >= 32 && group % 32 == 0 && K % group == 0 && (long long)(K / 32) * (group / 32) < (1 << 20); }
 
 
 __device__ __forceinline__ void ts_begin(unsigned long long* ts, int id) {
@@ -48,7 +81,8 @@ struct FGArgs {
   const float* x; long long xrs;   // input row m at x + m * xrs (PRO 2: 2K floats, gate | up)
   const float* nw; float eps;      // PRO 1
   const int* codes; int cstride, cb, V, rows; const float* emb;  // PRO 3: row m is item m / rows; its LAST row is emb[(codes[item * cstride] + cb * V)], others come from x
-  const uint16_t* w;
+  const void* w;                   // fragment pack (bf16, or the quantised integers)
+  const float2* wp; int gmagic;    // quantised formats: (scale, bias) pairs, wf_group_magic(group size)
   int K, N, M;
   int kper;                         // gemvm_kernel: K rows per split-K slice (NOT K / gridDim.y in the kernel: gridDim is a dependent vector load from the
                                     // hidden kernel arguments ahead of every weight load, + an integer division)
@@ -86,7 +120,9 @@ struct FGArgs {
 //     contiguous bytes.  LDS: 2304 bytes per 32 k (72 KB for K = 1024, 144 KB for K = 2048).
 //   * RMSNorm: sum of squares per row while staging (fixed order: lane butterfly, then waves 0..7), scale applied to the finished dot
 //     products; EPI as before.  grid = (column blocks, K slices, 8-row chunks of M).
-template <int NSUB, int PRO, int EPI, int ROUNDS>
+// FMT (quantised formats): the ring holds the narrower fragment + its pair; the loads keep their places (unconditional, ahead of the staging,
+// first round plain, refills nontemporal) and a slot is decoded to bf16 where the bf16 form reinterprets it.
+template <int FMT, int NSUB, int PRO, int EPI, int ROUNDS>
 __global__ __launch_bounds__(512) void gemvm_kernel(FGArgs a) {
   constexpr int KOP = 288, FRAG = 4 * KOP, CHB = 2 * FRAG;
   extern __shared__ __attribute__((aligned(16))) char smc[];
@@ -101,9 +137,13 @@ __global__ __launch_bounds__(512) void gemvm_kernel(FGArgs a) {
   char* xf = smc;                           // [nch + 1 spare][2 fragments][4 k octets at pitch 288][16 m slots][8 bf16]
   float* red = (float*)smc;                 // [8 waves][NSUB][2][64] (aliases xf after the main loop)
   float* rsq = (float*)(smc + mainb);       // [8 waves][8 rows] sums of squares (PRO 1)
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4* wblk = (const u32x4*)a.w + ((long long)nb * (K >> 5) + (k_lo >> 5)) * (NSUB * 64) + lane;  // chunk c, sub-block s at + (c NSUB + s) 64
-  u32x4 ring[4][NSUB];
+  typedef typename WFrag<FMT>::Q WQ;
+  const WQ* wblk = (const WQ*)a.w + ((long long)nb * (K >> 5) + (k_lo >> 5)) * (NSUB * 64) + lane;  // chunk c, sub-block s at + (c NSUB + s) 64
+  WQ ring[4][NSUB];
+  // pairs of this column block: group g, sub-block s at + (g NSUB + s) 16
+  const float2* pblk = FMT == KK_WF_BF16 ? nullptr : a.wp + (long long)nb * wf_group(K >> 5, a.gmagic) * (NSUB * 16) + (lane & 15);
+  const int kc0 = k_lo >> 5;
+  float2 pring[FMT == KK_WF_BF16 ? 1 : 4][NSUB] = {};
   // ---- the input rows' loads go out FIRST, the first round of weight loads right behind them: a wave's loads return in order, so the
   // input is there ahead of the weights and the prologue / split runs while the weights are in flight.  Every load below is unconditional
   // (a chunk or octet past the end is clamped to a valid one and its result dropped) and the code is straight-line per ROUNDS: the
@@ -143,6 +183,11 @@ __global__ __launch_bounds__(512) void gemvm_kernel(FGArgs a) {
     const int c = wave + 8 * j, cc = c < nch ? c : nch - 1;
 #pragma unroll
     for (int s = 0; s < NSUB; ++s) ring[j][s] = *(wblk + (long long)(cc * NSUB + s) * 64);
+    if (FMT != KK_WF_BF16) {
+      const int gq = wf_group(kc0 + cc, a.gmagic);
+#pragma unroll
+      for (int s = 0; s < NSUB; ++s) pring[j][s] = *(pblk + (long long)(gq * NSUB + s) * 16);
+    }
   }
   __builtin_amdgcn_sched_barrier(0);  // (the scheduler otherwise issues most of the weight loads BEHIND the split arithmetic to save registers)
   // ---- prologue, exact three-way bf16 split, fragment order
@@ -208,11 +253,16 @@ __global__ __launch_bounds__(512) void gemvm_kernel(FGArgs a) {
         const int c = wave + 8 * (4 * rd + j);
         kk_bf16x8 b[NSUB];
 #pragma unroll
-        for (int s = 0; s < NSUB; ++s) b[s] = __builtin_bit_cast(kk_bf16x8, ring[j][s]);
+        for (int s = 0; s < NSUB; ++s) b[s] = wf_decode(ring[j][s], pring[FMT == KK_WF_BF16 ? 0 : j][s]);
         if (rd + 1 < ROUNDS) {  // refill the slot for the next round
           const int cn = c + 32 < nch ? c + 32 : nch - 1;
 #pragma unroll
           for (int s = 0; s < NSUB; ++s) ring[j][s] = __builtin_nontemporal_load(wblk + (long long)(cn * NSUB + s) * 64);
+          if (FMT != KK_WF_BF16) {
+            const int gq = wf_group(kc0 + cn, a.gmagic);
+#pragma unroll
+            for (int s = 0; s < NSUB; ++s) pring[j][s] = *(pblk + (long long)(gq * NSUB + s) * 16);
+          }
         }
         if (c < nch) {
           const kk_bf16x8 a1 = *(const kk_bf16x8*)(xl + c * CHB), a2 = *(const kk_bf16x8*)(xl + c * CHB + FRAG);

@@ -29,6 +29,7 @@ int kk_fail(const char* msg) {
 }
 extern "C" const char* kk_last_error(void) { return g_err.c_str(); }
 extern "C" int kk_abi_version(void) { return KK_ABI_VERSION; }
+extern "C" int kk_abi_minor(void) { return KK_ABI_MINOR; }
 
 // ------------------------------------------------------------------------------------------------
 // model structures

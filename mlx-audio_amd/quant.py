@@ -33,7 +33,19 @@ def quantize_affine(w: np.ndarray, group_size: int = 64, bits: int = 8):
     return words, scales, lo.astype(np.float32)
 
 
+def check_bits(bits: int) -> int:
+    """The word layout this module states (32 / bits values per uint32 word, none straddling a word) exists for bits 2, 4 and 8 only.  MLX also
+    writes 3- and 6-bit checkpoints, whose values are packed across word boundaries in a layout that is not restated here: refuse them
+    instead of guessing."""
+    bits = int(bits)
+    if bits not in (2, 4, 8):
+        raise ValueError(f"bits={bits}: only 2, 4 and 8 bits fit the word layout dequantize_affine unpacks (32 / bits values per uint32 word); "
+                         "MLX packs 3- and 6-bit values across word boundaries, and that layout is not implemented")
+    return bits
+
+
 def dequantize_affine(words: np.ndarray, scales: np.ndarray, biases: np.ndarray, group_size: int = 64, bits: int = 8) -> np.ndarray:
+    check_bits(bits)
     words = np.asarray(words).astype(np.uint32)
     O = words.shape[0]
     per = 32 // bits
@@ -81,11 +93,45 @@ def quantised_layer_names(weights: Dict[str, np.ndarray], group_size: int = 64):
     return names
 
 
-def quantize_checkpoint(weights: Dict[str, np.ndarray], group_size: int = 64, bits: int = 8) -> Dict[str, np.ndarray]:
-    """What `convert(..., quantize=True)` leaves on disk for the layer set above: uint32-packed `weight`, `scales`, `biases`
-    (test fixtures and bench.py --quantized; the product path only ever DEquantises)."""
-    out = dict(weights)
+def csm_quantised_layer_names(weights: Dict[str, np.ndarray], group_size: int = 64):
+    """The same predicate on a CSM checkpoint (sesame.py:470-474: everything outside `_audio_tokenizer`): the Linears of both Llama stacks,
+    `projection`, `codebook0_head` and the two embedding tables.  `audio_head` is a raw array without a `.weight` suffix and the norms are
+    1-D: both stay as they are.  Names with or without the `model.` prefix."""
+    names = []
     for k in quantised_layer_names(weights, group_size):
+        bare = k[len("model."):] if k.startswith("model.") else k
+        if not bare.startswith("_audio_tokenizer.") and bare != "audio_head":
+            names.append(k)
+    return names
+
+
+def split_triplets(weights: Dict[str, np.ndarray], group_size: int, bits: int, per_layer: Optional[dict] = None):
+    """(plain, triplets): `triplets[{p}.weight] = (words uint32, scales float32, biases float32, group_size, bits)` for every `{p}.weight` that
+    comes with `{p}.scales` and `{p}.biases`, with the layer's own parameters where config["quantization"][p] gives them; a layer mapped to
+    False and everything else lands in `plain` unchanged.  Raises ValueError for bits that check_bits refuses."""
+    per_layer = per_layer or {}
+    plain, trip = {}, {}
+    for k, v in weights.items():
+        if k.endswith(".scales") or k.endswith(".biases"):
+            p = k[: -len(".scales")]
+            if f"{p}.weight" in weights and per_layer.get(p) is not False:
+                continue
+        p = k[: -len(".weight")] if k.endswith(".weight") else None
+        own = per_layer.get(p) if p is not None else None
+        if p is not None and own is not False and f"{p}.scales" in weights and f"{p}.biases" in weights:
+            g, nb = (int(own.get("group_size", group_size)), int(own.get("bits", bits))) if isinstance(own, dict) else (int(group_size), int(bits))
+            trip[k] = (np.ascontiguousarray(np.asarray(v).astype(np.uint32)), np.ascontiguousarray(weights[f"{p}.scales"], np.float32),
+                       np.ascontiguousarray(weights[f"{p}.biases"], np.float32), g, check_bits(nb))
+        else:
+            plain[k] = v
+    return plain, trip
+
+
+def quantize_checkpoint(weights: Dict[str, np.ndarray], group_size: int = 64, bits: int = 8, names=None) -> Dict[str, np.ndarray]:
+    """What `convert(..., quantize=True)` leaves on disk for the layer set above: uint32-packed `weight`, `scales`, `biases`
+    (test fixtures and bench.py --quantized; the product path only ever DEquantises).  `names`: another layer set (csm_quantised_layer_names)."""
+    out = dict(weights)
+    for k in (quantised_layer_names(weights, group_size) if names is None else names):
         words, scales, biases = quantize_affine(np.asarray(weights[k], np.float32), group_size, bits)
         p = k[: -len(".weight")]
         out[k], out[p + ".scales"], out[p + ".biases"] = words, scales, biases

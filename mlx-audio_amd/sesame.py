@@ -76,11 +76,12 @@ class Model:
     `config["mimi_path"]` (a directory with the codec's safetensors in the MLX layout) -- the reference downloads it (sesame.py:456)."""
 
     def __init__(self, config, mimi: Optional[Mimi] = None, weights: Optional[Dict[str, np.ndarray]] = None, weight_dtype: str = "float32",
-                 csm: Optional[SesameModel] = None):
+                 csm: Optional[SesameModel] = None, weight_storage: str = "packed"):
         if isinstance(config, SesameModel):  # round-1 signature Model(csm, mimi)
             csm, config = config, config.cfg
         self.config = config
         self._weight_dtype = weight_dtype
+        self._weight_storage = weight_storage  # of a checkpoint with config["quantization"] (csm.SesameModel)
         self.model = csm
         self._audio_tokenizer = mimi
         self._streaming_decoder = None
@@ -139,16 +140,27 @@ class Model:
     def load_weights(self, weights, strict: bool = True):
         """Accepts checkpoint names with or without the `model.` prefix, sanitized or not; codec tensors (`_audio_tokenizer.*`) are split off."""
         items = dict(weights.items() if hasattr(weights, "items") else weights)
-        items = self.sanitize(items)
+        items = self.sanitize(items)  # (the renames act on the layer path, so a quantised layer's .weight / .scales / .biases move together)
+        quantization = self.config.get("quantization") if isinstance(self.config, dict) else None
+        bare = lambda k: k[len("model."):] if k.startswith("model.") else k
+        if quantization is not None:  # per-layer entries are keyed by module path: the same renames, the same prefix
+            quantization = {k if k in ("group_size", "bits") else bare(next(iter(self.sanitize({k + ".weight": None}))))[: -len(".weight")]: v
+                            for k, v in quantization.items()}
+        names = {bare(k) for k in items}
         csm_w, mimi_w = {}, {}
         for k, v in items.items():
-            k = k[len("model."):] if k.startswith("model.") else k
-            a = v.float().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, np.float32)
+            k = bare(k)
+            p = k[: -len(".weight")] if k.endswith(".weight") else None
+            if quantization is not None and p is not None and p + ".scales" in names and quantization.get(p) is not False:
+                # the uint32 words of a quantised layer: bit patterns, not numbers
+                a = v.view(torch.int32).numpy().view(np.uint32) if isinstance(v, torch.Tensor) else np.asarray(v).astype(np.uint32)
+            else:
+                a = v.float().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, np.float32)
             if k.startswith("_audio_tokenizer."):
                 mimi_w[k[len("_audio_tokenizer."):]] = a
             else:
                 csm_w[k] = a
-        self.model = SesameModel(self._cfg(), csm_w, weight_dtype=self._weight_dtype)
+        self.model = SesameModel(self._cfg(), csm_w, weight_dtype=self._weight_dtype, quantization=quantization, weight_storage=self._weight_storage)
         if mimi_w and self._audio_tokenizer is None:
             from .mimi import mimi_202407
 

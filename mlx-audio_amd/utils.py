@@ -52,12 +52,18 @@ def get_model_and_args(model_type: str, model_name):
     raise ValueError(msg)
 
 
-def load_model(model_path, lazy: bool = False, strict: bool = True, compute_dtype: str = None, quantization_kernel: str = "exact", **kwargs):
+def load_model(model_path, lazy: bool = False, strict: bool = True, compute_dtype: str = None, quantization_kernel: str = "exact",
+               weight_storage: str = "packed", **kwargs):
     """Returns a ready `kokoro.Model` (weights folded, packed and resident in HBM).
     Raises FileNotFoundError when no safetensors are found, ValueError for an unsupported model type.
     quantization_kernel (only matters for a checkpoint with config["quantization"]): "exact" (default) multiplies by the dequantised
     weights `scale * q + bias` with the mode's ordinary kernels, i.e. the reference's arithmetic (tts/utils.py:241-260); "mxfp8" is the
-    opt-in that re-quantises an 8-bit checkpoint's linears to e4m3 and runs them on the block-scaled fp8 matrix instruction."""
+    opt-in that re-quantises an 8-bit checkpoint's linears to e4m3 and runs them on the block-scaled fp8 matrix instruction.
+    weight_storage (a sesame checkpoint with config["quantization"]): "packed" (default) keeps the 4- / 8-bit Linears quantised in device memory
+    and decodes them inside the matrix-core kernels -- the bits of bf16 weight mode on the dequantised checkpoint; "dequantized" dequantises
+    at load.  2-bit checkpoints are always dequantised; 3- and 6-bit ones raise ValueError (quant.check_bits)."""
+    if weight_storage not in ("packed", "dequantized"):
+        raise ValueError(f"weight_storage must be 'packed' or 'dequantized', not {weight_storage!r}")
     if quantization_kernel not in ("exact", "mxfp8"):
         raise ValueError(f"quantization_kernel must be 'exact' or 'mxfp8', not {quantization_kernel!r}")
     if isinstance(model_path, str):
@@ -89,9 +95,10 @@ def load_model(model_path, lazy: bool = False, strict: bool = True, compute_dtyp
         any_bf16 = any(getattr(v, "dtype", None) == torch.bfloat16 for v in weights.values())
         compute_dtype = "bfloat16" if any_bf16 else "float32"  # the checkpoint dtype decides, as in the reference
     if model_type == "sesame":
-        # sesame.Model(config) has no ModelConfig (tts/utils.py:226-230 passes the dict); the checkpoint dtype picks the weight storage
+        # sesame.Model(config) has no ModelConfig (tts/utils.py:226-230 passes the dict); the checkpoint dtype picks the weight storage, and
+        # config["quantization"] (read by Model.load_weights) routes the uint32 / scales / biases triplets to the quantised loader
         model = arch.Model(dict(config, **{k: v for k, v in kwargs.items() if k in ("mimi_path", "text_tokenizer")}),
-                           weight_dtype="bfloat16" if compute_dtype == "bfloat16" else "float32", mimi=kwargs.get("mimi"))
+                           weight_dtype="bfloat16" if compute_dtype == "bfloat16" else "float32", mimi=kwargs.get("mimi"), weight_storage=weight_storage)
         model.load_weights(weights, strict=strict)
         return model
     quantization = config.get("quantization", None)

@@ -1,5 +1,6 @@
 """CSM-1B frame generation rate (config 4): B streams, one prompt block then N single-token frames; audio-seconds (80 ms per frame)
-per wall-second.  python tools/bench_csm.py [--batch 8] [--prompt 64] [--frames 10] [--layers 16]"""
+per wall-second.  python tools/bench_csm.py [--batch 8] [--prompt 64] [--frames 10] [--weights float32|bfloat16|q8|q4] [--group-size 64]
+--weights q8 / q4: the synthetic checkpoint MLX-affine-quantised (quant.quantize_checkpoint) and kept packed in device memory."""
 import argparse
 import json
 import os
@@ -19,13 +20,25 @@ ap.add_argument("--batch", type=int, default=8)
 ap.add_argument("--prompt", type=int, default=64)
 ap.add_argument("--frames", type=int, default=10)
 ap.add_argument("--e2e", action="store_true", help="config 4 end to end: reference-audio prompt (Mimi.encode) -> frame loop -> Mimi.decode")
-ap.add_argument("--weights", default="float32", choices=["float32", "bfloat16"], help="weight storage of the Linear layers (kk_csm_set_weight_dtype)")
+ap.add_argument("--weights", default="float32", choices=["float32", "bfloat16", "q8", "q4"],
+                help="weight storage of the Linear layers (kk_csm_set_weight_dtype; q8 / q4: a quantised checkpoint, packed storage)")
+ap.add_argument("--group-size", type=int, default=64, help="quantisation group of --weights q8 / q4")
 a = ap.parse_args()
 cfg = P.csm_config()
 t0 = time.time()
 w = P.csm_synth_checkpoint(cfg, 0)
+quantization = None
+if a.weights in ("q8", "q4"):
+    from mlx_audio_amd.quant import csm_quantised_layer_names, quantize_checkpoint
+
+    # (the embedding tables are gather tables, dequantised at load whatever the storage: left as floats here to spare the host their quantisation)
+    names = [k for k in csm_quantised_layer_names(w, a.group_size) if not k.endswith("embeddings.weight")]
+    quantization = {"group_size": a.group_size, "bits": int(a.weights[1])}
+    w = quantize_checkpoint(w, a.group_size, quantization["bits"], names=names)
 t1 = time.time()
-model = SesameModel(cfg, w, weight_dtype=a.weights)
+model = SesameModel(cfg, w, weight_dtype="float32" if quantization else a.weights, quantization=quantization)
+storage = {"weight_format": model.weight_format, "weight_fallback": model.weight_fallback, "weight_bytes": model.weight_bytes}
+wname = {"float32": "fp32", "bfloat16": "bf16 weights / fp32 arithmetic"}.get(a.weights, f"{a.weights} packed weights (group {a.group_size}) / fp32 arithmetic")
 del w
 model.setup_caches(a.batch)
 t2 = time.time()
@@ -46,7 +59,7 @@ if a.e2e:
     secs = res.audio[0].shape[0] / 24000.0
     print(json.dumps({"metric": "audio-sec/sec (xRT), CSM-1B end to end: reference-audio prompt (Mimi.encode) + text ids -> frames -> Mimi.decode",
                       "value": B * secs / res.processing_time_seconds, "wall_s": res.processing_time_seconds, "audio_s_per_stream": secs, "batch": B,
-                      "frames": res.frames[0], "prompt_frames": 24 + 26 + 24, "dtype": ("bf16-weight" if a.weights == "bfloat16" else "f32") + " frame generator, fp32 Mimi.encode, bf16 Mimi.decode",
+                      "frames": res.frames[0], "prompt_frames": 24 + 26 + 24, "dtype": ("f32" if a.weights == "float32" else a.weights + "-weight") + " frame generator, fp32 Mimi.encode, bf16 Mimi.decode", **storage,
                       "data": "synthetic (random-init weights, random token ids, noise reference audio, EOS ignored)",
                       "setup_s": {"synth_checkpoint": round(t1 - t0, 1), "load_finalize": round(t2 - t1, 1)}}))
     sys.exit(0)
@@ -82,7 +95,7 @@ for i in range(a.frames):
     codes = model.generate_frame(step_tok, step_msk, temperature=0.9, top_k=50, uniforms=us[3 + i])
 torch.cuda.synchronize()
 dt = (time.perf_counter() - ts) / a.frames
-print(json.dumps({"metric": "audio-sec/sec (xRT), CSM-1B frame generation (80 ms of audio per frame and stream), " + ("bf16 weights / fp32 arithmetic" if a.weights == "bfloat16" else "fp32"), "value": B * 0.08 / dt,
-                  "ms_per_frame": dt * 1e3, "batch": B, "prompt_tokens": a.prompt, "prefill_ms": prefill_ms, "prefill_ms_second_call": prefill2_ms, "frames_timed": a.frames, "dtype": "bf16 weights, f32 arithmetic" if a.weights == "bfloat16" else "f32",
+print(json.dumps({"metric": "audio-sec/sec (xRT), CSM-1B frame generation (80 ms of audio per frame and stream), " + wname, "value": B * 0.08 / dt,
+                  "ms_per_frame": dt * 1e3, "batch": B, "prompt_tokens": a.prompt, "prefill_ms": prefill_ms, "prefill_ms_second_call": prefill2_ms, "frames_timed": a.frames, "dtype": wname, **storage,
                   "data": "synthetic (random-init CSM-1B weights, random prompt, injected uniforms)",
                   "setup_s": {"synth_checkpoint": round(t1 - t0, 1), "load_finalize": round(t2 - t1, 1)}}))

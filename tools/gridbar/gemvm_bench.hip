@@ -41,8 +41,8 @@ int main(int argc, char** argv) {
   hipLaunchKernelGGL(fill_kernel, dim3(32), dim3(256), 0, st, (uint32_t*)h, (size_t)M * D, 0x3f000000u);
   hipLaunchKernelGGL(fill_kernel, dim3(4), dim3(256), 0, st, (uint32_t*)nw, (size_t)D, 0x3f800000u);
   CK(hipStreamSynchronize(st));
-  CK(hipFuncSetAttribute((const void*)gemvm_kernel<4, 1, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  CK(hipFuncSetAttribute((const void*)gemvm_kernel<2, 2, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  CK(hipFuncSetAttribute((const void*)gemvm_kernel<KK_WF_BF16, 4, 1, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  CK(hipFuncSetAttribute((const void*)gemvm_kernel<KK_WF_BF16, 2, 2, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   const int mode = argc > 1 ? atoi(argv[1]) : 0;
   const bool marks = argc > 2 ? atoi(argv[2]) != 0 : true;  // in-kernel marks (their atomics cost ~1 us per kernel)  // 0 gate|up -> down -> combine; 1 gate|up only; 2 gate|up -> down
   hipGraph_t g; hipGraphExec_t ge;
@@ -51,12 +51,12 @@ int main(int argc, char** argv) {
     FGArgs a; memset(&a, 0, sizeof a);
     a.x = h; a.xrs = D; a.nw = nw; a.eps = 1e-5f; a.w = wgu + (size_t)(i % nmat) * gub; a.K = D; a.kper = D; a.N = 2 * I; a.M = M; a.out = gu; a.ors = 2 * I;
     a.ts = marks ? ts + (size_t)(3 * i) * TSW : nullptr; a.ts_id = 1;
-    hipLaunchKernelGGL((gemvm_kernel<4, 1, 0, 1>), dim3(2 * I / 64, 1, 1), dim3(512), gm_lds_bytes(4, D), st, a);
+    hipLaunchKernelGGL((gemvm_kernel<KK_WF_BF16, 4, 1, 0, 1>), dim3(2 * I / 64, 1, 1), dim3(512), gm_lds_bytes(4, D), st, a);
     if (mode == 1) continue;
     memset(&a, 0, sizeof a);
     a.x = gu; a.xrs = 2 * I; a.w = wdn + (size_t)(i % nmat) * dnb; a.K = I; a.kper = I / 8; a.N = D; a.M = M; a.out = part; a.ors = D; a.pss = (long long)M * D;
     a.ts = marks ? ts + (size_t)(3 * i + 1) * TSW : nullptr; a.ts_id = 2;
-    hipLaunchKernelGGL((gemvm_kernel<2, 2, 2, 1>), dim3(D / 32, 8, 1), dim3(512), gm_lds_bytes(2, I / 8), st, a);
+    hipLaunchKernelGGL((gemvm_kernel<KK_WF_BF16, 2, 2, 2, 1>), dim3(D / 32, 8, 1), dim3(512), gm_lds_bytes(2, I / 8), st, a);
     if (mode == 2) continue;
     hipLaunchKernelGGL(combine_kernel, dim3(M * D / 256), dim3(256), 0, st, part, 8, (long long)M * D, (long long)M * D, h);
   }
