@@ -30,7 +30,8 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 1   /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...) */
+#define KK_ABI_MINOR 2   /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+                            2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -345,11 +346,39 @@ int kk_csm_set_padding(kk_csm* m, int B, const int32_t* pad_host);
 size_t kk_csm_workspace_bytes(kk_csm* m, int B, int S);
 /* One audio frame.  tokens [B][S][n_cb+1] int32 and tokens_mask (same shape, float 0/1) on the device; the S new positions continue
  * the backbone cache (a block of S > 1 must start an empty cache, as index_causal_mask implies, sesame.py:41-48).  Sampling:
- * temperature == 0 or uniforms == NULL -> argmax (make_sampler's rule for temp 0); otherwise inverse CDF over the top_k (<= 64)
- * logits of softmax(logit / temperature) in descending order with the injected uniforms [B][n_cb] -- the distribution of
- * make_sampler(temp, top_k) with a reproducible draw.  codes_out [B][n_cb] int32. */
+ * temperature == 0 or uniforms == NULL -> argmax (make_sampler's rule for temp 0); otherwise inverse CDF over the top_k logits
+ * (top_k 0 / -1: the whole vocabulary; see kk_csm_sampler) of softmax(logit / temperature) in descending order with the injected
+ * uniforms [B][n_cb] -- the distribution of make_sampler(temp, top_k) with a reproducible draw.  codes_out [B][n_cb] int32. */
 int kk_csm_generate_frame(kk_csm* m, void* stream, int B, int S, const int32_t* tokens, const float* tokens_mask, float temperature, int top_k,
                           const float* uniforms, void* workspace, size_t workspace_bytes, int32_t* codes_out);
+/* The sampler of a frame: mlx_lm's make_sampler(temp, top_p, min_p, min_tokens_to_keep, top_k) as sesame.py:696,719 takes it.  mlx_lm is not
+ * part of the reference tree: the rule below is written from upstream knowledge and parity with mlx_lm is UNPINNED.
+ *   l[0..V) one row of fp32 logits (a NaN reads as -inf); order = indices by (logit descending, index ascending); p = softmax(l) over the
+ *   WHOLE vocabulary at temperature 1 (the filters see untempered probabilities; the temperature acts in the draw only).  Every filter keeps a
+ *   prefix of `order`, the kept set is the shortest:
+ *     n_k = top_k if 0 < top_k < V, else V (0 and -1 switch the filter off; no clamp at 64);
+ *     n_p: with 0 < top_p < 1, order[j] is kept iff sum(p[order[:j]]) < top_p (the first token always); else V;
+ *     n_m: with min_p > 0, the tokens with p >= min_p p[order[0]], never fewer than min_tokens_to_keep; else V;
+ *     n = min(n_k, n_p, n_m); weights w[j] = exp((l[order[j]] - l[order[0]]) / temperature) for j < n, running sums c, target = u c[n-1],
+ *     the pick is order[j] for the first j with c[j] >= target (the last kept token if none).
+ *   temperature == 0, or no uniform source: arg-max, lower index on ties.  A pick is always in [0, V).
+ * Uniforms: the injected array has priority.  Without it and with use_device_rng, Philox4x32-10 in the sampling kernels:
+ *   philox4(seed, (uint64) stream_id << 32 | pos, code book) -> u = ((out[0] >> 8) + 0.5) 2^-24, in (0, 1); pos = the item's own position of the
+ *   frame being generated (cache slot minus its padding), stream_id = stream_ids[b] or b.  Nothing in the counter depends on the batch layout.
+ * With top_p and min_p off and 0 < top_k <= 64 the kernel and the picks are those of kk_csm_generate_frame before this struct existed. */
+typedef struct kk_csm_sampler {
+  float temperature;
+  int32_t top_k;
+  float top_p, min_p;
+  int32_t min_tokens_to_keep;
+  uint64_t seed;
+  int32_t use_device_rng;
+} kk_csm_sampler;
+/* kk_csm_generate_frame with the whole sampler; kk_csm_generate_frame is this call with {temperature, top_k, 0, 0, 1, 0, 0} and no stream ids.
+ * stream_ids: device int32 [B] or NULL (read by the kernels at every frame, replayed graphs included).  The seed is copied to device memory
+ * when it changes, so a new seed replays the same graph; every other sampler field and the stream_ids pointer key the graph. */
+int kk_csm_generate_frame_ex(kk_csm* m, void* stream, int B, int S, const int32_t* tokens, const float* tokens_mask, const kk_csm_sampler* sampler,
+                             const float* uniforms, const int32_t* stream_ids, void* workspace, size_t workspace_bytes, int32_t* codes_out);
 /* graph replay of the single-token frame step: the third call with identical pointers / B / sampler settings and every later one is ONE
  * hipGraphLaunch (the backbone position is a device counter, so the captured step is position-independent); results are unchanged */
 int kk_csm_set_graph_mode(kk_csm* m, int on);
@@ -363,6 +392,12 @@ int kk_csm_debug_timestamps(unsigned long long* buf, int capacity);
 /* the sampler of generate_frame on its own (mlx_lm make_sampler(temp, top_k), sesame.py:335-336,719): logits [B][V] -> codes [B];
  * uniforms [B] or NULL (argmax).  Radix select of the top_k set + one-wave sort; V <= 8192. */
 int kk_op_csm_sample(void* stream, int B, int V, const float* logits, float temperature, int top_k, const float* uniforms, int32_t* codes_out);
+/* kk_op_csm_sample with the whole kk_csm_sampler, through the launcher the frame uses: uniforms [B] (priority) or, with use_device_rng, Philox on
+ * (sampler->seed, stream_ids[b] or b, pos[b] or 0, code book 0); stream_ids / pos: device int32 [B] or NULL.  Synchronises when it draws on the device. */
+int kk_op_csm_sample_ex(void* stream, int B, int V, const float* logits, const kk_csm_sampler* sampler, const float* uniforms, const int32_t* stream_ids,
+                        const int32_t* pos, int32_t* codes_out);
+/* the uniforms the sampling kernels draw: out [B][n_cb] (device) for (seed, stream_ids[b] or b, pos[b] or 0, code book 0..n_cb-1).  Synchronises. */
+int kk_op_csm_uniforms(void* stream, int B, int n_cb, uint64_t seed, const int32_t* stream_ids, const int32_t* pos, float* out);
 /* The kernels of the frame step on their own (tests), each through the launcher the frame runs.  Fragment pack of the bf16 weights (host):
  * kk_csm_frag_choice gives the split-K slices and 16-column sub-blocks per block the generator picks for a K x N matrix (nsub = 0: no pack;
  * split_ok: the matrix is a down projection, the one launched split-K); kk_csm_frag_pack lays w [K][N] fp32 out as bf16 (round to nearest

@@ -49,6 +49,11 @@ class KKCsmConfig(C.Structure):
                 ("backbone", KKLlamaArgs), ("decoder", KKLlamaArgs)]
 
 
+class KKCsmSampler(C.Structure):  # kk_csm_sampler
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("min_p", C.c_float), ("min_tokens_to_keep", C.c_int32),
+                ("seed", C.c_uint64), ("use_device_rng", C.c_int32)]
+
+
 # every symbol include/kokoro_hip.h declares: name -> (restype, argtypes)
 _vp, _i, _f, _sz, _u64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_uint64
 SIGNATURES = {
@@ -103,10 +108,13 @@ SIGNATURES = {
     "kk_csm_set_padding": (_i, [_vp, _i, _vp]),
     "kk_csm_workspace_bytes": (_sz, [_vp, _i, _i]),
     "kk_csm_generate_frame": (_i, [_vp, _vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _sz, _vp]),
+    "kk_csm_generate_frame_ex": (_i, [_vp, _vp, _i, _i, _vp, _vp, C.POINTER(KKCsmSampler), _vp, _vp, _vp, _sz, _vp]),
     "kk_csm_set_graph_mode": (_i, [_vp, _i]),
     "kk_csm_debug_logits": (_i, [_vp, _vp, _i, _vp]),
     "kk_csm_debug_timestamps": (_i, [_vp, _i]),
     "kk_op_csm_sample": (_i, [_vp, _i, _i, _vp, _f, _i, _vp, _vp]),
+    "kk_op_csm_sample_ex": (_i, [_vp, _i, _i, _vp, C.POINTER(KKCsmSampler), _vp, _vp, _vp, _vp]),
+    "kk_op_csm_uniforms": (_i, [_vp, _i, _i, _u64, _vp, _vp, _vp]),
     "kk_csm_frag_choice": (_i, [_i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "kk_csm_frag_pack": (_i, [_vp, _i, _i, _i, _vp]),
     "kk_csm_qfrag_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(_sz), C.POINTER(_sz)]),
@@ -186,7 +194,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 1:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 2:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

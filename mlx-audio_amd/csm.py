@@ -58,6 +58,7 @@ class SesameModel:
         self.max_batch = 0
         self._graph = False
         self._gbuf = {}
+        self._sid = {}
         if weights is not None:
             self.load_weights(weights)
 
@@ -72,7 +73,7 @@ class SesameModel:
         h = C.c_void_p()
         check(self.lib.kk_csm_share(self._h, C.byref(h)), "kk_csm_share")
         other._h, other._parent = h, self
-        other._ws, other._enabled, other.max_batch, other._graph, other._gbuf = None, False, 0, False, {}
+        other._ws, other._enabled, other.max_batch, other._graph, other._gbuf, other._sid = None, False, 0, False, {}, {}
         return other
 
     def __del__(self):
@@ -167,9 +168,13 @@ class SesameModel:
         return int(self.lib.kk_csm_position(self._h))
 
     # ---- sesame.py:349-395
-    def generate_frame(self, tokens, tokens_mask, input_pos=None, temperature: float = 0.0, top_k: int = 50, uniforms=None) -> torch.Tensor:
+    def generate_frame(self, tokens, tokens_mask, input_pos=None, temperature: float = 0.0, top_k: int = 50, uniforms=None, sampler=None,
+                       seed: Optional[int] = None, stream_ids=None) -> torch.Tensor:
         """tokens [B, S, n_cb+1] int, tokens_mask same shape; `input_pos` (the reference's argument) is checked against the cache position.
-        Returns codes [B, n_cb] int32 on the device."""
+        `sampler` (anything with temp / top_k / top_p / min_p / min_tokens_to_keep, e.g. sesame.Sampler) replaces `temperature` / `top_k` and
+        brings the top-p / min-p filters (the rule: kk_csm_sampler in kokoro_hip.h).  `uniforms` [B, n_cb] are the injected draws; without them
+        and with `seed`, the kernels draw from Philox on (seed, stream id, position, code book) -- `stream_ids` [B] int, default the batch
+        index.  Neither: arg-max.  Returns codes [B, n_cb] int32 on the device."""
         assert self.caches_are_enabled(), "backbone caches are not enabled"
         tokens = torch.as_tensor(tokens).to(device=self.device, dtype=torch.int32).contiguous()
         mask = torch.as_tensor(tokens_mask).to(device=self.device, dtype=torch.float32).contiguous()
@@ -186,6 +191,21 @@ class SesameModel:
             u = torch.as_tensor(uniforms).to(device=self.device, dtype=torch.float32).contiguous()
             if tuple(u.shape) != (B, ncb):
                 raise ValueError(f"uniforms must be [B, {ncb}]")
+        sp = _lib.KKCsmSampler(float(temperature), int(top_k), 0.0, 0.0, 1, 0, 0)
+        if sampler is not None:
+            sp = _lib.KKCsmSampler(float(sampler.temp), int(sampler.top_k), float(getattr(sampler, "top_p", 0.0)), float(getattr(sampler, "min_p", 0.0)),
+                                   int(getattr(sampler, "min_tokens_to_keep", 1)), 0, 0)
+        sid = None
+        if u is None and seed is not None:
+            sp.seed, sp.use_device_rng = int(seed) & 0xFFFFFFFFFFFFFFFF, 1
+            if stream_ids is not None:
+                sid = self._sid.get(B)  # one persistent buffer per batch size: a replayed graph reads it through the same pointer
+                if sid is None:
+                    sid = self._sid[B] = torch.empty(B, dtype=torch.int32, device=self.device)
+                ids = torch.as_tensor(stream_ids).to(dtype=torch.int32).reshape(-1)
+                if ids.numel() != B:
+                    raise ValueError(f"stream_ids must hold {B} entries")
+                sid.copy_(ids)
         if self._graph and S == 1:
             key = (B, u is not None)
             if key not in self._gbuf:
@@ -205,9 +225,10 @@ class SesameModel:
             if self._ws is None or self._ws.numel() < need:
                 self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             codes = self._gbuf[(B, u is not None)][3] if (self._graph and S == 1) else torch.empty((B, ncb), dtype=torch.int32, device=self.device)
-            check(self.lib.kk_csm_generate_frame(self._h, self._stream(), B, S, C.c_void_p(tokens.data_ptr()), C.c_void_p(mask.data_ptr()),
-                                                 float(temperature), int(top_k), C.c_void_p(u.data_ptr()) if u is not None else None,
-                                                 C.c_void_p(self._ws.data_ptr()), need, C.c_void_p(codes.data_ptr())), "kk_csm_generate_frame")
+            check(self.lib.kk_csm_generate_frame_ex(self._h, self._stream(), B, S, C.c_void_p(tokens.data_ptr()), C.c_void_p(mask.data_ptr()),
+                                                    C.byref(sp), C.c_void_p(u.data_ptr()) if u is not None else None,
+                                                    C.c_void_p(sid.data_ptr()) if sid is not None else None,
+                                                    C.c_void_p(self._ws.data_ptr()), need, C.c_void_p(codes.data_ptr())), "kk_csm_generate_frame")
         self._last_B = B
         return codes
 

@@ -19,6 +19,7 @@
 #include "../../include/kokoro_hip.h"
 #include "kk_common.h"
 #include "kk_host.h"
+#include "kk_philox.h"
 
 namespace {
 
@@ -95,6 +96,10 @@ struct kk_csm {
   // synchronous hipMemset / hipMemcpy here would touch the legacy stream and break another thread's graph capture)
   bool reset_pending = false, pad_pending = false;
   std::vector<int32_t> pad_host;
+  // device RNG of the sampler (kk_csm_sampler.use_device_rng): the Philox seed in device memory, read by the sampling kernels
+  unsigned long long* seed_dev = nullptr;
+  unsigned long long seed_host = 0;
+  bool seed_valid = false;
   const kk_csm* weights_of = nullptr;  // kk_csm_share: `dev` / `devb` / `devq` belong to that generator (immutable after finalize), not to this one
 };
 
@@ -645,13 +650,47 @@ __global__ __launch_bounds__(256) void swiglu_kernel(const float* gu, int I, lon
   out[e] = (g / (1.0f + expf(-g))) * u;
 }
 
+// Where a sampling launch takes its uniform from: the injected array (priority), or Philox4x32-10 keyed by the device seed on the counter
+// (stream id << 32 | position, code book) -- nothing in it depends on the batch layout, so a stream draws the same numbers alone, in a ragged
+// batch or in another slot.  position = *pos + pos_add - pad[b]: the frame being generated, counted in the item's own tokens.
+struct SampleSrc {
+  const float* u = nullptr;  // [B] at pitch ustride, or null
+  int ustride = 0;
+  const unsigned long long* seed = nullptr;  // device; null = no device RNG
+  const int* sid = nullptr;                  // [B] stream ids, null = batch index
+  const int* pos = nullptr;                  // device position(s): pos[b * pos_stride]
+  int pos_stride = 0, pos_add = 0;
+  const int* pad = nullptr;                  // [B] left padding, or null
+  int cb = 0;
+};
+__device__ __forceinline__ float sample_uniform(const SampleSrc& a, int b) {
+  if (a.u) return a.u[(long long)b * a.ustride];
+  const uint32_t sid = a.sid ? (uint32_t)a.sid[b] : (uint32_t)b;
+  const int p = (a.pos ? a.pos[(long long)b * a.pos_stride] : 0) + a.pos_add - (a.pad ? a.pad[b] : 0);
+  uint32_t r[4];
+  philox4(*a.seed, ((uint64_t)sid << 32) | (uint32_t)p, (uint32_t)a.cb, r);
+  return philox_unit(r[0]);
+}
+__global__ __launch_bounds__(256) void sample_uniforms_kernel(SampleSrc a, int B, int ncb, float* out) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= B * ncb) return;
+  a.cb = e % ncb;
+  out[e] = sample_uniform(a, e / ncb);
+}
+struct SampleCfg {  // kk_csm_sampler as the kernels read it (kokoro_hip.h states the rule)
+  float temp = 0.f;
+  int top_k = 0;
+  float top_p = 0.f, min_p = 0.f;
+  int min_keep = 1;
+};
+
 // one workgroup per item: argmax (temp == 0 or no uniforms) or inverse CDF over the top_k logits in descending order
-// (ties: lower index first) of softmax(logit / temp) with the injected uniform u[b].
+// (ties: lower index first) of softmax(logit / temp) with the uniform of item b (sample_uniform).
 // Round-based selection (the fallback of sample_select_kernel below): every thread keeps its V / 256 logits and their running maximum in registers; a round is one wave-shuffle argmax, one
 // LDS exchange between the four waves (double-buffered: one barrier per round) and a re-scan by the single thread that owned the
 // winner -- ~0.3 us per round instead of a scan of all V logits from LDS plus an eight-level LDS tree (90 -> ~15 us for top-50).
 template <int NPER>
-__device__ void sample_rounds(float (&v)[NPER], int V, float temp, int top_k, const float* u, int ustride, int* out, int ostride) {
+__device__ void sample_rounds(float (&v)[NPER], int V, float temp, int top_k, const SampleSrc& src, int* out, int ostride) {
   __shared__ float wv[2][4];
   __shared__ int wi[2][4];
   __shared__ float topv[64];
@@ -662,7 +701,7 @@ __device__ void sample_rounds(float (&v)[NPER], int V, float temp, int top_k, co
 #pragma unroll
   for (int i = 0; i < NPER; ++i)
     if (v[i] > bv) { bv = v[i]; bi = tid + 256 * i; }  // ascending index: the lower index wins a tie
-  const bool greedy = u == nullptr || temp == 0.f;
+  const bool greedy = (src.u == nullptr && src.seed == nullptr) || temp == 0.f;
   const int k = greedy ? 1 : (top_k < 64 ? (top_k < V ? top_k : V) : 64);
   for (int r = 0; r < k; ++r) {
     float cv = bv;
@@ -705,12 +744,12 @@ __device__ void sample_rounds(float (&v)[NPER], int V, float temp, int top_k, co
         run += expf(topv[r] / temp - z0);
         c[r] = run;
       }
-      const float target = u[(long long)b * ustride] * run;
+      const float target = sample_uniform(src, b) * run;
       int j = 0;
       while (j < k - 1 && c[j] < target) ++j;
       pick = topi[j];
     }
-    out[(long long)b * ostride] = pick;
+    out[(long long)b * ostride] = (unsigned)pick < (unsigned)V ? pick : 0;  // (a row of NaNs wins no round: still a valid row of the next launch's gather)
   }
 }
 // Top-k by radix SELECT instead of k rounds of arg-max (rounds are serial: 50 x ~1.3 us however they are organised -- a 256-thread
@@ -726,8 +765,7 @@ __device__ __forceinline__ unsigned sk_key(float f) {
 __device__ __forceinline__ float sk_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 template <int NPER>
-__global__ __launch_bounds__(256) void sample_select_kernel(const float* logits, int V, float temp, int top_k, const float* u, int ustride, int* out,
-                                                            int ostride) {
+__global__ __launch_bounds__(256) void sample_select_kernel(const float* logits, int V, float temp, int top_k, SampleSrc src, int* out, int ostride) {
   __shared__ unsigned hist[256];
   __shared__ unsigned s_prefix, s_krem, s_bin, ccount;
   __shared__ unsigned ckey[64];
@@ -739,7 +777,7 @@ __global__ __launch_bounds__(256) void sample_select_kernel(const float* logits,
     const int j = tid + 256 * i;
     key[i] = j < V ? sk_key(logits[(long long)b * V + j]) : 0u;
   }
-  const bool greedy = u == nullptr || temp == 0.f;
+  const bool greedy = (src.u == nullptr && src.seed == nullptr) || temp == 0.f;
   const int k = greedy ? 1 : (top_k < 64 ? (top_k < V ? top_k : V) : 64);
   if (greedy) {  // arg-max (lower index on ties): the key order is the float order, so one max over (key, ~index) does it -- no histogram
     __shared__ unsigned long long wbest[4];
@@ -816,7 +854,7 @@ __global__ __launch_bounds__(256) void sample_select_kernel(const float* logits,
     float v[NPER];
 #pragma unroll
     for (int i = 0; i < NPER; ++i) v[i] = tid + 256 * i < V ? sk_unkey(key[i]) : -INFINITY;
-    sample_rounds<NPER>(v, V, temp, top_k, u, ustride, out, ostride);
+    sample_rounds<NPER>(v, V, temp, top_k, src, out, ostride);
     return;
   }
   if (wave != 0) return;
@@ -842,7 +880,7 @@ __global__ __launch_bounds__(256) void sample_select_kernel(const float* logits,
   if (!greedy) {
     float run = 0.f;
     for (int r = 0; r < k; ++r) run += lane_f(e, r);
-    const float target = u[(long long)b * ustride] * run;
+    const float target = sample_uniform(src, b) * run;
     int j = 0;
     float c = lane_f(e, 0);
     while (j < k - 1 && c < target) {
@@ -851,14 +889,170 @@ __global__ __launch_bounds__(256) void sample_select_kernel(const float* logits,
     }
     pick = __builtin_amdgcn_readlane(ii, __builtin_amdgcn_readfirstlane(j));
   }
-  if (lane == 0) out[(long long)b * ostride] = pick;
+  if (lane == 0) out[(long long)b * ostride] = (unsigned)pick < (unsigned)V ? pick : 0;
 }
 
-int launch_sample(const float* logits, int V, float temp, int top_k, const float* u, int ustride, int* out, int ostride, int B, hipStream_t st) {
-  if (V <= 256 * 4) hipLaunchKernelGGL(sample_select_kernel<4>, dim3(B), dim3(256), 0, st, logits, V, temp, top_k, u, ustride, out, ostride);
-  else if (V <= 256 * 9) hipLaunchKernelGGL(sample_select_kernel<9>, dim3(B), dim3(256), 0, st, logits, V, temp, top_k, u, ustride, out, ostride);
-  else if (V <= 256 * 32) hipLaunchKernelGGL(sample_select_kernel<32>, dim3(B), dim3(256), 0, st, logits, V, temp, top_k, u, ustride, out, ostride);
-  else return kk_fail("kk_csm: audio vocabulary larger than 8192 entries");
+// The full make_sampler family on the WHOLE vocabulary (top_k = 0 / >= V / > 64, top_p, min_p): one 256-thread workgroup per item.
+//   1. (order-preserving key, ~index) pairs of all V logits in LDS (NaN reads as -inf), bitonic sort descending: the order is (logit
+//      descending, index ascending), the order of sample_select_kernel and of the oracle;
+//   2. thread t owns the N / 256 consecutive sorted positions t N / 256 ..: it sums p-weights exp(l - l_max) and draw weights
+//      exp((l - l_max) / temp) over them in order, one fixed-tree block scan (wave shuffles, then the four wave totals in wave order) gives
+//      every thread the sums in front of its positions and Z -- no atomics anywhere, the same inputs give the same pick in every slot;
+//   3. the cuts: the first sorted position whose mass in front is not < top_p Z, the first whose weight is not >= min_p (p_max's weight
+//      is 1), each by a block minimum; n = min(n_k, n_p, max(n_m, min_keep));
+//   4. c[n - 1] from its owner, target = u c[n - 1], the first position j < n with c[j] >= target by a block minimum (n - 1 if none).
+// Dynamic LDS: N pairs of 8 bytes (64 KiB at N = 8192) + 64 bytes of exchange; no scratch.
+__device__ __forceinline__ int sf_block_min(int v, int* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int t = __shfl_xor(v, o);
+    v = t < v ? t : v;
+  }
+  __syncthreads();  // (sh may still be read from the previous use)
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const int a = sh[0] < sh[1] ? sh[0] : sh[1], b = sh[2] < sh[3] ? sh[2] : sh[3];
+  return a < b ? a : b;
+}
+template <int N>
+__global__ __launch_bounds__(256) void sample_full_kernel(const float* logits, int V, SampleCfg cfg, SampleSrc src, int* out, int ostride) {
+  extern __shared__ unsigned long long sf_lds[];
+  unsigned long long* sk = sf_lds;
+  float* shf = (float*)(sf_lds + N);  // [8]: wave totals of the two scans
+  int* shi = (int*)(shf + 8);         // [4] block minimum; [4] c[n - 1]
+  constexpr int PER = N / 256;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int i = tid; i < N; i += 256) {
+    unsigned long long e = 0ull;  // padding sorts behind every logit (the smallest key of a number is that of -inf, 0x007fffff)
+    if (i < V) {
+      float l = logits[(long long)b * V + i];
+      if (!(l == l)) l = -INFINITY;
+      if (l == 0.f) l = 0.f;  // -0 and +0 are one logit: a tie, decided by the index (their keys would differ)
+      e = ((unsigned long long)sk_key(l) << 32) | (unsigned)(0xffffffffu - (unsigned)i);
+    }
+    sk[i] = e;
+  }
+  for (int size = 2; size <= N; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      __syncthreads();
+      for (int t = tid; t < N / 2; t += 256) {
+        const int i = 2 * t - (t & (stride - 1)), j = i + stride;
+        const unsigned long long x = sk[i], y = sk[j];
+        if ((x < y) == ((i & size) == 0)) { sk[i] = y; sk[j] = x; }  // descending blocks where bit `size` of i is clear (all of them in the last merge)
+      }
+    }
+  __syncthreads();
+  const float lmax = sk_unkey((unsigned)(sk[0] >> 32));
+  const float temp = cfg.temp;
+  // weight of sorted position j at temperature 1 / temp; l == l_max counts as distance 0 (so a row of -inf, or +inf on top, stays finite)
+  auto dist = [&](int j) __attribute__((always_inline)) {
+    const float l = sk_unkey((unsigned)(sk[j] >> 32));
+    return l == lmax ? 0.f : l - lmax;
+  };
+  const int j0 = tid * PER;
+  float s1 = 0.f, sT = 0.f;
+  for (int i = 0; i < PER; ++i)
+    if (j0 + i < V) {
+      const float d = dist(j0 + i);
+      s1 += expf(d);
+      sT += expf(d / temp);
+    }
+  float i1 = s1, iT = sT;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float t1 = __shfl_up(i1, o), tT = __shfl_up(iT, o);
+    if (lane >= o) { i1 += t1; iT += tT; }
+  }
+  if (lane == 63) { shf[wave] = i1; shf[4 + wave] = iT; }
+  float off1 = __shfl_up(i1, 1), offT = __shfl_up(iT, 1);
+  if (lane == 0) { off1 = 0.f; offT = 0.f; }
+  __syncthreads();
+  float base1 = 0.f, baseT = 0.f, Z = 0.f;
+  for (int w = 0; w < 4; ++w) {
+    if (w < wave) { base1 += shf[w]; baseT += shf[4 + w]; }
+    Z += shf[w];
+  }
+  off1 = base1 + off1;
+  offT = baseT + offT;
+  const bool use_p = cfg.top_p > 0.f && cfg.top_p < 1.f, use_m = cfg.min_p > 0.f;
+  int np = V, nm = V;
+  if (use_p || use_m) {
+    const float cut = cfg.top_p * Z;
+    float run = off1;
+    for (int i = 0; i < PER; ++i) {
+      const int j = j0 + i;
+      if (j < V) {
+        const float w = expf(dist(j));
+        if (use_p && !(run < cut) && j < np) np = j;
+        if (use_m && !(w >= cfg.min_p) && j < nm) nm = j;
+        run += w;
+      }
+    }
+    if (use_p) np = sf_block_min(np, shi);
+    if (use_m) nm = sf_block_min(nm, shi);
+  }
+  if (nm < cfg.min_keep) nm = cfg.min_keep;
+  int n = (cfg.top_k > 0 && cfg.top_k < V) ? cfg.top_k : V;
+  n = np < n ? np : n;
+  n = nm < n ? nm : n;
+  n = n < 1 ? 1 : (n > V ? V : n);
+  float* ctot = (float*)(shi + 4);
+  if ((n - 1) / PER == tid) {
+    float run = offT;
+    for (int i = 0; i < PER; ++i)
+      if (j0 + i < n) run += expf(dist(j0 + i) / temp);
+    *ctot = run;
+  }
+  __syncthreads();
+  const float target = sample_uniform(src, b) * *ctot;
+  int first = n - 1;
+  {
+    float run = offT;
+    for (int i = 0; i < PER; ++i) {
+      const int j = j0 + i;
+      if (j < n) {
+        run += expf(dist(j) / temp);
+        if (run >= target && j < first) first = j;
+      }
+    }
+  }
+  first = sf_block_min(first, shi);
+  if (tid == 0) {
+    const unsigned idx = 0xffffffffu - (unsigned)(sk[first] & 0xffffffffull);
+    out[(long long)b * ostride] = idx < (unsigned)V ? (int)idx : 0;  // always a valid row of the next launch's embedding gather
+  }
+}
+
+template <int N>
+int launch_sample_full(const float* logits, int V, const SampleCfg& cfg, const SampleSrc& src, int* out, int ostride, int B, hipStream_t st) {
+  const size_t lds = (size_t)N * 8 + 64;
+  static KKDevOnce attr;
+  if (attr.first()) {
+    (void)hipFuncSetAttribute((const void*)sample_full_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr.done();
+  }
+  hipLaunchKernelGGL(sample_full_kernel<N>, dim3(B), dim3(256), lds, st, logits, V, cfg, src, out, ostride);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
+// Which kernel draws: argmax, or top_k in 1..64 with top_p / min_p off -> sample_select_kernel (the shipped default, unchanged picks);
+// everything else -> sample_full_kernel.
+int launch_sample(const float* logits, int V, const SampleCfg& cfg, const SampleSrc& src, int* out, int ostride, int B, hipStream_t st) {
+  if (V > 256 * 32) return kk_fail("kk_csm: audio vocabulary larger than 8192 entries");
+  const bool greedy = (src.u == nullptr && src.seed == nullptr) || cfg.temp == 0.f;
+  const bool filters = (cfg.top_p > 0.f && cfg.top_p < 1.f) || cfg.min_p > 0.f;
+  if (!greedy && (filters || cfg.top_k <= 0 || cfg.top_k > 64)) {
+    if (V <= 1024) return launch_sample_full<1024>(logits, V, cfg, src, out, ostride, B, st);
+    if (V <= 2048) return launch_sample_full<2048>(logits, V, cfg, src, out, ostride, B, st);
+    if (V <= 4096) return launch_sample_full<4096>(logits, V, cfg, src, out, ostride, B, st);
+    return launch_sample_full<8192>(logits, V, cfg, src, out, ostride, B, st);
+  }
+  const float temp = cfg.temp;
+  const int top_k = cfg.top_k;
+  if (V <= 256 * 4) hipLaunchKernelGGL(sample_select_kernel<4>, dim3(B), dim3(256), 0, st, logits, V, temp, top_k, src, out, ostride);
+  else if (V <= 256 * 9) hipLaunchKernelGGL(sample_select_kernel<9>, dim3(B), dim3(256), 0, st, logits, V, temp, top_k, src, out, ostride);
+  else hipLaunchKernelGGL(sample_select_kernel<32>, dim3(B), dim3(256), 0, st, logits, V, temp, top_k, src, out, ostride);
   KK_CHECK_LAUNCH();
   return 0;
 }
@@ -1790,8 +1984,17 @@ int stack_step(Run& r, Stack& st, float* h, int rows, int offset, const FGArgs* 
   return 0;
 }
 
-int run_frame(Run& r, int S, const int* tokens, const float* mask, float temp, int top_k, const float* uniforms, int* codes) {
+// `seed`: the device seed of the Philox uniforms, or null (injected uniforms / argmax)
+int run_frame(Run& r, int S, const int* tokens, const float* mask, const SampleCfg& sc, const float* uniforms, const unsigned long long* seed,
+              const int* stream_ids, int* codes) {
   kk_csm* m = r.m;
+  // the uniform of (item, code book i): uniforms[b][i], or Philox at the position of the frame being generated (slot *pos_dev + S, minus the padding)
+  auto src_of = [&](int i) {
+    SampleSrc s;
+    s.u = uniforms ? uniforms + i : nullptr; s.ustride = m->cfg.audio_num_codebooks;
+    s.seed = uniforms ? nullptr : seed; s.sid = stream_ids; s.pos = m->bb.pos_dev; s.pos_stride = 0; s.pos_add = S; s.pad = m->bb.pad_dev; s.cb = i;
+    return s;
+  };
   const kk_csm_config& c = m->cfg;
   const int B = r.B, ncb = c.audio_num_codebooks, V = c.audio_vocab_size, D = c.backbone.hidden, Dd = c.decoder.hidden;
   const size_t mark = r.used;
@@ -1840,7 +2043,7 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, float temp, i
       memset(&g, 0, sizeof g);
       g.x = last_h; g.xrs = last_rs; g.out = logits; g.ors = V;
       KK_TRY(launch_gemv(m->c0_head, 0, 0, g, B, r.st));
-      KK_TRY(launch_sample(logits, V, temp, top_k, uniforms, ncb, codes, ncb, B, r.st));
+      KK_TRY(launch_sample(logits, V, sc, src_of(0), codes, ncb, B, r.st));
     }
     int rows = 2, dpos = 0;
     for (int i = 1; i < ncb; ++i) {
@@ -1868,14 +2071,14 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, float temp, i
         memset(&g, 0, sizeof g);
         g.x = pin + (size_t)(rows - 1) * Dd; g.xrs = (long long)rows * Dd; g.nw = m->dec.norm.p; g.eps = c.decoder.rms_eps; g.out = logits; g.ors = V;
         KK_TRY(launch_gemv(m->audio_head[i - 1], 1, 0, g, B, r.st));
-        KK_TRY(launch_sample(logits, V, temp, top_k, uniforms ? uniforms + i : nullptr, ncb, codes + i, ncb, B, r.st));
+        KK_TRY(launch_sample(logits, V, sc, src_of(i), codes + i, ncb, B, r.st));
       }
       rows = 1;
     }
   } else {
   KK_TRY(r.lin(m->c0_head, last_h, last_rs, 1, logits, V, nullptr));
   if (!r.dry) {
-    KK_TRY(launch_sample(logits, V, temp, top_k, uniforms, ncb, codes, ncb, B, r.st));
+    KK_TRY(launch_sample(logits, V, sc, src_of(0), codes, ncb, B, r.st));
     // curr = [last_h, embed_audio(0, c0)]
     hipLaunchKernelGGL(copy_rows_kernel, dim3(B), dim3(256), 0, r.st, last_h, last_rs, curr, (long long)2 * D, D);
     KK_CHECK_LAUNCH();
@@ -1893,7 +2096,7 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, float temp, i
     if (!r.dry && m->dbg_logits) logits = m->dbg_logits + (size_t)i * m->max_batch * V;
     KK_TRY(r.lin(m->audio_head[i - 1], dl, (long long)rows * Dd, 1, logits, V, nullptr));
     if (!r.dry) {
-      KK_TRY(launch_sample(logits, V, temp, top_k, uniforms ? uniforms + i : nullptr, ncb, codes + i, ncb, B, r.st));
+      KK_TRY(launch_sample(logits, V, sc, src_of(i), codes + i, ncb, B, r.st));
       hipLaunchKernelGGL(embed_audio_kernel, dim3(B), dim3(256), 0, r.st, codes + i, ncb, m->audio_emb.p, i, V, D, curr, 1, 0);
       KK_CHECK_LAUNCH();
     }
@@ -1938,7 +2141,61 @@ int kk_launch_attn_cache(const float* qkv, int S, int H, int KV, int hd, int off
 // make_sampler(temp, top_k) on its own (tests): logits [B][V] fp32 -> codes [B] int32, uniforms [B] (NULL or temp == 0: argmax)
 extern "C" int kk_op_csm_sample(void* stream, int B, int V, const float* logits, float temperature, int top_k, const float* uniforms, int32_t* codes_out) {
   if (!logits || !codes_out || B < 1 || V < 1) return kk_fail("kk_op_csm_sample: bad argument");
-  return launch_sample(logits, V, temperature, top_k, uniforms, 1, codes_out, 1, B, (hipStream_t)stream);
+  SampleCfg c;
+  c.temp = temperature; c.top_k = top_k;
+  SampleSrc s;
+  s.u = uniforms; s.ustride = 1;
+  return launch_sample(logits, V, c, s, codes_out, 1, B, (hipStream_t)stream);
+}
+
+namespace {
+int sampler_cfg(const kk_csm_sampler* sp, SampleCfg* c, const char* who) {
+  if (!sp) return kk_failf("%s: null sampler", who);
+  if (!(sp->temperature >= 0.f) || !(sp->top_p >= 0.f && sp->top_p <= 1.f) || !(sp->min_p >= 0.f && sp->min_p <= 1.f) || sp->min_tokens_to_keep < 1 || sp->top_k < -1)
+    return kk_failf("%s: sampler out of range (temperature >= 0, top_p and min_p in [0, 1], min_tokens_to_keep >= 1, top_k >= -1)", who);
+  c->temp = sp->temperature; c->top_k = sp->top_k; c->top_p = sp->top_p; c->min_p = sp->min_p; c->min_keep = sp->min_tokens_to_keep;
+  return 0;
+}
+}  // namespace
+
+// the whole sampler on its own (tests): uniforms [B] have priority; without them and with use_device_rng, Philox on (seed, stream id, pos[b], code
+// book 0) -- `seed` is passed by value here and staged in a device word for the launch; pos [B] device int32 or NULL (0)
+extern "C" int kk_op_csm_sample_ex(void* stream, int B, int V, const float* logits, const kk_csm_sampler* sampler, const float* uniforms,
+                                   const int32_t* stream_ids, const int32_t* pos, int32_t* codes_out) {
+  if (!logits || !codes_out || B < 1 || V < 1) return kk_fail("kk_op_csm_sample_ex: bad argument");
+  SampleCfg c;
+  KK_TRY(sampler_cfg(sampler, &c, "kk_op_csm_sample_ex"));
+  SampleSrc s;
+  s.u = uniforms; s.ustride = 1;
+  unsigned long long* seed_dev = nullptr;
+  if (!uniforms && sampler->use_device_rng) {
+    if (hipMalloc((void**)&seed_dev, 8) != hipSuccess) return kk_fail("kk_op_csm_sample_ex: hipMalloc failed");
+    const unsigned long long sd = sampler->seed;
+    if (hipMemcpy(seed_dev, &sd, 8, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(seed_dev); return kk_fail("kk_op_csm_sample_ex: seed upload failed"); }
+    s.seed = seed_dev; s.sid = stream_ids; s.pos = pos; s.pos_stride = 1;
+  }
+  const int rc = launch_sample(logits, V, c, s, codes_out, 1, B, (hipStream_t)stream);
+  if (seed_dev) {
+    (void)hipStreamSynchronize((hipStream_t)stream);
+    (void)hipFree(seed_dev);
+  }
+  return rc;
+}
+
+// the uniforms the sampling kernels draw (sample_uniform): out [B][n_cb] for (seed, stream_ids[b] or b, pos[b] or 0, code book)
+extern "C" int kk_op_csm_uniforms(void* stream, int B, int n_cb, uint64_t seed, const int32_t* stream_ids, const int32_t* pos, float* out) {
+  if (!out || B < 1 || n_cb < 1) return kk_fail("kk_op_csm_uniforms: bad argument");
+  unsigned long long* seed_dev = nullptr;
+  if (hipMalloc((void**)&seed_dev, 8) != hipSuccess) return kk_fail("kk_op_csm_uniforms: hipMalloc failed");
+  const unsigned long long sd = seed;
+  if (hipMemcpy(seed_dev, &sd, 8, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(seed_dev); return kk_fail("kk_op_csm_uniforms: seed upload failed"); }
+  SampleSrc s;
+  s.seed = seed_dev; s.sid = stream_ids; s.pos = pos; s.pos_stride = 1;
+  hipLaunchKernelGGL(sample_uniforms_kernel, dim3((B * n_cb + 255) / 256), dim3(256), 0, (hipStream_t)stream, s, B, n_cb, out);
+  const bool ok = hipGetLastError() == hipSuccess;
+  (void)hipStreamSynchronize((hipStream_t)stream);
+  (void)hipFree(seed_dev);
+  return ok ? 0 : kk_fail("kk_op_csm_uniforms: launch failed");
 }
 
 // ---- the kernels of the frame step on their own (tests): each entry point runs the launcher the frame runs, on caller-owned buffers
@@ -2107,6 +2364,8 @@ extern "C" int kk_csm_share(const kk_csm* m, kk_csm** out) {
   }
   c->max_batch = 0;
   c->dbg_logits = nullptr;
+  c->seed_dev = nullptr;
+  c->seed_valid = false;
   c->reset_pending = c->pad_pending = false;
   c->pad_host.clear();
   *out = c;
@@ -2126,6 +2385,7 @@ extern "C" void kk_csm_destroy(kk_csm* m) {
   if (m->dbg_logits) (void)hipFree(m->dbg_logits);
   if (m->bb.pos_dev) (void)hipFree(m->bb.pos_dev);
   if (m->bb.pad_dev) (void)hipFree(m->bb.pad_dev);
+  if (m->seed_dev) (void)hipFree(m->seed_dev);
   m->graphs.clear();
   delete m;
 }
@@ -2280,6 +2540,7 @@ extern "C" int kk_csm_setup_caches(kk_csm* m, int max_batch) {
     return kk_fail("kk_csm_setup_caches: hipMalloc failed");
   if (!m->bb.pos_dev && hipMalloc((void**)&m->bb.pos_dev, 4) != hipSuccess) return kk_fail("kk_csm_setup_caches: hipMalloc failed");
   if (hipMemset(m->bb.pos_dev, 0, 4) != hipSuccess) return kk_fail("kk_csm_setup_caches: memset failed");
+  if (!m->seed_dev && hipMalloc((void**)&m->seed_dev, 8) != hipSuccess) return kk_fail("kk_csm_setup_caches: hipMalloc failed");
   if (m->bb.pad_dev) (void)hipFree(m->bb.pad_dev);
   m->bb.pad_dev = nullptr;
   if (hipMalloc((void**)&m->bb.pad_dev, (size_t)max_batch * 4) != hipSuccess || hipMemset(m->bb.pad_dev, 0, (size_t)max_batch * 4) != hipSuccess)
@@ -2314,12 +2575,20 @@ extern "C" int kk_csm_position(const kk_csm* m) { return m ? m->bb.offset : -1; 
 extern "C" size_t kk_csm_workspace_bytes(kk_csm* m, int B, int S) {
   if (!m || !m->finalized || B <= 0 || S <= 0) return 0;
   Run r(m, nullptr, B, nullptr, 0);
-  if (run_frame(r, S, nullptr, nullptr, 0.f, 1, nullptr, nullptr) != 0) return 0;
+  if (run_frame(r, S, nullptr, nullptr, SampleCfg(), nullptr, nullptr, nullptr, nullptr) != 0) return 0;
   return r.used + 256;
 }
 
 extern "C" int kk_csm_generate_frame(kk_csm* m, void* stream, int B, int S, const int32_t* tokens, const float* tokens_mask, float temperature,
                                      int top_k, const float* uniforms, void* workspace, size_t workspace_bytes, int32_t* codes_out) {
+  kk_csm_sampler sp;
+  memset(&sp, 0, sizeof sp);
+  sp.temperature = temperature; sp.top_k = top_k; sp.min_tokens_to_keep = 1;
+  return kk_csm_generate_frame_ex(m, stream, B, S, tokens, tokens_mask, &sp, uniforms, nullptr, workspace, workspace_bytes, codes_out);
+}
+
+extern "C" int kk_csm_generate_frame_ex(kk_csm* m, void* stream, int B, int S, const int32_t* tokens, const float* tokens_mask, const kk_csm_sampler* sampler,
+                                        const float* uniforms, const int32_t* stream_ids, void* workspace, size_t workspace_bytes, int32_t* codes_out) {
   if (!m || !m->finalized) return kk_fail("kk_csm_generate_frame: model not finalized");
   if (m->max_batch < 1) return kk_fail("kk_csm_generate_frame: call kk_csm_setup_caches first");
   if (B <= 0 || B > m->max_batch || S <= 0 || !tokens || !tokens_mask || !workspace || !codes_out) return kk_fail("kk_csm_generate_frame: bad argument");
@@ -2337,20 +2606,33 @@ extern "C" int kk_csm_generate_frame(kk_csm* m, void* stream, int B, int S, cons
       return kk_fail("kk_csm_generate_frame: padding upload failed");
     m->pad_pending = false;
   }
+  SampleCfg sc;
+  KK_TRY(sampler_cfg(sampler, &sc, "kk_csm_generate_frame"));
+  const bool dev_rng = !uniforms && sampler->use_device_rng && sc.temp > 0.f;
+  if (dev_rng && (!m->seed_valid || m->seed_host != sampler->seed)) {  // the seed lives in device memory: a new one does not re-capture the graph
+    m->seed_host = sampler->seed;
+    if (hipMemcpyAsync(m->seed_dev, &m->seed_host, 8, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess)
+      return kk_fail("kk_csm_generate_frame: seed upload failed");
+    m->seed_valid = true;
+  }
   auto eager = [&](void* on_stream) -> int {
     Run r(m, (hipStream_t)on_stream, B, workspace, workspace_bytes);
-    return run_frame(r, S, tokens, tokens_mask, temperature, top_k, uniforms, codes_out);
+    return run_frame(r, S, tokens, tokens_mask, sc, uniforms, dev_rng ? m->seed_dev : nullptr, dev_rng ? stream_ids : nullptr, codes_out);
   };
   int rc;
   if (!m->graph_mode || S != 1) {
     rc = eager(stream);
   } else {
     // the single-token step (~1400 launches) as one hipGraphLaunch: every position-dependent kernel reads the device counter
-    unsigned tbits;
-    memcpy(&tbits, &temperature, 4);
+    unsigned tbits, pbits, mbits;
+    memcpy(&tbits, &sc.temp, 4);
+    memcpy(&pbits, &sc.top_p, 4);
+    memcpy(&mbits, &sc.min_p, 4);
     const std::vector<unsigned long long> key = {(unsigned long long)B, (unsigned long long)(uintptr_t)tokens, (unsigned long long)(uintptr_t)tokens_mask,
-        (unsigned long long)tbits, (unsigned long long)top_k, (unsigned long long)(uintptr_t)uniforms, (unsigned long long)(uintptr_t)workspace,
-        (unsigned long long)workspace_bytes, (unsigned long long)(uintptr_t)codes_out, (unsigned long long)(uintptr_t)g_ts};
+        (unsigned long long)tbits, (unsigned long long)(long long)sc.top_k, (unsigned long long)(uintptr_t)uniforms, (unsigned long long)(uintptr_t)workspace,
+        (unsigned long long)workspace_bytes, (unsigned long long)(uintptr_t)codes_out, (unsigned long long)(uintptr_t)g_ts,
+        (unsigned long long)pbits, (unsigned long long)mbits, (unsigned long long)sc.min_keep, (unsigned long long)dev_rng,
+        (unsigned long long)(uintptr_t)(dev_rng ? stream_ids : nullptr)};
     hipGraphExec_t ex = nullptr;
     rc = m->graphs.run(key, (hipStream_t)stream, [&](hipStream_t on_stream, bool) { return eager((void*)on_stream); }, &ex, "kk_csm");
     if (rc != 0) return rc;

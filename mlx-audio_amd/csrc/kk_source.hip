@@ -15,6 +15,7 @@
 #include "kk_common.h"
 #include "kk_kernels.h"
 #include "kk_istft_math.h"
+#include "kk_philox.h"
 
 namespace {
 
@@ -68,27 +69,7 @@ __global__ __launch_bounds__(64) void source_phase_kernel(KKSourceArgs a) {
   }
 }
 
-// ------------------------------------------------------------------ Philox4x32-10 + Box-Muller
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-  const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-  const uint32_t n1 = (uint32_t)p1;
-  const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-  const uint32_t n3 = (uint32_t)p0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-__device__ __forceinline__ void philox4(uint64_t seed, uint64_t ctr, uint32_t sub, uint32_t (&out)[4]) {
-  uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), sub, 0x4B4B5352u};
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; out[3] = c[3];
-}
+// ------------------------------------------------------------------ Box-Muller on Philox4x32-10 (kk_philox.h)
 __device__ __forceinline__ void box_muller(uint32_t u0, uint32_t u1, float& z0, float& z1) {
   const float a = ((float)(u0 >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0,1)
   const float bq = ((float)(u1 >> 8) + 0.5f) * (1.0f / 16777216.0f);

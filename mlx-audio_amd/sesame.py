@@ -34,13 +34,40 @@ TextLike = Union[str, Sequence[int]]
 
 @dataclass(frozen=True)
 class Sampler:
-    """What the frame loop needs of mlx_lm's `make_sampler(temp, top_k)` (sesame.py:14-17,719): the two numbers.  temp 0 = argmax."""
+    """What the frame loop needs of mlx_lm's `make_sampler` (sesame.py:14-17,719): its numbers; the engine applies them on the device (the
+    rule: kk_csm_sampler in include/kokoro_hip.h; mlx_lm is not in the reference tree, parity with it is unpinned).  temp 0 = argmax;
+    top_k 0 or -1, top_p 0 or 1, min_p 0: that filter is off."""
     temp: float = 0.9
     top_k: int = 50
+    top_p: float = 0.0
+    min_p: float = 0.0
+    min_tokens_to_keep: int = 1
 
 
-def make_sampler(temp: float = 0.9, top_k: int = 50, **_unused) -> Sampler:
-    return Sampler(float(temp), int(top_k))
+def make_sampler(temp: float = 0.9, top_p: float = 0.0, min_p: float = 0.0, min_tokens_to_keep: int = 1, top_k: int = 50,
+                 xtc_probability: float = 0.0, **_unused) -> Sampler:
+    """mlx_lm's argument names and defaults, except this module's own temp 0.9 / top_k 50 (sesame.py:719).  XTC is not built: asking for
+    it raises instead of sampling without it; other unknown keyword arguments are ignored."""
+    temp, top_p, min_p, min_tokens_to_keep, top_k = float(temp), float(top_p), float(min_p), int(min_tokens_to_keep), int(top_k)
+    if xtc_probability and float(xtc_probability) > 0.0:
+        raise ValueError("make_sampler: xtc_probability > 0 (XTC sampling) is not implemented")
+    if not temp >= 0.0:
+        raise ValueError(f"make_sampler: temp must be >= 0, not {temp}")
+    if not 0.0 <= top_p <= 1.0:
+        raise ValueError(f"make_sampler: top_p must be in [0, 1], not {top_p}")
+    if not 0.0 <= min_p <= 1.0:
+        raise ValueError(f"make_sampler: min_p must be in [0, 1], not {min_p}")
+    if min_tokens_to_keep < 1:
+        raise ValueError(f"make_sampler: min_tokens_to_keep must be >= 1, not {min_tokens_to_keep}")
+    if top_k < -1:
+        raise ValueError(f"make_sampler: top_k must be >= 0 (0 or -1: no top-k filter), not {top_k}")
+    return Sampler(temp, top_k, top_p, min_p, min_tokens_to_keep)
+
+
+def _check_rng(rng: str) -> str:
+    if rng not in ("host", "device"):
+        raise ValueError(f"rng must be 'host' or 'device', not {rng!r}")
+    return rng
 
 
 @dataclass
@@ -258,10 +285,13 @@ class Model:
         return np.concatenate(ft, 0), np.concatenate(fm, 0)
 
     # ---- the frame loop over B streams ------------------------------------------------------------------------------------------------------
-    def _frame_loop(self, prompts, max_audio_frames: int, temperature: float, top_k: int, seed: Optional[int], stop_on_eos: bool,
-                    uniforms: Optional[Callable[[int], np.ndarray]] = None):
+    def _frame_loop(self, prompts, max_audio_frames: int, sampler: Sampler, seed: Optional[int], stop_on_eos: bool,
+                    uniforms: Optional[Callable[[int], np.ndarray]] = None, rng: str = "host", stream_ids=None):
         """Generator over frames: yields (codes [B, n_cb] int32 on the device, done [B] bool: streams whose EOS frame has been seen BEFORE this
-        frame).  Ragged prompts are left-padded; the loop ends when every stream has produced its EOS frame (an all-zero frame, sesame.py:765)."""
+        frame).  Ragged prompts are left-padded; the loop ends when every stream has produced its EOS frame (an all-zero frame, sesame.py:765).
+        rng "host": one [B, n_cb] block of numpy uniforms per frame (or `uniforms(i)`), uploaded in front of the frame.  rng "device": the
+        sampling kernels draw from Philox on (seed, stream id, the stream's own position, code book) -- no host work per frame, and a
+        stream's draws do not depend on the batch it runs in."""
         B = len(prompts)
         lens = [p[0].shape[0] for p in prompts]
         S = max(lens)
@@ -282,16 +312,26 @@ class Model:
             self.model.set_padding([S - l for l in lens])
         self.model.set_graph_mode(True)  # the frame steps after the prompt block are replayed as one hipGraph
         # make_sampler(temp, top_k) draws from MLX's global RNG; here the uniforms are explicit: seeded, or fresh entropy when seed is None
-        rng = np.random.default_rng(seed) if (temperature > 0 and uniforms is None) else None
+        temperature = float(sampler.temp)
+        device_rng = _check_rng(rng) == "device" and uniforms is None and temperature > 0
+        if device_rng and seed is None:
+            seed = int(np.random.SeedSequence().generate_state(2, np.uint32).view(np.uint64)[0])  # fresh entropy, as the host generator takes
+        rng = np.random.default_rng(seed) if (temperature > 0 and uniforms is None and not device_rng) else None
+        # a sampler of (temp, top_k) alone on host uniforms is the call frame generators have always received
+        plain = not device_rng and not (0.0 < sampler.top_p < 1.0) and not sampler.min_p > 0.0
         curr, cmask = torch.tensor(tok, device=dev), torch.tensor(msk, device=dev)
         step_mask = torch.zeros((B, 1, n + 1), dtype=torch.float32, device=dev)
         step_mask[:, 0, :n] = 1
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         for i in range(max_audio_frames):
             u = None
-            if temperature > 0:
+            if temperature > 0 and not device_rng:
                 u = torch.tensor(np.asarray(uniforms(i) if uniforms is not None else rng.uniform(size=(B, n)), np.float32), device=dev)
-            sample = self.model.generate_frame(curr, cmask, temperature=temperature, top_k=top_k, uniforms=u)
+            if plain:
+                sample = self.model.generate_frame(curr, cmask, temperature=temperature, top_k=int(sampler.top_k), uniforms=u)
+            else:
+                sample = self.model.generate_frame(curr, cmask, sampler=sampler, uniforms=u, seed=seed if device_rng else None,
+                                                   stream_ids=stream_ids if device_rng else None)
             was_done = done
             if stop_on_eos:
                 done = done | (sample == 0).all(dim=1)  # an all-zero frame is EOS (sesame.py:765-766)
@@ -302,16 +342,22 @@ class Model:
 
     def generate_batch(self, prompts, max_audio_length_ms: float = 90_000, temperature: float = 0.9, top_k: int = 50, seed: Optional[int] = 0,
                        stop_on_eos: bool = True, eos_check_interval: int = 8, decode: bool = True,
-                       uniforms: Optional[Callable[[int], np.ndarray]] = None) -> BatchResult:
+                       uniforms: Optional[Callable[[int], np.ndarray]] = None, sampler: Optional[Sampler] = None, rng: str = "host",
+                       stream_ids: Optional[Sequence[int]] = None) -> BatchResult:
         """prompts: one (tokens, mask) pair per stream (`prompt_frames`), lengths may differ.  `uniforms(i)` (optional) supplies frame i's
-        [B, n_cb] sampling uniforms instead of the seeded generator.  Frames are generated for all streams until every
+        [B, n_cb] sampling uniforms instead of the seeded generator.  `sampler` (make_sampler) replaces `temperature` / `top_k` and adds
+        top-p / min-p.  rng "device": draws come from the device generator keyed by (seed, stream_ids[b], position, code book), so stream b's
+        codes are those of a batch-1 run with the same seed and stream id, whatever else is in the batch (stream_ids default: 0..B-1).  Frames are generated for all streams until every
         stream has emitted its EOS frame; the host looks at the EOS flags only every `eos_check_interval` frames (one sync per interval instead
         of one per frame), so a few frames past the last EOS may be generated and are dropped.  Stream b's audio holds exactly its own frames."""
         start = time.perf_counter()
         B = len(prompts)
         max_audio_frames = int(max_audio_length_ms / 80)
         frames, first_eos = [], torch.full((B,), -1, dtype=torch.int64, device=self.model.device)
-        for i, (sample, was_done, done) in enumerate(self._frame_loop(prompts, max_audio_frames, temperature, top_k, seed, stop_on_eos, uniforms)):
+        sampler = sampler if sampler is not None else make_sampler(temp=temperature, top_k=top_k)
+        if stream_ids is not None and len(stream_ids) != B:
+            raise ValueError(f"stream_ids must hold one id per prompt ({B})")
+        for i, (sample, was_done, done) in enumerate(self._frame_loop(prompts, max_audio_frames, sampler, seed, stop_on_eos, uniforms, rng, stream_ids)):
             frames.append(sample)
             newly = done & ~was_done
             first_eos = torch.where(newly, torch.full_like(first_eos, i), first_eos)
@@ -372,13 +418,15 @@ class Model:
     def generate(self, text: Union[TextLike, List[TextLike]], voice: Optional[str] = None, speaker: int = 0, context: Optional[List[Segment]] = None,
                  split_pattern: Optional[str] = r"\n+", sampler: Callable = None, max_audio_length_ms: float = 90_000, ref_audio=None,
                  ref_text: Optional[TextLike] = None, stream: bool = False, streaming_interval: float = 0.5, voice_match: bool = True,
-                 seed: Optional[int] = None, stop_on_eos: bool = True, **kwargs):
+                 seed: Optional[int] = None, stop_on_eos: bool = True, rng: str = "host", **kwargs):
         """Yields one GenerationResult per text prompt (per `streaming_interval` seconds of frames with stream=True).  `sampler` is what
         `make_sampler(temp, top_k)` of this module returns (the reference takes mlx_lm's callable of the same name, sesame.py:719) and
-        defaults, as there, to temp 0.9 / top_k 50.  A bare `temperature=` -- generate_audio forwards its own default 0.7 to every model
-        (generate.py:288-300) -- lands in **kwargs and is IGNORED, exactly as the reference's signature ignores it."""
+        defaults, as there, to temp 0.9 / top_k 50; its top_p / min_p / min_tokens_to_keep are honoured.  rng "host" (default) draws numpy
+        uniforms per frame, "device" draws in the sampling kernels from `seed` (no per-frame upload).  A bare `temperature=` / `top_p=` /
+        `top_k=` -- generate_audio forwards its own defaults to every model (generate.py:288-300) -- lands in **kwargs and is IGNORED,
+        exactly as the reference's signature ignores it."""
         sampler = sampler or make_sampler(temp=0.9, top_k=50)
-        temperature, top_k = float(sampler.temp), int(sampler.top_k)
+        _check_rng(rng)
         context = list(context or [])
         if not context and ref_audio is not None and ref_text is not None:
             a = ref_audio.detach().cpu().numpy() if isinstance(ref_audio, torch.Tensor) else np.asarray(ref_audio, np.float32)
@@ -400,8 +448,8 @@ class Model:
                 self._streaming_decoder.reset()
             samples = []
             self._seed_counter += 1
-            for sample, was_done, done in self._frame_loop([frames], max_audio_frames, temperature, top_k,
-                                                           seed if seed is None else seed + self._seed_counter - 1, stop_on_eos):
+            for sample, was_done, done in self._frame_loop([frames], max_audio_frames, sampler,
+                                                           seed if seed is None else seed + self._seed_counter - 1, stop_on_eos, rng=rng):
                 if bool(done[0]):
                     break  # eos (batch 1: one sync per frame, as in the reference)
                 samples.append(sample)
@@ -422,8 +470,9 @@ class Model:
         prompts = [self.prompt_frames(c, p, 0, voice_match=False) for c, p in zip(contexts, prompts_ids)]
         dec = _D(self._audio_tokenizer)
         samples, start = [], time.perf_counter()
-        for sample, was_done, done in self._frame_loop(prompts, max_audio_frames, kw.get("temperature", 0.9), kw.get("top_k", 50), kw.get("seed", 0),
-                                                       kw.get("stop_on_eos", True)):
+        sampler = kw.get("sampler") or make_sampler(temp=kw.get("temperature", 0.9), top_k=kw.get("top_k", 50))
+        for sample, was_done, done in self._frame_loop(prompts, max_audio_frames, sampler, kw.get("seed", 0), kw.get("stop_on_eos", True),
+                                                       rng=kw.get("rng", "host"), stream_ids=kw.get("stream_ids")):
             if kw.get("stop_on_eos", True) and bool(done.all()):
                 break
             samples.append(sample)

@@ -1,5 +1,6 @@
 """CSM-1B frame generation rate (config 4): B streams, one prompt block then N single-token frames; audio-seconds (80 ms per frame)
 per wall-second.  python tools/bench_csm.py [--batch 8] [--prompt 64] [--frames 10] [--weights float32|bfloat16|q8|q4] [--group-size 64]
+--top-k / --top-p / --min-p: the sampler (defaults: top-50 alone, the shipped configuration); --rng device: Philox uniforms inside the sampling kernels.
 --weights q8 / q4: the synthetic checkpoint MLX-affine-quantised (quant.quantize_checkpoint) and kept packed in device memory."""
 import argparse
 import json
@@ -23,6 +24,10 @@ ap.add_argument("--e2e", action="store_true", help="config 4 end to end: referen
 ap.add_argument("--weights", default="float32", choices=["float32", "bfloat16", "q8", "q4"],
                 help="weight storage of the Linear layers (kk_csm_set_weight_dtype; q8 / q4: a quantised checkpoint, packed storage)")
 ap.add_argument("--group-size", type=int, default=64, help="quantisation group of --weights q8 / q4")
+ap.add_argument("--top-k", type=int, default=50, help="0: no top-k filter (the whole vocabulary)")
+ap.add_argument("--top-p", type=float, default=0.0)
+ap.add_argument("--min-p", type=float, default=0.0)
+ap.add_argument("--rng", default="host", choices=["host", "device"], help="host: injected uniforms (resident on the device); device: Philox in the sampling kernels")
 a = ap.parse_args()
 cfg = P.csm_config()
 t0 = time.time()
@@ -67,9 +72,20 @@ tok = np.zeros((B, a.prompt, n + 1), np.int64)
 msk = np.zeros((B, a.prompt, n + 1), np.float32)
 tok[:, :, -1] = rng.integers(0, cfg["text_vocab_size"], (B, a.prompt))
 msk[:, :, -1] = 1
+from mlx_audio_amd.sesame import make_sampler  # noqa: E402
+
+sampler = make_sampler(temp=0.9, top_k=a.top_k, top_p=a.top_p, min_p=a.min_p)
+
+
+def frame(t, m, u):
+    if a.rng == "device":
+        return model.generate_frame(t, m, sampler=sampler, seed=0)
+    return model.generate_frame(t, m, sampler=sampler, uniforms=u)
+
+
 torch.cuda.synchronize()
 tp = time.perf_counter()
-codes = model.generate_frame(torch.tensor(tok), torch.tensor(msk), temperature=0.9, top_k=50, uniforms=torch.tensor(rng.uniform(size=(B, n)).astype(np.float32)))
+codes = frame(torch.tensor(tok), torch.tensor(msk), torch.tensor(rng.uniform(size=(B, n)).astype(np.float32)))
 torch.cuda.synchronize()
 prefill_ms = (time.perf_counter() - tp) * 1e3
 # the same prompt again on reset caches: without the first call's one-time costs (kernel loading, workspace allocation)
@@ -77,7 +93,7 @@ model.reset_caches()
 ptok, pmsk, pu = torch.tensor(tok).cuda(), torch.tensor(msk).cuda(), torch.tensor(rng.uniform(size=(B, n)).astype(np.float32)).cuda()
 torch.cuda.synchronize()
 tp = time.perf_counter()
-codes = model.generate_frame(ptok, pmsk, temperature=0.9, top_k=50, uniforms=pu)
+codes = frame(ptok, pmsk, pu)
 torch.cuda.synchronize()
 prefill2_ms = (time.perf_counter() - tp) * 1e3
 step_tok = torch.zeros((B, 1, n + 1), dtype=torch.int32, device="cuda")
@@ -87,15 +103,16 @@ us = torch.tensor(rng.uniform(size=(a.frames + 3, B, n)).astype(np.float32), dev
 model.set_graph_mode(True)
 for i in range(3):  # warm-up frames (eager, capture, first replay)
     step_tok[:, 0, :n] = codes
-    codes = model.generate_frame(step_tok, step_msk, temperature=0.9, top_k=50, uniforms=us[i])
+    codes = frame(step_tok, step_msk, us[i])
 torch.cuda.synchronize()
 ts = time.perf_counter()
 for i in range(a.frames):
     step_tok[:, 0, :n] = codes
-    codes = model.generate_frame(step_tok, step_msk, temperature=0.9, top_k=50, uniforms=us[3 + i])
+    codes = frame(step_tok, step_msk, us[3 + i])
 torch.cuda.synchronize()
 dt = (time.perf_counter() - ts) / a.frames
 print(json.dumps({"metric": "audio-sec/sec (xRT), CSM-1B frame generation (80 ms of audio per frame and stream), " + wname, "value": B * 0.08 / dt,
                   "ms_per_frame": dt * 1e3, "batch": B, "prompt_tokens": a.prompt, "prefill_ms": prefill_ms, "prefill_ms_second_call": prefill2_ms, "frames_timed": a.frames, "dtype": wname, **storage,
-                  "data": "synthetic (random-init CSM-1B weights, random prompt, injected uniforms)",
+                  "sampler": {"temp": 0.9, "top_k": a.top_k, "top_p": a.top_p, "min_p": a.min_p, "rng": a.rng},
+                  "data": "synthetic (random-init CSM-1B weights, random prompt, " + ("injected uniforms)" if a.rng == "host" else "device uniforms)"),
                   "setup_s": {"synth_checkpoint": round(t1 - t0, 1), "load_finalize": round(t2 - t1, 1)}}))
