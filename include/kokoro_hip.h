@@ -30,8 +30,9 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 2   /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
-                            2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms) */
+#define KK_ABI_MINOR 3   /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+                            2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
+                            3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -379,6 +380,29 @@ typedef struct kk_csm_sampler {
  * when it changes, so a new seed replays the same graph; every other sampler field and the stream_ids pointer key the graph. */
 int kk_csm_generate_frame_ex(kk_csm* m, void* stream, int B, int S, const int32_t* tokens, const float* tokens_mask, const kk_csm_sampler* sampler,
                              const float* uniforms, const int32_t* stream_ids, void* workspace, size_t workspace_bytes, int32_t* codes_out);
+/* Continuous batching: streams enter and leave a RUNNING batch (after kk_csm_setup_caches(max_batch); none of these changes what the entries
+ * above do).  All rows share the slot counter P (kk_csm_position); row b's tokens live in slots [pad[b], P) at position slot - pad[b].
+ *   kk_csm_park_row: the row is retired -- pad[row] = max_seq_len.  From the next frame on its attention sees no key (zero output) and appends
+ *     nothing; it still rides through the frame step, its codes are unspecified but in [0, V), and nothing it does reaches another row.
+ *   kk_csm_reset_caches_parked: kk_csm_reset_caches (P = 0) with EVERY row parked, the start of a serving session.  The classic reset leaves
+ *     every row live (pad 0), as before.
+ *   kk_csm_admit: the prompt frame of ONE new stream (tokens / tokens_mask [S][n_cb+1] on the device) into the parked row `row` while other rows
+ *     are live.  Needs S <= P.  Sets pad[row] = P - S, runs the prompt block on that row alone at slots [P - S, P) -- the kernels and B = 1 shapes
+ *     of kk_csm_generate_frame_ex(B = 1, S) on an empty cache, so codes_out [n_cb] carries that call's bits --, and does NOT advance P: from the
+ *     next frame on the row is an ordinary row of the single-token step.  uniforms [n_cb] or NULL; the device RNG draws at (stream_id, position S).
+ *     Never captured into a graph; the captured frame step of the other rows stays valid.
+ *   kk_csm_shift_caches: moves the window [pad[b], P) of every live row by `delta` slots (either sign, overlap allowed) in every layer's K and V and
+ *     adds delta to P and to every live pad[b].  Keys are stored rotated by the stream's OWN position, which does not change, so the move is exact.
+ *     Down by min(pad[live]) when P reaches max_seq_len; up by S - P before admitting a prompt longer than P.  Fails, changing nothing, if P or a
+ *     live window would leave [0, max_seq_len).  workspace is unused (may be NULL).
+ *   kk_csm_row_state: pad_out [max_batch] (HOST; max_seq_len = parked) and P, as the next frame will see them.
+ * Every refusal (live row, row out of range, S > P, a window leaving the cache, no caches) is decided on the host before any launch. */
+int kk_csm_admit(kk_csm* m, void* stream, int row, int S, const int32_t* tokens, const float* tokens_mask, const kk_csm_sampler* sampler,
+                 const float* uniforms, int32_t stream_id, void* workspace, size_t workspace_bytes, int32_t* codes_out);
+int kk_csm_park_row(kk_csm* m, int row);
+int kk_csm_reset_caches_parked(kk_csm* m);
+int kk_csm_shift_caches(kk_csm* m, void* stream, int delta, void* workspace, size_t workspace_bytes);
+int kk_csm_row_state(const kk_csm* m, int32_t* pad_out, int32_t* position);
 /* graph replay of the single-token frame step: the third call with identical pointers / B / sampler settings and every later one is ONE
  * hipGraphLaunch (the backbone position is a device counter, so the captured step is position-independent); results are unchanged */
 int kk_csm_set_graph_mode(kk_csm* m, int on);

@@ -109,6 +109,11 @@ SIGNATURES = {
     "kk_csm_workspace_bytes": (_sz, [_vp, _i, _i]),
     "kk_csm_generate_frame": (_i, [_vp, _vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _sz, _vp]),
     "kk_csm_generate_frame_ex": (_i, [_vp, _vp, _i, _i, _vp, _vp, C.POINTER(KKCsmSampler), _vp, _vp, _vp, _sz, _vp]),
+    "kk_csm_admit": (_i, [_vp, _vp, _i, _i, _vp, _vp, C.POINTER(KKCsmSampler), _vp, C.c_int32, _vp, _sz, _vp]),
+    "kk_csm_park_row": (_i, [_vp, _i]),
+    "kk_csm_reset_caches_parked": (_i, [_vp]),
+    "kk_csm_shift_caches": (_i, [_vp, _vp, _i, _vp, _sz]),
+    "kk_csm_row_state": (_i, [_vp, _vp, C.POINTER(C.c_int32)]),
     "kk_csm_set_graph_mode": (_i, [_vp, _i]),
     "kk_csm_debug_logits": (_i, [_vp, _vp, _i, _vp]),
     "kk_csm_debug_timestamps": (_i, [_vp, _i]),
@@ -194,7 +199,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 2:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 3:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

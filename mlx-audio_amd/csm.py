@@ -59,6 +59,7 @@ class SesameModel:
         self._graph = False
         self._gbuf = {}
         self._sid = {}
+        self._ws_admit = None
         if weights is not None:
             self.load_weights(weights)
 
@@ -74,6 +75,7 @@ class SesameModel:
         check(self.lib.kk_csm_share(self._h, C.byref(h)), "kk_csm_share")
         other._h, other._parent = h, self
         other._ws, other._enabled, other.max_batch, other._graph, other._gbuf, other._sid = None, False, 0, False, {}, {}
+        other._ws_admit = None
         return other
 
     def __del__(self):
@@ -230,6 +232,80 @@ class SesameModel:
                                                     C.c_void_p(sid.data_ptr()) if sid is not None else None,
                                                     C.c_void_p(self._ws.data_ptr()), need, C.c_void_p(codes.data_ptr())), "kk_csm_generate_frame")
         self._last_B = B
+        return codes
+
+    # ---- continuous batching (kk_csm_admit / park_row / shift_caches / row_state)
+    def reset_caches_parked(self) -> None:
+        """reset_caches with every row parked: the start of a serving session (streams enter through `admit`)."""
+        check(self.lib.kk_csm_reset_caches_parked(self._h), "kk_csm_reset_caches_parked")
+
+    def park(self, row: int) -> None:
+        """Retire cache row `row`: from the next frame on it sees no key and appends nothing; `admit` may reuse it."""
+        if not 0 <= int(row) < self.max_batch:
+            raise ValueError(f"park: row {row} out of range [0, {self.max_batch})")
+        check(self.lib.kk_csm_park_row(self._h, int(row)), "kk_csm_park_row")
+
+    def row_state(self):
+        """(pad [max_batch] as a list -- max_seq_len marks a parked row --, P): what the next frame will see."""
+        assert self.caches_are_enabled(), "backbone caches are not enabled"
+        pad, pos = (C.c_int32 * self.max_batch)(), C.c_int32(0)
+        check(self.lib.kk_csm_row_state(self._h, pad, C.byref(pos)), "kk_csm_row_state")
+        return list(pad), int(pos.value)
+
+    def shift(self, delta: int) -> None:
+        """Move every live row's window, and the shared position, by `delta` cache slots (exact: keys carry their stream's own position).
+        ValueError if the position or a live window would leave the cache."""
+        pad, P = self.row_state()
+        mp = int(self.cfg["max_seq_len"])
+        delta = int(delta)
+        if not 0 <= P + delta <= mp or any(p < mp and p + delta < 0 for p in pad):
+            raise ValueError(f"shift by {delta}: a live window would leave the cache [0, {mp}) (position {P}, pad {pad})")
+        with torch.cuda.device(self.device):
+            check(self.lib.kk_csm_shift_caches(self._h, self._stream(), delta, None, 0), "kk_csm_shift_caches")
+
+    def admit(self, row: int, tokens, tokens_mask, temperature: float = 0.0, top_k: int = 50, uniforms=None, sampler=None, seed: Optional[int] = None,
+              stream_id: int = 0) -> torch.Tensor:
+        """The prompt frame of ONE new stream (tokens / tokens_mask [S, n_cb+1]) into the parked cache row `row` of a running batch; the
+        other rows keep their state and the shared position does not move.  Sampling as in generate_frame (`uniforms` [n_cb]; or `seed`
+        with `stream_id`: the device generator at the stream's own position S).  Returns codes [n_cb] int32 -- the bits of
+        generate_frame on the prompt alone.  ValueError for a live row, a row out of range, or a prompt longer than the position
+        (`shift(S - P)` first)."""
+        assert self.caches_are_enabled(), "backbone caches are not enabled"
+        tokens = torch.as_tensor(tokens).to(device=self.device, dtype=torch.int32).contiguous()
+        mask = torch.as_tensor(tokens_mask).to(device=self.device, dtype=torch.float32).contiguous()
+        ncb = self.cfg["audio_num_codebooks"]
+        if tokens.dim() != 2 or tokens.shape[1] != ncb + 1 or mask.shape != tokens.shape:
+            raise ValueError(f"tokens / tokens_mask must be [S, {ncb + 1}]")
+        S = int(tokens.shape[0])
+        if not 0 <= int(row) < self.max_batch:
+            raise ValueError(f"admit: row {row} out of range [0, {self.max_batch})")
+        pad, P = self.row_state()
+        if pad[int(row)] < int(self.cfg["max_seq_len"]):
+            raise ValueError(f"admit: row {row} is live (park it first)")
+        if S < 1 or S > P:
+            raise ValueError(f"admit: a prompt of {S} frames does not fit below position {P} (shift by {S - P} first)")
+        u = None
+        if uniforms is not None:
+            u = torch.as_tensor(uniforms).to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+            if u.numel() != ncb:
+                raise ValueError(f"uniforms must hold {ncb} entries")
+        sp = _lib.KKCsmSampler(float(temperature), int(top_k), 0.0, 0.0, 1, 0, 0)
+        if sampler is not None:
+            sp = _lib.KKCsmSampler(float(sampler.temp), int(sampler.top_k), float(getattr(sampler, "top_p", 0.0)), float(getattr(sampler, "min_p", 0.0)),
+                                   int(getattr(sampler, "min_tokens_to_keep", 1)), 0, 0)
+        if u is None and seed is not None:
+            sp.seed, sp.use_device_rng = int(seed) & 0xFFFFFFFFFFFFFFFF, 1
+        with torch.cuda.device(self.device):
+            need = int(self.lib.kk_csm_workspace_bytes(self._h, 1, S))
+            if need == 0:
+                raise KokoroHipError("kk_csm_workspace_bytes failed")
+            # a workspace of its own: the captured frame step of the running batch is keyed on ITS workspace pointer
+            if self._ws_admit is None or self._ws_admit.numel() < need:
+                self._ws_admit = torch.empty(need, dtype=torch.uint8, device=self.device)
+            codes = torch.empty(ncb, dtype=torch.int32, device=self.device)
+            check(self.lib.kk_csm_admit(self._h, self._stream(), int(row), S, C.c_void_p(tokens.data_ptr()), C.c_void_p(mask.data_ptr()), C.byref(sp),
+                                        C.c_void_p(u.data_ptr()) if u is not None else None, int(stream_id) & 0x7FFFFFFF,
+                                        C.c_void_p(self._ws_admit.data_ptr()), need, C.c_void_p(codes.data_ptr())), "kk_csm_admit")
         return codes
 
     def debug_logits(self) -> torch.Tensor:

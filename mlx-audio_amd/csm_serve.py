@@ -1,0 +1,405 @@
+"""Continuous batching for CSM: independent requests enter and leave ONE running batch on one copy of the weights.
+
+`generate_batch` is static: B prompts start together and all B rows are stepped until the last stream ends.  `CSMBatcher` keeps a batch of
+`max_batch` cache rows running instead.  A finished stream's row is PARKED (kk_csm_park_row: it sees no key and appends nothing) and handed
+to the next queued request, whose prompt is written right-aligned below the shared cache position (kk_csm_admit) while the other rows keep
+their state; when the position reaches the end of the cache every live window is moved down (kk_csm_shift_caches), and up when a prompt is
+longer than the position.  A stream's codes and waveform are, bit for bit, those of `Model.generate_batch([prompt], seed=...)` alone:
+  * rng "host": one `np.random.default_rng(seed)` per stream, one [n_cb] draw per frame, stacked per frame over the rows;
+  * rng "device": the sampling kernels draw from Philox on (the batcher's seed, the stream's id, the stream's own position, code book).
+
+One scheduling round (`step`): poll the EOS flags (one sync every `eos_check_interval` frames, as generate_batch does), park finished rows
+and decode them (streams of equal length in one Mimi.decode call), admit queued requests FIFO into parked rows, shift if needed, then one
+frame for all rows through the captured single-token graph.  An admission stalls the other rows for one prompt block and one B = 1 frame.
+
+Not here: chunked audio while a stream runs (the streaming Mimi decoder carries one position for all rows)."""
+from __future__ import annotations
+
+import threading
+import time
+from collections import deque
+from concurrent.futures import Future
+from dataclasses import dataclass, field
+from typing import Deque, Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+
+@dataclass
+class StreamResult:
+    """One request's result: what `BatchResult` holds for one stream."""
+    audio: Optional[torch.Tensor]  # [samples], None with decode=False
+    frames: int                    # frames generated (up to, not including, the EOS frame)
+    codes: torch.Tensor            # [n_cb, frames]
+    sample_rate: int
+    stream_id: int
+    row: int                       # the cache row the stream ran in
+    processing_time_seconds: float  # submit -> result
+
+
+@dataclass
+class _Stream:
+    future: Future
+    context: Sequence
+    text: object
+    speaker: int
+    voice_match: bool
+    max_frames: int
+    seed: Optional[int]
+    stream_id: int
+    length: int                     # prompt frames
+    t0: float
+    prompt: Optional[tuple] = None  # (tokens [S, n_cb+1], mask)
+    row: int = -1
+    rng: Optional[np.random.Generator] = None
+    codes: List[torch.Tensor] = field(default_factory=list)  # one [n_cb] tensor per generated frame
+
+
+class ModelEngine:
+    """What the batcher needs of a `sesame.Model` (frame generator + codec).  The scheduler talks to this surface only, so it can be
+    driven against a scripted engine without a device."""
+
+    def __init__(self, model):
+        self.model = model
+        self.csm = model.model
+        self.n_cb = int(model.n_cb)
+        self.max_pos = int(self.csm.cfg["max_seq_len"])
+        self.sample_rate = int(model.sample_rate)
+        self.device = self.csm.device
+
+    def start(self, max_batch: int) -> None:
+        if not self.csm.caches_are_enabled() or self.csm.max_batch != max_batch:
+            self.csm.setup_caches(max_batch)
+        self.csm.reset_caches_parked()
+        self.csm.set_graph_mode(True)
+
+    def prompt_length(self, context, text, speaker: int, voice_match: bool) -> int:
+        """Frames of `Model.prompt_frames(...)` from lengths alone (no device work: submit() runs on the caller's thread)."""
+        m = self.model
+        mimi = m._audio_tokenizer
+
+        def audio_frames(a):
+            return int(mimi.lib.kk_mimi_encode_frames(mimi._h, int(np.asarray(a).shape[-1])))
+
+        if voice_match:
+            if not context:
+                raise ValueError("voice_match needs a context segment")
+            c0 = context[0]
+            if text is None:
+                n = len(m._text_ids(c0.text, speaker))
+            elif not isinstance(c0.text, str) or not isinstance(text, str):
+                n = len(m._text_ids(c0.text, speaker)) + len(m._text_ids(text, speaker))
+            else:
+                n = len(m._text_ids((c0.text + " " + text).strip(), speaker))
+            return n + (audio_frames(c0.audio) if c0.audio is not None else 0)
+        n = 0
+        for seg in context:
+            n += len(m._text_ids(seg.text, seg.speaker)) + (audio_frames(seg.audio) + 1 if seg.audio is not None else 0)
+        return n + (len(m._text_ids(text, speaker)) if text is not None else 0)
+
+    def prompts(self, streams: Sequence[_Stream]):
+        """The prompts of the requests admitted in one round; streams that agree on (speaker, voice_match) share Mimi.encode calls."""
+        out: Dict[int, tuple] = {}
+        groups: Dict[tuple, List[int]] = {}
+        for i, s in enumerate(streams):
+            groups.setdefault((s.speaker, s.voice_match), []).append(i)
+        for (speaker, vm), idx in groups.items():
+            got = self.model.prompt_frames_batch([streams[i].context for i in idx], [streams[i].text for i in idx], speaker, vm)
+            for i, p in zip(idx, got):
+                out[i] = p
+        return [out[i] for i in range(len(streams))]
+
+    def row_state(self):
+        return self.csm.row_state()
+
+    def park(self, row: int) -> None:
+        self.csm.park(row)
+
+    def shift(self, delta: int) -> None:
+        self.csm.shift(delta)
+
+    def admit(self, row: int, prompt, sampler, uniforms, seed, stream_id: int) -> torch.Tensor:
+        return self.csm.admit(row, prompt[0], prompt[1], sampler=sampler, uniforms=uniforms, seed=seed, stream_id=stream_id)
+
+    def frame(self, prev: torch.Tensor, sampler, uniforms, seed, stream_ids) -> torch.Tensor:
+        B, n = prev.shape
+        curr = torch.zeros((B, 1, n + 1), dtype=torch.int32, device=self.device)
+        curr[:, 0, :n] = prev
+        mask = torch.zeros((B, 1, n + 1), dtype=torch.float32, device=self.device)
+        mask[:, 0, :n] = 1
+        u = torch.tensor(np.asarray(uniforms, np.float32), device=self.device) if uniforms is not None else None
+        return self.csm.generate_frame(curr, mask, sampler=sampler, uniforms=u, seed=seed, stream_ids=stream_ids)
+
+    def decode(self, codes: torch.Tensor) -> torch.Tensor:
+        if self.model._audio_tokenizer is None:
+            raise ValueError("decoding needs the Mimi codec: pass mimi= or config['mimi_path']")
+        return self.model._audio_tokenizer.decode(codes)[:, 0]
+
+    def synchronize(self) -> None:
+        torch.cuda.current_stream(self.device).synchronize()
+
+
+class CSMBatcher:
+    def __init__(self, model, max_batch: int = 8, eos_check_interval: int = 8, rng: str = "device", sampler=None, seed: int = 0,
+                 stop_on_eos: bool = True, decode: bool = True, profile: bool = False, engine=None):
+        """model: a loaded sesame.Model (its frame generator's caches are taken over; use `model.share()` for a generator of its own).
+        sampler: `make_sampler(...)` for every stream of the batch (default temp 0.9 / top_k 50).  seed: the device generator's seed (rng
+        "device": one seed per batcher, streams differ by their ids).  profile: time admissions and shifts (one sync each) into `stats`.
+        engine: the surface of `ModelEngine`, for a scheduler without a device."""
+        if rng not in ("host", "device"):
+            raise ValueError(f"rng must be 'host' or 'device', not {rng!r}")
+        if max_batch < 1 or eos_check_interval < 1:
+            raise ValueError("max_batch and eos_check_interval must be >= 1")
+        if sampler is None:
+            from .sesame import make_sampler
+
+            sampler = make_sampler(temp=0.9, top_k=50)
+        self.engine = engine if engine is not None else ModelEngine(model)
+        self.max_batch, self.interval, self.rng, self.sampler, self.seed = int(max_batch), int(eos_check_interval), rng, sampler, int(seed)
+        self.stop_on_eos, self.decode, self.profile = bool(stop_on_eos), bool(decode), bool(profile)
+        self._sampled = float(sampler.temp) > 0
+        self._lock = threading.Lock()          # queue, closed flag, stream id counter
+        self._wake = threading.Condition(self._lock)
+        self._queue: Deque[_Stream] = deque()
+        self._closed = False
+        self._thread: Optional[threading.Thread] = None
+        self._next_id = 0
+        self._rows: List[Optional[_Stream]] = [None] * self.max_batch
+        self._since_poll = 0
+        self.stats = {"frames": 0, "live_row_frames": 0, "admissions": 0, "admit_seconds": 0.0, "shifts": 0, "shift_seconds": 0.0,
+                      "shifts_down": 0, "shifts_up": 0, "polls": 0, "finished": 0}
+        self.engine.start(self.max_batch)
+        dev = self.engine.device
+        self._prev = torch.zeros((self.max_batch, self.engine.n_cb), dtype=torch.int32, device=dev)
+        self._first_eos = torch.full((self.max_batch,), -1, dtype=torch.int64, device=dev)  # stream-local index of the first all-zero frame
+        self._local = torch.zeros((self.max_batch,), dtype=torch.int64, device=dev)        # stream-local index of the next frame
+
+    # ---- requests ---------------------------------------------------------------------------------------------------------------------
+    def submit(self, context, text, speaker: int = 0, voice_match: bool = True, max_audio_length_ms: float = 90_000, seed: Optional[int] = None,
+               stream_id: Optional[int] = None, prompt=None) -> Future:
+        """Queue one request; the future yields a `StreamResult`.  `prompt` (tokens, mask) skips the prompt building.  rng "host": `seed`
+        seeds this stream's generator (None: fresh entropy).  rng "device": the batcher's seed is used, `seed` must be None or equal to it.
+        ValueError at once for a request that cannot fit the cache; a request that races `close()` gets a failed future."""
+        max_frames = int(max_audio_length_ms / 80)
+        if prompt is not None:
+            prompt = (np.asarray(prompt[0], np.int32), np.asarray(prompt[1], np.float32))
+            length = int(prompt[0].shape[0])
+        else:
+            length = int(self.engine.prompt_length(context, text, speaker, voice_match))
+        limit = self.engine.max_pos - max_frames
+        if length >= limit:
+            raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {limit}")  # sesame.py:755-758
+        if max_frames < 1 or length < 1:
+            raise ValueError("a request needs a prompt and at least one frame")
+        if self.rng == "device" and seed is not None and int(seed) != self.seed:
+            raise ValueError(f"rng 'device': every stream draws from the batcher's seed {self.seed}; streams differ by stream_id")
+        if stream_id is not None and not 0 <= int(stream_id) < 2 ** 31:
+            raise ValueError("stream_id must be in [0, 2^31)")
+        fut: Future = Future()
+        with self._lock:
+            if self._closed:
+                fut.set_exception(RuntimeError("CSMBatcher is closed"))
+                return fut
+            if stream_id is None:
+                stream_id = self._next_id
+            self._next_id = max(self._next_id, int(stream_id)) + 1
+            self._queue.append(_Stream(future=fut, context=context, text=text, speaker=int(speaker), voice_match=bool(voice_match),
+                                       max_frames=max_frames, seed=seed, stream_id=int(stream_id), length=length, t0=time.perf_counter(),
+                                       prompt=prompt))
+            self._wake.notify()
+        return fut
+
+    # ---- one scheduling round -----------------------------------------------------------------------------------------------------------
+    def _live(self) -> List[_Stream]:
+        return [s for s in self._rows if s is not None]
+
+    def _poll(self) -> None:
+        """One sync: which streams have ended (EOS frame seen, or their own frame limit), park their rows, decode, resolve."""
+        self.stats["polls"] += 1
+        self._since_poll = 0
+        fe = self._first_eos.cpu().tolist() if self.stop_on_eos else [-1] * self.max_batch
+        done: Dict[int, List[_Stream]] = {}
+        for s in self._live():
+            eos = fe[s.row]
+            if eos < 0 and len(s.codes) < s.max_frames:
+                continue
+            count = min(eos if eos >= 0 else len(s.codes), s.max_frames)  # frames past the EOS frame / the limit are dropped
+            self.engine.park(s.row)
+            self._rows[s.row] = None
+            done.setdefault(count, []).append(s)
+        for count, group in done.items():
+            self.stats["finished"] += len(group)
+            if count == 0:
+                for s in group:
+                    s.future.set_exception(AssertionError("No audio generated"))
+                continue
+            try:
+                codes = torch.stack([torch.stack(s.codes[:count], dim=1) for s in group])  # [b, n_cb, T]
+                pcm = self.engine.decode(codes) if self.decode else None
+                if pcm is not None:
+                    self.engine.synchronize()
+                for j, s in enumerate(group):
+                    s.future.set_result(StreamResult(audio=pcm[j] if pcm is not None else None, frames=count, codes=codes[j],
+                                                     sample_rate=self.engine.sample_rate, stream_id=s.stream_id, row=s.row,
+                                                     processing_time_seconds=time.perf_counter() - s.t0))
+            except Exception as e:  # noqa: BLE001
+                for s in group:
+                    if not s.future.done():
+                        s.future.set_exception(e)
+
+    def _timed(self, what: str, fn) -> None:
+        if self.profile:
+            self.engine.synchronize()
+            t = time.perf_counter()
+            fn()
+            self.engine.synchronize()
+            self.stats[what + "_seconds"] += time.perf_counter() - t
+        else:
+            fn()
+
+    def _shift(self, delta: int) -> None:
+        self._timed("shift", lambda: self.engine.shift(delta))
+        self.stats["shifts"] += 1
+        self.stats["shifts_down" if delta < 0 else "shifts_up"] += 1
+
+    def _admit(self) -> None:
+        free = [r for r in range(self.max_batch) if self._rows[r] is None]
+        with self._lock:
+            new = [self._queue.popleft() for _ in range(min(len(free), len(self._queue)))]
+        if not new:
+            return
+        need = [s for s in new if s.prompt is None]
+        try:
+            for s, p in zip(need, self.engine.prompts(need)):
+                s.prompt = p
+        except Exception as e:  # noqa: BLE001
+            for s in need:
+                s.future.set_exception(e)
+            new = [s for s in new if s.prompt is not None]
+        for s, row in zip(new, free):
+            S = int(s.prompt[0].shape[0])
+            try:
+                if S != s.length:
+                    raise ValueError(f"the prompt has {S} frames, {s.length} were announced")
+                _, P = self.engine.row_state()
+                if not self._live() and P != S:
+                    self._shift(S - P)       # nothing live: only the position moves
+                elif S > P:
+                    self._shift(S - P)       # the live windows move up so that the prompt fits below the position
+                u = None
+                if self._sampled and self.rng == "host":
+                    s.rng = np.random.default_rng(s.seed)
+                    u = s.rng.uniform(size=(1, self.engine.n_cb))[0].astype(np.float32)
+                seed = self.seed if (self._sampled and self.rng == "device") else None
+                out: List[torch.Tensor] = []
+                self._timed("admit", lambda: out.append(self.engine.admit(row, s.prompt, self.sampler, u, seed, s.stream_id)))
+                codes = out[0]
+            except Exception as e:  # noqa: BLE001
+                s.future.set_exception(e)
+                continue
+            self.stats["admissions"] += 1
+            s.row = row
+            s.codes = [codes]
+            self._rows[row] = s
+            self._prev[row] = codes
+            self._first_eos[row] = torch.where((codes == 0).all(), 0, -1)
+            self._local[row] = 1
+
+    def _frame(self) -> None:
+        live = self._live()
+        pad, P = self.engine.row_state()
+        if P >= self.engine.max_pos:  # the position has reached the end of the cache: every live window moves down to slot 0 of the longest
+            self._shift(-min(pad[s.row] for s in live))
+        u = None
+        if self._sampled and self.rng == "host":
+            u = np.full((self.max_batch, self.engine.n_cb), 0.5, np.float32)
+            for s in live:
+                u[s.row] = s.rng.uniform(size=(1, self.engine.n_cb))[0]
+        seed = self.seed if (self._sampled and self.rng == "device") else None
+        ids = [self._rows[r].stream_id if self._rows[r] is not None else 0 for r in range(self.max_batch)] if seed is not None else None
+        sample = self.engine.frame(self._prev, self.sampler, u, seed, ids).clone()  # (graph replay hands back a view of a persistent buffer)
+        self._prev = sample
+        if self.stop_on_eos:
+            zero = (sample == 0).all(dim=1)  # an all-zero frame is EOS (sesame.py:765-766)
+            self._first_eos = torch.where((self._first_eos < 0) & zero, self._local, self._first_eos)
+        self._local = self._local + 1
+        for s in live:
+            s.codes.append(sample[s.row])
+        self.stats["frames"] += 1
+        self.stats["live_row_frames"] += len(live)
+        self._since_poll += 1
+
+    def step(self) -> bool:
+        """One scheduling round; False when there was nothing to do (no live stream, empty queue)."""
+        while True:
+            self._admit()  # (rows a poll has just freed are refilled in the same round)
+            live = self._live()
+            if not (live and (self._since_poll >= self.interval or any(len(s.codes) >= s.max_frames for s in live))):
+                break
+            self._poll()
+        if not self._live():
+            return False
+        self._frame()
+        return True
+
+    def run_until_idle(self) -> None:
+        while self.step() or self._queue:
+            pass
+
+    @property
+    def occupancy(self) -> float:
+        """live row-frames / computed row-frames of the single-token steps so far"""
+        return self.stats["live_row_frames"] / max(1, self.stats["frames"] * self.max_batch)
+
+    # ---- background thread --------------------------------------------------------------------------------------------------------------
+    def start(self) -> "CSMBatcher":
+        with self._lock:
+            if self._closed:
+                raise RuntimeError("CSMBatcher is closed")
+            if self._thread is None:
+                self._thread = threading.Thread(target=self._worker, name="csm-batcher", daemon=True)
+                self._thread.start()
+        return self
+
+    def _worker(self) -> None:
+        while True:
+            with self._lock:
+                while not self._closed and not self._queue and not self._live():
+                    self._wake.wait()
+                if self._closed:
+                    return
+            try:
+                self.step()
+            except Exception as e:  # noqa: BLE001  (a failed round fails the streams in flight, the thread lives on)
+                for s in self._live():
+                    if not s.future.done():
+                        s.future.set_exception(e)
+                    self._rows[s.row] = None
+                    self.engine.park(s.row)
+
+    def close(self) -> None:
+        """Stop the worker.  Requests still queued or in flight are FAILED, never dropped (their callers sit in Future.result()); the
+        closed flag and the queue change under one lock, so a submit() that races close() either lands in the queue before the flag --
+        and is failed here -- or sees the flag and fails at once."""
+        with self._lock:
+            self._closed = True
+            self._wake.notify_all()
+            thread, self._thread = self._thread, None
+        if thread is not None:
+            thread.join()
+        with self._lock:
+            pending = list(self._queue)
+            self._queue.clear()
+        for s in pending + self._live():
+            if not s.future.done():
+                s.future.set_exception(RuntimeError("CSMBatcher is closed"))
+        for s in self._live():
+            self._rows[s.row] = None
+            self.engine.park(s.row)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

@@ -95,7 +95,9 @@ struct kk_csm {
   // kk_csm_reset_caches / kk_csm_set_padding take no stream: what they change on the device is applied on the NEXT frame's stream (a
   // synchronous hipMemset / hipMemcpy here would touch the legacy stream and break another thread's graph capture)
   bool reset_pending = false, pad_pending = false;
-  std::vector<int32_t> pad_host;
+  std::vector<int32_t> pad_host;  // host mirror of bb.pad_dev ([max_batch] since kk_csm_setup_caches); max_pos = a parked row (kk_csm_park_row)
+  int* admit_sid_dev = nullptr;   // kk_csm_admit: the new stream's id where the sampling kernels read it
+  int32_t admit_sid_host = 0;
   // device RNG of the sampler (kk_csm_sampler.use_device_rng): the Philox seed in device memory, read by the sampling kernels
   unsigned long long* seed_dev = nullptr;
   unsigned long long seed_host = 0;
@@ -183,6 +185,7 @@ __global__ __launch_bounds__(256) void rope_append_kernel(float* qkv, int S, int
   const int W = (H + 2 * KV) * hd, half = hd / 2;
   float* row = qkv + ((long long)b * S + s) * W;
   const int pd = pad ? pad[b] : 0;
+  if (pd >= max_pos) return;  // a parked row (kk_csm_park_row): no key of its own, nothing appended -- as the single-token attention forms treat nk <= 0
   const int rpos = offset + s - pd > 0 ? offset + s - pd : 0;
   const float* cs = rope + (long long)rpos * half * 2;
   float* kdst = kc + ((long long)b * max_pos + offset + s) * KV * hd;
@@ -639,6 +642,42 @@ static size_t attn_decode_lds_bytes(int hd, int G) {
 static size_t attn_lds_bytes(int max_pos, int hd) { return ((size_t)((max_pos + 3) & ~3) + hd + (size_t)(512 / hd) * hd + 2 * hd) * 4; }
 
 __global__ void advance_pos_kernel(int* pos, int by) { *pos += by; }
+
+// kk_csm_shift_caches: the window [pad[b], P) of every live row moves by `delta` slots, in every layer, K (blockIdx.z even) and V (odd).
+// Source and destination overlap whenever |delta| is smaller than the row's length, so the walk is ordered PER THREAD: a thread owns one
+// 16-byte column of the row (rowf4 = KV hd / 4 of them, 64 neighbours per workgroup: a slot is read and written in 1 KiB pieces) and moves it
+// slot by slot in the safe direction -- ascending for a move down, descending for a move up --, eight slots per trip, all eight loads in
+// front of the eight stores.  A store lands on a slot this thread has already read (or outside the window), and no other thread touches the
+// column, so no barrier or bounce buffer is needed.  P and pad are read from device memory; they are updated behind this kernel in stream order.
+// The host has checked that every live window stays inside [0, max_pos); the same test here turns a violation into a no-op for that row.
+__global__ __launch_bounds__(64) void shift_cache_kernel(float* kc, float* vc, int maxB, int max_pos, int rowf4, const int* pos_dev, const int* pad,
+                                                         int delta) {
+  const int c = blockIdx.x * 64 + threadIdx.x, b = blockIdx.y, layer = blockIdx.z >> 1;
+  if (c >= rowf4) return;
+  const int hi = *pos_dev, lo = pad[b];
+  if (lo >= hi || lo < 0 || lo + delta < 0 || hi + delta > max_pos) return;  // parked / empty row, or a window that would leave the cache
+  float4* base = (float4*)((blockIdx.z & 1) ? vc : kc) + ((long long)layer * maxB + b) * max_pos * rowf4 + c;
+  float4 r[8];
+  if (delta < 0) {
+    for (int s = lo; s < hi; s += 8) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        if (s + i < hi) r[i] = base[(long long)(s + i) * rowf4];
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        if (s + i < hi) base[(long long)(s + i + delta) * rowf4] = r[i];
+    }
+  } else {
+    for (int s = hi - 1; s >= lo; s -= 8) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        if (s - i >= lo) r[i] = base[(long long)(s - i) * rowf4];
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        if (s - i >= lo) base[(long long)(s - i + delta) * rowf4] = r[i];
+    }
+  }
+}
 
 // silu(gate) * up, gu [rows][2I] -> [rows][I]
 __global__ __launch_bounds__(256) void swiglu_kernel(const float* gu, int I, long long n, float* out) {
@@ -1985,14 +2024,17 @@ int stack_step(Run& r, Stack& st, float* h, int rows, int offset, const FGArgs* 
 }
 
 // `seed`: the device seed of the Philox uniforms, or null (injected uniforms / argmax)
+// `own_pos` >= 0 (kk_csm_admit): the frame is the prompt block of ONE stream in a row view of the backbone cache -- its Philox position is that
+// constant (the stream's own position, not slot - padding) and the shared slot counter is NOT advanced
 int run_frame(Run& r, int S, const int* tokens, const float* mask, const SampleCfg& sc, const float* uniforms, const unsigned long long* seed,
-              const int* stream_ids, int* codes) {
+              const int* stream_ids, int* codes, int own_pos = -1) {
   kk_csm* m = r.m;
   // the uniform of (item, code book i): uniforms[b][i], or Philox at the position of the frame being generated (slot *pos_dev + S, minus the padding)
   auto src_of = [&](int i) {
     SampleSrc s;
     s.u = uniforms ? uniforms + i : nullptr; s.ustride = m->cfg.audio_num_codebooks;
     s.seed = uniforms ? nullptr : seed; s.sid = stream_ids; s.pos = m->bb.pos_dev; s.pos_stride = 0; s.pos_add = S; s.pad = m->bb.pad_dev; s.cb = i;
+    if (own_pos >= 0) { s.pos = nullptr; s.pad = nullptr; s.pos_add = own_pos; }
     return s;
   };
   const kk_csm_config& c = m->cfg;
@@ -2036,7 +2078,8 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, const SampleC
   size_t peak = r.used;
   r.used = inner;  // the stack's scratch is free again
   // the heads write their logits straight into the slot kk_csm_debug_logits reads ([n_cb][maxB][V], first B rows): no copy per code book
-  if (!r.dry && m->dbg_logits) logits = m->dbg_logits;
+  const bool dbg = !r.dry && m->dbg_logits && own_pos < 0;  // (an admission leaves the live rows' debug logits alone)
+  if (dbg) logits = m->dbg_logits;
   if (fast && heads_fast) {
     if (!r.dry) {
       FGArgs g;
@@ -2066,7 +2109,7 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, const SampleC
       if (r.used > peak) peak = r.used;
       dpos += rows;
       if (!r.dry) {
-        if (m->dbg_logits) logits = m->dbg_logits + (size_t)i * m->max_batch * V;
+        if (dbg) logits = m->dbg_logits + (size_t)i * m->max_batch * V;
         FGArgs g;
         memset(&g, 0, sizeof g);
         g.x = pin + (size_t)(rows - 1) * Dd; g.xrs = (long long)rows * Dd; g.nw = m->dec.norm.p; g.eps = c.decoder.rms_eps; g.out = logits; g.ors = V;
@@ -2093,7 +2136,7 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, const SampleC
     if (r.used > peak) peak = r.used;
     dpos += rows;
     const float* dl = dn ? dn + (size_t)(rows - 1) * Dd : nullptr;
-    if (!r.dry && m->dbg_logits) logits = m->dbg_logits + (size_t)i * m->max_batch * V;
+    if (dbg) logits = m->dbg_logits + (size_t)i * m->max_batch * V;
     KK_TRY(r.lin(m->audio_head[i - 1], dl, (long long)rows * Dd, 1, logits, V, nullptr));
     if (!r.dry) {
       KK_TRY(launch_sample(logits, V, sc, src_of(i), codes + i, ncb, B, r.st));
@@ -2103,7 +2146,7 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, const SampleC
     rows = 1;
   }
   }
-  if (!r.dry) {
+  if (!r.dry && own_pos < 0) {
     hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(1), 0, r.st, m->bb.pos_dev, S);
     KK_CHECK_LAUNCH();
   }
@@ -2365,6 +2408,7 @@ extern "C" int kk_csm_share(const kk_csm* m, kk_csm** out) {
   c->max_batch = 0;
   c->dbg_logits = nullptr;
   c->seed_dev = nullptr;
+  c->admit_sid_dev = nullptr;
   c->seed_valid = false;
   c->reset_pending = c->pad_pending = false;
   c->pad_host.clear();
@@ -2386,6 +2430,7 @@ extern "C" void kk_csm_destroy(kk_csm* m) {
   if (m->bb.pos_dev) (void)hipFree(m->bb.pos_dev);
   if (m->bb.pad_dev) (void)hipFree(m->bb.pad_dev);
   if (m->seed_dev) (void)hipFree(m->seed_dev);
+  if (m->admit_sid_dev) (void)hipFree(m->admit_sid_dev);
   m->graphs.clear();
   delete m;
 }
@@ -2541,11 +2586,13 @@ extern "C" int kk_csm_setup_caches(kk_csm* m, int max_batch) {
   if (!m->bb.pos_dev && hipMalloc((void**)&m->bb.pos_dev, 4) != hipSuccess) return kk_fail("kk_csm_setup_caches: hipMalloc failed");
   if (hipMemset(m->bb.pos_dev, 0, 4) != hipSuccess) return kk_fail("kk_csm_setup_caches: memset failed");
   if (!m->seed_dev && hipMalloc((void**)&m->seed_dev, 8) != hipSuccess) return kk_fail("kk_csm_setup_caches: hipMalloc failed");
+  if (!m->admit_sid_dev && hipMalloc((void**)&m->admit_sid_dev, 4) != hipSuccess) return kk_fail("kk_csm_setup_caches: hipMalloc failed");
   if (m->bb.pad_dev) (void)hipFree(m->bb.pad_dev);
   m->bb.pad_dev = nullptr;
   if (hipMalloc((void**)&m->bb.pad_dev, (size_t)max_batch * 4) != hipSuccess || hipMemset(m->bb.pad_dev, 0, (size_t)max_batch * 4) != hipSuccess)
     return kk_fail("kk_csm_setup_caches: hipMalloc failed");
   m->max_batch = max_batch;
+  m->pad_host.assign((size_t)max_batch, 0);
   m->reset_pending = m->pad_pending = false;  // freshly zeroed above
   return 0;
 }
@@ -2568,6 +2615,7 @@ extern "C" int kk_csm_reset_caches(kk_csm* m) {
   m->dec.offset = 0;
   m->reset_pending = true;  // position counter and padding are cleared on the next frame's stream
   m->pad_pending = false;
+  m->pad_host.assign((size_t)m->max_batch, 0);
   return 0;
 }
 extern "C" int kk_csm_position(const kk_csm* m) { return m ? m->bb.offset : -1; }
@@ -2577,6 +2625,30 @@ extern "C" size_t kk_csm_workspace_bytes(kk_csm* m, int B, int S) {
   Run r(m, nullptr, B, nullptr, 0);
   if (run_frame(r, S, nullptr, nullptr, SampleCfg(), nullptr, nullptr, nullptr, nullptr) != 0) return 0;
   return r.used + 256;
+}
+
+// what kk_csm_reset_caches / kk_csm_set_padding / kk_csm_park_row deferred, in stream order before the next frame, admission or shift (never
+// inside a capture)
+static int flush_pending(kk_csm* m, hipStream_t st) {
+  if (m->reset_pending) {  // deferred kk_csm_reset_caches
+    if (hipMemsetAsync(m->bb.pos_dev, 0, 4, st) != hipSuccess || hipMemsetAsync(m->bb.pad_dev, 0, (size_t)m->max_batch * 4, st) != hipSuccess)
+      return kk_fail("kk_csm_generate_frame: cache reset failed");
+    m->reset_pending = false;
+  }
+  if (m->pad_pending) {  // deferred kk_csm_set_padding / kk_csm_park_row
+    if (hipMemcpyAsync(m->bb.pad_dev, m->pad_host.data(), (size_t)m->max_batch * 4, hipMemcpyHostToDevice, st) != hipSuccess)
+      return kk_fail("kk_csm_generate_frame: padding upload failed");
+    m->pad_pending = false;
+  }
+  return 0;
+}
+// the Philox seed lives in device memory: a new one does not re-capture the graph
+static int upload_seed(kk_csm* m, unsigned long long seed, hipStream_t st) {
+  if (m->seed_valid && m->seed_host == seed) return 0;
+  m->seed_host = seed;
+  if (hipMemcpyAsync(m->seed_dev, &m->seed_host, 8, hipMemcpyHostToDevice, st) != hipSuccess) return kk_fail("kk_csm_generate_frame: seed upload failed");
+  m->seed_valid = true;
+  return 0;
 }
 
 extern "C" int kk_csm_generate_frame(kk_csm* m, void* stream, int B, int S, const int32_t* tokens, const float* tokens_mask, float temperature,
@@ -2595,26 +2667,11 @@ extern "C" int kk_csm_generate_frame_ex(kk_csm* m, void* stream, int B, int S, c
   if (m->bb.offset + S > m->bb.max_pos) return kk_fail("kk_csm_generate_frame: sequence exceeds max_seq_len");
   if (S > 1 && m->bb.offset != 0) return kk_fail("kk_csm_generate_frame: a multi-token block must start an empty cache (sesame.py:41-48)");
   if (workspace_bytes < kk_csm_workspace_bytes(m, B, S)) return kk_fail("kk_csm_generate_frame: workspace too small");
-  if (m->reset_pending) {  // deferred kk_csm_reset_caches, in stream order before this frame (never inside a capture)
-    if (hipMemsetAsync(m->bb.pos_dev, 0, 4, (hipStream_t)stream) != hipSuccess ||
-        hipMemsetAsync(m->bb.pad_dev, 0, (size_t)m->max_batch * 4, (hipStream_t)stream) != hipSuccess)
-      return kk_fail("kk_csm_generate_frame: cache reset failed");
-    m->reset_pending = false;
-  }
-  if (m->pad_pending) {  // deferred kk_csm_set_padding
-    if (hipMemcpyAsync(m->bb.pad_dev, m->pad_host.data(), (size_t)m->max_batch * 4, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess)
-      return kk_fail("kk_csm_generate_frame: padding upload failed");
-    m->pad_pending = false;
-  }
+  KK_TRY(flush_pending(m, (hipStream_t)stream));
   SampleCfg sc;
   KK_TRY(sampler_cfg(sampler, &sc, "kk_csm_generate_frame"));
   const bool dev_rng = !uniforms && sampler->use_device_rng && sc.temp > 0.f;
-  if (dev_rng && (!m->seed_valid || m->seed_host != sampler->seed)) {  // the seed lives in device memory: a new one does not re-capture the graph
-    m->seed_host = sampler->seed;
-    if (hipMemcpyAsync(m->seed_dev, &m->seed_host, 8, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess)
-      return kk_fail("kk_csm_generate_frame: seed upload failed");
-    m->seed_valid = true;
-  }
+  if (dev_rng) KK_TRY(upload_seed(m, sampler->seed, (hipStream_t)stream));
   auto eager = [&](void* on_stream) -> int {
     Run r(m, (hipStream_t)on_stream, B, workspace, workspace_bytes);
     return run_frame(r, S, tokens, tokens_mask, sc, uniforms, dev_rng ? m->seed_dev : nullptr, dev_rng ? stream_ids : nullptr, codes_out);
@@ -2640,6 +2697,103 @@ extern "C" int kk_csm_generate_frame_ex(kk_csm* m, void* stream, int B, int S, c
   }
   if (rc == 0) m->bb.offset += S;
   return rc;
+}
+
+// ---- continuous batching: streams enter and leave a running batch -------------------------------------------------------------
+// All rows share the slot counter P (bb.offset / *bb.pos_dev); row b's tokens live in slots [pad[b], P) at position slot - pad[b].  A PARKED row
+// has pad[b] = max_pos: every attention form sees nk <= 0 for it (zero output, nothing appended), so it rides through the frame step's GEMVs
+// with finite values and cannot reach another row.
+
+// kk_csm_reset_caches with every row parked: P = 0, pad[b] = max_pos (the start of a serving session; the classic reset leaves all rows live)
+extern "C" int kk_csm_reset_caches_parked(kk_csm* m) {
+  if (!m || m->max_batch < 1) return kk_fail("kk_csm_reset_caches_parked: call kk_csm_setup_caches first");
+  KK_TRY(kk_csm_reset_caches(m));
+  m->pad_host.assign((size_t)m->max_batch, m->bb.max_pos);
+  m->pad_pending = true;  // uploaded behind the deferred reset
+  return 0;
+}
+
+extern "C" int kk_csm_park_row(kk_csm* m, int row) {
+  if (!m || m->max_batch < 1) return kk_fail("kk_csm_park_row: call kk_csm_setup_caches first");
+  if (row < 0 || row >= m->max_batch) return kk_fail("kk_csm_park_row: row out of range");
+  m->pad_host[row] = m->bb.max_pos;
+  m->pad_pending = true;  // uploaded on the next frame's stream
+  return 0;
+}
+
+extern "C" int kk_csm_row_state(const kk_csm* m, int32_t* pad_out, int32_t* position) {
+  if (!m || m->max_batch < 1) return kk_fail("kk_csm_row_state: call kk_csm_setup_caches first");
+  if (pad_out) memcpy(pad_out, m->pad_host.data(), (size_t)m->max_batch * 4);
+  if (position) *position = m->bb.offset;
+  return 0;
+}
+
+extern "C" int kk_csm_shift_caches(kk_csm* m, void* stream, int delta, void* workspace, size_t workspace_bytes) {
+  (void)workspace; (void)workspace_bytes;  // the walk is ordered per thread (shift_cache_kernel): no bounce buffer
+  if (!m || m->max_batch < 1) return kk_fail("kk_csm_shift_caches: call kk_csm_setup_caches first");
+  const int P = m->bb.offset, mp = m->bb.max_pos;
+  if (P + delta < 0 || P + delta > mp) return kk_fail("kk_csm_shift_caches: the position would leave the cache");
+  for (int b = 0; b < m->max_batch; ++b)
+    if (m->pad_host[b] < mp && m->pad_host[b] + delta < 0) return kk_fail("kk_csm_shift_caches: a live row's window would leave the cache");
+  if (delta == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  KK_TRY(flush_pending(m, st));
+  const kk_llama_args& a = m->bb.a;
+  const int rowf4 = a.num_kv_heads * a.head_dim / 4;
+  hipLaunchKernelGGL(shift_cache_kernel, dim3((rowf4 + 63) / 64, m->max_batch, 2 * a.num_layers), dim3(64), 0, st, m->bb.kc, m->bb.vc, m->max_batch, mp, rowf4,
+                     m->bb.pos_dev, m->bb.pad_dev, delta);
+  KK_CHECK_LAUNCH();
+  hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(1), 0, st, m->bb.pos_dev, delta);
+  KK_CHECK_LAUNCH();
+  for (int b = 0; b < m->max_batch; ++b)
+    if (m->pad_host[b] < mp) m->pad_host[b] += delta;
+  m->bb.offset = P + delta;
+  if (hipMemcpyAsync(m->bb.pad_dev, m->pad_host.data(), (size_t)m->max_batch * 4, hipMemcpyHostToDevice, st) != hipSuccess)
+    return kk_fail("kk_csm_shift_caches: padding upload failed");
+  return 0;
+}
+
+namespace {
+// The backbone as kk_csm_admit sees it: ONE row of the caches (layer pitch unchanged: max_batch rows), that row's padding entry, and the
+// slot offset as a launch constant instead of the device counter.  Restored on every way out.
+struct RowView {
+  Stack& s;
+  float *kc, *vc;
+  int *pos, *pad;
+  int off;
+  RowView(Stack& st, int row, int slot0) : s(st), kc(st.kc), vc(st.vc), pos(st.pos_dev), pad(st.pad_dev), off(st.offset) {
+    const size_t rs = (size_t)st.max_pos * st.a.num_kv_heads * st.a.head_dim;
+    s.kc = kc + row * rs; s.vc = vc + row * rs; s.pos_dev = nullptr; s.pad_dev = pad + row; s.offset = slot0;
+  }
+  ~RowView() { s.kc = kc; s.vc = vc; s.pos_dev = pos; s.pad_dev = pad; s.offset = off; }
+};
+}  // namespace
+
+extern "C" int kk_csm_admit(kk_csm* m, void* stream, int row, int S, const int32_t* tokens, const float* tokens_mask, const kk_csm_sampler* sampler,
+                            const float* uniforms, int32_t stream_id, void* workspace, size_t workspace_bytes, int32_t* codes_out) {
+  if (!m || !m->finalized) return kk_fail("kk_csm_admit: model not finalized");
+  if (m->max_batch < 1) return kk_fail("kk_csm_admit: call kk_csm_setup_caches first");
+  if (row < 0 || row >= m->max_batch) return kk_fail("kk_csm_admit: row out of range");
+  if (S <= 0 || !tokens || !tokens_mask || !sampler || !workspace || !codes_out) return kk_fail("kk_csm_admit: bad argument");
+  const int P = m->bb.offset, mp = m->bb.max_pos;
+  if (m->pad_host[row] < mp) return kk_fail("kk_csm_admit: the row is live (kk_csm_park_row first)");
+  if (S > P) return kk_fail("kk_csm_admit: the prompt is longer than the cache position (kk_csm_shift_caches by S - P first)");
+  if (workspace_bytes < kk_csm_workspace_bytes(m, 1, S)) return kk_fail("kk_csm_admit: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  SampleCfg sc;
+  KK_TRY(sampler_cfg(sampler, &sc, "kk_csm_admit"));
+  const bool dev_rng = !uniforms && sampler->use_device_rng && sc.temp > 0.f;
+  m->pad_host[row] = P - S;
+  m->pad_pending = true;
+  KK_TRY(flush_pending(m, st));
+  if (dev_rng) {
+    KK_TRY(upload_seed(m, sampler->seed, st));
+    m->admit_sid_host = stream_id;
+    if (hipMemcpyAsync(m->admit_sid_dev, &m->admit_sid_host, 4, hipMemcpyHostToDevice, st) != hipSuccess) return kk_fail("kk_csm_admit: stream id upload failed");
+  }
+  RowView view(m->bb, row, P - S);
+  Run r(m, st, 1, workspace, workspace_bytes);
+  return run_frame(r, S, tokens, tokens_mask, sc, uniforms, dev_rng ? m->seed_dev : nullptr, dev_rng ? m->admit_sid_dev : nullptr, codes_out, S);
 }
 
 extern "C" int kk_csm_debug_timestamps(unsigned long long* buf, int capacity) {

@@ -382,6 +382,13 @@ class Model:
         return BatchResult(audio=audio, frames=counts, sample_rate=self.sample_rate, processing_time_seconds=dt,
                            real_time_factor=dt / secs if secs > 0 else 0.0, codes=codes)
 
+    def serve(self, **kw):
+        """Continuous batching (csm_serve.CSMBatcher): requests enter and leave one running batch on this model's weights; every stream's
+        result equals its own `generate_batch([prompt])` run.  Keyword arguments are CSMBatcher's."""
+        from .csm_serve import CSMBatcher
+
+        return CSMBatcher(self, **kw)
+
     # ---- results (sesame.py:619-680) ------------------------------------------------------------------------------------------------------------
     def _result(self, audio: torch.Tensor, token_count: int, start_time: float) -> GenerationResult:
         torch.cuda.synchronize()

@@ -1,0 +1,118 @@
+"""CSM-1B serving throughput on a mixed-length workload: static batches (`generate_batch`, groups of --batch in arrival order, every group runs
+until its longest stream is done) against continuous batching (`csm_serve.CSMBatcher`: a finished stream's row goes to the next request).
+python tools/bench_csm_serve.py [--mode both|static|continuous] [--requests 32] [--batch 8] [--weights bfloat16] [--max-seq-len 512] [--seed 0]
+Synthetic weights as tools/bench_csm.py uses; stream lengths are IMPOSED (EOS ignored) and, like the prompt lengths, drawn with --seed from
+fixed lists; all requests are queued at time 0; no codec (audio = 80 ms per frame).  Prints one JSON line and writes it to
+profiles/csm_serve_bench.json: audio-seconds per wall-second of both modes, their ratio and the ratio the lengths alone allow (frame steps
+of the static plan / of a FIFO row schedule, computed on the host), the row occupancy (live row-frames / computed row-frames), and the mean
+cost of an admission and of a cache shift (a second, profiled continuous run: one sync around each).  --max-seq-len is small by default so
+that the session passes the end of the cache and down-shifts happen."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import mlx_audio_amd.params as P  # noqa: E402
+from mlx_audio_amd.sesame import Model, make_sampler  # noqa: E402
+
+PROMPTS = [32, 48, 64, 96]
+LENGTHS = [25, 30, 40, 50, 60, 90, 125, 250]
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--mode", default="both", choices=["both", "static", "continuous"])
+ap.add_argument("--requests", type=int, default=32)
+ap.add_argument("--batch", type=int, default=8)
+ap.add_argument("--weights", default="bfloat16", choices=["float32", "bfloat16"])
+ap.add_argument("--max-seq-len", type=int, default=512)
+ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "csm_serve_bench.json"))
+a = ap.parse_args()
+
+cfg = dict(P.csm_config(), max_seq_len=a.max_seq_len)
+loop = Model(cfg, weights=P.csm_synth_checkpoint(cfg, 0), weight_dtype=a.weights)
+n, B = cfg["audio_num_codebooks"], a.batch
+rng = np.random.default_rng(a.seed)
+plen = rng.choice(PROMPTS, a.requests).tolist()
+flen = rng.choice(LENGTHS, a.requests).tolist()
+prompts = []
+for L in plen:
+    tok, msk = np.zeros((L, n + 1), np.int32), np.zeros((L, n + 1), np.float32)
+    tok[:, -1], msk[:, -1] = rng.integers(0, cfg["text_vocab_size"], L), 1
+    prompts.append((tok, msk))
+sampler = make_sampler(temp=0.9, top_k=50)
+audio_s = 0.08 * sum(flen)
+groups = [list(range(i, min(i + B, a.requests))) for i in range(0, a.requests, B)]
+
+
+def fifo_steps():
+    """frame steps of a FIFO row schedule on the lengths alone (a stream of f frames holds its row for f - 1 single-token steps)"""
+    rows, queue, steps, live_rf = [0] * B, [f - 1 for f in flen], 0, 0
+    while queue or any(rows):
+        for r in range(B):
+            if rows[r] == 0 and queue:
+                rows[r] = queue.pop(0)
+        live = sum(1 for r in rows if r > 0)
+        if live == 0:
+            break
+        steps, live_rf, rows = steps + 1, live_rf + live, [max(0, r - 1) for r in rows]
+    return steps, live_rf
+
+
+def run_static():
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    for g in groups:
+        loop.generate_batch([prompts[i] for i in g], max_audio_length_ms=80 * max(flen[i] for i in g), sampler=sampler, seed=a.seed, stop_on_eos=False,
+                            decode=False, rng="device")
+    torch.cuda.synchronize()
+    return time.perf_counter() - t
+
+
+def run_continuous(profile):
+    bat = loop.serve(max_batch=B, rng="device", sampler=sampler, seed=a.seed, stop_on_eos=False, decode=False, profile=profile)
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    futs = [bat.submit(None, None, prompt=prompts[i], max_audio_length_ms=80 * flen[i]) for i in range(a.requests)]
+    bat.run_until_idle()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t
+    assert [f.result(timeout=0).frames for f in futs] == flen
+    return dt, bat
+
+
+static_steps = sum(max(flen[i] for i in g) - 1 for g in groups)
+static_rf = sum(sum(flen[i] - 1 for i in g) for g in groups)
+cont_steps, cont_rf = fifo_steps()
+out = {"metric": "audio-sec/sec (xRT), CSM-1B serving, mixed-length workload, " + a.weights, "requests": a.requests, "batch": B,
+       "max_seq_len": a.max_seq_len, "prompt_frames": plen, "stream_frames": flen, "audio_s": audio_s,
+       "ideal": {"static_steps": static_steps, "continuous_steps": cont_steps, "ratio": static_steps / cont_steps,
+                 "static_occupancy": static_rf / (static_steps * B), "continuous_occupancy": cont_rf / (cont_steps * B)},
+       "data": "synthetic (random-init CSM-1B weights, random text prompts, imposed stream lengths, device uniforms, no codec)"}
+if a.mode in ("both", "static"):
+    run_static()  # warm-up: kernel loading, workspaces, graph capture
+    dt = run_static()
+    out["static"] = {"wall_s": dt, "xrt": audio_s / dt, "occupancy": static_rf / (static_steps * B)}
+if a.mode in ("both", "continuous"):
+    run_continuous(False)  # warm-up
+    dt, bat = run_continuous(False)
+    st = bat.stats
+    out["continuous"] = {"wall_s": dt, "xrt": audio_s / dt, "occupancy": bat.occupancy, "frame_steps": st["frames"], "admissions": st["admissions"],
+                         "shifts_down": st["shifts_down"], "shifts_up": st["shifts_up"]}
+    _, prof = run_continuous(True)
+    ps = prof.stats
+    out["continuous"].update(admit_ms_mean=1e3 * ps["admit_seconds"] / max(1, ps["admissions"]), shift_ms_mean=1e3 * ps["shift_seconds"] / max(1, ps["shifts"]),
+                             shifts_profiled=ps["shifts"])
+if "static" in out and "continuous" in out:
+    out["value"] = out["continuous"]["xrt"] / out["static"]["xrt"]
+    out["value_is"] = "continuous / static audio-sec/sec"
+print(json.dumps(out))
+os.makedirs(os.path.dirname(a.out), exist_ok=True)
+with open(a.out, "w") as f:
+    json.dump(out, f, indent=1)
+    f.write("\n")
