@@ -30,9 +30,10 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 3   /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 4   /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
-                            3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked) */
+                            3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
+                            4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -403,6 +404,34 @@ int kk_csm_park_row(kk_csm* m, int row);
 int kk_csm_reset_caches_parked(kk_csm* m);
 int kk_csm_shift_caches(kk_csm* m, void* stream, int delta, void* workspace, size_t workspace_bytes);
 int kk_csm_row_state(const kk_csm* m, int32_t* pad_out, int32_t* position);
+/* A shared voice prefix: the backbone K / V of `n` prompt positions that many streams start with (a speaker's reference segment), computed once
+ * and copied under every stream admitted on top of it.  A key is stored rotated by its stream's OWN position, so the K / V of positions 0 .. n-1
+ * depend on neither the cache row, nor the slot, nor what follows them.
+ *   kk_csm_prefix_create: runs the backbone prompt block of ONE stream (tokens / tokens_mask [S][n_cb+1] on the device) at positions 0 .. S-1
+ *     into a buffer of its own, [layer][K|V][S][kv_heads * head_dim] fp32 -- no depth decoder, no sampler.  It touches no cache row, neither P nor
+ *     pad, is never captured and leaves captured frame steps valid: legal while a batch runs (pass a workspace that no captured step uses, of
+ *     kk_csm_workspace_bytes(m, 1, S) bytes).  The object is immutable and records the weight set it was computed with; generators made by
+ *     kk_csm_share from the same weights may all use it.  It needs no caches.
+ *   kk_csm_prefix_length / kk_csm_prefix_bytes: n / the buffer's bytes (-1 / 0 for a null or destroyed prefix).
+ *   kk_csm_prefix_read: the buffer, device to device (tests: a prefix does not change under the streams that use it).
+ *   kk_csm_admit_prefixed: kk_csm_admit for a stream whose prompt is the prefix followed by the S >= 1 frames of `tokens`.  Needs n + S <= P and a
+ *     parked row.  Sets pad[row] = P - n - S, copies the prefix into the row's slots [P - n - S, P - S) (one launch for all layers' K and V), runs
+ *     the suffix block at slots [P - S, P) -- positions n .. n+S-1 --, then the depth decoder and the sampler as kk_csm_admit does; the device RNG
+ *     draws at (stream_id, position n + S).  P does not move.  Both entries run their blocks through the PROMPT kernels whatever the row count
+ *     (a block of one or two rows is not sent to the single-token kernels), so codes_out and the row's K / V carry, bit for bit, what
+ *     kk_csm_generate_frame_ex(B = 1, n + S) computes on the whole prompt from an empty cache.
+ * Refusals (live row, row out of range, n + S > P, a prefix of another weight set, a null or destroyed prefix, workspace too small) are decided
+ * on the host before any launch. */
+typedef struct kk_csm_prefix kk_csm_prefix;
+int kk_csm_prefix_create(kk_csm* m, void* stream, int S, const int32_t* tokens, const float* tokens_mask, void* workspace, size_t workspace_bytes,
+                         kk_csm_prefix** out);
+int kk_csm_prefix_length(const kk_csm_prefix* p);
+size_t kk_csm_prefix_bytes(const kk_csm_prefix* p);
+int kk_csm_prefix_read(const kk_csm_prefix* p, void* stream, float* dst, size_t dst_bytes);
+void kk_csm_prefix_destroy(kk_csm_prefix* p);
+int kk_csm_admit_prefixed(kk_csm* m, void* stream, int row, const kk_csm_prefix* prefix, int S, const int32_t* tokens, const float* tokens_mask,
+                          const kk_csm_sampler* sampler, const float* uniforms, int32_t stream_id, void* workspace, size_t workspace_bytes,
+                          int32_t* codes_out);
 /* graph replay of the single-token frame step: the third call with identical pointers / B / sampler settings and every later one is ONE
  * hipGraphLaunch (the backbone position is a device counter, so the captured step is position-independent); results are unchanged */
 int kk_csm_set_graph_mode(kk_csm* m, int on);

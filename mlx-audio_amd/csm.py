@@ -22,6 +22,40 @@ def _llama_args(d: dict) -> _lib.KKLlamaArgs:
     return a
 
 
+class Prefix:
+    """kk_csm_prefix: the backbone K / V of a prompt's first `length` frames on the device, immutable, shared by every stream admitted on top of
+    it (`SesameModel.admit(..., prefix=)`).  Usable from the generator it was made on and from its `share()`s.  Freed by `close()` / on collection."""
+
+    def __init__(self, lib, handle, length: int, device, owner):
+        self.lib, self._h, self.length, self.device = lib, handle, int(length), device
+        self._owner = owner  # the weights outlive the prefix
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.lib.kk_csm_prefix_bytes(self._h)) if self._h else 0
+
+    def save(self) -> torch.Tensor:
+        """A copy of the buffer, [layers, 2 (K, V), length, kv_heads * head_dim] float32 as one flat device tensor."""
+        if not self._h:
+            raise ValueError("Prefix.save: the prefix is closed")
+        out = torch.empty(self.nbytes // 4, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.lib.kk_csm_prefix_read(self._h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), C.c_void_p(out.data_ptr()),
+                                              out.numel() * 4), "kk_csm_prefix_read")
+        return out
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self.lib.kk_csm_prefix_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SesameModel:
     def __init__(self, cfg: dict, weights: Optional[Dict[str, np.ndarray]] = None, device: str = "cuda:0", weight_dtype: str = "float32",
                  quantization: Optional[dict] = None, weight_storage: str = "packed"):
@@ -77,6 +111,13 @@ class SesameModel:
         other._ws, other._enabled, other.max_batch, other._graph, other._gbuf, other._sid = None, False, 0, False, {}, {}
         other._ws_admit = None
         return other
+
+    def weights_root(self) -> "SesameModel":
+        """The generator that owns the device weights this one runs on (itself, unless it came from `share()`)."""
+        m = self
+        while getattr(m, "_parent", None) is not None:
+            m = m._parent
+        return m
 
     def __del__(self):
         try:
@@ -263,13 +304,43 @@ class SesameModel:
         with torch.cuda.device(self.device):
             check(self.lib.kk_csm_shift_caches(self._h, self._stream(), delta, None, 0), "kk_csm_shift_caches")
 
+    def _admit_workspace(self, S: int):
+        need = int(self.lib.kk_csm_workspace_bytes(self._h, 1, max(2, S)))
+        if need == 0:
+            raise KokoroHipError("kk_csm_workspace_bytes failed")
+        # a workspace of its own: the captured frame step of the running batch is keyed on ITS workspace pointer
+        if self._ws_admit is None or self._ws_admit.numel() < need:
+            self._ws_admit = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws_admit, need
+
+    def make_prefix(self, tokens, tokens_mask) -> Prefix:
+        """kk_csm_prefix_create: the backbone K / V of the frames tokens / tokens_mask [n, n_cb+1] at positions 0 .. n-1 as a `Prefix`.  No cache
+        row, position or captured graph is touched: legal while a batch runs.  No depth decoder, no sampling."""
+        tokens = torch.as_tensor(tokens).to(device=self.device, dtype=torch.int32).contiguous()
+        mask = torch.as_tensor(tokens_mask).to(device=self.device, dtype=torch.float32).contiguous()
+        ncb = self.cfg["audio_num_codebooks"]
+        if tokens.dim() != 2 or tokens.shape[1] != ncb + 1 or mask.shape != tokens.shape:
+            raise ValueError(f"tokens / tokens_mask must be [n, {ncb + 1}]")
+        n = int(tokens.shape[0])
+        if not 1 <= n < int(self.cfg["max_seq_len"]):
+            raise ValueError(f"make_prefix: {n} frames; a prefix holds 1 .. max_seq_len - 1 frames")
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            ws, need = self._admit_workspace(n)
+            check(self.lib.kk_csm_prefix_create(self._h, self._stream(), n, C.c_void_p(tokens.data_ptr()), C.c_void_p(mask.data_ptr()),
+                                                C.c_void_p(ws.data_ptr()), need, C.byref(h)), "kk_csm_prefix_create")
+        return Prefix(self.lib, h, n, self.device, self)
+
     def admit(self, row: int, tokens, tokens_mask, temperature: float = 0.0, top_k: int = 50, uniforms=None, sampler=None, seed: Optional[int] = None,
-              stream_id: int = 0) -> torch.Tensor:
+              stream_id: int = 0, prefix: Optional[Prefix] = None) -> torch.Tensor:
         """The prompt frame of ONE new stream (tokens / tokens_mask [S, n_cb+1]) into the parked cache row `row` of a running batch; the
         other rows keep their state and the shared position does not move.  Sampling as in generate_frame (`uniforms` [n_cb]; or `seed`
         with `stream_id`: the device generator at the stream's own position S).  Returns codes [n_cb] int32 -- the bits of
         generate_frame on the prompt alone.  ValueError for a live row, a row out of range, or a prompt longer than the position
-        (`shift(S - P)` first)."""
+        (`shift(S - P)` first).
+        `prefix` (make_prefix): the stream's prompt is the prefix followed by `tokens`; the prefix's K / V are copied under the suffix instead of
+        being computed, the result is, bit for bit, that of the whole prompt.  Then the prompt length that must fit is prefix.length + S; a
+        closed prefix or one of another weight set is a ValueError."""
         assert self.caches_are_enabled(), "backbone caches are not enabled"
         tokens = torch.as_tensor(tokens).to(device=self.device, dtype=torch.int32).contiguous()
         mask = torch.as_tensor(tokens_mask).to(device=self.device, dtype=torch.float32).contiguous()
@@ -282,8 +353,13 @@ class SesameModel:
         pad, P = self.row_state()
         if pad[int(row)] < int(self.cfg["max_seq_len"]):
             raise ValueError(f"admit: row {row} is live (park it first)")
-        if S < 1 or S > P:
-            raise ValueError(f"admit: a prompt of {S} frames does not fit below position {P} (shift by {S - P} first)")
+        n = 0
+        if prefix is not None:
+            if not isinstance(prefix, Prefix) or not prefix._h:
+                raise ValueError("admit: prefix must be an open Prefix (make_prefix)")
+            n = prefix.length
+        if S < 1 or n + S > P:
+            raise ValueError(f"admit: a prompt of {n + S} frames does not fit below position {P} (shift by {n + S - P} first)")
         u = None
         if uniforms is not None:
             u = torch.as_tensor(uniforms).to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
@@ -296,16 +372,19 @@ class SesameModel:
         if u is None and seed is not None:
             sp.seed, sp.use_device_rng = int(seed) & 0xFFFFFFFFFFFFFFFF, 1
         with torch.cuda.device(self.device):
-            need = int(self.lib.kk_csm_workspace_bytes(self._h, 1, S))
-            if need == 0:
-                raise KokoroHipError("kk_csm_workspace_bytes failed")
-            # a workspace of its own: the captured frame step of the running batch is keyed on ITS workspace pointer
-            if self._ws_admit is None or self._ws_admit.numel() < need:
-                self._ws_admit = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws, need = self._admit_workspace(S)
             codes = torch.empty(ncb, dtype=torch.int32, device=self.device)
+            if prefix is not None:
+                rc = self.lib.kk_csm_admit_prefixed(self._h, self._stream(), int(row), prefix._h, S, C.c_void_p(tokens.data_ptr()),
+                                                    C.c_void_p(mask.data_ptr()), C.byref(sp), C.c_void_p(u.data_ptr()) if u is not None else None,
+                                                    int(stream_id) & 0x7FFFFFFF, C.c_void_p(ws.data_ptr()), need, C.c_void_p(codes.data_ptr()))
+                if rc != 0 and b"another weight set" in (self.lib.kk_last_error() or b""):
+                    raise ValueError("admit: the prefix was computed with another weight set")
+                check(rc, "kk_csm_admit_prefixed")
+                return codes
             check(self.lib.kk_csm_admit(self._h, self._stream(), int(row), S, C.c_void_p(tokens.data_ptr()), C.c_void_p(mask.data_ptr()), C.byref(sp),
                                         C.c_void_p(u.data_ptr()) if u is not None else None, int(stream_id) & 0x7FFFFFFF,
-                                        C.c_void_p(self._ws_admit.data_ptr()), need, C.c_void_p(codes.data_ptr())), "kk_csm_admit")
+                                        C.c_void_p(ws.data_ptr()), need, C.c_void_p(codes.data_ptr())), "kk_csm_admit")
         return codes
 
     def debug_logits(self) -> torch.Tensor:

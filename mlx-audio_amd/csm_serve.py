@@ -12,6 +12,11 @@ One scheduling round (`step`): poll the EOS flags (one sync every `eos_check_int
 and decode them (streams of equal length in one Mimi.decode call), admit queued requests FIFO into parked rows, shift if needed, then one
 frame for all rows through the captured single-token graph.  An admission stalls the other rows for one prompt block and one B = 1 frame.
 
+A voice service's requests share most of their prompt: the speaker's reference segment.  `submit(prefix=vp, text=...)` (vp from
+`Model.voice_prefix(context)`) admits a request on top of the prefix's K / V, which are copied under the request's own text frames instead of being
+computed again (kk_csm_admit_prefixed): no Mimi.encode and no context tokenisation per request, a prompt block of the text frames
+only, the same bits.  Requests with and without a prefix mix freely in one batch.
+
 Not here: chunked audio while a stream runs (the streaming Mimi decoder carries one position for all rows)."""
 from __future__ import annotations
 
@@ -50,7 +55,8 @@ class _Stream:
     stream_id: int
     length: int                     # prompt frames
     t0: float
-    prompt: Optional[tuple] = None  # (tokens [S, n_cb+1], mask)
+    prompt: Optional[tuple] = None  # (tokens [S, n_cb+1], mask); with `prefix`: the frames behind the prefix
+    prefix: object = None           # sesame.VoicePrefix: the prompt is the prefix followed by `prompt`
     row: int = -1
     rng: Optional[np.random.Generator] = None
     codes: List[torch.Tensor] = field(default_factory=list)  # one [n_cb] tensor per generated frame
@@ -110,6 +116,13 @@ class ModelEngine:
                 out[i] = p
         return [out[i] for i in range(len(streams))]
 
+    def prefixed_prompt(self, prefix, text, speaker: int):
+        """The frames a request puts behind the voice prefix `prefix` (sesame.VoicePrefix): its own text segment.  Host work only.  ValueError
+        for a prefix that was made on other weights than this engine's."""
+        if getattr(prefix, "root", None) is not self.csm.weights_root():
+            raise ValueError("the voice prefix was made on another model's weights (Model.voice_prefix on this model or one it shares weights with)")
+        return self.model._tokenize_text_segment(text, speaker)
+
     def row_state(self):
         return self.csm.row_state()
 
@@ -119,8 +132,9 @@ class ModelEngine:
     def shift(self, delta: int) -> None:
         self.csm.shift(delta)
 
-    def admit(self, row: int, prompt, sampler, uniforms, seed, stream_id: int) -> torch.Tensor:
-        return self.csm.admit(row, prompt[0], prompt[1], sampler=sampler, uniforms=uniforms, seed=seed, stream_id=stream_id)
+    def admit(self, row: int, prompt, sampler, uniforms, seed, stream_id: int, prefix=None) -> torch.Tensor:
+        return self.csm.admit(row, prompt[0], prompt[1], sampler=sampler, uniforms=uniforms, seed=seed, stream_id=stream_id,
+                              prefix=prefix.prefix if prefix is not None else None)
 
     def frame(self, prev: torch.Tensor, sampler, uniforms, seed, stream_ids) -> torch.Tensor:
         B, n = prev.shape
@@ -168,7 +182,7 @@ class CSMBatcher:
         self._rows: List[Optional[_Stream]] = [None] * self.max_batch
         self._since_poll = 0
         self.stats = {"frames": 0, "live_row_frames": 0, "admissions": 0, "admit_seconds": 0.0, "shifts": 0, "shift_seconds": 0.0,
-                      "shifts_down": 0, "shifts_up": 0, "polls": 0, "finished": 0}
+                      "shifts_down": 0, "shifts_up": 0, "polls": 0, "finished": 0, "prefixed_admissions": 0}
         self.engine.start(self.max_batch)
         dev = self.engine.device
         self._prev = torch.zeros((self.max_batch, self.engine.n_cb), dtype=torch.int32, device=dev)
@@ -176,17 +190,31 @@ class CSMBatcher:
         self._local = torch.zeros((self.max_batch,), dtype=torch.int64, device=dev)        # stream-local index of the next frame
 
     # ---- requests ---------------------------------------------------------------------------------------------------------------------
-    def submit(self, context, text, speaker: int = 0, voice_match: bool = True, max_audio_length_ms: float = 90_000, seed: Optional[int] = None,
-               stream_id: Optional[int] = None, prompt=None) -> Future:
+    def submit(self, context=None, text=None, speaker: int = 0, voice_match: Optional[bool] = None, max_audio_length_ms: float = 90_000,
+               seed: Optional[int] = None, stream_id: Optional[int] = None, prompt=None, prefix=None) -> Future:
         """Queue one request; the future yields a `StreamResult`.  `prompt` (tokens, mask) skips the prompt building.  rng "host": `seed`
         seeds this stream's generator (None: fresh entropy).  rng "device": the batcher's seed is used, `seed` must be None or equal to it.
-        ValueError at once for a request that cannot fit the cache; a request that races `close()` gets a failed future."""
+        ValueError at once for a request that cannot fit the cache; a request that races `close()` gets a failed future.
+        `prefix` (`Model.voice_prefix(context)`): the request's prompt is the prefix followed by the text segment of `text` / `speaker` -- the
+        non-voice_match layout with the prefix's context.  Its length is prefix.length + the text frames; the prefix's K / V are copied under
+        the text frames at admission, nothing of the context is encoded, tokenised or computed again.  `prefix` excludes `context`, `prompt`
+        and `voice_match=True` (ValueError): the voice_match layout merges the context's text with the request's in front of the audio, so it
+        has no shareable prefix.  voice_match defaults to True without a prefix, as before."""
         max_frames = int(max_audio_length_ms / 80)
-        if prompt is not None:
+        if prefix is not None:
+            if context or prompt is not None or voice_match:
+                raise ValueError("prefix= stands for the context of the non-voice_match layout: it excludes context, prompt and voice_match=True")
+            if text is None:
+                raise ValueError("a request on a prefix needs its own text")
+            voice_match = False
+            prompt = self.engine.prefixed_prompt(prefix, text, speaker)
+            prompt = (np.asarray(prompt[0], np.int32), np.asarray(prompt[1], np.float32))
+            length = int(prefix.length) + int(prompt[0].shape[0])
+        elif prompt is not None:
             prompt = (np.asarray(prompt[0], np.int32), np.asarray(prompt[1], np.float32))
             length = int(prompt[0].shape[0])
         else:
-            length = int(self.engine.prompt_length(context, text, speaker, voice_match))
+            length = int(self.engine.prompt_length(context, text, speaker, True if voice_match is None else voice_match))
         limit = self.engine.max_pos - max_frames
         if length >= limit:
             raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {limit}")  # sesame.py:755-758
@@ -204,9 +232,10 @@ class CSMBatcher:
             if stream_id is None:
                 stream_id = self._next_id
             self._next_id = max(self._next_id, int(stream_id)) + 1
-            self._queue.append(_Stream(future=fut, context=context, text=text, speaker=int(speaker), voice_match=bool(voice_match),
+            self._queue.append(_Stream(future=fut, context=context, text=text, speaker=int(speaker),
+                                       voice_match=True if voice_match is None else bool(voice_match),
                                        max_frames=max_frames, seed=seed, stream_id=int(stream_id), length=length, t0=time.perf_counter(),
-                                       prompt=prompt))
+                                       prompt=prompt, prefix=prefix))
             self._wake.notify()
         return fut
 
@@ -271,14 +300,14 @@ class CSMBatcher:
             return
         need = [s for s in new if s.prompt is None]
         try:
-            for s, p in zip(need, self.engine.prompts(need)):
+            for s, p in zip(need, self.engine.prompts(need) if need else []):
                 s.prompt = p
         except Exception as e:  # noqa: BLE001
             for s in need:
                 s.future.set_exception(e)
             new = [s for s in new if s.prompt is not None]
         for s, row in zip(new, free):
-            S = int(s.prompt[0].shape[0])
+            S = int(s.prompt[0].shape[0]) + (int(s.prefix.length) if s.prefix is not None else 0)  # the whole prompt: what must fit below P
             try:
                 if S != s.length:
                     raise ValueError(f"the prompt has {S} frames, {s.length} were announced")
@@ -293,12 +322,16 @@ class CSMBatcher:
                     u = s.rng.uniform(size=(1, self.engine.n_cb))[0].astype(np.float32)
                 seed = self.seed if (self._sampled and self.rng == "device") else None
                 out: List[torch.Tensor] = []
-                self._timed("admit", lambda: out.append(self.engine.admit(row, s.prompt, self.sampler, u, seed, s.stream_id)))
+                if s.prefix is not None:
+                    self._timed("admit", lambda: out.append(self.engine.admit(row, s.prompt, self.sampler, u, seed, s.stream_id, prefix=s.prefix)))
+                else:
+                    self._timed("admit", lambda: out.append(self.engine.admit(row, s.prompt, self.sampler, u, seed, s.stream_id)))
                 codes = out[0]
             except Exception as e:  # noqa: BLE001
                 s.future.set_exception(e)
                 continue
             self.stats["admissions"] += 1
+            self.stats["prefixed_admissions"] += s.prefix is not None
             s.row = row
             s.codes = [codes]
             self._rows[row] = s

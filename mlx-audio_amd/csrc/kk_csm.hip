@@ -11,7 +11,9 @@
 #include <math.h>
 #include <string.h>
 
+#include <atomic>
 #include <map>
+#include <mutex>
 #include <set>
 #include <string>
 #include <vector>
@@ -62,6 +64,7 @@ struct Stack {
   int max_pos = 0, offset = 0;
   int* pos_dev = nullptr;  // backbone only: device copy of `offset` (null: positions are launch constants)
   int* pad_dev = nullptr;  // backbone only: [max_batch] left padding of each item's prompt (kk_csm_set_padding), zeros by default
+  size_t layer_pitch = 0;  // floats between two layers of kc / vc; 0: the caches' own max_batch * max_pos * KV * hd (kk_csm_prefix_create sets its buffer's)
 };
 
 }  // namespace
@@ -102,6 +105,7 @@ struct kk_csm {
   unsigned long long* seed_dev = nullptr;
   unsigned long long seed_host = 0;
   bool seed_valid = false;
+  unsigned long long weights_id = 0;   // the weight set (kk_csm_finalize; kk_csm_share copies it): what a kk_csm_prefix is tied to
   const kk_csm* weights_of = nullptr;  // kk_csm_share: `dev` / `devb` / `devq` belong to that generator (immutable after finalize), not to this one
 };
 
@@ -677,6 +681,26 @@ __global__ __launch_bounds__(64) void shift_cache_kernel(float* kc, float* vc, i
         if (s - i >= lo) base[(long long)(s - i + delta) * rowf4] = r[i];
     }
   }
+}
+
+// kk_csm_admit_prefixed: the K / V of a shared prefix ([layer][K|V][n][KV hd] fp32, compact) go under a stream's suffix -- into the n slots of ONE
+// cache row that start at `kc` / `vc` (the caller has added row and first slot), in every layer: blockIdx.y = 2 layer + (0 K, 1 V).  Per (layer,
+// K|V) both sides are ONE contiguous run of seg4 = n KV hd / 4 16-byte columns, so this is a plain streaming copy: a workgroup owns 16 KiB of
+// the run (eight 2 KiB slot rows at CSM-1B's geometry), a thread four columns 4 KiB apart -- every wave instruction moves 1 KiB of consecutive
+// bytes --, the four loads are issued ahead of the four stores.  Default cache policy on both sides: the prefix is read again by the next
+// admission (10 MB at n = 160 stay in the last-level cache) and the row is read right behind by the suffix block's attention.
+__global__ __launch_bounds__(256) void prefix_restore_kernel(const float4* src, float* kc, float* vc, long long layer_pitch4, long long seg4) {
+  const int z = blockIdx.y;
+  const float4* s = src + (long long)z * seg4;
+  float4* d = (float4*)((z & 1) ? vc : kc) + (long long)(z >> 1) * layer_pitch4;
+  const long long i0 = (long long)blockIdx.x * 1024 + threadIdx.x;
+  float4 r[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+    if (i0 + 256 * u < seg4) r[u] = s[i0 + 256 * u];
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+    if (i0 + 256 * u < seg4) d[i0 + 256 * u] = r[u];
 }
 
 // silu(gate) * up, gu [rows][2I] -> [rows][I]
@@ -1725,6 +1749,13 @@ struct Run : Workspace {
   int B;
   float* skinny_scratch = nullptr;  // partial sums of the skinny GEMM
   size_t skinny_floats = 0;
+  // Which kernel a Linear takes is a function of the block's rows per item (below).  A prompt that is SPLIT into a prefix block and a suffix block
+  // (kk_csm_prefix_create / kk_csm_admit_prefixed) must carry the bits of the unsplit block, whose rows all took the prompt kernels:
+  //   LIN_PROMPT: a block of <= 2 rows goes where a long block goes (gemmp_kernel on a fragment pack, else the generic fp32 kernel);
+  //   LIN_GENERIC: the generic fp32 kernel -- where the last row of a long block goes for the first head (a strided one-row block).
+  // Both kernels compute an output row from its input row alone, in an order that does not depend on the row count.
+  enum { LIN_AUTO = 0, LIN_PROMPT, LIN_GENERIC };
+  int lin_mode = LIN_AUTO;
   Run(kk_csm* m_, hipStream_t st_, int B_, void* ws, size_t ws_bytes) : m(m_), st(st_), B(B_) {
     base = (char*)ws; cap = ws_bytes; dry = ws == nullptr;
   }
@@ -1743,7 +1774,7 @@ struct Run : Workspace {
     a.Q = rows; a.Lo_rows = rows; a.lin = KKLen{nullptr, 0, rows}; a.lout = KKLen{nullptr, 0, rows};
     a.in_slope = 1.f; a.scale = 1.f;
     int nb = B;
-    if (xbs == (long long)rows * w.Cin && obs == (long long)rows * w.Cout && rows <= 2 && skinny_scratch && w.w) {
+    if (xbs == (long long)rows * w.Cin && obs == (long long)rows * w.Cout && rows <= 2 && skinny_scratch && w.w && lin_mode == LIN_AUTO) {
       // single-token steps (and the decoder's 2-token first step): the HBM-bound skinny GEMM (every CU streams a slice of W once for up
       // to 16 rows).  The choice depends on the rows PER ITEM only, never on B, so a stream's bits do not depend on its batch.
       const int Mtot = B * rows;
@@ -1758,7 +1789,8 @@ struct Run : Workspace {
         return 0;
       }
     }
-    if (xbs == (long long)rows * w.Cin && obs == (long long)rows * w.Cout && w.wm && w.nsub && (rows > 2 || !w.w)) {
+    if (xbs == (long long)rows * w.Cin && obs == (long long)rows * w.Cout && w.wm && w.nsub && (rows > 2 || !w.w || lin_mode == LIN_PROMPT) &&
+        lin_mode != LIN_GENERIC) {
       // the prompt block in bf16 weight mode: matrix cores (gemmp_kernel); without a fragment pack, the generic fp32 kernel below.
       // The choice depends on the rows PER ITEM only, never on B: a stream's bits do not depend on its batch.  (A packed quantised matrix has
       // no fp32 copy for the skinny GEMM: its one- and two-row blocks come here too.)
@@ -1951,11 +1983,12 @@ int stack_forward(Run& r, Stack& st, float* h, int S, int offset, float* out) {
   }
   for (int l = 0; l < a.num_layers; ++l) {
     const LlamaLayer& L = st.layers[l];
-    float* kc = st.kc + (size_t)l * r.m->max_batch * st.max_pos * KV * hd;
-    float* vc = st.vc + (size_t)l * r.m->max_batch * st.max_pos * KV * hd;
+    const size_t lp = st.layer_pitch ? st.layer_pitch : (size_t)r.m->max_batch * st.max_pos * KV * hd;
+    float* kc = st.kc + (size_t)l * lp;
+    float* vc = st.vc + (size_t)l * lp;
     KK_TRY(r.lin(L.qkv, x, (long long)S * D, S, qkv, (long long)S * W, nullptr));
     if (!r.dry) {
-      if (S == 1)  // single-token step: RoPE + cache append inside the attention kernel
+      if (S == 1 && r.lin_mode == Run::LIN_AUTO)  // single-token step: RoPE + cache append inside the attention kernel
         KK_TRY(attn_single(ATTN_CACHE, qkv, B, H, KV, hd, st.pos_dev, st.pos_dev ? 0 : offset, kc, vc, st.max_pos, st.rope.p, st.pad_dev, att, nullptr, r.st));
       else
         KK_TRY(attn_prompt(qkv, B, S, H, KV, hd, st.pos_dev, st.pos_dev ? 0 : offset, kc, vc, st.max_pos, st.rope.p, st.pad_dev, att, r.st));
@@ -2026,8 +2059,10 @@ int stack_step(Run& r, Stack& st, float* h, int rows, int offset, const FGArgs* 
 // `seed`: the device seed of the Philox uniforms, or null (injected uniforms / argmax)
 // `own_pos` >= 0 (kk_csm_admit): the frame is the prompt block of ONE stream in a row view of the backbone cache -- its Philox position is that
 // constant (the stream's own position, not slot - padding) and the shared slot counter is NOT advanced
+// `split` (kk_csm_admit_prefixed): the block is the tail of a longer prompt -- its backbone rows and the first head take the kernels the rows of the
+// unsplit block take, whatever S (Run::lin_mode); the depth decoder sees the same shapes either way
 int run_frame(Run& r, int S, const int* tokens, const float* mask, const SampleCfg& sc, const float* uniforms, const unsigned long long* seed,
-              const int* stream_ids, int* codes, int own_pos = -1) {
+              const int* stream_ids, int* codes, int own_pos = -1, bool split = false) {
   kk_csm* m = r.m;
   // the uniform of (item, code book i): uniforms[b][i], or Philox at the position of the frame being generated (slot *pos_dev + S, minus the padding)
   auto src_of = [&](int i) {
@@ -2063,7 +2098,7 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, const SampleC
   for (const auto& l : m->audio_head) heads_fast = heads_fast && l.wm;
   const float* last_h;   // the backbone's final-normed last position of every item
   long long last_rs;     // its item pitch
-  if (fast && heads_fast && S == 1) {
+  if (fast && heads_fast && S == 1 && !split) {
     KK_TRY(stack_step(r, m->bb, h, 1, m->bb.offset));
     if (!r.dry) {
       hipLaunchKernelGGL(rmsnorm_kernel, dim3(B), dim3(256), 0, r.st, h, m->bb.norm.p, D, c.backbone.rms_eps, hn);
@@ -2071,7 +2106,10 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, const SampleC
     }
     last_h = hn; last_rs = D;
   } else {
-    KK_TRY(stack_forward(r, m->bb, h, S, m->bb.offset, hn));
+    if (split) r.lin_mode = Run::LIN_PROMPT;
+    const int rc_ = stack_forward(r, m->bb, h, S, m->bb.offset, hn);
+    r.lin_mode = Run::LIN_AUTO;
+    if (rc_ != 0) return rc_;
     last_h = hn ? hn + (size_t)(S - 1) * D : nullptr;  // row S-1 of every item (pitch S*D)
     last_rs = (long long)S * D;
   }
@@ -2119,7 +2157,12 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, const SampleC
       rows = 1;
     }
   } else {
-  KK_TRY(r.lin(m->c0_head, last_h, last_rs, 1, logits, V, nullptr));
+  if (split) r.lin_mode = Run::LIN_GENERIC;
+  {
+    const int rc_ = r.lin(m->c0_head, last_h, last_rs, 1, logits, V, nullptr);
+    r.lin_mode = Run::LIN_AUTO;
+    if (rc_ != 0) return rc_;
+  }
   if (!r.dry) {
     KK_TRY(launch_sample(logits, V, sc, src_of(0), codes, ncb, B, r.st));
     // curr = [last_h, embed_audio(0, c0)]
@@ -2528,6 +2571,8 @@ extern "C" int kk_csm_finalize(kk_csm* m, void* stream) {
     for (const auto& l : m->audio_head) ok = ok && l.wm;
     if (!ok) return kk_fail("kk_csm_finalize: internal: packed storage without a complete fast path");
   }
+  static std::atomic<unsigned long long> next_weights_id{1};
+  m->weights_id = next_weights_id++;
   m->finalized = true;
   return 0;
 }
@@ -2794,6 +2839,150 @@ extern "C" int kk_csm_admit(kk_csm* m, void* stream, int row, int S, const int32
   RowView view(m->bb, row, P - S);
   Run r(m, st, 1, workspace, workspace_bytes);
   return run_frame(r, S, tokens, tokens_mask, sc, uniforms, dev_rng ? m->seed_dev : nullptr, dev_rng ? m->admit_sid_dev : nullptr, codes_out, S);
+}
+
+// ---- shared voice prefixes -----------------------------------------------------------------------------------------------------
+struct kk_csm_prefix {
+  float* buf = nullptr;  // [layers][K|V][n][KV hd]
+  int n = 0, layers = 0, kvw = 0;
+  unsigned long long weights_id = 0;
+};
+static size_t kk_csm_prefix_bytes_of(const kk_csm_prefix* p) { return (size_t)2 * p->layers * p->n * p->kvw * 4; }
+
+namespace {
+// the live prefixes: a destroyed (or never created) handle is refused by address, without reading through it
+std::mutex g_prefix_mu;
+std::set<const kk_csm_prefix*> g_prefixes;
+bool prefix_live(const kk_csm_prefix* p) {
+  std::lock_guard<std::mutex> lk(g_prefix_mu);
+  return p && g_prefixes.count(p) != 0;
+}
+// The backbone as kk_csm_prefix_create sees it: the prefix buffer as a one-row cache of its own (layer pitch 2 n KV hd, K in front of V), positions
+// from 0 as launch constants, no padding.  No cache row, counter or padding entry of the generator is read or written.  Restored on every way out.
+struct PrefixView {
+  Stack& s;
+  float *kc, *vc;
+  int *pos, *pad;
+  int off;
+  size_t lp;
+  PrefixView(Stack& st, float* buf, int n) : s(st), kc(st.kc), vc(st.vc), pos(st.pos_dev), pad(st.pad_dev), off(st.offset), lp(st.layer_pitch) {
+    const size_t seg = (size_t)n * st.a.num_kv_heads * st.a.head_dim;
+    s.kc = buf; s.vc = buf + seg; s.pos_dev = nullptr; s.pad_dev = nullptr; s.offset = 0; s.layer_pitch = 2 * seg;
+  }
+  ~PrefixView() { s.kc = kc; s.vc = vc; s.pos_dev = pos; s.pad_dev = pad; s.offset = off; s.layer_pitch = lp; }
+};
+// the workspace of a block run by the two entries below: a one-row block takes the prompt path, whose scratch the S = 2 plan covers
+size_t split_workspace_bytes(kk_csm* m, int S) { return kk_csm_workspace_bytes(m, 1, S < 2 ? 2 : S); }
+}  // namespace
+
+extern "C" int kk_csm_prefix_create(kk_csm* m, void* stream, int S, const int32_t* tokens, const float* tokens_mask, void* workspace,
+                                    size_t workspace_bytes, kk_csm_prefix** out) {
+  if (!m || !m->finalized) return kk_fail("kk_csm_prefix_create: model not finalized");
+  if (S <= 0 || !tokens || !tokens_mask || !workspace || !out) return kk_fail("kk_csm_prefix_create: bad argument");
+  const kk_llama_args& a = m->bb.a;
+  const int kvw = a.num_kv_heads * a.head_dim;
+  if (kvw % 4 != 0) return kk_fail("kk_csm_prefix_create: kv_heads * head_dim must be a multiple of 4");
+  if (S >= m->bb.max_pos) return kk_fail("kk_csm_prefix_create: the prefix must leave room for a suffix below max_seq_len");
+  if (m->cfg.audio_num_codebooks > 71) return kk_fail("kk_csm: more than 71 code books");
+  if (workspace_bytes < split_workspace_bytes(m, S)) return kk_fail("kk_csm_prefix_create: workspace too small");
+  kk_csm_prefix* p = new (std::nothrow) kk_csm_prefix();
+  if (!p) return kk_fail("kk_csm_prefix_create: out of memory");
+  p->n = S; p->layers = a.num_layers; p->kvw = kvw; p->weights_id = m->weights_id;
+  if (hipMalloc((void**)&p->buf, kk_csm_prefix_bytes_of(p)) != hipSuccess) {
+    delete p;
+    return kk_fail("kk_csm_prefix_create: hipMalloc failed");
+  }
+  int rc;
+  {
+    hipStream_t st = (hipStream_t)stream;
+    const kk_csm_config& c = m->cfg;
+    const int D = c.backbone.hidden;
+    PrefixView view(m->bb, p->buf, S);
+    Run r(m, st, 1, workspace, workspace_bytes);
+    float* h = r.f32((size_t)S * D);
+    float* hn = r.f32((size_t)S * D);
+    if (r.oom) rc = kk_fail("kk_csm_prefix_create: workspace too small");
+    else {
+      hipLaunchKernelGGL(embed_sum_kernel, dim3(S, (D + 255) / 256), dim3(256), 0, st, tokens, tokens_mask, m->audio_emb.p, m->text_emb.p,
+                         c.audio_num_codebooks, c.audio_vocab_size, c.text_vocab_size, D, h);
+      rc = hipGetLastError() == hipSuccess ? 0 : kk_fail("kk_csm_prefix_create: launch failed");
+      r.lin_mode = Run::LIN_PROMPT;
+      if (rc == 0) rc = stack_forward(r, m->bb, h, S, 0, hn);
+    }
+  }
+  if (rc != 0) {
+    (void)hipStreamSynchronize((hipStream_t)stream);  // nothing in flight may still write the buffer
+    (void)hipFree(p->buf);
+    delete p;
+    return rc;
+  }
+  {
+    std::lock_guard<std::mutex> lk(g_prefix_mu);
+    g_prefixes.insert(p);
+  }
+  *out = p;
+  return 0;
+}
+
+extern "C" int kk_csm_prefix_length(const kk_csm_prefix* p) { return prefix_live(p) ? p->n : -1; }
+extern "C" size_t kk_csm_prefix_bytes(const kk_csm_prefix* p) { return prefix_live(p) ? kk_csm_prefix_bytes_of(p) : 0; }
+
+extern "C" int kk_csm_prefix_read(const kk_csm_prefix* p, void* stream, float* dst, size_t dst_bytes) {
+  if (!prefix_live(p)) return kk_fail("kk_csm_prefix_read: null or destroyed prefix");
+  if (!dst || dst_bytes < kk_csm_prefix_bytes_of(p)) return kk_fail("kk_csm_prefix_read: destination too small");
+  if (hipMemcpyAsync(dst, p->buf, kk_csm_prefix_bytes_of(p), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
+    return kk_fail("kk_csm_prefix_read: copy failed");
+  return 0;
+}
+
+extern "C" void kk_csm_prefix_destroy(kk_csm_prefix* p) {
+  {
+    std::lock_guard<std::mutex> lk(g_prefix_mu);
+    if (!p || g_prefixes.erase(p) == 0) return;
+  }
+  (void)hipDeviceSynchronize();  // an admission in flight may still read it
+  (void)hipFree(p->buf);
+  delete p;
+}
+
+extern "C" int kk_csm_admit_prefixed(kk_csm* m, void* stream, int row, const kk_csm_prefix* prefix, int S, const int32_t* tokens,
+                                     const float* tokens_mask, const kk_csm_sampler* sampler, const float* uniforms, int32_t stream_id,
+                                     void* workspace, size_t workspace_bytes, int32_t* codes_out) {
+  if (!m || !m->finalized) return kk_fail("kk_csm_admit_prefixed: model not finalized");
+  if (m->max_batch < 1) return kk_fail("kk_csm_admit_prefixed: call kk_csm_setup_caches first");
+  if (row < 0 || row >= m->max_batch) return kk_fail("kk_csm_admit_prefixed: row out of range");
+  if (!prefix_live(prefix)) return kk_fail("kk_csm_admit_prefixed: null or destroyed prefix");
+  if (S <= 0 || !tokens || !tokens_mask || !sampler || !workspace || !codes_out) return kk_fail("kk_csm_admit_prefixed: bad argument");
+  const kk_llama_args& a = m->bb.a;
+  const int P = m->bb.offset, mp = m->bb.max_pos, n = prefix->n, kvw = a.num_kv_heads * a.head_dim;
+  if (prefix->weights_id != m->weights_id || prefix->layers != a.num_layers || prefix->kvw != kvw)
+    return kk_fail("kk_csm_admit_prefixed: the prefix was computed with another weight set");
+  if (m->pad_host[row] < mp) return kk_fail("kk_csm_admit_prefixed: the row is live (kk_csm_park_row first)");
+  if (n + S > P) return kk_fail("kk_csm_admit_prefixed: prefix + suffix are longer than the cache position (kk_csm_shift_caches by n + S - P first)");
+  if (workspace_bytes < split_workspace_bytes(m, S)) return kk_fail("kk_csm_admit_prefixed: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  SampleCfg sc;
+  KK_TRY(sampler_cfg(sampler, &sc, "kk_csm_admit_prefixed"));
+  const bool dev_rng = !uniforms && sampler->use_device_rng && sc.temp > 0.f;
+  m->pad_host[row] = P - n - S;
+  m->pad_pending = true;
+  KK_TRY(flush_pending(m, st));
+  if (dev_rng) {
+    KK_TRY(upload_seed(m, sampler->seed, st));
+    m->admit_sid_host = stream_id;
+    if (hipMemcpyAsync(m->admit_sid_dev, &m->admit_sid_host, 4, hipMemcpyHostToDevice, st) != hipSuccess)
+      return kk_fail("kk_csm_admit_prefixed: stream id upload failed");
+  }
+  {  // the prefix under the suffix: slots [P - n - S, P - S) of the row, every layer's K and V in one launch (0 <= P - n - S and P - S < max_pos: inside the row)
+    const size_t at = ((size_t)row * mp + (size_t)(P - n - S)) * kvw;
+    const long long seg4 = (long long)n * kvw / 4, pitch4 = (long long)m->max_batch * mp * kvw / 4;
+    hipLaunchKernelGGL(prefix_restore_kernel, dim3((unsigned)((seg4 + 1023) / 1024), 2 * a.num_layers), dim3(256), 0, st, (const float4*)prefix->buf,
+                       m->bb.kc + at, m->bb.vc + at, pitch4, seg4);
+    KK_CHECK_LAUNCH();
+  }
+  RowView view(m->bb, row, P - S);
+  Run r(m, st, 1, workspace, workspace_bytes);
+  return run_frame(r, S, tokens, tokens_mask, sc, uniforms, dev_rng ? m->seed_dev : nullptr, dev_rng ? m->admit_sid_dev : nullptr, codes_out, n + S, true);
 }
 
 extern "C" int kk_csm_debug_timestamps(unsigned long long* buf, int capacity) {

@@ -93,6 +93,20 @@ class BatchResult:
     codes: Optional[torch.Tensor] = None  # [B, n_cb, T] as generated (frames past a stream's EOS are whatever the loop produced)
 
 
+@dataclass
+class VoicePrefix:
+    """`Model.voice_prefix`: a speaker's context segments as a shared prompt prefix -- their K / V on the device (`csm.Prefix`) and the token
+    frames they were computed from.  Requests of `Model.serve()` and the lines of `Model.generate(cache_context=True)` are admitted on top of it."""
+    prefix: object             # csm.Prefix
+    tokens: np.ndarray         # [length, n_cb+1] int32
+    mask: np.ndarray           # [length, n_cb+1] float32
+    length: int
+    root: object               # the SesameModel that owns the weights the K / V were computed with
+
+    def close(self) -> None:
+        self.prefix.close()
+
+
 def _is_ids(t) -> bool:
     return not isinstance(t, str)
 
@@ -284,6 +298,21 @@ class Model:
             fm.append(b)
         return np.concatenate(ft, 0), np.concatenate(fm, 0)
 
+    def voice_prefix(self, context: Sequence[Segment]) -> VoicePrefix:
+        """The context of the non-`voice_match` prompt layout (`prompt_frames`: every segment with its EOS frame, then the text) as a shared
+        prefix: tokenised once (clips through `encode_audios`), run through the backbone once (`SesameModel.make_prefix`), and reused by every
+        stream admitted on top of it -- from this model or its `share()`s.  A stream on the prefix carries the bits of the whole prompt run
+        alone.  The `voice_match=True` layout merges the context's text with the request's into ONE text segment in front of the audio, so
+        nothing in front of the request's own text is shared: it has no prefix."""
+        context = list(context)
+        if not context:
+            raise ValueError("voice_prefix needs at least one context segment")
+        clips = [seg.audio for seg in context if seg.audio is not None]
+        codes = {id(a): c for a, c in zip(clips, self.encode_audios(clips))} if clips else {}
+        tokens, mask = self.prompt_frames(context, None, voice_match=False, _codes=codes)
+        return VoicePrefix(prefix=self.model.make_prefix(tokens, mask), tokens=tokens, mask=mask, length=int(tokens.shape[0]),
+                           root=self.model.weights_root())
+
     # ---- the frame loop over B streams ------------------------------------------------------------------------------------------------------
     def _frame_loop(self, prompts, max_audio_frames: int, sampler: Sampler, seed: Optional[int], stop_on_eos: bool,
                     uniforms: Optional[Callable[[int], np.ndarray]] = None, rng: str = "host", stream_ids=None):
@@ -339,6 +368,51 @@ class Model:
             curr = torch.zeros((B, 1, n + 1), dtype=torch.int32, device=dev)
             curr[:, 0, :n] = sample
             cmask = step_mask
+
+    def _frame_loop_prefixed(self, vp: VoicePrefix, suffix, max_audio_frames: int, sampler: Sampler, seed: Optional[int], stop_on_eos: bool,
+                             rng: str = "host"):
+        """`_frame_loop([vp.tokens + suffix])` for one stream without re-running the prefix: the cache starts parked at position
+        vp.length + S, the suffix is admitted on top of the prefix into row 0 (`SesameModel.admit(prefix=)`), and the frame steps follow as in
+        `_frame_loop`.  Same draws, same kernels on the same cache slots: the same frames, bit for bit."""
+        csm, n = self.model, self.n_cb
+        tok, msk = suffix
+        L = vp.length + int(tok.shape[0])
+        max_seq_len = csm.cfg["max_seq_len"] - max_audio_frames
+        if L >= max_seq_len:
+            raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {max_seq_len}")  # sesame.py:755-758
+        if vp.root is not csm.weights_root():
+            raise ValueError("the voice prefix was made on another model's weights")
+        dev = csm.device
+        if not csm.caches_are_enabled():
+            csm.setup_caches(1)
+        csm.reset_caches_parked()
+        csm.set_graph_mode(True)
+        csm.shift(L)  # nothing is live: only the position moves, and the stream's window starts at slot 0 as in the unsplit run
+        temperature = float(sampler.temp)
+        device_rng = _check_rng(rng) == "device" and temperature > 0
+        if device_rng and seed is None:
+            seed = int(np.random.SeedSequence().generate_state(2, np.uint32).view(np.uint64)[0])
+        gen = np.random.default_rng(seed) if (temperature > 0 and not device_rng) else None
+        plain = not device_rng and not (0.0 < sampler.top_p < 1.0) and not sampler.min_p > 0.0
+        step_mask = torch.zeros((1, 1, n + 1), dtype=torch.float32, device=dev)
+        step_mask[:, 0, :n] = 1
+        done = torch.zeros(1, dtype=torch.bool, device=dev)
+        curr = None
+        for i in range(max_audio_frames):
+            u = None
+            if gen is not None:
+                u = torch.tensor(np.asarray(gen.uniform(size=(1, n)), np.float32), device=dev)
+            how = dict(temperature=temperature, top_k=int(sampler.top_k)) if plain else dict(sampler=sampler, seed=seed if device_rng else None)
+            if i == 0:
+                sample = csm.admit(0, tok, msk, uniforms=u, prefix=vp.prefix, **how)[None]
+            else:
+                sample = csm.generate_frame(curr, step_mask, uniforms=u, **how)
+            was_done = done
+            if stop_on_eos:
+                done = done | (sample == 0).all(dim=1)
+            yield sample.clone(), was_done, done
+            curr = torch.zeros((1, 1, n + 1), dtype=torch.int32, device=dev)
+            curr[:, 0, :n] = sample
 
     def generate_batch(self, prompts, max_audio_length_ms: float = 90_000, temperature: float = 0.9, top_k: int = 50, seed: Optional[int] = 0,
                        stop_on_eos: bool = True, eos_check_interval: int = 8, decode: bool = True,
@@ -425,15 +499,20 @@ class Model:
     def generate(self, text: Union[TextLike, List[TextLike]], voice: Optional[str] = None, speaker: int = 0, context: Optional[List[Segment]] = None,
                  split_pattern: Optional[str] = r"\n+", sampler: Callable = None, max_audio_length_ms: float = 90_000, ref_audio=None,
                  ref_text: Optional[TextLike] = None, stream: bool = False, streaming_interval: float = 0.5, voice_match: bool = True,
-                 seed: Optional[int] = None, stop_on_eos: bool = True, rng: str = "host", **kwargs):
+                 seed: Optional[int] = None, stop_on_eos: bool = True, rng: str = "host", cache_context: bool = False, **kwargs):
         """Yields one GenerationResult per text prompt (per `streaming_interval` seconds of frames with stream=True).  `sampler` is what
         `make_sampler(temp, top_k)` of this module returns (the reference takes mlx_lm's callable of the same name, sesame.py:719) and
         defaults, as there, to temp 0.9 / top_k 50; its top_p / min_p / min_tokens_to_keep are honoured.  rng "host" (default) draws numpy
         uniforms per frame, "device" draws in the sampling kernels from `seed` (no per-frame upload).  A bare `temperature=` / `top_p=` /
         `top_k=` -- generate_audio forwards its own defaults to every model (generate.py:288-300) -- lands in **kwargs and is IGNORED,
-        exactly as the reference's signature ignores it."""
+        exactly as the reference's signature ignores it.
+        cache_context (an addition, needs voice_match=False): the context is run through the backbone ONCE for the call (`voice_prefix`) and
+        every line of `text` is admitted on top of its K / V instead of re-running the context per line; the output per line is that of
+        cache_context=False, bit for bit.  The voice_match=True layout has no shareable prefix (see `voice_prefix`)."""
         sampler = sampler or make_sampler(temp=0.9, top_k=50)
         _check_rng(rng)
+        if cache_context and voice_match:
+            raise ValueError("cache_context needs voice_match=False: the merged-text layout has no shareable prefix")
         context = list(context or [])
         if not context and ref_audio is not None and ref_text is not None:
             a = ref_audio.detach().cpu().numpy() if isinstance(ref_audio, torch.Tensor) else np.asarray(ref_audio, np.float32)
@@ -446,17 +525,20 @@ class Model:
             text = re.split(split_pattern, text.strip()) if split_pattern else [text]
         elif text and isinstance(text[0], (int, np.integer)):
             text = [text]  # one pre-tokenised prompt
+        vp = self.voice_prefix(context) if cache_context else None
         for prompt in text:
             start = time.perf_counter()
-            frames = self.prompt_frames(context, prompt, speaker, voice_match=voice_match)
+            frames = self._tokenize_text_segment(prompt, speaker) if vp is not None else self.prompt_frames(context, prompt, speaker, voice_match=voice_match)
             if stream:
                 if self._streaming_decoder is None:
                     self._streaming_decoder = MimiStreamingDecoder(self._audio_tokenizer)
                 self._streaming_decoder.reset()
             samples = []
             self._seed_counter += 1
-            for sample, was_done, done in self._frame_loop([frames], max_audio_frames, sampler,
-                                                           seed if seed is None else seed + self._seed_counter - 1, stop_on_eos, rng=rng):
+            line_seed = seed if seed is None else seed + self._seed_counter - 1
+            loop = (self._frame_loop_prefixed(vp, frames, max_audio_frames, sampler, line_seed, stop_on_eos, rng=rng) if vp is not None
+                    else self._frame_loop([frames], max_audio_frames, sampler, line_seed, stop_on_eos, rng=rng))
+            for sample, was_done, done in loop:
                 if bool(done[0]):
                     break  # eos (batch 1: one sync per frame, as in the reference)
                 samples.append(sample)

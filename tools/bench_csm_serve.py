@@ -6,7 +6,10 @@ fixed lists; all requests are queued at time 0; no codec (audio = 80 ms per fram
 profiles/csm_serve_bench.json: audio-seconds per wall-second of both modes, their ratio and the ratio the lengths alone allow (frame steps
 of the static plan / of a FIFO row schedule, computed on the host), the row occupancy (live row-frames / computed row-frames), and the mean
 cost of an admission and of a cache shift (a second, profiled continuous run: one sync around each).  --max-seq-len is small by default so
-that the session passes the end of the cache and down-shifts happen."""
+that the session passes the end of the cache and down-shifts happen.
+--prefix N: instead, the same stream lengths with every request's prompt = one shared N-frame voice prefix (text + audio + EOS frames) followed by
+its own 16-48 text frames, continuous batching only, admitted plain (the whole prompt per request) / on the prefix (`submit(prefix=)`) / plain
+again; per run wall, audio-s/s, frame steps and (a second, profiled run) the mean admission ms.  Written to profiles/csm_serve_prefix_bench.json."""
 import argparse
 import json
 import os
@@ -31,8 +34,11 @@ ap.add_argument("--batch", type=int, default=8)
 ap.add_argument("--weights", default="bfloat16", choices=["float32", "bfloat16"])
 ap.add_argument("--max-seq-len", type=int, default=512)
 ap.add_argument("--seed", type=int, default=0)
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "csm_serve_bench.json"))
+ap.add_argument("--prefix", type=int, default=0, help="frames of a voice prefix shared by every request (0: the static / continuous comparison)")
+ap.add_argument("--out", default=None)
 a = ap.parse_args()
+if a.out is None:
+    a.out = os.path.join(ROOT, "profiles", "csm_serve_prefix_bench.json" if a.prefix else "csm_serve_bench.json")
 
 cfg = dict(P.csm_config(), max_seq_len=a.max_seq_len)
 loop = Model(cfg, weights=P.csm_synth_checkpoint(cfg, 0), weight_dtype=a.weights)
@@ -85,6 +91,62 @@ def run_continuous(profile):
     assert [f.result(timeout=0).frames for f in futs] == flen
     return dt, bat
 
+
+def bench_prefix():
+    from mlx_audio_amd.sesame import VoicePrefix
+
+    N, nt = a.prefix, min(32, a.prefix // 4)
+    ptok, pmsk = np.zeros((N, n + 1), np.int32), np.zeros((N, n + 1), np.float32)
+    ptok[:nt, -1], pmsk[:nt, -1] = rng.integers(0, cfg["text_vocab_size"], nt), 1
+    ptok[nt:N - 1, :n] = rng.integers(0, cfg["audio_vocab_size"], (N - 1 - nt, n))  # the clip's frames, then the all-zero EOS frame
+    pmsk[nt:, :n] = 1
+    texts = [rng.integers(0, cfg["text_vocab_size"], int(L)).tolist() for L in rng.integers(16, 49, a.requests)]
+    vp = VoicePrefix(prefix=loop.model.make_prefix(ptok, pmsk), tokens=ptok, mask=pmsk, length=N, root=loop.model.weights_root())
+    whole = [tuple(np.concatenate([p, t], 0) for p, t in zip((ptok, pmsk), loop._tokenize_text_segment(x, 0))) for x in texts]
+
+    def run(prefixed, profile):
+        bat = loop.serve(max_batch=B, rng="device", sampler=sampler, seed=a.seed, stop_on_eos=False, decode=False, profile=profile)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        if prefixed:
+            futs = [bat.submit(prefix=vp, text=texts[i], max_audio_length_ms=80 * flen[i]) for i in range(a.requests)]
+        else:
+            futs = [bat.submit(None, None, prompt=whole[i], max_audio_length_ms=80 * flen[i]) for i in range(a.requests)]
+        bat.run_until_idle()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t
+        assert [f.result(timeout=0).frames for f in futs] == flen
+        return dt, bat.stats
+
+    def both(prefixed):
+        dt, st = run(prefixed, False)
+        _, ps = run(prefixed, True)
+        return {"wall_s": dt, "xrt": audio_s / dt, "frame_steps": st["frames"], "admissions": st["admissions"],
+                "prefixed_admissions": st["prefixed_admissions"], "admit_ms_mean": 1e3 * ps["admit_seconds"] / max(1, ps["admissions"]),
+                "shifts_down": st["shifts_down"], "shifts_up": st["shifts_up"]}
+
+    run(False, False), run(True, False)  # warm-up: kernel loading, workspaces, graph capture
+    res = {"metric": "CSM-1B serving on a shared voice prefix, plain vs prefixed admission, " + a.weights, "requests": a.requests, "batch": B,
+           "max_seq_len": a.max_seq_len, "prefix_frames": N, "prefix_bytes": vp.prefix.nbytes, "text_frames": [len(x) for x in texts],
+           "stream_frames": flen, "audio_s": audio_s, "order": ["plain_first", "prefixed", "plain_last"],
+           "data": "synthetic (random-init CSM-1B weights, random prefix and text frames, imposed stream lengths, device uniforms, no codec)"}
+    res["plain_first"], res["prefixed"], res["plain_last"] = both(False), both(True), both(False)
+    plain = [res["plain_first"]["admit_ms_mean"], res["plain_last"]["admit_ms_mean"]]
+    res["value"] = res["prefixed"]["admit_ms_mean"] / (0.5 * sum(plain))
+    res["value_is"] = "prefixed / plain mean admission ms (plain: mean of the two runs; their spread %.3f ms)" % abs(plain[0] - plain[1])
+    return res
+
+
+if a.prefix:
+    if not 8 <= a.prefix < a.max_seq_len - 48 - max(LENGTHS):
+        sys.exit(f"--prefix must be in [8, {a.max_seq_len - 48 - max(LENGTHS)}) at --max-seq-len {a.max_seq_len}")
+    out = bench_prefix()
+    print(json.dumps(out))
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    sys.exit(0)
 
 static_steps = sum(max(flen[i] for i in g) - 1 for g in groups)
 static_rf = sum(sum(flen[i] - 1 for i in g) for g in groups)
