@@ -30,10 +30,12 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 4   /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 5   /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
-                            4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed) */
+                            4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
+                            5: row-mode streaming Mimi decode (kk_mimi_stream_create_rows, kk_mimi_stream_reset_row, kk_mimi_decode_step_rows,
+                               kk_mimi_stream_row_frames, kk_mimi_stream_row_snapshot) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -280,6 +282,20 @@ int kk_mimi_stream_set_context(kk_mimi_stream* s, int context); /* TransformerCo
 size_t kk_mimi_stream_workspace_bytes(kk_mimi_stream* s, int B);
 int kk_mimi_decode_step(kk_mimi_stream* s, void* stream, int B, const int32_t* codes, void* workspace, size_t workspace_bytes, float* pcm_out);
 int kk_mimi_encode_step(kk_mimi_stream* s, void* stream, int B, const float* pcm, void* workspace, size_t workspace_bytes, int32_t* codes_out); /* Mimi.encode_step (mimi.py:156-161) */
+/* Row mode (ABI minor 5): a decode stream whose rows each have their own position and lifetime, for a codec that follows a continuously
+ * batched generator.  Positions live on the device (one int per row); a host mirror of the per-row frame counts carries every bound check,
+ * so a refusal happens before any launch.  kk_mimi_decode_step_rows takes F <= max_chunk frames for ALL max_batch rows
+ * (codes [max_batch][nq][F] on the device, active [max_batch] on the HOST); rows with active[b] == 0 ride along: their carried state, their
+ * K / V below their position and their position are bit-unchanged, their pcm is finite and meaningless, their code entries may hold anything.
+ * An active row's pcm is, bit for bit, that of a batch-1 kk_mimi_decode_step stream fed the same codes in the same step sizes.
+ * kk_mimi_stream_reset_row starts one row over (one launch in stream order, no other row touched).  kk_mimi_decode_step, kk_mimi_stream_reset
+ * and the encoder are refused on such a stream; kk_mimi_stream_set_context needs every row fresh; workspace: kk_mimi_stream_workspace_bytes(s, max_batch).
+ * kk_mimi_stream_row_snapshot (tests): the row's device position (transformer rows), carried rows and K / V below the position, to the host. */
+int kk_mimi_stream_create_rows(kk_mimi* m, int max_batch, int max_frames, int max_chunk, kk_mimi_stream** out);
+int kk_mimi_stream_reset_row(kk_mimi_stream* s, void* stream, int row);
+int kk_mimi_stream_row_frames(const kk_mimi_stream* s, int row);
+int kk_mimi_decode_step_rows(kk_mimi_stream* s, void* stream, int F, const int32_t* codes, const int32_t* active, void* workspace, size_t workspace_bytes, float* pcm_out);
+int kk_mimi_stream_row_snapshot(kk_mimi_stream* s, void* stream, int row, int32_t* pos_out, float* dst, size_t dst_floats, size_t* floats_out);
 /* intermediates of the last decode / encode (tests): "quantized", "upsampled", "transformer", "layer0".."layer3" (decode), "seanet", "transformer", "downsampled" (encode); [B][rows][channels] fp32 */
 int kk_mimi_debug_info(kk_mimi* m, const char* name, int64_t* rows, int64_t* channels);
 int kk_mimi_debug_fetch(kk_mimi* m, void* stream, const char* name, float* dst);

@@ -17,9 +17,16 @@ A voice service's requests share most of their prompt: the speaker's reference s
 computed again (kk_csm_admit_prefixed): no Mimi.encode and no context tokenisation per request, a prompt block of the text frames
 only, the same bits.  Requests with and without a prefix mix freely in one batch.
 
-Not here: chunked audio while a stream runs (the streaming Mimi decoder carries one position for all rows)."""
+Audio while a stream runs: `CSMBatcher(..., stream_chunk_frames=N)` and `submit_stream(...)`.  The codec follows the batch in
+a row-mode streaming decoder (`Mimi.row_decoder`: one position and one lifetime per row, the decoder row is the cache row), and a request's
+audio arrives in chunks of N frames -- chunk k is its frames [kN, (k+1)N), the last one the remainder -- whose concatenation is, bit for
+bit, a batch-1 `Mimi.decode_step` stream over its codes in steps of N, ..., r.  A chunk is decoded only after an EOS poll has confirmed its
+frames (polls run every N frames then), so nothing at or after a stream's EOS frame or past its frame limit is ever emitted.  Ready chunks
+are decoded in one aligned round per poll: all rows with a full chunk in one `step(F=N)`, tails grouped by equal r.  `submit` is unchanged
+(one offline `Mimi.decode` at the end) and mixes with `submit_stream` in one batch."""
 from __future__ import annotations
 
+import queue
 import threading
 import time
 from collections import deque
@@ -44,6 +51,44 @@ class StreamResult:
 
 
 @dataclass
+class AudioChunk:
+    """One piece of a streaming request's waveform: stream-local frames [first_frame, first_frame + frames)."""
+    audio: torch.Tensor  # [samples]
+    first_frame: int
+    frames: int
+    final: bool          # the stream's last chunk: `result()` is ready
+
+
+class CSMAudioStream:
+    """What `submit_stream` returns.  Iterating yields the request's `AudioChunk`s as the scheduler produces them and ends behind the final
+    one; a failed request (or `close()`) ends the iteration by raising its error, never by hanging.  `result(timeout)` is the usual
+    `StreamResult`; its audio is the concatenation of the chunks.  `first_audio_seconds`: submit -> first chunk, once there is one."""
+
+    def __init__(self, future: Future):
+        self.future = future
+        self.first_audio_seconds: Optional[float] = None
+        self._q: "queue.Queue" = queue.Queue()
+        future.add_done_callback(self._ended)
+
+    def _ended(self, fut: Future) -> None:  # a failure from ANY path of the scheduler reaches the consumer (success: the final chunk is already queued)
+        e = fut.exception()
+        if e is not None:
+            self._q.put(e)
+
+    def __iter__(self):
+        while True:
+            item = self._q.get()
+            if isinstance(item, BaseException):
+                raise item
+            yield item
+            if item.final:
+                return
+
+    def result(self, timeout: Optional[float] = None) -> StreamResult:
+        return self.future.result(timeout)
+
+
+@dataclass
 class _Stream:
     future: Future
     context: Sequence
@@ -60,6 +105,11 @@ class _Stream:
     row: int = -1
     rng: Optional[np.random.Generator] = None
     codes: List[torch.Tensor] = field(default_factory=list)  # one [n_cb] tensor per generated frame
+    audio: Optional[CSMAudioStream] = None  # submit_stream: where the chunks go
+    chunks: List[torch.Tensor] = field(default_factory=list)  # the audio of the chunks emitted so far
+    emitted: int = 0                # frames decoded and emitted
+    confirmed: int = 0              # frames a poll has confirmed (below the EOS frame and the limit)
+    ended: bool = False             # a poll has seen the stream's end: `confirmed` is its length
 
 
 class ModelEngine:
@@ -150,21 +200,33 @@ class ModelEngine:
             raise ValueError("decoding needs the Mimi codec: pass mimi= or config['mimi_path']")
         return self.model._audio_tokenizer.decode(codes)[:, 0]
 
+    def row_decoder(self, max_batch: int, max_frames: int, max_chunk: int):
+        """The codec's row-mode streaming decoder (mimi.MimiRowDecoder): reset_row, step(codes, active), row_frames, close."""
+        if self.model._audio_tokenizer is None:
+            raise ValueError("streaming audio needs the Mimi codec: pass mimi= or config['mimi_path']")
+        return self.model._audio_tokenizer.row_decoder(max_batch, max_frames, max_chunk)
+
     def synchronize(self) -> None:
         torch.cuda.current_stream(self.device).synchronize()
 
 
 class CSMBatcher:
     def __init__(self, model, max_batch: int = 8, eos_check_interval: int = 8, rng: str = "device", sampler=None, seed: int = 0,
-                 stop_on_eos: bool = True, decode: bool = True, profile: bool = False, engine=None):
+                 stop_on_eos: bool = True, decode: bool = True, profile: bool = False, engine=None, stream_chunk_frames: Optional[int] = None,
+                 stream_max_frames: int = 1125):
         """model: a loaded sesame.Model (its frame generator's caches are taken over; use `model.share()` for a generator of its own).
         sampler: `make_sampler(...)` for every stream of the batch (default temp 0.9 / top_k 50).  seed: the device generator's seed (rng
         "device": one seed per batcher, streams differ by their ids).  profile: time admissions and shifts (one sync each) into `stats`.
-        engine: the surface of `ModelEngine`, for a scheduler without a device."""
+        engine: the surface of `ModelEngine`, for a scheduler without a device.
+        stream_chunk_frames: N enables `submit_stream` (audio in chunks of N frames through the codec's row-mode decoder); the EOS flags are
+        then polled every N frames instead of every `eos_check_interval`.  stream_max_frames: the longest streaming request (the decoder's K / V
+        cache holds that many frames per row; 1125 = the default 90 s limit of a request)."""
         if rng not in ("host", "device"):
             raise ValueError(f"rng must be 'host' or 'device', not {rng!r}")
         if max_batch < 1 or eos_check_interval < 1:
             raise ValueError("max_batch and eos_check_interval must be >= 1")
+        if stream_chunk_frames is not None and (int(stream_chunk_frames) < 1 or int(stream_max_frames) < int(stream_chunk_frames) or not decode):
+            raise ValueError("stream_chunk_frames must be in [1, stream_max_frames] and needs decode=True")
         if sampler is None:
             from .sesame import make_sampler
 
@@ -184,6 +246,13 @@ class CSMBatcher:
         self.stats = {"frames": 0, "live_row_frames": 0, "admissions": 0, "admit_seconds": 0.0, "shifts": 0, "shift_seconds": 0.0,
                       "shifts_down": 0, "shifts_up": 0, "polls": 0, "finished": 0, "prefixed_admissions": 0}
         self.engine.start(self.max_batch)
+        self.chunk = int(stream_chunk_frames) if stream_chunk_frames is not None else None
+        self.stream_max_frames = int(stream_max_frames)
+        self._dec = None
+        if self.chunk is not None:
+            self.interval = self.chunk  # a chunk is decoded once a poll has confirmed it: poll at the chunk cadence
+            self.stats.update(chunks=0, chunk_rounds=0)
+            self._dec = self.engine.row_decoder(self.max_batch, self.stream_max_frames, self.chunk)
         dev = self.engine.device
         self._prev = torch.zeros((self.max_batch, self.engine.n_cb), dtype=torch.int32, device=dev)
         self._first_eos = torch.full((self.max_batch,), -1, dtype=torch.int64, device=dev)  # stream-local index of the first all-zero frame
@@ -200,6 +269,17 @@ class CSMBatcher:
         the text frames at admission, nothing of the context is encoded, tokenised or computed again.  `prefix` excludes `context`, `prompt`
         and `voice_match=True` (ValueError): the voice_match layout merges the context's text with the request's in front of the audio, so it
         has no shareable prefix.  voice_match defaults to True without a prefix, as before."""
+        return self._enqueue(False, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix)
+
+    def submit_stream(self, context=None, text=None, speaker: int = 0, voice_match: Optional[bool] = None, max_audio_length_ms: float = 90_000,
+                      seed: Optional[int] = None, stream_id: Optional[int] = None, prompt=None, prefix=None) -> CSMAudioStream:
+        """`submit` with the audio delivered while the stream runs: the same arguments and refusals, a `CSMAudioStream` back.  Needs a batcher
+        made with `stream_chunk_frames=N`; the request may not be longer than `stream_max_frames`."""
+        if self._dec is None:
+            raise ValueError("submit_stream needs a batcher made with stream_chunk_frames=N")
+        return self._enqueue(True, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix)
+
+    def _enqueue(self, _streaming: bool, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix):
         max_frames = int(max_audio_length_ms / 80)
         if prefix is not None:
             if context or prompt is not None or voice_match:
@@ -220,24 +300,27 @@ class CSMBatcher:
             raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {limit}")  # sesame.py:755-758
         if max_frames < 1 or length < 1:
             raise ValueError("a request needs a prompt and at least one frame")
+        if _streaming and max_frames > self.stream_max_frames:
+            raise ValueError(f"a streaming request of {max_frames} frames: the batcher was made for stream_max_frames = {self.stream_max_frames}")
         if self.rng == "device" and seed is not None and int(seed) != self.seed:
             raise ValueError(f"rng 'device': every stream draws from the batcher's seed {self.seed}; streams differ by stream_id")
         if stream_id is not None and not 0 <= int(stream_id) < 2 ** 31:
             raise ValueError("stream_id must be in [0, 2^31)")
         fut: Future = Future()
+        audio = CSMAudioStream(fut) if _streaming else None
         with self._lock:
             if self._closed:
                 fut.set_exception(RuntimeError("CSMBatcher is closed"))
-                return fut
+                return audio if _streaming else fut
             if stream_id is None:
                 stream_id = self._next_id
             self._next_id = max(self._next_id, int(stream_id)) + 1
             self._queue.append(_Stream(future=fut, context=context, text=text, speaker=int(speaker),
                                        voice_match=True if voice_match is None else bool(voice_match),
                                        max_frames=max_frames, seed=seed, stream_id=int(stream_id), length=length, t0=time.perf_counter(),
-                                       prompt=prompt, prefix=prefix))
+                                       prompt=prompt, prefix=prefix, audio=audio))
             self._wake.notify()
-        return fut
+        return audio if _streaming else fut
 
     # ---- one scheduling round -----------------------------------------------------------------------------------------------------------
     def _live(self) -> List[_Stream]:
@@ -249,7 +332,19 @@ class CSMBatcher:
         self._since_poll = 0
         fe = self._first_eos.cpu().tolist() if self.stop_on_eos else [-1] * self.max_batch
         done: Dict[int, List[_Stream]] = {}
+        streaming = [s for s in self._live() if s.audio is not None]
+        for s in streaming:  # this poll confirms every frame generated so far, up to the EOS frame and the limit
+            eos = fe[s.row]
+            s.confirmed = min(eos if eos >= 0 else len(s.codes), s.max_frames)
+            s.ended = eos >= 0 or len(s.codes) >= s.max_frames
+            if s.ended:
+                self.engine.park(s.row)
+                self._rows[s.row] = None  # (the decoder row keeps its state until the next admission resets it: the tail is decoded below)
+        if streaming:
+            self._emit(streaming)
         for s in self._live():
+            if s.audio is not None:
+                continue
             eos = fe[s.row]
             if eos < 0 and len(s.codes) < s.max_frames:
                 continue
@@ -276,6 +371,62 @@ class CSMBatcher:
                 for s in group:
                     if not s.future.done():
                         s.future.set_exception(e)
+
+    # ---- streaming audio --------------------------------------------------------------------------------------------------
+    def _emit(self, streams: List[_Stream]) -> None:
+        """The aligned decode round of one poll.  Chunk k of a stream is its frames [kN, (k+1)N): it is decoded once a poll has confirmed one
+        frame MORE (the stream goes on, so the chunk is not its last) or the stream's end (then `final` is known: when the length is a
+        multiple of N the last full chunk carries it).  All rows with such a chunk go through one step(F=N); then the tails, grouped by r."""
+        N = self.chunk
+        while True:
+            ready = [s for s in streams if not s.future.done() and s.emitted + N <= s.confirmed and (s.ended or s.emitted + N < s.confirmed)]
+            if not ready:
+                break
+            self._decode_round(ready, N)
+        tails: Dict[int, List[_Stream]] = {}
+        for s in streams:
+            if s.ended and not s.future.done() and 0 < s.confirmed - s.emitted:
+                tails.setdefault(s.confirmed - s.emitted, []).append(s)
+        for r, group in tails.items():
+            self._decode_round(group, r)
+        for s in streams:
+            if not s.ended or s.future.done():
+                continue
+            self.stats["finished"] += 1
+            if s.confirmed == 0:
+                s.future.set_exception(AssertionError("No audio generated"))
+                continue
+            s.future.set_result(StreamResult(audio=torch.cat(s.chunks), frames=s.confirmed, codes=torch.stack(s.codes[: s.confirmed], dim=1),
+                                             sample_rate=self.engine.sample_rate, stream_id=s.stream_id, row=s.row,
+                                             processing_time_seconds=time.perf_counter() - s.t0))
+
+    def _decode_round(self, group: List[_Stream], F: int) -> None:
+        """One step of the row decoder: F frames for the rows of `group`, the other rows inactive.  A failure fails the group's requests
+        (their iterators raise) and frees their rows; the other streams go on."""
+        try:
+            codes = torch.zeros((self.max_batch, self.engine.n_cb, F), dtype=torch.int32, device=self.engine.device)
+            active = [False] * self.max_batch
+            for s in group:
+                codes[s.row] = torch.stack(s.codes[s.emitted : s.emitted + F], dim=1)
+                active[s.row] = True
+            pcm = self._dec.step(codes, active)
+            self.engine.synchronize()
+            self.stats["chunk_rounds"] += 1
+            for s in group:
+                chunk = AudioChunk(audio=pcm[s.row, 0].clone(), first_frame=s.emitted, frames=F, final=s.ended and s.emitted + F == s.confirmed)
+                s.chunks.append(chunk.audio)
+                s.emitted += F
+                if s.audio.first_audio_seconds is None:
+                    s.audio.first_audio_seconds = time.perf_counter() - s.t0
+                self.stats["chunks"] += 1
+                s.audio._q.put(chunk)
+        except Exception as e:  # noqa: BLE001
+            for s in group:
+                if not s.future.done():
+                    s.future.set_exception(e)
+                if self._rows[s.row] is s:
+                    self._rows[s.row] = None
+                    self.engine.park(s.row)
 
     def _timed(self, what: str, fn) -> None:
         if self.profile:
@@ -330,6 +481,13 @@ class CSMBatcher:
             except Exception as e:  # noqa: BLE001
                 s.future.set_exception(e)
                 continue
+            if s.audio is not None:
+                try:
+                    self._dec.reset_row(row)  # the decoder row is the cache row: a new stream starts in it
+                except Exception as e:  # noqa: BLE001
+                    s.future.set_exception(e)
+                    self.engine.park(row)
+                    continue
             self.stats["admissions"] += 1
             self.stats["prefixed_admissions"] += s.prefix is not None
             s.row = row
@@ -430,6 +588,8 @@ class CSMBatcher:
         for s in self._live():
             self._rows[s.row] = None
             self.engine.park(s.row)
+        if self._dec is not None:
+            self._dec.close()
 
     def __enter__(self):
         return self

@@ -324,6 +324,118 @@ __global__ __launch_bounds__(128) void attn_cache_kernel(const float* qkv, int S
   }
 }
 
+// ---- per-row-offset forms (the row-mode streaming codec, kk_mimi_decode_step_rows): item b's block of S rows sits at ITS OWN position
+// row_pos[b] (device memory) instead of one launch-wide offset, and only rows with active[b] != 0 take part.  Within one row the
+// expressions and their order are those of rope_append_kernel / attn_cache_kernel<false> with offset = row_pos[b], pad = null and
+// causal = 0, so a row's bits are those of a kk_launch_rope_append / kk_launch_attn_cache call at the same position.  An inactive row
+// appends nothing (its K / V and position stay as they are) and gets a zero attention output (finite, never used).  The host has
+// checked row_pos[b] + S <= max_pos for every active row; the same test here turns a violation into an inactive row.
+__global__ __launch_bounds__(256) void rope_append_rows_kernel(float* qkv, int S, int H, int KV, int hd, const float* rope, const int* row_pos,
+                                                               const int* active, float* kc, float* vc, int max_pos) {
+  const int s = blockIdx.x, b = blockIdx.y;
+  const int offset = row_pos[b];
+  if (!active[b] || offset < 0 || offset + S > max_pos) return;
+  const int W = (H + 2 * KV) * hd, half = hd / 2;
+  float* row = qkv + ((long long)b * S + s) * W;
+  const float* cs = rope + (long long)(offset + s) * half * 2;
+  float* kdst = kc + ((long long)b * max_pos + offset + s) * KV * hd;
+  float* vdst = vc + ((long long)b * max_pos + offset + s) * KV * hd;
+  for (int e = threadIdx.x; e < (H + KV) * half; e += 256) {
+    const int hh = e / half, i = e - hh * half;
+    float* p = row + hh * hd + 2 * i;
+    const float c = cs[2 * i], sn = cs[2 * i + 1];
+    const float x0 = p[0], x1 = p[1];
+    const float y0 = x0 * c - x1 * sn, y1 = x1 * c + x0 * sn;
+    if (hh < H) {
+      p[0] = y0; p[1] = y1;
+    } else {
+      kdst[(hh - H) * hd + 2 * i] = y0;
+      kdst[(hh - H) * hd + 2 * i + 1] = y1;
+    }
+  }
+  const float* vsrc = row + (H + KV) * hd;
+  for (int e = threadIdx.x; e < KV * hd; e += 256) vdst[e] = vsrc[e];
+}
+
+// every query of row b's block sees the keys [max(0, row_pos[b] - ctx), row_pos[b] + S): at most sc_cap = min(max_pos, ctx + S) of them,
+// which is what the score buffer holds (dynamic LDS: sc_cap rounded up to 4, + hd + (512 / hd) * hd floats)
+__global__ __launch_bounds__(128) void attn_cache_rows_kernel(const float* qkv, int S, int H, int KV, int hd, const int* row_pos, const int* active,
+                                                              const float* kc, const float* vc, int max_pos, float scale, float* out, int ctx,
+                                                              int sc_cap) {
+  extern __shared__ __attribute__((aligned(16))) float sc[];  // [sc_cap] scores, [hd] q, [G][hd] partial outputs
+  __shared__ float red[2];
+  const int s = blockIdx.x, h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
+  const int offset = row_pos[b];
+  const int klo = ctx >= 0 && offset > ctx ? offset - ctx : 0;
+  const int W = (H + 2 * KV) * hd, kvh = h / (H / KV), nk = offset + S - klo;
+  if (!active[b] || offset < 0 || offset + S > max_pos || nk > sc_cap) {
+    for (int e = tid; e < hd; e += 128) out[((long long)b * S + s) * H * hd + h * hd + e] = 0.f;
+    return;
+  }
+  const int mp4 = (sc_cap + 3) & ~3;
+  float* qs = sc + mp4;  // [hd]
+  float* po = qs + hd;   // [G][hd]
+  const float* q = qkv + ((long long)b * S + s) * W + h * hd;
+  const float* kb = kc + ((long long)b * max_pos + klo) * KV * hd + kvh * hd;
+  const float* vb = vc + ((long long)b * max_pos + klo) * KV * hd + kvh * hd;
+  for (int e = tid; e < hd; e += 128) qs[e] = q[e];
+  __syncthreads();
+  const int hd4 = hd >> 2;
+  float mx = -INFINITY;
+  for (int j = tid; j < nk; j += 128) {
+    const float4* kr = (const float4*)(kb + (long long)j * KV * hd);
+    float d = 0.f;
+    for (int e0 = 0; e0 < hd4; e0 += 16) {
+      float4 kv[16];
+#pragma unroll
+      for (int t = 0; t < 16; ++t) kv[t] = kr[e0 + t];
+#pragma unroll
+      for (int t = 0; t < 16; ++t) {
+        const float4 qv = *(const float4*)(qs + 4 * (e0 + t));
+        d = __builtin_fmaf(qv.x, kv[t].x, d);
+        d = __builtin_fmaf(qv.y, kv[t].y, d);
+        d = __builtin_fmaf(qv.z, kv[t].z, d);
+        d = __builtin_fmaf(qv.w, kv[t].w, d);
+      }
+    }
+    d *= scale;
+    sc[j] = d;
+    mx = fmaxf(mx, d);
+  }
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  if ((tid & 63) == 0) red[tid >> 6] = mx;
+  __syncthreads();
+  mx = fmaxf(red[0], red[1]);
+  __syncthreads();
+  float sum = 0.f;
+  for (int j = tid; j < nk; j += 128) {
+    const float p = expf(sc[j] - mx);
+    sc[j] = p;
+    sum += p;
+  }
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+  if ((tid & 63) == 0) red[tid >> 6] = sum;
+  __syncthreads();
+  const float inv = 1.0f / (red[0] + red[1]);
+  const int G = 128 / hd4, e4 = tid % hd4, g = tid / hd4;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int j = g; j < nk; j += G) {
+    const float p = sc[j];
+    const float4 v = *(const float4*)(vb + (long long)j * KV * hd + 4 * e4);
+    acc.x = __builtin_fmaf(p, v.x, acc.x);
+    acc.y = __builtin_fmaf(p, v.y, acc.y);
+    acc.z = __builtin_fmaf(p, v.z, acc.z);
+    acc.w = __builtin_fmaf(p, v.w, acc.w);
+  }
+  *(float4*)(po + g * hd + 4 * e4) = acc;
+  __syncthreads();
+  for (int e = tid; e < hd; e += 128) {
+    float a = 0.f;
+    for (int gg = 0; gg < G; ++gg) a += po[gg * hd + e];  // group order
+    out[((long long)b * S + s) * H * hd + h * hd + e] = a * inv;
+  }
+}
+
 // attn_step_kernel (round 3): the single-token attention over a SHORT cache (max_pos <= 64: the depth decoder's 33 positions, small test
 // stacks) as ONE memory round trip.  attn_cache_kernel walks the keys in dependent steps (a thread per key with 2 x 16 loads, then the
 // values 4 keys at a time): 7.6 us per launch in the frame (frame time with it not launched), 124 launches.  Here a workgroup owns one (item, kv
@@ -2220,6 +2332,25 @@ int kk_launch_attn_cache(const float* qkv, int S, int H, int KV, int hd, int off
   if (hd != 64 && hd != 128) return kk_fail("attn_cache: head_dim must be 64 or 128");
   hipLaunchKernelGGL(attn_cache_kernel<false>, dim3(S, H, B), dim3(128), attn_lds_bytes(max_pos, hd), st, qkv, S, H, KV, hd, (const int*)nullptr, offset,
                      const_cast<float*>(kc), const_cast<float*>(vc), max_pos, scale, out, causal, ctx, (const float*)nullptr, (const int*)nullptr);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+// the per-row-offset forms: row b's S rows sit at position row_pos[b] (device, [B]); rows with active[b] == 0 (device, [B]) are left alone.
+// No causal mask (Mimi's streaming transformer); ctx >= 0 limits the look-back to the last ctx cached keys of the row.
+int kk_launch_rope_append_rows(float* qkv, int S, int H, int KV, int hd, const float* rope, const int* row_pos, const int* active, float* kc, float* vc,
+                               int max_pos, int B, hipStream_t st) {
+  if (hd != 64 && hd != 128) return kk_fail("rope_append_rows: head_dim must be 64 or 128");
+  hipLaunchKernelGGL(rope_append_rows_kernel, dim3(S, B), dim3(256), 0, st, qkv, S, H, KV, hd, rope, row_pos, active, kc, vc, max_pos);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+int kk_launch_attn_cache_rows(const float* qkv, int S, int H, int KV, int hd, const int* row_pos, const int* active, const float* kc, const float* vc,
+                              int max_pos, float scale, float* out, int ctx, int B, hipStream_t st) {
+  if (hd != 64 && hd != 128) return kk_fail("attn_cache_rows: head_dim must be 64 or 128");
+  const int cap = ctx >= 0 && ctx + S < max_pos ? ctx + S : max_pos;
+  const size_t lds = ((size_t)((cap + 3) & ~3) + hd + (size_t)(512 / hd) * hd) * 4;
+  if (lds > 64 * 1024) return kk_fail("attn_cache_rows: the key window does not fit the score buffer");
+  hipLaunchKernelGGL(attn_cache_rows_kernel, dim3(S, H, B), dim3(128), lds, st, qkv, S, H, KV, hd, row_pos, active, kc, vc, max_pos, scale, out, ctx, cap);
   KK_CHECK_LAUNCH();
   return 0;
 }

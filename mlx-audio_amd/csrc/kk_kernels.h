@@ -314,3 +314,8 @@ int kk_launch_linear_mxfp8(const KKFp8Args& a, hipStream_t st);
 int kk_launch_rope_append(float* qkv, int S, int H, int KV, int hd, const float* rope, int offset, float* kc, float* vc, int max_pos, int B, hipStream_t st);
 int kk_launch_attn_cache(const float* qkv, int S, int H, int KV, int hd, int offset, const float* kc, const float* vc, int max_pos, float scale, float* out,
                          int causal, int ctx, int B, hipStream_t st);
+// per-row positions (row-mode streaming codec): row b appends / attends at row_pos[b]; rows with active[b] == 0 are left alone (both device, [B])
+int kk_launch_rope_append_rows(float* qkv, int S, int H, int KV, int hd, const float* rope, const int* row_pos, const int* active, float* kc, float* vc,
+                               int max_pos, int B, hipStream_t st);
+int kk_launch_attn_cache_rows(const float* qkv, int S, int H, int KV, int hd, const int* row_pos, const int* active, const float* kc, const float* vc,
+                              int max_pos, float scale, float* out, int ctx, int B, hipStream_t st);

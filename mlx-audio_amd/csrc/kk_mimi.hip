@@ -691,6 +691,50 @@ int state_shift(const StateBuf& b, int B, hipStream_t st) {
   return 0;
 }
 
+// ---- row mode (kk_mimi_stream_create_rows): every row of the stream has its own position and lifetime.  The carry of ALL state buffers
+// is one launch over a device table of them, masked per row; a buffer's rows per step are npf per code frame (n = F * npf).
+struct RowBuf {
+  float* p;
+  int S, npf, C;
+  long long pitch;
+};
+// active[i] = bit i of the launch argument: the host's mask reaches the device in stream order, with no host buffer to keep alive
+__global__ void set_active_kernel(int* active, unsigned long long mask, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) active[i] = (int)((mask >> i) & 1ull);
+}
+// state_shift_kernel for (buffer blockIdx.x, row blockIdx.y) of an ACTIVE row: rows [n, n + S) -> [0, S), everything read before anything is
+// written; then the row's position advances by pos_step.  An inactive row keeps its carried rows (whatever this step's producers left in
+// its fresh region never reaches them) and its position.
+__global__ __launch_bounds__(256) void state_shift_rows_kernel(const RowBuf* tab, int F, const int* active, int* pos, int pos_step) {
+  const int row = blockIdx.y;
+  if (!active[row]) return;
+  const RowBuf t = tab[blockIdx.x];
+  float* q = t.p + (long long)row * t.pitch;
+  const int total = t.S * t.C, n = F * t.npf;
+  float v[SHIFT_PER_THREAD];
+#pragma unroll
+  for (int k = 0; k < SHIFT_PER_THREAD; ++k) {
+    const int e = threadIdx.x + k * 256;
+    v[k] = e < total ? q[(long long)n * t.C + e] : 0.f;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < SHIFT_PER_THREAD; ++k) {
+    const int e = threadIdx.x + k * 256;
+    if (e < total) q[e] = v[k];
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) pos[row] += pos_step;
+}
+// kk_mimi_stream_reset_row: the carried rows of one row in every buffer become zeros (the left padding of a first step; "no previous input"
+// for the transposed convolutions and the resampler) and its position 0.  Its K / V stay: a step reads keys below the position only.
+__global__ __launch_bounds__(256) void state_reset_row_kernel(const RowBuf* tab, int row, int* pos) {
+  const RowBuf t = tab[blockIdx.x];
+  float* q = t.p + (long long)row * t.pitch;
+  for (int e = threadIdx.x; e < t.S * t.C; e += 256) q[e] = 0.f;
+  if (blockIdx.x == 0 && threadIdx.x == 0) pos[row] = 0;
+}
+
 }  // namespace
 
 struct kk_mimi_stream {
@@ -710,6 +754,13 @@ struct kk_mimi_stream {
   std::vector<StateBuf> up, blk;
   int frames = 0, pos = 0, B = 0;
   bool fresh = true;
+  // row mode: per-row positions on the device (in transformer rows), their host mirror in code frames, the step's active mask, the carry table
+  bool rows_mode = false;
+  int* pos_dev = nullptr;     // [max_batch]
+  int* active_dev = nullptr;  // [max_batch]
+  RowBuf* table_dev = nullptr;
+  int ntable = 0;
+  std::vector<int> row_frames;
 };
 
 namespace {
@@ -725,8 +776,14 @@ int run_transformer_step(Run& r, kk_mimi_stream* s, const std::vector<MimiLayer>
     KK_TRY(r.layernorm(x, n, L.n1w.p, L.n1b.p));
     KK_TRY(r.conv(L.in_proj, n, qkv, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
     if (!r.dry) {
-      KK_TRY(kk_launch_rope_append((float*)qkv.p, T, H, H, hd, s->rope, s->pos, kcl, vcl, s->max_pos, B, r.st));
-      KK_TRY(kk_launch_attn_cache((const float*)qkv.p, T, H, H, hd, s->pos, kcl, vcl, s->max_pos, 1.0f / sqrtf((float)hd), (float*)att.p, 0, s->context, B, r.st));
+      if (s->rows_mode) {
+        KK_TRY(kk_launch_rope_append_rows((float*)qkv.p, T, H, H, hd, s->rope, s->pos_dev, s->active_dev, kcl, vcl, s->max_pos, B, r.st));
+        KK_TRY(kk_launch_attn_cache_rows((const float*)qkv.p, T, H, H, hd, s->pos_dev, s->active_dev, kcl, vcl, s->max_pos, 1.0f / sqrtf((float)hd),
+                                         (float*)att.p, s->context, B, r.st));
+      } else {
+        KK_TRY(kk_launch_rope_append((float*)qkv.p, T, H, H, hd, s->rope, s->pos, kcl, vcl, s->max_pos, B, r.st));
+        KK_TRY(kk_launch_attn_cache((const float*)qkv.p, T, H, H, hd, s->pos, kcl, vcl, s->max_pos, 1.0f / sqrtf((float)hd), (float*)att.p, 0, s->context, B, r.st));
+      }
     }
     KK_TRY(r.conv(L.out_proj, att, x, 0, 1, false, 1, 0, KK_ACT_NONE, &x, 0));
     KK_TRY(r.layernorm(x, n, L.n2w.p, L.n2b.p));
@@ -812,6 +869,12 @@ void stream_set_rows(kk_mimi_stream* s, int F) {
   }
 }
 
+// the carry of one buffer behind its consumer; a row-mode stream carries all its buffers in one masked launch at the end of the step
+int carry(Run& r, const kk_mimi_stream* s, const StateBuf& b) {
+  if (r.dry || s->rows_mode) return 0;
+  return state_shift(b, r.B, r.st);
+}
+
 int stream_begin(Run& r, kk_mimi_stream* s) {  // zero state on the first step after create / reset
   if (r.dry || !s->fresh) return 0;
   if (hipMemsetAsync(s->pool, 0, s->pool_floats * 4, r.st) != hipSuccess) return kk_fail("mimi stream: state reset failed");
@@ -838,7 +901,7 @@ int run_decode_step(Run& r, kk_mimi_stream* s, const int* codes, float* pcm_out)
   Act n = r.act(F * us, D), qkv = r.act(F * us, 3 * D), att = r.act(F * us, D), hbuf = r.act(F * us, c.dim_feedforward);
   stream_elu_scratch(r, s);
   if (r.oom) return kk_fail("kk_mimi_decode_step: workspace too small");
-  if (!r.dry && s->pos + F * us > s->max_pos) return kk_fail("kk_mimi_decode_step: the stream is longer than max_frames (kk_mimi_stream_create)");
+  if (!r.dry && !s->rows_mode && s->pos + F * us > s->max_pos) return kk_fail("kk_mimi_decode_step: the stream is longer than max_frames (kk_mimi_stream_create)");
   KK_TRY(stream_begin(r, s));
   // ---- quantizer.decode of the new frames, straight behind the previous one
   Act xq = s->resample.fresh();
@@ -856,7 +919,7 @@ int run_decode_step(Run& r, kk_mimi_stream* s, const int* codes, float* pcm_out)
   }
   KK_TRY(copy_rows(r, xu, us, x, F * us));
   KK_TRY(copy_rows(r, x, 0, xup, F * us));  // debug hook: the transformer updates x in place
-  if (!r.dry) KK_TRY(state_shift(s->resample, B, r.st));
+  KK_TRY(carry(r, s, s->resample));
   r.note("upsampled", xup);
   // ---- decoder_transformer with the KV caches
   KK_TRY(run_transformer_step(r, s, m->layers, x, n, qkv, att, hbuf));
@@ -864,7 +927,7 @@ int run_decode_step(Run& r, kk_mimi_stream* s, const int* codes, float* pcm_out)
   // ---- decoder.step (seanet.py:228-283 through each module's step)
   KK_TRY(copy_rows(r, x, 0, s->first.fresh(), F * us));
   KK_TRY(r.conv(m->init_conv, s->first.all(), s->up[0].fresh(), 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
-  if (!r.dry) KK_TRY(state_shift(s->first, B, r.st));
+  KK_TRY(carry(r, s, s->first));
   static const char* lname[8] = {"layer0", "layer1", "layer2", "layer3", "layer4", "layer5", "layer6", "layer7"};
   for (size_t l = 0; l < m->sea.size(); ++l) {
     const SeaLayer& S = m->sea[l];
@@ -875,17 +938,20 @@ int run_decode_step(Run& r, kk_mimi_stream* s, const int* codes, float* pcm_out)
     if (r.oom) return kk_fail("kk_mimi_decode_step: workspace too small");
     KK_TRY(r.conv(S.up, U.all(), full, 0, 1, true, S.ratio, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
     KK_TRY(copy_rows(r, full, S.ratio, Bk.fresh(), Bk.n));
-    if (!r.dry) KK_TRY(state_shift(U, B, r.st));
+    KK_TRY(carry(r, s, U));
     KK_TRY(r.conv(S.b0, Bk.all(), hb, 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
     const Act skip = Bk.fresh();
     KK_TRY(r.conv(S.b1, hb, nextb.fresh(), 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, &skip, 0));
-    if (!r.dry) KK_TRY(state_shift(Bk, B, r.st));
+    KK_TRY(carry(r, s, Bk));
     r.note(l < 8 ? lname[l] : "layerN", nextb.fresh());
   }
   Act out;
   out.p = pcm_out; out.rows = s->last.n; out.C = 1; out.ld = 1; out.dtype = KK_F32;
   KK_TRY(r.conv(m->final_conv, s->last.all(), out, 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
-  if (!r.dry) {
+  if (!r.dry && s->rows_mode) {  // active rows: every buffer's carry and the position, one launch (the host mirror is the caller's)
+    hipLaunchKernelGGL(state_shift_rows_kernel, dim3(s->ntable, B), dim3(256), 0, r.st, s->table_dev, F, s->active_dev, s->pos_dev, F * us);
+    KK_CHECK_LAUNCH();
+  } else if (!r.dry) {
     KK_TRY(state_shift(s->last, B, r.st));
     s->pos += F * us;
     s->frames += F;
@@ -1270,10 +1336,13 @@ extern "C" void kk_mimi_stream_destroy(kk_mimi_stream* s) {
   if (!s) return;
   for (float* p : {s->pool, s->kc, s->vc, s->rope})
     if (p) (void)hipFree(p);
+  for (void* p : {(void*)s->pos_dev, (void*)s->active_dev, (void*)s->table_dev})
+    if (p) (void)hipFree(p);
   delete s;
 }
 extern "C" int kk_mimi_stream_reset(kk_mimi_stream* s) {  // MimiStreamingDecoder.reset / Mimi.reset_state (mimi.py:131-137,274-279)
   if (!s) return kk_fail("kk_mimi_stream_reset: null stream");
+  if (s->rows_mode) return kk_fail("kk_mimi_stream_reset: a row-mode stream is reset row by row (kk_mimi_stream_reset_row)");
   s->frames = s->pos = 0;
   s->B = 0;
   s->fresh = true;  // the state buffers are zeroed on the next step's stream
@@ -1285,6 +1354,8 @@ extern "C" int kk_mimi_stream_chunk_frames(const kk_mimi_stream* s) { return s ?
 extern "C" int kk_mimi_stream_set_context(kk_mimi_stream* s, int context) {
   if (!s || context < 0) return kk_fail("kk_mimi_stream_set_context: bad argument");
   if (s->frames != 0) return kk_fail("kk_mimi_stream_set_context: only on a fresh or reset stream");
+  for (int f : s->row_frames)
+    if (f != 0) return kk_fail("kk_mimi_stream_set_context: only while every row of a row-mode stream is fresh or reset");
   s->context = context;
   return 0;
 }
@@ -1302,6 +1373,7 @@ extern "C" size_t kk_mimi_stream_workspace_bytes(kk_mimi_stream* s, int B) {
 static int step_check(kk_mimi_stream* s, bool encoder, int B, const void* in, void* workspace, size_t workspace_bytes, void* out, const char* who) {
   if (!s || !in || !workspace || !out || B < 1 || B > s->max_batch) return kk_failf("%s: bad argument", who);
   if (s->encoder != encoder) return kk_failf("%s: the stream was created for the other direction", who);
+  if (s->rows_mode) return kk_failf("%s: a row-mode stream is stepped with kk_mimi_decode_step_rows", who);
   if (s->frames > 0 && B != s->B) return kk_failf("%s: the batch size of a stream is fixed until it is reset", who);
   if (workspace_bytes < kk_mimi_stream_workspace_bytes(s, B)) return kk_failf("%s: workspace too small", who);
   return 0;
@@ -1324,6 +1396,125 @@ extern "C" int kk_mimi_encode_step(kk_mimi_stream* s, void* stream, int B, const
   Run r(s->m, (hipStream_t)stream, B, workspace, workspace_bytes);
   r.adt = KK_F32;
   return run_encode_step(r, s, pcm, codes_out);
+}
+
+// ---- row mode (ABI minor 5): a decode stream in which every row has its own position and lifetime, for a codec that rides along with a
+// continuously batched generator (csm_serve.CSMBatcher).  Every bound is checked here, on the host mirror, before any launch.
+extern "C" int kk_mimi_stream_create_rows(kk_mimi* m, int max_batch, int max_frames, int max_chunk, kk_mimi_stream** out) {
+  const char* who = "kk_mimi_stream_create_rows";
+  if (max_batch > 64) return kk_failf("%s: at most 64 rows (the active mask of a step is one 64-bit launch argument)", who);
+  kk_mimi_stream* s = nullptr;
+  KK_TRY(stream_create(m, false, max_batch, max_frames, max_chunk, &s, who));
+  std::vector<RowBuf> tab;
+  auto add = [&](const StateBuf& b, int npf) {
+    if (b.S > 0) tab.push_back(RowBuf{b.p, b.S, npf, b.C, b.pitch()});
+  };
+  bool fits = true;
+  auto chk = [&](const StateBuf& b) { fits = fits && b.S * b.C <= 256 * SHIFT_PER_THREAD; };
+  const kk_mimi_config& c = m->cfg;
+  int npf = c.upsample_stride;
+  add(s->resample, 1); chk(s->resample);
+  add(s->first, npf); chk(s->first);
+  for (int l = 0; l < c.n_ratios; ++l) {
+    add(s->up[l], npf); chk(s->up[l]);
+    npf *= m->sea[l].ratio;
+    add(s->blk[l], npf); chk(s->blk[l]);
+  }
+  add(s->last, npf); chk(s->last);
+  s->ntable = (int)tab.size();
+  s->rows_mode = true;
+  s->fresh = false;  // (the pool is zeroed here, once; afterwards rows are reset one by one)
+  s->B = max_batch;
+  s->row_frames.assign(max_batch, 0);
+  if (!fits || tab.empty()) {
+    kk_mimi_stream_destroy(s);
+    return kk_failf("%s: carried state larger than the shift kernel takes", who);
+  }
+  if (hipMalloc((void**)&s->pos_dev, (size_t)max_batch * 4) != hipSuccess || hipMalloc((void**)&s->active_dev, (size_t)max_batch * 4) != hipSuccess ||
+      hipMalloc((void**)&s->table_dev, tab.size() * sizeof(RowBuf)) != hipSuccess ||
+      hipMemset(s->pos_dev, 0, (size_t)max_batch * 4) != hipSuccess || hipMemset(s->active_dev, 0, (size_t)max_batch * 4) != hipSuccess ||
+      hipMemset(s->pool, 0, s->pool_floats * 4) != hipSuccess ||
+      hipMemcpy(s->table_dev, tab.data(), tab.size() * sizeof(RowBuf), hipMemcpyHostToDevice) != hipSuccess ||
+      hipDeviceSynchronize() != hipSuccess) {  // (the zeroes are in place before a step on any stream)
+    kk_mimi_stream_destroy(s);
+    return kk_failf("%s: hipMalloc failed", who);
+  }
+  *out = s;
+  return 0;
+}
+// the row starts over: zero carried rows in every state buffer, position 0.  One launch in stream order; no other row's bytes are touched.
+extern "C" int kk_mimi_stream_reset_row(kk_mimi_stream* s, void* stream, int row) {
+  if (!s || !s->rows_mode) return kk_fail("kk_mimi_stream_reset_row: not a row-mode stream (kk_mimi_stream_create_rows)");
+  if (row < 0 || row >= s->max_batch) return kk_fail("kk_mimi_stream_reset_row: row out of range");
+  hipLaunchKernelGGL(state_reset_row_kernel, dim3(s->ntable), dim3(256), 0, (hipStream_t)stream, s->table_dev, row, s->pos_dev);
+  KK_CHECK_LAUNCH();
+  s->row_frames[row] = 0;
+  return 0;
+}
+extern "C" int kk_mimi_stream_row_frames(const kk_mimi_stream* s, int row) {
+  return (s && s->rows_mode && row >= 0 && row < s->max_batch) ? s->row_frames[row] : -1;
+}
+// F code frames for every row: codes [max_batch][nq][F] int32 (device), active [max_batch] (HOST: != 0 = the row advances) ->
+// pcm [max_batch][F * samples_per_frame].  All rows ride through the step (fixed launch shapes); only active rows append K / V, carry
+// their state and advance.  An inactive row's carried state, its K / V below its position and its position are bit-unchanged; its pcm is
+// finite and means nothing; its code entries may hold anything (the code-book gather clamps every id into [0, bins)).
+extern "C" int kk_mimi_decode_step_rows(kk_mimi_stream* s, void* stream, int F, const int32_t* codes, const int32_t* active, void* workspace,
+                                        size_t workspace_bytes, float* pcm_out) {
+  const char* who = "kk_mimi_decode_step_rows";
+  if (!s || !s->rows_mode) return kk_failf("%s: not a row-mode stream (kk_mimi_stream_create_rows)", who);
+  if (!codes || !active || !workspace || !pcm_out) return kk_failf("%s: bad argument", who);
+  if (F < 1 || F > s->max_chunk) return kk_failf("%s: %d frames per step, the stream takes 1 .. %d", who, F, s->max_chunk);
+  const int max_frames = s->max_pos / s->m->cfg.upsample_stride;
+  unsigned long long mask = 0;
+  for (int b = 0; b < s->max_batch; ++b) {
+    if (!active[b]) continue;
+    if (s->row_frames[b] + F > max_frames)
+      return kk_failf("%s: row %d would hold %d frames, the stream was created for %d (kk_mimi_stream_create_rows)", who, b, s->row_frames[b] + F, max_frames);
+    mask |= 1ull << b;
+  }
+  if (workspace_bytes < kk_mimi_stream_workspace_bytes(s, s->max_batch)) return kk_failf("%s: workspace too small", who);
+  stream_set_rows(s, F);
+  { std::lock_guard<std::mutex> lk(s->m->dbg_mu); s->m->dbg.map.clear(); }
+  hipLaunchKernelGGL(set_active_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, s->active_dev, mask, s->max_batch);
+  KK_CHECK_LAUNCH();
+  Run r(s->m, (hipStream_t)stream, s->max_batch, workspace, workspace_bytes);
+  r.adt = KK_F32;
+  KK_TRY(run_decode_step(r, s, codes, pcm_out));
+  for (int b = 0; b < s->max_batch; ++b)
+    if (active[b]) s->row_frames[b] += F;
+  return 0;
+}
+// tests: one row's device state as the library holds it -- position (transformer rows), then the carried rows of every state buffer in
+// table order, then per layer its K and its V below the position.  dst == nullptr: only *floats_out.  Synchronises `stream`.
+extern "C" int kk_mimi_stream_row_snapshot(kk_mimi_stream* s, void* stream, int row, int32_t* pos_out, float* dst, size_t dst_floats, size_t* floats_out) {
+  const char* who = "kk_mimi_stream_row_snapshot";
+  if (!s || !s->rows_mode || row < 0 || row >= s->max_batch || !pos_out || !floats_out) return kk_failf("%s: bad argument", who);
+  hipStream_t st = (hipStream_t)stream;
+  int pos = 0;
+  std::vector<RowBuf> tab(s->ntable);
+  if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(&pos, s->pos_dev + row, 4, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(tab.data(), s->table_dev, tab.size() * sizeof(RowBuf), hipMemcpyDeviceToHost) != hipSuccess)
+    return kk_failf("%s: copy failed", who);
+  if (pos < 0 || pos > s->max_pos) return kk_failf("%s: the device position %d is outside the cache", who, pos);
+  const size_t D = s->m->cfg.dim, nl = s->m->layers.size();
+  size_t need = 2 * nl * (size_t)pos * D;
+  for (const RowBuf& t : tab) need += (size_t)t.S * t.C;
+  *pos_out = pos;
+  *floats_out = need;
+  if (!dst) return 0;
+  if (dst_floats < need) return kk_failf("%s: destination too small", who);
+  size_t off = 0;
+  for (const RowBuf& t : tab) {
+    if (hipMemcpy(dst + off, t.p + (long long)row * t.pitch, (size_t)t.S * t.C * 4, hipMemcpyDeviceToHost) != hipSuccess) return kk_failf("%s: copy failed", who);
+    off += (size_t)t.S * t.C;
+  }
+  for (size_t l = 0; l < nl && pos > 0; ++l)
+    for (float* base : {s->kc, s->vc}) {
+      const float* src = base + ((l * s->max_batch + row) * (size_t)s->max_pos) * D;
+      if (hipMemcpy(dst + off, src, (size_t)pos * D * 4, hipMemcpyDeviceToHost) != hipSuccess) return kk_failf("%s: copy failed", who);
+      off += (size_t)pos * D;
+    }
+  return 0;
 }
 
 extern "C" int kk_mimi_encode_frames(const kk_mimi* m, int N) { return (m && N > 0) ? mimi_encode_frames(m->cfg, N) : 0; }

@@ -1,7 +1,7 @@
 """Host mirror of the reference's Mimi codec surface for the DECODE path (mlx_audio/codec/models/mimi/mimi.py): `mimi_202407`,
 `Mimi(cfg)`, `Mimi.decode(codes)`, `.sample_rate`, `.frame_rate`.  The arithmetic runs in libkokoro_hip.so (kk_mimi_*, csrc/kk_mimi.hip);
-PyTorch allocates device memory and provides the stream.  `Mimi.encode` (mimi.py:138-145) runs on the fp32 kernels; the streaming
-`*_step` entry points are not built."""
+PyTorch allocates device memory and provides the stream.  `Mimi.encode` (mimi.py:138-145) and the streaming `*_step` entry points run on
+the fp32 kernels; `Mimi.row_decoder` is the streaming decoder with one position per row (for a continuously batched generator)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -231,6 +231,13 @@ class Mimi:
                                                C.c_void_p(codes.data_ptr())), "kk_mimi_encode_step")
         return codes
 
+    def row_decoder(self, max_batch: int, max_frames: int = 2048, max_chunk: int = 1) -> "MimiRowDecoder":
+        """A streaming decoder whose rows each have their own position and lifetime (kk_mimi_stream_create_rows): a row can be restarted
+        or sit out a step while the others go on.  It owns its stream and workspace; the "dec" slot of decode_step is not involved."""
+        if not self._final:
+            raise KokoroHipError("Mimi.row_decoder: load_weights first")
+        return MimiRowDecoder(self, max_batch, max_frames, max_chunk)
+
     def reset_stream(self) -> None:
         """Mimi.reset_state (mimi.py:131-137): both directions start over."""
         for st in self._streams.values():
@@ -271,3 +278,92 @@ class MimiStreamingDecoder:
         if tokens.ndim == 2:
             tokens = tokens[None]
         return torch.cat([self._mimi.decode_step(tokens[:, :, t : t + 1]) for t in range(tokens.shape[-1])], dim=-1)
+
+
+class MimiRowDecoder:
+    """`Mimi.row_decoder(...)`: decode_step for a batch whose rows start, pause and end on their own.  `step(codes, active)` carries F frames
+    for all `max_batch` rows; only rows with active[b] advance, the others keep their state, cache and position bit for bit.  An active
+    row's pcm equals, bit for bit, a batch-1 `Mimi.decode_step` stream fed the same codes in the same step sizes."""
+
+    def __init__(self, mimi: Mimi, max_batch: int, max_frames: int, max_chunk: int):
+        self._mimi, self.lib, self.device = mimi, mimi.lib, mimi.device  # (keeps the codec alive)
+        self.max_batch, self.max_frames, self.max_chunk = int(max_batch), int(max_frames), int(max_chunk)
+        self._h = None
+        with torch.cuda.device(self.device):
+            h = C.c_void_p()
+            check(self.lib.kk_mimi_stream_create_rows(mimi._h, self.max_batch, self.max_frames, self.max_chunk, C.byref(h)), "kk_mimi_stream_create_rows")
+            self._h = h
+            need = int(self.lib.kk_mimi_stream_workspace_bytes(h, self.max_batch))
+            if need == 0:
+                self.close()
+                raise KokoroHipError("kk_mimi_stream_workspace_bytes failed")
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self.spf = int(self.lib.kk_mimi_samples_per_frame(mimi._h))
+
+    def _handle(self):
+        if self._h is None:
+            raise KokoroHipError("MimiRowDecoder is closed")
+        return self._h
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def reset_row(self, row: int) -> None:
+        """The row starts a new stream at its next active step (zero carried state, position 0); the other rows are not touched."""
+        with torch.cuda.device(self.device):
+            check(self.lib.kk_mimi_stream_reset_row(self._handle(), self._stream(), int(row)), "kk_mimi_stream_reset_row")
+
+    def row_frames(self, row: int) -> int:
+        n = int(self.lib.kk_mimi_stream_row_frames(self._handle(), int(row)))
+        if n < 0:
+            raise ValueError(f"row {row} is outside [0, {self.max_batch})")
+        return n
+
+    def set_context(self, context: int) -> None:
+        """TransformerConfig.context (default 250) for every row; only while all rows are fresh or reset."""
+        check(self.lib.kk_mimi_stream_set_context(self._handle(), int(context)), "kk_mimi_stream_set_context")
+
+    def step(self, codes, active) -> torch.Tensor:
+        """codes [max_batch, nq, F] (F <= max_chunk), active [max_batch] (host booleans) -> pcm [max_batch, 1, F * samples_per_frame].
+        Entries of inactive rows may hold anything; their pcm is finite and meaningless.  A row that would pass max_frames, a bad F or a
+        bad shape is refused before anything is launched."""
+        h = self._handle()
+        codes = torch.as_tensor(codes).to(device=self.device, dtype=torch.int32)
+        nq = self._mimi.cfg.nq
+        if codes.ndim != 3 or codes.shape[0] != self.max_batch or codes.shape[1] != nq or codes.shape[2] < 1:
+            raise ValueError(f"codes must be [{self.max_batch}, {nq}, F >= 1], got {tuple(codes.shape)}")
+        act = np.ascontiguousarray(np.asarray(active).astype(bool).astype(np.int32))
+        if act.shape != (self.max_batch,):
+            raise ValueError(f"active must hold {self.max_batch} flags, got shape {act.shape}")
+        F = int(codes.shape[2])
+        codes = codes.contiguous()
+        with torch.cuda.device(self.device):
+            pcm = torch.empty((self.max_batch, 1, self.spf * F), dtype=torch.float32, device=self.device)
+            self._mimi._last_B = self.max_batch
+            check(self.lib.kk_mimi_decode_step_rows(h, self._stream(), F, C.c_void_p(codes.data_ptr()), act.ctypes.data_as(C.c_void_p),
+                                                    C.c_void_p(self._ws.data_ptr()), self._ws.numel(), C.c_void_p(pcm.data_ptr())),
+                  "kk_mimi_decode_step_rows")
+        return pcm
+
+    def snapshot(self, row: int):
+        """(position in transformer rows, float32 array: the row's carried state and its K / V below the position) -- what an inactive
+        step must leave unchanged.  Synchronises."""
+        h = self._handle()
+        pos, n = C.c_int32(0), C.c_size_t(0)
+        with torch.cuda.device(self.device):
+            check(self.lib.kk_mimi_stream_row_snapshot(h, self._stream(), int(row), C.byref(pos), None, 0, C.byref(n)), "kk_mimi_stream_row_snapshot")
+            buf = np.empty(n.value, np.float32)
+            check(self.lib.kk_mimi_stream_row_snapshot(h, self._stream(), int(row), C.byref(pos), buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(n)),
+                  "kk_mimi_stream_row_snapshot")
+        return int(pos.value), buf
+
+    def close(self) -> None:
+        if self._h is not None:
+            self.lib.kk_mimi_stream_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -9,7 +9,11 @@ cost of an admission and of a cache shift (a second, profiled continuous run: on
 that the session passes the end of the cache and down-shifts happen.
 --prefix N: instead, the same stream lengths with every request's prompt = one shared N-frame voice prefix (text + audio + EOS frames) followed by
 its own 16-48 text frames, continuous batching only, admitted plain (the whole prompt per request) / on the prefix (`submit(prefix=)`) / plain
-again; per run wall, audio-s/s, frame steps and (a second, profiled run) the mean admission ms.  Written to profiles/csm_serve_prefix_bench.json."""
+again; per run wall, audio-s/s, frame steps and (a second, profiled run) the mean admission ms.  Written to profiles/csm_serve_prefix_bench.json.
+--stream-chunk N: instead, continuous batching WITH the codec (synthetic mimi_202407 weights), the same workload twice: plain `submit` (one
+offline Mimi.decode per finished stream; time to first audio = submit -> result) and `submit_stream` in chunks of N frames (time to first
+audio = submit -> first chunk); p50 / p95 of both over the requests, audio-s/s of both, and the cost of one row-mode decode step at --batch rows
+against a Mimi.decode_step of the same batch and F.  Written to profiles/csm_serve_stream_bench.json."""
 import argparse
 import json
 import os
@@ -35,13 +39,21 @@ ap.add_argument("--weights", default="bfloat16", choices=["float32", "bfloat16"]
 ap.add_argument("--max-seq-len", type=int, default=512)
 ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--prefix", type=int, default=0, help="frames of a voice prefix shared by every request (0: the static / continuous comparison)")
+ap.add_argument("--stream-chunk", type=int, default=0, help="frames per audio chunk: time to first audio of submit_stream against plain submit")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 if a.out is None:
-    a.out = os.path.join(ROOT, "profiles", "csm_serve_prefix_bench.json" if a.prefix else "csm_serve_bench.json")
+    name = "csm_serve_stream_bench.json" if a.stream_chunk else "csm_serve_prefix_bench.json" if a.prefix else "csm_serve_bench.json"
+    a.out = os.path.join(ROOT, "profiles", name)
 
 cfg = dict(P.csm_config(), max_seq_len=a.max_seq_len)
-loop = Model(cfg, weights=P.csm_synth_checkpoint(cfg, 0), weight_dtype=a.weights)
+mimi = None
+if a.stream_chunk:
+    from mlx_audio_amd.mimi import Mimi, MimiConfig
+
+    mcfg = P.mimi_config(cfg["audio_num_codebooks"])
+    mimi = Mimi(MimiConfig.from_dict(mcfg), P.mimi_synth_checkpoint(mcfg, 0))
+loop = Model(cfg, mimi=mimi, weights=P.csm_synth_checkpoint(cfg, 0), weight_dtype=a.weights)
 n, B = cfg["audio_num_codebooks"], a.batch
 rng = np.random.default_rng(a.seed)
 plen = rng.choice(PROMPTS, a.requests).tolist()
@@ -136,6 +148,71 @@ def bench_prefix():
     res["value_is"] = "prefixed / plain mean admission ms (plain: mean of the two runs; their spread %.3f ms)" % abs(plain[0] - plain[1])
     return res
 
+
+def bench_stream():
+    N = a.stream_chunk
+
+    def pct(v, q):
+        return float(np.percentile(np.asarray(v, np.float64), q))
+
+    def run(streamed):
+        bat = loop.serve(max_batch=B, rng="device", sampler=sampler, seed=a.seed, stop_on_eos=False, stream_chunk_frames=N if streamed else None,
+                         stream_max_frames=max(LENGTHS))
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        fn = bat.submit_stream if streamed else bat.submit
+        hs = [fn(None, None, prompt=prompts[i], max_audio_length_ms=80 * flen[i]) for i in range(a.requests)]
+        bat.run_until_idle()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t
+        res = [h.result(timeout=0) for h in hs]
+        assert [r.frames for r in res] == flen
+        first = [h.first_audio_seconds for h in hs] if streamed else [r.processing_time_seconds for r in res]
+        st = dict(bat.stats)
+        bat.close()
+        return {"wall_s": dt, "xrt": audio_s / dt, "first_audio_s_p50": pct(first, 50), "first_audio_s_p95": pct(first, 95), "frame_steps": st["frames"],
+                "polls": st["polls"], "chunks": st.get("chunks", 0), "chunk_rounds": st.get("chunk_rounds", 0)}
+
+    def step_ms(fn, reps=40):
+        fn()
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t) / reps
+
+    run(False), run(True)  # warm-up: kernel loading, workspaces, graph capture
+    res = {"metric": "CSM-1B serving with the codec: time to first audio, plain submit vs submit_stream, " + a.weights, "requests": a.requests, "batch": B,
+           "max_seq_len": a.max_seq_len, "chunk_frames": N, "stream_frames": flen, "audio_s": audio_s, "order": ["plain_first", "streamed", "plain_last"],
+           "note": "all requests are queued at time 0, so a request's time to first audio includes its wait for a row",
+           "data": "synthetic (random-init CSM-1B and mimi_202407 weights, random text prompts, imposed stream lengths, device uniforms)"}
+    res["plain_first"], res["streamed"], res["plain_last"] = run(False), run(True), run(False)
+    codes = torch.randint(0, 2048, (B, n, N), dtype=torch.int32, device="cuda")
+    dec = mimi.row_decoder(B, 64 * N, N)
+    rows_ms = step_ms(lambda: dec.step(codes, [True] * B))  # (41 steps of N frames: inside the 64 N the decoder was made for)
+    dec.close()
+    mimi.close_stream()
+    solo_ms = step_ms(lambda: mimi.decode_step(codes, max_frames=64 * N))
+    mimi.close_stream()
+    res["decode_step_ms"] = {"rows_mode": rows_ms, "decode_step": solo_ms, "batch": B, "frames": N}
+    plain = 0.5 * (res["plain_first"]["xrt"] + res["plain_last"]["xrt"])
+    res["value"] = res["streamed"]["first_audio_s_p50"] / (0.5 * (res["plain_first"]["first_audio_s_p50"] + res["plain_last"]["first_audio_s_p50"]))
+    res["value_is"] = "streamed / plain p50 time to first audio; audio-s/s streamed / plain = %.3f (plain runs differ by %.3f xRT)" % (
+        res["streamed"]["xrt"] / plain, abs(res["plain_first"]["xrt"] - res["plain_last"]["xrt"]))
+    return res
+
+
+if a.stream_chunk:
+    if a.prefix or not 1 <= a.stream_chunk <= min(LENGTHS):
+        sys.exit(f"--stream-chunk must be in [1, {min(LENGTHS)}] and excludes --prefix")
+    out = bench_stream()
+    print(json.dumps(out))
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    sys.exit(0)
 
 if a.prefix:
     if not 8 <= a.prefix < a.max_seq_len - 48 - max(LENGTHS):
