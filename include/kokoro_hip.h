@@ -30,12 +30,13 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 5   /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 6   /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
                             5: row-mode streaming Mimi decode (kk_mimi_stream_create_rows, kk_mimi_stream_reset_row, kk_mimi_decode_step_rows,
-                               kk_mimi_stream_row_frames, kk_mimi_stream_row_snapshot) */
+                               kk_mimi_stream_row_frames, kk_mimi_stream_row_snapshot);
+                            6: per-row sampler settings of a CSM batch (kk_csm_set_row_sampler, kk_csm_generate_frame_rows, kk_op_csm_sample_rows) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -397,6 +398,21 @@ typedef struct kk_csm_sampler {
  * when it changes, so a new seed replays the same graph; every other sampler field and the stream_ids pointer key the graph. */
 int kk_csm_generate_frame_ex(kk_csm* m, void* stream, int B, int S, const int32_t* tokens, const float* tokens_mask, const kk_csm_sampler* sampler,
                              const float* uniforms, const int32_t* stream_ids, void* workspace, size_t workspace_bytes, int32_t* codes_out);
+/* Per-row sampler settings: a device table with one 32-byte entry per cache row, {temperature, top_k, top_p, min_p, min_tokens_to_keep, pad, seed},
+ * read by the sampling kernel of the row's workgroup instead of launch arguments.  kk_csm_setup_caches and kk_csm_reset_caches_parked zero it; a
+ * zero entry has temperature 0: arg-max, so a parked or never-set row still yields codes in [0, V).
+ *   kk_csm_set_row_sampler: validates the sampler (the rule of every entry above) and the row on the host, then writes the entry in stream order
+ *     (the values travel as launch arguments: `sampler` need not outlive the call).  `seed` is stored and read only by launches that draw on the
+ *     device; use_device_rng is a property of the frame call, not of the entry.
+ *   kk_csm_generate_frame_rows: kk_csm_generate_frame_ex with the sampler of item b read from table row b -- the same launches, and row b's codes
+ *     are, bit for bit, those of the launch-argument kernels with the entry's values.  Any S the _ex call accepts.  uniforms [B][n_cb] have priority;
+ *     without them and with use_device_rng each row draws Philox on ITS entry's seed (stream id, position and code book as before); without either,
+ *     arg-max.  Graph mode: the captured step is keyed by this mode, B, the pointers and the uniform source, never by what the table holds -- a
+ *     kk_csm_set_row_sampler between two replays takes effect in the next replay without a new capture.
+ * kk_csm_admit / kk_csm_admit_prefixed are unchanged: they take the request's sampler for their B = 1 block. */
+int kk_csm_set_row_sampler(kk_csm* m, void* stream, int row, const kk_csm_sampler* sampler);
+int kk_csm_generate_frame_rows(kk_csm* m, void* stream, int B, int S, const int32_t* tokens, const float* tokens_mask, int use_device_rng,
+                               const float* uniforms, const int32_t* stream_ids, void* workspace, size_t workspace_bytes, int32_t* codes_out);
 /* Continuous batching: streams enter and leave a RUNNING batch (after kk_csm_setup_caches(max_batch); none of these changes what the entries
  * above do).  All rows share the slot counter P (kk_csm_position); row b's tokens live in slots [pad[b], P) at position slot - pad[b].
  *   kk_csm_park_row: the row is retired -- pad[row] = max_seq_len.  From the next frame on its attention sees no key (zero output) and appends
@@ -465,6 +481,11 @@ int kk_op_csm_sample(void* stream, int B, int V, const float* logits, float temp
  * (sampler->seed, stream_ids[b] or b, pos[b] or 0, code book 0); stream_ids / pos: device int32 [B] or NULL.  Synchronises when it draws on the device. */
 int kk_op_csm_sample_ex(void* stream, int B, int V, const float* logits, const kk_csm_sampler* sampler, const float* uniforms, const int32_t* stream_ids,
                         const int32_t* pos, int32_t* codes_out);
+/* kk_op_csm_sample_ex with one sampler PER ROW (samplers: HOST array [B]) through the launcher kk_csm_generate_frame_rows uses: a temporary device
+ * table is uploaded, one launch serves all rows, then it synchronises and frees the table.  Row b's pick is that of kk_op_csm_sample_ex on row b alone
+ * with samplers[b].  use_device_rng must agree across the entries (it is a property of the launch); each row draws on its own seed. */
+int kk_op_csm_sample_rows(void* stream, int B, int V, const float* logits, const kk_csm_sampler* samplers, const float* uniforms,
+                          const int32_t* stream_ids, const int32_t* pos, int32_t* codes_out);
 /* the uniforms the sampling kernels draw: out [B][n_cb] (device) for (seed, stream_ids[b] or b, pos[b] or 0, code book 0..n_cb-1).  Synchronises. */
 int kk_op_csm_uniforms(void* stream, int B, int n_cb, uint64_t seed, const int32_t* stream_ids, const int32_t* pos, float* out);
 /* The kernels of the frame step on their own (tests), each through the launcher the frame runs.  Fragment pack of the bf16 weights (host):

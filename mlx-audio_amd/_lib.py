@@ -109,6 +109,8 @@ SIGNATURES = {
     "kk_csm_workspace_bytes": (_sz, [_vp, _i, _i]),
     "kk_csm_generate_frame": (_i, [_vp, _vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _sz, _vp]),
     "kk_csm_generate_frame_ex": (_i, [_vp, _vp, _i, _i, _vp, _vp, C.POINTER(KKCsmSampler), _vp, _vp, _vp, _sz, _vp]),
+    "kk_csm_set_row_sampler": (_i, [_vp, _vp, _i, C.POINTER(KKCsmSampler)]),
+    "kk_csm_generate_frame_rows": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "kk_csm_admit": (_i, [_vp, _vp, _i, _i, _vp, _vp, C.POINTER(KKCsmSampler), _vp, C.c_int32, _vp, _sz, _vp]),
     "kk_csm_prefix_create": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _sz, C.POINTER(_vp)]),
     "kk_csm_prefix_length": (_i, [_vp]),
@@ -125,6 +127,7 @@ SIGNATURES = {
     "kk_csm_debug_timestamps": (_i, [_vp, _i]),
     "kk_op_csm_sample": (_i, [_vp, _i, _i, _vp, _f, _i, _vp, _vp]),
     "kk_op_csm_sample_ex": (_i, [_vp, _i, _i, _vp, C.POINTER(KKCsmSampler), _vp, _vp, _vp, _vp]),
+    "kk_op_csm_sample_rows": (_i, [_vp, _i, _i, _vp, C.POINTER(KKCsmSampler), _vp, _vp, _vp, _vp]),
     "kk_op_csm_uniforms": (_i, [_vp, _i, _i, _u64, _vp, _vp, _vp]),
     "kk_csm_frag_choice": (_i, [_i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "kk_csm_frag_pack": (_i, [_vp, _i, _i, _i, _vp]),
@@ -210,7 +213,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 5:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 6:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

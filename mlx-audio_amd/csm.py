@@ -22,6 +22,12 @@ def _llama_args(d: dict) -> _lib.KKLlamaArgs:
     return a
 
 
+def _sampler_struct(sampler) -> _lib.KKCsmSampler:
+    """kk_csm_sampler of anything with temp / top_k (and optionally top_p / min_p / min_tokens_to_keep), e.g. sesame.Sampler; no seed, no device RNG"""
+    return _lib.KKCsmSampler(float(sampler.temp), int(sampler.top_k), float(getattr(sampler, "top_p", 0.0)), float(getattr(sampler, "min_p", 0.0)),
+                             int(getattr(sampler, "min_tokens_to_keep", 1)), 0, 0)
+
+
 class Prefix:
     """kk_csm_prefix: the backbone K / V of a prompt's first `length` frames on the device, immutable, shared by every stream admitted on top of
     it (`SesameModel.admit(..., prefix=)`).  Usable from the generator it was made on and from its `share()`s.  Freed by `close()` / on collection."""
@@ -212,12 +218,15 @@ class SesameModel:
 
     # ---- sesame.py:349-395
     def generate_frame(self, tokens, tokens_mask, input_pos=None, temperature: float = 0.0, top_k: int = 50, uniforms=None, sampler=None,
-                       seed: Optional[int] = None, stream_ids=None) -> torch.Tensor:
+                       seed: Optional[int] = None, stream_ids=None, device_rng: bool = False) -> torch.Tensor:
         """tokens [B, S, n_cb+1] int, tokens_mask same shape; `input_pos` (the reference's argument) is checked against the cache position.
         `sampler` (anything with temp / top_k / top_p / min_p / min_tokens_to_keep, e.g. sesame.Sampler) replaces `temperature` / `top_k` and
         brings the top-p / min-p filters (the rule: kk_csm_sampler in kokoro_hip.h).  `uniforms` [B, n_cb] are the injected draws; without them
         and with `seed`, the kernels draw from Philox on (seed, stream id, position, code book) -- `stream_ids` [B] int, default the batch
-        index.  Neither: arg-max.  Returns codes [B, n_cb] int32 on the device."""
+        index.  Neither: arg-max.  Returns codes [B, n_cb] int32 on the device.
+        `sampler="rows"` (kk_csm_generate_frame_rows): item b samples with the settings `set_row_sampler(b, ...)` stored for cache row b -- one
+        launch per code book whatever the mix, and a replayed graph that never re-captures when a row's settings change.  `temperature`, `top_k`
+        and `seed` are not read then: with `device_rng=True` (and no `uniforms`) every row draws on the seed of ITS entry."""
         assert self.caches_are_enabled(), "backbone caches are not enabled"
         tokens = torch.as_tensor(tokens).to(device=self.device, dtype=torch.int32).contiguous()
         mask = torch.as_tensor(tokens_mask).to(device=self.device, dtype=torch.float32).contiguous()
@@ -234,13 +243,20 @@ class SesameModel:
             u = torch.as_tensor(uniforms).to(device=self.device, dtype=torch.float32).contiguous()
             if tuple(u.shape) != (B, ncb):
                 raise ValueError(f"uniforms must be [B, {ncb}]")
+        rows = isinstance(sampler, str)
+        if rows and sampler != "rows":
+            raise ValueError('sampler must be a sampler object or "rows"')
+        if rows and seed is not None:
+            raise ValueError('sampler="rows": the seeds are those of set_row_sampler; pass device_rng=True to draw on them')
+        if device_rng and not rows:
+            raise ValueError('device_rng belongs to sampler="rows"; pass `seed` otherwise')
         sp = _lib.KKCsmSampler(float(temperature), int(top_k), 0.0, 0.0, 1, 0, 0)
-        if sampler is not None:
-            sp = _lib.KKCsmSampler(float(sampler.temp), int(sampler.top_k), float(getattr(sampler, "top_p", 0.0)), float(getattr(sampler, "min_p", 0.0)),
-                                   int(getattr(sampler, "min_tokens_to_keep", 1)), 0, 0)
+        if sampler is not None and not rows:
+            sp = _sampler_struct(sampler)
         sid = None
-        if u is None and seed is not None:
-            sp.seed, sp.use_device_rng = int(seed) & 0xFFFFFFFFFFFFFFFF, 1
+        if u is None and (seed is not None or (rows and device_rng)):
+            if not rows:
+                sp.seed, sp.use_device_rng = int(seed) & 0xFFFFFFFFFFFFFFFF, 1
             if stream_ids is not None:
                 sid = self._sid.get(B)  # one persistent buffer per batch size: a replayed graph reads it through the same pointer
                 if sid is None:
@@ -268,12 +284,34 @@ class SesameModel:
             if self._ws is None or self._ws.numel() < need:
                 self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             codes = self._gbuf[(B, u is not None)][3] if (self._graph and S == 1) else torch.empty((B, ncb), dtype=torch.int32, device=self.device)
-            check(self.lib.kk_csm_generate_frame_ex(self._h, self._stream(), B, S, C.c_void_p(tokens.data_ptr()), C.c_void_p(mask.data_ptr()),
-                                                    C.byref(sp), C.c_void_p(u.data_ptr()) if u is not None else None,
-                                                    C.c_void_p(sid.data_ptr()) if sid is not None else None,
-                                                    C.c_void_p(self._ws.data_ptr()), need, C.c_void_p(codes.data_ptr())), "kk_csm_generate_frame")
+            if rows:
+                check(self.lib.kk_csm_generate_frame_rows(self._h, self._stream(), B, S, C.c_void_p(tokens.data_ptr()), C.c_void_p(mask.data_ptr()),
+                                                          1 if device_rng else 0, C.c_void_p(u.data_ptr()) if u is not None else None,
+                                                          C.c_void_p(sid.data_ptr()) if sid is not None else None,
+                                                          C.c_void_p(self._ws.data_ptr()), need, C.c_void_p(codes.data_ptr())), "kk_csm_generate_frame_rows")
+            else:
+                check(self.lib.kk_csm_generate_frame_ex(self._h, self._stream(), B, S, C.c_void_p(tokens.data_ptr()), C.c_void_p(mask.data_ptr()),
+                                                        C.byref(sp), C.c_void_p(u.data_ptr()) if u is not None else None,
+                                                        C.c_void_p(sid.data_ptr()) if sid is not None else None,
+                                                        C.c_void_p(self._ws.data_ptr()), need, C.c_void_p(codes.data_ptr())), "kk_csm_generate_frame")
         self._last_B = B
         return codes
+
+    def set_row_sampler(self, row: int, sampler, seed: Optional[int] = None) -> None:
+        """kk_csm_set_row_sampler: cache row `row` samples with `sampler` (temp / top_k / top_p / min_p / min_tokens_to_keep) in every later
+        `generate_frame(..., sampler="rows")`, a replayed graph included; `seed` is the row's Philox seed for frames that draw on the device.
+        Written in stream order.  setup_caches and reset_caches_parked zero every entry (arg-max).  ValueError for a row out of range or a
+        sampler out of range, before anything is launched."""
+        assert self.caches_are_enabled(), "backbone caches are not enabled"
+        if not 0 <= int(row) < self.max_batch:
+            raise ValueError(f"set_row_sampler: row {row} out of range [0, {self.max_batch})")
+        sp = _sampler_struct(sampler)
+        if not (sp.temperature >= 0.0 and 0.0 <= sp.top_p <= 1.0 and 0.0 <= sp.min_p <= 1.0 and sp.min_tokens_to_keep >= 1 and sp.top_k >= -1):
+            raise ValueError("set_row_sampler: sampler out of range (temp >= 0, top_p and min_p in [0, 1], min_tokens_to_keep >= 1, top_k >= -1)")
+        if seed is not None:
+            sp.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        with torch.cuda.device(self.device):
+            check(self.lib.kk_csm_set_row_sampler(self._h, self._stream(), int(row), C.byref(sp)), "kk_csm_set_row_sampler")
 
     # ---- continuous batching (kk_csm_admit / park_row / shift_caches / row_state; DESIGN 8d-2)
     def reset_caches_parked(self) -> None:
@@ -367,8 +405,7 @@ class SesameModel:
                 raise ValueError(f"uniforms must hold {ncb} entries")
         sp = _lib.KKCsmSampler(float(temperature), int(top_k), 0.0, 0.0, 1, 0, 0)
         if sampler is not None:
-            sp = _lib.KKCsmSampler(float(sampler.temp), int(sampler.top_k), float(getattr(sampler, "top_p", 0.0)), float(getattr(sampler, "min_p", 0.0)),
-                                   int(getattr(sampler, "min_tokens_to_keep", 1)), 0, 0)
+            sp = _sampler_struct(sampler)
         if u is None and seed is not None:
             sp.seed, sp.use_device_rng = int(seed) & 0xFFFFFFFFFFFFFFFF, 1
         with torch.cuda.device(self.device):

@@ -23,7 +23,12 @@ audio arrives in chunks of N frames -- chunk k is its frames [kN, (k+1)N), the l
 bit, a batch-1 `Mimi.decode_step` stream over its codes in steps of N, ..., r.  A chunk is decoded only after an EOS poll has confirmed its
 frames (polls run every N frames then), so nothing at or after a stream's EOS frame or past its frame limit is ever emitted.  Ready chunks
 are decoded in one aligned round per poll: all rows with a full chunk in one `step(F=N)`, tails grouped by equal r.  `submit` is unchanged
-(one offline `Mimi.decode` at the end) and mixes with `submit_stream` in one batch."""
+(one offline `Mimi.decode` at the end) and mixes with `submit_stream` in one batch.
+
+A sampler per request: `CSMBatcher(..., row_samplers=True)` and `submit(..., sampler=, seed=)`.  The frame step then reads every
+row's settings from a device table (`SesameModel.set_row_sampler`, written at admission) instead of launch arguments: a greedy request, one at
+temp 0.7 / top_p 0.9 and one with a seed of its own run in ONE batch, in the same launches per frame and one captured graph whatever the mix.
+Each request still carries the bits of its own `generate_batch([prompt], sampler=its own, seed=its own)`."""
 from __future__ import annotations
 
 import queue
@@ -106,6 +111,7 @@ class _Stream:
     rng: Optional[np.random.Generator] = None
     codes: List[torch.Tensor] = field(default_factory=list)  # one [n_cb] tensor per generated frame
     audio: Optional[CSMAudioStream] = None  # submit_stream: where the chunks go
+    sampler: object = None          # row_samplers: the request's sampler (the batcher's when it gave none)
     chunks: List[torch.Tensor] = field(default_factory=list)  # the audio of the chunks emitted so far
     emitted: int = 0                # frames decoded and emitted
     confirmed: int = 0              # frames a poll has confirmed (below the EOS frame and the limit)
@@ -186,13 +192,20 @@ class ModelEngine:
         return self.csm.admit(row, prompt[0], prompt[1], sampler=sampler, uniforms=uniforms, seed=seed, stream_id=stream_id,
                               prefix=prefix.prefix if prefix is not None else None)
 
-    def frame(self, prev: torch.Tensor, sampler, uniforms, seed, stream_ids) -> torch.Tensor:
+    def set_row_sampler(self, row: int, sampler, seed) -> None:
+        """Cache row `row` samples with `sampler` (and draws on `seed` on the device) in every later `frame(sampler="rows")`."""
+        self.csm.set_row_sampler(row, sampler, seed)
+
+    def frame(self, prev: torch.Tensor, sampler, uniforms, seed, stream_ids, device_rng: bool = False) -> torch.Tensor:
+        """sampler "rows": every row's settings (and seed, with device_rng) are those of `set_row_sampler`; `seed` is not read then."""
         B, n = prev.shape
         curr = torch.zeros((B, 1, n + 1), dtype=torch.int32, device=self.device)
         curr[:, 0, :n] = prev
         mask = torch.zeros((B, 1, n + 1), dtype=torch.float32, device=self.device)
         mask[:, 0, :n] = 1
         u = torch.tensor(np.asarray(uniforms, np.float32), device=self.device) if uniforms is not None else None
+        if isinstance(sampler, str):
+            return self.csm.generate_frame(curr, mask, sampler=sampler, uniforms=u, device_rng=device_rng, stream_ids=stream_ids)
         return self.csm.generate_frame(curr, mask, sampler=sampler, uniforms=u, seed=seed, stream_ids=stream_ids)
 
     def decode(self, codes: torch.Tensor) -> torch.Tensor:
@@ -210,17 +223,31 @@ class ModelEngine:
         torch.cuda.current_stream(self.device).synchronize()
 
 
+def _check_sampler(sampler) -> None:
+    """The ranges the library accepts (kk_csm_sampler), checked where the request is made"""
+    try:
+        temp, top_k = float(sampler.temp), int(sampler.top_k)
+        top_p, min_p, keep = float(getattr(sampler, "top_p", 0.0)), float(getattr(sampler, "min_p", 0.0)), int(getattr(sampler, "min_tokens_to_keep", 1))
+    except (AttributeError, TypeError) as e:
+        raise ValueError(f"sampler must carry temp / top_k (make_sampler): {e}") from None
+    if not (temp >= 0.0 and 0.0 <= top_p <= 1.0 and 0.0 <= min_p <= 1.0 and keep >= 1 and top_k >= -1):
+        raise ValueError("sampler out of range (temp >= 0, top_p and min_p in [0, 1], min_tokens_to_keep >= 1, top_k >= -1)")
+
+
 class CSMBatcher:
     def __init__(self, model, max_batch: int = 8, eos_check_interval: int = 8, rng: str = "device", sampler=None, seed: int = 0,
                  stop_on_eos: bool = True, decode: bool = True, profile: bool = False, engine=None, stream_chunk_frames: Optional[int] = None,
-                 stream_max_frames: int = 1125):
+                 stream_max_frames: int = 1125, row_samplers: bool = False):
         """model: a loaded sesame.Model (its frame generator's caches are taken over; use `model.share()` for a generator of its own).
-        sampler: `make_sampler(...)` for every stream of the batch (default temp 0.9 / top_k 50).  seed: the device generator's seed (rng
+        sampler: `make_sampler(...)` for every stream of the batch (default temp 0.9 / top_k 50; with `row_samplers` the default of a request).  seed: the device generator's seed (rng
         "device": one seed per batcher, streams differ by their ids).  profile: time admissions and shifts (one sync each) into `stats`.
         engine: the surface of `ModelEngine`, for a scheduler without a device.
         stream_chunk_frames: N enables `submit_stream` (audio in chunks of N frames through the codec's row-mode decoder); the EOS flags are
         then polled every N frames instead of every `eos_check_interval`.  stream_max_frames: the longest streaming request (the decoder's K / V
-        cache holds that many frames per row; 1125 = the default 90 s limit of a request)."""
+        cache holds that many frames per row; 1125 = the default 90 s limit of a request).
+        row_samplers: True lets `submit` / `submit_stream` take a `sampler` (None: the batcher's) and, with rng "device", a `seed` of the
+        request's own (None: the batcher's); the frame step then reads each row's settings from the device table (`set_row_sampler`).  Off by
+        default: the frame step is the launch-argument one, and a per-request sampler or a foreign seed is refused."""
         if rng not in ("host", "device"):
             raise ValueError(f"rng must be 'host' or 'device', not {rng!r}")
         if max_batch < 1 or eos_check_interval < 1:
@@ -235,6 +262,9 @@ class CSMBatcher:
         self.max_batch, self.interval, self.rng, self.sampler, self.seed = int(max_batch), int(eos_check_interval), rng, sampler, int(seed)
         self.stop_on_eos, self.decode, self.profile = bool(stop_on_eos), bool(decode), bool(profile)
         self._sampled = float(sampler.temp) > 0
+        self.row_samplers = bool(row_samplers)
+        if self.row_samplers:
+            _check_sampler(sampler)
         self._lock = threading.Lock()          # queue, closed flag, stream id counter
         self._wake = threading.Condition(self._lock)
         self._queue: Deque[_Stream] = deque()
@@ -260,7 +290,7 @@ class CSMBatcher:
 
     # ---- requests ---------------------------------------------------------------------------------------------------------------------
     def submit(self, context=None, text=None, speaker: int = 0, voice_match: Optional[bool] = None, max_audio_length_ms: float = 90_000,
-               seed: Optional[int] = None, stream_id: Optional[int] = None, prompt=None, prefix=None) -> Future:
+               seed: Optional[int] = None, stream_id: Optional[int] = None, prompt=None, prefix=None, sampler=None) -> Future:
         """Queue one request; the future yields a `StreamResult`.  `prompt` (tokens, mask) skips the prompt building.  rng "host": `seed`
         seeds this stream's generator (None: fresh entropy).  rng "device": the batcher's seed is used, `seed` must be None or equal to it.
         ValueError at once for a request that cannot fit the cache; a request that races `close()` gets a failed future.
@@ -268,19 +298,27 @@ class CSMBatcher:
         non-voice_match layout with the prefix's context.  Its length is prefix.length + the text frames; the prefix's K / V are copied under
         the text frames at admission, nothing of the context is encoded, tokenised or computed again.  `prefix` excludes `context`, `prompt`
         and `voice_match=True` (ValueError): the voice_match layout merges the context's text with the request's in front of the audio, so it
-        has no shareable prefix.  voice_match defaults to True without a prefix, as before."""
-        return self._enqueue(False, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix)
+        has no shareable prefix.  voice_match defaults to True without a prefix, as before.
+        `sampler` (a batcher made with `row_samplers=True`; ValueError otherwise): this request's `make_sampler(...)`, None = the batcher's;
+        with rng "device" such a batcher also takes a `seed` of the request's own.  An out-of-range sampler is a ValueError here."""
+        return self._enqueue(False, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix, sampler)
 
     def submit_stream(self, context=None, text=None, speaker: int = 0, voice_match: Optional[bool] = None, max_audio_length_ms: float = 90_000,
-                      seed: Optional[int] = None, stream_id: Optional[int] = None, prompt=None, prefix=None) -> CSMAudioStream:
+                      seed: Optional[int] = None, stream_id: Optional[int] = None, prompt=None, prefix=None, sampler=None) -> CSMAudioStream:
         """`submit` with the audio delivered while the stream runs: the same arguments and refusals, a `CSMAudioStream` back.  Needs a batcher
         made with `stream_chunk_frames=N`; the request may not be longer than `stream_max_frames`."""
         if self._dec is None:
             raise ValueError("submit_stream needs a batcher made with stream_chunk_frames=N")
-        return self._enqueue(True, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix)
+        return self._enqueue(True, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix, sampler)
 
-    def _enqueue(self, _streaming: bool, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix):
+    def _enqueue(self, _streaming: bool, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix, sampler=None):
         max_frames = int(max_audio_length_ms / 80)
+        if sampler is not None:
+            if not self.row_samplers:
+                raise ValueError("a per-request sampler needs a batcher made with row_samplers=True; this one samples every stream with its own")
+            _check_sampler(sampler)
+        elif self.row_samplers:
+            sampler = self.sampler
         if prefix is not None:
             if context or prompt is not None or voice_match:
                 raise ValueError("prefix= stands for the context of the non-voice_match layout: it excludes context, prompt and voice_match=True")
@@ -302,7 +340,9 @@ class CSMBatcher:
             raise ValueError("a request needs a prompt and at least one frame")
         if _streaming and max_frames > self.stream_max_frames:
             raise ValueError(f"a streaming request of {max_frames} frames: the batcher was made for stream_max_frames = {self.stream_max_frames}")
-        if self.rng == "device" and seed is not None and int(seed) != self.seed:
+        if self.rng == "device" and seed is None and self.row_samplers:
+            seed = self.seed
+        if self.rng == "device" and seed is not None and int(seed) != self.seed and not self.row_samplers:
             raise ValueError(f"rng 'device': every stream draws from the batcher's seed {self.seed}; streams differ by stream_id")
         if stream_id is not None and not 0 <= int(stream_id) < 2 ** 31:
             raise ValueError("stream_id must be in [0, 2^31)")
@@ -318,7 +358,7 @@ class CSMBatcher:
             self._queue.append(_Stream(future=fut, context=context, text=text, speaker=int(speaker),
                                        voice_match=True if voice_match is None else bool(voice_match),
                                        max_frames=max_frames, seed=seed, stream_id=int(stream_id), length=length, t0=time.perf_counter(),
-                                       prompt=prompt, prefix=prefix, audio=audio))
+                                       prompt=prompt, prefix=prefix, audio=audio, sampler=sampler))
             self._wake.notify()
         return audio if _streaming else fut
 
@@ -468,16 +508,20 @@ class CSMBatcher:
                 elif S > P:
                     self._shift(S - P)       # the live windows move up so that the prompt fits below the position
                 u = None
-                if self._sampled and self.rng == "host":
+                sampler = s.sampler if self.row_samplers else self.sampler  # the request's own: its admission block, then its row's table entry
+                sampled = float(sampler.temp) > 0 if self.row_samplers else self._sampled
+                if sampled and self.rng == "host":  # (a greedy stream has no generator: it consumes no draws, as its solo run)
                     s.rng = np.random.default_rng(s.seed)
                     u = s.rng.uniform(size=(1, self.engine.n_cb))[0].astype(np.float32)
-                seed = self.seed if (self._sampled and self.rng == "device") else None
+                seed = (s.seed if self.row_samplers else self.seed) if (sampled and self.rng == "device") else None
                 out: List[torch.Tensor] = []
                 if s.prefix is not None:
-                    self._timed("admit", lambda: out.append(self.engine.admit(row, s.prompt, self.sampler, u, seed, s.stream_id, prefix=s.prefix)))
+                    self._timed("admit", lambda: out.append(self.engine.admit(row, s.prompt, sampler, u, seed, s.stream_id, prefix=s.prefix)))
                 else:
-                    self._timed("admit", lambda: out.append(self.engine.admit(row, s.prompt, self.sampler, u, seed, s.stream_id)))
+                    self._timed("admit", lambda: out.append(self.engine.admit(row, s.prompt, sampler, u, seed, s.stream_id)))
                 codes = out[0]
+                if self.row_samplers:
+                    self.engine.set_row_sampler(row, sampler, seed)
             except Exception as e:  # noqa: BLE001
                 s.future.set_exception(e)
                 continue
@@ -502,14 +546,18 @@ class CSMBatcher:
         pad, P = self.engine.row_state()
         if P >= self.engine.max_pos:  # the position has reached the end of the cache: every live window moves down to slot 0 of the longest
             self._shift(-min(pad[s.row] for s in live))
-        u = None
-        if self._sampled and self.rng == "host":
-            u = np.full((self.max_batch, self.engine.n_cb), 0.5, np.float32)
-            for s in live:
-                u[s.row] = s.rng.uniform(size=(1, self.engine.n_cb))[0]
-        seed = self.seed if (self._sampled and self.rng == "device") else None
-        ids = [self._rows[r].stream_id if self._rows[r] is not None else 0 for r in range(self.max_batch)] if seed is not None else None
-        sample = self.engine.frame(self._prev, self.sampler, u, seed, ids).clone()  # (graph replay hands back a view of a persistent buffer)
+        if self.row_samplers:  # every row's settings come from its table entry: one uniform source for the batcher's life, one captured graph
+            u, ids = None, None
+            if self.rng == "host":  # a greedy stream's row (and a parked one) is a constant: only sampled streams draw
+                u = np.full((self.max_batch, self.engine.n_cb), 0.5, np.float32)
+                for s in live:
+                    if s.rng is not None:
+                        u[s.row] = s.rng.uniform(size=(1, self.engine.n_cb))[0]
+            else:
+                ids = [self._rows[r].stream_id if self._rows[r] is not None else 0 for r in range(self.max_batch)]
+            sample = self.engine.frame(self._prev, "rows", u, None, ids, device_rng=self.rng == "device").clone()
+        else:
+            sample = self._frame_one_sampler(live)
         self._prev = sample
         if self.stop_on_eos:
             zero = (sample == 0).all(dim=1)  # an all-zero frame is EOS (sesame.py:765-766)
@@ -520,6 +568,17 @@ class CSMBatcher:
         self.stats["frames"] += 1
         self.stats["live_row_frames"] += len(live)
         self._since_poll += 1
+
+    def _frame_one_sampler(self, live: List[_Stream]) -> torch.Tensor:
+        """The frame step with the batcher's sampler for every row (launch arguments)"""
+        u = None
+        if self._sampled and self.rng == "host":
+            u = np.full((self.max_batch, self.engine.n_cb), 0.5, np.float32)
+            for s in live:
+                u[s.row] = s.rng.uniform(size=(1, self.engine.n_cb))[0]
+        seed = self.seed if (self._sampled and self.rng == "device") else None
+        ids = [self._rows[r].stream_id if self._rows[r] is not None else 0 for r in range(self.max_batch)] if seed is not None else None
+        return self.engine.frame(self._prev, self.sampler, u, seed, ids).clone()  # (graph replay hands back a view of a persistent buffer)
 
     def step(self) -> bool:
         """One scheduling round; False when there was nothing to do (no live stream, empty queue)."""

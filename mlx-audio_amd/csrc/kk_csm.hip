@@ -105,6 +105,9 @@ struct kk_csm {
   unsigned long long* seed_dev = nullptr;
   unsigned long long seed_host = 0;
   bool seed_valid = false;
+  // per-row sampler table (kk_csm_set_row_sampler / kk_csm_generate_frame_rows): [max_batch] entries of 32 bytes (RowSampler), zero = arg-max
+  void* row_samplers = nullptr;
+  bool row_samplers_zero_pending = false;  // kk_csm_reset_caches_parked takes no stream: zeroed on the next stream that flushes
   unsigned long long weights_id = 0;   // the weight set (kk_csm_finalize; kk_csm_share copies it): what a kk_csm_prefix is tied to
   const kk_csm* weights_of = nullptr;  // kk_csm_share: `dev` / `devb` / `devq` belong to that generator (immutable after finalize), not to this one
 };
@@ -832,6 +835,7 @@ struct SampleSrc {
   const float* u = nullptr;  // [B] at pitch ustride, or null
   int ustride = 0;
   const unsigned long long* seed = nullptr;  // device; null = no device RNG
+  int seed_stride = 0;                       // 64-bit words between the seeds of two items: 0 = one word for the launch, 4 = the row's RowSampler entry
   const int* sid = nullptr;                  // [B] stream ids, null = batch index
   const int* pos = nullptr;                  // device position(s): pos[b * pos_stride]
   int pos_stride = 0, pos_add = 0;
@@ -843,7 +847,7 @@ __device__ __forceinline__ float sample_uniform(const SampleSrc& a, int b) {
   const uint32_t sid = a.sid ? (uint32_t)a.sid[b] : (uint32_t)b;
   const int p = (a.pos ? a.pos[(long long)b * a.pos_stride] : 0) + a.pos_add - (a.pad ? a.pad[b] : 0);
   uint32_t r[4];
-  philox4(*a.seed, ((uint64_t)sid << 32) | (uint32_t)p, (uint32_t)a.cb, r);
+  philox4(a.seed[(long long)b * a.seed_stride], ((uint64_t)sid << 32) | (uint32_t)p, (uint32_t)a.cb, r);
   return philox_unit(r[0]);
 }
 __global__ __launch_bounds__(256) void sample_uniforms_kernel(SampleSrc a, int B, int ncb, float* out) {
@@ -939,8 +943,35 @@ __device__ __forceinline__ unsigned sk_key(float f) {
 }
 __device__ __forceinline__ float sk_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
+// The bodies of the sampling kernels as device functions: sample_select_kernel / sample_full_kernel (settings as launch arguments) and
+// sample_rows_kernel (settings from the row's table entry) run the SAME source, so with -ffp-contract=off the same arithmetic and the same picks.
+// arg-max (lower index on ties): the key order is the float order, so one max over (key, ~index) does it -- no histogram
 template <int NPER>
-__global__ __launch_bounds__(256) void sample_select_kernel(const float* logits, int V, float temp, int top_k, SampleSrc src, int* out, int ostride) {
+__device__ __forceinline__ void sample_argmax_body(const unsigned (&key)[NPER], int V, int* out, int ostride) {
+  __shared__ unsigned long long wbest[4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  unsigned long long best = 0ull;
+#pragma unroll
+  for (int i = 0; i < NPER; ++i) {
+    const int j = tid + 256 * i;
+    const unsigned long long c = j < V ? (((unsigned long long)key[i] << 32) | (unsigned)(0x7fffffff - j)) : 0ull;
+    best = c > best ? c : best;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long t = __shfl_xor(best, o);
+    best = t > best ? t : best;
+  }
+  if (lane == 0) wbest[wave] = best;
+  __syncthreads();
+  if (tid == 0) {
+    unsigned long long g = wbest[0];
+    for (int w = 1; w < 4; ++w) g = wbest[w] > g ? wbest[w] : g;
+    out[(long long)b * ostride] = 0x7fffffff - (int)(unsigned)(g & 0xffffffffull);
+  }
+}
+template <int NPER>
+__device__ __forceinline__ void sample_select_body(const float* logits, int V, float temp, int top_k, const SampleSrc& src, int* out, int ostride) {
   __shared__ unsigned hist[256];
   __shared__ unsigned s_prefix, s_krem, s_bin, ccount;
   __shared__ unsigned ckey[64];
@@ -954,27 +985,8 @@ __global__ __launch_bounds__(256) void sample_select_kernel(const float* logits,
   }
   const bool greedy = (src.u == nullptr && src.seed == nullptr) || temp == 0.f;
   const int k = greedy ? 1 : (top_k < 64 ? (top_k < V ? top_k : V) : 64);
-  if (greedy) {  // arg-max (lower index on ties): the key order is the float order, so one max over (key, ~index) does it -- no histogram
-    __shared__ unsigned long long wbest[4];
-    unsigned long long best = 0ull;
-#pragma unroll
-    for (int i = 0; i < NPER; ++i) {
-      const int j = tid + 256 * i;
-      const unsigned long long c = j < V ? (((unsigned long long)key[i] << 32) | (unsigned)(0x7fffffff - j)) : 0ull;
-      best = c > best ? c : best;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned long long t = __shfl_xor(best, o);
-      best = t > best ? t : best;
-    }
-    if (lane == 0) wbest[wave] = best;
-    __syncthreads();
-    if (tid == 0) {
-      unsigned long long g = wbest[0];
-      for (int w = 1; w < 4; ++w) g = wbest[w] > g ? wbest[w] : g;
-      out[(long long)b * ostride] = 0x7fffffff - (int)(unsigned)(g & 0xffffffffull);
-    }
+  if (greedy) {
+    sample_argmax_body<NPER>(key, V, out, ostride);
     return;
   }
   unsigned prefix = 0u, mask = 0u, krem = (unsigned)k;
@@ -1066,6 +1078,10 @@ __global__ __launch_bounds__(256) void sample_select_kernel(const float* logits,
   }
   if (lane == 0) out[(long long)b * ostride] = (unsigned)pick < (unsigned)V ? pick : 0;
 }
+template <int NPER>
+__global__ __launch_bounds__(256) void sample_select_kernel(const float* logits, int V, float temp, int top_k, SampleSrc src, int* out, int ostride) {
+  sample_select_body<NPER>(logits, V, temp, top_k, src, out, ostride);
+}
 
 // The full make_sampler family on the WHOLE vocabulary (top_k = 0 / >= V / > 64, top_p, min_p): one 256-thread workgroup per item.
 //   1. (order-preserving key, ~index) pairs of all V logits in LDS (NaN reads as -inf), bitonic sort descending: the order is (logit
@@ -1090,8 +1106,8 @@ __device__ __forceinline__ int sf_block_min(int v, int* sh) {
   return a < b ? a : b;
 }
 template <int N>
-__global__ __launch_bounds__(256) void sample_full_kernel(const float* logits, int V, SampleCfg cfg, SampleSrc src, int* out, int ostride) {
-  extern __shared__ unsigned long long sf_lds[];
+__device__ __forceinline__ void sample_full_body(unsigned long long* sf_lds, const float* logits, int V, const SampleCfg& cfg, const SampleSrc& src, int* out,
+                                                 int ostride) {
   unsigned long long* sk = sf_lds;
   float* shf = (float*)(sf_lds + N);  // [8]: wave totals of the two scans
   int* shi = (int*)(shf + 8);         // [4] block minimum; [4] c[n - 1]
@@ -1197,6 +1213,42 @@ __global__ __launch_bounds__(256) void sample_full_kernel(const float* logits, i
     out[(long long)b * ostride] = idx < (unsigned)V ? (int)idx : 0;  // always a valid row of the next launch's embedding gather
   }
 }
+template <int N>
+__global__ __launch_bounds__(256) void sample_full_kernel(const float* logits, int V, SampleCfg cfg, SampleSrc src, int* out, int ostride) {
+  extern __shared__ unsigned long long sf_lds[];
+  sample_full_body<N>(sf_lds, logits, V, cfg, src, out, ostride);
+}
+
+// The sampler with its settings PER ROW: one table entry per cache row (kk_csm_set_row_sampler), read by the row's workgroup, which then takes --
+// block-uniformly -- exactly the branch launch_sample would have chosen for that entry, through the bodies above.  One launch per code book serves a
+// batch whose rows mix greedy, top-k and top-p / min-p streams, and nothing of the entry is a launch argument: a captured frame step replays
+// unchanged when a row's sampler changes.  An all-zero entry (a parked or never-set row) has temp == 0: arg-max, a code in [0, V).
+struct RowSampler {  // 32 bytes
+  float temp;
+  int top_k;
+  float top_p, min_p;
+  int min_keep, pad_;
+  unsigned long long seed;  // Philox seed of the row's stream (SampleSrc::seed_stride = 4)
+};
+static_assert(sizeof(RowSampler) == 32, "RowSampler is 32 bytes");
+__global__ void set_row_sampler_kernel(RowSampler* table, int row, RowSampler e) { table[row] = e; }
+
+__device__ __forceinline__ int rs_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ float rs_uniform(float v) { return __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(v))); }
+// NPER: the select path's logits per thread (V <= 256 NPER); N: the full path's sort size (V <= N).  Every workgroup reserves the full path's
+// dynamic LDS (8 N + 64 bytes), whichever branch it takes; the select path's small arrays stay static next to it.
+template <int NPER, int N>
+__global__ __launch_bounds__(256) void sample_rows_kernel(const float* logits, int V, const RowSampler* table, SampleSrc src, int* out, int ostride) {
+  extern __shared__ unsigned long long sf_lds[];
+  const RowSampler* e = table + blockIdx.x;
+  SampleCfg cfg;  // the entry is one value for the workgroup: held in scalar registers like the launch arguments it replaces
+  cfg.temp = rs_uniform(e->temp); cfg.top_k = rs_uniform(e->top_k); cfg.top_p = rs_uniform(e->top_p); cfg.min_p = rs_uniform(e->min_p);
+  cfg.min_keep = rs_uniform(e->min_keep);
+  const bool greedy = (src.u == nullptr && src.seed == nullptr) || cfg.temp == 0.f;  // launch_sample's rule, word for word
+  const bool filters = (cfg.top_p > 0.f && cfg.top_p < 1.f) || cfg.min_p > 0.f;
+  if (!greedy && (filters || cfg.top_k <= 0 || cfg.top_k > 64)) sample_full_body<N>(sf_lds, logits, V, cfg, src, out, ostride);
+  else sample_select_body<NPER>(logits, V, cfg.temp, cfg.top_k, src, out, ostride);
+}
 
 template <int N>
 int launch_sample_full(const float* logits, int V, const SampleCfg& cfg, const SampleSrc& src, int* out, int ostride, int B, hipStream_t st) {
@@ -1230,6 +1282,28 @@ int launch_sample(const float* logits, int V, const SampleCfg& cfg, const Sample
   else hipLaunchKernelGGL(sample_select_kernel<32>, dim3(B), dim3(256), 0, st, logits, V, temp, top_k, src, out, ostride);
   KK_CHECK_LAUNCH();
   return 0;
+}
+
+template <int NPER, int N>
+int launch_sample_rows_t(const float* logits, int V, const RowSampler* table, const SampleSrc& src, int* out, int ostride, int B, hipStream_t st) {
+  const size_t lds = (size_t)N * 8 + 64;
+  static KKDevOnce attr;
+  if (attr.first()) {
+    (void)hipFuncSetAttribute((const void*)sample_rows_kernel<NPER, N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr.done();
+  }
+  hipLaunchKernelGGL((sample_rows_kernel<NPER, N>), dim3(B), dim3(256), lds, st, logits, V, table, src, out, ostride);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+// launch_sample with row b's settings read from table[b]: V picks the pair (NPER of the select path, N of the full path) launch_sample picks one by one
+int launch_sample_rows(const float* logits, int V, const RowSampler* table, const SampleSrc& src, int* out, int ostride, int B, hipStream_t st) {
+  if (V > 256 * 32) return kk_fail("kk_csm: audio vocabulary larger than 8192 entries");
+  if (V <= 1024) return launch_sample_rows_t<4, 1024>(logits, V, table, src, out, ostride, B, st);
+  if (V <= 2048) return launch_sample_rows_t<9, 2048>(logits, V, table, src, out, ostride, B, st);
+  if (V <= 256 * 9) return launch_sample_rows_t<9, 4096>(logits, V, table, src, out, ostride, B, st);
+  if (V <= 4096) return launch_sample_rows_t<32, 4096>(logits, V, table, src, out, ostride, B, st);
+  return launch_sample_rows_t<32, 8192>(logits, V, table, src, out, ostride, B, st);
 }
 
 // Skinny GEMM for the single-token steps (M = B rows <= 16): out[m][n] = sum_k x[m][k] W[k][n].  The grid is (column blocks) x (KS
@@ -2174,7 +2248,7 @@ int stack_step(Run& r, Stack& st, float* h, int rows, int offset, const FGArgs* 
 // `split` (kk_csm_admit_prefixed): the block is the tail of a longer prompt -- its backbone rows and the first head take the kernels the rows of the
 // unsplit block take, whatever S (Run::lin_mode); the depth decoder sees the same shapes either way
 int run_frame(Run& r, int S, const int* tokens, const float* mask, const SampleCfg& sc, const float* uniforms, const unsigned long long* seed,
-              const int* stream_ids, int* codes, int own_pos = -1, bool split = false) {
+              const int* stream_ids, int* codes, int own_pos = -1, bool split = false, const RowSampler* table = nullptr) {
   kk_csm* m = r.m;
   // the uniform of (item, code book i): uniforms[b][i], or Philox at the position of the frame being generated (slot *pos_dev + S, minus the padding)
   auto src_of = [&](int i) {
@@ -2182,7 +2256,13 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, const SampleC
     s.u = uniforms ? uniforms + i : nullptr; s.ustride = m->cfg.audio_num_codebooks;
     s.seed = uniforms ? nullptr : seed; s.sid = stream_ids; s.pos = m->bb.pos_dev; s.pos_stride = 0; s.pos_add = S; s.pad = m->bb.pad_dev; s.cb = i;
     if (own_pos >= 0) { s.pos = nullptr; s.pad = nullptr; s.pos_add = own_pos; }
+    if (table && s.seed) { s.seed = &table->seed; s.seed_stride = (int)(sizeof(RowSampler) / 8); }  // table mode: `seed` only says that the launch draws
     return s;
+  };
+  // the sampling launch of code book i: the settings as launch arguments, or (table mode) row b's from table[b] -- one launch either way
+  auto sample = [&](const float* lg, int i, int* out) {
+    return table ? launch_sample_rows(lg, m->cfg.audio_vocab_size, table, src_of(i), out, m->cfg.audio_num_codebooks, r.B, r.st)
+                 : launch_sample(lg, m->cfg.audio_vocab_size, sc, src_of(i), out, m->cfg.audio_num_codebooks, r.B, r.st);
   };
   const kk_csm_config& c = m->cfg;
   const int B = r.B, ncb = c.audio_num_codebooks, V = c.audio_vocab_size, D = c.backbone.hidden, Dd = c.decoder.hidden;
@@ -2236,7 +2316,7 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, const SampleC
       memset(&g, 0, sizeof g);
       g.x = last_h; g.xrs = last_rs; g.out = logits; g.ors = V;
       KK_TRY(launch_gemv(m->c0_head, 0, 0, g, B, r.st));
-      KK_TRY(launch_sample(logits, V, sc, src_of(0), codes, ncb, B, r.st));
+      KK_TRY(sample(logits, 0, codes));
     }
     int rows = 2, dpos = 0;
     for (int i = 1; i < ncb; ++i) {
@@ -2264,7 +2344,7 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, const SampleC
         memset(&g, 0, sizeof g);
         g.x = pin + (size_t)(rows - 1) * Dd; g.xrs = (long long)rows * Dd; g.nw = m->dec.norm.p; g.eps = c.decoder.rms_eps; g.out = logits; g.ors = V;
         KK_TRY(launch_gemv(m->audio_head[i - 1], 1, 0, g, B, r.st));
-        KK_TRY(launch_sample(logits, V, sc, src_of(i), codes + i, ncb, B, r.st));
+        KK_TRY(sample(logits, i, codes + i));
       }
       rows = 1;
     }
@@ -2276,7 +2356,7 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, const SampleC
     if (rc_ != 0) return rc_;
   }
   if (!r.dry) {
-    KK_TRY(launch_sample(logits, V, sc, src_of(0), codes, ncb, B, r.st));
+    KK_TRY(sample(logits, 0, codes));
     // curr = [last_h, embed_audio(0, c0)]
     hipLaunchKernelGGL(copy_rows_kernel, dim3(B), dim3(256), 0, r.st, last_h, last_rs, curr, (long long)2 * D, D);
     KK_CHECK_LAUNCH();
@@ -2294,7 +2374,7 @@ int run_frame(Run& r, int S, const int* tokens, const float* mask, const SampleC
     if (dbg) logits = m->dbg_logits + (size_t)i * m->max_batch * V;
     KK_TRY(r.lin(m->audio_head[i - 1], dl, (long long)rows * Dd, 1, logits, V, nullptr));
     if (!r.dry) {
-      KK_TRY(launch_sample(logits, V, sc, src_of(i), codes + i, ncb, B, r.st));
+      KK_TRY(sample(logits, i, codes + i));
       hipLaunchKernelGGL(embed_audio_kernel, dim3(B), dim3(256), 0, r.st, codes + i, ncb, m->audio_emb.p, i, V, D, curr, 1, 0);
       KK_CHECK_LAUNCH();
     }
@@ -2396,6 +2476,36 @@ extern "C" int kk_op_csm_sample_ex(void* stream, int B, int V, const float* logi
     (void)hipStreamSynchronize((hipStream_t)stream);
     (void)hipFree(seed_dev);
   }
+  return rc;
+}
+
+// launch_sample_rows on its own (tests): row b's settings from samplers[b] (HOST array), through a temporary device table.  uniforms [B] have priority;
+// without them the launch draws on the device when the entries say so (use_device_rng must agree across the entries: it is a property of the launch)
+extern "C" int kk_op_csm_sample_rows(void* stream, int B, int V, const float* logits, const kk_csm_sampler* samplers, const float* uniforms,
+                                     const int32_t* stream_ids, const int32_t* pos, int32_t* codes_out) {
+  if (!logits || !codes_out || !samplers || B < 1 || V < 1) return kk_fail("kk_op_csm_sample_rows: bad argument");
+  std::vector<RowSampler> host((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    SampleCfg c;
+    KK_TRY(sampler_cfg(samplers + b, &c, "kk_op_csm_sample_rows"));
+    if ((samplers[b].use_device_rng != 0) != (samplers[0].use_device_rng != 0)) return kk_fail("kk_op_csm_sample_rows: use_device_rng differs between the entries");
+    RowSampler& e = host[(size_t)b];
+    e.temp = c.temp; e.top_k = c.top_k; e.top_p = c.top_p; e.min_p = c.min_p; e.min_keep = c.min_keep; e.pad_ = 0; e.seed = samplers[b].seed;
+  }
+  RowSampler* table = nullptr;
+  if (hipMalloc((void**)&table, (size_t)B * sizeof(RowSampler)) != hipSuccess) return kk_fail("kk_op_csm_sample_rows: hipMalloc failed");
+  if (hipMemcpy(table, host.data(), (size_t)B * sizeof(RowSampler), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(table);
+    return kk_fail("kk_op_csm_sample_rows: table upload failed");
+  }
+  SampleSrc s;
+  s.u = uniforms; s.ustride = 1;
+  if (!uniforms && samplers[0].use_device_rng) {
+    s.seed = &table->seed; s.seed_stride = (int)(sizeof(RowSampler) / 8); s.sid = stream_ids; s.pos = pos; s.pos_stride = 1;
+  }
+  const int rc = launch_sample_rows(logits, V, table, s, codes_out, 1, B, (hipStream_t)stream);
+  (void)hipStreamSynchronize((hipStream_t)stream);
+  (void)hipFree(table);
   return rc;
 }
 
@@ -2583,6 +2693,8 @@ extern "C" int kk_csm_share(const kk_csm* m, kk_csm** out) {
   c->dbg_logits = nullptr;
   c->seed_dev = nullptr;
   c->admit_sid_dev = nullptr;
+  c->row_samplers = nullptr;
+  c->row_samplers_zero_pending = false;
   c->seed_valid = false;
   c->reset_pending = c->pad_pending = false;
   c->pad_host.clear();
@@ -2605,6 +2717,7 @@ extern "C" void kk_csm_destroy(kk_csm* m) {
   if (m->bb.pad_dev) (void)hipFree(m->bb.pad_dev);
   if (m->seed_dev) (void)hipFree(m->seed_dev);
   if (m->admit_sid_dev) (void)hipFree(m->admit_sid_dev);
+  if (m->row_samplers) (void)hipFree(m->row_samplers);
   m->graphs.clear();
   delete m;
 }
@@ -2767,9 +2880,14 @@ extern "C" int kk_csm_setup_caches(kk_csm* m, int max_batch) {
   m->bb.pad_dev = nullptr;
   if (hipMalloc((void**)&m->bb.pad_dev, (size_t)max_batch * 4) != hipSuccess || hipMemset(m->bb.pad_dev, 0, (size_t)max_batch * 4) != hipSuccess)
     return kk_fail("kk_csm_setup_caches: hipMalloc failed");
+  if (m->row_samplers) (void)hipFree(m->row_samplers);
+  m->row_samplers = nullptr;
+  if (hipMalloc(&m->row_samplers, (size_t)max_batch * sizeof(RowSampler)) != hipSuccess ||
+      hipMemset(m->row_samplers, 0, (size_t)max_batch * sizeof(RowSampler)) != hipSuccess)
+    return kk_fail("kk_csm_setup_caches: hipMalloc failed");
   m->max_batch = max_batch;
   m->pad_host.assign((size_t)max_batch, 0);
-  m->reset_pending = m->pad_pending = false;  // freshly zeroed above
+  m->reset_pending = m->pad_pending = m->row_samplers_zero_pending = false;  // freshly zeroed above
   return 0;
 }
 // Ragged prompts: the streams of a batch are LEFT-padded to the longest prompt (padding frames carry an all-zero mask); pad[b] = number of
@@ -2815,6 +2933,11 @@ static int flush_pending(kk_csm* m, hipStream_t st) {
     if (hipMemcpyAsync(m->bb.pad_dev, m->pad_host.data(), (size_t)m->max_batch * 4, hipMemcpyHostToDevice, st) != hipSuccess)
       return kk_fail("kk_csm_generate_frame: padding upload failed");
     m->pad_pending = false;
+  }
+  if (m->row_samplers_zero_pending) {  // deferred kk_csm_reset_caches_parked: every row's sampler entry back to zero (arg-max)
+    if (hipMemsetAsync(m->row_samplers, 0, (size_t)m->max_batch * sizeof(RowSampler), st) != hipSuccess)
+      return kk_fail("kk_csm_generate_frame: sampler table reset failed");
+    m->row_samplers_zero_pending = false;
   }
   return 0;
 }
@@ -2875,6 +2998,56 @@ extern "C" int kk_csm_generate_frame_ex(kk_csm* m, void* stream, int B, int S, c
   return rc;
 }
 
+// ---- per-row sampler settings ---------------------------------------------------------------------------------------------------
+extern "C" int kk_csm_set_row_sampler(kk_csm* m, void* stream, int row, const kk_csm_sampler* sampler) {
+  if (!m || m->max_batch < 1 || !m->row_samplers) return kk_fail("kk_csm_set_row_sampler: call kk_csm_setup_caches first");
+  if (row < 0 || row >= m->max_batch) return kk_fail("kk_csm_set_row_sampler: row out of range");
+  SampleCfg sc;
+  KK_TRY(sampler_cfg(sampler, &sc, "kk_csm_set_row_sampler"));
+  hipStream_t st = (hipStream_t)stream;
+  KK_TRY(flush_pending(m, st));  // a deferred zeroing of the table must not land behind this entry
+  RowSampler e;
+  e.temp = sc.temp; e.top_k = sc.top_k; e.top_p = sc.top_p; e.min_p = sc.min_p; e.min_keep = sc.min_keep; e.pad_ = 0; e.seed = sampler->seed;
+  hipLaunchKernelGGL(set_row_sampler_kernel, dim3(1), dim3(1), 0, st, (RowSampler*)m->row_samplers, row, e);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int kk_csm_generate_frame_rows(kk_csm* m, void* stream, int B, int S, const int32_t* tokens, const float* tokens_mask, int use_device_rng,
+                                          const float* uniforms, const int32_t* stream_ids, void* workspace, size_t workspace_bytes, int32_t* codes_out) {
+  if (!m || !m->finalized) return kk_fail("kk_csm_generate_frame_rows: model not finalized");
+  if (m->max_batch < 1 || !m->row_samplers) return kk_fail("kk_csm_generate_frame_rows: call kk_csm_setup_caches first");
+  if (B <= 0 || B > m->max_batch || S <= 0 || !tokens || !tokens_mask || !workspace || !codes_out) return kk_fail("kk_csm_generate_frame_rows: bad argument");
+  if (m->bb.offset + S > m->bb.max_pos) return kk_fail("kk_csm_generate_frame_rows: sequence exceeds max_seq_len");
+  if (S > 1 && m->bb.offset != 0) return kk_fail("kk_csm_generate_frame_rows: a multi-token block must start an empty cache (sesame.py:41-48)");
+  if (workspace_bytes < kk_csm_workspace_bytes(m, B, S)) return kk_fail("kk_csm_generate_frame_rows: workspace too small");
+  KK_TRY(flush_pending(m, (hipStream_t)stream));
+  const bool dev_rng = !uniforms && use_device_rng != 0;
+  const RowSampler* table = (const RowSampler*)m->row_samplers;
+  auto eager = [&](void* on_stream) -> int {
+    Run r(m, (hipStream_t)on_stream, B, workspace, workspace_bytes);
+    // (`seed` non-null only tells run_frame that the launches draw on the device: in table mode the word itself is the row's entry)
+    return run_frame(r, S, tokens, tokens_mask, SampleCfg(), uniforms, dev_rng ? &table->seed : nullptr, dev_rng ? stream_ids : nullptr, codes_out, -1, false, table);
+  };
+  int rc;
+  if (!m->graph_mode || S != 1) {
+    rc = eager(stream);
+  } else {
+    // keyed by the MODE (the leading tag; the key of kk_csm_generate_frame_ex has another length), B, the pointers and the uniform source -- never by
+    // what the table holds: kk_csm_set_row_sampler between two replays changes the next replay's picks without a new capture
+    const std::vector<unsigned long long> key = {~0ull, (unsigned long long)B, (unsigned long long)(uintptr_t)tokens, (unsigned long long)(uintptr_t)tokens_mask,
+        (unsigned long long)(uintptr_t)uniforms, (unsigned long long)(uintptr_t)workspace, (unsigned long long)workspace_bytes,
+        (unsigned long long)(uintptr_t)codes_out, (unsigned long long)(uintptr_t)g_ts, (unsigned long long)dev_rng,
+        (unsigned long long)(uintptr_t)(dev_rng ? stream_ids : nullptr), (unsigned long long)(uintptr_t)table};
+    hipGraphExec_t ex = nullptr;
+    rc = m->graphs.run(key, (hipStream_t)stream, [&](hipStream_t on_stream, bool) { return eager((void*)on_stream); }, &ex, "kk_csm");
+    if (rc != 0) return rc;
+    if (ex && hipGraphLaunch(ex, (hipStream_t)stream) != hipSuccess) return kk_fail("kk_csm: hipGraphLaunch failed");
+  }
+  if (rc == 0) m->bb.offset += S;
+  return rc;
+}
+
 // ---- continuous batching: streams enter and leave a running batch -------------------------------------------------------------
 // All rows share the slot counter P (bb.offset / *bb.pos_dev); row b's tokens live in slots [pad[b], P) at position slot - pad[b].  A PARKED row
 // has pad[b] = max_pos: every attention form sees nk <= 0 for it (zero output, nothing appended), so it rides through the frame step's GEMVs
@@ -2886,6 +3059,7 @@ extern "C" int kk_csm_reset_caches_parked(kk_csm* m) {
   KK_TRY(kk_csm_reset_caches(m));
   m->pad_host.assign((size_t)m->max_batch, m->bb.max_pos);
   m->pad_pending = true;  // uploaded behind the deferred reset
+  m->row_samplers_zero_pending = true;
   return 0;
 }
 

@@ -320,7 +320,13 @@ class Model:
         frame).  Ragged prompts are left-padded; the loop ends when every stream has produced its EOS frame (an all-zero frame, sesame.py:765).
         rng "host": one [B, n_cb] block of numpy uniforms per frame (or `uniforms(i)`), uploaded in front of the frame.  rng "device": the
         sampling kernels draw from Philox on (seed, stream id, the stream's own position, code book) -- no host work per frame, and a
-        stream's draws do not depend on the batch it runs in."""
+        stream's draws do not depend on the batch it runs in.
+        `sampler` as a list (one per stream; `seed` then a list too, or one value for all): the loop runs in table mode
+        (`SesameModel.set_row_sampler`, `generate_frame(sampler="rows")`).  Host rng: every stream has a generator of its own and draws its
+        [n_cb] uniforms per frame only if its own temp > 0 -- as its solo run does; device rng: every stream draws on its own seed."""
+        if isinstance(sampler, (list, tuple)):
+            yield from self._frame_loop_rows(prompts, max_audio_frames, list(sampler), seed, stop_on_eos, uniforms, rng, stream_ids)
+            return
         B = len(prompts)
         lens = [p[0].shape[0] for p in prompts]
         S = max(lens)
@@ -365,6 +371,62 @@ class Model:
             if stop_on_eos:
                 done = done | (sample == 0).all(dim=1)  # an all-zero frame is EOS (sesame.py:765-766)
             yield sample.clone(), was_done, done  # (graph replay hands back a view of a persistent buffer)
+            curr = torch.zeros((B, 1, n + 1), dtype=torch.int32, device=dev)
+            curr[:, 0, :n] = sample
+            cmask = step_mask
+
+    def _frame_loop_rows(self, prompts, max_audio_frames: int, samplers, seed, stop_on_eos: bool, uniforms, rng: str, stream_ids):
+        """`_frame_loop` with one sampler (and seed) per stream, through the per-row sampler table: the same launches per frame, and stream b's
+        frames are those of `_frame_loop([prompts[b]], samplers[b], seeds[b])`."""
+        B = len(prompts)
+        seeds = list(seed) if isinstance(seed, (list, tuple)) else [seed] * B
+        if len(samplers) != B or len(seeds) != B:
+            raise ValueError(f"sampler / seed lists must hold one entry per prompt ({B})")
+        lens = [p[0].shape[0] for p in prompts]
+        S = max(lens)
+        max_seq_len = self.model.cfg["max_seq_len"] - max_audio_frames
+        if S >= max_seq_len:
+            raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {max_seq_len}")  # sesame.py:755-758
+        n = self.n_cb
+        tok = np.zeros((B, S, n + 1), np.int32)
+        msk = np.zeros((B, S, n + 1), np.float32)
+        for b, (t, m) in enumerate(prompts):
+            tok[b, S - lens[b]:] = t
+            msk[b, S - lens[b]:] = m
+        csm, dev = self.model, self.model.device
+        if not csm.caches_are_enabled() or csm.max_batch < B:
+            csm.setup_caches(B)
+        csm.reset_caches()
+        if any(l != S for l in lens):
+            csm.set_padding([S - l for l in lens])
+        csm.set_graph_mode(True)
+        hot = [float(sp.temp) > 0 for sp in samplers]
+        device_rng = _check_rng(rng) == "device" and uniforms is None and any(hot)
+        if device_rng:  # fresh entropy where no seed was given, as the host generator takes
+            seeds = [int(np.random.SeedSequence().generate_state(2, np.uint32).view(np.uint64)[0]) if sd is None else sd for sd in seeds]
+        for b, sp in enumerate(samplers):
+            csm.set_row_sampler(b, sp, seeds[b] if device_rng else None)
+        gens = [np.random.default_rng(seeds[b]) if (hot[b] and uniforms is None and not device_rng) else None for b in range(B)]
+        curr, cmask = torch.tensor(tok, device=dev), torch.tensor(msk, device=dev)
+        step_mask = torch.zeros((B, 1, n + 1), dtype=torch.float32, device=dev)
+        step_mask[:, 0, :n] = 1
+        done = torch.zeros(B, dtype=torch.bool, device=dev)
+        for i in range(max_audio_frames):
+            u = None
+            if any(hot) and not device_rng:
+                if uniforms is not None:
+                    host_u = np.asarray(uniforms(i), np.float32)
+                else:  # a greedy stream's row is a constant: it consumes no draws
+                    host_u = np.full((B, n), 0.5, np.float32)
+                    for b, g in enumerate(gens):
+                        if g is not None:
+                            host_u[b] = g.uniform(size=(1, n))[0]
+                u = torch.tensor(host_u, device=dev)
+            sample = csm.generate_frame(curr, cmask, sampler="rows", uniforms=u, device_rng=device_rng, stream_ids=stream_ids if device_rng else None)
+            was_done = done
+            if stop_on_eos:
+                done = done | (sample == 0).all(dim=1)
+            yield sample.clone(), was_done, done
             curr = torch.zeros((B, 1, n + 1), dtype=torch.int32, device=dev)
             curr[:, 0, :n] = sample
             cmask = step_mask
@@ -421,7 +483,11 @@ class Model:
         """prompts: one (tokens, mask) pair per stream (`prompt_frames`), lengths may differ.  `uniforms(i)` (optional) supplies frame i's
         [B, n_cb] sampling uniforms instead of the seeded generator.  `sampler` (make_sampler) replaces `temperature` / `top_k` and adds
         top-p / min-p.  rng "device": draws come from the device generator keyed by (seed, stream_ids[b], position, code book), so stream b's
-        codes are those of a batch-1 run with the same seed and stream id, whatever else is in the batch (stream_ids default: 0..B-1).  Frames are generated for all streams until every
+        codes are those of a batch-1 run with the same seed and stream id, whatever else is in the batch (stream_ids default: 0..B-1).
+        `sampler` may be a LIST with one sampler per prompt (and `seed` a list with one seed per prompt): the loop then reads every stream's
+        settings from the per-row sampler table, in the same launches, and stream b's result is that of
+        `generate_batch([prompts[b]], sampler=sampler[b], seed=seed[b])`.  A single sampler keeps the launch-argument path.
+        Frames are generated for all streams until every
         stream has emitted its EOS frame; the host looks at the EOS flags only every `eos_check_interval` frames (one sync per interval instead
         of one per frame), so a few frames past the last EOS may be generated and are dropped.  Stream b's audio holds exactly its own frames."""
         start = time.perf_counter()
@@ -429,6 +495,13 @@ class Model:
         max_audio_frames = int(max_audio_length_ms / 80)
         frames, first_eos = [], torch.full((B,), -1, dtype=torch.int64, device=self.model.device)
         sampler = sampler if sampler is not None else make_sampler(temp=temperature, top_k=top_k)
+        if isinstance(sampler, (list, tuple)):
+            if len(sampler) != B:
+                raise ValueError(f"a sampler list must hold one sampler per prompt ({B})")
+            if isinstance(seed, (list, tuple)) and len(seed) != B:
+                raise ValueError(f"a seed list must hold one seed per prompt ({B})")
+        elif isinstance(seed, (list, tuple)):
+            raise ValueError("a seed list needs a sampler list (one sampler and one seed per prompt)")
         if stream_ids is not None and len(stream_ids) != B:
             raise ValueError(f"stream_ids must hold one id per prompt ({B})")
         for i, (sample, was_done, done) in enumerate(self._frame_loop(prompts, max_audio_frames, sampler, seed, stop_on_eos, uniforms, rng, stream_ids)):

@@ -1,6 +1,8 @@
 """CSM-1B frame generation rate (config 4): B streams, one prompt block then N single-token frames; audio-seconds (80 ms per frame)
 per wall-second.  python tools/bench_csm.py [--batch 8] [--prompt 64] [--frames 10] [--weights float32|bfloat16|q8|q4] [--group-size 64]
 --top-k / --top-p / --min-p: the sampler (defaults: top-50 alone, the shipped configuration); --rng device: Philox uniforms inside the sampling kernels.
+--row-samplers: the frame loop in table mode (generate_frame(sampler="rows")) with the sampler above stored in every row's table entry, to be
+compared with the same command without the flag (launch-argument mode).
 --weights q8 / q4: the synthetic checkpoint MLX-affine-quantised (quant.quantize_checkpoint) and kept packed in device memory."""
 import argparse
 import json
@@ -28,6 +30,7 @@ ap.add_argument("--top-k", type=int, default=50, help="0: no top-k filter (the w
 ap.add_argument("--top-p", type=float, default=0.0)
 ap.add_argument("--min-p", type=float, default=0.0)
 ap.add_argument("--rng", default="host", choices=["host", "device"], help="host: injected uniforms (resident on the device); device: Philox in the sampling kernels")
+ap.add_argument("--row-samplers", action="store_true", help="read every row's sampler from the device table (set_row_sampler) instead of launch arguments")
 a = ap.parse_args()
 cfg = P.csm_config()
 t0 = time.time()
@@ -77,7 +80,14 @@ from mlx_audio_amd.sesame import make_sampler  # noqa: E402
 sampler = make_sampler(temp=0.9, top_k=a.top_k, top_p=a.top_p, min_p=a.min_p)
 
 
+if a.row_samplers:
+    for b in range(B):
+        model.set_row_sampler(b, sampler, seed=0)
+
+
 def frame(t, m, u):
+    if a.row_samplers:
+        return model.generate_frame(t, m, sampler="rows", device_rng=True) if a.rng == "device" else model.generate_frame(t, m, sampler="rows", uniforms=u)
     if a.rng == "device":
         return model.generate_frame(t, m, sampler=sampler, seed=0)
     return model.generate_frame(t, m, sampler=sampler, uniforms=u)
@@ -113,6 +123,7 @@ torch.cuda.synchronize()
 dt = (time.perf_counter() - ts) / a.frames
 print(json.dumps({"metric": "audio-sec/sec (xRT), CSM-1B frame generation (80 ms of audio per frame and stream), " + wname, "value": B * 0.08 / dt,
                   "ms_per_frame": dt * 1e3, "batch": B, "prompt_tokens": a.prompt, "prefill_ms": prefill_ms, "prefill_ms_second_call": prefill2_ms, "frames_timed": a.frames, "dtype": wname, **storage,
-                  "sampler": {"temp": 0.9, "top_k": a.top_k, "top_p": a.top_p, "min_p": a.min_p, "rng": a.rng},
+                  "sampler": {"temp": 0.9, "top_k": a.top_k, "top_p": a.top_p, "min_p": a.min_p, "rng": a.rng,
+                              "settings": "per-row table" if a.row_samplers else "launch arguments"},
                   "data": "synthetic (random-init CSM-1B weights, random prompt, " + ("injected uniforms)" if a.rng == "host" else "device uniforms)"),
                   "setup_s": {"synth_checkpoint": round(t1 - t0, 1), "load_finalize": round(t2 - t1, 1)}}))
