@@ -30,13 +30,14 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 6   /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 7   /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
                             5: row-mode streaming Mimi decode (kk_mimi_stream_create_rows, kk_mimi_stream_reset_row, kk_mimi_decode_step_rows,
                                kk_mimi_stream_row_frames, kk_mimi_stream_row_snapshot);
-                            6: per-row sampler settings of a CSM batch (kk_csm_set_row_sampler, kk_csm_generate_frame_rows, kk_op_csm_sample_rows) */
+                            6: per-row sampler settings of a CSM batch (kk_csm_set_row_sampler, kk_csm_generate_frame_rows, kk_op_csm_sample_rows);
+                            7: a prefix captured from a live cache row (kk_csm_prefix_capture) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -452,6 +453,11 @@ int kk_csm_row_state(const kk_csm* m, int32_t* pad_out, int32_t* position);
  *     draws at (stream_id, position n + S).  P does not move.  Both entries run their blocks through the PROMPT kernels whatever the row count
  *     (a block of one or two rows is not sent to the single-token kernels), so codes_out and the row's K / V carry, bit for bit, what
  *     kk_csm_generate_frame_ex(B = 1, n + S) computes on the whole prompt from an empty cache.
+ *   kk_csm_prefix_capture (ABI minor 7): the first n positions of LIVE row `row` -- slots [pad[row], pad[row] + n) of K and V in every backbone layer --
+ *     as a new immutable prefix of the same layout, tied to the weight set as kk_csm_prefix_create ties it.  One copy launch; it reads nothing but
+ *     that row's window and writes nothing but its own buffer: P, pad and captured frame steps are untouched, so it is legal between two frames of
+ *     a running batch.  Positions that a single-token step appended carry that step's bits, not a prompt block's; they are the same bits whatever
+ *     row, slot and batch the stream ran in.  Refused: no caches, row out of range, a parked row, n < 1, n > P - pad[row], kv_heads * head_dim % 4.
  * Refusals (live row, row out of range, n + S > P, a prefix of another weight set, a null or destroyed prefix, workspace too small) are decided
  * on the host before any launch. */
 typedef struct kk_csm_prefix kk_csm_prefix;
@@ -461,6 +467,7 @@ int kk_csm_prefix_length(const kk_csm_prefix* p);
 size_t kk_csm_prefix_bytes(const kk_csm_prefix* p);
 int kk_csm_prefix_read(const kk_csm_prefix* p, void* stream, float* dst, size_t dst_bytes);
 void kk_csm_prefix_destroy(kk_csm_prefix* p);
+int kk_csm_prefix_capture(kk_csm* m, void* stream, int row, int n, kk_csm_prefix** out);
 int kk_csm_admit_prefixed(kk_csm* m, void* stream, int row, const kk_csm_prefix* prefix, int S, const int32_t* tokens, const float* tokens_mask,
                           const kk_csm_sampler* sampler, const float* uniforms, int32_t stream_id, void* workspace, size_t workspace_bytes,
                           int32_t* codes_out);

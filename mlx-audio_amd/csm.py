@@ -369,6 +369,25 @@ class SesameModel:
                                                 C.c_void_p(ws.data_ptr()), need, C.byref(h)), "kk_csm_prefix_create")
         return Prefix(self.lib, h, n, self.device, self)
 
+    def capture_prefix(self, row: int, n: int) -> Prefix:
+        """kk_csm_prefix_capture: a copy of the first `n` positions of LIVE cache row `row` (every backbone layer's K and V) as a `Prefix`, the
+        class `make_prefix` returns -- `admit(prefix=)` takes it unchanged.  It reads that row's window and writes its own buffer only: the
+        position, the paddings and the captured frame step are untouched, so it is legal between two frames of a running batch.  ValueError for
+        a row out of range, a parked row, or n outside [1, positions the row holds]."""
+        assert self.caches_are_enabled(), "backbone caches are not enabled"
+        row, n = int(row), int(n)
+        if not 0 <= row < self.max_batch:
+            raise ValueError(f"capture_prefix: row {row} out of range [0, {self.max_batch})")
+        pad, P = self.row_state()
+        if pad[row] >= int(self.cfg["max_seq_len"]):
+            raise ValueError(f"capture_prefix: row {row} is parked")
+        if not 1 <= n <= P - pad[row]:
+            raise ValueError(f"capture_prefix: row {row} holds {P - pad[row]} positions, {n} were asked for")
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self.lib.kk_csm_prefix_capture(self._h, self._stream(), row, n, C.byref(h)), "kk_csm_prefix_capture")
+        return Prefix(self.lib, h, n, self.device, self)
+
     def admit(self, row: int, tokens, tokens_mask, temperature: float = 0.0, top_k: int = 50, uniforms=None, sampler=None, seed: Optional[int] = None,
               stream_id: int = 0, prefix: Optional[Prefix] = None) -> torch.Tensor:
         """The prompt frame of ONE new stream (tokens / tokens_mask [S, n_cb+1]) into the parked cache row `row` of a running batch; the

@@ -28,7 +28,13 @@ are decoded in one aligned round per poll: all rows with a full chunk in one `st
 A sampler per request: `CSMBatcher(..., row_samplers=True)` and `submit(..., sampler=, seed=)`.  The frame step then reads every
 row's settings from a device table (`SesameModel.set_row_sampler`, written at admission) instead of launch arguments: a greedy request, one at
 temp 0.7 / top_p 0.9 and one with a seed of its own run in ONE batch, in the same launches per frame and one captured graph whatever the mix.
-Each request still carries the bits of its own `generate_batch([prompt], sampler=its own, seed=its own)`."""
+Each request still carries the bits of its own `generate_batch([prompt], sampler=its own, seed=its own)`.
+
+A conversation: `sess = batcher.session(context)` and `submit(session=sess, text=...)`.  When a session's turn ends, the K / V of
+its prompt and of the frames it kept are copied out of the row before it is parked (kk_csm_prefix_capture); the next turn is admitted on top of
+that copy and computes only what is new: the frames the cache did not hold yet, the EOS frame, what the session has heard since
+(`sess.hear(segment)`) and the turn's text.  No earlier answer is encoded by Mimi again and no earlier position is computed again.  A session's
+turns are, bit for bit, those of the same session run alone, whatever else the batch runs."""
 from __future__ import annotations
 
 import queue
@@ -116,6 +122,155 @@ class _Stream:
     emitted: int = 0                # frames decoded and emitted
     confirmed: int = 0              # frames a poll has confirmed (below the EOS frame and the limit)
     ended: bool = False             # a poll has seen the stream's end: `confirmed` is its length
+    session: object = None          # CSMSession: the request is a turn of it
+    captured: Optional[dict] = None  # the session's next state (CSMSession._capture), taken before the row was parked
+    capture_error: Optional[BaseException] = None
+
+
+def _no_frames(n_cb: int):
+    return np.zeros((0, n_cb + 1), np.int32), np.zeros((0, n_cb + 1), np.float32)
+
+
+def _cat(a, b):
+    return np.concatenate([a[0], b[0]], 0), np.concatenate([a[1], b[1]], 0)
+
+
+class CSMSession:
+    """One conversation on a `CSMBatcher` (`batcher.session(context, speaker)`): the K / V of everything said so far stay on the device between
+    its turns.  `submit(text)` / `submit_stream(text)` (or the batcher's `submit(session=self, ...)`) run the next turn, `hear(segment)` adds
+    another speaker's turn, `rebuild()` re-prefills the history when it has outgrown the cache, `close()` frees the device copy.
+
+    prefix: None, or what the next turn is admitted on top of -- the K / V captured at the end of the last turn, or the caller's `VoicePrefix`
+    the session started from.  n: the positions it covers.  pending: host frames (tokens, mask), each [k, n_cb+1], that belong to the history but
+    are not in the prefix yet: the next turn's prompt block starts with them.  history: the frames of all n + k positions.  turns: (speaker,
+    text, frames generated) per turn, 0 frames for a turn that was heard.
+
+    One turn at a time: a second `submit` while one is queued or live is refused, and so is `hear`.  A turn that fails, wherever, leaves the
+    session as it was: the state is replaced as a whole when the turn's result is ready.  The session destroys the prefixes it captured (on
+    replace and on `close`), never a caller's `VoicePrefix`."""
+
+    def __init__(self, batcher: "CSMBatcher", context=None, speaker: int = 0):
+        self.batcher, self.engine, self.speaker = batcher, batcher.engine, int(speaker)
+        self.prefix, self.n, self._own = None, 0, False
+        self.pending = _no_frames(self.engine.n_cb)
+        self.history = _no_frames(self.engine.n_cb)
+        self.turns: List[tuple] = []
+        self._starts: List[int] = []  # where in `history` each turn begins
+        self._voice = 0               # leading history frames that are no turn: the caller's voice prefix (`rebuild` keeps them)
+        self._turn: Optional[Future] = None
+        self._closed = False
+        if context is None:
+            return
+        if hasattr(context, "length"):  # a sesame.VoicePrefix: its K / V are on the device already
+            if not self.engine.owns(context):
+                raise ValueError("the voice prefix was made on another model's weights (Model.voice_prefix on this model or one it shares weights with)")
+            self.prefix, self.n = context, int(context.length)
+            self._voice = self.n
+            self.history = (np.array(context.tokens, np.int32), np.array(context.mask, np.float32))
+            return
+        for seg in context:
+            self.hear(seg)
+
+    @property
+    def length(self) -> int:
+        """Positions of the history: what the next turn's text is put behind."""
+        return self.n + int(self.pending[0].shape[0])
+
+    @property
+    def busy(self) -> bool:
+        return self._turn is not None and not self._turn.done()
+
+    def _ready(self, what: str) -> None:
+        if self._closed:
+            raise ValueError(f"{what}: the session is closed")
+        if self.busy:
+            raise ValueError(f"{what}: the session has a turn queued or live; wait for its result first")
+
+    def hear(self, segment, codes=None) -> None:
+        """Another speaker's turn: its text frames, its audio frames and the EOS frame, as `Model.prompt_frames` lays a context segment out.
+        They join `pending`; the frame generator sees them at the next admission.  The clip goes through `Model.encode_audios` here, on the
+        caller's thread, unless `codes` [n_cb, T] (its Mimi codes) are passed."""
+        self._ready("hear")
+        f = self.engine.segment_frames(segment, codes)
+        f = (np.asarray(f[0], np.int32), np.asarray(f[1], np.float32))
+        self._starts.append(int(self.history[0].shape[0]))
+        self.turns.append((int(segment.speaker), segment.text, 0))
+        self.pending, self.history = _cat(self.pending, f), _cat(self.history, f)
+
+    def submit(self, text, **kw) -> Future:
+        kw.setdefault("speaker", self.speaker)
+        return self.batcher.submit(session=self, text=text, **kw)
+
+    def submit_stream(self, text, **kw) -> CSMAudioStream:
+        kw.setdefault("speaker", self.speaker)
+        return self.batcher.submit_stream(session=self, text=text, **kw)
+
+    # ---- the end of a turn (the scheduler's thread) ------------------------------------------------------------------------------------
+    def _capture(self, s: "_Stream", count: int) -> dict:
+        """Before the turn's row is parked: the session's next state.  The prompt had L positions; after len(codes) samples the row holds
+        L + len(codes) - 1 (the last sample was never fed).  Of the `count` kept frames those that were fed are in the cache: the capture
+        takes L + min(count, len(codes) - 1) positions and never one past the kept frames, so it does not depend on how far the row ran
+        beyond its EOS frame.  What the cache lacks -- the last kept frame after a limit end, nothing after an EOS end -- and the EOS frame
+        are the next turn's first prompt frames."""
+        L, n_cb = int(s.length), self.engine.n_cb
+        n = L + min(count, len(s.codes) - 1)
+        prefix = self.engine.capture(s.row, n)
+        try:
+            kept = torch.stack(s.codes[:count]).cpu().numpy()
+            tok, msk = np.zeros((count + 1, n_cb + 1), np.int32), np.zeros((count + 1, n_cb + 1), np.float32)
+            tok[:count, :n_cb] = kept  # (the last row stays zero: the EOS frame, Model._tokenize_audio)
+            msk[:, :n_cb] = 1
+            k = int(self.pending[0].shape[0])
+            said = (s.prompt[0][k:], s.prompt[1][k:])  # the turn's text frames
+            return dict(prefix=prefix, n=n, pending=(tok[n - L:], msk[n - L:]), history=_cat(_cat(self.history, said), (tok, msk)),
+                        turn=(s.speaker, s.text, count))
+        except BaseException:
+            prefix.close()
+            raise
+
+    def _commit(self, c: dict) -> None:
+        if self._closed:
+            c["prefix"].close()
+            return
+        old, own = self.prefix, self._own
+        self._starts.append(int(self.history[0].shape[0]))
+        self.turns.append(c["turn"])
+        self.prefix, self.n, self.pending, self.history, self._own = c["prefix"], c["n"], c["pending"], c["history"], True
+        if own and old is not None:
+            old.close()
+
+    # ---- the way out of a full cache ---------------------------------------------------------------------------------------------------
+    def rebuild(self, keep_last_turns: Optional[int] = None) -> None:
+        """Compute the prefix again from `history` through the prompt kernels (`SesameModel.make_prefix`) -- of the whole history, or of the
+        voice prefix the session started from and its last `keep_last_turns` turns; the dropped turns leave `history` and `turns`.  The kept
+        turns move to new positions and their K / V are a prompt block's from then on: later turns differ from those of the untrimmed
+        session, as any shorter prompt's would.  Runs on the caller's thread, as `Model.voice_prefix` does."""
+        self._ready("rebuild")
+        tok, msk = self.history
+        if keep_last_turns is not None:
+            k = int(keep_last_turns)
+            if k < 0:
+                raise ValueError("keep_last_turns must be >= 0")
+            if k < len(self.turns):
+                cut = self._starts[len(self.turns) - k] if k > 0 else int(tok.shape[0])
+                v = self._voice
+                tok, msk = np.concatenate([tok[:v], tok[cut:]], 0), np.concatenate([msk[:v], msk[cut:]], 0)
+                self.turns = self.turns[len(self.turns) - k:] if k > 0 else []
+                self._starts = [st - (cut - v) for st in self._starts[len(self._starts) - k:]] if k > 0 else []
+        new = self.engine.make_prefix(tok, msk) if tok.shape[0] else None
+        old, own = self.prefix, self._own
+        self.prefix, self.n, self._own = new, int(tok.shape[0]), new is not None
+        self.history, self.pending = (tok, msk), _no_frames(self.engine.n_cb)
+        if own and old is not None:
+            old.close()
+
+    def close(self) -> None:
+        """Free the session's captured prefix; a turn still queued or live fails or is dropped at its end.  Later submits are refused."""
+        self._closed = True
+        if self._own and self.prefix is not None and not self.busy:
+            self.prefix.close()
+        if not self.busy:
+            self.prefix, self._own = None, False
 
 
 class ModelEngine:
@@ -178,6 +333,33 @@ class ModelEngine:
         if getattr(prefix, "root", None) is not self.csm.weights_root():
             raise ValueError("the voice prefix was made on another model's weights (Model.voice_prefix on this model or one it shares weights with)")
         return self.model._tokenize_text_segment(text, speaker)
+
+    def owns(self, prefix) -> bool:
+        """Whether a sesame.VoicePrefix was made on the weights this engine runs on."""
+        return getattr(prefix, "root", None) is self.csm.weights_root()
+
+    def segment_frames(self, segment, codes=None):
+        """A heard turn's frames (text, audio, EOS) for `CSMSession.hear`; `codes`: the clip's Mimi codes, else it is encoded here."""
+        return self.model._tokenize_segment(segment, add_eos=True, codes=codes)
+
+    def make_prefix(self, tokens, mask):
+        """`CSMSession.rebuild`: the frames' K / V through the prompt kernels, as a VoicePrefix."""
+        from .sesame import VoicePrefix
+
+        return VoicePrefix(prefix=self.csm.make_prefix(tokens, mask), tokens=tokens, mask=mask, length=int(tokens.shape[0]), root=self.csm.weights_root())
+
+    def session_prompt(self, sess: CSMSession, text, speaker: int):
+        """The frames a session's turn puts behind the session's prefix: its pending history frames, then the turn's own text segment.  Host
+        work only.  ValueError for a session of another engine."""
+        if sess.engine is not self:
+            raise ValueError("the session belongs to another batcher's engine (CSMBatcher.session on this batcher)")
+        return _cat(sess.pending, self.model._tokenize_text_segment(text, speaker))
+
+    def capture(self, row: int, n: int):
+        """The first `n` positions of live row `row` as a prefix of the session's own (SesameModel.capture_prefix): what `admit(prefix=)` takes."""
+        from .sesame import VoicePrefix
+
+        return VoicePrefix(prefix=self.csm.capture_prefix(row, n), tokens=None, mask=None, length=int(n), root=self.csm.weights_root())
 
     def row_state(self):
         return self.csm.row_state()
@@ -274,7 +456,7 @@ class CSMBatcher:
         self._rows: List[Optional[_Stream]] = [None] * self.max_batch
         self._since_poll = 0
         self.stats = {"frames": 0, "live_row_frames": 0, "admissions": 0, "admit_seconds": 0.0, "shifts": 0, "shift_seconds": 0.0,
-                      "shifts_down": 0, "shifts_up": 0, "polls": 0, "finished": 0, "prefixed_admissions": 0}
+                      "shifts_down": 0, "shifts_up": 0, "polls": 0, "finished": 0, "prefixed_admissions": 0, "session_admissions": 0, "captures": 0}
         self.engine.start(self.max_batch)
         self.chunk = int(stream_chunk_frames) if stream_chunk_frames is not None else None
         self.stream_max_frames = int(stream_max_frames)
@@ -289,8 +471,13 @@ class CSMBatcher:
         self._local = torch.zeros((self.max_batch,), dtype=torch.int64, device=dev)        # stream-local index of the next frame
 
     # ---- requests ---------------------------------------------------------------------------------------------------------------------
+    def session(self, context=None, speaker: int = 0) -> CSMSession:
+        """A conversation on this batcher (`CSMSession`).  context: None, a `Model.voice_prefix(...)` (its K / V are used as they are and stay
+        the caller's), or segments that the session hears before its first turn.  speaker: the default speaker of the session's own turns."""
+        return CSMSession(self, context, speaker)
+
     def submit(self, context=None, text=None, speaker: int = 0, voice_match: Optional[bool] = None, max_audio_length_ms: float = 90_000,
-               seed: Optional[int] = None, stream_id: Optional[int] = None, prompt=None, prefix=None, sampler=None) -> Future:
+               seed: Optional[int] = None, stream_id: Optional[int] = None, prompt=None, prefix=None, sampler=None, session=None) -> Future:
         """Queue one request; the future yields a `StreamResult`.  `prompt` (tokens, mask) skips the prompt building.  rng "host": `seed`
         seeds this stream's generator (None: fresh entropy).  rng "device": the batcher's seed is used, `seed` must be None or equal to it.
         ValueError at once for a request that cannot fit the cache; a request that races `close()` gets a failed future.
@@ -300,18 +487,25 @@ class CSMBatcher:
         and `voice_match=True` (ValueError): the voice_match layout merges the context's text with the request's in front of the audio, so it
         has no shareable prefix.  voice_match defaults to True without a prefix, as before.
         `sampler` (a batcher made with `row_samplers=True`; ValueError otherwise): this request's `make_sampler(...)`, None = the batcher's;
-        with rng "device" such a batcher also takes a `seed` of the request's own.  An out-of-range sampler is a ValueError here."""
-        return self._enqueue(False, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix, sampler)
+        with rng "device" such a batcher also takes a `seed` of the request's own.  An out-of-range sampler is a ValueError here.
+        `session` (`self.session(...)`): the request is the session's next turn.  Its prompt is the session's prefix followed by the session's
+        pending frames and the text segment of `text` / `speaker`; without a prefix (a first turn without a voice prefix) the whole goes through
+        the plain admission.  The length that counts everywhere is session.n + those frames.  When the turn ends its K / V are captured for the
+        next one.  `session` excludes `context`, `prompt`, `prefix` and `voice_match=True`; a session with a turn queued or live, a closed one
+        and one of another batcher are refused (ValueError)."""
+        return self._enqueue(False, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix, sampler, session)
 
     def submit_stream(self, context=None, text=None, speaker: int = 0, voice_match: Optional[bool] = None, max_audio_length_ms: float = 90_000,
-                      seed: Optional[int] = None, stream_id: Optional[int] = None, prompt=None, prefix=None, sampler=None) -> CSMAudioStream:
+                      seed: Optional[int] = None, stream_id: Optional[int] = None, prompt=None, prefix=None, sampler=None,
+                      session=None) -> CSMAudioStream:
         """`submit` with the audio delivered while the stream runs: the same arguments and refusals, a `CSMAudioStream` back.  Needs a batcher
         made with `stream_chunk_frames=N`; the request may not be longer than `stream_max_frames`."""
         if self._dec is None:
             raise ValueError("submit_stream needs a batcher made with stream_chunk_frames=N")
-        return self._enqueue(True, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix, sampler)
+        return self._enqueue(True, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix, sampler, session)
 
-    def _enqueue(self, _streaming: bool, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix, sampler=None):
+    def _enqueue(self, _streaming: bool, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix, sampler=None,
+                 session=None):
         max_frames = int(max_audio_length_ms / 80)
         if sampler is not None:
             if not self.row_samplers:
@@ -319,7 +513,18 @@ class CSMBatcher:
             _check_sampler(sampler)
         elif self.row_samplers:
             sampler = self.sampler
-        if prefix is not None:
+        if session is not None:
+            if context or prompt is not None or prefix is not None or voice_match:
+                raise ValueError("session= carries the conversation: it excludes context, prompt, prefix and voice_match=True")
+            if text is None:
+                raise ValueError("a session's turn needs its own text")
+            session._ready("submit")
+            voice_match = False
+            prompt = self.engine.session_prompt(session, text, speaker)
+            prompt = (np.asarray(prompt[0], np.int32), np.asarray(prompt[1], np.float32))
+            prefix = session.prefix
+            length = int(session.n) + int(prompt[0].shape[0])
+        elif prefix is not None:
             if context or prompt is not None or voice_match:
                 raise ValueError("prefix= stands for the context of the non-voice_match layout: it excludes context, prompt and voice_match=True")
             if text is None:
@@ -335,7 +540,8 @@ class CSMBatcher:
             length = int(self.engine.prompt_length(context, text, speaker, True if voice_match is None else voice_match))
         limit = self.engine.max_pos - max_frames
         if length >= limit:
-            raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {limit}")  # sesame.py:755-758
+            raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {limit}"  # sesame.py:755-758
+                             + ("; session.rebuild(keep_last_turns=k) re-prefills a shorter history" if session is not None else ""))
         if max_frames < 1 or length < 1:
             raise ValueError("a request needs a prompt and at least one frame")
         if _streaming and max_frames > self.stream_max_frames:
@@ -352,13 +558,16 @@ class CSMBatcher:
             if self._closed:
                 fut.set_exception(RuntimeError("CSMBatcher is closed"))
                 return audio if _streaming else fut
+            if session is not None:
+                session._ready("submit")  # (again, under the lock: two threads on one session)
+                session._turn = fut
             if stream_id is None:
                 stream_id = self._next_id
             self._next_id = max(self._next_id, int(stream_id)) + 1
             self._queue.append(_Stream(future=fut, context=context, text=text, speaker=int(speaker),
                                        voice_match=True if voice_match is None else bool(voice_match),
                                        max_frames=max_frames, seed=seed, stream_id=int(stream_id), length=length, t0=time.perf_counter(),
-                                       prompt=prompt, prefix=prefix, audio=audio, sampler=sampler))
+                                       prompt=prompt, prefix=prefix, audio=audio, sampler=sampler, session=session))
             self._wake.notify()
         return audio if _streaming else fut
 
@@ -378,6 +587,7 @@ class CSMBatcher:
             s.confirmed = min(eos if eos >= 0 else len(s.codes), s.max_frames)
             s.ended = eos >= 0 or len(s.codes) >= s.max_frames
             if s.ended:
+                self._turn_end(s, s.confirmed)
                 self.engine.park(s.row)
                 self._rows[s.row] = None  # (the decoder row keeps its state until the next admission resets it: the tail is decoded below)
         if streaming:
@@ -389,6 +599,7 @@ class CSMBatcher:
             if eos < 0 and len(s.codes) < s.max_frames:
                 continue
             count = min(eos if eos >= 0 else len(s.codes), s.max_frames)  # frames past the EOS frame / the limit are dropped
+            self._turn_end(s, count)
             self.engine.park(s.row)
             self._rows[s.row] = None
             done.setdefault(count, []).append(s)
@@ -404,13 +615,37 @@ class CSMBatcher:
                 if pcm is not None:
                     self.engine.synchronize()
                 for j, s in enumerate(group):
-                    s.future.set_result(StreamResult(audio=pcm[j] if pcm is not None else None, frames=count, codes=codes[j],
-                                                     sample_rate=self.engine.sample_rate, stream_id=s.stream_id, row=s.row,
-                                                     processing_time_seconds=time.perf_counter() - s.t0))
+                    self._resolve(s, StreamResult(audio=pcm[j] if pcm is not None else None, frames=count, codes=codes[j],
+                                                  sample_rate=self.engine.sample_rate, stream_id=s.stream_id, row=s.row,
+                                                  processing_time_seconds=time.perf_counter() - s.t0))
             except Exception as e:  # noqa: BLE001
                 for s in group:
                     if not s.future.done():
                         s.future.set_exception(e)
+
+    # ---- sessions ----------------------------------------------------------------------------------------------------------
+    def _turn_end(self, s: _Stream, count: int) -> None:
+        """A session's turn has ended with `count` kept frames and its row is about to be parked: copy its K / V out first (a parked row has no
+        window).  The copy becomes the session's prefix when the turn's result is ready (`_resolve`); if the turn fails on the way there it
+        is destroyed and the session stays as it was."""
+        if s.session is None or count == 0 or s.future.done():
+            return
+        try:
+            s.captured = c = s.session._capture(s, count)
+            self.stats["captures"] += 1
+            s.future.add_done_callback(lambda f: c["prefix"].close() if f.exception() is not None else None)
+        except Exception as e:  # noqa: BLE001
+            s.capture_error = e
+
+    def _resolve(self, s: _Stream, result: StreamResult) -> None:
+        if s.future.done():
+            return
+        if s.capture_error is not None:
+            s.future.set_exception(s.capture_error)
+            return
+        if s.captured is not None:
+            s.session._commit(s.captured)  # before the result: whoever waits on it finds the session ready for the next turn
+        s.future.set_result(result)
 
     # ---- streaming audio (DESIGN 8d-4) --------------------------------------------------------------------------------------------------
     def _emit(self, streams: List[_Stream]) -> None:
@@ -436,9 +671,9 @@ class CSMBatcher:
             if s.confirmed == 0:
                 s.future.set_exception(AssertionError("No audio generated"))
                 continue
-            s.future.set_result(StreamResult(audio=torch.cat(s.chunks), frames=s.confirmed, codes=torch.stack(s.codes[: s.confirmed], dim=1),
-                                             sample_rate=self.engine.sample_rate, stream_id=s.stream_id, row=s.row,
-                                             processing_time_seconds=time.perf_counter() - s.t0))
+            self._resolve(s, StreamResult(audio=torch.cat(s.chunks), frames=s.confirmed, codes=torch.stack(s.codes[: s.confirmed], dim=1),
+                                          sample_rate=self.engine.sample_rate, stream_id=s.stream_id, row=s.row,
+                                          processing_time_seconds=time.perf_counter() - s.t0))
 
     def _decode_round(self, group: List[_Stream], F: int) -> None:
         """One step of the row decoder: F frames for the rows of `group`, the other rows inactive.  A failure fails the group's requests
@@ -534,6 +769,7 @@ class CSMBatcher:
                     continue
             self.stats["admissions"] += 1
             self.stats["prefixed_admissions"] += s.prefix is not None
+            self.stats["session_admissions"] += s.session is not None
             s.row = row
             s.codes = [codes]
             self._rows[row] = s

@@ -818,6 +818,24 @@ __global__ __launch_bounds__(256) void prefix_restore_kernel(const float4* src, 
     if (i0 + 256 * u < seg4) d[i0 + 256 * u] = r[u];
 }
 
+// kk_csm_prefix_capture: the mirror of prefix_restore_kernel.  The first n slots of ONE live cache row (`kc` / `vc`: the caller has added row and
+// first slot) leave for a compact prefix buffer `dst` ([layer][K|V][n][KV hd] fp32), every layer's K and V in one launch: blockIdx.y = 2 layer +
+// (0 K, 1 V).  Same work division: 16 KiB per workgroup, four 16-byte columns 4 KiB apart per thread, loads ahead of stores, the tail checked.
+// It reads nothing outside the row's window [first slot, first slot + n) and writes nothing but `dst`.
+__global__ __launch_bounds__(256) void prefix_capture_kernel(const float* kc, const float* vc, float4* dst, long long layer_pitch4, long long seg4) {
+  const int z = blockIdx.y;
+  const float4* s = (const float4*)((z & 1) ? vc : kc) + (long long)(z >> 1) * layer_pitch4;
+  float4* d = dst + (long long)z * seg4;
+  const long long i0 = (long long)blockIdx.x * 1024 + threadIdx.x;
+  float4 r[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+    if (i0 + 256 * u < seg4) r[u] = s[i0 + 256 * u];
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+    if (i0 + 256 * u < seg4) d[i0 + 256 * u] = r[u];
+}
+
 // silu(gate) * up, gu [rows][2I] -> [rows][I]
 __global__ __launch_bounds__(256) void swiglu_kernel(const float* gu, int I, long long n, float* out) {
   const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -3288,6 +3306,50 @@ extern "C" int kk_csm_admit_prefixed(kk_csm* m, void* stream, int row, const kk_
   RowView view(m->bb, row, P - S);
   Run r(m, st, 1, workspace, workspace_bytes);
   return run_frame(r, S, tokens, tokens_mask, sc, uniforms, dev_rng ? m->seed_dev : nullptr, dev_rng ? m->admit_sid_dev : nullptr, codes_out, n + S, true);
+}
+
+// The first n positions of live row `row` as a new prefix: slots [pad[row], pad[row] + n) of every layer's K and V, one launch.  The row's window is
+// [pad[row], P), so n <= P - pad[row] keeps the read inside it; the write goes to the new buffer alone.  P, pad, the frame-step graph and its key are
+// untouched: legal between two frames of a running batch.
+extern "C" int kk_csm_prefix_capture(kk_csm* m, void* stream, int row, int n, kk_csm_prefix** out) {
+  if (!m || !m->finalized) return kk_fail("kk_csm_prefix_capture: model not finalized");
+  if (!out) return kk_fail("kk_csm_prefix_capture: bad argument");
+  if (m->max_batch < 1 || !m->bb.kc || !m->bb.vc) return kk_fail("kk_csm_prefix_capture: call kk_csm_setup_caches first");
+  if (row < 0 || row >= m->max_batch) return kk_fail("kk_csm_prefix_capture: row out of range");
+  const kk_llama_args& a = m->bb.a;
+  const int P = m->bb.offset, mp = m->bb.max_pos, kvw = a.num_kv_heads * a.head_dim, pad = m->pad_host[row];
+  if (pad >= mp) return kk_fail("kk_csm_prefix_capture: the row is parked");
+  if (n < 1) return kk_fail("kk_csm_prefix_capture: n must be at least 1");
+  if (pad < 0 || n > P - pad) return kk_fail("kk_csm_prefix_capture: the row holds fewer than n positions");
+  if (kvw % 4 != 0) return kk_fail("kk_csm_prefix_capture: kv_heads * head_dim must be a multiple of 4");
+  kk_csm_prefix* p = new (std::nothrow) kk_csm_prefix();
+  if (!p) return kk_fail("kk_csm_prefix_capture: out of memory");
+  p->n = n; p->layers = a.num_layers; p->kvw = kvw; p->weights_id = m->weights_id;
+  if (hipMalloc((void**)&p->buf, kk_csm_prefix_bytes_of(p)) != hipSuccess) {
+    delete p;
+    return kk_fail("kk_csm_prefix_capture: hipMalloc failed");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  int rc = flush_pending(m, st);
+  if (rc == 0) {
+    const size_t at = ((size_t)row * mp + (size_t)pad) * kvw;
+    const long long seg4 = (long long)n * kvw / 4, pitch4 = (long long)m->max_batch * mp * kvw / 4;
+    hipLaunchKernelGGL(prefix_capture_kernel, dim3((unsigned)((seg4 + 1023) / 1024), 2 * a.num_layers), dim3(256), 0, st, m->bb.kc + at, m->bb.vc + at,
+                       (float4*)p->buf, pitch4, seg4);
+    rc = hipGetLastError() == hipSuccess ? 0 : kk_fail("kk_csm_prefix_capture: launch failed");
+  }
+  if (rc != 0) {
+    (void)hipStreamSynchronize(st);  // nothing in flight may still write the buffer
+    (void)hipFree(p->buf);
+    delete p;
+    return rc;
+  }
+  {
+    std::lock_guard<std::mutex> lk(g_prefix_mu);
+    g_prefixes.insert(p);
+  }
+  *out = p;
+  return 0;
 }
 
 extern "C" int kk_csm_debug_timestamps(unsigned long long* buf, int capacity) {

@@ -13,7 +13,12 @@ again; per run wall, audio-s/s, frame steps and (a second, profiled run) the mea
 --stream-chunk N: instead, continuous batching WITH the codec (synthetic mimi_202407 weights), the same workload twice: plain `submit` (one
 offline Mimi.decode per finished stream; time to first audio = submit -> result) and `submit_stream` in chunks of N frames (time to first
 audio = submit -> first chunk); p50 / p95 of both over the requests, audio-s/s of both, and the cost of one row-mode decode step at --batch rows
-against a Mimi.decode_step of the same batch and F.  Written to profiles/csm_serve_stream_bench.json."""
+against a Mimi.decode_step of the same batch and F.  Written to profiles/csm_serve_stream_bench.json.
+--sessions N --turns K: instead, N dialogues of K turns (24 text frames and 25 imposed frames per turn) through one batcher of N rows, turn k of
+all dialogues queued together: as sessions (`submit(session=)`: a turn is admitted on the K / V captured at the end of the one before) / with
+every turn resubmitted as a plain request whose `prompt` is the full history frames (what a caller does without sessions, minus Mimi.encode) /
+as sessions again; per run wall, audio-s/s and (a second, profiled run) the mean admission ms BY TURN NUMBER.  Written to
+profiles/csm_serve_session_bench.json."""
 import argparse
 import json
 import os
@@ -40,10 +45,12 @@ ap.add_argument("--max-seq-len", type=int, default=512)
 ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--prefix", type=int, default=0, help="frames of a voice prefix shared by every request (0: the static / continuous comparison)")
 ap.add_argument("--stream-chunk", type=int, default=0, help="frames per audio chunk: time to first audio of submit_stream against plain submit")
+ap.add_argument("--sessions", type=int, default=0, help="dialogues run as sessions against full-history resubmission (with --turns)")
+ap.add_argument("--turns", type=int, default=4)
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 if a.out is None:
-    name = "csm_serve_stream_bench.json" if a.stream_chunk else "csm_serve_prefix_bench.json" if a.prefix else "csm_serve_bench.json"
+    name = "csm_serve_session_bench.json" if a.sessions else "csm_serve_stream_bench.json" if a.stream_chunk else "csm_serve_prefix_bench.json" if a.prefix else "csm_serve_bench.json"
     a.out = os.path.join(ROOT, "profiles", name)
 
 cfg = dict(P.csm_config(), max_seq_len=a.max_seq_len)
@@ -202,6 +209,68 @@ def bench_stream():
         res["streamed"]["xrt"] / plain, abs(res["plain_first"]["xrt"] - res["plain_last"]["xrt"]))
     return res
 
+
+def bench_sessions():
+    N, K, T, F = a.sessions, a.turns, 24, 25
+    texts = [[rng.integers(0, cfg["text_vocab_size"], T).tolist() for _ in range(K)] for _ in range(N)]
+
+    def run(form, profile, histories=None):
+        """form "session" or "history"; returns wall, stats, per-turn admission seconds and (session form) every turn's prompt as a plain request"""
+        bat = loop.serve(max_batch=N, rng="device", sampler=sampler, seed=a.seed, stop_on_eos=False, decode=False, profile=profile)
+        sess = [bat.session() for _ in range(N)] if form == "session" else None
+        admit, prompts_of = [], []
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for k in range(K):
+            before = bat.stats["admit_seconds"]
+            if form == "session":
+                prompts_of.append([tuple(np.concatenate([h, x], 0) for h, x in zip(s.history, loop._tokenize_text_segment(texts[i][k], 0)))
+                                   for i, s in enumerate(sess)])
+                futs = [s.submit(texts[i][k], max_audio_length_ms=80 * F, stream_id=i) for i, s in enumerate(sess)]
+            else:
+                futs = [bat.submit(None, None, prompt=histories[k][i], max_audio_length_ms=80 * F, stream_id=i) for i in range(N)]
+            bat.run_until_idle()
+            assert [f.result(timeout=0).frames for f in futs] == [F] * N
+            admit.append((bat.stats["admit_seconds"] - before) / N)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t
+        st = dict(bat.stats)
+        for s in sess or []:
+            s.close()
+        bat.close()
+        return dt, st, admit, prompts_of
+
+    _, _, _, histories = run("session", False)  # warm-up; its turns' prompts are what the history form resubmits
+    run("history", False, histories)
+
+    def both(form):
+        dt, st, _, _ = run(form, False, histories)
+        _, _, admit, _ = run(form, True, histories)
+        return {"wall_s": dt, "xrt": 0.08 * F * N * K / dt, "frame_steps": st["frames"], "admissions": st["admissions"],
+                "session_admissions": st["session_admissions"], "captures": st["captures"], "admit_ms_by_turn": [1e3 * x for x in admit],
+                "shifts_down": st["shifts_down"], "shifts_up": st["shifts_up"]}
+
+    res = {"metric": "CSM-1B serving, multi-turn dialogues: sessions vs full-history resubmission, " + a.weights, "sessions": N, "turns": K, "batch": N,
+           "max_seq_len": a.max_seq_len, "text_frames_per_turn": T, "frames_per_turn": F, "prompt_frames_by_turn": [int(h[0][0].shape[0]) for h in histories],
+           "audio_s": 0.08 * F * N * K, "order": ["session_first", "history", "session_last"],
+           "data": "synthetic (random-init CSM-1B weights, random text frames, imposed stream lengths, device uniforms, no codec)"}
+    res["session_first"], res["history"], res["session_last"] = both("session"), both("history"), both("session")
+    last = [res[k]["admit_ms_by_turn"][-1] for k in ("session_first", "session_last")]
+    res["value"] = 0.5 * sum(last) / res["history"]["admit_ms_by_turn"][-1]
+    res["value_is"] = "session / history mean admission ms of the last turn (session: mean of the two runs; their spread %.3f ms)" % abs(last[0] - last[1])
+    return res
+
+
+if a.sessions:
+    if a.prefix or a.stream_chunk or a.turns < 1 or a.turns * 50 + 25 >= a.max_seq_len:
+        sys.exit(f"--sessions excludes --prefix / --stream-chunk and needs turns * 50 + 25 < --max-seq-len {a.max_seq_len}")
+    out = bench_sessions()
+    print(json.dumps(out))
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    sys.exit(0)
 
 if a.stream_chunk:
     if a.prefix or not 1 <= a.stream_chunk <= min(LENGTHS):
