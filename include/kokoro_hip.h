@@ -30,14 +30,15 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 7   /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 8   /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
                             5: row-mode streaming Mimi decode (kk_mimi_stream_create_rows, kk_mimi_stream_reset_row, kk_mimi_decode_step_rows,
                                kk_mimi_stream_row_frames, kk_mimi_stream_row_snapshot);
                             6: per-row sampler settings of a CSM batch (kk_csm_set_row_sampler, kk_csm_generate_frame_rows, kk_op_csm_sample_rows);
-                            7: a prefix captured from a live cache row (kk_csm_prefix_capture) */
+                            7: a prefix captured from a live cache row (kk_csm_prefix_capture);
+                            8: a finished admission moved between two generators' cache rows (kk_csm_admit_transfer) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -458,6 +459,14 @@ int kk_csm_row_state(const kk_csm* m, int32_t* pad_out, int32_t* position);
  *     that row's window and writes nothing but its own buffer: P, pad and captured frame steps are untouched, so it is legal between two frames of
  *     a running batch.  Positions that a single-token step appended carry that step's bits, not a prompt block's; they are the same bits whatever
  *     row, slot and batch the stream ran in.  Refused: no caches, row out of range, a parked row, n < 1, n > P - pad[row], kv_heads * head_dim % 4.
+ *   kk_csm_admit_transfer (ABI minor 8): an admission prefilled on ANOTHER generator of the same weights (kk_csm_share) enters this one.  `src_row` of
+ *     `src` is a live row whose window [pad_s, P_s) holds the L = P_s - pad_s positions of a finished kk_csm_admit / kk_csm_admit_prefixed; `row` of
+ *     `m` is parked.  Sets pad[row] = P - L and copies the window into slots [P - L, P) of `row` in every backbone layer's K and V: one copy launch,
+ *     no prompt block, no depth decoder, no sampler.  P, the other rows, the frame-step graph and its key are untouched (legal between two replays);
+ *     `src_row` stays live, the caller parks it.  The entry orders the two streams itself: `stream` waits for what `src_stream` holds at the call,
+ *     and `src_stream` waits for the copy (events owned by `m`; no allocation and no synchronisation on this path).  Refused on the host, with
+ *     nothing changed: m == src, no caches on either side, a row out of range, `row` live, `src_row` parked, L < 1, L > P (kk_csm_shift_caches by
+ *     L - P first), different weight sets or K / V geometry, kv_heads * head_dim not a multiple of 4.
  * Refusals (live row, row out of range, n + S > P, a prefix of another weight set, a null or destroyed prefix, workspace too small) are decided
  * on the host before any launch. */
 typedef struct kk_csm_prefix kk_csm_prefix;
@@ -468,6 +477,7 @@ size_t kk_csm_prefix_bytes(const kk_csm_prefix* p);
 int kk_csm_prefix_read(const kk_csm_prefix* p, void* stream, float* dst, size_t dst_bytes);
 void kk_csm_prefix_destroy(kk_csm_prefix* p);
 int kk_csm_prefix_capture(kk_csm* m, void* stream, int row, int n, kk_csm_prefix** out);
+int kk_csm_admit_transfer(kk_csm* m, void* stream, int row, kk_csm* src, void* src_stream, int src_row);
 int kk_csm_admit_prefixed(kk_csm* m, void* stream, int row, const kk_csm_prefix* prefix, int S, const int32_t* tokens, const float* tokens_mask,
                           const kk_csm_sampler* sampler, const float* uniforms, int32_t stream_id, void* workspace, size_t workspace_bytes,
                           int32_t* codes_out);

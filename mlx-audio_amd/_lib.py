@@ -118,6 +118,7 @@ SIGNATURES = {
     "kk_csm_prefix_read": (_i, [_vp, _vp, _vp, _sz]),
     "kk_csm_prefix_destroy": (None, [_vp]),
     "kk_csm_prefix_capture": (_i, [_vp, _vp, _i, _i, C.POINTER(_vp)]),
+    "kk_csm_admit_transfer": (_i, [_vp, _vp, _i, _vp, _vp, _i]),
     "kk_csm_admit_prefixed": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, C.POINTER(KKCsmSampler), _vp, C.c_int32, _vp, _sz, _vp]),
     "kk_csm_park_row": (_i, [_vp, _i]),
     "kk_csm_reset_caches_parked": (_i, [_vp]),
@@ -214,7 +215,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 7:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 8:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -443,6 +443,22 @@ class SesameModel:
                                         C.c_void_p(ws.data_ptr()), need, C.c_void_p(codes.data_ptr())), "kk_csm_admit")
         return codes
 
+    def admit_transfer(self, row: int, src: "SesameModel", src_row: int = 0, src_stream=None) -> None:
+        """kk_csm_admit_transfer: the finished admission in live row `src_row` of `src` -- another generator on the same weights (`share()`),
+        which ran `admit` on `src_stream` (a torch.cuda.Stream; None: the current one) -- enters the parked row `row` of this one: its window
+        is copied below the position, in every layer's K and V, on the current stream.  One copy launch; the position, the other rows and the
+        captured frame step are untouched.  The entry orders the two streams (this one waits for the admission, `src_stream` waits for the copy);
+        `src_row` stays live: park it.  ValueError for what the library refuses on the host (the same generator, a row out of range, a live
+        `row`, a parked `src_row`, a window longer than the position -- `shift` first --, other weights); nothing is changed then."""
+        assert self.caches_are_enabled(), "backbone caches are not enabled"
+        if not isinstance(src, SesameModel) or not src.caches_are_enabled():
+            raise ValueError("admit_transfer: src must be a SesameModel with caches")
+        with torch.cuda.device(self.device):
+            sst = C.c_void_p((src_stream if src_stream is not None else torch.cuda.current_stream(self.device)).cuda_stream)
+            rc = self.lib.kk_csm_admit_transfer(self._h, self._stream(), int(row), src._h, sst, int(src_row))
+        if rc != 0:
+            raise ValueError((self.lib.kk_last_error() or b"kk_csm_admit_transfer failed").decode())
+
     def debug_logits(self) -> torch.Tensor:
         B, ncb, V = self._last_B, self.cfg["audio_num_codebooks"], self.cfg["audio_vocab_size"]
         out = torch.empty((ncb, B, V), dtype=torch.float32, device=self.device)

@@ -34,7 +34,13 @@ A conversation: `sess = batcher.session(context)` and `submit(session=sess, text
 its prompt and of the frames it kept are copied out of the row before it is parked (kk_csm_prefix_capture); the next turn is admitted on top of
 that copy and computes only what is new: the frames the cache did not hold yet, the EOS frame, what the session has heard since
 (`sess.hear(segment)`) and the turn's text.  No earlier answer is encoded by Mimi again and no earlier position is computed again.  A session's
-turns are, bit for bit, those of the same session run alone, whatever else the batch runs."""
+turns are, bit for bit, those of the same session run alone, whatever else the batch runs.
+
+Admissions off the batch's stream: `CSMBatcher(..., overlap_admission=True, prefill_lanes=1)`.  The head of the queue is prefilled
+in a LANE -- a `share()` generator with one cache row -- on a side stream while the batch keeps stepping: the same `admit` / `admit(prefix=)`
+calls, so the same first frame and K / V.  When a row is free and the lane's event has completed, the request is COMMITTED: one copy launch
+moves the lane's window into the row (kk_csm_admit_transfer), which is all the batch's stream pays for the admission.  FIFO order is kept, and
+every request still carries the bits of its own `generate_batch([prompt])` run."""
 from __future__ import annotations
 
 import queue
@@ -125,6 +131,9 @@ class _Stream:
     session: object = None          # CSMSession: the request is a turn of it
     captured: Optional[dict] = None  # the session's next state (CSMSession._capture), taken before the row was parked
     capture_error: Optional[BaseException] = None
+    lane: int = -1                  # overlap_admission: the prefill lane that holds the request until it is committed
+    prefill: object = None          # what the engine's `prefill` returned for it
+    admit_args: Optional[tuple] = None  # (sampler, seed) of its admission: what `set_row_sampler` takes at the commit
 
 
 def _no_frames(n_cb: int):
@@ -346,7 +355,15 @@ class ModelEngine:
         """`CSMSession.rebuild`: the frames' K / V through the prompt kernels, as a VoicePrefix."""
         from .sesame import VoicePrefix
 
-        return VoicePrefix(prefix=self.csm.make_prefix(tokens, mask), tokens=tokens, mask=mask, length=int(tokens.shape[0]), root=self.csm.weights_root())
+        return self._mark(VoicePrefix(prefix=self.csm.make_prefix(tokens, mask), tokens=tokens, mask=mask, length=int(tokens.shape[0]),
+                                      root=self.csm.weights_root()))
+
+    def _mark(self, vp):
+        """With prefill lanes: an event behind the launch that wrote the prefix, for the side stream to wait on (`prefill`)."""
+        if getattr(self, "_side", None) is not None:
+            vp.ready = torch.cuda.Event()
+            vp.ready.record(torch.cuda.current_stream(self.device))
+        return vp
 
     def session_prompt(self, sess: CSMSession, text, speaker: int):
         """The frames a session's turn puts behind the session's prefix: its pending history frames, then the turn's own text segment.  Host
@@ -359,7 +376,7 @@ class ModelEngine:
         """The first `n` positions of live row `row` as a prefix of the session's own (SesameModel.capture_prefix): what `admit(prefix=)` takes."""
         from .sesame import VoicePrefix
 
-        return VoicePrefix(prefix=self.csm.capture_prefix(row, n), tokens=None, mask=None, length=int(n), root=self.csm.weights_root())
+        return self._mark(VoicePrefix(prefix=self.csm.capture_prefix(row, n), tokens=None, mask=None, length=int(n), root=self.csm.weights_root()))
 
     def row_state(self):
         return self.csm.row_state()
@@ -404,6 +421,79 @@ class ModelEngine:
     def synchronize(self) -> None:
         torch.cuda.current_stream(self.device).synchronize()
 
+    # ---- prefill lanes: admissions computed on a side stream, committed by one copy -------------------------------------------
+    def open_lanes(self, n: int) -> None:
+        """`n` one-row generators on this model's weights (`share()` + `setup_caches(1)`) and ONE side stream that runs all their prefills.
+        A second stream runs no kernel: it stands for "this lane's prefill is done" at a commit (`commit`)."""
+        self._side = torch.cuda.Stream(self.device)
+        self._hand = torch.cuda.Stream(self.device)
+        self._lanes = []
+        for _ in range(int(n)):
+            g = self.csm.share()
+            g.setup_caches(1)
+            self._lanes.append(g)
+
+    def prefill(self, lane: int, prompt, sampler, uniforms, seed, stream_id: int, prefix=None, timed: bool = False):
+        """Begin a request's admission in lane `lane`, on the side stream: what the batcher does on its own generator for a plain admission --
+        `reset_caches_parked`, a bare position move to the prompt's length, `admit` / `admit(prefix=)` into row 0 -- and an event behind it.
+        Nothing here waits for the device: the frames go up from pinned memory.  Returns the handle `prefill_ready` and `commit` take."""
+        g, dev = self._lanes[lane], self.device
+        L = int(prompt[0].shape[0]) + (int(prefix.length) if prefix is not None else 0)
+
+        def up(a, dtype):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype)).pin_memory().to(dev, non_blocking=True)
+
+        main = torch.cuda.current_stream(dev)
+        if prefix is not None:  # its K / V were written on the batch's stream (a capture, `make_prefix`): the lane reads them behind that point
+            ready = getattr(prefix, "ready", None)
+            if ready is None:
+                ready = prefix.ready = torch.cuda.Event()
+                ready.record(main)
+            self._side.wait_event(ready)
+        with torch.cuda.stream(self._side):
+            start = None
+            if timed:
+                start = torch.cuda.Event(enable_timing=True)
+                start.record()
+            g.reset_caches_parked()
+            g.shift(L)  # nothing is live in the lane: only its position moves
+            u = up(np.asarray(uniforms, np.float32).reshape(-1), np.float32) if uniforms is not None else None
+            codes = g.admit(0, up(prompt[0], np.int32), up(prompt[1], np.float32), sampler=sampler, uniforms=u, seed=seed, stream_id=stream_id,
+                            prefix=prefix.prefix if prefix is not None else None)
+            end = torch.cuda.Event(enable_timing=timed)
+            end.record()
+        codes.record_stream(main)  # read by the batch's stream behind the commit
+        return {"codes": codes, "start": start, "end": end}
+
+    def prefill_ready(self, handle, wait: bool = False) -> bool:
+        """Whether the lane's admission has completed (`event.query()`: no sync).  wait: block until it has -- only while no row is live."""
+        if wait:
+            handle["end"].synchronize()
+            return True
+        return bool(handle["end"].query())
+
+    def commit(self, row: int, lane: int, handle) -> torch.Tensor:
+        """The lane's finished admission enters cache row `row` (`SesameModel.admit_transfer`: one copy launch on the batch's stream, ordered
+        behind the lane's work and ahead of the lane's next use) and the lane's row is parked.  Returns the admission's codes [n_cb].
+        The entry orders the copy behind everything its source stream holds at the call.  On the side stream that would include the prefills
+        other lanes have queued behind this one, so the source stream handed over is the hand-off stream, which waits for THIS prefill's
+        event only; the side stream then waits for the hand-off stream, which the entry has put behind the copy."""
+        g = self._lanes[lane]
+        self._hand.wait_event(handle["end"])
+        self.csm.admit_transfer(row, g, 0, self._hand)
+        self._side.wait_stream(self._hand)
+        g.park(0)
+        return handle["codes"]
+
+    def prefill_seconds(self, handle) -> float:
+        """Device time of a completed `prefill(timed=True)` on the side stream."""
+        return float(handle["start"].elapsed_time(handle["end"])) * 1e-3 if handle["start"] is not None else 0.0
+
+    def close_lanes(self) -> None:
+        if getattr(self, "_side", None) is not None:
+            self._side.synchronize()
+        self._lanes, self._side, self._hand = [], None, None
+
 
 def _check_sampler(sampler) -> None:
     """The ranges the library accepts (kk_csm_sampler), checked where the request is made"""
@@ -419,7 +509,7 @@ def _check_sampler(sampler) -> None:
 class CSMBatcher:
     def __init__(self, model, max_batch: int = 8, eos_check_interval: int = 8, rng: str = "device", sampler=None, seed: int = 0,
                  stop_on_eos: bool = True, decode: bool = True, profile: bool = False, engine=None, stream_chunk_frames: Optional[int] = None,
-                 stream_max_frames: int = 1125, row_samplers: bool = False):
+                 stream_max_frames: int = 1125, row_samplers: bool = False, overlap_admission: bool = False, prefill_lanes: int = 1):
         """model: a loaded sesame.Model (its frame generator's caches are taken over; use `model.share()` for a generator of its own).
         sampler: `make_sampler(...)` for every stream of the batch (default temp 0.9 / top_k 50; with `row_samplers` the default of a request).  seed: the device generator's seed (rng
         "device": one seed per batcher, streams differ by their ids).  profile: time admissions and shifts (one sync each) into `stats`.
@@ -429,7 +519,12 @@ class CSMBatcher:
         cache holds that many frames per row; 1125 = the default 90 s limit of a request).
         row_samplers: True lets `submit` / `submit_stream` take a `sampler` (None: the batcher's) and, with rng "device", a `seed` of the
         request's own (None: the batcher's); the frame step then reads each row's settings from the device table (`set_row_sampler`).  Off by
-        default: the frame step is the launch-argument one, and a per-request sampler or a foreign seed is refused."""
+        default: the frame step is the launch-argument one, and a per-request sampler or a foreign seed is refused.
+        overlap_admission: True prefills every request in one of `prefill_lanes` lanes (a `share()` generator with one cache row each, one side
+        stream for all) while the batch keeps stepping, and commits it with one copy when a row is free and the lane is done.
+        Off by default: no lane is made and admissions run on the batch's stream."""
+        if overlap_admission and int(prefill_lanes) < 1:
+            raise ValueError("prefill_lanes must be >= 1")
         if rng not in ("host", "device"):
             raise ValueError(f"rng must be 'host' or 'device', not {rng!r}")
         if max_batch < 1 or eos_check_interval < 1:
@@ -456,8 +551,17 @@ class CSMBatcher:
         self._rows: List[Optional[_Stream]] = [None] * self.max_batch
         self._since_poll = 0
         self.stats = {"frames": 0, "live_row_frames": 0, "admissions": 0, "admit_seconds": 0.0, "shifts": 0, "shift_seconds": 0.0,
-                      "shifts_down": 0, "shifts_up": 0, "polls": 0, "finished": 0, "prefixed_admissions": 0, "session_admissions": 0, "captures": 0}
+                      "shifts_down": 0, "shifts_up": 0, "polls": 0, "finished": 0, "prefixed_admissions": 0, "session_admissions": 0, "captures": 0,
+                      "overlapped_admissions": 0, "commit_seconds": 0.0, "prefill_seconds": 0.0}
         self.engine.start(self.max_batch)
+        self.overlap = bool(overlap_admission)
+        self._lane_of: List[Optional[_Stream]] = []   # per lane: the request it holds
+        self._inflight: Deque[_Stream] = deque()      # requests in a lane, in queue order: only the head may be committed
+        if self.overlap:
+            self.engine.open_lanes(int(prefill_lanes))
+            self._lane_of = [None] * int(prefill_lanes)
+            if self.profile:  # the frame step's time with / without a prefill in flight on the side stream
+                self.stats.update(frames_prefill_in_flight=0, frame_seconds_prefill_in_flight=0.0, frames_no_prefill=0, frame_seconds_no_prefill=0.0)
         self.chunk = int(stream_chunk_frames) if stream_chunk_frames is not None else None
         self.stream_max_frames = int(stream_max_frames)
         self._dec = None
@@ -718,7 +822,118 @@ class CSMBatcher:
         self.stats["shifts"] += 1
         self.stats["shifts_down" if delta < 0 else "shifts_up"] += 1
 
+    def _draws(self, s: _Stream):
+        """(sampler, first-frame uniforms, device seed) of a request's admission; a sampled host-rng stream gets its generator here."""
+        u = None
+        sampler = s.sampler if self.row_samplers else self.sampler  # the request's own: its admission block, then its row's table entry
+        sampled = float(sampler.temp) > 0 if self.row_samplers else self._sampled
+        if sampled and self.rng == "host":  # (a greedy stream has no generator: it consumes no draws, as its solo run)
+            s.rng = np.random.default_rng(s.seed)
+            u = s.rng.uniform(size=(1, self.engine.n_cb))[0].astype(np.float32)
+        seed = (s.seed if self.row_samplers else self.seed) if (sampled and self.rng == "device") else None
+        return sampler, u, seed
+
+    # ---- admissions off the batch's stream (DESIGN 8d-7) -----------------------------------------------------------------------------------
+    def _begin_prefills(self) -> bool:
+        """Queue heads go to free lanes, in queue order, whether or not a cache row is free.  Host work and launches on the side stream only."""
+        began = False
+        while None in self._lane_of:
+            with self._lock:
+                s = self._queue.popleft() if self._queue else None
+            if s is None:
+                break
+            began = True
+            lane = self._lane_of.index(None)
+            try:
+                if s.prompt is None:
+                    s.prompt = self.engine.prompts([s])[0]
+                S = int(s.prompt[0].shape[0]) + (int(s.prefix.length) if s.prefix is not None else 0)
+                if S != s.length:
+                    raise ValueError(f"the prompt has {S} frames, {s.length} were announced")
+                sampler, u, seed = self._draws(s)
+                s.admit_args = (sampler, seed)
+                s.prefill = self.engine.prefill(lane, s.prompt, sampler, u, seed, s.stream_id, prefix=s.prefix, timed=self.profile)
+            except Exception as e:  # noqa: BLE001  (the lane stays free: its next prefill starts from a reset)
+                s.future.set_exception(e)
+                continue
+            s.lane = lane
+            self._lane_of[lane] = s
+            self._inflight.append(s)
+        return began
+
+    def _commit_ready(self) -> bool:
+        """The oldest request in a lane enters a free row once its prefill has completed; never a later one in front of it.  While rows are
+        live the lane is only asked (`event.query()`), so the frames go on; with nothing live there is nothing to stall and the batcher waits."""
+        done = False
+        while self._inflight:
+            free = [r for r in range(self.max_batch) if self._rows[r] is None]
+            if not free:
+                break
+            s, row = self._inflight[0], free[0]
+            try:
+                if not self.engine.prefill_ready(s.prefill, wait=not self._live()):
+                    break
+            except Exception as e:  # noqa: BLE001
+                self._drop_prefill(s, e)
+                done = True
+                continue
+            self._inflight.popleft()
+            self._lane_of[s.lane] = None
+            done = True
+            moved = False
+            try:
+                _, P = self.engine.row_state()
+                if not self._live() and P != s.length:
+                    self._shift(s.length - P)   # nothing live: only the position moves
+                elif s.length > P:
+                    self._shift(s.length - P)   # the live windows move up so that the admission fits below the position
+                out: List[torch.Tensor] = []
+                self._timed("commit", lambda: out.append(self.engine.commit(row, s.lane, s.prefill)))
+                moved = True
+                if self.row_samplers:
+                    self.engine.set_row_sampler(row, *s.admit_args)
+                if s.audio is not None:
+                    self._dec.reset_row(row)  # the decoder row is the cache row: a new stream starts in it
+                if self.profile:
+                    self.stats["prefill_seconds"] += self.engine.prefill_seconds(s.prefill)
+            except Exception as e:  # noqa: BLE001
+                s.future.set_exception(e)
+                if moved:
+                    self.engine.park(row)
+                continue
+            self.stats["overlapped_admissions"] += 1
+            self._seat(s, row, out[0])
+        return done
+
+    def _drop_prefill(self, s: _Stream, e: BaseException) -> None:
+        if self._inflight and self._inflight[0] is s:
+            self._inflight.popleft()
+        else:
+            self._inflight.remove(s)
+        self._lane_of[s.lane] = None
+        if not s.future.done():
+            s.future.set_exception(e)
+
+    def _seat(self, s: _Stream, row: int, codes: torch.Tensor) -> None:
+        """The request's stream is live in `row` with `codes` as its first frame."""
+        self.stats["admissions"] += 1
+        self.stats["prefixed_admissions"] += s.prefix is not None
+        self.stats["session_admissions"] += s.session is not None
+        s.row = row
+        s.codes = [codes]
+        self._rows[row] = s
+        self._prev[row] = codes
+        self._first_eos[row] = torch.where((codes == 0).all(), 0, -1)
+        self._local[row] = 1
+
     def _admit(self) -> None:
+        if self.overlap:
+            # Commits only, while rows are live: the next queue heads go to the lanes BEHIND the round's frame launch (`step`), so that the
+            # batch's stream has a frame to run while the host enqueues a prompt block on the side stream.  With nothing live and nothing in
+            # a lane there is no frame to put in front: the heads start now and the first is waited for.
+            while self._commit_ready() | (not self._live() and not self._inflight and self._begin_prefills()):
+                pass
+            return
         free = [r for r in range(self.max_batch) if self._rows[r] is None]
         with self._lock:
             new = [self._queue.popleft() for _ in range(min(len(free), len(self._queue)))]
@@ -742,13 +957,7 @@ class CSMBatcher:
                     self._shift(S - P)       # nothing live: only the position moves
                 elif S > P:
                     self._shift(S - P)       # the live windows move up so that the prompt fits below the position
-                u = None
-                sampler = s.sampler if self.row_samplers else self.sampler  # the request's own: its admission block, then its row's table entry
-                sampled = float(sampler.temp) > 0 if self.row_samplers else self._sampled
-                if sampled and self.rng == "host":  # (a greedy stream has no generator: it consumes no draws, as its solo run)
-                    s.rng = np.random.default_rng(s.seed)
-                    u = s.rng.uniform(size=(1, self.engine.n_cb))[0].astype(np.float32)
-                seed = (s.seed if self.row_samplers else self.seed) if (sampled and self.rng == "device") else None
+                sampler, u, seed = self._draws(s)
                 out: List[torch.Tensor] = []
                 if s.prefix is not None:
                     self._timed("admit", lambda: out.append(self.engine.admit(row, s.prompt, sampler, u, seed, s.stream_id, prefix=s.prefix)))
@@ -767,17 +976,27 @@ class CSMBatcher:
                     s.future.set_exception(e)
                     self.engine.park(row)
                     continue
-            self.stats["admissions"] += 1
-            self.stats["prefixed_admissions"] += s.prefix is not None
-            self.stats["session_admissions"] += s.session is not None
-            s.row = row
-            s.codes = [codes]
-            self._rows[row] = s
-            self._prev[row] = codes
-            self._first_eos[row] = torch.where((codes == 0).all(), 0, -1)
-            self._local[row] = 1
+            self._seat(s, row, codes)
 
     def _frame(self) -> None:
+        if not (self.overlap and self.profile):
+            return self._frame_step()
+        # profile: the step's time, booked by whether a prefill was in flight on the side stream from its start to its end
+        before = [self.engine.prefill_ready(s.prefill) for s in self._inflight]
+        self.engine.synchronize()
+        t = time.perf_counter()
+        self._frame_step()
+        self.engine.synchronize()
+        dt = time.perf_counter() - t
+        after = [self.engine.prefill_ready(s.prefill) for s in self._inflight]
+        if not all(after):
+            self.stats["frames_prefill_in_flight"] += 1
+            self.stats["frame_seconds_prefill_in_flight"] += dt
+        elif all(before):
+            self.stats["frames_no_prefill"] += 1
+            self.stats["frame_seconds_no_prefill"] += dt
+
+    def _frame_step(self) -> None:
         live = self._live()
         pad, P = self.engine.row_state()
         if P >= self.engine.max_pos:  # the position has reached the end of the cache: every live window moves down to slot 0 of the longest
@@ -827,10 +1046,12 @@ class CSMBatcher:
         if not self._live():
             return False
         self._frame()
+        if self.overlap:
+            self._begin_prefills()  # (also the lane a commit of this round has freed)
         return True
 
     def run_until_idle(self) -> None:
-        while self.step() or self._queue:
+        while self.step() or self._queue or self._inflight:
             pass
 
     @property
@@ -851,7 +1072,7 @@ class CSMBatcher:
     def _worker(self) -> None:
         while True:
             with self._lock:
-                while not self._closed and not self._queue and not self._live():
+                while not self._closed and not self._queue and not self._live() and not self._inflight:
                     self._wake.wait()
                 if self._closed:
                     return
@@ -877,7 +1098,10 @@ class CSMBatcher:
         with self._lock:
             pending = list(self._queue)
             self._queue.clear()
-        for s in pending + self._live():
+        held = list(self._inflight)  # prefilled or being prefilled in a lane, not committed
+        self._inflight.clear()
+        self._lane_of = [None] * len(self._lane_of)
+        for s in pending + held + self._live():
             if not s.future.done():
                 s.future.set_exception(RuntimeError("CSMBatcher is closed"))
         for s in self._live():
@@ -885,6 +1109,8 @@ class CSMBatcher:
             self.engine.park(s.row)
         if self._dec is not None:
             self._dec.close()
+        if self.overlap:
+            self.engine.close_lanes()
 
     def __enter__(self):
         return self

@@ -110,6 +110,9 @@ struct kk_csm {
   bool row_samplers_zero_pending = false;  // kk_csm_reset_caches_parked takes no stream: zeroed on the next stream that flushes
   unsigned long long weights_id = 0;   // the weight set (kk_csm_finalize; kk_csm_share copies it): what a kk_csm_prefix is tied to
   const kk_csm* weights_of = nullptr;  // kk_csm_share: `dev` / `devb` / `devq` belong to that generator (immutable after finalize), not to this one
+  // kk_csm_admit_transfer into THIS generator: the source's stream has finished the admission / this stream has finished the copy.  Created at the
+  // first transfer, destroyed with the generator (a kk_csm_share copy starts without them).
+  hipEvent_t xfer_ready = nullptr, xfer_done = nullptr;
 };
 
 namespace {
@@ -826,6 +829,27 @@ __global__ __launch_bounds__(256) void prefix_capture_kernel(const float* kc, co
   const int z = blockIdx.y;
   const float4* s = (const float4*)((z & 1) ? vc : kc) + (long long)(z >> 1) * layer_pitch4;
   float4* d = dst + (long long)z * seg4;
+  const long long i0 = (long long)blockIdx.x * 1024 + threadIdx.x;
+  float4 r[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+    if (i0 + 256 * u < seg4) r[u] = s[i0 + 256 * u];
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+    if (i0 + 256 * u < seg4) d[i0 + 256 * u] = r[u];
+}
+
+// kk_csm_admit_transfer: the window of ONE live row of another generator's cache (`skc` / `svc`: the caller has added row and first slot) goes
+// into the same number of slots of ONE row of this generator's (`kc` / `vc`, likewise), every layer's K and V in one launch: blockIdx.y =
+// 2 layer + (0 K, 1 V).  A key is stored rotated by its stream's own position, so the move is a plain copy.  Per (layer, K|V) both sides are one
+// contiguous run of seg4 16-byte columns; only the layer pitches differ (max_batch * max_pos of the two generators need not match).  The form
+// of prefix_restore_kernel: 16 KiB per workgroup, four 16-byte columns 4 KiB apart per thread, loads ahead of stores, the tail checked.  It
+// reads nothing outside the source window and writes nothing outside the destination's L slots.
+__global__ __launch_bounds__(256) void row_transfer_kernel(const float* skc, const float* svc, long long src_pitch4, float* kc, float* vc,
+                                                           long long dst_pitch4, long long seg4) {
+  const int z = blockIdx.y;
+  const float4* s = (const float4*)((z & 1) ? svc : skc) + (long long)(z >> 1) * src_pitch4;
+  float4* d = (float4*)((z & 1) ? vc : kc) + (long long)(z >> 1) * dst_pitch4;
   const long long i0 = (long long)blockIdx.x * 1024 + threadIdx.x;
   float4 r[4];
 #pragma unroll
@@ -2716,6 +2740,7 @@ extern "C" int kk_csm_share(const kk_csm* m, kk_csm** out) {
   c->seed_valid = false;
   c->reset_pending = c->pad_pending = false;
   c->pad_host.clear();
+  c->xfer_ready = c->xfer_done = nullptr;
   *out = c;
   return 0;
 }
@@ -2736,6 +2761,8 @@ extern "C" void kk_csm_destroy(kk_csm* m) {
   if (m->seed_dev) (void)hipFree(m->seed_dev);
   if (m->admit_sid_dev) (void)hipFree(m->admit_sid_dev);
   if (m->row_samplers) (void)hipFree(m->row_samplers);
+  if (m->xfer_ready) (void)hipEventDestroy(m->xfer_ready);
+  if (m->xfer_done) (void)hipEventDestroy(m->xfer_done);
   m->graphs.clear();
   delete m;
 }
@@ -3349,6 +3376,58 @@ extern "C" int kk_csm_prefix_capture(kk_csm* m, void* stream, int row, int n, kk
     g_prefixes.insert(p);
   }
   *out = p;
+  return 0;
+}
+
+// A finished admission moves from another generator's cache row into a parked row of this one: the window [pad_s, P_s) of live row
+// `src_row` of `src` -- L positions -- goes to slots [P - L, P) of `row`, pad[row] = P - L, every layer's K and V in one launch.  No prompt
+// block, no depth decoder, no sampler; P, the other rows, the frame-step graph and its key are untouched: legal between two replays.  The
+// ordering is made here: `stream` waits for what `src_stream` holds now (the admission), and `src_stream` waits for the copy, so the source's
+// next reset or admission cannot overwrite the window early.  Everything is refused on the host before anything is enqueued.
+extern "C" int kk_csm_admit_transfer(kk_csm* m, void* stream, int row, kk_csm* src, void* src_stream, int src_row) {
+  if (!m || !src || !m->finalized || !src->finalized) return kk_fail("kk_csm_admit_transfer: needs two finalized generators");
+  if (m == src) return kk_fail("kk_csm_admit_transfer: source and destination are the same generator");
+  if (m->max_batch < 1 || !m->bb.kc || !m->bb.vc || src->max_batch < 1 || !src->bb.kc || !src->bb.vc)
+    return kk_fail("kk_csm_admit_transfer: call kk_csm_setup_caches on both generators first");
+  if (row < 0 || row >= m->max_batch) return kk_fail("kk_csm_admit_transfer: row out of range");
+  if (src_row < 0 || src_row >= src->max_batch) return kk_fail("kk_csm_admit_transfer: source row out of range");
+  const kk_llama_args &a = m->bb.a, &sa = src->bb.a;
+  const int P = m->bb.offset, mp = m->bb.max_pos, smp = src->bb.max_pos, kvw = a.num_kv_heads * a.head_dim, spad = src->pad_host[src_row];
+  if (m->pad_host[row] < mp) return kk_fail("kk_csm_admit_transfer: the row is live (kk_csm_park_row first)");
+  if (spad >= smp) return kk_fail("kk_csm_admit_transfer: the source row is parked");
+  const int L = src->bb.offset - spad;
+  if (spad < 0 || L < 1) return kk_fail("kk_csm_admit_transfer: the source row holds no position");
+  if (L > P) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "kk_csm_admit_transfer: the admission is longer than the cache position (kk_csm_shift_caches by %d first)", L - P);
+    return kk_fail(msg);
+  }
+  if (src->weights_id != m->weights_id || sa.num_layers != a.num_layers || sa.num_kv_heads * sa.head_dim != kvw)
+    return kk_fail("kk_csm_admit_transfer: the two generators run on different weight sets");
+  if (kvw % 4 != 0) return kk_fail("kk_csm_admit_transfer: kv_heads * head_dim must be a multiple of 4");
+  if (!m->xfer_ready && hipEventCreateWithFlags(&m->xfer_ready, hipEventDisableTiming) != hipSuccess) {
+    m->xfer_ready = nullptr;
+    return kk_fail("kk_csm_admit_transfer: event creation failed");
+  }
+  if (!m->xfer_done && hipEventCreateWithFlags(&m->xfer_done, hipEventDisableTiming) != hipSuccess) {
+    m->xfer_done = nullptr;
+    return kk_fail("kk_csm_admit_transfer: event creation failed");
+  }
+  hipStream_t st = (hipStream_t)stream, sst = (hipStream_t)src_stream;
+  if (hipEventRecord(m->xfer_ready, sst) != hipSuccess || hipStreamWaitEvent(st, m->xfer_ready, 0) != hipSuccess)
+    return kk_fail("kk_csm_admit_transfer: could not order the copy behind the source stream");
+  m->pad_host[row] = P - L;
+  m->pad_pending = true;
+  KK_TRY(flush_pending(m, st));
+  {  // source [spad, spad + L) of src_row (spad + L = P_s <= its max_pos), destination [P - L, P) of row (0 <= P - L, P <= max_pos): both inside their rows
+    const size_t sat = ((size_t)src_row * smp + (size_t)spad) * kvw, at = ((size_t)row * mp + (size_t)(P - L)) * kvw;
+    const long long seg4 = (long long)L * kvw / 4, spitch4 = (long long)src->max_batch * smp * kvw / 4, pitch4 = (long long)m->max_batch * mp * kvw / 4;
+    hipLaunchKernelGGL(row_transfer_kernel, dim3((unsigned)((seg4 + 1023) / 1024), 2 * a.num_layers), dim3(256), 0, st, src->bb.kc + sat, src->bb.vc + sat,
+                       spitch4, m->bb.kc + at, m->bb.vc + at, pitch4, seg4);
+    KK_CHECK_LAUNCH();
+  }
+  if (hipEventRecord(m->xfer_done, st) != hipSuccess || hipStreamWaitEvent(sst, m->xfer_done, 0) != hipSuccess)
+    return kk_fail("kk_csm_admit_transfer: could not order the source stream behind the copy");
   return 0;
 }
 

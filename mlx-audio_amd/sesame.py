@@ -531,7 +531,8 @@ class Model:
 
     def serve(self, **kw):
         """Continuous batching (csm_serve.CSMBatcher): requests enter and leave one running batch on this model's weights; every stream's
-        result equals its own `generate_batch([prompt])` run.  Keyword arguments are CSMBatcher's."""
+        result equals its own `generate_batch([prompt])` run.  Keyword arguments are CSMBatcher's; `overlap_admission=True` (with
+        `prefill_lanes=N`) prefills requests on a side stream while the batch keeps stepping."""
         from .csm_serve import CSMBatcher
 
         return CSMBatcher(self, **kw)

@@ -18,7 +18,11 @@ against a Mimi.decode_step of the same batch and F.  Written to profiles/csm_ser
 all dialogues queued together: as sessions (`submit(session=)`: a turn is admitted on the K / V captured at the end of the one before) / with
 every turn resubmitted as a plain request whose `prompt` is the full history frames (what a caller does without sessions, minus Mimi.encode) /
 as sessions again; per run wall, audio-s/s and (a second, profiled run) the mean admission ms BY TURN NUMBER.  Written to
-profiles/csm_serve_session_bench.json."""
+profiles/csm_serve_session_bench.json.
+--overlap [--lanes N]: instead, the mixed workload three times in one process: continuous / with `overlap_admission=True` (every request prefilled in
+a lane on a side stream and committed by one copy) / continuous again; per run wall, audio-s/s, occupancy and (a second, profiled run) the mean
+stall of the batch's stream per admission -- the admission itself, or the commit --, the lanes' device time per prefill, and the frame step's time
+while a prefill was in flight beside its time while none was.  Written to profiles/csm_serve_overlap_bench.json."""
 import argparse
 import json
 import os
@@ -47,10 +51,12 @@ ap.add_argument("--prefix", type=int, default=0, help="frames of a voice prefix 
 ap.add_argument("--stream-chunk", type=int, default=0, help="frames per audio chunk: time to first audio of submit_stream against plain submit")
 ap.add_argument("--sessions", type=int, default=0, help="dialogues run as sessions against full-history resubmission (with --turns)")
 ap.add_argument("--turns", type=int, default=4)
+ap.add_argument("--overlap", action="store_true", help="continuous batching with admissions prefilled on a side stream against plain continuous batching")
+ap.add_argument("--lanes", type=int, default=1, help="prefill lanes of --overlap")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 if a.out is None:
-    name = "csm_serve_session_bench.json" if a.sessions else "csm_serve_stream_bench.json" if a.stream_chunk else "csm_serve_prefix_bench.json" if a.prefix else "csm_serve_bench.json"
+    name = "csm_serve_overlap_bench.json" if a.overlap else "csm_serve_session_bench.json" if a.sessions else "csm_serve_stream_bench.json" if a.stream_chunk else "csm_serve_prefix_bench.json" if a.prefix else "csm_serve_bench.json"
     a.out = os.path.join(ROOT, "profiles", name)
 
 cfg = dict(P.csm_config(), max_seq_len=a.max_seq_len)
@@ -99,8 +105,8 @@ def run_static():
     return time.perf_counter() - t
 
 
-def run_continuous(profile):
-    bat = loop.serve(max_batch=B, rng="device", sampler=sampler, seed=a.seed, stop_on_eos=False, decode=False, profile=profile)
+def run_continuous(profile, **kw):
+    bat = loop.serve(max_batch=B, rng="device", sampler=sampler, seed=a.seed, stop_on_eos=False, decode=False, profile=profile, **kw)
     torch.cuda.synchronize()
     t = time.perf_counter()
     futs = [bat.submit(None, None, prompt=prompts[i], max_audio_length_ms=80 * flen[i]) for i in range(a.requests)]
@@ -108,7 +114,42 @@ def run_continuous(profile):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t
     assert [f.result(timeout=0).frames for f in futs] == flen
+    bat.close()
     return dt, bat
+
+
+def bench_overlap():
+    def both(overlap):
+        kw = dict(overlap_admission=True, prefill_lanes=a.lanes) if overlap else {}
+        dt, bat = run_continuous(False, **kw)
+        st = bat.stats
+        _, prof = run_continuous(True, **kw)
+        ps = prof.stats
+        n = max(1, ps["admissions"])
+        r = {"wall_s": dt, "xrt": audio_s / dt, "occupancy": bat.occupancy, "frame_steps": st["frames"], "admissions": st["admissions"],
+             "overlapped_admissions": st["overlapped_admissions"], "shifts_down": st["shifts_down"], "shifts_up": st["shifts_up"],
+             "main_stream_stall_ms_per_admission": 1e3 * (ps["commit_seconds"] if overlap else ps["admit_seconds"]) / n,
+             "shift_ms_mean": 1e3 * ps["shift_seconds"] / max(1, ps["shifts"]), "profiled_wall_note": "stall, shift, prefill and frame-step times are of the profiled run"}
+        if overlap:
+            r["prefill_seconds"] = ps["prefill_seconds"]
+            r["prefill_ms_mean"] = 1e3 * ps["prefill_seconds"] / n
+            r["frame_step_ms"] = {"prefill_in_flight": 1e3 * ps["frame_seconds_prefill_in_flight"] / max(1, ps["frames_prefill_in_flight"]),
+                                  "frames_prefill_in_flight": ps["frames_prefill_in_flight"],
+                                  "no_prefill": 1e3 * ps["frame_seconds_no_prefill"] / max(1, ps["frames_no_prefill"]),
+                                  "frames_no_prefill": ps["frames_no_prefill"]}
+        return r
+
+    run_continuous(False), run_continuous(False, overlap_admission=True, prefill_lanes=a.lanes)  # warm-up: kernel loading, workspaces, graph capture
+    cont_steps, cont_rf = fifo_steps()
+    res = {"metric": "CSM-1B serving, admissions prefilled on a side stream vs on the batch's stream, " + a.weights, "requests": a.requests, "batch": B,
+           "lanes": a.lanes, "max_seq_len": a.max_seq_len, "prompt_frames": plen, "stream_frames": flen, "audio_s": audio_s,
+           "ideal_continuous_steps": cont_steps, "order": ["continuous_first", "overlapped", "continuous_last"],
+           "data": "synthetic (random-init CSM-1B weights, random text prompts, imposed stream lengths, device uniforms, no codec)"}
+    res["continuous_first"], res["overlapped"], res["continuous_last"] = both(False), both(True), both(False)
+    plain = [res["continuous_first"]["xrt"], res["continuous_last"]["xrt"]]
+    res["value"] = res["overlapped"]["xrt"] / (0.5 * sum(plain))
+    res["value_is"] = "overlapped / continuous audio-sec/sec (continuous: mean of the two runs; they differ by %.3f xRT)" % abs(plain[0] - plain[1])
+    return res
 
 
 def bench_prefix():
@@ -260,6 +301,17 @@ def bench_sessions():
     res["value_is"] = "session / history mean admission ms of the last turn (session: mean of the two runs; their spread %.3f ms)" % abs(last[0] - last[1])
     return res
 
+
+if a.overlap:
+    if a.prefix or a.stream_chunk or a.sessions or a.lanes < 1:
+        sys.exit("--overlap excludes --prefix / --stream-chunk / --sessions and needs --lanes >= 1")
+    out = bench_overlap()
+    print(json.dumps(out))
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    sys.exit(0)
 
 if a.sessions:
     if a.prefix or a.stream_chunk or a.turns < 1 or a.turns * 50 + 25 >= a.max_seq_len:
