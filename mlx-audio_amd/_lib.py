@@ -90,6 +90,7 @@ SIGNATURES = {
     "kk_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
     "kk_debug_override": (_i, [_vp, C.c_char_p, _vp]),
     "kk_debug_clear": (None, [_vp]),
+    # flags: see include/kokoro_hip.h; bit 11 (2048) = conv variant 4 slab by slab also where its whole-K form is routed
     "kk_debug_force_generic": (None, [_vp, _i]),
     "kk_op_pack_w_frag": (_i, [_vp, _vp, _vp, _i, _i, _i]),
     "kk_csm_create": (_i, [C.POINTER(KKCsmConfig), C.POINTER(_vp)]),
@@ -173,7 +174,8 @@ SIGNATURES = {
     "kk_mimi_debug_info": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "kk_mimi_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
     "kk_debug_set_op_wfrag": (None, [_vp]),
-    "kk_debug_set_op_variant": (None, [_i]),
+    "kk_debug_set_op_variant": (None, [_i]),  # 4 (default), 5, or 40 = variant 4 slab by slab where its whole-K form would run
+    "kk_debug_set_op_post_slope": (None, [_f]),
     "kk_set_graph_mode": (_i, [_vp, _i]),
     "kk_set_quantization": (_i, [_vp, _i, _i]),
     "kk_quantized_layers": (_i, [_vp]),

@@ -140,6 +140,8 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     const int lin_hi = Lin > 0 ? Lin - 1 : 0;
     const int cin_real = a.Cin > 0 ? a.Cin : a.CinP;
 
+#define KK_STG(name) name
+#define KK_STG_XS Xs
 #include "kk_conv_mfma_stage.h"  // xreg / preg / xok, load_x, store_p, store_x (shared with variant 4)
     // four named registers instead of an array: hipcc kept a `uint4 wreg[4]` captured by the lambdas in scratch memory
     // (global load -> wait -> scratch store), which turned the prefetch into a synchronous copy

@@ -1,40 +1,35 @@
 // Variant 4 of the bf16 MFMA implicit-GEMM convolution (see kk_conv_mfma.hip for the base design): the weight (B) fragments
 // do NOT go through LDS.  W is packed in FRAGMENT ORDER at load time (kk_mfma4_pack_index), so a wave fetches the 1 KiB
-// fragment of its 32 output channels x 16 k for one k-step as ONE fully coalesced global_load_dwordx4, straight into the MFMA
-// operand registers, one (tap, slab) iteration ahead.  That removes the W double buffer (LDS 73 -> 48 KB), the ds_write of W,
+// fragment of 16 output channels x 32 k of one k-step as ONE fully coalesced global_load_dwordx4, straight into the MFMA
+// operand registers, one (tap, slab) iteration ahead.  Against the LDS-staged kernel that removes the W double buffer, the ds_write of W,
 // 8 of the 20 ds_read_b128 per wave and iteration, and the barrier per tap: waves synchronise only when the X slab changes.
 //
-// bf16 MFMA implicit-GEMM convolution for frames-major tensors (gfx950, v_mfma_f32_32x32x16_bf16).
+// bf16 MFMA implicit-GEMM convolution for frames-major tensors (gfx950, v_mfma_f32_16x16x32_bf16).
 //
 //   out[b][q][n] = sum_t sum_ci  W[t][n][ci] * f(X[b][q + off_t][ci])       (stride 1, any dilation)
 //   transposed conv = `stride` independent phase convolutions with 2 taps each (polyphase form, see kk_conv.hip)
-//   f = identity, LeakyReLU, or the fused AdaIN apply + Snake / LeakyReLU of the reference's resblocks
+//   f = identity, LeakyReLU, ELU, or the fused AdaIN apply + Snake / LeakyReLU of the reference's resblocks
 //
-// GEMM view per workgroup: M = BM output rows (128 or 256), N = 128 output channels, K = taps x Cin walked in slabs of
-// 64 channels.  A = X rows (positions), B = W rows (output channels); both are k-contiguous in LDS so a lane's MFMA
-// fragment (8 consecutive k) is ONE ds_read_b128.  LDS rows are padded 128 B -> 144 B: 16 consecutive rows start on 16
-// distinct 4-bank groups, so the b128 fragment reads are conflict-free (banks = (addr/4) % 64).
-//
-//   * 4 waves as 2 x 2; a wave owns WM x 64 outputs (WM = 64 or 128) = (WM/32) x 2 accumulators of 32 x 32.  WM = 128
-//     re-uses every B (weight) fragment for 4 row tiles: 6 ds_read_b128 per 8 MFMAs instead of 4 per 4 -- with two
-//     workgroups per CU the 64-row variant saturates the LDS read port (1 b128 read per MFMA and wave = 256 B/clk/CU),
-//     and it halves the L2 traffic for W per MFMA.
-//   * the X slab [BM + halo rows][64 ch] is loaded once per channel slab (register prefetch issued at the first tap of
-//     the previous slab) and re-used by every tap as a shifted window
-//   * W tiles [128 n][64 ci] are double-buffered in LDS and prefetched through registers one tap ahead: one barrier per tap
+// GEMM view per workgroup: M = 192 output rows, N = 128 output channels, K = taps x Cin walked in slabs of 64 channels (slab outer, tap
+// inner).  A = X rows (positions) from LDS, B = W rows (output channels) from global memory in fragment order.
+//   * 4 waves as 2 x 2; a wave owns 96 x 64 outputs = 6 x 4 accumulator blocks of 16 x 16 (lane l holds rows 4 * (l / 16) .. + 3 of column
+//     l % 16): 96 registers.  Per k-step (32 channels) a wave's 4 B fragments stay in registers while its 6 A fragments stream through.
+//   * A fragment of lane l: row l % 16, k-group l / 16 (4 groups of 8 k), ONE ds_read_b128.  LDS rows have a 160-BYTE PITCH (XLD = 80
+//     elements): 16 consecutive rows land on the even 16-byte granules and the odd k-groups on the odd ones, so the four lane groups of
+//     a read are conflict-free (a 144-byte pitch, right for the older 32x32x16 fragments, collides 2-way here).  Slab: 38.7 KB.
+//   * B fragment of lane l: column l % 16, k-group l / 16; pack order [tap][n block][chunk][wc][ks][ni][lane] x 16 bytes: one coalesced
+//     1 KiB load per fragment, requested right behind the MFMAs of the k-step that frees its registers.
+//   * the X slab [192 + halo rows][64 ch] is staged once per channel slab (kk_conv_mfma_stage.h: registers -> fused transform -> LDS) and
+//     re-used by every tap as a shifted window.  Two forms: the slab-by-slab kernel (any slab count; the next slab is requested at the
+//     first tap of the current one and stored between two barriers after its last tap) and the WHOLE-K kernel for exactly two slabs
+//     (CinP == 128: both staged in the prologue into buffers of their own, no staging in the loop -- see conv_mfma4_wholek_kernel).
 //   * all global loads are unconditional (clamped address + mask at use): a load under a data-dependent branch makes
 //     hipcc wait vmcnt(0) right behind it, which serialises the loads (one HBM round trip each)
-//   * epilogue through a 128 x 128 fp32 LDS tile per 128 rows: bias / activation / residual / scale / accumulate / length
-//     mask on coalesced 16-byte rows, ONE rounding to bf16, optional per-tile column sums for the next instance norm.
-// Round 3: the matrix instruction is v_mfma_f32_16x16x32_bf16 instead of round 2's 32x32x16.
-// Same FLOPs per cycle and the same operand bytes per FLOP from LDS / global memory, but the chip holds a higher clock on it under load
-// (MI355X_MICROARCH.md, DVFS give-back item 7: 1.12-1.15 x in MFMA-paced loops): -3 ... -11 % on every conv shape.  What changes with the shape:
-//   * A fragment of lane l: row l % 16, k-group l / 16 (4 groups of 8 k = 32 k per step, two steps per 64-channel slab).  With the 144-byte
-//     row pitch the four lane groups of a ds_read_b128 collide 2-way; a 160-BYTE PITCH puts 16 consecutive rows on the even 16-byte granules
-//     and the odd k-groups on the odd ones: conflict-free again (slab 38.7 KB instead of 34.8).
-//   * B fragment of lane l: column l % 16, k-group l / 16; a wave's 64 columns are 4 fragments per k-step: pack order
-//     [tap][n block][chunk][wc][ks][ni][lane] x 16 bytes, still ONE coalesced 1 KiB load per fragment.
-//   * accumulators: 16 x 16 blocks, lane l holds rows 4 * (l / 16) .. + 3 of column l % 16: (WM / 16) x 4 blocks of 4 registers = the same 96.
+//   * epilogue (kk_conv_mfma_epilogue.h) through a 96 x 128 fp32 LDS tile per wave row, aliasing the slab: bias / activation / residual /
+//     scale / accumulate / length mask on coalesced 16-byte rows, ONE rounding to bf16, optional per-tile column sums for the next
+//     instance norm.
+// The 16x16x32 instruction (round 3) has the FLOPs per cycle and operand bytes per FLOP of round 2's 32x32x16, but the chip holds a higher
+// clock on it under load (MI355X_MICROARCH.md, DVFS give-back item 7: 1.12-1.15 x in MFMA-paced loops): -3 ... -11 % on every conv shape.
 #include <stdlib.h>
 
 #include "kk_common.h"
@@ -144,6 +139,8 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     const int lin_hi = Lin > 0 ? Lin - 1 : 0;
     const int cin_real = a.Cin > 0 ? a.Cin : a.CinP;
 
+#define KK_STG(name) name
+#define KK_STG_XS Xs
 #include "kk_conv_mfma_stage.h"  // xreg / preg / xok, load_x, store_p, store_x (shared with variant 2)
     // B fragments of one (tap, slab) iteration: [ks][ni], loaded from the fragment-order pack one iteration ahead.  Named
     // scalars, not an array (hipcc put a lambda-captured register array in scratch once already).
@@ -201,6 +198,138 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #include "kk_conv_mfma_epilogue.h"  // (shared with variant 2)
 }
 
+// ---- the WHOLE-K form: stride-1 convolutions with CinP == 128 (the stage-1 resblocks: 24 launches, more than half of the forward's conv time).
+// Two 64-channel slabs ARE the whole K of such a tile, so both are staged in the prologue -- ONE request round (parameters and rows of both slabs,
+// the first weight fragments), both transforms, both slabs into LDS buffers of their own, ONE barrier -- and the main loop is nothing but
+// MFMAs, A-fragment reads and the next iteration's weight requests: no slab request, no transform, no barrier, no condition around a load.
+// The slab-by-slab kernel above staged slab 1 in the MIDDLE of the loop (request at tap 0, then barrier / transform by all four waves with
+// this workgroup's matrix pipe idle / barrier).  Also gone:
+//   * dead staging rows: XR = 7 chunks per thread and slab (224 rows) where the launch's halo (taps - 1) * dil is <= 32 -- every stage-1
+//     layer except 11 taps at dilation 5 -- instead of the 8 (256 rows, 242 kept) that the largest halo needs;
+//   * the final iteration's weight request (the loop above re-requests its own fragments there): that iteration is peeled.
+// Iteration order (slab outer, tap inner, two k-steps), operands and epilogue are those of the slab-by-slab kernel: outputs and statistics
+// partials are BIT-IDENTICAL (tests/test_gpu_conv_wholek.py compares the two forms with torch.equal).
+template <int XR>
+struct GeoWK {
+  static constexpr int SROWS = XR == 7 ? 224 : 192 + MAX_HALO;  // rows of one slab buffer
+  static constexpr int SLAB = SROWS * XLD;                      // elements
+  static constexpr int XS_BYTES = 2 * SLAB * 2;
+  static constexpr int MAIN_BYTES = XS_BYTES + PS_BYTES;  // 73 216 / 78 976 B: two workgroups per CU in 160 KB
+  static constexpr int RPP = 96;
+  static constexpr int EPI_BYTES = RPP * CLD * 4;
+  static constexpr int LDS_BYTES = MAIN_BYTES > EPI_BYTES ? MAIN_BYTES : EPI_BYTES;
+};
+
+template <int NRM, int XR>
+__global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_mfma4_wholek_kernel(KKMfmaArgs a) {
+  using TO = bf16_t;
+  constexpr int WM = 96, BM = 2 * WM, MI16 = WM / 16, XREG = XR;
+  constexpr bool ACC16 = true;
+  using G = GeoWK<XR>;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  bf16_t* Xs = (bf16_t*)smem;                 // [2 slabs][SROWS][XLD]
+  float* Ps = (float*)(smem + G::XS_BYTES);  // [2 slabs][3][64]
+  float* Cs = (float*)smem;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  constexpr int nphase = 1, phase = 0;
+  int bx, by, b;  // XCD-aware tile order, as above
+  {
+    const int gx = gridDim.x, gy = gridDim.y, total = gx * gy * gridDim.z;
+    int lid = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
+    const int per = total / 8, rem = total - per * 8;
+    const int xcd = lid & 7, idx = lid >> 3;
+    lid = xcd * per + (xcd < rem ? xcd : rem) + idx;
+    by = lid % gy;
+    const int t = lid / gy;
+    bx = t % gx;
+    b = t / gx;
+  }
+  const int q0 = bx * BM, n0 = by * BN;
+  const int Lin = kk_len(a.lin, b), Lout = kk_len(a.lout, b);
+  const int ntaps = a.Kw, off0 = -a.pad, dstep = a.dil, min_off = off0;
+  const int xrows = BM + (ntaps - 1) * dstep;  // <= GeoWK<XR>::SROWS (the launcher picks XR by the halo)
+  const bool tile_live = q0 < Lout;            // uniform over the workgroup
+
+  const unsigned long long tr0 = TR_NOW();
+  (void)tr0;
+  f32x4 acc[MI16][4];
+#pragma unroll
+  for (int i = 0; i < MI16; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  if (tile_live) {
+    const bf16_t* xb = a.x + (long long)b * a.xbs;
+    const int nit = 2 * ntaps;
+    const int lin_hi = Lin > 0 ? Lin - 1 : 0;
+    const int cin_real = a.Cin > 0 ? a.Cin : a.CinP;
+
+    // one register set and one LDS buffer per slab: xreg_s0 / load_x_s0 / ... and xreg_s1 / load_x_s1 / ...
+#define KK_STG(name) name##_s0
+#define KK_STG_XS Xs
+#include "kk_conv_mfma_stage.h"
+#define KK_STG(name) name##_s1
+#define KK_STG_XS (Xs + G::SLAB)
+#include "kk_conv_mfma_stage.h"
+    uint4 q00, q01, q02, q03, q10, q11, q12, q13;  // B fragments of one (tap, slab) iteration, [ks][ni], one iteration ahead
+    auto frag_ptr = [&](int it) __attribute__((always_inline)) -> const uint4* {
+      const int chunk = it >= ntaps ? 1 : 0, tap = it - chunk * ntaps;
+      // pack order: [tap][n block][chunk][wc][ks][ni][lane] x 16 bytes
+      const long long blk = ((long long)tap * (a.CoutP / BN) + by) * 2 + chunk;
+      return (const uint4*)a.wf + blk * 1024 + (wc * 2) * 4 * 64 + lane;
+    };
+    // ---- prologue: everything a tile reads except the later weight fragments, in one request round
+    load_x_s0(0);
+    load_x_s1(1);
+    {
+      const uint4* fp = frag_ptr(0);
+      q00 = fp[0 * 64]; q01 = fp[1 * 64]; q02 = fp[2 * 64]; q03 = fp[3 * 64];
+      q10 = fp[4 * 64]; q11 = fp[5 * 64]; q12 = fp[6 * 64]; q13 = fp[7 * 64];
+      asm volatile("" ::: "memory");
+    }
+    store_p_s0(0);
+    store_p_s1(1);
+    __syncthreads();
+    store_x_s0(0);  // (slab 1's rows are still landing)
+    store_x_s1(1);
+    __syncthreads();
+
+    const int arow = wr * WM + (lane & 15);  // + mi*16 + tap shift
+    const int kofs = 8 * (lane >> 4);
+    for (int it = 0; it + 1 < nit; ++it) {
+      const int chunk = it >= ntaps ? 1 : 0, tap = it - chunk * ntaps;
+      const uint4* fn = frag_ptr(it + 1);
+      const bf16_t* xa = Xs + chunk * G::SLAB + (arow + tap * dstep) * XLD + kofs;
+      KK_MFMA_ITER(q00, q01, q02, q03, q10, q11, q12, q13)
+      asm volatile("" ::: "memory");
+    }
+    {  // the final iteration (slab 1, last tap): no fragment request
+      const bf16_t* xa = Xs + G::SLAB + (arow + (ntaps - 1) * dstep) * XLD + kofs;
+      KK_MFMA_ITER_LAST(q00, q01, q02, q03, q10, q11, q12, q13)
+      asm volatile("" ::: "memory");
+    }
+    __syncthreads();  // main-loop LDS is dead; the epilogue tile aliases it
+  }
+
+#include "kk_conv_mfma_epilogue.h"  // (shared with variant 2 and the slab-by-slab kernel)
+}
+
+template <int NRM, int XR>
+int launch_wholek(const KKMfmaArgs& a, int B, hipStream_t st) {
+  using G = GeoWK<XR>;
+  static KKDevOnce attr_once;
+  if (attr_once.first()) {
+    (void)hipFuncSetAttribute((const void*)conv_mfma4_wholek_kernel<NRM, XR>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
+    attr_once.done();
+  }
+  dim3 grid(kk_cdiv(a.Q, 192), a.CoutP / BN, B);
+  hipLaunchKernelGGL((conv_mfma4_wholek_kernel<NRM, XR>), grid, dim3(256), G::LDS_BYTES, st, a);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
 template <typename TO, int WM, int NRM>
 int launch_one(const KKMfmaArgs& a, int B, hipStream_t st) {
   using G = Geo<2 * WM>;
@@ -235,6 +364,11 @@ int kk_launch_pack_w_frag(const void* w, void* wf, int Kw, int CoutP, int CinP, 
   return 0;
 }
 
+// what the whole-K form takes: stride-1 convolutions whose K is exactly two 64-channel slabs, halo within the slab buffers
+bool kk_mfma4_wholek_eligible(const KKMfmaArgs& a) {
+  return a.mode == KK_CONV && a.stride == 1 && a.CinP == 2 * CK && a.dil >= 1 && (a.Kw - 1) * a.dil <= MAX_HALO;
+}
+
 int kk_launch_conv_mfma4(const KKMfmaArgs& a, int B, int out_dtype, hipStream_t st) {
   if (a.Q <= 0 || B <= 0) return 0;
   if (!a.wf) return kk_fail("conv_mfma4: fragment-order weights missing");
@@ -243,6 +377,13 @@ int kk_launch_conv_mfma4(const KKMfmaArgs& a, int B, int out_dtype, hipStream_t 
   KKMfmaArgs g = a;
   if (nrm == 2 && a.nrm_act != KK_ACT_LRELU) g.nrm_slope = 1.0f;  // plain AdaIN: identity activation
   if (out_dtype != KK_BF16) return kk_fail("conv_mfma4: bf16 output only");
+  if (kk_mfma4_wholek_eligible(g) && !g.slabwise) {
+    // chunk registers per thread and slab by the launch's halo: 7 x 32 = 224 rows cover a 192-row tile with a halo of up to 32
+    const bool x7 = (g.Kw - 1) * g.dil <= 32;
+    if (nrm == 1) return x7 ? launch_wholek<1, 7>(g, B, st) : launch_wholek<1, 8>(g, B, st);
+    if (nrm == 2) return x7 ? launch_wholek<2, 7>(g, B, st) : launch_wholek<2, 8>(g, B, st);
+    return x7 ? launch_wholek<0, 7>(g, B, st) : launch_wholek<0, 8>(g, B, st);
+  }
   if (nrm == 1) return launch_one<bf16_t, 96, 1>(g, B, st);
   if (nrm == 2) return launch_one<bf16_t, 96, 2>(g, B, st);
   return launch_one<bf16_t, 96, 0>(g, B, st);

@@ -67,7 +67,9 @@ constexpr int RED_BYTES = 4 * 2 * BN * 4;
 constexpr int MAX_B5 = 256;  // utterances per launch (the LDS table of output lengths)
 constexpr int MAX_C5 = 1280;  // channels per side (the LDS tables of bias and Snake alpha)
 constexpr int LDS5_BYTES = XS_BYTES + CS_BYTES + RED_BYTES + 2 * MAX_B5 * 4 + 2 * MAX_C5 * 4;
-constexpr int XREG = (XROWS * 8 + 255) / 256;  // 16-byte chunks of the slab per service thread
+// 16-byte chunks of the slab per service thread (32 slab rows each): template parameter XREG of the kernel, 7 where the launch's halo is <= 32
+// (224 rows: every stage-1 layer but 11 taps at dilation 5), else the 8 that XROWS needs -- a chunk past the launch's rows is loaded and
+// transformed for nothing
 constexpr int NTASK = BM * 16 / 256;           // epilogue row tasks per service thread and tile (12)
 
 
@@ -91,7 +93,7 @@ struct Item {
 // NRM: 0 = raw input, 1 = AdaIN + Snake while staging, 2 = AdaIN + LeakyReLU(nrm_slope; 1 = identity) while staging
 // TPP: epilogue row tasks of the previous tile that ride in one slab period (12 / min(slabs per tile, 4): the last 12 / TPP periods of a tile)
 // ACC: the output rows are read and added to (Generator's sum over the three resblocks): its own kernel, the rows cost 4 * TPP registers
-template <int NRM, int TPP, bool ACC>
+template <int NRM, int TPP, bool ACC, int XREG>
 __global__ __launch_bounds__(512, 2) void conv_mfma5_kernel(KKMfmaArgs a, int B) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   bf16_t* Xs = (bf16_t*)smem;
@@ -618,14 +620,14 @@ __global__ __launch_bounds__(512, 2) void conv_mfma5_kernel(KKMfmaArgs a, int B)
   }
 }
 
-template <int NRM, int TPP, bool ACC>
-int launch5(const KKMfmaArgs& a, int B, hipStream_t st) {
+template <int NRM, int TPP, bool ACC, int XREG>
+int launch5x(const KKMfmaArgs& a, int B, hipStream_t st) {
   static KKDevOnce attr_once;
   static int ncu_dev[64];  // CUs of each device this process has launched on (the persistent grid = CUs)
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (attr_once.first()) {
-    (void)hipFuncSetAttribute((const void*)conv_mfma5_kernel<NRM, TPP, ACC>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS5_BYTES);
+    (void)hipFuncSetAttribute((const void*)conv_mfma5_kernel<NRM, TPP, ACC, XREG>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS5_BYTES);
     int n = 0;
     if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
     ncu_dev[dev & 63] = n;
@@ -634,9 +636,13 @@ int launch5(const KKMfmaArgs& a, int B, hipStream_t st) {
   const int ncu = ncu_dev[dev & 63];
   const int total = B * kk_cdiv(a.Q, BM) * (a.CoutP / BN);
   const int grid = total < ncu ? total : ncu;
-  hipLaunchKernelGGL((conv_mfma5_kernel<NRM, TPP, ACC>), dim3(grid), dim3(512), LDS5_BYTES, st, a, B);
+  hipLaunchKernelGGL((conv_mfma5_kernel<NRM, TPP, ACC, XREG>), dim3(grid), dim3(512), LDS5_BYTES, st, a, B);
   KK_CHECK_LAUNCH();
   return 0;
+}
+template <int NRM, int TPP, bool ACC>
+int launch5(const KKMfmaArgs& a, int B, hipStream_t st) {
+  return (a.Kw - 1) * a.dil <= 32 ? launch5x<NRM, TPP, ACC, 7>(a, B, st) : launch5x<NRM, TPP, ACC, 8>(a, B, st);
 }
 template <int NRM>
 int launch5n(const KKMfmaArgs& a, int B, hipStream_t st) {

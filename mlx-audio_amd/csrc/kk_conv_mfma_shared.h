@@ -53,4 +53,26 @@ typedef __bf16 kk_bf16x8 __attribute__((ext_vector_type(8)));
     }                                                                                                                                        \
     __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);                                                                                       \
   }
+// The same iteration with NO refill of the B registers: a tile's final (tap, slab) iteration where it is peeled off the loop (the whole-K
+// form of variant 4), so that no fragment set is requested that nobody multiplies.  Same MFMAs on the same operands in the same order.
+#define KK_MFMA_KSTEP_LAST(KS, B0, B1, B2, B3)                                                                                             \
+  {                                                                                                                                          \
+    const kk_bf16x8 b0 = __builtin_bit_cast(kk_bf16x8, B0), b1 = __builtin_bit_cast(kk_bf16x8, B1);                                          \
+    const kk_bf16x8 b2 = __builtin_bit_cast(kk_bf16x8, B2), b3 = __builtin_bit_cast(kk_bf16x8, B3);                                          \
+    _Pragma("unroll") for (int mi = 0; mi < MI16; ++mi) {                                                                                    \
+      const kk_bf16x8 av = *(const kk_bf16x8*)(xa + mi * 16 * XLD + (KS) * 32);                                                              \
+      acc[mi][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, b0, acc[mi][0], 0, 0, 0);                                                     \
+      acc[mi][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, b1, acc[mi][1], 0, 0, 0);                                                     \
+      acc[mi][2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, b2, acc[mi][2], 0, 0, 0);                                                     \
+      acc[mi][3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, b3, acc[mi][3], 0, 0, 0);                                                     \
+    }                                                                                                                                        \
+  }
+#define KK_MFMA_ITER_LAST(Q00, Q01, Q02, Q03, Q10, Q11, Q12, Q13)                                                                          \
+  KK_MFMA_KSTEP_LAST(0, Q00, Q01, Q02, Q03)                                                                                                \
+  KK_MFMA_KSTEP_LAST(1, Q10, Q11, Q12, Q13)                                                                                                \
+  __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                                                                                         \
+  _Pragma("unroll") for (int j = 0; j < 2 * MI16; ++j) {                                                                                     \
+    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                                                                                       \
+    if (j + 2 < 2 * MI16) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                                                 \
+  }
 }  // namespace

@@ -3,12 +3,18 @@
 // prefetch, the fused AdaIN + Snake / LeakyReLU transform and the padding masks, so the two kernels cannot drift apart (they are compared
 // bit for bit by the `mfma4` test fixture).  Names taken from the including scope: a, b, tid, q0, off0, min_off, xrows, xb, Lin, lin_hi,
 // cin_real, Xs, Ps, XREG, XLD, CK, NRM, bf16_t / bf16x2.  Defines: xreg, preg, xok, load_x(chunk), store_p(chunk), store_x(chunk).
-    uint4 xreg[XREG];
-    float4 preg = make_float4(0.f, 0.f, 0.f, 0.f);  // lanes 0..15 of waves 0 / 1 / 2: one float4 of the slab's A / B / alpha
-    unsigned xok = 0;
+// XREG, the 16-byte chunks per thread and slab (32 slab rows each), is the includer's: it may be smaller than the largest halo needs where
+// the launch's own halo fits (the whole-K form of variant 4).  Two macros are set by the includer before EACH include and undefined again
+// at the end of this file, so that a kernel that stages more than one slab at a time can include it once per register set:
+//   KK_STG(name)  the names defined here, as the includer wants them spelled (`name` itself, or suffixed per set)
+//   KK_STG_XS     the LDS slab buffer store_x writes (Xs, or a slab's own buffer)
+// The parameter table Ps holds two slabs ((chunk & 1) selects the half), so two sets share it.
+    uint4 KK_STG(xreg)[XREG];
+    float4 KK_STG(preg) = make_float4(0.f, 0.f, 0.f, 0.f);  // lanes 0..15 of waves 0 / 1 / 2: one float4 of the slab's A / B / alpha
+    unsigned KK_STG(xok) = 0;
 
-    auto load_x = [&](int chunk) __attribute__((always_inline)) {
-      xok = 0;
+    auto KK_STG(load_x) = [&](int chunk) __attribute__((always_inline)) {
+      KK_STG(xok) = 0;
       // parameter loads go FIRST: vmcnt retires in order, so storing them to LDS one tap later does not wait for the slab
       // ONE unconditional float4 per thread, its source chosen per WAVE (wave 0: A, 1: B, 2: alpha; lanes 0..15 hold the slab's 64 channels,
       // the other lanes and wave 3 re-read valid rows and store nothing): a load under `if (which == ...)` is waited for where the paths
@@ -19,7 +25,7 @@
         const int which = __builtin_amdgcn_readfirstlane(tid >> 6), c = chunk * CK + (tid & 15) * 4;
         const float* base = (NRM == 1 && which == 2) ? a.nrm_alpha : (which == 1 ? a.nrm_b : a.nrm_a) + (long long)b * a.nrm_stride;
         const int off = (NRM == 1 && which == 2) ? (c + 3 < a.nrm_C ? c : 0) : c;
-        preg = *(const float4*)(base + off);
+        KK_STG(preg) = *(const float4*)(base + off);
       }
 #pragma unroll
       for (int i = 0; i < XREG; ++i) {
@@ -28,25 +34,25 @@
         int row = q0 + min_off + r;
         const bool ok0 = row >= 0 && r < xrows;
         if (a.in_shift) row >>= a.in_shift;
-        if (ok0 && row < Lin) xok |= 1u << i;
+        if (ok0 && row < Lin) KK_STG(xok) |= 1u << i;
         const int rc = row < 0 ? 0 : (row > lin_hi ? lin_hi : row);
-        xreg[i] = *(const uint4*)(xb + (long long)rc * a.ldx + chunk * CK + c8);
+        KK_STG(xreg)[i] = *(const uint4*)(xb + (long long)rc * a.ldx + chunk * CK + c8);
       }
       asm volatile("" ::: "memory");
     };
-    auto store_p = [&](int chunk) __attribute__((always_inline)) {
+    auto KK_STG(store_p) = [&](int chunk) __attribute__((always_inline)) {
       if (NRM && tid < 192 && (tid & 63) < 16) {
         const int which = tid >> 6, l = tid & 15;
-        float4 p = preg;
+        float4 p = KK_STG(preg);
         if (NRM == 1 && which == 2 && chunk * CK + l * 4 + 3 >= a.nrm_C) p = make_float4(1.0f, 1.0f, 1.0f, 1.0f);  // pad channels
         *(float4*)(Ps + (chunk & 1) * 3 * CK + which * CK + l * 4) = p;
       }
     };
-    auto store_x = [&](int chunk) __attribute__((always_inline)) {
+    auto KK_STG(store_x) = [&](int chunk) __attribute__((always_inline)) {
       // value barrier: without it hipcc hoists the first unpack instructions of this function up to the loads in load_x
       // (one k-slab earlier) and waits for the slab there, which turns the prefetch into a synchronous load
 #pragma unroll
-      for (int i = 0; i < XREG; ++i) asm volatile("" : "+v"(xreg[i].x), "+v"(xreg[i].y), "+v"(xreg[i].z), "+v"(xreg[i].w));
+      for (int i = 0; i < XREG; ++i) asm volatile("" : "+v"(KK_STG(xreg)[i].x), "+v"(KK_STG(xreg)[i].y), "+v"(KK_STG(xreg)[i].z), "+v"(KK_STG(xreg)[i].w));
       if (NRM) {
         // y = act(x * A + B): AdaIN1d + Snake / LeakyReLU (istftnet.py:333-337,382) applied while staging.  This thread's 8
         // channels are the same for all its rows ((id & 7) == (tid & 7)); they are handled one packed PAIR at a time so that
@@ -67,7 +73,7 @@
           }
 #pragma unroll
           for (int i = 0; i < XREG; ++i) {
-            const unsigned wd = kk == 0 ? xreg[i].x : kk == 1 ? xreg[i].y : kk == 2 ? xreg[i].z : xreg[i].w;
+            const unsigned wd = kk == 0 ? KK_STG(xreg)[i].x : kk == 1 ? KK_STG(xreg)[i].y : kk == 2 ? KK_STG(xreg)[i].z : KK_STG(xreg)[i].w;
             float y0 = __builtin_fmaf(__uint_as_float(wd << 16), a0, b0);
             float y1 = __builtin_fmaf(__uint_as_float(wd & 0xFFFF0000u), a1, b1);
             if (NRM == 1) {
@@ -80,10 +86,10 @@
             }
             const bf16x2 pk = {(bf16_t)y0, (bf16_t)y1};
             const unsigned o = __builtin_bit_cast(unsigned, pk);
-            if (kk == 0) xreg[i].x = o;
-            else if (kk == 1) xreg[i].y = o;
-            else if (kk == 2) xreg[i].z = o;
-            else xreg[i].w = o;
+            if (kk == 0) KK_STG(xreg)[i].x = o;
+            else if (kk == 1) KK_STG(xreg)[i].y = o;
+            else if (kk == 2) KK_STG(xreg)[i].z = o;
+            else KK_STG(xreg)[i].w = o;
           }
         }
       }
@@ -96,7 +102,7 @@
           for (int i = 0; i < XREG; ++i) {
             const int id = i * 256 + tid;
             const int r = id >> 3, c8 = (id & 7) * 8;
-            if (r < xrows) *(uint4*)(Xs + r * XLD + c8) = xreg[i];
+            if (r < xrows) *(uint4*)(KK_STG_XS + r * XLD + c8) = KK_STG(xreg)[i];
           }
           return;
         }
@@ -111,10 +117,10 @@
         const int id = i * 256 + tid;
         const int r = id >> 3, c8 = (id & 7) * 8;
         if (r < xrows) {
-          const unsigned msk = (xok >> i) & 1u ? 0xFFFFFFFFu : 0u;
+          const unsigned msk = (KK_STG(xok) >> i) & 1u ? 0xFFFFFFFFu : 0u;
           // padding rows / pad channels stay exactly zero.  32-bit integer ops only: touching the slab registers as bf16
           // ELEMENTS makes hipcc split them into 16-bit pieces right at the loads (and wait for the loads there)
-          unsigned wq[4] = {xreg[i].x & msk & cm[0], xreg[i].y & msk & cm[1], xreg[i].z & msk & cm[2], xreg[i].w & msk & cm[3]};
+          unsigned wq[4] = {KK_STG(xreg)[i].x & msk & cm[0], KK_STG(xreg)[i].y & msk & cm[1], KK_STG(xreg)[i].z & msk & cm[2], KK_STG(xreg)[i].w & msk & cm[3]};
           if (NRM == 0 && a.in_act == KK_ACT_ELU) {  // nn.elu: where(x > 0, x, exp(x) - 1); elu(0) = 0 keeps the padding zero
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -134,7 +140,9 @@
               wq[k] = __builtin_bit_cast(unsigned, pk);
             }
           }
-          *(uint4*)(Xs + r * XLD + c8) = make_uint4(wq[0], wq[1], wq[2], wq[3]);
+          *(uint4*)(KK_STG_XS + r * XLD + c8) = make_uint4(wq[0], wq[1], wq[2], wq[3]);
         }
       }
     };
+#undef KK_STG
+#undef KK_STG_XS

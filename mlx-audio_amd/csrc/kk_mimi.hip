@@ -450,6 +450,7 @@ struct Run : Workspace {
       g.Q = transposed ? kk_cdiv(Lout, stride) : Lout; g.Lo_rows = Lout;
       g.lin = KKLen{nullptr, 0, Lin}; g.lout = KKLen{nullptr, 0, Lout};
       g.in_slope = 1.f; g.scale = 1.f; g.accumulate = accumulate; g.act = act_; g.in_act = in_act;
+      g.slabwise = 1;  // the whole-K form is routed per measured layer class (Ctx::conv of kk_model.hip); the codec's plain convolutions are none of them
       return kk_launch_conv_mfma4(g, B, KK_BF16, st);
     }
     // few rows per item (the streaming steps): the weight-streaming kernel instead of the 64-row conv tile.  Chosen by the rows per ITEM,

@@ -21,7 +21,8 @@
 // ------------------------------------------------------------------------------------------------
 static thread_local std::string g_err;
 static const void* g_op_wfrag = nullptr;  // kk_debug_set_op_wfrag: fragment-order weights for the single-kernel conv entry points
-static int g_op_variant = 4;              // kk_debug_set_op_variant: which fragment-order kernel they use (4 or 5)
+static float g_op_post_slope = 0.f;       // kk_debug_set_op_post_slope: LeakyReLU of the final stored value in those calls (0 = none)
+static int g_op_variant = 4;              // kk_debug_set_op_variant: which fragment-order kernel they use (4, 5, or 40 = variant 4 slab by slab)
 
 int kk_fail(const char* msg) {
   g_err = msg ? msg : "unknown error";
@@ -157,6 +158,7 @@ struct kk_context {
   hipStream_t side_stream = nullptr;
   hipEvent_t side_fork[2] = {nullptr, nullptr}, side_join[2] = {nullptr, nullptr};
   bool no_side = false;  // debug bit 8 of kk_debug_force_generic: everything on the caller's stream
+  bool no_wholek = false;  // debug bit 11: variant 4 slab by slab also where its whole-K form is routed (the form's reference path)
   int linrows_mode = 0;  // debug bits 9 / 10: the streaming Linear kernel never / at every size (default: up to 1024 rows in flight)
   struct ProfRec { int cls; double flops; double bytes; };
   std::vector<ProfRec> prof_rec;
@@ -933,6 +935,10 @@ struct Ctx : Workspace {  // Workspace::raw never runs past `cap`: every entry p
       // Linear layers over short utterances (Albert, T = 130 rows per item): the rows of a dense [B][T][C] tensor as ONE flat item, so that the
       // 192-row tiles run across utterance boundaries (32 x 130 rows = 22 tiles instead of 32).  k = 1, so rows do not interact; input rows past
       // an utterance's length are zeros already and the epilogue stores zeros there (KKMfmaArgs::flat_T).
+      // whole-K form of variant 4 (CinP == 128: both slabs staged in the prologue), per layer class as measured: the fused AdaIN
+      // layers at every tap count that variant 4 runs (-9 % at 3 taps, -8 % at 7, -4 ... -7 % at 11 where variant 5 is not eligible); plain
+      // inputs stay slab by slab (level at 3 taps: with no transform there is little staging to take out of the loop)
+      g.slabwise = (cx->no_wholek || !g.nrm_a) ? 1 : 0;
       int Bl = B;
       if (!v5 && B > 1 && w.Kw == 1 && o.mode == KK_CONV && o.stride == 1 && o.pad == 0 && o.dil == 1 && o.in_shift == 0 && !o.nrm_a && !o.want_stats &&
           Q == x.rows && Q == out.rows && Q % 192 != 0 && x.bs == (long long)x.rows * x.ld && out.bs == (long long)out.rows * out.ld &&
@@ -1720,7 +1726,9 @@ extern "C" int kk_op_conv1d_bf16(void* stream, int B, const void* x, int ldx, in
   if (!kk_mfma_eligible(CinP, Cout, Kw, g.mode, stride, dil)) return kk_fail("kk_op_conv1d_bf16: shape not eligible for the MFMA kernel");
   if (g_op_wfrag && out_dtype == KK_BF16) {
     g.wf = (const bf16_t*)g_op_wfrag;
+    g.post_slope = g_op_post_slope;
     if (g_op_variant == 5 && kk_mfma5_eligible(g, out_dtype)) return kk_launch_conv_mfma5(g, B, out_dtype, (hipStream_t)stream);
+    g.slabwise = g_op_variant == 40;
     return kk_launch_conv_mfma4(g, B, out_dtype, (hipStream_t)stream);
   }
   return kk_launch_conv_mfma(g, B, out_dtype, (hipStream_t)stream);
@@ -1747,7 +1755,9 @@ extern "C" int kk_op_conv1d_bf16_fused(void* stream, int B, const void* x, int l
   if (!kk_mfma_eligible(CinP, Cout, Kw, KK_CONV, 1, dil)) return kk_fail("kk_op_conv1d_bf16_fused: shape not eligible for the MFMA kernel");
   if (g_op_wfrag) {
     g.wf = (const bf16_t*)g_op_wfrag;
+    g.post_slope = g_op_post_slope;
     if (g_op_variant == 5 && kk_mfma5_eligible(g, KK_BF16)) return kk_launch_conv_mfma5(g, B, KK_BF16, (hipStream_t)stream);
+    g.slabwise = g_op_variant == 40;
     return kk_launch_conv_mfma4(g, B, KK_BF16, (hipStream_t)stream);
   }
   return kk_launch_conv_mfma(g, B, KK_BF16, (hipStream_t)stream);
@@ -1895,6 +1905,7 @@ extern "C" void kk_debug_force_generic(kk_context* cx, int on) {
   cx->keep_debug = (on & 16) != 0;      // bit 4: also materialise the tensors that fused kernels skip (conv_post), for kk_debug_fetch
   cx->no_head_fusion = (on & 32) != 0;  // bit 5: stand-alone conv_post + iSTFT head kernels instead of the fused head
   cx->no_side = (on & 256) != 0;        // bit 8: no side stream (every launch of a forward on the caller's stream)
+  cx->no_wholek = (on & 2048) != 0;     // bit 11: conv variant 4 slab by slab also where its whole-K form is routed (CinP == 128)
   cx->linrows_mode = (on & 512) ? 2 : (on & 1024) ? 1 : 0;  // bit 9: Linear layers never on the streaming kernel; bit 10: always (default: by the rows in flight)
   cx->v5_mode = (on & 64) ? 1 : (on & 128) ? 2 : 0;  // bit 6: conv variant 5 (wave-specialised persistent) wherever eligible; bit 7: never (default: >= 9 taps)
 }
@@ -1945,7 +1956,8 @@ extern "C" int kk_op_linear_mxfp8(void* stream, const void* x_bf16, int ldx, int
   return kk_launch_linear_mxfp8(f, (hipStream_t)stream);
 }
 extern "C" void kk_debug_set_op_wfrag(const void* w_frag) { g_op_wfrag = w_frag; }
-extern "C" void kk_debug_set_op_variant(int v) { g_op_variant = v == 5 ? 5 : 4; }
+extern "C" void kk_debug_set_op_post_slope(float slope) { g_op_post_slope = slope; }
+extern "C" void kk_debug_set_op_variant(int v) { g_op_variant = (v == 5 || v == 40) ? v : 4; }
 extern "C" int kk_op_pack_w_frag(void* stream, const void* w_bf16, void* w_frag, int Kw, int CoutP, int CinP) {
   return kk_launch_pack_w_frag(w_bf16, w_frag, Kw, CoutP, CinP, (hipStream_t)stream);
 }

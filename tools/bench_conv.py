@@ -19,6 +19,7 @@ SHAPES = [
     # name, B, L, Cin, Cout, K, dil, residual
     ("st1_k3", 32, 78001, 128, 128, 3, 1, True),
     ("st1_k7_d3", 32, 78001, 128, 128, 7, 3, True),
+    ("st1_k11", 32, 78001, 128, 128, 11, 1, True),
     ("st1_k11_d5", 32, 78001, 128, 128, 11, 5, True),
     ("st0_k3", 32, 13000, 256, 256, 3, 1, True),
     ("st0_k7", 32, 13000, 256, 256, 7, 1, True),
@@ -59,7 +60,7 @@ def run(name, B, L, Cin, Cout, K, dil, res, iters=5, fused=False):
         wf = torch.empty_like(w)
         assert lib.kk_op_pack_w_frag(st(), P(w), P(wf), K, CoutP, CinP) == 0
         lib.kk_debug_set_op_wfrag(P(wf))
-        lib.kk_debug_set_op_variant(5 if V5 else 4)
+        lib.kk_debug_set_op_variant(5 if V5 else 40 if SLABWISE else 4)
     call = call_fused if fused else call_plain
     call()
     torch.cuda.synchronize()
@@ -96,7 +97,7 @@ def run(name, B, L, Cin, Cout, K, dil, res, iters=5, fused=False):
     if V4:
         torch.cuda.synchronize()
         lib.kk_debug_set_op_wfrag(None)
-    out = {"name": name + ("+fused" if fused else "") + ("+v5" if V5 else "+v4" if V4 else ""), "ms": round(ms, 4), "TFLOPs": round(fl / ms / 1e9, 1), "GBs": round(by / ms / 1e6, 1)}
+    out = {"name": name + ("+fused" if fused else "") + ("+v5" if V5 else "+v4slabwise" if SLABWISE else "+v4" if V4 else ""), "ms": round(ms, 4), "TFLOPs": round(fl / ms / 1e9, 1), "GBs": round(by / ms / 1e6, 1)}
     if trace:
         out["trace_cycles"] = trace
     return out
@@ -104,6 +105,7 @@ def run(name, B, L, Cin, Cout, K, dil, res, iters=5, fused=False):
 
 V5 = "--v5" in sys.argv
 V4 = "--v4" in sys.argv or V5
+SLABWISE = V4 and not V5 and "--slabwise" in sys.argv  # variant 4 slab by slab also where its whole-K form applies (the A/B reference)
 
 if __name__ == "__main__":
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
