@@ -40,14 +40,20 @@ Admissions off the batch's stream: `CSMBatcher(..., overlap_admission=True, pref
 in a LANE -- a `share()` generator with one cache row -- on a side stream while the batch keeps stepping: the same `admit` / `admit(prefix=)`
 calls, so the same first frame and K / V.  When a row is free and the lane's event has completed, the request is COMMITTED: one copy launch
 moves the lane's window into the row (kk_csm_admit_transfer), which is all the batch's stream pays for the admission.  FIFO order is kept, and
-every request still carries the bits of its own `generate_batch([prompt])` run."""
+every request still carries the bits of its own `generate_batch([prompt])` run.
+
+Stopping: `cancel(handle)` and `interrupt(handle, played_frames=)` (also on a `CSMAudioStream` and a `CSMSession`).  A caller's thread
+only records the wish; the scheduler applies it at the top of its next round.  A cancelled request leaves the queue, its lane or its row at once
+and never happened: `CancelledError` for whoever waits, the session as it was.  An interrupted stream ends NOW with the k frames that were heard:
+its limit is lowered to k and the EOS flags are polled, so its result, its last chunk and -- for a session's turn -- the K / V the next turn
+is conditioned on are those of a turn of k frames.  The other rows see a park and a poll, neither of which they can tell from any other."""
 from __future__ import annotations
 
 import queue
 import threading
 import time
 from collections import deque
-from concurrent.futures import Future
+from concurrent.futures import CancelledError, Future, InvalidStateError
 from dataclasses import dataclass, field
 from typing import Deque, Dict, List, Optional, Sequence
 
@@ -65,6 +71,7 @@ class StreamResult:
     stream_id: int
     row: int                       # the cache row the stream ran in
     processing_time_seconds: float  # submit -> result
+    interrupted: bool = False      # ended by `interrupt`: `frames` is what was kept of it
 
 
 @dataclass
@@ -78,17 +85,19 @@ class AudioChunk:
 
 class CSMAudioStream:
     """What `submit_stream` returns.  Iterating yields the request's `AudioChunk`s as the scheduler produces them and ends behind the final
-    one; a failed request (or `close()`) ends the iteration by raising its error, never by hanging.  `result(timeout)` is the usual
-    `StreamResult`; its audio is the concatenation of the chunks.  `first_audio_seconds`: submit -> first chunk, once there is one."""
+    one; a failed request (or `close()`) ends the iteration by raising its error and a cancelled one by raising `CancelledError`, never by
+    hanging.  `result(timeout)` is the usual `StreamResult`; its audio is the concatenation of the chunks (of an interrupted stream: cut to
+    the frames kept).  `first_audio_seconds`: submit -> first chunk, once there is one.  `cancel()` / `interrupt(...)`: the batcher's."""
 
-    def __init__(self, future: Future):
+    def __init__(self, future: Future, batcher: Optional["CSMBatcher"] = None):
         self.future = future
+        self._batcher = batcher
         self.first_audio_seconds: Optional[float] = None
         self._q: "queue.Queue" = queue.Queue()
         future.add_done_callback(self._ended)
 
     def _ended(self, fut: Future) -> None:  # a failure from ANY path of the scheduler reaches the consumer (success: the final chunk is already queued)
-        e = fut.exception()
+        e = CancelledError() if fut.cancelled() else fut.exception()
         if e is not None:
             self._q.put(e)
 
@@ -103,6 +112,12 @@ class CSMAudioStream:
 
     def result(self, timeout: Optional[float] = None) -> StreamResult:
         return self.future.result(timeout)
+
+    def cancel(self) -> bool:
+        return self._batcher.cancel(self)
+
+    def interrupt(self, played_frames: Optional[int] = None, played_samples: Optional[int] = None) -> bool:
+        return self._batcher.interrupt(self, played_frames=played_frames, played_samples=played_samples)
 
 
 @dataclass
@@ -134,6 +149,9 @@ class _Stream:
     lane: int = -1                  # overlap_admission: the prefill lane that holds the request until it is committed
     prefill: object = None          # what the engine's `prefill` returned for it
     admit_args: Optional[tuple] = None  # (sampler, seed) of its admission: what `set_row_sampler` takes at the commit
+    cut: Optional[int] = None       # interrupt: the frames that were heard; the next poll ends the stream with at most that many
+    decodable: int = 0              # interrupt of a streaming request: the frames that poll confirmed before the cut (what the codec may be fed)
+    held: bool = True               # the scheduler still has the request (queue, lane or row): a cancelled turn keeps its session busy until it is dropped
 
 
 def _no_frames(n_cb: int):
@@ -167,6 +185,7 @@ class CSMSession:
         self._starts: List[int] = []  # where in `history` each turn begins
         self._voice = 0               # leading history frames that are no turn: the caller's voice prefix (`rebuild` keeps them)
         self._turn: Optional[Future] = None
+        self._stream: Optional[_Stream] = None  # the turn's request, while the scheduler has it
         self._closed = False
         if context is None:
             return
@@ -187,7 +206,9 @@ class CSMSession:
 
     @property
     def busy(self) -> bool:
-        return self._turn is not None and not self._turn.done()
+        """A turn is queued or live.  A cancelled turn counts until the scheduler has dropped it: its row is live until then."""
+        t, s = self._turn, self._stream
+        return t is not None and (not t.done() or (t.cancelled() and s is not None and s.held))
 
     def _ready(self, what: str) -> None:
         if self._closed:
@@ -213,6 +234,17 @@ class CSMSession:
     def submit_stream(self, text, **kw) -> CSMAudioStream:
         kw.setdefault("speaker", self.speaker)
         return self.batcher.submit_stream(session=self, text=text, **kw)
+
+    def cancel(self) -> bool:
+        """`CSMBatcher.cancel` of the session's queued or live turn: the turn did not happen, the session is as it was before its submit and takes
+        the next `submit` / `hear` once the scheduler has dropped the turn (`busy`).  False without such a turn."""
+        return self._turn is not None and self.batcher.cancel(self._turn)
+
+    def interrupt(self, played_frames: Optional[int] = None, played_samples: Optional[int] = None) -> bool:
+        """`CSMBatcher.interrupt` of the session's queued or live turn: the turn ends now and enters the history as a turn of the k frames that
+        were heard (its text frames stay whole: they are in the K / V already and the listener's side of the conversation has no say in them).
+        With k = 0 the turn is cancelled.  False without such a turn."""
+        return self._turn is not None and self.batcher.interrupt(self._turn, played_frames=played_frames, played_samples=played_samples)
 
     # ---- the end of a turn (the scheduler's thread) ------------------------------------------------------------------------------------
     def _capture(self, s: "_Stream", count: int) -> dict:
@@ -293,6 +325,12 @@ class ModelEngine:
         self.max_pos = int(self.csm.cfg["max_seq_len"])
         self.sample_rate = int(model.sample_rate)
         self.device = self.csm.device
+
+    @property
+    def samples_per_frame(self) -> int:
+        """Waveform samples of one frame: what `interrupt(played_samples=)` divides by (a frame is 80 ms where there is no codec to ask)."""
+        mimi = self.model._audio_tokenizer
+        return int(mimi.lib.kk_mimi_samples_per_frame(mimi._h)) if mimi is not None else int(round(self.sample_rate * 0.08))
 
     def start(self, max_batch: int) -> None:
         if not self.csm.caches_are_enabled() or self.csm.max_batch != max_batch:
@@ -506,6 +544,22 @@ def _check_sampler(sampler) -> None:
         raise ValueError("sampler out of range (temp >= 0, top_p and min_p in [0, 1], min_tokens_to_keep >= 1, top_k >= -1)")
 
 
+def _fail(s: _Stream, e: BaseException) -> None:
+    """The request failed and is nowhere in the scheduler any more.  A future that was cancelled meanwhile keeps its cancellation."""
+    s.held = False
+    try:
+        s.future.set_exception(e)
+    except InvalidStateError:
+        pass
+
+
+def _claim(fut: Future) -> bool:
+    """True: the future is the scheduler's to finish and a `cancel()` can no longer succeed; False: it is cancelled (or finished)."""
+    if fut.running():
+        return True
+    return not fut.done() and fut.set_running_or_notify_cancel()
+
+
 class CSMBatcher:
     def __init__(self, model, max_batch: int = 8, eos_check_interval: int = 8, rng: str = "device", sampler=None, seed: int = 0,
                  stop_on_eos: bool = True, decode: bool = True, profile: bool = False, engine=None, stream_chunk_frames: Optional[int] = None,
@@ -542,9 +596,10 @@ class CSMBatcher:
         self.row_samplers = bool(row_samplers)
         if self.row_samplers:
             _check_sampler(sampler)
-        self._lock = threading.Lock()          # queue, closed flag, stream id counter
+        self._lock = threading.Lock()          # queue, closed flag, stream id counter, pending controls
         self._wake = threading.Condition(self._lock)
         self._queue: Deque[_Stream] = deque()
+        self._controls: List[tuple] = []       # (future, "cancel" | "interrupt", frames heard or None): recorded by callers, applied by `step`
         self._closed = False
         self._thread: Optional[threading.Thread] = None
         self._next_id = 0
@@ -552,7 +607,7 @@ class CSMBatcher:
         self._since_poll = 0
         self.stats = {"frames": 0, "live_row_frames": 0, "admissions": 0, "admit_seconds": 0.0, "shifts": 0, "shift_seconds": 0.0,
                       "shifts_down": 0, "shifts_up": 0, "polls": 0, "finished": 0, "prefixed_admissions": 0, "session_admissions": 0, "captures": 0,
-                      "overlapped_admissions": 0, "commit_seconds": 0.0, "prefill_seconds": 0.0}
+                      "overlapped_admissions": 0, "commit_seconds": 0.0, "prefill_seconds": 0.0, "cancelled": 0, "interrupted": 0}
         self.engine.start(self.max_batch)
         self.overlap = bool(overlap_admission)
         self._lane_of: List[Optional[_Stream]] = []   # per lane: the request it holds
@@ -657,7 +712,7 @@ class CSMBatcher:
         if stream_id is not None and not 0 <= int(stream_id) < 2 ** 31:
             raise ValueError("stream_id must be in [0, 2^31)")
         fut: Future = Future()
-        audio = CSMAudioStream(fut) if _streaming else None
+        audio = CSMAudioStream(fut, self) if _streaming else None
         with self._lock:
             if self._closed:
                 fut.set_exception(RuntimeError("CSMBatcher is closed"))
@@ -672,17 +727,102 @@ class CSMBatcher:
                                        voice_match=True if voice_match is None else bool(voice_match),
                                        max_frames=max_frames, seed=seed, stream_id=int(stream_id), length=length, t0=time.perf_counter(),
                                        prompt=prompt, prefix=prefix, audio=audio, sampler=sampler, session=session))
+            if session is not None:
+                session._stream = self._queue[-1]
             self._wake.notify()
         return audio if _streaming else fut
+
+    # ---- stopping a request ------------------------------------------------------------------------------------------------
+    def _control(self, handle, kind: str, frames: Optional[int]) -> bool:
+        """A caller's thread: record the wish and wake the scheduler.  Nothing of the engine, the rows or the lanes is touched here."""
+        fut = handle.future if isinstance(handle, CSMAudioStream) else handle
+        if not isinstance(fut, Future):
+            raise TypeError("cancel / interrupt take what submit / submit_stream returned")
+        with self._lock:
+            if fut.done():
+                return False
+            self._controls.append((fut, kind, frames))
+            self._wake.notify()
+        return True
+
+    def cancel(self, handle) -> bool:
+        """The request of `handle` (the `Future` of `submit`, the `CSMAudioStream` of `submit_stream`) did not happen.  Applied at the top of the
+        scheduler's next round: a queued request is never admitted, one in a prefill lane leaves it, a live one has its row parked, without
+        a capture; the row goes to the next queued request in that round.  Then `future.cancelled()` is true, `result()` and the stream's
+        iterator raise `CancelledError`, and a session is what it was before the turn.  A plain `future.cancel()` has the same effect.
+        False, and no effect, for a request that has already finished.  Any thread."""
+        return self._control(handle, "cancel", None)
+
+    def interrupt(self, handle, played_frames: Optional[int] = None, played_samples: Optional[int] = None) -> bool:
+        """End the stream now and keep what was heard.  Heard: `played_frames`, or ceil(`played_samples` / samples per frame) -- a frame that was
+        partly played counts --, or with neither the frames emitted so far (`submit_stream`) / generated so far (`submit`).  Kept: k = min(heard,
+        the frames generated, the index of the first EOS frame, the request's limit).  Applied at the top of the scheduler's next round, with
+        one poll.  k >= 1: the future resolves with a `StreamResult` of k frames and `interrupted=True`; a plain request decodes its k frames,
+        a streaming one gets the chunks up to frame k it has not had yet -- the last with `final=True` -- or, when it has had them all,
+        one `AudioChunk` of 0 frames with `final=True`, and its result's audio is what was emitted cut to k frames.  A session's turn is
+        committed as a turn of k frames.  k = 0, a request still queued or in a prefill lane: as `cancel`.  False for a finished request.
+        Any thread."""
+        if played_frames is not None and played_samples is not None:
+            raise ValueError("interrupt takes played_frames or played_samples, not both")
+        heard = played_frames
+        if played_samples is not None:
+            heard = -(-int(played_samples) // int(self.engine.samples_per_frame))
+        if heard is not None and int(heard) < 0:
+            raise ValueError("played_frames / played_samples must be >= 0")
+        return self._control(handle, "interrupt", None if heard is None else int(heard))
+
+    def _release(self, s: _Stream) -> None:
+        """The stream's row is parked and free for the next admission."""
+        self.engine.park(s.row)
+        self._rows[s.row] = None
+        s.held = False
+
+    def _drop(self, s: _Stream) -> None:
+        """A cancelled request leaves the scheduler: a live row is parked without a capture (its decoder row is reset by the next admission)."""
+        if s.row >= 0 and self._rows[s.row] is s:
+            self._release(s)
+        s.held = False
+        s.future.cancel()
+        self.stats["cancelled"] += 1
+
+    def _apply_controls(self) -> bool:
+        """The scheduler's thread, at the top of a round: every request with a cancel wish or a cancelled future leaves the queue, its lane or
+        its row; an interrupt lowers its stream's limit.  True when a stream was interrupted: the round polls at once."""
+        with self._lock:
+            controls, self._controls = self._controls, []
+            wish: Dict[Future, list] = {}
+            for fut, kind, frames in controls:
+                wish.setdefault(fut, []).append((kind, frames))
+            gone = [s for s in self._queue if s.future.cancelled() or s.future in wish]  # (an interrupt of a request nobody has heard yet: a cancel)
+            for s in gone:
+                self._queue.remove(s)
+        for s in [s for s in self._inflight if s.future.cancelled() or s.future in wish]:
+            self._inflight.remove(s)  # (the others keep their order; the lane's next prefill starts from a reset, behind this one on the side stream)
+            self._lane_of[s.lane] = None
+            gone.append(s)
+        poll = False
+        for s in self._live():
+            w = wish.get(s.future)
+            if s.future.cancelled() or (w is not None and any(kind == "cancel" for kind, _ in w)):
+                gone.append(s)
+            elif w is not None:
+                so_far = s.emitted if s.audio is not None else len(s.codes)
+                s.cut = min([so_far if frames is None else frames for _, frames in w] + ([s.cut] if s.cut is not None else []))
+                poll = True
+        for s in gone:
+            self._drop(s)
+        return poll
 
     # ---- one scheduling round -----------------------------------------------------------------------------------------------------------
     def _live(self) -> List[_Stream]:
         return [s for s in self._rows if s is not None]
 
-    def _poll(self) -> None:
-        """One sync: which streams have ended (EOS frame seen, or their own frame limit), park their rows, decode, resolve."""
+    def _poll(self, keep_cadence: bool = False) -> None:
+        """One sync: which streams have ended (EOS frame seen, their own frame limit, or an interrupt: `cut`), park their rows, decode,
+        resolve.  keep_cadence: a poll an interrupt asked for between two regular ones, which come when they would have."""
         self.stats["polls"] += 1
-        self._since_poll = 0
+        if not keep_cadence:
+            self._since_poll = 0
         fe = self._first_eos.cpu().tolist() if self.stop_on_eos else [-1] * self.max_batch
         done: Dict[int, List[_Stream]] = {}
         streaming = [s for s in self._live() if s.audio is not None]
@@ -690,28 +830,37 @@ class CSMBatcher:
             eos = fe[s.row]
             s.confirmed = min(eos if eos >= 0 else len(s.codes), s.max_frames)
             s.ended = eos >= 0 or len(s.codes) >= s.max_frames
+            if s.cut is not None:  # interrupted: the stream ends here with what was heard of the confirmed frames
+                s.decodable, s.confirmed, s.ended = s.confirmed, min(s.confirmed, s.cut), True
+                if s.confirmed == 0:  # nothing was heard: the request did not happen
+                    self._drop(s)
+                    continue
             if s.ended:
                 self._turn_end(s, s.confirmed)
-                self.engine.park(s.row)
-                self._rows[s.row] = None  # (the decoder row keeps its state until the next admission resets it: the tail is decoded below)
+                self._release(s)  # (the decoder row keeps its state until the next admission resets it: the tail is decoded below)
         if streaming:
             self._emit(streaming)
         for s in self._live():
             if s.audio is not None:
                 continue
             eos = fe[s.row]
-            if eos < 0 and len(s.codes) < s.max_frames:
+            if eos < 0 and len(s.codes) < s.max_frames and s.cut is None:
                 continue
             count = min(eos if eos >= 0 else len(s.codes), s.max_frames)  # frames past the EOS frame / the limit are dropped
+            if s.cut is not None:  # interrupted: and those that were not heard
+                count = min(count, s.cut)
+                if count == 0:  # nothing was heard: the request did not happen
+                    self._drop(s)
+                    continue
             self._turn_end(s, count)
-            self.engine.park(s.row)
-            self._rows[s.row] = None
+            self._release(s)
             done.setdefault(count, []).append(s)
         for count, group in done.items():
             self.stats["finished"] += len(group)
+            self.stats["interrupted"] += sum(s.cut is not None for s in group)
             if count == 0:
                 for s in group:
-                    s.future.set_exception(AssertionError("No audio generated"))
+                    _fail(s, AssertionError("No audio generated"))
                 continue
             try:
                 codes = torch.stack([torch.stack(s.codes[:count], dim=1) for s in group])  # [b, n_cb, T]
@@ -721,11 +870,10 @@ class CSMBatcher:
                 for j, s in enumerate(group):
                     self._resolve(s, StreamResult(audio=pcm[j] if pcm is not None else None, frames=count, codes=codes[j],
                                                   sample_rate=self.engine.sample_rate, stream_id=s.stream_id, row=s.row,
-                                                  processing_time_seconds=time.perf_counter() - s.t0))
+                                                  processing_time_seconds=time.perf_counter() - s.t0, interrupted=s.cut is not None))
             except Exception as e:  # noqa: BLE001
                 for s in group:
-                    if not s.future.done():
-                        s.future.set_exception(e)
+                    _fail(s, e)
 
     # ---- sessions ----------------------------------------------------------------------------------------------------------
     def _turn_end(self, s: _Stream, count: int) -> None:
@@ -737,12 +885,12 @@ class CSMBatcher:
         try:
             s.captured = c = s.session._capture(s, count)
             self.stats["captures"] += 1
-            s.future.add_done_callback(lambda f: c["prefix"].close() if f.exception() is not None else None)
+            s.future.add_done_callback(lambda f: c["prefix"].close() if f.cancelled() or f.exception() is not None else None)
         except Exception as e:  # noqa: BLE001
             s.capture_error = e
 
     def _resolve(self, s: _Stream, result: StreamResult) -> None:
-        if s.future.done():
+        if not _claim(s.future):  # cancelled on the way here: nothing is committed (the capture is destroyed by its callback)
             return
         if s.capture_error is not None:
             s.future.set_exception(s.capture_error)
@@ -762,26 +910,37 @@ class CSMBatcher:
             if not ready:
                 break
             self._decode_round(ready, N)
-        tails: Dict[int, List[_Stream]] = {}
+        tails: Dict[tuple, List[_Stream]] = {}
         for s in streams:
             if s.ended and not s.future.done() and 0 < s.confirmed - s.emitted:
-                tails.setdefault(s.confirmed - s.emitted, []).append(s)
-        for r, group in tails.items():
-            self._decode_round(group, r)
+                r = s.confirmed - s.emitted
+                # An interrupted stream's last chunk goes through the step its chunk would have had -- the N frames if they exist -- and is cut
+                # to the r frames that were heard: the codec is causal, so these are the samples the uninterrupted stream carries there.
+                tails.setdefault((r, min(N, s.decodable - s.emitted) if s.cut is not None else r), []).append(s)
+        for (r, F), group in tails.items():
+            self._decode_round(group, F, keep=r)
         for s in streams:
             if not s.ended or s.future.done():
                 continue
             self.stats["finished"] += 1
             if s.confirmed == 0:
-                s.future.set_exception(AssertionError("No audio generated"))
+                _fail(s, AssertionError("No audio generated"))
                 continue
-            self._resolve(s, StreamResult(audio=torch.cat(s.chunks), frames=s.confirmed, codes=torch.stack(s.codes[: s.confirmed], dim=1),
+            audio = torch.cat(s.chunks)
+            if s.cut is not None:
+                self.stats["interrupted"] += 1
+                if s.emitted >= s.confirmed:  # it has had every frame that was heard: the iterator ends behind an empty chunk
+                    audio = audio[: s.confirmed * (audio.shape[0] // s.emitted)]
+                    s.audio._q.put(AudioChunk(audio=audio[:0], first_frame=s.confirmed, frames=0, final=True))
+            self._resolve(s, StreamResult(audio=audio, frames=s.confirmed, codes=torch.stack(s.codes[: s.confirmed], dim=1),
                                           sample_rate=self.engine.sample_rate, stream_id=s.stream_id, row=s.row,
-                                          processing_time_seconds=time.perf_counter() - s.t0))
+                                          processing_time_seconds=time.perf_counter() - s.t0, interrupted=s.cut is not None))
 
-    def _decode_round(self, group: List[_Stream], F: int) -> None:
-        """One step of the row decoder: F frames for the rows of `group`, the other rows inactive.  A failure fails the group's requests
-        (their iterators raise) and frees their rows; the other streams go on."""
+    def _decode_round(self, group: List[_Stream], F: int, keep: Optional[int] = None) -> None:
+        """One step of the row decoder: F frames for the rows of `group`, the other rows inactive; the chunks carry the first `keep` of them
+        (all, but for an interrupted stream's last chunk).  A failure fails the group's requests (their iterators raise) and frees their
+        rows; the other streams go on."""
+        keep = F if keep is None else keep
         try:
             codes = torch.zeros((self.max_batch, self.engine.n_cb, F), dtype=torch.int32, device=self.engine.device)
             active = [False] * self.max_batch
@@ -792,20 +951,19 @@ class CSMBatcher:
             self.engine.synchronize()
             self.stats["chunk_rounds"] += 1
             for s in group:
-                chunk = AudioChunk(audio=pcm[s.row, 0].clone(), first_frame=s.emitted, frames=F, final=s.ended and s.emitted + F == s.confirmed)
+                chunk = AudioChunk(audio=pcm[s.row, 0, : keep * (pcm.shape[-1] // F)].clone(), first_frame=s.emitted, frames=keep,
+                                   final=s.ended and s.emitted + keep == s.confirmed)
                 s.chunks.append(chunk.audio)
-                s.emitted += F
+                s.emitted += keep
                 if s.audio.first_audio_seconds is None:
                     s.audio.first_audio_seconds = time.perf_counter() - s.t0
                 self.stats["chunks"] += 1
                 s.audio._q.put(chunk)
         except Exception as e:  # noqa: BLE001
             for s in group:
-                if not s.future.done():
-                    s.future.set_exception(e)
+                _fail(s, e)
                 if self._rows[s.row] is s:
-                    self._rows[s.row] = None
-                    self.engine.park(s.row)
+                    self._release(s)
 
     def _timed(self, what: str, fn) -> None:
         if self.profile:
@@ -842,6 +1000,9 @@ class CSMBatcher:
                 s = self._queue.popleft() if self._queue else None
             if s is None:
                 break
+            if s.future.cancelled():
+                self._drop(s)
+                continue
             began = True
             lane = self._lane_of.index(None)
             try:
@@ -854,7 +1015,7 @@ class CSMBatcher:
                 s.admit_args = (sampler, seed)
                 s.prefill = self.engine.prefill(lane, s.prompt, sampler, u, seed, s.stream_id, prefix=s.prefix, timed=self.profile)
             except Exception as e:  # noqa: BLE001  (the lane stays free: its next prefill starts from a reset)
-                s.future.set_exception(e)
+                _fail(s, e)
                 continue
             s.lane = lane
             self._lane_of[lane] = s
@@ -897,7 +1058,7 @@ class CSMBatcher:
                 if self.profile:
                     self.stats["prefill_seconds"] += self.engine.prefill_seconds(s.prefill)
             except Exception as e:  # noqa: BLE001
-                s.future.set_exception(e)
+                _fail(s, e)
                 if moved:
                     self.engine.park(row)
                 continue
@@ -911,8 +1072,7 @@ class CSMBatcher:
         else:
             self._inflight.remove(s)
         self._lane_of[s.lane] = None
-        if not s.future.done():
-            s.future.set_exception(e)
+        _fail(s, e)
 
     def _seat(self, s: _Stream, row: int, codes: torch.Tensor) -> None:
         """The request's stream is live in `row` with `codes` as its first frame."""
@@ -937,6 +1097,9 @@ class CSMBatcher:
         free = [r for r in range(self.max_batch) if self._rows[r] is None]
         with self._lock:
             new = [self._queue.popleft() for _ in range(min(len(free), len(self._queue)))]
+        for s in [s for s in new if s.future.cancelled()]:  # (cancelled since the top of the round: no prompt is built for it)
+            new.remove(s)
+            self._drop(s)
         if not new:
             return
         need = [s for s in new if s.prompt is None]
@@ -945,7 +1108,7 @@ class CSMBatcher:
                 s.prompt = p
         except Exception as e:  # noqa: BLE001
             for s in need:
-                s.future.set_exception(e)
+                _fail(s, e)
             new = [s for s in new if s.prompt is not None]
         for s, row in zip(new, free):
             S = int(s.prompt[0].shape[0]) + (int(s.prefix.length) if s.prefix is not None else 0)  # the whole prompt: what must fit below P
@@ -967,13 +1130,13 @@ class CSMBatcher:
                 if self.row_samplers:
                     self.engine.set_row_sampler(row, sampler, seed)
             except Exception as e:  # noqa: BLE001
-                s.future.set_exception(e)
+                _fail(s, e)
                 continue
             if s.audio is not None:
                 try:
                     self._dec.reset_row(row)  # the decoder row is the cache row: a new stream starts in it
                 except Exception as e:  # noqa: BLE001
-                    s.future.set_exception(e)
+                    _fail(s, e)
                     self.engine.park(row)
                     continue
             self._seat(s, row, codes)
@@ -1037,12 +1200,18 @@ class CSMBatcher:
 
     def step(self) -> bool:
         """One scheduling round; False when there was nothing to do (no live stream, empty queue)."""
+        now = self._apply_controls()  # (before the admissions: a row a cancel has freed is refilled in this round)
         while True:
             self._admit()  # (rows a poll has just freed are refilled in the same round)
             live = self._live()
-            if not (live and (self._since_poll >= self.interval or any(len(s.codes) >= s.max_frames for s in live))):
+            due = self._since_poll >= self.interval or any(len(s.codes) >= s.max_frames for s in live)
+            if not (live and (due or now)):
                 break
-            self._poll()
+            if due:
+                self._poll()
+            else:
+                self._poll(keep_cadence=True)
+            now = False
         if not self._live():
             return False
         self._frame()
@@ -1072,7 +1241,7 @@ class CSMBatcher:
     def _worker(self) -> None:
         while True:
             with self._lock:
-                while not self._closed and not self._queue and not self._live() and not self._inflight:
+                while not self._closed and not self._queue and not self._live() and not self._inflight and not self._controls:
                     self._wake.wait()
                 if self._closed:
                     return
@@ -1080,15 +1249,14 @@ class CSMBatcher:
                 self.step()
             except Exception as e:  # noqa: BLE001  (a failed round fails the streams in flight, the thread lives on)
                 for s in self._live():
-                    if not s.future.done():
-                        s.future.set_exception(e)
-                    self._rows[s.row] = None
-                    self.engine.park(s.row)
+                    _fail(s, e)
+                    self._release(s)
 
     def close(self) -> None:
         """Stop the worker.  Requests still queued or in flight are FAILED, never dropped (their callers sit in Future.result()); the
         closed flag and the queue change under one lock, so a submit() that races close() either lands in the queue before the flag --
-        and is failed here -- or sees the flag and fails at once."""
+        and is failed here -- or sees the flag and fails at once.  A request with a `cancel` still pending is cancelled instead; a pending
+        `interrupt` is not applied (no round runs any more) and its request fails like the others."""
         with self._lock:
             self._closed = True
             self._wake.notify_all()
@@ -1098,15 +1266,17 @@ class CSMBatcher:
         with self._lock:
             pending = list(self._queue)
             self._queue.clear()
+            unwanted = {fut for fut, kind, _ in self._controls if kind == "cancel"}
+            self._controls = []
         held = list(self._inflight)  # prefilled or being prefilled in a lane, not committed
         self._inflight.clear()
         self._lane_of = [None] * len(self._lane_of)
         for s in pending + held + self._live():
-            if not s.future.done():
-                s.future.set_exception(RuntimeError("CSMBatcher is closed"))
+            if s.future in unwanted:
+                s.future.cancel()
+            _fail(s, RuntimeError("CSMBatcher is closed"))
         for s in self._live():
-            self._rows[s.row] = None
-            self.engine.park(s.row)
+            self._release(s)
         if self._dec is not None:
             self._dec.close()
         if self.overlap:

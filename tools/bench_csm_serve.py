@@ -22,7 +22,12 @@ profiles/csm_serve_session_bench.json.
 --overlap [--lanes N]: instead, the mixed workload three times in one process: continuous / with `overlap_admission=True` (every request prefilled in
 a lane on a side stream and committed by one copy) / continuous again; per run wall, audio-s/s, occupancy and (a second, profiled run) the mean
 stall of the batch's stream per admission -- the admission itself, or the commit --, the lanes' device time per prefill, and the frame step's time
-while a prefill was in flight beside its time while none was.  Written to profiles/csm_serve_overlap_bench.json."""
+while a prefill was in flight beside its time while none was.  Written to profiles/csm_serve_overlap_bench.json.
+--stream-chunk N --abandon FRACTION: instead, the streamed workload (with the codec) three times in one process: every stream left to run to its
+limit -- what happens to a stream whose listener has gone when nothing can stop it -- / a seeded FRACTION of the requests interrupted
+(`CSMAudioStream.interrupt(played_frames=)`) once a seeded number of their chunks has come out / left to run again; per run finished requests per
+second, the mean submit -> first audio of the requests that were queued behind a full batch, and the occupancy.  Written to
+profiles/csm_serve_interrupt_bench.json."""
 import argparse
 import json
 import os
@@ -49,6 +54,7 @@ ap.add_argument("--max-seq-len", type=int, default=512)
 ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--prefix", type=int, default=0, help="frames of a voice prefix shared by every request (0: the static / continuous comparison)")
 ap.add_argument("--stream-chunk", type=int, default=0, help="frames per audio chunk: time to first audio of submit_stream against plain submit")
+ap.add_argument("--abandon", type=float, default=0.0, help="with --stream-chunk: share of the requests whose listener leaves (interrupted against left to run)")
 ap.add_argument("--sessions", type=int, default=0, help="dialogues run as sessions against full-history resubmission (with --turns)")
 ap.add_argument("--turns", type=int, default=4)
 ap.add_argument("--overlap", action="store_true", help="continuous batching with admissions prefilled on a side stream against plain continuous batching")
@@ -56,7 +62,7 @@ ap.add_argument("--lanes", type=int, default=1, help="prefill lanes of --overlap
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 if a.out is None:
-    name = "csm_serve_overlap_bench.json" if a.overlap else "csm_serve_session_bench.json" if a.sessions else "csm_serve_stream_bench.json" if a.stream_chunk else "csm_serve_prefix_bench.json" if a.prefix else "csm_serve_bench.json"
+    name = "csm_serve_overlap_bench.json" if a.overlap else "csm_serve_session_bench.json" if a.sessions else "csm_serve_interrupt_bench.json" if a.abandon else "csm_serve_stream_bench.json" if a.stream_chunk else "csm_serve_prefix_bench.json" if a.prefix else "csm_serve_bench.json"
     a.out = os.path.join(ROOT, "profiles", name)
 
 cfg = dict(P.csm_config(), max_seq_len=a.max_seq_len)
@@ -251,6 +257,45 @@ def bench_stream():
     return res
 
 
+def bench_abandon():
+    N = a.stream_chunk
+    pick = np.random.default_rng(a.seed + 1)
+    gone = sorted(pick.choice(a.requests, max(1, int(round(a.abandon * a.requests))), replace=False).tolist())
+    played = {i: int(pick.integers(1, (flen[i] - 1) // N + 1)) for i in gone}  # chunks that came out before the listener left: fewer than the stream has
+
+    def run(interrupt):
+        bat = loop.serve(max_batch=B, rng="device", sampler=sampler, seed=a.seed, stop_on_eos=False, stream_chunk_frames=N, stream_max_frames=max(LENGTHS))
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        hs = [bat.submit_stream(None, None, prompt=prompts[i], max_audio_length_ms=80 * flen[i]) for i in range(a.requests)]
+        waiting = dict(played) if interrupt else {}
+        while bat.step() or bat._queue:
+            for i in [i for i, c in waiting.items() if hs[i]._q.qsize() >= c]:
+                hs[i].interrupt(played_frames=waiting.pop(i) * N)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t
+        res = [h.result(timeout=0) for h in hs]
+        assert [r.frames for r in res] == [played[i] * N if interrupt and i in played else flen[i] for i in range(a.requests)]
+        behind = [hs[i].first_audio_seconds for i in range(B, a.requests)]  # all are queued at time 0: the first B get a row at once
+        st, occ = dict(bat.stats), bat.occupancy
+        bat.close()
+        return {"wall_s": dt, "finished_requests_per_s": a.requests / dt, "first_audio_s_mean_queued_behind_full_batch": float(np.mean(behind)) if behind else None,
+                "occupancy": occ, "frame_steps": st["frames"], "polls": st["polls"], "interrupted": st["interrupted"],
+                "audio_s_delivered": 0.08 * sum(r.frames for r in res), "audio_s_generated": 0.08 * (st["live_row_frames"] + st["admissions"])}
+
+    run(False), run(True)  # warm-up: kernel loading, workspaces, graph capture
+    res = {"metric": "CSM-1B serving with the codec: abandoned streams interrupted vs left to run to their limit, " + a.weights, "requests": a.requests,
+           "batch": B, "max_seq_len": a.max_seq_len, "chunk_frames": N, "abandon": a.abandon, "abandoned_requests": gone,
+           "played_chunks": [played[i] for i in gone], "stream_frames": flen, "order": ["left_first", "interrupted", "left_last"],
+           "note": "all requests are queued at time 0; an interrupt is issued between two scheduling rounds once the stream's played chunks have come out",
+           "data": "synthetic (random-init CSM-1B and mimi_202407 weights, random text prompts, imposed stream lengths, device uniforms)"}
+    res["left_first"], res["interrupted"], res["left_last"] = run(False), run(True), run(False)
+    left = [res["left_first"]["finished_requests_per_s"], res["left_last"]["finished_requests_per_s"]]
+    res["value"] = res["interrupted"]["finished_requests_per_s"] / (0.5 * sum(left))
+    res["value_is"] = "interrupted / left finished requests per second (left: mean of the two runs; they differ by %.3f requests/s)" % abs(left[0] - left[1])
+    return res
+
+
 def bench_sessions():
     N, K, T, F = a.sessions, a.turns, 24, 25
     texts = [[rng.integers(0, cfg["text_vocab_size"], T).tolist() for _ in range(K)] for _ in range(N)]
@@ -324,10 +369,15 @@ if a.sessions:
         f.write("\n")
     sys.exit(0)
 
+if a.abandon and not a.stream_chunk:
+    sys.exit("--abandon needs --stream-chunk N")
+
 if a.stream_chunk:
     if a.prefix or not 1 <= a.stream_chunk <= min(LENGTHS):
         sys.exit(f"--stream-chunk must be in [1, {min(LENGTHS)}] and excludes --prefix")
-    out = bench_stream()
+    if a.abandon and not (0.0 < a.abandon <= 1.0 and a.stream_chunk < min(LENGTHS)):
+        sys.exit(f"--abandon must be in (0, 1] and needs --stream-chunk below {min(LENGTHS)}")
+    out = bench_abandon() if a.abandon else bench_stream()
     print(json.dumps(out))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
