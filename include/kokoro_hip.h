@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 8   /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 9   /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -38,7 +38,9 @@ extern "C" {
                                kk_mimi_stream_row_frames, kk_mimi_stream_row_snapshot);
                             6: per-row sampler settings of a CSM batch (kk_csm_set_row_sampler, kk_csm_generate_frame_rows, kk_op_csm_sample_rows);
                             7: a prefix captured from a live cache row (kk_csm_prefix_capture);
-                            8: a finished admission moved between two generators' cache rows (kk_csm_admit_transfer) */
+                            8: a finished admission moved between two generators' cache rows (kk_csm_admit_transfer);
+                            9: row-mode streaming Mimi ENCODE (kk_mimi_stream_create_rows_encoder, kk_mimi_encode_step_rows; kk_mimi_stream_reset_row,
+                               kk_mimi_stream_row_frames, kk_mimi_stream_set_context and kk_mimi_stream_row_snapshot take either direction) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -300,6 +302,18 @@ int kk_mimi_stream_reset_row(kk_mimi_stream* s, void* stream, int row);
 int kk_mimi_stream_row_frames(const kk_mimi_stream* s, int row);
 int kk_mimi_decode_step_rows(kk_mimi_stream* s, void* stream, int F, const int32_t* codes, const int32_t* active, void* workspace, size_t workspace_bytes, float* pcm_out);
 int kk_mimi_stream_row_snapshot(kk_mimi_stream* s, void* stream, int row, int32_t* pos_out, float* dst, size_t dst_floats, size_t* floats_out);
+/* Row mode of the ENCODER (ABI minor 9): the same stream object for Mimi.encode_step, for microphones that start and stop on their own.  The
+ * checkpoint must hold encoder.* parameters.  kk_mimi_encode_step_rows takes F <= max_chunk frames of pcm for ALL max_batch rows
+ * (pcm [max_batch][F * samples_per_frame] float32 on the device, active [max_batch] on the HOST) and writes codes [max_batch][nq][F].  An
+ * active row's codes equal, as integers, those of a fresh batch-1 kk_mimi_encode_step stream fed the same pcm in the same step sizes, whatever
+ * the other rows do.  The resampler's 'edge' left padding is per row: an active row at position 0 (new, or after kk_mimi_stream_reset_row) has
+ * its carried rows filled from its own first new row; no other row is touched.  An inactive row's pcm may hold anything (NaN, inf): nothing of
+ * it reaches another row or its own carried rows, K / V and position; its code entries are unspecified and written in range.  Every bound
+ * (frames per row, F, workspace, direction) is checked on the host before any launch.  kk_mimi_decode_step_rows on an encoder stream,
+ * kk_mimi_encode_step_rows on a decoder stream and kk_mimi_encode_step on a row-mode stream are refused.  kk_mimi_stream_row_snapshot holds the
+ * K / V of the encoder's layers for such a stream. */
+int kk_mimi_stream_create_rows_encoder(kk_mimi* m, int max_batch, int max_frames, int max_chunk, kk_mimi_stream** out);
+int kk_mimi_encode_step_rows(kk_mimi_stream* s, void* stream, int F, const float* pcm, const int32_t* active, void* workspace, size_t workspace_bytes, int32_t* codes_out);
 /* intermediates of the last decode / encode (tests): "quantized", "upsampled", "transformer", "layer0".."layer3" (decode), "seanet", "transformer", "downsampled" (encode); [B][rows][channels] fp32 */
 int kk_mimi_debug_info(kk_mimi* m, const char* name, int64_t* rows, int64_t* channels);
 int kk_mimi_debug_fetch(kk_mimi* m, void* stream, const char* name, float* dst);

@@ -168,6 +168,8 @@ SIGNATURES = {
     "kk_mimi_stream_row_frames": (_i, [_vp, _i]),
     "kk_mimi_decode_step_rows": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "kk_mimi_stream_row_snapshot": (_i, [_vp, _vp, _i, C.POINTER(C.c_int32), _vp, _sz, C.POINTER(_sz)]),
+    "kk_mimi_stream_create_rows_encoder": (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+    "kk_mimi_encode_step_rows": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "kk_mimi_encode_frames": (_i, [_vp, _i]),
     "kk_mimi_encode_workspace_bytes": (_sz, [_vp, _i, _i]),
     "kk_mimi_encode": (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
@@ -217,7 +219,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 8:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 9:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

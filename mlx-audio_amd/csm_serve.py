@@ -46,7 +46,15 @@ Stopping: `cancel(handle)` and `interrupt(handle, played_frames=)` (DESIGN 8d-8;
 only records the wish; the scheduler applies it at the top of its next round.  A cancelled request leaves the queue, its lane or its row at once
 and never happened: `CancelledError` for whoever waits, the session as it was.  An interrupted stream ends NOW with the k frames that were heard:
 its limit is lowered to k and the EOS flags are polled, so its result, its last chunk and -- for a session's turn -- the K / V the next turn
-is conditioned on are those of a turn of k frames.  The other rows see a park and a poll, neither of which they can tell from any other."""
+is conditioned on are those of a turn of k frames.  The other rows see a park and a poll, neither of which they can tell from any other.
+
+Listening: `CSMBatcher(..., listen_rows=K)` and `batcher.listen()` / `sess.listen(speaker)`.  A `CSMListener` takes microphone
+audio in arbitrary slices (`feed`, any thread, host work only) -- also while the session's own turn is live, which is what a barge-in is -- and
+the scheduler tokenises it as it arrives in a row-mode streaming ENCODER (`Mimi.row_encoder`: one position and lifetime per row, independent of
+the cache rows).  The steps of a listener's stream are fixed by its length alone, [M] * (T // M) + [T % M] with M = listen_chunk_frames, so its
+codes never depend on timing or slicing: they equal a fresh batch-1 `Mimi.encode_step` stream over its zero-padded pcm in those steps.  These
+are streaming-encoder codes, NOT those of `Mimi.encode(clip)` (whose transformer sees the whole clip without a mask).  `end(text)` resolves
+with a `ListenResult`; for a session's listener the turn has entered the history by then exactly as `hear(Segment(...), codes=codes)` does."""
 from __future__ import annotations
 
 import queue
@@ -81,6 +89,106 @@ class AudioChunk:
     first_frame: int
     frames: int
     final: bool          # the stream's last chunk: `result()` is ready
+
+
+@dataclass
+class ListenResult:
+    """What a listener's `end()` resolves with.  `codes` are streaming-encoder codes (`Mimi.encode_step` in `steps`), not `Mimi.encode`'s."""
+    codes: torch.Tensor  # [n_cb, frames] int32
+    frames: int          # T = ceil(samples / samples per frame): a partial last frame is zero-padded
+    samples: int         # samples fed
+    steps: List[int]     # the encoder steps of this stream: [M] * (T // M) + [T % M]
+
+
+class CSMListener:
+    """What `CSMBatcher.listen` / `CSMSession.listen` return: one microphone.  `feed(pcm)` from any thread, `frames` / `codes()` for what
+    has been tokenised so far, `end(text)` for the `Future[ListenResult]`, `cancel()` to drop it.  It holds one row of the batcher's row-mode
+    streaming encoder from `listen` until the result (or `cancel`)."""
+
+    def __init__(self, batcher: "CSMBatcher", row: int, speaker: int, session=None):
+        self.batcher, self.row, self.speaker, self.session = batcher, int(row), int(speaker), session
+        self.spf = int(batcher.engine.samples_per_frame)
+        self._pcm = np.zeros(batcher.listen_max_frames * self.spf, np.float32)  # (zeros behind `samples`: the padding of a partial last frame)
+        self.samples = 0                      # fed
+        self.frames = 0                       # encoded
+        self.steps: List[int] = []
+        self._codes: List[torch.Tensor] = []  # one [n_cb, F] device tensor per step
+        self._fresh = True                    # the encoder row is reset before this listener's first step
+        self._future: Optional[Future] = None
+        self._text = None
+        self._open = True                     # False once cancelled or resolved: the row is someone else's
+
+    @property
+    def ended(self) -> bool:
+        return self._future is not None
+
+    def _total(self) -> int:
+        """Frames the stream holds for the scheduler: whole frames while it is open, ceil once it has ended."""
+        return -(-self.samples // self.spf) if self.ended else self.samples // self.spf
+
+    def feed(self, pcm) -> None:
+        """Mono float32 at the model's sample rate, any number of samples.  Host work only: the samples join a buffer under the batcher's
+        lock and an idle scheduler is woken.  ValueError, with nothing changed, when the total would pass `listen_max_frames`."""
+        a = np.asarray(pcm, np.float32).reshape(-1)
+        b = self.batcher
+        with b._lock:
+            if b._closed:
+                raise RuntimeError("CSMBatcher is closed")
+            if not self._open or self.ended:
+                raise ValueError("feed: the listener has ended or was cancelled")
+            if self.samples + a.shape[0] > self._pcm.shape[0]:
+                raise ValueError(f"feed: {self.samples + a.shape[0]} samples are more than listen_max_frames = {b.listen_max_frames} frames")
+            self._pcm[self.samples : self.samples + a.shape[0]] = a
+            self.samples += int(a.shape[0])
+            b._wake.notify()
+
+    def codes(self) -> torch.Tensor:
+        """The codes encoded so far, [n_cb, frames] int32 on the host (a copy from the device)."""
+        with self.batcher._lock:
+            parts = list(self._codes)
+        if not parts:
+            return torch.zeros((self.batcher.engine.n_cb, 0), dtype=torch.int32)
+        return torch.cat(parts, dim=1).cpu()
+
+    def end(self, text=None) -> Future:
+        """No more audio; a partial last frame is zero-padded.  The future resolves with the `ListenResult` once the scheduler has encoded the
+        rest and freed the encoder row.  A session's listener: `text` is the turn's transcript, and the turn enters the session's history
+        before the future resolves, as `hear(Segment(speaker, text, audio), codes=codes)` would put it.  Refused (ValueError, the listener
+        stays open) while the session's turn is queued or live, as `hear` is; from here to the result the session is busy."""
+        b = self.batcher
+        with b._lock:
+            if b._closed:
+                raise RuntimeError("CSMBatcher is closed")
+            if not self._open or self.ended:
+                raise ValueError("end: the listener has ended or was cancelled")
+            if self.samples == 0:
+                raise ValueError("end: nothing was fed")
+            if self.session is not None:
+                if text is None:
+                    raise ValueError("end: a session's heard turn needs its text")
+                self.session._ready("end")
+            fut: Future = Future()
+            self._text = text
+            if self.session is not None:
+                self.session._hearing = fut
+            self._future = fut
+            b._wake.notify()
+        return fut
+
+    def cancel(self) -> bool:
+        """Drop the buffered audio and free the encoder row; a pending `end()` future is cancelled and the session is as it was.  False when
+        the listener has already finished."""
+        b = self.batcher
+        with b._lock:
+            if not self._open:
+                return False
+            self._open = False
+            if b._listeners[self.row] is self:
+                b._listeners[self.row] = None
+            fut = self._future
+        if fut is not None:
+            fut.cancel()
+        return True
 
 
 class CSMAudioStream:
@@ -186,6 +294,7 @@ class CSMSession:
         self._voice = 0               # leading history frames that are no turn: the caller's voice prefix (`rebuild` keeps them)
         self._turn: Optional[Future] = None
         self._stream: Optional[_Stream] = None  # the turn's request, while the scheduler has it
+        self._hearing: Optional[Future] = None  # a listener's `end()`, until the scheduler has entered the heard turn
         self._closed = False
         if context is None:
             return
@@ -207,7 +316,9 @@ class CSMSession:
     @property
     def busy(self) -> bool:
         """A turn is queued or live.  A cancelled turn counts until the scheduler has dropped it: its row is live until then."""
-        t, s = self._turn, self._stream
+        t, s, h = self._turn, self._stream, self._hearing
+        if h is not None and not h.done():  # from a listener's `end()` to its result
+            return True
         return t is not None and (not t.done() or (t.cancelled() and s is not None and s.held))
 
     def _ready(self, what: str) -> None:
@@ -221,11 +332,21 @@ class CSMSession:
         They join `pending`; the frame generator sees them at the next admission.  The clip goes through `Model.encode_audios` here, on the
         caller's thread, unless `codes` [n_cb, T] (its Mimi codes) are passed."""
         self._ready("hear")
+        self._hear(segment, codes)
+
+    def _hear(self, segment, codes) -> None:
         f = self.engine.segment_frames(segment, codes)
         f = (np.asarray(f[0], np.int32), np.asarray(f[1], np.float32))
         self._starts.append(int(self.history[0].shape[0]))
         self.turns.append((int(segment.speaker), segment.text, 0))
         self.pending, self.history = _cat(self.pending, f), _cat(self.history, f)
+
+    def listen(self, speaker: int = 0) -> "CSMListener":
+        """`CSMBatcher.listen` for this conversation: another speaker's microphone.  Allowed while the session's own turn is queued or live
+        (a barge-in); the turn enters the history at the listener's `end(text)`, which waits for that turn as `hear` does."""
+        if self._closed:
+            raise ValueError("listen: the session is closed")
+        return self.batcher.listen(speaker=speaker, session=self)
 
     def submit(self, text, **kw) -> Future:
         kw.setdefault("speaker", self.speaker)
@@ -456,6 +577,18 @@ class ModelEngine:
             raise ValueError("streaming audio needs the Mimi codec: pass mimi= or config['mimi_path']")
         return self.model._audio_tokenizer.row_decoder(max_batch, max_frames, max_chunk)
 
+    def row_encoder(self, max_batch: int, max_frames: int, max_chunk: int):
+        """The codec's row-mode streaming encoder (mimi.MimiRowEncoder): reset_row, step(pcm, active), row_frames, close."""
+        if self.model._audio_tokenizer is None:
+            raise ValueError("listening needs the Mimi codec: pass mimi= or config['mimi_path']")
+        return self.model._audio_tokenizer.row_encoder(max_batch, max_frames, max_chunk)
+
+    def heard_segment(self, speaker: int, text, audio):
+        """The `Segment` a listened turn enters a session's history as (`CSMSession._hear` -> `segment_frames`)."""
+        from .sesame import Segment
+
+        return Segment(speaker=int(speaker), text=text, audio=audio)
+
     def synchronize(self) -> None:
         torch.cuda.current_stream(self.device).synchronize()
 
@@ -563,7 +696,8 @@ def _claim(fut: Future) -> bool:
 class CSMBatcher:
     def __init__(self, model, max_batch: int = 8, eos_check_interval: int = 8, rng: str = "device", sampler=None, seed: int = 0,
                  stop_on_eos: bool = True, decode: bool = True, profile: bool = False, engine=None, stream_chunk_frames: Optional[int] = None,
-                 stream_max_frames: int = 1125, row_samplers: bool = False, overlap_admission: bool = False, prefill_lanes: int = 1):
+                 stream_max_frames: int = 1125, row_samplers: bool = False, overlap_admission: bool = False, prefill_lanes: int = 1,
+                 listen_rows: int = 0, listen_chunk_frames: int = 6, listen_max_frames: int = 375):
         """model: a loaded sesame.Model (its frame generator's caches are taken over; use `model.share()` for a generator of its own).
         sampler: `make_sampler(...)` for every stream of the batch (default temp 0.9 / top_k 50; with `row_samplers` the default of a request).  seed: the device generator's seed (rng
         "device": one seed per batcher, streams differ by their ids).  profile: time admissions and shifts (one sync each) into `stats`.
@@ -576,7 +710,11 @@ class CSMBatcher:
         default: the frame step is the launch-argument one, and a per-request sampler or a foreign seed is refused.
         overlap_admission: True prefills every request in one of `prefill_lanes` lanes (a `share()` generator with one cache row each, one side
         stream for all) while the batch keeps stepping, and commits it with one copy when a row is free and the lane is done.
-        Off by default: no lane is made and admissions run on the batch's stream."""
+        Off by default: no lane is made and admissions run on the batch's stream.
+        listen_rows: K > 0 enables `listen` (up to K listeners at a time) on one row-mode streaming encoder of K rows; encoder rows are not
+        cache rows, so listening never occupies a generation row.  listen_chunk_frames: M, the frames of one encode step (a listener's
+        stream is always encoded in [M] * (T // M) + [T % M]).  listen_max_frames: the longest heard turn (the encoder's K / V cache holds
+        that many frames per row; 375 = 30 s).  0: no encoder is made and `step` is what it was."""
         if overlap_admission and int(prefill_lanes) < 1:
             raise ValueError("prefill_lanes must be >= 1")
         if rng not in ("host", "device"):
@@ -585,6 +723,8 @@ class CSMBatcher:
             raise ValueError("max_batch and eos_check_interval must be >= 1")
         if stream_chunk_frames is not None and (int(stream_chunk_frames) < 1 or int(stream_max_frames) < int(stream_chunk_frames) or not decode):
             raise ValueError("stream_chunk_frames must be in [1, stream_max_frames] and needs decode=True")
+        if int(listen_rows) < 0 or (int(listen_rows) > 0 and not 1 <= int(listen_chunk_frames) <= int(listen_max_frames)):
+            raise ValueError("listen_rows must be >= 0 and listen_chunk_frames in [1, listen_max_frames]")
         if sampler is None:
             from .sesame import make_sampler
 
@@ -624,6 +764,12 @@ class CSMBatcher:
             self.interval = self.chunk  # a chunk is decoded once a poll has confirmed it: poll at the chunk cadence
             self.stats.update(chunks=0, chunk_rounds=0)
             self._dec = self.engine.row_decoder(self.max_batch, self.stream_max_frames, self.chunk)
+        self.listen_rows, self.listen_chunk, self.listen_max_frames = int(listen_rows), int(listen_chunk_frames), int(listen_max_frames)
+        self._enc = None
+        self._listeners: List[Optional[CSMListener]] = [None] * self.listen_rows  # per encoder row (under the lock)
+        if self.listen_rows > 0:
+            self.stats.update(listen_rounds=0, listen_frames=0, listen_seconds=0.0)
+            self._enc = self.engine.row_encoder(self.listen_rows, self.listen_max_frames, self.listen_chunk)
         dev = self.engine.device
         self._prev = torch.zeros((self.max_batch, self.engine.n_cb), dtype=torch.int32, device=dev)
         self._first_eos = torch.full((self.max_batch,), -1, dtype=torch.int64, device=dev)  # stream-local index of the first all-zero frame
@@ -634,6 +780,120 @@ class CSMBatcher:
         """A conversation on this batcher (`CSMSession`).  context: None, a `Model.voice_prefix(...)` (its K / V are used as they are and stay
         the caller's), or segments that the session hears before its first turn.  speaker: the default speaker of the session's own turns."""
         return CSMSession(self, context, speaker)
+
+    def listen(self, speaker: int = 0, session: Optional[CSMSession] = None) -> CSMListener:
+        """A microphone (`CSMListener`) on a free row of the batcher's streaming encoder; ValueError when all `listen_rows` are taken (or
+        the batcher was made without any).  `session`: what `CSMSession.listen` passes.  Any thread; nothing of the device is touched."""
+        if self._enc is None:
+            raise ValueError("listen needs a batcher made with listen_rows=K")
+        if session is not None and session.batcher is not self:
+            raise ValueError("the session belongs to another batcher (CSMBatcher.session on this batcher)")
+        with self._lock:
+            if self._closed:
+                raise RuntimeError("CSMBatcher is closed")
+            free = [r for r in range(self.listen_rows) if self._listeners[r] is None]
+            if not free:
+                raise ValueError(f"all {self.listen_rows} listen rows are taken")
+            lis = self._listeners[free[0]] = CSMListener(self, free[0], speaker, session)
+        return lis
+
+    # ---- listening (DESIGN 8d-9) -----------------------------------------------------------------------------------------------------------
+    def _listen_plan(self):
+        """Under the lock: (rows with >= M frames not yet encoded, ended rows by remainder 0 < r < M, ended rows with nothing left)."""
+        M = self.listen_chunk
+        full, tails, done = [], {}, []
+        for lis in self._listeners:
+            if lis is None or not lis._open:
+                continue
+            left = lis._total() - lis.frames
+            if left >= M:
+                full.append(lis)
+            elif lis.ended and left > 0:
+                tails.setdefault(left, []).append(lis)
+            elif lis.ended:
+                done.append(lis)
+        return full, tails, done
+
+    def _listen_due(self) -> bool:
+        full, tails, done = self._listen_plan()
+        return bool(full or tails or done)
+
+    def _listen_round(self) -> bool:
+        """The scheduler's thread, once per scheduling round: ONE encode step of M frames for every row that holds M frames not yet encoded,
+        then one step per distinct remainder r for the ended rows whose remainder is due, then the ended rows with nothing left resolve.  A
+        listener's steps are therefore [M] * (T // M) + [T % M] whatever the slicing and the timing of its `feed` calls."""
+        with self._lock:
+            full, _, _ = self._listen_plan()
+        if full:
+            self._encode_round(full, self.listen_chunk)
+        with self._lock:
+            _, tails, _ = self._listen_plan()  # (after the full round: a row it brought to its remainder goes on in this round)
+        for r in sorted(tails):
+            self._encode_round(tails[r], r)
+        with self._lock:
+            _, _, done = self._listen_plan()
+        for lis in done:
+            self._listen_finish(lis)
+        return bool(full or tails or done)
+
+    def _encode_round(self, group: List[CSMListener], F: int) -> None:
+        """One step of the row encoder: F frames for the rows of `group`, the other rows inactive.  A failure fails the group's listeners."""
+        try:
+            spf = group[0].spf
+            pcm = np.zeros((self.listen_rows, 1, F * spf), np.float32)
+            active = [False] * self.listen_rows
+            for lis in group:
+                if lis._fresh:  # a new stream starts in the row: zero carried state, position 0, the edge fill on this step
+                    self._enc.reset_row(lis.row)
+                    lis._fresh = False
+                pcm[lis.row, 0] = lis._pcm[lis.frames * spf : (lis.frames + F) * spf]  # (zeros behind the fed samples)
+                active[lis.row] = True
+            out: List[torch.Tensor] = []
+            self._timed("listen", lambda: out.append(self._enc.step(torch.from_numpy(pcm), active)))
+            self.stats["listen_rounds"] += 1
+            self.stats["listen_frames"] += F * len(group)
+            with self._lock:
+                for lis in group:
+                    lis._codes.append(out[0][lis.row].clone())
+                    lis.steps.append(F)
+                    lis.frames += F
+        except Exception as e:  # noqa: BLE001
+            for lis in group:
+                self._listen_fail(lis, e)
+
+    def _listen_free(self, lis: CSMListener) -> None:
+        with self._lock:
+            lis._open = False
+            if self._listeners[lis.row] is lis:
+                self._listeners[lis.row] = None
+
+    def _listen_fail(self, lis: CSMListener, e: BaseException) -> None:
+        self._listen_free(lis)
+        if lis._future is not None:
+            try:
+                lis._future.set_exception(e)
+            except InvalidStateError:
+                pass
+
+    def _listen_finish(self, lis: CSMListener) -> None:
+        """An ended listener has all its frames: free its row, enter a session's heard turn, resolve."""
+        fut = lis._future
+        self._listen_free(lis)
+        if not _claim(fut):
+            return
+        try:
+            codes = torch.cat(lis._codes, dim=1)
+            if lis.session is not None:
+                if lis.session._closed:
+                    raise ValueError("end: the session is closed")
+                host = codes.cpu().numpy()  # (synchronises: the codes are the session's prompt frames from here on)
+                seg = self.engine.heard_segment(lis.speaker, lis._text, lis._pcm[: lis.samples].copy())
+                lis.session._hear(seg, host)  # before the result: whoever waits on it finds the turn in the history
+            fut.set_result(ListenResult(codes=codes, frames=lis.frames, samples=lis.samples, steps=list(lis.steps)))
+        except Exception as e:  # noqa: BLE001
+            fut.set_exception(e)
+            if lis.session is not None and lis.session._closed:
+                lis.session.close()  # (closed while it was busy with this listener: its prefix is freed now)
 
     def submit(self, context=None, text=None, speaker: int = 0, voice_match: Optional[bool] = None, max_audio_length_ms: float = 90_000,
                seed: Optional[int] = None, stream_id: Optional[int] = None, prompt=None, prefix=None, sampler=None, session=None) -> Future:
@@ -1199,8 +1459,9 @@ class CSMBatcher:
         return self.engine.frame(self._prev, self.sampler, u, seed, ids).clone()  # (graph replay hands back a view of a persistent buffer)
 
     def step(self) -> bool:
-        """One scheduling round; False when there was nothing to do (no live stream, empty queue)."""
+        """One scheduling round; False when there was nothing to do (no live stream, empty queue, no listen round due)."""
         now = self._apply_controls()  # (before the admissions: a row a cancel has freed is refilled in this round)
+        heard = self._enc is not None and self._listen_round()  # due listen rounds are work, with or without a live row
         while True:
             self._admit()  # (rows a poll has just freed are refilled in the same round)
             live = self._live()
@@ -1213,7 +1474,7 @@ class CSMBatcher:
                 self._poll(keep_cadence=True)
             now = False
         if not self._live():
-            return False
+            return heard
         self._frame()
         if self.overlap:
             self._begin_prefills()  # (also the lane a commit of this round has freed)
@@ -1241,7 +1502,8 @@ class CSMBatcher:
     def _worker(self) -> None:
         while True:
             with self._lock:
-                while not self._closed and not self._queue and not self._live() and not self._inflight and not self._controls:
+                while (not self._closed and not self._queue and not self._live() and not self._inflight and not self._controls
+                       and not (self._enc is not None and self._listen_due())):
                     self._wake.wait()
                 if self._closed:
                     return
@@ -1268,6 +1530,10 @@ class CSMBatcher:
             self._queue.clear()
             unwanted = {fut for fut, kind, _ in self._controls if kind == "cancel"}
             self._controls = []
+            listeners = [lis for lis in self._listeners if lis is not None]
+            self._listeners = [None] * self.listen_rows
+            for lis in listeners:
+                lis._open = False
         held = list(self._inflight)  # prefilled or being prefilled in a lane, not committed
         self._inflight.clear()
         self._lane_of = [None] * len(self._lane_of)
@@ -1277,8 +1543,16 @@ class CSMBatcher:
             _fail(s, RuntimeError("CSMBatcher is closed"))
         for s in self._live():
             self._release(s)
+        for lis in listeners:  # a pending `end()` fails; a listener that never ended just stops
+            if lis._future is not None and not lis._future.done():
+                try:
+                    lis._future.set_exception(RuntimeError("CSMBatcher is closed"))
+                except InvalidStateError:
+                    pass
         if self._dec is not None:
             self._dec.close()
+        if self._enc is not None:
+            self._enc.close()
         if self.overlap:
             self.engine.close_lanes()
 

@@ -259,7 +259,9 @@ __global__ __launch_bounds__(256) void rvq_argmin_kernel(const float* dots, cons
     }
     __syncthreads();
   }
-  const int idx = si[0];
+  // every distance NaN or +inf (an inactive row of a row-mode step may carry anything): no thread found a minimum and si[0] is still the
+  // sentinel; the clamp keeps the code-book read in range.  A row with one finite distance is not affected.
+  const int idx = si[0] < bins ? si[0] : bins - 1;
   if (tid == 0) codes[((long long)b * nq + cbi) * T + t] = idx;
   float* r = residual + ((long long)b * T + t) * qdim;
   for (int c = tid; c < qdim; c += 256) r[c] -= cb[(long long)idx * qdim + c];
@@ -684,6 +686,16 @@ __global__ __launch_bounds__(256) void state_edge_fill_kernel(float* p, int S, i
   for (int e = threadIdx.x; e < S * C; e += 256) q[e] = q[(long long)S * C + e % C];
 }
 
+// the same fill per row of a row-mode encoder stream (grid: one block per row): only a row that is active AND at position 0 -- its first
+// step after creation or kk_mimi_stream_reset_row -- gets it.  A row further on keeps its carried rows, an inactive row is not touched.
+// It runs in stream order before the masked carry that advances pos[], so pos[row] is the row's position BEFORE this step.
+__global__ __launch_bounds__(256) void state_edge_fill_rows_kernel(float* p, int S, int C, long long pitch, const int* active, const int* pos) {
+  const int row = blockIdx.x;
+  if (!active[row] || pos[row] != 0) return;
+  float* q = p + (long long)row * pitch;
+  for (int e = threadIdx.x; e < S * C; e += 256) q[e] = q[(long long)S * C + e % C];
+}
+
 int state_shift(const StateBuf& b, int B, hipStream_t st) {
   if (b.S == 0) return 0;
   if (b.S * b.C > 256 * SHIFT_PER_THREAD) return kk_fail("mimi stream: carried state larger than the shift kernel takes");
@@ -967,7 +979,7 @@ int run_encode_step(Run& r, kk_mimi_stream* s, const float* pcm, int* codes) {
   const kk_mimi_config& c = m->cfg;
   const int B = r.B, D = c.dim, Q = c.qdim, us = c.upsample_stride, F = s->chunk, T = F * us;
   const int N = s->first.n;
-  if (!r.dry && s->pos + T > s->max_pos) return kk_fail("kk_mimi_encode_step: the stream is longer than max_frames (kk_mimi_encode_stream_create)");
+  if (!r.dry && !s->rows_mode && s->pos + T > s->max_pos) return kk_fail("kk_mimi_encode_step: the stream is longer than max_frames (kk_mimi_encode_stream_create)");
   stream_elu_scratch(r, s);
   if (r.oom) return kk_fail("kk_mimi_encode_step: workspace too small");
   KK_TRY(stream_begin(r, s));
@@ -975,7 +987,7 @@ int run_encode_step(Run& r, kk_mimi_stream* s, const float* pcm, int* codes) {
   in.p = const_cast<float*>(pcm); in.rows = N; in.C = 1; in.ld = 1; in.dtype = KK_F32;
   KK_TRY(copy_rows(r, in, 0, s->first.fresh(), N));
   KK_TRY(r.conv(m->enc_init, s->first.all(), s->blk[0].fresh(), 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
-  if (!r.dry) KK_TRY(state_shift(s->first, B, r.st));
+  KK_TRY(carry(r, s, s->first));
   for (size_t l = 0; l < m->enc_sea.size(); ++l) {
     const SeaLayer& S = m->enc_sea[l];
     const StateBuf& Bk = s->blk[l];
@@ -986,27 +998,31 @@ int run_encode_step(Run& r, kk_mimi_stream* s, const float* pcm, int* codes) {
     KK_TRY(r.conv(S.b0, Bk.all(), hb, 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
     const Act skip = Bk.fresh();
     KK_TRY(r.conv(S.b1, hb, Dn.fresh(), 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, &skip, 0));
-    if (!r.dry) KK_TRY(state_shift(Bk, B, r.st));
+    KK_TRY(carry(r, s, Bk));
     KK_TRY(r.conv(S.up, Dn.all(), nextb.fresh(), 0, 1, false, S.ratio, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
-    if (!r.dry) KK_TRY(state_shift(Dn, B, r.st));
+    KK_TRY(carry(r, s, Dn));
   }
   Act x = r.act(T, D), n = r.act(T, D), qkv = r.act(T, 3 * D), att = r.act(T, D), hbuf = r.act(T, c.dim_feedforward);
   Act xd = r.act(F, D), res = r.act(F, Q), dots = r.act(F, c.bins), xs = r.act(T, D);
   if (r.oom) return kk_fail("kk_mimi_encode_step: workspace too small");
   KK_TRY(r.conv(m->enc_final, s->last.all(), xs, 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
-  if (!r.dry) KK_TRY(state_shift(s->last, B, r.st));
+  KK_TRY(carry(r, s, s->last));
   r.note("seanet", xs);
   KK_TRY(copy_rows(r, xs, 0, x, T));  // (the transformer updates x in place; xs stays for the debug hook)
   KK_TRY(run_transformer_step(r, s, m->enc_layers, x, n, qkv, att, hbuf));
   r.note("transformer", x);
   // downsample.step: conv k = 2 us, stride us, 'edge' left padding on the first step
   KK_TRY(copy_rows(r, x, 0, s->resample.fresh(), T));
-  if (!r.dry && s->fresh) {
+  if (!r.dry && s->rows_mode) {  // per row: active rows at position 0 only
+    hipLaunchKernelGGL(state_edge_fill_rows_kernel, dim3(B), dim3(256), 0, r.st, s->resample.p, s->resample.S, s->resample.C, s->resample.pitch(),
+                       (const int*)s->active_dev, (const int*)s->pos_dev);
+    KK_CHECK_LAUNCH();
+  } else if (!r.dry && s->fresh) {
     hipLaunchKernelGGL(state_edge_fill_kernel, dim3(B), dim3(256), 0, r.st, s->resample.p, s->resample.S, s->resample.n, s->resample.C, s->resample.pitch());
     KK_CHECK_LAUNCH();
   }
   KK_TRY(r.conv(m->enc_down, s->resample.all(), xd, 0, 1, false, us, 0, KK_ACT_NONE, nullptr, 0));
-  if (!r.dry) KK_TRY(state_shift(s->resample, B, r.st));
+  KK_TRY(carry(r, s, s->resample));
   r.note("downsampled", xd);
   for (int i = 0; i < c.nq; ++i) {  // split RVQ search, as in run_encode
     if (i == 0) KK_TRY(r.conv(m->inproj_first, xd, res, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
@@ -1018,7 +1034,10 @@ int run_encode_step(Run& r, kk_mimi_stream* s, const float* pcm, int* codes) {
       KK_CHECK_LAUNCH();
     }
   }
-  if (!r.dry) {
+  if (!r.dry && s->rows_mode) {  // active rows: every buffer's carry and the position, one launch (the host mirror is the caller's)
+    hipLaunchKernelGGL(state_shift_rows_kernel, dim3(s->ntable, B), dim3(256), 0, r.st, s->table_dev, F, s->active_dev, s->pos_dev, T);
+    KK_CHECK_LAUNCH();
+  } else if (!r.dry) {
     s->pos += T;
     s->frames += F;
     s->fresh = false;
@@ -1374,7 +1393,7 @@ extern "C" size_t kk_mimi_stream_workspace_bytes(kk_mimi_stream* s, int B) {
 static int step_check(kk_mimi_stream* s, bool encoder, int B, const void* in, void* workspace, size_t workspace_bytes, void* out, const char* who) {
   if (!s || !in || !workspace || !out || B < 1 || B > s->max_batch) return kk_failf("%s: bad argument", who);
   if (s->encoder != encoder) return kk_failf("%s: the stream was created for the other direction", who);
-  if (s->rows_mode) return kk_failf("%s: a row-mode stream is stepped with kk_mimi_decode_step_rows", who);
+  if (s->rows_mode) return kk_failf("%s: a row-mode stream is stepped with %s", who, encoder ? "kk_mimi_encode_step_rows" : "kk_mimi_decode_step_rows");
   if (s->frames > 0 && B != s->B) return kk_failf("%s: the batch size of a stream is fixed until it is reset", who);
   if (workspace_bytes < kk_mimi_stream_workspace_bytes(s, B)) return kk_failf("%s: workspace too small", who);
   return 0;
@@ -1401,11 +1420,10 @@ extern "C" int kk_mimi_encode_step(kk_mimi_stream* s, void* stream, int B, const
 
 // ---- row mode (ABI minor 5): a decode stream in which every row has its own position and lifetime, for a codec that rides along with a
 // continuously batched generator (csm_serve.CSMBatcher).  Every bound is checked here, on the host mirror, before any launch.
-extern "C" int kk_mimi_stream_create_rows(kk_mimi* m, int max_batch, int max_frames, int max_chunk, kk_mimi_stream** out) {
-  const char* who = "kk_mimi_stream_create_rows";
+static int stream_create_rows(kk_mimi* m, bool encoder, int max_batch, int max_frames, int max_chunk, kk_mimi_stream** out, const char* who) {
   if (max_batch > 64) return kk_failf("%s: at most 64 rows (the active mask of a step is one 64-bit launch argument)", who);
   kk_mimi_stream* s = nullptr;
-  KK_TRY(stream_create(m, false, max_batch, max_frames, max_chunk, &s, who));
+  KK_TRY(stream_create(m, encoder, max_batch, max_frames, max_chunk, &s, who));
   std::vector<RowBuf> tab;
   auto add = [&](const StateBuf& b, int npf) {
     if (b.S > 0) tab.push_back(RowBuf{b.p, b.S, npf, b.C, b.pitch()});
@@ -1413,15 +1431,27 @@ extern "C" int kk_mimi_stream_create_rows(kk_mimi* m, int max_batch, int max_fra
   bool fits = true;
   auto chk = [&](const StateBuf& b) { fits = fits && b.S * b.C <= 256 * SHIFT_PER_THREAD; };
   const kk_mimi_config& c = m->cfg;
-  int npf = c.upsample_stride;
-  add(s->resample, 1); chk(s->resample);
-  add(s->first, npf); chk(s->first);
-  for (int l = 0; l < c.n_ratios; ++l) {
-    add(s->up[l], npf); chk(s->up[l]);
-    npf *= m->sea[l].ratio;
-    add(s->blk[l], npf); chk(s->blk[l]);
+  if (!encoder) {
+    int npf = c.upsample_stride;
+    add(s->resample, 1); chk(s->resample);
+    add(s->first, npf); chk(s->first);
+    for (int l = 0; l < c.n_ratios; ++l) {
+      add(s->up[l], npf); chk(s->up[l]);
+      npf *= m->sea[l].ratio;
+      add(s->blk[l], npf); chk(s->blk[l]);
+    }
+    add(s->last, npf); chk(s->last);
+  } else {  // the encoder's buffers (stream_layout): rows per code frame from samples per frame down to upsample_stride
+    int npf = (int)kk_mimi_samples_per_frame(m);
+    add(s->first, npf); chk(s->first);
+    for (int l = 0; l < c.n_ratios; ++l) {
+      add(s->blk[l], npf); chk(s->blk[l]);
+      add(s->up[l], npf); chk(s->up[l]);
+      npf /= m->enc_sea[l].ratio;
+    }
+    add(s->last, npf); chk(s->last);
+    add(s->resample, npf); chk(s->resample);  // npf == upsample_stride here
   }
-  add(s->last, npf); chk(s->last);
   s->ntable = (int)tab.size();
   s->rows_mode = true;
   s->fresh = false;  // (the pool is zeroed here, once; afterwards rows are reset one by one)
@@ -1443,6 +1473,13 @@ extern "C" int kk_mimi_stream_create_rows(kk_mimi* m, int max_batch, int max_fra
   *out = s;
   return 0;
 }
+extern "C" int kk_mimi_stream_create_rows(kk_mimi* m, int max_batch, int max_frames, int max_chunk, kk_mimi_stream** out) {
+  return stream_create_rows(m, false, max_batch, max_frames, max_chunk, out, "kk_mimi_stream_create_rows");
+}
+// ABI minor 9: the encoder in row mode (csm_serve's listeners: microphones that start and stop on their own)
+extern "C" int kk_mimi_stream_create_rows_encoder(kk_mimi* m, int max_batch, int max_frames, int max_chunk, kk_mimi_stream** out) {
+  return stream_create_rows(m, true, max_batch, max_frames, max_chunk, out, "kk_mimi_stream_create_rows_encoder");
+}
 // the row starts over: zero carried rows in every state buffer, position 0.  One launch in stream order; no other row's bytes are touched.
 extern "C" int kk_mimi_stream_reset_row(kk_mimi_stream* s, void* stream, int row) {
   if (!s || !s->rows_mode) return kk_fail("kk_mimi_stream_reset_row: not a row-mode stream (kk_mimi_stream_create_rows)");
@@ -1463,6 +1500,7 @@ extern "C" int kk_mimi_decode_step_rows(kk_mimi_stream* s, void* stream, int F, 
                                         size_t workspace_bytes, float* pcm_out) {
   const char* who = "kk_mimi_decode_step_rows";
   if (!s || !s->rows_mode) return kk_failf("%s: not a row-mode stream (kk_mimi_stream_create_rows)", who);
+  if (s->encoder) return kk_failf("%s: the stream was created for the other direction", who);
   if (!codes || !active || !workspace || !pcm_out) return kk_failf("%s: bad argument", who);
   if (F < 1 || F > s->max_chunk) return kk_failf("%s: %d frames per step, the stream takes 1 .. %d", who, F, s->max_chunk);
   const int max_frames = s->max_pos / s->m->cfg.upsample_stride;
@@ -1485,6 +1523,38 @@ extern "C" int kk_mimi_decode_step_rows(kk_mimi_stream* s, void* stream, int F, 
     if (active[b]) s->row_frames[b] += F;
   return 0;
 }
+// The encoder's row step (ABI minor 9): pcm [max_batch][F * samples_per_frame] float32 (device), active [max_batch] (HOST) ->
+// codes [max_batch][nq][F] int32.  As above: all rows ride along, only active rows append K / V, carry and advance; an active row at
+// position 0 gets the resampler's 'edge' fill from its own first new row.  An inactive row's pcm may hold anything, non-finite values
+// included: every kernel of the step works per row, so nothing of it reaches another row, and its own carried rows, K / V and position are
+// not written; its code entries are unspecified (the code-book search clamps its pick into [0, bins)).
+extern "C" int kk_mimi_encode_step_rows(kk_mimi_stream* s, void* stream, int F, const float* pcm, const int32_t* active, void* workspace,
+                                        size_t workspace_bytes, int32_t* codes_out) {
+  const char* who = "kk_mimi_encode_step_rows";
+  if (!s || !s->rows_mode) return kk_failf("%s: not a row-mode stream (kk_mimi_stream_create_rows_encoder)", who);
+  if (!s->encoder) return kk_failf("%s: the stream was created for the other direction", who);
+  if (!pcm || !active || !workspace || !codes_out) return kk_failf("%s: bad argument", who);
+  if (F < 1 || F > s->max_chunk) return kk_failf("%s: %d frames per step, the stream takes 1 .. %d", who, F, s->max_chunk);
+  const int max_frames = s->max_pos / s->m->cfg.upsample_stride;
+  unsigned long long mask = 0;
+  for (int b = 0; b < s->max_batch; ++b) {
+    if (!active[b]) continue;
+    if (s->row_frames[b] + F > max_frames)
+      return kk_failf("%s: row %d would hold %d frames, the stream was created for %d (kk_mimi_stream_create_rows_encoder)", who, b, s->row_frames[b] + F, max_frames);
+    mask |= 1ull << b;
+  }
+  if (workspace_bytes < kk_mimi_stream_workspace_bytes(s, s->max_batch)) return kk_failf("%s: workspace too small", who);
+  stream_set_rows(s, F);
+  { std::lock_guard<std::mutex> lk(s->m->dbg_mu); s->m->dbg.map.clear(); }
+  hipLaunchKernelGGL(set_active_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, s->active_dev, mask, s->max_batch);
+  KK_CHECK_LAUNCH();
+  Run r(s->m, (hipStream_t)stream, s->max_batch, workspace, workspace_bytes);
+  r.adt = KK_F32;
+  KK_TRY(run_encode_step(r, s, pcm, codes_out));
+  for (int b = 0; b < s->max_batch; ++b)
+    if (active[b]) s->row_frames[b] += F;
+  return 0;
+}
 // tests: one row's device state as the library holds it -- position (transformer rows), then the carried rows of every state buffer in
 // table order, then per layer its K and its V below the position.  dst == nullptr: only *floats_out.  Synchronises `stream`.
 extern "C" int kk_mimi_stream_row_snapshot(kk_mimi_stream* s, void* stream, int row, int32_t* pos_out, float* dst, size_t dst_floats, size_t* floats_out) {
@@ -1497,7 +1567,7 @@ extern "C" int kk_mimi_stream_row_snapshot(kk_mimi_stream* s, void* stream, int 
       hipMemcpy(tab.data(), s->table_dev, tab.size() * sizeof(RowBuf), hipMemcpyDeviceToHost) != hipSuccess)
     return kk_failf("%s: copy failed", who);
   if (pos < 0 || pos > s->max_pos) return kk_failf("%s: the device position %d is outside the cache", who, pos);
-  const size_t D = s->m->cfg.dim, nl = s->m->layers.size();
+  const size_t D = s->m->cfg.dim, nl = s->encoder ? s->m->enc_layers.size() : s->m->layers.size();
   size_t need = 2 * nl * (size_t)pos * D;
   for (const RowBuf& t : tab) need += (size_t)t.S * t.C;
   *pos_out = pos;

@@ -1,7 +1,8 @@
 """Host mirror of the reference's Mimi codec surface for the DECODE path (mlx_audio/codec/models/mimi/mimi.py): `mimi_202407`,
 `Mimi(cfg)`, `Mimi.decode(codes)`, `.sample_rate`, `.frame_rate`.  The arithmetic runs in libkokoro_hip.so (kk_mimi_*, csrc/kk_mimi.hip);
 PyTorch allocates device memory and provides the stream.  `Mimi.encode` (mimi.py:138-145) and the streaming `*_step` entry points run on
-the fp32 kernels; `Mimi.row_decoder` is the streaming decoder with one position per row (for a continuously batched generator)."""
+the fp32 kernels; `Mimi.row_decoder` is the streaming decoder with one position per row (for a continuously batched generator) and
+`Mimi.row_encoder` the streaming encoder of the same kind (for microphones that start and stop on their own)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -238,6 +239,14 @@ class Mimi:
             raise KokoroHipError("Mimi.row_decoder: load_weights first")
         return MimiRowDecoder(self, max_batch, max_frames, max_chunk)
 
+    def row_encoder(self, max_batch: int, max_frames: int = 2048, max_chunk: int = 1) -> "MimiRowEncoder":
+        """A streaming ENCODER whose rows each have their own position and lifetime (kk_mimi_stream_create_rows_encoder).  It owns its
+        stream and workspace; the "enc" slot of encode_step is not involved.  Its codes are streaming-encoder codes (those of `encode_step`),
+        not those of `encode(clip)`, whose transformer sees the whole clip without a mask."""
+        if not self._final:
+            raise KokoroHipError("Mimi.row_encoder: load_weights first")
+        return MimiRowEncoder(self, max_batch, max_frames, max_chunk)
+
     def reset_stream(self) -> None:
         """Mimi.reset_state (mimi.py:131-137): both directions start over."""
         for st in self._streams.values():
@@ -285,13 +294,15 @@ class MimiRowDecoder:
     for all `max_batch` rows; only rows with active[b] advance, the others keep their state, cache and position bit for bit.  An active
     row's pcm equals, bit for bit, a batch-1 `Mimi.decode_step` stream fed the same codes in the same step sizes."""
 
+    _CREATE = "kk_mimi_stream_create_rows"
+
     def __init__(self, mimi: Mimi, max_batch: int, max_frames: int, max_chunk: int):
         self._mimi, self.lib, self.device = mimi, mimi.lib, mimi.device  # (keeps the codec alive)
         self.max_batch, self.max_frames, self.max_chunk = int(max_batch), int(max_frames), int(max_chunk)
         self._h = None
         with torch.cuda.device(self.device):
             h = C.c_void_p()
-            check(self.lib.kk_mimi_stream_create_rows(mimi._h, self.max_batch, self.max_frames, self.max_chunk, C.byref(h)), "kk_mimi_stream_create_rows")
+            check(getattr(self.lib, self._CREATE)(mimi._h, self.max_batch, self.max_frames, self.max_chunk, C.byref(h)), self._CREATE)
             self._h = h
             need = int(self.lib.kk_mimi_stream_workspace_bytes(h, self.max_batch))
             if need == 0:
@@ -367,3 +378,34 @@ class MimiRowDecoder:
             self.close()
         except Exception:
             pass
+
+
+class MimiRowEncoder(MimiRowDecoder):
+    """`Mimi.row_encoder(...)`: encode_step for a batch whose rows start, pause and end on their own -- `reset_row`, `row_frames`,
+    `set_context`, `snapshot` and `close` are the row decoder's.  `step(pcm, active)` carries F frames for all `max_batch` rows; only rows
+    with active[b] advance, the others keep their state, cache and position bit for bit.  An active row's codes equal, as integers, a fresh
+    batch-1 `Mimi.encode_step` stream fed the same pcm in the same step sizes, wherever the row started and whatever the other rows do: the
+    resampler's 'edge' padding of a first step is applied per row.  These are streaming codes, not those of `Mimi.encode(clip)`."""
+
+    _CREATE = "kk_mimi_stream_create_rows_encoder"
+
+    def step(self, pcm, active) -> torch.Tensor:
+        """pcm [max_batch, 1, F * samples_per_frame] (1 <= F <= max_chunk), active [max_batch] (host booleans) -> codes [max_batch, nq, F]
+        int32.  Entries of inactive rows may hold anything, NaN and inf included; their codes mean nothing.  A row that would pass
+        max_frames, a bad F or a bad shape is refused before anything is launched."""
+        h = self._handle()
+        pcm = torch.as_tensor(pcm).to(device=self.device, dtype=torch.float32)
+        if pcm.ndim != 3 or pcm.shape[0] != self.max_batch or pcm.shape[1] != 1 or pcm.shape[2] < self.spf or pcm.shape[2] % self.spf:
+            raise ValueError(f"pcm must be [{self.max_batch}, 1, F * {self.spf}] with F >= 1, got {tuple(pcm.shape)}")
+        act = np.ascontiguousarray(np.asarray(active).astype(bool).astype(np.int32))
+        if act.shape != (self.max_batch,):
+            raise ValueError(f"active must hold {self.max_batch} flags, got shape {act.shape}")
+        F = int(pcm.shape[2]) // self.spf
+        pcm = pcm.reshape(self.max_batch, F * self.spf).contiguous()
+        with torch.cuda.device(self.device):
+            codes = torch.empty((self.max_batch, self._mimi.cfg.nq, F), dtype=torch.int32, device=self.device)
+            self._mimi._last_B = self.max_batch
+            check(self.lib.kk_mimi_encode_step_rows(h, self._stream(), F, C.c_void_p(pcm.data_ptr()), act.ctypes.data_as(C.c_void_p),
+                                                    C.c_void_p(self._ws.data_ptr()), self._ws.numel(), C.c_void_p(codes.data_ptr())),
+                  "kk_mimi_encode_step_rows")
+        return codes

@@ -231,7 +231,9 @@ class Model:
     def encode_audios(self, audios: Sequence[np.ndarray]) -> List[np.ndarray]:
         """Mimi codes (K, T) of several clips; clips of equal length go through ONE `Mimi.encode` call (an addition: the reference encodes
         one clip per call, sesame.py:500-510; a batch item's codes do not depend on its neighbours).  Clips of different lengths are not
-        padded into one call: the encoder transformer sees the whole clip (no mask), so padding would change the codes."""
+        padded into one call: the encoder transformer sees the whole clip (no mask), so padding would change the codes.  For the same
+        reason these codes are not those a `CSMBatcher` listener produces for the same clip: a listener runs the STREAMING encoder
+        (`Mimi.encode_step`: causal, in fixed steps), whose codes `hear(segment, codes=...)` takes as they are."""
         if self._audio_tokenizer is None:
             raise ValueError("reference audio needs the Mimi codec: pass mimi= or config['mimi_path']")
         out: List[Optional[np.ndarray]] = [None] * len(audios)
@@ -532,7 +534,9 @@ class Model:
     def serve(self, **kw):
         """Continuous batching (csm_serve.CSMBatcher): requests enter and leave one running batch on this model's weights; every stream's
         result equals its own `generate_batch([prompt])` run.  Keyword arguments are CSMBatcher's; `overlap_admission=True` (with
-        `prefill_lanes=N`) prefills requests on a side stream while the batch keeps stepping."""
+        `prefill_lanes=N`) prefills requests on a side stream while the batch keeps stepping; `listen_rows=K` lets up to K
+        callers feed microphone audio (`listen()` / `session.listen()`), tokenised as it arrives by the codec's row-mode streaming encoder
+        (DESIGN 8d-9).  Those are streaming-encoder codes, not the whole-clip codes of `encode_audios`."""
         from .csm_serve import CSMBatcher
 
         return CSMBatcher(self, **kw)

@@ -27,7 +27,12 @@ while a prefill was in flight beside its time while none was.  Written to profil
 limit -- what happens to a stream whose listener has gone when nothing can stop it -- / a seeded FRACTION of the requests interrupted
 (`CSMAudioStream.interrupt(played_frames=)`) once a seeded number of their chunks has come out / left to run again; per run finished requests per
 second, the mean submit -> first audio of the requests that were queued behind a full batch, and the occupancy.  Written to
-profiles/csm_serve_interrupt_bench.json."""
+profiles/csm_serve_interrupt_bench.json.
+--listen K: instead, the mixed workload (with the codec's encoder, synthetic mimi_202407 weights) with K session listeners that are each fed a 5 s
+clip in 80 ms slices, one slice per scheduling round, while the requests run, against the same workload with `listen_rows=0`: finished requests
+per second of both (untimed rounds), the scheduling round's time with and without a listen round in it (a second run, one sync around each
+round), and the time from `end()` to its result against `sess.hear(segment)` with the whole-clip `Mimi.encode`.  Written to
+profiles/csm_serve_listen_bench.json."""
 import argparse
 import json
 import os
@@ -59,19 +64,21 @@ ap.add_argument("--sessions", type=int, default=0, help="dialogues run as sessio
 ap.add_argument("--turns", type=int, default=4)
 ap.add_argument("--overlap", action="store_true", help="continuous batching with admissions prefilled on a side stream against plain continuous batching")
 ap.add_argument("--lanes", type=int, default=1, help="prefill lanes of --overlap")
+ap.add_argument("--listen", type=int, default=0, help="listeners fed a 5 s clip in 80 ms slices beside the mixed workload, against none")
+ap.add_argument("--listen-chunk", type=int, default=6, help="listen_chunk_frames of --listen")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 if a.out is None:
-    name = "csm_serve_overlap_bench.json" if a.overlap else "csm_serve_session_bench.json" if a.sessions else "csm_serve_interrupt_bench.json" if a.abandon else "csm_serve_stream_bench.json" if a.stream_chunk else "csm_serve_prefix_bench.json" if a.prefix else "csm_serve_bench.json"
+    name = "csm_serve_listen_bench.json" if a.listen else "csm_serve_overlap_bench.json" if a.overlap else "csm_serve_session_bench.json" if a.sessions else "csm_serve_interrupt_bench.json" if a.abandon else "csm_serve_stream_bench.json" if a.stream_chunk else "csm_serve_prefix_bench.json" if a.prefix else "csm_serve_bench.json"
     a.out = os.path.join(ROOT, "profiles", name)
 
 cfg = dict(P.csm_config(), max_seq_len=a.max_seq_len)
 mimi = None
-if a.stream_chunk:
+if a.stream_chunk or a.listen:
     from mlx_audio_amd.mimi import Mimi, MimiConfig
 
     mcfg = P.mimi_config(cfg["audio_num_codebooks"])
-    mimi = Mimi(MimiConfig.from_dict(mcfg), P.mimi_synth_checkpoint(mcfg, 0))
+    mimi = Mimi(MimiConfig.from_dict(mcfg), P.mimi_synth_checkpoint(mcfg, 0, encode=True) if a.listen else P.mimi_synth_checkpoint(mcfg, 0))
 loop = Model(cfg, mimi=mimi, weights=P.csm_synth_checkpoint(cfg, 0), weight_dtype=a.weights)
 n, B = cfg["audio_num_codebooks"], a.batch
 rng = np.random.default_rng(a.seed)
@@ -155,6 +162,87 @@ def bench_overlap():
     plain = [res["continuous_first"]["xrt"], res["continuous_last"]["xrt"]]
     res["value"] = res["overlapped"]["xrt"] / (0.5 * sum(plain))
     res["value_is"] = "overlapped / continuous audio-sec/sec (continuous: mean of the two runs; they differ by %.3f xRT)" % abs(plain[0] - plain[1])
+    return res
+
+
+def bench_listen():
+    from mlx_audio_amd.sesame import Segment
+
+    K, spf = a.listen, 1920
+    clips = [(0.3 * rng.standard_normal(5 * 24000)).astype(np.float32) for _ in range(K)]
+    heard = rng.integers(0, cfg["text_vocab_size"], 12).tolist()
+
+    def run(k, timed):
+        """The workload beside k listeners; timed: one sync around every scheduling round (its time booked by whether a listen round ran)."""
+        bat = loop.serve(max_batch=B, rng="device", sampler=sampler, seed=a.seed, stop_on_eos=False, decode=False, listen_rows=k,
+                         listen_chunk_frames=a.listen_chunk)
+        ls = [bat.session().listen(1) for _ in range(k)]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        futs = [bat.submit(None, None, prompt=prompts[i], max_audio_length_ms=80 * flen[i]) for i in range(a.requests)]
+        book = {True: [0, 0.0], False: [0, 0.0]}
+        fed, ends, t_end, lat = 0, [], None, []
+        while True:
+            if k and fed < clips[0].shape[0]:
+                for lis, c in zip(ls, clips):
+                    lis.feed(c[fed : fed + spf])
+                fed += spf
+                if fed >= clips[0].shape[0]:  # the speaker stops: the transcript arrives with the end
+                    t_end = time.perf_counter()
+                    ends = [lis.end(heard) for lis in ls]
+            before = (bat.stats["frames"], bat.stats.get("listen_rounds", 0))
+            if timed:
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+            more = bat.step()
+            if timed:
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t
+                if bat.stats["frames"] > before[0]:  # (rounds that ran a frame step)
+                    b = book[bat.stats.get("listen_rounds", 0) > before[1]]
+                    b[0], b[1] = b[0] + 1, b[1] + dt
+            for f in [f for f in ends if f.done()]:
+                ends.remove(f)
+                lat.append(time.perf_counter() - t_end)
+            if not more and not bat._queue and not ends and (not k or fed >= clips[0].shape[0]):
+                break
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        assert [f.result(timeout=0).frames for f in futs] == flen
+        st = dict(bat.stats)
+        bat.close()
+        r = {"wall_s": wall, "requests_per_s": a.requests / wall, "frame_steps": st["frames"], "listen_rounds": st.get("listen_rounds", 0),
+             "listen_frames": st.get("listen_frames", 0)}
+        if k:
+            r["end_to_result_ms"] = {"mean": 1e3 * float(np.mean(lat)), "max": 1e3 * float(np.max(lat))}
+        if timed:
+            r["round_ms"] = {"with_listen_round": 1e3 * book[True][1] / max(1, book[True][0]), "rounds_with": book[True][0],
+                             "without_listen_round": 1e3 * book[False][1] / max(1, book[False][0]), "rounds_without": book[False][0]}
+        return r
+
+    def hear_ms():
+        bat = loop.serve(max_batch=B, rng="device", sampler=sampler, seed=a.seed, stop_on_eos=False, decode=False)
+        out = []
+        for c in clips + clips[:1]:
+            sess = bat.session()
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            sess.hear(Segment(speaker=1, text=heard, audio=c))  # whole-clip Mimi.encode on the caller's thread
+            out.append(1e3 * (time.perf_counter() - t))
+        bat.close()
+        return out[1:]  # (the first call sizes the workspace)
+
+    run(0, False), run(K, False)  # warm-up: kernel loading, workspaces, graph capture
+    res = {"metric": "CSM-1B serving with live listeners (row-mode streaming Mimi encoder) vs without, " + a.weights, "requests": a.requests, "batch": B,
+           "listeners": K, "listen_chunk_frames": a.listen_chunk, "clip_seconds": 5.0, "slice_ms": 80, "order": ["plain_first", "listening", "plain_last"],
+           "data": "synthetic (random-init CSM-1B and mimi_202407 weights, random prompts and clips, imposed stream lengths, device uniforms)"}
+    res["plain_first"], res["listening"], res["plain_last"] = run(0, False), run(K, False), run(0, False)
+    res["listening_timed"], res["plain_timed"] = run(K, True), run(0, True)
+    h = hear_ms()
+    res["hear_whole_clip_ms"] = {"mean": float(np.mean(h)), "max": float(np.max(h))}
+    plain = [res["plain_first"]["requests_per_s"], res["plain_last"]["requests_per_s"]]
+    res["value"] = res["listening"]["requests_per_s"] / (0.5 * sum(plain))
+    res["value_is"] = "requests/s with listeners / without (without: mean of the two runs; they differ by %.3f)" % abs(plain[0] - plain[1])
     return res
 
 
@@ -378,6 +466,15 @@ if a.stream_chunk:
     if a.abandon and not (0.0 < a.abandon <= 1.0 and a.stream_chunk < min(LENGTHS)):
         sys.exit(f"--abandon must be in (0, 1] and needs --stream-chunk below {min(LENGTHS)}")
     out = bench_abandon() if a.abandon else bench_stream()
+    print(json.dumps(out))
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    sys.exit(0)
+
+if a.listen:
+    out = bench_listen()
     print(json.dumps(out))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:

@@ -1,6 +1,8 @@
 """Mimi.decode throughput (CSM row C4): B items x Nf frames of random codes -> pcm; audio-seconds per wall-second, plus the CPU
 oracle on one item.  python tools/bench_mimi.py [--batch 8] [--frames 125] [--steps 10]
---stream: the frame-by-frame path instead (Mimi.decode_step, kk_mimi_decode_step): ms per one-frame step of the whole batch."""
+--stream: the frame-by-frame path instead (Mimi.decode_step, kk_mimi_decode_step): ms per one-frame step of the whole batch.
+--stream --rows-encode: the row-mode streaming ENCODER (Mimi.row_encoder, kk_mimi_encode_step_rows) at 1, 4 and 8 rows, F = 1 and 6 frames per
+step, beside Mimi.encode_step at the same B and F: ms per step, one JSON line."""
 import argparse
 import json
 import os
@@ -22,8 +24,42 @@ ap.add_argument("--steps", type=int, default=10)
 ap.add_argument("--no-cpu-baseline", action="store_true")
 ap.add_argument("--dtype", default="bfloat16", choices=["float32", "bfloat16"])
 ap.add_argument("--stream", action="store_true")
+ap.add_argument("--rows-encode", action="store_true")
 a = ap.parse_args()
 cfg = P.mimi_config(32)
+if a.stream and a.rows_encode:
+    model = Mimi(mimi_202407(32), P.mimi_synth_checkpoint(cfg, 0, encode=True), compute_dtype="float32")
+    spf, reps, out = 1920, max(2, a.steps), []
+    g = np.random.default_rng(0)
+
+    def timed(fn, reset):
+        """ms per call over `reps` calls of a stream that was warmed by one call and reset"""
+        fn()
+        reset()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps, (time.perf_counter() - t0) / reps * 1e3
+
+    for B in (1, 4, 8):
+        for F in (1, 6):
+            pcm = torch.tensor((0.3 * g.standard_normal((B, 1, F * spf))).astype(np.float32), device="cuda")
+            enc = model.row_encoder(B, max_frames=F * (reps + 2), max_chunk=F)
+            active = [True] * B
+            rows = timed(lambda: enc.step(pcm, active), lambda: [enc.reset_row(r) for r in range(B)])
+            enc.close()
+            model.close_stream()
+            plain = timed(lambda: model.encode_step(pcm, max_frames=F * (reps + 2)), model.reset_stream)
+            out.append({"rows": B, "frames_per_step": F, "rows_ms_gpu": rows[0], "rows_ms_wall": rows[1], "encode_step_ms_gpu": plain[0],
+                        "encode_step_ms_wall": plain[1]})
+    print(json.dumps({"metric": "ms per streaming encode step, Mimi.row_encoder.step beside Mimi.encode_step, mimi_202407 fp32", "steps": reps,
+                      "cases": out}))
+    sys.exit(0)
 w = P.mimi_synth_checkpoint(cfg, 0)
 model = Mimi(mimi_202407(32), w, compute_dtype=a.dtype)
 codes = torch.tensor(np.random.default_rng(0).integers(0, 2048, (a.batch, 32, a.frames)), device="cuda", dtype=torch.int32)
