@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 9   /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 10  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -40,7 +40,9 @@ extern "C" {
                             7: a prefix captured from a live cache row (kk_csm_prefix_capture);
                             8: a finished admission moved between two generators' cache rows (kk_csm_admit_transfer);
                             9: row-mode streaming Mimi ENCODE (kk_mimi_stream_create_rows_encoder, kk_mimi_encode_step_rows; kk_mimi_stream_reset_row,
-                               kk_mimi_stream_row_frames, kk_mimi_stream_set_context and kk_mimi_stream_row_snapshot take either direction) */
+                               kk_mimi_stream_row_frames, kk_mimi_stream_set_context and kk_mimi_stream_row_snapshot take either direction);
+                            10: row-mode polyphase resampler (kk_resampler_create, kk_resampler_destroy, kk_resampler_set_row, kk_resampler_step,
+                               kk_resampler_block_outputs, kk_op_resample) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -317,6 +319,41 @@ int kk_mimi_encode_step_rows(kk_mimi_stream* s, void* stream, int F, const float
 /* intermediates of the last decode / encode (tests): "quantized", "upsampled", "transformer", "layer0".."layer3" (decode), "seanet", "transformer", "downsampled" (encode); [B][rows][channels] fp32 */
 int kk_mimi_debug_info(kk_mimi* m, const char* name, int64_t* rows, int64_t* channels);
 int kk_mimi_debug_fetch(kk_mimi* m, void* stream, const char* name, float* dst);
+
+/* =====================================================================================================================
+ * Row-mode polyphase FIR resampler (ABI minor 10): the sample-rate edge of CSM serving.  The reference resamples whole clips
+ * with a Fourier scipy.signal.resample (sesame.py load_audio); a stream fed in arbitrary slices needs a causal filter whose bits do not
+ * depend on the slicing.  For a row with ratio L / M (destination / source rate over their gcd), half = 10 max(L, M) and the 2 half + 1 taps
+ *   h = firwin(2 half + 1, 1 / max(L, M), window = ("kaiser", 5.0)) L        (designed by the caller: mlx-audio_amd/resample.py design)
+ * output n of a clip x[0..N) is
+ *   y[n] = sum_j h[n M + half - j L] x[j],  x = 0 outside [0, N),  0 <= n < out_len(N) = ceil(N L / M)
+ * which is scipy.signal.resample_poly(x, L, M) with its defaults.  While a stream is open and N samples were fed, the outputs below
+ * ready(N) = max(0, (N L - 1 - half) / M + 1) (floor) are final; a flush emits the rest up to out_len(N) with zeros behind the clip.
+ * Each output is ONE fmaf chain from 0.0f over its phase's T = ceil((2 half + 1) / L) taps in ascending input order, zeros multiplied like
+ * samples, so an output's bits depend on its index and the clip alone: any slicing of the steps, any row, any neighbours give the same bits.
+ *   kk_resampler_create: max_rows <= 64 rows, at most max_in_per_step new samples per row and step.
+ *   kk_resampler_set_row: a new stream starts in `row` with zero history and zero counts.  max(L, M) <= 320.  taps: HOST fp32, phase-major
+ *     [L][T], taps[p][t] = h[p + t L], zero where p + t L > 2 half; copied before the call returns.  Enqueues two copies and a memset.
+ *   kk_resampler_step: x [max_rows][ldx] and y [max_rows][ldy] on the device (x 16-byte aligned, ldx % 4 == 0); n_in, flush and n_out are HOST
+ *     arrays [max_rows].  A row with n_in == 0 and flush == 0 sits out: nothing of it is read (its x entries may hold NaN), nothing of it
+ *     changes, n_out = 0.  Any other row consumes x[row][0 .. n_in) and writes its next n_out = ready(N) - emitted outputs (flush:
+ *     out_len(N) - emitted) to y[row][0 .. n_out).  n_out is host integer arithmetic on a mirror of the device counts: no step synchronises.
+ *     One launch for all rows; the carried state (the last T inputs, inputs consumed, outputs emitted) stays on the device.
+ *   kk_resampler_block_outputs: the outputs one workgroup owns (tests place their edge lengths around it).
+ *   kk_op_resample: a whole clip, stateless: x [N] and y [out_len(N)] on the device (x 16-byte aligned), taps on the HOST.  A one-row
+ *     resampler is created, stepped once with flush and destroyed; synchronises `stream`.
+ * All work is enqueued on the `stream` of the call: the caller passes the stream of the consumer (or producer) of y, which orders the two.
+ * Refused on the host before any launch, with nothing changed: a row out of range, max(L, M) > 320, a T that does not fit L / M, n_in < 0,
+ * n_in > max_in_per_step or > ldx, n_out > ldy, a row without a ratio, a step of a row after its flush, a misaligned x.
+ * ===================================================================================================================== */
+typedef struct kk_resampler kk_resampler;
+int kk_resampler_create(int max_rows, int max_in_per_step, kk_resampler** out);
+void kk_resampler_destroy(kk_resampler* r);
+int kk_resampler_set_row(kk_resampler* r, void* stream, int row, int L, int M, const float* taps, int T);
+int kk_resampler_step(kk_resampler* r, void* stream, const float* x, long long ldx, const int32_t* n_in, const int32_t* flush, float* y,
+                      long long ldy, int32_t* n_out);
+int kk_resampler_block_outputs(void);
+int kk_op_resample(void* stream, const float* x, int N, int L, int M, const float* taps, int T, float* y);
 
 /* =====================================================================================================================
  * CSM-1B frame generator (rows C1-C3): SesameModel.generate_frame, mlx_audio/tts/models/sesame/sesame.py:349-395, with the

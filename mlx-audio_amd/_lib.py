@@ -173,6 +173,12 @@ SIGNATURES = {
     "kk_mimi_encode_frames": (_i, [_vp, _i]),
     "kk_mimi_encode_workspace_bytes": (_sz, [_vp, _i, _i]),
     "kk_mimi_encode": (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "kk_resampler_create": (_i, [_i, _i, C.POINTER(_vp)]),
+    "kk_resampler_destroy": (None, [_vp]),
+    "kk_resampler_set_row": (_i, [_vp, _vp, _i, _i, _i, _vp, _i]),
+    "kk_resampler_step": (_i, [_vp, _vp, _vp, C.c_longlong, _vp, _vp, _vp, C.c_longlong, _vp]),
+    "kk_resampler_block_outputs": (_i, []),
+    "kk_op_resample": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "kk_mimi_debug_info": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "kk_mimi_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
     "kk_debug_set_op_wfrag": (None, [_vp]),
@@ -219,7 +225,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 9:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 10:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

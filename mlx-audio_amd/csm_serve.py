@@ -54,7 +54,14 @@ the scheduler tokenises it as it arrives in a row-mode streaming ENCODER (`Mimi.
 the cache rows).  The steps of a listener's stream are fixed by its length alone, [M] * (T // M) + [T % M] with M = listen_chunk_frames, so its
 codes never depend on timing or slicing: they equal a fresh batch-1 `Mimi.encode_step` stream over its zero-padded pcm in those steps.  These
 are streaming-encoder codes, NOT those of `Mimi.encode(clip)` (whose transformer sees the whole clip without a mask).  `end(text)` resolves
-with a `ListenResult`; for a session's listener the turn has entered the history by then exactly as `hear(Segment(...), codes=codes)` does."""
+with a `ListenResult`; for a session's listener the turn has entered the history by then exactly as `hear(Segment(...), codes=codes)` does.
+
+Other sample rates: `listen(sample_rate=R)`, `submit(..., sample_rate=R)` / `submit_stream(..., sample_rate=R)`.  A listener is then
+fed at R: the scheduler uploads each row's new samples once per round, resamples them into a per-row device buffer at the model's rate
+(`resample.RowResampler`: one launch for all listeners, a position per row) and encodes from that buffer; its codes are those of a listener fed
+`resample(clip, R, model rate)`, whatever the slicing.  A request's audio leaves at R: every chunk passes through the cache row's resampler row, the
+last one flushes, and the chunks concatenate, bit for bit, to `resample(a, model rate, R)` of the audio `a` the request yields without a rate.
+Without a rate nothing of this exists: no resampler is made."""
 from __future__ import annotations
 
 import queue
@@ -65,8 +72,12 @@ from concurrent.futures import CancelledError, Future, InvalidStateError
 from dataclasses import dataclass, field
 from typing import Deque, Dict, List, Optional, Sequence
 
+import weakref
+
 import numpy as np
 import torch
+
+from . import resample as RS
 
 
 @dataclass
@@ -84,7 +95,10 @@ class StreamResult:
 
 @dataclass
 class AudioChunk:
-    """One piece of a streaming request's waveform: stream-local frames [first_frame, first_frame + frames)."""
+    """One piece of a streaming request's waveform: stream-local frames [first_frame, first_frame + frames).  A request made with
+    `sample_rate=R` gets its audio at R: a chunk then holds the resampler's finished outputs for the samples up to its frames (about ten samples
+    of the slower rate lag behind), the final chunk the rest.  The chunks add up to `StreamResult.audio` unless an `interrupt` cut the stream
+    inside a chunk it had already been sent: then the result is the resample of the kept audio and the chunks sent are not a prefix of it."""
     audio: torch.Tensor  # [samples]
     first_frame: int
     frames: int
@@ -98,6 +112,7 @@ class ListenResult:
     frames: int          # T = ceil(samples / samples per frame): a partial last frame is zero-padded
     samples: int         # samples fed
     steps: List[int]     # the encoder steps of this stream: [M] * (T // M) + [T % M]
+    sample_rate: int = 0  # the rate the samples were fed at; with `listen(sample_rate=R)` T = ceil(out_len(samples) / samples per frame)
 
 
 class CSMListener:
@@ -105,10 +120,18 @@ class CSMListener:
     has been tokenised so far, `end(text)` for the `Future[ListenResult]`, `cancel()` to drop it.  It holds one row of the batcher's row-mode
     streaming encoder from `listen` until the result (or `cancel`)."""
 
-    def __init__(self, batcher: "CSMBatcher", row: int, speaker: int, session=None):
+    def __init__(self, batcher: "CSMBatcher", row: int, speaker: int, session=None, sample_rate: Optional[int] = None):
         self.batcher, self.row, self.speaker, self.session = batcher, int(row), int(speaker), session
         self.spf = int(batcher.engine.samples_per_frame)
-        self._pcm = np.zeros(batcher.listen_max_frames * self.spf, np.float32)  # (zeros behind `samples`: the padding of a partial last frame)
+        self.rate = sample_rate               # None: fed at the model's rate; else the scheduler resamples what is fed (DESIGN 8d-10)
+        cap = batcher.listen_max_frames * self.spf
+        if self.rate is not None:             # the most samples at `rate` whose out_len fits the row: N L <= cap M
+            L, M = RS.ratio(self.rate, batcher.engine.sample_rate)
+            cap = cap * M // L
+        self._pcm = np.zeros(cap, np.float32)  # (zeros behind `samples`: the padding of a partial last frame)
+        self._up = 0                          # a rate listener: samples handed to the resampler, ...
+        self._n24 = 0                         # ... samples at the model's rate its device buffer holds, ...
+        self._flushed = False                 # ... and whether the resampler row has been flushed (the stream has ended and is whole)
         self.samples = 0                      # fed
         self.frames = 0                       # encoded
         self.steps: List[int] = []
@@ -123,12 +146,20 @@ class CSMListener:
         return self._future is not None
 
     def _total(self) -> int:
-        """Frames the stream holds for the scheduler: whole frames while it is open, ceil once it has ended."""
+        """Frames the stream holds for the scheduler: whole frames while it is open, ceil once it has ended.  A rate listener: of the
+        samples its device buffer holds -- ready(fed) while it is open, out_len(fed) once it has been flushed."""
+        if self.rate is not None:
+            return -(-self._n24 // self.spf) if self._flushed else self._n24 // self.spf
         return -(-self.samples // self.spf) if self.ended else self.samples // self.spf
 
+    def _unresampled(self) -> bool:
+        """Under the lock: the scheduler's next round has samples of this listener to resample, or its flush."""
+        return self.rate is not None and (self._up < self.samples or (self.ended and not self._flushed))
+
     def feed(self, pcm) -> None:
-        """Mono float32 at the model's sample rate, any number of samples.  Host work only: the samples join a buffer under the batcher's
-        lock and an idle scheduler is woken.  ValueError, with nothing changed, when the total would pass `listen_max_frames`."""
+        """Mono float32 at the listener's sample rate (the model's, or the `sample_rate` it was made with), any number of samples.  Host
+        work only: the samples join a buffer under the batcher's lock and an idle scheduler is woken.  ValueError, with nothing changed, when
+        the total -- at the model's rate: out_len of it -- would pass `listen_max_frames`."""
         a = np.asarray(pcm, np.float32).reshape(-1)
         b = self.batcher
         with b._lock:
@@ -259,6 +290,9 @@ class _Stream:
     admit_args: Optional[tuple] = None  # (sampler, seed) of its admission: what `set_row_sampler` takes at the commit
     cut: Optional[int] = None       # interrupt: the frames that were heard; the next poll ends the stream with at most that many
     decodable: int = 0              # interrupt of a streaming request: the frames that poll confirmed before the cut (what the codec may be fed)
+    rate: Optional[int] = None      # sample_rate=R: the audio leaves at R (None: the model's rate)
+    rchunks: List[torch.Tensor] = field(default_factory=list)  # a streaming request with a rate: the audio of its chunks at R
+    rflushed: bool = False          # ... and whether its resampler row has been flushed: `rchunks` is then the whole result
     held: bool = True               # the scheduler still has the request (queue, lane or row): a cancelled turn keeps its session busy until it is dropped
 
 
@@ -341,12 +375,12 @@ class CSMSession:
         self.turns.append((int(segment.speaker), segment.text, 0))
         self.pending, self.history = _cat(self.pending, f), _cat(self.history, f)
 
-    def listen(self, speaker: int = 0) -> "CSMListener":
+    def listen(self, speaker: int = 0, sample_rate: Optional[int] = None) -> "CSMListener":
         """`CSMBatcher.listen` for this conversation: another speaker's microphone.  Allowed while the session's own turn is queued or live
         (a barge-in); the turn enters the history at the listener's `end(text)`, which waits for that turn as `hear` does."""
         if self._closed:
             raise ValueError("listen: the session is closed")
-        return self.batcher.listen(speaker=speaker, session=self)
+        return self.batcher.listen(speaker=speaker, session=self, sample_rate=sample_rate)
 
     def submit(self, text, **kw) -> Future:
         kw.setdefault("speaker", self.speaker)
@@ -583,6 +617,10 @@ class ModelEngine:
             raise ValueError("listening needs the Mimi codec: pass mimi= or config['mimi_path']")
         return self.model._audio_tokenizer.row_encoder(max_batch, max_frames, max_chunk)
 
+    def row_resampler(self, max_rows: int, max_in: int):
+        """A row-mode polyphase resampler on the engine's device (resample.RowResampler): set_row, step(x, n_in, flush), close."""
+        return RS.RowResampler(max_rows, max_in, device=self.device)
+
     def heard_segment(self, speaker: int, text, audio):
         """The `Segment` a listened turn enters a session's history as (`CSMSession._hear` -> `segment_frames`)."""
         from .sesame import Segment
@@ -770,6 +808,12 @@ class CSMBatcher:
         if self.listen_rows > 0:
             self.stats.update(listen_rounds=0, listen_frames=0, listen_seconds=0.0)
             self._enc = self.engine.row_encoder(self.listen_rows, self.listen_max_frames, self.listen_chunk)
+        # other sample rates: made by the scheduler when the first listener / request with a rate needs them, never before
+        self._lrs = None                       # the listeners' resampler, one row per encoder row
+        self._heard: Optional[torch.Tensor] = None  # [listen_rows, listen_max_frames * spf]: what the rate listeners' rows hold at the model's rate
+        self._ors = None                       # the streaming requests' resampler, one row per cache row
+        self._crs = None                       # one row for whole clips (a plain request's result): made once, so no allocation per result
+        self._rate_of: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()  # future -> the request's rate (under the lock)
         dev = self.engine.device
         self._prev = torch.zeros((self.max_batch, self.engine.n_cb), dtype=torch.int32, device=dev)
         self._first_eos = torch.full((self.max_batch,), -1, dtype=torch.int64, device=dev)  # stream-local index of the first all-zero frame
@@ -781,11 +825,13 @@ class CSMBatcher:
         the caller's), or segments that the session hears before its first turn.  speaker: the default speaker of the session's own turns."""
         return CSMSession(self, context, speaker)
 
-    def listen(self, speaker: int = 0, session: Optional[CSMSession] = None) -> CSMListener:
+    def listen(self, speaker: int = 0, session: Optional[CSMSession] = None, sample_rate: Optional[int] = None) -> CSMListener:
         """A microphone (`CSMListener`) on a free row of the batcher's streaming encoder; ValueError when all `listen_rows` are taken (or
-        the batcher was made without any).  `session`: what `CSMSession.listen` passes.  Any thread; nothing of the device is touched."""
+        the batcher was made without any).  `session`: what `CSMSession.listen` passes.  `sample_rate`: the rate `feed` takes (None: the
+        model's); ValueError for a rate the resampler does not take.  Any thread; nothing of the device is touched."""
         if self._enc is None:
             raise ValueError("listen needs a batcher made with listen_rows=K")
+        sample_rate = self._rate(sample_rate, inward=True)
         if session is not None and session.batcher is not self:
             raise ValueError("the session belongs to another batcher (CSMBatcher.session on this batcher)")
         with self._lock:
@@ -794,34 +840,94 @@ class CSMBatcher:
             free = [r for r in range(self.listen_rows) if self._listeners[r] is None]
             if not free:
                 raise ValueError(f"all {self.listen_rows} listen rows are taken")
-            lis = self._listeners[free[0]] = CSMListener(self, free[0], speaker, session)
+            lis = self._listeners[free[0]] = CSMListener(self, free[0], speaker, session, sample_rate)
         return lis
+
+    def _rate(self, sample_rate, inward: bool) -> Optional[int]:
+        """A caller's `sample_rate` checked where it is given: None for None and for the model's own rate (today's path), else the rate."""
+        if sample_rate is None or int(sample_rate) == int(self.engine.sample_rate):
+            return None
+        RS.ratio(sample_rate, self.engine.sample_rate) if inward else RS.ratio(self.engine.sample_rate, sample_rate)
+        return int(sample_rate)
 
     # ---- listening (DESIGN 8d-9) -----------------------------------------------------------------------------------------------------------
     def _listen_plan(self):
-        """Under the lock: (rows with >= M frames not yet encoded, ended rows by remainder 0 < r < M, ended rows with nothing left)."""
+        """Under the lock: (rows with >= M frames not yet encoded, ended rows by remainder 0 < r < M, ended rows with nothing left).  A rate
+        listener counts as ended only once its resampler row has been flushed: `end()` may come from another thread between the round's
+        resampler step and this plan, and until the next round's step has taken the rest of its samples and the flush, `_total()` is not
+        its length yet."""
         M = self.listen_chunk
         full, tails, done = [], {}, []
         for lis in self._listeners:
             if lis is None or not lis._open:
                 continue
             left = lis._total() - lis.frames
+            ended = lis.ended and (lis.rate is None or lis._flushed)
             if left >= M:
                 full.append(lis)
-            elif lis.ended and left > 0:
+            elif ended and left > 0:
                 tails.setdefault(left, []).append(lis)
-            elif lis.ended:
+            elif ended:
                 done.append(lis)
         return full, tails, done
 
     def _listen_due(self) -> bool:
         full, tails, done = self._listen_plan()
-        return bool(full or tails or done)
+        return bool(full or tails or done) or any(lis is not None and lis._open and lis._unresampled() for lis in self._listeners)
+
+    LISTEN_IN = 1 << 15  # samples per row and resampler step: a long clip fed at once takes several steps in its round
+
+    def _listen_resample(self) -> bool:
+        """The scheduler's thread, at the top of a listen round: every rate listener's new samples go up once and through ONE
+        resampler step into the row's buffer at the model's rate; a listener that has ended is flushed.  What the round then encodes is
+        counted from those buffers (`CSMListener._total`), so the frames follow from the samples fed and never from the slicing."""
+        with self._lock:
+            work = [(lis, lis.samples, lis.ended) for lis in self._listeners if lis is not None and lis._open and lis._unresampled()]
+        if not work:
+            return False
+        try:
+            if self._lrs is None:
+                self._lrs = self.engine.row_resampler(self.listen_rows, self.LISTEN_IN)
+                self._heard = torch.zeros((self.listen_rows, self.listen_max_frames * work[0][0].spf), dtype=torch.float32, device=self.engine.device)
+        except Exception as e:  # noqa: BLE001
+            for lis, _, _ in work:
+                self._listen_fail(lis, e)
+            return True
+        for item in list(work):
+            lis = item[0]
+            if lis._up == 0 and lis._n24 == 0 and not lis._flushed:  # a new stream starts in the row: zero history, zero counts, zeros behind
+                try:
+                    self._lrs.set_row(lis.row, lis.rate, self.engine.sample_rate)
+                    self._heard[lis.row].zero_()
+                except Exception as e:  # noqa: BLE001  (this row's own failure: the others go on)
+                    work.remove(item)
+                    self._listen_fail(lis, e)
+        try:
+            while True:
+                todo = [(lis, min(self.LISTEN_IN, fed - lis._up), ended) for lis, fed, ended in work if lis._up < fed or (ended and not lis._flushed)]
+                if not todo:
+                    break
+                x = np.zeros((self.listen_rows, max(4, -(-max(k for _, k, _ in todo) // 4) * 4)), np.float32)
+                n_in, flush = [0] * self.listen_rows, [False] * self.listen_rows
+                for lis, k, ended in todo:
+                    x[lis.row, :k] = lis._pcm[lis._up : lis._up + k]
+                    n_in[lis.row], flush[lis.row] = k, ended and lis._up + k == lis.samples
+                y, n_out = self._lrs.step(torch.from_numpy(x).to(self.engine.device), n_in, flush)
+                for lis, k, _ in todo:
+                    n = n_out[lis.row]
+                    self._heard[lis.row, lis._n24 : lis._n24 + n] = y[lis.row, :n]
+                    with self._lock:
+                        lis._up, lis._n24, lis._flushed = lis._up + k, lis._n24 + n, flush[lis.row]
+        except Exception as e:  # noqa: BLE001  (the shared step: it fails the rows that took part in it, as an encode step fails its group)
+            for lis, _, _ in work:
+                self._listen_fail(lis, e)
+        return True
 
     def _listen_round(self) -> bool:
         """The scheduler's thread, once per scheduling round: ONE encode step of M frames for every row that holds M frames not yet encoded,
         then one step per distinct remainder r for the ended rows whose remainder is due, then the ended rows with nothing left resolve.  A
         listener's steps are therefore [M] * (T // M) + [T % M] whatever the slicing and the timing of its `feed` calls."""
+        fresh = self._listen_resample()
         with self._lock:
             full, _, _ = self._listen_plan()
         if full:
@@ -834,7 +940,7 @@ class CSMBatcher:
             _, _, done = self._listen_plan()
         for lis in done:
             self._listen_finish(lis)
-        return bool(full or tails or done)
+        return bool(full or tails or done or fresh)
 
     def _encode_round(self, group: List[CSMListener], F: int) -> None:
         """One step of the row encoder: F frames for the rows of `group`, the other rows inactive.  A failure fails the group's listeners."""
@@ -846,10 +952,17 @@ class CSMBatcher:
                 if lis._fresh:  # a new stream starts in the row: zero carried state, position 0, the edge fill on this step
                     self._enc.reset_row(lis.row)
                     lis._fresh = False
-                pcm[lis.row, 0] = lis._pcm[lis.frames * spf : (lis.frames + F) * spf]  # (zeros behind the fed samples)
+                if lis.rate is None:
+                    pcm[lis.row, 0] = lis._pcm[lis.frames * spf : (lis.frames + F) * spf]  # (zeros behind the fed samples)
                 active[lis.row] = True
+            x = torch.from_numpy(pcm)
+            rated = [lis for lis in group if lis.rate is not None]
+            if rated:  # their samples are on the device already, at the model's rate (zeros behind what the resampler wrote)
+                x = x.to(self.engine.device)
+                for lis in rated:
+                    x[lis.row, 0] = self._heard[lis.row, lis.frames * spf : (lis.frames + F) * spf]
             out: List[torch.Tensor] = []
-            self._timed("listen", lambda: out.append(self._enc.step(torch.from_numpy(pcm), active)))
+            self._timed("listen", lambda: out.append(self._enc.step(x, active)))
             self.stats["listen_rounds"] += 1
             self.stats["listen_frames"] += F * len(group)
             with self._lock:
@@ -887,16 +1000,19 @@ class CSMBatcher:
                 if lis.session._closed:
                     raise ValueError("end: the session is closed")
                 host = codes.cpu().numpy()  # (synchronises: the codes are the session's prompt frames from here on)
-                seg = self.engine.heard_segment(lis.speaker, lis._text, lis._pcm[: lis.samples].copy())
+                audio = lis._pcm[: lis.samples].copy() if lis.rate is None else self._heard[lis.row, : lis._n24].cpu().numpy()
+                seg = self.engine.heard_segment(lis.speaker, lis._text, audio)  # (at the model's rate: what `hear` takes)
                 lis.session._hear(seg, host)  # before the result: whoever waits on it finds the turn in the history
-            fut.set_result(ListenResult(codes=codes, frames=lis.frames, samples=lis.samples, steps=list(lis.steps)))
+            fut.set_result(ListenResult(codes=codes, frames=lis.frames, samples=lis.samples, steps=list(lis.steps),
+                                        sample_rate=lis.rate if lis.rate is not None else int(self.engine.sample_rate)))
         except Exception as e:  # noqa: BLE001
             fut.set_exception(e)
             if lis.session is not None and lis.session._closed:
                 lis.session.close()  # (closed while it was busy with this listener: its prefix is freed now)
 
     def submit(self, context=None, text=None, speaker: int = 0, voice_match: Optional[bool] = None, max_audio_length_ms: float = 90_000,
-               seed: Optional[int] = None, stream_id: Optional[int] = None, prompt=None, prefix=None, sampler=None, session=None) -> Future:
+               seed: Optional[int] = None, stream_id: Optional[int] = None, prompt=None, prefix=None, sampler=None, session=None,
+               sample_rate: Optional[int] = None) -> Future:
         """Queue one request; the future yields a `StreamResult`.  `prompt` (tokens, mask) skips the prompt building.  rng "host": `seed`
         seeds this stream's generator (None: fresh entropy).  rng "device": the batcher's seed is used, `seed` must be None or equal to it.
         ValueError at once for a request that cannot fit the cache; a request that races `close()` gets a failed future.
@@ -911,21 +1027,33 @@ class CSMBatcher:
         pending frames and the text segment of `text` / `speaker`; without a prefix (a first turn without a voice prefix) the whole goes through
         the plain admission.  The length that counts everywhere is session.n + those frames.  When the turn ends its K / V are captured for the
         next one.  `session` excludes `context`, `prompt`, `prefix` and `voice_match=True`; a session with a turn queued or live, a closed one
-        and one of another batcher are refused (ValueError)."""
-        return self._enqueue(False, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix, sampler, session)
+        and one of another batcher are refused (ValueError).
+        `sample_rate` (None: the model's): the result's audio is `resample(a, model rate, sample_rate)` of the audio `a` the request yields
+        without it, and `StreamResult.sample_rate` says so; `interrupt(played_samples=)` then counts samples at that rate.  ValueError for a
+        rate the resampler does not take, and for a batcher made with decode=False."""
+        return self._enqueue(False, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix, sampler, session,
+                             sample_rate)
 
     def submit_stream(self, context=None, text=None, speaker: int = 0, voice_match: Optional[bool] = None, max_audio_length_ms: float = 90_000,
                       seed: Optional[int] = None, stream_id: Optional[int] = None, prompt=None, prefix=None, sampler=None,
-                      session=None) -> CSMAudioStream:
+                      session=None, sample_rate: Optional[int] = None) -> CSMAudioStream:
         """`submit` with the audio delivered while the stream runs: the same arguments and refusals, a `CSMAudioStream` back.  Needs a batcher
-        made with `stream_chunk_frames=N`; the request may not be longer than `stream_max_frames`."""
+        made with `stream_chunk_frames=N`; the request may not be longer than `stream_max_frames`.  With `sample_rate` every chunk passes
+        through the cache row's resampler row and the final chunk flushes it: `AudioChunk.audio` is at that rate, a chunk's `frames` still
+        count codec frames, and the chunks concatenate, bit for bit, to the resampled whole.  That also holds for a stream interrupted at or
+        behind the frames it has been sent (the last chunk, of the frames still due or of 0 frames, carries the flush).  It does NOT hold for
+        one cut inside a chunk it was already sent: the samples behind the cut have left, and the result is the resample of the kept audio."""
         if self._dec is None:
             raise ValueError("submit_stream needs a batcher made with stream_chunk_frames=N")
-        return self._enqueue(True, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix, sampler, session)
+        return self._enqueue(True, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix, sampler, session,
+                             sample_rate)
 
     def _enqueue(self, _streaming: bool, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix, sampler=None,
-                 session=None):
+                 session=None, sample_rate=None):
         max_frames = int(max_audio_length_ms / 80)
+        sample_rate = self._rate(sample_rate, inward=False)
+        if sample_rate is not None and not self.decode:
+            raise ValueError("sample_rate= resamples the decoded audio: the batcher was made with decode=False")
         if sampler is not None:
             if not self.row_samplers:
                 raise ValueError("a per-request sampler needs a batcher made with row_samplers=True; this one samples every stream with its own")
@@ -986,7 +1114,9 @@ class CSMBatcher:
             self._queue.append(_Stream(future=fut, context=context, text=text, speaker=int(speaker),
                                        voice_match=True if voice_match is None else bool(voice_match),
                                        max_frames=max_frames, seed=seed, stream_id=int(stream_id), length=length, t0=time.perf_counter(),
-                                       prompt=prompt, prefix=prefix, audio=audio, sampler=sampler, session=session))
+                                       prompt=prompt, prefix=prefix, audio=audio, sampler=sampler, session=session, rate=sample_rate))
+            if sample_rate is not None:
+                self._rate_of[fut] = sample_rate
             if session is not None:
                 session._stream = self._queue[-1]
             self._wake.notify()
@@ -1016,7 +1146,7 @@ class CSMBatcher:
     def interrupt(self, handle, played_frames: Optional[int] = None, played_samples: Optional[int] = None) -> bool:
         """End the stream now and keep what was heard.  Heard: `played_frames`, or ceil(`played_samples` / samples per frame) -- a frame that was
         partly played counts --, or with neither the frames emitted so far (`submit_stream`) / generated so far (`submit`).  Kept: k = min(heard,
-        the frames generated, the index of the first EOS frame, the request's limit).  Applied at the top of the scheduler's next round, with
+        the frames generated, the index of the first EOS frame, the request's limit).  A request made with `sample_rate=R` counts `played_samples` at R: p R-samples are p * model rate // R of the codec's.  Applied at the top of the scheduler's next round, with
         one poll.  k >= 1: the future resolves with a `StreamResult` of k frames and `interrupted=True`; a plain request decodes its k frames,
         a streaming one gets the chunks up to frame k it has not had yet -- the last with `final=True` -- or, when it has had them all,
         one `AudioChunk` of 0 frames with `final=True`, and its result's audio is what was emitted cut to k frames.  A session's turn is
@@ -1026,6 +1156,10 @@ class CSMBatcher:
             raise ValueError("interrupt takes played_frames or played_samples, not both")
         heard = played_frames
         if played_samples is not None:
+            with self._lock:
+                rate = self._rate_of.get(handle.future if isinstance(handle, CSMAudioStream) else handle)
+            if rate is not None:  # the caller counts what it played at the request's own rate
+                played_samples = int(played_samples) * int(self.engine.sample_rate) // rate
             heard = -(-int(played_samples) // int(self.engine.samples_per_frame))
         if heard is not None and int(heard) < 0:
             raise ValueError("played_frames / played_samples must be >= 0")
@@ -1128,8 +1262,11 @@ class CSMBatcher:
                 if pcm is not None:
                     self.engine.synchronize()
                 for j, s in enumerate(group):
-                    self._resolve(s, StreamResult(audio=pcm[j] if pcm is not None else None, frames=count, codes=codes[j],
-                                                  sample_rate=self.engine.sample_rate, stream_id=s.stream_id, row=s.row,
+                    audio = pcm[j] if pcm is not None else None
+                    if s.rate is not None:
+                        audio = self._resample_clip(audio, s.rate)
+                    self._resolve(s, StreamResult(audio=audio, frames=count, codes=codes[j],
+                                                  sample_rate=s.rate if s.rate is not None else self.engine.sample_rate, stream_id=s.stream_id, row=s.row,
                                                   processing_time_seconds=time.perf_counter() - s.t0, interrupted=s.cut is not None))
             except Exception as e:  # noqa: BLE001
                 for s in group:
@@ -1187,13 +1324,31 @@ class CSMBatcher:
                 _fail(s, AssertionError("No audio generated"))
                 continue
             audio = torch.cat(s.chunks)
-            if s.cut is not None:
-                self.stats["interrupted"] += 1
-                if s.emitted >= s.confirmed:  # it has had every frame that was heard: the iterator ends behind an empty chunk
-                    audio = audio[: s.confirmed * (audio.shape[0] // s.emitted)]
-                    s.audio._q.put(AudioChunk(audio=audio[:0], first_frame=s.confirmed, frames=0, final=True))
+            try:
+                if s.cut is not None:
+                    self.stats["interrupted"] += 1
+                    if s.emitted >= s.confirmed:  # it has had every frame that was heard: the iterator ends behind a chunk of 0 frames
+                        audio = audio[: s.confirmed * (audio.shape[0] // s.emitted)]
+                        tail = audio[:0]
+                        if s.rate is not None and not s.rflushed and s.emitted == s.confirmed:
+                            # the cut is where the emitted chunks end: the row is flushed now and the 0-frame chunk carries the filter's tail
+                            n_in, flush = [0] * self.max_batch, [False] * self.max_batch
+                            flush[s.row] = True
+                            out, n_out = self._ors.step(torch.zeros((self.max_batch, 4), dtype=torch.float32, device=self.engine.device), n_in, flush)
+                            tail = out[s.row, : n_out[s.row]].clone()
+                            s.rchunks.append(tail)
+                            s.rflushed = True
+                        s.audio._q.put(AudioChunk(audio=tail, first_frame=s.confirmed, frames=0, final=True))
+                if s.rate is not None:
+                    # Flushed with its last chunk: the chunks are the whole.  An interrupted stream that was cut INSIDE what it had been sent
+                    # cannot be flushed (its row has consumed samples behind the cut): its result is the resample of the 24 kHz audio that was
+                    # kept, as a plain request's is, and its chunks do not add up to it.
+                    audio = torch.cat(s.rchunks) if s.rflushed else self._resample_clip(audio, s.rate)
+            except Exception as e:  # noqa: BLE001
+                _fail(s, e)
+                continue
             self._resolve(s, StreamResult(audio=audio, frames=s.confirmed, codes=torch.stack(s.codes[: s.confirmed], dim=1),
-                                          sample_rate=self.engine.sample_rate, stream_id=s.stream_id, row=s.row,
+                                          sample_rate=s.rate if s.rate is not None else self.engine.sample_rate, stream_id=s.stream_id, row=s.row,
                                           processing_time_seconds=time.perf_counter() - s.t0, interrupted=s.cut is not None))
 
     def _decode_round(self, group: List[_Stream], F: int, keep: Optional[int] = None) -> None:
@@ -1208,12 +1363,22 @@ class CSMBatcher:
                 codes[s.row] = torch.stack(s.codes[s.emitted : s.emitted + F], dim=1)
                 active[s.row] = True
             pcm = self._dec.step(codes, active)
+            rated = [s for s in group if s.rate is not None]
+            if rated:  # ONE resampler step for the round's rows with a rate: the kept samples in, the final chunk flushes
+                n_in, flush = [0] * self.max_batch, [False] * self.max_batch
+                for s in rated:
+                    n_in[s.row], flush[s.row] = keep * (pcm.shape[-1] // F), s.ended and s.emitted + keep == s.confirmed
+                out, n_out = self._ors.step(pcm[:, 0, :], n_in, flush)
             self.engine.synchronize()
             self.stats["chunk_rounds"] += 1
             for s in group:
                 chunk = AudioChunk(audio=pcm[s.row, 0, : keep * (pcm.shape[-1] // F)].clone(), first_frame=s.emitted, frames=keep,
                                    final=s.ended and s.emitted + keep == s.confirmed)
                 s.chunks.append(chunk.audio)
+                if s.rate is not None:
+                    chunk.audio = out[s.row, : n_out[s.row]].clone()
+                    s.rchunks.append(chunk.audio)
+                    s.rflushed = flush[s.row]
                 s.emitted += keep
                 if s.audio.first_audio_seconds is None:
                     s.audio.first_audio_seconds = time.perf_counter() - s.t0
@@ -1224,6 +1389,23 @@ class CSMBatcher:
                 _fail(s, e)
                 if self._rows[s.row] is s:
                     self._release(s)
+
+    def _resample_clip(self, audio: torch.Tensor, rate: int) -> torch.Tensor:
+        """A whole clip at the model's rate -> `rate`: one step with the flush on a one-row resampler the batcher keeps, on the batch's stream.
+        The same kernel and bits as `resample.resample`, without that call's allocations and its synchronisation."""
+        if self._crs is None:
+            self._crs = self.engine.row_resampler(1, 1 << 30)
+        self._crs.set_row(0, self.engine.sample_rate, rate)
+        y, n = self._crs.step(audio.reshape(1, -1), [int(audio.shape[0])], [True])
+        return y[0, : n[0]].clone()
+
+    def _out_row(self, s: _Stream, row: int) -> None:
+        """A streaming request with a rate is admitted: its resampler row is the cache row, and a new stream starts in it."""
+        if s.rate is None:
+            return
+        if self._ors is None:
+            self._ors = self.engine.row_resampler(self.max_batch, self.chunk * int(self.engine.samples_per_frame))
+        self._ors.set_row(row, self.engine.sample_rate, s.rate)
 
     def _timed(self, what: str, fn) -> None:
         if self.profile:
@@ -1315,6 +1497,7 @@ class CSMBatcher:
                     self.engine.set_row_sampler(row, *s.admit_args)
                 if s.audio is not None:
                     self._dec.reset_row(row)  # the decoder row is the cache row: a new stream starts in it
+                    self._out_row(s, row)
                 if self.profile:
                     self.stats["prefill_seconds"] += self.engine.prefill_seconds(s.prefill)
             except Exception as e:  # noqa: BLE001
@@ -1395,6 +1578,7 @@ class CSMBatcher:
             if s.audio is not None:
                 try:
                     self._dec.reset_row(row)  # the decoder row is the cache row: a new stream starts in it
+                    self._out_row(s, row)
                 except Exception as e:  # noqa: BLE001
                     _fail(s, e)
                     self.engine.park(row)
@@ -1553,6 +1737,9 @@ class CSMBatcher:
             self._dec.close()
         if self._enc is not None:
             self._enc.close()
+        for rs in (self._lrs, self._ors, self._crs):
+            if rs is not None:
+                rs.close()
         if self.overlap:
             self.engine.close_lanes()
 
