@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 10  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 11  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -42,7 +42,9 @@ extern "C" {
                             9: row-mode streaming Mimi ENCODE (kk_mimi_stream_create_rows_encoder, kk_mimi_encode_step_rows; kk_mimi_stream_reset_row,
                                kk_mimi_stream_row_frames, kk_mimi_stream_set_context and kk_mimi_stream_row_snapshot take either direction);
                             10: row-mode polyphase resampler (kk_resampler_create, kk_resampler_destroy, kk_resampler_set_row, kk_resampler_step,
-                               kk_resampler_block_outputs, kk_op_resample) */
+                               kk_resampler_block_outputs, kk_op_resample);
+                            11: PCM wire formats at the resampler's edges and on their own (KK_PCM_*, kk_resampler_set_row_fmt, kk_resampler_step_fmt,
+                               kk_pcm_convert_rows, kk_op_pcm_convert) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -354,6 +356,34 @@ int kk_resampler_step(kk_resampler* r, void* stream, const float* x, long long l
                       long long ldy, int32_t* n_out);
 int kk_resampler_block_outputs(void);
 int kk_op_resample(void* stream, const float* x, int N, int L, int M, const float* taps, int T, float* y);
+
+/* =====================================================================================================================
+ * PCM wire formats (ABI minor 11): what a phone line, a browser microphone and a playback device speak.  A sample is stored as
+ *   KK_PCM_F32    4 bytes, the float itself
+ *   KK_PCM_S16LE  2 bytes, little-endian int16 s:  x = s / 32768 (exact);  s = clamp(rint(x 32768), -32768, 32767), ties to even,
+ *                 +-inf -> full scale, NaN -> 0
+ *   KK_PCM_MULAW  1 byte, G.711 mu-law of s (decodes to +-32124);  KK_PCM_ALAW  1 byte, G.711 A-law of s (decodes to +-32256)
+ * with the integer rules of Python's audioop at width 2 (lin2ulaw, ulaw2lin, lin2alaw, alaw2lin), computed with shifts and a count of
+ * leading zeros, no table.  encode(decode(c)) == c for every int16, every A-law octet and every mu-law octet but 0x7F (negative zero -> 0xFF).
+ *   kk_resampler_set_row_fmt: kk_resampler_set_row with the format the row's new samples are stored as and the format its outputs are stored
+ *     as.  kk_resampler_set_row means f32 for both.
+ *   kk_resampler_step_fmt: kk_resampler_step on BYTE buffers: x [max_rows][ldx_bytes] and y [max_rows][ldy_bytes], both 16-byte aligned with
+ *     pitches that are multiples of 16.  n_in and n_out count SAMPLES of the row's own formats.  Samples are decoded as they are staged (the
+ *     carried history stays fp32) and the outputs are encoded as they are stored: a row's outputs are encode(resample(decode(clip))) bit for
+ *     bit, and an f32 -> f32 row gives the bits kk_resampler_step gives.  kk_resampler_step refuses a row whose formats are not both f32.
+ *   kk_pcm_convert_rows: rows that need no ratio: y[row][i] = encode(decode(x[row][i])), i < n[row], any format to any format, stateless.
+ *     in_fmt, out_fmt and n are HOST arrays [rows], rows <= 64; a row with n = 0 sits out and nothing of it is read.  One launch.
+ *   kk_op_pcm_convert: one row x [n] -> y [n] (both 16-byte aligned), for tools and tests.  Neither entry synchronises.
+ * Refused on the host before any launch, with nothing changed: an unknown format, a misaligned x or y, a pitch that is not a multiple of 16,
+ * a row too short for its n_in, n_out or n in its own sample size.
+ * ===================================================================================================================== */
+enum { KK_PCM_F32 = 0, KK_PCM_S16LE = 1, KK_PCM_MULAW = 2, KK_PCM_ALAW = 3 };
+int kk_resampler_set_row_fmt(kk_resampler* r, void* stream, int row, int L, int M, const float* taps, int T, int in_fmt, int out_fmt);
+int kk_resampler_step_fmt(kk_resampler* r, void* stream, const void* x, long long ldx_bytes, const int32_t* n_in, const int32_t* flush, void* y,
+                          long long ldy_bytes, int32_t* n_out);
+int kk_pcm_convert_rows(void* stream, int rows, const void* x, long long ldx_bytes, const int32_t* in_fmt, void* y, long long ldy_bytes,
+                        const int32_t* out_fmt, const int32_t* n);
+int kk_op_pcm_convert(void* stream, const void* x, int in_fmt, void* y, int out_fmt, int n);
 
 /* =====================================================================================================================
  * CSM-1B frame generator (rows C1-C3): SesameModel.generate_frame, mlx_audio/tts/models/sesame/sesame.py:349-395, with the

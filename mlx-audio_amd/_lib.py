@@ -13,6 +13,7 @@ CSM_WEIGHTS = {0: "f32", 1: "bf16", 2: "q8", 3: "q4"}  # kk_csm_weight_format
 CSM_WEIGHTS_MIXED, CSM_WEIGHTS_DEQUANTIZED = 0x100, 0x200
 NOISE_ZERO, NOISE_INJECTED, NOISE_PHILOX = 0, 1, 2
 ACT_NONE, ACT_LRELU, ACT_GELU, ACT_SNAKE = 0, 1, 2, 3
+KK_PCM_F32, KK_PCM_S16LE, KK_PCM_MULAW, KK_PCM_ALAW = 0, 1, 2, 3
 
 
 class KKConfig(C.Structure):
@@ -179,6 +180,10 @@ SIGNATURES = {
     "kk_resampler_step": (_i, [_vp, _vp, _vp, C.c_longlong, _vp, _vp, _vp, C.c_longlong, _vp]),
     "kk_resampler_block_outputs": (_i, []),
     "kk_op_resample": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
+    "kk_resampler_set_row_fmt": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i]),
+    "kk_resampler_step_fmt": (_i, [_vp, _vp, _vp, C.c_longlong, _vp, _vp, _vp, C.c_longlong, _vp]),
+    "kk_pcm_convert_rows": (_i, [_vp, _i, _vp, C.c_longlong, _vp, _vp, C.c_longlong, _vp, _vp]),
+    "kk_op_pcm_convert": (_i, [_vp, _vp, _i, _vp, _i, _i]),
     "kk_mimi_debug_info": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "kk_mimi_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
     "kk_debug_set_op_wfrag": (None, [_vp]),
@@ -225,7 +230,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 10:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 11:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

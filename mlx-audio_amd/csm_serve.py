@@ -61,7 +61,16 @@ fed at R: the scheduler uploads each row's new samples once per round, resamples
 (`resample.RowResampler`: one launch for all listeners, a position per row) and encodes from that buffer; its codes are those of a listener fed
 `resample(clip, R, model rate)`, whatever the slicing.  A request's audio leaves at R: every chunk passes through the cache row's resampler row, the
 last one flushes, and the chunks concatenate, bit for bit, to `resample(a, model rate, R)` of the audio `a` the request yields without a rate.
-Without a rate nothing of this exists: no resampler is made."""
+Without a rate nothing of this exists: no resampler is made.
+
+PCM formats: `listen(format="mulaw")`, `submit(..., format="s16le")` / `submit_stream(..., format=...)` with or without a rate (DESIGN 8d-11;
+`pcm.FORMATS`: "f32", "s16le", "mulaw", "alaw").  A listener with a format is fed bytes (or an array of the format's dtype), keeps them in
+that format and uploads them once per round; they are decoded inside the resampler step (a listener with a rate) or by one convert launch
+(`pcm.RowConverter`, a listener at the model's rate) into the same per-row device buffer, so its codes are those of an f32 listener fed
+`pcm.decode(the bytes)`.  A request with a format gets `int16` / `uint8` device tensors: the resampler step of its decode round encodes
+them (at the model's rate: one convert launch for the round's rows), and the chunks concatenate, element for element, to `pcm.encode` of the
+audio the request yields without a format.  Counts (`listen_max_frames`, `ListenResult.samples`, `played_samples`) stay in samples.
+Without a format nothing of this exists: no converter is made and every call is the one it was."""
 from __future__ import annotations
 
 import queue
@@ -77,6 +86,7 @@ import weakref
 import numpy as np
 import torch
 
+from . import pcm as PCM
 from . import resample as RS
 
 
@@ -91,6 +101,7 @@ class StreamResult:
     row: int                       # the cache row the stream ran in
     processing_time_seconds: float  # submit -> result
     interrupted: bool = False      # ended by `interrupt`: `frames` is what was kept of it
+    format: str = "f32"            # what `audio` holds (`pcm.FORMATS`): float32, int16 ("s16le") or uint8 ("mulaw", "alaw") samples
 
 
 @dataclass
@@ -103,6 +114,7 @@ class AudioChunk:
     first_frame: int
     frames: int
     final: bool          # the stream's last chunk: `result()` is ready
+    format: str = "f32"  # what `audio` holds (`pcm.FORMATS`): a request made with `format=` gets int16 / uint8 samples
 
 
 @dataclass
@@ -113,6 +125,7 @@ class ListenResult:
     samples: int         # samples fed
     steps: List[int]     # the encoder steps of this stream: [M] * (T // M) + [T % M]
     sample_rate: int = 0  # the rate the samples were fed at; with `listen(sample_rate=R)` T = ceil(out_len(samples) / samples per frame)
+    format: str = "f32"   # the format the samples were fed in (`listen(format=)`); `samples` counts samples, not bytes
 
 
 class CSMListener:
@@ -120,16 +133,18 @@ class CSMListener:
     has been tokenised so far, `end(text)` for the `Future[ListenResult]`, `cancel()` to drop it.  It holds one row of the batcher's row-mode
     streaming encoder from `listen` until the result (or `cancel`)."""
 
-    def __init__(self, batcher: "CSMBatcher", row: int, speaker: int, session=None, sample_rate: Optional[int] = None):
+    def __init__(self, batcher: "CSMBatcher", row: int, speaker: int, session=None, sample_rate: Optional[int] = None, fmt: Optional[str] = None):
         self.batcher, self.row, self.speaker, self.session = batcher, int(row), int(speaker), session
         self.spf = int(batcher.engine.samples_per_frame)
         self.rate = sample_rate               # None: fed at the model's rate; else the scheduler resamples what is fed (DESIGN 8d-10)
+        self.fmt = fmt                        # None: fed float32; else the samples are kept and uploaded in this format (DESIGN 8d-11)
+        self._dev = sample_rate is not None or fmt is not None  # the encoder reads this listener from its device buffer at the model's rate
         cap = batcher.listen_max_frames * self.spf
         if self.rate is not None:             # the most samples at `rate` whose out_len fits the row: N L <= cap M
             L, M = RS.ratio(self.rate, batcher.engine.sample_rate)
             cap = cap * M // L
-        self._pcm = np.zeros(cap, np.float32)  # (zeros behind `samples`: the padding of a partial last frame)
-        self._up = 0                          # a rate listener: samples handed to the resampler, ...
+        self._pcm = np.zeros(cap, PCM.dtype(fmt))  # (f32: zeros behind `samples`, the padding of a partial last frame)
+        self._up = 0                          # a rate or format listener: samples handed to the resampler / converter, ...
         self._n24 = 0                         # ... samples at the model's rate its device buffer holds, ...
         self._flushed = False                 # ... and whether the resampler row has been flushed (the stream has ended and is whole)
         self.samples = 0                      # fed
@@ -148,19 +163,24 @@ class CSMListener:
     def _total(self) -> int:
         """Frames the stream holds for the scheduler: whole frames while it is open, ceil once it has ended.  A rate listener: of the
         samples its device buffer holds -- ready(fed) while it is open, out_len(fed) once it has been flushed."""
-        if self.rate is not None:
+        if self._dev:
             return -(-self._n24 // self.spf) if self._flushed else self._n24 // self.spf
         return -(-self.samples // self.spf) if self.ended else self.samples // self.spf
 
     def _unresampled(self) -> bool:
         """Under the lock: the scheduler's next round has samples of this listener to resample, or its flush."""
-        return self.rate is not None and (self._up < self.samples or (self.ended and not self._flushed))
+        return self._dev and (self._up < self.samples or (self.ended and not self._flushed))
 
     def feed(self, pcm) -> None:
         """Mono float32 at the listener's sample rate (the model's, or the `sample_rate` it was made with), any number of samples.  Host
         work only: the samples join a buffer under the batcher's lock and an idle scheduler is woken.  ValueError, with nothing changed, when
-        the total -- at the model's rate: out_len of it -- would pass `listen_max_frames`."""
-        a = np.asarray(pcm, np.float32).reshape(-1)
+        the total -- at the model's rate: out_len of it -- would pass `listen_max_frames`.
+        A listener made with `format=`: `bytes`, `bytearray`, `memoryview` or a numpy array of the format's dtype, a whole number of samples
+        (an "s16le" feed of an odd number of bytes is a ValueError, nothing changed; no byte is carried to the next feed)."""
+        if self.fmt is not None or isinstance(pcm, (bytes, bytearray, memoryview)):
+            a = PCM.samples(pcm, self.fmt)
+        else:
+            a = np.asarray(pcm, np.float32).reshape(-1)
         b = self.batcher
         with b._lock:
             if b._closed:
@@ -293,6 +313,7 @@ class _Stream:
     rate: Optional[int] = None      # sample_rate=R: the audio leaves at R (None: the model's rate)
     rchunks: List[torch.Tensor] = field(default_factory=list)  # a streaming request with a rate: the audio of its chunks at R
     rflushed: bool = False          # ... and whether its resampler row has been flushed: `rchunks` is then the whole result
+    fmt: Optional[str] = None       # format=: the audio leaves as int16 / uint8 samples (None: float32); `rchunks` then holds the encoded chunks
     held: bool = True               # the scheduler still has the request (queue, lane or row): a cancelled turn keeps its session busy until it is dropped
 
 
@@ -375,12 +396,14 @@ class CSMSession:
         self.turns.append((int(segment.speaker), segment.text, 0))
         self.pending, self.history = _cat(self.pending, f), _cat(self.history, f)
 
-    def listen(self, speaker: int = 0, sample_rate: Optional[int] = None) -> "CSMListener":
+    def listen(self, speaker: int = 0, sample_rate: Optional[int] = None, format: Optional[str] = None) -> "CSMListener":
         """`CSMBatcher.listen` for this conversation: another speaker's microphone.  Allowed while the session's own turn is queued or live
         (a barge-in); the turn enters the history at the listener's `end(text)`, which waits for that turn as `hear` does."""
         if self._closed:
             raise ValueError("listen: the session is closed")
-        return self.batcher.listen(speaker=speaker, session=self, sample_rate=sample_rate)
+        if format is None:
+            return self.batcher.listen(speaker=speaker, session=self, sample_rate=sample_rate)
+        return self.batcher.listen(speaker=speaker, session=self, sample_rate=sample_rate, format=format)
 
     def submit(self, text, **kw) -> Future:
         kw.setdefault("speaker", self.speaker)
@@ -618,8 +641,12 @@ class ModelEngine:
         return self.model._audio_tokenizer.row_encoder(max_batch, max_frames, max_chunk)
 
     def row_resampler(self, max_rows: int, max_in: int):
-        """A row-mode polyphase resampler on the engine's device (resample.RowResampler): set_row, step(x, n_in, flush), close."""
+        """A row-mode polyphase resampler on the engine's device (resample.RowResampler): set_row, step(x, n_in, flush), out_view, close."""
         return RS.RowResampler(max_rows, max_in, device=self.device)
+
+    def pcm_converter(self):
+        """The PCM converter of rows at the model's own rate on the engine's device (pcm.RowConverter): convert(x, in_formats, out_formats, n), close."""
+        return PCM.RowConverter(device=self.device)
 
     def heard_segment(self, speaker: int, text, audio):
         """The `Segment` a listened turn enters a session's history as (`CSMSession._hear` -> `segment_frames`)."""
@@ -814,6 +841,7 @@ class CSMBatcher:
         self._ors = None                       # the streaming requests' resampler, one row per cache row
         self._crs = None                       # one row for whole clips (a plain request's result): made once, so no allocation per result
         self._rate_of: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()  # future -> the request's rate (under the lock)
+        self._cvt = None                       # PCM formats at the model's own rate: one stateless converter, made with the first such row
         dev = self.engine.device
         self._prev = torch.zeros((self.max_batch, self.engine.n_cb), dtype=torch.int32, device=dev)
         self._first_eos = torch.full((self.max_batch,), -1, dtype=torch.int64, device=dev)  # stream-local index of the first all-zero frame
@@ -825,13 +853,16 @@ class CSMBatcher:
         the caller's), or segments that the session hears before its first turn.  speaker: the default speaker of the session's own turns."""
         return CSMSession(self, context, speaker)
 
-    def listen(self, speaker: int = 0, session: Optional[CSMSession] = None, sample_rate: Optional[int] = None) -> CSMListener:
+    def listen(self, speaker: int = 0, session: Optional[CSMSession] = None, sample_rate: Optional[int] = None,
+               format: Optional[str] = None) -> CSMListener:
         """A microphone (`CSMListener`) on a free row of the batcher's streaming encoder; ValueError when all `listen_rows` are taken (or
         the batcher was made without any).  `session`: what `CSMSession.listen` passes.  `sample_rate`: the rate `feed` takes (None: the
-        model's); ValueError for a rate the resampler does not take.  Any thread; nothing of the device is touched."""
+        model's); ValueError for a rate the resampler does not take.  `format` (`pcm.FORMATS`; None or "f32": float32): what `feed` takes --
+        "s16le", "mulaw" or "alaw" bytes; ValueError for another name.  Any thread; nothing of the device is touched."""
         if self._enc is None:
             raise ValueError("listen needs a batcher made with listen_rows=K")
         sample_rate = self._rate(sample_rate, inward=True)
+        fmt = self._format(format)
         if session is not None and session.batcher is not self:
             raise ValueError("the session belongs to another batcher (CSMBatcher.session on this batcher)")
         with self._lock:
@@ -840,8 +871,13 @@ class CSMBatcher:
             free = [r for r in range(self.listen_rows) if self._listeners[r] is None]
             if not free:
                 raise ValueError(f"all {self.listen_rows} listen rows are taken")
-            lis = self._listeners[free[0]] = CSMListener(self, free[0], speaker, session, sample_rate)
+            lis = self._listeners[free[0]] = CSMListener(self, free[0], speaker, session, sample_rate, fmt)
         return lis
+
+    @staticmethod
+    def _format(fmt) -> Optional[str]:
+        """A caller's `format` checked where it is given: None for None and for "f32" (today's path), else the name."""
+        return None if PCM.check(fmt) == "f32" else fmt
 
     def _rate(self, sample_rate, inward: bool) -> Optional[int]:
         """A caller's `sample_rate` checked where it is given: None for None and for the model's own rate (today's path), else the rate."""
@@ -862,7 +898,7 @@ class CSMBatcher:
             if lis is None or not lis._open:
                 continue
             left = lis._total() - lis.frames
-            ended = lis.ended and (lis.rate is None or lis._flushed)
+            ended = lis.ended and (not lis._dev or lis._flushed)
             if left >= M:
                 full.append(lis)
             elif ended and left > 0:
@@ -880,14 +916,19 @@ class CSMBatcher:
     def _listen_resample(self) -> bool:
         """The scheduler's thread, at the top of a listen round: every rate listener's new samples go up once and through ONE
         resampler step into the row's buffer at the model's rate; a listener that has ended is flushed.  What the round then encodes is
-        counted from those buffers (`CSMListener._total`), so the frames follow from the samples fed and never from the slicing."""
+        counted from those buffers (`CSMListener._total`), so the frames follow from the samples fed and never from the slicing.
+        Formats (DESIGN 8d-11): a listener's new samples go up as the bytes it was fed.  With a rate they are decoded in that resampler step;
+        at the model's rate ONE convert launch decodes the round's rows into the same buffers."""
         with self._lock:
             work = [(lis, lis.samples, lis.ended) for lis in self._listeners if lis is not None and lis._open and lis._unresampled()]
         if not work:
             return False
         try:
-            if self._lrs is None:
+            if self._lrs is None and any(lis.rate is not None for lis, _, _ in work):
                 self._lrs = self.engine.row_resampler(self.listen_rows, self.LISTEN_IN)
+            if self._cvt is None and any(lis.rate is None for lis, _, _ in work):
+                self._cvt = self.engine.pcm_converter()
+            if self._heard is None:
                 self._heard = torch.zeros((self.listen_rows, self.listen_max_frames * work[0][0].spf), dtype=torch.float32, device=self.engine.device)
         except Exception as e:  # noqa: BLE001
             for lis, _, _ in work:
@@ -897,31 +938,65 @@ class CSMBatcher:
             lis = item[0]
             if lis._up == 0 and lis._n24 == 0 and not lis._flushed:  # a new stream starts in the row: zero history, zero counts, zeros behind
                 try:
-                    self._lrs.set_row(lis.row, lis.rate, self.engine.sample_rate)
+                    if lis.rate is not None and lis.fmt is None:
+                        self._lrs.set_row(lis.row, lis.rate, self.engine.sample_rate)
+                    elif lis.rate is not None:
+                        self._lrs.set_row(lis.row, lis.rate, self.engine.sample_rate, in_format=lis.fmt)
                     self._heard[lis.row].zero_()
                 except Exception as e:  # noqa: BLE001  (this row's own failure: the others go on)
                     work.remove(item)
                     self._listen_fail(lis, e)
+        rated = [w for w in work if w[0].rate is not None]
+        plain = [w for w in work if w[0].rate is None]
         try:
             while True:
-                todo = [(lis, min(self.LISTEN_IN, fed - lis._up), ended) for lis, fed, ended in work if lis._up < fed or (ended and not lis._flushed)]
+                todo = [(lis, min(self.LISTEN_IN, fed - lis._up), ended) for lis, fed, ended in rated if lis._up < fed or (ended and not lis._flushed)]
                 if not todo:
                     break
-                x = np.zeros((self.listen_rows, max(4, -(-max(k for _, k, _ in todo) // 4) * 4)), np.float32)
                 n_in, flush = [0] * self.listen_rows, [False] * self.listen_rows
+                if any(lis.fmt is not None for lis, _, _ in todo):  # the rows' bytes, each in its own format: 1, 2 or 4 per sample
+                    x = np.zeros((self.listen_rows, max(16, -(-max(k * lis._pcm.itemsize for lis, k, _ in todo) // 16) * 16)), np.uint8)
+                    for lis, k, _ in todo:
+                        x[lis.row, : k * lis._pcm.itemsize] = lis._pcm[lis._up : lis._up + k].view(np.uint8)
+                else:
+                    x = np.zeros((self.listen_rows, max(4, -(-max(k for _, k, _ in todo) // 4) * 4)), np.float32)
+                    for lis, k, _ in todo:
+                        x[lis.row, :k] = lis._pcm[lis._up : lis._up + k]
                 for lis, k, ended in todo:
-                    x[lis.row, :k] = lis._pcm[lis._up : lis._up + k]
                     n_in[lis.row], flush[lis.row] = k, ended and lis._up + k == lis.samples
                 y, n_out = self._lrs.step(torch.from_numpy(x).to(self.engine.device), n_in, flush)
                 for lis, k, _ in todo:
                     n = n_out[lis.row]
-                    self._heard[lis.row, lis._n24 : lis._n24 + n] = y[lis.row, :n]
+                    self._heard[lis.row, lis._n24 : lis._n24 + n] = self._rs_out(self._lrs, y, lis.row, n)
                     with self._lock:
                         lis._up, lis._n24, lis._flushed = lis._up + k, lis._n24 + n, flush[lis.row]
         except Exception as e:  # noqa: BLE001  (the shared step: it fails the rows that took part in it, as an encode step fails its group)
-            for lis, _, _ in work:
+            for lis, _, _ in rated:
+                self._listen_fail(lis, e)
+        try:
+            todo = [(lis, fed - lis._up, ended) for lis, fed, ended in plain]
+            if any(k > 0 for _, k, _ in todo):  # ONE convert launch: the rows' bytes -> float32 at the model's rate
+                x = np.zeros((self.listen_rows, max(16, -(-max(k * lis._pcm.itemsize for lis, k, _ in todo) // 16) * 16)), np.uint8)
+                fmts, n = ["f32"] * self.listen_rows, [0] * self.listen_rows
+                for lis, k, _ in todo:
+                    x[lis.row, : k * lis._pcm.itemsize] = lis._pcm[lis._up : lis._up + k].view(np.uint8)
+                    fmts[lis.row], n[lis.row] = lis.fmt, k
+                y = self._cvt.convert(torch.from_numpy(x).to(self.engine.device), fmts, ["f32"] * self.listen_rows, n)
+                for lis, k, _ in todo:
+                    self._heard[lis.row, lis._n24 : lis._n24 + k] = PCM.view(y, lis.row, "f32")[:k]
+            for lis, k, ended in todo:
+                with self._lock:
+                    lis._up, lis._n24, lis._flushed = lis._up + k, lis._n24 + k, ended  # (ended with this snapshot: these were its last samples)
+        except Exception as e:  # noqa: BLE001
+            for lis, _, _ in plain:
                 self._listen_fail(lis, e)
         return True
+
+    @staticmethod
+    def _rs_out(rs, y, row: int, n: int) -> torch.Tensor:
+        """Row `row`'s `n` new outputs of a resampler step: of a float32 y as they are, of a byte y (a row of the object has a format) as the
+        row's own dtype."""
+        return y[row, :n] if y.dtype == torch.float32 else rs.out_view(y, row)[:n]
 
     def _listen_round(self) -> bool:
         """The scheduler's thread, once per scheduling round: ONE encode step of M frames for every row that holds M frames not yet encoded,
@@ -952,12 +1027,12 @@ class CSMBatcher:
                 if lis._fresh:  # a new stream starts in the row: zero carried state, position 0, the edge fill on this step
                     self._enc.reset_row(lis.row)
                     lis._fresh = False
-                if lis.rate is None:
+                if not lis._dev:
                     pcm[lis.row, 0] = lis._pcm[lis.frames * spf : (lis.frames + F) * spf]  # (zeros behind the fed samples)
                 active[lis.row] = True
             x = torch.from_numpy(pcm)
-            rated = [lis for lis in group if lis.rate is not None]
-            if rated:  # their samples are on the device already, at the model's rate (zeros behind what the resampler wrote)
+            rated = [lis for lis in group if lis._dev]
+            if rated:  # their samples are on the device already, at the model's rate (zeros behind what the resampler / converter wrote)
                 x = x.to(self.engine.device)
                 for lis in rated:
                     x[lis.row, 0] = self._heard[lis.row, lis.frames * spf : (lis.frames + F) * spf]
@@ -1000,11 +1075,12 @@ class CSMBatcher:
                 if lis.session._closed:
                     raise ValueError("end: the session is closed")
                 host = codes.cpu().numpy()  # (synchronises: the codes are the session's prompt frames from here on)
-                audio = lis._pcm[: lis.samples].copy() if lis.rate is None else self._heard[lis.row, : lis._n24].cpu().numpy()
+                audio = lis._pcm[: lis.samples].copy() if not lis._dev else self._heard[lis.row, : lis._n24].cpu().numpy()
                 seg = self.engine.heard_segment(lis.speaker, lis._text, audio)  # (at the model's rate: what `hear` takes)
                 lis.session._hear(seg, host)  # before the result: whoever waits on it finds the turn in the history
             fut.set_result(ListenResult(codes=codes, frames=lis.frames, samples=lis.samples, steps=list(lis.steps),
-                                        sample_rate=lis.rate if lis.rate is not None else int(self.engine.sample_rate)))
+                                        sample_rate=lis.rate if lis.rate is not None else int(self.engine.sample_rate),
+                                        **({"format": lis.fmt} if lis.fmt is not None else {})))
         except Exception as e:  # noqa: BLE001
             fut.set_exception(e)
             if lis.session is not None and lis.session._closed:
@@ -1012,7 +1088,7 @@ class CSMBatcher:
 
     def submit(self, context=None, text=None, speaker: int = 0, voice_match: Optional[bool] = None, max_audio_length_ms: float = 90_000,
                seed: Optional[int] = None, stream_id: Optional[int] = None, prompt=None, prefix=None, sampler=None, session=None,
-               sample_rate: Optional[int] = None) -> Future:
+               sample_rate: Optional[int] = None, format: Optional[str] = None) -> Future:
         """Queue one request; the future yields a `StreamResult`.  `prompt` (tokens, mask) skips the prompt building.  rng "host": `seed`
         seeds this stream's generator (None: fresh entropy).  rng "device": the batcher's seed is used, `seed` must be None or equal to it.
         ValueError at once for a request that cannot fit the cache; a request that races `close()` gets a failed future.
@@ -1030,30 +1106,38 @@ class CSMBatcher:
         and one of another batcher are refused (ValueError).
         `sample_rate` (None: the model's): the result's audio is `resample(a, model rate, sample_rate)` of the audio `a` the request yields
         without it, and `StreamResult.sample_rate` says so; `interrupt(played_samples=)` then counts samples at that rate.  ValueError for a
-        rate the resampler does not take, and for a batcher made with decode=False."""
+        rate the resampler does not take, and for a batcher made with decode=False.
+        `format` (`pcm.FORMATS`; None or "f32": float32): the result's audio is `pcm.encode(a, format)` of the audio `a` the request yields
+        without it at the same rate -- an int16 ("s16le") or uint8 ("mulaw", "alaw") device tensor, encoded in the resampler's launch or, at
+        the model's rate, by one convert launch -- and `StreamResult.format` says so.  ValueError for another name and with decode=False."""
         return self._enqueue(False, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix, sampler, session,
-                             sample_rate)
+                             sample_rate, format)
 
     def submit_stream(self, context=None, text=None, speaker: int = 0, voice_match: Optional[bool] = None, max_audio_length_ms: float = 90_000,
                       seed: Optional[int] = None, stream_id: Optional[int] = None, prompt=None, prefix=None, sampler=None,
-                      session=None, sample_rate: Optional[int] = None) -> CSMAudioStream:
+                      session=None, sample_rate: Optional[int] = None, format: Optional[str] = None) -> CSMAudioStream:
         """`submit` with the audio delivered while the stream runs: the same arguments and refusals, a `CSMAudioStream` back.  Needs a batcher
         made with `stream_chunk_frames=N`; the request may not be longer than `stream_max_frames`.  With `sample_rate` every chunk passes
         through the cache row's resampler row and the final chunk flushes it: `AudioChunk.audio` is at that rate, a chunk's `frames` still
         count codec frames, and the chunks concatenate, bit for bit, to the resampled whole.  That also holds for a stream interrupted at or
         behind the frames it has been sent (the last chunk, of the frames still due or of 0 frames, carries the flush).  It does NOT hold for
-        one cut inside a chunk it was already sent: the samples behind the cut have left, and the result is the resample of the kept audio."""
+        one cut inside a chunk it was already sent: the samples behind the cut have left, and the result is the resample of the kept audio.
+        With `format` every chunk is encoded in that resampler step (at the model's rate: one convert launch for the round's rows):
+        `AudioChunk.audio` holds int16 / uint8 samples and the chunks concatenate, element for element, to the encoded whole."""
         if self._dec is None:
             raise ValueError("submit_stream needs a batcher made with stream_chunk_frames=N")
         return self._enqueue(True, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix, sampler, session,
-                             sample_rate)
+                             sample_rate, format)
 
     def _enqueue(self, _streaming: bool, context, text, speaker, voice_match, max_audio_length_ms, seed, stream_id, prompt, prefix, sampler=None,
-                 session=None, sample_rate=None):
+                 session=None, sample_rate=None, fmt=None):
         max_frames = int(max_audio_length_ms / 80)
         sample_rate = self._rate(sample_rate, inward=False)
         if sample_rate is not None and not self.decode:
             raise ValueError("sample_rate= resamples the decoded audio: the batcher was made with decode=False")
+        fmt = self._format(fmt)
+        if fmt is not None and not self.decode:
+            raise ValueError("format= encodes the decoded audio: the batcher was made with decode=False")
         if sampler is not None:
             if not self.row_samplers:
                 raise ValueError("a per-request sampler needs a batcher made with row_samplers=True; this one samples every stream with its own")
@@ -1114,7 +1198,7 @@ class CSMBatcher:
             self._queue.append(_Stream(future=fut, context=context, text=text, speaker=int(speaker),
                                        voice_match=True if voice_match is None else bool(voice_match),
                                        max_frames=max_frames, seed=seed, stream_id=int(stream_id), length=length, t0=time.perf_counter(),
-                                       prompt=prompt, prefix=prefix, audio=audio, sampler=sampler, session=session, rate=sample_rate))
+                                       prompt=prompt, prefix=prefix, audio=audio, sampler=sampler, session=session, rate=sample_rate, fmt=fmt))
             if sample_rate is not None:
                 self._rate_of[fut] = sample_rate
             if session is not None:
@@ -1263,11 +1347,13 @@ class CSMBatcher:
                     self.engine.synchronize()
                 for j, s in enumerate(group):
                     audio = pcm[j] if pcm is not None else None
-                    if s.rate is not None:
+                    if s.fmt is not None:
+                        audio = self._resample_clip(audio, s.rate, s.fmt)
+                    elif s.rate is not None:
                         audio = self._resample_clip(audio, s.rate)
                     self._resolve(s, StreamResult(audio=audio, frames=count, codes=codes[j],
                                                   sample_rate=s.rate if s.rate is not None else self.engine.sample_rate, stream_id=s.stream_id, row=s.row,
-                                                  processing_time_seconds=time.perf_counter() - s.t0, interrupted=s.cut is not None))
+                                                  processing_time_seconds=time.perf_counter() - s.t0, interrupted=s.cut is not None, **self._fmt_kw(s)))
             except Exception as e:  # noqa: BLE001
                 for s in group:
                     _fail(s, e)
@@ -1329,17 +1415,22 @@ class CSMBatcher:
                     self.stats["interrupted"] += 1
                     if s.emitted >= s.confirmed:  # it has had every frame that was heard: the iterator ends behind a chunk of 0 frames
                         audio = audio[: s.confirmed * (audio.shape[0] // s.emitted)]
-                        tail = audio[:0]
+                        tail = audio[:0] if s.fmt is None else torch.zeros(0, dtype=PCM.torch_dtype(s.fmt), device=audio.device)
                         if s.rate is not None and not s.rflushed and s.emitted == s.confirmed:
                             # the cut is where the emitted chunks end: the row is flushed now and the 0-frame chunk carries the filter's tail
                             n_in, flush = [0] * self.max_batch, [False] * self.max_batch
                             flush[s.row] = True
                             out, n_out = self._ors.step(torch.zeros((self.max_batch, 4), dtype=torch.float32, device=self.engine.device), n_in, flush)
-                            tail = out[s.row, : n_out[s.row]].clone()
+                            tail = self._rs_out(self._ors, out, s.row, n_out[s.row]).clone()
                             s.rchunks.append(tail)
                             s.rflushed = True
-                        s.audio._q.put(AudioChunk(audio=tail, first_frame=s.confirmed, frames=0, final=True))
-                if s.rate is not None:
+                        s.audio._q.put(AudioChunk(audio=tail, first_frame=s.confirmed, frames=0, final=True, **self._fmt_kw(s)))
+                if s.rate is None and s.fmt is not None:
+                    # At the model's rate the encoding is element-wise: the encoded chunks, cut where the kept audio ends, are the encoded whole.
+                    audio = torch.cat(s.rchunks)[: audio.shape[0]]
+                elif s.rate is not None and s.fmt is not None:
+                    audio = torch.cat(s.rchunks) if s.rflushed else self._resample_clip(audio, s.rate, s.fmt)
+                elif s.rate is not None:
                     # Flushed with its last chunk: the chunks are the whole.  An interrupted stream that was cut INSIDE what it had been sent
                     # cannot be flushed (its row has consumed samples behind the cut): its result is the resample of the 24 kHz audio that was
                     # kept, as a plain request's is, and its chunks do not add up to it.
@@ -1349,7 +1440,11 @@ class CSMBatcher:
                 continue
             self._resolve(s, StreamResult(audio=audio, frames=s.confirmed, codes=torch.stack(s.codes[: s.confirmed], dim=1),
                                           sample_rate=s.rate if s.rate is not None else self.engine.sample_rate, stream_id=s.stream_id, row=s.row,
-                                          processing_time_seconds=time.perf_counter() - s.t0, interrupted=s.cut is not None))
+                                          processing_time_seconds=time.perf_counter() - s.t0, interrupted=s.cut is not None, **self._fmt_kw(s)))
+
+    @staticmethod
+    def _fmt_kw(s: _Stream) -> dict:
+        return {"format": s.fmt} if s.fmt is not None else {}
 
     def _decode_round(self, group: List[_Stream], F: int, keep: Optional[int] = None) -> None:
         """One step of the row decoder: F frames for the rows of `group`, the other rows inactive; the chunks carry the first `keep` of them
@@ -1369,6 +1464,12 @@ class CSMBatcher:
                 for s in rated:
                     n_in[s.row], flush[s.row] = keep * (pcm.shape[-1] // F), s.ended and s.emitted + keep == s.confirmed
                 out, n_out = self._ors.step(pcm[:, 0, :], n_in, flush)
+            coded = [s for s in group if s.rate is None and s.fmt is not None]
+            if coded:  # ONE convert launch for the round's rows with a format at the model's rate: the kept samples, encoded
+                fmts, cnt = ["f32"] * self.max_batch, [0] * self.max_batch
+                for s in coded:
+                    fmts[s.row], cnt[s.row] = s.fmt, keep * (pcm.shape[-1] // F)
+                enc = self._cvt.convert(pcm[:, 0, :], ["f32"] * self.max_batch, fmts, cnt)
             self.engine.synchronize()
             self.stats["chunk_rounds"] += 1
             for s in group:
@@ -1376,9 +1477,14 @@ class CSMBatcher:
                                    final=s.ended and s.emitted + keep == s.confirmed)
                 s.chunks.append(chunk.audio)
                 if s.rate is not None:
-                    chunk.audio = out[s.row, : n_out[s.row]].clone()
+                    chunk.audio = self._rs_out(self._ors, out, s.row, n_out[s.row]).clone()
                     s.rchunks.append(chunk.audio)
                     s.rflushed = flush[s.row]
+                elif s.fmt is not None:
+                    chunk.audio = PCM.view(enc, s.row, s.fmt)[: cnt[s.row]].clone()
+                    s.rchunks.append(chunk.audio)
+                if s.fmt is not None:
+                    chunk.format = s.fmt
                 s.emitted += keep
                 if s.audio.first_audio_seconds is None:
                     s.audio.first_audio_seconds = time.perf_counter() - s.t0
@@ -1390,22 +1496,36 @@ class CSMBatcher:
                 if self._rows[s.row] is s:
                     self._release(s)
 
-    def _resample_clip(self, audio: torch.Tensor, rate: int) -> torch.Tensor:
+    def _resample_clip(self, audio: torch.Tensor, rate: Optional[int], fmt: Optional[str] = None) -> torch.Tensor:
         """A whole clip at the model's rate -> `rate`: one step with the flush on a one-row resampler the batcher keeps, on the batch's stream.
-        The same kernel and bits as `resample.resample`, without that call's allocations and its synchronisation."""
+        The same kernel and bits as `resample.resample`, without that call's allocations and its synchronisation.  `fmt`: the step encodes
+        its outputs; without a rate there is no ratio and the clip goes through one convert launch instead."""
+        if rate is None:
+            if self._cvt is None:
+                self._cvt = self.engine.pcm_converter()
+            y = self._cvt.convert(audio.reshape(1, -1), ["f32"], [fmt], [int(audio.shape[0])])
+            return PCM.view(y, 0, fmt)[: int(audio.shape[0])].clone()
         if self._crs is None:
             self._crs = self.engine.row_resampler(1, 1 << 30)
-        self._crs.set_row(0, self.engine.sample_rate, rate)
+        if fmt is None:
+            self._crs.set_row(0, self.engine.sample_rate, rate)
+        else:
+            self._crs.set_row(0, self.engine.sample_rate, rate, out_format=fmt)
         y, n = self._crs.step(audio.reshape(1, -1), [int(audio.shape[0])], [True])
-        return y[0, : n[0]].clone()
+        return self._rs_out(self._crs, y, 0, n[0]).clone()
 
     def _out_row(self, s: _Stream, row: int) -> None:
         """A streaming request with a rate is admitted: its resampler row is the cache row, and a new stream starts in it."""
         if s.rate is None:
+            if s.fmt is not None and self._cvt is None:  # at the model's rate its chunks go through the stateless converter
+                self._cvt = self.engine.pcm_converter()
             return
         if self._ors is None:
             self._ors = self.engine.row_resampler(self.max_batch, self.chunk * int(self.engine.samples_per_frame))
-        self._ors.set_row(row, self.engine.sample_rate, s.rate)
+        if s.fmt is None:
+            self._ors.set_row(row, self.engine.sample_rate, s.rate)
+        else:
+            self._ors.set_row(row, self.engine.sample_rate, s.rate, out_format=s.fmt)
 
     def _timed(self, what: str, fn) -> None:
         if self.profile:
@@ -1737,7 +1857,7 @@ class CSMBatcher:
             self._dec.close()
         if self._enc is not None:
             self._enc.close()
-        for rs in (self._lrs, self._ors, self._crs):
+        for rs in (self._lrs, self._ors, self._crs, self._cvt):
             if rs is not None:
                 rs.close()
         if self.overlap:

@@ -536,7 +536,8 @@ class Model:
         result equals its own `generate_batch([prompt])` run.  Keyword arguments are CSMBatcher's; `overlap_admission=True` (with
         `prefill_lanes=N`) prefills requests on a side stream while the batch keeps stepping; `listen_rows=K` lets up to K
         callers feed microphone audio (`listen()` / `session.listen()`), tokenised as it arrives by the codec's row-mode streaming encoder
-        (DESIGN 8d-9).  Those are streaming-encoder codes, not the whole-clip codes of `encode_audios`."""
+        (DESIGN 8d-9).  Those are streaming-encoder codes, not the whole-clip codes of `encode_audios`.  Both audio edges take a
+        `sample_rate=` and a `format=` -- "s16le", "mulaw" or "alaw" bytes in, int16 / uint8 tensors out."""
         from .csm_serve import CSMBatcher
 
         return CSMBatcher(self, **kw)

@@ -3,7 +3,9 @@ each with the samples of one round of 6 frames (0.48 s) at its source rate, for 
 to 24 kHz, and the three mixed in one launch.  Prints one JSON line per case: the stream's time per step (device events around `--steps` steps
 after `--warmup`, so host enqueue gaps count where the host is the slower side) and the host's wall-clock per step.
 
-Usage:  python tools/bench_resample.py [--rows 8] [--steps 10000] [--warmup 200] [--out profiles/resample_bench.json]
+Usage:  python tools/bench_resample.py [--rows 8] [--steps 10000] [--warmup 200] [--format f32] [--out profiles/resample_bench.json]
+`--format`: what every row's new samples are stored as -- "f32" (the default: the f32 entry points, as before), "s16le", "mulaw"
+or "alaw", decoded inside the same launch; `bytes_up_per_step` is what a listen round uploads for the step.
 
 The kernel alone (the steps above are host-bound) comes from a kernel trace, taken in a run of its own and summarised by this tool:
     rocprofv3 --kernel-trace --stats -d DIR -o rs -- python tools/bench_resample.py --steps 1000 --warmup 50
@@ -22,18 +24,25 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from mlx_audio_amd import pcm as PCM  # noqa: E402
 from mlx_audio_amd import resample as RS  # noqa: E402
 
 SR, ROUND_SECONDS = 24000, 0.48  # 6 frames of 80 ms
 
 
-def case(name, rates, rows, steps, warmup):
+def case(name, rates, rows, steps, warmup, fmt="f32"):
     rs = RS.RowResampler(rows, max(int(r * ROUND_SECONDS) for r in rates))
     n_in = [int(rates[b % len(rates)] * ROUND_SECONDS) for b in range(rows)]
     for b in range(rows):
-        rs.set_row(b, rates[b % len(rates)], SR)
+        if fmt == "f32":
+            rs.set_row(b, rates[b % len(rates)], SR)
+        else:
+            rs.set_row(b, rates[b % len(rates)], SR, in_format=fmt)
     g = torch.Generator().manual_seed(0)
-    x = (0.3 * torch.randn((rows, -(-max(n_in) // 4) * 4), generator=g)).cuda()
+    x = 0.3 * torch.randn((rows, -(-max(n_in) // 16) * 16), generator=g)
+    if fmt != "f32":  # the rows' samples in their format, as bytes
+        x = torch.from_numpy(np.stack([PCM.encode(r.numpy(), fmt) for r in x]).view(np.uint8))
+    x = x.cuda()
     flush = [False] * rows
     n_out = None
     for _ in range(warmup):
@@ -49,10 +58,10 @@ def case(name, rates, rows, steps, warmup):
     torch.cuda.synchronize()
     rs.close()
     ratios = sorted({RS.ratio(r, SR) for r in rates})
-    return dict(case=name, rows=rows, ratios=[f"{L}/{M}" for L, M in ratios], taps_per_output=[RS.taps_per_output(L, M) for L, M in ratios],
+    return dict(case=name, format=fmt, bytes_up_per_step=PCM.bytes_per_sample(fmt) * sum(n_in), rows=rows, ratios=[f"{L}/{M}" for L, M in ratios], taps_per_output=[RS.taps_per_output(L, M) for L, M in ratios],
                 samples_in_per_row=n_in, samples_out_per_row=n_out, steps=steps, warmup=warmup,
                 stream_us_per_step=round(start.elapsed_time(end) * 1e3 / steps, 2), host_us_per_step=round(host * 1e6 / steps, 2),
-                bytes_in_out_per_step=4 * (sum(n_in) + sum(n_out)))
+                bytes_in_out_per_step=PCM.bytes_per_sample(fmt) * sum(n_in) + 4 * sum(n_out))
 
 
 CASES = (("8k", [8000]), ("16k", [16000]), ("44k1", [44100]), ("mixed", [8000, 16000, 44100]))
@@ -85,6 +94,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--format", default="f32", choices=PCM.FORMATS)
     ap.add_argument("--summarise-trace", default=None, metavar="DB")
     a = ap.parse_args()
     if a.summarise_trace:
@@ -98,7 +108,7 @@ def main():
         return
     if not torch.cuda.is_available():
         raise SystemExit("bench_resample.py needs a GPU: a time taken elsewhere says nothing")
-    results = [case(name, rates, a.rows, a.steps, a.warmup)
+    results = [case(name, rates, a.rows, a.steps, a.warmup, a.format)
                for name, rates in CASES]
     for r in results:
         print(json.dumps(r))
