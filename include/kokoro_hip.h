@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 11  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 12  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -44,7 +44,8 @@ extern "C" {
                             10: row-mode polyphase resampler (kk_resampler_create, kk_resampler_destroy, kk_resampler_set_row, kk_resampler_step,
                                kk_resampler_block_outputs, kk_op_resample);
                             11: PCM wire formats at the resampler's edges and on their own (KK_PCM_*, kk_resampler_set_row_fmt, kk_resampler_step_fmt,
-                               kk_pcm_convert_rows, kk_op_pcm_convert) */
+                               kk_pcm_convert_rows, kk_op_pcm_convert);
+                            12: row-mode voice-activity detector (kk_vad_create, kk_vad_destroy, kk_vad_set_row, kk_vad_step, kk_op_vad) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -384,6 +385,39 @@ int kk_resampler_step_fmt(kk_resampler* r, void* stream, const void* x, long lon
 int kk_pcm_convert_rows(void* stream, int rows, const void* x, long long ldx_bytes, const int32_t* in_fmt, void* y, long long ldy_bytes,
                         const int32_t* out_fmt, const int32_t* n);
 int kk_op_pcm_convert(void* stream, const void* x, int in_fmt, void* y, int out_fmt, int n);
+
+/* =====================================================================================================================
+ * Row-mode voice-activity detector (ABI minor 12): endpointing and barge-in for the listening edge of CSM serving.  The
+ * reference's energy rule and listener loop (mlx_audio/sts/voice_pipeline.py _is_silent, _listener; webrtcvad's model is not restated):
+ * a frame of frame_len samples is speech iff its energy E = sum x^2 >= thr2n = float32(threshold^2 frame_len) -- rms >= threshold without
+ * the square root and the division -- and, per row and in frame order,
+ *   speech:  speaking = 1, silent = 0, last_speech = f, onset = f if there was none
+ *   silence while speaking:  ++silent; silent > hang_frames: endpoint = f, and the row classifies nothing after it
+ *   silence before any speech:  nothing
+ * E is ONE wave's fixed order: lane l runs acc = fmaf(x[i], x[i], acc) from 0.0f over i = l, l + 64, ... ascending within the frame, and an
+ * xor butterfly over the distances 32, 16, 8, 4, 2, 1 adds the 64 partial sums; E's bits depend on the frame's samples alone.  A NaN energy
+ * compares false and reads as silence.
+ *   kk_vad_create: max_rows <= 64 independent streams.
+ *   kk_vad_set_row: a new stream starts in `row` with zero counts and no onset (one tiny launch on `stream`).  frame_len in [1, 4096],
+ *     hang_frames >= 0, thr2n finite and >= 0 (computed by the caller in double precision, rounded once).
+ *   kk_vad_step: x [max_rows][ldx] on the device; x[row][0 .. n_avail[row]) is the row's stream FROM ITS FIRST SAMPLE, the same buffer every
+ *     step.  n_avail is a HOST array [max_rows].  The step classifies the whole frames classified <= f < n_avail / frame_len.  A row whose
+ *     n_avail gives no new whole frame sits out, as does a row without a kk_vad_set_row and a row that has reached its endpoint: nothing
+ *     of it is read (it may hold NaN), its state and status stay.  status [max_rows][4] int32 on the DEVICE: {classified, onset,
+ *     last_speech, endpoint} per row, -1 for "none", written for the rows that took part.  energy: NULL, or [max_rows][lde] fp32 on the
+ *     device: the E of the frames this step classified, energy[row][f - first new frame].  One launch, one workgroup per row; no
+ *     synchronisation: the host mirrors the frame count with integers.
+ *   kk_op_vad: a whole clip x [n] (device) on a one-row detector; status_host [4] on the HOST, energy_or_null [n / frame_len] on the device.
+ *     Synchronises `stream`.  For tools and tests.
+ * Refused on the host before any launch, with nothing changed: a row out of range, frame_len or hang_frames out of range, a negative,
+ * infinite or NaN thr2n, an n_avail below the row's previous one or above ldx, an lde shorter than a row's new frames.
+ * ===================================================================================================================== */
+typedef struct kk_vad kk_vad;
+int kk_vad_create(int max_rows, kk_vad** out);
+void kk_vad_destroy(kk_vad* v);
+int kk_vad_set_row(kk_vad* v, void* stream, int row, int frame_len, float thr2n, int hang_frames);
+int kk_vad_step(kk_vad* v, void* stream, const float* x, long long ldx, const int32_t* n_avail, int32_t* status, float* energy, long long lde);
+int kk_op_vad(void* stream, const float* x, int n, int frame_len, float thr2n, int hang_frames, int32_t status_host[4], float* energy_or_null);
 
 /* =====================================================================================================================
  * CSM-1B frame generator (rows C1-C3): SesameModel.generate_frame, mlx_audio/tts/models/sesame/sesame.py:349-395, with the

@@ -70,7 +70,16 @@ that format and uploads them once per round; they are decoded inside the resampl
 `pcm.decode(the bytes)`.  A request with a format gets `int16` / `uint8` device tensors: the resampler step of its decode round encodes
 them (at the model's rate: one convert launch for the round's rows), and the chunks concatenate, element for element, to `pcm.encode` of the
 audio the request yields without a format.  Counts (`listen_max_frames`, `ListenResult.samples`, `played_samples`) stay in samples.
-Without a format nothing of this exists: no converter is made and every call is the one it was."""
+Without a format nothing of this exists: no converter is made and every call is the one it was.
+
+Endpointing and barge-in: `listen(vad=VadConfig())`, `sess.listen(speaker, vad=..., barge_in=True)`.  Behind the round's resampler /
+convert launches ONE detector step (`vad.RowVad`: the reference's energy rule and listener loop) classifies every VAD listener's new whole
+frames in its device buffer; the status table travels to pinned host memory behind an event and is consumed at the top of a later round, so no
+round waits for it.  A VAD listener's encoder stream is heard[start:], nothing of it is encoded before the onset, and while it is open only
+steps below what the consumed status has made certain; at an endpoint (`lis.endpoint`) or at `end()` the span heard[start:stop] is final and
+the rest is encoded, zeros behind `stop`: codes, frames and steps are those of a plain listener fed heard[start:stop] and ended.  `lis.onset`
+resolves with the onset; with `barge_in` that round interrupts the session's turn through the controls of 8d-8.
+Without `vad=` nothing of this exists: no detector is made and a listen round is the launches it was."""
 from __future__ import annotations
 
 import queue
@@ -88,6 +97,7 @@ import torch
 
 from . import pcm as PCM
 from . import resample as RS
+from . import vad as VAD
 
 
 @dataclass
@@ -126,6 +136,21 @@ class ListenResult:
     steps: List[int]     # the encoder steps of this stream: [M] * (T // M) + [T % M]
     sample_rate: int = 0  # the rate the samples were fed at; with `listen(sample_rate=R)` T = ceil(out_len(samples) / samples per frame)
     format: str = "f32"   # the format the samples were fed in (`listen(format=)`); `samples` counts samples, not bytes
+    speech_start: Optional[int] = None  # a listener made with `vad=`: the samples [speech_start, speech_stop) at the model's rate of what was
+    speech_stop: Optional[int] = None   # fed are what `codes` encode; None for a listener without a detector
+
+
+@dataclass
+class SpeechSpan:
+    """What a VAD listener's `endpoint` future resolves with: the utterance is over.  Samples and frames at the model's rate; the same span
+    counted at the rate the listener is fed at in `rate_start` / `rate_stop` (floor / ceil)."""
+    start: int           # the first sample kept: the onset frame's first sample less the pre-roll
+    stop: int            # one past the last sample kept
+    onset_frame: int     # the first speech frame, in detector frames
+    endpoint_frame: int  # the silent frame that made the count pass the hang
+    sample_rate: int = 0  # the listener's own rate
+    rate_start: int = 0
+    rate_stop: int = 0
 
 
 class CSMListener:
@@ -133,12 +158,24 @@ class CSMListener:
     has been tokenised so far, `end(text)` for the `Future[ListenResult]`, `cancel()` to drop it.  It holds one row of the batcher's row-mode
     streaming encoder from `listen` until the result (or `cancel`)."""
 
-    def __init__(self, batcher: "CSMBatcher", row: int, speaker: int, session=None, sample_rate: Optional[int] = None, fmt: Optional[str] = None):
+    def __init__(self, batcher: "CSMBatcher", row: int, speaker: int, session=None, sample_rate: Optional[int] = None, fmt: Optional[str] = None,
+                 vad: Optional[VAD.VadConfig] = None, barge_in: bool = False):
         self.batcher, self.row, self.speaker, self.session = batcher, int(row), int(speaker), session
+        # voice activity (DESIGN 8d-12): the detector's settings, or None -- then nothing below `barge_in` is ever touched
+        self.vad, self.barge_in = vad, bool(barge_in)
+        self.onset: Optional[Future] = Future() if vad is not None else None     # -> the first kept sample at the model's rate, once speech began
+        self.endpoint: Optional[Future] = Future() if vad is not None else None  # -> SpeechSpan, once the speaker has finished
+        self._vset = False                    # the detector row holds this listener's stream
+        self._vsent = 0                       # the `_n24` of the last detector step that took the row
+        self._vst = VAD.NO_STATUS             # the last status the scheduler consumed, and ...
+        self._vn = 0                          # ... the `_n24` it covers
+        self._vstart: Optional[int] = None    # the encoder's stream is heard[_vstart:], once an onset was consumed
+        self._vstop: Optional[int] = None     # ... and ends at heard[_vstop], once the span is final (`_vclosed`)
+        self._vclosed = False                 # an endpoint was consumed, or `end()` and the status that covers everything fed
         self.spf = int(batcher.engine.samples_per_frame)
         self.rate = sample_rate               # None: fed at the model's rate; else the scheduler resamples what is fed (DESIGN 8d-10)
         self.fmt = fmt                        # None: fed float32; else the samples are kept and uploaded in this format (DESIGN 8d-11)
-        self._dev = sample_rate is not None or fmt is not None  # the encoder reads this listener from its device buffer at the model's rate
+        self._dev = sample_rate is not None or fmt is not None or vad is not None  # the encoder reads this listener from its device buffer at the model's rate
         cap = batcher.listen_max_frames * self.spf
         if self.rate is not None:             # the most samples at `rate` whose out_len fits the row: N L <= cap M
             L, M = RS.ratio(self.rate, batcher.engine.sample_rate)
@@ -163,13 +200,32 @@ class CSMListener:
     def _total(self) -> int:
         """Frames the stream holds for the scheduler: whole frames while it is open, ceil once it has ended.  A rate listener: of the
         samples its device buffer holds -- ready(fed) while it is open, out_len(fed) once it has been flushed."""
+        if self.vad is not None:
+            return self._vad_total()
         if self._dev:
             return -(-self._n24 // self.spf) if self._flushed else self._n24 // self.spf
         return -(-self.samples // self.spf) if self.ended else self.samples // self.spf
 
+    def _vad_total(self) -> int:
+        """A VAD listener's frames: of heard[start:stop] once the span is final; while it is open only the whole frames below
+        B = min(classified fl, (last_speech + 1) fl + keep) - start, which the final span can only grow beyond; none before an onset."""
+        if self._vstart is None:
+            return 0
+        if self._vclosed:
+            return -(-(self._vstop - self._vstart) // self.spf)
+        sp = VAD.span(self.vad, self._vst, self._vn, False, self.batcher.engine.sample_rate)
+        return max(0, sp[1] - self._vstart) // self.spf
+
     def _unresampled(self) -> bool:
         """Under the lock: the scheduler's next round has samples of this listener to resample, or its flush."""
-        return self._dev and (self._up < self.samples or (self.ended and not self._flushed))
+        return self._dev and not self._vclosed and (self._up < self.samples or (self.ended and not self._flushed))
+
+    def _vad_due(self) -> bool:
+        """Under the lock: the detector has new samples of this listener to classify, or `end()` has come and the status that covers
+        everything fed has been consumed: the scheduler's next round closes it."""
+        if self.vad is None or self._vclosed:
+            return False
+        return (self._vset and self._vsent != self._n24) or (self.ended and self._flushed and self._vn == self._n24)
 
     def feed(self, pcm) -> None:
         """Mono float32 at the listener's sample rate (the model's, or the `sample_rate` it was made with), any number of samples.  Host
@@ -187,6 +243,8 @@ class CSMListener:
                 raise RuntimeError("CSMBatcher is closed")
             if not self._open or self.ended:
                 raise ValueError("feed: the listener has ended or was cancelled")
+            if self._vclosed:  # behind a detected endpoint: accepted and ignored
+                return
             if self.samples + a.shape[0] > self._pcm.shape[0]:
                 raise ValueError(f"feed: {self.samples + a.shape[0]} samples are more than listen_max_frames = {b.listen_max_frames} frames")
             self._pcm[self.samples : self.samples + a.shape[0]] = a
@@ -237,8 +295,9 @@ class CSMListener:
             if b._listeners[self.row] is self:
                 b._listeners[self.row] = None
             fut = self._future
-        if fut is not None:
-            fut.cancel()
+        for f in (fut, self.onset, self.endpoint):
+            if f is not None:
+                f.cancel()
         return True
 
 
@@ -396,14 +455,19 @@ class CSMSession:
         self.turns.append((int(segment.speaker), segment.text, 0))
         self.pending, self.history = _cat(self.pending, f), _cat(self.history, f)
 
-    def listen(self, speaker: int = 0, sample_rate: Optional[int] = None, format: Optional[str] = None) -> "CSMListener":
+    def listen(self, speaker: int = 0, sample_rate: Optional[int] = None, format: Optional[str] = None, vad=None, barge_in: bool = False) -> "CSMListener":
         """`CSMBatcher.listen` for this conversation: another speaker's microphone.  Allowed while the session's own turn is queued or live
-        (a barge-in); the turn enters the history at the listener's `end(text)`, which waits for that turn as `hear` does."""
+        (a barge-in); the turn enters the history at the listener's `end(text)`, which waits for that turn as `hear` does.
+        vad (`vad.VadConfig`, or True for the defaults): the scheduler finds the utterance itself.  barge_in (needs vad): the
+        round that sees the speaker's onset interrupts this session's queued or live turn, which keeps what it has emitted."""
         if self._closed:
             raise ValueError("listen: the session is closed")
-        if format is None:
-            return self.batcher.listen(speaker=speaker, session=self, sample_rate=sample_rate)
-        return self.batcher.listen(speaker=speaker, session=self, sample_rate=sample_rate, format=format)
+        kw = {} if format is None else {"format": format}
+        if vad is not None and vad is not False:
+            kw.update(vad=vad, barge_in=barge_in)
+        elif barge_in:
+            raise ValueError("listen: barge_in needs vad=")
+        return self.batcher.listen(speaker=speaker, session=self, sample_rate=sample_rate, **kw)
 
     def submit(self, text, **kw) -> Future:
         kw.setdefault("speaker", self.speaker)
@@ -644,6 +708,10 @@ class ModelEngine:
         """A row-mode polyphase resampler on the engine's device (resample.RowResampler): set_row, step(x, n_in, flush), out_view, close."""
         return RS.RowResampler(max_rows, max_in, device=self.device)
 
+    def row_vad(self, max_rows: int):
+        """A row-mode voice-activity detector on the engine's device (vad.RowVad): set_row, step(x, n_avail), fetch, close."""
+        return VAD.RowVad(max_rows, device=self.device)
+
     def pcm_converter(self):
         """The PCM converter of rows at the model's own rate on the engine's device (pcm.RowConverter): convert(x, in_formats, out_formats, n), close."""
         return PCM.RowConverter(device=self.device)
@@ -842,6 +910,9 @@ class CSMBatcher:
         self._crs = None                       # one row for whole clips (a plain request's result): made once, so no allocation per result
         self._rate_of: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()  # future -> the request's rate (under the lock)
         self._cvt = None                       # PCM formats at the model's own rate: one stateless converter, made with the first such row
+        self._vad = None                       # voice activity: one detector row per encoder row, made with the first VAD listener
+        self._vad_n = [0] * self.listen_rows   # per detector row: the n_avail of its last step (a row no step takes is handed the same again)
+        self._vad_out: Deque[tuple] = deque()  # (ticket, {row: (listener, the `_n24` covered)}): status tables on their way to the host
         dev = self.engine.device
         self._prev = torch.zeros((self.max_batch, self.engine.n_cb), dtype=torch.int32, device=dev)
         self._first_eos = torch.full((self.max_batch,), -1, dtype=torch.int64, device=dev)  # stream-local index of the first all-zero frame
@@ -854,15 +925,32 @@ class CSMBatcher:
         return CSMSession(self, context, speaker)
 
     def listen(self, speaker: int = 0, session: Optional[CSMSession] = None, sample_rate: Optional[int] = None,
-               format: Optional[str] = None) -> CSMListener:
+               format: Optional[str] = None, vad=None, barge_in: bool = False) -> CSMListener:
         """A microphone (`CSMListener`) on a free row of the batcher's streaming encoder; ValueError when all `listen_rows` are taken (or
         the batcher was made without any).  `session`: what `CSMSession.listen` passes.  `sample_rate`: the rate `feed` takes (None: the
         model's); ValueError for a rate the resampler does not take.  `format` (`pcm.FORMATS`; None or "f32": float32): what `feed` takes --
-        "s16le", "mulaw" or "alaw" bytes; ValueError for another name.  Any thread; nothing of the device is touched."""
+        "s16le", "mulaw" or "alaw" bytes; ValueError for another name.  Any thread; nothing of the device is touched.
+        `vad` (`vad.VadConfig`, or True for the reference's defaults): the scheduler runs a voice-activity detector over what
+        the listener is fed, on the device and at the model's rate.  Nothing is encoded before the speaker's onset (`lis.onset`, a
+        `Future[int]`: the first kept sample); after `silence_ms` of silence `lis.endpoint` resolves with a `SpeechSpan` and later feeds are
+        ignored; `end(text)` -- before or after the endpoint -- resolves with the `ListenResult` of a plain listener fed
+        heard[speech_start:speech_stop] and ended, or fails with ValueError("no speech").  `barge_in` (a session's listener): the onset
+        interrupts the session's queued or live turn in the round that sees it."""
         if self._enc is None:
             raise ValueError("listen needs a batcher made with listen_rows=K")
         sample_rate = self._rate(sample_rate, inward=True)
         fmt = self._format(format)
+        if vad is None or vad is False:
+            vad = None
+            if barge_in:
+                raise ValueError("listen: barge_in needs vad=")
+        else:
+            vad = VAD.VadConfig() if vad is True else vad
+            if not isinstance(vad, VAD.VadConfig):
+                raise ValueError("listen: vad takes a vad.VadConfig or True")
+            vad.frame_len(self.engine.sample_rate)  # (ValueError for a frame the detector does not take)
+            if barge_in and session is None:
+                raise ValueError("listen: barge_in needs a session's listener (CSMSession.listen)")
         if session is not None and session.batcher is not self:
             raise ValueError("the session belongs to another batcher (CSMBatcher.session on this batcher)")
         with self._lock:
@@ -871,7 +959,8 @@ class CSMBatcher:
             free = [r for r in range(self.listen_rows) if self._listeners[r] is None]
             if not free:
                 raise ValueError(f"all {self.listen_rows} listen rows are taken")
-            lis = self._listeners[free[0]] = CSMListener(self, free[0], speaker, session, sample_rate, fmt)
+            extra = {} if vad is None else {"vad": vad, "barge_in": barge_in}
+            lis = self._listeners[free[0]] = CSMListener(self, free[0], speaker, session, sample_rate, fmt, **extra)
         return lis
 
     @staticmethod
@@ -899,9 +988,12 @@ class CSMBatcher:
                 continue
             left = lis._total() - lis.frames
             ended = lis.ended and (not lis._dev or lis._flushed)
+            whole = ended  # the stream's length is final: its remainder may be encoded
+            if lis.vad is not None:  # the span is final at an endpoint or at `end()`; the result waits for the caller's `end()`
+                whole, ended = lis._vclosed, lis._vclosed and lis.ended
             if left >= M:
                 full.append(lis)
-            elif ended and left > 0:
+            elif whole and left > 0:
                 tails.setdefault(left, []).append(lis)
             elif ended:
                 done.append(lis)
@@ -909,6 +1001,8 @@ class CSMBatcher:
 
     def _listen_due(self) -> bool:
         full, tails, done = self._listen_plan()
+        if self._vad_out or any(lis is not None and lis._open and lis._vad_due() for lis in self._listeners):
+            return True  # a status on its way to the host, or samples the detector has not seen, are work due
         return bool(full or tails or done) or any(lis is not None and lis._open and lis._unresampled() for lis in self._listeners)
 
     LISTEN_IN = 1 << 15  # samples per row and resampler step: a long clip fed at once takes several steps in its round
@@ -928,6 +1022,8 @@ class CSMBatcher:
                 self._lrs = self.engine.row_resampler(self.listen_rows, self.LISTEN_IN)
             if self._cvt is None and any(lis.rate is None for lis, _, _ in work):
                 self._cvt = self.engine.pcm_converter()
+            if self._vad is None and any(lis.vad is not None for lis, _, _ in work):
+                self._vad = self.engine.row_vad(self.listen_rows)
             if self._heard is None:
                 self._heard = torch.zeros((self.listen_rows, self.listen_max_frames * work[0][0].spf), dtype=torch.float32, device=self.engine.device)
         except Exception as e:  # noqa: BLE001
@@ -943,6 +1039,10 @@ class CSMBatcher:
                     elif lis.rate is not None:
                         self._lrs.set_row(lis.row, lis.rate, self.engine.sample_rate, in_format=lis.fmt)
                     self._heard[lis.row].zero_()
+                    if lis.vad is not None:
+                        sr = self.engine.sample_rate
+                        self._vad.set_row(lis.row, lis.vad.frame_len(sr), lis.vad.thr2n(sr), lis.vad.hang_frames)
+                        self._vad_n[lis.row], lis._vset = 0, True
                 except Exception as e:  # noqa: BLE001  (this row's own failure: the others go on)
                     work.remove(item)
                     self._listen_fail(lis, e)
@@ -980,7 +1080,7 @@ class CSMBatcher:
                 fmts, n = ["f32"] * self.listen_rows, [0] * self.listen_rows
                 for lis, k, _ in todo:
                     x[lis.row, : k * lis._pcm.itemsize] = lis._pcm[lis._up : lis._up + k].view(np.uint8)
-                    fmts[lis.row], n[lis.row] = lis.fmt, k
+                    fmts[lis.row], n[lis.row] = lis.fmt or "f32", k  # (f32 at the model's rate: a VAD listener, whose samples must be in the device buffer)
                 y = self._cvt.convert(torch.from_numpy(x).to(self.engine.device), fmts, ["f32"] * self.listen_rows, n)
                 for lis, k, _ in todo:
                     self._heard[lis.row, lis._n24 : lis._n24 + k] = PCM.view(y, lis.row, "f32")[:k]
@@ -1003,6 +1103,8 @@ class CSMBatcher:
         then one step per distinct remainder r for the ended rows whose remainder is due, then the ended rows with nothing left resolve.  A
         listener's steps are therefore [M] * (T // M) + [T % M] whatever the slicing and the timing of its `feed` calls."""
         fresh = self._listen_resample()
+        if self._vad is not None and (self._vad_step() or self._vad_out):
+            fresh = True
         with self._lock:
             full, _, _ = self._listen_plan()
         if full:
@@ -1035,7 +1137,13 @@ class CSMBatcher:
             if rated:  # their samples are on the device already, at the model's rate (zeros behind what the resampler / converter wrote)
                 x = x.to(self.engine.device)
                 for lis in rated:
-                    x[lis.row, 0] = self._heard[lis.row, lis.frames * spf : (lis.frames + F) * spf]
+                    if lis.vad is None:
+                        x[lis.row, 0] = self._heard[lis.row, lis.frames * spf : (lis.frames + F) * spf]
+                        continue
+                    # a VAD listener's stream is heard[start:stop]: zeros, not the samples the buffer holds there, behind `stop`
+                    a = lis._vstart + lis.frames * spf
+                    b = a + F * spf if not lis._vclosed else min(a + F * spf, lis._vstop)
+                    x[lis.row, 0, : b - a] = self._heard[lis.row, a:b]
             out: List[torch.Tensor] = []
             self._timed("listen", lambda: out.append(self._enc.step(x, active)))
             self.stats["listen_rounds"] += 1
@@ -1054,6 +1162,75 @@ class CSMBatcher:
             lis._open = False
             if self._listeners[lis.row] is lis:
                 self._listeners[lis.row] = None
+        for f in (lis.onset, lis.endpoint):  # a VAD listener that leaves without them: whoever waits is told
+            if f is not None:
+                f.cancel()
+
+    # ---- voice activity -----------------------------------------------------------------------------------------------------
+    def _vad_step(self) -> bool:
+        """The scheduler's thread, behind the round's resampler / convert launches: ONE detector step over the listeners' device buffers for
+        every VAD row that holds samples the detector has not seen, then the status table starts its way to pinned host memory (`fetch`: a
+        copy and an event, nothing waits).  The status is consumed at the top of a later round (`_vad_consume`)."""
+        with self._lock:
+            rows = [lis for lis in self._listeners if lis is not None and lis._open and lis.vad is not None and lis._vset and not lis._vclosed
+                    and lis._vsent != lis._n24]
+            if not rows:
+                return False
+            n = list(self._vad_n)
+            for lis in rows:
+                n[lis.row] = lis._n24
+        try:
+            self._vad.step(self._heard, n)
+            self._vad_n = n  # (the detector's own counts have moved, whatever becomes of the hand-back)
+            ticket = self._vad.fetch()
+        except Exception as e:  # noqa: BLE001  (the shared step: it fails the rows that took part in it)
+            for lis in rows:
+                self._listen_fail(lis, e)
+            return True
+        with self._lock:
+            for lis in rows:
+                lis._vsent = n[lis.row]
+        self._vad_out.append((ticket, {lis.row: (lis, n[lis.row]) for lis in rows}))
+        return True
+
+    def _vad_consume(self) -> None:
+        """The scheduler's thread, at the top of a round: every status table that has landed (`ready()`, no sync) becomes its listeners'
+        state.  An onset resolves `lis.onset` and, with `barge_in`, records an interrupt of the session's turn, which this same round's
+        `_apply_controls` applies.  An endpoint, or `end()` and the status that covers everything fed, makes the span final."""
+        while self._vad_out and self._vad_out[0][0].ready():
+            ticket, covered = self._vad_out.popleft()
+            table = ticket.take()
+            with self._lock:
+                for row, (lis, n24) in covered.items():
+                    if lis._open and self._listeners[row] is lis and not lis._vclosed:
+                        lis._vst, lis._vn = tuple(int(v) for v in table[row]), n24
+        with self._lock:
+            mine = [lis for lis in self._listeners if lis is not None and lis._open and lis.vad is not None and not lis._vclosed]
+        sr = int(self.engine.sample_rate)
+        for lis in mine:
+            _, o, _, e = lis._vst
+            if lis._vstart is None and o >= 0:
+                start = VAD.span(lis.vad, lis._vst, lis._vn, False, sr)[0]
+                with self._lock:
+                    lis._vstart = start
+                    turn = lis.session._turn if (lis.barge_in and lis.session is not None) else None
+                    if turn is not None and not turn.done():  # queued, in a lane or live: it ends with what it has emitted (`interrupt`)
+                        self._controls.append((turn, "interrupt", None))
+                if _claim(lis.onset):
+                    lis.onset.set_result(start)
+            with self._lock:
+                final = e >= 0 or (lis.ended and lis._flushed and lis._vn == lis._n24)
+                if not final:
+                    continue
+                sp = VAD.span(lis.vad, lis._vst, lis._n24, True, sr)
+                lis._vstop = sp[1] if sp is not None else 0
+                lis._vclosed = True
+            if e >= 0 and _claim(lis.endpoint):
+                R = lis.rate if lis.rate is not None else sr
+                lis.endpoint.set_result(SpeechSpan(start=sp[0], stop=sp[1], onset_frame=o, endpoint_frame=e, sample_rate=R,
+                                                   rate_start=sp[0] * R // sr, rate_stop=min(lis.samples, -(-sp[1] * R // sr))))
+            elif e < 0:
+                lis.endpoint.cancel()  # the caller ended the listener first: there was no endpoint
 
     def _listen_fail(self, lis: CSMListener, e: BaseException) -> None:
         self._listen_free(lis)
@@ -1070,17 +1247,23 @@ class CSMBatcher:
         if not _claim(fut):
             return
         try:
+            if lis.vad is not None and lis._vstart is None:
+                raise ValueError("no speech")  # (the session is as it was: nothing was heard)
             codes = torch.cat(lis._codes, dim=1)
+            span = {} if lis.vad is None else {"speech_start": lis._vstart, "speech_stop": lis._vstop}
             if lis.session is not None:
                 if lis.session._closed:
                     raise ValueError("end: the session is closed")
                 host = codes.cpu().numpy()  # (synchronises: the codes are the session's prompt frames from here on)
-                audio = lis._pcm[: lis.samples].copy() if not lis._dev else self._heard[lis.row, : lis._n24].cpu().numpy()
+                if lis.vad is not None:
+                    audio = self._heard[lis.row, lis._vstart : lis._vstop].cpu().numpy()
+                else:
+                    audio = lis._pcm[: lis.samples].copy() if not lis._dev else self._heard[lis.row, : lis._n24].cpu().numpy()
                 seg = self.engine.heard_segment(lis.speaker, lis._text, audio)  # (at the model's rate: what `hear` takes)
                 lis.session._hear(seg, host)  # before the result: whoever waits on it finds the turn in the history
             fut.set_result(ListenResult(codes=codes, frames=lis.frames, samples=lis.samples, steps=list(lis.steps),
                                         sample_rate=lis.rate if lis.rate is not None else int(self.engine.sample_rate),
-                                        **({"format": lis.fmt} if lis.fmt is not None else {})))
+                                        **({"format": lis.fmt} if lis.fmt is not None else {}), **span))
         except Exception as e:  # noqa: BLE001
             fut.set_exception(e)
             if lis.session is not None and lis.session._closed:
@@ -1764,6 +1947,8 @@ class CSMBatcher:
 
     def step(self) -> bool:
         """One scheduling round; False when there was nothing to do (no live stream, empty queue, no listen round due)."""
+        if self._vad is not None:
+            self._vad_consume()  # (before the controls: a barge-in's interrupt is applied in the round that sees the onset)
         now = self._apply_controls()  # (before the admissions: a row a cancel has freed is refilled in this round)
         heard = self._enc is not None and self._listen_round()  # due listen rounds are work, with or without a live row
         while True:
@@ -1838,6 +2023,11 @@ class CSMBatcher:
             self._listeners = [None] * self.listen_rows
             for lis in listeners:
                 lis._open = False
+        self._vad_out.clear()
+        for lis in listeners:
+            for f in (lis.onset, lis.endpoint):
+                if f is not None:
+                    f.cancel()
         held = list(self._inflight)  # prefilled or being prefilled in a lane, not committed
         self._inflight.clear()
         self._lane_of = [None] * len(self._lane_of)
@@ -1857,7 +2047,7 @@ class CSMBatcher:
             self._dec.close()
         if self._enc is not None:
             self._enc.close()
-        for rs in (self._lrs, self._ors, self._crs, self._cvt):
+        for rs in (self._lrs, self._ors, self._crs, self._cvt, self._vad):
             if rs is not None:
                 rs.close()
         if self.overlap:

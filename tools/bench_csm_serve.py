@@ -32,7 +32,11 @@ profiles/csm_serve_interrupt_bench.json.
 clip in 80 ms slices, one slice per scheduling round, while the requests run, against the same workload with `listen_rows=0`: finished requests
 per second of both (untimed rounds), the scheduling round's time with and without a listen round in it (a second run, one sync around each
 round), and the time from `end()` to its result against `sess.hear(segment)` with the whole-clip `Mimi.encode`.  Written to
-profiles/csm_serve_listen_bench.json."""
+profiles/csm_serve_listen_bench.json.
+--listen K --vad: the same K listeners made with `vad=` over 5 s clips with a second of near-silence in front of and behind 3 s of
+noise speech, against the same clips heard by plain listeners: requests per second and the scheduling round's time of both, and the detector
+step's device time (events around `RowVad.step`) for 8 rows of 16 new 720-sample frames and for one 30 s clip, beside the time a float4 copy
+of the same bytes takes at the part's measured 6.29 TB/s.  Recorded in profiles/csm_vad_bench.json."""
 import argparse
 import json
 import os
@@ -66,10 +70,11 @@ ap.add_argument("--overlap", action="store_true", help="continuous batching with
 ap.add_argument("--lanes", type=int, default=1, help="prefill lanes of --overlap")
 ap.add_argument("--listen", type=int, default=0, help="listeners fed a 5 s clip in 80 ms slices beside the mixed workload, against none")
 ap.add_argument("--listen-chunk", type=int, default=6, help="listen_chunk_frames of --listen")
+ap.add_argument("--vad", action="store_true", help="with --listen: listeners with a voice-activity detector against plain ones, and the detector step's time")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 if a.out is None:
-    name = "csm_serve_listen_bench.json" if a.listen else "csm_serve_overlap_bench.json" if a.overlap else "csm_serve_session_bench.json" if a.sessions else "csm_serve_interrupt_bench.json" if a.abandon else "csm_serve_stream_bench.json" if a.stream_chunk else "csm_serve_prefix_bench.json" if a.prefix else "csm_serve_bench.json"
+    name = "csm_vad_bench.json" if a.listen and a.vad else "csm_serve_listen_bench.json" if a.listen else "csm_serve_overlap_bench.json" if a.overlap else "csm_serve_session_bench.json" if a.sessions else "csm_serve_interrupt_bench.json" if a.abandon else "csm_serve_stream_bench.json" if a.stream_chunk else "csm_serve_prefix_bench.json" if a.prefix else "csm_serve_bench.json"
     a.out = os.path.join(ROOT, "profiles", name)
 
 cfg = dict(P.csm_config(), max_seq_len=a.max_seq_len)
@@ -170,13 +175,17 @@ def bench_listen():
 
     K, spf = a.listen, 1920
     clips = [(0.3 * rng.standard_normal(5 * 24000)).astype(np.float32) for _ in range(K)]
+    if a.vad:  # a second of near-silence, 3 s of speech, a second of near-silence: the detector drops the first and ends within the last
+        for c in clips:
+            c[:24000] *= 0.01
+            c[4 * 24000 :] *= 0.01
     heard = rng.integers(0, cfg["text_vocab_size"], 12).tolist()
 
-    def run(k, timed):
+    def run(k, timed, vad=None):
         """The workload beside k listeners; timed: one sync around every scheduling round (its time booked by whether a listen round ran)."""
         bat = loop.serve(max_batch=B, rng="device", sampler=sampler, seed=a.seed, stop_on_eos=False, decode=False, listen_rows=k,
                          listen_chunk_frames=a.listen_chunk)
-        ls = [bat.session().listen(1) for _ in range(k)]
+        ls = [bat.session().listen(1, vad=vad) for _ in range(k)]
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         futs = [bat.submit(None, None, prompt=prompts[i], max_audio_length_ms=80 * flen[i]) for i in range(a.requests)]
@@ -232,6 +241,8 @@ def bench_listen():
         bat.close()
         return out[1:]  # (the first call sizes the workspace)
 
+    if a.vad:
+        return bench_vad(run)
     run(0, False), run(K, False)  # warm-up: kernel loading, workspaces, graph capture
     res = {"metric": "CSM-1B serving with live listeners (row-mode streaming Mimi encoder) vs without, " + a.weights, "requests": a.requests, "batch": B,
            "listeners": K, "listen_chunk_frames": a.listen_chunk, "clip_seconds": 5.0, "slice_ms": 80, "order": ["plain_first", "listening", "plain_last"],
@@ -243,6 +254,59 @@ def bench_listen():
     plain = [res["plain_first"]["requests_per_s"], res["plain_last"]["requests_per_s"]]
     res["value"] = res["listening"]["requests_per_s"] / (0.5 * sum(plain))
     res["value_is"] = "requests/s with listeners / without (without: mean of the two runs; they differ by %.3f)" % abs(plain[0] - plain[1])
+    return res
+
+
+def vad_step_us():
+    """Device time of one `RowVad.step` (events around it, so the launch is in it): 8 rows of 16 new 720-sample frames per step, and one
+    row's 30 s clip in one step.  Threshold 0: every frame is speech and no row ends."""
+    from mlx_audio_amd.vad import RowVad
+
+    fl, reps, out = 720, 60, {}
+    hbm = 6.29e12  # bytes/s of a float4 copy on the part (measured; the spec is 8 TB/s)
+
+    def series(rv, x, rows, new):
+        for b in range(rows):
+            rv.set_row(b, fl, 0.0, 50)
+        ev = []
+        for i in range(x.shape[1] // new):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            rv.step(x, [new * (i + 1)] * rows)
+            e1.record()
+            ev.append((e0, e1))
+        torch.cuda.synchronize()
+        return [1e3 * e0.elapsed_time(e1) for e0, e1 in ev]
+
+    for name, rows, new, steps in (("rows8_frames16", 8, 16 * fl, reps), ("one_clip_30s", 1, 30 * 24000, 1)):
+        rv = RowVad(rows)
+        x = (0.3 * torch.randn((rows, new * steps), device="cuda")).contiguous()
+        t = []
+        for _ in range(1 if steps > 1 else reps):
+            series(rv, x, rows, new)  # (warm, and for the clip: one step per series)
+            t += series(rv, x, rows, new)
+        nbytes = 4 * rows * new
+        out[name] = {"rows": rows, "new_frames_per_row": new // fl, "bytes_read": nbytes, "steps_timed": len(t), "median_us": float(np.median(t)),
+                     "min_us": float(np.min(t)), "max_us": float(np.max(t)), "float4_copy_us_at_6.29TBps": 1e6 * nbytes / hbm}
+        rv.close()
+    return out
+
+
+def bench_vad(run):
+    from mlx_audio_amd.vad import VadConfig
+
+    K, vcfg = a.listen, VadConfig(silence_ms=300)
+    run(K, False), run(K, False, vcfg)  # warm-up: kernel loading, workspaces, graph capture
+    res = {"metric": "CSM-1B serving, listeners with a voice-activity detector vs plain listeners, " + a.weights, "requests": a.requests, "batch": B,
+           "listeners": K, "listen_chunk_frames": a.listen_chunk, "clip_seconds": 5.0, "speech_seconds": [1.0, 4.0], "slice_ms": 80,
+           "vad_config": {"frame_ms": vcfg.frame_ms, "threshold": vcfg.threshold, "silence_ms": vcfg.silence_ms}, "order": ["plain_first", "vad", "plain_last"],
+           "data": "synthetic (random-init CSM-1B and mimi_202407 weights, random prompts, noise clips, imposed stream lengths, device uniforms)"}
+    res["plain_first"], res["vad"], res["plain_last"] = run(K, False), run(K, False, vcfg), run(K, False)
+    res["vad_timed"], res["plain_timed"] = run(K, True, vcfg), run(K, True)
+    res["vad_step_us"] = vad_step_us()
+    plain = [res["plain_first"]["requests_per_s"], res["plain_last"]["requests_per_s"]]
+    res["value"] = res["vad"]["requests_per_s"] / (0.5 * sum(plain))
+    res["value_is"] = "requests/s with VAD listeners / with plain listeners (plain: mean of the two runs; they differ by %.3f)" % abs(plain[0] - plain[1])
     return res
 
 
