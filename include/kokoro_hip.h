@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 12  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 13  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -45,7 +45,9 @@ extern "C" {
                                kk_resampler_block_outputs, kk_op_resample);
                             11: PCM wire formats at the resampler's edges and on their own (KK_PCM_*, kk_resampler_set_row_fmt, kk_resampler_step_fmt,
                                kk_pcm_convert_rows, kk_op_pcm_convert);
-                            12: row-mode voice-activity detector (kk_vad_create, kk_vad_destroy, kk_vad_set_row, kk_vad_step, kk_op_vad) */
+                            12: row-mode voice-activity detector (kk_vad_create, kk_vad_destroy, kk_vad_set_row, kk_vad_step, kk_op_vad);
+                            13: re-arming detector over a ring and row-table ring copies (kk_vad_ring_create, kk_vad_ring_destroy,
+                               kk_vad_ring_set_row, kk_vad_ring_step, kk_ring_write_rows, kk_ring_read_rows) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -418,6 +420,53 @@ void kk_vad_destroy(kk_vad* v);
 int kk_vad_set_row(kk_vad* v, void* stream, int row, int frame_len, float thr2n, int hang_frames);
 int kk_vad_step(kk_vad* v, void* stream, const float* x, long long ldx, const int32_t* n_avail, int32_t* status, float* energy, long long lde);
 int kk_op_vad(void* stream, const float* x, int n, int frame_len, float thr2n, int hang_frames, int32_t status_host[4], float* energy_or_null);
+
+/* =====================================================================================================================
+ * Re-arming voice-activity detector over a ring (ABI minor 13): a microphone that stays open.  The rule, the energy and its
+ * bits are kk_vad's; what differs is the coordinates and what happens behind an utterance.  A row's stream is numbered from 0 at
+ * kk_vad_ring_set_row, in 64-bit positions everywhere (launch tables, device state, status), and sample p lives at x[row][p % ring_len],
+ * frame_len <= ring_len <= ldx, so frame f = positions [f frame_len, (f + 1) frame_len) wraps at most once.  Only the address is taken
+ * modulo the ring: E is bit-equal to kk_op_vad on the same stream laid out flat.  Per row and in frame order,
+ *   speech:  speaking = 1, silent = 0, last_speech = f, onset = f if there was none
+ *   silence while speaking:  ++silent; silent > hang_frames closes the utterance at endpoint = f (flags 0)
+ *   otherwise, while speaking:  f - onset + 1 == max_frames closes it at endpoint = f with flags 1 ("forced")
+ *   closing appends {onset, last_speech, endpoint, flags} to the row's log and re-arms (speaking = silent = 0, onset = last_speech = -1);
+ *   the walk goes on with frame f + 1 in the same launch.  NaN energy reads as silence, inf as speech.
+ * The log is a device ring of KK_VAD_LOG = 8 records per row: record k (counted from 0 at set_row) lives at log[row][k % 8].  The step's
+ * acked[row] is the number of records the host has consumed; the walk stops in front of any frame while closed - acked == 8, and a later
+ * step resumes from the device's own `classified` (the caller keeps those frames in the ring until a status shows them classified).
+ *   kk_vad_ring_step: x [max_rows][ldx] fp32 on the device; n_avail and acked are HOST arrays [max_rows] of int64: the row's samples so far
+ *     and its consumed records.  status [max_rows][4] int64 on the DEVICE: {classified, closed, onset, last_speech}, the last two of the open
+ *     utterance, -1 for none; log [max_rows][8][4] int64 on the DEVICE.  Both are written by the rows that walked.  energy: NULL, or
+ *     [max_rows][lde] fp32 on the device, frame f's E at energy[row][f % lde].  A row takes part when n_avail gives a new whole frame or
+ *     acked has moved; a row without a set_row sits out and nothing of it is read.  One launch, one workgroup per row, no synchronisation.
+ * Refused on the host before any launch, with nothing changed: a row out of range, frame_len outside [1, 4096], ring_len < frame_len or
+ * > ldx, a negative hang_frames, max_frames < 1, a negative, infinite or NaN thr2n, an n_avail below the row's previous one, an n_avail -
+ * ring_len above the first position of the oldest frame not yet handed to a step (unseen samples would have been overwritten), an acked
+ * below its previous value or above the frames handed out before this step (a record takes a frame of its own).
+ * ===================================================================================================================== */
+#define KK_VAD_LOG 8
+typedef struct kk_vad_ring kk_vad_ring;
+int kk_vad_ring_create(int max_rows, kk_vad_ring** out);
+void kk_vad_ring_destroy(kk_vad_ring* v);
+int kk_vad_ring_set_row(kk_vad_ring* v, void* stream, int row, int frame_len, float thr2n, int hang_frames, long long max_frames, long long ring_len);
+int kk_vad_ring_step(kk_vad_ring* v, void* stream, const float* x, long long ldx, const int64_t* n_avail, const int64_t* acked, int64_t* status,
+                     int64_t* log, float* energy, long long lde);
+
+/* =====================================================================================================================
+ * Row-table ring copies (ABI minor 13): rows <= 64 rows in one launch, the table a launch argument.  pos, n and n_total are
+ * HOST arrays [rows]; src, ring and dst are fp32 on the device with pitches lds, ldr, ldd in floats; ring_len <= ldr is every row's ring.
+ *   kk_ring_write_rows: ring[b][(pos[b] + i) % ring_len] = src[b][i], i < n[b].  A row with n = 0 sits out.
+ *   kk_ring_read_rows:  dst[b][i] = ring[b][(pos[b] + i) % ring_len], i < n[b], and 0.0f for n[b] <= i < n_total[b].  A row with
+ *     n_total = 0 is not touched.
+ * 16-byte accesses where both sides are aligned and the run does not wrap, element by element otherwise: a copy either way.
+ * Refused on the host before any launch: rows outside [1, 64], n > ring_len, n > n_total, a negative count or position, a row longer than
+ * its pitch (n > lds, n_total > ldd, ring_len > ldr).  Neither entry synchronises.
+ * ===================================================================================================================== */
+int kk_ring_write_rows(void* stream, int rows, const float* src, long long lds, float* ring, long long ldr, long long ring_len, const int64_t* pos,
+                       const int32_t* n);
+int kk_ring_read_rows(void* stream, int rows, const float* ring, long long ldr, long long ring_len, float* dst, long long ldd, const int64_t* pos,
+                      const int32_t* n, const int32_t* n_total);
 
 /* =====================================================================================================================
  * CSM-1B frame generator (rows C1-C3): SesameModel.generate_frame, mlx_audio/tts/models/sesame/sesame.py:349-395, with the

@@ -189,6 +189,12 @@ SIGNATURES = {
     "kk_vad_set_row": (_i, [_vp, _vp, _i, _i, _f, _i]),
     "kk_vad_step": (_i, [_vp, _vp, _vp, C.c_longlong, _vp, _vp, _vp, C.c_longlong]),
     "kk_op_vad": (_i, [_vp, _vp, _i, _i, _f, _i, _vp, _vp]),
+    "kk_vad_ring_create": (_i, [_i, C.POINTER(_vp)]),
+    "kk_vad_ring_destroy": (None, [_vp]),
+    "kk_vad_ring_set_row": (_i, [_vp, _vp, _i, _i, _f, _i, C.c_longlong, C.c_longlong]),
+    "kk_vad_ring_step": (_i, [_vp, _vp, _vp, C.c_longlong, _vp, _vp, _vp, _vp, _vp, C.c_longlong]),
+    "kk_ring_write_rows": (_i, [_vp, _i, _vp, C.c_longlong, _vp, C.c_longlong, C.c_longlong, _vp, _vp]),
+    "kk_ring_read_rows": (_i, [_vp, _i, _vp, C.c_longlong, C.c_longlong, _vp, C.c_longlong, _vp, _vp, _vp]),
     "kk_mimi_debug_info": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "kk_mimi_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
     "kk_debug_set_op_wfrag": (None, [_vp]),
@@ -235,7 +241,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 12:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 13:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -79,7 +79,11 @@ round waits for it.  A VAD listener's encoder stream is heard[start:], nothing o
 steps below what the consumed status has made certain; at an endpoint (`lis.endpoint`) or at `end()` the span heard[start:stop] is final and
 the rest is encoded, zeros behind `stop`: codes, frames and steps are those of a plain listener fed heard[start:stop] and ended.  `lis.onset`
 resolves with the onset; with `barge_in` that round interrupts the session's turn through the controls of 8d-8.
-Without `vad=` nothing of this exists: no detector is made and a listen round is the launches it was."""
+Without `vad=` nothing of this exists: no detector is made and a listen round is the launches it was.
+
+Always-open microphones: `listen(vad=..., continuous=True)` (csm_continuous.py).  One listener yields utterance after
+utterance (`CSMUtterance`) from a ring on the device, a detector that re-arms behind every endpoint and a host queue that a silent microphone
+never fills.  Without `continuous=True` nothing of it exists."""
 from __future__ import annotations
 
 import queue
@@ -97,7 +101,9 @@ import torch
 
 from . import pcm as PCM
 from . import resample as RS
+from . import ring as RING
 from . import vad as VAD
+from .csm_continuous import ContinuousMixin, CSMContinuousListener, CSMUtterance  # noqa: F401
 
 
 @dataclass
@@ -151,6 +157,7 @@ class SpeechSpan:
     sample_rate: int = 0  # the listener's own rate
     rate_start: int = 0
     rate_stop: int = 0
+    forced: bool = False  # a continuous listener's utterance that the length limit closed, not the silence
 
 
 class CSMListener:
@@ -455,14 +462,19 @@ class CSMSession:
         self.turns.append((int(segment.speaker), segment.text, 0))
         self.pending, self.history = _cat(self.pending, f), _cat(self.history, f)
 
-    def listen(self, speaker: int = 0, sample_rate: Optional[int] = None, format: Optional[str] = None, vad=None, barge_in: bool = False) -> "CSMListener":
+    def listen(self, speaker: int = 0, sample_rate: Optional[int] = None, format: Optional[str] = None, vad=None, barge_in: bool = False,
+               continuous: bool = False):
         """`CSMBatcher.listen` for this conversation: another speaker's microphone.  Allowed while the session's own turn is queued or live
         (a barge-in); the turn enters the history at the listener's `end(text)`, which waits for that turn as `hear` does.
         vad (`vad.VadConfig`, or True for the defaults): the scheduler finds the utterance itself.  barge_in (needs vad): the
-        round that sees the speaker's onset interrupts this session's queued or live turn, which keeps what it has emitted."""
+        round that sees the speaker's onset interrupts this session's queued or live turn, which keeps what it has emitted.
+        continuous (needs vad): the microphone stays open and yields one `CSMUtterance` per utterance (`CSMContinuousListener`, DESIGN
+        8d-13); each `utt.end(text)` enters the history as `hear` would, and with barge_in EVERY onset interrupts the queued or live turn."""
         if self._closed:
             raise ValueError("listen: the session is closed")
         kw = {} if format is None else {"format": format}
+        if continuous:
+            kw["continuous"] = True
         if vad is not None and vad is not False:
             kw.update(vad=vad, barge_in=barge_in)
         elif barge_in:
@@ -712,6 +724,18 @@ class ModelEngine:
         """A row-mode voice-activity detector on the engine's device (vad.RowVad): set_row, step(x, n_avail), fetch, close."""
         return VAD.RowVad(max_rows, device=self.device)
 
+    def row_ring_vad(self, max_rows: int):
+        """The re-arming detector over a ring on the engine's device (vad.RingVad): set_row, step(x, n_avail, acked), fetch, close."""
+        return VAD.RingVad(max_rows, device=self.device)
+
+    def ring_write(self, src, ring, ring_len: int, pos, n) -> None:
+        """ring[b, (pos[b] + i) % ring_len] = src[b, i], i < n[b]: one launch for all rows (ring.write_rows)."""
+        RING.write_rows(src, ring, ring_len, pos, n)
+
+    def ring_read(self, ring, ring_len: int, dst, pos, n, n_total) -> None:
+        """dst[b, i] = ring[b, (pos[b] + i) % ring_len], i < n[b], zeros up to n_total[b]: one launch for all rows (ring.read_rows)."""
+        RING.read_rows(ring, ring_len, dst, pos, n, n_total)
+
     def pcm_converter(self):
         """The PCM converter of rows at the model's own rate on the engine's device (pcm.RowConverter): convert(x, in_formats, out_formats, n), close."""
         return PCM.RowConverter(device=self.device)
@@ -826,7 +850,7 @@ def _claim(fut: Future) -> bool:
     return not fut.done() and fut.set_running_or_notify_cancel()
 
 
-class CSMBatcher:
+class CSMBatcher(ContinuousMixin):
     def __init__(self, model, max_batch: int = 8, eos_check_interval: int = 8, rng: str = "device", sampler=None, seed: int = 0,
                  stop_on_eos: bool = True, decode: bool = True, profile: bool = False, engine=None, stream_chunk_frames: Optional[int] = None,
                  stream_max_frames: int = 1125, row_samplers: bool = False, overlap_admission: bool = False, prefill_lanes: int = 1,
@@ -913,6 +937,7 @@ class CSMBatcher:
         self._vad = None                       # voice activity: one detector row per encoder row, made with the first VAD listener
         self._vad_n = [0] * self.listen_rows   # per detector row: the n_avail of its last step (a row no step takes is handed the same again)
         self._vad_out: Deque[tuple] = deque()  # (ticket, {row: (listener, the `_n24` covered)}): status tables on their way to the host
+        self._cont_init()                      # always-open microphones: nothing is made before the first `listen(continuous=True)`
         dev = self.engine.device
         self._prev = torch.zeros((self.max_batch, self.engine.n_cb), dtype=torch.int32, device=dev)
         self._first_eos = torch.full((self.max_batch,), -1, dtype=torch.int64, device=dev)  # stream-local index of the first all-zero frame
@@ -925,7 +950,7 @@ class CSMBatcher:
         return CSMSession(self, context, speaker)
 
     def listen(self, speaker: int = 0, session: Optional[CSMSession] = None, sample_rate: Optional[int] = None,
-               format: Optional[str] = None, vad=None, barge_in: bool = False) -> CSMListener:
+               format: Optional[str] = None, vad=None, barge_in: bool = False, continuous: bool = False):
         """A microphone (`CSMListener`) on a free row of the batcher's streaming encoder; ValueError when all `listen_rows` are taken (or
         the batcher was made without any).  `session`: what `CSMSession.listen` passes.  `sample_rate`: the rate `feed` takes (None: the
         model's); ValueError for a rate the resampler does not take.  `format` (`pcm.FORMATS`; None or "f32": float32): what `feed` takes --
@@ -935,7 +960,11 @@ class CSMBatcher:
         `Future[int]`: the first kept sample); after `silence_ms` of silence `lis.endpoint` resolves with a `SpeechSpan` and later feeds are
         ignored; `end(text)` -- before or after the endpoint -- resolves with the `ListenResult` of a plain listener fed
         heard[speech_start:speech_stop] and ended, or fails with ValueError("no speech").  `barge_in` (a session's listener): the onset
-        interrupts the session's queued or live turn in the round that sees it."""
+        interrupts the session's queued or live turn in the round that sees it.
+        `continuous` (needs `vad`): the microphone stays open -> a `CSMContinuousListener`: one `CSMUtterance` per detected
+        utterance, each with its own `onset`, `endpoint` and `end(text)`, until `close()`."""
+        if continuous and (vad is None or vad is False):
+            raise ValueError("listen: continuous=True needs vad=")
         if self._enc is None:
             raise ValueError("listen needs a batcher made with listen_rows=K")
         sample_rate = self._rate(sample_rate, inward=True)
@@ -959,6 +988,9 @@ class CSMBatcher:
             free = [r for r in range(self.listen_rows) if self._listeners[r] is None]
             if not free:
                 raise ValueError(f"all {self.listen_rows} listen rows are taken")
+            if continuous:
+                lis = self._listeners[free[0]] = self._cont_listen(free[0], speaker, session, sample_rate, fmt, vad, barge_in)
+                return lis
             extra = {} if vad is None else {"vad": vad, "barge_in": barge_in}
             lis = self._listeners[free[0]] = CSMListener(self, free[0], speaker, session, sample_rate, fmt, **extra)
         return lis
@@ -1000,6 +1032,8 @@ class CSMBatcher:
         return full, tails, done
 
     def _listen_due(self) -> bool:
+        if self._cont_made and self._cont_due():
+            return True
         full, tails, done = self._listen_plan()
         if self._vad_out or any(lis is not None and lis._open and lis._vad_due() for lis in self._listeners):
             return True  # a status on its way to the host, or samples the detector has not seen, are work due
@@ -1949,8 +1983,12 @@ class CSMBatcher:
         """One scheduling round; False when there was nothing to do (no live stream, empty queue, no listen round due)."""
         if self._vad is not None:
             self._vad_consume()  # (before the controls: a barge-in's interrupt is applied in the round that sees the onset)
+        if self._cont_made:
+            self._cont_consume()  # (likewise: every onset of a barge-in microphone)
         now = self._apply_controls()  # (before the admissions: a row a cancel has freed is refilled in this round)
         heard = self._enc is not None and self._listen_round()  # due listen rounds are work, with or without a live row
+        if self._cont_made:
+            heard = self._cont_round() or heard
         while True:
             self._admit()  # (rows a poll has just freed are refilled in the same round)
             live = self._live()
@@ -2024,6 +2062,8 @@ class CSMBatcher:
             for lis in listeners:
                 lis._open = False
         self._vad_out.clear()
+        if self._cont_made:
+            self._cont_close(listeners)
         for lis in listeners:
             for f in (lis.onset, lis.endpoint):
                 if f is not None:

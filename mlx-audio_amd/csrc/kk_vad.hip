@@ -8,9 +8,30 @@
 // frame's samples alone, never on the step, the row or the neighbours.  Wave w takes new frames w, w + 4, ... of a batch of at most
 // VAD_BATCH frames and leaves E in LDS; behind the barrier one lane walks the batch in frame order through the state machine.
 // A NaN energy compares false and reads as silence.  The row's state stays on the device; the host mirrors the frame count with integers.
+// Below the flat detector: the same energy routine over a ring, with a state machine that re-arms behind every utterance (kk_vad_ring; ABI minor 13).
 #include "../../include/kokoro_hip.h"
 #include "kk_host.h"
 #include "kk_vad_host.h"
+#include "kk_vad_ring_host.h"
+
+static_assert(VAD_LOG == KK_VAD_LOG, "kk_vad_ring_host.h and kokoro_hip.h disagree");
+
+// The energy of one frame, by one wave: lane l runs fmaf from 0.0f over i = l, l + 64, ... ascending, then the xor butterfly over 32 ... 1.
+// The frame starts at xr[off]; RING: sample i lives at (off + i) modulo ring_len -- off < ring_len and frame_len <= ring_len, so one
+// conditional subtract -- and only the address differs from the flat form: the same values enter the same chain in the same order.
+template <bool RING>
+__device__ static inline float vad_frame_energy(const float* xr, long long off, int fl, long long ring_len, int lane) {
+  float acc = 0.f;
+  for (int i = lane; i < fl; i += 64) {
+    long long a = off + i;
+    if (RING && a >= ring_len) a -= ring_len;
+    const float v = xr[a];
+    acc = fmaf(v, v, acc);
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+  return acc;
+}
 
 struct VadRow {  // device state of one row
   int frame_len, hang;
@@ -45,11 +66,7 @@ __global__ __launch_bounds__(256) void vad_rows_kernel(VadRow* rows, VadSteps st
   for (int b0 = first; b0 < upto; b0 += VAD_BATCH) {
     const int nb = min(VAD_BATCH, upto - b0);
     for (int k = wave; k < nb; k += 4) {
-      const float* p = xr + (long long)(b0 + k) * fl;
-      float acc = 0.f;
-      for (int i = lane; i < fl; i += 64) acc = fmaf(p[i], p[i], acc);
-#pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+      const float acc = vad_frame_energy<false>(xr, (long long)(b0 + k) * fl, fl, 0, lane);
       if (lane == 0) e_s[k] = acc;
     }
     __syncthreads();
@@ -77,6 +94,95 @@ __global__ __launch_bounds__(256) void vad_rows_kernel(VadRow* rows, VadSteps st
     rows[row] = r;
     int32_t* s = status + row * 4;
     s[0] = r.classified, s[1] = r.onset, s[2] = r.last_speech, s[3] = r.endpoint;
+  }
+}
+
+// ---- the re-arming detector over a ring (ABI minor 13) -------------------------------------------------------------------
+// A row's stream is numbered from 0 at set_row in 64-bit positions; sample p lives at x[row][p % ring_len].  The state machine is the flat
+// one with the reset the reference's `while True` does behind an utterance: closing (silent > hang, or the utterance reaching max_frames:
+// flag 1, "forced") appends {onset, last_speech, endpoint, flags} to the row's log of VAD_LOG records and re-arms, and the walk goes on
+// with the next frame in the same launch.  The walking lane stops in front of any frame while closed - acked == VAD_LOG; a later step
+// resumes from the device's own `classified`.
+struct VadRingRow {
+  int frame_len, hang;
+  float thr2n;
+  int speaking;
+  long long max_frames, ring_len;
+  long long classified, closed, onset, last_speech;  // what status[row] shows; -1: no open utterance
+  long long silent;
+};
+
+struct VadRingSteps {
+  int64_t upto[VAD_MAX_ROWS];
+  int64_t acked[VAD_MAX_ROWS];
+};
+
+__global__ void vad_ring_set_row_kernel(VadRingRow* rows, int row, int frame_len, float thr2n, int hang, long long max_frames, long long ring_len) {
+  if (threadIdx.x != 0) return;
+  VadRingRow r;
+  r.frame_len = frame_len, r.hang = hang, r.thr2n = thr2n, r.speaking = 0, r.max_frames = max_frames, r.ring_len = ring_len;
+  r.classified = 0, r.closed = 0, r.onset = -1, r.last_speech = -1, r.silent = 0;
+  rows[row] = r;
+}
+
+__global__ __launch_bounds__(256) void vad_ring_rows_kernel(VadRingRow* rows, VadRingSteps steps, const float* x, long long ldx, int64_t* status,
+                                                            int64_t* log, float* energy, long long lde) {
+  __shared__ float e_s[VAD_BATCH];
+  __shared__ int walked_s[2];  // frames of the batch the walk classified, and whether it stopped in front of a full log
+  const int row = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const long long upto = steps.upto[row], acked = steps.acked[row];
+  if (upto < 0) return;  // a row that sits out: nothing of it is read
+  VadRingRow r = rows[row];
+  if (upto <= r.classified || r.closed - acked >= VAD_LOG) return;  // nothing new, or the log is still full: state and status stay
+  const int fl = r.frame_len;
+  const long long ring_len = r.ring_len;
+  const float* xr = x + row * ldx;
+  int64_t* lg = log + (long long)row * VAD_LOG * 4;
+  for (long long b0 = r.classified; b0 < upto; b0 += VAD_BATCH) {
+    const int nb = (int)min((long long)VAD_BATCH, upto - b0);
+    for (int k = wave; k < nb; k += 4) {
+      const long long off = ((b0 + k) * fl) % ring_len;  // the frame's first position in the ring; (b0 + k + 1) fl <= n_avail: no overflow
+      const float acc = vad_frame_energy<true>(xr, off, fl, ring_len, lane);
+      if (lane == 0) e_s[k] = acc;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int k = 0, stalled = 0;
+      for (; k < nb; ++k) {
+        if (r.closed - acked >= VAD_LOG) {
+          stalled = 1;
+          break;
+        }
+        const long long f = b0 + k;
+        int close = 0, flags = 0;
+        if (e_s[k] >= r.thr2n) {
+          r.speaking = 1, r.silent = 0, r.last_speech = f;
+          if (r.onset < 0) r.onset = f;
+        } else if (r.speaking && ++r.silent > r.hang) {
+          close = 1;
+        }
+        if (!close && r.speaking && f - r.onset + 1 == r.max_frames) close = 1, flags = 1;
+        if (close) {
+          int64_t* rec = lg + (r.closed % VAD_LOG) * 4;
+          rec[0] = r.onset, rec[1] = r.last_speech, rec[2] = f, rec[3] = flags;
+          ++r.closed;
+          r.speaking = 0, r.silent = 0, r.onset = -1, r.last_speech = -1;
+        }
+      }
+      r.classified = b0 + k;
+      walked_s[0] = k, walked_s[1] = stalled;
+    }
+    __syncthreads();
+    const int walked = walked_s[0], stalled = walked_s[1];
+    if (energy)
+      for (int k = tid; k < walked; k += 256) energy[row * lde + (b0 + k) % lde] = e_s[k];
+    __syncthreads();  // e_s and walked_s are written again by the next batch
+    if (stalled) break;
+  }
+  if (tid == 0) {
+    rows[row] = r;
+    int64_t* s = status + row * 4;
+    s[0] = r.classified, s[1] = r.closed, s[2] = r.onset, s[3] = r.last_speech;
   }
 }
 
@@ -153,4 +259,62 @@ extern "C" int kk_op_vad(void* stream, const float* x, int n, int frame_len, flo
   if (d_status) (void)hipFree(d_status);
   kk_vad_destroy(v);
   return rc;
+}
+
+struct kk_vad_ring {
+  VadRingHost host;
+  VadRingRow* d_rows = nullptr;
+};
+
+extern "C" void kk_vad_ring_destroy(kk_vad_ring* v) {
+  if (!v) return;
+  if (v->d_rows) (void)hipFree(v->d_rows);
+  delete v;
+}
+
+extern "C" int kk_vad_ring_create(int max_rows, kk_vad_ring** out) {
+  const char* who = "kk_vad_ring_create";
+  if (!out) return kk_failf("%s: null out", who);
+  *out = nullptr;
+  if (max_rows < 1 || max_rows > VAD_MAX_ROWS) return kk_failf("%s: max_rows %d is outside [1, %d]", who, max_rows, VAD_MAX_ROWS);
+  kk_vad_ring* v = new kk_vad_ring;
+  v->host.fail = kk_failf;
+  v->host.rows.resize(max_rows);
+  if (hipMalloc((void**)&v->d_rows, sizeof(VadRingRow) * max_rows) != hipSuccess) {
+    kk_vad_ring_destroy(v);
+    return kk_failf("%s: allocation failed", who);
+  }
+  *out = v;
+  return 0;
+}
+
+extern "C" int kk_vad_ring_set_row(kk_vad_ring* v, void* stream, int row, int frame_len, float thr2n, int hang_frames, long long max_frames,
+                                   long long ring_len) {
+  const char* who = "kk_vad_ring_set_row";
+  if (!v) return kk_failf("%s: null detector", who);
+  KK_TRY(v->host.check_set_row(who, row, frame_len, thr2n, hang_frames, max_frames, ring_len));
+  hipLaunchKernelGGL(vad_ring_set_row_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, v->d_rows, row, frame_len, thr2n, hang_frames, max_frames,
+                     ring_len);
+  KK_CHECK_LAUNCH();
+  v->host.set_row(row, frame_len, thr2n, hang_frames, max_frames, ring_len);
+  return 0;
+}
+
+extern "C" int kk_vad_ring_step(kk_vad_ring* v, void* stream, const float* x, long long ldx, const int64_t* n_avail, const int64_t* acked,
+                                int64_t* status, int64_t* log, float* energy, long long lde) {
+  const char* who = "kk_vad_ring_step";
+  if (!v) return kk_failf("%s: null detector", who);
+  VadRingPlan plan;
+  KK_TRY(v->host.plan_step(who, n_avail, acked, ldx, energy != nullptr, lde, &plan));
+  if (plan.rows_in > 0) {
+    if (!x || !status || !log) return kk_failf("%s: null x, status or log", who);
+    VadRingSteps steps;
+    memcpy(steps.upto, plan.upto, sizeof steps.upto);
+    memcpy(steps.acked, plan.acked, sizeof steps.acked);
+    hipLaunchKernelGGL(vad_ring_rows_kernel, dim3((unsigned)v->host.rows.size()), dim3(256), 0, (hipStream_t)stream, v->d_rows, steps, x, ldx, status,
+                       log, energy, lde);
+    KK_CHECK_LAUNCH();
+  }
+  v->host.commit_step(n_avail, acked, plan);
+  return 0;
 }

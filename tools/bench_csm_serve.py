@@ -36,7 +36,11 @@ profiles/csm_serve_listen_bench.json.
 --listen K --vad: the same K listeners made with `vad=` over 5 s clips with a second of near-silence in front of and behind 3 s of
 noise speech, against the same clips heard by plain listeners: requests per second and the scheduling round's time of both, and the detector
 step's device time (events around `RowVad.step`) for 8 rows of 16 new 720-sample frames and for one 30 s clip, beside the time a float4 copy
-of the same bytes takes at the part's measured 6.29 TB/s.  Recorded in profiles/csm_vad_bench.json."""
+of the same bytes takes at the part's measured 6.29 TB/s.  Recorded in profiles/csm_vad_bench.json.
+--listen K --vad --continuous: K always-open microphones, each fed three such clips back to back on ONE listener and each
+utterance ended with its transcript when its endpoint resolves, against the one-shot VAD listeners over one clip: requests per second, the
+scheduling round's time, the library calls per listen round of both, the time from `end()` to the result, and the device time of one ring
+detector step and of the two ring copies at a round's size.  Recorded in profiles/csm_continuous_bench.json."""
 import argparse
 import json
 import os
@@ -71,10 +75,11 @@ ap.add_argument("--lanes", type=int, default=1, help="prefill lanes of --overlap
 ap.add_argument("--listen", type=int, default=0, help="listeners fed a 5 s clip in 80 ms slices beside the mixed workload, against none")
 ap.add_argument("--listen-chunk", type=int, default=6, help="listen_chunk_frames of --listen")
 ap.add_argument("--vad", action="store_true", help="with --listen: listeners with a voice-activity detector against plain ones, and the detector step's time")
+ap.add_argument("--continuous", action="store_true", help="with --listen K --vad: always-open microphones fed three clips back to back, against one-shot VAD listeners")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 if a.out is None:
-    name = "csm_vad_bench.json" if a.listen and a.vad else "csm_serve_listen_bench.json" if a.listen else "csm_serve_overlap_bench.json" if a.overlap else "csm_serve_session_bench.json" if a.sessions else "csm_serve_interrupt_bench.json" if a.abandon else "csm_serve_stream_bench.json" if a.stream_chunk else "csm_serve_prefix_bench.json" if a.prefix else "csm_serve_bench.json"
+    name = "csm_continuous_bench.json" if a.listen and a.vad and a.continuous else "csm_vad_bench.json" if a.listen and a.vad else "csm_serve_listen_bench.json" if a.listen else "csm_serve_overlap_bench.json" if a.overlap else "csm_serve_session_bench.json" if a.sessions else "csm_serve_interrupt_bench.json" if a.abandon else "csm_serve_stream_bench.json" if a.stream_chunk else "csm_serve_prefix_bench.json" if a.prefix else "csm_serve_bench.json"
     a.out = os.path.join(ROOT, "profiles", name)
 
 cfg = dict(P.csm_config(), max_seq_len=a.max_seq_len)
@@ -241,6 +246,8 @@ def bench_listen():
         bat.close()
         return out[1:]  # (the first call sizes the workspace)
 
+    if a.vad and a.continuous:
+        return bench_continuous(run, clips, heard)
     if a.vad:
         return bench_vad(run)
     run(0, False), run(K, False)  # warm-up: kernel loading, workspaces, graph capture
@@ -290,6 +297,172 @@ def vad_step_us():
                      "min_us": float(np.min(t)), "max_us": float(np.max(t)), "float4_copy_us_at_6.29TBps": 1e6 * nbytes / hbm}
         rv.close()
     return out
+
+
+class Calls:
+    """Counts the library calls a listen round makes (each is one launch, the encoder step its own fixed series): patched at the classes."""
+
+    def __init__(self):
+        from mlx_audio_amd import mimi as MI, pcm as PC, resample as RSM, ring as RG, vad as VD
+
+        self.n, self._undo = {}, []
+        for owner, name in ((RSM.RowResampler, "step"), (PC.RowConverter, "convert"), (VD.RowVad, "step"), (VD.RingVad, "step"), (RG, "write_rows"),
+                            (RG, "read_rows"), (MI.MimiRowEncoder, "step")):
+            self._wrap(owner, name, f"{getattr(owner, '__name__', 'ring').split('.')[-1]}.{name}")
+
+    def _wrap(self, owner, name, key):
+        fn = getattr(owner, name)
+
+        def counted(*args, **kw):
+            self.n[key] = self.n.get(key, 0) + 1
+            return fn(*args, **kw)
+
+        setattr(owner, name, counted)
+        self._undo.append((owner, name, fn))
+
+    def close(self):
+        for owner, name, fn in self._undo:
+            setattr(owner, name, fn)
+        return dict(self.n)
+
+
+def ring_step_us():
+    """Device time (events around each call, so the launch is in it) of one `RingVad.step`, one `ring.write_rows` and one `ring.read_rows`
+    at a round's size: 8 rows, 16 new 720-sample frames per row and step, a ring of 30 s; the read is an encode step's 6 codec frames."""
+    from mlx_audio_amd import ring as RG
+    from mlx_audio_amd.vad import RingVad
+
+    fl, rows, new, reps, ring_len = 720, 8, 16 * 720, 60, 30 * 24000
+    x = (0.3 * torch.randn((rows, ring_len), device="cuda")).contiguous()
+    src = (0.3 * torch.randn((rows, new), device="cuda")).contiguous()
+    dst = torch.zeros((rows, 6 * 1920), device="cuda")
+    rv = RingVad(rows)
+    out = {}
+
+    def series(fn):
+        ev = []
+        for i in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn(i)
+            e1.record()
+            ev.append((e0, e1))
+        torch.cuda.synchronize()
+        return [1e3 * e0.elapsed_time(e1) for e0, e1 in ev]
+
+    def detector(i):
+        if i == 0:
+            for b in range(rows):
+                rv.set_row(b, fl, 0.0, 50, 1 << 40, ring_len)
+        rv.step(x, [new * (i + 1)] * rows, [0] * rows)
+
+    cases = (("ring_vad_step_rows8_frames16", detector, 4 * rows * new),
+             ("ring_write_rows8_11520", lambda i: RG.write_rows(src, x, ring_len, [new * i + 4 * b for b in range(rows)], [new] * rows), 8 * rows * new),
+             ("ring_read_rows8_11520", lambda i: RG.read_rows(x, ring_len, dst, [new * i + 3 * b for b in range(rows)], [6 * 1920 - 100] * rows, [6 * 1920] * rows),
+              8 * rows * 6 * 1920))
+    for name, fn, nbytes in cases:
+        series(fn)  # warm
+        t = series(fn)
+        out[name] = {"rows": rows, "bytes_moved": nbytes, "steps_timed": len(t), "median_us": float(np.median(t)), "min_us": float(np.min(t)),
+                     "max_us": float(np.max(t)), "float4_copy_us_at_6.29TBps": 1e6 * nbytes / 6.29e12}
+    rv.close()
+    return out
+
+
+def bench_continuous(run, clips, heard):
+    from mlx_audio_amd.vad import VadConfig
+
+    K, vcfg, spf, reps = a.listen, VadConfig(silence_ms=300), 1920, 3
+    streams = [np.concatenate([c] * reps) for c in clips]  # three utterances per microphone, back to back
+
+    def run_cont(timed):
+        """The workload beside K always-open microphones; every utterance is ended with its transcript once its endpoint has resolved."""
+        bat = loop.serve(max_batch=B, rng="device", sampler=sampler, seed=a.seed, stop_on_eos=False, decode=False, listen_rows=K,
+                         listen_chunk_frames=a.listen_chunk)
+        ls = [bat.session().listen(1, vad=vcfg, continuous=True) for _ in range(K)]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        futs = [bat.submit(None, None, prompt=prompts[i], max_audio_length_ms=80 * flen[i]) for i in range(a.requests)]
+        book = {True: [0, 0.0], False: [0, 0.0]}
+        fed, open_utts, ends, lat, done = 0, [], [], [], 0
+        while True:
+            if fed < streams[0].shape[0]:
+                for lis, c in zip(ls, streams):
+                    lis.feed(c[fed : fed + spf])
+                fed += spf
+                if fed >= streams[0].shape[0]:
+                    for lis in ls:
+                        lis.close()
+            before = (bat.stats["frames"], bat.stats.get("listen_rounds", 0))
+            if timed:
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+            more = bat.step()
+            if timed:
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t
+                if bat.stats["frames"] > before[0]:
+                    b = book[bat.stats.get("listen_rounds", 0) > before[1]]
+                    b[0], b[1] = b[0] + 1, b[1] + dt
+            for lis in ls:
+                while True:
+                    try:
+                        u = lis.next_utterance(0)
+                    except Exception:  # noqa: BLE001  (queue.Empty)
+                        break
+                    if u is None:
+                        break
+                    open_utts.append(u)
+            for u in [u for u in open_utts if u.endpoint.done()]:  # the speaker has stopped: the transcript arrives with the end
+                open_utts.remove(u)
+                ends.append((u.end(heard), time.perf_counter()))
+            for f, t_end in [e for e in ends if e[0].done()]:
+                ends.remove((f, t_end))
+                f.result(timeout=0)
+                lat.append(time.perf_counter() - t_end)
+                done += 1
+            if not more and not bat._queue and not ends and not open_utts and fed >= streams[0].shape[0]:
+                break
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        assert [f.result(timeout=0).frames for f in futs] == flen and done == reps * K, (done, reps * K)
+        st = dict(bat.stats)
+        bat.close()
+        r = {"wall_s": wall, "requests_per_s": a.requests / wall, "frame_steps": st["frames"], "listen_rounds": st.get("listen_rounds", 0),
+             "listen_frames": st.get("listen_frames", 0), "utterances": done,
+             "end_to_result_ms": {"mean": 1e3 * float(np.mean(lat)), "max": 1e3 * float(np.max(lat))}}
+        if timed:
+            r["round_ms"] = {"with_listen_round": 1e3 * book[True][1] / max(1, book[True][0]), "rounds_with": book[True][0],
+                             "without_listen_round": 1e3 * book[False][1] / max(1, book[False][0]), "rounds_without": book[False][0]}
+        return r
+
+    def counted(fn):
+        c = Calls()
+        try:
+            r = fn()
+        finally:
+            n = c.close()
+        r["library_calls"] = n
+        r["library_calls_per_listen_round"] = sum(n.values()) / max(1, r["listen_rounds"])
+        return r
+
+    run(K, False, vcfg), run_cont(False)  # warm-up: kernel loading, workspaces, graph capture
+    res = {"metric": "CSM-1B serving, always-open microphones (ring + re-arming detector) vs one-shot VAD listeners, " + a.weights, "requests": a.requests,
+           "batch": B, "listeners": K, "listen_chunk_frames": a.listen_chunk, "clip_seconds": 5.0, "clips_per_microphone": reps, "slice_ms": 80,
+           "vad_config": {"frame_ms": vcfg.frame_ms, "threshold": vcfg.threshold, "silence_ms": vcfg.silence_ms},
+           "order": ["vad_first", "continuous", "vad_last"],
+           "library_calls_note": "calls of RowResampler.step, RowConverter.convert, RowVad.step, RingVad.step, ring.write_rows, ring.read_rows and "
+                                 "MimiRowEncoder.step; the one-shot path's torch slice copies (one per listener and upload, one per listener and encode "
+                                 "step) are not among them, the continuous path has none",
+           "data": "synthetic (random-init CSM-1B and mimi_202407 weights, random prompts, noise clips, imposed stream lengths, device uniforms)"}
+    res["vad_first"], res["continuous"], res["vad_last"] = run(K, False, vcfg), run_cont(False), run(K, False, vcfg)
+    res["continuous_timed"], res["vad_timed"] = run_cont(True), run(K, True, vcfg)
+    res["continuous_counted"], res["vad_counted"] = counted(lambda: run_cont(False)), counted(lambda: run(K, False, vcfg))
+    res["ring_step_us"] = ring_step_us()
+    one = [res["vad_first"]["requests_per_s"], res["vad_last"]["requests_per_s"]]
+    res["value"] = res["continuous"]["requests_per_s"] / (0.5 * sum(one))
+    res["value_is"] = "requests/s with always-open microphones (3 utterances each) / with one-shot VAD listeners (1 utterance each; mean of the two runs; they differ by %.3f)" % abs(one[0] - one[1])
+    return res
 
 
 def bench_vad(run):
