@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 13  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 14  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -47,7 +47,9 @@ extern "C" {
                                kk_pcm_convert_rows, kk_op_pcm_convert);
                             12: row-mode voice-activity detector (kk_vad_create, kk_vad_destroy, kk_vad_set_row, kk_vad_step, kk_op_vad);
                             13: re-arming detector over a ring and row-table ring copies (kk_vad_ring_create, kk_vad_ring_destroy,
-                               kk_vad_ring_set_row, kk_vad_ring_step, kk_ring_write_rows, kk_ring_read_rows) */
+                               kk_vad_ring_set_row, kk_vad_ring_step, kk_ring_write_rows, kk_ring_read_rows);
+                            14: Whisper's audio side (kk_op_log_mel, kk_op_attention_long, kk_whisper_create, kk_whisper_destroy, kk_whisper_load_tensor,
+                               kk_whisper_finalize, kk_whisper_encode_workspace_bytes, kk_whisper_encode) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -709,6 +711,41 @@ int kk_op_csm_attn_single(void* stream, int form, int B, int H, int KV, int hd, 
 /* a block of S new positions per item: RoPE (q in place) + append at slots offset .. offset + S - 1, then causal attention -> out [B][S][H hd] */
 int kk_op_csm_attn_prompt(void* stream, int B, int S, int H, int KV, int hd, float* qkv, float* kc, float* vc, int max_pos, int offset, const float* rope,
                           const int32_t* pad, float* out);
+
+/* =====================================================================================================================
+ * Whisper, audio side: log_mel_spectrogram (mlx_audio/stt/models/whisper/audio.py:41-82) and AudioEncoder / Model.embed_audio
+ * (whisper.py:171-199, 295).  Device pointers unless stated, work enqueued on `stream`, no device-to-host synchronisation, 0 = OK.
+ * ===================================================================================================================== */
+/* audio.py:70-82 with stft and hanning of mlx_audio/utils.py:11-14: per row b of x [B][ldx] fp32 at 16 kHz with n[b] samples (n: device int32
+ * [B]; the caller has checked n[b] + padding >= 201): `padding` zeros appended, 200 samples of reflect padding at both ends, frames of 400 at hop 160
+ * under the symmetric Hann window, the 201-bin power spectrum, the last frame dropped (F[b] = (n[b] + padding) / 160 frames), the n_mels x 201
+ * filter bank, log10(max(., 1e-10)), max(., row maximum - 8), (. + 4) / 4.  window [400], cos_sin [2][400] (cos | sin of 2 pi j / 400) and
+ * fbT [201][n_mels] are the caller's fp32 tables, made in float64 on the host.  partial: scratch, B * F_rows floats.  out fp32 [B][F_rows][n_mels],
+ * rows past F[b] written as zeros.  n_mels 80 or 128.  A row's bits depend on that row's samples alone. */
+int kk_op_log_mel(void* stream, int B, const float* x, long long ldx, const int32_t* n, int padding, int n_mels, const float* window,
+                  const float* cos_sin, const float* fbT, float* partial, float* out, int F_rows);
+/* MultiHeadAttention.qkv_attention without a mask (whisper.py:123-137) for heads of 64 channels over a long sequence: qkv bf16 [B][T_rows][ld],
+ * q | k | v at channels 0, heads * 64 and 2 * heads * 64 (ld >= 3 * heads * 64, ld % 8 == 0); out bf16 [B][T_rows][ldo] (ldo >= heads * 64, ldo % 4 == 0).
+ * softmax(q k^T 64^-0.5) v over the first T rows (the reference's 64^-0.25 on each side is the same product); rows >= T are neither read as keys
+ * nor written.  An item's bits do not depend on B. */
+int kk_op_attention_long(void* stream, int B, const void* qkv, int ld, int T_rows, int T, int heads, void* out, int ldo);
+
+typedef struct kk_whisper kk_whisper;
+/* the audio fields of ModelDimensions (whisper.py:67-78); n_audio_state / n_audio_head must be 64, n_mels 80 or 128 */
+typedef struct kk_whisper_config {
+  int32_t n_mels, n_audio_ctx, n_audio_state, n_audio_head, n_audio_layer;
+} kk_whisper_config;
+int kk_whisper_create(const kk_whisper_config* cfg, kk_whisper** out);
+void kk_whisper_destroy(kk_whisper* m);
+/* encoder.* parameters by their MLX checkpoint names (whisper.py:171-187, 90-97, 140-155), host fp32, MLX layouts: conv weights [O][K][I],
+ * Linear weights [out][in].  attn.key has no bias. */
+int kk_whisper_load_tensor(kk_whisper* m, const char* name, const int64_t* shape, int ndim, const float* data);
+/* rounds every matrix to bf16 (nearest even), packs and uploads; makes the sinusoidal positions (whisper.py:81-87) in fp32.  Fails naming a
+ * missing or misshapen parameter.  Synchronises `stream`. */
+int kk_whisper_finalize(kk_whisper* m, void* stream);
+size_t kk_whisper_encode_workspace_bytes(const kk_whisper* m, int B);
+/* AudioEncoder.__call__ (whisper.py:189-199): mel fp32 [B][2 * n_audio_ctx][n_mels] -> out fp32 [B][n_audio_ctx][n_audio_state] */
+int kk_whisper_encode(kk_whisper* m, void* stream, int B, const float* mel, void* workspace, size_t workspace_bytes, float* out);
 
 #ifdef __cplusplus
 }

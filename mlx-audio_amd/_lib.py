@@ -40,6 +40,11 @@ class KKMimiConfig(C.Structure):
     ]
 
 
+class KKWhisperConfig(C.Structure):
+    _fields_ = [("n_mels", C.c_int32), ("n_audio_ctx", C.c_int32), ("n_audio_state", C.c_int32), ("n_audio_head", C.c_int32),
+                ("n_audio_layer", C.c_int32)]
+
+
 class KKLlamaArgs(C.Structure):
     _fields_ = [("num_layers", C.c_int32), ("num_heads", C.c_int32), ("num_kv_heads", C.c_int32), ("head_dim", C.c_int32),
                 ("hidden", C.c_int32), ("intermediate", C.c_int32), ("rope_theta", C.c_float), ("rope_factor", C.c_float), ("rms_eps", C.c_float)]
@@ -195,6 +200,14 @@ SIGNATURES = {
     "kk_vad_ring_step": (_i, [_vp, _vp, _vp, C.c_longlong, _vp, _vp, _vp, _vp, _vp, C.c_longlong]),
     "kk_ring_write_rows": (_i, [_vp, _i, _vp, C.c_longlong, _vp, C.c_longlong, C.c_longlong, _vp, _vp]),
     "kk_ring_read_rows": (_i, [_vp, _i, _vp, C.c_longlong, C.c_longlong, _vp, C.c_longlong, _vp, _vp, _vp]),
+    "kk_op_log_mel": (_i, [_vp, _i, _vp, C.c_longlong, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i]),
+    "kk_op_attention_long": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i]),
+    "kk_whisper_create": (_i, [C.POINTER(KKWhisperConfig), C.POINTER(_vp)]),
+    "kk_whisper_destroy": (None, [_vp]),
+    "kk_whisper_load_tensor": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), _i, _vp]),
+    "kk_whisper_finalize": (_i, [_vp, _vp]),
+    "kk_whisper_encode_workspace_bytes": (_sz, [_vp, _i]),
+    "kk_whisper_encode": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "kk_mimi_debug_info": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "kk_mimi_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
     "kk_debug_set_op_wfrag": (None, [_vp]),
@@ -241,7 +254,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 13:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 14:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -76,6 +76,10 @@ def load_model(model_path, lazy: bool = False, strict: bool = True, compute_dtyp
     else:
         raise ValueError(f"Invalid model path type: {type(model_path)}")
     config = load_config(path)
+    from . import whisper
+
+    if whisper.is_whisper_config(config):  # stt/models/whisper: weights.safetensors / weights.npz + the ten ModelDimensions in config.json
+        return whisper.load_model(path, kwargs.get("dtype"), **{k: v for k, v in kwargs.items() if k == "device"})
     model_type = config.get("model_type") or (model_name[0] if model_name else None)
     weight_files = glob.glob(str(path / "*.safetensors"))
     if not weight_files:

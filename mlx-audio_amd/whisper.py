@@ -1,0 +1,375 @@
+"""Host mirror of the AUDIO side of the reference's Whisper (mlx_audio/stt/models/whisper): the constants, `pad_or_trim` and
+`log_mel_spectrogram` of audio.py:12-82, `ModelDimensions`, and `Model` with `embed_audio` / `load_weights` / `from_pretrained`
+(whisper.py:67-78, 251-353).  The arithmetic runs in libkokoro_hip.so (kk_op_log_mel, kk_whisper_*, csrc/kk_whisper.hip); PyTorch
+allocates device memory and provides the stream.  The text decoder and everything of decoding.py are not built: `logits`, `decode`,
+`generate` and `detect_language` raise NotImplementedError, and the `decoder.*` tensors of a checkpoint are kept on the host untouched."""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import math
+from dataclasses import dataclass, fields
+from pathlib import Path
+from typing import Dict, Optional
+
+import numpy as np
+
+# hard-coded audio hyper-parameters (audio.py:12-21)
+SAMPLE_RATE = 16000
+N_FFT = 400
+HOP_LENGTH = 160
+CHUNK_LENGTH = 30
+N_SAMPLES = CHUNK_LENGTH * SAMPLE_RATE  # 480000 samples in a 30-second chunk
+N_FRAMES = N_SAMPLES // HOP_LENGTH  # 3000 frames in a mel spectrogram input
+N_SAMPLES_PER_TOKEN = HOP_LENGTH * 2  # the stem's second convolution has stride 2
+FRAMES_PER_SECOND = SAMPLE_RATE // HOP_LENGTH  # 10 ms per audio frame
+TOKENS_PER_SECOND = SAMPLE_RATE // N_SAMPLES_PER_TOKEN  # 20 ms per audio token
+
+_NOT_BUILT = "text decoder: not built"
+
+
+def _is_torch(a) -> bool:
+    return type(a).__module__.split(".")[0] == "torch"
+
+
+def pad_or_trim(array, length: int = N_SAMPLES, *, axis: int = -1):
+    """audio.py:24-38: cut `axis` at `length`, or append zeros up to it.  numpy arrays and torch tensors (any device) keep their kind."""
+    n = array.shape[axis]
+    if n > length:
+        sl = [slice(None)] * array.ndim
+        sl[axis] = slice(0, length)
+        array = array[tuple(sl)]
+    elif n < length:
+        ax = axis % array.ndim
+        if _is_torch(array):
+            import torch
+
+            shape = list(array.shape)
+            shape[ax] = length - n
+            array = torch.cat([array, torch.zeros(shape, dtype=array.dtype, device=array.device)], dim=ax)
+        else:
+            widths = [(0, 0)] * array.ndim
+            widths[ax] = (0, length - n)
+            array = np.pad(array, widths)
+    return array
+
+
+def _hz_to_mel(f: float) -> float:
+    """Slaney's scale: linear (200/3 Hz per mel) below 1 kHz, logarithmic (27 mels per factor 6.4) above."""
+    return 15.0 + 27.0 * math.log(f / 1000.0) / math.log(6.4) if f >= 1000.0 else 3.0 * f / 200.0
+
+
+def mel_filters(n_mels: int) -> np.ndarray:
+    """The (n_mels, 201) float64 filter bank the reference builds with mel_filters(16000, 400, n_mels, norm="slaney", mel_scale=None)
+    (audio.py:76; mlx_audio/utils.py:165-237, where a mel_scale other than "htk" takes the Slaney branch): triangles between n_mels + 2
+    points equally spaced on Slaney's scale from 0 to 8 kHz, each scaled by 2 / (its width in Hz)."""
+    freqs = np.linspace(0.0, SAMPLE_RATE // 2, N_FFT // 2 + 1)
+    mels = np.linspace(_hz_to_mel(0.0), _hz_to_mel(SAMPLE_RATE / 2), n_mels + 2)
+    pts = np.where(mels >= 15.0, 1000.0 * np.exp(math.log(6.4) / 27.0 * (mels - 15.0)), 200.0 / 3 * mels)
+    width = np.diff(pts)
+    rel = pts[None, :] - freqs[:, None]  # (201, n_mels + 2)
+    bank = np.maximum(0.0, np.minimum(-rel[:, :-2] / width[:-1], rel[:, 2:] / width[1:]))
+    bank = bank * (2.0 / (pts[2:] - pts[:-2]))[None, :]
+    return np.ascontiguousarray(bank.T)
+
+
+_tables: Dict[tuple, tuple] = {}
+
+
+def _logmel_tables(device, n_mels: int):
+    """window [400] (symmetric Hann, mlx_audio/utils.py:11-14), cos | sin [2][400] of 2 pi j / 400, bank transposed [201][n_mels]: float64 on the
+    host, fp32 on the device, once per (device, n_mels)."""
+    import torch
+
+    key = (str(device), n_mels)
+    if key not in _tables:
+        j = np.arange(N_FFT, dtype=np.float64)
+        window = 0.5 * (1.0 - np.cos(2.0 * np.pi * j / (N_FFT - 1)))
+        cs = np.stack([np.cos(2.0 * np.pi * j / N_FFT), np.sin(2.0 * np.pi * j / N_FFT)])
+        _tables[key] = tuple(torch.from_numpy(np.ascontiguousarray(t, dtype=np.float32)).to(device)
+                             for t in (window, cs, mel_filters(n_mels).T))
+    return _tables[key]
+
+
+def check_log_mel_lengths(lengths, padding: int) -> None:
+    """The reflect padding of the STFT needs 201 samples (mlx_audio/utils.py:82-84)."""
+    for n in lengths:
+        if n + padding < N_FFT // 2 + 1:
+            raise ValueError(f"log_mel_spectrogram: {n} samples + {padding} padding is shorter than the {N_FFT // 2 + 1} the reflect padding needs")
+
+
+def log_mel_spectrogram(audio, n_mels: int = 80, padding: int = 0, device: str = "cuda:0"):
+    """audio.py:41-82 on the device.  audio: a 1-D numpy array or torch tensor (CPU or device) of 16 kHz samples -> fp32 device tensor
+    (n_frames, n_mels), n_frames = (len + padding) // 160; or a list of them (a ragged batch, one launch) -> a list of such tensors."""
+    if n_mels not in (80, 128):
+        raise ValueError("n_mels must be 80 or 128")
+    if padding < 0:
+        raise ValueError("padding must be >= 0")
+    single = not isinstance(audio, (list, tuple))
+    clips = [audio] if single else list(audio)
+    if not clips:
+        return []
+    lengths = []
+    for a in clips:
+        if a.ndim != 1:
+            raise ValueError("log_mel_spectrogram takes 1-D audio")
+        lengths.append(int(a.shape[0]))
+    check_log_mel_lengths(lengths, padding)
+    import torch
+
+    for a in clips:
+        if _is_torch(a) and a.is_cuda:
+            device = a.device
+            break
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        B, ldx = len(clips), max(lengths)
+        if B == 1:
+            x = torch.as_tensor(clips[0]).to(device=dev, dtype=torch.float32).contiguous().view(1, -1)
+        else:
+            x = torch.zeros((B, ldx), dtype=torch.float32, device=dev)
+            for b, a in enumerate(clips):
+                x[b, : lengths[b]] = torch.as_tensor(a).to(device=dev, dtype=torch.float32)
+        out = log_mel_rows(x, lengths, n_mels, padding)
+    res = [out[b, : (lengths[b] + padding) // HOP_LENGTH] for b in range(B)]
+    return res[0] if single else res
+
+
+def log_mel_rows(x, lengths, n_mels: int = 80, padding: int = 0):
+    """The kernel call itself: x fp32 device [B][ldx] (row b holds lengths[b] samples; what lies behind them is never read) ->
+    fp32 [B][max frames][n_mels], rows past a clip's frame count zero."""
+    import torch
+
+    from . import _lib
+
+    lib = _lib.load()
+    check_log_mel_lengths(lengths, padding)
+    B, ldx = x.shape
+    if len(lengths) != B or max(lengths) > ldx or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("log_mel_rows: x must be contiguous fp32 [B][ldx] with lengths[b] <= ldx")
+    dev = x.device
+    with torch.cuda.device(dev):
+        window, cs, fbT = _logmel_tables(dev, n_mels)
+        F_rows = max((n + padding) // HOP_LENGTH for n in lengths)
+        n_dev = torch.tensor(lengths, dtype=torch.int32).to(dev)
+        partial = torch.empty((B, F_rows), dtype=torch.float32, device=dev)
+        out = torch.empty((B, F_rows, n_mels), dtype=torch.float32, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.kk_op_log_mel(st, B, C.c_void_p(x.data_ptr()), ldx, C.c_void_p(n_dev.data_ptr()), padding, n_mels,
+                                     C.c_void_p(window.data_ptr()), C.c_void_p(cs.data_ptr()), C.c_void_p(fbT.data_ptr()),
+                                     C.c_void_p(partial.data_ptr()), C.c_void_p(out.data_ptr()), F_rows), "kk_op_log_mel")
+    return out
+
+
+@dataclass
+class ModelDimensions:
+    """whisper.py:67-78."""
+    n_mels: int
+    n_audio_ctx: int
+    n_audio_state: int
+    n_audio_head: int
+    n_audio_layer: int
+    n_vocab: int
+    n_text_ctx: int
+    n_text_state: int
+    n_text_head: int
+    n_text_layer: int
+
+
+DIMENSION_KEYS = tuple(f.name for f in fields(ModelDimensions))
+
+
+def is_whisper_config(config: dict) -> bool:
+    return config.get("model_type") == "whisper" or all(k in config for k in DIMENSION_KEYS)
+
+
+def _as_f32(v) -> np.ndarray:
+    if _is_torch(v):
+        v = v.detach().float().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(v), dtype=np.float32)
+
+
+def encoder_shapes(dims: ModelDimensions) -> Dict[str, tuple]:
+    """name -> shape of every encoder parameter, by the MLX checkpoint's names and layouts (conv weights [O, K, I]); whisper.py:171-187."""
+    D, M = dims.n_audio_state, dims.n_mels
+    s = {"encoder.conv1.weight": (D, 3, M), "encoder.conv1.bias": (D,), "encoder.conv2.weight": (D, 3, D), "encoder.conv2.bias": (D,),
+         "encoder.ln_post.weight": (D,), "encoder.ln_post.bias": (D,)}
+    for i in range(dims.n_audio_layer):
+        p = f"encoder.blocks.{i}."
+        for lin in ("query", "value", "out"):
+            s[p + f"attn.{lin}.weight"] = (D, D)
+            s[p + f"attn.{lin}.bias"] = (D,)
+        s[p + "attn.key.weight"] = (D, D)  # no bias (whisper.py:95)
+        s[p + "mlp1.weight"], s[p + "mlp1.bias"] = (4 * D, D), (4 * D,)
+        s[p + "mlp2.weight"], s[p + "mlp2.bias"] = (D, 4 * D), (D,)
+        for ln in ("attn_ln", "mlp_ln"):
+            s[p + ln + ".weight"] = s[p + ln + ".bias"] = (D,)
+    return s
+
+
+def split_weights(dims: ModelDimensions, weights: dict):
+    """-> (encoder tensors as fp32 numpy in the MLX layouts, everything else untouched).  A conv weight in the PyTorch layout [O, I, K] is told
+    apart by its shape and transposed.  A missing or misshapen encoder tensor is a ValueError that names it."""
+    want = encoder_shapes(dims)
+    enc, rest = {}, {}
+    for k, v in weights.items():
+        if k in want:
+            enc[k] = v
+        elif k.startswith("encoder.") and k != "encoder._positional_embedding" and k != "encoder.positional_embedding":
+            raise ValueError(f"unexpected encoder tensor: {k}")
+        else:
+            rest[k] = v
+    out = {}
+    for k, shape in want.items():
+        if k not in enc:
+            raise ValueError(f"missing encoder tensor: {k}")
+        a = _as_f32(enc[k])
+        if len(shape) == 3 and a.shape != shape and a.shape == (shape[0], shape[2], shape[1]):
+            a = np.ascontiguousarray(a.transpose(0, 2, 1))  # [O, I, K] -> [O, K, I]
+        if a.shape != shape:
+            raise ValueError(f"encoder tensor {k} has shape {tuple(a.shape)}, expected {shape}")
+        out[k] = a
+    return out, rest
+
+
+class Model:
+    """whisper.py:251-353, audio side.  The weights are held as bf16 on the device (fp16 / fp32 checkpoints are rounded to nearest even)."""
+
+    def __init__(self, dims: ModelDimensions, dtype: str = "bfloat16", device: str = "cuda:0"):
+        if str(dtype).replace("torch.", "") != "bfloat16":
+            raise ValueError("the encoder runs on bf16 matrix cores: dtype must be 'bfloat16' (an f16 mode is not built)")
+        self.dims = dims
+        self.dtype = "bfloat16"
+        self.device_name = device
+        self.decoder_weights: Dict[str, object] = {}
+        self._h = None
+        self._ws = None
+        self._lib = None
+
+    # ---- weights ---------------------------------------------------------------------------------------------------------------------
+    def load_weights(self, weights: dict) -> "Model":
+        enc, rest = split_weights(self.dims, weights)
+        self.decoder_weights = rest  # decoder.* (and alignment data): kept for the text side, not touched
+        import torch
+
+        from . import _lib
+
+        lib = self._lib = _lib.load()
+        if not torch.cuda.is_available():
+            raise _lib.KokoroHipError("whisper.Model needs a GPU: the encoder has no CPU fallback")
+        self.device = torch.device(self.device_name)
+        kc = _lib.KKWhisperConfig()
+        for k in ("n_mels", "n_audio_ctx", "n_audio_state", "n_audio_head", "n_audio_layer"):
+            setattr(kc, k, int(getattr(self.dims, k)))
+        self._release()
+        h = C.c_void_p()
+        _lib.check(lib.kk_whisper_create(C.byref(kc), C.byref(h)), "kk_whisper_create")
+        self._h = h
+        with torch.cuda.device(self.device):
+            for name, a in enc.items():
+                shp = (C.c_int64 * a.ndim)(*a.shape)
+                _lib.check(lib.kk_whisper_load_tensor(h, name.encode(), shp, a.ndim, a.ctypes.data_as(C.c_void_p)), "kk_whisper_load_tensor")
+            _lib.check(lib.kk_whisper_finalize(h, self._stream()), "kk_whisper_finalize")
+        return self
+
+    @classmethod
+    def from_pretrained(cls, path: str, dtype: str = "bfloat16", device: str = "cuda:0") -> "Model":
+        """whisper.py:320-353 for a LOCAL directory: config.json + weights.safetensors or weights.npz.  Never goes to the network."""
+        model_path = Path(path)
+        if not model_path.is_dir():
+            raise FileNotFoundError(f"{path} is not a local directory (checkpoints are not downloaded)")
+        with open(model_path / "config.json", encoding="utf-8") as f:
+            config = json.load(f)
+        dims = dimensions_from_config(config)
+        wf = model_path / "weights.safetensors"
+        if wf.exists():
+            from safetensors import safe_open
+
+            weights = {}
+            with safe_open(str(wf), framework="pt") as f:
+                for k in f.keys():
+                    weights[k] = f.get_tensor(k)
+        else:
+            wf = model_path / "weights.npz"
+            if not wf.exists():
+                raise FileNotFoundError(f"no weights.safetensors or weights.npz in {path}")
+            with np.load(str(wf)) as z:
+                weights = {k: z[k] for k in z.files}
+        return cls(dims, dtype, device).load_weights(weights)
+
+    # ---- the encoder -----------------------------------------------------------------------------------------------------------------
+    def embed_audio(self, mel):
+        """whisper.py:295 -> AudioEncoder.__call__: mel (2 * n_audio_ctx, n_mels) or (B, 2 * n_audio_ctx, n_mels) -> fp32 device tensor
+        (n_audio_ctx, n_audio_state) or (B, ...)."""
+        d = self.dims
+        shape = tuple(mel.shape)
+        assert len(shape) in (2, 3) and shape[-2:] == (2 * d.n_audio_ctx, d.n_mels), "incorrect audio shape"
+        if self._h is None:
+            raise RuntimeError("whisper.Model.embed_audio: load_weights first")
+        import torch
+
+        from . import _lib
+
+        lib = self._lib
+        x = torch.as_tensor(mel).to(device=self.device, dtype=torch.float32).contiguous()
+        B = 1 if x.ndim == 2 else x.shape[0]
+        with torch.cuda.device(self.device):
+            need = int(lib.kk_whisper_encode_workspace_bytes(self._h, B))
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            out = torch.empty((B, d.n_audio_ctx, d.n_audio_state), dtype=torch.float32, device=self.device)
+            _lib.check(lib.kk_whisper_encode(self._h, self._stream(), B, C.c_void_p(x.data_ptr()), C.c_void_p(self._ws.data_ptr()), need,
+                                             C.c_void_p(out.data_ptr())), "kk_whisper_encode")
+        return out[0] if x.ndim == 2 else out
+
+    # ---- the text side: not built ----------------------------------------------------------------------------------------------------
+    def logits(self, *a, **kw):
+        raise NotImplementedError(_NOT_BUILT)
+
+    def decode(self, *a, **kw):
+        raise NotImplementedError(_NOT_BUILT)
+
+    def generate(self, *a, **kw):
+        raise NotImplementedError(_NOT_BUILT)
+
+    def detect_language(self, *a, **kw):
+        raise NotImplementedError(_NOT_BUILT)
+
+    @property
+    def is_multilingual(self) -> bool:
+        return self.dims.n_vocab >= 51865
+
+    @property
+    def num_languages(self) -> int:
+        return self.dims.n_vocab - 51765 - int(self.is_multilingual)
+
+    def _stream(self):
+        import torch
+
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _release(self):
+        if getattr(self, "_h", None) is not None and self._lib is not None:
+            self._lib.kk_whisper_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+
+def dimensions_from_config(config: dict) -> ModelDimensions:
+    """whisper.py:329-334.  A quantised checkpoint is refused: its Linears would need the packed kernels the text side will bring."""
+    if config.get("quantization") is not None:
+        raise ValueError("quantised Whisper checkpoints are not supported yet")
+    missing = [k for k in DIMENSION_KEYS if k not in config]
+    if missing:
+        raise ValueError(f"config.json lacks the Whisper dimensions {missing}")
+    return ModelDimensions(**{k: int(config[k]) for k in DIMENSION_KEYS})
+
+
+def load_model(model_path, dtype: Optional[str] = None, **kwargs) -> Model:
+    """What utils.load_model routes a Whisper checkpoint to."""
+    return Model.from_pretrained(str(model_path), dtype or "bfloat16", **{k: v for k, v in kwargs.items() if k == "device"})
