@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 14  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 15  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -49,7 +49,9 @@ extern "C" {
                             13: re-arming detector over a ring and row-table ring copies (kk_vad_ring_create, kk_vad_ring_destroy,
                                kk_vad_ring_set_row, kk_vad_ring_step, kk_ring_write_rows, kk_ring_read_rows);
                             14: Whisper's audio side (kk_op_log_mel, kk_op_attention_long, kk_whisper_create, kk_whisper_destroy, kk_whisper_load_tensor,
-                               kk_whisper_finalize, kk_whisper_encode_workspace_bytes, kk_whisper_encode) */
+                               kk_whisper_finalize, kk_whisper_encode_workspace_bytes, kk_whisper_encode);
+                            15: Whisper's text side (kk_op_whisper_attn_rows, kk_op_whisper_linear_rows, kk_op_whisper_embed, kk_op_whisper_pick,
+                               kk_op_whisper_pick_reset, kk_whisper_text_*) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -746,6 +748,86 @@ int kk_whisper_finalize(kk_whisper* m, void* stream);
 size_t kk_whisper_encode_workspace_bytes(const kk_whisper* m, int B);
 /* AudioEncoder.__call__ (whisper.py:189-199): mel fp32 [B][2 * n_audio_ctx][n_mels] -> out fp32 [B][n_audio_ctx][n_audio_state] */
 int kk_whisper_encode(kk_whisper* m, void* stream, int B, const float* mel, void* workspace, size_t workspace_bytes, float* out);
+
+/* =====================================================================================================================
+ * Whisper, text side: TextDecoder (whisper.py:202-248) and the token selection of decoding.py:255-395 (csrc/kk_whisper_text.hip).
+ * Device pointers unless stated, work enqueued on `stream`, 0 = OK.  A row's bits never depend on how many rows a call carries or on what
+ * the other rows hold.
+ * ===================================================================================================================== */
+/* One query row per r against a bf16 K/V store, heads of 64 channels: q fp32 [R][heads * 64]; kv bf16 [items][T_rows][ld] with the keys at
+ * channel k_off and the values at v_off (multiples of 8, like ld); row r attends to the first len[r] keys of item item[r] (device int32 [R]);
+ * out fp32 [R][heads * 64] = softmax(q k^T 64^-0.5) v in fp32.  Keys at or past len[r] and rows >= T_rows are not read.  scratch:
+ * kk_op_whisper_attn_rows_scratch_bytes(R, heads, T_rows), 16-byte aligned.  This entry reads item / len back (it synchronises `stream`) and refuses
+ * item[r] outside [0, items) and len[r] outside [1, T_rows]. */
+size_t kk_op_whisper_attn_rows_scratch_bytes(int R, int heads, int T_rows);
+int kk_op_whisper_attn_rows(void* stream, int R, int heads, const float* q, const void* kv, int k_off, int v_off, int items, int T_rows, int ld,
+                            const int32_t* item, const int32_t* len, float* out, void* scratch, size_t scratch_bytes);
+/* out[m] = act(x[m] W^T + bias) (+ res[m]) for 1 <= M <= 16 rows on the bf16 matrix cores: x fp32 [M][ldx] (rounded to bf16, nearest even), W bf16
+ * [N][K] dense (K % 32 == 0, any N), bias fp32 [N] or null, act 0 (none) or 2 (exact GELU), res fp32 [M][ldr] or null.  The result goes to out
+ * (fp32 [M][ldo], or null) and / or, rounded to bf16, to row rows_bf16[m] (device int32 [M]; null: row m) of out_bf16 [nrows_bf16][ld_bf16]; a row
+ * index outside the store is skipped.  Every weight byte is read once per call. */
+int kk_op_whisper_linear_rows(void* stream, int M, int N, int K, const float* x, long long ldx, const void* w, const float* bias, int act,
+                              const float* res, long long ldr, float* out, long long ldo, void* out_bf16, long long ld_bf16, const int32_t* rows_bf16,
+                              int nrows_bf16);
+/* out[r] = table[clamp(tok[r])] + positions[clamp(pos[r])]: table bf16 [n_vocab][D], positions fp32 [n_ctx][D], out fp32 [R][D] */
+int kk_op_whisper_embed(void* stream, int R, int D, const int32_t* tok, const int32_t* pos, const void* table_bf16, int n_vocab, const float* positions,
+                        int n_ctx, float* out);
+/* the token selection of one decode step (decoding.py:302-395 then :260-278 at temperature 0), one launch, no host round trip */
+typedef struct kk_whisper_pick_params {
+  int32_t n_vocab, eot, blank;           /* blank: the token of " " (220), masked with eot at the first sampled position when suppress_blank */
+  int32_t no_timestamps, timestamp_begin;
+  int32_t max_initial_timestamp_index;   /* < 0: none */
+  int32_t without_timestamps, suppress_blank;
+} kk_whisper_pick_params;
+typedef struct kk_whisper_pick_state {   /* one per row */
+  int32_t last, penultimate;             /* the last two sampled tokens, -1 = none yet */
+  int32_t last_timestamp;                /* the last sampled token >= timestamp_begin, -1 = none */
+  int32_t ended, count;                  /* eot was sampled; tokens sampled so far */
+  float sum_logprob, last_logprob;
+  int32_t reserved;
+} kk_whisper_pick_state;
+/* logits fp32 [B][ldl]; params: ONE device struct; suppress: device bitmask over n_vocab (bit i of word i / 32) or null; state: device [B];
+ * tokens: device int32 [B][cap], the chosen token is appended at state.count; next: device int32 [B], the chosen tokens; not_ended: device
+ * int32 counter of rows that have not sampled eot (kk_op_whisper_pick_reset sets it to B).  An ended row emits eot and keeps its sum. */
+int kk_op_whisper_pick(void* stream, int B, const float* logits, long long ldl, const kk_whisper_pick_params* params, const uint32_t* suppress,
+                       kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next, int32_t* not_ended);
+int kk_op_whisper_pick_reset(void* stream, int B, kk_whisper_pick_state* state, int32_t* not_ended);
+
+typedef struct kk_whisper_text kk_whisper_text;
+/* the text fields of ModelDimensions plus the audio side's output shape; n_text_state / n_text_head must be 64, n_text_state a multiple of 128 and
+ * at most 2048, n_audio_state == n_text_state */
+typedef struct kk_whisper_text_config {
+  int32_t n_vocab, n_text_ctx, n_text_state, n_text_head, n_text_layer, n_audio_ctx, n_audio_state;
+} kk_whisper_text_config;
+int kk_whisper_text_create(const kk_whisper_text_config* cfg, kk_whisper_text** out);
+void kk_whisper_text_destroy(kk_whisper_text* m);
+/* decoder.* parameters by their MLX checkpoint names, host fp32, Linear weights [out][in]; the keys have no bias */
+int kk_whisper_text_load_tensor(kk_whisper_text* m, const char* name, const int64_t* shape, int ndim, const float* data);
+/* rounds every matrix to bf16 (nearest even), one at a time, into ONE device copy (the token embedding serves the gather and the logits); the
+ * learned positions, biases and LayerNorm parameters stay fp32.  Fails naming a missing or misshapen parameter.  Synchronises `stream`. */
+int kk_whisper_text_finalize(kk_whisper_text* m, void* stream);
+/* the caller's memory: one persistent state buffer per batch (cross and self K/V in bf16, the pick state and token buffers) and a workspace per call */
+size_t kk_whisper_text_state_bytes(const kk_whisper_text* m, int B);
+size_t kk_whisper_text_workspace_bytes(const kk_whisper_text* m, int B, int S);
+/* a new window: audio_features fp32 [B][n_audio_ctx][n_audio_state] rounded to bf16 once, every layer's cross K and V computed once (whisper.py:114-116)
+ * into `state`, the rows' position set to 0.  `state` must stay alive and untouched until the next set_audio.  workspace: ..._workspace_bytes(m, B, 1) */
+int kk_whisper_text_set_audio(kk_whisper_text* m, void* stream, int B, const float* audio_features, void* state, size_t state_bytes, void* workspace,
+                              size_t workspace_bytes);
+/* TextDecoder.__call__ on S tokens per row at the rows' position: tokens device int32 [B][S] (null with S = 1: the tokens of the last pick); the self
+ * K/V of the new positions are appended, the position advances by S.  logits_out fp32 [B][S][n_vocab] (all_positions) or [B][n_vocab] (the last
+ * position only); it must stay alive until the pick that follows.  More than n_text_ctx positions is an error.  Never synchronises. */
+int kk_whisper_text_forward(kk_whisper_text* m, void* stream, int B, int S, const int32_t* tokens, float* logits_out, int all_positions, void* workspace,
+                            size_t workspace_bytes);
+int kk_whisper_text_position(const kk_whisper_text* m);  /* positions consumed since set_audio, -1 before it */
+/* back to an earlier position of the same window (0: a new sequence on the cross K/V set_audio made) */
+int kk_whisper_text_rewind(kk_whisper_text* m, int position);
+/* params (HOST) and the suppress bitmask (HOST, (n_vocab + 31) / 32 words, or null) are copied into the state buffer and the rows' pick state is
+ * reset; synchronises.  pick runs kk_op_whisper_pick on the last forward's last-position logits; never synchronises. */
+int kk_whisper_text_pick_setup(kk_whisper_text* m, void* stream, const kk_whisper_pick_params* params, const uint32_t* suppress);
+int kk_whisper_text_pick(kk_whisper_text* m, void* stream);
+/* read back (HOST destinations, synchronise): the count of rows not ended; the token buffers [B][cap] and the rows' states [B] */
+int kk_whisper_text_not_ended(kk_whisper_text* m, void* stream, int32_t* out);
+int kk_whisper_text_read(kk_whisper_text* m, void* stream, int32_t* tokens, int cap, kk_whisper_pick_state* rows);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,21 @@ class KKWhisperConfig(C.Structure):
                 ("n_audio_layer", C.c_int32)]
 
 
+class KKWhisperTextConfig(C.Structure):
+    _fields_ = [("n_vocab", C.c_int32), ("n_text_ctx", C.c_int32), ("n_text_state", C.c_int32), ("n_text_head", C.c_int32),
+                ("n_text_layer", C.c_int32), ("n_audio_ctx", C.c_int32), ("n_audio_state", C.c_int32)]
+
+
+class KKWhisperPickParams(C.Structure):  # kk_whisper_pick_params
+    _fields_ = [("n_vocab", C.c_int32), ("eot", C.c_int32), ("blank", C.c_int32), ("no_timestamps", C.c_int32), ("timestamp_begin", C.c_int32),
+                ("max_initial_timestamp_index", C.c_int32), ("without_timestamps", C.c_int32), ("suppress_blank", C.c_int32)]
+
+
+class KKWhisperPickState(C.Structure):  # kk_whisper_pick_state
+    _fields_ = [("last", C.c_int32), ("penultimate", C.c_int32), ("last_timestamp", C.c_int32), ("ended", C.c_int32), ("count", C.c_int32),
+                ("sum_logprob", C.c_float), ("last_logprob", C.c_float), ("reserved", C.c_int32)]
+
+
 class KKLlamaArgs(C.Structure):
     _fields_ = [("num_layers", C.c_int32), ("num_heads", C.c_int32), ("num_kv_heads", C.c_int32), ("head_dim", C.c_int32),
                 ("hidden", C.c_int32), ("intermediate", C.c_int32), ("rope_theta", C.c_float), ("rope_factor", C.c_float), ("rms_eps", C.c_float)]
@@ -208,6 +223,26 @@ SIGNATURES = {
     "kk_whisper_finalize": (_i, [_vp, _vp]),
     "kk_whisper_encode_workspace_bytes": (_sz, [_vp, _i]),
     "kk_whisper_encode": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "kk_op_whisper_attn_rows_scratch_bytes": (_sz, [_i, _i, _i]),
+    "kk_op_whisper_attn_rows": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz]),
+    "kk_op_whisper_linear_rows": (_i, [_vp, _i, _i, _i, _vp, C.c_longlong, _vp, _vp, _i, _vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong, _vp, _i]),
+    "kk_op_whisper_embed": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
+    "kk_op_whisper_pick": (_i, [_vp, _i, _vp, C.c_longlong, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "kk_op_whisper_pick_reset": (_i, [_vp, _i, _vp, _vp]),
+    "kk_whisper_text_create": (_i, [C.POINTER(KKWhisperTextConfig), C.POINTER(_vp)]),
+    "kk_whisper_text_destroy": (None, [_vp]),
+    "kk_whisper_text_load_tensor": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), _i, _vp]),
+    "kk_whisper_text_finalize": (_i, [_vp, _vp]),
+    "kk_whisper_text_state_bytes": (_sz, [_vp, _i]),
+    "kk_whisper_text_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "kk_whisper_text_set_audio": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _sz]),
+    "kk_whisper_text_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _sz]),
+    "kk_whisper_text_position": (_i, [_vp]),
+    "kk_whisper_text_rewind": (_i, [_vp, _i]),
+    "kk_whisper_text_pick_setup": (_i, [_vp, _vp, C.POINTER(KKWhisperPickParams), _vp]),
+    "kk_whisper_text_pick": (_i, [_vp, _vp]),
+    "kk_whisper_text_not_ended": (_i, [_vp, _vp, C.POINTER(C.c_int32)]),
+    "kk_whisper_text_read": (_i, [_vp, _vp, _vp, _i, _vp]),
     "kk_mimi_debug_info": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "kk_mimi_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
     "kk_debug_set_op_wfrag": (None, [_vp]),
@@ -254,7 +289,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 14:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 15:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

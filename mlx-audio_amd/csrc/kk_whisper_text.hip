@@ -1,0 +1,854 @@
+// Whisper, text side (gfx950): the decode-step kernels and the text decoder behind a handle.  Restates TextDecoder
+// (mlx_audio/stt/models/whisper/whisper.py:202-248, blocks :140-168, attention :90-137) and the token selection of decoding.py:255-395; DESIGN 8g.
+//
+// The invariant of every kernel here: a row's bits depend on that row's inputs alone -- not on how many rows a call carries, not on what the
+// other rows hold.  Reduction orders are fixed, split results are merged in index order by a second launch, no floating-point atomics.
+//
+// ---- attn_rows: one query row against a bf16 K/V store -------------------------------------------------------------------------------------
+//   grid (split, head, row), one wave per workgroup.  Lane (kg = lane >> 3, ch = lane & 7) owns channels 8 ch .. 8 ch + 7 of the keys
+//   k0 + 8 j + kg, j = 0 .. 7, of a 64-key tile: eight lanes read one key's 128 contiguous bytes, a load instruction covers 8 whole rows, and
+//   K / V go straight to registers (nothing is shared between waves, so LDS would be a detour).  The score is the lane's 8-term dot, summed over
+//   the 8 lanes of the key by xor-butterflies (1, 2, 4: every lane ends with the same bits); the probability of a key lives in the very lanes
+//   that hold the key's V chunk, so P V is a per-lane fma and the 8 key groups are summed once, at the end (xor 8, 16, 32).  Running maximum and
+//   sum in fp32 in the log2 domain (scale 64^-0.5 and log2 e in one multiply after the dot, v_exp_f32).  A split covers ATTN_SPLIT keys; the
+//   number of splits is a function of T_rows alone.  Keys >= len[r] are not read (a tile is cut at len, the lanes past it load nothing).
+//   attn_merge: per (head, row), thread d combines the splits' (max, sum, acc[d]) in index order.
+//
+// ---- linear_rows: out[m] = act(x[m] W^T + bias) (+ res[m]), 1 <= M <= 16, W bf16 [N][K] dense ------------------------------------------------
+//   v_mfma_f32_16x16x32_bf16 with A = x (the M rows are the 16-row side; rows >= M are zero fragments) and B = W: lane (lr, g) of B holds
+//   W[n0 + lr][32 ks + 8 g .. + 7], which in row-major [N][K] is one 16-byte load -- the dense matrix IS the fragment order along k, so the
+//   same copy serves this kernel, the bf16 MFMA convolution kernel (set_audio's K / V projections) and the embedding gather.  One workgroup
+//   owns 16 output columns and reads their 16 x K weights exactly once for all M rows; its 16 waves take the k-steps ks = wave, wave + 16, ...
+//   (together they read whole 1 KiB stretches of a row), loads go straight to registers, two k-steps in flight, and the sixteen partial tiles
+//   are added through LDS in wave order.  (Measured, DESIGN 8g: with 4 waves the D x D Linears, 80 workgroups each, had too few loads in flight.)  x is fp32 and is rounded to bf16 (nearest even) as the A fragment is built.  Columns >= N (the vocabulary's tail) read a
+//   clamped row and are not stored.  The result can be stored as fp32 rows and / or as bf16 into row rows[m] of a strided store (the step's
+//   K and V land in the self-attention cache without a copy launch).
+//
+// ---- pick: the token selection of one decode step, one workgroup of 1024 threads per row -----------------------------------------------------
+//   Two passes over the row's fp32 logits (L2 resident).  Pass A (timestamp mode only) takes, over the logits after every mask but the last rule's,
+//   the log-sum-exp of the timestamp range and the maximum of the text range (decoding.py:381-394).  Pass B takes maximum, lowest arg-maximum and
+//   sum of exponentials of the fully filtered logits, each thread online over its strided share, the shares combined by xor-butterflies and then
+//   across the 16 waves in wave order.  Thread 0 updates the row's state.  The count of rows not yet ended is an integer atomic.
+#include "kk_host.h"
+#include "../../include/kokoro_hip.h"
+
+#include <math.h>
+
+namespace {
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int ATTN_SPLIT = 128;   // keys per split
+constexpr int ATTN_REC = 80;      // floats per split record: max, sum, pad to 16, acc[64]
+
+__device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xFFFF0000u); }
+
+// ---------------------------------------------------------------------------------------------------------------------------- attention
+__global__ __launch_bounds__(64) void attn_rows_kernel(const float* q, const bf16_t* kv, int k_off, int v_off, long long item_stride, int ld, int T_rows,
+                                                       int items, const int* item, const int* len, int heads, float* scratch, int nsplit) {
+  const int sp = blockIdx.x, h = blockIdx.y, r = blockIdx.z, lane = threadIdx.x, kg = lane >> 3, ch = lane & 7;
+  int L = len[r];
+  L = L < T_rows ? L : T_rows;
+  int it = item[r];
+  it = it < 0 ? 0 : (it >= items ? items - 1 : it);
+  float* rec = scratch + (((long long)r * heads + h) * nsplit + sp) * ATTN_REC;
+  const int k_lo = sp * ATTN_SPLIT, k_hi = k_lo + ATTN_SPLIT < L ? k_lo + ATTN_SPLIT : L;
+  if (k_lo >= k_hi) {  // (uniform) nothing of this row in the split
+    if (lane == 0) { rec[0] = -INFINITY; rec[1] = 0.f; }
+    rec[16 + lane] = 0.f;
+    return;
+  }
+  const float* qp = q + ((long long)r * heads + h) * 64 + ch * 8;
+  const float4 qa = *(const float4*)qp, qb = *(const float4*)(qp + 4);
+  const bf16_t* base = kv + (long long)it * item_stride + h * 64 + ch * 8;
+  const float sc = 0.125f * 1.4426950408889634f;  // 64^-0.5 log2(e)
+  float m = -INFINITY, l = 0.f, acc[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) acc[c] = 0.f;
+  for (int k0 = k_lo; k0 < k_hi; k0 += 64) {
+    uint4 kr[8], vr[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int key = k0 + 8 * j + kg;
+      kr[j] = vr[j] = uint4{0u, 0u, 0u, 0u};
+      if (key < k_hi) {
+        const bf16_t* p = base + (long long)key * ld;
+        kr[j] = *(const uint4*)(p + k_off);
+        vr[j] = *(const uint4*)(p + v_off);
+      }
+    }
+    float s[8], mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float d = qa.x * bf_lo(kr[j].x);
+      d = __builtin_fmaf(qa.y, bf_hi(kr[j].x), d);
+      d = __builtin_fmaf(qa.z, bf_lo(kr[j].y), d);
+      d = __builtin_fmaf(qa.w, bf_hi(kr[j].y), d);
+      d = __builtin_fmaf(qb.x, bf_lo(kr[j].z), d);
+      d = __builtin_fmaf(qb.y, bf_hi(kr[j].z), d);
+      d = __builtin_fmaf(qb.z, bf_lo(kr[j].w), d);
+      d = __builtin_fmaf(qb.w, bf_hi(kr[j].w), d);
+      d += __shfl_xor(d, 1);
+      d += __shfl_xor(d, 2);
+      d += __shfl_xor(d, 4);
+      s[j] = k0 + 8 * j + kg < k_hi ? d * sc : -INFINITY;
+      mx = fmaxf(mx, s[j]);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 8));
+    mx = fmaxf(mx, __shfl_xor(mx, 16));
+    mx = fmaxf(mx, __shfl_xor(mx, 32));  // finite: key k0 is below k_hi
+    const float mn = fmaxf(m, mx);
+    const float alpha = __builtin_amdgcn_exp2f(m - mn);
+    m = mn;
+    l *= alpha;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) acc[c] *= alpha;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float p = __builtin_amdgcn_exp2f(s[j] - mn);  // exactly 0 for a key past k_hi, whose V registers are zeros
+      l += p;
+      acc[0] = __builtin_fmaf(p, bf_lo(vr[j].x), acc[0]);
+      acc[1] = __builtin_fmaf(p, bf_hi(vr[j].x), acc[1]);
+      acc[2] = __builtin_fmaf(p, bf_lo(vr[j].y), acc[2]);
+      acc[3] = __builtin_fmaf(p, bf_hi(vr[j].y), acc[3]);
+      acc[4] = __builtin_fmaf(p, bf_lo(vr[j].z), acc[4]);
+      acc[5] = __builtin_fmaf(p, bf_hi(vr[j].z), acc[5]);
+      acc[6] = __builtin_fmaf(p, bf_lo(vr[j].w), acc[6]);
+      acc[7] = __builtin_fmaf(p, bf_hi(vr[j].w), acc[7]);
+    }
+  }
+#pragma unroll
+  for (int o = 8; o < 64; o <<= 1) {
+    l += __shfl_xor(l, o);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) acc[c] += __shfl_xor(acc[c], o);
+  }
+  if (lane == 0) { rec[0] = m; rec[1] = l; }
+  if (kg == 0) {
+    *(float4*)(rec + 16 + ch * 8) = float4{acc[0], acc[1], acc[2], acc[3]};
+    *(float4*)(rec + 16 + ch * 8 + 4) = float4{acc[4], acc[5], acc[6], acc[7]};
+  }
+}
+
+__global__ __launch_bounds__(64) void attn_merge_kernel(const float* scratch, int nsplit, int heads, const int* len, float* out) {
+  const int h = blockIdx.x, r = blockIdx.y, d = threadIdx.x;
+  const float* rec = scratch + ((long long)r * heads + h) * nsplit * ATTN_REC;
+  float* o = out + ((long long)r * heads + h) * 64 + d;
+  if (len[r] < 1) {  // (the host entries refuse it; a row without keys has no softmax)
+    *o = 0.f;
+    return;
+  }
+  float M = -INFINITY;
+  for (int s = 0; s < nsplit; ++s) M = fmaxf(M, rec[s * ATTN_REC]);
+  float L = 0.f, a = 0.f;
+  for (int s = 0; s < nsplit; ++s) {
+    const float w = __builtin_amdgcn_exp2f(rec[s * ATTN_REC] - M);  // 0 for an empty split
+    L = __builtin_fmaf(rec[s * ATTN_REC + 1], w, L);
+    a = __builtin_fmaf(rec[s * ATTN_REC + 16 + d], w, a);
+  }
+  *o = a / L;
+}
+
+inline int attn_nsplit(int T_rows) { return (T_rows + ATTN_SPLIT - 1) / ATTN_SPLIT; }
+inline size_t attn_scratch_floats(int R, int heads, int T_rows) { return (size_t)R * heads * attn_nsplit(T_rows) * ATTN_REC; }
+
+int launch_attn_rows(hipStream_t st, int R, int heads, const float* q, const bf16_t* kv, int k_off, int v_off, int items, int T_rows, int ld, const int* item,
+                     const int* len, float* out, float* scratch) {
+  const int ns = attn_nsplit(T_rows);
+  for (int r0 = 0; r0 < R; r0 += 32768) {  // grid.z limit
+    const int n = R - r0 < 32768 ? R - r0 : 32768;
+    float* sc = scratch + (size_t)r0 * heads * ns * ATTN_REC;
+    hipLaunchKernelGGL(attn_rows_kernel, dim3(ns, heads, n), dim3(64), 0, st, q + (size_t)r0 * heads * 64, kv, k_off, v_off, (long long)T_rows * ld, ld, T_rows,
+                       items, item + r0, len + r0, heads, sc, ns);
+    KK_CHECK_LAUNCH();
+    hipLaunchKernelGGL(attn_merge_kernel, dim3(heads, n), dim3(64), 0, st, sc, ns, heads, len + r0, out + (size_t)r0 * heads * 64);
+    KK_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------- linear
+struct LinRows {
+  const float* x;
+  long long ldx;
+  const bf16_t* w;
+  const float* bias;
+  const float* res;
+  long long ldr;
+  float* out;
+  long long ldo;
+  bf16_t* ob;
+  long long ldb;
+  const int* rows;  // destination row of x row m in the bf16 store
+  int nrows;        // rows the store has; a destination outside [0, nrows) is not written
+  int M, N, K, act;
+};
+
+constexpr int LIN_WAVES = 16;  // waves of a workgroup = slices of K, summed in wave order
+
+__global__ __launch_bounds__(64 * LIN_WAVES) void linear_rows_kernel(LinRows a) {
+  __shared__ float red[LIN_WAVES][16][17];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, g = lane >> 4;
+  const int n0 = blockIdx.x * 16, nsteps = a.K >> 5;
+  const int nrow = n0 + lr < a.N ? n0 + lr : a.N - 1;  // the tail's columns read the last row; they are not stored
+  const bf16_t* wp = a.w + (long long)nrow * a.K + 8 * g + wave * 32;
+  const bool mvalid = lr < a.M;
+  const float* xp = a.x + (long long)(mvalid ? lr : 0) * a.ldx + 8 * g + wave * 32;  // lanes past M read row 0 and SELECT zeros: the loop has no branch
+  const bf16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  auto frag = [&](const float4& a0, const float4& a1) __attribute__((always_inline)) {
+    const bf16x8 xf = {(bf16_t)a0.x, (bf16_t)a0.y, (bf16_t)a0.z, (bf16_t)a0.w, (bf16_t)a1.x, (bf16_t)a1.y, (bf16_t)a1.z, (bf16_t)a1.w};
+    return mvalid ? xf : zero;
+  };
+  const int mine = wave < nsteps ? (nsteps - wave + LIN_WAVES - 1) / LIN_WAVES : 0;  // k-steps wave, wave + LIN_WAVES, ...
+  constexpr int STEP = 32 * LIN_WAVES;
+  int i = 0;
+  for (; i + 1 < mine; i += 2) {  // two k-steps' loads in flight before the first is used
+    const bf16x8 w0 = *(const bf16x8*)(wp + i * STEP), w1 = *(const bf16x8*)(wp + (i + 1) * STEP);
+    const float4 a0 = *(const float4*)(xp + i * STEP), a1 = *(const float4*)(xp + i * STEP + 4);
+    const float4 b0 = *(const float4*)(xp + (i + 1) * STEP), b1 = *(const float4*)(xp + (i + 1) * STEP + 4);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(a0, a1), w0, acc, 0, 0, 0);  // D[m = 4 g + r][n = lr]
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(b0, b1), w1, acc, 0, 0, 0);
+  }
+  if (i < mine) {
+    const bf16x8 w0 = *(const bf16x8*)(wp + i * STEP);
+    const float4 a0 = *(const float4*)(xp + i * STEP), a1 = *(const float4*)(xp + i * STEP + 4);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(a0, a1), w0, acc, 0, 0, 0);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) red[wave][4 * g + r][lr] = acc[r];
+  __syncthreads();
+  const int m = tid >> 4, c = tid & 15, n = n0 + c;
+  if (tid >= 256 || m >= a.M || n >= a.N) return;
+  float v = red[0][m][c];
+#pragma unroll
+  for (int w = 1; w < LIN_WAVES; ++w) v += red[w][m][c];
+  if (a.bias) v += a.bias[n];
+  if (a.act == KK_ACT_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
+  if (a.res) v += a.res[(long long)m * a.ldr + n];
+  if (a.out) a.out[(long long)m * a.ldo + n] = v;
+  if (a.ob) {
+    const int row = a.rows ? a.rows[m] : m;
+    if (row >= 0 && row < a.nrows) a.ob[(long long)row * a.ldb + n] = (bf16_t)v;
+  }
+}
+
+int launch_linear_rows(hipStream_t st, const LinRows& a) {
+  hipLaunchKernelGGL(linear_rows_kernel, dim3((a.N + 15) / 16), dim3(64 * LIN_WAVES), 0, st, a);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
+// -------------------------------------------------------------------------------------------------------------------------------- embed
+__global__ __launch_bounds__(256) void embed_kernel(const int* tok, const int* pos, const bf16_t* table, int n_vocab, const float* positions, int n_ctx, int D,
+                                                    float* out) {
+  const int r = blockIdx.x;
+  int t = tok[r], p = pos[r];
+  t = t < 0 ? 0 : (t >= n_vocab ? n_vocab - 1 : t);  // a bad id reads a row of the table, never past it
+  p = p < 0 ? 0 : (p >= n_ctx ? n_ctx - 1 : p);
+  const bf16_t* e = table + (long long)t * D;
+  const float* pe = positions + (long long)p * D;
+  for (int c = threadIdx.x; c < D; c += 256) out[(long long)r * D + c] = (float)e[c] + pe[c];
+}
+
+// --------------------------------------------------------------------------------------------------------------------------------- pick
+struct Osm {  // online softmax share: maximum, sum of exp(. - maximum), lowest index of the maximum
+  float m, s;
+  int i;
+};
+__device__ __forceinline__ void osm_add(Osm& a, float x, int i) {
+  if (x == -INFINITY) return;
+  if (x > a.m) {
+    a.s = a.s * expf(a.m - x) + 1.0f;  // (a.m = -inf: 0 * 0 + 1)
+    a.m = x;
+    a.i = i;
+  } else {
+    a.s += expf(x - a.m);
+  }
+}
+__device__ __forceinline__ Osm osm_merge(const Osm& a, const Osm& b) {  // symmetric in its bits: a butterfly leaves every lane with the same result
+  if (b.m == -INFINITY) return a;
+  if (a.m == -INFINITY) return b;
+  Osm r;
+  r.m = fmaxf(a.m, b.m);
+  r.s = a.s * expf(a.m - r.m) + b.s * expf(b.m - r.m);
+  r.i = a.m > b.m ? a.i : (b.m > a.m ? b.i : (a.i < b.i ? a.i : b.i));
+  return r;
+}
+__device__ __forceinline__ Osm osm_block(Osm v, Osm* sh) {  // all 1024 threads; the result in every thread
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    Osm t;
+    t.m = __shfl_xor(v.m, o);
+    t.s = __shfl_xor(v.s, o);
+    t.i = __shfl_xor(v.i, o);
+    v = osm_merge(v, t);
+  }
+  __syncthreads();  // the previous use of sh is over
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  Osm r = sh[0];
+  for (int w = 1; w < 16; ++w) r = osm_merge(r, sh[w]);
+  return r;
+}
+
+__global__ __launch_bounds__(1024) void pick_kernel(const float* logits, long long ldl, const kk_whisper_pick_params* params, const uint32_t* suppress,
+                                                    kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next, int32_t* not_ended) {
+  __shared__ Osm sh[16];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const kk_whisper_pick_params P = *params;
+  const kk_whisper_pick_state S = state[b];
+  const float* lg = logits + (long long)b * ldl;
+  const int V = P.n_vocab, tb = P.timestamp_begin;
+  const bool first = S.count == 0, ts = !P.without_timestamps;
+  const bool last_ts = ts && S.count >= 1 && S.last >= tb, pen_ts = S.count < 2 || S.penultimate >= tb;
+  const int ts_floor = S.last_timestamp >= tb ? (last_ts && !pen_ts ? S.last_timestamp : S.last_timestamp + 1) : tb;  // timestamps in [tb, ts_floor) are masked
+  const int last_allowed = P.max_initial_timestamp_index >= 0 ? tb + P.max_initial_timestamp_index : V;
+  auto pre = [&](int i, unsigned word) -> bool {  // SuppressBlank, SuppressTokens (word: the bitmask word of i)
+    if (first && P.suppress_blank && (i == P.blank || i == P.eot)) return true;
+    return (word >> (i & 31)) & 1u;
+  };
+  // a thread's share i = tid, tid + 1024, ... in that order, eight logits (and their bitmask words) requested before the first is used: the walk is
+  // bound by the latency of its loads, not by their volume
+  auto walk = [&](auto&& f) __attribute__((always_inline)) {
+    for (int base = tid; base < V; base += 8 * 1024) {
+      float x[8];
+      unsigned w[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = base + 1024 * u;
+        x[u] = i < V ? lg[i] : -INFINITY;
+        w[u] = i < V && suppress ? suppress[i >> 5] : 0u;
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (base + 1024 * u < V) f(base + 1024 * u, x[u], w[u]);
+    }
+  };
+  auto rules = [&](int i) -> bool {  // ApplyTimestampRules, all but its last rule
+    if (i == P.no_timestamps) return true;
+    if (last_ts && (pen_ts ? i >= tb : i < P.eot)) return true;
+    if (i >= tb && i < ts_floor) return true;
+    if (first && (i < tb || i > last_allowed)) return true;
+    return false;
+  };
+  bool mass = false;
+  if (ts) {  // decoding.py:381-394, taken AFTER the masks above as OpenAI's original does (on the logits the filter was handed, a row can lose every token)
+    Osm t = {-INFINITY, 0.f, 0};
+    float mt = -INFINITY;
+    walk([&](int i, float v, unsigned word) {
+      const float x = pre(i, word) || rules(i) ? -INFINITY : v;
+      if (i >= tb) osm_add(t, x, i);
+      else mt = fmaxf(mt, x);
+    });
+    t = osm_block(t, sh);
+    Osm u = {mt, 1.f, 0};
+    u = osm_block(u, sh);
+    mass = t.m != -INFINITY && t.m + logf(t.s) > u.m;
+  }
+  Osm f = {-INFINITY, 0.f, 0};
+  walk([&](int i, float v, unsigned word) {
+    const bool masked = pre(i, word) || (ts && (rules(i) || (mass && i < tb)));
+    osm_add(f, masked ? -INFINITY : v, i);
+  });
+  f = osm_block(f, sh);
+  if (tid != 0) return;
+  kk_whisper_pick_state N = S;
+  int tok = f.i;
+  float lp = 0.f;
+  if (f.m == -INFINITY) tok = P.eot;  // everything masked: end the row
+  else lp = lg[tok] - (f.m + logf(f.s));
+  if (S.ended) tok = P.eot;  // decoding.py:273-274
+  else N.sum_logprob = S.sum_logprob + lp;  // :271
+  if (S.count < cap) tokens[(long long)b * cap + S.count] = tok;
+  next[b] = tok;
+  if (!S.ended && tok == P.eot) {
+    N.ended = 1;
+    atomicSub(not_ended, 1);
+  }
+  N.penultimate = S.last;
+  N.last = tok;
+  if (tok >= tb) N.last_timestamp = tok;
+  N.last_logprob = lp;
+  N.count = S.count + 1;
+  state[b] = N;
+}
+
+__global__ void pick_reset_kernel(kk_whisper_pick_state* state, int B, int32_t* not_ended) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) state[b] = kk_whisper_pick_state{-1, -1, -1, 0, 0, 0.f, 0.f, 0};
+  if (b == 0) *not_ended = B;
+}
+
+// the per-row index arrays of a forward call: row r = (b, s) sits at position pos + s of item b
+__global__ void text_rows_kernel(int B, int S, int pos, int n_text_ctx, int n_audio_ctx, int* item, int* posr, int* len_self, int* len_cross, int* cache_row) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= B * S) return;
+  const int b = r / S, p = pos + r % S;
+  item[r] = b;
+  posr[r] = p;
+  len_self[r] = p + 1;
+  len_cross[r] = n_audio_ctx;
+  cache_row[r] = b * n_text_ctx + p;
+}
+}  // namespace
+
+// ============================================================================================================================ kk_op_* entries
+extern "C" size_t kk_op_whisper_attn_rows_scratch_bytes(int R, int heads, int T_rows) {
+  if (R < 1 || heads < 1 || T_rows < 1) return 0;
+  return attn_scratch_floats(R, heads, T_rows) * sizeof(float);
+}
+
+extern "C" int kk_op_whisper_attn_rows(void* stream, int R, int heads, const float* q, const void* kv, int k_off, int v_off, int items, int T_rows, int ld,
+                                       const int32_t* item, const int32_t* len, float* out, void* scratch, size_t scratch_bytes) {
+  if (!q || !kv || !item || !len || !out || !scratch) return kk_fail("kk_op_whisper_attn_rows: null argument");
+  if (R < 1 || heads < 1 || items < 1 || T_rows < 1) return kk_fail("kk_op_whisper_attn_rows: bad argument (need R, heads, items, T_rows >= 1)");
+  if (k_off < 0 || v_off < 0 || k_off % 8 != 0 || v_off % 8 != 0 || ld % 8 != 0 || k_off + heads * 64 > ld || v_off + heads * 64 > ld)
+    return kk_fail("kk_op_whisper_attn_rows: k_off / v_off / ld must be multiples of 8 with `heads` heads of 64 channels inside a row");
+  if (((uintptr_t)kv & 15) || ((uintptr_t)q & 15) || ((uintptr_t)scratch & 15)) return kk_fail("kk_op_whisper_attn_rows: q, kv and scratch must be 16-byte aligned");
+  if (scratch_bytes < kk_op_whisper_attn_rows_scratch_bytes(R, heads, T_rows)) return kk_fail("kk_op_whisper_attn_rows: scratch too small");
+  // the only entry that looks at device data: the row table decides what memory is read, so it is checked here (the handle's forward, which
+  // makes its own tables, calls the launcher and never synchronises)
+  std::vector<int32_t> hv(2 * (size_t)R);
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemcpyAsync(hv.data(), item, (size_t)R * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(hv.data() + R, len, (size_t)R * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return kk_fail("kk_op_whisper_attn_rows: reading the row table failed");
+  for (int r = 0; r < R; ++r) {
+    if (hv[r] < 0 || hv[r] >= items) return kk_failf("kk_op_whisper_attn_rows: item[%d] = %d is outside [0, %d)", r, hv[r], items);
+    if (hv[R + r] < 1 || hv[R + r] > T_rows) return kk_failf("kk_op_whisper_attn_rows: len[%d] = %d is outside [1, %d]", r, hv[R + r], T_rows);
+  }
+  return launch_attn_rows(st, R, heads, q, (const bf16_t*)kv, k_off, v_off, items, T_rows, ld, item, len, out, (float*)scratch);
+}
+
+extern "C" int kk_op_whisper_linear_rows(void* stream, int M, int N, int K, const float* x, long long ldx, const void* w, const float* bias, int act,
+                                         const float* res, long long ldr, float* out, long long ldo, void* out_bf16, long long ld_bf16, const int32_t* rows_bf16,
+                                         int nrows_bf16) {
+  if (!x || !w || (!out && !out_bf16)) return kk_fail("kk_op_whisper_linear_rows: null argument");
+  if (M < 1 || M > 16) return kk_fail("kk_op_whisper_linear_rows: 1 <= M <= 16 rows per call");
+  if (N < 1 || K < 32 || K % 32 != 0) return kk_fail("kk_op_whisper_linear_rows: N >= 1 and K a multiple of 32");
+  if (act != KK_ACT_NONE && act != KK_ACT_GELU) return kk_fail("kk_op_whisper_linear_rows: act must be none (0) or GELU (2)");
+  if (ldx < K || ldx % 4 != 0 || ((uintptr_t)x & 15) || ((uintptr_t)w & 15)) return kk_fail("kk_op_whisper_linear_rows: x and w must be 16-byte aligned, ldx >= K, ldx % 4 == 0");
+  if ((out && ldo < N) || (res && ldr < N) || (out_bf16 && (ld_bf16 < N || nrows_bf16 < 1))) return kk_fail("kk_op_whisper_linear_rows: a row pitch is smaller than N");
+  LinRows a{x, ldx, (const bf16_t*)w, bias, res, ldr, out, ldo, (bf16_t*)out_bf16, ld_bf16, rows_bf16, nrows_bf16, M, N, K, act};
+  return launch_linear_rows((hipStream_t)stream, a);
+}
+
+extern "C" int kk_op_whisper_embed(void* stream, int R, int D, const int32_t* tok, const int32_t* pos, const void* table_bf16, int n_vocab, const float* positions,
+                                   int n_ctx, float* out) {
+  if (!tok || !pos || !table_bf16 || !positions || !out) return kk_fail("kk_op_whisper_embed: null argument");
+  if (R < 1 || D < 1 || n_vocab < 1 || n_ctx < 1) return kk_fail("kk_op_whisper_embed: bad argument");
+  hipLaunchKernelGGL(embed_kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, tok, pos, (const bf16_t*)table_bf16, n_vocab, positions, n_ctx, D, out);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int kk_op_whisper_pick(void* stream, int B, const float* logits, long long ldl, const kk_whisper_pick_params* params, const uint32_t* suppress,
+                                  kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next, int32_t* not_ended) {
+  if (!logits || !params || !state || !tokens || !next || !not_ended) return kk_fail("kk_op_whisper_pick: null argument");
+  if (B < 1 || cap < 1 || ldl < 1) return kk_fail("kk_op_whisper_pick: bad argument");
+  hipLaunchKernelGGL(pick_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, logits, ldl, params, suppress, state, tokens, cap, next, not_ended);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int kk_op_whisper_pick_reset(void* stream, int B, kk_whisper_pick_state* state, int32_t* not_ended) {
+  if (!state || !not_ended || B < 1) return kk_fail("kk_op_whisper_pick_reset: bad argument");
+  hipLaunchKernelGGL(pick_reset_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, state, B, not_ended);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
+// ================================================================================================================================ the handle
+struct TLin {  // a Linear: bf16 [N][K] dense at `w` of wdev, fp32 bias [N] at `b` of fdev
+  size_t w = 0, b = 0;
+  int N = 0, K = 0;
+  bool bias = false;
+};
+struct TLayer {
+  TLin q, k, v, out, cq, ckv, cout, mlp1, mlp2;
+  size_t attn_ln_w = 0, attn_ln_b = 0, cross_ln_w = 0, cross_ln_b = 0, mlp_ln_w = 0, mlp_ln_b = 0;
+};
+
+struct kk_whisper_text {
+  kk_whisper_text_config cfg;
+  std::map<std::string, HostTensor> host;
+  bool finalized = false;
+  bf16_t* wdev = nullptr;  // every matrix, once: the blocks' Linears and the token embedding [V][D]
+  float* fdev = nullptr;   // biases, LayerNorm parameters, the learned positions
+  TLin emb;
+  std::vector<TLayer> layers;
+  size_t ln_w = 0, ln_b = 0, pos = 0;
+  // the window in flight (set_audio): the caller's state buffer, its batch and the rows' common position
+  char* state = nullptr;
+  int B = 0, at = 0;
+  const float* last_logits = nullptr;  // the last forward's last-position logits [B][last_ld], in the caller's memory
+  long long last_ld = 0;
+};
+
+namespace {
+int check_text_cfg(const kk_whisper_text_config& c) {
+  if (c.n_vocab < 1 || c.n_text_ctx < 1 || c.n_text_layer < 1 || c.n_text_head < 1 || c.n_audio_ctx < 1) return kk_fail("kk_whisper_text_create: bad dimensions");
+  if (c.n_text_state != 64 * c.n_text_head) return kk_fail("kk_whisper_text_create: the head dimension n_text_state / n_text_head must be 64");
+  if (c.n_text_state % 128 != 0 || c.n_text_state > 2048) return kk_fail("kk_whisper_text_create: n_text_state must be a multiple of 128, at most 2048");
+  if (c.n_audio_state != c.n_text_state) return kk_fail("kk_whisper_text_create: n_audio_state must equal n_text_state");
+  return 0;
+}
+
+struct TextState {  // the caller's state buffer
+  bf16_t *cross, *self;  // [layer][B][ctx][2 D]: K | V
+  kk_whisper_pick_params* params;
+  uint32_t* suppress;
+  kk_whisper_pick_state* rows;
+  int32_t *tokens, *next, *not_ended;
+};
+void plan_state(const kk_whisper_text_config& c, int B, Workspace& ws, TextState& s) {
+  const size_t D = c.n_text_state, L = c.n_text_layer;
+  s.cross = (bf16_t*)ws.raw(L * B * c.n_audio_ctx * 2 * D * 2);
+  s.self = (bf16_t*)ws.raw(L * B * c.n_text_ctx * 2 * D * 2);
+  s.params = (kk_whisper_pick_params*)ws.raw(sizeof(kk_whisper_pick_params));
+  s.suppress = (uint32_t*)ws.raw(((size_t)c.n_vocab + 31) / 32 * 4);
+  s.rows = (kk_whisper_pick_state*)ws.raw((size_t)B * sizeof(kk_whisper_pick_state));
+  s.tokens = (int32_t*)ws.raw((size_t)B * c.n_text_ctx * 4);
+  s.next = (int32_t*)ws.raw((size_t)B * 4);
+  s.not_ended = (int32_t*)ws.raw(4);
+}
+struct TextWork {
+  float *x, *ln, *q, *att, *h, *scratch;
+  int *item, *posr, *len_self, *len_cross, *cache_row;
+  bf16_t* feat;
+};
+void plan_work(const kk_whisper_text_config& c, int B, int S, Workspace& ws, TextWork& p) {
+  const size_t D = c.n_text_state, R = (size_t)B * S;
+  const int Tmax = c.n_audio_ctx > c.n_text_ctx ? c.n_audio_ctx : c.n_text_ctx;
+  p.x = (float*)ws.raw(R * D * 4);
+  p.ln = (float*)ws.raw(R * D * 4);
+  p.q = (float*)ws.raw(R * D * 4);
+  p.att = (float*)ws.raw(R * D * 4);
+  p.h = (float*)ws.raw(R * 4 * D * 4);
+  p.scratch = (float*)ws.raw(attn_scratch_floats((int)R, c.n_text_head, Tmax) * 4);
+  p.item = (int*)ws.raw(R * 4);
+  p.posr = (int*)ws.raw(R * 4);
+  p.len_self = (int*)ws.raw(R * 4);
+  p.len_cross = (int*)ws.raw(R * 4);
+  p.cache_row = (int*)ws.raw(R * 4);
+  p.feat = (bf16_t*)ws.raw((size_t)B * c.n_audio_ctx * D * 2);  // set_audio only
+}
+int bind(Workspace& ws, void* mem, size_t bytes) {
+  ws.base = (char*)(((uintptr_t)mem + 255) & ~(uintptr_t)255);
+  const size_t skip = (size_t)(ws.base - (char*)mem);
+  ws.cap = bytes > skip ? bytes - skip : 0;
+  return 0;
+}
+}  // namespace
+
+extern "C" int kk_whisper_text_create(const kk_whisper_text_config* cfg, kk_whisper_text** out) {
+  if (!cfg || !out) return kk_fail("kk_whisper_text_create: null argument");
+  KK_TRY(check_text_cfg(*cfg));
+  kk_whisper_text* m = new kk_whisper_text();
+  m->cfg = *cfg;
+  *out = m;
+  return 0;
+}
+
+extern "C" void kk_whisper_text_destroy(kk_whisper_text* m) {
+  if (!m) return;
+  if (m->wdev) (void)hipFree(m->wdev);
+  if (m->fdev) (void)hipFree(m->fdev);
+  delete m;
+}
+
+extern "C" int kk_whisper_text_load_tensor(kk_whisper_text* m, const char* name, const int64_t* shape, int ndim, const float* data) {
+  if (!m || !name || !shape || !data || ndim < 1) return kk_fail("kk_whisper_text_load_tensor: bad argument");
+  if (m->finalized) return kk_fail("kk_whisper_text_load_tensor: model already finalized");
+  size_t n = 1;
+  for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
+  HostTensor& t = m->host[name];
+  t.d.assign(data, data + n);
+  t.shape.assign(shape, shape + ndim);
+  return 0;
+}
+
+extern "C" int kk_whisper_text_finalize(kk_whisper_text* m, void* stream) {
+  if (!m) return kk_fail("kk_whisper_text_finalize: null model");
+  if (m->finalized) return kk_fail("kk_whisper_text_finalize: already finalized");
+  const kk_whisper_text_config& c = m->cfg;
+  const int D = c.n_text_state, V = c.n_vocab;
+  hipStream_t st = (hipStream_t)stream;
+  size_t wn = 0, fn = 0;
+  auto plan = [&](TLin& l, int N, int K, bool bias) {
+    l.N = N; l.K = K; l.bias = bias;
+    l.w = wn; wn += ((size_t)N * K + 63) & ~(size_t)63;
+    if (bias) { l.b = fn; fn += ((size_t)N + 63) & ~(size_t)63; }
+  };
+  auto planv = [&](size_t& off, size_t n) { off = fn; fn += (n + 63) & ~(size_t)63; };
+  m->layers.resize(c.n_text_layer);
+  for (auto& L : m->layers) {
+    plan(L.q, D, D, true); plan(L.k, D, D, false); plan(L.v, D, D, true); plan(L.out, D, D, true);
+    plan(L.cq, D, D, true); plan(L.ckv, 2 * D, D, true); plan(L.cout, D, D, true);  // cross key | value as ONE [2 D][D] Linear (the key's half of the bias is zero)
+    plan(L.mlp1, 4 * D, D, true); plan(L.mlp2, D, 4 * D, true);
+    planv(L.attn_ln_w, D); planv(L.attn_ln_b, D); planv(L.cross_ln_w, D); planv(L.cross_ln_b, D); planv(L.mlp_ln_w, D); planv(L.mlp_ln_b, D);
+  }
+  plan(m->emb, V, D, false);
+  planv(m->ln_w, D); planv(m->ln_b, D);
+  planv(m->pos, (size_t)c.n_text_ctx * D);
+
+  // everything is checked before anything is allocated
+  std::string err;
+  auto need = [&](const std::string& name, std::initializer_list<int64_t> shape) -> const HostTensor* {
+    auto it = m->host.find(name);
+    if (it == m->host.end()) {
+      if (err.empty()) err = "missing parameter: " + name;
+      return nullptr;
+    }
+    if (it->second.shape != std::vector<int64_t>(shape)) {
+      if (err.empty()) err = "unexpected shape for " + name;
+      return nullptr;
+    }
+    return &it->second;
+  };
+  std::vector<float> fpack(fn, 0.f);
+  auto vecp = [&](size_t off, const std::string& name, int n) {
+    if (const HostTensor* t = need(name, {n})) memcpy(&fpack[off], t->d.data(), (size_t)n * 4);
+  };
+  struct Job { const TLin* l; std::string name; int row0, N; };
+  std::vector<Job> jobs;
+  auto lin = [&](const TLin& l, const std::string& p, int row0, int N, bool bias) {
+    need(p + ".weight", {N, l.K});
+    if (bias) vecp(l.b + row0, p + ".bias", N);
+    jobs.push_back(Job{&l, p + ".weight", row0, N});
+  };
+  for (int li = 0; li < c.n_text_layer; ++li) {
+    TLayer& L = m->layers[li];
+    const std::string p = "decoder.blocks." + std::to_string(li) + ".";
+    lin(L.q, p + "attn.query", 0, D, true); lin(L.k, p + "attn.key", 0, D, false); lin(L.v, p + "attn.value", 0, D, true); lin(L.out, p + "attn.out", 0, D, true);
+    lin(L.cq, p + "cross_attn.query", 0, D, true); lin(L.ckv, p + "cross_attn.key", 0, D, false); lin(L.ckv, p + "cross_attn.value", D, D, true);
+    lin(L.cout, p + "cross_attn.out", 0, D, true);
+    lin(L.mlp1, p + "mlp1", 0, 4 * D, true); lin(L.mlp2, p + "mlp2", 0, D, true);
+    vecp(L.attn_ln_w, p + "attn_ln.weight", D); vecp(L.attn_ln_b, p + "attn_ln.bias", D);
+    vecp(L.cross_ln_w, p + "cross_attn_ln.weight", D); vecp(L.cross_ln_b, p + "cross_attn_ln.bias", D);
+    vecp(L.mlp_ln_w, p + "mlp_ln.weight", D); vecp(L.mlp_ln_b, p + "mlp_ln.bias", D);
+  }
+  need("decoder.token_embedding.weight", {V, D});
+  jobs.push_back(Job{&m->emb, "decoder.token_embedding.weight", 0, V});
+  vecp(m->ln_w, "decoder.ln.weight", D); vecp(m->ln_b, "decoder.ln.bias", D);
+  if (const HostTensor* t = need("decoder.positional_embedding", {c.n_text_ctx, D})) memcpy(&fpack[m->pos], t->d.data(), t->d.size() * 4);
+  if (!err.empty()) return kk_failf("kk_whisper_text_finalize: %s", err.c_str());
+
+  if (hipMalloc((void**)&m->wdev, wn * sizeof(bf16_t)) != hipSuccess || hipMalloc((void**)&m->fdev, fn * sizeof(float)) != hipSuccess)
+    return kk_fail("kk_whisper_text_finalize: hipMalloc failed");
+  // one matrix at a time: round to nearest even, copy, drop the host copy -- a large checkpoint is never held twice
+  std::vector<uint16_t> wpack;
+  for (const Job& j : jobs) {
+    HostTensor& t = m->host[j.name];
+    const size_t n = (size_t)j.N * j.l->K;
+    wpack.resize(n);
+    for (size_t i = 0; i < n; ++i) wpack[i] = f32_to_bf16_rne(t.d[i]);
+    if (hipMemcpyAsync((uint16_t*)m->wdev + j.l->w + (size_t)j.row0 * j.l->K, wpack.data(), n * 2, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return kk_fail("kk_whisper_text_finalize: upload failed");
+    m->host.erase(j.name);
+  }
+  if (hipMemcpyAsync(m->fdev, fpack.data(), fn * 4, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return kk_fail("kk_whisper_text_finalize: upload failed");
+  m->host.clear();
+  m->finalized = true;
+  return 0;
+}
+
+extern "C" size_t kk_whisper_text_state_bytes(const kk_whisper_text* m, int B) {
+  if (!m || B < 1) return 0;
+  Workspace ws;
+  TextState s;
+  plan_state(m->cfg, B, ws, s);
+  return ws.used + 256;
+}
+
+extern "C" size_t kk_whisper_text_workspace_bytes(const kk_whisper_text* m, int B, int S) {
+  if (!m || B < 1 || S < 1) return 0;
+  Workspace ws;
+  TextWork p;
+  plan_work(m->cfg, B, S, ws, p);
+  return ws.used + 256;
+}
+
+extern "C" int kk_whisper_text_set_audio(kk_whisper_text* m, void* stream, int B, const float* audio_features, void* state, size_t state_bytes, void* workspace,
+                                         size_t workspace_bytes) {
+  if (!m || !audio_features || !state || !workspace || B < 1) return kk_fail("kk_whisper_text_set_audio: bad argument");
+  if (!m->finalized) return kk_fail("kk_whisper_text_set_audio: model not finalized");
+  const kk_whisper_text_config& c = m->cfg;
+  const int D = c.n_text_state, ctx = c.n_audio_ctx;
+  hipStream_t st = (hipStream_t)stream;
+  Workspace ss, ws;
+  bind(ss, state, state_bytes);
+  bind(ws, workspace, workspace_bytes);
+  TextState s;
+  TextWork p;
+  plan_state(c, B, ss, s);
+  plan_work(c, B, 1, ws, p);
+  if (ss.oom) return kk_fail("kk_whisper_text_set_audio: state buffer too small");
+  if (ws.oom) return kk_fail("kk_whisper_text_set_audio: workspace too small");
+  KK_TRY(kk_launch_convert(audio_features, KK_F32, (long long)ctx * D, D, p.feat, KK_BF16, (long long)ctx * D, D, D, ctx, B, st));  // rounded once
+  for (int li = 0; li < c.n_text_layer; ++li) {  // whisper.py:114-116, once per window: key | value of every layer on the bf16 MFMA kernel
+    const TLin& l = m->layers[li].ckv;
+    KKMfmaArgs g;
+    memset(&g, 0, sizeof g);
+    g.x = p.feat; g.xbs = (long long)ctx * D; g.ldx = D; g.w = m->wdev + l.w; g.CinP = D; g.CoutP = 2 * D; g.Cin = D;
+    g.bias = m->fdev + l.b; g.out = s.cross + (size_t)li * B * ctx * 2 * D; g.obs = (long long)ctx * 2 * D; g.ldo = 2 * D;
+    g.Cout = 2 * D; g.Kw = 1; g.mode = KK_CONV; g.stride = 1; g.pad = 0; g.dil = 1; g.Q = ctx; g.Lo_rows = ctx;
+    g.lin = KKLen{nullptr, 0, ctx}; g.lout = KKLen{nullptr, 0, ctx};
+    g.in_slope = 1.0f; g.scale = 1.0f; g.act = KK_ACT_NONE;
+    KK_TRY(kk_launch_conv_mfma(g, B, KK_BF16, st));
+  }
+  m->state = (char*)state;
+  m->B = B;
+  m->at = 0;
+  m->last_logits = nullptr;
+  return 0;
+}
+
+extern "C" int kk_whisper_text_position(const kk_whisper_text* m) { return m && m->state ? m->at : -1; }
+
+extern "C" int kk_whisper_text_rewind(kk_whisper_text* m, int position) {
+  if (!m || !m->state) return kk_fail("kk_whisper_text_rewind: set_audio first");
+  if (position < 0 || position > m->at) return kk_failf("kk_whisper_text_rewind: position %d is outside [0, %d]", position, m->at);
+  m->at = position;  // the self K/V behind it is overwritten by the next forward; the cross K/V of the window stays
+  m->last_logits = nullptr;
+  return 0;
+}
+
+extern "C" int kk_whisper_text_forward(kk_whisper_text* m, void* stream, int B, int S, const int32_t* tokens, float* logits_out, int all_positions,
+                                       void* workspace, size_t workspace_bytes) {
+  if (!m || !logits_out || !workspace || B < 1 || S < 1) return kk_fail("kk_whisper_text_forward: bad argument");
+  if (!m->state || B != m->B) return kk_fail("kk_whisper_text_forward: set_audio first, with the same B");
+  const kk_whisper_text_config& c = m->cfg;
+  if (m->at + S > c.n_text_ctx) return kk_failf("kk_whisper_text_forward: position %d + %d tokens exceeds n_text_ctx = %d", m->at, S, c.n_text_ctx);
+  const int D = c.n_text_state, H = c.n_text_head, V = c.n_vocab, R = B * S;
+  hipStream_t st = (hipStream_t)stream;
+  Workspace ss, ws;
+  bind(ss, m->state, (size_t)-1 / 2);
+  bind(ws, workspace, workspace_bytes);
+  TextState s;
+  TextWork p;
+  plan_state(c, B, ss, s);
+  plan_work(c, B, S, ws, p);
+  if (ws.oom) return kk_fail("kk_whisper_text_forward: workspace too small");
+  if (!tokens) {  // the step after a pick: the tokens it chose
+    if (S != 1) return kk_fail("kk_whisper_text_forward: tokens may be null only for S = 1 (the tokens of the last pick)");
+    tokens = s.next;
+  }
+  hipLaunchKernelGGL(text_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, st, B, S, m->at, c.n_text_ctx, c.n_audio_ctx, p.item, p.posr, p.len_self, p.len_cross,
+                     p.cache_row);
+  KK_CHECK_LAUNCH();
+  hipLaunchKernelGGL(embed_kernel, dim3(R), dim3(256), 0, st, tokens, p.posr, m->wdev + m->emb.w, V, m->fdev + m->pos, c.n_text_ctx, D, p.x);
+  KK_CHECK_LAUNCH();
+
+  // a Linear over `rows` rows, 16 at a time (S = 1: one launch, every weight byte read once for the batch)
+  auto lin = [&](const TLin& l, int n0, int N, const float* x, long long ldx, int rows, int act, const float* res, float* out, long long ldo, bf16_t* ob,
+                 const int* dst) -> int {
+    for (int r0 = 0; r0 < rows; r0 += 16) {
+      LinRows a{x + (long long)r0 * ldx, ldx, m->wdev + l.w + (size_t)n0 * l.K, l.bias ? m->fdev + l.b + n0 : nullptr, res ? res + (long long)r0 * ldo : nullptr, ldo,
+                out ? out + (long long)r0 * ldo : nullptr, ldo, ob, 2 * D, dst ? dst + r0 : nullptr, B * c.n_text_ctx, rows - r0 < 16 ? rows - r0 : 16, N, l.K, act};
+      KK_TRY(launch_linear_rows(st, a));
+    }
+    return 0;
+  };
+  auto ln = [&](size_t w, size_t b, const float* src, long long ldx, int rows) -> int {
+    KKLnArgs a;
+    memset(&a, 0, sizeof a);
+    a.x = src; a.xbs = 0; a.ldx = (int)ldx; a.out = p.ln; a.obs = 0; a.ldo = D; a.C = D; a.Lmax = rows;
+    a.len = KKLen{nullptr, 0, rows}; a.w = m->fdev + w; a.bias = m->fdev + b; a.eps = 1e-5f;
+    return kk_launch_layernorm(a, 1, KK_F32, st);
+  };
+  for (int li = 0; li < c.n_text_layer; ++li) {  // whisper.py:157-168
+    const TLayer& L = m->layers[li];
+    bf16_t* selfc = s.self + (size_t)li * B * c.n_text_ctx * 2 * D;
+    const bf16_t* crossc = s.cross + (size_t)li * B * c.n_audio_ctx * 2 * D;
+    KK_TRY(ln(L.attn_ln_w, L.attn_ln_b, p.x, D, R));
+    KK_TRY(lin(L.q, 0, D, p.ln, D, R, KK_ACT_NONE, nullptr, p.q, D, nullptr, nullptr));
+    KK_TRY(lin(L.k, 0, D, p.ln, D, R, KK_ACT_NONE, nullptr, nullptr, D, selfc, p.cache_row));      // K and V of the new positions straight into the cache
+    KK_TRY(lin(L.v, 0, D, p.ln, D, R, KK_ACT_NONE, nullptr, nullptr, D, selfc + D, p.cache_row));
+    KK_TRY(launch_attn_rows(st, R, H, p.q, selfc, 0, D, B, c.n_text_ctx, 2 * D, p.item, p.len_self, p.att, p.scratch));  // causal: row (b, s) sees pos + s + 1 keys
+    KK_TRY(lin(L.out, 0, D, p.att, D, R, KK_ACT_NONE, p.x, p.x, D, nullptr, nullptr));
+    KK_TRY(ln(L.cross_ln_w, L.cross_ln_b, p.x, D, R));
+    KK_TRY(lin(L.cq, 0, D, p.ln, D, R, KK_ACT_NONE, nullptr, p.q, D, nullptr, nullptr));
+    KK_TRY(launch_attn_rows(st, R, H, p.q, crossc, 0, D, B, c.n_audio_ctx, 2 * D, p.item, p.len_cross, p.att, p.scratch));
+    KK_TRY(lin(L.cout, 0, D, p.att, D, R, KK_ACT_NONE, p.x, p.x, D, nullptr, nullptr));
+    KK_TRY(ln(L.mlp_ln_w, L.mlp_ln_b, p.x, D, R));
+    KK_TRY(lin(L.mlp1, 0, 4 * D, p.ln, D, R, KK_ACT_GELU, nullptr, p.h, 4 * D, nullptr, nullptr));
+    KK_TRY(lin(L.mlp2, 0, D, p.h, 4 * D, R, KK_ACT_NONE, p.x, p.x, D, nullptr, nullptr));
+  }
+  // decoder.ln and the tied embedding as the output Linear (whisper.py:247-248)
+  if (all_positions) {
+    KK_TRY(ln(m->ln_w, m->ln_b, p.x, D, R));
+    KK_TRY(lin(m->emb, 0, V, p.ln, D, R, KK_ACT_NONE, nullptr, logits_out, V, nullptr, nullptr));
+    m->last_logits = logits_out + (size_t)(S - 1) * V;  // the last position of item b is S rows after that of item b - 1
+    m->last_ld = (long long)S * V;
+  } else {
+    KK_TRY(ln(m->ln_w, m->ln_b, p.x + (size_t)(S - 1) * D, (long long)S * D, B));  // the last position of every item
+    KK_TRY(lin(m->emb, 0, V, p.ln, D, B, KK_ACT_NONE, nullptr, logits_out, V, nullptr, nullptr));
+    m->last_logits = logits_out;
+    m->last_ld = V;
+  }
+  m->at += S;
+  return 0;
+}
+
+extern "C" int kk_whisper_text_pick_setup(kk_whisper_text* m, void* stream, const kk_whisper_pick_params* params, const uint32_t* suppress) {
+  if (!m || !params) return kk_fail("kk_whisper_text_pick_setup: null argument");
+  if (!m->state) return kk_fail("kk_whisper_text_pick_setup: set_audio first");
+  const kk_whisper_text_config& c = m->cfg;
+  if (params->n_vocab != c.n_vocab) return kk_fail("kk_whisper_text_pick_setup: params.n_vocab differs from the model's");
+  if (params->eot < 0 || params->eot >= c.n_vocab || params->timestamp_begin < 0 || params->timestamp_begin > c.n_vocab)
+    return kk_fail("kk_whisper_text_pick_setup: token ids outside the vocabulary");
+  hipStream_t st = (hipStream_t)stream;
+  Workspace ss;
+  bind(ss, m->state, (size_t)-1 / 2);
+  TextState s;
+  plan_state(c, m->B, ss, s);
+  const size_t words = ((size_t)c.n_vocab + 31) / 32;
+  if (hipMemcpyAsync(s.params, params, sizeof *params, hipMemcpyHostToDevice, st) != hipSuccess) return kk_fail("kk_whisper_text_pick_setup: upload failed");
+  if ((suppress ? hipMemcpyAsync(s.suppress, suppress, words * 4, hipMemcpyHostToDevice, st) : hipMemsetAsync(s.suppress, 0, words * 4, st)) != hipSuccess)
+    return kk_fail("kk_whisper_text_pick_setup: upload failed");
+  if (hipStreamSynchronize(st) != hipSuccess) return kk_fail("kk_whisper_text_pick_setup: stream sync failed");  // the host arrays may go away
+  return kk_op_whisper_pick_reset(stream, m->B, s.rows, s.not_ended);
+}
+
+extern "C" int kk_whisper_text_pick(kk_whisper_text* m, void* stream) {
+  if (!m) return kk_fail("kk_whisper_text_pick: null model");
+  if (!m->state || !m->last_logits) return kk_fail("kk_whisper_text_pick: no logits: run forward first");
+  Workspace ss;
+  bind(ss, m->state, (size_t)-1 / 2);
+  TextState s;
+  plan_state(m->cfg, m->B, ss, s);
+  return kk_op_whisper_pick(stream, m->B, m->last_logits, m->last_ld, s.params, s.suppress, s.rows, s.tokens, m->cfg.n_text_ctx, s.next, s.not_ended);
+}
+
+extern "C" int kk_whisper_text_not_ended(kk_whisper_text* m, void* stream, int32_t* out) {
+  if (!m || !out) return kk_fail("kk_whisper_text_not_ended: null argument");
+  if (!m->state) return kk_fail("kk_whisper_text_not_ended: set_audio first");
+  Workspace ss;
+  bind(ss, m->state, (size_t)-1 / 2);
+  TextState s;
+  plan_state(m->cfg, m->B, ss, s);
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemcpyAsync(out, s.not_ended, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return kk_fail("kk_whisper_text_not_ended: read failed");
+  return 0;
+}
+
+extern "C" int kk_whisper_text_read(kk_whisper_text* m, void* stream, int32_t* tokens, int cap, kk_whisper_pick_state* rows) {
+  if (!m || !tokens || !rows || cap < 1) return kk_fail("kk_whisper_text_read: bad argument");
+  if (!m->state) return kk_fail("kk_whisper_text_read: set_audio first");
+  Workspace ss;
+  bind(ss, m->state, (size_t)-1 / 2);
+  TextState s;
+  plan_state(m->cfg, m->B, ss, s);
+  hipStream_t st = (hipStream_t)stream;
+  const int n = cap < m->cfg.n_text_ctx ? cap : m->cfg.n_text_ctx;
+  if (hipMemcpy2DAsync(tokens, (size_t)cap * 4, s.tokens, (size_t)m->cfg.n_text_ctx * 4, (size_t)n * 4, m->B, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(rows, s.rows, (size_t)m->B * sizeof *rows, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return kk_fail("kk_whisper_text_read: read failed");
+  return 0;
+}

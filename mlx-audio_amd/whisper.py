@@ -1,8 +1,12 @@
-"""Host mirror of the AUDIO side of the reference's Whisper (mlx_audio/stt/models/whisper): the constants, `pad_or_trim` and
-`log_mel_spectrogram` of audio.py:12-82, `ModelDimensions`, and `Model` with `embed_audio` / `load_weights` / `from_pretrained`
-(whisper.py:67-78, 251-353).  The arithmetic runs in libkokoro_hip.so (kk_op_log_mel, kk_whisper_*, csrc/kk_whisper.hip); PyTorch
-allocates device memory and provides the stream.  The text decoder and everything of decoding.py are not built: `logits`, `decode`,
-`generate` and `detect_language` raise NotImplementedError, and the `decoder.*` tensors of a checkpoint are kept on the host untouched."""
+"""Host mirror of the reference's Whisper (mlx_audio/stt/models/whisper): the constants, `pad_or_trim` and `log_mel_spectrogram` of
+audio.py:12-82, `ModelDimensions`, and `Model` with `embed_audio` / `load_weights` / `from_pretrained` (whisper.py:67-78, 251-353) and, at token
+level, `logits`, `detect_language` and `decode` (whisper.py:298, decoding.py; the options, results and special tokens live in whisper_decoding.py
+and are re-exported here).  The arithmetic runs in libkokoro_hip.so (kk_op_log_mel, kk_whisper_*, csrc/kk_whisper.hip; kk_whisper_text_*,
+kk_op_whisper_*, csrc/kk_whisper_text.hip); PyTorch allocates device memory and provides the stream.
+
+The text side is built when a checkpoint holds the COMPLETE `decoder.*` set; otherwise the model is encoder-only and `logits`, `decode` and
+`detect_language` raise NotImplementedError("text decoder: not built").  `generate` (transcription of long audio, which needs the tokenizer) is not
+built.  `Model.decoder_weights` keeps the non-encoder tensors of a checkpoint on the host, untouched, either way."""
 from __future__ import annotations
 
 import ctypes as C
@@ -25,7 +29,8 @@ N_SAMPLES_PER_TOKEN = HOP_LENGTH * 2  # the stem's second convolution has stride
 FRAMES_PER_SECOND = SAMPLE_RATE // HOP_LENGTH  # 10 ms per audio frame
 TOKENS_PER_SECOND = SAMPLE_RATE // N_SAMPLES_PER_TOKEN  # 20 ms per audio token
 
-_NOT_BUILT = "text decoder: not built"
+from .whisper_decoding import (NOT_BUILT as _NOT_BUILT, DecodingOptions, DecodingResult, SpecialTokens, decoder_shapes,  # noqa: E402,F401
+                               decoder_tensors, special_tokens)
 
 
 def _is_torch(a) -> bool:
@@ -245,6 +250,7 @@ class Model:
         self._h = None
         self._ws = None
         self._lib = None
+        self._text = None
 
     # ---- weights ---------------------------------------------------------------------------------------------------------------------
     def load_weights(self, weights: dict) -> "Model":
@@ -270,6 +276,11 @@ class Model:
                 shp = (C.c_int64 * a.ndim)(*a.shape)
                 _lib.check(lib.kk_whisper_load_tensor(h, name.encode(), shp, a.ndim, a.ctypes.data_as(C.c_void_p)), "kk_whisper_load_tensor")
             _lib.check(lib.kk_whisper_finalize(h, self._stream()), "kk_whisper_finalize")
+            dec = decoder_tensors(self.dims, rest)  # None: no complete decoder set, the model stays encoder-only
+            if dec is not None:
+                from .whisper_decoding import TextRuntime
+
+                self._text = TextRuntime(lib, self.dims, dec, self.device, self._stream())
         return self
 
     @classmethod
@@ -322,18 +333,47 @@ class Model:
                                              C.c_void_p(out.data_ptr())), "kk_whisper_encode")
         return out[0] if x.ndim == 2 else out
 
-    # ---- the text side: not built ----------------------------------------------------------------------------------------------------
-    def logits(self, *a, **kw):
-        raise NotImplementedError(_NOT_BUILT)
+    # ---- the text side -----------------------------------------------------------------------------------------------------------------
+    @property
+    def has_text_decoder(self) -> bool:
+        return self._text is not None
+
+    def logits(self, tokens=None, audio_features=None, *a, **kw):
+        """whisper.py:298: tokens (B, S) ints, audio_features (B, n_audio_ctx, n_audio_state) -> fp32 device (B, S, n_vocab).  No cache is carried
+        over between calls."""
+        if self._text is None:
+            raise NotImplementedError(_NOT_BUILT)
+        import torch
+
+        d = self.dims
+        tokens = torch.as_tensor(tokens)
+        feats = torch.as_tensor(audio_features)
+        if tokens.ndim != 2 or feats.ndim != 3 or tokens.shape[0] != feats.shape[0] or tuple(feats.shape[1:]) != (d.n_audio_ctx, d.n_audio_state):
+            raise ValueError("logits takes tokens (B, S) and audio features (B, n_audio_ctx, n_audio_state)")
+        if not 1 <= tokens.shape[1] <= d.n_text_ctx:
+            raise ValueError(f"1 <= S <= n_text_ctx = {d.n_text_ctx}")
+        with torch.cuda.device(self.device):
+            self._text.set_audio(feats.to(device=self.device, dtype=torch.float32).contiguous())
+            return self._text.forward(tokens.to(device=self.device, dtype=torch.int32).contiguous(), True)
 
     def decode(self, *a, **kw):
-        raise NotImplementedError(_NOT_BUILT)
+        """decoding.py:710-742 at token level, see whisper_decoding.decode"""
+        if self._text is None:
+            raise NotImplementedError(_NOT_BUILT)
+        from .whisper_decoding import decode
+
+        return decode(self, *a, **kw)
 
     def generate(self, *a, **kw):
         raise NotImplementedError(_NOT_BUILT)
 
     def detect_language(self, *a, **kw):
-        raise NotImplementedError(_NOT_BUILT)
+        """decoding.py:20-79, see whisper_decoding.detect_language"""
+        if self._text is None:
+            raise NotImplementedError(_NOT_BUILT)
+        from .whisper_decoding import detect_language
+
+        return detect_language(self, *a, **kw)
 
     @property
     def is_multilingual(self) -> bool:
@@ -352,6 +392,9 @@ class Model:
         if getattr(self, "_h", None) is not None and self._lib is not None:
             self._lib.kk_whisper_destroy(self._h)
         self._h = None
+        if getattr(self, "_text", None) is not None:
+            self._text.release()
+        self._text = None
 
     def __del__(self):
         try:

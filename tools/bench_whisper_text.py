@@ -1,0 +1,201 @@
+"""Times of the Whisper text side (mlx-audio_amd/whisper_decoding.py, csrc/kk_whisper_text.hip) at the whisper-large-v3-turbo decoder shape
+-- 4 layers of width 1280, 20 heads, 51866 tokens, 1500 audio positions -- on synthetic weights, for B = 1 and 8: `set_audio` (the cross K/V of a
+window), a 4-token prefill, and the steady-state decode step (one forward of S = 1 plus one pick) at a fixed position, with the bytes the step must
+read and the rate that makes of the measured time.  Every figure is the median of `--steps` samples after `--warmup`, each sample `--inner` calls
+between two device events.  Prints one JSON line per case.
+
+The per-step share of each kernel family comes from a run of its own under the profiler (tracing slows the host, so no time above is taken there):
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o k -- python tools/bench_whisper_text.py --only-steps 200 --batch 8
+    python tools/bench_whisper_text.py --digest DIR/.../k_kernel_trace.csv --digest-steps 200 --batch 8 [--out the bench's file: appended]
+
+Usage:  python tools/bench_whisper_text.py [--steps 20] [--warmup 3] [--inner 20] [--position 64] [--out profiles/whisper_text_bench.json]"""
+import argparse
+import csv
+import json
+import math
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+CTX, WIDTH, HEADS, LAYERS, VOCAB, TEXT_CTX = 1500, 1280, 20, 4, 51866, 448
+
+FAMILIES = (("linear_rows", "linear_rows_kernel"), ("attention", "attn_rows_kernel"), ("attention", "attn_merge_kernel"), ("layernorm", "layernorm_kernel"),
+            ("pick", "pick_kernel"), ("embed + row tables", "embed_kernel"), ("embed + row tables", "text_rows_kernel"))
+
+
+def step_bytes(B, position):
+    """what one decode step must read, from the shapes: every block Linear and the tied embedding once (bf16), every layer's cross K/V of every row
+    and the self K/V up to the position (bf16); and what it must write and re-read of the logits (fp32: written once, read twice by the pick)"""
+    D = WIDTH
+    weights = LAYERS * 14 * D * D * 2
+    embedding = VOCAB * D * 2
+    cross = LAYERS * B * CTX * 2 * D * 2
+    self_kv = LAYERS * B * (position + 1) * 2 * D * 2
+    logits = B * VOCAB * 4 * 3
+    return dict(block_weights=weights, embedding=embedding, cross_kv=cross, self_kv=self_kv, logits=logits, total=weights + embedding + cross + self_kv + logits)
+
+
+def digest(path, steps):
+    """rocprofv3's kernel_trace.csv of an --only-steps run -> microseconds per step and share by kernel family, over the dispatches AFTER the first pick
+    (what comes before it is the window's set-up and the prompt), and the steps' span from the first dispatch's start to the last one's end"""
+    rows = []
+    with open(path, newline="") as f:
+        for row in csv.DictReader(f):
+            rows.append((int(row["Start_Timestamp"]), int(row["End_Timestamp"]), row["Kernel_Name"]))
+    rows.sort()
+    first = next(i for i, r in enumerate(rows) if "pick_kernel" in r[2])
+    rows = rows[first + 1:]
+    fam, calls, total, other = {}, {}, 0.0, 0.0
+    for t0, t1, name in rows:
+        for label, needle in FAMILIES:
+            if needle in name:
+                fam[label] = fam.get(label, 0.0) + (t1 - t0)
+                calls[label] = calls.get(label, 0) + 1
+                total += t1 - t0
+                break
+        else:
+            other += t1 - t0
+    span = rows[-1][1] - rows[0][0]
+    return dict(case="step_kernel_families", steps=steps, us_per_step=round(total / steps / 1e3, 2), span_us_per_step=round(span / steps / 1e3, 2),
+                other_kernels_us_per_step=round(other / steps / 1e3, 2),
+                families={k: dict(us_per_step=round(v / steps / 1e3, 2), launches_per_step=round(calls[k] / steps, 2), share=round(v / max(total, 1.0), 4))
+                          for k, v in sorted(fam.items(), key=lambda kv: -kv[1])})
+
+
+def synthetic_model():
+    """N(0, 1 / fan_in) matrices, one set of arrays shared by every layer (the time does not depend on the values being distinct)"""
+    from mlx_audio_amd import whisper
+
+    d = whisper.ModelDimensions(128, CTX, WIDTH, HEADS, 1, VOCAB, TEXT_CTX, WIDTH, HEADS, LAYERS)
+    g = np.random.default_rng(0)
+    made = {}
+
+    def arr(shape):
+        if shape not in made:
+            fan_in = shape[-1] * (shape[1] if len(shape) == 3 else 1)
+            made[shape] = (g.standard_normal(shape, dtype=np.float32) / np.float32(math.sqrt(fan_in))) if len(shape) > 1 else \
+                (0.1 * g.standard_normal(shape)).astype(np.float32)
+        return made[shape]
+
+    shapes = {**whisper.encoder_shapes(d), **whisper.decoder_shapes(d)}
+    w = {k: (np.ones(s, np.float32) if "ln" in k and k.endswith("weight") else arr(s)) for k, s in shapes.items()}
+    return d, whisper.Model(d).load_weights(w)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--inner", type=int, default=20)
+    ap.add_argument("--position", type=int, default=64)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--only-steps", type=int, default=0, help="run this many decode steps and nothing else (the profiler's run)")
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--digest", default=None)
+    ap.add_argument("--digest-steps", type=int, default=200)
+    a = ap.parse_args()
+    if a.digest:
+        r = digest(a.digest, a.digest_steps)
+        print(json.dumps(r))
+        if a.out and os.path.exists(a.out):  # appended to the bench's file
+            with open(a.out) as f:
+                doc = json.load(f)
+            doc["results"].append(dict(r, B=a.batch))
+            with open(a.out, "w") as f:
+                json.dump(doc, f, indent=1)
+                f.write("\n")
+        return
+    import torch
+
+    from mlx_audio_amd import _lib
+    from mlx_audio_amd import whisper_decoding as WD
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_whisper_text.py needs a GPU: a time taken elsewhere says nothing")
+    if a.steps < 20 and not a.only_steps:
+        raise SystemExit("--steps must be at least 20 (the figures are medians)")
+    d, model = synthetic_model()
+    rt, tok = model._text, WD.special_tokens(d)
+    params = _lib.KKWhisperPickParams(n_vocab=d.n_vocab, eot=tok.eot, blank=WD.BLANK_TOKEN, no_timestamps=tok.no_timestamps, timestamp_begin=tok.timestamp_begin,
+                                      max_initial_timestamp_index=50, without_timestamps=0, suppress_blank=1)
+    bits = WD.suppress_bitmask(d.n_vocab, WD.suppress_list(tok, WD.DecodingOptions()))
+
+    def begin(B):
+        feats = torch.randn((B, CTX, WIDTH), generator=torch.Generator().manual_seed(B)).cuda()
+        rt.set_audio(feats)
+        rt.pick_setup(params, bits)
+        prompt = torch.randint(0, 50000, (B, a.position), generator=torch.Generator().manual_seed(1), dtype=torch.int32).cuda()
+        rt.forward(prompt, False)  # the self K/V up to the position
+        rt.pick()
+        return feats
+
+    def step():
+        rt.rewind(a.position)  # host only: every timed step runs at the same position
+        rt.step()
+        rt.pick()
+
+    if a.only_steps:
+        begin(a.batch)
+        for _ in range(a.only_steps):
+            step()
+        torch.cuda.synchronize()
+        return
+
+    def timed(fn, inner):
+        for _ in range(a.warmup):
+            fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.steps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(inner):
+                fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1) / inner)
+        return dict(ms_median=round(statistics.median(ms), 4), ms_min=round(min(ms), 4), ms_max=round(max(ms), 4), steps=a.steps, warmup=a.warmup, inner=inner)
+
+    results = []
+
+    def emit(r):
+        results.append(r)
+        print(json.dumps(r), flush=True)
+
+    for B in (1, 8):
+        feats = begin(B)
+        emit(dict(case="set_audio", B=B, **timed(lambda: rt.set_audio(feats), 1)))
+        begin(B)
+        four = torch.randint(0, 50000, (B, 4), generator=torch.Generator().manual_seed(2), dtype=torch.int32).cuda()
+
+        def prefill():
+            rt.rewind(0)
+            rt.forward(four, True)
+
+        emit(dict(case="prefill_4_tokens", B=B, **timed(prefill, 1)))
+        begin(B)
+        r = timed(step, a.inner)
+        by = step_bytes(B, a.position)
+        emit(dict(case="decode_step", B=B, position=a.position, bytes=by, tbytes_per_s=round(by["total"] / (r["ms_median"] * 1e-3) / 1e12, 3),
+                  tokens_per_s=round(B / (r["ms_median"] * 1e-3), 1), note="forward(S = 1) + pick, eager launches, no host synchronisation inside the window", **r))
+
+        def forward_only():
+            rt.rewind(a.position)
+            rt.step()
+
+        emit(dict(case="decode_step_forward_only", B=B, position=a.position, **timed(forward_only, a.inner)))
+        emit(dict(case="pick_only", B=B, **timed(rt.pick, a.inner)))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(dict(device=torch.cuda.get_device_name(0), shape=dict(ctx=CTX, width=WIDTH, heads=HEADS, layers=LAYERS, n_vocab=VOCAB, n_text_ctx=TEXT_CTX),
+                           results=results), f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
