@@ -234,9 +234,9 @@ void kk_debug_clear(kk_context* cx);
  * with that pack (NULL = back to the LDS-staged kernel).  The model packs both layouts in kk_finalize. */
 int kk_op_pack_w_frag(void* stream, const void* w_bf16, void* w_frag, int Kw, int CoutP, int CinP);
 void kk_debug_set_op_wfrag(const void* w_frag);
-void kk_debug_set_op_variant(int v); /* 4 (default), 5 or 40: which fragment-order kernel those calls use (5 = wave-specialised persistent, kk_conv_mfma5.hip; 40 = variant 4 slab by slab also where its whole-K form applies -- stride 1, 128 padded input channels -- the reference path of that form's test) */
+void kk_debug_set_op_variant(int v); /* 4 (default), 5 or 40: which fragment-order kernel those calls use (5 = wave-specialised persistent, kk_conv_mfma5.hip; 40 = variant 4 slab by slab also where its whole-K form (stride 1, 128 padded input channels) or its ring form (192 or more) applies -- the reference path of those forms' tests) */
 void kk_debug_set_op_post_slope(float slope); /* LeakyReLU(slope) of the final stored value in the kk_op_conv1d_bf16* calls that follow (variants 4 / 5; 0 or 1 = none, the default) */
-void kk_debug_force_generic(kk_context* cx, int flags); /* A/B tests in bf16 mode: bit0 no MFMA kernel, bit1 MFMA without norm fusion, bit2 LDS-staged MFMA kernel instead of variant 4, bit3 quantised model without the fp8 kernel, bit4 also materialise tensors fused kernels skip, bit5 stand-alone conv_post + iSTFT kernels, bit6 variant-5 (wave-specialised persistent) conv kernel wherever eligible, bit7 never (default: the layers with >= 9 taps), bit8 no side stream (the TextEncoder / harmonic-source branches of a forward on the caller's stream too), bit9 Linear layers never on the streaming kernel, bit10 always (default: by the rows in flight), bit11 conv variant 4 slab by slab also where its whole-K form is routed (128 padded input channels; part of the graph-cache key like every bit) */
+void kk_debug_force_generic(kk_context* cx, int flags); /* A/B tests in bf16 mode: bit0 no MFMA kernel, bit1 MFMA without norm fusion, bit2 LDS-staged MFMA kernel instead of variant 4, bit3 quantised model without the fp8 kernel, bit4 also materialise tensors fused kernels skip, bit5 stand-alone conv_post + iSTFT kernels, bit6 variant-5 (wave-specialised persistent) conv kernel wherever eligible, bit7 never (default: the layers with >= 9 taps), bit8 no side stream (the TextEncoder / harmonic-source branches of a forward on the caller's stream too), bit9 Linear layers never on the streaming kernel, bit10 always (default: by the rows in flight), bit11 conv variant 4 slab by slab also where its whole-K or ring form is routed (128 / 192 or more padded input channels; part of the graph-cache key like every bit) */
 
 /* ---- per-kernel-class timing (bench.py): HIP events around every launch on the forward's stream ----
  * classes: 0 conv_generic 1 conv_mfma 2 instnorm_stats 3 adain_act 4 lstm 5 istft_head 6 layernorm 7 attention

@@ -111,7 +111,7 @@ SIGNATURES = {
     "kk_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
     "kk_debug_override": (_i, [_vp, C.c_char_p, _vp]),
     "kk_debug_clear": (None, [_vp]),
-    # flags: see include/kokoro_hip.h; bit 11 (2048) = conv variant 4 slab by slab also where its whole-K form is routed
+    # flags: see include/kokoro_hip.h; bit 11 (2048) = conv variant 4 slab by slab also where its whole-K or ring form is routed
     "kk_debug_force_generic": (None, [_vp, _i]),
     "kk_op_pack_w_frag": (_i, [_vp, _vp, _vp, _i, _i, _i]),
     "kk_csm_create": (_i, [C.POINTER(KKCsmConfig), C.POINTER(_vp)]),

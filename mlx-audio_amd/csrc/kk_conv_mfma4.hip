@@ -20,9 +20,11 @@
 //   * B fragment of lane l: column l % 16, k-group l / 16; pack order [tap][n block][chunk][wc][ks][ni][lane] x 16 bytes: one coalesced
 //     1 KiB load per fragment, requested right behind the MFMAs of the k-step that frees its registers.
 //   * the X slab [192 + halo rows][64 ch] is staged once per channel slab (kk_conv_mfma_stage.h: registers -> fused transform -> LDS) and
-//     re-used by every tap as a shifted window.  Two forms: the slab-by-slab kernel (any slab count; the next slab is requested at the
-//     first tap of the current one and stored between two barriers after its last tap) and the WHOLE-K kernel for exactly two slabs
-//     (CinP == 128: both staged in the prologue into buffers of their own, no staging in the loop -- see conv_mfma4_wholek_kernel).
+//     re-used by every tap as a shifted window.  Three forms: the slab-by-slab kernel (any slab count; the next slab is requested at the
+//     first tap of the current one and stored between two barriers after its last tap), the WHOLE-K kernel for exactly two slabs
+//     (CinP == 128: both staged in the prologue into buffers of their own, no staging in the loop -- see conv_mfma4_wholek_kernel) and
+//     the RING kernel for three or more (two LDS buffers, the next slab stored behind the current one's last tap, ONE barrier per slab:
+//     the Linears and the fused AdaIN + Snake layers -- see conv_mfma4_ring_kernel).
 //   * all global loads are unconditional (clamped address + mask at use): a load under a data-dependent branch makes
 //     hipcc wait vmcnt(0) right behind it, which serialises the loads (one HBM round trip each)
 //   * epilogue (kk_conv_mfma_epilogue.h) through a 96 x 128 fp32 LDS tile per wave row, aliasing the slab: bias / activation / residual /
@@ -316,6 +318,181 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #include "kk_conv_mfma_epilogue.h"  // (shared with variant 2 and the slab-by-slab kernel)
 }
 
+// ---- the RING form: stride-1 convolutions over three or more slabs (CinP >= 192) with a halo of at most 32 rows, for the layer classes
+// where it measures faster: the Linears (k = 1, plain input: Albert, bert_encoder, the 1 x 1 shortcuts) and the fused AdaIN +
+// Snake layers with 3 or 7 taps (the 3-tap layers of stage 0).  The slab-by-slab kernel above gives every
+// 64-channel slab a barrier / transform-and-store by all four waves / barrier gap after its last tap.  Here:
+//   * two LDS slab buffers of whole-K's geometry (224 rows each; slab c lives in buffer c & 1): slab c + 1 is unpacked, transformed and stored
+//     into the other buffer right behind the MFMAs of slab c's last tap -- that buffer is free since the barrier that ended slab c - 1 -- and
+//     the ONE barrier at the end of slab c publishes slab c + 1 and retires slab c.  No barrier between a slab's taps, and a wave that has
+//     issued its MFMAs goes on to the store without waiting for the other three;
+//   * ONE register set of XR chunks (6 for k = 1: 192 rows, else 7), requested ahead of the MFMAs of slab c's first tap (as measured: behind
+//     them is 1 % slower on the fused layers).  A second set, which would give a k = 1 slab two periods to land, does not fit: 1, 60 and
+//     223 spilled VGPRs in the three arrangements built;
+//   * the requests are unconditional: the first tap of a slab period, the tile's last slab and its final iteration are peeled, no load sits
+//     under a branch, no weight fragment is requested that nobody multiplies;
+//   * the AdaIN parameters of slab c + 2 are requested at slab c's first tap and stored at its last (the table's half of slab c is free since
+//     slab c was stored, one barrier ago), so that the barrier at the end of slab c publishes them ahead of slab c + 1's period, which reads them.
+// Iteration order, operands and epilogue are those of the slab-by-slab kernel: outputs and statistics partials are BIT-IDENTICAL
+// (tests/test_gpu_conv_ring.py).  Plain inputs with two or more taps and the polyphase transposed convs measured level or slower in this
+// form (-2 ... -5 % at 3 / 5 taps plain) and stay slab by slab.
+template <int NRM, int XR>
+__global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_mfma4_ring_kernel(KKMfmaArgs a) {
+  using TO = bf16_t;
+  constexpr int WM = 96, BM = 2 * WM, MI16 = WM / 16, XREG = XR;
+  constexpr bool ACC16 = true;
+  using G = GeoWK<7>;  // two buffers of 224 rows (XR = 6 fills 192 of them)
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  bf16_t* Xs = (bf16_t*)smem;                 // [2 buffers][SROWS][XLD]
+  float* Ps = (float*)(smem + G::XS_BYTES);  // [2][3][64]: the half (chunk & 1) holds slab `chunk`
+  float* Cs = (float*)smem;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  constexpr bool K1 = XR == 6;  // k = 1 (the Linears): one tap, no halo, plain input -- the launcher sends nothing else here
+  static_assert(!(K1 && NRM), "the one-tap schedule carries no parameter pipeline");
+  constexpr int nphase = 1, phase = 0;
+  int bx, by, b;  // XCD-aware tile order, as above
+  {
+    const int gx = gridDim.x, gy = gridDim.y, total = gx * gy * gridDim.z;
+    int lid = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
+    const int per = total / 8, rem = total - per * 8;
+    const int xcd = lid & 7, idx = lid >> 3;
+    lid = xcd * per + (xcd < rem ? xcd : rem) + idx;
+    by = lid % gy;
+    const int t = lid / gy;
+    bx = t % gx;
+    b = t / gx;
+  }
+  const int q0 = bx * BM, n0 = by * BN;
+  const int Lin = kk_len(a.lin, b), Lout = kk_len(a.lout, b);
+  const int ntaps = K1 ? 1 : a.Kw, off0 = -a.pad, dstep = K1 ? 1 : a.dil, min_off = off0;
+  const int xrows = BM + (ntaps - 1) * dstep;  // <= XR * 32 (the launcher picks XR by the halo)
+  const bool tile_live = q0 < Lout;            // uniform over the workgroup
+
+  const unsigned long long tr0 = TR_NOW();
+  (void)tr0;
+  f32x4 acc[MI16][4];
+#pragma unroll
+  for (int i = 0; i < MI16; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  if (tile_live) {
+    const bf16_t* xb = a.x + (long long)b * a.xbs;
+    const int nchunk = a.CinP / CK;  // >= 3
+    const int lin_hi = Lin > 0 ? Lin - 1 : 0;
+    const int cin_real = a.Cin > 0 ? a.Cin : a.CinP;
+
+    // store_x writes the buffer that `stbuf` selects
+    int stbuf = 0;
+#define KK_STG(name) name
+#define KK_STG_XS (Xs + stbuf)
+#include "kk_conv_mfma_stage.h"
+    // The AdaIN parameters travel one slab ahead of the rows (below), so they have a request of their own, at the addresses load_x uses
+    // (kk_conv_mfma_stage.h); the one load_x issues with the rows is overwritten before anybody reads it and drops out of the loop.
+    auto load_p = [&](int chunk) __attribute__((always_inline)) -> float4 {
+      if (!NRM) return make_float4(0.f, 0.f, 0.f, 0.f);
+      const int which = __builtin_amdgcn_readfirstlane(tid >> 6), c = chunk * CK + (tid & 15) * 4;
+      const float* base = (NRM == 1 && which == 2) ? a.nrm_alpha : (which == 1 ? a.nrm_b : a.nrm_a) + (long long)b * a.nrm_stride;
+      const int off = (NRM == 1 && which == 2) ? (c + 3 < a.nrm_C ? c : 0) : c;
+      return *(const float4*)(base + off);
+    };
+    uint4 q00, q01, q02, q03, q10, q11, q12, q13;  // B fragments of one (tap, slab) iteration, [ks][ni], one iteration ahead
+    auto frag_ptr = [&](int chunk, int tap) __attribute__((always_inline)) -> const uint4* {
+      // pack order: [tap][n block][chunk][wc][ks][ni][lane] x 16 bytes
+      const long long blk = ((long long)tap * (a.CoutP / BN) + by) * nchunk + chunk;
+      return (const uint4*)a.wf + blk * 1024 + (wc * 2) * 4 * 64 + lane;
+    };
+    const int arow = wr * WM + (lane & 15);  // + mi*16 + tap shift
+    const int kofs = 8 * (lane >> 4);
+    // one (tap, slab) iteration on slab C in buffer C & 1; the next iteration's fragments are those of (FC, FT)
+#define KK_RING_ITER(C, TAP, FC, FT)                                                                            \
+    {                                                                                                             \
+      const uint4* fn = frag_ptr(FC, FT);                                                                         \
+      const bf16_t* xa = Xs + ((C) & 1) * G::SLAB + (arow + (TAP) * dstep) * XLD + kofs;                       \
+      KK_MFMA_ITER(q00, q01, q02, q03, q10, q11, q12, q13)                                                       \
+      asm volatile("" ::: "memory");                                                                              \
+    }
+
+    // ---- prologue: slab 0, the parameters of slabs 0 and 1, the first weight fragments
+    load_x(0);
+    {
+      const uint4* fp = frag_ptr(0, 0);
+      q00 = fp[0 * 64]; q01 = fp[1 * 64]; q02 = fp[2 * 64]; q03 = fp[3 * 64];
+      q10 = fp[4 * 64]; q11 = fp[5 * 64]; q12 = fp[6 * 64]; q13 = fp[7 * 64];
+      asm volatile("" ::: "memory");
+    }
+    float4 pnext = load_p(1);
+    store_p(0);
+    if (NRM) {
+      preg = pnext;
+      store_p(1);
+    }
+    __syncthreads();
+    store_x(0);
+    __syncthreads();
+
+    int c = 0;
+    if (K1) {
+      // ---- one tap: slab c + 1 is requested ahead of slab c's MFMAs (the fragments they multiply are in flight already, the fragments
+      // requested behind it are not needed before it is stored) and stored right behind them
+#pragma unroll 1
+      for (; c + 1 < nchunk; ++c) {
+        load_x(c + 1);
+        KK_RING_ITER(c, 0, c + 1, 0)
+        stbuf = ((c + 1) & 1) * G::SLAB;
+        store_x(c + 1);
+        __syncthreads();  // publishes slab c + 1, retires slab c
+      }
+    } else {
+      // ---- two or more taps: slab c + 1 (and the parameters of slab c + 2) requested at slab c's first tap and stored behind its last tap
+#pragma unroll 1
+      for (; c + 1 < nchunk; ++c) {
+        pnext = load_p(c + 2 < nchunk ? c + 2 : c + 1);
+        load_x(c + 1);
+        KK_RING_ITER(c, 0, c, 1)
+        for (int tap = 1; tap < ntaps; ++tap) {
+          const bool lt = tap + 1 == ntaps;
+          KK_RING_ITER(c, tap, lt ? c + 1 : c, lt ? 0 : tap + 1)
+        }
+        if (NRM && c + 2 < nchunk) {
+          preg = pnext;
+          store_p(c + 2);
+        }
+        stbuf = ((c + 1) & 1) * G::SLAB;
+        store_x(c + 1);
+        __syncthreads();  // publishes slab c + 1 (and the parameters of slab c + 2), retires slab c
+      }
+    }
+    // ---- the last slab: MFMAs and weight requests alone; the final iteration requests nothing
+    for (int tap = 0; tap + 1 < ntaps; ++tap) KK_RING_ITER(c, tap, c, tap + 1)
+    {
+      const bf16_t* xa = Xs + (c & 1) * G::SLAB + (arow + (ntaps - 1) * dstep) * XLD + kofs;
+      KK_MFMA_ITER_LAST(q00, q01, q02, q03, q10, q11, q12, q13)
+      asm volatile("" ::: "memory");
+    }
+#undef KK_RING_ITER
+    __syncthreads();  // main-loop LDS is dead; the epilogue tile aliases it
+  }
+
+#include "kk_conv_mfma_epilogue.h"  // (shared with variant 2 and the other forms)
+}
+
+template <int NRM, int XR>
+int launch_ring(const KKMfmaArgs& a, int B, hipStream_t st) {
+  using G = GeoWK<7>;
+  static KKDevOnce attr_once;
+  if (attr_once.first()) {
+    (void)hipFuncSetAttribute((const void*)conv_mfma4_ring_kernel<NRM, XR>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
+    attr_once.done();
+  }
+  dim3 grid(kk_cdiv(a.Q, 192), a.CoutP / BN, B);
+  hipLaunchKernelGGL((conv_mfma4_ring_kernel<NRM, XR>), grid, dim3(256), G::LDS_BYTES, st, a);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
 template <int NRM, int XR>
 int launch_wholek(const KKMfmaArgs& a, int B, hipStream_t st) {
   using G = GeoWK<XR>;
@@ -369,6 +546,15 @@ bool kk_mfma4_wholek_eligible(const KKMfmaArgs& a) {
   return a.mode == KK_CONV && a.stride == 1 && a.CinP == 2 * CK && a.dil >= 1 && (a.Kw - 1) * a.dil <= MAX_HALO;
 }
 
+// what the ring form takes: stride-1 convolutions over three or more slabs with a halo within its 224-row buffers, in the layer classes that
+// measured faster in it in every run of every pass: the Linears (one tap, plain input) and the fused AdaIN + Snake layers with 3 or
+// 7 taps.  Plain inputs with more taps and the transposed convs were level or slower; the fused AdaIN + LeakyReLU layers (3 and 5 taps) were
+// 1.5 - 2.8 % faster by the median but had a run inside the reference's range in one pass each; other tap counts were not measured.
+static bool ring_eligible(const KKMfmaArgs& a, int nrm) {
+  if (a.mode != KK_CONV || a.stride != 1 || a.CinP < 3 * CK || a.dil < 1 || (a.Kw - 1) * a.dil > 32) return false;
+  return a.Kw == 1 ? nrm == 0 : (nrm == 1 && (a.Kw == 3 || a.Kw == 7));
+}
+
 int kk_launch_conv_mfma4(const KKMfmaArgs& a, int B, int out_dtype, hipStream_t st) {
   if (a.Q <= 0 || B <= 0) return 0;
   if (!a.wf) return kk_fail("conv_mfma4: fragment-order weights missing");
@@ -383,6 +569,9 @@ int kk_launch_conv_mfma4(const KKMfmaArgs& a, int B, int out_dtype, hipStream_t 
     if (nrm == 1) return x7 ? launch_wholek<1, 7>(g, B, st) : launch_wholek<1, 8>(g, B, st);
     if (nrm == 2) return x7 ? launch_wholek<2, 7>(g, B, st) : launch_wholek<2, 8>(g, B, st);
     return x7 ? launch_wholek<0, 7>(g, B, st) : launch_wholek<0, 8>(g, B, st);
+  }
+  if (!g.slabwise && ring_eligible(g, nrm)) {
+    return nrm == 1 ? launch_ring<1, 7>(g, B, st) : launch_ring<0, 6>(g, B, st);
   }
   if (nrm == 1) return launch_one<bf16_t, 96, 1>(g, B, st);
   if (nrm == 2) return launch_one<bf16_t, 96, 2>(g, B, st);

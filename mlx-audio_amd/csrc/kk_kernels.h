@@ -46,7 +46,8 @@ struct KKMfmaArgs {
   int flat_T;
   KKLen flat_len;
   float post_slope;  // variants 4 / 5 (bf16 out): LeakyReLU(post_slope) of the final stored value; 0 or 1 = none
-  int slabwise;      // variant 4: 1 = the slab-by-slab kernel also where the whole-K form is eligible (routing, and the reference path of its test)
+  int slabwise;      // variant 4: 1 = the slab-by-slab kernel also where the whole-K form (CinP == 128) or the ring form (CinP >= 192: one tap plain, 3 or 7 taps
+                     // with the fused Snake input) is eligible (routing, and the reference path of their tests)
 };
 // Streaming matrix-core Linear over token rows (kk_linear_rows.hip): out[b][t][:] = act(x[b][t][:] W + bias), zeros past an utterance's length
 struct KKLinMfmaArgs {
@@ -77,7 +78,8 @@ constexpr int KK_MFMA_TILE_ROWS = 192;
 int kk_launch_conv_mfma(const KKMfmaArgs& a, int B, int out_dtype, hipStream_t st);
 // variant 4 (kk_conv_mfma4.hip): W fragments straight from global memory into the MFMA operand registers; 192-row tiles, bf16 out
 int kk_launch_conv_mfma4(const KKMfmaArgs& a, int B, int out_dtype, hipStream_t st);
-// its whole-K form (CinP == 128, stride 1: both slabs staged in the prologue, nothing but MFMAs in the loop); taken unless a.slabwise
+// its whole-K form (CinP == 128, stride 1: both slabs staged in the prologue, nothing but MFMAs in the loop); taken unless a.slabwise.  (The ring form,
+// CinP >= 192, is chosen inside the launcher under the same switch.)
 bool kk_mfma4_wholek_eligible(const KKMfmaArgs& a);
 // variant 5 (kk_conv_mfma5.hip): wave-specialised persistent kernel (4 MFMA waves + 4 service waves per CU) for stride-1 convolutions
 bool kk_mfma5_eligible(const KKMfmaArgs& a, int out_dtype);

@@ -158,7 +158,7 @@ struct kk_context {
   hipStream_t side_stream = nullptr;
   hipEvent_t side_fork[2] = {nullptr, nullptr}, side_join[2] = {nullptr, nullptr};
   bool no_side = false;  // debug bit 8 of kk_debug_force_generic: everything on the caller's stream
-  bool no_wholek = false;  // debug bit 11: variant 4 slab by slab also where its whole-K form is routed (the form's reference path)
+  bool no_wholek = false;  // debug bit 11: variant 4 slab by slab also where its whole-K or ring form is routed (the forms' reference path)
   int linrows_mode = 0;  // debug bits 9 / 10: the streaming Linear kernel never / at every size (default: up to 1024 rows in flight)
   struct ProfRec { int cls; double flops; double bytes; };
   std::vector<ProfRec> prof_rec;
@@ -937,8 +937,11 @@ struct Ctx : Workspace {  // Workspace::raw never runs past `cap`: every entry p
       // an utterance's length are zeros already and the epilogue stores zeros there (KKMfmaArgs::flat_T).
       // whole-K form of variant 4 (CinP == 128: both slabs staged in the prologue), per layer class as measured: the fused AdaIN
       // layers at every tap count that variant 4 runs (-9 % at 3 taps, -8 % at 7, -4 ... -7 % at 11 where variant 5 is not eligible); plain
-      // inputs stay slab by slab (level at 3 taps: with no transform there is little staging to take out of the loop)
-      g.slabwise = (cx->no_wholek || !g.nrm_a) ? 1 : 0;
+      // inputs stay slab by slab (level at 3 taps: with no transform there is little staging to take out of the loop).  From three slabs on
+      // (CinP >= 192) the launcher itself picks the ring form for the classes that measured faster in it (one tap with a plain
+      // input -- Albert, bert_encoder, the 1 x 1 shortcuts -- and fused Snake inputs with 3 or 7 taps), so plain inputs are no longer pinned there.  Debug bit
+      // 11 keeps meaning "slab by slab everywhere".
+      g.slabwise = (cx->no_wholek || (!g.nrm_a && g.CinP < 192)) ? 1 : 0;
       int Bl = B;
       if (!v5 && B > 1 && w.Kw == 1 && o.mode == KK_CONV && o.stride == 1 && o.pad == 0 && o.dil == 1 && o.in_shift == 0 && !o.nrm_a && !o.want_stats &&
           Q == x.rows && Q == out.rows && Q % 192 != 0 && x.bs == (long long)x.rows * x.ld && out.bs == (long long)out.rows * out.ld &&
@@ -1905,7 +1908,7 @@ extern "C" void kk_debug_force_generic(kk_context* cx, int on) {
   cx->keep_debug = (on & 16) != 0;      // bit 4: also materialise the tensors that fused kernels skip (conv_post), for kk_debug_fetch
   cx->no_head_fusion = (on & 32) != 0;  // bit 5: stand-alone conv_post + iSTFT head kernels instead of the fused head
   cx->no_side = (on & 256) != 0;        // bit 8: no side stream (every launch of a forward on the caller's stream)
-  cx->no_wholek = (on & 2048) != 0;     // bit 11: conv variant 4 slab by slab also where its whole-K form is routed (CinP == 128)
+  cx->no_wholek = (on & 2048) != 0;     // bit 11: conv variant 4 slab by slab also where its whole-K (CinP == 128) or ring form (CinP >= 192) is routed
   cx->linrows_mode = (on & 512) ? 2 : (on & 1024) ? 1 : 0;  // bit 9: Linear layers never on the streaming kernel; bit 10: always (default: by the rows in flight)
   cx->v5_mode = (on & 64) ? 1 : (on & 128) ? 2 : 0;  // bit 6: conv variant 5 (wave-specialised persistent) wherever eligible; bit 7: never (default: >= 9 taps)
 }
