@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import queue
 from collections import deque
-from concurrent.futures import Future, InvalidStateError
+from concurrent.futures import Future
 from typing import Deque, List, Optional
 
 import numpy as np
@@ -28,11 +28,12 @@ import torch
 from . import pcm as PCM
 from . import resample as RS
 from . import vad as VAD
+from .csm_listen import ListenMixin, _claim, _fail_future, _Heard, _speech_span, _vacate
 
 _END = object()  # what the utterance queue holds behind the last utterance of a closed microphone
 
 
-class CSMUtterance:
+class CSMUtterance(_Heard):
     """One utterance of a continuous listener.  `onset`: its first kept sample at the model's rate (the onset frame's first sample less the
     pre-roll).  `endpoint`: a `Future[SpeechSpan]` that resolves when the detector has closed the utterance (`forced`: by the length limit
     that keeps it inside the encoder's capacity); cancelled when `close()` ended the microphone first.  `end(text)` -- before or after the
@@ -42,48 +43,26 @@ class CSMUtterance:
     DROPPED -- `dropped` is set, a later `end()` is a ValueError and nothing of it enters a session."""
 
     def __init__(self, listener: "CSMContinuousListener", start: int, onset_frame: int):
+        super().__init__(listener.batcher)
         self.listener, self.onset, self.onset_frame = listener, int(start), int(onset_frame)
         self.endpoint: Future = Future()
         self.forced = False
         self.dropped = False
-        self.frames = 0                       # encoded
-        self.steps: List[int] = []
-        self._codes: List[torch.Tensor] = []
         self._start, self._stop, self._final = int(start), None, False
-        self._fresh = True                    # the encoder row is reset before this utterance's first step
-        self._future: Optional[Future] = None
-        self._text = None
         self._done = False                    # resolved, dropped or failed: the scheduler has let go of it
 
-    def end(self, text=None) -> Future:
-        lis = self.listener
-        b = lis.batcher
-        with b._lock:
-            if b._closed:
-                raise RuntimeError("CSMBatcher is closed")
-            if self.dropped:
-                raise ValueError("end: the utterance was dropped: the next one needed its encoder row and its room in the ring")
-            if self._future is not None or self._done or not lis._open:
-                raise ValueError("end: the utterance has ended or its listener was cancelled")
-            if lis.session is not None:
-                if text is None:
-                    raise ValueError("end: a session's heard turn needs its text")
-                lis.session._ready("end")
-            fut: Future = Future()
-            self._text = text
-            if lis.session is not None:
-                lis.session._hearing = fut
-            self._future = fut
-            b._wake.notify()
-        return fut
+    def _took(self, codes: torch.Tensor, F: int) -> None:
+        super()._took(codes, F)
+        self.listener.frames += F
 
-    def codes(self) -> torch.Tensor:
-        """The codes encoded so far, [n_cb, frames] int32 on the host."""
-        with self.listener.batcher._lock:
-            parts = list(self._codes)
-        if not parts:
-            return torch.zeros((self.listener.batcher.engine.n_cb, 0), dtype=torch.int32)
-        return torch.cat(parts, dim=1).cpu()
+    def _end_refused(self) -> None:
+        if self.dropped:
+            raise ValueError("end: the utterance was dropped: the next one needed its encoder row and its room in the ring")
+        if self._future is not None or self._done or not self.listener._open:
+            raise ValueError("end: the utterance has ended or its listener was cancelled")
+
+    def end(self, text=None) -> Future:
+        return self._begin_end(self.listener.session, text)
 
 
 class CSMContinuousListener:
@@ -94,14 +73,10 @@ class CSMContinuousListener:
     last utterance has resolved.  `cancel()` drops everything at once.  It holds one row of the batcher's streaming encoder, resampler,
     detector and device buffer from `listen` until then."""
 
-    continuous = True
-
     def __init__(self, batcher, row: int, speaker: int, session, sample_rate: Optional[int], fmt: Optional[str], vad: VAD.VadConfig, barge_in: bool):
         self.batcher, self.row, self.speaker, self.session = batcher, int(row), int(speaker), session
         self.cfg, self.barge_in = vad, bool(barge_in)
-        self.vad = None                       # (what the one-shot paths look at: they pass this listener by)
-        self.onset = self.endpoint = self._future = None
-        self._vset, self._vclosed, self._dev, self._open = False, False, True, True
+        self._open = True                     # False once cancelled or freed: the row is someone else's
         self.spf = int(batcher.engine.samples_per_frame)
         self.rate, self.fmt = sample_rate, fmt
         sr = int(batcher.engine.sample_rate)
@@ -131,18 +106,6 @@ class CSMContinuousListener:
         self._utts: Deque[CSMUtterance] = deque()  # not yet resolved or dropped, oldest first
         self._open_utt: Optional[CSMUtterance] = None  # the one the detector has not closed yet
         self._uq: "queue.Queue" = queue.Queue()
-
-    # ---- what the one-shot scheduler paths ask of every listener: nothing of this one is theirs -------------------------------------------------
-    ended = False
-
-    def _total(self) -> int:
-        return self.frames
-
-    def _unresampled(self) -> bool:
-        return False
-
-    def _vad_due(self) -> bool:
-        return False
 
     # ---- the caller's side ------------------------------------------------------------------------------------------------------------------
     def feed(self, pcm) -> None:
@@ -207,31 +170,35 @@ class CSMContinuousListener:
             b._wake.notify()
 
     def cancel(self) -> bool:
-        b = self.batcher
-        with b._lock:
+        with self.batcher._lock:
             if not self._open:
                 return False
-            self._open = False
-            if b._listeners[self.row] is self:
-                b._listeners[self.row] = None
-            utts = list(self._utts)
-            self._utts.clear()
+            _vacate(self)
             self._q.clear()
             self._qn = 0
-        for u in utts:
-            u._done = True
-            for f in (u._future, u.endpoint):
-                if f is not None:
-                    f.cancel()
-        self._uq.put(_END)
+        self._shut(None)
         return True
 
+    def _shut(self, e: Optional[BaseException]) -> None:
+        """The microphone leaves: its row is the next caller's, the utterances the scheduler still held lose their endpoint, a pending
+        `end()` fails with `e` (None: it is cancelled), and the utterance queue ends."""
+        with self.batcher._lock:
+            _vacate(self)
+            utts = list(self._utts)
+            self._utts.clear()
+        for u in utts:
+            u._done = True
+            u.endpoint.cancel()
+            _fail_future(u._future, e)
+        self._uq.put(_END)
 
-class ContinuousMixin:
-    """The scheduler's half (methods of `CSMBatcher`).  Nothing here runs, and none of its objects is made, before the first
-    `listen(continuous=True)`."""
 
-    def _cont_init(self) -> None:
+class ContinuousMixin(ListenMixin):
+    """The scheduler's half (methods of `CSMBatcher`), on top of the one-shot listeners'.  Nothing here runs, and none of its objects is
+    made, before the first `listen(continuous=True)`."""
+
+    def _listen_init(self, *a) -> None:
+        super()._listen_init(*a)
         self._cont_made = False                 # a continuous listener was made: the hooks of `step` are live
         self._rvad = None                       # vad.RingVad, one row per encoder row
         self._rvad_n = [0] * self.listen_rows   # per detector row: the n_avail and ...
@@ -245,7 +212,26 @@ class ContinuousMixin:
         return lis
 
     def _cont_mics(self) -> List[CSMContinuousListener]:
-        return [lis for lis in self._listeners if lis is not None and lis._open and getattr(lis, "continuous", False)]
+        return [lis for lis in self._listeners if isinstance(lis, CSMContinuousListener) and lis._open]
+
+    # ---- the batcher's hooks: the one-shot listeners first, then this ----------------------------------------------------------------------------
+    def _listen_due(self) -> bool:
+        return bool(self._cont_made and self._cont_due()) or super()._listen_due()
+
+    def _listen_consume(self) -> None:
+        super()._listen_consume()
+        if self._cont_made:
+            self._cont_consume()  # (likewise before the controls: every onset of a barge-in microphone)
+
+    def _listen_round(self) -> bool:
+        heard = super()._listen_round()
+        return (self._cont_made and self._cont_round()) or heard
+
+    def _listen_close(self) -> None:
+        self._cont_out.clear()
+        if self._rvad is not None:
+            self._rvad.close()
+        super()._listen_close()
 
     # ---- arithmetic (under the lock) ----------------------------------------------------------------------------------------------------------
     def _cont_room(self, lis: CSMContinuousListener) -> int:
@@ -364,24 +350,8 @@ class ContinuousMixin:
 
     def _cont_free(self, lis: CSMContinuousListener) -> None:
         with self._lock:
-            lis._open = False
-            if self._listeners[lis.row] is lis:
-                self._listeners[lis.row] = None
+            _vacate(lis)
         lis._uq.put(_END)
-
-    def _cont_fail(self, lis: CSMContinuousListener, e: BaseException) -> None:
-        with self._lock:
-            utts = list(lis._utts)
-            lis._utts.clear()
-        self._cont_free(lis)
-        for u in utts:
-            u._done = True
-            u.endpoint.cancel()
-            if u._future is not None:
-                try:
-                    u._future.set_exception(e)
-                except InvalidStateError:
-                    pass
 
     def _cont_upload(self) -> bool:
         """Every continuous listener's queued samples that the gate lets through go up once: the rows with a rate through ONE resampler
@@ -394,51 +364,43 @@ class ContinuousMixin:
             return False
         sr = int(self.engine.sample_rate)
         try:
-            if self._lrs is None and any(lis.rate is not None for lis in work):
-                self._lrs = self.engine.row_resampler(self.listen_rows, self.LISTEN_IN)
-            if self._cvt is None and any(lis.rate is None for lis in work):
-                self._cvt = self.engine.pcm_converter()
+            self._listen_made(work)
             if self._rvad is None:
                 self._rvad = self.engine.row_ring_vad(self.listen_rows)
-            if self._heard is None:
-                self._heard = torch.zeros((self.listen_rows, self.listen_max_frames * work[0].spf), dtype=torch.float32, device=self.engine.device)
         except Exception as e:  # noqa: BLE001
             for lis in work:
-                self._cont_fail(lis, e)
+                lis._shut(e)
             return True
         for lis in list(work):
             if lis._cset:
                 continue
             try:  # a new stream starts in the row: position 0 of the ring, zero resampler history, an armed detector with an empty log
-                if lis.rate is not None and lis.fmt is None:
-                    self._lrs.set_row(lis.row, lis.rate, sr)
-                elif lis.rate is not None:
-                    self._lrs.set_row(lis.row, lis.rate, sr, in_format=lis.fmt)
+                self._listen_set_row(lis)
                 self._rvad.set_row(lis.row, lis.cfg.frame_len(sr), lis.cfg.thr2n(sr), lis.cfg.hang_frames, lis.max_frames, lis.ring_len)
                 self._rvad_n[lis.row] = self._rvad_a[lis.row] = 0
                 lis._cset = True
             except Exception as e:  # noqa: BLE001  (this row's own failure: the others go on)
                 work.remove(lis)
-                self._cont_fail(lis, e)
+                lis._shut(e)
         did = False
         carried = [lis for lis in work if lis._carry is not None]
         for lis in carried:  # (only at a full ring or behind a flush, and one small write each)
             try:
                 did = self._cont_write_carry(lis) or did
             except Exception as e:  # noqa: BLE001
-                self._cont_fail(lis, e)
+                lis._shut(e)
         rated = [lis for lis in work if lis.rate is not None and lis._open and lis._carry is None and not lis._flushed]
         plain = [lis for lis in work if lis.rate is None and lis._open and not lis._flushed]
         try:
             did = self._cont_upload_rated(rated) or did
         except Exception as e:  # noqa: BLE001  (the shared step: it fails the rows that took part in it)
             for lis in rated:
-                self._cont_fail(lis, e)
+                lis._shut(e)
         try:
             did = self._cont_upload_plain(plain) or did
         except Exception as e:  # noqa: BLE001
             for lis in plain:
-                self._cont_fail(lis, e)
+                lis._shut(e)
         return did
 
     def _cont_write_carry(self, lis: CSMContinuousListener) -> bool:
@@ -470,17 +432,10 @@ class ContinuousMixin:
         if not todo:
             return False
         n_in, fl = [0] * self.listen_rows, [False] * self.listen_rows
-        if any(lis.fmt is not None for lis, _, _ in todo):  # the rows' bytes, each in its own format
-            x = np.zeros((self.listen_rows, max(16, -(-max(a.shape[0] * a.itemsize for _, a, _ in todo) // 16) * 16)), np.uint8)
-            for lis, a, _ in todo:
-                x[lis.row, : a.shape[0] * a.itemsize] = a.view(np.uint8)
-        else:
-            x = np.zeros((self.listen_rows, max(4, -(-max(a.shape[0] for _, a, _ in todo) // 4) * 4)), np.float32)
-            for lis, a, _ in todo:
-                x[lis.row, : a.shape[0]] = a
         for lis, a, flush in todo:
             n_in[lis.row], fl[lis.row] = int(a.shape[0]), flush
-        y, n_out = self._lrs.step(torch.from_numpy(x).to(self.engine.device), n_in, fl)
+        x = self._listen_stage([(lis.row, a) for lis, a, _ in todo], any(lis.fmt is not None for lis, _, _ in todo))
+        y, n_out = self._lrs.step(x, n_in, fl)
         yf = y if y.dtype == torch.float32 else y.view(torch.float32)  # (a byte y: rows of 16-byte multiples, the outputs float32)
         pos, n = [0] * self.listen_rows, [0] * self.listen_rows
         with self._lock:
@@ -510,12 +465,10 @@ class ContinuousMixin:
                     lis._flushed = True  # (nothing is carried between steps at the model's rate: the stream is whole)
         if not todo:
             return False
-        x = np.zeros((self.listen_rows, max(16, -(-max(a.shape[0] * a.itemsize for _, a in todo) // 16) * 16)), np.uint8)
         fmts, n, pos = ["f32"] * self.listen_rows, [0] * self.listen_rows, [0] * self.listen_rows
         for lis, a in todo:
-            x[lis.row, : a.shape[0] * a.itemsize] = a.view(np.uint8)
             fmts[lis.row], n[lis.row], pos[lis.row] = lis.fmt or "f32", int(a.shape[0]), lis._n24
-        y = self._cvt.convert(torch.from_numpy(x).to(self.engine.device), fmts, ["f32"] * self.listen_rows, n)
+        y = self._cvt.convert(self._listen_stage([(lis.row, a) for lis, a in todo], True), fmts, ["f32"] * self.listen_rows, n)
         self.engine.ring_write(y.view(torch.float32), self._heard, todo[0][0].ring_len, pos, n)
         with self._lock:
             for lis, a in todo:
@@ -541,7 +494,7 @@ class ContinuousMixin:
             ticket = self._rvad.fetch()
         except Exception as e:  # noqa: BLE001  (the shared step: it fails the rows that took part in it)
             for lis in rows:
-                self._cont_fail(lis, e)
+                lis._shut(e)
             return True
         with self._lock:
             for lis in rows:
@@ -554,8 +507,6 @@ class ContinuousMixin:
         listeners' state.  New records close the open utterance or, when an utterance began and closed between two consumed tables, make
         one that is final at once; an onset behind them makes the open one.  Every new utterance of a `barge_in` listener records the
         interrupt of the session's queued or live turn, which this same round's `_apply_controls` applies."""
-        from .csm_serve import SpeechSpan, _claim
-
         sr = int(self.engine.sample_rate)
         # tables land in the order of their steps, the status is cumulative and a record stays in the log until it is acked: the newest
         # table that has landed says everything the older ones say, so those are let go unread
@@ -581,9 +532,7 @@ class ContinuousMixin:
                         u = CSMUtterance(lis, max(0, onset_frame * fl - lis.cfg.pre_roll(sr)), onset_frame)
                         lis._utts.append(u)
                         made.append(u)
-                        turn = lis.session._turn if (lis.barge_in and lis.session is not None) else None
-                        if turn is not None and not turn.done():
-                            self._controls.append((turn, "interrupt", None))
+                        self._barge_in(lis)
                         return u
 
                     for r in range(lis._acked, closed):
@@ -599,100 +548,51 @@ class ContinuousMixin:
                     lis._cst, lis._cn = (c, closed, o, s), n24
                 for u in made:
                     lis._uq.put(u)
-                R = lis.rate if lis.rate is not None else sr
                 for u, rec, sp in closed_now:
                     if _claim(u.endpoint):
-                        u.endpoint.set_result(SpeechSpan(start=sp[0], stop=sp[1], onset_frame=rec[0], endpoint_frame=rec[2], sample_rate=R,
-                                                         rate_start=sp[0] * R // sr, rate_stop=-(-sp[1] * R // sr), forced=u.forced))
+                        u.endpoint.set_result(_speech_span(sp, rec[0], rec[2], lis.rate, sr, forced=u.forced))
 
     def _cont_encode(self, group, F: int) -> None:
         """One step of the row encoder: F frames of every utterance of `group`, read out of the rings by ONE ring read -- S[start:stop],
-        and zeros, not what the ring holds there, behind `stop`."""
+        and zeros, not what the ring holds there, behind `stop`.  A failure fails the group's microphones."""
         lises = [lis for lis, _ in group]
-        try:
-            spf = lises[0].spf
+
+        def fill():
             x = torch.zeros((self.listen_rows, 1, F * spf), dtype=torch.float32, device=self.engine.device)
-            active = [False] * self.listen_rows
             pos, n, tot = [0] * self.listen_rows, [0] * self.listen_rows, [0] * self.listen_rows
             for lis, u in group:
-                if u._fresh:  # a new stream starts in the row: zero carried state, position 0
-                    self._enc.reset_row(lis.row)
-                    u._fresh = False
                 a = u._start + u.frames * spf
                 b = a + F * spf if not u._final else min(a + F * spf, u._stop)
-                pos[lis.row], n[lis.row], tot[lis.row], active[lis.row] = a, b - a, F * spf, True
+                pos[lis.row], n[lis.row], tot[lis.row] = a, b - a, F * spf
             self.engine.ring_read(self._heard, lises[0].ring_len, x.view(self.listen_rows, F * spf), pos, n, tot)
-            out: List[torch.Tensor] = []
-            self._timed("listen", lambda: out.append(self._enc.step(x, active)))
-            self.stats["listen_rounds"] += 1
-            self.stats["listen_frames"] += F * len(group)
-            with self._lock:
-                for lis, u in group:
-                    u._codes.append(out[0][lis.row].clone())
-                    u.steps.append(F)
-                    u.frames += F
-                    lis.frames += F
+            return x
+
+        try:
+            spf = lises[0].spf
+            self._encode_step([(lis.row, u) for lis, u in group], F, fill)
         except Exception as e:  # noqa: BLE001
             for lis in lises:
-                self._cont_fail(lis, e)
+                lis._shut(e)
 
     def _cont_drop(self, lis: CSMContinuousListener, u: CSMUtterance) -> None:
-        with self._lock:
-            if lis._utts and lis._utts[0] is u:
-                lis._utts.popleft()
-            u.dropped = u._done = True
+        self._cont_pop(lis, u, dropped=True)
         u.endpoint.cancel()  # (no effect on one that has resolved)
 
     def _cont_finish(self, lis: CSMContinuousListener, u: CSMUtterance) -> None:
         """A final utterance has all its frames and its `end()`: its audio S[start:stop] leaves the ring for a session's history, the
         result resolves, and its room in the ring and the encoder row are the next one's."""
-        from .csm_serve import ListenResult, _claim
+        k = u._stop - u._start
 
-        fut = u._future
-        if not _claim(fut):
-            self._cont_pop(lis, u)
-            return
-        try:
-            codes = torch.cat(u._codes, dim=1)
-            if lis.session is not None:
-                if lis.session._closed:
-                    raise ValueError("end: the session is closed")
-                host = codes.cpu().numpy()
-                k = u._stop - u._start
-                audio = torch.zeros((1, k), dtype=torch.float32, device=self.engine.device)
-                self.engine.ring_read(self._heard[lis.row : lis.row + 1], lis.ring_len, audio, [u._start], [k], [k])
-                seg = self.engine.heard_segment(lis.speaker, u._text, audio[0].cpu().numpy())
-                lis.session._hear(seg, host)  # before the result: whoever waits on it finds the turn in the history
-            self._cont_pop(lis, u)
-            fut.set_result(ListenResult(codes=codes, frames=u.frames, samples=u._stop - u._start, steps=list(u.steps),
-                                        sample_rate=int(self.engine.sample_rate), speech_start=u._start, speech_stop=u._stop))
-        except Exception as e:  # noqa: BLE001
-            self._cont_pop(lis, u)
-            fut.set_exception(e)
-            if lis.session is not None and lis.session._closed:
-                lis.session.close()
+        def audio():
+            out = torch.zeros((1, k), dtype=torch.float32, device=self.engine.device)
+            self.engine.ring_read(self._heard[lis.row : lis.row + 1], lis.ring_len, out, [u._start], [k], [k])
+            return out[0].cpu().numpy()
 
-    def _cont_pop(self, lis: CSMContinuousListener, u: CSMUtterance) -> None:
+        self._heard_turn(u, lis, audio, dict(samples=k, sample_rate=int(self.engine.sample_rate), speech_start=u._start, speech_stop=u._stop),
+                         release=lambda: self._cont_pop(lis, u))
+
+    def _cont_pop(self, lis: CSMContinuousListener, u: CSMUtterance, dropped: bool = False) -> None:
         with self._lock:
             if lis._utts and lis._utts[0] is u:
                 lis._utts.popleft()
-            u._done = True
-
-    def _cont_close(self, listeners) -> None:
-        """`CSMBatcher.close`: whoever waits on a continuous listener is told."""
-        for lis in listeners:
-            if not getattr(lis, "continuous", False):
-                continue
-            for u in list(lis._utts):
-                u._done = True
-                u.endpoint.cancel()
-                if u._future is not None and not u._future.done():
-                    try:
-                        u._future.set_exception(RuntimeError("CSMBatcher is closed"))
-                    except InvalidStateError:
-                        pass
-            lis._utts.clear()
-            lis._uq.put(_END)
-        self._cont_out.clear()
-        if self._rvad is not None:
-            self._rvad.close()
+            u.dropped, u._done = u.dropped or dropped, True
