@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 15  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 16  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -51,7 +51,9 @@ extern "C" {
                             14: Whisper's audio side (kk_op_log_mel, kk_op_attention_long, kk_whisper_create, kk_whisper_destroy, kk_whisper_load_tensor,
                                kk_whisper_finalize, kk_whisper_encode_workspace_bytes, kk_whisper_encode);
                             15: Whisper's text side (kk_op_whisper_attn_rows, kk_op_whisper_linear_rows, kk_op_whisper_embed, kk_op_whisper_pick,
-                               kk_op_whisper_pick_reset, kk_whisper_text_*) */
+                               kk_op_whisper_pick_reset, kk_whisper_text_*);
+                            16: Whisper's token timestamps (kk_op_whisper_qk_rows, kk_op_whisper_align_matrix, kk_op_whisper_dtw with their
+                               ..._workspace_bytes, kk_op_whisper_median_filter, kk_whisper_text_forward_qk, kk_whisper_text_qk_bytes) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -828,6 +830,45 @@ int kk_whisper_text_pick(kk_whisper_text* m, void* stream);
 /* read back (HOST destinations, synchronise): the count of rows not ended; the token buffers [B][cap] and the rows' states [B] */
 int kk_whisper_text_not_ended(kk_whisper_text* m, void* stream, int32_t* out);
 int kk_whisper_text_read(kk_whisper_text* m, void* stream, int32_t* tokens, int cap, kk_whisper_pick_state* rows);
+
+/* =====================================================================================================================
+ * Whisper, token timestamps from cross-attention: timing.py:19-100, 143-157 and Model.forward_with_cross_qk (csrc/kk_whisper_align.hip,
+ * DESIGN 8h).  Device pointers unless stated, work enqueued on `stream`, 0 = OK.  An item's bits depend on that item's inputs alone.
+ * ===================================================================================================================== */
+/* Raw cross-attention scores (whisper.py:125-130, before the softmax): q fp32 [items * rows][heads * 64], 16-byte aligned; k bf16
+ * [items][T_rows][ld] with the keys at channel 0 (the cross store of the text handle, ld = 2 * n_text_state); sel: HOST int32 [n_sel], the
+ * heads wanted, any order.  out fp32 [n_sel][items * rows][ldo]: out[j][r][key] = 64^-0.5 q[r][sel[j]] . k[r / rows][key][sel[j]] for
+ * key < n_keys <= T_rows; keys at or past n_keys are neither read nor written.  Needs no workspace (the size entry returns 0). */
+size_t kk_op_whisper_qk_rows_workspace_bytes(int items, int rows, int n_sel, int n_keys);
+int kk_op_whisper_qk_rows(void* stream, int items, int rows, int heads, const float* q, const void* k, int T_rows, int ld, const int32_t* sel, int n_sel,
+                          int n_keys, float* out, long long ldo);
+/* timing.py:147-155 per item b: softmax over the first n_frames[b] columns of qk * qk_scale for each of n_heads heads and n_rows[b] rows,
+ * per (head, column) the mean and population deviation over the rows and (w - mean) / deviation, a median filter of odd width
+ * medfilt_width in 1 .. 31 along the columns with reflect padding (skipped when n_frames[b] <= medfilt_width / 2), the mean over the heads
+ * summed in head order.  qk fp32 at qk[b * stride_b + h * stride_h + r * ld_in + c]; n_rows, n_frames device int32 [B], each within
+ * [1, rows_max] and [1, cols_max] (read back and checked: the entry synchronises).  out fp32 [B][rows_max][ld_out]; cells behind an item's
+ * rows and frames are not written.  group: heads per pass (0: the default); the workspace holds one group and the result's bits do not
+ * depend on it. */
+size_t kk_op_whisper_align_matrix_workspace_bytes(int B, int n_heads, int rows_max, int cols_max, int group);
+int kk_op_whisper_align_matrix(void* stream, int B, int n_heads, const float* qk, long long stride_b, long long stride_h, int ld_in, const int32_t* n_rows,
+                               int rows_max, const int32_t* n_frames, int cols_max, float qk_scale, int medfilt_width, int group, float* out, int ld_out,
+                               void* workspace, size_t workspace_bytes);
+/* timing.py:19-44 on its own: out[r][c] = the median of the reflect-padded window of odd `width` in 1 .. 31 around x[r][c], rows of n values
+ * (n > width / 2; the reference returns shorter rows unfiltered, so does the Python caller), fp32, row pitches ldx and ldo */
+int kk_op_whisper_median_filter(void* stream, long long rows, int n, const float* x, long long ldx, int width, float* out, long long ldo);
+/* timing.py:47-95 per item b on x[b] (n_rows[b] x n_cols[b] of fp32 [B][..][ld] at item stride stride_b; negate: on -x): fp32 costs, the
+ * reference's tie rule, its backtrace.  text_indices, time_indices int32 [B][rows_max + cols_max]: the path in forward order, length[b]
+ * entries; first_cols int32 [B][rows_max]: per row the column of the path's first entry there (time_indices[jumps]).  n_rows, n_cols device
+ * int32 [B] within [1, rows_max] and [1, cols_max] (read back and checked: the entry synchronises); cols_max at most 15360. */
+size_t kk_op_whisper_dtw_workspace_bytes(int B, int rows_max, int cols_max);
+int kk_op_whisper_dtw(void* stream, int B, const float* x, long long stride_b, int ld, const int32_t* n_rows, int rows_max, const int32_t* n_cols, int cols_max,
+                      int negate, int32_t* text_indices, int32_t* time_indices, int32_t* length, int32_t* first_cols, void* workspace, size_t workspace_bytes);
+/* kk_whisper_text_forward with all_positions = 1 that also captures: pairs HOST int32 [n_pairs][2] of (layer, head); after each listed
+ * layer's cross_attn.query Linear the raw scores of its listed heads go to qk_out fp32 [B][n_pairs][S][n_keys], pair p in slot p.  The
+ * logits are the bits of the plain forward.  qk_bytes: at least what the size entry returns.  workspace: as for the plain forward. */
+size_t kk_whisper_text_qk_bytes(const kk_whisper_text* m, int B, int S, int n_pairs, int n_keys);
+int kk_whisper_text_forward_qk(kk_whisper_text* m, void* stream, int B, int S, const int32_t* tokens, float* logits_out, const int32_t* pairs, int n_pairs,
+                               int n_keys, float* qk_out, size_t qk_bytes, void* workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

@@ -243,6 +243,15 @@ SIGNATURES = {
     "kk_whisper_text_pick": (_i, [_vp, _vp]),
     "kk_whisper_text_not_ended": (_i, [_vp, _vp, C.POINTER(C.c_int32)]),
     "kk_whisper_text_read": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "kk_op_whisper_qk_rows_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "kk_op_whisper_qk_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, C.c_longlong]),
+    "kk_op_whisper_align_matrix_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "kk_op_whisper_align_matrix": (_i, [_vp, _i, _i, _vp, C.c_longlong, C.c_longlong, _i, _vp, _i, _vp, _i, _f, _i, _i, _vp, _i, _vp, _sz]),
+    "kk_op_whisper_median_filter": (_i, [_vp, C.c_longlong, _i, _vp, C.c_longlong, _i, _vp, C.c_longlong]),
+    "kk_op_whisper_dtw_workspace_bytes": (_sz, [_i, _i, _i]),
+    "kk_op_whisper_dtw": (_i, [_vp, _i, _vp, C.c_longlong, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "kk_whisper_text_qk_bytes": (_sz, [_vp, _i, _i, _i, _i]),
+    "kk_whisper_text_forward_qk": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz]),
     "kk_mimi_debug_info": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "kk_mimi_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
     "kk_debug_set_op_wfrag": (None, [_vp]),
@@ -289,7 +298,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 15:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 16:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

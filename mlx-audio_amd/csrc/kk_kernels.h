@@ -324,3 +324,13 @@ int kk_launch_rope_append_rows(float* qkv, int S, int H, int KV, int hd, const f
                                int max_pos, int B, hipStream_t st);
 int kk_launch_attn_cache_rows(const float* qkv, int S, int H, int KV, int hd, const int* row_pos, const int* active, const float* kc, const float* vc,
                               int max_pos, float scale, float* out, int ctx, int B, hipStream_t st);
+
+// ---- Whisper alignment (kk_whisper_align.hip): raw cross-attention scores of selected heads, launched by the text handle's capturing forward
+struct KKQkSel {  // up to 32 heads of one layer per launch: head[j] goes to output slot slot[j]
+  int n;
+  int head[32], slot[32];
+};
+// out[slot * stride_slot + item * stride_item + r * ldo + key] = 64^-0.5 q[item * rows + r][head] . k[item][key][head], keys 0 .. n_keys - 1;
+// q fp32 [items * rows][heads * 64], k bf16 at channel 0 of [items][item_stride / ld][ld]
+int kk_launch_whisper_qk_rows(hipStream_t st, const float* q, const bf16_t* k, long long item_stride, int ld, int heads, int items, int rows, int n_keys,
+                              const KKQkSel& sel, float* out, long long stride_slot, long long stride_item, long long ldo);

@@ -718,12 +718,20 @@ extern "C" int kk_whisper_text_rewind(kk_whisper_text* m, int position) {
   return 0;
 }
 
-extern "C" int kk_whisper_text_forward(kk_whisper_text* m, void* stream, int B, int S, const int32_t* tokens, float* logits_out, int all_positions,
-                                       void* workspace, size_t workspace_bytes) {
-  if (!m || !logits_out || !workspace || B < 1 || S < 1) return kk_fail("kk_whisper_text_forward: bad argument");
-  if (!m->state || B != m->B) return kk_fail("kk_whisper_text_forward: set_audio first, with the same B");
+namespace {
+struct QkCapture {  // the capturing forward: raw cross-attention scores of the listed (layer, head) pairs, pair p into qk_out[b][p][s][n_keys]
+  const int32_t* pairs;  // host [n_pairs][2]
+  int n_pairs, n_keys;
+  float* qk_out;
+};
+
+// the one layer loop behind kk_whisper_text_forward and kk_whisper_text_forward_qk (cap == null: nothing is captured, the launches are those of the plain forward)
+int text_forward(const char* who, kk_whisper_text* m, void* stream, int B, int S, const int32_t* tokens, float* logits_out, int all_positions, void* workspace,
+                 size_t workspace_bytes, const QkCapture* cap) {
+  if (!m || !logits_out || !workspace || B < 1 || S < 1) return kk_failf("%s: bad argument", who);
+  if (!m->state || B != m->B) return kk_failf("%s: set_audio first, with the same B", who);
   const kk_whisper_text_config& c = m->cfg;
-  if (m->at + S > c.n_text_ctx) return kk_failf("kk_whisper_text_forward: position %d + %d tokens exceeds n_text_ctx = %d", m->at, S, c.n_text_ctx);
+  if (m->at + S > c.n_text_ctx) return kk_failf("%s: position %d + %d tokens exceeds n_text_ctx = %d", who, m->at, S, c.n_text_ctx);
   const int D = c.n_text_state, H = c.n_text_head, V = c.n_vocab, R = B * S;
   hipStream_t st = (hipStream_t)stream;
   Workspace ss, ws;
@@ -733,9 +741,9 @@ extern "C" int kk_whisper_text_forward(kk_whisper_text* m, void* stream, int B, 
   TextWork p;
   plan_state(c, B, ss, s);
   plan_work(c, B, S, ws, p);
-  if (ws.oom) return kk_fail("kk_whisper_text_forward: workspace too small");
+  if (ws.oom) return kk_failf("%s: workspace too small", who);
   if (!tokens) {  // the step after a pick: the tokens it chose
-    if (S != 1) return kk_fail("kk_whisper_text_forward: tokens may be null only for S = 1 (the tokens of the last pick)");
+    if (S != 1) return kk_failf("%s: tokens may be null only for S = 1 (the tokens of the last pick)", who);
     tokens = s.next;
   }
   hipLaunchKernelGGL(text_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, st, B, S, m->at, c.n_text_ctx, c.n_audio_ctx, p.item, p.posr, p.len_self, p.len_cross,
@@ -773,6 +781,21 @@ extern "C" int kk_whisper_text_forward(kk_whisper_text* m, void* stream, int B, 
     KK_TRY(lin(L.out, 0, D, p.att, D, R, KK_ACT_NONE, p.x, p.x, D, nullptr, nullptr));
     KK_TRY(ln(L.cross_ln_w, L.cross_ln_b, p.x, D, R));
     KK_TRY(lin(L.cq, 0, D, p.ln, D, R, KK_ACT_NONE, nullptr, p.q, D, nullptr, nullptr));
+    if (cap) {  // this layer's listed heads, 32 to a launch, each into the slot of its pair
+      KKQkSel sel;
+      sel.n = 0;
+      for (int pi = 0; pi <= cap->n_pairs; ++pi) {
+        if (pi < cap->n_pairs && cap->pairs[2 * pi] == li) {
+          sel.head[sel.n] = cap->pairs[2 * pi + 1];
+          sel.slot[sel.n++] = pi;
+        }
+        if (sel.n == 32 || (pi == cap->n_pairs && sel.n > 0)) {
+          KK_TRY(kk_launch_whisper_qk_rows(st, p.q, crossc, (long long)c.n_audio_ctx * 2 * D, 2 * D, H, B, S, cap->n_keys, sel, cap->qk_out,
+                                           (long long)S * cap->n_keys, (long long)cap->n_pairs * S * cap->n_keys, cap->n_keys));
+          sel.n = 0;
+        }
+      }
+    }
     KK_TRY(launch_attn_rows(st, R, H, p.q, crossc, 0, D, B, c.n_audio_ctx, 2 * D, p.item, p.len_cross, p.att, p.scratch));
     KK_TRY(lin(L.cout, 0, D, p.att, D, R, KK_ACT_NONE, p.x, p.x, D, nullptr, nullptr));
     KK_TRY(ln(L.mlp_ln_w, L.mlp_ln_b, p.x, D, R));
@@ -793,6 +816,32 @@ extern "C" int kk_whisper_text_forward(kk_whisper_text* m, void* stream, int B, 
   }
   m->at += S;
   return 0;
+}
+}  // namespace
+
+extern "C" int kk_whisper_text_forward(kk_whisper_text* m, void* stream, int B, int S, const int32_t* tokens, float* logits_out, int all_positions,
+                                       void* workspace, size_t workspace_bytes) {
+  return text_forward("kk_whisper_text_forward", m, stream, B, S, tokens, logits_out, all_positions, workspace, workspace_bytes, nullptr);
+}
+
+extern "C" size_t kk_whisper_text_qk_bytes(const kk_whisper_text* m, int B, int S, int n_pairs, int n_keys) {
+  if (!m || B < 1 || S < 1 || n_pairs < 1 || n_keys < 1 || n_keys > m->cfg.n_audio_ctx) return 0;
+  return (size_t)B * n_pairs * S * n_keys * sizeof(float);
+}
+
+extern "C" int kk_whisper_text_forward_qk(kk_whisper_text* m, void* stream, int B, int S, const int32_t* tokens, float* logits_out, const int32_t* pairs,
+                                          int n_pairs, int n_keys, float* qk_out, size_t qk_bytes, void* workspace, size_t workspace_bytes) {
+  const char* who = "kk_whisper_text_forward_qk";
+  if (!m || !tokens || !pairs || !qk_out || n_pairs < 1) return kk_failf("%s: bad argument", who);
+  const kk_whisper_text_config& c = m->cfg;
+  if (n_keys < 1 || n_keys > c.n_audio_ctx) return kk_failf("%s: n_keys = %d is outside [1, n_audio_ctx = %d]", who, n_keys, c.n_audio_ctx);
+  for (int pi = 0; pi < n_pairs; ++pi)
+    if (pairs[2 * pi] < 0 || pairs[2 * pi] >= c.n_text_layer || pairs[2 * pi + 1] < 0 || pairs[2 * pi + 1] >= c.n_text_head)
+      return kk_failf("%s: pair %d = (layer %d, head %d) is outside the decoder's %d layers of %d heads", who, pi, pairs[2 * pi], pairs[2 * pi + 1], c.n_text_layer,
+                      c.n_text_head);
+  if (B < 1 || S < 1 || qk_bytes < kk_whisper_text_qk_bytes(m, B, S, n_pairs, n_keys)) return kk_failf("%s: qk_out too small", who);
+  const QkCapture cap{pairs, n_pairs, n_keys, qk_out};
+  return text_forward(who, m, stream, B, S, tokens, logits_out, 1, workspace, workspace_bytes, &cap);
 }
 
 extern "C" int kk_whisper_text_pick_setup(kk_whisper_text* m, void* stream, const kk_whisper_pick_params* params, const uint32_t* suppress) {

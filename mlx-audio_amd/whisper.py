@@ -4,12 +4,19 @@ level, `logits`, `detect_language` and `decode` (whisper.py:298, decoding.py; th
 and are re-exported here).  The arithmetic runs in libkokoro_hip.so (kk_op_log_mel, kk_whisper_*, csrc/kk_whisper.hip; kk_whisper_text_*,
 kk_op_whisper_*, csrc/kk_whisper_text.hip); PyTorch allocates device memory and provides the stream.
 
-The text side is built when a checkpoint holds the COMPLETE `decoder.*` set; otherwise the model is encoder-only and `logits`, `decode` and
-`detect_language` raise NotImplementedError("text decoder: not built").  `generate` (transcription of long audio, which needs the tokenizer) is not
-built.  `Model.decoder_weights` keeps the non-encoder tensors of a checkpoint on the host, untouched, either way."""
+The text side is built when a checkpoint holds the COMPLETE `decoder.*` set; otherwise the model is encoder-only and `logits`, `decode`,
+`detect_language`, `forward_with_cross_qk` and the alignment heads raise NotImplementedError("text decoder: not built").  `generate` (transcription of
+long audio, which needs the tokenizer) is not built.  `Model.decoder_weights` keeps the non-encoder tensors of a checkpoint on the host, untouched,
+either way -- an `alignment_heads` entry included: the heads are set with `set_alignment_heads`, never parsed from a checkpoint.
+
+Token timestamps (`Model.alignment_heads`, `set_alignment_heads`, `forward_with_cross_qk`, whisper.py:272-303; `find_alignment`, `dtw`, `median_filter`,
+`TokenTiming`, `WordTiming` of whisper_timing.py, re-exported here) run on kk_op_whisper_qk_rows / align_matrix / dtw and kk_whisper_text_forward_qk
+(csrc/kk_whisper_align.hip)."""
 from __future__ import annotations
 
+import base64
 import ctypes as C
+import gzip
 import json
 import math
 from dataclasses import dataclass, fields
@@ -31,6 +38,7 @@ TOKENS_PER_SECOND = SAMPLE_RATE // N_SAMPLES_PER_TOKEN  # 20 ms per audio token
 
 from .whisper_decoding import (NOT_BUILT as _NOT_BUILT, DecodingOptions, DecodingResult, SpecialTokens, decoder_shapes,  # noqa: E402,F401
                                decoder_tensors, special_tokens)
+from .whisper_timing import TokenTiming, WordTiming, dtw, find_alignment, median_filter  # noqa: E402,F401
 
 
 def _is_torch(a) -> bool:
@@ -251,6 +259,7 @@ class Model:
         self._ws = None
         self._lib = None
         self._text = None
+        self._alignment_heads = None  # the default is made on first use
 
     # ---- weights ---------------------------------------------------------------------------------------------------------------------
     def load_weights(self, weights: dict) -> "Model":
@@ -355,6 +364,65 @@ class Model:
         with torch.cuda.device(self.device):
             self._text.set_audio(feats.to(device=self.device, dtype=torch.float32).contiguous())
             return self._text.forward(tokens.to(device=self.device, dtype=torch.int32).contiguous(), True)
+
+    # ---- token timestamps (whisper.py:272-303) ------------------------------------------------------------------------------------------
+    @property
+    def alignment_heads(self) -> np.ndarray:
+        """int array (n, 2) of (layer, head); by default every head of the upper half of the decoder's layers (whisper.py:274-278)"""
+        if self._text is None:
+            raise NotImplementedError(_NOT_BUILT)
+        if self._alignment_heads is None:
+            all_heads = np.zeros((self.dims.n_text_layer, self.dims.n_text_head), dtype=bool)
+            all_heads[self.dims.n_text_layer // 2:] = True
+            self._alignment_heads = np.asarray(all_heads.nonzero()).T.astype(np.int64)
+        return self._alignment_heads
+
+    def set_alignment_heads(self, dump):
+        """whisper.py:280-293: an int array (n, 2), or the base85-encoded gzip of a boolean (n_text_layer, n_text_head) mask"""
+        if self._text is None:
+            raise NotImplementedError(_NOT_BUILT)
+        d = self.dims
+        if isinstance(dump, np.ndarray):
+            heads = np.asarray(dump)
+            if heads.ndim != 2 or heads.shape[1] != 2 or heads.shape[0] < 1 or heads.dtype.kind not in "iu":
+                raise ValueError("alignment heads must be a non-empty integer array of shape (n, 2)")
+            heads = heads.astype(np.int64)
+        elif isinstance(dump, bytes):
+            array = np.frombuffer(gzip.decompress(base64.b85decode(dump)), dtype=bool).copy()
+            if array.size != d.n_text_layer * d.n_text_head:
+                raise ValueError(f"the alignment-head mask holds {array.size} entries, the decoder has {d.n_text_layer} x {d.n_text_head} heads")
+            heads = np.asarray(array.reshape(d.n_text_layer, d.n_text_head).nonzero()).T.astype(np.int64)
+            if heads.shape[0] < 1:
+                raise ValueError("the alignment-head mask selects no head")
+        else:
+            raise ValueError(f"Invalid type for `dump`: {type(dump)}. Expected a np.ndarray or base85-encoded bytes containing"
+                             " alignment_head information")
+        if (heads < 0).any() or (heads[:, 0] >= d.n_text_layer).any() or (heads[:, 1] >= d.n_text_head).any():
+            raise ValueError(f"alignment heads outside the decoder's {d.n_text_layer} layers of {d.n_text_head} heads")
+        self._alignment_heads = heads
+
+    def forward_with_cross_qk(self, mel_or_features, tokens):
+        """whisper.py:301-303: a mel (B, 2 n_audio_ctx, n_mels) or audio features (B, n_audio_ctx, n_audio_state), tokens (B, S) ints ->
+        (logits fp32 device (B, S, n_vocab), [per layer: the raw cross-attention scores, fp32 device (B, n_text_head, S, n_audio_ctx)])"""
+        if self._text is None:
+            raise NotImplementedError(_NOT_BUILT)
+        import torch
+
+        from .whisper_decoding import _features
+
+        d = self.dims
+        tokens = torch.as_tensor(tokens)
+        if tokens.ndim != 2 or not 1 <= tokens.shape[1] <= d.n_text_ctx:
+            raise ValueError(f"forward_with_cross_qk takes tokens (B, S) with 1 <= S <= n_text_ctx = {d.n_text_ctx}")
+        feats, _ = _features(self, mel_or_features)
+        if feats.shape[0] != tokens.shape[0]:
+            raise ValueError("forward_with_cross_qk: the batch sizes of the audio and of the tokens differ")
+        pairs = np.asarray([(l, h) for l in range(d.n_text_layer) for h in range(d.n_text_head)], np.int32)
+        with torch.cuda.device(self.device):
+            self._text.set_audio(feats)
+            logits, qk = self._text.forward_qk(tokens.to(device=self.device, dtype=torch.int32).contiguous(), pairs, d.n_audio_ctx)
+        qk = qk.view(tokens.shape[0], d.n_text_layer, d.n_text_head, tokens.shape[1], d.n_audio_ctx)
+        return logits, [qk[:, l] for l in range(d.n_text_layer)]
 
     def decode(self, *a, **kw):
         """decoding.py:710-742 at token level, see whisper_decoding.decode"""

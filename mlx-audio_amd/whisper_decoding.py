@@ -5,6 +5,7 @@ launch per step that applies the logit filters, takes the arg-maximum and the lo
 looks at a device counter of unfinished rows every `eos_check_interval` steps.
 
 There is no tokenizer here (the vocabulary files are not part of this repository): tokens go in and come out as ids, `DecodingResult.text` stays "".
+`TextRuntime.forward_qk` is the forward that also hands out raw cross-attention scores; the token timestamps made from them live in whisper_timing.py.
 """
 from __future__ import annotations
 
@@ -298,6 +299,25 @@ class TextRuntime:
                                                      ws, wsn), "kk_whisper_text_forward")
         self._last = out  # the pick that follows reads it
         return out
+
+    def forward_qk(self, tokens, pairs, n_keys: int):
+        """the capturing forward: tokens int32 device (B, S), pairs an int array (n, 2) of (layer, head) -> (logits fp32 (B, S, V), the raw cross-attention
+        scores 64^-0.5 q k of the pairs, fp32 (B, n, S, n_keys)); the logits are the bits of forward(tokens, True)"""
+        import torch
+
+        from . import _lib
+
+        B, S = tokens.shape
+        pairs = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+        n = int(pairs.shape[0])
+        out = torch.empty((B, S, self.dims.n_vocab), dtype=torch.float32, device=self.device)
+        qk = torch.empty((B, n, S, n_keys), dtype=torch.float32, device=self.device)
+        ws, wsn = self._workspace(B, S)
+        _lib.check(self._lib.kk_whisper_text_forward_qk(self._h, self._stream(), B, S, C.c_void_p(tokens.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                        pairs.ctypes.data_as(C.c_void_p), n, int(n_keys), C.c_void_p(qk.data_ptr()), qk.numel() * 4, ws, wsn),
+                   "kk_whisper_text_forward_qk")
+        self._last = out
+        return out, qk
 
     def step(self):
         """one position on the tokens the last pick chose; the logits stay in a buffer the runtime keeps"""

@@ -8,7 +8,14 @@ The per-step share of each kernel family comes from a run of its own under the p
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o k -- python tools/bench_whisper_text.py --only-steps 200 --batch 8
     python tools/bench_whisper_text.py --digest DIR/.../k_kernel_trace.csv --digest-steps 200 --batch 8 [--out the bench's file: appended]
 
-Usage:  python tools/bench_whisper_text.py [--steps 20] [--warmup 3] [--inner 20] [--position 64] [--out profiles/whisper_text_bench.json]"""
+`--align` times the token-timestamp path instead (mlx-audio_amd/whisper_timing.py, csrc/kk_whisper_align.hip) at the same shape: a 448-token
+sequence (443 text tokens, 444 warped rows) against 1500 frames with the default alignment heads (the upper two layers, 40 heads), B = 1 and 8 -- the
+capturing forward, `align_matrix`, and the DTW with its backtrace, each between device events of its own (the two raw entries read their row and column
+counts back, so their figures include that round trip).  The kernels' own durations come from a profiler run of its own:
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o k -- python tools/bench_whisper_text.py --align --only-steps 20 --batch 8
+
+Usage:  python tools/bench_whisper_text.py [--steps 20] [--warmup 3] [--inner 20] [--position 64] [--out profiles/whisper_text_bench.json]
+        python tools/bench_whisper_text.py --align [--steps 20] [--warmup 3] [--out profiles/whisper_align_bench.json]"""
 import argparse
 import csv
 import json
@@ -96,6 +103,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--only-steps", type=int, default=0, help="run this many decode steps and nothing else (the profiler's run)")
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--align", action="store_true", help="time the token-timestamp path (capturing forward, align_matrix, dtw) instead of the decode step")
     ap.add_argument("--digest", default=None)
     ap.add_argument("--digest-steps", type=int, default=200)
     a = ap.parse_args()
@@ -139,7 +147,7 @@ def main():
         rt.step()
         rt.pick()
 
-    if a.only_steps:
+    if a.only_steps and not a.align:
         begin(a.batch)
         for _ in range(a.only_steps):
             step()
@@ -167,6 +175,57 @@ def main():
         results.append(r)
         print(json.dumps(r), flush=True)
 
+    def write_out():
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(dict(device=torch.cuda.get_device_name(0), shape=dict(ctx=CTX, width=WIDTH, heads=HEADS, layers=LAYERS, n_vocab=VOCAB, n_text_ctx=TEXT_CTX),
+                               results=results), f, indent=1)
+                f.write("\n")
+
+    if a.align:
+        from mlx_audio_amd import whisper_timing as WT
+
+        heads = model.alignment_heads
+        text = [int(t) for t in np.random.default_rng(3).integers(0, tok.eot, TEXT_CTX - 5)]  # sot, language, task, no_timestamps, 443 text tokens, eot
+        seq, r0, r1 = WT.alignment_tokens(d, text)
+        for B in ((a.batch,) if a.only_steps else (1, 8)):
+            feats = torch.randn((B, CTX, WIDTH), generator=torch.Generator().manual_seed(B)).cuda()
+            rt.set_audio(feats)
+            toks = torch.tensor([seq] * B, dtype=torch.int32).cuda()
+            rows, frames = [len(seq)] * B, [CTX] * B
+            state = {}
+
+            def forward():
+                rt.rewind(0)
+                state["qk"] = rt.forward_qk(toks, heads, CTX)[1]
+
+            def plain():
+                rt.rewind(0)
+                rt.forward(toks, True)
+
+            def matrix():
+                state["mat"] = WT.align_matrix_rows(state["qk"], rows, frames, 7, 1.0)
+
+            def warp():
+                state["path"] = WT.dtw_rows(state["warped"], [r1 - r0] * B, frames, negate=True)
+
+            if a.only_steps:  # the profiler's run: the three stages back to back and nothing else
+                for _ in range(a.only_steps):
+                    forward()
+                    matrix()
+                    state["warped"] = state["mat"][:, r0:r1].contiguous()
+                    warp()
+                torch.cuda.synchronize()
+                return
+            emit(dict(case="align_forward_plain", B=B, tokens=len(seq), **timed(plain, 1)))
+            emit(dict(case="align_forward_qk", B=B, tokens=len(seq), pairs=int(heads.shape[0]), n_keys=CTX, **timed(forward, 1)))
+            emit(dict(case="align_matrix", B=B, heads=int(heads.shape[0]), rows=len(seq), frames=CTX, medfilt_width=7, **timed(matrix, 1)))
+            state["warped"] = state["mat"][:, r0:r1].contiguous()
+            r = timed(warp, 1)
+            emit(dict(case="align_dtw_and_backtrace", B=B, rows=r1 - r0, frames=CTX, path_length=int(state["path"][2][0]), **r))
+        write_out()
+        return
+
     for B in (1, 8):
         feats = begin(B)
         emit(dict(case="set_audio", B=B, **timed(lambda: rt.set_audio(feats), 1)))
@@ -190,11 +249,7 @@ def main():
 
         emit(dict(case="decode_step_forward_only", B=B, position=a.position, **timed(forward_only, a.inner)))
         emit(dict(case="pick_only", B=B, **timed(rt.pick, a.inner)))
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(dict(device=torch.cuda.get_device_name(0), shape=dict(ctx=CTX, width=WIDTH, heads=HEADS, layers=LAYERS, n_vocab=VOCAB, n_text_ctx=TEXT_CTX),
-                           results=results), f, indent=1)
-            f.write("\n")
+    write_out()
 
 
 if __name__ == "__main__":
