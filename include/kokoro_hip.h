@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 16  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 17  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -53,7 +53,8 @@ extern "C" {
                             15: Whisper's text side (kk_op_whisper_attn_rows, kk_op_whisper_linear_rows, kk_op_whisper_embed, kk_op_whisper_pick,
                                kk_op_whisper_pick_reset, kk_whisper_text_*);
                             16: Whisper's token timestamps (kk_op_whisper_qk_rows, kk_op_whisper_align_matrix, kk_op_whisper_dtw with their
-                               ..._workspace_bytes, kk_op_whisper_median_filter, kk_whisper_text_forward_qk, kk_whisper_text_qk_bytes) */
+                               ..._workspace_bytes, kk_op_whisper_median_filter, kk_whisper_text_forward_qk, kk_whisper_text_qk_bytes);
+                            17: the cache attention's block forms on caller-owned buffers (kk_op_attn_cache_block) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -715,6 +716,11 @@ int kk_op_csm_attn_single(void* stream, int form, int B, int H, int KV, int hd, 
 /* a block of S new positions per item: RoPE (q in place) + append at slots offset .. offset + S - 1, then causal attention -> out [B][S][H hd] */
 int kk_op_csm_attn_prompt(void* stream, int B, int S, int H, int KV, int hd, float* qkv, float* kc, float* vc, int max_pos, int offset, const float* rope,
                           const int32_t* pad, float* out);
+/* the block forms Mimi's streaming transformer runs (no causal mask inside the block; ctx >= 0: only the last ctx cached keys + the block):
+ * row_pos == NULL: RoPE + append at `offset` for every item, then the attention (kk_launch_rope_append + kk_launch_attn_cache);
+ * otherwise item b sits at row_pos[b] and takes part only if active[b] != 0 (both device, [B]; `offset` unused): the per-row forms */
+int kk_op_attn_cache_block(void* stream, int B, int S, int H, int KV, int hd, float* qkv, float* kc, float* vc, int max_pos, int offset,
+                           const int32_t* row_pos, const int32_t* active, const float* rope, int ctx, float* out);
 
 /* =====================================================================================================================
  * Whisper, audio side: log_mel_spectrogram (mlx_audio/stt/models/whisper/audio.py:41-82) and AudioEncoder / Model.embed_audio

@@ -165,6 +165,7 @@ SIGNATURES = {
     "kk_op_csm_linear_skinny": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz]),
     "kk_op_csm_attn_single": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "kk_op_csm_attn_prompt": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "kk_op_attn_cache_block": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "kk_mimi_create": (_i, [C.POINTER(KKMimiConfig), C.POINTER(_vp)]),
     "kk_mimi_destroy": (None, [_vp]),
     "kk_mimi_load_tensor": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), _i, _vp]),
@@ -298,7 +299,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 16:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 17:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -41,36 +41,7 @@ static int wf_group_magic(int group) { return (int)(((1u << 20) + (unsigned)(gro
 static bool wf_group_ok(int K, int group) { return group >= 32 && group % 32 == 0 && K % group == 0 && (long long)(K / 32) * (group / 32) < (1 << 20); }
 
 
-__device__ __forceinline__ void ts_begin(unsigned long long* ts, int id) {
-  if (ts && threadIdx.x == 0) {
-    atomicMin(ts + 1, (unsigned long long)wall_clock64());
-#ifdef KK_TS_PER_WG  // (tools/gridbar/gemvm_bench.hip: every workgroup's own start / end behind the 8 summary words)
-    ts[8 + 2 * (blockIdx.x + 32 * blockIdx.y)] = (unsigned long long)wall_clock64();
-#endif
-    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
-      ts[0] = (unsigned long long)id;
-      ts[4] = (unsigned long long)wall_clock64();
-    }
-  }
-}
-__device__ __forceinline__ void ts_mid(unsigned long long* ts) {
-  if (ts && threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) ts[3] = (unsigned long long)wall_clock64();
-}
-__device__ __forceinline__ void ts_mark(unsigned long long* ts, int k) {  // k = 5, 7: further marks of workgroup 0
-  if (ts && threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) ts[k] = (unsigned long long)wall_clock64();
-}
-__device__ __forceinline__ void ts_end(unsigned long long* ts) {
-  if (ts && threadIdx.x == 0) {
-    atomicMax(ts + 2, (unsigned long long)wall_clock64());
-#ifdef KK_TS_PER_WG
-    ts[9 + 2 * (blockIdx.x + 32 * blockIdx.y)] = (unsigned long long)wall_clock64();
-    ts[8 + 2 * 256 + (blockIdx.x + 32 * blockIdx.y)] = ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | (unsigned)__builtin_amdgcn_s_getreg(63492);  // XCC_ID | HW_ID
-#endif
-    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
-      ts[6] = (unsigned long long)wall_clock64();
-    }
-  }
-}
+#include "kk_ts.h"
 
 // (ids are clamped into their tables on the device: an id outside -- a caller's mistake, or a code sampled from non-finite logits -- reads a
 // valid row instead of faulting the GPU)

@@ -315,7 +315,18 @@ int kk_mxfp8_pack_weight_host(const float* w, int N, int K, int group, unsigned 
 int kk_launch_mxfp8_quant_rows(const void* x_bf16, int ldx, int M, int K, void* aq, void* as, hipStream_t st);
 int kk_launch_linear_mxfp8(const KKFp8Args& a, hipStream_t st);
 
-// ---- KV-cache kernels of kk_csm.hip, shared with Mimi's streaming transformer (kk_mimi.hip)
+// ---- KV-cache attention (kk_attn_cache.hip): the CSM Llama stacks (kk_csm.hip) and Mimi's streaming transformer (kk_mimi.hip)
+// One new position per item, RoPE + cache append inside; `form` picks the kernel (ATTN_AUTO: attn_auto_form).  pos_dev (nullable): the position in
+// device memory, added to `offset`; pad (nullable, [B]): left padding per item; attp: key-split partials, 8 B H (hd + 2) floats; ts: debug
+// timestamp slot of the ATTN_STEP kernel or null.
+enum { ATTN_AUTO = 0, ATTN_STEP = 1, ATTN_DECODE = 2, ATTN_CACHE = 3 };
+inline int attn_auto_form(int G, int max_pos) { return G > 8 ? ATTN_CACHE : (max_pos <= 64 ? ATTN_STEP : ATTN_DECODE); }
+int attn_single(int form, const float* qkv, int B, int H, int KV, int hd, const int* pos_dev, int offset, float* kc, float* vc, int max_pos,
+                const float* rope, const int* pad, float* att, float* attp, unsigned long long* ts, hipStream_t st);
+// a block of S new positions per item: RoPE (q in place in qkv) + cache append, then causal attention of the block over the cache
+int attn_prompt(float* qkv, int B, int S, int H, int KV, int hd, const int* pos_dev, int offset, float* kc, float* vc, int max_pos, const float* rope,
+                const int* pad, float* att, hipStream_t st);
+// the block forms on their own (no device position, no padding; `causal` 0: no mask inside the block; ctx >= 0: the last ctx cached keys + the block)
 int kk_launch_rope_append(float* qkv, int S, int H, int KV, int hd, const float* rope, int offset, float* kc, float* vc, int max_pos, int B, hipStream_t st);
 int kk_launch_attn_cache(const float* qkv, int S, int H, int KV, int hd, int offset, const float* kc, const float* vc, int max_pos, float scale, float* out,
                          int causal, int ctx, int B, hipStream_t st);

@@ -662,10 +662,10 @@ struct StateBuf {
   }
 };
 
-// rows [n, n + S) -> rows [0, S) of every item; the ranges overlap when n < S, so a block reads everything before it writes
+// rows [n, n + S) -> rows [0, S) of one item's buffer `q` ([S + n][C]); the ranges overlap when n < S, so the block reads everything before
+// it writes.  One body for the plain carry (state_shift_kernel) and the masked row-mode one (state_shift_rows_kernel).
 constexpr int SHIFT_PER_THREAD = 32;
-__global__ __launch_bounds__(256) void state_shift_kernel(float* p, int S, int n, int C, long long pitch) {
-  float* q = p + (long long)blockIdx.x * pitch;
+__device__ __forceinline__ void state_shift_body(float* q, int S, int n, int C) {
   const int total = S * C;
   float v[SHIFT_PER_THREAD];
 #pragma unroll
@@ -680,10 +680,15 @@ __global__ __launch_bounds__(256) void state_shift_kernel(float* p, int S, int n
     if (e < total) q[e] = v[k];
   }
 }
+__global__ __launch_bounds__(256) void state_shift_kernel(float* p, int S, int n, int C, long long pitch) {
+  state_shift_body(p + (long long)blockIdx.x * pitch, S, n, C);
+}
 // 'edge' left padding of a fresh resampler state (conv.py:265-281 with pad_mode "edge"): the carried rows repeat the first new row
-__global__ __launch_bounds__(256) void state_edge_fill_kernel(float* p, int S, int n, int C, long long pitch) {
-  float* q = p + (long long)blockIdx.x * pitch;
+__device__ __forceinline__ void state_edge_fill_body(float* q, int S, int C) {
   for (int e = threadIdx.x; e < S * C; e += 256) q[e] = q[(long long)S * C + e % C];
+}
+__global__ __launch_bounds__(256) void state_edge_fill_kernel(float* p, int S, int n, int C, long long pitch) {
+  state_edge_fill_body(p + (long long)blockIdx.x * pitch, S, C);
 }
 
 // the same fill per row of a row-mode encoder stream (grid: one block per row): only a row that is active AND at position 0 -- its first
@@ -692,8 +697,7 @@ __global__ __launch_bounds__(256) void state_edge_fill_kernel(float* p, int S, i
 __global__ __launch_bounds__(256) void state_edge_fill_rows_kernel(float* p, int S, int C, long long pitch, const int* active, const int* pos) {
   const int row = blockIdx.x;
   if (!active[row] || pos[row] != 0) return;
-  float* q = p + (long long)row * pitch;
-  for (int e = threadIdx.x; e < S * C; e += 256) q[e] = q[(long long)S * C + e % C];
+  state_edge_fill_body(p + (long long)row * pitch, S, C);
 }
 
 int state_shift(const StateBuf& b, int B, hipStream_t st) {
@@ -723,20 +727,7 @@ __global__ __launch_bounds__(256) void state_shift_rows_kernel(const RowBuf* tab
   const int row = blockIdx.y;
   if (!active[row]) return;
   const RowBuf t = tab[blockIdx.x];
-  float* q = t.p + (long long)row * t.pitch;
-  const int total = t.S * t.C, n = F * t.npf;
-  float v[SHIFT_PER_THREAD];
-#pragma unroll
-  for (int k = 0; k < SHIFT_PER_THREAD; ++k) {
-    const int e = threadIdx.x + k * 256;
-    v[k] = e < total ? q[(long long)n * t.C + e] : 0.f;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < SHIFT_PER_THREAD; ++k) {
-    const int e = threadIdx.x + k * 256;
-    if (e < total) q[e] = v[k];
-  }
+  state_shift_body(t.p + (long long)row * t.pitch, t.S, F * t.npf, t.C);
   if (blockIdx.x == 0 && threadIdx.x == 0) pos[row] += pos_step;
 }
 // kk_mimi_stream_reset_row: the carried rows of one row in every buffer become zeros (the left padding of a first step; "no previous input"
@@ -894,6 +885,22 @@ int stream_begin(Run& r, kk_mimi_stream* s) {  // zero state on the first step a
   return 0;
 }
 
+// the end of a step of F frames = T transformer rows.  A row-mode stream carries every buffer of its active rows and advances their
+// positions in one masked launch (the host mirror is the caller's); a plain stream carries `last` (null: its consumer carried it) and advances.
+int stream_end(Run& r, kk_mimi_stream* s, int F, int T, const StateBuf* last) {
+  if (r.dry) return 0;
+  if (s->rows_mode) {
+    hipLaunchKernelGGL(state_shift_rows_kernel, dim3(s->ntable, r.B), dim3(256), 0, r.st, s->table_dev, F, s->active_dev, s->pos_dev, T);
+    KK_CHECK_LAUNCH();
+    return 0;
+  }
+  if (last) KK_TRY(state_shift(*last, r.B, r.st));
+  s->pos += T;
+  s->frames += F;
+  s->fresh = false;
+  return 0;
+}
+
 // dense scratch for the ELU'd input of the few-rows kernel: the largest [S + n][C] block among the stream's state buffers (and the
 // residual blocks' hidden rows, which are never wider than their input)
 void stream_elu_scratch(Run& r, kk_mimi_stream* s) {
@@ -961,16 +968,7 @@ int run_decode_step(Run& r, kk_mimi_stream* s, const int* codes, float* pcm_out)
   Act out;
   out.p = pcm_out; out.rows = s->last.n; out.C = 1; out.ld = 1; out.dtype = KK_F32;
   KK_TRY(r.conv(m->final_conv, s->last.all(), out, 0, 1, false, 1, KK_ACT_ELU, KK_ACT_NONE, nullptr, 0));
-  if (!r.dry && s->rows_mode) {  // active rows: every buffer's carry and the position, one launch (the host mirror is the caller's)
-    hipLaunchKernelGGL(state_shift_rows_kernel, dim3(s->ntable, B), dim3(256), 0, r.st, s->table_dev, F, s->active_dev, s->pos_dev, F * us);
-    KK_CHECK_LAUNCH();
-  } else if (!r.dry) {
-    KK_TRY(state_shift(s->last, B, r.st));
-    s->pos += F * us;
-    s->frames += F;
-    s->fresh = false;
-  }
-  return 0;
+  return stream_end(r, s, F, F * us, &s->last);
 }
 
 // Mimi.encode_step (mimi.py:156-161): pcm [B][chunk * samples_per_frame] -> codes [B][nq][chunk]
@@ -1034,15 +1032,7 @@ int run_encode_step(Run& r, kk_mimi_stream* s, const float* pcm, int* codes) {
       KK_CHECK_LAUNCH();
     }
   }
-  if (!r.dry && s->rows_mode) {  // active rows: every buffer's carry and the position, one launch (the host mirror is the caller's)
-    hipLaunchKernelGGL(state_shift_rows_kernel, dim3(s->ntable, B), dim3(256), 0, r.st, s->table_dev, F, s->active_dev, s->pos_dev, T);
-    KK_CHECK_LAUNCH();
-  } else if (!r.dry) {
-    s->pos += T;
-    s->frames += F;
-    s->fresh = false;
-  }
-  return 0;
+  return stream_end(r, s, F, T, nullptr);  // (s->last went behind enc_final)
 }
 
 int mimi_encode_frames(const kk_mimi_config& c, int N) {

@@ -1,4 +1,4 @@
-"""GPU parity tests, kernel level, of the CSM frame step (kk_csm.hip, kk_csm_gemvm.h) through its kk_op_csm_* entry points -- the launchers
+"""GPU parity tests, kernel level, of the CSM frame step (kk_csm.hip, kk_csm_gemvm.h, kk_attn_cache.hip) through its kk_op_csm_* entry points -- the launchers
 the frame itself runs -- against float64 numpy statements of the same operation.  u = 2^-24.
 
 * Matrix-core GEMV (gemvm_kernel), prompt GEMM (gemmp_kernel), fp32 skinny GEMM: BIT-EXACT on integer-valued data whose every partial sum
@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+from _attn_ref import attn_ref, make_attn_case, rope_table, rot32, rot64
 from _util import report
 
 pytestmark = pytest.mark.gpu
@@ -380,66 +381,6 @@ def test_batch_invariance_gemv_gemm_prompt_skinny(lib):
 
 
 # ------------------------------------------------------------------------------------------------------------- attention
-def rope_table(rng, max_pos, hd):
-    ang = rng.uniform(-np.pi, np.pi, (max_pos, hd // 2))
-    ang[0] = 0.0
-    return np.stack([np.cos(ang), np.sin(ang)], -1).astype(np.float32)
-
-
-def rot32(x, cs):
-    """the kernels' RoPE in fp32 arithmetic (no contraction): y0 = x0 c - x1 s, y1 = x1 c + x0 s on interleaved pairs"""
-    x = np.asarray(x, np.float32)
-    x0, x1, c, s = x[..., 0::2], x[..., 1::2], cs[..., 0], cs[..., 1]
-    y = np.empty_like(x)
-    y[..., 0::2] = x0 * c - x1 * s
-    y[..., 1::2] = x1 * c + x0 * s
-    return y
-
-
-def rot64(x, cs):
-    x, cs = np.asarray(x, np.float64), np.asarray(cs, np.float64)
-    x0, x1, c, s = x[..., 0::2], x[..., 1::2], cs[..., 0], cs[..., 1]
-    y = np.empty_like(x)
-    y[..., 0::2] = x0 * c - x1 * s
-    y[..., 1::2] = x1 * c + x0 * s
-    return y
-
-
-def attn_ref(q, keys, vals, scale):
-    """q [H][hd], keys / vals [n][KV][hd] (float64) -> [H][hd]; GQA: head h reads kv head h / (H / KV)"""
-    H, KV = q.shape[0], keys.shape[1]
-    G = H // KV
-    out = np.zeros(q.shape)
-    for h in range(H):
-        s = keys[:, h // G] @ q[h] * scale
-        p = np.exp(s - s.max())
-        out[h] = p @ vals[:, h // G] / p.sum()
-    return out
-
-
-def make_attn_case(rng, B, H, KV, hd, max_pos, offset, pads, regime, dom=None):
-    """qkv [B][(H + 2 KV) hd], caches [B][max_pos][KV hd] (slots outside pad .. offset - 1 hold large junk no kernel may read), rope table.
-    regime "large": scores up to ~80, the dominant key of item b at slot dom[b] (or the new key when dom[b] == offset)."""
-    W = (H + 2 * KV) * hd
-    rope = rope_table(rng, max_pos, hd)
-    qkv = rng.standard_normal((B, W)).astype(np.float32)
-    kc = (rng.standard_normal((B, max_pos, KV * hd)) * 1e3).astype(np.float32)
-    vc = (rng.standard_normal((B, max_pos, KV * hd)) * 1e3).astype(np.float32)
-    scale = 1.0 / np.sqrt(np.float32(hd))
-    for b in range(B):
-        live = slice(pads[b], offset)
-        kc[b, live] = rng.standard_normal((offset - pads[b], KV * hd))
-        vc[b, live] = rng.standard_normal((offset - pads[b], KV * hd))
-        if regime == "large":
-            kc[b, live] *= 3.0  # background scores of ~ +-10 .. 30
-            if dom is not None and pads[b] <= dom[b] < offset:
-                qr = rot64(qkv[b, : H * hd].reshape(H, hd), rope[offset - pads[b]])
-                for kvh in range(KV):
-                    qh = qr[kvh * (H // KV)]
-                    kc[b, dom[b], kvh * hd : (kvh + 1) * hd] = qh * (80.0 / (scale * (qh @ qh)))
-    return qkv, kc, vc, rope
-
-
 def attn_single_ref(qkv, kc, vc, rope, H, KV, hd, offset, pads):
     B = qkv.shape[0]
     scale = float(1.0 / np.sqrt(np.float32(hd)))

@@ -17,6 +17,7 @@ import torch  # noqa: E402
 
 import mimi_oracle as M  # noqa: E402
 import mlx_audio_amd.params as P  # noqa: E402
+from _attn_ref import check_bits  # noqa: E402
 from _util import err_stats, report  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -102,6 +103,8 @@ def test_rows_started_at_different_steps_equal_their_solo_streams_and_the_oracle
         worst = max(worst, e["max_abs"] / max(1.0, e["ref_max"]))
         assert e["max_abs"] <= 1e-3 * max(1.0, e["ref_max"]), (r, e)
     report(f"mimi/rows/{which}", worst_rel=worst)
+    if which == "tiny":  # the pcm bits recorded before the stream-state kernels got their shared bodies
+        check_bits("mimi_rows/decode_pcm/tiny", *[np.concatenate(pcm[r]).astype(np.float32) for r in range(4)])
     dec.close()
 
 
