@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 17  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 18  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -54,7 +54,8 @@ extern "C" {
                                kk_op_whisper_pick_reset, kk_whisper_text_*);
                             16: Whisper's token timestamps (kk_op_whisper_qk_rows, kk_op_whisper_align_matrix, kk_op_whisper_dtw with their
                                ..._workspace_bytes, kk_op_whisper_median_filter, kk_whisper_text_forward_qk, kk_whisper_text_qk_bytes);
-                            17: the cache attention's block forms on caller-owned buffers (kk_op_attn_cache_block) */
+                            17: the cache attention's block forms on caller-owned buffers (kk_op_attn_cache_block);
+                            18: row mode of Whisper's text side (kk_whisper_text_rows_*, kk_whisper_rows_item, KK_WHISPER_MAX_ROWS) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -836,6 +837,45 @@ int kk_whisper_text_pick(kk_whisper_text* m, void* stream);
 /* read back (HOST destinations, synchronise): the count of rows not ended; the token buffers [B][cap] and the rows' states [B] */
 int kk_whisper_text_not_ended(kk_whisper_text* m, void* stream, int32_t* out);
 int kk_whisper_text_read(kk_whisper_text* m, void* stream, int32_t* tokens, int cap, kk_whisper_pick_state* rows);
+
+/* ---- row mode: decoder rows that join and leave one running batch -----------------------------------------------------------
+ * A second state beside the window of set_audio, on the same weights and the same stream: max_rows <= KK_WHISPER_MAX_ROWS rows, each with its
+ * own cross K/V (one window), self K/V, pick parameters, suppress bitmask, pick state, initial-token and sampled-token stores (n_text_ctx ids
+ * each) and two kept logits rows.  A row's position is the caller's (initial tokens plus picks).  Opening and using row mode leaves the window
+ * state alone.  Every argument error is an error return before anything is launched. */
+#define KK_WHISPER_MAX_ROWS 32
+typedef struct kk_whisper_rows_item {
+  int32_t row, pos, count;  /* decoder row, its first position of this round, tokens of this round */
+  int32_t from;             /* >= 0: the tokens are `count` ids at this offset of the row's initial tokens; -1 (count 1): the token of the row's last pick */
+  int32_t keep, slot;       /* keep >= 0: the logits of the item's position pos + keep (which out_rows must list) are also copied to the row's kept slot 0 or 1 */
+} kk_whisper_rows_item;
+/* the caller's memory: one persistent state buffer, and a workspace that serves rounds of up to max_round_rows flat rows in up to max_items items
+ * (and admissions); 0 for a bad argument */
+size_t kk_whisper_text_rows_state_bytes(const kk_whisper_text* m, int max_rows);
+size_t kk_whisper_text_rows_workspace_bytes(const kk_whisper_text* m, int max_round_rows, int max_items);
+/* `state` must stay alive and untouched by the caller while row mode is used; every row's ended flag is cleared.  Never synchronises. */
+int kk_whisper_text_rows_open(kk_whisper_text* m, void* stream, int max_rows, void* state, size_t state_bytes);
+/* a request takes a row: audio_features fp32 [n_audio_ctx][n_audio_state] rounded to bf16 once and every layer's cross K | V computed into THIS
+ * row's slice (set_audio's launch with B = 1; the other rows' slices are not touched); tokens (HOST, n ids), params (HOST) and the bitmask (HOST,
+ * (n_vocab + 31) / 32 words, or null) are uploaded, the row's pick state is reset.  Synchronises (the host arrays may go away). */
+int kk_whisper_text_rows_admit(kk_whisper_text* m, void* stream, int row, const float* audio_features, const int32_t* tokens, int n,
+                               const kk_whisper_pick_params* params, const uint32_t* suppress, void* workspace, size_t workspace_bytes);
+/* one round of the decoder over R = sum(count) flat rows (item i's rows follow item i - 1's), any mix of prefill and step items; items HOST
+ * [n_items], each row at most once; out_rows HOST [n_out]: the distinct flat rows whose logits are wanted, logits_out fp32 [n_out][n_vocab] in
+ * that order (it must stay alive until the rows_pick that follows).  The self K/V of the new positions are written.  Refused: a row outside
+ * [0, max_rows), never admitted or listed twice; pos + count > n_text_ctx; from + count beyond the row's initial tokens; from = -1 with
+ * count != 1 or before the row's pick; a workspace too small for R.  Never synchronises. */
+int kk_whisper_text_rows_forward(kk_whisper_text* m, void* stream, const kk_whisper_rows_item* items, int n_items, const int32_t* out_rows, int n_out,
+                                 float* logits_out, void* workspace, size_t workspace_bytes);
+/* the pick of kk_op_whisper_pick for the listed rows (HOST [n], each once), every row on ITS params, bitmask and state and on the logits of its
+ * last position in the last rows_forward (which must have listed it in out_rows); state.ended is the row's flag.  Never synchronises. */
+int kk_whisper_text_rows_pick(kk_whisper_text* m, void* stream, const int32_t* rows, int n);
+/* the poll: ended HOST int32 [max_rows] (0 for a row that was never admitted); synchronises */
+int kk_whisper_text_rows_flags(kk_whisper_text* m, void* stream, int32_t* ended);
+/* a row's sampled tokens (HOST [cap]) and pick state (HOST) and, unless null, its two kept logits rows (DEVICE fp32 [2][n_vocab]); synchronises */
+int kk_whisper_text_rows_read(kk_whisper_text* m, void* stream, int row, int32_t* tokens, int cap, kk_whisper_pick_state* state, float* kept);
+/* initial token `index` of a row from DEVICE memory (the detected language, with no host round trip); never synchronises */
+int kk_whisper_text_rows_set_token(kk_whisper_text* m, void* stream, int row, int index, const int32_t* token);
 
 /* =====================================================================================================================
  * Whisper, token timestamps from cross-attention: timing.py:19-100, 143-157 and Model.forward_with_cross_qk (csrc/kk_whisper_align.hip,

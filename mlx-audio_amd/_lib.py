@@ -60,6 +60,13 @@ class KKWhisperPickState(C.Structure):  # kk_whisper_pick_state
                 ("sum_logprob", C.c_float), ("last_logprob", C.c_float), ("reserved", C.c_int32)]
 
 
+class KKWhisperRowsItem(C.Structure):  # kk_whisper_rows_item
+    _fields_ = [("row", C.c_int32), ("pos", C.c_int32), ("count", C.c_int32), ("from_", C.c_int32), ("keep", C.c_int32), ("slot", C.c_int32)]
+
+
+WHISPER_MAX_ROWS = 32  # KK_WHISPER_MAX_ROWS
+
+
 class KKLlamaArgs(C.Structure):
     _fields_ = [("num_layers", C.c_int32), ("num_heads", C.c_int32), ("num_kv_heads", C.c_int32), ("head_dim", C.c_int32),
                 ("hidden", C.c_int32), ("intermediate", C.c_int32), ("rope_theta", C.c_float), ("rope_factor", C.c_float), ("rms_eps", C.c_float)]
@@ -244,6 +251,15 @@ SIGNATURES = {
     "kk_whisper_text_pick": (_i, [_vp, _vp]),
     "kk_whisper_text_not_ended": (_i, [_vp, _vp, C.POINTER(C.c_int32)]),
     "kk_whisper_text_read": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "kk_whisper_text_rows_state_bytes": (_sz, [_vp, _i]),
+    "kk_whisper_text_rows_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "kk_whisper_text_rows_open": (_i, [_vp, _vp, _i, _vp, _sz]),
+    "kk_whisper_text_rows_admit": (_i, [_vp, _vp, _i, _vp, _vp, _i, C.POINTER(KKWhisperPickParams), _vp, _vp, _sz]),
+    "kk_whisper_text_rows_forward": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _sz]),
+    "kk_whisper_text_rows_pick": (_i, [_vp, _vp, _vp, _i]),
+    "kk_whisper_text_rows_flags": (_i, [_vp, _vp, _vp]),
+    "kk_whisper_text_rows_read": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "kk_whisper_text_rows_set_token": (_i, [_vp, _vp, _i, _i, _vp]),
     "kk_op_whisper_qk_rows_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "kk_op_whisper_qk_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, C.c_longlong]),
     "kk_op_whisper_align_matrix_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
@@ -299,7 +315,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 17:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 18:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -28,7 +28,12 @@
 //   Two passes over the row's fp32 logits (L2 resident).  Pass A (timestamp mode only) takes, over the logits after every mask but the last rule's,
 //   the log-sum-exp of the timestamp range and the maximum of the text range (decoding.py:381-394).  Pass B takes maximum, lowest arg-maximum and
 //   sum of exponentials of the fully filtered logits, each thread online over its strided share, the shares combined by xor-butterflies and then
-//   across the 16 waves in wave order.  Thread 0 updates the row's state.  The count of rows not yet ended is an integer atomic.
+//   across the 16 waves in wave order.  Thread 0 updates the row's state.  The count of rows not yet ended is an integer atomic.  One body (pick_row) serves
+//   the launch-wide kernel (one params, one bitmask) and the per-row kernel of row mode (each row its own; the row's state.ended is its flag).
+//
+// ---- row mode (the end of this file) ---------------------------------------------------------------------------------------------------
+//   Rows with their own window, position, pick parameters and lifetime in a second state buffer.  A round is the window's launch sequence behind
+//   text_plan_kernel, which fills the per-row index arrays and tokens from a table of items passed as the launch's argument.
 #include "kk_host.h"
 #include "../../include/kokoro_hip.h"
 
@@ -293,13 +298,12 @@ __device__ __forceinline__ Osm osm_block(Osm v, Osm* sh) {  // all 1024 threads;
   return r;
 }
 
-__global__ __launch_bounds__(1024) void pick_kernel(const float* logits, long long ldl, const kk_whisper_pick_params* params, const uint32_t* suppress,
-                                                    kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next, int32_t* not_ended) {
-  __shared__ Osm sh[16];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const kk_whisper_pick_params P = *params;
-  const kk_whisper_pick_state S = state[b];
-  const float* lg = logits + (long long)b * ldl;
+// The pick of ONE row by one workgroup: lg the row's logits, P its parameters, suppress its bitmask (or null), st its state, tokens its store of
+// `cap` ids, next where its choice goes.  not_ended: the launch-wide counter, or null (the per-row form: the row's state.ended is its flag).
+__device__ __forceinline__ void pick_row(const float* lg, const kk_whisper_pick_params P, const uint32_t* suppress, kk_whisper_pick_state* st, int32_t* tokens,
+                                         int cap, int32_t* next, int32_t* not_ended, Osm* sh) {
+  const int tid = threadIdx.x;
+  const kk_whisper_pick_state S = *st;
   const int V = P.n_vocab, tb = P.timestamp_begin;
   const bool first = S.count == 0, ts = !P.without_timestamps;
   const bool last_ts = ts && S.count >= 1 && S.last >= tb, pen_ts = S.count < 2 || S.penultimate >= tb;
@@ -361,18 +365,38 @@ __global__ __launch_bounds__(1024) void pick_kernel(const float* logits, long lo
   else lp = lg[tok] - (f.m + logf(f.s));
   if (S.ended) tok = P.eot;  // decoding.py:273-274
   else N.sum_logprob = S.sum_logprob + lp;  // :271
-  if (S.count < cap) tokens[(long long)b * cap + S.count] = tok;
-  next[b] = tok;
+  if (S.count < cap) tokens[S.count] = tok;
+  *next = tok;
   if (!S.ended && tok == P.eot) {
     N.ended = 1;
-    atomicSub(not_ended, 1);
+    if (not_ended) atomicSub(not_ended, 1);
   }
   N.penultimate = S.last;
   N.last = tok;
   if (tok >= tb) N.last_timestamp = tok;
   N.last_logprob = lp;
   N.count = S.count + 1;
-  state[b] = N;
+  *st = N;
+}
+
+// launch-wide: block b is row b, ONE params and ONE bitmask for the launch
+__global__ __launch_bounds__(1024) void pick_kernel(const float* logits, long long ldl, const kk_whisper_pick_params* params, const uint32_t* suppress,
+                                                    kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next, int32_t* not_ended) {
+  __shared__ Osm sh[16];
+  const int b = blockIdx.x;
+  pick_row(logits + (long long)b * ldl, *params, suppress, state + b, tokens + (long long)b * cap, cap, next + b, not_ended, sh);
+}
+
+// per-row: block j picks for decoder row sel.row[j] on logits row sel.logit[j], with that row's params, bitmask (`words` words each), state and store
+struct PickSel {
+  int row[KK_WHISPER_MAX_ROWS], logit[KK_WHISPER_MAX_ROWS];
+};
+__global__ __launch_bounds__(1024) void pick_rows_kernel(PickSel sel, const float* logits, long long ldl, const kk_whisper_pick_params* params,
+                                                         const uint32_t* suppress, int words, kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next) {
+  __shared__ Osm sh[16];
+  const int r = sel.row[blockIdx.x];
+  pick_row(logits + (long long)sel.logit[blockIdx.x] * ldl, params[r], suppress + (long long)r * words, state + r, tokens + (long long)r * cap, cap, next + r, nullptr,
+           sh);
 }
 
 __global__ void pick_reset_kernel(kk_whisper_pick_state* state, int B, int32_t* not_ended) {
@@ -391,6 +415,37 @@ __global__ void text_rows_kernel(int B, int S, int pos, int n_text_ctx, int n_au
   len_self[r] = p + 1;
   len_cross[r] = n_audio_ctx;
   cache_row[r] = b * n_text_ctx + p;
+}
+
+// Row mode's plan: the same arrays, and the rows' tokens, from a table of items that travels as the launch's argument.  Item i covers the flat rows
+// first[i] .. first[i] + count[i] - 1: decoder row row[i] at positions pos[i] + s, fed from offset from[i] + s of the row's initial-token store, or
+// (from[i] < 0, count 1) with the token the row's last pick chose.
+struct RowItems {
+  int n;
+  int row[KK_WHISPER_MAX_ROWS], pos[KK_WHISPER_MAX_ROWS], count[KK_WHISPER_MAX_ROWS], from[KK_WHISPER_MAX_ROWS], first[KK_WHISPER_MAX_ROWS];
+};
+__global__ void text_plan_kernel(RowItems t, int R, int n_text_ctx, int n_audio_ctx, const int32_t* init, const int32_t* next, int* item, int* posr, int* len_self,
+                                 int* len_cross, int* cache_row, int32_t* tok) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  int i = 0;
+  while (i + 1 < t.n && r >= t.first[i + 1]) ++i;
+  const int s = r - t.first[i], row = t.row[i], p = t.pos[i] + s;
+  item[r] = row;
+  posr[r] = p;
+  len_self[r] = p + 1;
+  len_cross[r] = n_audio_ctx;
+  cache_row[r] = row * n_text_ctx + p;
+  tok[r] = t.from[i] >= 0 ? init[(long long)row * n_text_ctx + t.from[i] + s] : next[row];
+}
+
+// rows sel.src[j] of x to row j of out (the rows whose logits a row-mode round wants, made contiguous for the final LayerNorm)
+struct RowGather {
+  int src[2 * KK_WHISPER_MAX_ROWS];
+};
+__global__ __launch_bounds__(256) void gather_rows_kernel(RowGather sel, const float* x, int D, float* out) {
+  const float* s = x + (long long)sel.src[blockIdx.x] * D;
+  for (int c = threadIdx.x; c < D; c += 256) out[(long long)blockIdx.x * D + c] = s[c];
 }
 }  // namespace
 
@@ -485,6 +540,15 @@ struct kk_whisper_text {
   int B = 0, at = 0;
   const float* last_logits = nullptr;  // the last forward's last-position logits [B][last_ld], in the caller's memory
   long long last_ld = 0;
+  // row mode (rows_open), beside the window: the caller's second state buffer and what the host knows of every row
+  struct Row {
+    bool admitted = false;
+    int n_init = 0;      // initial tokens uploaded at admission
+    int logit = -1;      // the row of the last rows_forward's logits_out that holds this row's last position, -1: none
+  };
+  char* rows_state = nullptr;
+  std::vector<Row> rows;
+  const float* rows_logits = nullptr;  // the last rows_forward's logits_out
 };
 
 namespace {
@@ -725,6 +789,84 @@ struct QkCapture {  // the capturing forward: raw cross-attention scores of the 
   float* qk_out;
 };
 
+// The layer loop and the logits of a forward over R flat rows whose index arrays (p.item, p.posr, p.len_self, p.len_cross, p.cache_row) and embedded
+// tokens (p.x) are in place.  `items` slots of n_text_ctx / n_audio_ctx positions per layer in the self / cross stores: the batch of the window, or the
+// rows of row mode -- the launches are the same.
+struct TextPass {
+  kk_whisper_text* m;
+  hipStream_t st;
+  int items;
+  bf16_t* self;
+  const bf16_t* cross;
+  const TextWork& p;
+
+  // a Linear over `rows` rows, 16 at a time (S = 1: one launch, every weight byte read once for the batch)
+  int lin(const TLin& l, int n0, int N, const float* x, long long ldx, int rows, int act, const float* res, float* out, long long ldo, bf16_t* ob,
+          const int* dst) const {
+    const int D = m->cfg.n_text_state;
+    for (int r0 = 0; r0 < rows; r0 += 16) {
+      LinRows a{x + (long long)r0 * ldx, ldx, m->wdev + l.w + (size_t)n0 * l.K, l.bias ? m->fdev + l.b + n0 : nullptr, res ? res + (long long)r0 * ldo : nullptr, ldo,
+                out ? out + (long long)r0 * ldo : nullptr, ldo, ob, 2 * D, dst ? dst + r0 : nullptr, items * m->cfg.n_text_ctx, rows - r0 < 16 ? rows - r0 : 16, N, l.K,
+                act};
+      KK_TRY(launch_linear_rows(st, a));
+    }
+    return 0;
+  }
+  int ln(size_t w, size_t b, const float* src, long long ldx, int rows) const {
+    const int D = m->cfg.n_text_state;
+    KKLnArgs a;
+    memset(&a, 0, sizeof a);
+    a.x = src; a.xbs = 0; a.ldx = (int)ldx; a.out = p.ln; a.obs = 0; a.ldo = D; a.C = D; a.Lmax = rows;
+    a.len = KKLen{nullptr, 0, rows}; a.w = m->fdev + w; a.bias = m->fdev + b; a.eps = 1e-5f;
+    return kk_launch_layernorm(a, 1, KK_F32, st);
+  }
+  // cap (window mode only): R = B * S rows, S per item
+  int layers(int R, const QkCapture* cap, int B, int S) const {
+    const kk_whisper_text_config& c = m->cfg;
+    const int D = c.n_text_state, H = c.n_text_head;
+    for (int li = 0; li < c.n_text_layer; ++li) {  // whisper.py:157-168
+      const TLayer& L = m->layers[li];
+      bf16_t* selfc = self + (size_t)li * items * c.n_text_ctx * 2 * D;
+      const bf16_t* crossc = cross + (size_t)li * items * c.n_audio_ctx * 2 * D;
+      KK_TRY(ln(L.attn_ln_w, L.attn_ln_b, p.x, D, R));
+      KK_TRY(lin(L.q, 0, D, p.ln, D, R, KK_ACT_NONE, nullptr, p.q, D, nullptr, nullptr));
+      KK_TRY(lin(L.k, 0, D, p.ln, D, R, KK_ACT_NONE, nullptr, nullptr, D, selfc, p.cache_row));      // K and V of the new positions straight into the cache
+      KK_TRY(lin(L.v, 0, D, p.ln, D, R, KK_ACT_NONE, nullptr, nullptr, D, selfc + D, p.cache_row));
+      KK_TRY(launch_attn_rows(st, R, H, p.q, selfc, 0, D, items, c.n_text_ctx, 2 * D, p.item, p.len_self, p.att, p.scratch));  // causal: row (b, s) sees pos + s + 1 keys
+      KK_TRY(lin(L.out, 0, D, p.att, D, R, KK_ACT_NONE, p.x, p.x, D, nullptr, nullptr));
+      KK_TRY(ln(L.cross_ln_w, L.cross_ln_b, p.x, D, R));
+      KK_TRY(lin(L.cq, 0, D, p.ln, D, R, KK_ACT_NONE, nullptr, p.q, D, nullptr, nullptr));
+      if (cap) {  // this layer's listed heads, 32 to a launch, each into the slot of its pair
+        KKQkSel sel;
+        sel.n = 0;
+        for (int pi = 0; pi <= cap->n_pairs; ++pi) {
+          if (pi < cap->n_pairs && cap->pairs[2 * pi] == li) {
+            sel.head[sel.n] = cap->pairs[2 * pi + 1];
+            sel.slot[sel.n++] = pi;
+          }
+          if (sel.n == 32 || (pi == cap->n_pairs && sel.n > 0)) {
+            KK_TRY(kk_launch_whisper_qk_rows(st, p.q, crossc, (long long)c.n_audio_ctx * 2 * D, 2 * D, H, B, S, cap->n_keys, sel, cap->qk_out,
+                                             (long long)S * cap->n_keys, (long long)cap->n_pairs * S * cap->n_keys, cap->n_keys));
+            sel.n = 0;
+          }
+        }
+      }
+      KK_TRY(launch_attn_rows(st, R, H, p.q, crossc, 0, D, items, c.n_audio_ctx, 2 * D, p.item, p.len_cross, p.att, p.scratch));
+      KK_TRY(lin(L.cout, 0, D, p.att, D, R, KK_ACT_NONE, p.x, p.x, D, nullptr, nullptr));
+      KK_TRY(ln(L.mlp_ln_w, L.mlp_ln_b, p.x, D, R));
+      KK_TRY(lin(L.mlp1, 0, 4 * D, p.ln, D, R, KK_ACT_GELU, nullptr, p.h, 4 * D, nullptr, nullptr));
+      KK_TRY(lin(L.mlp2, 0, D, p.h, 4 * D, R, KK_ACT_NONE, p.x, p.x, D, nullptr, nullptr));
+    }
+    return 0;
+  }
+  // decoder.ln and the tied embedding as the output Linear (whisper.py:247-248) on `rows` rows of x at pitch ldx
+  int logits(const float* x, long long ldx, int rows, float* out) const {
+    const int D = m->cfg.n_text_state, V = m->cfg.n_vocab;
+    KK_TRY(ln(m->ln_w, m->ln_b, x, ldx, rows));
+    return lin(m->emb, 0, V, p.ln, D, rows, KK_ACT_NONE, nullptr, out, V, nullptr, nullptr);
+  }
+};
+
 // the one layer loop behind kk_whisper_text_forward and kk_whisper_text_forward_qk (cap == null: nothing is captured, the launches are those of the plain forward)
 int text_forward(const char* who, kk_whisper_text* m, void* stream, int B, int S, const int32_t* tokens, float* logits_out, int all_positions, void* workspace,
                  size_t workspace_bytes, const QkCapture* cap) {
@@ -732,7 +874,7 @@ int text_forward(const char* who, kk_whisper_text* m, void* stream, int B, int S
   if (!m->state || B != m->B) return kk_failf("%s: set_audio first, with the same B", who);
   const kk_whisper_text_config& c = m->cfg;
   if (m->at + S > c.n_text_ctx) return kk_failf("%s: position %d + %d tokens exceeds n_text_ctx = %d", who, m->at, S, c.n_text_ctx);
-  const int D = c.n_text_state, H = c.n_text_head, V = c.n_vocab, R = B * S;
+  const int D = c.n_text_state, V = c.n_vocab, R = B * S;
   hipStream_t st = (hipStream_t)stream;
   Workspace ss, ws;
   bind(ss, m->state, (size_t)-1 / 2);
@@ -752,65 +894,14 @@ int text_forward(const char* who, kk_whisper_text* m, void* stream, int B, int S
   hipLaunchKernelGGL(embed_kernel, dim3(R), dim3(256), 0, st, tokens, p.posr, m->wdev + m->emb.w, V, m->fdev + m->pos, c.n_text_ctx, D, p.x);
   KK_CHECK_LAUNCH();
 
-  // a Linear over `rows` rows, 16 at a time (S = 1: one launch, every weight byte read once for the batch)
-  auto lin = [&](const TLin& l, int n0, int N, const float* x, long long ldx, int rows, int act, const float* res, float* out, long long ldo, bf16_t* ob,
-                 const int* dst) -> int {
-    for (int r0 = 0; r0 < rows; r0 += 16) {
-      LinRows a{x + (long long)r0 * ldx, ldx, m->wdev + l.w + (size_t)n0 * l.K, l.bias ? m->fdev + l.b + n0 : nullptr, res ? res + (long long)r0 * ldo : nullptr, ldo,
-                out ? out + (long long)r0 * ldo : nullptr, ldo, ob, 2 * D, dst ? dst + r0 : nullptr, B * c.n_text_ctx, rows - r0 < 16 ? rows - r0 : 16, N, l.K, act};
-      KK_TRY(launch_linear_rows(st, a));
-    }
-    return 0;
-  };
-  auto ln = [&](size_t w, size_t b, const float* src, long long ldx, int rows) -> int {
-    KKLnArgs a;
-    memset(&a, 0, sizeof a);
-    a.x = src; a.xbs = 0; a.ldx = (int)ldx; a.out = p.ln; a.obs = 0; a.ldo = D; a.C = D; a.Lmax = rows;
-    a.len = KKLen{nullptr, 0, rows}; a.w = m->fdev + w; a.bias = m->fdev + b; a.eps = 1e-5f;
-    return kk_launch_layernorm(a, 1, KK_F32, st);
-  };
-  for (int li = 0; li < c.n_text_layer; ++li) {  // whisper.py:157-168
-    const TLayer& L = m->layers[li];
-    bf16_t* selfc = s.self + (size_t)li * B * c.n_text_ctx * 2 * D;
-    const bf16_t* crossc = s.cross + (size_t)li * B * c.n_audio_ctx * 2 * D;
-    KK_TRY(ln(L.attn_ln_w, L.attn_ln_b, p.x, D, R));
-    KK_TRY(lin(L.q, 0, D, p.ln, D, R, KK_ACT_NONE, nullptr, p.q, D, nullptr, nullptr));
-    KK_TRY(lin(L.k, 0, D, p.ln, D, R, KK_ACT_NONE, nullptr, nullptr, D, selfc, p.cache_row));      // K and V of the new positions straight into the cache
-    KK_TRY(lin(L.v, 0, D, p.ln, D, R, KK_ACT_NONE, nullptr, nullptr, D, selfc + D, p.cache_row));
-    KK_TRY(launch_attn_rows(st, R, H, p.q, selfc, 0, D, B, c.n_text_ctx, 2 * D, p.item, p.len_self, p.att, p.scratch));  // causal: row (b, s) sees pos + s + 1 keys
-    KK_TRY(lin(L.out, 0, D, p.att, D, R, KK_ACT_NONE, p.x, p.x, D, nullptr, nullptr));
-    KK_TRY(ln(L.cross_ln_w, L.cross_ln_b, p.x, D, R));
-    KK_TRY(lin(L.cq, 0, D, p.ln, D, R, KK_ACT_NONE, nullptr, p.q, D, nullptr, nullptr));
-    if (cap) {  // this layer's listed heads, 32 to a launch, each into the slot of its pair
-      KKQkSel sel;
-      sel.n = 0;
-      for (int pi = 0; pi <= cap->n_pairs; ++pi) {
-        if (pi < cap->n_pairs && cap->pairs[2 * pi] == li) {
-          sel.head[sel.n] = cap->pairs[2 * pi + 1];
-          sel.slot[sel.n++] = pi;
-        }
-        if (sel.n == 32 || (pi == cap->n_pairs && sel.n > 0)) {
-          KK_TRY(kk_launch_whisper_qk_rows(st, p.q, crossc, (long long)c.n_audio_ctx * 2 * D, 2 * D, H, B, S, cap->n_keys, sel, cap->qk_out,
-                                           (long long)S * cap->n_keys, (long long)cap->n_pairs * S * cap->n_keys, cap->n_keys));
-          sel.n = 0;
-        }
-      }
-    }
-    KK_TRY(launch_attn_rows(st, R, H, p.q, crossc, 0, D, B, c.n_audio_ctx, 2 * D, p.item, p.len_cross, p.att, p.scratch));
-    KK_TRY(lin(L.cout, 0, D, p.att, D, R, KK_ACT_NONE, p.x, p.x, D, nullptr, nullptr));
-    KK_TRY(ln(L.mlp_ln_w, L.mlp_ln_b, p.x, D, R));
-    KK_TRY(lin(L.mlp1, 0, 4 * D, p.ln, D, R, KK_ACT_GELU, nullptr, p.h, 4 * D, nullptr, nullptr));
-    KK_TRY(lin(L.mlp2, 0, D, p.h, 4 * D, R, KK_ACT_NONE, p.x, p.x, D, nullptr, nullptr));
-  }
-  // decoder.ln and the tied embedding as the output Linear (whisper.py:247-248)
+  const TextPass run{m, st, B, s.self, s.cross, p};
+  KK_TRY(run.layers(R, cap, B, S));
   if (all_positions) {
-    KK_TRY(ln(m->ln_w, m->ln_b, p.x, D, R));
-    KK_TRY(lin(m->emb, 0, V, p.ln, D, R, KK_ACT_NONE, nullptr, logits_out, V, nullptr, nullptr));
+    KK_TRY(run.logits(p.x, D, R, logits_out));
     m->last_logits = logits_out + (size_t)(S - 1) * V;  // the last position of item b is S rows after that of item b - 1
     m->last_ld = (long long)S * V;
   } else {
-    KK_TRY(ln(m->ln_w, m->ln_b, p.x + (size_t)(S - 1) * D, (long long)S * D, B));  // the last position of every item
-    KK_TRY(lin(m->emb, 0, V, p.ln, D, B, KK_ACT_NONE, nullptr, logits_out, V, nullptr, nullptr));
+    KK_TRY(run.logits(p.x + (size_t)(S - 1) * D, (long long)S * D, B, logits_out));  // the last position of every item
     m->last_logits = logits_out;
     m->last_ld = V;
   }
@@ -899,5 +990,283 @@ extern "C" int kk_whisper_text_read(kk_whisper_text* m, void* stream, int32_t* t
   if (hipMemcpy2DAsync(tokens, (size_t)cap * 4, s.tokens, (size_t)m->cfg.n_text_ctx * 4, (size_t)n * 4, m->B, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipMemcpyAsync(rows, s.rows, (size_t)m->B * sizeof *rows, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
     return kk_fail("kk_whisper_text_read: read failed");
+  return 0;
+}
+
+// ================================================================================================================================== row mode
+// A second state beside the window's: max_rows decoder rows on the same weights, each with its own cross and self K/V, position (the caller's),
+// pick parameters, bitmask, pick state, token stores and two kept logits rows.  A round (rows_forward) is the window's layer loop over any mix of
+// prefill and step rows; what differs is the plan kernel in front of it and the per-row pick behind it.  DESIGN 8i.
+namespace {
+struct RowsState {  // the caller's row-mode state buffer
+  bf16_t *cross, *self;  // [layer][max_rows][ctx][2 D]: K | V, the window's layout with the rows as its batch
+  kk_whisper_pick_params* params;  // [max_rows]
+  uint32_t* suppress;              // [max_rows][words]
+  kk_whisper_pick_state* rows;     // [max_rows]; .ended is the row's flag
+  int32_t *tokens, *init, *next, *not_ended;  // sampled [max_rows][n_text_ctx], initial [max_rows][n_text_ctx], [max_rows], the reset kernel's counter
+  float* kept;                     // [max_rows][2][n_vocab]
+};
+inline size_t mask_words(const kk_whisper_text_config& c) { return ((size_t)c.n_vocab + 31) / 32; }
+void plan_rows_state(const kk_whisper_text_config& c, int N, Workspace& ws, RowsState& s) {
+  const size_t D = c.n_text_state, L = c.n_text_layer;
+  s.cross = (bf16_t*)ws.raw(L * N * c.n_audio_ctx * 2 * D * 2);
+  s.self = (bf16_t*)ws.raw(L * N * c.n_text_ctx * 2 * D * 2);
+  s.params = (kk_whisper_pick_params*)ws.raw((size_t)N * sizeof(kk_whisper_pick_params));
+  s.suppress = (uint32_t*)ws.raw((size_t)N * mask_words(c) * 4);
+  s.rows = (kk_whisper_pick_state*)ws.raw((size_t)N * sizeof(kk_whisper_pick_state));
+  s.tokens = (int32_t*)ws.raw((size_t)N * c.n_text_ctx * 4);
+  s.init = (int32_t*)ws.raw((size_t)N * c.n_text_ctx * 4);
+  s.next = (int32_t*)ws.raw((size_t)N * 4);
+  s.not_ended = (int32_t*)ws.raw(4);
+  s.kept = (float*)ws.raw((size_t)N * 2 * c.n_vocab * 4);
+}
+struct RowsWork {
+  TextWork t;    // t.feat: ONE window (rows_admit)
+  int32_t* tok;  // [R]
+};
+void plan_rows_work(const kk_whisper_text_config& c, int R, Workspace& ws, RowsWork& p) {
+  plan_work(c, 1, R, ws, p.t);  // B = 1, S = R: R flat rows and one window of features
+  p.tok = (int32_t*)ws.raw((size_t)R * 4);
+}
+int rows_bound(const char* who, const kk_whisper_text* m, RowsState& s) {
+  if (!m) return kk_failf("%s: null model", who);
+  if (!m->rows_state) return kk_failf("%s: row mode not opened (kk_whisper_text_rows_open first)", who);
+  Workspace ss;
+  bind(ss, m->rows_state, (size_t)-1 / 2);
+  plan_rows_state(m->cfg, (int)m->rows.size(), ss, s);
+  return 0;
+}
+int rows_check_row(const char* who, const kk_whisper_text* m, int row, bool admitted) {
+  const int N = (int)m->rows.size();
+  if (row < 0 || row >= N) return kk_failf("%s: row %d is outside [0, max_rows = %d)", who, row, N);
+  if (admitted && !m->rows[row].admitted) return kk_failf("%s: row %d was never admitted", who, row);
+  return 0;
+}
+}  // namespace
+
+extern "C" size_t kk_whisper_text_rows_state_bytes(const kk_whisper_text* m, int max_rows) {
+  if (!m || max_rows < 1 || max_rows > KK_WHISPER_MAX_ROWS) return 0;
+  Workspace ws;
+  RowsState s;
+  plan_rows_state(m->cfg, max_rows, ws, s);
+  return ws.used + 256;
+}
+
+extern "C" size_t kk_whisper_text_rows_workspace_bytes(const kk_whisper_text* m, int max_round_rows, int max_items) {
+  if (!m || max_round_rows < 1 || max_items < 1 || max_items > KK_WHISPER_MAX_ROWS) return 0;
+  Workspace ws;
+  RowsWork p;
+  plan_rows_work(m->cfg, max_round_rows, ws, p);
+  return ws.used + 256;
+}
+
+extern "C" int kk_whisper_text_rows_open(kk_whisper_text* m, void* stream, int max_rows, void* state, size_t state_bytes) {
+  const char* who = "kk_whisper_text_rows_open";
+  if (!m || !state) return kk_failf("%s: null argument", who);
+  if (!m->finalized) return kk_failf("%s: model not finalized", who);
+  if (max_rows < 1 || max_rows > KK_WHISPER_MAX_ROWS) return kk_failf("%s: max_rows = %d is outside [1, %d]", who, max_rows, KK_WHISPER_MAX_ROWS);
+  Workspace ss;
+  bind(ss, state, state_bytes);
+  RowsState s;
+  plan_rows_state(m->cfg, max_rows, ss, s);
+  if (ss.oom) return kk_failf("%s: state buffer too small", who);
+  KK_TRY(kk_op_whisper_pick_reset(stream, max_rows, s.rows, s.not_ended));  // every row's flag reads 0 before its first admission
+  m->rows_state = (char*)state;
+  m->rows.assign(max_rows, kk_whisper_text::Row());
+  m->rows_logits = nullptr;
+  return 0;
+}
+
+extern "C" int kk_whisper_text_rows_admit(kk_whisper_text* m, void* stream, int row, const float* audio_features, const int32_t* tokens, int n,
+                                          const kk_whisper_pick_params* params, const uint32_t* suppress, void* workspace, size_t workspace_bytes) {
+  const char* who = "kk_whisper_text_rows_admit";
+  RowsState s;
+  KK_TRY(rows_bound(who, m, s));
+  KK_TRY(rows_check_row(who, m, row, false));
+  if (!audio_features || !tokens || !params || !workspace) return kk_failf("%s: null argument", who);
+  const kk_whisper_text_config& c = m->cfg;
+  if (n < 1 || n > c.n_text_ctx) return kk_failf("%s: %d initial tokens are outside [1, n_text_ctx = %d]", who, n, c.n_text_ctx);
+  if (params->n_vocab != c.n_vocab) return kk_failf("%s: params.n_vocab differs from the model's", who);
+  if (params->eot < 0 || params->eot >= c.n_vocab || params->timestamp_begin < 0 || params->timestamp_begin > c.n_vocab)
+    return kk_failf("%s: token ids outside the vocabulary", who);
+  const int D = c.n_text_state, ctx = c.n_audio_ctx, N = (int)m->rows.size();
+  hipStream_t st = (hipStream_t)stream;
+  Workspace ws;
+  bind(ws, workspace, workspace_bytes);
+  RowsWork p;
+  plan_rows_work(c, 1, ws, p);
+  if (ws.oom) return kk_failf("%s: workspace too small", who);
+  m->rows[row].admitted = false;  // a failure below leaves the row unusable, not half new
+  m->rows[row].logit = -1;
+  KK_TRY(kk_launch_convert(audio_features, KK_F32, (long long)ctx * D, D, p.t.feat, KK_BF16, (long long)ctx * D, D, D, ctx, 1, st));  // rounded once
+  for (int li = 0; li < c.n_text_layer; ++li) {  // set_audio's launch with B = 1, into this row's slice of every layer
+    const TLin& l = m->layers[li].ckv;
+    KKMfmaArgs g;
+    memset(&g, 0, sizeof g);
+    g.x = p.t.feat; g.xbs = (long long)ctx * D; g.ldx = D; g.w = m->wdev + l.w; g.CinP = D; g.CoutP = 2 * D; g.Cin = D;
+    g.bias = m->fdev + l.b; g.out = s.cross + ((size_t)li * N + row) * ctx * 2 * D; g.obs = (long long)ctx * 2 * D; g.ldo = 2 * D;
+    g.Cout = 2 * D; g.Kw = 1; g.mode = KK_CONV; g.stride = 1; g.pad = 0; g.dil = 1; g.Q = ctx; g.Lo_rows = ctx;
+    g.lin = KKLen{nullptr, 0, ctx}; g.lout = KKLen{nullptr, 0, ctx};
+    g.in_slope = 1.0f; g.scale = 1.0f; g.act = KK_ACT_NONE;
+    KK_TRY(kk_launch_conv_mfma(g, 1, KK_BF16, st));
+  }
+  const size_t words = mask_words(c);
+  uint32_t* mask = s.suppress + (size_t)row * words;
+  if (hipMemcpyAsync(s.init + (size_t)row * c.n_text_ctx, tokens, (size_t)n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(s.params + row, params, sizeof *params, hipMemcpyHostToDevice, st) != hipSuccess ||
+      (suppress ? hipMemcpyAsync(mask, suppress, words * 4, hipMemcpyHostToDevice, st) : hipMemsetAsync(mask, 0, words * 4, st)) != hipSuccess)
+    return kk_failf("%s: upload failed", who);
+  if (hipStreamSynchronize(st) != hipSuccess) return kk_failf("%s: stream sync failed", who);  // the host arrays may go away
+  KK_TRY(kk_op_whisper_pick_reset(stream, 1, s.rows + row, s.not_ended));
+  m->rows[row].admitted = true;
+  m->rows[row].n_init = n;
+  return 0;
+}
+
+extern "C" int kk_whisper_text_rows_forward(kk_whisper_text* m, void* stream, const kk_whisper_rows_item* items, int n_items, const int32_t* out_rows, int n_out,
+                                            float* logits_out, void* workspace, size_t workspace_bytes) {
+  const char* who = "kk_whisper_text_rows_forward";
+  RowsState s;
+  KK_TRY(rows_bound(who, m, s));
+  if (!items || !out_rows || !logits_out || !workspace) return kk_failf("%s: null argument", who);
+  if (n_items < 1 || n_items > KK_WHISPER_MAX_ROWS) return kk_failf("%s: %d items are outside [1, %d]", who, n_items, KK_WHISPER_MAX_ROWS);
+  const kk_whisper_text_config& c = m->cfg;
+  const int D = c.n_text_state, V = c.n_vocab, N = (int)m->rows.size();
+  // everything is checked on the host before anything is launched: the table decides what memory the round reads and writes
+  RowItems t;
+  memset(&t, 0, sizeof t);
+  t.n = n_items;
+  long long R = 0;
+  unsigned seen = 0;
+  for (int i = 0; i < n_items; ++i) {
+    const kk_whisper_rows_item& it = items[i];
+    KK_TRY(rows_check_row(who, m, it.row, true));
+    if (seen >> it.row & 1u) return kk_failf("%s: row %d appears twice in one round", who, it.row);
+    seen |= 1u << it.row;
+    if (it.count < 1 || it.pos < 0 || (long long)it.pos + it.count > c.n_text_ctx)
+      return kk_failf("%s: item %d: position %d + %d tokens exceeds n_text_ctx = %d", who, i, it.pos, it.count, c.n_text_ctx);
+    if (it.from < -1) return kk_failf("%s: item %d: from = %d (an offset of the initial tokens, or -1 for the last pick's token)", who, i, it.from);
+    if (it.from == -1 && it.count != 1) return kk_failf("%s: item %d: from = -1 (the last pick's token) needs count 1, not %d", who, i, it.count);
+    if (it.from == -1 && m->rows[it.row].logit != -2) return kk_failf("%s: item %d: row %d has no picked token to step on", who, i, it.row);
+    if (it.from >= 0 && (long long)it.from + it.count > m->rows[it.row].n_init)
+      return kk_failf("%s: item %d: from %d + %d tokens is beyond row %d's %d initial tokens", who, i, it.from, it.count, it.row, m->rows[it.row].n_init);
+    if (it.keep < -1 || it.keep >= it.count || (it.keep >= 0 && (it.slot < 0 || it.slot > 1)))
+      return kk_failf("%s: item %d: keep = %d must be -1 or an offset below count, slot 0 or 1", who, i, it.keep);
+    t.row[i] = it.row; t.pos[i] = it.pos; t.count[i] = it.count; t.from[i] = it.from; t.first[i] = (int)R;
+    R += it.count;
+  }
+  Workspace ws;
+  bind(ws, workspace, workspace_bytes);
+  RowsWork p;
+  plan_rows_work(c, (int)R, ws, p);
+  if (ws.oom) return kk_failf("%s: workspace too small for R = %lld rows", who, R);
+  if (n_out < 1 || n_out > 2 * n_items || n_out > R) return kk_failf("%s: n_out = %d is outside [1, min(2 n_items, R)]", who, n_out);
+  std::vector<int> where((size_t)R, -1);  // flat row -> its row of logits_out
+  bool identity = n_out == R;
+  RowGather sel;
+  memset(&sel, 0, sizeof sel);
+  for (int j = 0; j < n_out; ++j) {
+    if (out_rows[j] < 0 || out_rows[j] >= R) return kk_failf("%s: out_rows[%d] = %d is outside [0, R = %lld)", who, j, out_rows[j], R);
+    if (where[out_rows[j]] >= 0) return kk_failf("%s: out_rows lists flat row %d twice", who, out_rows[j]);
+    where[out_rows[j]] = j;
+    sel.src[j] = out_rows[j];
+    identity = identity && out_rows[j] == j;
+  }
+  for (int i = 0; i < n_items; ++i)
+    if (items[i].keep >= 0 && where[t.first[i] + items[i].keep] < 0) return kk_failf("%s: item %d: the kept position is not in out_rows", who, i);
+
+  hipStream_t st = (hipStream_t)stream;
+  for (auto& r : m->rows)
+    if (r.logit >= 0) r.logit = -1;
+  m->rows_logits = logits_out;
+  hipLaunchKernelGGL(text_plan_kernel, dim3(((int)R + 255) / 256), dim3(256), 0, st, t, (int)R, c.n_text_ctx, c.n_audio_ctx, s.init, s.next, p.t.item, p.t.posr,
+                     p.t.len_self, p.t.len_cross, p.t.cache_row, p.tok);
+  KK_CHECK_LAUNCH();
+  hipLaunchKernelGGL(embed_kernel, dim3((int)R), dim3(256), 0, st, p.tok, p.t.posr, m->wdev + m->emb.w, V, m->fdev + m->pos, c.n_text_ctx, D, p.t.x);
+  KK_CHECK_LAUNCH();
+  const TextPass run{m, st, N, s.self, s.cross, p.t};
+  KK_TRY(run.layers((int)R, nullptr, 0, 0));
+  const float* x = p.t.x;
+  if (!identity) {  // a round of steps wants every row: nothing to gather
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(n_out), dim3(256), 0, st, sel, p.t.x, D, p.t.q);
+    KK_CHECK_LAUNCH();
+    x = p.t.q;
+  }
+  KK_TRY(run.logits(x, D, n_out, logits_out));
+  for (int i = 0; i < n_items; ++i) {
+    const kk_whisper_rows_item& it = items[i];
+    kk_whisper_text::Row& r = m->rows[it.row];
+    const int last = where[t.first[i] + it.count - 1];
+    r.logit = last >= 0 ? last : -1;
+    if (it.keep >= 0 && hipMemcpyAsync(s.kept + ((size_t)it.row * 2 + it.slot) * V, logits_out + (size_t)where[t.first[i] + it.keep] * V, (size_t)V * 4,
+                                       hipMemcpyDeviceToDevice, st) != hipSuccess)
+      return kk_failf("%s: keeping a logits row failed", who);
+  }
+  return 0;
+}
+
+extern "C" int kk_whisper_text_rows_pick(kk_whisper_text* m, void* stream, const int32_t* rows, int n) {
+  const char* who = "kk_whisper_text_rows_pick";
+  RowsState s;
+  KK_TRY(rows_bound(who, m, s));
+  if (!rows) return kk_failf("%s: null argument", who);
+  if (n < 1 || n > KK_WHISPER_MAX_ROWS) return kk_failf("%s: %d rows are outside [1, %d]", who, n, KK_WHISPER_MAX_ROWS);
+  PickSel sel;
+  memset(&sel, 0, sizeof sel);
+  unsigned seen = 0;
+  for (int j = 0; j < n; ++j) {
+    KK_TRY(rows_check_row(who, m, rows[j], true));
+    if (seen >> rows[j] & 1u) return kk_failf("%s: row %d appears twice", who, rows[j]);
+    seen |= 1u << rows[j];
+    if (m->rows[rows[j]].logit < 0 || !m->rows_logits) return kk_failf("%s: row %d has no logits of its last position from the last round", who, rows[j]);
+    sel.row[j] = rows[j];
+    sel.logit[j] = m->rows[rows[j]].logit;
+  }
+  const kk_whisper_text_config& c = m->cfg;
+  hipLaunchKernelGGL(pick_rows_kernel, dim3(n), dim3(1024), 0, (hipStream_t)stream, sel, m->rows_logits, (long long)c.n_vocab, s.params, s.suppress,
+                     (int)mask_words(c), s.rows, s.tokens, c.n_text_ctx, s.next);
+  KK_CHECK_LAUNCH();
+  for (int j = 0; j < n; ++j) m->rows[rows[j]].logit = -2;  // picked: the row can step on its token, and is not picked twice on the same logits
+  return 0;
+}
+
+extern "C" int kk_whisper_text_rows_flags(kk_whisper_text* m, void* stream, int32_t* ended) {
+  const char* who = "kk_whisper_text_rows_flags";
+  RowsState s;
+  KK_TRY(rows_bound(who, m, s));
+  if (!ended) return kk_failf("%s: null argument", who);
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemcpy2DAsync(ended, 4, &s.rows[0].ended, sizeof(kk_whisper_pick_state), 4, m->rows.size(), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return kk_failf("%s: read failed", who);
+  return 0;
+}
+
+extern "C" int kk_whisper_text_rows_read(kk_whisper_text* m, void* stream, int row, int32_t* tokens, int cap, kk_whisper_pick_state* state, float* kept) {
+  const char* who = "kk_whisper_text_rows_read";
+  RowsState s;
+  KK_TRY(rows_bound(who, m, s));
+  KK_TRY(rows_check_row(who, m, row, true));
+  if (!tokens || !state || cap < 1) return kk_failf("%s: bad argument", who);
+  const kk_whisper_text_config& c = m->cfg;
+  hipStream_t st = (hipStream_t)stream;
+  const int n = cap < c.n_text_ctx ? cap : c.n_text_ctx;
+  if (hipMemcpyAsync(tokens, s.tokens + (size_t)row * c.n_text_ctx, (size_t)n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(state, s.rows + row, sizeof *state, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      (kept && hipMemcpyAsync(kept, s.kept + (size_t)row * 2 * c.n_vocab, (size_t)2 * c.n_vocab * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return kk_failf("%s: read failed", who);
+  return 0;
+}
+
+extern "C" int kk_whisper_text_rows_set_token(kk_whisper_text* m, void* stream, int row, int index, const int32_t* token) {
+  const char* who = "kk_whisper_text_rows_set_token";
+  RowsState s;
+  KK_TRY(rows_bound(who, m, s));
+  KK_TRY(rows_check_row(who, m, row, true));
+  if (!token) return kk_failf("%s: null argument", who);
+  if (index < 0 || index >= m->rows[row].n_init) return kk_failf("%s: index %d is outside row %d's %d initial tokens", who, index, row, m->rows[row].n_init);
+  if (hipMemcpyAsync(s.init + (size_t)row * m->cfg.n_text_ctx + index, token, 4, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
+    return kk_failf("%s: copy failed", who);
   return 0;
 }

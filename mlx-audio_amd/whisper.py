@@ -11,7 +11,10 @@ either way -- an `alignment_heads` entry included: the heads are set with `set_a
 
 Token timestamps (`Model.alignment_heads`, `set_alignment_heads`, `forward_with_cross_qk`, whisper.py:272-303; `find_alignment`, `dtw`, `median_filter`,
 `TokenTiming`, `WordTiming` of whisper_timing.py, re-exported here) run on kk_op_whisper_qk_rows / align_matrix / dtw and kk_whisper_text_forward_qk
-(csrc/kk_whisper_align.hip)."""
+(csrc/kk_whisper_align.hip).
+
+`Model.serve(...)` returns a `whisper_serve.WhisperBatcher`: windows with their own options join and leave one running decoder batch (the row mode of the
+text handle, kk_whisper_text_rows_*), each with the result `decode` gives it alone."""
 from __future__ import annotations
 
 import base64
@@ -259,6 +262,7 @@ class Model:
         self._ws = None
         self._lib = None
         self._text = None
+        self._server = None  # the open WhisperBatcher, if any (serve)
         self._alignment_heads = None  # the default is made on first use
 
     # ---- weights ---------------------------------------------------------------------------------------------------------------------
@@ -432,6 +436,19 @@ class Model:
 
         return decode(self, *a, **kw)
 
+    def serve(self, max_rows: int = 8, eos_check_interval: int = 8, max_round_tokens: int = 256):
+        """A running decoder batch that windows join and leave (whisper_serve.WhisperBatcher): `submit(window, options)` returns a Future of
+        the DecodingResult `decode` would return for that window alone.  `decode`, `logits`, `detect_language` and `find_alignment` keep working on this
+        model between the batcher's rounds.  One batcher per model at a time: close() it before asking for another."""
+        if self._text is None:
+            raise NotImplementedError(_NOT_BUILT)
+        from .whisper_serve import WhisperBatcher
+
+        if self._server is not None and not self._server.closed:
+            raise RuntimeError("this model's WhisperBatcher is still open: close() it first")
+        self._server = WhisperBatcher(self, max_rows=max_rows, eos_check_interval=eos_check_interval, max_round_tokens=max_round_tokens)
+        return self._server
+
     def generate(self, *a, **kw):
         raise NotImplementedError(_NOT_BUILT)
 
@@ -457,6 +474,9 @@ class Model:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _release(self):
+        if getattr(self, "_server", None) is not None:
+            self._server.close()  # its rows live in the text handle's memory
+        self._server = None
         if getattr(self, "_h", None) is not None and self._lib is not None:
             self._lib.kk_whisper_destroy(self._h)
         self._h = None

@@ -6,6 +6,8 @@ looks at a device counter of unfinished rows every `eos_check_interval` steps.
 
 There is no tokenizer here (the vocabulary files are not part of this repository): tokens go in and come out as ids, `DecodingResult.text` stays "".
 `TextRuntime.forward_qk` is the forward that also hands out raw cross-attention scores; the token timestamps made from them live in whisper_timing.py.
+`RowRuntime` is the handle's row mode (kk_whisper_text_rows_*): rows with their own window, position, options and lifetime; the batcher on
+top of it lives in whisper_serve.py.
 """
 from __future__ import annotations
 
@@ -405,8 +407,6 @@ def decode(model, mel_or_features, options: DecodingOptions = DecodingOptions(),
     """decoding.py:710-742 -> DecodingTask.run (:618-707), greedy at temperature 0"""
     import torch
 
-    from . import _lib
-
     if kwargs:
         options = replace(options, **kwargs)
     options = verify_options(options)
@@ -436,12 +436,7 @@ def decode(model, mel_or_features, options: DecodingOptions = DecodingOptions(),
         res = [DecodingResult(audio_features=feats[b], language=languages[b], language_probs=lang_probs[b]) for b in range(B)]
         return res[0] if single else res
 
-    params = _lib.KKWhisperPickParams(n_vocab=d.n_vocab, eot=tok.eot, blank=BLANK_TOKEN, no_timestamps=tok.no_timestamps, timestamp_begin=tok.timestamp_begin,
-                                      max_initial_timestamp_index=-1, without_timestamps=int(options.without_timestamps), suppress_blank=int(options.suppress_blank))
-    if not options.without_timestamps and options.max_initial_timestamp:
-        precision = CHUNK_LENGTH / d.n_audio_ctx  # usually 0.02 seconds
-        params.max_initial_timestamp_index = round(options.max_initial_timestamp / precision)
-    bits = suppress_bitmask(d.n_vocab, suppress_list(tok, options)) if options.suppress_tokens else None
+    params, bits = pick_params(d, tok, options)
 
     with torch.cuda.device(model.device):
         if lang_probs is None:
@@ -469,3 +464,110 @@ def decode(model, mel_or_features, options: DecodingOptions = DecodingOptions(),
         out.append(DecodingResult(audio_features=feats[b], language=languages[b], tokens=seq,
                                   avg_logprob=float(rows[b].sum_logprob) / (len(seq) + 1), no_speech_prob=float(no_speech[b]), temperature=options.temperature))
     return out[0] if single else out
+
+
+# ---- row mode: decoder rows that join and leave one running batch (kk_whisper_text_rows_*) ------------------------------------------
+def pick_params(dims, tok: SpecialTokens, options: DecodingOptions):
+    """-> (kk_whisper_pick_params, suppress bitmask or None) of `options`, as decode sets them up"""
+    from . import _lib
+
+    params = _lib.KKWhisperPickParams(n_vocab=dims.n_vocab, eot=tok.eot, blank=BLANK_TOKEN, no_timestamps=tok.no_timestamps, timestamp_begin=tok.timestamp_begin,
+                                      max_initial_timestamp_index=-1, without_timestamps=int(options.without_timestamps), suppress_blank=int(options.suppress_blank))
+    if not options.without_timestamps and options.max_initial_timestamp:
+        precision = CHUNK_LENGTH / dims.n_audio_ctx  # usually 0.02 seconds
+        params.max_initial_timestamp_index = round(options.max_initial_timestamp / precision)
+    bits = suppress_bitmask(dims.n_vocab, suppress_list(tok, options)) if options.suppress_tokens else None
+    return params, bits
+
+
+class RowRuntime:
+    """Row mode of a TextRuntime's handle: thin ctypes plumbing over kk_whisper_text_rows_* that owns the PyTorch memory (the row state, a workspace
+    that grows with the largest round, the last round's logits).  The window state of the TextRuntime is not touched."""
+
+    def __init__(self, text: TextRuntime, max_rows: int):
+        import torch
+
+        from . import _lib
+
+        if not 1 <= max_rows <= _lib.WHISPER_MAX_ROWS:
+            raise ValueError(f"max_rows must be in 1 .. {_lib.WHISPER_MAX_ROWS}")
+        self._t, self._lib, self.dims, self.device, self.max_rows = text, text._lib, text.dims, text.device, max_rows
+        self._h = text._h
+        with torch.cuda.device(self.device):
+            need = int(self._lib.kk_whisper_text_rows_state_bytes(self._h, max_rows))
+            self._state = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._ws = None
+            _lib.check(self._lib.kk_whisper_text_rows_open(self._h, self._stream(), max_rows, C.c_void_p(self._state.data_ptr()), need),
+                       "kk_whisper_text_rows_open")
+        self._logits = None
+
+    def _stream(self):
+        return self._t._stream()
+
+    def _workspace(self, R: int, n_items: int):
+        import torch
+
+        need = int(self._lib.kk_whisper_text_rows_workspace_bytes(self._h, R, n_items))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return C.c_void_p(self._ws.data_ptr()), self._ws.numel()
+
+    def admit(self, row: int, features, tokens, params, suppress_bits: Optional[np.ndarray]):
+        """features: fp32 device (n_audio_ctx, n_audio_state), contiguous; tokens: the initial ids"""
+        from . import _lib
+
+        toks = np.ascontiguousarray(np.asarray(tokens, np.int32))
+        sp = None if suppress_bits is None else suppress_bits.ctypes.data_as(C.c_void_p)
+        ws, wsn = self._workspace(1, 1)
+        _lib.check(self._lib.kk_whisper_text_rows_admit(self._h, self._stream(), row, C.c_void_p(features.data_ptr()), toks.ctypes.data_as(C.c_void_p), len(toks),
+                                                        C.byref(params), sp, ws, wsn), "kk_whisper_text_rows_admit")
+
+    def forward(self, items, out_rows):
+        """items: (row, pos, count, from, keep, slot) tuples; out_rows: flat rows -> fp32 device (len(out_rows), V), alive until the next forward"""
+        import torch
+
+        from . import _lib
+
+        n = len(items)
+        arr = (_lib.KKWhisperRowsItem * max(n, 1))(*[_lib.KKWhisperRowsItem(*it) for it in items])
+        out = np.ascontiguousarray(np.asarray(out_rows, np.int32))
+        R = sum(max(int(it[2]), 0) for it in items)
+        logits = torch.empty((max(len(out), 1), self.dims.n_vocab), dtype=torch.float32, device=self.device)
+        ws, wsn = self._workspace(max(R, 1), max(min(n, _lib.WHISPER_MAX_ROWS), 1))
+        _lib.check(self._lib.kk_whisper_text_rows_forward(self._h, self._stream(), C.cast(arr, C.c_void_p), n, out.ctypes.data_as(C.c_void_p), len(out),
+                                                          C.c_void_p(logits.data_ptr()), ws, wsn), "kk_whisper_text_rows_forward")
+        self._logits = logits  # the pick that follows reads it
+        return logits
+
+    def pick(self, rows):
+        from . import _lib
+
+        r = np.ascontiguousarray(np.asarray(rows, np.int32))
+        _lib.check(self._lib.kk_whisper_text_rows_pick(self._h, self._stream(), r.ctypes.data_as(C.c_void_p), len(r)), "kk_whisper_text_rows_pick")
+
+    def flags(self) -> List[bool]:
+        from . import _lib
+
+        out = np.zeros(self.max_rows, np.int32)
+        _lib.check(self._lib.kk_whisper_text_rows_flags(self._h, self._stream(), out.ctypes.data_as(C.c_void_p)), "kk_whisper_text_rows_flags")
+        return [bool(v) for v in out]
+
+    def read(self, row: int, kept: bool = True):
+        """-> (sampled tokens int32 [n_text_ctx], pick state, the two kept logits rows fp32 device (2, V) or None)"""
+        import torch
+
+        from . import _lib
+
+        cap = self.dims.n_text_ctx
+        toks = np.zeros(cap, np.int32)
+        st = _lib.KKWhisperPickState()
+        k = torch.empty((2, self.dims.n_vocab), dtype=torch.float32, device=self.device) if kept else None
+        _lib.check(self._lib.kk_whisper_text_rows_read(self._h, self._stream(), row, toks.ctypes.data_as(C.c_void_p), cap, C.byref(st),
+                                                       None if k is None else C.c_void_p(k.data_ptr())), "kk_whisper_text_rows_read")
+        return toks, st, k
+
+    def set_token(self, row: int, index: int, token):
+        """token: an int32 device tensor of one element"""
+        from . import _lib
+
+        _lib.check(self._lib.kk_whisper_text_rows_set_token(self._h, self._stream(), row, index, C.c_void_p(token.data_ptr())), "kk_whisper_text_rows_set_token")
