@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 18  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 19  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -55,7 +55,8 @@ extern "C" {
                             16: Whisper's token timestamps (kk_op_whisper_qk_rows, kk_op_whisper_align_matrix, kk_op_whisper_dtw with their
                                ..._workspace_bytes, kk_op_whisper_median_filter, kk_whisper_text_forward_qk, kk_whisper_text_qk_bytes);
                             17: the cache attention's block forms on caller-owned buffers (kk_op_attn_cache_block);
-                            18: row mode of Whisper's text side (kk_whisper_text_rows_*, kk_whisper_rows_item, KK_WHISPER_MAX_ROWS) */
+                            18: row mode of Whisper's text side (kk_whisper_text_rows_*, kk_whisper_rows_item, KK_WHISPER_MAX_ROWS);
+                            19: the fused statistics' finalize / fold step on caller-owned buffers (kk_op_norm_finalize) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -180,10 +181,27 @@ int kk_op_conv1d_bf16_fused(void* stream, int B, const void* x, int ldx, int L_r
                             int CoutP, const float* bias, int Cin, int Cout, int Kw, int pad, int dil, const float* nrm_a,
                             const float* nrm_b, int nrm_stride, int nrm_act, float nrm_slope, const float* nrm_alpha, const void* res,
                             int ldr, float scale, void* out, int ldo, float* stat_part, int* stat_ntiles_out);
-/* InstanceNorm statistics + AdaIN1d + activation (+ pool)  --  istftnet.py:216-268,327-338,382,874-882 */
+/* InstanceNorm statistics + AdaIN1d + activation (+ pool)  --  istftnet.py:216-268,327-338,382,874-882
+ * `scratch` (at least nchunk * B * 2 * C + 2 * B * C floats, nchunk = ceil(L_rows / 512)) holds on return:
+ *   the partial sums  [B][nchunk][2][C]   (sum and sum of squares of x - x[b][0][c] over each 512-row chunk),
+ *   then mean [B][C]  at offset B * nchunk * 2 * C,
+ *   then rstd [B][C]  = 1 / sqrt(var + 1e-5), ddof 0; both 0 for an item of length 0. */
 int kk_op_adain(void* stream, int B, const void* x, int ldx, int L_rows, const int32_t* len, int C, const float* gamma_beta, int gbs,
                 int act, float slope, const float* alpha, int pool, const float* pool_w, const float* pool_b, void* out, int ldo, int Cpad,
                 int Lout_rows, float* scratch, size_t scratch_floats, int dtype, int fast);
+/* The tail of the fused statistics on caller-owned buffers: the step from the per-tile column sums that kk_op_conv1d_bf16_fused writes to the
+ * next AdaIN's parameters (istftnet.py:229-230,333-337).  Two forms:
+ *   finalize (partial != NULL): partial [B][ntiles][2][C] holds UN-shifted sums and sums of squares per tile; all ntiles tiles are summed in double,
+ *     mean = S / n, var = max(SS / n - mean^2, 0), rstd = 1 / sqrt(var + 1e-5) with n = len[b] (L_rows for every item when len == NULL); an item
+ *     of length 0 gets mean = rstd = 0.  mean / rstd [B][C] are written where given.  With add_row_bf16 (bf16, item b at add_row_bf16 +
+ *     b * add_row_bs elements) row 0 of each item and its square are first added to tile 0 of `partial` in place, the other tiles stay as they are.
+ *   fold (partial == NULL): mean / rstd [B][C] are inputs.
+ * With pa / pb (both, and gamma_beta [B][gbs], gamma = [c], beta = [C + c]): pa[b * pstride + c] = rstd * (1 + gamma), pb = beta - mean * pa for
+ * c < C, exactly 0 for C <= c < Cp, untouched from Cp on.  Refused before any launch: B, C or (finalize form) ntiles <= 0, pa without pb or without
+ * gamma_beta, Cp < C, pstride < Cp, the fold form without mean / rstd / pa or with add_row_bf16. */
+int kk_op_norm_finalize(void* stream, int B, int C, const int32_t* len, int L_rows, float* partial, int ntiles, const void* add_row_bf16,
+                        long long add_row_bs, const float* gamma_beta, int gbs, float* mean, float* rstd, float* pa, float* pb, int pstride,
+                        int Cp);
 /* nn.LayerNorm / AdaLayerNorm  --  modules.py:33,71-90 */
 int kk_op_layernorm(void* stream, int B, const void* x, int ldx, const void* res, int ldr, int L_rows, const int32_t* len, int C,
                     const float* w, const float* b, const float* gamma_beta, int gbs, float eps, int act, float slope, void* out, int ldo,

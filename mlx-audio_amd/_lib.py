@@ -105,6 +105,7 @@ SIGNATURES = {
     "kk_op_conv1d_bf16_fused": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _vp, _vp, _i, _f,
                                      _vp, _i, _vp, C.POINTER(C.c_int)]),
     "kk_op_adain": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _i, _f, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _i, _i]),
+    "kk_op_norm_finalize": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, C.c_longlong, _vp, _i, _vp, _vp, _vp, _vp, _i, _i]),
     "kk_op_layernorm": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _f, _i, _f, _vp, _i, _i]),
     "kk_op_lstm": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i]),
     "kk_op_lstm_bf16": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i]),
@@ -315,7 +316,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 18:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 19:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -1784,6 +1784,25 @@ extern "C" int kk_op_adain(void* stream, int B, const void* x, int ldx, int L_ro
   return kk_launch_adain_act(a, B, dtype, (hipStream_t)stream);
 }
 
+extern "C" int kk_op_norm_finalize(void* stream, int B, int C, const int32_t* len, int L_rows, float* partial, int ntiles, const void* add_row_bf16,
+                                   long long add_row_bs, const float* gamma_beta, int gbs, float* mean, float* rstd, float* pa, float* pb,
+                                   int pstride, int Cp) {
+  if (B <= 0 || C <= 0) return kk_fail("kk_op_norm_finalize: B and C must be positive");
+  if ((pa != nullptr) != (pb != nullptr)) return kk_fail("kk_op_norm_finalize: pa and pb come together");
+  if (pa && !gamma_beta) return kk_fail("kk_op_norm_finalize: pa / pb need gamma_beta");
+  if (pa && (Cp < C || pstride < Cp)) return kk_fail("kk_op_norm_finalize: need C <= Cp <= pstride");
+  if (partial && ntiles <= 0) return kk_fail("kk_op_norm_finalize: ntiles must be positive");
+  if (!partial && (!mean || !rstd)) return kk_fail("kk_op_norm_finalize: the fold form (partial == NULL) needs mean and rstd");
+  if (!partial && (!pa || add_row_bf16)) return kk_fail("kk_op_norm_finalize: the fold form (partial == NULL) needs pa / pb and takes no add_row");
+  if (partial && add_row_bf16) KK_TRY(kk_launch_stat_add_row(add_row_bf16, add_row_bs, partial, ntiles, C, B, (hipStream_t)stream));
+  KKStatsArgs a;
+  memset(&a, 0, sizeof a);
+  a.C = C; a.len = KKLen{len, len ? 1 : 0, len ? 0 : L_rows}; a.partial = partial; a.nchunk = ntiles; a.mean = mean; a.rstd = rstd; a.eps = 1e-5f;
+  a.fused = partial ? 1 : 2;
+  if (pa) { a.gb = gamma_beta; a.gbs = gbs; a.pa = pa; a.pb = pb; a.pstride = pstride; a.Cp = Cp; }
+  return kk_launch_norm_finalize(a, B, (hipStream_t)stream);
+}
+
 extern "C" int kk_op_layernorm(void* stream, int B, const void* x, int ldx, const void* res, int ldr, int L_rows, const int32_t* len, int C,
                                const float* w, const float* b, const float* gamma_beta, int gbs, float eps, int act, float slope, void* out,
                                int ldo, int dtype) {
