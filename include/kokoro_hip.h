@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 19  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 20  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -56,7 +56,10 @@ extern "C" {
                                ..._workspace_bytes, kk_op_whisper_median_filter, kk_whisper_text_forward_qk, kk_whisper_text_qk_bytes);
                             17: the cache attention's block forms on caller-owned buffers (kk_op_attn_cache_block);
                             18: row mode of Whisper's text side (kk_whisper_text_rows_*, kk_whisper_rows_item, KK_WHISPER_MAX_ROWS);
-                            19: the fused statistics' finalize / fold step on caller-owned buffers (kk_op_norm_finalize) */
+                            19: the fused statistics' finalize / fold step on caller-owned buffers (kk_op_norm_finalize);
+                            20: the Mimi codec's own kernels and its conv dispatch on caller-owned buffers (kk_op_mimi_conv, kk_op_mimi_rvq_sum,
+                               kk_op_mimi_upsample, kk_op_mimi_rope, kk_op_mimi_conv_cout1, kk_op_mimi_edge_pad, kk_op_mimi_rvq_argmin,
+                               kk_op_mimi_carry) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -350,6 +353,76 @@ int kk_mimi_encode_step_rows(kk_mimi_stream* s, void* stream, int F, const float
 /* intermediates of the last decode / encode (tests): "quantized", "upsampled", "transformer", "layer0".."layer3" (decode), "seanet", "transformer", "downsampled" (encode); [B][rows][channels] fp32 */
 int kk_mimi_debug_info(kk_mimi* m, const char* name, int64_t* rows, int64_t* channels);
 int kk_mimi_debug_fetch(kk_mimi* m, void* stream, const char* name, float* dst);
+
+/* ---- the codec's kernels on their own (ABI minor 20; single-kernel entry points as above: device pointers, caller-owned buffers, work enqueued
+ * on `stream`, 0 = OK; every bad argument is refused on the host before any launch with a kk_last_error() text).  Tensors are frames-major
+ * [B][rows][ld]; dtypes are KK_DTYPE_F32 / KK_DTYPE_BF16; pitches count elements.  These call the launch functions the codec calls. */
+enum { KK_MIMI_CONV_GENERIC = 0, KK_MIMI_CONV_FEW_ROWS = 1, KK_MIMI_CONV_MFMA = 2 };           /* *path_out of kk_op_mimi_conv */
+enum { KK_MIMI_COUT1_F32 = 0, KK_MIMI_COUT1_BF16 = 1, KK_MIMI_COUT1_BF16_STAGED = 2 };         /* *form_out of kk_op_mimi_conv_cout1 */
+enum { KK_MIMI_CARRY_SHIFT = 0, KK_MIMI_CARRY_EDGE_FILL = 1, KK_MIMI_CARRY_EDGE_FILL_ROWS = 2, KK_MIMI_CARRY_SHIFT_ROWS = 3,
+       KK_MIMI_CARRY_RESET_ROW = 4, KK_MIMI_CARRY_SET_ACTIVE = 5 };                             /* op of kk_op_mimi_carry */
+/* The codec's conv / transposed conv / linear dispatch (every convolution and Linear of kk_mimi_decode / encode and their steps goes through
+ * it) on the caller's tensors and weights; *path_out says which kernel it launched (-1 when refused):
+ *   KK_MIMI_CONV_MFMA      the variant-4 matrix-core kernel: w_frag given, x and out bf16, ldx >= CinP, shape eligible (Cout % 8 == 0,
+ *                          Cin, Cout >= 16, stride 1 unless transposed, halo within the kernel's);
+ *   KK_MIMI_CONV_FEW_ROWS  the weight-streaming kernel of the streaming steps: fp32 in and out, pad 0, dil 1, Cout >= 32, ldx == Cin, and either
+ *                          stride 1 with x_rows == out_rows + Kw - 1 and out_rows <= 128 (linear / causal conv over contiguous rows), or
+ *                          transposed with Kw == 2 * stride, out_rows == x_rows * stride, 2 <= x_rows <= 129, no res, no accumulate (row 0 of x is
+ *                          the carried previous input row: output rows [0, stride) are NOT written); in_act = ELU runs a pre-pass into elu_tmp,
+ *                          which must hold B * x_rows * ldx floats: a smaller one is refused, and only when this kernel is the one taken (no
+ *                          other path reads elu_tmp); without elu_tmp (NULL, elu_floats 0 -- they come together) such a call goes to the
+ *                          generic kernel;
+ *   KK_MIMI_CONV_GENERIC   everything else (kk_op_conv1d's kernel, here with in_act and stride > 1).
+ * out[b][q] = act(bias + sum_k sum_c in_act(x[b][q * stride - pad + k * dil][c]) w[k][c][:]) (+ res[b][q]) (+ old out when accumulate);
+ * transposed: out[b][p] sums w[k] x[b][(p + pad - k) / stride] over the k with an integral row; rows outside [0, x_rows) are zeros.
+ * w_packed [Kw][Cin][ldw] fp32 (ldw % 4 == 0, >= Cout rounded up to 64; columns >= Cout are never used).  w_frag (optional): the bf16 pack
+ * [Kw][CoutP][CinP] in fragment order (kk_op_pack_w_frag), CinP % 64 == 0, CoutP % 128 == 0; bias then has CoutP entries and must be given;
+ * with w_frag, bf16 x / out / res need pitches that are multiples of 8 and 16-byte aligned pointers.  Channels [Cin, ldx) of x are never used.
+ * x: item pitch xbs >= x_rows * ldx; out and res (res has out's dtype and row count) likewise.  in_act: 0 or 5 (ELU); act: 0 or 4 (tanh-GELU). */
+int kk_op_mimi_conv(void* stream, int B, const void* x, long long xbs, int ldx, int x_rows, int x_dtype, const float* w_packed, int ldw,
+                    const void* w_frag, int CinP, int CoutP, const float* bias, int Cin, int Cout, int Kw, int pad, int dil, int transposed,
+                    int stride, int in_act, int act, const void* res, long long rbs, int ldr, int accumulate, void* out, long long obs, int ldo,
+                    int out_rows, int out_dtype, float* elu_tmp, size_t elu_floats, int* path_out);
+/* split-RVQ decode (quantization.py:97-101): codes [B][nq][Nf] int32 (clamped into [0, bins)), codebooks [nq][bins][qdim] fp32 ->
+ * q_first [B][Nf][ld] = row of code book 0, q_rest = the sum of the rows of code books 1 .. nq-1 in ascending order in fp32 (zeros when nq == 1).
+ * Columns [qdim, ld) are not written. */
+int kk_op_mimi_rvq_sum(void* stream, int B, const int32_t* codes, const float* codebooks, int nq, int bins, int qdim, int Nf, int ld, void* q_first,
+                       void* q_rest, int dtype);
+/* depth-wise causal transposed conv, kernel 2 s, stride s (conv.py:82-95,379-401): x [B][Lin][ld] at item pitch xbs, w [2 s][C] fp32 ->
+ * out [B][Lin * s][ld] dense; out[s t + j] = x[t] w[j] + x[t - 1] w[j + s] (the second term only for t > 0).  Columns [C, ld) are not written. */
+int kk_op_mimi_upsample(void* stream, int B, const void* x, long long xbs, const float* w, int C, int ld, int Lin, int s, void* out, int dtype);
+/* nn.RoPE(traditional) in place on the q and k thirds of qkv [B][T][ld] (ld >= 3 D): pairs (2 i, 2 i + 1) of every head of size hd rotated by
+ * t * inv_freq[i], inv_freq [hd / 2] fp32.  The v third and columns >= 3 D are not touched. */
+int kk_op_mimi_rope(void* stream, int B, int T, int D, int ld, int hd, const float* inv_freq, void* qkv, int dtype);
+/* SEANet's last conv, Cout = 1 (seanet.py:258-268): out[b][t] = bias[0] + sum_k sum_c elu?(x[b][t - pad + k][c]) w_packed[(k Cin + c) ldw], rows
+ * outside [0, L) are zeros; x [B][L][ld] dense, out [B][L] fp32.  Kw * Cin <= 8192.  *form_out: which of the three kernels ran
+ * (KK_MIMI_COUT1_BF16_STAGED: bf16, Cin % 8 == 0, Cin <= 64, ld % 8 == 0, Kw <= 16; it rounds elu(x) to bf16 while staging). */
+int kk_op_mimi_conv_cout1(void* stream, int B, const void* x, int dtype, int ld, int L, int Cin, int Kw, int pad, const float* w_packed, int ldw,
+                          const float* bias, int elu, float* out, int* form_out);
+/* mx.pad(mode="edge") of the resampler (conv.py:350-367): out [B][Lp][C] row p = x [B][L][C] row clamp(p - left, 0, L - 1); fp32, dense */
+int kk_op_mimi_edge_pad(void* stream, int B, const float* x, int L, int C, int left, int Lp, float* out);
+/* EuclideanCodebook.encode + the residual update (quantization.py:35-39,84-92): dots [B][T][bins], c2 [bins], codebook [bins][qdim] ->
+ * codes[(b nq + cbi) T + t] = argmin_j (c2[j] - dots[j]) in fp32, the first index on ties, NaN distances skipped, bins - 1 when none is below
+ * +inf; residual [B][T][qdim] -= codebook[code] in fp32.  No other entry of codes is written. */
+int kk_op_mimi_rvq_argmin(void* stream, int B, const float* dots, const float* c2, const float* codebook, int bins, int qdim, int T, int nq, int cbi,
+                          float* residual, int32_t* codes);
+/* The streaming state's carry kernels.  A buffer i is bufs[i] (device) = [B items at pitch[i]][S[i] carried rows | new rows][C[i]] fp32; bufs, S, n,
+ * C, pitch are HOST arrays of nbuf entries (nbuf == 1 except for the two table ops).  B is the number of items / rows.  Arguments an op does not
+ * name are ignored by it.  Every op but SET_ACTIVE needs nbuf >= 1 and, per buffer, a non-null pointer, S, n, C >= 1 and
+ * pitch >= (S + n) * C -- for the two table ops n counts rows per code frame, F >= 1 is required and the check is pitch >= (S + n * F) * C.
+ * (S == 0 is refused: the codec never launches a carry for a buffer without carried rows.)
+ *   SHIFT            (bufs, S, n, C, pitch; nbuf == 1)  rows [n, n + S) -> [0, S) of every item (they overlap when n < S); refused when
+ *                    S * C > 8192 or when pitch is not a multiple of C
+ *   EDGE_FILL        (bufs, S, n, C, pitch; nbuf == 1)  rows [0, S) = row S of every item
+ *   EDGE_FILL_ROWS   (the same + active, pos: device int32 [B], both required)  the fill for the items with active[b] != 0 and pos[b] == 0 only
+ *   SHIFT_ROWS       (bufs, S, n, C, pitch of nbuf >= 1 buffers, table_dev, active, pos, F, pos_step)  every buffer of the table, items with
+ *                    active[b] != 0 only: rows [F n, F n + S) -> [0, S), then pos[b] += pos_step ONCE per item; inactive items and their pos
+ *                    are not touched; refused when a buffer has S * C > 8192
+ *   RESET_ROW        (the same table arguments, F as for SHIFT_ROWS, row in [0, B))  rows [0, S) of item `row` in every buffer = 0, pos[row] = 0
+ *   SET_ACTIVE       (active, mask; no buffer)  active[b] = bit b of mask, b < B <= 64
+ * The table ops need table_dev (nbuf * 32 bytes, device), active and pos; they upload the table to table_dev after synchronising `stream`. */
+int kk_op_mimi_carry(void* stream, int op, int B, int nbuf, float* const* bufs, const int* S, const int* n, const int* C, const long long* pitch,
+                     void* table_dev, int32_t* active, int32_t* pos, int F, int pos_step, int row, unsigned long long mask);
 
 /* =====================================================================================================================
  * Row-mode polyphase FIR resampler (ABI minor 10): the sample-rate edge of CSM serving.  The reference resamples whole clips

@@ -106,6 +106,16 @@ SIGNATURES = {
                                      _vp, _i, _vp, C.POINTER(C.c_int)]),
     "kk_op_adain": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _i, _f, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _i, _i]),
     "kk_op_norm_finalize": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, C.c_longlong, _vp, _i, _vp, _vp, _vp, _vp, _i, _i]),
+    "kk_op_mimi_conv": (_i, [_vp, _i, _vp, C.c_longlong, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_longlong, _i, _i,
+                             _vp, C.c_longlong, _i, _i, _i, _vp, _sz, C.POINTER(C.c_int)]),
+    "kk_op_mimi_rvq_sum": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i]),
+    "kk_op_mimi_upsample": (_i, [_vp, _i, _vp, C.c_longlong, _vp, _i, _i, _i, _i, _vp, _i]),
+    "kk_op_mimi_rope": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i]),
+    "kk_op_mimi_conv_cout1": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, C.POINTER(C.c_int)]),
+    "kk_op_mimi_edge_pad": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    "kk_op_mimi_rvq_argmin": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "kk_op_mimi_carry": (_i, [_vp, _i, _i, _i, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                              C.POINTER(C.c_longlong), _vp, _vp, _vp, _i, _i, _i, C.c_ulonglong]),
     "kk_op_layernorm": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _f, _i, _f, _vp, _i, _i]),
     "kk_op_lstm": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i]),
     "kk_op_lstm_bf16": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i]),
@@ -316,7 +326,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 19:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 20:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -354,6 +354,69 @@ __global__ __launch_bounds__(256) void elu_rows_kernel(const float* x, long long
   out[(long long)blockIdx.y * n + e] = v > 0.f ? v : expf(v) - 1.0f;
 }
 
+// ---- launch shapes of the kernels above: one function each, called by the codec and by the single-kernel entry points (kk_op_mimi_*), so a
+// test cannot pass on a grid, block or LDS size the codec does not use
+int launch_rvq_sum(const int* codes, const float* cb, int nq, int bins, int qdim, int Nf, int ld, void* q_first, void* q_rest, int B, int dtype,
+                   hipStream_t st) {
+  if (dtype == KK_BF16)
+    hipLaunchKernelGGL(rvq_sum_kernel<bf16_t>, dim3(Nf, B), dim3(256), 0, st, codes, cb, nq, bins, qdim, Nf, ld, (bf16_t*)q_first, (bf16_t*)q_rest);
+  else
+    hipLaunchKernelGGL(rvq_sum_kernel<float>, dim3(Nf, B), dim3(256), 0, st, codes, cb, nq, bins, qdim, Nf, ld, (float*)q_first, (float*)q_rest);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+// x [B][Lin rows at pitch ld, item pitch xbs] -> out [B][Lin * s][ld] dense
+int launch_upsample_dw(const void* x, long long xbs, const float* w, int C, int ld, int Lin, int s, void* out, int B, int dtype, hipStream_t st) {
+  if (dtype == KK_BF16)
+    hipLaunchKernelGGL(upsample_dw_kernel<bf16_t>, dim3(Lin * s, B), dim3(256), 0, st, (const bf16_t*)x, xbs, w, C, ld, Lin, s, (bf16_t*)out);
+  else
+    hipLaunchKernelGGL(upsample_dw_kernel<float>, dim3(Lin * s, B), dim3(256), 0, st, (const float*)x, xbs, w, C, ld, Lin, s, (float*)out);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+int launch_rope(void* qkv, const float* inv_freq, int T, int D, int ld, int hd, int B, int dtype, hipStream_t st) {
+  if (dtype == KK_BF16)
+    hipLaunchKernelGGL(rope_kernel<bf16_t>, dim3(T, B), dim3(256), 0, st, (bf16_t*)qkv, inv_freq, T, D, ld, hd);
+  else
+    hipLaunchKernelGGL(rope_kernel<float>, dim3(T, B), dim3(256), 0, st, (float*)qkv, inv_freq, T, D, ld, hd);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+// SEANet's last conv.  cout1_takes: what the three Cout = 1 kernels take at all (their K * Cin weights sit in LDS); the form is chosen here:
+//   KK_MIMI_COUT1_F32 (0) conv_cout1_kernel<float>;  KK_MIMI_COUT1_BF16 (1) conv_cout1_kernel<bf16_t> (its inner loop reads 16-byte vectors when Cin and
+//   the pitch are multiples of 8, scalars otherwise);  KK_MIMI_COUT1_BF16_STAGED (2) conv_cout1_bf16_kernel: Cin % 8 == 0, Cin <= 64, pitch % 8 == 0,
+//   K <= 16 (its LDS rows hold 64 channels)
+bool cout1_takes(int Cout, int K, int Cin) { return Cout == 1 && K >= 1 && Cin >= 1 && (size_t)K * Cin * 4 <= 32768; }
+int launch_conv_cout1(const void* x, int dtype, int ld, int L, int Cin, int K, int pad, const float* w, int ldw, const float* bias, int elu,
+                      float* out, int B, hipStream_t st, int* form) {
+  const size_t lds = (size_t)K * Cin * 4;
+  dim3 grid(kk_cdiv(L, 256), B);
+  if (dtype == KK_BF16 && Cin % 8 == 0 && Cin <= 64 && ld % 8 == 0 && K <= 16) {
+    const size_t l2 = (size_t)(256 + K - 1) * C1_LD * 2 + (size_t)K * Cin * 4;
+    hipLaunchKernelGGL(conv_cout1_bf16_kernel, grid, dim3(256), l2, st, (const bf16_t*)x, ld, L, Cin, K, pad, w, ldw, bias, elu, out);
+    if (form) *form = KK_MIMI_COUT1_BF16_STAGED;
+  } else if (dtype == KK_BF16) {
+    hipLaunchKernelGGL(conv_cout1_kernel<bf16_t>, grid, dim3(256), lds, st, (const bf16_t*)x, ld, L, Cin, K, pad, w, ldw, bias, elu, out);
+    if (form) *form = KK_MIMI_COUT1_BF16;
+  } else {
+    hipLaunchKernelGGL(conv_cout1_kernel<float>, grid, dim3(256), lds, st, (const float*)x, ld, L, Cin, K, pad, w, ldw, bias, elu, out);
+    if (form) *form = KK_MIMI_COUT1_F32;
+  }
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+int launch_edge_pad(const float* x, int L, int C, int left, int Lp, float* out, int B, hipStream_t st) {
+  hipLaunchKernelGGL(edge_pad_kernel, dim3(Lp, B), dim3(256), 0, st, x, L, C, left, Lp, out);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+int launch_rvq_argmin(const float* dots, const float* c2, const float* cb, int bins, int qdim, int T, int nq, int cbi, float* residual, int* codes,
+                      int B, hipStream_t st) {
+  hipLaunchKernelGGL(rvq_argmin_kernel, dim3(T, B), dim3(256), 0, st, dots, c2, cb, bins, qdim, T, nq, cbi, residual, codes);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------------------- host
 struct Packer {
   kk_mimi* m;
@@ -424,6 +487,7 @@ struct Run : Workspace {
   int adt = -1;  // activation dtype of this run (-1: the model's)
   float* elu_tmp = nullptr;  // dense scratch for an ELU'd input of the few-rows kernel (streaming steps allocate it)
   size_t elu_floats = 0;
+  int path = -1;  // the kernel the last conv() launched: KK_MIMI_CONV_GENERIC / _FEW_ROWS / _MFMA (kk_op_mimi_conv reports it)
   Run(kk_mimi* m_, hipStream_t st_, int B_, void* ws, size_t ws_bytes) : m(m_), st(st_), B(B_) {
     base = (char*)ws; cap = ws_bytes; dry = ws == nullptr;
   }
@@ -437,7 +501,8 @@ struct Run : Workspace {
     t.p = raw((size_t)B * rows * t.ld * (t.dtype == KK_BF16 ? 2 : 4));
     return t;
   }
-  // conv / transposed conv / linear
+  // conv / transposed conv / linear.  Works on its arguments, st, B, elu_tmp / elu_floats and dry alone: it must not dereference m
+  // (kk_op_mimi_conv runs it on a Run without a model)
   int conv(const PackedConv& w, const Act& x, const Act& out, int pad, int dil, bool transposed, int stride, int in_act, int act_,
            const Act* res, int accumulate) {
     if (dry) return 0;
@@ -453,6 +518,7 @@ struct Run : Workspace {
       g.lin = KKLen{nullptr, 0, Lin}; g.lout = KKLen{nullptr, 0, Lout};
       g.in_slope = 1.f; g.scale = 1.f; g.accumulate = accumulate; g.act = act_; g.in_act = in_act;
       g.slabwise = 1;  // the whole-K form is routed per measured layer class (Ctx::conv of kk_model.hip); the codec's plain convolutions are none of them
+      path = KK_MIMI_CONV_MFMA;
       return kk_launch_conv_mfma4(g, B, KK_BF16, st);
     }
     // few rows per item (the streaming steps): the weight-streaming kernel instead of the 64-row conv tile.  Chosen by the rows per ITEM,
@@ -485,9 +551,11 @@ struct Run : Workspace {
         else if (M <= 8) hipLaunchKernelGGL(linear_rows_kernel<8>, dim3(kk_cdiv(g.N, LR_COLS), kk_cdiv(M, 8), nz), dim3(256), 0, st, g);
         else hipLaunchKernelGGL(linear_rows_kernel<16>, dim3(kk_cdiv(g.N, LR_COLS), kk_cdiv(M, 16), nz), dim3(256), 0, st, g);
         KK_CHECK_LAUNCH();
+        path = KK_MIMI_CONV_FEW_ROWS;
         return 0;
       }
     }
+    path = KK_MIMI_CONV_GENERIC;
     KKConvArgs a;
     memset(&a, 0, sizeof a);
     a.x = x.p; a.xbs = x.bs(); a.ldx = x.ld;
@@ -529,11 +597,7 @@ int run_transformer(Run& r, const std::vector<MimiLayer>& layers, Act& x, Act& n
     KK_TRY(r.layernorm(x, n, L.n1w.p, L.n1b.p));
     KK_TRY(r.conv(L.in_proj, n, qkv, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
     if (!r.dry) {
-      if (bf)
-        hipLaunchKernelGGL(rope_kernel<bf16_t>, dim3(T, B), dim3(256), 0, r.st, (bf16_t*)qkv.p, m->inv_freq.p, T, D, qkv.ld, D / c.num_heads);
-      else
-        hipLaunchKernelGGL(rope_kernel<float>, dim3(T, B), dim3(256), 0, r.st, (float*)qkv.p, m->inv_freq.p, T, D, qkv.ld, D / c.num_heads);
-      KK_CHECK_LAUNCH();
+      KK_TRY(launch_rope(qkv.p, m->inv_freq.p, T, D, qkv.ld, D / c.num_heads, B, bf ? KK_BF16 : KK_F32, r.st));
       KKAttnArgs a;
       memset(&a, 0, sizeof a);
       a.qkv = qkv.p; a.bs = qkv.bs(); a.ld = qkv.ld; a.out = att.p; a.obs = att.bs(); a.ldo = att.ld;
@@ -571,19 +635,10 @@ int run_seanet(Run& r, const Act& x, float* pcm, const char* who) {
   }
   Act out;
   out.p = pcm; out.rows = y.rows; out.C = 1; out.ld = 1; out.dtype = KK_F32;
-  if (m->final_conv.Cout == 1 && (size_t)m->final_conv.K * m->final_conv.Cin * 4 <= 32768) {
+  if (cout1_takes(m->final_conv.Cout, m->final_conv.K, m->final_conv.Cin)) {
     if (!r.dry) {
       const PackedConv& w = m->final_conv;
-      const size_t lds = (size_t)w.K * w.Cin * 4;
-      dim3 grid(kk_cdiv(y.rows, 256), B);
-      if (y.dtype == KK_BF16 && w.Cin % 8 == 0 && w.Cin <= 64 && y.ld % 8 == 0 && w.K <= 16) {
-        const size_t l2 = (size_t)(256 + w.K - 1) * C1_LD * 2 + (size_t)w.K * w.Cin * 4;
-        hipLaunchKernelGGL(conv_cout1_bf16_kernel, grid, dim3(256), l2, r.st, (const bf16_t*)y.p, y.ld, y.rows, w.Cin, w.K, c.last_ksize - 1, w.w, w.ldw, w.b, 1, pcm);
-      } else if (y.dtype == KK_BF16)
-        hipLaunchKernelGGL(conv_cout1_kernel<bf16_t>, grid, dim3(256), lds, r.st, (const bf16_t*)y.p, y.ld, y.rows, w.Cin, w.K, c.last_ksize - 1, w.w, w.ldw, w.b, 1, pcm);
-      else
-        hipLaunchKernelGGL(conv_cout1_kernel<float>, grid, dim3(256), lds, r.st, (const float*)y.p, y.ld, y.rows, w.Cin, w.K, c.last_ksize - 1, w.w, w.ldw, w.b, 1, pcm);
-      KK_CHECK_LAUNCH();
+      KK_TRY(launch_conv_cout1(y.p, y.dtype, y.ld, y.rows, w.Cin, w.K, c.last_ksize - 1, w.w, w.ldw, w.b, 1, pcm, B, r.st, nullptr));
     }
     return 0;
   }
@@ -601,22 +656,13 @@ int run_decode(Run& r, int Nf, const int* codes, float* pcm) {
   Act n = r.act(T, D), qkv = r.act(T, 3 * D), att = r.act(T, D), hbuf = r.act(T, c.dim_feedforward);
   if (r.oom) return kk_fail("kk_mimi_decode: workspace too small");
   if (!r.dry) {
-    if (bf) {
-      hipLaunchKernelGGL(rvq_sum_kernel<bf16_t>, dim3(Nf, B), dim3(256), 0, r.st, codes, m->codebooks.p, c.nq, c.bins, Q, Nf, q1.ld, (bf16_t*)q1.p, (bf16_t*)q2.p);
-    } else {
-      hipLaunchKernelGGL(rvq_sum_kernel<float>, dim3(Nf, B), dim3(256), 0, r.st, codes, m->codebooks.p, c.nq, c.bins, Q, Nf, q1.ld, (float*)q1.p, (float*)q2.p);
-    }
-    KK_CHECK_LAUNCH();
+    KK_TRY(launch_rvq_sum(codes, m->codebooks.p, c.nq, c.bins, Q, Nf, q1.ld, q1.p, q2.p, B, bf ? KK_BF16 : KK_F32, r.st));
   }
   KK_TRY(r.conv(m->proj_first, q1, x0, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
   if (c.nq > 1) KK_TRY(r.conv(m->proj_rest, q2, x0, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 1));
   r.note("quantized", x0);
   if (!r.dry) {
-    if (bf)
-      hipLaunchKernelGGL(upsample_dw_kernel<bf16_t>, dim3(T, B), dim3(256), 0, r.st, (const bf16_t*)x0.p, x0.bs(), m->up_w.p, D, x0.ld, Nf, c.upsample_stride, (bf16_t*)xu.p);
-    else
-      hipLaunchKernelGGL(upsample_dw_kernel<float>, dim3(T, B), dim3(256), 0, r.st, (const float*)x0.p, x0.bs(), m->up_w.p, D, x0.ld, Nf, c.upsample_stride, (float*)xu.p);
-    KK_CHECK_LAUNCH();
+    KK_TRY(launch_upsample_dw(x0.p, x0.bs(), m->up_w.p, D, x0.ld, Nf, c.upsample_stride, xu.p, B, bf ? KK_BF16 : KK_F32, r.st));  // T = Nf * stride rows
     // xu is kept for the debug hook: the transformer updates x in place
     if (hipMemcpyAsync(x.p, xu.p, (size_t)B * T * xu.ld * (bf ? 2 : 4), hipMemcpyDeviceToDevice, r.st) != hipSuccess) return kk_fail("kk_mimi_decode: copy failed");
   }
@@ -665,6 +711,7 @@ struct StateBuf {
 // rows [n, n + S) -> rows [0, S) of one item's buffer `q` ([S + n][C]); the ranges overlap when n < S, so the block reads everything before
 // it writes.  One body for the plain carry (state_shift_kernel) and the masked row-mode one (state_shift_rows_kernel).
 constexpr int SHIFT_PER_THREAD = 32;
+bool shift_fits(int S, int C) { return (long long)S * C <= 256 * SHIFT_PER_THREAD; }  // what state_shift_body holds in registers
 __device__ __forceinline__ void state_shift_body(float* q, int S, int n, int C) {
   const int total = S * C;
   float v[SHIFT_PER_THREAD];
@@ -702,7 +749,7 @@ __global__ __launch_bounds__(256) void state_edge_fill_rows_kernel(float* p, int
 
 int state_shift(const StateBuf& b, int B, hipStream_t st) {
   if (b.S == 0) return 0;
-  if (b.S * b.C > 256 * SHIFT_PER_THREAD) return kk_fail("mimi stream: carried state larger than the shift kernel takes");
+  if (!shift_fits(b.S, b.C)) return kk_fail("mimi stream: carried state larger than the shift kernel takes");
   hipLaunchKernelGGL(state_shift_kernel, dim3(B), dim3(256), 0, st, b.p, b.S, b.n, b.C, b.pitch());
   KK_CHECK_LAUNCH();
   return 0;
@@ -737,6 +784,33 @@ __global__ __launch_bounds__(256) void state_reset_row_kernel(const RowBuf* tab,
   float* q = t.p + (long long)row * t.pitch;
   for (int e = threadIdx.x; e < t.S * t.C; e += 256) q[e] = 0.f;
   if (blockIdx.x == 0 && threadIdx.x == 0) pos[row] = 0;
+}
+
+// launch shapes of the carry kernels (the codec and kk_op_mimi_carry call these)
+int launch_edge_fill(float* p, int S, int n, int C, long long pitch, int B, hipStream_t st) {
+  hipLaunchKernelGGL(state_edge_fill_kernel, dim3(B), dim3(256), 0, st, p, S, n, C, pitch);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+int launch_edge_fill_rows(float* p, int S, int C, long long pitch, const int* active, const int* pos, int B, hipStream_t st) {
+  hipLaunchKernelGGL(state_edge_fill_rows_kernel, dim3(B), dim3(256), 0, st, p, S, C, pitch, active, pos);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+int launch_shift_rows(const RowBuf* tab, int ntable, int F, const int* active, int* pos, int pos_step, int B, hipStream_t st) {
+  hipLaunchKernelGGL(state_shift_rows_kernel, dim3(ntable, B), dim3(256), 0, st, tab, F, active, pos, pos_step);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+int launch_reset_row(const RowBuf* tab, int ntable, int row, int* pos, hipStream_t st) {
+  hipLaunchKernelGGL(state_reset_row_kernel, dim3(ntable), dim3(256), 0, st, tab, row, pos);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+int launch_set_active(int* active, unsigned long long mask, int n, hipStream_t st) {  // n <= 64: one block of 64 threads, one 64-bit mask
+  hipLaunchKernelGGL(set_active_kernel, dim3(1), dim3(64), 0, st, active, mask, n);
+  KK_CHECK_LAUNCH();
+  return 0;
 }
 
 }  // namespace
@@ -890,9 +964,7 @@ int stream_begin(Run& r, kk_mimi_stream* s) {  // zero state on the first step a
 int stream_end(Run& r, kk_mimi_stream* s, int F, int T, const StateBuf* last) {
   if (r.dry) return 0;
   if (s->rows_mode) {
-    hipLaunchKernelGGL(state_shift_rows_kernel, dim3(s->ntable, r.B), dim3(256), 0, r.st, s->table_dev, F, s->active_dev, s->pos_dev, T);
-    KK_CHECK_LAUNCH();
-    return 0;
+    return launch_shift_rows(s->table_dev, s->ntable, F, s->active_dev, s->pos_dev, T, r.B, r.st);
   }
   if (last) KK_TRY(state_shift(*last, r.B, r.st));
   s->pos += T;
@@ -926,16 +998,14 @@ int run_decode_step(Run& r, kk_mimi_stream* s, const int* codes, float* pcm_out)
   // ---- quantizer.decode of the new frames, straight behind the previous one
   Act xq = s->resample.fresh();
   if (!r.dry) {
-    hipLaunchKernelGGL(rvq_sum_kernel<float>, dim3(F, B), dim3(256), 0, r.st, codes, m->codebooks.p, c.nq, c.bins, Q, F, q1.ld, (float*)q1.p, (float*)q2.p);
-    KK_CHECK_LAUNCH();
+    KK_TRY(launch_rvq_sum(codes, m->codebooks.p, c.nq, c.bins, Q, F, q1.ld, q1.p, q2.p, B, KK_F32, r.st));
   }
   KK_TRY(r.conv(m->proj_first, q1, xq, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
   if (c.nq > 1) KK_TRY(r.conv(m->proj_rest, q2, xq, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 1));
   // ---- upsample.step: the depthwise transposed conv over [previous | new]; its first `us` rows repeat the last step's
   if (!r.dry) {
     const Act w = s->resample.all();
-    hipLaunchKernelGGL(upsample_dw_kernel<float>, dim3((F + 1) * us, B), dim3(256), 0, r.st, (const float*)w.p, w.bs(), m->up_w.p, D, w.ld, F + 1, us, (float*)xu.p);
-    KK_CHECK_LAUNCH();
+    KK_TRY(launch_upsample_dw(w.p, w.bs(), m->up_w.p, D, w.ld, F + 1, us, xu.p, B, KK_F32, r.st));
   }
   KK_TRY(copy_rows(r, xu, us, x, F * us));
   KK_TRY(copy_rows(r, x, 0, xup, F * us));  // debug hook: the transformer updates x in place
@@ -1012,12 +1082,9 @@ int run_encode_step(Run& r, kk_mimi_stream* s, const float* pcm, int* codes) {
   // downsample.step: conv k = 2 us, stride us, 'edge' left padding on the first step
   KK_TRY(copy_rows(r, x, 0, s->resample.fresh(), T));
   if (!r.dry && s->rows_mode) {  // per row: active rows at position 0 only
-    hipLaunchKernelGGL(state_edge_fill_rows_kernel, dim3(B), dim3(256), 0, r.st, s->resample.p, s->resample.S, s->resample.C, s->resample.pitch(),
-                       (const int*)s->active_dev, (const int*)s->pos_dev);
-    KK_CHECK_LAUNCH();
+    KK_TRY(launch_edge_fill_rows(s->resample.p, s->resample.S, s->resample.C, s->resample.pitch(), s->active_dev, s->pos_dev, B, r.st));
   } else if (!r.dry && s->fresh) {
-    hipLaunchKernelGGL(state_edge_fill_kernel, dim3(B), dim3(256), 0, r.st, s->resample.p, s->resample.S, s->resample.n, s->resample.C, s->resample.pitch());
-    KK_CHECK_LAUNCH();
+    KK_TRY(launch_edge_fill(s->resample.p, s->resample.S, s->resample.n, s->resample.C, s->resample.pitch(), B, r.st));
   }
   KK_TRY(r.conv(m->enc_down, s->resample.all(), xd, 0, 1, false, us, 0, KK_ACT_NONE, nullptr, 0));
   KK_TRY(carry(r, s, s->resample));
@@ -1027,9 +1094,8 @@ int run_encode_step(Run& r, kk_mimi_stream* s, const float* pcm, int* codes) {
     if (i == 1) KK_TRY(r.conv(m->inproj_rest, xd, res, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
     KK_TRY(r.conv(m->cb_dot[i], res, dots, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
     if (!r.dry) {
-      hipLaunchKernelGGL(rvq_argmin_kernel, dim3(F, B), dim3(256), 0, r.st, (const float*)dots.p, m->c2.p + (size_t)i * c.bins,
-                         m->codebooks.p + (size_t)i * c.bins * Q, c.bins, Q, F, c.nq, i, (float*)res.p, codes);
-      KK_CHECK_LAUNCH();
+      KK_TRY(launch_rvq_argmin((const float*)dots.p, m->c2.p + (size_t)i * c.bins, m->codebooks.p + (size_t)i * c.bins * Q, c.bins, Q, F, c.nq, i,
+                               (float*)res.p, codes, B, r.st));
     }
   }
   return stream_end(r, s, F, T, nullptr);  // (s->last went behind enc_final)
@@ -1080,8 +1146,7 @@ int run_encode(Run& r, int N, const float* pcm, int* codes) {
   Act xp = r.act(Lp, D), xd = r.act(Nf, D), res = r.act(Nf, Q), dots = r.act(Nf, c.bins);
   if (r.oom) return kk_fail("kk_mimi_encode: workspace too small");
   if (!r.dry) {
-    hipLaunchKernelGGL(edge_pad_kernel, dim3(Lp, B), dim3(256), 0, r.st, (const float*)xt.p, T, D, left, Lp, (float*)xp.p);
-    KK_CHECK_LAUNCH();
+    KK_TRY(launch_edge_pad((const float*)xt.p, T, D, left, Lp, (float*)xp.p, B, r.st));
   }
   KK_TRY(r.conv(m->enc_down, xp, xd, 0, 1, false, s, 0, KK_ACT_NONE, nullptr, 0));
   r.note("downsampled", xd);
@@ -1091,9 +1156,8 @@ int run_encode(Run& r, int N, const float* pcm, int* codes) {
     if (i == 1) KK_TRY(r.conv(m->inproj_rest, xd, res, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
     KK_TRY(r.conv(m->cb_dot[i], res, dots, 0, 1, false, 1, 0, KK_ACT_NONE, nullptr, 0));
     if (!r.dry) {
-      hipLaunchKernelGGL(rvq_argmin_kernel, dim3(Nf, B), dim3(256), 0, r.st, (const float*)dots.p, m->c2.p + (size_t)i * c.bins,
-                         m->codebooks.p + (size_t)i * c.bins * Q, c.bins, Q, Nf, c.nq, i, (float*)res.p, codes);
-      KK_CHECK_LAUNCH();
+      KK_TRY(launch_rvq_argmin((const float*)dots.p, m->c2.p + (size_t)i * c.bins, m->codebooks.p + (size_t)i * c.bins * Q, c.bins, Q, Nf, c.nq, i,
+                               (float*)res.p, codes, B, r.st));
     }
   }
   return 0;
@@ -1419,7 +1483,7 @@ static int stream_create_rows(kk_mimi* m, bool encoder, int max_batch, int max_f
     if (b.S > 0) tab.push_back(RowBuf{b.p, b.S, npf, b.C, b.pitch()});
   };
   bool fits = true;
-  auto chk = [&](const StateBuf& b) { fits = fits && b.S * b.C <= 256 * SHIFT_PER_THREAD; };
+  auto chk = [&](const StateBuf& b) { fits = fits && shift_fits(b.S, b.C); };
   const kk_mimi_config& c = m->cfg;
   if (!encoder) {
     int npf = c.upsample_stride;
@@ -1474,8 +1538,7 @@ extern "C" int kk_mimi_stream_create_rows_encoder(kk_mimi* m, int max_batch, int
 extern "C" int kk_mimi_stream_reset_row(kk_mimi_stream* s, void* stream, int row) {
   if (!s || !s->rows_mode) return kk_fail("kk_mimi_stream_reset_row: not a row-mode stream (kk_mimi_stream_create_rows)");
   if (row < 0 || row >= s->max_batch) return kk_fail("kk_mimi_stream_reset_row: row out of range");
-  hipLaunchKernelGGL(state_reset_row_kernel, dim3(s->ntable), dim3(256), 0, (hipStream_t)stream, s->table_dev, row, s->pos_dev);
-  KK_CHECK_LAUNCH();
+  KK_TRY(launch_reset_row(s->table_dev, s->ntable, row, s->pos_dev, (hipStream_t)stream));
   s->row_frames[row] = 0;
   return 0;
 }
@@ -1504,8 +1567,7 @@ extern "C" int kk_mimi_decode_step_rows(kk_mimi_stream* s, void* stream, int F, 
   if (workspace_bytes < kk_mimi_stream_workspace_bytes(s, s->max_batch)) return kk_failf("%s: workspace too small", who);
   stream_set_rows(s, F);
   { std::lock_guard<std::mutex> lk(s->m->dbg_mu); s->m->dbg.map.clear(); }
-  hipLaunchKernelGGL(set_active_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, s->active_dev, mask, s->max_batch);
-  KK_CHECK_LAUNCH();
+  KK_TRY(launch_set_active(s->active_dev, mask, s->max_batch, (hipStream_t)stream));
   Run r(s->m, (hipStream_t)stream, s->max_batch, workspace, workspace_bytes);
   r.adt = KK_F32;
   KK_TRY(run_decode_step(r, s, codes, pcm_out));
@@ -1536,8 +1598,7 @@ extern "C" int kk_mimi_encode_step_rows(kk_mimi_stream* s, void* stream, int F, 
   if (workspace_bytes < kk_mimi_stream_workspace_bytes(s, s->max_batch)) return kk_failf("%s: workspace too small", who);
   stream_set_rows(s, F);
   { std::lock_guard<std::mutex> lk(s->m->dbg_mu); s->m->dbg.map.clear(); }
-  hipLaunchKernelGGL(set_active_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, s->active_dev, mask, s->max_batch);
-  KK_CHECK_LAUNCH();
+  KK_TRY(launch_set_active(s->active_dev, mask, s->max_batch, (hipStream_t)stream));
   Run r(s->m, (hipStream_t)stream, s->max_batch, workspace, workspace_bytes);
   r.adt = KK_F32;
   KK_TRY(run_encode_step(r, s, pcm, codes_out));
@@ -1608,4 +1669,150 @@ extern "C" int kk_mimi_debug_fetch(kk_mimi* m, void* stream, const char* name, f
   if (!m || !name || !dst) return kk_fail("kk_mimi_debug_fetch: bad argument");
   std::lock_guard<std::mutex> lk(m->dbg_mu);
   return m->dbg.fetch("kk_mimi_debug_fetch", name, (hipStream_t)stream, dst);
+}
+
+// ------------------------------------------------------------------------------------------------ single-kernel entry points (ABI minor 20)
+// The codec's own dispatch and launch functions on caller-owned device buffers (tests/test_gpu_mimi_kernels.py).  Every argument is checked
+// here, on the host, before any launch.
+namespace {
+bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+bool dt_ok(int d) { return d == KK_F32 || d == KK_BF16; }
+}  // namespace
+
+extern "C" int kk_op_mimi_conv(void* stream, int B, const void* x, long long xbs, int ldx, int x_rows, int x_dtype, const float* w_packed, int ldw,
+                               const void* w_frag, int CinP, int CoutP, const float* bias, int Cin, int Cout, int Kw, int pad, int dil,
+                               int transposed, int stride, int in_act, int act, const void* res, long long rbs, int ldr, int accumulate, void* out,
+                               long long obs, int ldo, int out_rows, int out_dtype, float* elu_tmp, size_t elu_floats, int* path_out) {
+  const char* who = "kk_op_mimi_conv";
+  if (path_out) *path_out = -1;
+  if (B <= 0 || !x || !w_packed || !out) return kk_failf("%s: B must be positive, x / w_packed / out non-null", who);
+  if (!dt_ok(x_dtype) || !dt_ok(out_dtype)) return kk_failf("%s: dtypes are KK_DTYPE_F32 or KK_DTYPE_BF16", who);
+  if (Cin < 1 || Cout < 1 || Kw < 1 || x_rows < 1 || out_rows < 1) return kk_failf("%s: Cin, Cout, Kw and the row counts must be positive", who);
+  if (pad < 0 || dil < 1 || stride < 1 || (transposed && dil != 1)) return kk_failf("%s: need pad >= 0, dil >= 1, stride >= 1, dil == 1 when transposed", who);
+  if (in_act != 0 && in_act != KK_ACT_ELU) return kk_failf("%s: in_act is 0 or ELU (5)", who);
+  if (act != KK_ACT_NONE && act != KK_ACT_GELU_TANH) return kk_failf("%s: act is none (0) or tanh-GELU (4)", who);
+  if (ldw % 4 != 0 || ldw < kk_cdiv(Cout, 64) * 64) return kk_failf("%s: ldw must be a multiple of 4 covering Cout rounded up to 64", who);
+  if (ldx < Cin || ldo < Cout || (res && ldr < Cout)) return kk_failf("%s: a row pitch is smaller than its channel count", who);
+  if (xbs < (long long)x_rows * ldx || obs < (long long)out_rows * ldo || (res && rbs < (long long)out_rows * ldr))
+    return kk_failf("%s: an item pitch is smaller than rows * row pitch", who);
+  if (accumulate != 0 && accumulate != 1) return kk_failf("%s: accumulate is 0 or 1", who);
+  if ((elu_tmp == nullptr) != (elu_floats == 0)) return kk_failf("%s: elu_tmp and elu_floats come together", who);
+  PackedConv w;
+  w.Cin = Cin; w.Cout = Cout; w.K = Kw; w.ldw = ldw; w.w = w_packed; w.b = bias; w.has_bias = bias != nullptr;
+  if (w_frag) {
+    if (CinP % 64 != 0 || CoutP % 128 != 0 || CinP < Cin || CoutP < Cout) return kk_failf("%s: w_frag needs CinP %% 64 == 0 >= Cin, CoutP %% 128 == 0 >= Cout", who);
+    if (!bias) return kk_failf("%s: w_frag needs a bias of CoutP entries (zeros where there is none)", who);
+    if (!al16(w_frag)) return kk_failf("%s: w_frag must be 16-byte aligned", who);
+    // the bf16 tensors of the codec (Run::act) have 64-multiple pitches; the MFMA kernel reads and writes 16-byte vectors
+    if (x_dtype == KK_BF16 && out_dtype == KK_BF16 &&
+        (ldx % 8 || ldo % 8 || xbs % 8 || obs % 8 || !al16(x) || !al16(out) || (res && (ldr % 8 || rbs % 8 || !al16(res)))))
+      return kk_failf("%s: with w_frag, bf16 tensors need pitches that are multiples of 8 and 16-byte aligned pointers", who);
+    w.mfma = true; w.CinP = CinP; w.CoutP = CoutP; w.wf = (const bf16_t*)w_frag;
+  }
+  Act ax, ao, ar;
+  ax.p = const_cast<void*>(x); ax.rows = x_rows; ax.C = Cin; ax.ld = ldx; ax.dtype = x_dtype; ax.bstride = xbs;
+  ao.p = out; ao.rows = out_rows; ao.C = Cout; ao.ld = ldo; ao.dtype = out_dtype; ao.bstride = obs;
+  if (res) { ar.p = const_cast<void*>(res); ar.rows = out_rows; ar.C = Cout; ar.ld = ldr; ar.dtype = out_dtype; ar.bstride = rbs; }
+  Run r(nullptr, (hipStream_t)stream, B, nullptr, 0);
+  r.dry = false;  // (no workspace: every tensor is the caller's)
+  r.elu_tmp = elu_tmp; r.elu_floats = elu_floats;
+  const int rc = r.conv(w, ax, ao, pad, dil, transposed != 0, stride, in_act, act, res ? &ar : nullptr, accumulate);
+  if (path_out) *path_out = r.path;
+  return rc;
+}
+
+extern "C" int kk_op_mimi_rvq_sum(void* stream, int B, const int32_t* codes, const float* codebooks, int nq, int bins, int qdim, int Nf, int ld,
+                                  void* q_first, void* q_rest, int dtype) {
+  const char* who = "kk_op_mimi_rvq_sum";
+  if (B <= 0 || nq < 1 || bins < 1 || qdim < 1 || Nf < 1) return kk_failf("%s: B, nq, bins, qdim and Nf must be positive", who);
+  if (!codes || !codebooks || !q_first || !q_rest) return kk_failf("%s: null pointer", who);
+  if (!dt_ok(dtype) || ld < qdim) return kk_failf("%s: dtype is f32 or bf16, ld >= qdim", who);
+  return launch_rvq_sum(codes, codebooks, nq, bins, qdim, Nf, ld, q_first, q_rest, B, dtype, (hipStream_t)stream);
+}
+
+extern "C" int kk_op_mimi_upsample(void* stream, int B, const void* x, long long xbs, const float* w, int C, int ld, int Lin, int s, void* out,
+                                   int dtype) {
+  const char* who = "kk_op_mimi_upsample";
+  if (B <= 0 || C < 1 || Lin < 1 || s < 1) return kk_failf("%s: B, C, Lin and the stride must be positive", who);
+  if (!x || !w || !out || x == out) return kk_failf("%s: null pointer, or out == x", who);
+  if (!dt_ok(dtype) || ld < C || xbs < (long long)Lin * ld) return kk_failf("%s: dtype is f32 or bf16, ld >= C, xbs >= Lin * ld", who);
+  return launch_upsample_dw(x, xbs, w, C, ld, Lin, s, out, B, dtype, (hipStream_t)stream);
+}
+
+extern "C" int kk_op_mimi_rope(void* stream, int B, int T, int D, int ld, int hd, const float* inv_freq, void* qkv, int dtype) {
+  const char* who = "kk_op_mimi_rope";
+  if (B <= 0 || T < 1 || D < 2 || hd < 2 || hd % 2 != 0 || D % hd != 0) return kk_failf("%s: need B, T > 0, an even head size dividing D", who);
+  if (!inv_freq || !qkv || !dt_ok(dtype) || ld < 3 * D) return kk_failf("%s: null pointer, bad dtype, or ld < 3 * D", who);
+  return launch_rope(qkv, inv_freq, T, D, ld, hd, B, dtype, (hipStream_t)stream);
+}
+
+extern "C" int kk_op_mimi_conv_cout1(void* stream, int B, const void* x, int dtype, int ld, int L, int Cin, int Kw, int pad, const float* w_packed,
+                                     int ldw, const float* bias, int elu, float* out, int* form_out) {
+  const char* who = "kk_op_mimi_conv_cout1";
+  if (form_out) *form_out = -1;
+  if (B <= 0 || L < 1 || !x || !w_packed || !out) return kk_failf("%s: B and L must be positive, x / w_packed / out non-null", who);
+  if (!dt_ok(dtype) || ld < Cin || ldw < 1 || pad < 0 || (elu != 0 && elu != 1)) return kk_failf("%s: bad dtype, ld < Cin, ldw < 1, pad < 0 or elu not 0 / 1", who);
+  if (!cout1_takes(1, Kw, Cin)) return kk_failf("%s: Kw * Cin weights must be 1 .. 8192 floats (they sit in LDS)", who);
+  if (dtype == KK_BF16 && Cin % 8 == 0 && ld % 8 == 0 && !al16(x)) return kk_failf("%s: bf16 rows read as 16-byte vectors need a 16-byte aligned x", who);
+  return launch_conv_cout1(x, dtype, ld, L, Cin, Kw, pad, w_packed, ldw, bias, elu, out, B, (hipStream_t)stream, form_out);
+}
+
+extern "C" int kk_op_mimi_edge_pad(void* stream, int B, const float* x, int L, int C, int left, int Lp, float* out) {
+  const char* who = "kk_op_mimi_edge_pad";
+  if (B <= 0 || L < 1 || C < 1 || left < 0 || Lp < 1) return kk_failf("%s: need B, L, C, Lp > 0 and left >= 0", who);
+  if (!x || !out || x == out) return kk_failf("%s: null pointer, or out == x", who);
+  return launch_edge_pad(x, L, C, left, Lp, out, B, (hipStream_t)stream);
+}
+
+extern "C" int kk_op_mimi_rvq_argmin(void* stream, int B, const float* dots, const float* c2, const float* codebook, int bins, int qdim, int T,
+                                     int nq, int cbi, float* residual, int32_t* codes) {
+  const char* who = "kk_op_mimi_rvq_argmin";
+  if (B <= 0 || bins < 1 || qdim < 1 || T < 1 || nq < 1) return kk_failf("%s: B, bins, qdim, T and nq must be positive", who);
+  if (cbi < 0 || cbi >= nq) return kk_failf("%s: code book index outside [0, nq)", who);
+  if (!dots || !c2 || !codebook || !residual || !codes) return kk_failf("%s: null pointer", who);
+  return launch_rvq_argmin(dots, c2, codebook, bins, qdim, T, nq, cbi, residual, codes, B, (hipStream_t)stream);
+}
+
+extern "C" int kk_op_mimi_carry(void* stream, int op, int B, int nbuf, float* const* bufs, const int* S, const int* n, const int* C,
+                                const long long* pitch, void* table_dev, int32_t* active, int32_t* pos, int F, int pos_step, int row,
+                                unsigned long long mask) {
+  const char* who = "kk_op_mimi_carry";
+  hipStream_t st = (hipStream_t)stream;
+  if (op < KK_MIMI_CARRY_SHIFT || op > KK_MIMI_CARRY_SET_ACTIVE) return kk_failf("%s: unknown op %d", who, op);
+  if (B <= 0) return kk_failf("%s: B must be positive", who);
+  if (op == KK_MIMI_CARRY_SET_ACTIVE) {
+    if (!active || B > 64) return kk_failf("%s: set_active needs `active` and at most 64 rows (one 64-bit mask)", who);
+    return launch_set_active(active, mask, B, st);
+  }
+  if (nbuf < 1 || !bufs || !S || !n || !C || !pitch) return kk_failf("%s: needs at least one buffer and its S / n / C / pitch", who);
+  const bool table = op == KK_MIMI_CARRY_SHIFT_ROWS || op == KK_MIMI_CARRY_RESET_ROW;
+  if (!table && nbuf != 1) return kk_failf("%s: this op takes one buffer", who);
+  if (table && F < 1) return kk_failf("%s: F must be positive", who);
+  for (int i = 0; i < nbuf; ++i) {
+    // S == 0 is what the codec never launches (state_shift returns, the table skips such a buffer)
+    if (!bufs[i] || S[i] < 1 || n[i] < 1 || C[i] < 1) return kk_failf("%s: buffer %d: null pointer or S / n / C < 1", who, i);
+    const long long rows = S[i] + (long long)n[i] * (table ? F : 1);  // table ops: n is the rows per code frame
+    if (pitch[i] < rows * C[i]) return kk_failf("%s: buffer %d: pitch smaller than (S + n) * C", who, i);
+    if (op != KK_MIMI_CARRY_EDGE_FILL && op != KK_MIMI_CARRY_EDGE_FILL_ROWS && op != KK_MIMI_CARRY_RESET_ROW && !shift_fits(S[i], C[i]))
+      return kk_failf("%s: buffer %d: carried state larger than the shift kernel takes (S * C > %d)", who, i, 256 * SHIFT_PER_THREAD);
+  }
+  if (op == KK_MIMI_CARRY_SHIFT) {
+    StateBuf b;
+    b.p = bufs[0]; b.S = S[0]; b.n = n[0]; b.C = C[0]; b.maxB = B;
+    if (pitch[0] % C[0] != 0) return kk_failf("%s: shift: the pitch must be a whole number of rows", who);
+    b.nmax = (int)(pitch[0] / C[0]) - S[0];
+    return state_shift(b, B, st);
+  }
+  if (op == KK_MIMI_CARRY_EDGE_FILL) return launch_edge_fill(bufs[0], S[0], n[0], C[0], pitch[0], B, st);
+  if (!active || !pos) return kk_failf("%s: the row-mode ops need `active` and `pos`", who);
+  if (op == KK_MIMI_CARRY_EDGE_FILL_ROWS) return launch_edge_fill_rows(bufs[0], S[0], C[0], pitch[0], active, pos, B, st);
+  if (!table_dev) return kk_failf("%s: the table ops need table_dev (nbuf * 32 bytes on the device)", who);
+  if (op == KK_MIMI_CARRY_RESET_ROW && (row < 0 || row >= B)) return kk_failf("%s: row out of range", who);
+  std::vector<RowBuf> tab;
+  for (int i = 0; i < nbuf; ++i) tab.push_back(RowBuf{bufs[i], S[i], n[i], C[i], pitch[i]});
+  static_assert(sizeof(RowBuf) == 32, "kk_op_mimi_carry documents 32 bytes per table entry");
+  if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(table_dev, tab.data(), tab.size() * sizeof(RowBuf), hipMemcpyHostToDevice) != hipSuccess)
+    return kk_failf("%s: table upload failed", who);
+  if (op == KK_MIMI_CARRY_SHIFT_ROWS) return launch_shift_rows((const RowBuf*)table_dev, nbuf, F, active, pos, pos_step, B, st);
+  return launch_reset_row((const RowBuf*)table_dev, nbuf, row, pos, st);
 }
