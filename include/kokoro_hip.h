@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 20  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 21  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -59,7 +59,10 @@ extern "C" {
                             19: the fused statistics' finalize / fold step on caller-owned buffers (kk_op_norm_finalize);
                             20: the Mimi codec's own kernels and its conv dispatch on caller-owned buffers (kk_op_mimi_conv, kk_op_mimi_rvq_sum,
                                kk_op_mimi_upsample, kk_op_mimi_rope, kk_op_mimi_conv_cout1, kk_op_mimi_edge_pad, kk_op_mimi_rvq_argmin,
-                               kk_op_mimi_carry) */
+                               kk_op_mimi_carry);
+                            21: Whisper sampling: the sampled pick and window groups on one cross K/V slice (kk_op_whisper_pick_sampled,
+                               kk_whisper_text_state_bytes_groups, kk_whisper_text_set_audio_groups,
+                               kk_whisper_text_sample_setup, KK_WHISPER_MAX_GROUP) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -892,6 +895,15 @@ typedef struct kk_whisper_pick_state {   /* one per row */
 int kk_op_whisper_pick(void* stream, int B, const float* logits, long long ldl, const kk_whisper_pick_params* params, const uint32_t* suppress,
                        kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next, int32_t* not_ended);
 int kk_op_whisper_pick_reset(void* stream, int B, kk_whisper_pick_state* state, int32_t* not_ended);
+/* The same step at temperature > 0 (decoding.py:263-278 behind the same filters): token ~ Categorical(softmax(l / temperature)) over the filtered
+ * logits l, logprob = l[token] - logsumexp(l) on the UNTEMPERED l; everything else as kk_op_whisper_pick.  The draw is Gumbel-max in the pass that
+ * takes the log-sum-exp: token = argmax_i (l_i / temperature - log(-log u_i)) over the unmasked i, lowest index on ties; u_i = ((r >> 9) + 0.5) 2^-23
+ * with r = word i & 3 of Philox4x32-10 on the counter (low state.count, high streams[b], i >> 2, a fixed tag) and the key `seed`.  A row's draws
+ * depend on seed, its stream id and its own history alone.  streams: device uint32 [B].  A temperature that is not finite or not > 0 is refused
+ * before anything is launched. */
+int kk_op_whisper_pick_sampled(void* stream, int B, const float* logits, long long ldl, const kk_whisper_pick_params* params, const uint32_t* suppress,
+                               float temperature, uint64_t seed, const uint32_t* streams, kk_whisper_pick_state* state, int32_t* tokens, int cap,
+                               int32_t* next, int32_t* not_ended);
 
 typedef struct kk_whisper_text kk_whisper_text;
 /* the text fields of ModelDimensions plus the audio side's output shape; n_text_state / n_text_head must be 64, n_text_state a multiple of 128 and
@@ -928,6 +940,18 @@ int kk_whisper_text_pick(kk_whisper_text* m, void* stream);
 /* read back (HOST destinations, synchronise): the count of rows not ended; the token buffers [B][cap] and the rows' states [B] */
 int kk_whisper_text_not_ended(kk_whisper_text* m, void* stream, int32_t* out);
 int kk_whisper_text_read(kk_whisper_text* m, void* stream, int32_t* tokens, int cap, kk_whisper_pick_state* rows);
+/* ---- groups: n_group decoder rows per window on ONE cross K/V slice (best_of) -------------------------------------------------
+ * set_audio_groups is set_audio for n_audio windows (audio_features fp32 [n_audio][n_audio_ctx][n_audio_state]) whose cross K/V is projected and
+ * kept once per window; the state then carries B = n_audio * n_group rows, row b on window b / n_group, 1 <= n_group <= KK_WHISPER_MAX_GROUP.
+ * forward, rewind, pick_setup, pick, not_ended and read work on the B rows; workspace: ..._workspace_bytes(m, B, 1).  set_audio is n_group = 1.
+ * The capturing forward refuses a state with n_group > 1. */
+#define KK_WHISPER_MAX_GROUP 8
+size_t kk_whisper_text_state_bytes_groups(const kk_whisper_text* m, int n_audio, int n_group);
+int kk_whisper_text_set_audio_groups(kk_whisper_text* m, void* stream, int n_audio, int n_group, const float* audio_features, void* state,
+                                     size_t state_bytes, void* workspace, size_t workspace_bytes);
+/* after pick_setup: pick launches kk_op_whisper_pick_sampled with this temperature, seed and the rows' stream ids (HOST uint32 [B], copied;
+ * synchronises) until the next pick_setup, which returns the handle to the greedy pick.  Refuses a temperature that is not finite or not > 0. */
+int kk_whisper_text_sample_setup(kk_whisper_text* m, void* stream, float temperature, uint64_t seed, const uint32_t* streams);
 
 /* ---- row mode: decoder rows that join and leave one running batch -----------------------------------------------------------
  * A second state beside the window of set_audio, on the same weights and the same stream: max_rows <= KK_WHISPER_MAX_ROWS rows, each with its

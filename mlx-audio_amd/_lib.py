@@ -65,6 +65,7 @@ class KKWhisperRowsItem(C.Structure):  # kk_whisper_rows_item
 
 
 WHISPER_MAX_ROWS = 32  # KK_WHISPER_MAX_ROWS
+WHISPER_MAX_GROUP = 8  # KK_WHISPER_MAX_GROUP
 
 
 class KKLlamaArgs(C.Structure):
@@ -248,6 +249,7 @@ SIGNATURES = {
     "kk_op_whisper_embed": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "kk_op_whisper_pick": (_i, [_vp, _i, _vp, C.c_longlong, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "kk_op_whisper_pick_reset": (_i, [_vp, _i, _vp, _vp]),
+    "kk_op_whisper_pick_sampled": (_i, [_vp, _i, _vp, C.c_longlong, _vp, _vp, _f, _u64, _vp, _vp, _vp, _i, _vp, _vp]),
     "kk_whisper_text_create": (_i, [C.POINTER(KKWhisperTextConfig), C.POINTER(_vp)]),
     "kk_whisper_text_destroy": (None, [_vp]),
     "kk_whisper_text_load_tensor": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), _i, _vp]),
@@ -262,6 +264,9 @@ SIGNATURES = {
     "kk_whisper_text_pick": (_i, [_vp, _vp]),
     "kk_whisper_text_not_ended": (_i, [_vp, _vp, C.POINTER(C.c_int32)]),
     "kk_whisper_text_read": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "kk_whisper_text_state_bytes_groups": (_sz, [_vp, _i, _i]),
+    "kk_whisper_text_set_audio_groups": (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp, _sz]),
+    "kk_whisper_text_sample_setup": (_i, [_vp, _vp, _f, _u64, _vp]),
     "kk_whisper_text_rows_state_bytes": (_sz, [_vp, _i]),
     "kk_whisper_text_rows_workspace_bytes": (_sz, [_vp, _i, _i]),
     "kk_whisper_text_rows_open": (_i, [_vp, _vp, _i, _vp, _sz]),
@@ -326,7 +331,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 20:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 21:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

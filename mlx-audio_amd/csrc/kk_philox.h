@@ -1,5 +1,5 @@
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11), counter-based: shared by the Kokoro noise source
-// (kk_source.hip: Box-Muller on top) and the CSM sampler's device uniforms (kk_csm.hip).
+// (kk_source.hip: Box-Muller on top), the CSM sampler's device uniforms (kk_csm.hip) and the Whisper pick's Gumbel noise (kk_whisper_text.hip).
 #pragma once
 #include <stdint.h>
 
@@ -28,3 +28,7 @@ __device__ __forceinline__ void philox4(uint64_t seed, uint64_t ctr, uint32_t su
 }
 // 24 random bits -> a float strictly inside (0, 1)
 __device__ __forceinline__ float philox_unit(uint32_t r) { return ((float)(r >> 8) + 0.5f) * (1.0f / 16777216.0f); }
+// 23 random bits -> a float in [2^-24, 1 - 2^-24]: a 23-bit integer plus a half is exact in fp32, so neither end of the unit interval is ever
+// returned (philox_unit's 24-bit integer plus a half rounds to 2^24 for the top values of r and gives exactly 1.0 there).  The Whisper pick's
+// Gumbel noise -log(-log u) needs the open interval; philox_unit's users keep their bits.
+__device__ __forceinline__ float philox_open(uint32_t r) { return ((float)(r >> 9) + 0.5f) * (1.0f / 8388608.0f); }

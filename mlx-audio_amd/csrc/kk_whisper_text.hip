@@ -30,11 +30,19 @@
 //   sum of exponentials of the fully filtered logits, each thread online over its strided share, the shares combined by xor-butterflies and then
 //   across the 16 waves in wave order.  Thread 0 updates the row's state.  The count of rows not yet ended is an integer atomic.  One body (pick_row) serves
 //   the launch-wide kernel (one params, one bitmask) and the per-row kernel of row mode (each row its own; the row's state.ended is its flag).
+//   The sampled form (temperature > 0) is the same body with one more branch in pass B: Gumbel-max on Philox uniforms beside the sum of
+//   exponentials, so a sampled step reads the row's logits as often as a greedy one; a row's draws depend on (seed, its stream id, its history) alone.
+//
+// ---- groups -------------------------------------------------------------------------------------------------------------------------------
+//   A window state may carry n_group decoder rows per window (best_of): the cross K/V is projected and kept once per WINDOW, the self K/V, pick state
+//   and token stores once per row, and the row-table kernel writes a second table item_cross[r] = item[r] / n_group that the cross-attention reads.
+//   n_group = 1 is set_audio: one table, the launches and arguments of before.
 //
 // ---- row mode (the end of this file) ---------------------------------------------------------------------------------------------------
 //   Rows with their own window, position, pick parameters and lifetime in a second state buffer.  A round is the window's launch sequence behind
 //   text_plan_kernel, which fills the per-row index arrays and tokens from a table of items passed as the launch's argument.
 #include "kk_host.h"
+#include "kk_philox.h"
 #include "../../include/kokoro_hip.h"
 
 #include <math.h>
@@ -298,10 +306,21 @@ __device__ __forceinline__ Osm osm_block(Osm v, Osm* sh) {  // all 1024 threads;
   return r;
 }
 
+// what a sampled pick adds to a row's arguments: 1 / temperature, the Philox key and the row's stream id
+struct PickDraw {
+  float inv_t;
+  uint64_t seed;
+  uint32_t stream;
+};
+
 // The pick of ONE row by one workgroup: lg the row's logits, P its parameters, suppress its bitmask (or null), st its state, tokens its store of
 // `cap` ids, next where its choice goes.  not_ended: the launch-wide counter, or null (the per-row form: the row's state.ended is its flag).
+// SAMPLE: the token is drawn from softmax(l / T) over the filtered logits l by Gumbel-max in the same pass that takes the log-sum-exp of the
+// UNTEMPERED l (decoding.py:263-270): token = argmax_i (l_i / T - log(-log u_i)), lowest index on ties, u_i = philox_open of word i & 3 of
+// philox4(seed, stream << 32 | state.count, i >> 2).  A masked token gets no noise.  A row's draws depend on (seed, stream, its own history) alone.
+template <bool SAMPLE>
 __device__ __forceinline__ void pick_row(const float* lg, const kk_whisper_pick_params P, const uint32_t* suppress, kk_whisper_pick_state* st, int32_t* tokens,
-                                         int cap, int32_t* next, int32_t* not_ended, Osm* sh) {
+                                         int cap, int32_t* next, int32_t* not_ended, Osm* sh, const PickDraw dr = PickDraw{0.f, 0, 0}) {
   const int tid = threadIdx.x;
   const kk_whisper_pick_state S = *st;
   const int V = P.n_vocab, tb = P.timestamp_begin;
@@ -351,15 +370,30 @@ __device__ __forceinline__ void pick_row(const float* lg, const kk_whisper_pick_
     u = osm_block(u, sh);
     mass = t.m != -INFINITY && t.m + logf(t.s) > u.m;
   }
-  Osm f = {-INFINITY, 0.f, 0};
+  Osm f = {-INFINITY, 0.f, 0}, best = {-INFINITY, 1.f, 0};  // best (SAMPLE): the highest noisy score of the share and its lowest index
+  const uint64_t ctr = ((uint64_t)dr.stream << 32) | (uint32_t)S.count;
   walk([&](int i, float v, unsigned word) {
     const bool masked = pre(i, word) || (ts && (rules(i) || (mass && i < tb)));
     osm_add(f, masked ? -INFINITY : v, i);
+    if constexpr (SAMPLE) {
+      if (!masked && v != -INFINITY) {
+        uint32_t r[4];
+        philox4(dr.seed, ctr, (uint32_t)i >> 2, r);
+        const int k = i & 3;
+        const float u = philox_open(k == 0 ? r[0] : (k == 1 ? r[1] : (k == 2 ? r[2] : r[3])));
+        const float score = v * dr.inv_t - logf(-logf(u));
+        if (score > best.m) {  // the share is walked in rising i: the first of equal scores stays
+          best.m = score;
+          best.i = i;
+        }
+      }
+    }
   });
   f = osm_block(f, sh);
+  if constexpr (SAMPLE) best = osm_block(best, sh);  // (.s rides along unused, as in the text maximum above)
   if (tid != 0) return;
   kk_whisper_pick_state N = S;
-  int tok = f.i;
+  int tok = SAMPLE ? best.i : f.i;
   float lp = 0.f;
   if (f.m == -INFINITY) tok = P.eot;  // everything masked: end the row
   else lp = lg[tok] - (f.m + logf(f.s));
@@ -384,7 +418,17 @@ __global__ __launch_bounds__(1024) void pick_kernel(const float* logits, long lo
                                                     kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next, int32_t* not_ended) {
   __shared__ Osm sh[16];
   const int b = blockIdx.x;
-  pick_row(logits + (long long)b * ldl, *params, suppress, state + b, tokens + (long long)b * cap, cap, next + b, not_ended, sh);
+  pick_row<false>(logits + (long long)b * ldl, *params, suppress, state + b, tokens + (long long)b * cap, cap, next + b, not_ended, sh);
+}
+
+// launch-wide, sampled: row b draws on its stream id streams[b]
+__global__ __launch_bounds__(1024) void pick_sampled_kernel(const float* logits, long long ldl, const kk_whisper_pick_params* params, const uint32_t* suppress,
+                                                            float inv_t, uint64_t seed, const uint32_t* streams, kk_whisper_pick_state* state, int32_t* tokens,
+                                                            int cap, int32_t* next, int32_t* not_ended) {
+  __shared__ Osm sh[16];
+  const int b = blockIdx.x;
+  pick_row<true>(logits + (long long)b * ldl, *params, suppress, state + b, tokens + (long long)b * cap, cap, next + b, not_ended, sh,
+                 PickDraw{inv_t, seed, streams[b]});
 }
 
 // per-row: block j picks for decoder row sel.row[j] on logits row sel.logit[j], with that row's params, bitmask (`words` words each), state and store
@@ -395,8 +439,8 @@ __global__ __launch_bounds__(1024) void pick_rows_kernel(PickSel sel, const floa
                                                          const uint32_t* suppress, int words, kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next) {
   __shared__ Osm sh[16];
   const int r = sel.row[blockIdx.x];
-  pick_row(logits + (long long)sel.logit[blockIdx.x] * ldl, params[r], suppress + (long long)r * words, state + r, tokens + (long long)r * cap, cap, next + r, nullptr,
-           sh);
+  pick_row<false>(logits + (long long)sel.logit[blockIdx.x] * ldl, params[r], suppress + (long long)r * words, state + r, tokens + (long long)r * cap, cap, next + r,
+                  nullptr, sh);
 }
 
 __global__ void pick_reset_kernel(kk_whisper_pick_state* state, int B, int32_t* not_ended) {
@@ -405,12 +449,15 @@ __global__ void pick_reset_kernel(kk_whisper_pick_state* state, int B, int32_t* 
   if (b == 0) *not_ended = B;
 }
 
-// the per-row index arrays of a forward call: row r = (b, s) sits at position pos + s of item b
-__global__ void text_rows_kernel(int B, int S, int pos, int n_text_ctx, int n_audio_ctx, int* item, int* posr, int* len_self, int* len_cross, int* cache_row) {
+// the per-row index arrays of a forward call: row r = (b, s) sits at position pos + s of item b.  item_cross (a grouped state, else null): the window
+// whose cross K/V row b reads, b / n_group
+__global__ void text_rows_kernel(int B, int S, int pos, int n_text_ctx, int n_audio_ctx, int n_group, int* item, int* item_cross, int* posr, int* len_self,
+                                 int* len_cross, int* cache_row) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= B * S) return;
   const int b = r / S, p = pos + r % S;
   item[r] = b;
+  if (item_cross) item_cross[r] = b / n_group;
   posr[r] = p;
   len_self[r] = p + 1;
   len_cross[r] = n_audio_ctx;
@@ -508,6 +555,20 @@ extern "C" int kk_op_whisper_pick(void* stream, int B, const float* logits, long
   return 0;
 }
 
+extern "C" int kk_op_whisper_pick_sampled(void* stream, int B, const float* logits, long long ldl, const kk_whisper_pick_params* params, const uint32_t* suppress,
+                                          float temperature, uint64_t seed, const uint32_t* streams, kk_whisper_pick_state* state, int32_t* tokens, int cap,
+                                          int32_t* next, int32_t* not_ended) {
+  if (!logits || !params || !streams || !state || !tokens || !next || !not_ended) return kk_fail("kk_op_whisper_pick_sampled: null argument");
+  if (B < 1 || cap < 1 || ldl < 1) return kk_fail("kk_op_whisper_pick_sampled: bad argument");
+  const float inv_t = 1.0f / temperature;
+  if (!(temperature > 0.f) || !std::isfinite(temperature) || !std::isfinite(inv_t))
+    return kk_fail("kk_op_whisper_pick_sampled: temperature must be finite and > 0 (temperature 0 is kk_op_whisper_pick)");
+  hipLaunchKernelGGL(pick_sampled_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, logits, ldl, params, suppress, inv_t, seed, streams, state, tokens, cap, next,
+                     not_ended);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int kk_op_whisper_pick_reset(void* stream, int B, kk_whisper_pick_state* state, int32_t* not_ended) {
   if (!state || !not_ended || B < 1) return kk_fail("kk_op_whisper_pick_reset: bad argument");
   hipLaunchKernelGGL(pick_reset_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, state, B, not_ended);
@@ -538,6 +599,10 @@ struct kk_whisper_text {
   // the window in flight (set_audio): the caller's state buffer, its batch and the rows' common position
   char* state = nullptr;
   int B = 0, at = 0;
+  int n_audio = 0, n_group = 1;  // B = n_audio * n_group rows; the n_group rows of a window read ONE cross K/V slice (set_audio_groups)
+  bool sampling = false;         // sample_setup: pick launches the sampled kernel until the next pick_setup
+  float temperature = 0.f;
+  uint64_t seed = 0;
   const float* last_logits = nullptr;  // the last forward's last-position logits [B][last_ld], in the caller's memory
   long long last_ld = 0;
   // row mode (rows_open), beside the window: the caller's second state buffer and what the host knows of every row
@@ -561,15 +626,16 @@ int check_text_cfg(const kk_whisper_text_config& c) {
 }
 
 struct TextState {  // the caller's state buffer
-  bf16_t *cross, *self;  // [layer][B][ctx][2 D]: K | V
+  bf16_t *cross, *self;  // K | V: cross [layer][n_audio][ctx][2 D], one slice per WINDOW; self [layer][B][ctx][2 D], one per row
   kk_whisper_pick_params* params;
   uint32_t* suppress;
   kk_whisper_pick_state* rows;
   int32_t *tokens, *next, *not_ended;
+  uint32_t* streams;  // [B] stream ids of a sampled pick (sample_setup); behind everything the greedy path lays out
 };
-void plan_state(const kk_whisper_text_config& c, int B, Workspace& ws, TextState& s) {
+void plan_state(const kk_whisper_text_config& c, int n_audio, int B, Workspace& ws, TextState& s) {
   const size_t D = c.n_text_state, L = c.n_text_layer;
-  s.cross = (bf16_t*)ws.raw(L * B * c.n_audio_ctx * 2 * D * 2);
+  s.cross = (bf16_t*)ws.raw(L * n_audio * c.n_audio_ctx * 2 * D * 2);
   s.self = (bf16_t*)ws.raw(L * B * c.n_text_ctx * 2 * D * 2);
   s.params = (kk_whisper_pick_params*)ws.raw(sizeof(kk_whisper_pick_params));
   s.suppress = (uint32_t*)ws.raw(((size_t)c.n_vocab + 31) / 32 * 4);
@@ -577,11 +643,13 @@ void plan_state(const kk_whisper_text_config& c, int B, Workspace& ws, TextState
   s.tokens = (int32_t*)ws.raw((size_t)B * c.n_text_ctx * 4);
   s.next = (int32_t*)ws.raw((size_t)B * 4);
   s.not_ended = (int32_t*)ws.raw(4);
+  s.streams = (uint32_t*)ws.raw((size_t)B * 4);
 }
 struct TextWork {
   float *x, *ln, *q, *att, *h, *scratch;
   int *item, *posr, *len_self, *len_cross, *cache_row;
   bf16_t* feat;
+  int* item_cross;  // a grouped state's second row table
 };
 void plan_work(const kk_whisper_text_config& c, int B, int S, Workspace& ws, TextWork& p) {
   const size_t D = c.n_text_state, R = (size_t)B * S;
@@ -598,6 +666,7 @@ void plan_work(const kk_whisper_text_config& c, int B, int S, Workspace& ws, Tex
   p.len_cross = (int*)ws.raw(R * 4);
   p.cache_row = (int*)ws.raw(R * 4);
   p.feat = (bf16_t*)ws.raw((size_t)B * c.n_audio_ctx * D * 2);  // set_audio only
+  p.item_cross = (int*)ws.raw(R * 4);
 }
 int bind(Workspace& ws, void* mem, size_t bytes) {
   ws.base = (char*)(((uintptr_t)mem + 255) & ~(uintptr_t)255);
@@ -721,13 +790,15 @@ extern "C" int kk_whisper_text_finalize(kk_whisper_text* m, void* stream) {
   return 0;
 }
 
-extern "C" size_t kk_whisper_text_state_bytes(const kk_whisper_text* m, int B) {
-  if (!m || B < 1) return 0;
+extern "C" size_t kk_whisper_text_state_bytes_groups(const kk_whisper_text* m, int n_audio, int n_group) {
+  if (!m || n_audio < 1 || n_group < 1 || n_group > KK_WHISPER_MAX_GROUP) return 0;
   Workspace ws;
   TextState s;
-  plan_state(m->cfg, B, ws, s);
+  plan_state(m->cfg, n_audio, n_audio * n_group, ws, s);
   return ws.used + 256;
 }
+
+extern "C" size_t kk_whisper_text_state_bytes(const kk_whisper_text* m, int B) { return kk_whisper_text_state_bytes_groups(m, B, 1); }
 
 extern "C" size_t kk_whisper_text_workspace_bytes(const kk_whisper_text* m, int B, int S) {
   if (!m || B < 1 || S < 1) return 0;
@@ -737,39 +808,56 @@ extern "C" size_t kk_whisper_text_workspace_bytes(const kk_whisper_text* m, int 
   return ws.used + 256;
 }
 
-extern "C" int kk_whisper_text_set_audio(kk_whisper_text* m, void* stream, int B, const float* audio_features, void* state, size_t state_bytes, void* workspace,
-                                         size_t workspace_bytes) {
-  if (!m || !audio_features || !state || !workspace || B < 1) return kk_fail("kk_whisper_text_set_audio: bad argument");
-  if (!m->finalized) return kk_fail("kk_whisper_text_set_audio: model not finalized");
+namespace {
+// the one body of set_audio (n_group 1) and set_audio_groups: n_audio windows, n_group decoder rows on each window's cross K/V
+int text_set_audio(const char* who, kk_whisper_text* m, void* stream, int n_audio, int n_group, const float* audio_features, void* state, size_t state_bytes,
+                   void* workspace, size_t workspace_bytes) {
+  if (!m || !audio_features || !state || !workspace || n_audio < 1) return kk_failf("%s: bad argument", who);
+  if (n_group < 1 || n_group > KK_WHISPER_MAX_GROUP) return kk_failf("%s: n_group = %d is outside [1, %d]", who, n_group, KK_WHISPER_MAX_GROUP);
+  if (!m->finalized) return kk_failf("%s: model not finalized", who);
   const kk_whisper_text_config& c = m->cfg;
-  const int D = c.n_text_state, ctx = c.n_audio_ctx;
+  const int D = c.n_text_state, ctx = c.n_audio_ctx, B = n_audio * n_group;
   hipStream_t st = (hipStream_t)stream;
   Workspace ss, ws;
   bind(ss, state, state_bytes);
   bind(ws, workspace, workspace_bytes);
   TextState s;
   TextWork p;
-  plan_state(c, B, ss, s);
+  plan_state(c, n_audio, B, ss, s);
   plan_work(c, B, 1, ws, p);
-  if (ss.oom) return kk_fail("kk_whisper_text_set_audio: state buffer too small");
-  if (ws.oom) return kk_fail("kk_whisper_text_set_audio: workspace too small");
-  KK_TRY(kk_launch_convert(audio_features, KK_F32, (long long)ctx * D, D, p.feat, KK_BF16, (long long)ctx * D, D, D, ctx, B, st));  // rounded once
+  if (ss.oom) return kk_failf("%s: state buffer too small", who);
+  if (ws.oom) return kk_failf("%s: workspace too small", who);
+  KK_TRY(kk_launch_convert(audio_features, KK_F32, (long long)ctx * D, D, p.feat, KK_BF16, (long long)ctx * D, D, D, ctx, n_audio, st));  // rounded once
   for (int li = 0; li < c.n_text_layer; ++li) {  // whisper.py:114-116, once per window: key | value of every layer on the bf16 MFMA kernel
     const TLin& l = m->layers[li].ckv;
     KKMfmaArgs g;
     memset(&g, 0, sizeof g);
     g.x = p.feat; g.xbs = (long long)ctx * D; g.ldx = D; g.w = m->wdev + l.w; g.CinP = D; g.CoutP = 2 * D; g.Cin = D;
-    g.bias = m->fdev + l.b; g.out = s.cross + (size_t)li * B * ctx * 2 * D; g.obs = (long long)ctx * 2 * D; g.ldo = 2 * D;
+    g.bias = m->fdev + l.b; g.out = s.cross + (size_t)li * n_audio * ctx * 2 * D; g.obs = (long long)ctx * 2 * D; g.ldo = 2 * D;
     g.Cout = 2 * D; g.Kw = 1; g.mode = KK_CONV; g.stride = 1; g.pad = 0; g.dil = 1; g.Q = ctx; g.Lo_rows = ctx;
     g.lin = KKLen{nullptr, 0, ctx}; g.lout = KKLen{nullptr, 0, ctx};
     g.in_slope = 1.0f; g.scale = 1.0f; g.act = KK_ACT_NONE;
-    KK_TRY(kk_launch_conv_mfma(g, B, KK_BF16, st));
+    KK_TRY(kk_launch_conv_mfma(g, n_audio, KK_BF16, st));
   }
   m->state = (char*)state;
   m->B = B;
+  m->n_audio = n_audio;
+  m->n_group = n_group;
+  m->sampling = false;
   m->at = 0;
   m->last_logits = nullptr;
   return 0;
+}
+}  // namespace
+
+extern "C" int kk_whisper_text_set_audio(kk_whisper_text* m, void* stream, int B, const float* audio_features, void* state, size_t state_bytes, void* workspace,
+                                         size_t workspace_bytes) {
+  return text_set_audio("kk_whisper_text_set_audio", m, stream, B, 1, audio_features, state, state_bytes, workspace, workspace_bytes);
+}
+
+extern "C" int kk_whisper_text_set_audio_groups(kk_whisper_text* m, void* stream, int n_audio, int n_group, const float* audio_features, void* state,
+                                                size_t state_bytes, void* workspace, size_t workspace_bytes) {
+  return text_set_audio("kk_whisper_text_set_audio_groups", m, stream, n_audio, n_group, audio_features, state, state_bytes, workspace, workspace_bytes);
 }
 
 extern "C" int kk_whisper_text_position(const kk_whisper_text* m) { return m && m->state ? m->at : -1; }
@@ -795,9 +883,10 @@ struct QkCapture {  // the capturing forward: raw cross-attention scores of the 
 struct TextPass {
   kk_whisper_text* m;
   hipStream_t st;
-  int items;
+  int items, items_cross;  // slots of the self store (one per row) and of the cross store (one per window)
   bf16_t* self;
   const bf16_t* cross;
+  const int* item_cross;   // per flat row, the cross slot it reads (the row's own slot when every row has its window)
   const TextWork& p;
 
   // a Linear over `rows` rows, 16 at a time (S = 1: one launch, every weight byte read once for the batch)
@@ -827,7 +916,7 @@ struct TextPass {
     for (int li = 0; li < c.n_text_layer; ++li) {  // whisper.py:157-168
       const TLayer& L = m->layers[li];
       bf16_t* selfc = self + (size_t)li * items * c.n_text_ctx * 2 * D;
-      const bf16_t* crossc = cross + (size_t)li * items * c.n_audio_ctx * 2 * D;
+      const bf16_t* crossc = cross + (size_t)li * items_cross * c.n_audio_ctx * 2 * D;
       KK_TRY(ln(L.attn_ln_w, L.attn_ln_b, p.x, D, R));
       KK_TRY(lin(L.q, 0, D, p.ln, D, R, KK_ACT_NONE, nullptr, p.q, D, nullptr, nullptr));
       KK_TRY(lin(L.k, 0, D, p.ln, D, R, KK_ACT_NONE, nullptr, nullptr, D, selfc, p.cache_row));      // K and V of the new positions straight into the cache
@@ -851,7 +940,7 @@ struct TextPass {
           }
         }
       }
-      KK_TRY(launch_attn_rows(st, R, H, p.q, crossc, 0, D, items, c.n_audio_ctx, 2 * D, p.item, p.len_cross, p.att, p.scratch));
+      KK_TRY(launch_attn_rows(st, R, H, p.q, crossc, 0, D, items_cross, c.n_audio_ctx, 2 * D, item_cross, p.len_cross, p.att, p.scratch));
       KK_TRY(lin(L.cout, 0, D, p.att, D, R, KK_ACT_NONE, p.x, p.x, D, nullptr, nullptr));
       KK_TRY(ln(L.mlp_ln_w, L.mlp_ln_b, p.x, D, R));
       KK_TRY(lin(L.mlp1, 0, 4 * D, p.ln, D, R, KK_ACT_GELU, nullptr, p.h, 4 * D, nullptr, nullptr));
@@ -881,20 +970,22 @@ int text_forward(const char* who, kk_whisper_text* m, void* stream, int B, int S
   bind(ws, workspace, workspace_bytes);
   TextState s;
   TextWork p;
-  plan_state(c, B, ss, s);
+  plan_state(c, m->n_audio, B, ss, s);
   plan_work(c, B, S, ws, p);
   if (ws.oom) return kk_failf("%s: workspace too small", who);
+  if (cap && m->n_group != 1) return kk_failf("%s: the window was set with n_group = %d; the capturing forward runs on a plain set_audio state", who, m->n_group);
+  int* item_cross = m->n_group > 1 ? p.item_cross : nullptr;  // n_group 1: the row's own slot, one table as before
   if (!tokens) {  // the step after a pick: the tokens it chose
     if (S != 1) return kk_failf("%s: tokens may be null only for S = 1 (the tokens of the last pick)", who);
     tokens = s.next;
   }
-  hipLaunchKernelGGL(text_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, st, B, S, m->at, c.n_text_ctx, c.n_audio_ctx, p.item, p.posr, p.len_self, p.len_cross,
-                     p.cache_row);
+  hipLaunchKernelGGL(text_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, st, B, S, m->at, c.n_text_ctx, c.n_audio_ctx, m->n_group, p.item, item_cross, p.posr,
+                     p.len_self, p.len_cross, p.cache_row);
   KK_CHECK_LAUNCH();
   hipLaunchKernelGGL(embed_kernel, dim3(R), dim3(256), 0, st, tokens, p.posr, m->wdev + m->emb.w, V, m->fdev + m->pos, c.n_text_ctx, D, p.x);
   KK_CHECK_LAUNCH();
 
-  const TextPass run{m, st, B, s.self, s.cross, p};
+  const TextPass run{m, st, B, m->n_audio, s.self, s.cross, item_cross ? item_cross : p.item, p};
   KK_TRY(run.layers(R, cap, B, S));
   if (all_positions) {
     KK_TRY(run.logits(p.x, D, R, logits_out));
@@ -946,13 +1037,33 @@ extern "C" int kk_whisper_text_pick_setup(kk_whisper_text* m, void* stream, cons
   Workspace ss;
   bind(ss, m->state, (size_t)-1 / 2);
   TextState s;
-  plan_state(c, m->B, ss, s);
+  plan_state(c, m->n_audio, m->B, ss, s);
   const size_t words = ((size_t)c.n_vocab + 31) / 32;
   if (hipMemcpyAsync(s.params, params, sizeof *params, hipMemcpyHostToDevice, st) != hipSuccess) return kk_fail("kk_whisper_text_pick_setup: upload failed");
   if ((suppress ? hipMemcpyAsync(s.suppress, suppress, words * 4, hipMemcpyHostToDevice, st) : hipMemsetAsync(s.suppress, 0, words * 4, st)) != hipSuccess)
     return kk_fail("kk_whisper_text_pick_setup: upload failed");
   if (hipStreamSynchronize(st) != hipSuccess) return kk_fail("kk_whisper_text_pick_setup: stream sync failed");  // the host arrays may go away
+  m->sampling = false;
   return kk_op_whisper_pick_reset(stream, m->B, s.rows, s.not_ended);
+}
+
+extern "C" int kk_whisper_text_sample_setup(kk_whisper_text* m, void* stream, float temperature, uint64_t seed, const uint32_t* streams) {
+  const char* who = "kk_whisper_text_sample_setup";
+  if (!m || !streams) return kk_failf("%s: null argument", who);
+  if (!m->state) return kk_failf("%s: set_audio first", who);
+  if (!(temperature > 0.f) || !std::isfinite(temperature) || !std::isfinite(1.0f / temperature))
+    return kk_failf("%s: temperature must be finite and > 0 (temperature 0 is the greedy pick: leave this call out)", who);
+  hipStream_t st = (hipStream_t)stream;
+  Workspace ss;
+  bind(ss, m->state, (size_t)-1 / 2);
+  TextState s;
+  plan_state(m->cfg, m->n_audio, m->B, ss, s);
+  if (hipMemcpyAsync(s.streams, streams, (size_t)m->B * 4, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return kk_failf("%s: upload failed", who);  // synchronised: the host array may go away
+  m->sampling = true;
+  m->temperature = temperature;
+  m->seed = seed;
+  return 0;
 }
 
 extern "C" int kk_whisper_text_pick(kk_whisper_text* m, void* stream) {
@@ -961,7 +1072,10 @@ extern "C" int kk_whisper_text_pick(kk_whisper_text* m, void* stream) {
   Workspace ss;
   bind(ss, m->state, (size_t)-1 / 2);
   TextState s;
-  plan_state(m->cfg, m->B, ss, s);
+  plan_state(m->cfg, m->n_audio, m->B, ss, s);
+  if (m->sampling)
+    return kk_op_whisper_pick_sampled(stream, m->B, m->last_logits, m->last_ld, s.params, s.suppress, m->temperature, m->seed, s.streams, s.rows, s.tokens,
+                                      m->cfg.n_text_ctx, s.next, s.not_ended);
   return kk_op_whisper_pick(stream, m->B, m->last_logits, m->last_ld, s.params, s.suppress, s.rows, s.tokens, m->cfg.n_text_ctx, s.next, s.not_ended);
 }
 
@@ -971,7 +1085,7 @@ extern "C" int kk_whisper_text_not_ended(kk_whisper_text* m, void* stream, int32
   Workspace ss;
   bind(ss, m->state, (size_t)-1 / 2);
   TextState s;
-  plan_state(m->cfg, m->B, ss, s);
+  plan_state(m->cfg, m->n_audio, m->B, ss, s);
   hipStream_t st = (hipStream_t)stream;
   if (hipMemcpyAsync(out, s.not_ended, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
     return kk_fail("kk_whisper_text_not_ended: read failed");
@@ -984,7 +1098,7 @@ extern "C" int kk_whisper_text_read(kk_whisper_text* m, void* stream, int32_t* t
   Workspace ss;
   bind(ss, m->state, (size_t)-1 / 2);
   TextState s;
-  plan_state(m->cfg, m->B, ss, s);
+  plan_state(m->cfg, m->n_audio, m->B, ss, s);
   hipStream_t st = (hipStream_t)stream;
   const int n = cap < m->cfg.n_text_ctx ? cap : m->cfg.n_text_ctx;
   if (hipMemcpy2DAsync(tokens, (size_t)cap * 4, s.tokens, (size_t)m->cfg.n_text_ctx * 4, (size_t)n * 4, m->B, hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -1184,7 +1298,7 @@ extern "C" int kk_whisper_text_rows_forward(kk_whisper_text* m, void* stream, co
   KK_CHECK_LAUNCH();
   hipLaunchKernelGGL(embed_kernel, dim3((int)R), dim3(256), 0, st, p.tok, p.t.posr, m->wdev + m->emb.w, V, m->fdev + m->pos, c.n_text_ctx, D, p.t.x);
   KK_CHECK_LAUNCH();
-  const TextPass run{m, st, N, s.self, s.cross, p.t};
+  const TextPass run{m, st, N, N, s.self, s.cross, p.t.item, p.t};
   KK_TRY(run.layers((int)R, nullptr, 0, 0));
   const float* x = p.t.x;
   if (!identity) {  // a round of steps wants every row: nothing to gather

@@ -436,6 +436,30 @@ class Model:
 
         return decode(self, *a, **kw)
 
+    def sample(self, *a, **kw):
+        """`decode` at temperature > 0 with `best_of` candidates and the maximum-likelihood ranker, see whisper_sampling.sample"""
+        if self._text is None:
+            raise NotImplementedError(_NOT_BUILT)
+        from .whisper_sampling import sample
+
+        return sample(self, *a, **kw)
+
+    def sample_candidates(self, *a, **kw):
+        """every sampled candidate of every window, before the ranker, see whisper_sampling.sample_candidates"""
+        if self._text is None:
+            raise NotImplementedError(_NOT_BUILT)
+        from .whisper_sampling import sample_candidates
+
+        return sample_candidates(self, *a, **kw)
+
+    def decode_with_fallback(self, *a, **kw):
+        """whisper.py:503-541 for a batch of windows, see whisper_sampling.decode_with_fallback"""
+        if self._text is None:
+            raise NotImplementedError(_NOT_BUILT)
+        from .whisper_sampling import decode_with_fallback
+
+        return decode_with_fallback(self, *a, **kw)
+
     def serve(self, max_rows: int = 8, eos_check_interval: int = 8, max_round_tokens: int = 256):
         """A running decoder batch that windows join and leave (whisper_serve.WhisperBatcher): `submit(window, options)` returns a Future of
         the DecodingResult `decode` would return for that window alone.  `decode`, `logits`, `detect_language` and `find_alignment` keep working on this

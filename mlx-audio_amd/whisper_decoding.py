@@ -7,7 +7,8 @@ looks at a device counter of unfinished rows every `eos_check_interval` steps.
 There is no tokenizer here (the vocabulary files are not part of this repository): tokens go in and come out as ids, `DecodingResult.text` stays "".
 `TextRuntime.forward_qk` is the forward that also hands out raw cross-attention scores; the token timestamps made from them live in whisper_timing.py.
 `RowRuntime` is the handle's row mode (kk_whisper_text_rows_*): rows with their own window, position, options and lifetime; the batcher on
-top of it lives in whisper_serve.py.
+top of it lives in whisper_serve.py.  Sampling at temperature > 0, `best_of` and the temperature fallback live in whisper_sampling.py, on
+`TextRuntime.set_audio_groups` / `sample_setup`; `decode` and `verify_options` here stay greedy and keep refusing a temperature.
 """
 from __future__ import annotations
 
@@ -281,6 +282,35 @@ class TextRuntime:
         _lib.check(self._lib.kk_whisper_text_set_audio(self._h, self._stream(), B, C.c_void_p(features.data_ptr()), C.c_void_p(self._state.data_ptr()),
                                                        self._state.numel(), ws, wsn), "kk_whisper_text_set_audio")
         self.B = B
+
+    def set_audio_groups(self, features, n_group: int):
+        """features: fp32 device (n_audio, n_audio_ctx, n_audio_state), contiguous.  B = n_audio * n_group rows, row b on the cross K/V of window
+        b // n_group, which is projected and kept once per window (DESIGN 8j)."""
+        import torch
+
+        from . import _lib
+
+        n_audio = features.shape[0]
+        B = n_audio * n_group
+        need = int(self._lib.kk_whisper_text_state_bytes_groups(self._h, n_audio, n_group))
+        if need == 0:
+            raise ValueError(f"n_group must be in 1 .. {_lib.WHISPER_MAX_GROUP}")
+        if self._state is None or self._state.numel() < need:
+            self._state = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws, wsn = self._workspace(B, 1)
+        _lib.check(self._lib.kk_whisper_text_set_audio_groups(self._h, self._stream(), n_audio, n_group, C.c_void_p(features.data_ptr()),
+                                                              C.c_void_p(self._state.data_ptr()), self._state.numel(), ws, wsn), "kk_whisper_text_set_audio_groups")
+        self.B = B
+
+    def sample_setup(self, temperature: float, seed: int, streams):
+        """after pick_setup: the picks draw at `temperature` on the Philox key `seed`, row b on stream id streams[b], until the next pick_setup"""
+        from . import _lib
+
+        ids = np.ascontiguousarray(np.asarray(streams, np.uint32))
+        if ids.shape != (self.B,):
+            raise ValueError(f"streams must hold one id per row ({self.B})")
+        _lib.check(self._lib.kk_whisper_text_sample_setup(self._h, self._stream(), float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, ids.ctypes.data_as(C.c_void_p)),
+                   "kk_whisper_text_sample_setup")
 
     def rewind(self, position: int = 0):
         from . import _lib

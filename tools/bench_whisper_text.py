@@ -14,8 +14,13 @@ capturing forward, `align_matrix`, and the DTW with its backtrace, each between 
 counts back, so their figures include that round trip).  The kernels' own durations come from a profiler run of its own:
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o k -- python tools/bench_whisper_text.py --align --only-steps 20 --batch 8
 
+`--best-of G` and / or `--temperature T` time sampling instead (mlx-audio_amd/whisper_sampling.py): for 1 and 8 windows of G rows each, the plain
+state of the same row count on repeated features (`set_audio`, the step with the greedy pick) against the grouped state on ONE cross K/V slice per window
+(`set_audio_groups`, the step with the sampled pick when T > 0), either pick alone, and the two states' sizes.
+
 Usage:  python tools/bench_whisper_text.py [--steps 20] [--warmup 3] [--inner 20] [--position 64] [--out profiles/whisper_text_bench.json]
-        python tools/bench_whisper_text.py --align [--steps 20] [--warmup 3] [--out profiles/whisper_align_bench.json]"""
+        python tools/bench_whisper_text.py --align [--steps 20] [--warmup 3] [--out profiles/whisper_align_bench.json]
+        python tools/bench_whisper_text.py --best-of 5 --temperature 1.0 [--steps 20] [--warmup 3] [--out profiles/whisper_sample_bench.json]"""
 import argparse
 import csv
 import json
@@ -32,7 +37,7 @@ sys.path.insert(0, ROOT)
 CTX, WIDTH, HEADS, LAYERS, VOCAB, TEXT_CTX = 1500, 1280, 20, 4, 51866, 448
 
 FAMILIES = (("linear_rows", "linear_rows_kernel"), ("attention", "attn_rows_kernel"), ("attention", "attn_merge_kernel"), ("layernorm", "layernorm_kernel"),
-            ("pick", "pick_kernel"), ("embed + row tables", "embed_kernel"), ("embed + row tables", "text_rows_kernel"))
+            ("pick", "pick_kernel"), ("pick", "pick_sampled_kernel"), ("embed + row tables", "embed_kernel"), ("embed + row tables", "text_rows_kernel"))
 
 
 def step_bytes(B, position):
@@ -55,7 +60,7 @@ def digest(path, steps):
         for row in csv.DictReader(f):
             rows.append((int(row["Start_Timestamp"]), int(row["End_Timestamp"]), row["Kernel_Name"]))
     rows.sort()
-    first = next(i for i, r in enumerate(rows) if "pick_kernel" in r[2])
+    first = next(i for i, r in enumerate(rows) if "pick_kernel" in r[2] or "pick_sampled_kernel" in r[2])
     rows = rows[first + 1:]
     fam, calls, total, other = {}, {}, 0.0, 0.0
     for t0, t1, name in rows:
@@ -104,6 +109,8 @@ def main():
     ap.add_argument("--only-steps", type=int, default=0, help="run this many decode steps and nothing else (the profiler's run)")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--align", action="store_true", help="time the token-timestamp path (capturing forward, align_matrix, dtw) instead of the decode step")
+    ap.add_argument("--temperature", type=float, default=0.0, help="> 0: the grouped state's picks are sampled at this temperature (DESIGN 8j)")
+    ap.add_argument("--best-of", type=int, default=0, help="G > 0: time G rows per window on one cross K/V slice against the plain state of as many rows")
     ap.add_argument("--digest", default=None)
     ap.add_argument("--digest-steps", type=int, default=200)
     a = ap.parse_args()
@@ -223,6 +230,48 @@ def main():
             state["warped"] = state["mat"][:, r0:r1].contiguous()
             r = timed(warp, 1)
             emit(dict(case="align_dtw_and_backtrace", B=B, rows=r1 - r0, frames=CTX, path_length=int(state["path"][2][0]), **r))
+        write_out()
+        return
+
+    if a.best_of or a.temperature:
+        G = a.best_of or 1
+        if a.temperature < 0 or not 1 <= G <= _lib.WHISPER_MAX_GROUP:
+            raise SystemExit(f"--temperature must be >= 0 and --best-of in 1 .. {_lib.WHISPER_MAX_GROUP}")
+        lib = rt._lib
+        for windows in ((a.batch,) if a.only_steps else (1, 8)):
+            B = windows * G
+            feats = torch.randn((windows, CTX, WIDTH), generator=torch.Generator().manual_seed(windows)).cuda()
+            prompt = torch.randint(0, 50000, (B, a.position), generator=torch.Generator().manual_seed(1), dtype=torch.int32).cuda()
+
+            def begin_state(grouped):
+                if grouped:
+                    rt.set_audio_groups(feats, G)
+                else:
+                    rt.set_audio(feats.repeat_interleave(G, dim=0).contiguous())
+                rt.pick_setup(params, bits)
+                if grouped and a.temperature > 0:
+                    rt.sample_setup(a.temperature, 0, np.arange(B))
+                rt.forward(prompt, False)
+                rt.pick()
+
+            if a.only_steps:  # the profiler's run: the grouped state's steps and nothing else
+                begin_state(True)
+                for _ in range(a.only_steps):
+                    step()
+                torch.cuda.synchronize()
+                return
+            emit(dict(case="state_bytes", windows=windows, G=G, rows=B, plain=int(lib.kk_whisper_text_state_bytes(rt._h, B)),
+                      grouped=int(lib.kk_whisper_text_state_bytes_groups(rt._h, windows, G))))
+            for grouped in (False, True):
+                kind = dict(windows=windows, G=G, rows=B, state="grouped" if grouped else "plain, repeated features",
+                            pick="sampled" if grouped and a.temperature > 0 else "greedy", temperature=a.temperature if grouped else 0.0)
+                rep = feats.repeat_interleave(G, dim=0).contiguous()
+                begin_state(grouped)
+                emit(dict(case="set_audio", **kind, **timed((lambda: rt.set_audio_groups(feats, G)) if grouped else (lambda: rt.set_audio(rep)), 1)))
+                del rep
+                begin_state(grouped)
+                emit(dict(case="decode_step", position=a.position, **kind, **timed(step, a.inner)))
+                emit(dict(case="pick_only", **kind, **timed(rt.pick, a.inner)))
         write_out()
         return
 
