@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 21  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 22  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -62,7 +62,9 @@ extern "C" {
                                kk_op_mimi_carry);
                             21: Whisper sampling: the sampled pick and window groups on one cross K/V slice (kk_op_whisper_pick_sampled,
                                kk_whisper_text_state_bytes_groups, kk_whisper_text_set_audio_groups,
-                               kk_whisper_text_sample_setup, KK_WHISPER_MAX_GROUP) */
+                               kk_whisper_text_sample_setup, KK_WHISPER_MAX_GROUP);
+                            22: the epilogue class of the fused conv kernels as a test switch and query (kk_debug_set_op_variant 41 / 51,
+                               kk_debug_last_conv_epi, kk_debug_set_op_accumulate) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -262,7 +264,9 @@ void kk_debug_clear(kk_context* cx);
  * with that pack (NULL = back to the LDS-staged kernel).  The model packs both layouts in kk_finalize. */
 int kk_op_pack_w_frag(void* stream, const void* w_bf16, void* w_frag, int Kw, int CoutP, int CinP);
 void kk_debug_set_op_wfrag(const void* w_frag);
-void kk_debug_set_op_variant(int v); /* 4 (default), 5 or 40: which fragment-order kernel those calls use (5 = wave-specialised persistent, kk_conv_mfma5.hip; 40 = variant 4 slab by slab also where its whole-K form (stride 1, 128 padded input channels) or its ring form (192 or more) applies -- the reference path of those forms' tests) */
+void kk_debug_set_op_accumulate(int on); /* kk_op_conv1d_bf16_fused with fragment-order weights adds its result to the output rows, as the last conv of a resblock adds to the mean over the three resblocks (0 = off, the default) */
+int kk_debug_last_conv_epi(void); /* epilogue class of the latest variant-4 / 5 conv launch of this process: -1 = the generic instantiation (every choice a runtime branch), else the compiled-in mask 1 residual | 2 scale != 1 | 4 final LeakyReLU | 8 statistics | 16 read-and-add (variant 4) */
+void kk_debug_set_op_variant(int v); /* 41 / 51: variant 4 / 5 with the generic epilogue instantiation also where a compiled-in class exists (the reference path of tests/test_gpu_conv_slim.py); 4 (default), 5 or 40: which fragment-order kernel those calls use (5 = wave-specialised persistent, kk_conv_mfma5.hip; 40 = variant 4 slab by slab also where its whole-K form (stride 1, 128 padded input channels) or its ring form (192 or more) applies -- the reference path of those forms' tests) */
 void kk_debug_set_op_post_slope(float slope); /* LeakyReLU(slope) of the final stored value in the kk_op_conv1d_bf16* calls that follow (variants 4 / 5; 0 or 1 = none, the default) */
 void kk_debug_force_generic(kk_context* cx, int flags); /* A/B tests in bf16 mode: bit0 no MFMA kernel, bit1 MFMA without norm fusion, bit2 LDS-staged MFMA kernel instead of variant 4, bit3 quantised model without the fp8 kernel, bit4 also materialise tensors fused kernels skip, bit5 stand-alone conv_post + iSTFT kernels, bit6 variant-5 (wave-specialised persistent) conv kernel wherever eligible, bit7 never (default: the layers with >= 9 taps), bit8 no side stream (the TextEncoder / harmonic-source branches of a forward on the caller's stream too), bit9 Linear layers never on the streaming kernel, bit10 always (default: by the rows in flight), bit11 conv variant 4 slab by slab also where its whole-K or ring form is routed (128 / 192 or more padded input channels; part of the graph-cache key like every bit) */
 

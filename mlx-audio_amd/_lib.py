@@ -288,7 +288,9 @@ SIGNATURES = {
     "kk_mimi_debug_info": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "kk_mimi_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
     "kk_debug_set_op_wfrag": (None, [_vp]),
-    "kk_debug_set_op_variant": (None, [_i]),  # 4 (default), 5, or 40 = variant 4 slab by slab where its whole-K form would run
+    "kk_debug_set_op_variant": (None, [_i]),  # 4 (default), 5, or 40 = variant 4 slab by slab where its whole-K form would run; 41 / 51 = generic epilogue
+    "kk_debug_last_conv_epi": (_i, []),
+    "kk_debug_set_op_accumulate": (None, [_i]),
     "kk_debug_set_op_post_slope": (None, [_f]),
     "kk_set_graph_mode": (_i, [_vp, _i]),
     "kk_set_quantization": (_i, [_vp, _i, _i]),

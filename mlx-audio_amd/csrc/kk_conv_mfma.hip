@@ -90,6 +90,7 @@ template <typename TO, int WM, int NRM>
 __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_mfma_kernel(KKMfmaArgs a) {
   constexpr int BM = 2 * WM, MI = WM / 32;
   constexpr bool ACC16 = false;  // 32 x 32 accumulator blocks (kk_conv_mfma_epilogue.h)
+  constexpr int EPI = KK_EPI_GENERIC;  // every epilogue choice at run time
   using G = Geo<BM>;
   constexpr int XREG = G::XREG;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];

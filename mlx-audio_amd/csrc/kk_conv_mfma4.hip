@@ -80,6 +80,7 @@ template <typename TO, int WM, int NRM>
 __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_mfma4_kernel(KKMfmaArgs a) {
   constexpr int BM = 2 * WM, MI16 = WM / 16;
   constexpr bool ACC16 = true;  // 16 x 16 accumulator blocks (kk_conv_mfma_epilogue.h)
+  constexpr int EPI = KK_EPI_GENERIC;  // the slab-by-slab kernel is the reference form: every epilogue choice at run time
   using G = Geo<BM>;
   constexpr int XREG = G::XREG;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -222,7 +223,7 @@ struct GeoWK {
   static constexpr int LDS_BYTES = MAIN_BYTES > EPI_BYTES ? MAIN_BYTES : EPI_BYTES;
 };
 
-template <int NRM, int XR>
+template <int NRM, int XR, int EPI>
 __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_mfma4_wholek_kernel(KKMfmaArgs a) {
   using TO = bf16_t;
   constexpr int WM = 96, BM = 2 * WM, MI16 = WM / 16, XREG = XR;
@@ -336,7 +337,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 // Iteration order, operands and epilogue are those of the slab-by-slab kernel: outputs and statistics partials are BIT-IDENTICAL
 // (tests/test_gpu_conv_ring.py).  Plain inputs with two or more taps and the polyphase transposed convs measured level or slower in this
 // form (-2 ... -5 % at 3 / 5 taps plain) and stay slab by slab.
-template <int NRM, int XR>
+template <int NRM, int XR, int EPI>
 __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_mfma4_ring_kernel(KKMfmaArgs a) {
   using TO = bf16_t;
   constexpr int WM = 96, BM = 2 * WM, MI16 = WM / 16, XREG = XR;
@@ -479,30 +480,30 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #include "kk_conv_mfma_epilogue.h"  // (shared with variant 2 and the other forms)
 }
 
-template <int NRM, int XR>
+template <int NRM, int XR, int EPI>
 int launch_ring(const KKMfmaArgs& a, int B, hipStream_t st) {
   using G = GeoWK<7>;
   static KKDevOnce attr_once;
   if (attr_once.first()) {
-    (void)hipFuncSetAttribute((const void*)conv_mfma4_ring_kernel<NRM, XR>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
+    (void)hipFuncSetAttribute((const void*)conv_mfma4_ring_kernel<NRM, XR, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
     attr_once.done();
   }
   dim3 grid(kk_cdiv(a.Q, 192), a.CoutP / BN, B);
-  hipLaunchKernelGGL((conv_mfma4_ring_kernel<NRM, XR>), grid, dim3(256), G::LDS_BYTES, st, a);
+  hipLaunchKernelGGL((conv_mfma4_ring_kernel<NRM, XR, EPI>), grid, dim3(256), G::LDS_BYTES, st, a);
   KK_CHECK_LAUNCH();
   return 0;
 }
 
-template <int NRM, int XR>
+template <int NRM, int XR, int EPI>
 int launch_wholek(const KKMfmaArgs& a, int B, hipStream_t st) {
   using G = GeoWK<XR>;
   static KKDevOnce attr_once;
   if (attr_once.first()) {
-    (void)hipFuncSetAttribute((const void*)conv_mfma4_wholek_kernel<NRM, XR>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
+    (void)hipFuncSetAttribute((const void*)conv_mfma4_wholek_kernel<NRM, XR, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
     attr_once.done();
   }
   dim3 grid(kk_cdiv(a.Q, 192), a.CoutP / BN, B);
-  hipLaunchKernelGGL((conv_mfma4_wholek_kernel<NRM, XR>), grid, dim3(256), G::LDS_BYTES, st, a);
+  hipLaunchKernelGGL((conv_mfma4_wholek_kernel<NRM, XR, EPI>), grid, dim3(256), G::LDS_BYTES, st, a);
   KK_CHECK_LAUNCH();
   return 0;
 }
@@ -563,16 +564,49 @@ int kk_launch_conv_mfma4(const KKMfmaArgs& a, int B, int out_dtype, hipStream_t 
   KKMfmaArgs g = a;
   if (nrm == 2 && a.nrm_act != KK_ACT_LRELU) g.nrm_slope = 1.0f;  // plain AdaIN: identity activation
   if (out_dtype != KK_BF16) return kk_fail("conv_mfma4: bf16 output only");
+  // The epilogue class (kk_conv_mfma_shared.h) is compiled in for the fused Snake layers of the Kokoro generator (run_resblock1 of
+  // kk_model.hip; 3 taps at both stages, 7 and 11 taps where variant 5 does not take them): first convolution of a pair (statistics),
+  // second one (residual + statistics), and the last second one of a resblock, which writes or adds to the mean over the three resblocks
+  // (residual + scale, read-and-add, the final LeakyReLU).  Everything else runs the generic instantiation.
+  const int epi = kk_epi_mask(g);
+  kk_conv_epi_last = KK_EPI_GENERIC;
+#define KK_EPI_CASE(LAUNCH, MASK) \
+  case (MASK):                    \
+    kk_conv_epi_last = (MASK);    \
+    return LAUNCH(MASK)(g, B, st);
   if (kk_mfma4_wholek_eligible(g) && !g.slabwise) {
     // chunk registers per thread and slab by the launch's halo: 7 x 32 = 224 rows cover a 192-row tile with a halo of up to 32
     const bool x7 = (g.Kw - 1) * g.dil <= 32;
-    if (nrm == 1) return x7 ? launch_wholek<1, 7>(g, B, st) : launch_wholek<1, 8>(g, B, st);
-    if (nrm == 2) return x7 ? launch_wholek<2, 7>(g, B, st) : launch_wholek<2, 8>(g, B, st);
-    return x7 ? launch_wholek<0, 7>(g, B, st) : launch_wholek<0, 8>(g, B, st);
+    if (nrm == 1 && x7) {
+      switch (epi) {
+#define KK_L(E) launch_wholek<1, 7, E>
+        KK_EPI_CASE(KK_L, KK_EPI_STAT)
+        KK_EPI_CASE(KK_L, KK_EPI_RES | KK_EPI_STAT)
+        KK_EPI_CASE(KK_L, KK_EPI_RES | KK_EPI_SCALE)
+        KK_EPI_CASE(KK_L, KK_EPI_RES | KK_EPI_SCALE | KK_EPI_ACC)
+        KK_EPI_CASE(KK_L, KK_EPI_RES | KK_EPI_SCALE | KK_EPI_ACC | KK_EPI_POST)
+#undef KK_L
+        default: break;
+      }
+    }
+    if (nrm == 1) return x7 ? launch_wholek<1, 7, KK_EPI_GENERIC>(g, B, st) : launch_wholek<1, 8, KK_EPI_GENERIC>(g, B, st);
+    if (nrm == 2) return x7 ? launch_wholek<2, 7, KK_EPI_GENERIC>(g, B, st) : launch_wholek<2, 8, KK_EPI_GENERIC>(g, B, st);
+    return x7 ? launch_wholek<0, 7, KK_EPI_GENERIC>(g, B, st) : launch_wholek<0, 8, KK_EPI_GENERIC>(g, B, st);
   }
   if (!g.slabwise && ring_eligible(g, nrm)) {
-    return nrm == 1 ? launch_ring<1, 7>(g, B, st) : launch_ring<0, 6>(g, B, st);
+    if (nrm == 1) {
+      switch (epi) {
+#define KK_L(E) launch_ring<1, 7, E>
+        KK_EPI_CASE(KK_L, KK_EPI_STAT)
+        KK_EPI_CASE(KK_L, KK_EPI_RES | KK_EPI_STAT)
+        KK_EPI_CASE(KK_L, KK_EPI_RES | KK_EPI_SCALE)
+#undef KK_L
+        default: break;
+      }
+    }
+    return nrm == 1 ? launch_ring<1, 7, KK_EPI_GENERIC>(g, B, st) : launch_ring<0, 6, KK_EPI_GENERIC>(g, B, st);
   }
+#undef KK_EPI_CASE
   if (nrm == 1) return launch_one<bf16_t, 96, 1>(g, B, st);
   if (nrm == 2) return launch_one<bf16_t, 96, 2>(g, B, st);
   return launch_one<bf16_t, 96, 0>(g, B, st);

@@ -93,7 +93,9 @@ struct Item {
 // NRM: 0 = raw input, 1 = AdaIN + Snake while staging, 2 = AdaIN + LeakyReLU(nrm_slope; 1 = identity) while staging
 // TPP: epilogue row tasks of the previous tile that ride in one slab period (12 / min(slabs per tile, 4): the last 12 / TPP periods of a tile)
 // ACC: the output rows are read and added to (Generator's sum over the three resblocks): its own kernel, the rows cost 4 * TPP registers
-template <int NRM, int TPP, bool ACC, int XREG>
+// EPI: the launch's epilogue class (KK_EPI_*, kk_conv_mfma_shared.h): KK_EPI_GENERIC = every choice a uniform runtime branch, else a mask that states
+// them at compile time (no output activation; the read-and-add bit is ACC's)
+template <int NRM, int TPP, bool ACC, int XREG, int EPI>
 __global__ __launch_bounds__(512, 2) void conv_mfma5_kernel(KKMfmaArgs a, int B) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   bf16_t* Xs = (bf16_t*)smem;
@@ -101,6 +103,10 @@ __global__ __launch_bounds__(512, 2) void conv_mfma5_kernel(KKMfmaArgs a, int B)
   float* red = (float*)(smem + XS_BYTES + CS_BYTES);  // [4 waves][2][128]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bool e_res = KK_EPI_ON(EPI, KK_EPI_RES, a.res != nullptr), e_scale = KK_EPI_ON(EPI, KK_EPI_SCALE, a.scale != 1.0f);
+  const bool e_post = KK_EPI_ON(EPI, KK_EPI_POST, a.post_slope != 0.f && a.post_slope != 1.0f);
+  const bool e_stat = KK_EPI_ON(EPI, KK_EPI_STAT, a.stat_part != nullptr);
+  const int e_act = EPI < 0 ? a.act : KK_ACT_NONE;
   const bool mfma_role = __builtin_amdgcn_readfirstlane(wave) < 4;
   const int ntaps = a.Kw, off0 = -a.pad, dstep = a.dil;
   const int halo = (ntaps - 1) * dstep, xrows = BM + halo;
@@ -244,7 +250,7 @@ __global__ __launch_bounds__(512, 2) void conv_mfma5_kernel(KKMfmaArgs a, int B)
     }
 #undef KK_ITER5
     TR5_ADD(0, TR5_NOW() - trm0);
-    if (a.stat_part) KK_BAR5();  // (the service waves' last statistics reduction has one more barrier: keep the counts equal)
+    if (e_stat) KK_BAR5();  // (the service waves' last statistics reduction has one more barrier: keep the counts equal)
     return;
   }
 
@@ -376,7 +382,7 @@ __global__ __launch_bounds__(512, 2) void conv_mfma5_kernel(KKMfmaArgs a, int B)
   uint4 rres[TPP], rold[ACC ? TPP : 1];
   auto epi_prefetch = [&](const Item& t, int tbase) __attribute__((always_inline)) {
     const bf16_t* ob = (const bf16_t*)a.out + (long long)t.b * a.obs;
-    const bf16_t* rb = a.res ? (const bf16_t*)a.res + (long long)t.b * a.rbs : nullptr;
+    const bf16_t* rb = e_res ? (const bf16_t*)a.res + (long long)t.b * a.rbs : nullptr;
     const int n = t.n0 + (stid & 15) * 8;
     const int nc = n < a.Cout ? n : 0;
     const int lo_hi = a.Lo_rows - 1;
@@ -386,7 +392,7 @@ __global__ __launch_bounds__(512, 2) void conv_mfma5_kernel(KKMfmaArgs a, int B)
       const int opc = q < 0 ? 0 : (q > lo_hi ? lo_hi : q);
       // (a wave-uniform condition; the explicit zero keeps the old value dead on the other path -- otherwise hipcc loads into temporaries
       //  and copies them behind a vmcnt(0) at the merge)
-      if (rb) rres[i] = *(const uint4*)(rb + (long long)opc * a.ldr + nc);
+      if (e_res) rres[i] = *(const uint4*)(rb + (long long)opc * a.ldr + nc);
       else rres[i] = make_uint4(0u, 0u, 0u, 0u);
       if (ACC) rold[i] = *(const uint4*)(ob + (long long)opc * a.ldo + nc);
     }
@@ -424,32 +430,32 @@ __global__ __launch_bounds__(512, 2) void conv_mfma5_kernel(KKMfmaArgs a, int B)
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[k] += bias2[k];
-      if (a.act == KK_ACT_LRELU) {
+      if (e_act == KK_ACT_LRELU) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const v2f m = v[k] * act_slope2;
           v[k].x = v[k].x > 0.f ? v[k].x : m.x;
           v[k].y = v[k].y > 0.f ? v[k].y : m.y;
         }
-      } else if (a.act == KK_ACT_GELU) {
+      } else if (e_act == KK_ACT_GELU) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           v[k].x = gelu_exact(v[k].x);
           v[k].y = gelu_exact(v[k].y);
         }
-      } else if (NRM == 0 && a.act == KK_ACT_GELU_TANH) {
+      } else if (NRM == 0 && e_act == KK_ACT_GELU_TANH) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           v[k].x = 0.5f * v[k].x * (1.0f + tanhf(0.7978845608028654f * (v[k].x + 0.044715f * (v[k].x * v[k].x * v[k].x))));
           v[k].y = 0.5f * v[k].y * (1.0f + tanhf(0.7978845608028654f * (v[k].y + 0.044715f * (v[k].y * v[k].y * v[k].y))));
         }
       }
-      if (a.res) {
+      if (e_res) {
         const unsigned w4[4] = {rres[i].x, rres[i].y, rres[i].z, rres[i].w};
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] += v2f{__uint_as_float(w4[k] << 16), __uint_as_float(w4[k] & 0xFFFF0000u)};
       }
-      if (a.scale != 1.0f) {  // (uniform; 1 everywhere but the mean over the three resblocks)
+      if (e_scale) {  // (uniform; 1 everywhere but the mean over the three resblocks)
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] *= scale2;
       }
@@ -458,7 +464,7 @@ __global__ __launch_bounds__(512, 2) void conv_mfma5_kernel(KKMfmaArgs a, int B)
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] += v2f{__uint_as_float(w4[k] << 16), __uint_as_float(w4[k] & 0xFFFF0000u)};
       }
-      if (a.post_slope != 0.f && a.post_slope != 1.0f) {  // (uniform) LeakyReLU of the finished value
+      if (e_post) {  // (uniform) LeakyReLU of the finished value
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const float mx = v[k].x * a.post_slope, my = v[k].y * a.post_slope;
@@ -482,7 +488,7 @@ __global__ __launch_bounds__(512, 2) void conv_mfma5_kernel(KKMfmaArgs a, int B)
       // in-order counter as loads, and a store hipcc cannot count makes the next wait for a load drain the row requests behind it.
       uint4* dst = wr_ok ? (uint4*)(ob + (long long)opc * a.ldo + n) : dump;
       *dst = make_uint4(w4[0], w4[1], w4[2], w4[3]);
-      if (a.stat_part) {  // column statistics from the fp32 values before the bf16 rounding (see kk_conv_mfma_epilogue.h)
+      if (e_stat) {  // column statistics from the fp32 values before the bf16 rounding (see kk_conv_mfma_epilogue.h)
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           st_s[k] += v[k];
@@ -570,7 +576,7 @@ __global__ __launch_bounds__(512, 2) void conv_mfma5_kernel(KKMfmaArgs a, int B)
     const unsigned long long t1 = TR5_NOW();
     if (have_prev && c >= act0) {  // (its residual rows were requested a slab period ago)
       epi_compute(prev, (c - act0) * TPP);
-      if (tail && a.stat_part) stats_to_lds();
+      if (tail && e_stat) stats_to_lds();
     }
     const unsigned long long t2 = TR5_NOW();
     if (stage1) transform_x(c1, XT, xkT, slab_inside(s1, c1));
@@ -583,7 +589,7 @@ __global__ __launch_bounds__(512, 2) void conv_mfma5_kernel(KKMfmaArgs a, int B)
     KK_BAR5();  // [A] the MFMA waves are done with the slab in LDS; the previous tile's C is consumed when this is a tile's last slab
     const unsigned long long t4 = TR5_NOW();
     if (stage1) store_x(XT);
-    if (have_prev && tail && a.stat_part) stats_to_global(prev);
+    if (have_prev && tail && e_stat) stats_to_global(prev);
     KK_BAR5();  // [B]
     TR5_ADD(4, t4 - t3);
     TR5_ADD(5, TR5_NOW() - t4);
@@ -607,27 +613,29 @@ __global__ __launch_bounds__(512, 2) void conv_mfma5_kernel(KKMfmaArgs a, int B)
   }
   TR5_ADD(3, TR5_NOW() - trs0);
   // ---- drain: the last tile's epilogue (group 0 was requested at the end of the loop)
+  // ONE copy of the epilogue body, looped: it runs once per workgroup, so its schedule does not matter, and NACT unrolled copies were as
+  // much code again as the service loop.  (The request behind the last group re-reads that group's rows: no load under a condition.)
   stats_reset();
-#pragma unroll
+#pragma unroll 1
   for (int g = 0; g < NACT; ++g) {
     epi_compute(prev, g * TPP);
-    if (g + 1 < NACT) epi_prefetch(prev, (g + 1) * TPP);
+    epi_prefetch(prev, (g + 1 < NACT ? g + 1 : g) * TPP);
   }
-  if (a.stat_part) {
+  if (e_stat) {
     stats_to_lds();
     KK_BAR5();
     stats_to_global(prev);
   }
 }
 
-template <int NRM, int TPP, bool ACC, int XREG>
+template <int NRM, int TPP, bool ACC, int XREG, int EPI>
 int launch5x(const KKMfmaArgs& a, int B, hipStream_t st) {
   static KKDevOnce attr_once;
   static int ncu_dev[64];  // CUs of each device this process has launched on (the persistent grid = CUs)
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (attr_once.first()) {
-    (void)hipFuncSetAttribute((const void*)conv_mfma5_kernel<NRM, TPP, ACC, XREG>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS5_BYTES);
+    (void)hipFuncSetAttribute((const void*)conv_mfma5_kernel<NRM, TPP, ACC, XREG, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS5_BYTES);
     int n = 0;
     if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
     ncu_dev[dev & 63] = n;
@@ -636,13 +644,43 @@ int launch5x(const KKMfmaArgs& a, int B, hipStream_t st) {
   const int ncu = ncu_dev[dev & 63];
   const int total = B * kk_cdiv(a.Q, BM) * (a.CoutP / BN);
   const int grid = total < ncu ? total : ncu;
-  hipLaunchKernelGGL((conv_mfma5_kernel<NRM, TPP, ACC, XREG>), dim3(grid), dim3(512), LDS5_BYTES, st, a, B);
+  hipLaunchKernelGGL((conv_mfma5_kernel<NRM, TPP, ACC, XREG, EPI>), dim3(grid), dim3(512), LDS5_BYTES, st, a, B);
   KK_CHECK_LAUNCH();
   return 0;
 }
+// The epilogue classes compiled in (kk_conv_mfma_shared.h): what the fused Snake layers of the Kokoro generator launch on this kernel
+// (run_resblock1 of kk_model.hip; 7 and 11 taps) -- the first convolution of a pair (statistics; the only one with a dilation, so the only
+// one that can need 8 chunks), the second one (residual + statistics; the last of a noise resblock has no statistics), and the read-and-add
+// into the mean over the three resblocks (residual + scale).  Every other launch runs the generic instantiation.
+constexpr bool epi5_compiled(int NRM, bool ACC, int XREG, int EPI) {
+  if (NRM != 1) return false;
+  if (ACC) return XREG == 7 && EPI == (KK_EPI_RES | KK_EPI_SCALE);
+  return EPI == KK_EPI_STAT || (XREG == 7 && (EPI == (KK_EPI_RES | KK_EPI_STAT) || EPI == KK_EPI_RES));
+}
+template <int NRM, int TPP, bool ACC, int XREG, int EPI>
+int launch5e(const KKMfmaArgs& a, int B, hipStream_t st) {
+  if constexpr (epi5_compiled(NRM, ACC, XREG, EPI)) {
+    kk_conv_epi_last = EPI;
+    return launch5x<NRM, TPP, ACC, XREG, EPI>(a, B, st);
+  } else {
+    return launch5x<NRM, TPP, ACC, XREG, KK_EPI_GENERIC>(a, B, st);
+  }
+}
+template <int NRM, int TPP, bool ACC, int XREG>
+int launch5m(const KKMfmaArgs& a, int B, hipStream_t st) {
+  const int m = kk_epi_mask(a);
+  kk_conv_epi_last = KK_EPI_GENERIC;
+  switch (m < 0 ? m : m & ~KK_EPI_ACC) {  // (read-and-add is the template parameter ACC here)
+    case KK_EPI_STAT: return launch5e<NRM, TPP, ACC, XREG, KK_EPI_STAT>(a, B, st);
+    case KK_EPI_RES | KK_EPI_STAT: return launch5e<NRM, TPP, ACC, XREG, KK_EPI_RES | KK_EPI_STAT>(a, B, st);
+    case KK_EPI_RES: return launch5e<NRM, TPP, ACC, XREG, KK_EPI_RES>(a, B, st);
+    case KK_EPI_RES | KK_EPI_SCALE: return launch5e<NRM, TPP, ACC, XREG, KK_EPI_RES | KK_EPI_SCALE>(a, B, st);
+    default: return launch5x<NRM, TPP, ACC, XREG, KK_EPI_GENERIC>(a, B, st);
+  }
+}
 template <int NRM, int TPP, bool ACC>
 int launch5(const KKMfmaArgs& a, int B, hipStream_t st) {
-  return (a.Kw - 1) * a.dil <= 32 ? launch5x<NRM, TPP, ACC, 7>(a, B, st) : launch5x<NRM, TPP, ACC, 8>(a, B, st);
+  return (a.Kw - 1) * a.dil <= 32 ? launch5m<NRM, TPP, ACC, 7>(a, B, st) : launch5m<NRM, TPP, ACC, 8>(a, B, st);
 }
 template <int NRM>
 int launch5n(const KKMfmaArgs& a, int B, hipStream_t st) {

@@ -2,17 +2,26 @@
 // kk_conv_mfma4.hip (variant 4): accumulators -> fp32 LDS tile (one wave row group per pass) -> coalesced 16-byte rows with bias /
 // activation / residual / scale / accumulate / length mask, per-tile column statistics of the stored values.  ONE copy for both kernels.
 // Names taken from the including scope: a, b, bx (row-tile index), phase, nphase, q0, n0, tid, lane, wave, wr, wc, acc, Cs, red (via smem),
-// tile_live, Lout, TO, WM, BM, G, NRM, ACC16 (accumulator layout: true = (WM / 16) x 4 blocks of 16 x 16 as in variant 4, false =
+// tile_live, Lout, TO, WM, BM, G, NRM, EPI (the launch's epilogue class, KK_EPI_* of kk_conv_mfma_shared.h: in a mask class the conditions below are
+// compile-time constants and the paths not taken are not compiled), ACC16 (accumulator layout: true = (WM / 16) x 4 blocks of 16 x 16 as in variant 4, false =
 // (WM / 32) x 2 blocks of 32 x 32 as in variant 2), v2f / fma2 / gelu_exact (kk_conv_mfma_shared.h).
   // ---- epilogue: per 128 rows, accumulators -> fp32 LDS tile -> coalesced rows --------------------------------------
+  // the launch's epilogue class: arguments in the generic class, constants in a mask class (uniform either way)
   TO* ob = (TO*)a.out + (long long)b * a.obs;
-  const TO* rb = a.res ? (const TO*)a.res + (long long)b * a.rbs : nullptr;
+  const TO* rb = KK_EPI_ON(EPI, KK_EPI_RES, a.res != nullptr) ? (const TO*)a.res + (long long)b * a.rbs : nullptr;
+// (macros, not hoisted booleans: the generic class must compile to the code it had when these were the conditions themselves)
+#define e_res KK_EPI_ON(EPI, KK_EPI_RES, rb != nullptr)
+#define e_scale KK_EPI_ON(EPI, KK_EPI_SCALE, a.scale != 1.0f)
+#define e_post KK_EPI_ON(EPI, KK_EPI_POST, a.post_slope != 0.f && a.post_slope != 1.0f)
+#define e_stat KK_EPI_ON(EPI, KK_EPI_STAT, a.stat_part != nullptr)
+#define e_acc KK_EPI_ON(EPI, KK_EPI_ACC, a.accumulate != 0)
+#define e_act (EPI < 0 ? a.act : (int)KK_ACT_NONE)
   const int n = n0 + (tid & 15) * 8;  // this thread's 8 output channels (same for all its rows)
   const int nc = n < a.Cout ? n : 0;  // clamped for the unconditional loads
   const int lo_hi = a.Lo_rows - 1;
   constexpr int VEC = sizeof(TO) == 2 ? 1 : 2;  // 16-byte vectors per 8 outputs
   // every row of the tile lies inside the utterance (uniform; true for all but the last tile of an utterance)
-  const bool tile_full = tile_live && !a.flat_T && (a.mode == KK_CONV ? q0 + BM - 1 : phase + a.stride * (q0 + BM - 1)) < Lout;
+  const bool tile_full = tile_live && (EPI >= 0 || !a.flat_T) && (a.mode == KK_CONV ? q0 + BM - 1 : phase + a.stride * (q0 + BM - 1)) < Lout;
   v2f bias2[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k)  // bias has CoutP entries
@@ -27,7 +36,7 @@
   // round trip per tile instead of one per (pass, half)
   constexpr bool PRE = sizeof(TO) == 2;
   uint4 rpre[PRE ? NPASS * 2 * TG : 1];
-  if (PRE && rb) {
+  if (PRE && e_res) {
 #pragma unroll
     for (int j = 0; j < NPASS * 2 * TG; ++j) {
       const int q = q0 + (j / (2 * TG)) * RPP + (((j % (2 * TG)) * 256 + tid) >> 4);
@@ -83,12 +92,12 @@
         opv[i] = op < 0 ? 0 : (op > lo_hi ? lo_hi : op);
         wr_ok[i] = q < a.Q && op < a.Lo_rows && n < a.Cout;
         live[i] = tile_live && op < Lout;
-        if (a.flat_T) {  // (uniform) flat rows: the item this row belongs to decides
+        if (EPI < 0 && a.flat_T) {  // (uniform) flat rows: the item this row belongs to decides
           const int bb = opv[i] / a.flat_T;
           live[i] = live[i] && (opv[i] - bb * a.flat_T) < kk_len(a.flat_len, bb);
         }
       }
-      if (rb) {  // wave-uniform
+      if (e_res) {  // wave-uniform
 #pragma unroll
         for (int i = 0; i < TG; ++i) {
           if (PRE) rres[i][0] = rpre[(pass * 2 + half) * TG + i];
@@ -97,7 +106,7 @@
             for (int v = 0; v < VEC; ++v) rres[i][v] = *((const uint4*)(rb + (long long)opv[i] * a.ldr + nc) + v);
         }
       }
-      if (a.accumulate) {
+      if (e_acc) {
 #pragma unroll
         for (int i = 0; i < TG; ++i)
 #pragma unroll
@@ -120,27 +129,27 @@
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] += bias2[k];
-        if (a.act == KK_ACT_LRELU) {
+        if (e_act == KK_ACT_LRELU) {
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             const v2f m = v[k] * act_slope2;
             v[k].x = v[k].x > 0.f ? v[k].x : m.x;
             v[k].y = v[k].y > 0.f ? v[k].y : m.y;
           }
-        } else if (a.act == KK_ACT_GELU) {
+        } else if (e_act == KK_ACT_GELU) {
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             v[k].x = gelu_exact(v[k].x);
             v[k].y = gelu_exact(v[k].y);
           }
-        } else if (NRM == 0 && a.act == KK_ACT_GELU_TANH) {  // nn.gelu_approx (plain variant only: keeps the fused variants' registers)
+        } else if (NRM == 0 && e_act == KK_ACT_GELU_TANH) {  // nn.gelu_approx (plain variant only: keeps the fused variants' registers)
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             v[k].x = 0.5f * v[k].x * (1.0f + tanhf(0.7978845608028654f * (v[k].x + 0.044715f * (v[k].x * v[k].x * v[k].x))));
             v[k].y = 0.5f * v[k].y * (1.0f + tanhf(0.7978845608028654f * (v[k].y + 0.044715f * (v[k].y * v[k].y * v[k].y))));
           }
         }
-        if (rb) {
+        if (e_res) {
           if (sizeof(TO) == 2) {
             const unsigned w4[4] = {rres[i][0].x, rres[i][0].y, rres[i][0].z, rres[i][0].w};
 #pragma unroll
@@ -153,11 +162,11 @@
             for (int k = 0; k < 4; ++k) v[k] += v2f{t.f[2 * k], t.f[2 * k + 1]};
           }
         }
-        if (a.scale != 1.0f) {  // (uniform; 1 everywhere but the mean over the three resblocks)
+        if (e_scale) {  // (uniform; 1 everywhere but the mean over the three resblocks)
 #pragma unroll
           for (int k = 0; k < 4; ++k) v[k] *= scale2;
         }
-        if (a.accumulate) {
+        if (e_acc) {
           if (sizeof(TO) == 2) {
             const unsigned w4[4] = {rold[i][0].x, rold[i][0].y, rold[i][0].z, rold[i][0].w};
 #pragma unroll
@@ -170,7 +179,7 @@
             for (int k = 0; k < 4; ++k) v[k] += v2f{t.f[2 * k], t.f[2 * k + 1]};
           }
         }
-        if (a.post_slope != 0.f && a.post_slope != 1.0f) {  // (uniform) LeakyReLU of the finished value: max(v, slope v) for 0 < slope < 1
+        if (e_post) {  // (uniform) LeakyReLU of the finished value: max(v, slope v) for 0 < slope < 1
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             const float mx = v[k].x * a.post_slope, my = v[k].y * a.post_slope;
@@ -192,7 +201,7 @@
           }
           if (wr_ok[i]) {
             *(uint4*)(ob + (long long)opv[i] * a.ldo + n) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
-            if (a.stat_part) {
+            if (e_stat) {
               // column statistics for the next instance norm, from the fp32 values BEFORE the bf16 rounding (round 3: the consumer reads the
               // rounded tensor, whose sums differ from these by the rounding noise averaged over the rows, ~1e-5 relative; the fp32 oracle
               // normalises unrounded values too; re-widening the packed words cost 2 of the 8 VALU instructions per element pair here)
@@ -220,7 +229,7 @@
   }
   TR_ADD(4, TR_NOW() - tr0);  // start .. end of the store phase
   TR_ADD(5, 1);
-  if (a.stat_part) {
+  if (e_stat) {
     // rows of one column group live in threads tid = rg*16 + cg: reduce rg over the wave by shuffles (xor 16, 32),
     // then over the 4 waves through LDS; one deterministic partial per (utterance, tile, column)
     __syncthreads();  // every wave is done reading the Cs tile
@@ -254,3 +263,9 @@
       a.stat_part[(((long long)b * a.stat_ntiles + tile) * 2 + which) * a.Cout + n0 + col] = v;
     }
   }
+#undef e_res
+#undef e_scale
+#undef e_post
+#undef e_stat
+#undef e_acc
+#undef e_act

@@ -16,6 +16,22 @@ __device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return v2f{__builtin_
 // nn.gelu (exact erf form, modules.py / transformer feed-forward)
 __device__ __forceinline__ float gelu_exact(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 
+// Epilogue class of a launch (template parameter EPI of the fused kernels of variants 4 / 5).  KK_EPI_GENERIC keeps every choice a uniform
+// runtime branch on the arguments (any activation, GELU and GELU-tanh included).  Every other value is a mask of the bits below and states
+// the launch at compile time: no output activation, and residual / scale != 1 / final LeakyReLU / statistics / read-and-add exactly as the
+// bits say, so that the code of the paths not taken -- the erff and tanhf expansions above all -- is not in the kernel.  The arithmetic of
+// a path is the same text in both forms.  The launchers compute the mask from the arguments (kk_epi_mask) and instantiate the masks that
+// the Kokoro generator launches on each kernel; everything else runs the generic instantiation.
+constexpr int KK_EPI_GENERIC = -1;
+constexpr int KK_EPI_RES = 1, KK_EPI_SCALE = 2, KK_EPI_POST = 4, KK_EPI_STAT = 8, KK_EPI_ACC = 16;
+#define KK_EPI_ON(EPI, BIT, RUNTIME) ((EPI) < 0 ? (RUNTIME) : (((EPI) & (BIT)) != 0))
+// the mask of a launch, or KK_EPI_GENERIC where a mask cannot state it (an output activation, flat rows) or the debug switch asks for it
+inline int kk_epi_mask(const KKMfmaArgs& a) {
+  if (kk_conv_epi_generic || a.act != KK_ACT_NONE || a.flat_T) return KK_EPI_GENERIC;
+  return (a.res ? KK_EPI_RES : 0) | (a.scale != 1.0f ? KK_EPI_SCALE : 0) | (a.post_slope != 0.f && a.post_slope != 1.0f ? KK_EPI_POST : 0) |
+         (a.stat_part ? KK_EPI_STAT : 0) | (a.accumulate ? KK_EPI_ACC : 0);
+}
+
 typedef float kk_f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 kk_bf16x8 __attribute__((ext_vector_type(8)));
 

@@ -84,6 +84,10 @@ bool kk_mfma4_wholek_eligible(const KKMfmaArgs& a);
 // variant 5 (kk_conv_mfma5.hip): wave-specialised persistent kernel (4 MFMA waves + 4 service waves per CU) for stride-1 convolutions
 bool kk_mfma5_eligible(const KKMfmaArgs& a, int out_dtype);
 int kk_launch_conv_mfma5(const KKMfmaArgs& a, int B, int out_dtype, hipStream_t st);
+// Epilogue class of the fused kernels of variants 4 / 5 (KK_EPI_*, kk_conv_mfma_shared.h): a function of the launch arguments alone.
+// kk_conv_epi_generic: debug switch of the single-op entry points (kk_debug_set_op_variant 41 / 51), 1 = the generic instantiation everywhere.
+// kk_conv_epi_last: the class of the latest variant-4 / 5 launch of this process (kk_debug_last_conv_epi; the tests ask it).
+extern int kk_conv_epi_generic, kk_conv_epi_last;
 // element index of W[tap][cout][k] in the fragment-order weight pack of variants 4 / 5: [tap][n block (128 columns)][chunk (64 k)]
 // [wc (2 x 64 columns)][ks (2 x 32 k)][ni (4 x 16 columns)][lane = k-group * 16 + column][8]: one 1 KiB v_mfma_f32_16x16x32_bf16 B fragment
 // per (wc, ks, ni).  The host packers call the function; the device re-layout (kk_launch_pack_w_frag) expands the macro in place, because

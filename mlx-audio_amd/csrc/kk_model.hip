@@ -23,6 +23,9 @@ static thread_local std::string g_err;
 static const void* g_op_wfrag = nullptr;  // kk_debug_set_op_wfrag: fragment-order weights for the single-kernel conv entry points
 static float g_op_post_slope = 0.f;       // kk_debug_set_op_post_slope: LeakyReLU of the final stored value in those calls (0 = none)
 static int g_op_variant = 4;              // kk_debug_set_op_variant: which fragment-order kernel they use (4, 5, or 40 = variant 4 slab by slab)
+static int g_op_accumulate = 0;           // kk_debug_set_op_accumulate: kk_op_conv1d_bf16_fused adds to the output rows (the model's sum over the resblocks)
+int kk_conv_epi_generic = 0;              // kk_debug_set_op_variant 41 / 51: the generic epilogue instantiation of variants 4 / 5 everywhere (kk_kernels.h)
+int kk_conv_epi_last = -1;                // kk_debug_last_conv_epi
 
 int kk_fail(const char* msg) {
   g_err = msg ? msg : "unknown error";
@@ -1759,6 +1762,7 @@ extern "C" int kk_op_conv1d_bf16_fused(void* stream, int B, const void* x, int l
   if (g_op_wfrag) {
     g.wf = (const bf16_t*)g_op_wfrag;
     g.post_slope = g_op_post_slope;
+    g.accumulate = g_op_accumulate;
     if (g_op_variant == 5 && kk_mfma5_eligible(g, KK_BF16)) return kk_launch_conv_mfma5(g, B, KK_BF16, (hipStream_t)stream);
     g.slabwise = g_op_variant == 40;
     return kk_launch_conv_mfma4(g, B, KK_BF16, (hipStream_t)stream);
@@ -1979,7 +1983,13 @@ extern "C" int kk_op_linear_mxfp8(void* stream, const void* x_bf16, int ldx, int
 }
 extern "C" void kk_debug_set_op_wfrag(const void* w_frag) { g_op_wfrag = w_frag; }
 extern "C" void kk_debug_set_op_post_slope(float slope) { g_op_post_slope = slope; }
-extern "C" void kk_debug_set_op_variant(int v) { g_op_variant = (v == 5 || v == 40) ? v : 4; }
+// 41 / 51 = variants 4 / 5 with the generic epilogue instantiation (a process-wide test switch: it also holds for a model forward run meanwhile)
+extern "C" void kk_debug_set_op_variant(int v) {
+  kk_conv_epi_generic = (v == 41 || v == 51) ? 1 : 0;
+  g_op_variant = (v == 5 || v == 51) ? 5 : v == 40 ? 40 : 4;
+}
+extern "C" int kk_debug_last_conv_epi(void) { return kk_conv_epi_last; }
+extern "C" void kk_debug_set_op_accumulate(int on) { g_op_accumulate = on ? 1 : 0; }
 extern "C" int kk_op_pack_w_frag(void* stream, const void* w_bf16, void* w_frag, int Kw, int CoutP, int CinP) {
   return kk_launch_pack_w_frag(w_bf16, w_frag, Kw, CoutP, CinP, (hipStream_t)stream);
 }
