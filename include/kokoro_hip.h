@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 22  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 23  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -64,7 +64,10 @@ extern "C" {
                                kk_whisper_text_state_bytes_groups, kk_whisper_text_set_audio_groups,
                                kk_whisper_text_sample_setup, KK_WHISPER_MAX_GROUP);
                             22: the epilogue class of the fused conv kernels as a test switch and query (kk_debug_set_op_variant 41 / 51,
-                               kk_debug_last_conv_epi, kk_debug_set_op_accumulate) */
+                               kk_debug_last_conv_epi, kk_debug_set_op_accumulate);
+                            23: Whisper beam search on the device (kk_op_whisper_beam_topk, kk_op_whisper_beam_select, kk_op_whisper_beam_reset,
+                               kk_op_whisper_attn_rows_owned, kk_whisper_beam_bufs, kk_whisper_text_beam_state_bytes, kk_whisper_text_beam_setup,
+                               kk_whisper_text_beam_not_complete, kk_whisper_text_beam_read) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -869,6 +872,12 @@ int kk_whisper_encode(kk_whisper* m, void* stream, int B, const float* mel, void
 size_t kk_op_whisper_attn_rows_scratch_bytes(int R, int heads, int T_rows);
 int kk_op_whisper_attn_rows(void* stream, int R, int heads, const float* q, const void* kv, int k_off, int v_off, int items, int T_rows, int ld,
                             const int32_t* item, const int32_t* len, float* out, void* scratch, size_t scratch_bytes);
+/* The same attention with the keys of a row scattered over the items (a beam's ancestry): owner is a device int32 table [R][T_rows], and key
+ * j of row r is read at owner[r][j] * T_rows * ld + j * ld instead of item[r] * T_rows * ld + j * ld.  The arithmetic is that of
+ * kk_op_whisper_attn_rows: the output is bit-equal to it on a store that holds the same keys gathered into one item.  Scratch, alignment and
+ * refusals as kk_op_whisper_attn_rows; owner[r][j] outside [0, items) for a j < len[r] is refused (the table is read back). */
+int kk_op_whisper_attn_rows_owned(void* stream, int R, int heads, const float* q, const void* kv, int k_off, int v_off, int items, int T_rows, int ld,
+                                  const int32_t* owner, const int32_t* len, float* out, void* scratch, size_t scratch_bytes);
 /* out[m] = act(x[m] W^T + bias) (+ res[m]) for 1 <= M <= 16 rows on the bf16 matrix cores: x fp32 [M][ldx] (rounded to bf16, nearest even), W bf16
  * [N][K] dense (K % 32 == 0, any N), bias fp32 [N] or null, act 0 (none) or 2 (exact GELU), res fp32 [M][ldr] or null.  The result goes to out
  * (fp32 [M][ldo], or null) and / or, rounded to bf16, to row rows_bf16[m] (device int32 [M]; null: row m) of out_bf16 [nrows_bf16][ld_bf16]; a row
@@ -956,6 +965,54 @@ int kk_whisper_text_set_audio_groups(kk_whisper_text* m, void* stream, int n_aud
 /* after pick_setup: pick launches kk_op_whisper_pick_sampled with this temperature, seed and the rows' stream ids (HOST uint32 [B], copied;
  * synchronises) until the next pick_setup, which returns the handle to the greedy pick.  Refuses a temperature that is not finite or not > 0. */
 int kk_whisper_text_sample_setup(kk_whisper_text* m, void* stream, float temperature, uint64_t seed, const uint32_t* streams);
+
+/* ---- beam search (OpenAI's BeamSearchDecoder on the device) -------------------------------------------------------------------
+ * n_audio windows of K = beam_size rows, B = n_audio * K, row b in window b / K.  A step is a forward, kk_op_whisper_beam_topk and
+ * kk_op_whisper_beam_select; nothing returns to the host in between.  The self K/V is never moved: owner[b][p] names the physical row that
+ * holds position p of beam b, and the step's self-attention reads its keys through it (kk_op_whisper_attn_rows_owned).
+ * The device buffers of a beam: */
+typedef struct kk_whisper_beam_bufs {
+  int32_t n_audio, beam_size;    /* 1 <= beam_size <= KK_WHISPER_MAX_GROUP */
+  int32_t max_candidates;        /* finished sequences a window keeps, round(beam_size * patience): 1 .. 2 KK_WHISPER_MAX_GROUP */
+  int32_t n_ctx, cap, reserved;  /* positions of an owner row; ids of a token row (tokens [B][cap], fin_tokens rows) */
+  int32_t* cand_token;           /* [B][beam_size + 1]: a row's offers in descending log-probability, -1 = none */
+  float* cand_logprob;           /* [B][beam_size + 1] */
+  int32_t* owner[2];             /* [B][n_ctx] each; select reads owner[flip] and writes owner[flip ^ 1] */
+  int32_t* parent;               /* [B]: the row the slot's new prefix extends, -1 for a dead slot */
+  float* fin_score;              /* [n_audio][max_candidates]: sum_logprob of a finished sequence */
+  int32_t* fin_length;           /* [n_audio][max_candidates]: its tokens before eot */
+  int32_t* fin_tokens;           /* [n_audio][max_candidates][cap]: the ids, materialised when it finished */
+  int32_t* fin_count;            /* [n_audio] */
+  int32_t* complete;             /* [n_audio]: fin_count reached max_candidates */
+  int32_t* not_complete;         /* [1]: windows not complete; decremented once per window */
+} kk_whisper_beam_bufs;
+/* Row b's beam_size + 1 most probable tokens over the logits filtered exactly as kk_op_whisper_pick filters them on state[b]: (token,
+ * l[token] - logsumexp(l)) in descending order, equal logits by the lower id, never a masked token; unused slots hold token -1.  The log-sum-exp
+ * is the greedy pick's (same order of operations), so the first offer is the greedy pick's token with its log-probability's bits.  A row with
+ * every token masked offers (eot, 0) alone; a dead row (state.sum_logprob == -inf) offers nothing.  state is only read. */
+int kk_op_whisper_beam_topk(void* stream, int B, int beam_size, const float* logits, long long ldl, const kk_whisper_pick_params* params,
+                            const uint32_t* suppress, const kk_whisper_pick_state* state, int32_t* cand_token, float* cand_logprob);
+/* bufs: a HOST struct of device pointers.  reset: owner[0][b][p] = b, fin_count = complete = 0, not_complete = n_audio. */
+int kk_op_whisper_beam_reset(void* stream, const kk_whisper_beam_bufs* bufs);
+/* One BeamSearchDecoder.update per window on the offers in bufs: candidate (row j, rank r) scores state[j].sum_logprob + logprob (fp32); at
+ * state.count == 0 only row 0 of a window offers.  The candidates are walked by score descending, then row ascending, then rank ascending: one
+ * ending in eot finishes (kept while fin_count < max_candidates, its ids materialised into fin_tokens), any other becomes the next free slot's
+ * prefix, until beam_size are saved.  Per slot: parent, next[] and tokens[slot][count] = the token, state = the PARENT's state advanced by the token
+ * with sum_logprob = the score, owner[flip ^ 1][slot][p] = owner[flip][parent][p] for p < pos (the positions the parents hold) and the slot itself
+ * from pos on.  Slots left over are dead: sum -inf, token eot, own table row.  Token i of a prefix lies at tokens[owner[row][pos - count + i]][i]. */
+int kk_op_whisper_beam_select(void* stream, const kk_whisper_beam_bufs* bufs, int flip, int pos, const kk_whisper_pick_params* params,
+                              kk_whisper_pick_state* state, int32_t* tokens, int32_t* next);
+/* The handle: after set_audio_groups(n_group = beam_size) and pick_setup, beam_setup lays the buffers above out in the caller's beam_state
+ * (..._beam_state_bytes; the window state keeps its size) and resets them.  Until the next pick_setup, kk_whisper_text_pick runs top-k and select,
+ * and a forward of one position reads the self K/V through the owner table.  not_complete reads the counter of incomplete windows (HOST int32;
+ * synchronises).  read (HOST destinations; synchronises): the finished stores -- fin_count [n_audio], fin_score and fin_length [n_audio][max_candidates],
+ * fin_tokens [n_audio][max_candidates][cap] -- and the live rows: live_tokens [B][cap] gathered through the table, live_sum and live_length [B]
+ * (a dead slot's sum is -inf). */
+size_t kk_whisper_text_beam_state_bytes(const kk_whisper_text* m, int n_audio, int beam_size, int max_candidates);
+int kk_whisper_text_beam_setup(kk_whisper_text* m, void* stream, int beam_size, int max_candidates, void* beam_state, size_t bytes);
+int kk_whisper_text_beam_not_complete(kk_whisper_text* m, void* stream, int32_t* out);
+int kk_whisper_text_beam_read(kk_whisper_text* m, void* stream, int cap, int32_t* fin_count, float* fin_score, int32_t* fin_length, int32_t* fin_tokens,
+                              int32_t* live_tokens, float* live_sum, int32_t* live_length);
 
 /* ---- row mode: decoder rows that join and leave one running batch -----------------------------------------------------------
  * A second state beside the window of set_audio, on the same weights and the same stream: max_rows <= KK_WHISPER_MAX_ROWS rows, each with its

@@ -64,6 +64,12 @@ class KKWhisperRowsItem(C.Structure):  # kk_whisper_rows_item
     _fields_ = [("row", C.c_int32), ("pos", C.c_int32), ("count", C.c_int32), ("from_", C.c_int32), ("keep", C.c_int32), ("slot", C.c_int32)]
 
 
+class KKWhisperBeamBufs(C.Structure):  # kk_whisper_beam_bufs: device pointers of a beam search on caller-owned buffers
+    _fields_ = [("n_audio", C.c_int32), ("beam_size", C.c_int32), ("max_candidates", C.c_int32), ("n_ctx", C.c_int32), ("cap", C.c_int32), ("reserved", C.c_int32),
+                ("cand_token", C.c_void_p), ("cand_logprob", C.c_void_p), ("owner", C.c_void_p * 2), ("parent", C.c_void_p), ("fin_score", C.c_void_p),
+                ("fin_length", C.c_void_p), ("fin_tokens", C.c_void_p), ("fin_count", C.c_void_p), ("complete", C.c_void_p), ("not_complete", C.c_void_p)]
+
+
 WHISPER_MAX_ROWS = 32  # KK_WHISPER_MAX_ROWS
 WHISPER_MAX_GROUP = 8  # KK_WHISPER_MAX_GROUP
 
@@ -267,6 +273,14 @@ SIGNATURES = {
     "kk_whisper_text_state_bytes_groups": (_sz, [_vp, _i, _i]),
     "kk_whisper_text_set_audio_groups": (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp, _sz]),
     "kk_whisper_text_sample_setup": (_i, [_vp, _vp, _f, _u64, _vp]),
+    "kk_op_whisper_attn_rows_owned": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz]),
+    "kk_op_whisper_beam_topk": (_i, [_vp, _i, _i, _vp, C.c_longlong, _vp, _vp, _vp, _vp, _vp]),
+    "kk_op_whisper_beam_reset": (_i, [_vp, C.POINTER(KKWhisperBeamBufs)]),
+    "kk_op_whisper_beam_select": (_i, [_vp, C.POINTER(KKWhisperBeamBufs), _i, _i, _vp, _vp, _vp, _vp]),
+    "kk_whisper_text_beam_state_bytes": (_sz, [_vp, _i, _i, _i]),
+    "kk_whisper_text_beam_setup": (_i, [_vp, _vp, _i, _i, _vp, _sz]),
+    "kk_whisper_text_beam_not_complete": (_i, [_vp, _vp, C.POINTER(C.c_int32)]),
+    "kk_whisper_text_beam_read": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "kk_whisper_text_rows_state_bytes": (_sz, [_vp, _i]),
     "kk_whisper_text_rows_workspace_bytes": (_sz, [_vp, _i, _i]),
     "kk_whisper_text_rows_open": (_i, [_vp, _vp, _i, _vp, _sz]),
@@ -333,7 +347,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 21:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 23:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

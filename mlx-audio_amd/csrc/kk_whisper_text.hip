@@ -38,6 +38,12 @@
 //   and token stores once per row, and the row-table kernel writes a second table item_cross[r] = item[r] / n_group that the cross-attention reads.
 //   n_group = 1 is set_audio: one table, the launches and arguments of before.
 //
+// ---- beam search ----------------------------------------------------------------------------------------------------------------------------
+//   On a grouped state with n_group = beam_size: a step is the forward plus beam_topk (a row's K + 1 best tokens behind the pick's filters) and beam_select
+//   (one workgroup per window: OpenAI's BeamSearchDecoder.update on the window's K (K + 1) candidates).  The self K/V is never moved: an owner table
+//   [row][position] names the physical row that holds each position of a beam, select rewrites it from the parents' rows (two copies, swapped every step),
+//   and the step's self-attention is attn_rows<OWNED>, which reads key j of row r in item owner[r][j].
+//
 // ---- row mode (the end of this file) ---------------------------------------------------------------------------------------------------
 //   Rows with their own window, position, pick parameters and lifetime in a second state buffer.  A round is the window's launch sequence behind
 //   text_plan_kernel, which fills the per-row index arrays and tokens from a table of items passed as the launch's argument.
@@ -58,13 +64,17 @@ __device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w <<
 __device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xFFFF0000u); }
 
 // ---------------------------------------------------------------------------------------------------------------------------- attention
+// OWNED: `item` is an owner table [row][T_rows] and key j of row r is read from item owner[r][j] -- a beam's keys stay in the physical rows
+// that computed them.  The arithmetic is the direct form's, so a row's bits are those of a plain row holding the same keys.
+template <bool OWNED>
 __global__ __launch_bounds__(64) void attn_rows_kernel(const float* q, const bf16_t* kv, int k_off, int v_off, long long item_stride, int ld, int T_rows,
                                                        int items, const int* item, const int* len, int heads, float* scratch, int nsplit) {
   const int sp = blockIdx.x, h = blockIdx.y, r = blockIdx.z, lane = threadIdx.x, kg = lane >> 3, ch = lane & 7;
   int L = len[r];
   L = L < T_rows ? L : T_rows;
-  int it = item[r];
+  int it = OWNED ? 0 : item[r];
   it = it < 0 ? 0 : (it >= items ? items - 1 : it);
+  const int* own = item + (long long)r * T_rows;  // OWNED only
   float* rec = scratch + (((long long)r * heads + h) * nsplit + sp) * ATTN_REC;
   const int k_lo = sp * ATTN_SPLIT, k_hi = k_lo + ATTN_SPLIT < L ? k_lo + ATTN_SPLIT : L;
   if (k_lo >= k_hi) {  // (uniform) nothing of this row in the split
@@ -81,12 +91,22 @@ __global__ __launch_bounds__(64) void attn_rows_kernel(const float* q, const bf1
   for (int c = 0; c < 8; ++c) acc[c] = 0.f;
   for (int k0 = k_lo; k0 < k_hi; k0 += 64) {
     uint4 kr[8], vr[8];
+    int ow[8];
+    if constexpr (OWNED) {  // the eight owners first: the K / V loads behind them are then in flight together
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int key = k0 + 8 * j + kg;
+        const int o = key < k_hi ? own[key] : 0;
+        ow[j] = o < 0 ? 0 : (o >= items ? items - 1 : o);
+      }
+    }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int key = k0 + 8 * j + kg;
       kr[j] = vr[j] = uint4{0u, 0u, 0u, 0u};
       if (key < k_hi) {
         const bf16_t* p = base + (long long)key * ld;
+        if constexpr (OWNED) p += (long long)ow[j] * item_stride;
         kr[j] = *(const uint4*)(p + k_off);
         vr[j] = *(const uint4*)(p + v_off);
       }
@@ -166,14 +186,16 @@ __global__ __launch_bounds__(64) void attn_merge_kernel(const float* scratch, in
 inline int attn_nsplit(int T_rows) { return (T_rows + ATTN_SPLIT - 1) / ATTN_SPLIT; }
 inline size_t attn_scratch_floats(int R, int heads, int T_rows) { return (size_t)R * heads * attn_nsplit(T_rows) * ATTN_REC; }
 
+// OWNED: `item` is the owner table [R][T_rows]
+template <bool OWNED = false>
 int launch_attn_rows(hipStream_t st, int R, int heads, const float* q, const bf16_t* kv, int k_off, int v_off, int items, int T_rows, int ld, const int* item,
                      const int* len, float* out, float* scratch) {
   const int ns = attn_nsplit(T_rows);
   for (int r0 = 0; r0 < R; r0 += 32768) {  // grid.z limit
     const int n = R - r0 < 32768 ? R - r0 : 32768;
     float* sc = scratch + (size_t)r0 * heads * ns * ATTN_REC;
-    hipLaunchKernelGGL(attn_rows_kernel, dim3(ns, heads, n), dim3(64), 0, st, q + (size_t)r0 * heads * 64, kv, k_off, v_off, (long long)T_rows * ld, ld, T_rows,
-                       items, item + r0, len + r0, heads, sc, ns);
+    hipLaunchKernelGGL(attn_rows_kernel<OWNED>, dim3(ns, heads, n), dim3(64), 0, st, q + (size_t)r0 * heads * 64, kv, k_off, v_off, (long long)T_rows * ld, ld, T_rows,
+                       items, item + (OWNED ? (size_t)r0 * T_rows : (size_t)r0), len + r0, heads, sc, ns);
     KK_CHECK_LAUNCH();
     hipLaunchKernelGGL(attn_merge_kernel, dim3(heads, n), dim3(64), 0, st, sc, ns, heads, len + r0, out + (size_t)r0 * heads * 64);
     KK_CHECK_LAUNCH();
@@ -306,23 +328,69 @@ __device__ __forceinline__ Osm osm_block(Osm v, Osm* sh) {  // all 1024 threads;
   return r;
 }
 
+// the beam's sizes, and a candidate of its top-k
+constexpr int BEAM_C = KK_WHISPER_MAX_GROUP + 1;               // candidates a row offers, at most
+constexpr int BEAM_N = KK_WHISPER_MAX_GROUP * BEAM_C;          // candidates of a window, at most
+constexpr int BEAM_FIN = 2 * KK_WHISPER_MAX_GROUP;             // finished sequences a window keeps, at most
+
+struct Top {  // a candidate of the top-k: ordered by value descending, then id ascending; {-inf, -1}: none
+  float v;
+  int i;
+};
+__device__ __forceinline__ Top top_merge(const Top a, const Top b) {  // symmetric in its bits, as osm_merge is
+  const bool take = b.v > a.v || (b.v == a.v && b.i >= 0 && (a.i < 0 || b.i < a.i));
+  return Top{take ? b.v : a.v, take ? b.i : a.i};  // (field by field: a select between two structs goes through memory)
+}
+__device__ __forceinline__ Top top_block(Top v, Top* sh) {  // all 1024 threads; the result in every thread
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) v = top_merge(v, Top{__shfl_xor(v.v, o), __shfl_xor(v.i, o)});
+  __syncthreads();  // the previous use of sh is over
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  Top r = sh[0];
+  for (int w = 1; w < 16; ++w) r = top_merge(r, sh[w]);
+  return r;
+}
+
 // what a sampled pick adds to a row's arguments: 1 / temperature, the Philox key and the row's stream id
 struct PickDraw {
   float inv_t;
   uint64_t seed;
   uint32_t stream;
 };
+// what the beam's top-k adds: the offers it writes (C pairs, descending) and the LDS of its block maximum
+struct PickTop {
+  int C;
+  int32_t* token;
+  float* logprob;
+  Top* sh;
+};
+enum { PICK_GREEDY = 0, PICK_SAMPLE = 1, PICK_TOPK = 2 };
 
 // The pick of ONE row by one workgroup: lg the row's logits, P its parameters, suppress its bitmask (or null), st its state, tokens its store of
 // `cap` ids, next where its choice goes.  not_ended: the launch-wide counter, or null (the per-row form: the row's state.ended is its flag).
 // SAMPLE: the token is drawn from softmax(l / T) over the filtered logits l by Gumbel-max in the same pass that takes the log-sum-exp of the
 // UNTEMPERED l (decoding.py:263-270): token = argmax_i (l_i / T - log(-log u_i)), lowest index on ties, u_i = philox_open of word i & 3 of
 // philox4(seed, stream << 32 | state.count, i >> 2).  A masked token gets no noise.  A row's draws depend on (seed, stream, its own history) alone.
-template <bool SAMPLE>
+// PICK_TOPK (the beam's offers): nothing is chosen and the state is only read.  The row's top.C best tokens over the same filtered logits go to
+// top.token / top.logprob in descending order, equal logits by the lower id, never a masked one, unused slots -1: (token, l[token] - logsumexp(l)) on
+// the log-sum-exp below, so the first offer is the greedy pick's token with its log-probability's bits.  Everything masked: (eot, 0) alone, as the greedy
+// pick ends such a row; a dead row (sum -inf): nothing.  Each thread keeps its own best in registers in the pass that takes the log-sum-exp (its share is
+// walked in rising id: a later equal stays behind), and top.C rounds of a block maximum over the threads' heads merge them.
+template <int MODE>
 __device__ __forceinline__ void pick_row(const float* lg, const kk_whisper_pick_params P, const uint32_t* suppress, kk_whisper_pick_state* st, int32_t* tokens,
-                                         int cap, int32_t* next, int32_t* not_ended, Osm* sh, const PickDraw dr = PickDraw{0.f, 0, 0}) {
+                                         int cap, int32_t* next, int32_t* not_ended, Osm* sh, const PickDraw dr = PickDraw{0.f, 0, 0},
+                                         const PickTop top = PickTop{0, nullptr, nullptr, nullptr}) {
+  constexpr bool SAMPLE = MODE == PICK_SAMPLE, TOPK = MODE == PICK_TOPK;
   const int tid = threadIdx.x;
   const kk_whisper_pick_state S = *st;
+  if constexpr (TOPK) {
+    if (tid < top.C) {
+      top.token[tid] = -1;
+      top.logprob[tid] = -INFINITY;
+    }
+    if (S.sum_logprob == -INFINITY) return;  // (uniform) a dead slot
+  }
   const int V = P.n_vocab, tb = P.timestamp_begin;
   const bool first = S.count == 0, ts = !P.without_timestamps;
   const bool last_ts = ts && S.count >= 1 && S.last >= tb, pen_ts = S.count < 2 || S.penultimate >= tb;
@@ -372,9 +440,33 @@ __device__ __forceinline__ void pick_row(const float* lg, const kk_whisper_pick_
   }
   Osm f = {-INFINITY, 0.f, 0}, best = {-INFINITY, 1.f, 0};  // best (SAMPLE): the highest noisy score of the share and its lowest index
   const uint64_t ctr = ((uint64_t)dr.stream << 32) | (uint32_t)S.count;
+  constexpr int NT = TOPK ? BEAM_C : 1;
+  float tv[NT];  // (TOPK) the share's best, descending
+  int ti[NT];
+#pragma unroll
+  for (int u = 0; u < NT; ++u) {
+    tv[u] = -INFINITY;
+    ti[u] = -1;
+  }
   walk([&](int i, float v, unsigned word) {
     const bool masked = pre(i, word) || (ts && (rules(i) || (mass && i < tb)));
     osm_add(f, masked ? -INFINITY : v, i);
+    if constexpr (TOPK) {
+      if (!masked && v > tv[NT - 1]) {  // (never a NaN or -inf logit)
+        tv[NT - 1] = v;
+        ti[NT - 1] = i;
+#pragma unroll
+        for (int u = NT - 1; u > 0; --u) {
+          const bool up = tv[u] > tv[u - 1];
+          const float xv = tv[u];
+          const int xi = ti[u];
+          tv[u] = up ? tv[u - 1] : xv;
+          ti[u] = up ? ti[u - 1] : xi;
+          tv[u - 1] = up ? xv : tv[u - 1];
+          ti[u - 1] = up ? xi : ti[u - 1];
+        }
+      }
+    }
     if constexpr (SAMPLE) {
       if (!masked && v != -INFINITY) {
         uint32_t r[4];
@@ -389,8 +481,36 @@ __device__ __forceinline__ void pick_row(const float* lg, const kk_whisper_pick_
       }
     }
   });
-  f = osm_block(f, sh);
+  f = osm_block(f, sh);  // (TOPK: its barriers order the stores of -1 above before thread 0's below)
   if constexpr (SAMPLE) best = osm_block(best, sh);  // (.s rides along unused, as in the text maximum above)
+  if constexpr (TOPK) {
+    if (f.m == -INFINITY) {  // everything masked
+      if (tid == 0) {
+        top.token[0] = P.eot;
+        top.logprob[0] = 0.f;
+      }
+      return;
+    }
+    const float lse = f.m + logf(f.s);
+    for (int k = 0; k < top.C; ++k) {
+      const Top t = top_block(Top{tv[0], ti[0]}, top.sh);
+      if (t.i < 0) break;  // (uniform) fewer than C unmasked tokens
+      if (t.i == ti[0]) {  // the winner's thread moves on to its next
+#pragma unroll
+        for (int u = 0; u + 1 < NT; ++u) {
+          tv[u] = tv[u + 1];
+          ti[u] = ti[u + 1];
+        }
+        tv[NT - 1] = -INFINITY;
+        ti[NT - 1] = -1;
+      }
+      if (tid == 0) {
+        top.token[k] = t.i;
+        top.logprob[k] = t.v - lse;
+      }
+    }
+    return;
+  }
   if (tid != 0) return;
   kk_whisper_pick_state N = S;
   int tok = SAMPLE ? best.i : f.i;
@@ -418,7 +538,7 @@ __global__ __launch_bounds__(1024) void pick_kernel(const float* logits, long lo
                                                     kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next, int32_t* not_ended) {
   __shared__ Osm sh[16];
   const int b = blockIdx.x;
-  pick_row<false>(logits + (long long)b * ldl, *params, suppress, state + b, tokens + (long long)b * cap, cap, next + b, not_ended, sh);
+  pick_row<PICK_GREEDY>(logits + (long long)b * ldl, *params, suppress, state + b, tokens + (long long)b * cap, cap, next + b, not_ended, sh);
 }
 
 // launch-wide, sampled: row b draws on its stream id streams[b]
@@ -427,7 +547,7 @@ __global__ __launch_bounds__(1024) void pick_sampled_kernel(const float* logits,
                                                             int cap, int32_t* next, int32_t* not_ended) {
   __shared__ Osm sh[16];
   const int b = blockIdx.x;
-  pick_row<true>(logits + (long long)b * ldl, *params, suppress, state + b, tokens + (long long)b * cap, cap, next + b, not_ended, sh,
+  pick_row<PICK_SAMPLE>(logits + (long long)b * ldl, *params, suppress, state + b, tokens + (long long)b * cap, cap, next + b, not_ended, sh,
                  PickDraw{inv_t, seed, streams[b]});
 }
 
@@ -439,7 +559,7 @@ __global__ __launch_bounds__(1024) void pick_rows_kernel(PickSel sel, const floa
                                                          const uint32_t* suppress, int words, kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next) {
   __shared__ Osm sh[16];
   const int r = sel.row[blockIdx.x];
-  pick_row<false>(logits + (long long)sel.logit[blockIdx.x] * ldl, params[r], suppress + (long long)r * words, state + r, tokens + (long long)r * cap, cap, next + r,
+  pick_row<PICK_GREEDY>(logits + (long long)sel.logit[blockIdx.x] * ldl, params[r], suppress + (long long)r * words, state + r, tokens + (long long)r * cap, cap, next + r,
                   nullptr, sh);
 }
 
@@ -447,6 +567,138 @@ __global__ void pick_reset_kernel(kk_whisper_pick_state* state, int B, int32_t* 
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b < B) state[b] = kk_whisper_pick_state{-1, -1, -1, 0, 0, 0.f, 0.f, 0};
   if (b == 0) *not_ended = B;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------- beam
+// One beam step behind a forward is two launches.  beam_topk: one workgroup per row, the pick's filters and the pick's log-sum-exp, and
+// the row's K + 1 best tokens.  beam_select: one workgroup per window orders the window's at most K (K + 1) candidates, walks them as OpenAI's
+// BeamSearchDecoder.update does, and writes the next live rows: parent, token, sum, pick state, owner table, and what finished.
+// the beam's offers: block b is row b, ONE params and ONE bitmask for the launch; cand_token / cand_logprob [B][C]
+__global__ __launch_bounds__(1024) void beam_topk_kernel(const float* logits, long long ldl, const kk_whisper_pick_params* params, const uint32_t* suppress,
+                                                         const kk_whisper_pick_state* state, int C, int32_t* cand_token, float* cand_logprob) {
+  __shared__ Osm sh[16];
+  __shared__ Top sht[16];
+  const int b = blockIdx.x;
+  pick_row<PICK_TOPK>(logits + (long long)b * ldl, *params, suppress, const_cast<kk_whisper_pick_state*>(state + b), nullptr, 0, nullptr, nullptr, sh,
+                      PickDraw{0.f, 0, 0}, PickTop{C, cand_token + (long long)b * C, cand_logprob + (long long)b * C, sht});
+}
+
+// owner[0][b][p] = b, nothing finished, every window incomplete
+__global__ void beam_reset_kernel(kk_whisper_beam_bufs b) {
+  const int B = b.n_audio * b.beam_size, n = B * b.n_ctx;
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) b.owner[0][e] = e / b.n_ctx;
+  if (blockIdx.x == 0) {
+    for (int w = threadIdx.x; w < b.n_audio; w += blockDim.x) {
+      b.fin_count[w] = 0;
+      b.complete[w] = 0;
+    }
+    if (threadIdx.x == 0) *b.not_complete = b.n_audio;
+  }
+}
+
+// Window w = blockIdx.x, rows w K .. w K + K - 1, whose parents hold `pos` positions; owner tables: b.owner[flip] is read, b.owner[flip ^ 1] written.
+// The walk's order is total -- score descending, parent row ascending, rank within the parent ascending -- so every thread computes its candidate's
+// place by counting, and thread 0 walks the sorted list.
+__global__ __launch_bounds__(256) void beam_select_kernel(kk_whisper_beam_bufs b, int flip, int pos, const kk_whisper_pick_params* params, kk_whisper_pick_state* state,
+                                                          int32_t* tokens, int32_t* next) {
+  __shared__ kk_whisper_pick_state par[KK_WHISPER_MAX_GROUP];
+  __shared__ float c_score[BEAM_N], c_lp[BEAM_N];
+  __shared__ int c_tok[BEAM_N], order[BEAM_N];
+  __shared__ int s_cand[KK_WHISPER_MAX_GROUP], f_cand[BEAM_FIN], f_slot[BEAM_FIN], n_new;
+  const int w = blockIdx.x, tid = threadIdx.x, K = b.beam_size, C = K + 1, n = K * C, row0 = w * K, T = b.n_ctx, cap = b.cap;
+  const int eot = params->eot, tb = params->timestamp_begin;
+  const int32_t* own_old = b.owner[flip & 1];
+  int32_t* own_new = b.owner[(flip & 1) ^ 1];
+  if (tid < K) par[tid] = state[row0 + tid];
+  if (tid < n) order[tid] = -1;
+  __syncthreads();
+  const int count = par[0].count;  // the rows of a window step together
+  if (tid < n) {
+    const int j = tid / C;
+    const int t = b.cand_token[(long long)row0 * C + tid];
+    const float lp = b.cand_logprob[(long long)row0 * C + tid];
+    const float s = par[j].sum_logprob + lp;
+    // at the first sampled position the rows of a window are one prefix: row 0 offers for all
+    const bool valid = t >= 0 && (count > 0 || j == 0) && par[j].sum_logprob != -INFINITY && s == s;
+    c_tok[tid] = valid ? t : -1;
+    c_score[tid] = valid ? s : -INFINITY;
+    c_lp[tid] = lp;
+  }
+  __syncthreads();
+  if (tid < n) {
+    const bool mv = c_tok[tid] >= 0;
+    const float ms = c_score[tid];
+    int place = 0;
+    for (int u = 0; u < n; ++u) {
+      const bool uv = c_tok[u] >= 0;
+      const float us = c_score[u];
+      place += uv != mv ? uv : (uv && us != ms ? us > ms : u < tid);  // valid ones first, by score, then by (parent, rank) = the index
+    }
+    order[place] = tid;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int saved = 0, nf = 0, fc = b.fin_count[w];
+    fc = fc < 0 ? 0 : fc;  // (a store that was never reset: nothing is written outside it)
+    for (int idx = 0; idx < n && saved < K; ++idx) {
+      const int c = order[idx];
+      if (c < 0 || c_tok[c] < 0) break;  // the offers are used up
+      if (c_tok[c] != eot) {
+        s_cand[saved++] = c;
+      } else if (fc < b.max_candidates && nf < BEAM_FIN) {  // finished, in descending score, while there is room
+        f_cand[nf] = c;
+        f_slot[nf++] = fc++;
+      }
+    }
+    for (int k = saved; k < K; ++k) s_cand[k] = -1;  // dead slots
+    n_new = nf;
+    b.fin_count[w] = fc;
+    if (fc >= b.max_candidates && !b.complete[w]) {
+      b.complete[w] = 1;
+      atomicSub(b.not_complete, 1);
+    }
+  }
+  __syncthreads();
+  if (tid < K) {  // the child's pick state from the PARENT's
+    const int c = s_cand[tid], row = row0 + tid;
+    kk_whisper_pick_state N = par[c >= 0 ? c / C : tid];
+    int tok = eot;
+    if (c >= 0) {
+      tok = c_tok[c];
+      N.sum_logprob = c_score[c];
+      N.last_logprob = c_lp[c];
+      if (tok >= tb) N.last_timestamp = tok;
+    } else {
+      N.sum_logprob = -INFINITY;
+      N.last_logprob = 0.f;
+    }
+    N.penultimate = N.last;
+    N.last = tok;
+    N.ended = 0;
+    N.count = count + 1;
+    state[row] = N;
+    next[row] = tok;
+    b.parent[row] = c >= 0 ? row0 + c / C : -1;
+    if (count >= 0 && count < cap) tokens[(long long)row * cap + count] = tok;
+  }
+  auto owner_of = [&](int row, int p) -> int {  // the physical row that holds position p of `row`, kept inside the window whatever the table holds
+    const int o = p >= 0 && p < T ? own_old[(long long)row * T + p] : row;
+    return o >= row0 && o < row0 + K ? o : row;
+  };
+  for (int e = tid; e < K * T; e += 256) {  // what the parent has is inherited; the positions from `pos` on are the row's own
+    const int k = e / T, p = e - k * T, c = s_cand[k];
+    own_new[(long long)(row0 + k) * T + p] = c >= 0 && p < pos ? owner_of(row0 + c / C, p) : row0 + k;
+  }
+  const int len = count < 0 ? 0 : (count < cap ? count : cap);
+  for (int f = 0; f < n_new; ++f) {  // the finished sequences, materialised now: their rows are overwritten from the next step on
+    const int c = f_cand[f], prow = row0 + c / C;
+    int32_t* dst = b.fin_tokens + ((long long)w * b.max_candidates + f_slot[f]) * cap;
+    for (int i = tid; i < len; i += 256) dst[i] = tokens[(long long)owner_of(prow, pos - count + i) * cap + i];
+    if (tid == 0) {
+      b.fin_score[w * b.max_candidates + f_slot[f]] = c_score[c];
+      b.fin_length[w * b.max_candidates + f_slot[f]] = len;
+    }
+  }
 }
 
 // the per-row index arrays of a forward call: row r = (b, s) sits at position pos + s of item b.  item_cross (a grouped state, else null): the window
@@ -502,26 +754,46 @@ extern "C" size_t kk_op_whisper_attn_rows_scratch_bytes(int R, int heads, int T_
   return attn_scratch_floats(R, heads, T_rows) * sizeof(float);
 }
 
+namespace {
+// the one body of kk_op_whisper_attn_rows (`table`: item [R]) and kk_op_whisper_attn_rows_owned (`table`: owner [R][T_rows])
+template <bool OWNED>
+int op_attn_rows(const char* who, void* stream, int R, int heads, const float* q, const void* kv, int k_off, int v_off, int items, int T_rows, int ld,
+                 const int32_t* table, const int32_t* len, float* out, void* scratch, size_t scratch_bytes) {
+  if (!q || !kv || !table || !len || !out || !scratch) return kk_failf("%s: null argument", who);
+  if (R < 1 || heads < 1 || items < 1 || T_rows < 1) return kk_failf("%s: bad argument (need R, heads, items, T_rows >= 1)", who);
+  if (k_off < 0 || v_off < 0 || k_off % 8 != 0 || v_off % 8 != 0 || ld % 8 != 0 || k_off + heads * 64 > ld || v_off + heads * 64 > ld)
+    return kk_failf("%s: k_off / v_off / ld must be multiples of 8 with `heads` heads of 64 channels inside a row", who);
+  if (((uintptr_t)kv & 15) || ((uintptr_t)q & 15) || ((uintptr_t)scratch & 15)) return kk_failf("%s: q, kv and scratch must be 16-byte aligned", who);
+  if (scratch_bytes < kk_op_whisper_attn_rows_scratch_bytes(R, heads, T_rows)) return kk_failf("%s: scratch too small", who);
+  // the only entries that look at device data: the row table decides what memory is read, so it is checked here (the handle's forward, which
+  // makes its own tables, calls the launcher and never synchronises)
+  const size_t per = OWNED ? (size_t)T_rows : 1;
+  std::vector<int32_t> hv((size_t)R * per), hl((size_t)R);
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemcpyAsync(hv.data(), table, hv.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(hl.data(), len, (size_t)R * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return kk_failf("%s: reading the row table failed", who);
+  for (int r = 0; r < R; ++r) {
+    if (hl[r] < 1 || hl[r] > T_rows) return kk_failf("%s: len[%d] = %d is outside [1, %d]", who, r, hl[r], T_rows);
+    if constexpr (OWNED) {
+      for (int j = 0; j < hl[r]; ++j)
+        if (hv[r * per + j] < 0 || hv[r * per + j] >= items) return kk_failf("%s: owner[%d][%d] = %d is outside [0, %d)", who, r, j, hv[r * per + j], items);
+    } else if (hv[r] < 0 || hv[r] >= items) {
+      return kk_failf("%s: item[%d] = %d is outside [0, %d)", who, r, hv[r], items);
+    }
+  }
+  return launch_attn_rows<OWNED>(st, R, heads, q, (const bf16_t*)kv, k_off, v_off, items, T_rows, ld, table, len, out, (float*)scratch);
+}
+}  // namespace
+
 extern "C" int kk_op_whisper_attn_rows(void* stream, int R, int heads, const float* q, const void* kv, int k_off, int v_off, int items, int T_rows, int ld,
                                        const int32_t* item, const int32_t* len, float* out, void* scratch, size_t scratch_bytes) {
-  if (!q || !kv || !item || !len || !out || !scratch) return kk_fail("kk_op_whisper_attn_rows: null argument");
-  if (R < 1 || heads < 1 || items < 1 || T_rows < 1) return kk_fail("kk_op_whisper_attn_rows: bad argument (need R, heads, items, T_rows >= 1)");
-  if (k_off < 0 || v_off < 0 || k_off % 8 != 0 || v_off % 8 != 0 || ld % 8 != 0 || k_off + heads * 64 > ld || v_off + heads * 64 > ld)
-    return kk_fail("kk_op_whisper_attn_rows: k_off / v_off / ld must be multiples of 8 with `heads` heads of 64 channels inside a row");
-  if (((uintptr_t)kv & 15) || ((uintptr_t)q & 15) || ((uintptr_t)scratch & 15)) return kk_fail("kk_op_whisper_attn_rows: q, kv and scratch must be 16-byte aligned");
-  if (scratch_bytes < kk_op_whisper_attn_rows_scratch_bytes(R, heads, T_rows)) return kk_fail("kk_op_whisper_attn_rows: scratch too small");
-  // the only entry that looks at device data: the row table decides what memory is read, so it is checked here (the handle's forward, which
-  // makes its own tables, calls the launcher and never synchronises)
-  std::vector<int32_t> hv(2 * (size_t)R);
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemcpyAsync(hv.data(), item, (size_t)R * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(hv.data() + R, len, (size_t)R * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return kk_fail("kk_op_whisper_attn_rows: reading the row table failed");
-  for (int r = 0; r < R; ++r) {
-    if (hv[r] < 0 || hv[r] >= items) return kk_failf("kk_op_whisper_attn_rows: item[%d] = %d is outside [0, %d)", r, hv[r], items);
-    if (hv[R + r] < 1 || hv[R + r] > T_rows) return kk_failf("kk_op_whisper_attn_rows: len[%d] = %d is outside [1, %d]", r, hv[R + r], T_rows);
-  }
-  return launch_attn_rows(st, R, heads, q, (const bf16_t*)kv, k_off, v_off, items, T_rows, ld, item, len, out, (float*)scratch);
+  return op_attn_rows<false>("kk_op_whisper_attn_rows", stream, R, heads, q, kv, k_off, v_off, items, T_rows, ld, item, len, out, scratch, scratch_bytes);
+}
+
+extern "C" int kk_op_whisper_attn_rows_owned(void* stream, int R, int heads, const float* q, const void* kv, int k_off, int v_off, int items, int T_rows, int ld,
+                                             const int32_t* owner, const int32_t* len, float* out, void* scratch, size_t scratch_bytes) {
+  return op_attn_rows<true>("kk_op_whisper_attn_rows_owned", stream, R, heads, q, kv, k_off, v_off, items, T_rows, ld, owner, len, out, scratch, scratch_bytes);
 }
 
 extern "C" int kk_op_whisper_linear_rows(void* stream, int M, int N, int K, const float* x, long long ldx, const void* w, const float* bias, int act,
@@ -576,6 +848,49 @@ extern "C" int kk_op_whisper_pick_reset(void* stream, int B, kk_whisper_pick_sta
   return 0;
 }
 
+extern "C" int kk_op_whisper_beam_topk(void* stream, int B, int beam_size, const float* logits, long long ldl, const kk_whisper_pick_params* params,
+                                       const uint32_t* suppress, const kk_whisper_pick_state* state, int32_t* cand_token, float* cand_logprob) {
+  if (!logits || !params || !state || !cand_token || !cand_logprob) return kk_fail("kk_op_whisper_beam_topk: null argument");
+  if (B < 1 || ldl < 1) return kk_fail("kk_op_whisper_beam_topk: bad argument");
+  if (beam_size < 1 || beam_size > KK_WHISPER_MAX_GROUP) return kk_failf("kk_op_whisper_beam_topk: beam_size = %d is outside [1, %d]", beam_size, KK_WHISPER_MAX_GROUP);
+  hipLaunchKernelGGL(beam_topk_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, logits, ldl, params, suppress, state, beam_size + 1, cand_token, cand_logprob);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
+namespace {
+int check_beam_bufs(const char* who, const kk_whisper_beam_bufs* b) {
+  if (!b) return kk_failf("%s: null argument", who);
+  if (b->n_audio < 1 || b->n_ctx < 1 || b->cap < 1) return kk_failf("%s: bad argument (need n_audio, n_ctx, cap >= 1)", who);
+  if (b->beam_size < 1 || b->beam_size > KK_WHISPER_MAX_GROUP) return kk_failf("%s: beam_size = %d is outside [1, %d]", who, b->beam_size, KK_WHISPER_MAX_GROUP);
+  if (b->max_candidates < 1 || b->max_candidates > BEAM_FIN) return kk_failf("%s: max_candidates = %d is outside [1, %d]", who, b->max_candidates, BEAM_FIN);
+  if (!b->cand_token || !b->cand_logprob || !b->owner[0] || !b->owner[1] || !b->parent || !b->fin_score || !b->fin_length || !b->fin_tokens || !b->fin_count ||
+      !b->complete || !b->not_complete)
+    return kk_failf("%s: a null buffer", who);
+  return 0;
+}
+}  // namespace
+
+extern "C" int kk_op_whisper_beam_reset(void* stream, const kk_whisper_beam_bufs* bufs) {
+  KK_TRY(check_beam_bufs("kk_op_whisper_beam_reset", bufs));
+  const long long n = (long long)bufs->n_audio * bufs->beam_size * bufs->n_ctx;
+  hipLaunchKernelGGL(beam_reset_kernel, dim3((unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024)), dim3(256), 0, (hipStream_t)stream, *bufs);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int kk_op_whisper_beam_select(void* stream, const kk_whisper_beam_bufs* bufs, int flip, int pos, const kk_whisper_pick_params* params,
+                                         kk_whisper_pick_state* state, int32_t* tokens, int32_t* next) {
+  const char* who = "kk_op_whisper_beam_select";
+  KK_TRY(check_beam_bufs(who, bufs));
+  if (!params || !state || !tokens || !next) return kk_failf("%s: null argument", who);
+  if (flip != 0 && flip != 1) return kk_failf("%s: flip must be 0 or 1", who);
+  if (pos < 0 || pos > bufs->n_ctx) return kk_failf("%s: pos = %d is outside [0, n_ctx = %d]", who, pos, bufs->n_ctx);
+  hipLaunchKernelGGL(beam_select_kernel, dim3(bufs->n_audio), dim3(256), 0, (hipStream_t)stream, *bufs, flip, pos, params, state, tokens, next);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
 // ================================================================================================================================ the handle
 struct TLin {  // a Linear: bf16 [N][K] dense at `w` of wdev, fp32 bias [N] at `b` of fdev
   size_t w = 0, b = 0;
@@ -605,6 +920,11 @@ struct kk_whisper_text {
   uint64_t seed = 0;
   const float* last_logits = nullptr;  // the last forward's last-position logits [B][last_ld], in the caller's memory
   long long last_ld = 0;
+  // beam search (beam_setup): until the next pick_setup, pick runs top-k + select on the caller's beam state and a forward of S = 1 reads
+  // the self K/V through the owner table owner[beam_flip]
+  bool picking = false, beam = false;  // pick_setup was called on this window; beam_setup after it
+  char* beam_state = nullptr;
+  int beam_cands = 0, beam_flip = 0, beam_picks = 0, beam_begin = 0;  // max_candidates, the current table, picks so far, the first sampled position
   // row mode (rows_open), beside the window: the caller's second state buffer and what the host knows of every row
   struct Row {
     bool admitted = false;
@@ -644,6 +964,26 @@ void plan_state(const kk_whisper_text_config& c, int n_audio, int B, Workspace& 
   s.next = (int32_t*)ws.raw((size_t)B * 4);
   s.not_ended = (int32_t*)ws.raw(4);
   s.streams = (uint32_t*)ws.raw((size_t)B * 4);
+}
+// the caller's beam state: what a beam search keeps beside the grouped window state of n_audio windows of K rows
+void plan_beam(const kk_whisper_text_config& c, int n_audio, int K, int max_candidates, Workspace& ws, kk_whisper_beam_bufs& b) {
+  const size_t B = (size_t)n_audio * K, T = c.n_text_ctx, F = (size_t)n_audio * max_candidates;
+  b.n_audio = n_audio;
+  b.beam_size = K;
+  b.max_candidates = max_candidates;
+  b.n_ctx = b.cap = c.n_text_ctx;
+  b.reserved = 0;
+  b.cand_token = (int32_t*)ws.raw(B * (K + 1) * 4);
+  b.cand_logprob = (float*)ws.raw(B * (K + 1) * 4);
+  b.owner[0] = (int32_t*)ws.raw(B * T * 4);
+  b.owner[1] = (int32_t*)ws.raw(B * T * 4);
+  b.parent = (int32_t*)ws.raw(B * 4);
+  b.fin_score = (float*)ws.raw(F * 4);
+  b.fin_length = (int32_t*)ws.raw(F * 4);
+  b.fin_tokens = (int32_t*)ws.raw(F * T * 4);
+  b.fin_count = (int32_t*)ws.raw((size_t)n_audio * 4);
+  b.complete = (int32_t*)ws.raw((size_t)n_audio * 4);
+  b.not_complete = (int32_t*)ws.raw(4);
 }
 struct TextWork {
   float *x, *ln, *q, *att, *h, *scratch;
@@ -843,7 +1183,7 @@ int text_set_audio(const char* who, kk_whisper_text* m, void* stream, int n_audi
   m->B = B;
   m->n_audio = n_audio;
   m->n_group = n_group;
-  m->sampling = false;
+  m->sampling = m->picking = m->beam = false;
   m->at = 0;
   m->last_logits = nullptr;
   return 0;
@@ -888,6 +1228,7 @@ struct TextPass {
   const bf16_t* cross;
   const int* item_cross;   // per flat row, the cross slot it reads (the row's own slot when every row has its window)
   const TextWork& p;
+  const int* owner = nullptr;  // a beam's step: the owner table [row][n_text_ctx] the self-attention reads its keys through (null: the row's own slot)
 
   // a Linear over `rows` rows, 16 at a time (S = 1: one launch, every weight byte read once for the batch)
   int lin(const TLin& l, int n0, int N, const float* x, long long ldx, int rows, int act, const float* res, float* out, long long ldo, bf16_t* ob,
@@ -921,7 +1262,10 @@ struct TextPass {
       KK_TRY(lin(L.q, 0, D, p.ln, D, R, KK_ACT_NONE, nullptr, p.q, D, nullptr, nullptr));
       KK_TRY(lin(L.k, 0, D, p.ln, D, R, KK_ACT_NONE, nullptr, nullptr, D, selfc, p.cache_row));      // K and V of the new positions straight into the cache
       KK_TRY(lin(L.v, 0, D, p.ln, D, R, KK_ACT_NONE, nullptr, nullptr, D, selfc + D, p.cache_row));
-      KK_TRY(launch_attn_rows(st, R, H, p.q, selfc, 0, D, items, c.n_text_ctx, 2 * D, p.item, p.len_self, p.att, p.scratch));  // causal: row (b, s) sees pos + s + 1 keys
+      if (owner)  // causal: row (b, s) sees pos + s + 1 keys
+        KK_TRY(launch_attn_rows<true>(st, R, H, p.q, selfc, 0, D, items, c.n_text_ctx, 2 * D, owner, p.len_self, p.att, p.scratch));
+      else
+        KK_TRY(launch_attn_rows(st, R, H, p.q, selfc, 0, D, items, c.n_text_ctx, 2 * D, p.item, p.len_self, p.att, p.scratch));
       KK_TRY(lin(L.out, 0, D, p.att, D, R, KK_ACT_NONE, p.x, p.x, D, nullptr, nullptr));
       KK_TRY(ln(L.cross_ln_w, L.cross_ln_b, p.x, D, R));
       KK_TRY(lin(L.cq, 0, D, p.ln, D, R, KK_ACT_NONE, nullptr, p.q, D, nullptr, nullptr));
@@ -975,6 +1319,15 @@ int text_forward(const char* who, kk_whisper_text* m, void* stream, int B, int S
   if (ws.oom) return kk_failf("%s: workspace too small", who);
   if (cap && m->n_group != 1) return kk_failf("%s: the window was set with n_group = %d; the capturing forward runs on a plain set_audio state", who, m->n_group);
   int* item_cross = m->n_group > 1 ? p.item_cross : nullptr;  // n_group 1: the row's own slot, one table as before
+  const int* owner = nullptr;
+  if (m->beam && m->beam_picks > 0) {  // before the first select every row holds its own keys
+    if (S != 1) return kk_failf("%s: a beam that has stepped takes one position at a time", who);
+    Workspace bs;
+    bind(bs, m->beam_state, (size_t)-1 / 2);
+    kk_whisper_beam_bufs bb;
+    plan_beam(c, m->n_audio, m->n_group, m->beam_cands, bs, bb);
+    owner = bb.owner[m->beam_flip];
+  }
   if (!tokens) {  // the step after a pick: the tokens it chose
     if (S != 1) return kk_failf("%s: tokens may be null only for S = 1 (the tokens of the last pick)", who);
     tokens = s.next;
@@ -985,7 +1338,7 @@ int text_forward(const char* who, kk_whisper_text* m, void* stream, int B, int S
   hipLaunchKernelGGL(embed_kernel, dim3(R), dim3(256), 0, st, tokens, p.posr, m->wdev + m->emb.w, V, m->fdev + m->pos, c.n_text_ctx, D, p.x);
   KK_CHECK_LAUNCH();
 
-  const TextPass run{m, st, B, m->n_audio, s.self, s.cross, item_cross ? item_cross : p.item, p};
+  const TextPass run{m, st, B, m->n_audio, s.self, s.cross, item_cross ? item_cross : p.item, p, owner};
   KK_TRY(run.layers(R, cap, B, S));
   if (all_positions) {
     KK_TRY(run.logits(p.x, D, R, logits_out));
@@ -1043,7 +1396,8 @@ extern "C" int kk_whisper_text_pick_setup(kk_whisper_text* m, void* stream, cons
   if ((suppress ? hipMemcpyAsync(s.suppress, suppress, words * 4, hipMemcpyHostToDevice, st) : hipMemsetAsync(s.suppress, 0, words * 4, st)) != hipSuccess)
     return kk_fail("kk_whisper_text_pick_setup: upload failed");
   if (hipStreamSynchronize(st) != hipSuccess) return kk_fail("kk_whisper_text_pick_setup: stream sync failed");  // the host arrays may go away
-  m->sampling = false;
+  m->sampling = m->beam = false;
+  m->picking = true;
   return kk_op_whisper_pick_reset(stream, m->B, s.rows, s.not_ended);
 }
 
@@ -1073,6 +1427,18 @@ extern "C" int kk_whisper_text_pick(kk_whisper_text* m, void* stream) {
   bind(ss, m->state, (size_t)-1 / 2);
   TextState s;
   plan_state(m->cfg, m->n_audio, m->B, ss, s);
+  if (m->beam) {
+    Workspace bs;
+    bind(bs, m->beam_state, (size_t)-1 / 2);
+    kk_whisper_beam_bufs bb;
+    plan_beam(m->cfg, m->n_audio, m->n_group, m->beam_cands, bs, bb);
+    if (m->beam_picks == 0) m->beam_begin = m->at;
+    KK_TRY(kk_op_whisper_beam_topk(stream, m->B, m->n_group, m->last_logits, m->last_ld, s.params, s.suppress, s.rows, bb.cand_token, bb.cand_logprob));
+    KK_TRY(kk_op_whisper_beam_select(stream, &bb, m->beam_flip, m->at, s.params, s.rows, s.tokens, s.next));
+    m->beam_flip ^= 1;
+    ++m->beam_picks;
+    return 0;
+  }
   if (m->sampling)
     return kk_op_whisper_pick_sampled(stream, m->B, m->last_logits, m->last_ld, s.params, s.suppress, m->temperature, m->seed, s.streams, s.rows, s.tokens,
                                       m->cfg.n_text_ctx, s.next, s.not_ended);
@@ -1104,6 +1470,94 @@ extern "C" int kk_whisper_text_read(kk_whisper_text* m, void* stream, int32_t* t
   if (hipMemcpy2DAsync(tokens, (size_t)cap * 4, s.tokens, (size_t)m->cfg.n_text_ctx * 4, (size_t)n * 4, m->B, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipMemcpyAsync(rows, s.rows, (size_t)m->B * sizeof *rows, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
     return kk_fail("kk_whisper_text_read: read failed");
+  return 0;
+}
+
+// ---- beam search on a grouped window state ---------------------------------------------------------------------------------------------
+extern "C" size_t kk_whisper_text_beam_state_bytes(const kk_whisper_text* m, int n_audio, int beam_size, int max_candidates) {
+  if (!m || n_audio < 1 || beam_size < 1 || beam_size > KK_WHISPER_MAX_GROUP || max_candidates < 1 || max_candidates > BEAM_FIN) return 0;
+  Workspace ws;
+  kk_whisper_beam_bufs b;
+  plan_beam(m->cfg, n_audio, beam_size, max_candidates, ws, b);
+  return ws.used + 256;
+}
+
+extern "C" int kk_whisper_text_beam_setup(kk_whisper_text* m, void* stream, int beam_size, int max_candidates, void* beam_state, size_t bytes) {
+  const char* who = "kk_whisper_text_beam_setup";
+  if (!m || !beam_state) return kk_failf("%s: null argument", who);
+  if (!m->state) return kk_failf("%s: set_audio_groups first", who);
+  if (!m->picking) return kk_failf("%s: pick_setup first", who);
+  if (beam_size != m->n_group) return kk_failf("%s: beam_size = %d, but the window was set with n_group = %d", who, beam_size, m->n_group);
+  if (max_candidates < 1 || max_candidates > BEAM_FIN) return kk_failf("%s: max_candidates = %d is outside [1, %d]", who, max_candidates, BEAM_FIN);
+  Workspace bs;
+  bind(bs, beam_state, bytes);
+  kk_whisper_beam_bufs bb;
+  plan_beam(m->cfg, m->n_audio, beam_size, max_candidates, bs, bb);
+  if (bs.oom) return kk_failf("%s: beam state buffer too small", who);
+  KK_TRY(kk_op_whisper_beam_reset(stream, &bb));
+  m->beam_state = (char*)beam_state;
+  m->beam_cands = max_candidates;
+  m->beam_flip = m->beam_picks = m->beam_begin = 0;
+  m->beam = true;
+  m->sampling = false;
+  return 0;
+}
+
+namespace {
+int beam_bound(const char* who, const kk_whisper_text* m, kk_whisper_beam_bufs& bb) {
+  if (!m) return kk_failf("%s: null model", who);
+  if (!m->state || !m->beam) return kk_failf("%s: no beam: kk_whisper_text_beam_setup first", who);
+  Workspace bs;
+  bind(bs, m->beam_state, (size_t)-1 / 2);
+  plan_beam(m->cfg, m->n_audio, m->n_group, m->beam_cands, bs, bb);
+  return 0;
+}
+}  // namespace
+
+extern "C" int kk_whisper_text_beam_not_complete(kk_whisper_text* m, void* stream, int32_t* out) {
+  const char* who = "kk_whisper_text_beam_not_complete";
+  kk_whisper_beam_bufs bb;
+  KK_TRY(beam_bound(who, m, bb));
+  if (!out) return kk_failf("%s: null argument", who);
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemcpyAsync(out, bb.not_complete, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return kk_failf("%s: read failed", who);
+  return 0;
+}
+
+extern "C" int kk_whisper_text_beam_read(kk_whisper_text* m, void* stream, int cap, int32_t* fin_count, float* fin_score, int32_t* fin_length, int32_t* fin_tokens,
+                                         int32_t* live_tokens, float* live_sum, int32_t* live_length) {
+  const char* who = "kk_whisper_text_beam_read";
+  kk_whisper_beam_bufs bb;
+  KK_TRY(beam_bound(who, m, bb));
+  if (!fin_count || !fin_score || !fin_length || !fin_tokens || !live_tokens || !live_sum || !live_length || cap < 1) return kk_failf("%s: bad argument", who);
+  Workspace ss;
+  bind(ss, m->state, (size_t)-1 / 2);
+  TextState s;
+  plan_state(m->cfg, m->n_audio, m->B, ss, s);
+  hipStream_t st = (hipStream_t)stream;
+  const int T = m->cfg.n_text_ctx, B = m->B, n = cap < T ? cap : T;
+  const size_t F = (size_t)m->n_audio * m->beam_cands;
+  std::vector<int32_t> tok((size_t)B * T), own((size_t)B * T);
+  std::vector<kk_whisper_pick_state> rows(B);
+  if (hipMemcpyAsync(fin_count, bb.fin_count, (size_t)m->n_audio * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(fin_score, bb.fin_score, F * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(fin_length, bb.fin_length, F * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpy2DAsync(fin_tokens, (size_t)cap * 4, bb.fin_tokens, (size_t)T * 4, (size_t)n * 4, F, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(tok.data(), s.tokens, tok.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(own.data(), bb.owner[m->beam_flip], own.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(rows.data(), s.rows, (size_t)B * sizeof(kk_whisper_pick_state), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return kk_failf("%s: read failed", who);
+  for (int b = 0; b < B; ++b) {  // a live row's tokens lie where its ancestors wrote them: token i in the row that owns position beam_begin + i
+    const int len = rows[b].count < 0 ? 0 : (rows[b].count < n ? rows[b].count : n);
+    live_sum[b] = rows[b].sum_logprob;
+    live_length[b] = len;
+    for (int i = 0; i < len; ++i) {
+      const int p = m->beam_begin + i;
+      int o = p < T ? own[(size_t)b * T + p] : b;
+      if (o < 0 || o >= B) o = b;
+      live_tokens[(size_t)b * cap + i] = tok[(size_t)o * T + i];
+    }
+  }
   return 0;
 }
 

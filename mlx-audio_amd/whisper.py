@@ -460,6 +460,30 @@ class Model:
 
         return decode_with_fallback(self, *a, **kw)
 
+    def beam_search(self, *a, **kw):
+        """`decode` by beam search (`beam_size`, `patience`) at temperature 0, see whisper_beam.beam_search"""
+        if self._text is None:
+            raise NotImplementedError(_NOT_BUILT)
+        from .whisper_beam import beam_search
+
+        return beam_search(self, *a, **kw)
+
+    def beam_candidates(self, *a, **kw):
+        """every window's `beam_size` candidates after the beam's finalize, before the ranker, see whisper_beam.beam_candidates"""
+        if self._text is None:
+            raise NotImplementedError(_NOT_BUILT)
+        from .whisper_beam import beam_candidates
+
+        return beam_candidates(self, *a, **kw)
+
+    def beam_decode_with_fallback(self, *a, **kw):
+        """the temperature fallback with beam search as its temperature-0 pass, see whisper_beam.decode_with_fallback"""
+        if self._text is None:
+            raise NotImplementedError(_NOT_BUILT)
+        from .whisper_beam import decode_with_fallback
+
+        return decode_with_fallback(self, *a, **kw)
+
     def serve(self, max_rows: int = 8, eos_check_interval: int = 8, max_round_tokens: int = 256):
         """A running decoder batch that windows join and leave (whisper_serve.WhisperBatcher): `submit(window, options)` returns a Future of
         the DecodingResult `decode` would return for that window alone.  `decode`, `logits`, `detect_language` and `find_alignment` keep working on this

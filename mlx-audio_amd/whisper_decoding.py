@@ -312,6 +312,46 @@ class TextRuntime:
         _lib.check(self._lib.kk_whisper_text_sample_setup(self._h, self._stream(), float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, ids.ctypes.data_as(C.c_void_p)),
                    "kk_whisper_text_sample_setup")
 
+    def beam_setup(self, beam_size: int, max_candidates: int):
+        """after set_audio_groups(features, beam_size) and pick_setup: `pick` runs the beam's top-k and select, `step` reads the self K/V through the
+        owner table, until the next pick_setup.  The beam state lives in memory of its own beside the window state."""
+        import torch
+
+        from . import _lib
+
+        n_audio = self.B // beam_size
+        need = int(self._lib.kk_whisper_text_beam_state_bytes(self._h, n_audio, beam_size, max_candidates))
+        if need == 0:
+            raise ValueError(f"beam_size must be in 1 .. {_lib.WHISPER_MAX_GROUP} and max_candidates in 1 .. {2 * _lib.WHISPER_MAX_GROUP}")
+        if getattr(self, "_beam_state", None) is None or self._beam_state.numel() < need:
+            self._beam_state = torch.empty(need, dtype=torch.uint8, device=self.device)
+        _lib.check(self._lib.kk_whisper_text_beam_setup(self._h, self._stream(), beam_size, max_candidates, C.c_void_p(self._beam_state.data_ptr()),
+                                                        self._beam_state.numel()), "kk_whisper_text_beam_setup")
+        self._beam = (n_audio, beam_size, max_candidates)
+
+    def beam_not_complete(self) -> int:
+        from . import _lib
+
+        n = C.c_int32()
+        _lib.check(self._lib.kk_whisper_text_beam_not_complete(self._h, self._stream(), C.byref(n)), "kk_whisper_text_beam_not_complete")
+        return int(n.value)
+
+    def beam_read(self):
+        """-> per window its finished sequences [(tokens, sum_logprob)] in the order they finished, and its live prefixes [(tokens, sum_logprob)] by slot
+        (a dead slot's sum is -inf)"""
+        from . import _lib
+
+        n_audio, K, mc = self._beam
+        cap = self.dims.n_text_ctx
+        fc, fs, fl = np.zeros(n_audio, np.int32), np.zeros((n_audio, mc), np.float32), np.zeros((n_audio, mc), np.int32)
+        ft, lt = np.zeros((n_audio, mc, cap), np.int32), np.zeros((self.B, cap), np.int32)
+        ls, ll = np.zeros(self.B, np.float32), np.zeros(self.B, np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _lib.check(self._lib.kk_whisper_text_beam_read(self._h, self._stream(), cap, p(fc), p(fs), p(fl), p(ft), p(lt), p(ls), p(ll)), "kk_whisper_text_beam_read")
+        finished = [[([int(t) for t in ft[a, f, : fl[a, f]]], float(fs[a, f])) for f in range(fc[a])] for a in range(n_audio)]
+        live = [[([int(t) for t in lt[a * K + k, : ll[a * K + k]]], float(ls[a * K + k])) for k in range(K)] for a in range(n_audio)]
+        return finished, live
+
     def rewind(self, position: int = 0):
         from . import _lib
 

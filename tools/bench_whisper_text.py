@@ -18,9 +18,15 @@ counts back, so their figures include that round trip).  The kernels' own durati
 state of the same row count on repeated features (`set_audio`, the step with the greedy pick) against the grouped state on ONE cross K/V slice per window
 (`set_audio_groups`, the step with the sampled pick when T > 0), either pick alone, and the two states' sizes.
 
+`--beam K` times beam search instead (mlx-audio_amd/whisper_beam.py): for 1 and 8 windows of K rows each on the grouped state, the beam step
+(forward through the owner table + top-k + select) next to the sampled `best_of = K` step at temperature 1, either pick alone, the forward alone at
+key counts 32, 224 and 448 under both (four layers of owned against direct self-attention on the same keys are all that differs), and the bytes of
+the beam state next to the grouped state.
+
 Usage:  python tools/bench_whisper_text.py [--steps 20] [--warmup 3] [--inner 20] [--position 64] [--out profiles/whisper_text_bench.json]
         python tools/bench_whisper_text.py --align [--steps 20] [--warmup 3] [--out profiles/whisper_align_bench.json]
-        python tools/bench_whisper_text.py --best-of 5 --temperature 1.0 [--steps 20] [--warmup 3] [--out profiles/whisper_sample_bench.json]"""
+        python tools/bench_whisper_text.py --best-of 5 --temperature 1.0 [--steps 20] [--warmup 3] [--out profiles/whisper_sample_bench.json]
+        python tools/bench_whisper_text.py --beam 5 [--steps 20] [--warmup 3] [--out profiles/whisper_beam_bench.json]"""
 import argparse
 import csv
 import json
@@ -37,7 +43,7 @@ sys.path.insert(0, ROOT)
 CTX, WIDTH, HEADS, LAYERS, VOCAB, TEXT_CTX = 1500, 1280, 20, 4, 51866, 448
 
 FAMILIES = (("linear_rows", "linear_rows_kernel"), ("attention", "attn_rows_kernel"), ("attention", "attn_merge_kernel"), ("layernorm", "layernorm_kernel"),
-            ("pick", "pick_kernel"), ("pick", "pick_sampled_kernel"), ("embed + row tables", "embed_kernel"), ("embed + row tables", "text_rows_kernel"))
+            ("pick", "pick_kernel"), ("pick", "pick_sampled_kernel"), ("beam top-k", "beam_topk_kernel"), ("beam select", "beam_select_kernel"), ("embed + row tables", "embed_kernel"), ("embed + row tables", "text_rows_kernel"))
 
 
 def step_bytes(B, position):
@@ -60,7 +66,7 @@ def digest(path, steps):
         for row in csv.DictReader(f):
             rows.append((int(row["Start_Timestamp"]), int(row["End_Timestamp"]), row["Kernel_Name"]))
     rows.sort()
-    first = next(i for i, r in enumerate(rows) if "pick_kernel" in r[2] or "pick_sampled_kernel" in r[2])
+    first = next(i for i, r in enumerate(rows) if "pick_kernel" in r[2] or "pick_sampled_kernel" in r[2] or "beam_select_kernel" in r[2])
     rows = rows[first + 1:]
     fam, calls, total, other = {}, {}, 0.0, 0.0
     for t0, t1, name in rows:
@@ -111,6 +117,7 @@ def main():
     ap.add_argument("--align", action="store_true", help="time the token-timestamp path (capturing forward, align_matrix, dtw) instead of the decode step")
     ap.add_argument("--temperature", type=float, default=0.0, help="> 0: the grouped state's picks are sampled at this temperature (DESIGN 8j)")
     ap.add_argument("--best-of", type=int, default=0, help="G > 0: time G rows per window on one cross K/V slice against the plain state of as many rows")
+    ap.add_argument("--beam", type=int, default=0, help="K > 0: time the beam step of K rows per window against the sampled best_of = K step (DESIGN 8k)")
     ap.add_argument("--digest", default=None)
     ap.add_argument("--digest-steps", type=int, default=200)
     a = ap.parse_args()
@@ -272,6 +279,54 @@ def main():
                 begin_state(grouped)
                 emit(dict(case="decode_step", position=a.position, **kind, **timed(step, a.inner)))
                 emit(dict(case="pick_only", **kind, **timed(rt.pick, a.inner)))
+        write_out()
+        return
+
+    if a.beam:
+        K = a.beam
+        if not 1 <= K <= _lib.WHISPER_MAX_GROUP:
+            raise SystemExit(f"--beam must be in 1 .. {_lib.WHISPER_MAX_GROUP}")
+        lib = rt._lib
+        for windows in ((a.batch,) if a.only_steps else (1, 8)):
+            B = windows * K
+            feats = torch.randn((windows, CTX, WIDTH), generator=torch.Generator().manual_seed(windows)).cuda()
+
+            def begin_beam(beam, position):
+                prompt = torch.randint(0, 50000, (B, position), generator=torch.Generator().manual_seed(1), dtype=torch.int32).cuda()
+                rt.set_audio_groups(feats, K)
+                rt.pick_setup(params, bits)
+                if beam:
+                    rt.beam_setup(K, K)
+                else:
+                    rt.sample_setup(1.0, 0, np.arange(B))
+                rt.forward(prompt, False)
+                rt.pick()
+                a.position = position  # what step() rewinds to
+                step()  # (beam: one select has run, so the forward reads through a table that is no longer the identity)
+
+            def forward_only():
+                rt.rewind(a.position)
+                rt.step()
+
+            if a.only_steps:  # the profiler's run: the beam's steps and nothing else
+                begin_beam(True, a.position)
+                for _ in range(a.only_steps):
+                    step()
+                torch.cuda.synchronize()
+                return
+            position = a.position
+            emit(dict(case="state_bytes", windows=windows, K=K, rows=B, grouped=int(lib.kk_whisper_text_state_bytes_groups(rt._h, windows, K)),
+                      beam=int(lib.kk_whisper_text_beam_state_bytes(rt._h, windows, K, K))))
+            for beam in (False, True):
+                kind = dict(windows=windows, K=K, rows=B, pick="beam top-k + select" if beam else "sampled, temperature 1.0")
+                begin_beam(beam, position)
+                emit(dict(case="decode_step", position=position, **kind, **timed(step, a.inner)))
+                emit(dict(case="pick_only", **kind, **timed(rt.pick, a.inner)))
+            for keys in (32, 224, 448):  # the forward alone, alternating the two states at every key count
+                for beam in (False, True, False, True):
+                    begin_beam(beam, keys - 1)
+                    emit(dict(case="forward_only", keys=keys, windows=windows, K=K, rows=B, self_attention="owned" if beam else "direct", **timed(forward_only, a.inner)))
+            a.position = position
         write_out()
         return
 
