@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 23  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 24  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -67,7 +67,9 @@ extern "C" {
                                kk_debug_last_conv_epi, kk_debug_set_op_accumulate);
                             23: Whisper beam search on the device (kk_op_whisper_beam_topk, kk_op_whisper_beam_select, kk_op_whisper_beam_reset,
                                kk_op_whisper_attn_rows_owned, kk_whisper_beam_bufs, kk_whisper_text_beam_state_bytes, kk_whisper_text_beam_setup,
-                               kk_whisper_text_beam_not_complete, kk_whisper_text_beam_read) */
+                               kk_whisper_text_beam_not_complete, kk_whisper_text_beam_read);
+                            24: quantised Whisper checkpoints, decoder matrices packed in device memory (kk_whisper_text_load_quantized,
+                               kk_whisper_text_weight_info, kk_whisper_text_weight_fallback, kk_op_whisper_linear_rows_q, kk_op_whisper_embed_q) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -888,6 +890,17 @@ int kk_op_whisper_linear_rows(void* stream, int M, int N, int K, const float* x,
 /* out[r] = table[clamp(tok[r])] + positions[clamp(pos[r])]: table bf16 [n_vocab][D], positions fp32 [n_ctx][D], out fp32 [R][D] */
 int kk_op_whisper_embed(void* stream, int R, int D, const int32_t* tok, const int32_t* pos, const void* table_bf16, int n_vocab, const float* positions,
                         int n_ctx, float* out);
+/* kk_op_whisper_linear_rows on an MLX affine-quantised W: words uint32 [N][K bits / 32] as the checkpoint holds them (value i of a row
+ * in bits [(i % per) bits, ...) of word i / per, per = 32 / bits; 8-byte aligned), pairs float [N][K / group_size][2] = (scale, bias) of every row and
+ * group (8-byte aligned); bits 4 or 8, group_size 32, 64 or 128 dividing K.  Each value is decoded in registers to bf16_rne(fp32(q) * scale + bias)
+ * (fp32 multiply, fp32 add) and meets the kernel of kk_op_whisper_linear_rows from there on: the result carries the bits that entry gives on the
+ * bf16 rounding of the dequantised matrix.  The other arguments and their checks are that entry's. */
+int kk_op_whisper_linear_rows_q(void* stream, int M, int N, int K, const float* x, long long ldx, const uint32_t* words, const float* pairs, int group_size,
+                                int bits, const float* bias, int act, const float* res, long long ldr, float* out, long long ldo, void* out_bf16,
+                                long long ld_bf16, const int32_t* rows_bf16, int nrows_bf16);
+/* kk_op_whisper_embed from the quantised table [n_vocab][D] in the layout above (words 4-byte, pairs 8-byte aligned; group_size divides D) */
+int kk_op_whisper_embed_q(void* stream, int R, int D, const int32_t* tok, const int32_t* pos, const uint32_t* words, const float* pairs, int group_size,
+                          int bits, int n_vocab, const float* positions, int n_ctx, float* out);
 /* the token selection of one decode step (decoding.py:302-395 then :260-278 at temperature 0), one launch, no host round trip */
 typedef struct kk_whisper_pick_params {
   int32_t n_vocab, eot, blank;           /* blank: the token of " " (220), masked with eot at the first sampled position when suppress_blank */
@@ -928,9 +941,22 @@ int kk_whisper_text_create(const kk_whisper_text_config* cfg, kk_whisper_text** 
 void kk_whisper_text_destroy(kk_whisper_text* m);
 /* decoder.* parameters by their MLX checkpoint names, host fp32, Linear weights [out][in]; the keys have no bias */
 int kk_whisper_text_load_tensor(kk_whisper_text* m, const char* name, const int64_t* shape, int ndim, const float* data);
+/* a matrix of an MLX affine-quantised checkpoint (`{p}.weight` with `{p}.scales` / `{p}.biases`) instead of kk_whisper_text_load_tensor: shape
+ * [out][in] of the dequantised matrix, words uint32 [out][in bits / 32], scales / biases fp32 [out][in / group_size]; bits 2, 4 or 8.  What becomes of it
+ * is kk_whisper_text_finalize's decision, matrix by matrix. */
+int kk_whisper_text_load_quantized(kk_whisper_text* m, const char* name, const int64_t* shape, const uint32_t* words, const float* scales, const float* biases,
+                                   int group_size, int bits);
 /* rounds every matrix to bf16 (nearest even), one at a time, into ONE device copy (the token embedding serves the gather and the logits); the
- * learned positions, biases and LayerNorm parameters stay fp32.  Fails naming a missing or misshapen parameter.  Synchronises `stream`. */
+ * learned positions, biases and LayerNorm parameters stay fp32.  A quantised matrix stays PACKED -- its words as they are plus one
+ * (scale, bias) pair per row and group, decoded inside kk_op_whisper_linear_rows_q / embed_q's kernels -- if its bits are 4 or 8 and its group size is
+ * 32, 64 or 128 and divides its input width; any other one, and the two halves of the stacked cross key | value matrix (which set_audio runs on the
+ * bf16 conv kernel), are dequantised on the host by the checkpoint's rule, fp32(q) * scale + bias in two roundings, and become bf16 matrices.  Either
+ * way the decoder computes the bits it computes on the dequantised checkpoint.  Fails naming a missing or misshapen parameter.  Synchronises `stream`. */
 int kk_whisper_text_finalize(kk_whisper_text* m, void* stream);
+/* what finalize decided: device bytes of the matrices and of all weights, the count of packed and of bf16 matrices (the stacked cross key | value
+ * counts once), and how many quantised tensors were dequantised; kk_whisper_text_weight_fallback(m, i) is "name<TAB>reason" of the i-th of them */
+int kk_whisper_text_weight_info(const kk_whisper_text* m, size_t* matrix_bytes, size_t* total_bytes, int* n_packed, int* n_bf16, int* n_fallback);
+const char* kk_whisper_text_weight_fallback(const kk_whisper_text* m, int i);
 /* the caller's memory: one persistent state buffer per batch (cross and self K/V in bf16, the pick state and token buffers) and a workspace per call */
 size_t kk_whisper_text_state_bytes(const kk_whisper_text* m, int B);
 size_t kk_whisper_text_workspace_bytes(const kk_whisper_text* m, int B, int S);

@@ -260,6 +260,12 @@ SIGNATURES = {
     "kk_whisper_text_destroy": (None, [_vp]),
     "kk_whisper_text_load_tensor": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), _i, _vp]),
     "kk_whisper_text_finalize": (_i, [_vp, _vp]),
+    "kk_whisper_text_load_quantized": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), _vp, _vp, _vp, _i, _i]),
+    "kk_whisper_text_weight_info": (_i, [_vp, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "kk_whisper_text_weight_fallback": (C.c_char_p, [_vp, _i]),
+    "kk_op_whisper_linear_rows_q": (_i, [_vp, _i, _i, _i, _vp, C.c_longlong, _vp, _vp, _i, _i, _vp, _i, _vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong,
+                                        _vp, _i]),
+    "kk_op_whisper_embed_q": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "kk_whisper_text_state_bytes": (_sz, [_vp, _i]),
     "kk_whisper_text_workspace_bytes": (_sz, [_vp, _i, _i]),
     "kk_whisper_text_set_audio": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _sz]),
@@ -347,7 +353,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 23:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 24:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

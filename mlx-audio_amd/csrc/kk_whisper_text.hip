@@ -222,6 +222,28 @@ struct LinRows {
 
 constexpr int LIN_WAVES = 16;  // waves of a workgroup = slices of K, summed in wave order
 
+// the end of a linear_rows workgroup (bf16 and quantised weights alike): the waves' partial tiles are added in wave order, then bias, GELU, residual
+// and the fp32 / bf16 stores.  acc: the wave's D[m = 4 g + r][n = lr]
+__device__ __forceinline__ void lin_finish(const LinRows& a, float (&red)[LIN_WAVES][16][17], const f32x4 acc, int n0) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, g = lane >> 4;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) red[wave][4 * g + r][lr] = acc[r];
+  __syncthreads();
+  const int m = tid >> 4, c = tid & 15, n = n0 + c;
+  if (tid >= 256 || m >= a.M || n >= a.N) return;
+  float v = red[0][m][c];
+#pragma unroll
+  for (int w = 1; w < LIN_WAVES; ++w) v += red[w][m][c];
+  if (a.bias) v += a.bias[n];
+  if (a.act == KK_ACT_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
+  if (a.res) v += a.res[(long long)m * a.ldr + n];
+  if (a.out) a.out[(long long)m * a.ldo + n] = v;
+  if (a.ob) {
+    const int row = a.rows ? a.rows[m] : m;
+    if (row >= 0 && row < a.nrows) a.ob[(long long)row * a.ldb + n] = (bf16_t)v;
+  }
+}
+
 __global__ __launch_bounds__(64 * LIN_WAVES) void linear_rows_kernel(LinRows a) {
   __shared__ float red[LIN_WAVES][16][17];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, g = lane >> 4;
@@ -251,26 +273,110 @@ __global__ __launch_bounds__(64 * LIN_WAVES) void linear_rows_kernel(LinRows a) 
     const float4 a0 = *(const float4*)(xp + i * STEP), a1 = *(const float4*)(xp + i * STEP + 4);
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(a0, a1), w0, acc, 0, 0, 0);
   }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) red[wave][4 * g + r][lr] = acc[r];
-  __syncthreads();
-  const int m = tid >> 4, c = tid & 15, n = n0 + c;
-  if (tid >= 256 || m >= a.M || n >= a.N) return;
-  float v = red[0][m][c];
-#pragma unroll
-  for (int w = 1; w < LIN_WAVES; ++w) v += red[w][m][c];
-  if (a.bias) v += a.bias[n];
-  if (a.act == KK_ACT_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
-  if (a.res) v += a.res[(long long)m * a.ldr + n];
-  if (a.out) a.out[(long long)m * a.ldo + n] = v;
-  if (a.ob) {
-    const int row = a.rows ? a.rows[m] : m;
-    if (row >= 0 && row < a.nrows) a.ob[(long long)row * a.ldb + n] = (bf16_t)v;
-  }
+  lin_finish(a, red, acc, n0);
 }
 
 int launch_linear_rows(hipStream_t st, const LinRows& a) {
   hipLaunchKernelGGL(linear_rows_kernel, dim3((a.N + 15) / 16), dim3(64 * LIN_WAVES), 0, st, a);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- linear_rows_q: the same Linear on the integers of an MLX affine-quantised matrix ------------------------------------------------
+//   W is `words` uint32 [N][K bits / 32] (value i of a row in bits [(i % per) bits, ...) of word i / per, per = 32 / bits: the checkpoint's own
+//   tensor) and `pairs` float2 [N][K / group] = (scale, bias) of the row's groups.  Row-major packing IS the fragment order along k, as for the
+//   bf16 matrix: lane (lr, g) of k-step ks needs values 32 ks + 8 g .. + 7 of row n0 + lr, which are 8 bytes (BITS 8: a row is K / 4 words, the
+//   lane's two at 8 ks + 2 g) or 4 bytes (BITS 4: K / 8 words, the lane's one at 4 ks + g), all in group 32 ks / group (group % 32 == 0).  Each
+//   value becomes  bf16_rne(fp32(q) * scale + bias)  -- fp32 multiply, fp32 add, no contraction (wf_decode of kk_csm_gemvm.h) -- which is bit
+//   for bit the element the bf16 copy of the dequantised matrix holds.  Everything else is linear_rows_kernel: the grid, the waves' k-steps, the
+//   order of a wave's MFMAs, the reduction in wave order, the clamped tail row, the epilogue.  So the result carries the bf16 kernel's bits.
+//   Two k-steps' words, pairs and x are requested before the first is decoded, as in the bf16 kernel.  The loads are narrower (4 or 8 bytes a lane
+//   and step, plus the pair), but deeper did not pay: at width 1280 a wave has 2 or 3 k-steps, and what the launch adds over its bf16 twin is the
+//   decode's vector arithmetic, not bytes in flight (DESIGN 8l has the figures).
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+template <int BITS> struct QWord;
+template <> struct QWord<8> { typedef u32x2 T; };
+template <> struct QWord<4> { typedef unsigned T; };
+__device__ __forceinline__ __bf16 q_value(unsigned q, float2 sb) { return (__bf16)__fadd_rn(__fmul_rn((float)q, sb.x), sb.y); }
+__device__ __forceinline__ bf16x8 q_decode(u32x2 q, float2 sb) {
+  bf16x8 v;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = q_value((q[j >> 2] >> (8 * (j & 3))) & 0xffu, sb);
+  return v;
+}
+__device__ __forceinline__ bf16x8 q_decode(unsigned q, float2 sb) {
+  bf16x8 v;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = q_value((q >> (4 * j)) & 0xfu, sb);
+  return v;
+}
+
+struct LinQ {
+  const uint32_t* words;
+  const float2* pairs;
+  int gshift;  // log2(group / 32): k-step ks lies in group ks >> gshift
+};
+
+template <int BITS>
+__global__ __launch_bounds__(64 * LIN_WAVES) void linear_rows_q_kernel(LinRows a, LinQ q) {
+  typedef typename QWord<BITS>::T WQ;
+  constexpr int WPS = BITS / 4;  // words of a lane per k-step
+  constexpr int DEPTH = 2;       // k-steps in flight, as in the bf16 kernel (measured against 3 and 4)
+  __shared__ float red[LIN_WAVES][16][17];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, g = lane >> 4;
+  const int n0 = blockIdx.x * 16, nsteps = a.K >> 5;
+  const int nrow = n0 + lr < a.N ? n0 + lr : a.N - 1;  // the tail's columns read the last row; they are not stored
+  const WQ* wp = (const WQ*)(q.words + (long long)nrow * (a.K / 32 * BITS)) + 4 * wave + g;  // k-step ks of the row: 4 ks + g, in units of WQ
+  const float2* pp = q.pairs + (long long)nrow * (nsteps >> q.gshift);
+  const bool mvalid = lr < a.M;
+  const float* xp = a.x + (long long)(mvalid ? lr : 0) * a.ldx + 8 * g + wave * 32;
+  const bf16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  auto frag = [&](const float4& a0, const float4& a1) __attribute__((always_inline)) {
+    const bf16x8 xf = {(bf16_t)a0.x, (bf16_t)a0.y, (bf16_t)a0.z, (bf16_t)a0.w, (bf16_t)a1.x, (bf16_t)a1.y, (bf16_t)a1.z, (bf16_t)a1.w};
+    return mvalid ? xf : zero;
+  };
+  const int mine = wave < nsteps ? (nsteps - wave + LIN_WAVES - 1) / LIN_WAVES : 0;  // k-steps wave, wave + LIN_WAVES, ...
+  constexpr int STEP = 32 * LIN_WAVES, WSTEP = 4 * LIN_WAVES;
+  static_assert(sizeof(WQ) == 4 * WPS, "a lane's share of a k-step");
+  int i = 0;
+  for (; i + DEPTH <= mine; i += DEPTH) {
+    WQ w[DEPTH];
+    float2 sb[DEPTH];
+    float4 x0[DEPTH], x1[DEPTH];
+#pragma unroll
+    for (int u = 0; u < DEPTH; ++u) {
+      w[u] = wp[(i + u) * WSTEP];
+      sb[u] = pp[(wave + (i + u) * LIN_WAVES) >> q.gshift];
+      x0[u] = *(const float4*)(xp + (i + u) * STEP);
+      x1[u] = *(const float4*)(xp + (i + u) * STEP + 4);
+    }
+#pragma unroll
+    for (int u = 0; u < DEPTH; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(x0[u], x1[u]), q_decode(w[u], sb[u]), acc, 0, 0, 0);  // in k order, as the bf16 kernel
+  }
+  for (; i < mine; ++i) {
+    const WQ w = wp[i * WSTEP];
+    const float2 sb = pp[(wave + i * LIN_WAVES) >> q.gshift];
+    const float4 a0 = *(const float4*)(xp + i * STEP), a1 = *(const float4*)(xp + i * STEP + 4);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(a0, a1), q_decode(w, sb), acc, 0, 0, 0);
+  }
+  lin_finish(a, red, acc, n0);
+}
+
+inline int q_gshift(int group) { return group == 32 ? 0 : (group == 64 ? 1 : 2); }
+// why a quantised [N][K] matrix cannot stay packed, or null: the formats linear_rows_q / embed_q read
+const char* q_refusal(int K, int group, int bits) {
+  if (bits != 4 && bits != 8) return "bits is not 4 or 8";
+  if (group != 32 && group != 64 && group != 128) return "group size is not 32, 64 or 128";
+  if (K < group || K % group != 0) return "the input width is not a multiple of the group size";
+  return nullptr;
+}
+
+// (a.w is not read)
+int launch_linear_rows_q(hipStream_t st, const LinRows& a, const uint32_t* words, const float2* pairs, int group, int bits) {
+  const LinQ q{words, pairs, q_gshift(group)};
+  if (bits == 8) hipLaunchKernelGGL(linear_rows_q_kernel<8>, dim3((a.N + 15) / 16), dim3(64 * LIN_WAVES), 0, st, a, q);
+  else hipLaunchKernelGGL(linear_rows_q_kernel<4>, dim3((a.N + 15) / 16), dim3(64 * LIN_WAVES), 0, st, a, q);
   KK_CHECK_LAUNCH();
   return 0;
 }
@@ -285,6 +391,30 @@ __global__ __launch_bounds__(256) void embed_kernel(const int* tok, const int* p
   const bf16_t* e = table + (long long)t * D;
   const float* pe = positions + (long long)p * D;
   for (int c = threadIdx.x; c < D; c += 256) out[(long long)r * D + c] = (float)e[c] + pe[c];
+}
+
+// the same gather from the quantised table (the layout of linear_rows_q): the row's values are decoded to the bf16 the dequantised table would hold
+template <int BITS>
+__global__ __launch_bounds__(256) void embed_q_kernel(const int* tok, const int* pos, const uint32_t* words, const float2* pairs, int group, int n_vocab,
+                                                      const float* positions, int n_ctx, int D, float* out) {
+  constexpr int PER = 32 / BITS;
+  const int r = blockIdx.x;
+  int t = tok[r], p = pos[r];
+  t = t < 0 ? 0 : (t >= n_vocab ? n_vocab - 1 : t);  // a bad id reads a row of the table, never past it
+  p = p < 0 ? 0 : (p >= n_ctx ? n_ctx - 1 : p);
+  const uint32_t* e = words + (long long)t * (D / PER);
+  const float2* sb = pairs + (long long)t * (D / group);
+  const float* pe = positions + (long long)p * D;
+  for (int c = threadIdx.x; c < D; c += 256)
+    out[(long long)r * D + c] = (float)q_value((e[c / PER] >> (BITS * (c % PER))) & ((1u << BITS) - 1u), sb[c / group]) + pe[c];
+}
+
+int launch_embed_q(hipStream_t st, int R, int D, const int* tok, const int* pos, const uint32_t* words, const float2* pairs, int group, int bits, int n_vocab,
+                   const float* positions, int n_ctx, float* out) {
+  if (bits == 8) hipLaunchKernelGGL(embed_q_kernel<8>, dim3(R), dim3(256), 0, st, tok, pos, words, pairs, group, n_vocab, positions, n_ctx, D, out);
+  else hipLaunchKernelGGL(embed_q_kernel<4>, dim3(R), dim3(256), 0, st, tok, pos, words, pairs, group, n_vocab, positions, n_ctx, D, out);
+  KK_CHECK_LAUNCH();
+  return 0;
 }
 
 // --------------------------------------------------------------------------------------------------------------------------------- pick
@@ -818,6 +948,30 @@ extern "C" int kk_op_whisper_embed(void* stream, int R, int D, const int32_t* to
   return 0;
 }
 
+extern "C" int kk_op_whisper_linear_rows_q(void* stream, int M, int N, int K, const float* x, long long ldx, const uint32_t* words, const float* pairs,
+                                           int group_size, int bits, const float* bias, int act, const float* res, long long ldr, float* out, long long ldo,
+                                           void* out_bf16, long long ld_bf16, const int32_t* rows_bf16, int nrows_bf16) {
+  if (!x || !words || !pairs || (!out && !out_bf16)) return kk_fail("kk_op_whisper_linear_rows_q: null argument");
+  if (M < 1 || M > 16) return kk_fail("kk_op_whisper_linear_rows_q: 1 <= M <= 16 rows per call");
+  if (N < 1 || K < 32 || K % 32 != 0) return kk_fail("kk_op_whisper_linear_rows_q: N >= 1 and K a multiple of 32");
+  if (const char* why = q_refusal(K, group_size, bits)) return kk_failf("kk_op_whisper_linear_rows_q: %s (bits 4 or 8, group size 32, 64 or 128 dividing K)", why);
+  if (act != KK_ACT_NONE && act != KK_ACT_GELU) return kk_fail("kk_op_whisper_linear_rows_q: act must be none (0) or GELU (2)");
+  if (ldx < K || ldx % 4 != 0 || ((uintptr_t)x & 15) || ((uintptr_t)words & 7) || ((uintptr_t)pairs & 7))
+    return kk_fail("kk_op_whisper_linear_rows_q: x must be 16-byte, words and pairs 8-byte aligned, ldx >= K, ldx % 4 == 0");
+  if ((out && ldo < N) || (res && ldr < N) || (out_bf16 && (ld_bf16 < N || nrows_bf16 < 1))) return kk_fail("kk_op_whisper_linear_rows_q: a row pitch is smaller than N");
+  LinRows a{x, ldx, nullptr, bias, res, ldr, out, ldo, (bf16_t*)out_bf16, ld_bf16, rows_bf16, nrows_bf16, M, N, K, act};
+  return launch_linear_rows_q((hipStream_t)stream, a, words, (const float2*)pairs, group_size, bits);
+}
+
+extern "C" int kk_op_whisper_embed_q(void* stream, int R, int D, const int32_t* tok, const int32_t* pos, const uint32_t* words, const float* pairs, int group_size,
+                                     int bits, int n_vocab, const float* positions, int n_ctx, float* out) {
+  if (!tok || !pos || !words || !pairs || !positions || !out) return kk_fail("kk_op_whisper_embed_q: null argument");
+  if (R < 1 || D < 1 || n_vocab < 1 || n_ctx < 1) return kk_fail("kk_op_whisper_embed_q: bad argument");
+  if (const char* why = q_refusal(D, group_size, bits)) return kk_failf("kk_op_whisper_embed_q: %s (bits 4 or 8, group size 32, 64 or 128 dividing D)", why);
+  if (((uintptr_t)words & 3) || ((uintptr_t)pairs & 7)) return kk_fail("kk_op_whisper_embed_q: words must be 4-byte and pairs 8-byte aligned");
+  return launch_embed_q((hipStream_t)stream, R, D, tok, pos, words, (const float2*)pairs, group_size, bits, n_vocab, positions, n_ctx, out);
+}
+
 extern "C" int kk_op_whisper_pick(void* stream, int B, const float* logits, long long ldl, const kk_whisper_pick_params* params, const uint32_t* suppress,
                                   kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next, int32_t* not_ended) {
   if (!logits || !params || !state || !tokens || !next || !not_ended) return kk_fail("kk_op_whisper_pick: null argument");
@@ -892,10 +1046,17 @@ extern "C" int kk_op_whisper_beam_select(void* stream, const kk_whisper_beam_buf
 }
 
 // ================================================================================================================================ the handle
-struct TLin {  // a Linear: bf16 [N][K] dense at `w` of wdev, fp32 bias [N] at `b` of fdev
-  size_t w = 0, b = 0;
-  int N = 0, K = 0;
+enum { TW_BF16 = 0, TW_Q8 = 8, TW_Q4 = 4 };  // a matrix's storage; the packed ones by their bits
+struct TLin {  // a Linear: bf16 [N][K] dense at `w` of wdev, or (fmt != TW_BF16) the checkpoint's words at `qw` of qdev with its (scale, bias)
+               // pairs at `qp` of pdev, quantised in groups of `group`; fp32 bias [N] at `b` of fdev
+  size_t w = 0, b = 0, qw = 0, qp = 0;
+  int N = 0, K = 0, fmt = TW_BF16, group = 0;
   bool bias = false;
+};
+struct TQHost {  // a quantised matrix as the checkpoint holds it (kk_whisper_text_load_quantized)
+  int O = 0, I = 0, group = 0, bits = 0;
+  std::vector<uint32_t> words;
+  std::vector<float> scales, biases;
 };
 struct TLayer {
   TLin q, k, v, out, cq, ckv, cout, mlp1, mlp2;
@@ -905,8 +1066,14 @@ struct TLayer {
 struct kk_whisper_text {
   kk_whisper_text_config cfg;
   std::map<std::string, HostTensor> host;
+  std::map<std::string, TQHost> qhost;
   bool finalized = false;
-  bf16_t* wdev = nullptr;  // every matrix, once: the blocks' Linears and the token embedding [V][D]
+  bf16_t* wdev = nullptr;  // every bf16 matrix, once: the blocks' Linears and the token embedding [V][D]
+  uint32_t* qdev = nullptr;  // the packed matrices' words
+  float2* pdev = nullptr;    // and their (scale, bias) pairs
+  size_t matrix_bytes = 0, total_bytes = 0;  // device bytes of the matrices / of every weight
+  int n_packed = 0, n_bf16 = 0;
+  std::vector<std::string> fallbacks;  // "name\treason" of every quantised matrix that was dequantised into a bf16 one
   float* fdev = nullptr;   // biases, LayerNorm parameters, the learned positions
   TLin emb;
   std::vector<TLayer> layers;
@@ -1028,6 +1195,8 @@ extern "C" int kk_whisper_text_create(const kk_whisper_text_config* cfg, kk_whis
 extern "C" void kk_whisper_text_destroy(kk_whisper_text* m) {
   if (!m) return;
   if (m->wdev) (void)hipFree(m->wdev);
+  if (m->qdev) (void)hipFree(m->qdev);
+  if (m->pdev) (void)hipFree(m->pdev);
   if (m->fdev) (void)hipFree(m->fdev);
   delete m;
 }
@@ -1040,8 +1209,42 @@ extern "C" int kk_whisper_text_load_tensor(kk_whisper_text* m, const char* name,
   HostTensor& t = m->host[name];
   t.d.assign(data, data + n);
   t.shape.assign(shape, shape + ndim);
+  m->qhost.erase(name);
   return 0;
 }
+
+extern "C" int kk_whisper_text_load_quantized(kk_whisper_text* m, const char* name, const int64_t* shape, const uint32_t* words, const float* scales,
+                                              const float* biases, int group_size, int bits) {
+  if (!m || !name || !shape || !words || !scales || !biases) return kk_fail("kk_whisper_text_load_quantized: bad argument");
+  if (m->finalized) return kk_fail("kk_whisper_text_load_quantized: model already finalized");
+  if (bits != 2 && bits != 4 && bits != 8)
+    return kk_fail("kk_whisper_text_load_quantized: bits must be 2, 4 or 8 (values of a word in bits [j bits, (j + 1) bits))");
+  const int64_t O = shape[0], I = shape[1];
+  if (O < 1 || I < 1 || O > (1 << 30) || I > (1 << 30) || group_size < 1 || I % group_size != 0 || (I * bits) % 32 != 0)
+    return kk_failf("kk_whisper_text_load_quantized: %s: shape / group size", name);
+  TQHost& t = m->qhost[name];
+  t.O = (int)O; t.I = (int)I; t.group = group_size; t.bits = bits;
+  t.words.assign(words, words + (size_t)O * (size_t)(I * bits / 32));
+  t.scales.assign(scales, scales + (size_t)O * (size_t)(I / group_size));
+  t.biases.assign(biases, biases + (size_t)O * (size_t)(I / group_size));
+  m->host.erase(name);
+  return 0;
+}
+
+namespace {
+// the checkpoint's own arithmetic on the host: w = fp32(q) * scale + bias, two roundings (quant.dequantize_affine; dequantize_host of kk_csm.hip)
+void text_dequantize(const TQHost& t, std::vector<float>& out) {
+  const int per = 32 / t.bits, wpr = t.I / per, ngrp = t.I / t.group;
+  const uint32_t mask = (1u << t.bits) - 1u;
+  out.resize((size_t)t.O * t.I);
+  for (int o = 0; o < t.O; ++o)
+    for (int i = 0; i < t.I; ++i) {
+      const float qf = (float)((t.words[(size_t)o * wpr + i / per] >> ((i % per) * t.bits)) & mask);
+      volatile float prod = qf * t.scales[(size_t)o * ngrp + i / t.group];  // (rounded to fp32 before the add whatever the compiler's contraction rule)
+      out[(size_t)o * t.I + i] = prod + t.biases[(size_t)o * ngrp + i / t.group];
+    }
+}
+}  // namespace
 
 extern "C" int kk_whisper_text_finalize(kk_whisper_text* m, void* stream) {
   if (!m) return kk_fail("kk_whisper_text_finalize: null model");
@@ -1049,21 +1252,43 @@ extern "C" int kk_whisper_text_finalize(kk_whisper_text* m, void* stream) {
   const kk_whisper_text_config& c = m->cfg;
   const int D = c.n_text_state, V = c.n_vocab;
   hipStream_t st = (hipStream_t)stream;
-  size_t wn = 0, fn = 0;
-  auto plan = [&](TLin& l, int N, int K, bool bias) {
-    l.N = N; l.K = K; l.bias = bias;
-    l.w = wn; wn += ((size_t)N * K + 63) & ~(size_t)63;
+  size_t wn = 0, fn = 0, qn = 0, pn = 0;
+  m->n_packed = m->n_bf16 = 0;
+  m->fallbacks.clear();
+  // `qname`: the one tensor this matrix is made of, which decides its storage if it arrived quantised (empty: a stacked matrix, always bf16)
+  auto plan = [&](TLin& l, int N, int K, bool bias, const std::string& qname) {
+    l.N = N; l.K = K; l.bias = bias; l.fmt = TW_BF16;
+    const auto it = qname.empty() ? m->qhost.end() : m->qhost.find(qname);
+    if (it != m->qhost.end() && it->second.O == N && it->second.I == K) {  // (a misshapen one is refused below)
+      const TQHost& t = it->second;
+      if (const char* why = q_refusal(K, t.group, t.bits)) {
+        m->fallbacks.push_back(qname + "\t" + why);
+      } else {
+        l.fmt = t.bits; l.group = t.group;
+        l.qw = qn; qn += ((size_t)N * (K / 32 * t.bits) + 63) & ~(size_t)63;
+        l.qp = pn; pn += ((size_t)N * (K / t.group) + 63) & ~(size_t)63;
+      }
+    }
+    if (l.fmt == TW_BF16) { l.w = wn; wn += ((size_t)N * K + 63) & ~(size_t)63; }
+    ++(l.fmt == TW_BF16 ? m->n_bf16 : m->n_packed);
     if (bias) { l.b = fn; fn += ((size_t)N + 63) & ~(size_t)63; }
   };
   auto planv = [&](size_t& off, size_t n) { off = fn; fn += (n + 63) & ~(size_t)63; };
   m->layers.resize(c.n_text_layer);
-  for (auto& L : m->layers) {
-    plan(L.q, D, D, true); plan(L.k, D, D, false); plan(L.v, D, D, true); plan(L.out, D, D, true);
-    plan(L.cq, D, D, true); plan(L.ckv, 2 * D, D, true); plan(L.cout, D, D, true);  // cross key | value as ONE [2 D][D] Linear (the key's half of the bias is zero)
-    plan(L.mlp1, 4 * D, D, true); plan(L.mlp2, D, 4 * D, true);
+  for (int li = 0; li < c.n_text_layer; ++li) {
+    TLayer& L = m->layers[li];
+    const std::string p = "decoder.blocks." + std::to_string(li) + ".";
+    plan(L.q, D, D, true, p + "attn.query.weight"); plan(L.k, D, D, false, p + "attn.key.weight"); plan(L.v, D, D, true, p + "attn.value.weight");
+    plan(L.out, D, D, true, p + "attn.out.weight"); plan(L.cq, D, D, true, p + "cross_attn.query.weight");
+    // cross key | value as ONE [2 D][D] Linear (the key's half of the bias is zero); set_audio runs it on the bf16 conv kernel, so it is always bf16
+    plan(L.ckv, 2 * D, D, true, "");
+    for (const char* part : {"cross_attn.key.weight", "cross_attn.value.weight"})
+      if (m->qhost.count(p + part)) m->fallbacks.push_back(p + part + "\tthe stacked cross key | value matrix feeds the bf16 conv kernel");
+    plan(L.cout, D, D, true, p + "cross_attn.out.weight");
+    plan(L.mlp1, 4 * D, D, true, p + "mlp1.weight"); plan(L.mlp2, D, 4 * D, true, p + "mlp2.weight");
     planv(L.attn_ln_w, D); planv(L.attn_ln_b, D); planv(L.cross_ln_w, D); planv(L.cross_ln_b, D); planv(L.mlp_ln_w, D); planv(L.mlp_ln_b, D);
   }
-  plan(m->emb, V, D, false);
+  plan(m->emb, V, D, false, "decoder.token_embedding.weight");
   planv(m->ln_w, D); planv(m->ln_b, D);
   planv(m->pos, (size_t)c.n_text_ctx * D);
 
@@ -1087,8 +1312,13 @@ extern "C" int kk_whisper_text_finalize(kk_whisper_text* m, void* stream) {
   };
   struct Job { const TLin* l; std::string name; int row0, N; };
   std::vector<Job> jobs;
+  auto needw = [&](const std::string& name, int N, int K) {  // a matrix: as floats, or quantised
+    const auto it = m->qhost.find(name);
+    if (it == m->qhost.end()) need(name, {N, K});
+    else if ((it->second.O != N || it->second.I != K) && err.empty()) err = "unexpected shape for " + name;
+  };
   auto lin = [&](const TLin& l, const std::string& p, int row0, int N, bool bias) {
-    need(p + ".weight", {N, l.K});
+    needw(p + ".weight", N, l.K);
     if (bias) vecp(l.b + row0, p + ".bias", N);
     jobs.push_back(Job{&l, p + ".weight", row0, N});
   };
@@ -1103,31 +1333,63 @@ extern "C" int kk_whisper_text_finalize(kk_whisper_text* m, void* stream) {
     vecp(L.cross_ln_w, p + "cross_attn_ln.weight", D); vecp(L.cross_ln_b, p + "cross_attn_ln.bias", D);
     vecp(L.mlp_ln_w, p + "mlp_ln.weight", D); vecp(L.mlp_ln_b, p + "mlp_ln.bias", D);
   }
-  need("decoder.token_embedding.weight", {V, D});
+  needw("decoder.token_embedding.weight", V, D);
   jobs.push_back(Job{&m->emb, "decoder.token_embedding.weight", 0, V});
   vecp(m->ln_w, "decoder.ln.weight", D); vecp(m->ln_b, "decoder.ln.bias", D);
   if (const HostTensor* t = need("decoder.positional_embedding", {c.n_text_ctx, D})) memcpy(&fpack[m->pos], t->d.data(), t->d.size() * 4);
   if (!err.empty()) return kk_failf("kk_whisper_text_finalize: %s", err.c_str());
 
-  if (hipMalloc((void**)&m->wdev, wn * sizeof(bf16_t)) != hipSuccess || hipMalloc((void**)&m->fdev, fn * sizeof(float)) != hipSuccess)
+  if (hipMalloc((void**)&m->wdev, wn * sizeof(bf16_t)) != hipSuccess || hipMalloc((void**)&m->fdev, fn * sizeof(float)) != hipSuccess ||
+      (qn && (hipMalloc((void**)&m->qdev, qn * sizeof(uint32_t)) != hipSuccess || hipMalloc((void**)&m->pdev, pn * sizeof(float2)) != hipSuccess)))
     return kk_fail("kk_whisper_text_finalize: hipMalloc failed");
-  // one matrix at a time: round to nearest even, copy, drop the host copy -- a large checkpoint is never held twice
+  m->matrix_bytes = wn * sizeof(bf16_t) + qn * sizeof(uint32_t) + pn * sizeof(float2);
+  m->total_bytes = m->matrix_bytes + fn * sizeof(float);
+  // one matrix at a time, and its host copy dropped -- a large checkpoint is never held twice.  A packed matrix: the checkpoint's words as they are and
+  // its scales and biases interleaved.  A bf16 one: dequantised first if it arrived quantised, then rounded to nearest even.
   std::vector<uint16_t> wpack;
+  std::vector<float> deq, pairs;
   for (const Job& j : jobs) {
-    HostTensor& t = m->host[j.name];
-    const size_t n = (size_t)j.N * j.l->K;
-    wpack.resize(n);
-    for (size_t i = 0; i < n; ++i) wpack[i] = f32_to_bf16_rne(t.d[i]);
-    if (hipMemcpyAsync((uint16_t*)m->wdev + j.l->w + (size_t)j.row0 * j.l->K, wpack.data(), n * 2, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-      return kk_fail("kk_whisper_text_finalize: upload failed");
+    const auto qi = m->qhost.find(j.name);
+    bool ok = true;
+    if (j.l->fmt != TW_BF16) {
+      const TQHost& t = qi->second;
+      const size_t np = t.scales.size();
+      pairs.resize(2 * np);
+      for (size_t i = 0; i < np; ++i) { pairs[2 * i] = t.scales[i]; pairs[2 * i + 1] = t.biases[i]; }
+      ok = hipMemcpyAsync(m->qdev + j.l->qw, t.words.data(), t.words.size() * 4, hipMemcpyHostToDevice, st) == hipSuccess &&
+           hipMemcpyAsync(m->pdev + j.l->qp, pairs.data(), np * sizeof(float2), hipMemcpyHostToDevice, st) == hipSuccess;
+    } else {
+      if (qi != m->qhost.end()) text_dequantize(qi->second, deq);
+      const float* src = qi != m->qhost.end() ? deq.data() : m->host[j.name].d.data();
+      const size_t n = (size_t)j.N * j.l->K;
+      wpack.resize(n);
+      for (size_t i = 0; i < n; ++i) wpack[i] = f32_to_bf16_rne(src[i]);
+      ok = hipMemcpyAsync((uint16_t*)m->wdev + j.l->w + (size_t)j.row0 * j.l->K, wpack.data(), n * 2, hipMemcpyHostToDevice, st) == hipSuccess;
+    }
+    if (!ok || hipStreamSynchronize(st) != hipSuccess) return kk_fail("kk_whisper_text_finalize: upload failed");
     m->host.erase(j.name);
+    m->qhost.erase(j.name);
   }
   if (hipMemcpyAsync(m->fdev, fpack.data(), fn * 4, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
     return kk_fail("kk_whisper_text_finalize: upload failed");
   m->host.clear();
+  m->qhost.clear();
   m->finalized = true;
   return 0;
+}
+
+extern "C" int kk_whisper_text_weight_info(const kk_whisper_text* m, size_t* matrix_bytes, size_t* total_bytes, int* n_packed, int* n_bf16, int* n_fallback) {
+  if (!m || !m->finalized) return kk_fail("kk_whisper_text_weight_info: needs a finalized model");
+  if (matrix_bytes) *matrix_bytes = m->matrix_bytes;
+  if (total_bytes) *total_bytes = m->total_bytes;
+  if (n_packed) *n_packed = m->n_packed;
+  if (n_bf16) *n_bf16 = m->n_bf16;
+  if (n_fallback) *n_fallback = (int)m->fallbacks.size();
+  return 0;
+}
+
+extern "C" const char* kk_whisper_text_weight_fallback(const kk_whisper_text* m, int i) {
+  return m && i >= 0 && i < (int)m->fallbacks.size() ? m->fallbacks[i].c_str() : "";
 }
 
 extern "C" size_t kk_whisper_text_state_bytes_groups(const kk_whisper_text* m, int n_audio, int n_group) {
@@ -1238,7 +1500,12 @@ struct TextPass {
       LinRows a{x + (long long)r0 * ldx, ldx, m->wdev + l.w + (size_t)n0 * l.K, l.bias ? m->fdev + l.b + n0 : nullptr, res ? res + (long long)r0 * ldo : nullptr, ldo,
                 out ? out + (long long)r0 * ldo : nullptr, ldo, ob, 2 * D, dst ? dst + r0 : nullptr, items * m->cfg.n_text_ctx, rows - r0 < 16 ? rows - r0 : 16, N, l.K,
                 act};
-      KK_TRY(launch_linear_rows(st, a));
+      if (l.fmt == TW_BF16) {
+        KK_TRY(launch_linear_rows(st, a));
+      } else {  // the matrix stayed packed: the same product, the B fragments decoded in registers
+        a.w = nullptr;
+        KK_TRY(launch_linear_rows_q(st, a, m->qdev + l.qw + (size_t)n0 * (l.K / 32 * l.fmt), m->pdev + l.qp + (size_t)n0 * (l.K / l.group), l.group, l.fmt));
+      }
     }
     return 0;
   }
@@ -1292,6 +1559,16 @@ struct TextPass {
     }
     return 0;
   }
+  // token + position of `R` rows into p.x, from the bf16 table or the packed one
+  int embed(int R, const int32_t* tok, const int* posr) const {
+    const kk_whisper_text_config& c = m->cfg;
+    const TLin& e = m->emb;
+    if (e.fmt != TW_BF16)
+      return launch_embed_q(st, R, c.n_text_state, tok, posr, m->qdev + e.qw, m->pdev + e.qp, e.group, e.fmt, c.n_vocab, m->fdev + m->pos, c.n_text_ctx, p.x);
+    hipLaunchKernelGGL(embed_kernel, dim3(R), dim3(256), 0, st, tok, posr, m->wdev + e.w, c.n_vocab, m->fdev + m->pos, c.n_text_ctx, c.n_text_state, p.x);
+    KK_CHECK_LAUNCH();
+    return 0;
+  }
   // decoder.ln and the tied embedding as the output Linear (whisper.py:247-248) on `rows` rows of x at pitch ldx
   int logits(const float* x, long long ldx, int rows, float* out) const {
     const int D = m->cfg.n_text_state, V = m->cfg.n_vocab;
@@ -1335,10 +1612,8 @@ int text_forward(const char* who, kk_whisper_text* m, void* stream, int B, int S
   hipLaunchKernelGGL(text_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, st, B, S, m->at, c.n_text_ctx, c.n_audio_ctx, m->n_group, p.item, item_cross, p.posr,
                      p.len_self, p.len_cross, p.cache_row);
   KK_CHECK_LAUNCH();
-  hipLaunchKernelGGL(embed_kernel, dim3(R), dim3(256), 0, st, tokens, p.posr, m->wdev + m->emb.w, V, m->fdev + m->pos, c.n_text_ctx, D, p.x);
-  KK_CHECK_LAUNCH();
-
   const TextPass run{m, st, B, m->n_audio, s.self, s.cross, item_cross ? item_cross : p.item, p, owner};
+  KK_TRY(run.embed(R, tokens, p.posr));
   KK_TRY(run.layers(R, cap, B, S));
   if (all_positions) {
     KK_TRY(run.logits(p.x, D, R, logits_out));
@@ -1750,9 +2025,8 @@ extern "C" int kk_whisper_text_rows_forward(kk_whisper_text* m, void* stream, co
   hipLaunchKernelGGL(text_plan_kernel, dim3(((int)R + 255) / 256), dim3(256), 0, st, t, (int)R, c.n_text_ctx, c.n_audio_ctx, s.init, s.next, p.t.item, p.t.posr,
                      p.t.len_self, p.t.len_cross, p.t.cache_row, p.tok);
   KK_CHECK_LAUNCH();
-  hipLaunchKernelGGL(embed_kernel, dim3((int)R), dim3(256), 0, st, p.tok, p.t.posr, m->wdev + m->emb.w, V, m->fdev + m->pos, c.n_text_ctx, D, p.t.x);
-  KK_CHECK_LAUNCH();
   const TextPass run{m, st, N, N, s.self, s.cross, p.t.item, p.t};
+  KK_TRY(run.embed((int)R, p.tok, p.t.posr));
   KK_TRY(run.layers((int)R, nullptr, 0, 0));
   const float* x = p.t.x;
   if (!identity) {  // a round of steps wants every row: nothing to gather

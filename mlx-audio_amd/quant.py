@@ -105,6 +105,44 @@ def csm_quantised_layer_names(weights: Dict[str, np.ndarray], group_size: int = 
     return names
 
 
+def whisper_quantised_layer_names(weights: Dict[str, np.ndarray], group_size: int = 64):
+    """What the reference's Whisper quantises (stt/models/whisper/whisper.py:343-348: nn.Linear / nn.Embedding): the 2-D `*.weight` of the Linears in
+    `encoder.blocks.*` / `decoder.blocks.*` and `decoder.token_embedding.weight`, where the input width is a multiple of the group size.  The stem's
+    convolutions (3-D), the LayerNorms (1-D) and the positional embeddings (raw arrays without a `.weight` suffix) stay as they are."""
+    names = []
+    for k, v in weights.items():
+        if not k.endswith(".weight") or np.ndim(v) != 2:
+            continue
+        if not (k.startswith("encoder.blocks.") or k.startswith("decoder.blocks.") or k == "decoder.token_embedding.weight"):
+            continue
+        if np.shape(v)[1] % group_size == 0:
+            names.append(k)
+    return names
+
+
+WHISPER_PACKED_BITS = (4, 8)
+WHISPER_PACKED_GROUPS = (32, 64, 128)
+
+
+def whisper_weight_route(name: str, in_width: int, group_size: int, bits: int):
+    """Where a quantised `{p}.weight` of a Whisper checkpoint lives under weight_storage="packed": ("packed", None) -- the checkpoint's integers stay
+    in device memory and the decoder's kernels decode them -- or ("bf16", reason): dequantised by the checkpoint's own rule and run as bf16.  The same
+    decision, with the same reasons, is taken by kk_whisper_text_finalize, which is what `Model.weight_report()` reads back; this restatement lets
+    the rule be tested without a device.  `in_width`: the matrix's input width (columns of the dequantised matrix)."""
+    check_bits(bits)
+    if name.startswith("encoder."):
+        return "bf16", "the encoder runs on the bf16 conv kernels"
+    if name.endswith("cross_attn.key.weight") or name.endswith("cross_attn.value.weight"):
+        return "bf16", "the stacked cross key | value matrix feeds the bf16 conv kernel"
+    if bits not in WHISPER_PACKED_BITS:
+        return "bf16", "bits is not 4 or 8"
+    if group_size not in WHISPER_PACKED_GROUPS:
+        return "bf16", "group size is not 32, 64 or 128"
+    if in_width < group_size or in_width % group_size != 0:
+        return "bf16", "the input width is not a multiple of the group size"
+    return "packed", None
+
+
 def split_triplets(weights: Dict[str, np.ndarray], group_size: int, bits: int, per_layer: Optional[dict] = None):
     """(plain, triplets): `triplets[{p}.weight] = (words uint32, scales float32, biases float32, group_size, bits)` for every `{p}.weight` that
     comes with `{p}.scales` and `{p}.biases`, with the layer's own parameters where config["quantization"][p] gives them; a layer mapped to

@@ -53,7 +53,7 @@ def get_model_and_args(model_type: str, model_name):
 
 
 def load_model(model_path, lazy: bool = False, strict: bool = True, compute_dtype: str = None, quantization_kernel: str = "exact",
-               weight_storage: str = "packed", **kwargs):
+               weight_storage: str = None, **kwargs):
     """Returns a ready `kokoro.Model` (weights folded, packed and resident in HBM).
     Raises FileNotFoundError when no safetensors are found, ValueError for an unsupported model type.
     quantization_kernel (only matters for a checkpoint with config["quantization"]): "exact" (default) multiplies by the dequantised
@@ -61,8 +61,9 @@ def load_model(model_path, lazy: bool = False, strict: bool = True, compute_dtyp
     opt-in that re-quantises an 8-bit checkpoint's linears to e4m3 and runs them on the block-scaled fp8 matrix instruction.
     weight_storage (a sesame checkpoint with config["quantization"]): "packed" (default) keeps the 4- / 8-bit Linears quantised in device memory
     and decodes them inside the matrix-core kernels -- the bits of bf16 weight mode on the dequantised checkpoint; "dequantized" dequantises
-    at load.  2-bit checkpoints are always dequantised; 3- and 6-bit ones raise ValueError (quant.check_bits)."""
-    if weight_storage not in ("packed", "dequantized"):
+    at load.  2-bit checkpoints are always dequantised; 3- and 6-bit ones raise ValueError (quant.check_bits).  A quantised Whisper checkpoint
+    takes the same two values but has no default: left out (None), it is refused (whisper.Model.from_pretrained)."""
+    if weight_storage not in (None, "packed", "dequantized"):
         raise ValueError(f"weight_storage must be 'packed' or 'dequantized', not {weight_storage!r}")
     if quantization_kernel not in ("exact", "mxfp8"):
         raise ValueError(f"quantization_kernel must be 'exact' or 'mxfp8', not {quantization_kernel!r}")
@@ -79,7 +80,7 @@ def load_model(model_path, lazy: bool = False, strict: bool = True, compute_dtyp
     from . import whisper
 
     if whisper.is_whisper_config(config):  # stt/models/whisper: weights.safetensors / weights.npz + the ten ModelDimensions in config.json
-        return whisper.load_model(path, kwargs.get("dtype"), **{k: v for k, v in kwargs.items() if k == "device"})
+        return whisper.load_model(path, kwargs.get("dtype"), weight_storage=weight_storage, **{k: v for k, v in kwargs.items() if k == "device"})
     model_type = config.get("model_type") or (model_name[0] if model_name else None)
     weight_files = glob.glob(str(path / "*.safetensors"))
     if not weight_files:
@@ -102,7 +103,7 @@ def load_model(model_path, lazy: bool = False, strict: bool = True, compute_dtyp
         # sesame.Model(config) has no ModelConfig (tts/utils.py:226-230 passes the dict); the checkpoint dtype picks the weight storage, and
         # config["quantization"] (read by Model.load_weights) routes the uint32 / scales / biases triplets to the quantised loader
         model = arch.Model(dict(config, **{k: v for k, v in kwargs.items() if k in ("mimi_path", "text_tokenizer")}),
-                           weight_dtype="bfloat16" if compute_dtype == "bfloat16" else "float32", mimi=kwargs.get("mimi"), weight_storage=weight_storage)
+                           weight_dtype="bfloat16" if compute_dtype == "bfloat16" else "float32", mimi=kwargs.get("mimi"), weight_storage=weight_storage or "packed")
         model.load_weights(weights, strict=strict)
         return model
     quantization = config.get("quantization", None)

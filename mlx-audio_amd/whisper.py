@@ -266,7 +266,16 @@ class Model:
         self._alignment_heads = None  # the default is made on first use
 
     # ---- weights ---------------------------------------------------------------------------------------------------------------------
-    def load_weights(self, weights: dict) -> "Model":
+    def load_weights(self, weights: dict, quantization: Optional[dict] = None, weight_storage: str = "packed") -> "Model":
+        """`quantization`: config["quantization"] of an MLX 4- / 8-bit checkpoint (group_size, bits, per-layer entries), whose `weights` hold
+        `{p}.weight` (uint32) / `{p}.scales` / `{p}.biases` triplets.  weight_storage "packed": the decoder's quantised matrices and the token embedding
+        stay the checkpoint's integers in device memory, matrix by matrix where the format allows (quant.whisper_weight_route; `weight_report()` says
+        what became of each); "dequantized": everything is dequantised here and runs as bf16.  Both compute the same bits.  The encoder's
+        Linears are dequantised either way."""
+        check_weight_storage(weight_storage)
+        packed = {}
+        if quantization is not None:
+            weights, packed = split_quantised(weights, quantization, weight_storage)
         enc, rest = split_weights(self.dims, weights)
         self.decoder_weights = rest  # decoder.* (and alignment data): kept for the text side, not touched
         import torch
@@ -289,22 +298,33 @@ class Model:
                 shp = (C.c_int64 * a.ndim)(*a.shape)
                 _lib.check(lib.kk_whisper_load_tensor(h, name.encode(), shp, a.ndim, a.ctypes.data_as(C.c_void_p)), "kk_whisper_load_tensor")
             _lib.check(lib.kk_whisper_finalize(h, self._stream()), "kk_whisper_finalize")
-            dec = decoder_tensors(self.dims, rest)  # None: no complete decoder set, the model stays encoder-only
+            dec = decoder_tensors(self.dims, rest, packed)  # None: no complete decoder set, the model stays encoder-only
             if dec is not None:
                 from .whisper_decoding import TextRuntime
 
-                self._text = TextRuntime(lib, self.dims, dec, self.device, self._stream())
+                self._text = TextRuntime(lib, self.dims, dec, self.device, self._stream(), quantized=packed)
         return self
 
+    def weight_report(self) -> dict:
+        """What the decoder's weights occupy on the device and how its matrices are stored: `matrix_bytes` (the Linears and the token embedding),
+        `resident_bytes` (those plus biases, LayerNorms and positions), `packed` / `bf16` (matrix counts; the stacked cross key | value counts once)
+        and `fallbacks`: name -> reason for every quantised tensor that was dequantised into a bf16 matrix."""
+        if self._text is None:
+            raise NotImplementedError(_NOT_BUILT)
+        return self._text.weight_report()
+
     @classmethod
-    def from_pretrained(cls, path: str, dtype: str = "bfloat16", device: str = "cuda:0") -> "Model":
-        """whisper.py:320-353 for a LOCAL directory: config.json + weights.safetensors or weights.npz.  Never goes to the network."""
+    def from_pretrained(cls, path: str, dtype: str = "bfloat16", device: str = "cuda:0", weight_storage: Optional[str] = None) -> "Model":
+        """whisper.py:320-353 for a LOCAL directory: config.json + weights.safetensors or weights.npz.  Never goes to the network.
+        weight_storage: None refuses a checkpoint with config["quantization"]; "packed" / "dequantized" load it (`load_weights`).  A checkpoint
+        that is not quantised ignores it."""
+        check_weight_storage(weight_storage, allow_none=True)
         model_path = Path(path)
         if not model_path.is_dir():
             raise FileNotFoundError(f"{path} is not a local directory (checkpoints are not downloaded)")
         with open(model_path / "config.json", encoding="utf-8") as f:
             config = json.load(f)
-        dims = dimensions_from_config(config)
+        dims = dimensions_from_config(config, weight_storage)
         wf = model_path / "weights.safetensors"
         if wf.exists():
             from safetensors import safe_open
@@ -319,7 +339,9 @@ class Model:
                 raise FileNotFoundError(f"no weights.safetensors or weights.npz in {path}")
             with np.load(str(wf)) as z:
                 weights = {k: z[k] for k in z.files}
-        return cls(dims, dtype, device).load_weights(weights)
+        if config.get("quantization") is None:
+            return cls(dims, dtype, device).load_weights(weights)
+        return cls(dims, dtype, device).load_weights(weights, config["quantization"], weight_storage)
 
     # ---- the encoder -----------------------------------------------------------------------------------------------------------------
     def embed_audio(self, mel):
@@ -539,10 +561,38 @@ class Model:
             pass
 
 
-def dimensions_from_config(config: dict) -> ModelDimensions:
-    """whisper.py:329-334.  A quantised checkpoint is refused: its Linears would need the packed kernels the text side will bring."""
-    if config.get("quantization") is not None:
-        raise ValueError("quantised Whisper checkpoints are not supported yet")
+WEIGHT_STORAGES = ("packed", "dequantized")
+
+
+def check_weight_storage(weight_storage, allow_none: bool = False) -> None:
+    if not (weight_storage in WEIGHT_STORAGES or (allow_none and weight_storage is None)):
+        raise ValueError(f"weight_storage must be 'packed' or 'dequantized', not {weight_storage!r}")
+
+
+def split_quantised(weights: dict, quantization: dict, weight_storage: str):
+    """(weights with every quantised tensor that does not stay packed dequantised to fp32, {name: (words, scales, biases, group_size, bits)} of the
+    ones that go to the text handle as they are).  A layer is quantised iff `{p}.scales` and `{p}.biases` come with `{p}.weight`; per-layer entries
+    of `quantization` are honoured as quant.split_triplets does.  Under "packed" every `decoder.*` triplet is handed on -- the handle decides per
+    matrix and dequantises by the same rule what it cannot keep packed -- and everything else (the encoder's Linears) is dequantised here."""
+    from .quant import dequantize_affine, split_triplets
+
+    as_np = {k: (v.float().numpy() if _is_torch(v) and v.dtype.is_floating_point else (v.numpy() if _is_torch(v) else np.asarray(v))) for k, v in weights.items()}
+    per_layer = {k: v for k, v in quantization.items() if k not in ("group_size", "bits")}
+    plain, triplets = split_triplets(as_np, int(quantization["group_size"]), int(quantization["bits"]), per_layer)
+    packed = {}
+    for k, t in triplets.items():
+        if weight_storage == "packed" and k.startswith("decoder."):
+            packed[k] = t
+        else:
+            plain[k] = dequantize_affine(*t)
+    return plain, packed
+
+
+def dimensions_from_config(config: dict, weight_storage: Optional[str] = None) -> ModelDimensions:
+    """whisper.py:329-334.  A quantised checkpoint is refused unless the caller says how its weights are to be stored (`Model.from_pretrained`)."""
+    if config.get("quantization") is not None and weight_storage is None:
+        raise ValueError("quantised Whisper checkpoints are not supported yet without a weight_storage: pass weight_storage='packed' (the decoder's "
+                         "matrices stay quantised in device memory) or 'dequantized'")
     missing = [k for k in DIMENSION_KEYS if k not in config]
     if missing:
         raise ValueError(f"config.json lacks the Whisper dimensions {missing}")
@@ -551,4 +601,4 @@ def dimensions_from_config(config: dict) -> ModelDimensions:
 
 def load_model(model_path, dtype: Optional[str] = None, **kwargs) -> Model:
     """What utils.load_model routes a Whisper checkpoint to."""
-    return Model.from_pretrained(str(model_path), dtype or "bfloat16", **{k: v for k, v in kwargs.items() if k == "device"})
+    return Model.from_pretrained(str(model_path), dtype or "bfloat16", **{k: v for k, v in kwargs.items() if k in ("device", "weight_storage")})

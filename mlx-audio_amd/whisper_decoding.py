@@ -49,14 +49,24 @@ def _as_f32(v) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(v), dtype=np.float32)
 
 
-def decoder_tensors(dims, rest: dict) -> Optional[Dict[str, np.ndarray]]:
+def decoder_tensors(dims, rest: dict, quantized: Optional[dict] = None) -> Optional[Dict[str, np.ndarray]]:
     """The complete decoder set of a checkpoint's non-encoder tensors as fp32 numpy, or None when a name of `decoder_shapes` is absent (an encoder-only
-    checkpoint: the text side stays unbuilt).  With the complete set present, a misshapen tensor is a ValueError that names it."""
+    checkpoint: the text side stays unbuilt).  With the complete set present, a misshapen tensor is a ValueError that names it.  `quantized`: matrices
+    that arrive as (words, scales, biases, group_size, bits) instead (quant.split_triplets); they count as present, are checked and are left out."""
+    quantized = quantized or {}
     want = decoder_shapes(dims)
-    if any(k not in rest for k in want):
+    if any(k not in rest and k not in quantized for k in want):
         return None
     out = {}
     for k, shape in want.items():
+        if k in quantized:
+            words, scales, biases, group, bits = quantized[k]
+            got = (words.shape[0], words.shape[-1] * (32 // bits)) if words.ndim == 2 else tuple(words.shape)
+            if got != shape:
+                raise ValueError(f"decoder tensor {k} has shape {got}, expected {shape}")
+            if got[1] % group != 0 or scales.shape != (got[0], got[1] // group) or biases.shape != scales.shape:
+                raise ValueError(f"decoder tensor {k}: scales / biases {tuple(scales.shape)} do not match {shape} at group size {group}")
+            continue
         try:
             a = _as_f32(rest[k])
         except Exception as e:  # not an array at all
@@ -229,7 +239,7 @@ def suppress_bitmask(n_vocab: int, ids: Iterable[int]) -> np.ndarray:
 class TextRuntime:
     """The text handle of one Model plus the PyTorch memory it runs in."""
 
-    def __init__(self, lib, dims, tensors: Dict[str, np.ndarray], device, stream):
+    def __init__(self, lib, dims, tensors: Dict[str, np.ndarray], device, stream, quantized: Optional[dict] = None):
         from . import _lib
 
         self._lib, self.dims, self.device = lib, dims, device
@@ -243,6 +253,11 @@ class TextRuntime:
             for name, a in tensors.items():
                 shp = (C.c_int64 * a.ndim)(*a.shape)
                 _lib.check(lib.kk_whisper_text_load_tensor(h, name.encode(), shp, a.ndim, a.ctypes.data_as(C.c_void_p)), "kk_whisper_text_load_tensor")
+            for name, (words, scales, biases, group, bits) in (quantized or {}).items():
+                if name in decoder_shapes(dims):  # (checked by decoder_tensors)
+                    shp = (C.c_int64 * 2)(words.shape[0], words.shape[1] * (32 // bits))
+                    _lib.check(lib.kk_whisper_text_load_quantized(h, name.encode(), shp, words.ctypes.data_as(C.c_void_p), scales.ctypes.data_as(C.c_void_p),
+                                                                  biases.ctypes.data_as(C.c_void_p), group, bits), "kk_whisper_text_load_quantized")
             _lib.check(lib.kk_whisper_text_finalize(h, stream), "kk_whisper_text_finalize")
         except Exception:
             self.release()
@@ -254,6 +269,17 @@ class TextRuntime:
         if getattr(self, "_h", None) is not None:
             self._lib.kk_whisper_text_destroy(self._h)
         self._h = None
+
+    def weight_report(self) -> dict:
+        """kk_whisper_text_weight_info / _fallback, see whisper.Model.weight_report"""
+        from . import _lib
+
+        mb, tb = C.c_size_t(), C.c_size_t()
+        n_packed, n_bf16, n_fb = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(self._lib.kk_whisper_text_weight_info(self._h, C.byref(mb), C.byref(tb), C.byref(n_packed), C.byref(n_bf16), C.byref(n_fb)),
+                   "kk_whisper_text_weight_info")
+        fallbacks = dict((self._lib.kk_whisper_text_weight_fallback(self._h, i) or b"\t").decode().split("\t", 1) for i in range(n_fb.value))
+        return {"matrix_bytes": mb.value, "resident_bytes": tb.value, "packed": n_packed.value, "bf16": n_bf16.value, "fallbacks": fallbacks}
 
     def _stream(self):
         import torch

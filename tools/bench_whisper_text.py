@@ -5,7 +5,7 @@ read and the rate that makes of the measured time.  Every figure is the median o
 between two device events.  Prints one JSON line per case.
 
 The per-step share of each kernel family comes from a run of its own under the profiler (tracing slows the host, so no time above is taken there):
-    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o k -- python tools/bench_whisper_text.py --only-steps 200 --batch 8
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o k -- python tools/bench_whisper_text.py --only-steps 200 --batch 8 [--weights q4 --layers 32]
     python tools/bench_whisper_text.py --digest DIR/.../k_kernel_trace.csv --digest-steps 200 --batch 8 [--out the bench's file: appended]
 
 `--align` times the token-timestamp path instead (mlx-audio_amd/whisper_timing.py, csrc/kk_whisper_align.hip) at the same shape: a 448-token
@@ -23,10 +23,17 @@ state of the same row count on repeated features (`set_audio`, the step with the
 key counts 32, 224 and 448 under both (four layers of owned against direct self-attention on the same keys are all that differs), and the bytes of
 the beam state next to the grouped state.
 
+`--weights bf16|q8|q4 [--group-size 64] [--layers N]` times the greedy decode step on a synthetic MLX-quantised checkpoint instead: the
+checkpoint is loaded twice in one process, "dequantized" (the bf16 kernels, which are what a float checkpoint runs) and "packed" (the decoder's matrices
+and the token embedding kept as integers), and the two models' steps are timed in alternating rounds at B = 1 and 8, each round the median of `--steps`
+samples.  `bf16` times the dequantised model against itself: the spread of a repeated measurement.  `--layers 4` (the default) is the large-v3-turbo
+decoder, `--layers 32` large-v3's.  Every case carries both models' `weight_report()` and is appended to `--out`.
+
 Usage:  python tools/bench_whisper_text.py [--steps 20] [--warmup 3] [--inner 20] [--position 64] [--out profiles/whisper_text_bench.json]
         python tools/bench_whisper_text.py --align [--steps 20] [--warmup 3] [--out profiles/whisper_align_bench.json]
         python tools/bench_whisper_text.py --best-of 5 --temperature 1.0 [--steps 20] [--warmup 3] [--out profiles/whisper_sample_bench.json]
-        python tools/bench_whisper_text.py --beam 5 [--steps 20] [--warmup 3] [--out profiles/whisper_beam_bench.json]"""
+        python tools/bench_whisper_text.py --beam 5 [--steps 20] [--warmup 3] [--out profiles/whisper_beam_bench.json]
+        python tools/bench_whisper_text.py --weights q4 [--group-size 64] [--layers 32] [--rounds 5] [--out profiles/whisper_text_bench.json]"""
 import argparse
 import csv
 import json
@@ -42,7 +49,7 @@ sys.path.insert(0, ROOT)
 
 CTX, WIDTH, HEADS, LAYERS, VOCAB, TEXT_CTX = 1500, 1280, 20, 4, 51866, 448
 
-FAMILIES = (("linear_rows", "linear_rows_kernel"), ("attention", "attn_rows_kernel"), ("attention", "attn_merge_kernel"), ("layernorm", "layernorm_kernel"),
+FAMILIES = (("linear_rows", "linear_rows_kernel"), ("linear_rows (packed)", "linear_rows_q_kernel"), ("embed + row tables", "embed_q_kernel"), ("attention", "attn_rows_kernel"), ("attention", "attn_merge_kernel"), ("layernorm", "layernorm_kernel"),
             ("pick", "pick_kernel"), ("pick", "pick_sampled_kernel"), ("beam top-k", "beam_topk_kernel"), ("beam select", "beam_select_kernel"), ("embed + row tables", "embed_kernel"), ("embed + row tables", "text_rows_kernel"))
 
 
@@ -85,7 +92,7 @@ def digest(path, steps):
                           for k, v in sorted(fam.items(), key=lambda kv: -kv[1])})
 
 
-def synthetic_model():
+def synthetic_weights():
     """N(0, 1 / fan_in) matrices, one set of arrays shared by every layer (the time does not depend on the values being distinct)"""
     from mlx_audio_amd import whisper
 
@@ -102,7 +109,34 @@ def synthetic_model():
 
     shapes = {**whisper.encoder_shapes(d), **whisper.decoder_shapes(d)}
     w = {k: (np.ones(s, np.float32) if "ln" in k and k.endswith("weight") else arr(s)) for k, s in shapes.items()}
+    return d, w
+
+
+def synthetic_model():
+    from mlx_audio_amd import whisper
+
+    d, w = synthetic_weights()
     return d, whisper.Model(d).load_weights(w)
+
+
+def quantised_models(bits, group):
+    """(dims, the model on the dequantised checkpoint, the model on the packed one); bits None: the dequantised model alone, twice.  A distinct array is
+    quantised once however many layers share it."""
+    from mlx_audio_amd import quant, whisper
+
+    d, w = synthetic_weights()
+    q, deq, done = dict(w), dict(w), {}
+    for k in quant.whisper_quantised_layer_names(w, group):
+        if id(w[k]) not in done:
+            t = quant.quantize_affine(w[k], group, bits or 4)
+            done[id(w[k])] = (t, quant.dequantize_affine(*t, group, bits or 4))
+        (words, scales, biases), back = done[id(w[k])]
+        p = k[: -len(".weight")]
+        q[k], q[p + ".scales"], q[p + ".biases"], deq[k] = words, scales, biases, back
+    bf16 = whisper.Model(d).load_weights(deq)
+    if bits is None:
+        return d, bf16, bf16
+    return d, bf16, whisper.Model(d).load_weights(q, {"group_size": group, "bits": bits}, "packed")
 
 
 def main():
@@ -118,6 +152,10 @@ def main():
     ap.add_argument("--temperature", type=float, default=0.0, help="> 0: the grouped state's picks are sampled at this temperature (DESIGN 8j)")
     ap.add_argument("--best-of", type=int, default=0, help="G > 0: time G rows per window on one cross K/V slice against the plain state of as many rows")
     ap.add_argument("--beam", type=int, default=0, help="K > 0: time the beam step of K rows per window against the sampled best_of = K step (DESIGN 8k)")
+    ap.add_argument("--weights", choices=("bf16", "q8", "q4"), default=None, help="time the step on a quantised checkpoint, packed against dequantised (DESIGN 8l)")
+    ap.add_argument("--group-size", type=int, default=64)
+    ap.add_argument("--layers", type=int, default=LAYERS, help="decoder layers of the --weights shape: 4 (large-v3-turbo) or 32 (large-v3)")
+    ap.add_argument("--rounds", type=int, default=5, help="alternating rounds per model of --weights")
     ap.add_argument("--digest", default=None)
     ap.add_argument("--digest-steps", type=int, default=200)
     a = ap.parse_args()
@@ -127,7 +165,7 @@ def main():
         if a.out and os.path.exists(a.out):  # appended to the bench's file
             with open(a.out) as f:
                 doc = json.load(f)
-            doc["results"].append(dict(r, B=a.batch))
+            doc["results"].append(dict(r, B=a.batch, **(dict(weights=a.weights, layers=a.layers) if a.weights else {})))
             with open(a.out, "w") as f:
                 json.dump(doc, f, indent=1)
                 f.write("\n")
@@ -141,6 +179,8 @@ def main():
         raise SystemExit("bench_whisper_text.py needs a GPU: a time taken elsewhere says nothing")
     if a.steps < 20 and not a.only_steps:
         raise SystemExit("--steps must be at least 20 (the figures are medians)")
+    if a.weights:
+        return bench_weights(a)
     d, model = synthetic_model()
     rt, tok = model._text, WD.special_tokens(d)
     params = _lib.KKWhisperPickParams(n_vocab=d.n_vocab, eot=tok.eot, blank=WD.BLANK_TOKEN, no_timestamps=tok.no_timestamps, timestamp_begin=tok.timestamp_begin,
@@ -354,6 +394,86 @@ def main():
         emit(dict(case="decode_step_forward_only", B=B, position=a.position, **timed(forward_only, a.inner)))
         emit(dict(case="pick_only", B=B, **timed(rt.pick, a.inner)))
     write_out()
+
+
+def bench_weights(a):
+    """--weights: see the module's text"""
+    global LAYERS
+    import torch
+
+    from mlx_audio_amd import _lib
+    from mlx_audio_amd import whisper_decoding as WD
+
+    LAYERS = a.layers
+    bits = {"bf16": None, "q8": 8, "q4": 4}[a.weights]
+    d, m_bf16, m_q = quantised_models(bits, a.group_size)
+    tok = WD.special_tokens(d)
+    params = _lib.KKWhisperPickParams(n_vocab=d.n_vocab, eot=tok.eot, blank=WD.BLANK_TOKEN, no_timestamps=tok.no_timestamps, timestamp_begin=tok.timestamp_begin,
+                                      max_initial_timestamp_index=50, without_timestamps=0, suppress_blank=1)
+    mask = WD.suppress_bitmask(d.n_vocab, WD.suppress_list(tok, WD.DecodingOptions()))
+    sides = (("bf16", m_bf16), ("bf16 again" if bits is None else a.weights, m_q))
+    if a.only_steps:  # the profiler's run: the steps of the --weights model and nothing else
+        rt = m_q._text
+        rt.set_audio(torch.randn((a.batch, CTX, WIDTH), generator=torch.Generator().manual_seed(a.batch)).cuda())
+        rt.pick_setup(params, mask)
+        rt.forward(torch.randint(0, 50000, (a.batch, a.position), generator=torch.Generator().manual_seed(1), dtype=torch.int32).cuda(), False)
+        rt.pick()
+        for _ in range(a.only_steps):
+            rt.rewind(a.position)
+            rt.step()
+            rt.pick()
+        torch.cuda.synchronize()
+        return
+    results = []
+    for B in (1, 8):
+        feats = torch.randn((B, CTX, WIDTH), generator=torch.Generator().manual_seed(B)).cuda()
+        prompt = torch.randint(0, 50000, (B, a.position), generator=torch.Generator().manual_seed(1), dtype=torch.int32).cuda()
+
+        def begin(rt):
+            rt.set_audio(feats)
+            rt.pick_setup(params, mask)
+            rt.forward(prompt, False)  # the self K/V up to the position
+            rt.pick()
+
+        def sample(rt):  # the median of --steps samples of --inner steps each, between device events
+            ms = []
+            for _ in range(a.steps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(a.inner):
+                    rt.rewind(a.position)  # host only: every timed step runs at the same position
+                    rt.step()
+                    rt.pick()
+                e1.record()
+                e1.synchronize()
+                ms.append(e0.elapsed_time(e1) / a.inner)
+            return statistics.median(ms)
+
+        rounds = {name: [] for name, _ in sides}
+        for r in range(a.rounds + 1):  # round 0 warms both up and is dropped
+            for name, m in sides:
+                if r == 0:  # each model keeps its own window state
+                    begin(m._text)
+                t = sample(m._text)
+                if r:
+                    rounds[name].append(round(t, 4))
+        base, other = (rounds[name] for name, _ in sides)
+        res = dict(case="decode_step_by_weights", weights=a.weights, group_size=a.group_size, layers=a.layers, B=B, position=a.position,
+                   bf16_ms_rounds=base, bf16_ms_median=round(statistics.median(base), 4), bf16_spread_ms=round(max(base) - min(base), 4),
+                   other=sides[1][0], other_ms_rounds=other, other_ms_median=round(statistics.median(other), 4),
+                   other_minus_bf16_ms=round(statistics.median(other) - statistics.median(base), 4), steps=a.steps, inner=a.inner, rounds=a.rounds,
+                   bf16_weight_report=m_bf16.weight_report(), other_weight_report=m_q.weight_report())
+        results.append(res)
+        print(json.dumps(res), flush=True)
+    if a.out:
+        doc = dict(device=torch.cuda.get_device_name(0), results=[])
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                doc = json.load(f)
+        doc["results"].extend(results)
+        with open(a.out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
 
 
 if __name__ == "__main__":
