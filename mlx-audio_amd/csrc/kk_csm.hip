@@ -45,12 +45,6 @@ struct Lin {  // generic-kernel pack [1][Cin][ldw]
   size_t qoff = 0, poff = 0;  // byte offsets into kk_csm::packq
   const float2* wp = nullptr;
 };
-// a quantised nn.Linear / nn.Embedding as the checkpoint holds it (host, until finalize)
-struct QHost {
-  int O = 0, I = 0, group = 0, bits = 0;
-  std::vector<uint32_t> words;       // [O][I * bits / 32]
-  std::vector<float> scales, biases; // [O][I / group]
-};
 struct LlamaLayer {
   Lin qkv, o, gu, down;
   ArenaVec n1, n2;
@@ -77,7 +71,7 @@ struct kk_csm {
   std::vector<uint16_t> packb;   // host staging of the bf16 copies
   uint16_t* devb = nullptr;
   // quantised checkpoint: tensors as loaded; the packed Linears' integer fragment packs + pairs (bytes; shared like devb)
-  std::map<std::string, QHost> qhost;
+  std::map<std::string, QuantHost> qhost;
   std::vector<uint8_t> packq;
   uint8_t* devq = nullptr;
   bool packed = false;           // kk_csm_finalize's all-or-nothing decision: every Linear of the fast path runs from its quantised pack
@@ -1138,19 +1132,6 @@ static void qfrag_pack_part(const uint32_t* words, const float* scales, const fl
     }
   }
 }
-// the checkpoint's own arithmetic on the host: w = fp32(q) * scale + bias, two roundings (quant.dequantize_affine)
-static void dequantize_host(const QHost& t, std::vector<float>& out) {
-  const int per = 32 / t.bits, wpr = t.I / per, ngrp = t.I / t.group;
-  const uint32_t mask = (1u << t.bits) - 1u;
-  out.resize((size_t)t.O * t.I);
-  for (int o = 0; o < t.O; ++o)
-    for (int i = 0; i < t.I; ++i) {
-      const float qf = (float)((t.words[(size_t)o * wpr + i / per] >> ((i % per) * t.bits)) & mask);
-      volatile float prod = qf * t.scales[(size_t)o * ngrp + i / t.group];  // (rounded to fp32 before the add whatever the compiler's contraction rule)
-      out[(size_t)o * t.I + i] = prod + t.biases[(size_t)o * ngrp + i / t.group];
-    }
-}
-
 // host tensors are erased as soon as they are packed: peak host memory stays near one copy of the 1.6 B parameters
 struct Packer {
   kk_csm* m;
@@ -1222,7 +1203,7 @@ struct Packer {
     for (int o : outs) O += o;
     l.Cin = I; l.Cout = O; l.ldw = rup(O, 64);
     l.has_f32 = false;
-    const QHost& first = m->qhost.at(names[0]);
+    const QuantHost& first = m->qhost.at(names[0]);
     l.fmt = first.bits == 8 ? KK_WF_Q8 : KK_WF_Q4;
     l.group = first.group;
     frag_choice(I, O, split_ok, &l.ks, &l.nsub);
@@ -1232,7 +1213,7 @@ struct Packer {
     m->packq.resize(l.poff + pb, 0);
     int base = 0;
     for (size_t k = 0; k < outs.size(); ++k) {
-      const QHost& t = m->qhost.at(names[k]);
+      const QuantHost& t = m->qhost.at(names[k]);
       qfrag_pack_part(t.words.data(), t.scales.data(), t.biases.data(), outs[k], base, I, l.nsub, l.group, t.bits, &m->packq[l.qoff],
                       (float*)&m->packq[l.poff]);
       m->qhost.erase(names[k]);
@@ -1278,7 +1259,7 @@ static std::string csm_can_pack(const kk_csm* m) {
     for (size_t k = 0; k < s.names.size(); ++k) {
       auto it = m->qhost.find(s.names[k]);
       if (it == m->qhost.end()) return s.names[k] + " is not quantised";
-      const QHost& t = it->second;
+      const QuantHost& t = it->second;
       if (t.O != s.outs[k] || t.I != s.I) return "unexpected shape for " + s.names[k];
       if (k == 0) { bits = t.bits; group = t.group; }
       if (t.bits != bits || t.group != group) return s.names[k] + ": the parts of a stacked matrix differ in bits / group size";
@@ -2082,13 +2063,7 @@ extern "C" int kk_csm_set_weight_dtype(kk_csm* m, int dtype) {
 }
 
 extern "C" int kk_csm_load_tensor(kk_csm* m, const char* name, const int64_t* shape, int ndim, const float* data) {
-  if (!m || !name || !shape || !data || ndim < 1) return kk_fail("kk_csm_load_tensor: bad argument");
-  if (m->finalized) return kk_fail("kk_csm_load_tensor: model already finalized");
-  size_t n = 1;
-  for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
-  HostTensor& t = m->arena.host[name];
-  t.d.assign(data, data + n);
-  t.shape.assign(shape, shape + ndim);
+  KK_TRY(kk_host_load_tensor("kk_csm_load_tensor", m ? &m->arena.host : nullptr, m && m->finalized, name, shape, ndim, data));
   m->qhost.erase(name);
   return 0;
 }
@@ -2170,17 +2145,7 @@ extern "C" int kk_csm_finalize(kk_csm* m, void* stream) {
 
 extern "C" int kk_csm_load_quantized(kk_csm* m, const char* name, const int64_t* shape, const uint32_t* words, const float* scales, const float* biases,
                                      int group_size, int bits) {
-  if (!m || !name || !shape || !words || !scales || !biases) return kk_fail("kk_csm_load_quantized: bad argument");
-  if (m->finalized) return kk_fail("kk_csm_load_quantized: model already finalized");
-  if (bits != 2 && bits != 4 && bits != 8) return kk_fail("kk_csm_load_quantized: bits must be 2, 4 or 8 (values of a word in bits [j bits, (j + 1) bits))");
-  const int64_t O = shape[0], I = shape[1];
-  if (O < 1 || I < 1 || O > (1 << 30) || I > (1 << 30) || group_size < 1 || I % group_size != 0 || (I * bits) % 32 != 0)
-    return kk_failf("kk_csm_load_quantized: %s: shape / group size", name);
-  QHost& t = m->qhost[name];
-  t.O = (int)O; t.I = (int)I; t.group = group_size; t.bits = bits;
-  t.words.assign(words, words + (size_t)O * (size_t)(I * bits / 32));
-  t.scales.assign(scales, scales + (size_t)O * (size_t)(I / group_size));
-  t.biases.assign(biases, biases + (size_t)O * (size_t)(I / group_size));
+  KK_TRY(kk_host_load_quantized("kk_csm_load_quantized", m ? &m->qhost : nullptr, m && m->finalized, name, shape, words, scales, biases, group_size, bits));
   m->arena.host.erase(name);
   return 0;
 }

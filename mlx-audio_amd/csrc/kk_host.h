@@ -1,5 +1,5 @@
-// Host-side plumbing shared by the three runtimes (Kokoro kk_model.hip, CSM kk_csm.hip, Mimi kk_mimi.hip): weight arena, graph
-// replay cache, workspace bump allocator, debug notes and the error helpers.
+// Host-side plumbing shared by the runtimes (Kokoro kk_model.hip, CSM kk_csm.hip, Mimi kk_mimi.hip, Whisper kk_whisper.hip and
+// kk_whisper_text.hip): parameter loaders, weight arena, graph replay cache, workspace bump allocator, debug notes and the error helpers.
 #pragma once
 #include <stdarg.h>
 #include <stdint.h>
@@ -55,6 +55,71 @@ struct HostTensor {  // a loaded parameter, fp32, with the shape it was loaded w
   std::vector<float> d;
   std::vector<int64_t> shape;
 };
+
+// the body of a handle's *_load_tensor (`host`: its map, null for a null handle)
+static inline int kk_host_load_tensor(const char* who, std::map<std::string, HostTensor>* host, bool finalized, const char* name, const int64_t* shape, int ndim,
+                                      const float* data) {
+  if (!host || !name || !shape || !data || ndim < 1) return kk_failf("%s: bad argument", who);
+  if (finalized) return kk_failf("%s: model already finalized", who);
+  size_t n = 1;
+  for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
+  HostTensor& t = (*host)[name];
+  t.d.assign(data, data + n);
+  t.shape.assign(shape, shape + ndim);
+  return 0;
+}
+
+// the loaded parameter `name` if it has `shape`, else null with the first such failure kept in `err`
+static inline const HostTensor* kk_host_want(const std::map<std::string, HostTensor>& host, const std::string& name, std::initializer_list<int64_t> shape,
+                                             std::string& err) {
+  auto it = host.find(name);
+  if (it == host.end()) {
+    if (err.empty()) err = "missing parameter: " + name;
+    return nullptr;
+  }
+  if (it->second.shape != std::vector<int64_t>(shape)) {
+    if (err.empty()) err = "unexpected shape for " + name;
+    return nullptr;
+  }
+  return &it->second;
+}
+
+// a quantised nn.Linear / nn.Embedding as an MLX checkpoint holds it (host, until finalize)
+struct QuantHost {
+  int O = 0, I = 0, group = 0, bits = 0;
+  std::vector<uint32_t> words;        // [O][I * bits / 32]
+  std::vector<float> scales, biases;  // [O][I / group]
+};
+
+// the body of a handle's *_load_quantized (`map`: its quantised tensors, null for a null handle)
+static inline int kk_host_load_quantized(const char* who, std::map<std::string, QuantHost>* map, bool finalized, const char* name, const int64_t* shape,
+                                         const uint32_t* words, const float* scales, const float* biases, int group_size, int bits) {
+  if (!map || !name || !shape || !words || !scales || !biases) return kk_failf("%s: bad argument", who);
+  if (finalized) return kk_failf("%s: model already finalized", who);
+  if (bits != 2 && bits != 4 && bits != 8) return kk_failf("%s: bits must be 2, 4 or 8 (values of a word in bits [j bits, (j + 1) bits))", who);
+  const int64_t O = shape[0], I = shape[1];
+  if (O < 1 || I < 1 || O > (1 << 30) || I > (1 << 30) || group_size < 1 || I % group_size != 0 || (I * bits) % 32 != 0)
+    return kk_failf("%s: %s: shape / group size", who, name);
+  QuantHost& t = (*map)[name];
+  t.O = (int)O; t.I = (int)I; t.group = group_size; t.bits = bits;
+  t.words.assign(words, words + (size_t)O * (size_t)(I * bits / 32));
+  t.scales.assign(scales, scales + (size_t)O * (size_t)(I / group_size));
+  t.biases.assign(biases, biases + (size_t)O * (size_t)(I / group_size));
+  return 0;
+}
+
+// the checkpoint's own arithmetic on the host: w = fp32(q) * scale + bias, two roundings (quant.dequantize_affine)
+static inline void dequantize_host(const QuantHost& t, std::vector<float>& out) {
+  const int per = 32 / t.bits, wpr = t.I / per, ngrp = t.I / t.group;
+  const uint32_t mask = (1u << t.bits) - 1u;
+  out.resize((size_t)t.O * t.I);
+  for (int o = 0; o < t.O; ++o)
+    for (int i = 0; i < t.I; ++i) {
+      const float qf = (float)((t.words[(size_t)o * wpr + i / per] >> ((i % per) * t.bits)) & mask);
+      volatile float prod = qf * t.scales[(size_t)o * ngrp + i / t.group];  // (rounded to fp32 before the add whatever the compiler's contraction rule)
+      out[(size_t)o * t.I + i] = prod + t.biases[(size_t)o * ngrp + i / t.group];
+    }
+}
 
 struct ArenaVec {  // n floats at `off` of the arena; `p` is set by resolve() after the upload
   size_t off = 0, n = 0;

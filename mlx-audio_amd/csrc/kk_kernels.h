@@ -1,6 +1,7 @@
 // Launch wrappers of every device kernel (host-callable, enqueue on the given stream, never sync).
 #pragma once
 #include "kk_common.h"
+#include "../../include/kokoro_hip.h"  // the ABI's limits and structs that launch arguments carry (KK_WHISPER_MAX_ROWS, kk_whisper_pick_params)
 
 // ---- convolution family (kk_conv.hip, kk_conv_mfma.hip)
 int kk_launch_conv_generic(const KKConvArgs& a, int B, int in_dtype, int out_dtype, hipStream_t st);
@@ -349,3 +350,50 @@ struct KKQkSel {  // up to 32 heads of one layer per launch: head[j] goes to out
 // q fp32 [items * rows][heads * 64], k bf16 at channel 0 of [items][item_stride / ld][ld]
 int kk_launch_whisper_qk_rows(hipStream_t st, const float* q, const bf16_t* k, long long item_stride, int ld, int heads, int items, int rows, int n_keys,
                               const KKQkSel& sel, float* out, long long stride_slot, long long stride_item, long long ldo);
+
+// ---- Whisper text side (kk_whisper_text_kernels.hip): the decode-step kernels, launched by the text handle (kk_whisper_text.hip)
+struct KKLinRows {  // out[m] = act(x[m] W^T + bias) (+ res[m]), 1 <= M <= 16 rows per launch; every row pointer is followed by its pitch
+  const float* x;
+  long long ldx;
+  const bf16_t* w;  // bf16 [N][K] dense; not read by the quantised launch
+  const float *bias, *res;
+  long long ldr;
+  float* out;
+  long long ldo;
+  bf16_t* ob;  // the result as bf16 into row rows[m] (null: m) of a store of nrows rows; a destination outside [0, nrows) is not written
+  long long ldb;
+  const int* rows;
+  int nrows, M, N, K, act;
+};
+int kk_launch_whisper_linear_rows(hipStream_t st, const KKLinRows& a);
+// the same Linear on an MLX affine-quantised matrix: `words` [N][K bits / 32], `pairs` (scale, bias) [N][K / group]
+int kk_launch_whisper_linear_rows_q(hipStream_t st, const KKLinRows& a, const uint32_t* words, const float2* pairs, int group, int bits);
+const char* kk_whisper_q_refusal(int K, int group, int bits);  // why a quantised [N][K] matrix cannot stay packed, or null
+// R query rows against a bf16 K | V store of `items` slots of T_rows positions; table: item [R], or (owned) the owner table [R][T_rows]
+size_t kk_whisper_attn_scratch_floats(int R, int heads, int T_rows);
+int kk_launch_whisper_attn_rows(hipStream_t st, bool owned, int R, int heads, const float* q, const bf16_t* kv, int k_off, int v_off, int items, int T_rows,
+                                int ld, const int* table, const int* len, float* out, float* scratch);
+constexpr int KK_WHISPER_BEAM_FIN = 2 * KK_WHISPER_MAX_GROUP;  // finished sequences a window keeps, at most
+// token + position embedding of R rows, from the bf16 table or the quantised one
+int kk_launch_whisper_embed(hipStream_t st, int R, int D, const int* tok, const int* pos, const bf16_t* table, int n_vocab, const float* positions, int n_ctx,
+                            float* out);
+int kk_launch_whisper_embed_q(hipStream_t st, int R, int D, const int* tok, const int* pos, const uint32_t* words, const float2* pairs, int group, int bits,
+                              int n_vocab, const float* positions, int n_ctx, float* out);
+// the per-row index arrays of a window forward (item_cross: null unless n_group > 1), and of a row-mode round from its table of items
+int kk_launch_whisper_text_rows(hipStream_t st, int B, int S, int pos, int n_text_ctx, int n_audio_ctx, int n_group, int* item, int* item_cross, int* posr,
+                                int* len_self, int* len_cross, int* cache_row);
+struct KKRowItems {  // item i: flat rows first[i] .. first[i] + count[i] - 1 are decoder row row[i] at pos[i] + s, fed from from[i] + s (or -1: the last pick)
+  int n;
+  int row[KK_WHISPER_MAX_ROWS], pos[KK_WHISPER_MAX_ROWS], count[KK_WHISPER_MAX_ROWS], from[KK_WHISPER_MAX_ROWS], first[KK_WHISPER_MAX_ROWS];
+};
+int kk_launch_whisper_text_plan(hipStream_t st, const KKRowItems& t, int R, int n_text_ctx, int n_audio_ctx, const int32_t* init, const int32_t* next, int* item,
+                                int* posr, int* len_self, int* len_cross, int* cache_row, int32_t* tok);
+struct KKRowGather {  // rows src[j] of x to row j of out
+  int src[2 * KK_WHISPER_MAX_ROWS];
+};
+int kk_launch_whisper_gather_rows(hipStream_t st, int n, const KKRowGather& sel, const float* x, int D, float* out);
+struct KKPickSel {  // block j picks for decoder row row[j] on logits row logit[j]
+  int row[KK_WHISPER_MAX_ROWS], logit[KK_WHISPER_MAX_ROWS];
+};
+int kk_launch_whisper_pick_rows(hipStream_t st, int n, const KKPickSel& sel, const float* logits, long long ldl, const kk_whisper_pick_params* params,
+                                const uint32_t* suppress, int words, kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next);

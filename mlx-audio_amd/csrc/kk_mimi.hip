@@ -1191,14 +1191,7 @@ extern "C" void kk_mimi_destroy(kk_mimi* m) {
 }
 
 extern "C" int kk_mimi_load_tensor(kk_mimi* m, const char* name, const int64_t* shape, int ndim, const float* data) {
-  if (!m || !name || !shape || !data || ndim < 1) return kk_fail("kk_mimi_load_tensor: bad argument");
-  if (m->finalized) return kk_fail("kk_mimi_load_tensor: model already finalized");
-  size_t n = 1;
-  for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
-  HostTensor& t = m->arena.host[name];
-  t.d.assign(data, data + n);
-  t.shape.assign(shape, shape + ndim);
-  return 0;
+  return kk_host_load_tensor("kk_mimi_load_tensor", m ? &m->arena.host : nullptr, m && m->finalized, name, shape, ndim, data);
 }
 
 extern "C" int kk_mimi_finalize(kk_mimi* m, void* stream) {

@@ -1,5 +1,5 @@
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11), counter-based: shared by the Kokoro noise source
-// (kk_source.hip: Box-Muller on top), the CSM sampler's device uniforms (kk_csm.hip) and the Whisper pick's Gumbel noise (kk_whisper_text.hip).
+// (kk_source.hip: Box-Muller on top), the CSM sampler's device uniforms (kk_csm.hip) and the Whisper pick's Gumbel noise (kk_whisper_text_kernels.hip).
 #pragma once
 #include <stdint.h>
 

@@ -285,19 +285,6 @@ int check_cfg(const kk_whisper_config& c) {
   if (c.n_audio_state % 128 != 0 || c.n_audio_state > 2048) return kk_fail("kk_whisper_create: n_audio_state must be a multiple of 128, at most 2048");
   return 0;
 }
-
-const HostTensor* want(kk_whisper* m, const std::string& name, std::initializer_list<int64_t> shape, std::string& err) {
-  auto it = m->host.find(name);
-  if (it == m->host.end()) {
-    if (err.empty()) err = "missing parameter: " + name;
-    return nullptr;
-  }
-  if (it->second.shape != std::vector<int64_t>(shape)) {
-    if (err.empty()) err = "unexpected shape for " + name;
-    return nullptr;
-  }
-  return &it->second;
-}
 }  // namespace
 
 extern "C" int kk_whisper_create(const kk_whisper_config* cfg, kk_whisper** out) {
@@ -317,14 +304,7 @@ extern "C" void kk_whisper_destroy(kk_whisper* m) {
 }
 
 extern "C" int kk_whisper_load_tensor(kk_whisper* m, const char* name, const int64_t* shape, int ndim, const float* data) {
-  if (!m || !name || !shape || !data || ndim < 1) return kk_fail("kk_whisper_load_tensor: bad argument");
-  if (m->finalized) return kk_fail("kk_whisper_load_tensor: model already finalized");
-  size_t n = 1;
-  for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
-  HostTensor& t = m->host[name];
-  t.d.assign(data, data + n);
-  t.shape.assign(shape, shape + ndim);
-  return 0;
+  return kk_host_load_tensor("kk_whisper_load_tensor", m ? &m->host : nullptr, m && m->finalized, name, shape, ndim, data);
 }
 
 extern "C" int kk_whisper_finalize(kk_whisper* m, void* stream) {
@@ -366,15 +346,12 @@ extern "C" int kk_whisper_finalize(kk_whisper* m, void* stream) {
       return kk_fail("kk_whisper_finalize: upload failed");
     return 0;
   };
-  auto bias = [&](const WLin& l, const std::string& name, int off, int n) {
-    if (const HostTensor* t = want(m, name, {n}, err)) memcpy(&fpack[l.b + off], t->d.data(), (size_t)n * 4);
-  };
   auto vecp = [&](size_t off, const std::string& name, int n) {
-    if (const HostTensor* t = want(m, name, {n}, err)) memcpy(&fpack[off], t->d.data(), (size_t)n * 4);
+    if (const HostTensor* t = kk_host_want(m->host, name, {n}, err)) memcpy(&fpack[off], t->d.data(), (size_t)n * 4);
   };
   // rows [o0, o0 + N) of a Linear's pack from an [N][K] matrix
   auto lin_rows = [&](const WLin& l, const std::string& name, int o0, int N, int K) {
-    const HostTensor* t = want(m, name, {N, K}, err);
+    const HostTensor* t = kk_host_want(m->host, name, {N, K}, err);
     if (!t) return;
     for (int o = 0; o < N; ++o)
       for (int i = 0; i < K; ++i) wpack[(size_t)(o0 + o) * l.CinP + i] = f32_to_bf16_rne(t->d[(size_t)o * K + i]);
@@ -382,16 +359,16 @@ extern "C" int kk_whisper_finalize(kk_whisper* m, void* stream) {
   };
   {  // conv1: MLX layout [O][K][I] -> [tap][O][128]
     wpack.assign((size_t)3 * D * 128, 0);
-    if (const HostTensor* t = want(m, "encoder.conv1.weight", {D, 3, M}, err))
+    if (const HostTensor* t = kk_host_want(m->host, "encoder.conv1.weight", {D, 3, M}, err))
       for (int o = 0; o < D; ++o)
         for (int k = 0; k < 3; ++k)
           for (int i = 0; i < M; ++i) wpack[((size_t)k * D + o) * 128 + i] = f32_to_bf16_rne(t->d[((size_t)o * 3 + k) * M + i]);
-    bias(m->conv1, "encoder.conv1.bias", 0, D);
+    vecp(m->conv1.b, "encoder.conv1.bias", D);
     KK_TRY(flush(m->conv1));
   }
   {  // conv2 over row pairs (x[2p] | x[2p + 1]): out[q] = [0 | W0] pair[q - 1] + [W1 | W2] pair[q]
     wpack.assign((size_t)2 * D * 2 * D, 0);
-    if (const HostTensor* t = want(m, "encoder.conv2.weight", {D, 3, D}, err))
+    if (const HostTensor* t = kk_host_want(m->host, "encoder.conv2.weight", {D, 3, D}, err))
       for (int o = 0; o < D; ++o)
         for (int i = 0; i < D; ++i) {
           const float* w = &t->d[(size_t)o * 3 * D + i];
@@ -400,7 +377,7 @@ extern "C" int kk_whisper_finalize(kk_whisper* m, void* stream) {
           wpack[((size_t)1 * D + o) * 2 * D + D + i] = f32_to_bf16_rne(w[2 * D]);
         }
     m->host.erase("encoder.conv2.weight");
-    bias(m->conv2, "encoder.conv2.bias", 0, D);
+    vecp(m->conv2.b, "encoder.conv2.bias", D);
     KK_TRY(flush(m->conv2));
   }
   for (int li = 0; li < c.n_audio_layer; ++li) {
@@ -410,19 +387,19 @@ extern "C" int kk_whisper_finalize(kk_whisper* m, void* stream) {
     lin_rows(L.qkv, p + "attn.query.weight", 0, D, D);
     lin_rows(L.qkv, p + "attn.key.weight", D, D, D);
     lin_rows(L.qkv, p + "attn.value.weight", 2 * D, D, D);
-    bias(L.qkv, p + "attn.query.bias", 0, D);  // the key has no bias: its third stays zero
-    bias(L.qkv, p + "attn.value.bias", 2 * D, D);
+    vecp(L.qkv.b, p + "attn.query.bias", D);  // the key has no bias: its third stays zero
+    vecp(L.qkv.b + 2 * D, p + "attn.value.bias", D);
     KK_TRY(flush(L.qkv));
     wpack.assign((size_t)D * D, 0);
     lin_rows(L.out, p + "attn.out.weight", 0, D, D);
-    bias(L.out, p + "attn.out.bias", 0, D);
+    vecp(L.out.b, p + "attn.out.bias", D);
     KK_TRY(flush(L.out));
     wpack.assign((size_t)4 * D * D, 0);
     lin_rows(L.mlp1, p + "mlp1.weight", 0, 4 * D, D);
-    bias(L.mlp1, p + "mlp1.bias", 0, 4 * D);
+    vecp(L.mlp1.b, p + "mlp1.bias", 4 * D);
     KK_TRY(flush(L.mlp1));
     lin_rows(L.mlp2, p + "mlp2.weight", 0, D, 4 * D);
-    bias(L.mlp2, p + "mlp2.bias", 0, D);
+    vecp(L.mlp2.b, p + "mlp2.bias", D);
     KK_TRY(flush(L.mlp2));
     vecp(L.attn_ln_w, p + "attn_ln.weight", D); vecp(L.attn_ln_b, p + "attn_ln.bias", D);
     vecp(L.mlp_ln_w, p + "mlp_ln.weight", D); vecp(L.mlp_ln_b, p + "mlp_ln.bias", D);

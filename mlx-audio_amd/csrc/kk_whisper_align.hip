@@ -1,7 +1,7 @@
 // Whisper, token timestamps from cross-attention (gfx950): the raw scores of selected heads, the alignment matrix and the dynamic time warping of
 // mlx_audio/stt/models/whisper/timing.py:19-100, 143-157 and whisper.py:125-130; DESIGN 8h.
 //
-// The invariant of kk_whisper_text.hip holds here too: an item's (a row's) bits depend on that item's inputs alone.  Reduction orders are fixed,
+// The invariant of kk_whisper_text_kernels.hip holds here too: an item's (a row's) bits depend on that item's inputs alone.  Reduction orders are fixed,
 // nothing is accumulated with floating-point atomics, and every loop bound is a function of the sizes, never of the data.
 //
 // ---- qk_rows: out[sel][row][key] = 64^-0.5 q . k, the score half of attn_rows ---------------------------------------------------------------

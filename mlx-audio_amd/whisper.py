@@ -2,7 +2,7 @@
 audio.py:12-82, `ModelDimensions`, and `Model` with `embed_audio` / `load_weights` / `from_pretrained` (whisper.py:67-78, 251-353) and, at token
 level, `logits`, `detect_language` and `decode` (whisper.py:298, decoding.py; the options, results and special tokens live in whisper_decoding.py
 and are re-exported here).  The arithmetic runs in libkokoro_hip.so (kk_op_log_mel, kk_whisper_*, csrc/kk_whisper.hip; kk_whisper_text_*,
-kk_op_whisper_*, csrc/kk_whisper_text.hip); PyTorch allocates device memory and provides the stream.
+kk_op_whisper_*, csrc/kk_whisper_text.hip with the kernels of csrc/kk_whisper_text_kernels.hip); PyTorch allocates device memory and provides the stream.
 
 The text side is built when a checkpoint holds the COMPLETE `decoder.*` set; otherwise the model is encoder-only and `logits`, `decode`,
 `detect_language`, `forward_with_cross_qk` and the alignment heads raise NotImplementedError("text decoder: not built").  `generate` (transcription of

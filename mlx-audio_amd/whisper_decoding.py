@@ -1,6 +1,6 @@
 """Host mirror of the TEXT side of the reference's Whisper at token level: the decoder's weight table, the special-token ids, `DecodingOptions` /
 `DecodingResult`, `detect_language` and the greedy `DecodingTask` of mlx_audio/stt/models/whisper/decoding.py:20-129, 398-742.  The arithmetic runs
-in libkokoro_hip.so (kk_whisper_text_*, kk_op_whisper_*, csrc/kk_whisper_text.hip): the decoder forward with its K/V caches, and ONE pick
+in libkokoro_hip.so (kk_whisper_text_*, kk_op_whisper_*; the handle in csrc/kk_whisper_text.hip, its kernels in csrc/kk_whisper_text_kernels.hip): the decoder forward with its K/V caches, and ONE pick
 launch per step that applies the logit filters, takes the arg-maximum and the log-probability and updates the rows' state on the device.  The host
 looks at a device counter of unfinished rows every `eos_check_interval` steps.
 

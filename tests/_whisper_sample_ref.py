@@ -1,4 +1,4 @@
-"""The sampled pick of the Whisper text side (csrc/kk_whisper_text.hip, kk_op_whisper_pick_sampled) restated in numpy: Philox4x32-10 in exact
+"""The sampled pick of the Whisper text side (csrc/kk_whisper_text_kernels.hip, kk_op_whisper_pick_sampled) restated in numpy: Philox4x32-10 in exact
 integer arithmetic (vectorised `_sampler_ref.philox4`), the uniform mapping `philox_open`, Gumbel scores in float64 on `_whisper_text_ref.filter_logits`,
 the admissible set of a draw, a `SampledRow` mirroring `GreedyRow`, and the ranker.  Also the inputs of the GPU kernel tests, so that the CPU test can
 evaluate the cap on draws with more than one admissible token on exactly those inputs.

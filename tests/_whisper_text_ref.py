@@ -1,4 +1,4 @@
-"""CPU references of the Whisper text side (mlx-audio_amd/whisper_decoding.py, csrc/kk_whisper_text.hip): synthetic decoder weights under
+"""CPU references of the Whisper text side (mlx-audio_amd/whisper_decoding.py, csrc/kk_whisper_text.hip and kk_whisper_text_kernels.hip): synthetic decoder weights under
 the MLX names, transformers' WhisperDecoder carrying them (the independent yardstick of the GPU tests), and a numpy restatement of the logit filters and
 the greedy update of mlx_audio/stt/models/whisper/decoding.py:255-395 in this repository's own words.  tests/test_whisper_text_cpu.py pins the
 restatement against transformers' logits processors; the GPU tests compare the pick kernel against it."""

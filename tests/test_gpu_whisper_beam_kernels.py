@@ -1,4 +1,4 @@
-"""The beam-search kernels of the Whisper text side (csrc/kk_whisper_text.hip) on their own, through the raw entries: the top-(K + 1) of a row
+"""The beam-search kernels of the Whisper text side (csrc/kk_whisper_text_kernels.hip) on their own, through the raw entries: the top-(K + 1) of a row
 against numpy, the select of a window against the restatement (tests/_whisper_beam_ref.py) with the owner tables against parent pointers followed on
 the host, the owned attention against the direct one on gathered keys bit for bit, and the refusals.  tests/test_whisper_beam_cpu.py shows that every
 decision compared here is decided by at least 1e-3."""

@@ -1,4 +1,4 @@
-"""The packed-weight kernels of the Whisper text side (csrc/kk_whisper_text.hip) on their own, through the raw kk_op_* entries: the skinny-M
+"""The packed-weight kernels of the Whisper text side (csrc/kk_whisper_text_kernels.hip) on their own, through the raw kk_op_* entries: the skinny-M
 Linear and the token gather on an MLX affine-quantised matrix must carry, bit for bit, what their bf16 twins give on the dequantised matrix rounded to
 bf16 -- every value is decoded to exactly that bf16 and the arithmetic behind it is the bf16 kernel's, in its order."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""The sampled pick of the Whisper text side (csrc/kk_whisper_text.hip) on its own, through the raw kk_op_whisper_pick_sampled entry: against
+"""The sampled pick of the Whisper text side (csrc/kk_whisper_text_kernels.hip) on its own, through the raw kk_op_whisper_pick_sampled entry: against
 the numpy restatement of its random contract (tests/_whisper_sample_ref.py), its determinism, masking, the distribution it draws from and its refusals."""
 import ctypes as C
 import os

@@ -1,4 +1,4 @@
-"""The decode-step kernels of the Whisper text side (csrc/kk_whisper_text.hip) on their own, through the raw kk_op_* entries: one-query
+"""The decode-step kernels of the Whisper text side (csrc/kk_whisper_text_kernels.hip) on their own, through the raw kk_op_* entries: one-query
 attention over a bf16 K/V store, the skinny-M Linear on bf16 weights, the embedding and the token pick, each against a float64 / numpy reference with
 a bound derived from the arithmetic, and each for the project's invariant: a row's bits do not depend on the rows beside it."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""Times of Whisper serving (mlx-audio_amd/whisper_serve.py, row mode of csrc/kk_whisper_text.hip) at the whisper-large-v3-turbo decoder shape
+"""Times of Whisper serving (mlx-audio_amd/whisper_serve.py, row mode of csrc/kk_whisper_text.hip on the kernels of csrc/kk_whisper_text_kernels.hip) at the whisper-large-v3-turbo decoder shape
 on synthetic weights (tools/bench_whisper_text.py's model), in ONE process:
 
  (a) the round with 8 live step rows (rows_forward of 8 one-token items + rows_pick) next to the static decode step at B = 8 (forward S = 1 + pick of

@@ -1,4 +1,4 @@
-"""Times of the Whisper text side (mlx-audio_amd/whisper_decoding.py, csrc/kk_whisper_text.hip) at the whisper-large-v3-turbo decoder shape
+"""Times of the Whisper text side (mlx-audio_amd/whisper_decoding.py, csrc/kk_whisper_text.hip and kk_whisper_text_kernels.hip) at the whisper-large-v3-turbo decoder shape
 -- 4 layers of width 1280, 20 heads, 51866 tokens, 1500 audio positions -- on synthetic weights, for B = 1 and 8: `set_audio` (the cross K/V of a
 window), a 4-token prefill, and the steady-state decode step (one forward of S = 1 plus one pick) at a fixed position, with the bytes the step must
 read and the rate that makes of the measured time.  Every figure is the median of `--steps` samples after `--warmup`, each sample `--inner` calls
