@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 24  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 25  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -69,7 +69,9 @@ extern "C" {
                                kk_op_whisper_attn_rows_owned, kk_whisper_beam_bufs, kk_whisper_text_beam_state_bytes, kk_whisper_text_beam_setup,
                                kk_whisper_text_beam_not_complete, kk_whisper_text_beam_read);
                             24: quantised Whisper checkpoints, decoder matrices packed in device memory (kk_whisper_text_load_quantized,
-                               kk_whisper_text_weight_info, kk_whisper_text_weight_fallback, kk_op_whisper_linear_rows_q, kk_op_whisper_embed_q) */
+                               kk_whisper_text_weight_info, kk_whisper_text_weight_fallback, kk_op_whisper_linear_rows_q, kk_op_whisper_embed_q);
+                            25: Whisper long-form transcription: a sampled pick per row of row mode and windows cut out of whole-file spectrograms
+                               (kk_whisper_text_rows_set_draw, kk_op_mel_windows) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -843,6 +845,14 @@ int kk_op_log_mel(void* stream, int B, const float* x, long long ldx, const int3
  * softmax(q k^T 64^-0.5) v over the first T rows (the reference's 64^-0.25 on each side is the same product); rows >= T are neither read as keys
  * nor written.  An item's bits do not depend on B. */
 int kk_op_attention_long(void* stream, int B, const void* qkv, int ld, int T_rows, int T, int heads, void* out, int ldo);
+/* The windows of a transcription round, cut out of whole-file spectrograms (whisper.py:641-644: mel[seek : seek + size], then pad_or_trim to W):
+ * row r copies frames first[r] .. first[r] + size[r] - 1 of src[r] (DEVICE fp32 [frames[r]][n_mels], 16-byte aligned; the rows may lie in different
+ * allocations) to out[r][0 .. size[r]) and writes zeros to out[r][size[r] .. W).  src, frames, first and size are HOST arrays of R entries that go to
+ * the kernel by value: 1 <= R <= KK_WHISPER_MAX_ROWS, 0 <= size[r] <= W, first[r] >= 0, first[r] + size[r] <= frames[r] (refused otherwise before
+ * anything is launched; src[r] may be null only where size[r] = 0).  out DEVICE fp32 [R][W][n_mels], 16-byte aligned.  n_mels 80 or 128.  One launch,
+ * 16-byte loads and stores, no arithmetic. */
+int kk_op_mel_windows(void* stream, int R, const float* const* src, const int32_t* frames, const int32_t* first, const int32_t* size, int W, int n_mels,
+                      float* out);
 
 typedef struct kk_whisper kk_whisper;
 /* the audio fields of ModelDimensions (whisper.py:67-78); n_audio_state / n_audio_head must be 64, n_mels 80 or 128 */
@@ -1078,6 +1088,10 @@ int kk_whisper_text_rows_flags(kk_whisper_text* m, void* stream, int32_t* ended)
 int kk_whisper_text_rows_read(kk_whisper_text* m, void* stream, int row, int32_t* tokens, int cap, kk_whisper_pick_state* state, float* kept);
 /* initial token `index` of a row from DEVICE memory (the detected language, with no host round trip); never synchronises */
 int kk_whisper_text_rows_set_token(kk_whisper_text* m, void* stream, int row, int index, const int32_t* token);
+/* after rows_admit (which leaves the row greedy): the row's picks draw at `temperature` on the Philox key `seed` and the stream id `stream_id`, with
+ * the bits kk_op_whisper_pick_sampled gives the same logits, parameters, state, seed and stream -- in the same ONE launch of rows_pick that picks
+ * the greedy rows.  Refused: temperature <= 0 or not finite, a row outside [0, max_rows) or never admitted.  Synchronises. */
+int kk_whisper_text_rows_set_draw(kk_whisper_text* m, void* stream, int row, float temperature, uint64_t seed, uint32_t stream_id);
 
 /* =====================================================================================================================
  * Whisper, token timestamps from cross-attention: timing.py:19-100, 143-157 and Model.forward_with_cross_qk (csrc/kk_whisper_align.hip,

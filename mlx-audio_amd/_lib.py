@@ -296,6 +296,8 @@ SIGNATURES = {
     "kk_whisper_text_rows_flags": (_i, [_vp, _vp, _vp]),
     "kk_whisper_text_rows_read": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
     "kk_whisper_text_rows_set_token": (_i, [_vp, _vp, _i, _i, _vp]),
+    "kk_whisper_text_rows_set_draw": (_i, [_vp, _vp, _i, C.c_float, C.c_uint64, C.c_uint32]),
+    "kk_op_mel_windows": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "kk_op_whisper_qk_rows_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "kk_op_whisper_qk_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, C.c_longlong]),
     "kk_op_whisper_align_matrix_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
@@ -353,7 +355,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 24:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 25:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

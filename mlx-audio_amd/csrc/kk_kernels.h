@@ -395,5 +395,12 @@ int kk_launch_whisper_gather_rows(hipStream_t st, int n, const KKRowGather& sel,
 struct KKPickSel {  // block j picks for decoder row row[j] on logits row logit[j]
   int row[KK_WHISPER_MAX_ROWS], logit[KK_WHISPER_MAX_ROWS];
 };
+// what a sampled pick adds to a row's arguments: 1 / temperature (0: the row picks greedily), the Philox key and the row's stream id
+struct PickDraw {
+  float inv_t;
+  uint64_t seed;
+  uint32_t stream;
+};
+// draws: [max_rows], indexed by decoder row like params and state
 int kk_launch_whisper_pick_rows(hipStream_t st, int n, const KKPickSel& sel, const float* logits, long long ldl, const kk_whisper_pick_params* params,
-                                const uint32_t* suppress, int words, kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next);
+                                const uint32_t* suppress, int words, const PickDraw* draws, kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next);

@@ -246,6 +246,60 @@ extern "C" int kk_op_log_mel(void* stream, int B, const float* x, long long ldx,
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------- mel windows
+// The windows of a transcription round: row r is `size[r]` frames of its file's spectrogram from frame first[r] on, then zeros up to W
+// frames.  A frame is n_mels floats (320 or 512 bytes), so a window is a run of 16-byte words in both the source and the output: thread t of
+// block x moves words 1024 x + t + 256 u, u = 0 .. 3, all four requested before the first is stored.  No arithmetic.
+namespace {
+struct KKMelWindows {  // by value: the rows may lie in different allocations
+  const float* src[KK_WHISPER_MAX_ROWS];
+  int first[KK_WHISPER_MAX_ROWS], size[KK_WHISPER_MAX_ROWS];
+};
+__global__ __launch_bounds__(256) void mel_windows_kernel(KKMelWindows t, int W, int n_mels, float* out) {
+  const int r = blockIdx.y, q = n_mels / 4;  // q: 16-byte words per frame
+  const long long total = (long long)W * q, have = (long long)t.size[r] * q;
+  const f32x4* src = (const f32x4*)t.src[r] + (long long)t.first[r] * q;
+  f32x4* dst = (f32x4*)out + (long long)r * total;
+  const long long base = (long long)blockIdx.x * 1024 + threadIdx.x;
+  f32x4 v[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const long long i = base + 256 * u;
+    v[u] = i < have ? src[i] : f32x4{0.f, 0.f, 0.f, 0.f};  // (i < have <= total: never past the file's frames, which the host has checked)
+  }
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const long long i = base + 256 * u;
+    if (i < total) dst[i] = v[u];
+  }
+}
+}  // namespace
+
+extern "C" int kk_op_mel_windows(void* stream, int R, const float* const* src, const int32_t* frames, const int32_t* first, const int32_t* size, int W, int n_mels,
+                                 float* out) {
+  const char* who = "kk_op_mel_windows";
+  if (!src || !frames || !first || !size || !out) return kk_failf("%s: null argument", who);
+  if (R < 1 || R > KK_WHISPER_MAX_ROWS) return kk_failf("%s: R = %d is outside [1, %d]", who, R, KK_WHISPER_MAX_ROWS);
+  if (W < 1) return kk_failf("%s: W = %d must be >= 1", who, W);
+  if (n_mels != 80 && n_mels != 128) return kk_failf("%s: n_mels must be 80 or 128", who);
+  if ((uintptr_t)out & 15) return kk_failf("%s: out must be 16-byte aligned", who);
+  KKMelWindows t;
+  memset(&t, 0, sizeof t);
+  for (int r = 0; r < R; ++r) {
+    if (size[r] < 0 || size[r] > W) return kk_failf("%s: row %d: size = %d is outside [0, W = %d]", who, r, size[r], W);
+    if (first[r] < 0 || frames[r] < 0 || (long long)first[r] + size[r] > frames[r])
+      return kk_failf("%s: row %d: frames %d .. %lld are outside the source's %d", who, r, first[r], (long long)first[r] + size[r], frames[r]);
+    if (size[r] > 0 && (!src[r] || ((uintptr_t)src[r] & 15))) return kk_failf("%s: row %d: the source must be a 16-byte aligned device pointer", who, r);
+    t.src[r] = src[r];
+    t.first[r] = first[r];
+    t.size[r] = size[r];
+  }
+  const long long total = (long long)W * (n_mels / 4);
+  hipLaunchKernelGGL(mel_windows_kernel, dim3((unsigned)((total + 1023) / 1024), R), dim3(256), 0, (hipStream_t)stream, t, W, n_mels, out);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int kk_op_attention_long(void* stream, int B, const void* qkv, int ld, int T_rows, int T, int heads, void* out, int ldo) {
   if (!qkv || !out) return kk_fail("kk_op_attention_long: null argument");
   if (B < 1 || heads < 1 || T < 1 || T > T_rows) return kk_fail("kk_op_attention_long: bad argument (need B, heads >= 1 and 1 <= T <= T_rows)");

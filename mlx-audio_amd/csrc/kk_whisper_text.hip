@@ -16,6 +16,7 @@
 // ---- row mode (the end of this file) ---------------------------------------------------------------------------------------------------
 //   Rows with their own window, position, pick parameters and lifetime in a second state buffer.  A round is the window's launch sequence behind
 //   text_plan_kernel, which fills the per-row index arrays and tokens from a table of items passed as the launch's argument.
+//   A row picks greedily unless rows_set_draw gave it a draw after its admission; the round's one pick launch serves both kinds.
 #include "kk_host.h"
 #include "kk_philox.h"
 #include "../../include/kokoro_hip.h"
@@ -774,6 +775,7 @@ struct RowsState {  // the caller's row-mode state buffer
   kk_whisper_pick_state* rows;     // [max_rows]; .ended is the row's flag
   int32_t *tokens, *init, *next, *not_ended;  // sampled [max_rows][n_text_ctx], initial [max_rows][n_text_ctx], [max_rows], the reset kernel's counter
   float* kept;                     // [max_rows][2][n_vocab]
+  PickDraw* draws;                 // [max_rows]; inv_t 0: the row picks greedily (rows_admit), > 0: it samples (rows_set_draw).  Behind everything older
 };
 void plan_rows_state(const kk_whisper_text_config& c, int N, Workspace& ws, RowsState& s) {
   const size_t D = c.n_text_state, L = c.n_text_layer;
@@ -787,6 +789,7 @@ void plan_rows_state(const kk_whisper_text_config& c, int N, Workspace& ws, Rows
   s.next = (int32_t*)ws.raw((size_t)N * 4);
   s.not_ended = (int32_t*)ws.raw(4);
   s.kept = (float*)ws.raw((size_t)N * 2 * c.n_vocab * 4);
+  s.draws = (PickDraw*)ws.raw((size_t)N * sizeof(PickDraw));
 }
 struct RowsWork {
   TextWork t;    // t.feat: ONE window (rows_admit)
@@ -839,6 +842,7 @@ extern "C" int kk_whisper_text_rows_open(kk_whisper_text* m, void* stream, int m
   plan_rows_state(m->cfg, max_rows, ss, s);
   if (ss.oom) return kk_failf("%s: state buffer too small", who);
   KK_TRY(kk_op_whisper_pick_reset(stream, max_rows, s.rows, s.not_ended));  // every row's flag reads 0 before its first admission
+  if (hipMemsetAsync(s.draws, 0, (size_t)max_rows * sizeof(PickDraw), (hipStream_t)stream) != hipSuccess) return kk_failf("%s: clearing the draws failed", who);
   m->rows_state = (char*)state;
   m->rows.assign(max_rows, kk_whisper_text::Row());
   m->rows_logits = nullptr;
@@ -867,6 +871,7 @@ extern "C" int kk_whisper_text_rows_admit(kk_whisper_text* m, void* stream, int 
   if (hipMemcpyAsync(s.init + (size_t)row * c.n_text_ctx, tokens, (size_t)n * 4, hipMemcpyHostToDevice, st) != hipSuccess) return kk_failf("%s: upload failed", who);
   KK_TRY(upload_pick_params(who, st, c, params, suppress, s.params + row, s.suppress + (size_t)row * mask_words(c)));
   KK_TRY(kk_op_whisper_pick_reset(stream, 1, s.rows + row, s.not_ended));
+  if (hipMemsetAsync(s.draws + row, 0, sizeof(PickDraw), st) != hipSuccess) return kk_failf("%s: clearing the draw failed", who);  // greedy until rows_set_draw
   m->rows[row].admitted = true;
   m->rows[row].n_init = n;
   return 0;
@@ -969,9 +974,24 @@ extern "C" int kk_whisper_text_rows_pick(kk_whisper_text* m, void* stream, const
     sel.logit[j] = m->rows[rows[j]].logit;
   }
   const kk_whisper_text_config& c = m->cfg;
-  KK_TRY(kk_launch_whisper_pick_rows((hipStream_t)stream, n, sel, m->rows_logits, (long long)c.n_vocab, s.params, s.suppress, (int)mask_words(c), s.rows, s.tokens,
+  KK_TRY(kk_launch_whisper_pick_rows((hipStream_t)stream, n, sel, m->rows_logits, (long long)c.n_vocab, s.params, s.suppress, (int)mask_words(c), s.draws, s.rows, s.tokens,
                                      c.n_text_ctx, s.next));
   for (int j = 0; j < n; ++j) m->rows[rows[j]].logit = -2;  // picked: the row can step on its token, and is not picked twice on the same logits
+  return 0;
+}
+
+extern "C" int kk_whisper_text_rows_set_draw(kk_whisper_text* m, void* stream, int row, float temperature, uint64_t seed, uint32_t stream_id) {
+  const char* who = "kk_whisper_text_rows_set_draw";
+  const float inv_t = 1.0f / temperature;
+  if (!(temperature > 0.f) || !std::isfinite(temperature) || !std::isfinite(inv_t))
+    return kk_failf("%s: temperature must be finite and > 0 (a row picks greedily from its admission on: leave this call out)", who);
+  RowsState s;
+  KK_TRY(rows_bound(who, m, s));
+  KK_TRY(rows_check_row(who, m, row, true));
+  const PickDraw dr{inv_t, seed, stream_id};
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemcpyAsync(s.draws + row, &dr, sizeof dr, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return kk_failf("%s: upload failed", who);  // synchronised: dr goes away
   return 0;
 }
 

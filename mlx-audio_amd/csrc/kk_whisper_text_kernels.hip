@@ -33,6 +33,7 @@
 //   the launch-wide kernel (one params, one bitmask) and the per-row kernel of row mode (each row its own; the row's state.ended is its flag).
 //   The sampled form (temperature > 0) is the same body with one more branch in pass B: Gumbel-max on Philox uniforms beside the sum of
 //   exponentials, so a sampled step reads the row's logits as often as a greedy one; a row's draws depend on (seed, its stream id, its history) alone.
+//   The per-row kernel takes either form per block from the row's draw (PickDraw, set by kk_whisper_text_rows_set_draw).
 #include "kk_host.h"
 #include "kk_philox.h"
 #include "../../include/kokoro_hip.h"
@@ -403,12 +404,7 @@ __device__ __forceinline__ Top top_block(Top v, Top* sh) {  // all 1024 threads;
   return r;
 }
 
-// what a sampled pick adds to a row's arguments: 1 / temperature, the Philox key and the row's stream id
-struct PickDraw {
-  float inv_t;
-  uint64_t seed;
-  uint32_t stream;
-};
+// (PickDraw, what a sampled pick adds to a row's arguments, lives in kk_kernels.h: the row mode keeps one per row)
 // what the beam's top-k adds: the offers it writes (C pairs, descending) and the LDS of its block maximum
 struct PickTop {
   int C;
@@ -602,13 +598,20 @@ __global__ __launch_bounds__(1024) void pick_sampled_kernel(const float* logits,
                  PickDraw{inv_t, seed, streams[b]});
 }
 
-// per-row: block j picks for decoder row sel.row[j] on logits row sel.logit[j], with that row's params, bitmask (`words` words each), state and store
+// per-row: block j picks for decoder row sel.row[j] on logits row sel.logit[j], with that row's params, bitmask (`words` words each), draw, state and
+// store.  A row whose draw has inv_t > 0 samples (the bits of pick_sampled_kernel), every other row picks greedily (the bits of pick_kernel); the
+// branch is uniform over the block, so each block runs one of the two bodies and the barriers inside them are met by all its threads.
 __global__ __launch_bounds__(1024) void pick_rows_kernel(KKPickSel sel, const float* logits, long long ldl, const kk_whisper_pick_params* params,
-                                                         const uint32_t* suppress, int words, kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next) {
+                                                         const uint32_t* suppress, int words, const PickDraw* draws, kk_whisper_pick_state* state, int32_t* tokens,
+                                                         int cap, int32_t* next) {
   __shared__ Osm sh[16];
   const int r = sel.row[blockIdx.x];
-  pick_row<PICK_GREEDY>(logits + (long long)sel.logit[blockIdx.x] * ldl, params[r], suppress + (long long)r * words, state + r, tokens + (long long)r * cap, cap, next + r,
-                  nullptr, sh);
+  const float* lg = logits + (long long)sel.logit[blockIdx.x] * ldl;
+  const PickDraw dr = draws[r];
+  if (dr.inv_t > 0.f)
+    pick_row<PICK_SAMPLE>(lg, params[r], suppress + (long long)r * words, state + r, tokens + (long long)r * cap, cap, next + r, nullptr, sh, dr);
+  else
+    pick_row<PICK_GREEDY>(lg, params[r], suppress + (long long)r * words, state + r, tokens + (long long)r * cap, cap, next + r, nullptr, sh);
 }
 
 __global__ void pick_reset_kernel(kk_whisper_pick_state* state, int B, int32_t* not_ended) {
@@ -867,8 +870,8 @@ int kk_launch_whisper_gather_rows(hipStream_t st, int n, const KKRowGather& sel,
 }
 
 int kk_launch_whisper_pick_rows(hipStream_t st, int n, const KKPickSel& sel, const float* logits, long long ldl, const kk_whisper_pick_params* params,
-                                const uint32_t* suppress, int words, kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next) {
-  hipLaunchKernelGGL(pick_rows_kernel, dim3(n), dim3(1024), 0, st, sel, logits, ldl, params, suppress, words, state, tokens, cap, next);
+                                const uint32_t* suppress, int words, const PickDraw* draws, kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next) {
+  hipLaunchKernelGGL(pick_rows_kernel, dim3(n), dim3(1024), 0, st, sel, logits, ldl, params, suppress, words, draws, state, tokens, cap, next);
   KK_CHECK_LAUNCH();
   return 0;
 }

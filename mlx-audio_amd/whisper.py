@@ -5,9 +5,9 @@ and are re-exported here).  The arithmetic runs in libkokoro_hip.so (kk_op_log_m
 kk_op_whisper_*, csrc/kk_whisper_text.hip with the kernels of csrc/kk_whisper_text_kernels.hip); PyTorch allocates device memory and provides the stream.
 
 The text side is built when a checkpoint holds the COMPLETE `decoder.*` set; otherwise the model is encoder-only and `logits`, `decode`,
-`detect_language`, `forward_with_cross_qk` and the alignment heads raise NotImplementedError("text decoder: not built").  `generate` (transcription of
-long audio, which needs the tokenizer) is not built.  `Model.decoder_weights` keeps the non-encoder tensors of a checkpoint on the host, untouched,
-either way -- an `alignment_heads` entry included: the heads are set with `set_alignment_heads`, never parsed from a checkpoint.
+`detect_language`, `forward_with_cross_qk` and the alignment heads raise NotImplementedError("text decoder: not built").  `generate` keeps raising;
+transcription of long audio is `Model.transcribe` (whisper_transcribe.py), with `mel_windows` here cutting a round's windows on the device.
+`Model.decoder_weights` keeps the non-encoder tensors of a checkpoint on the host, untouched, either way -- an `alignment_heads` entry included: the heads are set with `set_alignment_heads`, never parsed from a checkpoint.
 
 Token timestamps (`Model.alignment_heads`, `set_alignment_heads`, `forward_with_cross_qk`, whisper.py:272-303; `find_alignment`, `dtw`, `median_filter`,
 `TokenTiming`, `WordTiming` of whisper_timing.py, re-exported here) run on kk_op_whisper_qk_rows / align_matrix / dtw and kk_whisper_text_forward_qk
@@ -174,6 +174,38 @@ def log_mel_rows(x, lengths, n_mels: int = 80, padding: int = 0):
         _lib.check(lib.kk_op_log_mel(st, B, C.c_void_p(x.data_ptr()), ldx, C.c_void_p(n_dev.data_ptr()), padding, n_mels,
                                      C.c_void_p(window.data_ptr()), C.c_void_p(cs.data_ptr()), C.c_void_p(fbT.data_ptr()),
                                      C.c_void_p(partial.data_ptr()), C.c_void_p(out.data_ptr()), F_rows), "kk_op_log_mel")
+    return out
+
+
+def mel_windows(mels, seeks, sizes, W: int):
+    """The windows of a transcription round in ONE launch (kk_op_mel_windows): row r is `pad_or_trim(mels[r][seeks[r] : seeks[r] + sizes[r]], W,
+    axis=-2)` (whisper.py:592-596).  mels: fp32 device tensors (frames, n_mels), one per row -- views of different allocations are fine, the same
+    tensor may serve several rows; 0 <= sizes[r] <= W and seeks[r] + sizes[r] <= frames of row r.  -> fp32 device (R, W, n_mels)."""
+    import torch
+
+    from . import _lib
+
+    lib = _lib.load()
+    R = len(mels)
+    if not 1 <= R <= _lib.WHISPER_MAX_ROWS or len(seeks) != R or len(sizes) != R:
+        raise ValueError(f"mel_windows takes 1 .. {_lib.WHISPER_MAX_ROWS} spectrograms with one seek and one size each")
+    if W < 1:
+        raise ValueError("W must be >= 1")
+    n_mels = int(mels[0].shape[-1])
+    for m in mels:
+        if not _is_torch(m) or not m.is_cuda or m.dtype != torch.float32 or m.ndim != 2 or m.shape[1] != n_mels or not m.is_contiguous() or m.device != mels[0].device:
+            raise ValueError("mel_windows: every spectrogram must be a contiguous fp32 (frames, n_mels) tensor on one device")
+    for r in range(R):
+        if not 0 <= sizes[r] <= W or seeks[r] < 0 or seeks[r] + sizes[r] > mels[r].shape[0]:
+            raise ValueError(f"mel_windows: row {r}: frames {seeks[r]} .. {seeks[r] + sizes[r]} of {mels[r].shape[0]}, W = {W}")
+    dev = mels[0].device
+    src = (C.c_void_p * R)(*[m.data_ptr() for m in mels])
+    arr = lambda v: (C.c_int32 * R)(*[int(x) for x in v])  # noqa: E731
+    with torch.cuda.device(dev):
+        out = torch.empty((R, W, n_mels), dtype=torch.float32, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.kk_op_mel_windows(st, R, src, arr([m.shape[0] for m in mels]), arr(seeks), arr(sizes), W, n_mels, C.c_void_p(out.data_ptr())),
+                   "kk_op_mel_windows")
     return out
 
 
@@ -521,6 +553,15 @@ class Model:
 
     def generate(self, *a, **kw):
         raise NotImplementedError(_NOT_BUILT)
+
+    def transcribe(self, audio, **kw):
+        """whisper.py:355-866, the reference's `generate`, under OpenAI's name for it: one recording (1-D samples at 16 kHz) -> TranscribeResult, a list of
+        recordings -> a list, all of them on one running decoder batch; see whisper_transcribe.transcribe"""
+        if self._text is None:
+            raise NotImplementedError(_NOT_BUILT)
+        from .whisper_transcribe import transcribe
+
+        return transcribe(self, audio, **kw)
 
     def detect_language(self, *a, **kw):
         """decoding.py:20-79, see whisper_decoding.detect_language"""

@@ -618,6 +618,13 @@ class RowRuntime:
         _lib.check(self._lib.kk_whisper_text_rows_admit(self._h, self._stream(), row, C.c_void_p(features.data_ptr()), toks.ctypes.data_as(C.c_void_p), len(toks),
                                                         C.byref(params), sp, ws, wsn), "kk_whisper_text_rows_admit")
 
+    def set_draw(self, row: int, temperature: float, seed: int, stream: int):
+        """after admit (which leaves the row greedy): the row's picks draw at `temperature` on the Philox key `seed` and the stream id `stream`"""
+        from . import _lib
+
+        _lib.check(self._lib.kk_whisper_text_rows_set_draw(self._h, self._stream(), row, float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFF),
+                   "kk_whisper_text_rows_set_draw")
+
     def forward(self, items, out_rows):
         """items: (row, pos, count, from, keep, slot) tuples; out_rows: flat rows -> fp32 device (len(out_rows), V), alive until the next forward"""
         import torch

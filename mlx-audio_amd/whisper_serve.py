@@ -19,8 +19,12 @@ One round (`step`):
 A row that has ended keeps stepping and emits eot until the next poll notices, as in `decode`.  A request with `language=None` (or `task="lang_id"`)
 spends one extra round first; the arg-maximum over the language tokens goes into its initial tokens on the device, with no synchronisation.
 
-The scheduler talks to the model through an engine (`ModelEngine`); a fake engine tests it without a GPU.  Out of scope: the tokenizer, `generate`,
-temperature > 0 / best_of / beam search, hipGraph capture of the round, prefill on a side stream."""
+A request submitted with `submit_sampled` decodes at its own temperature: its row carries a draw (1 / T, Philox key, stream id) and the round's ONE
+pick launch samples it while it picks the greedy rows; its result is `model.sample`'s for that window alone.  `submit` itself keeps
+refusing a temperature.  `Model.transcribe` (whisper_transcribe.py) is the long-form loop on top of this batcher.
+
+The scheduler talks to the model through an engine (`ModelEngine`); a fake engine tests it without a GPU.  Out of scope: best_of groups and beam
+search inside the batcher, `generate` (see `Model.transcribe`), text-to-id encoding, hipGraph capture of the round, prefill on a side stream."""
 from __future__ import annotations
 
 import threading
@@ -77,8 +81,9 @@ class ModelEngine:
 
         self._rows = RowRuntime(self.model._text, max_rows)
 
-    def admit(self, row: int, x, init: Tuple[int, ...], options: DecodingOptions):
-        """-> the window's audio features (n_audio_ctx, n_audio_state); a mel goes through the encoder as the solo call's would"""
+    def admit(self, row: int, x, init: Tuple[int, ...], options: DecodingOptions, draw: Optional[Tuple[float, int, int]] = None):
+        """-> the window's audio features (n_audio_ctx, n_audio_state); a mel goes through the encoder as the solo call's would.  draw: None (the row
+        picks greedily) or (temperature, seed, stream id) of a sampled row"""
         import torch
 
         from .whisper_decoding import _features, pick_params
@@ -87,6 +92,8 @@ class ModelEngine:
         params, bits = pick_params(self.dims, self.tok, options)
         with torch.cuda.device(self.model.device):
             self._rows.admit(row, feats[0], init, params, bits)
+            if draw is not None:
+                self._rows.set_draw(row, *draw)
         return feats[0]
 
     def forward(self, items, out_rows) -> None:
@@ -145,8 +152,9 @@ class ModelEngine:
 
 
 class _Request:
-    def __init__(self, x, options: DecodingOptions, init: Tuple[int, ...], sot_index: int, limit: int, future: Future):
+    def __init__(self, x, options: DecodingOptions, init: Tuple[int, ...], sot_index: int, limit: int, future: Future, draw=None):
         self.x, self.options, self.init, self.sot_index, self.limit, self.future = x, options, init, sot_index, limit, future
+        self.draw = draw  # None: greedy; (temperature, seed, stream id): submit_sampled
         self.detect = options.language is None or options.task == "lang_id"
         self.row: Optional[int] = None
         self.phase = "detect" if self.detect else "prefill"  # -> "prefill" -> "step" -> "retire"
@@ -178,7 +186,25 @@ class WhisperBatcher:
         """One window (2-D) -> Future[DecodingResult].  The option checks of `decode` run here, in the caller's thread, with decode's exceptions."""
         if overrides:
             options = replace(options, **overrides)
-        options = verify_options(options)
+        return self._submit(mel_or_features, verify_options(options), None)
+
+    def submit_sampled(self, mel_or_features, options: DecodingOptions = DecodingOptions(temperature=1.0), seed: int = 0, stream: int = 0, **overrides) -> Future:
+        """One window (2-D) decoded at temperature > 0 -> Future[DecodingResult]: what `model.sample(window, options, seed=seed, streams=[stream])` returns
+        for it alone (`tokens`, `avg_logprob`, `no_speech_prob`, `language`, `temperature`; `language_probs` stays None), whatever else the batch runs.
+        The row draws by Gumbel-max on the Philox key `seed` and the stream id `stream` in the round's ONE pick launch (kk_whisper_text_rows_set_draw,
+        DESIGN 8n).  The option checks are whisper_sampling.verify_sampling_options'; `best_of` must be None or 1: groups are not built here."""
+        from .whisper_sampling import verify_sampling_options
+
+        if overrides:
+            options = replace(options, **overrides)
+        options = verify_sampling_options(options)
+        if options.best_of not in (None, 1):
+            raise NotImplementedError("best_of groups are not built in the batcher: submit_sampled takes best_of None or 1 (Model.sample runs groups)")
+        if isinstance(seed, bool) or not isinstance(seed, int) or isinstance(stream, bool) or not isinstance(stream, int) or not 0 <= stream <= 0xFFFFFFFF:
+            raise ValueError("seed must be an int and stream an int in 0 .. 2**32 - 1")
+        return self._submit(mel_or_features, options, (float(options.temperature), seed, stream))
+
+    def _submit(self, mel_or_features, options: DecodingOptions, draw) -> Future:
         d = self.engine.dims
         tok = special_tokens(d)
         n_ctx = d.n_text_ctx
@@ -192,7 +218,7 @@ class WhisperBatcher:
             raise ValueError(NO_LANGUAGE_TOKENS)
         # decode picks once after the prefill and once per step i = 1 .. sample_len - 1 while sample_begin + i <= n_ctx
         limit = min(sample_len, n_ctx - sample_begin + 1)
-        req = _Request(mel_or_features, options, init, sot_index, limit, Future())
+        req = _Request(mel_or_features, options, init, sot_index, limit, Future(), draw)
         with self._lock:
             if self.closed:
                 raise RuntimeError("WhisperBatcher is closed")
@@ -249,7 +275,10 @@ class WhisperBatcher:
             if not r.future.set_running_or_notify_cancel():
                 continue  # cancelled while it was queued
             try:
-                r.features = self.engine.admit(free[0], r.x, r.init, r.options)
+                if r.draw is None:
+                    r.features = self.engine.admit(free[0], r.x, r.init, r.options)
+                else:
+                    r.features = self.engine.admit(free[0], r.x, r.init, r.options, draw=r.draw)
             except BaseException as e:  # noqa: BLE001
                 r.future.set_exception(e)
                 continue
