@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 25  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 26  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -71,7 +71,10 @@ extern "C" {
                             24: quantised Whisper checkpoints, decoder matrices packed in device memory (kk_whisper_text_load_quantized,
                                kk_whisper_text_weight_info, kk_whisper_text_weight_fallback, kk_op_whisper_linear_rows_q, kk_op_whisper_embed_q);
                             25: Whisper long-form transcription: a sampled pick per row of row mode and windows cut out of whole-file spectrograms
-                               (kk_whisper_text_rows_set_draw, kk_op_mel_windows) */
+                               (kk_whisper_text_rows_set_draw, kk_op_mel_windows);
+                            26: groups of row mode: beam search and best_of in the running batch (kk_whisper_text_rows_groups_state_bytes,
+                               kk_whisper_text_rows_groups_bind, kk_whisper_text_rows_admit_group, kk_whisper_text_rows_group_read,
+                               kk_whisper_text_rows_group_release, kk_whisper_text_rows_group_offers, KK_WHISPER_GROUP_PLAIN / _BEAM) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -1092,6 +1095,38 @@ int kk_whisper_text_rows_set_token(kk_whisper_text* m, void* stream, int row, in
  * the bits kk_op_whisper_pick_sampled gives the same logits, parameters, state, seed and stream -- in the same ONE launch of rows_pick that picks
  * the greedy rows.  Refused: temperature <= 0 or not finite, a row outside [0, max_rows) or never admitted.  Synchronises. */
 int kk_whisper_text_rows_set_draw(kk_whisper_text* m, void* stream, int row, float temperature, uint64_t seed, uint32_t stream_id);
+/* ---- groups of row mode: G rows, 1 <= G <= KK_WHISPER_MAX_GROUP and not necessarily adjacent, that decode ONE window: admitted together,
+ * stepped and picked together at one position, released together.  The cross K/V is projected once, into the slices of the leader rows[0]; the other
+ * rows read it there.  A group is known by its leader row.  KK_WHISPER_GROUP_PLAIN: every row picks for itself, greedily or (rows_set_draw) on its own
+ * draw -- best_of.  KK_WHISPER_GROUP_BEAM (G = beam_size): rows_pick takes the rows' G + 1 best tokens in its one pick launch (the bits of
+ * kk_op_whisper_beam_topk) and runs one more launch with a select workgroup per listed beam group (kk_op_whisper_beam_select's walk, slots being the
+ * positions in rows[]), each group at its own position and owner-table flip; a beam row's step reads its self keys through its owner row.  The rows'
+ * state.ended then carries the group's complete flag, so rows_flags stays the ONE poll.
+ * What groups keep (offers, two owner tables and a parent per row; per leader the finished stores of 2 KK_WHISPER_MAX_GROUP sequences of n_text_ctx ids,
+ * their count and the complete flag) lives in a second caller-owned buffer, bound after rows_open (every rows_open unbinds it); bind launches nothing.
+ * Without it row mode is what it was, and rows_workspace_bytes asked after it includes the round's owner table.
+ * Refused, before anything is launched: groups used without the bind call; G outside 1 .. 8; max_candidates of a beam group outside 1 .. 16; a row
+ * listed twice or already in a group; rows_admit on a row of a group; a round or a pick that lists some rows of a group and not the others (only the
+ * leader may run alone, before the group's first pick: its language detection); rows of a group at different positions; a beam row given initial
+ * tokens after its group's first select. */
+#define KK_WHISPER_GROUP_PLAIN 0
+#define KK_WHISPER_GROUP_BEAM 1
+size_t kk_whisper_text_rows_groups_state_bytes(const kk_whisper_text* m, int max_rows);
+int kk_whisper_text_rows_groups_bind(kk_whisper_text* m, void* stream, void* state, size_t state_bytes);
+/* rows HOST [n_rows]; features, tokens, params and the bitmask as for rows_admit, given to every row; every row's pick state and draw are reset, a beam
+ * group's owner rows are identity and its stores empty.  Synchronises once. */
+int kk_whisper_text_rows_admit_group(kk_whisper_text* m, void* stream, const int32_t* rows, int n_rows, int kind, const float* audio_features,
+                                     const int32_t* tokens, int n, const kk_whisper_pick_params* params, const uint32_t* suppress, int max_candidates,
+                                     void* workspace, size_t workspace_bytes);
+/* what kk_whisper_text_beam_read returns for one window (HOST destinations; synchronises): fin_count [1], fin_score and fin_length [max_candidates],
+ * fin_tokens [max_candidates][cap] (a plain group: fin_count 0, the rest untouched), live_tokens [G][cap] by slot gathered through the owner table,
+ * live_sum and live_length [G]; and, unless null, the leader's two kept logits rows (DEVICE fp32 [2][n_vocab]) */
+int kk_whisper_text_rows_group_read(kk_whisper_text* m, void* stream, int leader, int cap, int32_t* fin_count, float* fin_score, int32_t* fin_length,
+                                    int32_t* fin_tokens, int32_t* live_tokens, float* live_sum, int32_t* live_length, float* kept);
+/* the group's rows are free again (each must be admitted anew before it runs); host only */
+int kk_whisper_text_rows_group_release(kk_whisper_text* m, int leader);
+/* the G + 1 offers of a beam row's last pick (HOST token and logprob [G + 1], descending, unused slots -1 / -inf); synchronises */
+int kk_whisper_text_rows_group_offers(kk_whisper_text* m, void* stream, int row, int32_t* token, float* logprob);
 
 /* =====================================================================================================================
  * Whisper, token timestamps from cross-attention: timing.py:19-100, 143-157 and Model.forward_with_cross_qk (csrc/kk_whisper_align.hip,

@@ -72,6 +72,7 @@ class KKWhisperBeamBufs(C.Structure):  # kk_whisper_beam_bufs: device pointers o
 
 WHISPER_MAX_ROWS = 32  # KK_WHISPER_MAX_ROWS
 WHISPER_MAX_GROUP = 8  # KK_WHISPER_MAX_GROUP
+WHISPER_GROUP_PLAIN, WHISPER_GROUP_BEAM = 0, 1  # KK_WHISPER_GROUP_*
 
 
 class KKLlamaArgs(C.Structure):
@@ -297,6 +298,12 @@ SIGNATURES = {
     "kk_whisper_text_rows_read": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
     "kk_whisper_text_rows_set_token": (_i, [_vp, _vp, _i, _i, _vp]),
     "kk_whisper_text_rows_set_draw": (_i, [_vp, _vp, _i, C.c_float, C.c_uint64, C.c_uint32]),
+    "kk_whisper_text_rows_groups_state_bytes": (_sz, [_vp, _i]),
+    "kk_whisper_text_rows_groups_bind": (_i, [_vp, _vp, _vp, _sz]),
+    "kk_whisper_text_rows_admit_group": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, C.POINTER(KKWhisperPickParams), _vp, _i, _vp, _sz]),
+    "kk_whisper_text_rows_group_read": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "kk_whisper_text_rows_group_release": (_i, [_vp, _i]),
+    "kk_whisper_text_rows_group_offers": (_i, [_vp, _vp, _i, _vp, _vp]),
     "kk_op_mel_windows": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "kk_op_whisper_qk_rows_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "kk_op_whisper_qk_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, C.c_longlong]),
@@ -355,7 +362,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 25:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 26:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -385,15 +385,22 @@ int kk_launch_whisper_text_rows(hipStream_t st, int B, int S, int pos, int n_tex
 struct KKRowItems {  // item i: flat rows first[i] .. first[i] + count[i] - 1 are decoder row row[i] at pos[i] + s, fed from from[i] + s (or -1: the last pick)
   int n;
   int row[KK_WHISPER_MAX_ROWS], pos[KK_WHISPER_MAX_ROWS], count[KK_WHISPER_MAX_ROWS], from[KK_WHISPER_MAX_ROWS], first[KK_WHISPER_MAX_ROWS];
+  // groups: the row whose cross slice the item reads (its group's leader, or itself), and which of the two owner tables a beam row's step
+  // reads its self keys through (-1: the row's own slot)
+  int cross[KK_WHISPER_MAX_ROWS], own[KK_WHISPER_MAX_ROWS];
 };
+// item_cross: null (every row reads its own cross slice), or the flat rows' cross slots from t.cross
 int kk_launch_whisper_text_plan(hipStream_t st, const KKRowItems& t, int R, int n_text_ctx, int n_audio_ctx, const int32_t* init, const int32_t* next, int* item,
-                                int* posr, int* len_self, int* len_cross, int* cache_row, int32_t* tok);
+                                int* item_cross, int* posr, int* len_self, int* len_cross, int* cache_row, int32_t* tok);
+// the round's owner table [R][n_text_ctx] for attn_rows<OWNED>: flat row r of item i gets row t.own[i] of its decoder row in own0 / own1 ([rows][n_text_ctx]),
+// or (t.own[i] < 0) its decoder row at every position
+int kk_launch_whisper_text_plan_owner(hipStream_t st, const KKRowItems& t, int R, int n_text_ctx, const int32_t* own0, const int32_t* own1, int* table);
 struct KKRowGather {  // rows src[j] of x to row j of out
   int src[2 * KK_WHISPER_MAX_ROWS];
 };
 int kk_launch_whisper_gather_rows(hipStream_t st, int n, const KKRowGather& sel, const float* x, int D, float* out);
-struct KKPickSel {  // block j picks for decoder row row[j] on logits row logit[j]
-  int row[KK_WHISPER_MAX_ROWS], logit[KK_WHISPER_MAX_ROWS];
+struct KKPickSel {  // block j picks for decoder row row[j] on logits row logit[j]; topk[j] > 0: a beam row, which offers its topk[j] best tokens instead
+  int row[KK_WHISPER_MAX_ROWS], logit[KK_WHISPER_MAX_ROWS], topk[KK_WHISPER_MAX_ROWS];
 };
 // what a sampled pick adds to a row's arguments: 1 / temperature (0: the row picks greedily), the Philox key and the row's stream id
 struct PickDraw {
@@ -402,5 +409,29 @@ struct PickDraw {
   uint32_t stream;
 };
 // draws: [max_rows], indexed by decoder row like params and state
+// cand_token / cand_logprob: the offers of the beam rows, [max_rows][KK_WHISPER_BEAM_C] (may be null when no topk[j] is set)
+constexpr int KK_WHISPER_BEAM_C = KK_WHISPER_MAX_GROUP + 1;  // candidates a row offers, at most
 int kk_launch_whisper_pick_rows(hipStream_t st, int n, const KKPickSel& sel, const float* logits, long long ldl, const kk_whisper_pick_params* params,
-                                const uint32_t* suppress, int words, const PickDraw* draws, kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next);
+                                const uint32_t* suppress, int words, const PickDraw* draws, kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next,
+                                int32_t* cand_token, float* cand_logprob);
+// row mode's beam groups: what a group keeps beside the row state, indexed by decoder row (offers, owner tables, parent) or by the group's
+// leader row (the finished stores of KK_WHISPER_BEAM_FIN sequences of n_text_ctx ids)
+struct KKGroupBufs {
+  int32_t* cand_token;
+  float* cand_logprob;
+  int32_t* owner[2];
+  int32_t* parent;
+  float* fin_score;
+  int32_t *fin_length, *fin_tokens, *fin_count, *complete;
+};
+struct KKGroupSel {  // block j runs the select of the beam group led by row leader[j]: K[j] rows rows[j][slot], whose parents hold pos[j] positions
+  int leader[KK_WHISPER_MAX_ROWS], K[KK_WHISPER_MAX_ROWS], pos[KK_WHISPER_MAX_ROWS], flip[KK_WHISPER_MAX_ROWS], max_candidates[KK_WHISPER_MAX_ROWS];
+  int rows[KK_WHISPER_MAX_ROWS][KK_WHISPER_MAX_GROUP];
+};
+int kk_launch_whisper_rows_select(hipStream_t st, int n, const KKGroupSel& sel, const KKGroupBufs& g, int n_text_ctx, const kk_whisper_pick_params* params,
+                                  kk_whisper_pick_state* state, int32_t* tokens, int32_t* next);
+struct KKGroupRows {
+  int row[KK_WHISPER_MAX_GROUP];
+};
+// a beam group's admission: owner[0] of its K rows is identity, nothing finished, not complete
+int kk_launch_whisper_rows_group_reset(hipStream_t st, const KKGroupRows& rows, int K, int n_text_ctx, const KKGroupBufs& g);

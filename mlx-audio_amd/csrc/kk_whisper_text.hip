@@ -17,6 +17,8 @@
 //   Rows with their own window, position, pick parameters and lifetime in a second state buffer.  A round is the window's launch sequence behind
 //   text_plan_kernel, which fills the per-row index arrays and tokens from a table of items passed as the launch's argument.
 //   A row picks greedily unless rows_set_draw gave it a draw after its admission; the round's one pick launch serves both kinds.
+//   Groups (rows_groups_bind, rows_admit_group): G rows on their leader's cross K/V that are admitted, stepped, picked and released together --
+//   a beam group (top-k in the same pick launch, one select workgroup per group, the step's self keys through the group's owner table) or a plain one.
 #include "kk_host.h"
 #include "kk_philox.h"
 #include "../../include/kokoro_hip.h"
@@ -70,10 +72,20 @@ struct kk_whisper_text {
     bool admitted = false;
     int n_init = 0;      // initial tokens uploaded at admission
     int logit = -1;      // the row of the last rows_forward's logits_out that holds this row's last position, -1: none
+    int group = -1, slot = 0;  // the group it belongs to (by its leader row) and its slot there; -1: a single row
+    int at = 0;          // positions it holds: pos + count of its last round
   };
   char* rows_state = nullptr;
   std::vector<Row> rows;
   const float* rows_logits = nullptr;  // the last rows_forward's logits_out
+  // groups of row mode (rows_groups_bind): G rows admitted and retired together on the leader's cross K/V; a group is known by its leader row
+  struct Group {
+    bool live = false;
+    int kind = 0, G = 0, rows[KK_WHISPER_MAX_GROUP] = {0};
+    int max_candidates = 0, flip = 0, picks = 0, begin = 0;  // beam: finished sequences kept, the current owner table, selects so far, the first sampled position
+  };
+  char* groups_state = nullptr;
+  std::vector<Group> groups;  // [max_rows], by leader row
 };
 
 namespace {
@@ -794,10 +806,33 @@ void plan_rows_state(const kk_whisper_text_config& c, int N, Workspace& ws, Rows
 struct RowsWork {
   TextWork t;    // t.feat: ONE window (rows_admit)
   int32_t* tok;  // [R]
+  int* own;      // [R][n_text_ctx]: the round's owner table (groups bound only)
 };
-void plan_rows_work(const kk_whisper_text_config& c, int R, Workspace& ws, RowsWork& p) {
+void plan_rows_work(const kk_whisper_text_config& c, int R, bool groups, Workspace& ws, RowsWork& p) {
   plan_work(c, 1, R, ws, p.t);  // B = 1, S = R: R flat rows and one window of features
   p.tok = (int32_t*)ws.raw((size_t)R * 4);
+  p.own = groups ? (int*)ws.raw((size_t)R * c.n_text_ctx * 4) : nullptr;
+}
+// the caller's second row-mode buffer: what groups keep beside the row state (kk_kernels.h: KKGroupBufs)
+void plan_groups_state(const kk_whisper_text_config& c, int N, Workspace& ws, KKGroupBufs& g) {
+  const size_t T = c.n_text_ctx, F = (size_t)N * KK_WHISPER_BEAM_FIN;
+  g.cand_token = (int32_t*)ws.raw((size_t)N * KK_WHISPER_BEAM_C * 4);
+  g.cand_logprob = (float*)ws.raw((size_t)N * KK_WHISPER_BEAM_C * 4);
+  g.owner[0] = (int32_t*)ws.raw((size_t)N * T * 4);
+  g.owner[1] = (int32_t*)ws.raw((size_t)N * T * 4);
+  g.parent = (int32_t*)ws.raw((size_t)N * 4);
+  g.fin_score = (float*)ws.raw(F * 4);
+  g.fin_length = (int32_t*)ws.raw(F * 4);
+  g.fin_tokens = (int32_t*)ws.raw(F * T * 4);
+  g.fin_count = (int32_t*)ws.raw((size_t)N * 4);
+  g.complete = (int32_t*)ws.raw((size_t)N * 4);
+}
+int groups_bound(const char* who, const kk_whisper_text* m, KKGroupBufs& g) {
+  if (!m->groups_state) return kk_failf("%s: groups are not bound (kk_whisper_text_rows_groups_bind after rows_open)", who);
+  Workspace gs;
+  bind(gs, m->groups_state, (size_t)-1 / 2);
+  plan_groups_state(m->cfg, (int)m->rows.size(), gs, g);
+  return 0;
 }
 int rows_bound(const char* who, const kk_whisper_text* m, RowsState& s) {
   if (!m) return kk_failf("%s: null model", who);
@@ -827,7 +862,7 @@ extern "C" size_t kk_whisper_text_rows_workspace_bytes(const kk_whisper_text* m,
   if (!m || max_round_rows < 1 || max_items < 1 || max_items > KK_WHISPER_MAX_ROWS) return 0;
   Workspace ws;
   RowsWork p;
-  plan_rows_work(m->cfg, max_round_rows, ws, p);
+  plan_rows_work(m->cfg, max_round_rows, m->groups_state != nullptr, ws, p);
   return ws.used + 256;
 }
 
@@ -846,6 +881,8 @@ extern "C" int kk_whisper_text_rows_open(kk_whisper_text* m, void* stream, int m
   m->rows_state = (char*)state;
   m->rows.assign(max_rows, kk_whisper_text::Row());
   m->rows_logits = nullptr;
+  m->groups_state = nullptr;  // groups are bound anew after every rows_open
+  m->groups.clear();
   return 0;
 }
 
@@ -863,8 +900,9 @@ extern "C" int kk_whisper_text_rows_admit(kk_whisper_text* m, void* stream, int 
   Workspace ws;
   bind(ws, workspace, workspace_bytes);
   RowsWork p;
-  plan_rows_work(c, 1, ws, p);
+  plan_rows_work(c, 1, false, ws, p);
   if (ws.oom) return kk_failf("%s: workspace too small", who);
+  if (m->rows[row].group >= 0) return kk_failf("%s: row %d belongs to the group led by row %d (kk_whisper_text_rows_group_release first)", who, row, m->rows[row].group);
   m->rows[row].admitted = false;  // a failure below leaves the row unusable, not half new
   m->rows[row].logit = -1;
   KK_TRY(project_cross(m, st, audio_features, 1, p.t.feat, s.cross, (int)m->rows.size(), row));  // set_audio's launches with one window, into this row's slices
@@ -907,12 +945,36 @@ extern "C" int kk_whisper_text_rows_forward(kk_whisper_text* m, void* stream, co
     if (it.keep < -1 || it.keep >= it.count || (it.keep >= 0 && (it.slot < 0 || it.slot > 1)))
       return kk_failf("%s: item %d: keep = %d must be -1 or an offset below count, slot 0 or 1", who, i, it.keep);
     t.row[i] = it.row; t.pos[i] = it.pos; t.count[i] = it.count; t.from[i] = it.from; t.first[i] = (int)R;
+    t.cross[i] = it.row; t.own[i] = -1;
     R += it.count;
+  }
+  // groups: a group's rows step together at one position -- before its first pick the leader may run alone (its detection round)
+  bool owned = false;
+  for (int i = 0; i < n_items && m->groups_state; ++i) {
+    const int lead = m->rows[items[i].row].group;
+    if (lead < 0) continue;
+    const kk_whisper_text::Group& g = m->groups[lead];
+    int listed = 0;
+    for (int k = 0; k < g.G; ++k) listed += seen >> g.rows[k] & 1u;
+    const bool alone = listed == 1 && items[i].row == lead && g.picks == 0;
+    if (listed != g.G && !alone)
+      return kk_failf("%s: item %d: the group led by row %d is stepped partially (%d of its %d rows are in this round)", who, i, lead, listed, g.G);
+    if (items[i].row != lead)
+      for (int j = 0; j < n_items; ++j)
+        if (items[j].row == lead && (items[j].pos != items[i].pos || items[j].count != items[i].count))
+          return kk_failf("%s: item %d: row %d is at position %d + %d, its group's leader %d at %d + %d", who, i, items[i].row, items[i].pos, items[i].count, lead,
+                          items[j].pos, items[j].count);
+    t.cross[i] = lead;
+    if (g.kind == KK_WHISPER_GROUP_BEAM && g.picks > 0) {
+      if (items[i].from >= 0) return kk_failf("%s: item %d: row %d of a beam group is prefilled after the group's first select", who, i, items[i].row);
+      t.own[i] = g.flip;  // the step reads its self keys through ITS owner row of the group's current table
+      owned = true;
+    }
   }
   Workspace ws;
   bind(ws, workspace, workspace_bytes);
   RowsWork p;
-  plan_rows_work(c, (int)R, ws, p);
+  plan_rows_work(c, (int)R, m->groups_state != nullptr, ws, p);
   if (ws.oom) return kk_failf("%s: workspace too small for R = %lld rows", who, R);
   if (n_out < 1 || n_out > 2 * n_items || n_out > R) return kk_failf("%s: n_out = %d is outside [1, min(2 n_items, R)]", who, n_out);
   std::vector<int> where((size_t)R, -1);  // flat row -> its row of logits_out
@@ -933,9 +995,15 @@ extern "C" int kk_whisper_text_rows_forward(kk_whisper_text* m, void* stream, co
   for (auto& r : m->rows)
     if (r.logit >= 0) r.logit = -1;
   m->rows_logits = logits_out;
-  KK_TRY(kk_launch_whisper_text_plan(st, t, (int)R, c.n_text_ctx, c.n_audio_ctx, s.init, s.next, p.t.item, p.t.posr, p.t.len_self, p.t.len_cross, p.t.cache_row,
-                                     p.tok));
-  const TextPass run{m, st, N, N, s.self, s.cross, p.t.item, p.t};
+  int* item_cross = m->groups_state ? p.t.item_cross : nullptr;  // without groups every row reads its own slice: one table, as before
+  KK_TRY(kk_launch_whisper_text_plan(st, t, (int)R, c.n_text_ctx, c.n_audio_ctx, s.init, s.next, p.t.item, item_cross, p.t.posr, p.t.len_self, p.t.len_cross,
+                                     p.t.cache_row, p.tok));
+  if (owned) {  // a round that steps a beam group: ONE more launch, however many groups, and the owned self-attention for every row (identity rows for the others)
+    KKGroupBufs gb;
+    KK_TRY(groups_bound(who, m, gb));
+    KK_TRY(kk_launch_whisper_text_plan_owner(st, t, (int)R, c.n_text_ctx, gb.owner[0], gb.owner[1], p.own));
+  }
+  const TextPass run{m, st, N, N, s.self, s.cross, item_cross ? item_cross : p.t.item, p.t, owned ? p.own : nullptr};
   KK_TRY(run.embed((int)R, p.tok, p.t.posr));
   KK_TRY(run.layers((int)R, nullptr, 0, 0));
   const float* x = p.t.x;
@@ -949,6 +1017,7 @@ extern "C" int kk_whisper_text_rows_forward(kk_whisper_text* m, void* stream, co
     kk_whisper_text::Row& r = m->rows[it.row];
     const int last = where[t.first[i] + it.count - 1];
     r.logit = last >= 0 ? last : -1;
+    r.at = it.pos + it.count;
     if (it.keep >= 0 && hipMemcpyAsync(s.kept + ((size_t)it.row * 2 + it.slot) * V, logits_out + (size_t)where[t.first[i] + it.keep] * V, (size_t)V * 4,
                                        hipMemcpyDeviceToDevice, st) != hipSuccess)
       return kk_failf("%s: keeping a logits row failed", who);
@@ -973,10 +1042,43 @@ extern "C" int kk_whisper_text_rows_pick(kk_whisper_text* m, void* stream, const
     sel.row[j] = rows[j];
     sel.logit[j] = m->rows[rows[j]].logit;
   }
+  // groups: a group is picked whole; a beam group's rows offer their top-k in the same launch, and ONE select launch behind it serves
+  // every listed beam group at its own position and flip
+  KKGroupSel gsel;
+  KKGroupBufs gb;
+  memset(&gsel, 0, sizeof gsel);
+  memset(&gb, 0, sizeof gb);
+  int n_beam = 0;
+  for (int j = 0; j < n && m->groups_state; ++j) {
+    const int lead = m->rows[rows[j]].group;
+    if (lead < 0) continue;
+    const kk_whisper_text::Group& g = m->groups[lead];
+    int listed = 0;
+    for (int k = 0; k < g.G; ++k) listed += seen >> g.rows[k] & 1u;
+    if (listed != g.G) return kk_failf("%s: the group led by row %d is picked partially (%d of its %d rows are listed)", who, lead, listed, g.G);
+    if (g.kind != KK_WHISPER_GROUP_BEAM) continue;
+    sel.topk[j] = g.G + 1;
+    if (rows[j] != lead) continue;
+    gsel.leader[n_beam] = lead; gsel.K[n_beam] = g.G; gsel.pos[n_beam] = m->rows[lead].at; gsel.flip[n_beam] = g.flip; gsel.max_candidates[n_beam] = g.max_candidates;
+    for (int k = 0; k < g.G; ++k) {
+      if (m->rows[g.rows[k]].at != m->rows[lead].at) return kk_failf("%s: row %d of the group led by row %d is at another position", who, g.rows[k], lead);
+      gsel.rows[n_beam][k] = g.rows[k];
+    }
+    ++n_beam;
+  }
+  if (n_beam) KK_TRY(groups_bound(who, m, gb));
   const kk_whisper_text_config& c = m->cfg;
   KK_TRY(kk_launch_whisper_pick_rows((hipStream_t)stream, n, sel, m->rows_logits, (long long)c.n_vocab, s.params, s.suppress, (int)mask_words(c), s.draws, s.rows, s.tokens,
-                                     c.n_text_ctx, s.next));
+                                     c.n_text_ctx, s.next, gb.cand_token, gb.cand_logprob));
+  if (n_beam) KK_TRY(kk_launch_whisper_rows_select((hipStream_t)stream, n_beam, gsel, gb, c.n_text_ctx, s.params, s.rows, s.tokens, s.next));
   for (int j = 0; j < n; ++j) m->rows[rows[j]].logit = -2;  // picked: the row can step on its token, and is not picked twice on the same logits
+  for (int j = 0; j < n && m->groups_state; ++j) {
+    const int lead = m->rows[rows[j]].group;
+    if (lead != rows[j]) continue;
+    kk_whisper_text::Group& g = m->groups[lead];
+    if (g.picks++ == 0) g.begin = m->rows[lead].at;
+    if (g.kind == KK_WHISPER_GROUP_BEAM) g.flip ^= 1;
+  }
   return 0;
 }
 
@@ -1033,5 +1135,186 @@ extern "C" int kk_whisper_text_rows_set_token(kk_whisper_text* m, void* stream, 
   if (index < 0 || index >= m->rows[row].n_init) return kk_failf("%s: index %d is outside row %d's %d initial tokens", who, index, row, m->rows[row].n_init);
   if (hipMemcpyAsync(s.init + (size_t)row * m->cfg.n_text_ctx + index, token, 4, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
     return kk_failf("%s: copy failed", who);
+  return 0;
+}
+
+// ---- groups of row mode ---------------------------------------------------------------------------------------------------------------
+// G rows, not necessarily adjacent, admitted and retired together on ONE cross K/V slice (the leader's, rows[0]): a beam group (G = beam_size: per-row
+// top-k in the round's pick launch, one select workgroup per group, the step's self keys through the group's owner table) or a plain group (best_of:
+// every row picks or draws for itself).  What they keep lives in a second caller-owned buffer; without the bind call row mode is what it was.
+extern "C" size_t kk_whisper_text_rows_groups_state_bytes(const kk_whisper_text* m, int max_rows) {
+  if (!m || max_rows < 1 || max_rows > KK_WHISPER_MAX_ROWS) return 0;
+  Workspace ws;
+  KKGroupBufs g;
+  plan_groups_state(m->cfg, max_rows, ws, g);
+  return ws.used + 256;
+}
+
+extern "C" int kk_whisper_text_rows_groups_bind(kk_whisper_text* m, void* stream, void* state, size_t state_bytes) {
+  const char* who = "kk_whisper_text_rows_groups_bind";
+  (void)stream;
+  RowsState s;
+  KK_TRY(rows_bound(who, m, s));
+  if (!state) return kk_failf("%s: null argument", who);
+  Workspace gs;
+  bind(gs, state, state_bytes);
+  KKGroupBufs g;
+  plan_groups_state(m->cfg, (int)m->rows.size(), gs, g);
+  if (gs.oom) return kk_failf("%s: state buffer too small", who);
+  for (const auto& r : m->rows)
+    if (r.group >= 0) return kk_failf("%s: a group is live", who);
+  m->groups_state = (char*)state;  // nothing is launched: an admission resets what its group reads
+  m->groups.assign(m->rows.size(), kk_whisper_text::Group());
+  return 0;
+}
+
+extern "C" int kk_whisper_text_rows_admit_group(kk_whisper_text* m, void* stream, const int32_t* rows, int n_rows, int kind, const float* audio_features,
+                                                const int32_t* tokens, int n, const kk_whisper_pick_params* params, const uint32_t* suppress, int max_candidates,
+                                                void* workspace, size_t workspace_bytes) {
+  const char* who = "kk_whisper_text_rows_admit_group";
+  RowsState s;
+  KK_TRY(rows_bound(who, m, s));
+  KKGroupBufs gb;
+  KK_TRY(groups_bound(who, m, gb));
+  if (!rows || !audio_features || !tokens || !params || !workspace) return kk_failf("%s: null argument", who);
+  if (n_rows < 1 || n_rows > KK_WHISPER_MAX_GROUP) return kk_failf("%s: a group of %d rows is outside [1, %d]", who, n_rows, KK_WHISPER_MAX_GROUP);
+  if (kind != KK_WHISPER_GROUP_PLAIN && kind != KK_WHISPER_GROUP_BEAM) return kk_failf("%s: kind = %d is neither plain (0) nor beam (1)", who, kind);
+  if (kind == KK_WHISPER_GROUP_BEAM && (max_candidates < 1 || max_candidates > KK_WHISPER_BEAM_FIN))
+    return kk_failf("%s: max_candidates = %d is outside [1, %d]", who, max_candidates, KK_WHISPER_BEAM_FIN);
+  unsigned seen = 0;
+  for (int k = 0; k < n_rows; ++k) {
+    KK_TRY(rows_check_row(who, m, rows[k], false));
+    if (seen >> rows[k] & 1u) return kk_failf("%s: row %d is listed twice", who, rows[k]);
+    seen |= 1u << rows[k];
+    if (m->rows[rows[k]].group >= 0) return kk_failf("%s: row %d is already in the group led by row %d", who, rows[k], m->rows[rows[k]].group);
+  }
+  const kk_whisper_text_config& c = m->cfg;
+  if (n < 1 || n > c.n_text_ctx) return kk_failf("%s: %d initial tokens are outside [1, n_text_ctx = %d]", who, n, c.n_text_ctx);
+  KK_TRY(check_pick_params(who, c, params));
+  hipStream_t st = (hipStream_t)stream;
+  Workspace ws;
+  bind(ws, workspace, workspace_bytes);
+  RowsWork p;
+  plan_rows_work(c, 1, false, ws, p);
+  if (ws.oom) return kk_failf("%s: workspace too small", who);
+  const int lead = rows[0];
+  for (int k = 0; k < n_rows; ++k) {  // a failure below leaves the rows unusable, not half new
+    m->rows[rows[k]].admitted = false;
+    m->rows[rows[k]].logit = -1;
+  }
+  KK_TRY(project_cross(m, st, audio_features, 1, p.t.feat, s.cross, (int)m->rows.size(), lead));  // ONCE, into the leader's slices: the others name them
+  const size_t words = mask_words(c);
+  KKGroupRows gr;
+  memset(&gr, 0, sizeof gr);
+  for (int k = 0; k < n_rows; ++k) {
+    const int row = rows[k];
+    gr.row[k] = row;
+    if (hipMemcpyAsync(s.init + (size_t)row * c.n_text_ctx, tokens, (size_t)n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(s.params + row, params, sizeof *params, hipMemcpyHostToDevice, st) != hipSuccess ||
+        (suppress ? hipMemcpyAsync(s.suppress + (size_t)row * words, suppress, words * 4, hipMemcpyHostToDevice, st)
+                  : hipMemsetAsync(s.suppress + (size_t)row * words, 0, words * 4, st)) != hipSuccess ||
+        hipMemsetAsync(s.draws + row, 0, sizeof(PickDraw), st) != hipSuccess)
+      return kk_failf("%s: upload failed", who);
+    KK_TRY(kk_op_whisper_pick_reset(stream, 1, s.rows + row, s.not_ended));
+  }
+  if (kind == KK_WHISPER_GROUP_BEAM) KK_TRY(kk_launch_whisper_rows_group_reset(st, gr, n_rows, c.n_text_ctx, gb));
+  if (hipStreamSynchronize(st) != hipSuccess) return kk_failf("%s: stream sync failed", who);  // once: the host arrays may go away
+  kk_whisper_text::Group& g = m->groups[lead];
+  g = kk_whisper_text::Group();
+  g.live = true;
+  g.kind = kind;
+  g.G = n_rows;
+  g.max_candidates = kind == KK_WHISPER_GROUP_BEAM ? max_candidates : 0;
+  for (int k = 0; k < n_rows; ++k) {
+    kk_whisper_text::Row& r = m->rows[rows[k]];
+    g.rows[k] = rows[k];
+    r.admitted = true;
+    r.n_init = n;
+    r.group = lead;
+    r.slot = k;
+    r.at = 0;
+  }
+  return 0;
+}
+
+extern "C" int kk_whisper_text_rows_group_release(kk_whisper_text* m, int leader) {
+  const char* who = "kk_whisper_text_rows_group_release";
+  if (!m) return kk_failf("%s: null model", who);
+  if (!m->rows_state || !m->groups_state) return kk_failf("%s: groups are not bound (kk_whisper_text_rows_groups_bind after rows_open)", who);
+  if (leader < 0 || leader >= (int)m->groups.size() || !m->groups[leader].live) return kk_failf("%s: row %d leads no group", who, leader);
+  kk_whisper_text::Group& g = m->groups[leader];
+  for (int k = 0; k < g.G; ++k) {
+    m->rows[g.rows[k]].group = -1;
+    m->rows[g.rows[k]].admitted = false;  // its cross K/V is the leader's: a released row is admitted anew before it runs again
+    m->rows[g.rows[k]].logit = -1;
+  }
+  g.live = false;
+  return 0;
+}
+
+extern "C" int kk_whisper_text_rows_group_read(kk_whisper_text* m, void* stream, int leader, int cap, int32_t* fin_count, float* fin_score, int32_t* fin_length,
+                                               int32_t* fin_tokens, int32_t* live_tokens, float* live_sum, int32_t* live_length, float* kept) {
+  const char* who = "kk_whisper_text_rows_group_read";
+  RowsState s;
+  KK_TRY(rows_bound(who, m, s));
+  KKGroupBufs gb;
+  KK_TRY(groups_bound(who, m, gb));
+  if (leader < 0 || leader >= (int)m->groups.size() || !m->groups[leader].live) return kk_failf("%s: row %d leads no group", who, leader);
+  if (!fin_count || !fin_score || !fin_length || !fin_tokens || !live_tokens || !live_sum || !live_length || cap < 1) return kk_failf("%s: bad argument", who);
+  const kk_whisper_text::Group& g = m->groups[leader];
+  const kk_whisper_text_config& c = m->cfg;
+  hipStream_t st = (hipStream_t)stream;
+  const int T = c.n_text_ctx, n = cap < T ? cap : T, G = g.G, F = g.max_candidates;
+  const bool beam = g.kind == KK_WHISPER_GROUP_BEAM;
+  std::vector<int32_t> tok((size_t)G * T), own((size_t)G * T);
+  std::vector<kk_whisper_pick_state> rows(G);
+  bool ok = true;
+  *fin_count = 0;
+  if (beam)
+    ok = hipMemcpyAsync(fin_count, gb.fin_count + leader, 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+         hipMemcpyAsync(fin_score, gb.fin_score + (size_t)leader * KK_WHISPER_BEAM_FIN, (size_t)F * 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+         hipMemcpyAsync(fin_length, gb.fin_length + (size_t)leader * KK_WHISPER_BEAM_FIN, (size_t)F * 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+         hipMemcpy2DAsync(fin_tokens, (size_t)cap * 4, gb.fin_tokens + (size_t)leader * KK_WHISPER_BEAM_FIN * T, (size_t)T * 4, (size_t)n * 4, F, hipMemcpyDeviceToHost,
+                          st) == hipSuccess;
+  for (int k = 0; k < G && ok; ++k) {
+    const int row = g.rows[k];
+    ok = hipMemcpyAsync(tok.data() + (size_t)k * T, s.tokens + (size_t)row * T, (size_t)T * 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+         hipMemcpyAsync(rows.data() + k, s.rows + row, sizeof(kk_whisper_pick_state), hipMemcpyDeviceToHost, st) == hipSuccess &&
+         (!beam || hipMemcpyAsync(own.data() + (size_t)k * T, gb.owner[g.flip] + (size_t)row * T, (size_t)T * 4, hipMemcpyDeviceToHost, st) == hipSuccess);
+  }
+  if (ok && kept) ok = hipMemcpyAsync(kept, s.kept + (size_t)leader * 2 * c.n_vocab, (size_t)2 * c.n_vocab * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
+  if (!ok || hipStreamSynchronize(st) != hipSuccess) return kk_failf("%s: read failed", who);
+  for (int k = 0; k < G; ++k) {  // a live beam's tokens lie where its ancestors wrote them: token i in the row that owns position begin + i
+    const int len = rows[k].count < 0 ? 0 : (rows[k].count < n ? rows[k].count : n);
+    live_sum[k] = rows[k].sum_logprob;
+    live_length[k] = len;
+    for (int i = 0; i < len; ++i) {
+      int slot = k;
+      if (beam && g.picks > 0 && g.begin + i < T) {
+        const int o = own[(size_t)k * T + g.begin + i];
+        for (int q = 0; q < G; ++q)
+          if (g.rows[q] == o) slot = q;
+      }
+      live_tokens[(size_t)k * cap + i] = tok[(size_t)slot * T + i];
+    }
+  }
+  return 0;
+}
+
+extern "C" int kk_whisper_text_rows_group_offers(kk_whisper_text* m, void* stream, int row, int32_t* token, float* logprob) {
+  const char* who = "kk_whisper_text_rows_group_offers";
+  RowsState s;
+  KK_TRY(rows_bound(who, m, s));
+  KKGroupBufs gb;
+  KK_TRY(groups_bound(who, m, gb));
+  KK_TRY(rows_check_row(who, m, row, true));
+  if (!token || !logprob) return kk_failf("%s: null argument", who);
+  const int lead = m->rows[row].group;
+  if (lead < 0 || m->groups[lead].kind != KK_WHISPER_GROUP_BEAM || m->groups[lead].picks == 0) return kk_failf("%s: row %d has no offers (a beam row after its pick)", who, row);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t n = (size_t)m->groups[lead].G + 1;
+  if (hipMemcpyAsync(token, gb.cand_token + (size_t)row * KK_WHISPER_BEAM_C, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(logprob, gb.cand_logprob + (size_t)row * KK_WHISPER_BEAM_C, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return kk_failf("%s: read failed", who);
   return 0;
 }

@@ -33,7 +33,8 @@
 //   the launch-wide kernel (one params, one bitmask) and the per-row kernel of row mode (each row its own; the row's state.ended is its flag).
 //   The sampled form (temperature > 0) is the same body with one more branch in pass B: Gumbel-max on Philox uniforms beside the sum of
 //   exponentials, so a sampled step reads the row's logits as often as a greedy one; a row's draws depend on (seed, its stream id, its history) alone.
-//   The per-row kernel takes either form per block from the row's draw (PickDraw, set by kk_whisper_text_rows_set_draw).
+//   The per-row kernel takes either form per block from the row's draw (PickDraw, set by kk_whisper_text_rows_set_draw), or the top-k form
+//   for a row of a beam group.
 #include "kk_host.h"
 #include "kk_philox.h"
 #include "../../include/kokoro_hip.h"
@@ -603,12 +604,16 @@ __global__ __launch_bounds__(1024) void pick_sampled_kernel(const float* logits,
 // branch is uniform over the block, so each block runs one of the two bodies and the barriers inside them are met by all its threads.
 __global__ __launch_bounds__(1024) void pick_rows_kernel(KKPickSel sel, const float* logits, long long ldl, const kk_whisper_pick_params* params,
                                                          const uint32_t* suppress, int words, const PickDraw* draws, kk_whisper_pick_state* state, int32_t* tokens,
-                                                         int cap, int32_t* next) {
+                                                         int cap, int32_t* next, int32_t* cand_token, float* cand_logprob) {
   __shared__ Osm sh[16];
-  const int r = sel.row[blockIdx.x];
+  __shared__ Top sht[16];
+  const int r = sel.row[blockIdx.x], C = sel.topk[blockIdx.x];
   const float* lg = logits + (long long)sel.logit[blockIdx.x] * ldl;
   const PickDraw dr = draws[r];
-  if (dr.inv_t > 0.f)
+  if (C > 0)  // a row of a beam group: its C best tokens (the bits of beam_topk_kernel) for the select launch behind this one
+    pick_row<PICK_TOPK>(lg, params[r], suppress + (long long)r * words, state + r, nullptr, 0, nullptr, nullptr, sh, PickDraw{0.f, 0, 0},
+                        PickTop{C, cand_token + (long long)r * BEAM_C, cand_logprob + (long long)r * BEAM_C, sht});
+  else if (dr.inv_t > 0.f)
     pick_row<PICK_SAMPLE>(lg, params[r], suppress + (long long)r * words, state + r, tokens + (long long)r * cap, cap, next + r, nullptr, sh, dr);
   else
     pick_row<PICK_GREEDY>(lg, params[r], suppress + (long long)r * words, state + r, tokens + (long long)r * cap, cap, next + r, nullptr, sh);
@@ -647,29 +652,50 @@ __global__ void beam_reset_kernel(kk_whisper_beam_bufs b) {
   }
 }
 
-// Window w = blockIdx.x, rows w K .. w K + K - 1, whose parents hold `pos` positions; owner tables: b.owner[flip] is read, b.owner[flip ^ 1] written.
-// The walk's order is total -- score descending, parent row ascending, rank within the parent ascending -- so every thread computes its candidate's
+// What one select works on: a window of window mode (rows w K .. w K + K - 1) or a beam group of row mode (any K rows).  The K rows are
+// named by SLOT through s_row (LDS, filled by the kernel): slots order the candidates and the next prefixes, while the owner tables, the parent
+// pointers and every token lookup name physical rows.  The arrays are indexed by physical row; the finished stores are this window's own.
+struct BeamView {
+  int K, T, cap, max_candidates, pos;  // rows; positions of an owner row; ids of a token row; finished sequences kept; positions the parents hold
+  int cstride;                         // offers per row in cand_token / cand_logprob
+  const int32_t* cand_token;
+  const float* cand_logprob;
+  const int32_t* own_old;
+  int32_t *own_new, *parent;
+  float* fin_score;
+  int32_t *fin_length, *fin_tokens, *fin_count, *complete, *not_complete;  // not_complete: the launch-wide counter, or null
+  const kk_whisper_pick_params* params;
+  kk_whisper_pick_state* state;
+  int32_t *tokens, *next;
+  bool flag_rows;  // row mode: the rows' state.ended carries the group's complete flag (the poll reads it with the plain rows' flags)
+};
+
+// OpenAI's BeamSearchDecoder.update on one window, by one workgroup of 256 threads; the parents hold v.pos positions, v.own_old is read, v.own_new written.
+// The walk's order is total -- score descending, parent slot ascending, rank within the parent ascending -- so every thread computes its candidate's
 // place by counting, and thread 0 walks the sorted list.
-__global__ __launch_bounds__(256) void beam_select_kernel(kk_whisper_beam_bufs b, int flip, int pos, const kk_whisper_pick_params* params, kk_whisper_pick_state* state,
-                                                          int32_t* tokens, int32_t* next) {
+__device__ __forceinline__ void beam_select_body(const BeamView& v, const int* s_row) {
   __shared__ kk_whisper_pick_state par[KK_WHISPER_MAX_GROUP];
   __shared__ float c_score[BEAM_N], c_lp[BEAM_N];
   __shared__ int c_tok[BEAM_N], order[BEAM_N];
-  __shared__ int s_cand[KK_WHISPER_MAX_GROUP], f_cand[BEAM_FIN], f_slot[BEAM_FIN], n_new;
-  const int w = blockIdx.x, tid = threadIdx.x, K = b.beam_size, C = K + 1, n = K * C, row0 = w * K, T = b.n_ctx, cap = b.cap;
-  const int eot = params->eot, tb = params->timestamp_begin;
-  const int32_t* own_old = b.owner[flip & 1];
-  int32_t* own_new = b.owner[(flip & 1) ^ 1];
-  if (tid < K) par[tid] = state[row0 + tid];
+  __shared__ int s_cand[KK_WHISPER_MAX_GROUP], f_cand[BEAM_FIN], f_slot[BEAM_FIN], n_new, s_done;
+  const int tid = threadIdx.x, K = v.K, C = K + 1, n = K * C, T = v.T, cap = v.cap, pos = v.pos;
+  const int eot = v.params->eot, tb = v.params->timestamp_begin;
+  const int32_t* own_old = v.own_old;
+  int32_t* own_new = v.own_new;
+  kk_whisper_pick_state* state = v.state;
+  int32_t *tokens = v.tokens, *next = v.next;
+  __syncthreads();  // s_row is filled
+  if (tid < K) par[tid] = state[s_row[tid]];
   if (tid < n) order[tid] = -1;
   __syncthreads();
   const int count = par[0].count;  // the rows of a window step together
   if (tid < n) {
     const int j = tid / C;
-    const int t = b.cand_token[(long long)row0 * C + tid];
-    const float lp = b.cand_logprob[(long long)row0 * C + tid];
+    const long long at = (long long)s_row[j] * v.cstride + (tid - j * C);
+    const int t = v.cand_token[at];
+    const float lp = v.cand_logprob[at];
     const float s = par[j].sum_logprob + lp;
-    // at the first sampled position the rows of a window are one prefix: row 0 offers for all
+    // at the first sampled position the rows of a window are one prefix: slot 0 offers for all
     const bool valid = t >= 0 && (count > 0 || j == 0) && par[j].sum_logprob != -INFINITY && s == s;
     c_tok[tid] = valid ? t : -1;
     c_score[tid] = valid ? s : -INFINITY;
@@ -689,29 +715,30 @@ __global__ __launch_bounds__(256) void beam_select_kernel(kk_whisper_beam_bufs b
   }
   __syncthreads();
   if (tid == 0) {
-    int saved = 0, nf = 0, fc = b.fin_count[w];
+    int saved = 0, nf = 0, fc = *v.fin_count;
     fc = fc < 0 ? 0 : fc;  // (a store that was never reset: nothing is written outside it)
     for (int idx = 0; idx < n && saved < K; ++idx) {
       const int c = order[idx];
       if (c < 0 || c_tok[c] < 0) break;  // the offers are used up
       if (c_tok[c] != eot) {
         s_cand[saved++] = c;
-      } else if (fc < b.max_candidates && nf < BEAM_FIN) {  // finished, in descending score, while there is room
+      } else if (fc < v.max_candidates && nf < BEAM_FIN) {  // finished, in descending score, while there is room
         f_cand[nf] = c;
         f_slot[nf++] = fc++;
       }
     }
     for (int k = saved; k < K; ++k) s_cand[k] = -1;  // dead slots
     n_new = nf;
-    b.fin_count[w] = fc;
-    if (fc >= b.max_candidates && !b.complete[w]) {
-      b.complete[w] = 1;
-      atomicSub(b.not_complete, 1);
+    *v.fin_count = fc;
+    if (fc >= v.max_candidates && !*v.complete) {
+      *v.complete = 1;
+      if (v.not_complete) atomicSub(v.not_complete, 1);
     }
+    s_done = fc >= v.max_candidates;
   }
   __syncthreads();
   if (tid < K) {  // the child's pick state from the PARENT's
-    const int c = s_cand[tid], row = row0 + tid;
+    const int c = s_cand[tid], row = s_row[tid];
     kk_whisper_pick_state N = par[c >= 0 ? c / C : tid];
     int tok = eot;
     if (c >= 0) {
@@ -725,30 +752,70 @@ __global__ __launch_bounds__(256) void beam_select_kernel(kk_whisper_beam_bufs b
     }
     N.penultimate = N.last;
     N.last = tok;
-    N.ended = 0;
+    N.ended = v.flag_rows ? s_done : 0;
     N.count = count + 1;
     state[row] = N;
     next[row] = tok;
-    b.parent[row] = c >= 0 ? row0 + c / C : -1;
+    v.parent[row] = c >= 0 ? s_row[c / C] : -1;
     if (count >= 0 && count < cap) tokens[(long long)row * cap + count] = tok;
   }
   auto owner_of = [&](int row, int p) -> int {  // the physical row that holds position p of `row`, kept inside the window whatever the table holds
     const int o = p >= 0 && p < T ? own_old[(long long)row * T + p] : row;
-    return o >= row0 && o < row0 + K ? o : row;
+    bool inside = false;
+    for (int k = 0; k < K; ++k) inside = inside || o == s_row[k];
+    return inside ? o : row;
   };
   for (int e = tid; e < K * T; e += 256) {  // what the parent has is inherited; the positions from `pos` on are the row's own
     const int k = e / T, p = e - k * T, c = s_cand[k];
-    own_new[(long long)(row0 + k) * T + p] = c >= 0 && p < pos ? owner_of(row0 + c / C, p) : row0 + k;
+    own_new[(long long)s_row[k] * T + p] = c >= 0 && p < pos ? owner_of(s_row[c / C], p) : s_row[k];
   }
   const int len = count < 0 ? 0 : (count < cap ? count : cap);
   for (int f = 0; f < n_new; ++f) {  // the finished sequences, materialised now: their rows are overwritten from the next step on
-    const int c = f_cand[f], prow = row0 + c / C;
-    int32_t* dst = b.fin_tokens + ((long long)w * b.max_candidates + f_slot[f]) * cap;
+    const int c = f_cand[f], prow = s_row[c / C];
+    int32_t* dst = v.fin_tokens + (long long)f_slot[f] * cap;
     for (int i = tid; i < len; i += 256) dst[i] = tokens[(long long)owner_of(prow, pos - count + i) * cap + i];
     if (tid == 0) {
-      b.fin_score[w * b.max_candidates + f_slot[f]] = c_score[c];
-      b.fin_length[w * b.max_candidates + f_slot[f]] = len;
+      v.fin_score[f_slot[f]] = c_score[c];
+      v.fin_length[f_slot[f]] = len;
     }
+  }
+}
+
+// window mode: window w = blockIdx.x, rows w K .. w K + K - 1; owner tables: b.owner[flip] is read, b.owner[flip ^ 1] written
+__global__ __launch_bounds__(256) void beam_select_kernel(kk_whisper_beam_bufs b, int flip, int pos, const kk_whisper_pick_params* params, kk_whisper_pick_state* state,
+                                                          int32_t* tokens, int32_t* next) {
+  __shared__ int s_row[KK_WHISPER_MAX_GROUP];
+  const int w = blockIdx.x, K = b.beam_size;
+  if (threadIdx.x < K) s_row[threadIdx.x] = w * K + threadIdx.x;
+  const long long f0 = (long long)w * b.max_candidates;
+  const BeamView v{K, b.n_ctx, b.cap, b.max_candidates, pos, K + 1, b.cand_token, b.cand_logprob, b.owner[flip & 1], b.owner[(flip & 1) ^ 1], b.parent,
+                   b.fin_score + f0, b.fin_length + f0, b.fin_tokens + f0 * b.cap, b.fin_count + w, b.complete + w, b.not_complete, params, state, tokens, next, false};
+  beam_select_body(v, s_row);
+}
+
+// row mode: block j is the beam group led by decoder row sel.leader[j], its rows by slot in sel.rows[j], at ITS position and flip; the group's params
+// are its leader's, its finished stores (BEAM_FIN sequences of T ids) are indexed by the leader row
+__global__ __launch_bounds__(256) void rows_select_kernel(KKGroupSel sel, KKGroupBufs g, int T, const kk_whisper_pick_params* params, kk_whisper_pick_state* state,
+                                                          int32_t* tokens, int32_t* next) {
+  __shared__ int s_row[KK_WHISPER_MAX_GROUP];
+  const int j = blockIdx.x, K = sel.K[j], lead = sel.leader[j], flip = sel.flip[j] & 1;
+  if (threadIdx.x < K) s_row[threadIdx.x] = sel.rows[j][threadIdx.x];
+  const long long f0 = (long long)lead * BEAM_FIN;
+  const BeamView v{K, T, T, sel.max_candidates[j], sel.pos[j], BEAM_C, g.cand_token, g.cand_logprob, flip ? g.owner[1] : g.owner[0], flip ? g.owner[0] : g.owner[1],
+                   g.parent, g.fin_score + f0, g.fin_length + f0, g.fin_tokens + f0 * T, g.fin_count + lead, g.complete + lead, nullptr, params + lead, state, tokens,
+                   next, true};
+  beam_select_body(v, s_row);
+}
+
+// a beam group's admission (one block): owner[0] of its K rows is identity, nothing finished, not complete
+__global__ __launch_bounds__(256) void rows_group_reset_kernel(KKGroupRows rows, int K, int T, KKGroupBufs g) {
+  for (int e = threadIdx.x; e < K * T; e += 256) {
+    const int row = rows.row[e / T];
+    g.owner[0][(long long)row * T + e % T] = row;
+  }
+  if (threadIdx.x == 0) {
+    g.fin_count[rows.row[0]] = 0;
+    g.complete[rows.row[0]] = 0;
   }
 }
 
@@ -770,19 +837,31 @@ __global__ void text_rows_kernel(int B, int S, int pos, int n_text_ctx, int n_au
 // Row mode's plan: the same arrays, and the rows' tokens, from a table of items that travels as the launch's argument.  Item i covers the flat rows
 // first[i] .. first[i] + count[i] - 1: decoder row row[i] at positions pos[i] + s, fed from offset from[i] + s of the row's initial-token store, or
 // (from[i] < 0, count 1) with the token the row's last pick chose.
-__global__ void text_plan_kernel(KKRowItems t, int R, int n_text_ctx, int n_audio_ctx, const int32_t* init, const int32_t* next, int* item, int* posr, int* len_self,
-                                 int* len_cross, int* cache_row, int32_t* tok) {
+__global__ void text_plan_kernel(KKRowItems t, int R, int n_text_ctx, int n_audio_ctx, const int32_t* init, const int32_t* next, int* item, int* item_cross,
+                                 int* posr, int* len_self, int* len_cross, int* cache_row, int32_t* tok) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= R) return;
   int i = 0;
   while (i + 1 < t.n && r >= t.first[i + 1]) ++i;
   const int s = r - t.first[i], row = t.row[i], p = t.pos[i] + s;
   item[r] = row;
+  if (item_cross) item_cross[r] = t.cross[i];  // a group's rows read their leader's slice, as item / n_group in text_rows_kernel
   posr[r] = p;
   len_self[r] = p + 1;
   len_cross[r] = n_audio_ctx;
   cache_row[r] = row * n_text_ctx + p;
   tok[r] = t.from[i] >= 0 ? init[(long long)row * n_text_ctx + t.from[i] + s] : next[row];
+}
+
+// The owner table of a round that steps a beam group, [R][T] for attn_rows<OWNED>: flat row r = blockIdx.y of item i reads position p in the
+// row that table t.own[i] of its decoder row names, or (t.own[i] < 0: a plain row, a prefill) in its own slot
+__global__ __launch_bounds__(256) void text_plan_owner_kernel(KKRowItems t, int T, const int32_t* own0, const int32_t* own1, int* table) {
+  const int r = blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= T) return;
+  int i = 0;
+  while (i + 1 < t.n && r >= t.first[i + 1]) ++i;
+  const int row = t.row[i], f = t.own[i];
+  table[(long long)r * T + p] = f < 0 ? row : (f & 1 ? own1 : own0)[(long long)row * T + p];
 }
 
 // rows sel.src[j] of x to row j of out (the rows whose logits a row-mode round wants, made contiguous for the final LayerNorm)
@@ -856,9 +935,28 @@ int kk_launch_whisper_text_rows(hipStream_t st, int B, int S, int pos, int n_tex
 }
 
 int kk_launch_whisper_text_plan(hipStream_t st, const KKRowItems& t, int R, int n_text_ctx, int n_audio_ctx, const int32_t* init, const int32_t* next, int* item,
-                                int* posr, int* len_self, int* len_cross, int* cache_row, int32_t* tok) {
-  hipLaunchKernelGGL(text_plan_kernel, dim3((R + 255) / 256), dim3(256), 0, st, t, R, n_text_ctx, n_audio_ctx, init, next, item, posr, len_self, len_cross, cache_row,
-                     tok);
+                                int* item_cross, int* posr, int* len_self, int* len_cross, int* cache_row, int32_t* tok) {
+  hipLaunchKernelGGL(text_plan_kernel, dim3((R + 255) / 256), dim3(256), 0, st, t, R, n_text_ctx, n_audio_ctx, init, next, item, item_cross, posr, len_self, len_cross,
+                     cache_row, tok);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
+int kk_launch_whisper_text_plan_owner(hipStream_t st, const KKRowItems& t, int R, int n_text_ctx, const int32_t* own0, const int32_t* own1, int* table) {
+  hipLaunchKernelGGL(text_plan_owner_kernel, dim3((n_text_ctx + 255) / 256, R), dim3(256), 0, st, t, n_text_ctx, own0, own1, table);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
+int kk_launch_whisper_rows_select(hipStream_t st, int n, const KKGroupSel& sel, const KKGroupBufs& g, int n_text_ctx, const kk_whisper_pick_params* params,
+                                  kk_whisper_pick_state* state, int32_t* tokens, int32_t* next) {
+  hipLaunchKernelGGL(rows_select_kernel, dim3(n), dim3(256), 0, st, sel, g, n_text_ctx, params, state, tokens, next);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
+int kk_launch_whisper_rows_group_reset(hipStream_t st, const KKGroupRows& rows, int K, int n_text_ctx, const KKGroupBufs& g) {
+  hipLaunchKernelGGL(rows_group_reset_kernel, dim3(1), dim3(256), 0, st, rows, K, n_text_ctx, g);
   KK_CHECK_LAUNCH();
   return 0;
 }
@@ -870,8 +968,10 @@ int kk_launch_whisper_gather_rows(hipStream_t st, int n, const KKRowGather& sel,
 }
 
 int kk_launch_whisper_pick_rows(hipStream_t st, int n, const KKPickSel& sel, const float* logits, long long ldl, const kk_whisper_pick_params* params,
-                                const uint32_t* suppress, int words, const PickDraw* draws, kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next) {
-  hipLaunchKernelGGL(pick_rows_kernel, dim3(n), dim3(1024), 0, st, sel, logits, ldl, params, suppress, words, draws, state, tokens, cap, next);
+                                const uint32_t* suppress, int words, const PickDraw* draws, kk_whisper_pick_state* state, int32_t* tokens, int cap, int32_t* next,
+                                int32_t* cand_token, float* cand_logprob) {
+  hipLaunchKernelGGL(pick_rows_kernel, dim3(n), dim3(1024), 0, st, sel, logits, ldl, params, suppress, words, draws, state, tokens, cap, next, cand_token,
+                     cand_logprob);
   KK_CHECK_LAUNCH();
   return 0;
 }

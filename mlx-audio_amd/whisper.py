@@ -563,6 +563,15 @@ class Model:
 
         return transcribe(self, audio, **kw)
 
+    def beam_transcribe(self, audio, **kw):
+        """`transcribe` with beam search at temperature 0 and `best_of` samples above it, every window a group of rows of the one running decoder
+        batch; see whisper_transcribe.beam_transcribe"""
+        if self._text is None:
+            raise NotImplementedError(_NOT_BUILT)
+        from .whisper_transcribe import beam_transcribe
+
+        return beam_transcribe(self, audio, **kw)
+
     def detect_language(self, *a, **kw):
         """decoding.py:20-79, see whisper_decoding.detect_language"""
         if self._text is None:

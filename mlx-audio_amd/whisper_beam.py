@@ -15,8 +15,9 @@ The step runs in libkokoro_hip.so with no host round trip: the grouped window st
 kk_op_whisper_beam_topk and kk_op_whisper_beam_select.  The self K/V is never moved: an owner table names the physical row that holds each position of a
 beam, and the step's self-attention reads its keys through it.
 
-`decode`, `verify_options`, `verify_sampling_options`, the batcher and `Model.decode_with_fallback` keep refusing `beam_size`; beam search is reached through
-the names of this module and the thin methods `Model.beam_search`, `Model.beam_candidates` and `Model.beam_decode_with_fallback`.
+`decode`, `verify_options`, `verify_sampling_options`, the batcher's `submit` and `Model.decode_with_fallback` keep refusing `beam_size`; beam search is reached
+through the names of this module, the thin methods `Model.beam_search`, `Model.beam_candidates` and `Model.beam_decode_with_fallback`, and, in the running batch,
+`WhisperBatcher.submit_beam` / `Model.beam_transcribe`.
 """
 from __future__ import annotations
 

@@ -6,8 +6,8 @@ looks at a device counter of unfinished rows every `eos_check_interval` steps.
 
 There is no tokenizer here (the vocabulary files are not part of this repository): tokens go in and come out as ids, `DecodingResult.text` stays "".
 `TextRuntime.forward_qk` is the forward that also hands out raw cross-attention scores; the token timestamps made from them live in whisper_timing.py.
-`RowRuntime` is the handle's row mode (kk_whisper_text_rows_*): rows with their own window, position, options and lifetime; the batcher on
-top of it lives in whisper_serve.py.  Sampling at temperature > 0, `best_of` and the temperature fallback live in whisper_sampling.py, on
+`RowRuntime` is the handle's row mode (kk_whisper_text_rows_*): rows with their own window, position, options and lifetime, and groups of
+rows on one window (beam search and best_of); the batcher on top of it lives in whisper_serve.py.  Sampling at temperature > 0, `best_of` and the temperature fallback live in whisper_sampling.py, on
 `TextRuntime.set_audio_groups` / `sample_setup`; `decode` and `verify_options` here stay greedy and keep refusing a temperature.
 """
 from __future__ import annotations
@@ -674,3 +674,53 @@ class RowRuntime:
         from . import _lib
 
         _lib.check(self._lib.kk_whisper_text_rows_set_token(self._h, self._stream(), row, index, C.c_void_p(token.data_ptr())), "kk_whisper_text_rows_set_token")
+
+    # ---- groups: G rows on the leader's cross K/V (kk_whisper_text_rows_groups_bind ...) -----------------------------------------------
+    def _bind_groups(self):
+        """the groups buffer, bound at the first group's admission: until then row mode launches and sizes what it always did"""
+        import torch
+
+        from . import _lib
+
+        if getattr(self, "_gstate", None) is None:
+            need = int(self._lib.kk_whisper_text_rows_groups_state_bytes(self._h, self.max_rows))
+            self._gstate = torch.empty(need, dtype=torch.uint8, device=self.device)
+            _lib.check(self._lib.kk_whisper_text_rows_groups_bind(self._h, self._stream(), C.c_void_p(self._gstate.data_ptr()), need), "kk_whisper_text_rows_groups_bind")
+
+    def admit_group(self, rows, beam: bool, features, tokens, params, suppress_bits: Optional[np.ndarray], max_candidates: int = 1):
+        """rows: the group's decoder rows, the leader first; beam: a beam group of len(rows) = beam_size, else a plain one (every row picks for itself)"""
+        from . import _lib
+
+        self._bind_groups()
+        r = np.ascontiguousarray(np.asarray(rows, np.int32))
+        toks = np.ascontiguousarray(np.asarray(tokens, np.int32))
+        sp = None if suppress_bits is None else suppress_bits.ctypes.data_as(C.c_void_p)
+        ws, wsn = self._workspace(1, 1)
+        _lib.check(self._lib.kk_whisper_text_rows_admit_group(self._h, self._stream(), r.ctypes.data_as(C.c_void_p), len(r),
+                                                              _lib.WHISPER_GROUP_BEAM if beam else _lib.WHISPER_GROUP_PLAIN, C.c_void_p(features.data_ptr()),
+                                                              toks.ctypes.data_as(C.c_void_p), len(toks), C.byref(params), sp, int(max_candidates), ws, wsn),
+                   "kk_whisper_text_rows_admit_group")
+
+    def group_read(self, leader: int, n_rows: int, kept: bool = True):
+        """-> (finished [(tokens, sum)] in the order they finished, live [(tokens, sum)] by slot -- TextRuntime.beam_read for one window -- and the
+        leader's two kept logits rows fp32 device (2, V) or None)"""
+        import torch
+
+        from . import _lib
+
+        cap, F = self.dims.n_text_ctx, 2 * _lib.WHISPER_MAX_GROUP
+        fc, fs, fl = np.zeros(1, np.int32), np.zeros(F, np.float32), np.zeros(F, np.int32)
+        ft, lt = np.zeros((F, cap), np.int32), np.zeros((n_rows, cap), np.int32)
+        ls, ll = np.zeros(n_rows, np.float32), np.zeros(n_rows, np.int32)
+        k = torch.empty((2, self.dims.n_vocab), dtype=torch.float32, device=self.device) if kept else None
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _lib.check(self._lib.kk_whisper_text_rows_group_read(self._h, self._stream(), leader, cap, p(fc), p(fs), p(fl), p(ft), p(lt), p(ls), p(ll),
+                                                             None if k is None else C.c_void_p(k.data_ptr())), "kk_whisper_text_rows_group_read")
+        finished = [([int(t) for t in ft[f, : fl[f]]], float(fs[f])) for f in range(fc[0])]
+        live = [([int(t) for t in lt[g, : ll[g]]], float(ls[g])) for g in range(n_rows)]
+        return finished, live, k
+
+    def group_release(self, leader: int):
+        from . import _lib
+
+        _lib.check(self._lib.kk_whisper_text_rows_group_release(self._h, leader), "kk_whisper_text_rows_group_release")

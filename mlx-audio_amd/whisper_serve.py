@@ -23,8 +23,14 @@ A request submitted with `submit_sampled` decodes at its own temperature: its ro
 pick launch samples it while it picks the greedy rows; its result is `model.sample`'s for that window alone.  `submit` itself keeps
 refusing a temperature.  `Model.transcribe` (whisper_transcribe.py) is the long-form loop on top of this batcher.
 
-The scheduler talks to the model through an engine (`ModelEngine`); a fake engine tests it without a GPU.  Out of scope: best_of groups and beam
-search inside the batcher, `generate` (see `Model.transcribe`), text-to-id encoding, hipGraph capture of the round, prefill on a side stream."""
+Groups: `submit_beam` runs a window's beam search, and `submit_group` its `best_of` samples, on G rows of the same batch -- admitted together
+when G rows are free (strictly FIFO: the head of the queue waits and nothing overtakes it), on ONE projection of the window's cross K/V, stepped and
+picked in the rounds and the launches of the single rows beside them, and retired together at the poll that finds a beam group complete or every row
+of a plain group ended, or at the group's own limit.  The results are `model.beam_search`'s and `model.sample`'s for that window alone;
+`Model.beam_transcribe` is the long-form loop that uses them.
+
+The scheduler talks to the model through an engine (`ModelEngine`); a fake engine tests it without a GPU.  Out of scope: `generate` (see
+`Model.transcribe`), text-to-id encoding, hipGraph capture of the round, prefill on a side stream, prefilling a group's leader alone."""
 from __future__ import annotations
 
 import threading
@@ -49,6 +55,15 @@ class RowRead:
 
 
 @dataclass
+class GroupRead:
+    """what retiring a group reads back: TextRuntime.beam_read's lists for one window (a plain group: nothing finished, its rows as the live ones)"""
+    finished: List[Tuple[List[int], float]]
+    live: List[Tuple[List[int], float]]
+    no_speech_prob: float = float("nan")
+    language_probs: Optional[Dict[int, float]] = None
+
+
+@dataclass
 class ServeStats:
     rounds: int = 0            # rows_forward calls
     admissions: int = 0
@@ -57,6 +72,9 @@ class ServeStats:
     retired: int = 0
     row_rounds: int = 0        # rows over all rounds
     ended_row_rounds: int = 0  # of them, picks of rows that had already sampled eot (the price of polling every eos_check_interval rounds)
+    groups: int = 0            # of the admissions, groups (submit_beam, submit_group) ...
+    group_rows: int = 0        # ... and the rows they took
+    groups_retired: int = 0
 
 
 class ModelEngine:
@@ -125,7 +143,7 @@ class ModelEngine:
         with torch.cuda.device(self.model.device):
             return self._rows.flags()
 
-    def read(self, row: int, detected: bool, sot_index: Optional[int]) -> RowRead:
+    def _probabilities(self, out, kept, detected: bool, sot_index: Optional[int]) -> None:
         """The probabilities are decode's and detect_language's own expressions on (1, n_languages) and (1, V).  sot_index: where the prefill kept
         its logits (None: nothing was decoded).  torch's softmax over a long row reduces in an order that depends on where the row starts within 16
         bytes, so the kept row is placed as decode's view `pre[:, sot_index]` of its (1, S, V) prefill logits lies: sot_index * V floats behind an
@@ -133,18 +151,62 @@ class ModelEngine:
         import torch
 
         tok, V = self.tok, self.dims.n_vocab
+        if detected:
+            lo, hi = tok.language_tokens[0], tok.language_tokens[-1] + 1
+            probs = torch.softmax(kept[0:1][:, lo:hi], dim=-1).cpu().numpy()
+            out.language_probs = {t: float(probs[0, t - lo]) for t in tok.language_tokens}
+        if sot_index is not None:
+            shift = sot_index * V % 4
+            at_sot = torch.empty(shift + V, dtype=torch.float32, device=kept.device)[shift:].view(1, V)
+            at_sot.copy_(kept[1:2])
+            out.no_speech_prob = float(torch.softmax(at_sot, dim=-1)[:, tok.no_speech].cpu().numpy()[0])
+
+    def read(self, row: int, detected: bool, sot_index: Optional[int]) -> RowRead:
+        import torch
+
         with torch.cuda.device(self.model.device):
             toks, st, kept = self._rows.read(row, kept=True)
             out = RowRead(tokens=[int(t) for t in toks[: st.count]], count=int(st.count), sum_logprob=float(st.sum_logprob))
-            if detected:
-                lo, hi = tok.language_tokens[0], tok.language_tokens[-1] + 1
-                probs = torch.softmax(kept[0:1][:, lo:hi], dim=-1).cpu().numpy()
-                out.language_probs = {t: float(probs[0, t - lo]) for t in tok.language_tokens}
-            if sot_index is not None:
-                shift = sot_index * V % 4
-                at_sot = torch.empty(shift + V, dtype=torch.float32, device=kept.device)[shift:].view(1, V)
-                at_sot.copy_(kept[1:2])
-                out.no_speech_prob = float(torch.softmax(at_sot, dim=-1)[:, tok.no_speech].cpu().numpy()[0])
+            self._probabilities(out, kept, detected, sot_index)
+        return out
+
+    # ---- groups ------------------------------------------------------------------------------------------------------------------
+    def admit_group(self, rows: Sequence[int], x, init: Tuple[int, ...], options: DecodingOptions, beam: bool, max_candidates: int = 1,
+                    draws: Optional[Sequence[Tuple[float, int, int]]] = None):
+        """`admit` for a group on rows[0]'s cross K/V.  beam: a beam group (len(rows) = beam_size); else a plain one whose row g draws on draws[g]"""
+        import torch
+
+        from .whisper_decoding import _features, pick_params
+
+        feats, _ = _features(self.model, x)
+        params, bits = pick_params(self.dims, self.tok, options)
+        with torch.cuda.device(self.model.device):
+            self._rows.admit_group(rows, beam, feats[0], init, params, bits, max_candidates)
+            for row, draw in zip(rows, draws or ()):
+                self._rows.set_draw(row, *draw)
+        return feats[0]
+
+    def detect_group(self, rows: Sequence[int], out_index: int, token_index: Optional[int]) -> None:
+        """`detect` on the leader's logits; the id goes into the initial tokens of EVERY row of the group, on the device"""
+        import torch
+
+        if token_index is None:
+            return
+        lo, hi = self.tok.language_tokens[0], self.tok.language_tokens[-1] + 1
+        with torch.cuda.device(self.model.device):
+            ids = (self._rows._logits[out_index:out_index + 1][:, lo:hi].argmax(dim=-1) + lo).to(torch.int32)
+            for row in rows:
+                self._rows.set_token(row, token_index, ids)
+
+    def read_group(self, rows: Sequence[int], detected: bool, sot_index: Optional[int]) -> GroupRead:
+        """reads the group back (the probabilities on the leader's kept rows, as `read` takes them) and releases its rows"""
+        import torch
+
+        with torch.cuda.device(self.model.device):
+            finished, live, kept = self._rows.group_read(rows[0], len(rows), kept=True)
+            out = GroupRead(finished=finished, live=live)
+            self._probabilities(out, kept, detected, sot_index)
+            self._rows.group_release(rows[0])
         return out
 
     def close(self) -> None:
@@ -155,6 +217,9 @@ class _Request:
     def __init__(self, x, options: DecodingOptions, init: Tuple[int, ...], sot_index: int, limit: int, future: Future, draw=None):
         self.x, self.options, self.init, self.sot_index, self.limit, self.future = x, options, init, sot_index, limit, future
         self.draw = draw  # None: greedy; (temperature, seed, stream id): submit_sampled
+        self.kind: Optional[str] = None  # "beam" (submit_beam) or "plain" (submit_group): a group of G rows; None: one row
+        self.G, self.max_candidates, self.draws = 1, 1, None
+        self.rows: List[int] = []
         self.detect = options.language is None or options.task == "lang_id"
         self.row: Optional[int] = None
         self.phase = "detect" if self.detect else "prefill"  # -> "prefill" -> "step" -> "retire"
@@ -204,7 +269,47 @@ class WhisperBatcher:
             raise ValueError("seed must be an int and stream an int in 0 .. 2**32 - 1")
         return self._submit(mel_or_features, options, (float(options.temperature), seed, stream))
 
-    def _submit(self, mel_or_features, options: DecodingOptions, draw) -> Future:
+    def submit_beam(self, mel_or_features, options: DecodingOptions = DecodingOptions(beam_size=5), **overrides) -> Future:
+        """One window (2-D) searched with a beam -> Future[DecodingResult]: what `model.beam_search(window, options)` returns for it alone, field by
+        field, on `beam_size` rows of the batch.  The option checks are whisper_beam.verify_beam_options'.  A patience below 1 that leaves
+        fewer finished sequences than beams is refused: such a window completes before `beam_size` sequences have finished, the live prefixes top its
+        candidates up, and they go on changing with every step behind completion -- the solo result then depends on `eos_check_interval`, so there
+        is no one result to equal."""
+        from .whisper_beam import max_candidates, verify_beam_options
+
+        if overrides:
+            options = replace(options, **overrides)
+        options = verify_beam_options(options)
+        mc = max_candidates(options.beam_size, options.patience)
+        if mc < options.beam_size:
+            raise ValueError(f"round(beam_size * patience) = {mc} finished sequences are fewer than beam_size = {options.beam_size}: the live prefixes that "
+                             "top the candidates up change with every step after completion, so the result depends on when the poll runs "
+                             "(Model.beam_search takes such a patience)")
+        return self._submit(mel_or_features, options, None, kind="beam", G=options.beam_size, max_candidates=mc)
+
+    def submit_group(self, mel_or_features, options: DecodingOptions = DecodingOptions(temperature=1.0, best_of=5), seed: int = 0, stream: int = 0,
+                     **overrides) -> Future:
+        """One window (2-D) sampled `best_of` >= 2 times at temperature > 0 -> Future[DecodingResult]: what `model.sample(window, options, seed=seed,
+        streams=[stream])` returns for it alone, on `best_of` rows of the batch; row g draws on the stream id `stream * best_of + g`, which must fit 32
+        bits.  The option checks are whisper_sampling.verify_sampling_options'."""
+        from .whisper_sampling import verify_sampling_options
+
+        if overrides:
+            options = replace(options, **overrides)
+        options = verify_sampling_options(options)
+        if options.best_of is None or options.best_of < 2:
+            raise ValueError("submit_group takes best_of >= 2 (one sample per window is submit_sampled)")
+        if isinstance(seed, bool) or not isinstance(seed, int) or isinstance(stream, bool) or not isinstance(stream, int) or stream < 0:
+            raise ValueError("seed must be an int and stream an int >= 0")
+        G = options.best_of
+        if stream * G + G - 1 > 0xFFFFFFFF:
+            raise ValueError("a stream id times best_of must fit 32 bits")
+        draws = [(float(options.temperature), seed, stream * G + g) for g in range(G)]
+        return self._submit(mel_or_features, options, None, kind="plain", G=G, draws=draws)
+
+    def _submit(self, mel_or_features, options: DecodingOptions, draw, kind=None, G: int = 1, max_candidates: int = 1, draws=None) -> Future:
+        if G > self.max_rows:
+            raise ValueError(f"a group of {G} rows does not fit max_rows = {self.max_rows}")
         d = self.engine.dims
         tok = special_tokens(d)
         n_ctx = d.n_text_ctx
@@ -219,6 +324,7 @@ class WhisperBatcher:
         # decode picks once after the prefill and once per step i = 1 .. sample_len - 1 while sample_begin + i <= n_ctx
         limit = min(sample_len, n_ctx - sample_begin + 1)
         req = _Request(mel_or_features, options, init, sot_index, limit, Future(), draw)
+        req.kind, req.G, req.max_candidates, req.draws = kind, G, max_candidates, draws
         with self._lock:
             if self.closed:
                 raise RuntimeError("WhisperBatcher is closed")
@@ -228,10 +334,33 @@ class WhisperBatcher:
 
     # ---- one round -------------------------------------------------------------------------------------------------------------------------
     def _live(self) -> List[_Request]:
-        return [r for r in self._rows if r is not None]
+        """the requests in flight, each once (a group sits in G rows), by their first row"""
+        out: List[_Request] = []
+        for r in self._rows:
+            if r is not None and not any(r is o for o in out):
+                out.append(r)
+        return out
 
     def _free(self, r: _Request) -> None:
-        self._rows[r.row] = None
+        for row in r.rows:
+            self._rows[row] = None
+
+    def _group_result(self, r: _Request, rd: GroupRead) -> DecodingResult:
+        """whisper_beam.finalize / whisper_sampling.rank and results on what the group read back: the solo calls' own host steps"""
+        from .whisper_beam import finalize
+        from .whisper_sampling import SampledWindows, results
+
+        tok = special_tokens(self.engine.dims)
+        language = None if not tok.multilingual else r.init[r.sot_index + 1]
+        if r.detect:
+            language = max(rd.language_probs, key=rd.language_probs.get)
+        if r.kind == "beam":
+            cands = finalize(rd.finished, rd.live, r.G)
+        else:
+            cands = [(seq[: seq.index(tok.eot)] if tok.eot in seq else list(seq), total) for seq, total in rd.live]
+        win = SampledWindows(candidates=[cands], languages=[language], language_probs=[rd.language_probs], no_speech_probs=[rd.no_speech_prob],
+                             audio_features=[r.features], single=True, temperature=float(r.options.temperature))
+        return results(win, r.options.length_penalty)
 
     def _result(self, r: _Request, rd: RowRead) -> DecodingResult:
         tok = special_tokens(self.engine.dims)
@@ -246,7 +375,20 @@ class WhisperBatcher:
         return DecodingResult(audio_features=r.features, language=language, tokens=seq, avg_logprob=rd.sum_logprob / (len(seq) + 1),
                               no_speech_prob=rd.no_speech_prob, temperature=r.options.temperature)
 
+    def _retire_group(self, r: _Request) -> None:
+        try:
+            res = self._group_result(r, self.engine.read_group(r.rows, r.detect, r.sot_index))
+        except BaseException as e:  # noqa: BLE001  (the caller sits in Future.result())
+            r.future.set_exception(e)
+        else:
+            r.future.set_result(res)
+        self.stats.retired += 1
+        self.stats.groups_retired += 1
+        self._free(r)  # all its rows, in this round
+
     def _retire(self, r: _Request) -> None:
+        if r.kind is not None:
+            return self._retire_group(r)
         try:
             rd = self.engine.read(r.row, r.detect, r.sot_index if r.options.task != "lang_id" else None)
             res = self._result(r, rd)
@@ -268,23 +410,37 @@ class WhisperBatcher:
                 if not free or not self._queue:
                     return
                 r = self._queue[0]
-                cost_now, cost_next = (1, len(r.init)) if r.detect else (len(r.init), 0)
+                if r.future.cancelled():  # (a cancelled group must not hold the queue up while it waits for rows it will never take)
+                    self._queue.popleft()
+                    r.future.set_running_or_notify_cancel()
+                    continue
+                if len(free) < r.G:
+                    return  # a group needs its G rows at once; the head of the queue waits and nothing overtakes it
+                prefill = len(r.init) * r.G  # every row of a group prefills; the detection round runs on the leader alone
+                cost_now, cost_next = (1, prefill) if r.detect else (prefill, 0)
                 if (now and now + cost_now > self.max_round_tokens) or (nxt and nxt + cost_next > self.max_round_tokens):
                     return
                 self._queue.popleft()
             if not r.future.set_running_or_notify_cancel():
                 continue  # cancelled while it was queued
+            rows = free[: r.G]
             try:
-                if r.draw is None:
+                if r.kind is not None:
+                    r.features = self.engine.admit_group(rows, r.x, r.init, r.options, r.kind == "beam", r.max_candidates, r.draws)
+                elif r.draw is None:
                     r.features = self.engine.admit(free[0], r.x, r.init, r.options)
                 else:
                     r.features = self.engine.admit(free[0], r.x, r.init, r.options, draw=r.draw)
             except BaseException as e:  # noqa: BLE001
                 r.future.set_exception(e)
                 continue
-            r.row, r.x = free[0], None
-            self._rows[r.row] = r
+            r.row, r.rows, r.x = rows[0], list(rows), None
+            for row in rows:
+                self._rows[row] = r
             self.stats.admissions += 1
+            if r.kind is not None:
+                self.stats.groups += 1
+                self.stats.group_rows += r.G
             now, nxt = now + cost_now, nxt + cost_next
 
     def step(self) -> bool:
@@ -300,10 +456,11 @@ class WhisperBatcher:
                 self.stats.polls += 1
                 self._since_poll = 0
                 for r in self._live():
-                    if r.picks and flags[r.row]:
+                    # (a beam group's rows all carry its complete flag; a plain group is over when every row has ended)
+                    if r.picks and all(flags[row] for row in r.rows):
                         self._retire(r)
                         retired = True
-            self._admit(sum(len(r.init) for r in self._live() if r.phase == "prefill"))
+            self._admit(sum(len(r.init) * r.G for r in self._live() if r.phase == "prefill"))
             live = self._live()
             if not live:
                 return retired
@@ -315,28 +472,35 @@ class WhisperBatcher:
                     detects.append((r, len(out_rows)))
                     out_rows.append(at)
                     at += 1
-                elif r.phase == "prefill":  # the initial tokens; the logits of the sot position kept in slot 1
-                    items.append((r.row, 0, n, 0, r.sot_index, 1))
-                    out_rows += [at + r.sot_index] + ([at + n - 1] if r.sot_index != n - 1 else [])
+                elif r.phase == "prefill":  # the initial tokens; the logits of the sot position kept in slot 1 (a group: of its leader)
+                    for row in r.rows:
+                        lead = row == r.row
+                        items.append((row, 0, n, 0, r.sot_index if lead else -1, 1 if lead else 0))
+                        out_rows += ([at + r.sot_index] if lead else []) + ([at + n - 1] if r.sot_index != n - 1 or not lead else [])
+                        at += n
                     picks.append(r)
-                    at += n
                 else:  # the token of the last pick at the row's own position
-                    items.append((r.row, n + r.picks - 1, 1, -1, -1, 0))
-                    out_rows.append(at)
+                    for row in r.rows:
+                        items.append((row, n + r.picks - 1, 1, -1, -1, 0))
+                        out_rows.append(at)
+                        at += 1
                     picks.append(r)
-                    at += 1
             self.engine.forward(items, out_rows)
             for r, j in detects:
-                self.engine.detect(r.row, j, r.sot_index + 1 if r.options.language is None else None)
+                token_index = r.sot_index + 1 if r.options.language is None else None
+                if r.kind is not None:
+                    self.engine.detect_group(r.rows, j, token_index)
+                else:
+                    self.engine.detect(r.row, j, token_index)
                 r.phase = "retire" if r.options.task == "lang_id" else "prefill"
                 self.stats.detections += 1
             if picks:
-                self.engine.pick([r.row for r in picks])
+                self.engine.pick([row for r in picks for row in r.rows])
             for r in picks:
                 r.picks += 1
                 r.phase = "retire" if r.picks >= r.limit else "step"
             self.stats.rounds += 1
-            self.stats.row_rounds += len(live)
+            self.stats.row_rounds += sum(len(r.rows) for r in live)
             self._since_poll += 1
             return True
 

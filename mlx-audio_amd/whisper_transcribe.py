@@ -20,8 +20,10 @@ reference's loop driven by `model.decode` / `model.sample` per window on `embed_
 
 W = 2 * n_audio_ctx stands where the reference writes N_FRAMES (3000 for every real checkpoint).  What is taken over as it is: the loop keeps ONE
 `seek` across the clips of `clip_timestamps` and never moves it up to a later clip's start (whisper.py:543-584), so a clip that starts behind the
-previous clip's end begins where that one stopped.  Not built: `word_timestamps`, `hallucination_silence_threshold`, `beam_size`, `best_of` > 1,
-text prompts (`initial_prompt` is a list of token ids), a vocabulary file (the caller names theirs: `tokenizer=`)."""
+previous clip's end begins where that one stopped.  `beam_transcribe` is the same loop with OpenAI's pairing: a window at temperature 0 is
+searched with a beam (`WhisperBatcher.submit_beam`), one above it sampled `best_of` times (`submit_group`); `transcribe` itself keeps refusing `beam_size`
+and `best_of` > 1.  Not built: `word_timestamps`, `hallucination_silence_threshold`, text prompts (`initial_prompt` is a list of token ids), a vocabulary
+file (the caller names theirs: `tokenizer=`)."""
 from __future__ import annotations
 
 import zlib
@@ -265,9 +267,10 @@ def drive(states: Sequence[FileState], backend, max_rows: int) -> None:
 
 # ---- on the device ----------------------------------------------------------------------------------------------------------------------------
 class _DeviceBackend:
-    def __init__(self, model, batcher, mels, languages, seed: int, decode_options: dict):
+    def __init__(self, model, batcher, mels, languages, seed: int, decode_options: dict, beam: Optional[dict] = None):
         self.model, self.batcher, self.mels, self.languages, self.seed, self.options = model, batcher, mels, languages, seed, decode_options
         self.W = 2 * model.dims.n_audio_ctx
+        self.beam = beam  # beam_transcribe: dict(beam_size, best_of, patience); None: transcribe
 
     def encode(self, batch):
         from .whisper import mel_windows
@@ -282,6 +285,8 @@ class _DeviceBackend:
         # (an English-only vocabulary has no language token: the options' language is never written into its sot sequence, 0 only passes the checks)
         kw = dict(self.options, language=0 if self.languages[i] is None else self.languages[i], prompt=list(req.prompt))
         kw.pop("best_of", None)
+        if self.beam is not None:
+            return submit_window(self.batcher, features, req, kw, self.seed, **self.beam)
         if req.temperature > 0:
             return self.batcher.submit_sampled(features, DecodingOptions(**kw, temperature=req.temperature), seed=self.seed, stream=req.stream)
         return self.batcher.submit(features, DecodingOptions(**kw, temperature=0.0))
@@ -290,14 +295,33 @@ class _DeviceBackend:
         self.batcher.step()
 
 
-def check_transcribe_options(decode_options: dict, word_timestamps=False, hallucination_silence_threshold=None) -> None:
+def group_stream(req: WindowRequest) -> int:
+    """the stream id of a window's best_of group: row g draws on group_stream * best_of + g, which fits 32 bits for best_of <= 8 (KK_WHISPER_MAX_GROUP)"""
+    return (req.seek * 16 + req.temperature_index) % 2 ** 28
+
+
+def submit_window(batcher, features, req: WindowRequest, kw: dict, seed: int, beam_size: Optional[int], best_of: Optional[int], patience: Optional[float]):
+    """beam_transcribe's routing of one window (OpenAI's pairing, as whisper_beam.decode_with_fallback's): at temperature 0 the beam search (greedy
+    `submit` when beam_size is None), above it `best_of` samples on the group's stream id (`submit_sampled` on it when best_of is None or 1)"""
+    from .whisper_decoding import DecodingOptions
+
+    if req.temperature > 0:
+        if best_of in (None, 1):
+            return batcher.submit_sampled(features, DecodingOptions(**kw, temperature=req.temperature), seed=seed, stream=group_stream(req))
+        return batcher.submit_group(features, DecodingOptions(**kw, temperature=req.temperature, best_of=best_of), seed=seed, stream=group_stream(req))
+    if beam_size is None:
+        return batcher.submit(features, DecodingOptions(**kw, temperature=0.0))
+    return batcher.submit_beam(features, DecodingOptions(**kw, temperature=0.0, beam_size=beam_size, patience=patience))
+
+
+def check_transcribe_options(decode_options: dict, word_timestamps=False, hallucination_silence_threshold=None, beam: bool = False) -> None:
     if word_timestamps:
         raise NotImplementedError("word_timestamps is not built in transcribe (find_alignment gives token timestamps for one window)")
     if hallucination_silence_threshold is not None:
         raise NotImplementedError("hallucination_silence_threshold needs word_timestamps, which transcribe does not build")
-    if decode_options.get("beam_size") is not None or decode_options.get("patience") is not None:
+    if not beam and (decode_options.get("beam_size") is not None or decode_options.get("patience") is not None):
         raise NotImplementedError("beam search is not built in transcribe: the batcher's rows decode greedily or sample (Model.beam_search runs one window)")
-    if decode_options.get("best_of") not in (None, 1):
+    if not beam and decode_options.get("best_of") not in (None, 1):
         raise NotImplementedError("best_of > 1 is not built in transcribe: the batcher has no candidate groups (Model.sample runs them for one window)")
     if decode_options.get("task", "transcribe") not in ("transcribe", "translate"):
         raise ValueError(f"transcribe takes task 'transcribe' or 'translate', not {decode_options.get('task')!r}")
@@ -308,7 +332,7 @@ def check_transcribe_options(decode_options: dict, word_timestamps=False, halluc
 def transcribe(model, audio, *, temperature=(0.0, 0.2, 0.4, 0.6, 0.8, 1.0), compression_ratio_threshold: Optional[float] = 2.4,
                logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6, condition_on_previous_text: bool = True,
                initial_prompt: Optional[Sequence[int]] = None, clip_timestamps: Union[str, Sequence[float]] = "0", tokenizer=None, seed: int = 0, max_rows: int = 8,
-               word_timestamps: bool = False, hallucination_silence_threshold: Optional[float] = None, **decode_options):
+               word_timestamps: bool = False, hallucination_silence_threshold: Optional[float] = None, _beam: Optional[dict] = None, **decode_options):
     """whisper.py:355-866 for one recording (1-D samples at 16 kHz: numpy or torch) -> TranscribeResult, or for a list of them -> a list, all on one
     decoder batch of `max_rows` rows.  tokenizer: a whisper_tokenizer.Tokenizer, or the path of a tiktoken-format rank file, or None (then every `text`
     is None and `compression_ratio_threshold` must be None).  decode_options: DecodingOptions fields (language, task, sample_len, suppress_tokens, ...)."""
@@ -321,7 +345,7 @@ def transcribe(model, audio, *, temperature=(0.0, 0.2, 0.4, 0.6, 0.8, 1.0), comp
     decode_options = dict(decode_options)
     decode_options.pop("max_tokens", None)  # (whisper.py:437-438)
     decode_options.pop("generation_stream", None)
-    check_transcribe_options(decode_options, word_timestamps, hallucination_silence_threshold)
+    check_transcribe_options(decode_options, word_timestamps, hallucination_silence_threshold, beam=_beam is not None)
     DecodingOptions(**decode_options)  # an unknown name is a TypeError here, before anything runs
     if isinstance(seed, bool) or not isinstance(seed, int):
         raise ValueError("seed must be an int")
@@ -354,8 +378,33 @@ def transcribe(model, audio, *, temperature=(0.0, 0.2, 0.4, 0.6, 0.8, 1.0), comp
             futs = [batcher.submit(m[:W], DecodingOptions(task="lang_id")) for m in mels]
             batcher.run_until_idle()
             languages = [f.result().language for f in futs]
-        drive(states, _DeviceBackend(model, batcher, mels, languages, seed, decode_options), max_rows)
+        # (beam_transcribe: max_rows files in flight may wait for each other's rows; the batcher queues them in order)
+        drive(states, _DeviceBackend(model, batcher, mels, languages, seed, decode_options, _beam), max_rows)
     finally:
         batcher.close()
     out = [s.result(l) for s, l in zip(states, languages)]
     return out[0] if single else out
+
+
+def beam_transcribe(model, audio, *, beam_size: Optional[int] = 5, best_of: Optional[int] = 5, patience: Optional[float] = None, **kw):
+    """`transcribe` with OpenAI's transcription defaults: a window at temperature 0 is searched with a beam of `beam_size`
+    (`WhisperBatcher.submit_beam`; greedy `submit` when beam_size is None), a window above it is sampled `best_of` times and ranked (`submit_group` on the
+    stream id `(seek * 16 + temperature index) % 2 ** 28`; `submit_sampled` on the same id when best_of is None or 1).  Every other argument is
+    transcribe's, and so are the loop, the files' state machines and the contract: a file's result equals that of the file alone.  max_rows must hold
+    the larger of the two group sizes."""
+    from .whisper_beam import max_candidates, verify_beam_options
+    from .whisper_decoding import DecodingOptions
+    from .whisper_sampling import MAX_GROUP
+
+    if beam_size is not None:
+        verify_beam_options(DecodingOptions(beam_size=beam_size, patience=patience))
+        if max_candidates(beam_size, patience) < beam_size:
+            raise ValueError("round(beam_size * patience) must be at least beam_size in the batcher (WhisperBatcher.submit_beam)")
+    elif patience is not None:
+        raise ValueError("patience requires beam_size to be given")
+    if best_of is not None and (isinstance(best_of, bool) or not isinstance(best_of, int) or not 1 <= best_of <= MAX_GROUP):
+        raise ValueError(f"best_of must be in 1 .. {MAX_GROUP} (KK_WHISPER_MAX_GROUP)")
+    need = max(beam_size or 1, best_of or 1)
+    if kw.get("max_rows", 8) < need:
+        raise ValueError(f"max_rows = {kw.get('max_rows', 8)} cannot hold a group of {need} rows")
+    return transcribe(model, audio, _beam=dict(beam_size=beam_size, best_of=best_of, patience=patience), **kw)
