@@ -17,8 +17,11 @@
 //   Rows with their own window, position, pick parameters and lifetime in a second state buffer.  A round is the window's launch sequence behind
 //   text_plan_kernel, which fills the per-row index arrays and tokens from a table of items passed as the launch's argument.
 //   A row picks greedily unless rows_set_draw gave it a draw after its admission; the round's one pick launch serves both kinds.
-//   Groups (rows_groups_bind, rows_admit_group): G rows on their leader's cross K/V that are admitted, stepped, picked and released together --
+//   Groups (rows_groups_bind, rows_admit_group): G >= 1 rows on their leader's cross K/V that are admitted, stepped, picked and released together --
 //   a beam group (top-k in the same pick launch, one select workgroup per group, the step's self keys through the group's owner table) or a plain one.
+//   A single row is the plain group of one: the same items, launches and values.  There is ONE admission (rows_admit_check, rows_admit_body) behind two
+//   entries: rows_admit_group, and rows_admit -- one row in no group, on a handle with or without the groups buffer, admitted over without a release.  The
+//   serving code binds the buffer when it opens row mode and admits every request as a group; rows of no group come from rows_admit alone.
 #include "kk_host.h"
 #include "kk_philox.h"
 #include "../../include/kokoro_hip.h"
@@ -206,7 +209,8 @@ int project_cross(const kk_whisper_text* m, hipStream_t st, const float* feature
   return 0;
 }
 inline size_t mask_words(const kk_whisper_text_config& c) { return ((size_t)c.n_vocab + 31) / 32; }
-// a pick's parameters against the model, and their upload with the suppress bitmask (null: nothing suppressed); synchronised, the host arrays may go away
+// a pick's parameters against the model, and their upload with the suppress bitmask (null: nothing suppressed); NOT synchronised: the caller
+// synchronises the stream before it returns, the host arrays may go away then
 int check_pick_params(const char* who, const kk_whisper_text_config& c, const kk_whisper_pick_params* params) {
   if (params->n_vocab != c.n_vocab) return kk_failf("%s: params.n_vocab differs from the model's", who);
   if (params->eot < 0 || params->eot >= c.n_vocab || params->timestamp_begin < 0 || params->timestamp_begin > c.n_vocab)
@@ -219,8 +223,23 @@ int upload_pick_params(const char* who, hipStream_t st, const kk_whisper_text_co
   if (hipMemcpyAsync(dparams, params, sizeof *params, hipMemcpyHostToDevice, st) != hipSuccess ||
       (suppress ? hipMemcpyAsync(dmask, suppress, bytes, hipMemcpyHostToDevice, st) : hipMemsetAsync(dmask, 0, bytes, st)) != hipSuccess)
     return kk_failf("%s: upload failed", who);
-  if (hipStreamSynchronize(st) != hipSuccess) return kk_failf("%s: stream sync failed", who);
   return 0;
+}
+// The live prefixes of B rows that were read back (pick states, token stores [B][T]) into the caller's live_tokens [B][cap], live_sum and live_length.
+// own: the rows' owner rows [B][T], or null.  A live beam's tokens lie where its ancestors wrote them: token i in the row that owns position begin + i;
+// slot_of maps that owner row to its place among the B (-1: not one of them, the row keeps its own token, as it does without a table).
+template <class SlotOf>
+void live_prefixes(int B, int T, int n, int cap, int begin, const kk_whisper_pick_state* rows, const int32_t* tok, const int32_t* own, SlotOf slot_of,
+                   int32_t* live_tokens, float* live_sum, int32_t* live_length) {
+  for (int b = 0; b < B; ++b) {
+    const int len = rows[b].count < 0 ? 0 : (rows[b].count < n ? rows[b].count : n);
+    live_sum[b] = rows[b].sum_logprob;
+    live_length[b] = len;
+    for (int i = 0; i < len; ++i) {
+      const int o = own && begin + i < T ? slot_of(own[(size_t)b * T + begin + i]) : b;
+      live_tokens[(size_t)b * cap + i] = tok[(size_t)(o < 0 ? b : o) * T + i];
+    }
+  }
 }
 }  // namespace
 
@@ -637,6 +656,7 @@ extern "C" int kk_whisper_text_pick_setup(kk_whisper_text* m, void* stream, cons
   KK_TRY(window_bound(who, m, s));
   KK_TRY(check_pick_params(who, m->cfg, params));
   KK_TRY(upload_pick_params(who, (hipStream_t)stream, m->cfg, params, suppress, s.params, s.suppress));
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return kk_failf("%s: stream sync failed", who);
   m->sampling = m->beam = false;
   m->picking = true;
   return kk_op_whisper_pick_reset(stream, m->B, s.rows, s.not_ended);
@@ -761,17 +781,8 @@ extern "C" int kk_whisper_text_beam_read(kk_whisper_text* m, void* stream, int c
       hipMemcpyAsync(own.data(), bb.owner[m->beam_flip], own.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipMemcpyAsync(rows.data(), s.rows, (size_t)B * sizeof(kk_whisper_pick_state), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
     return kk_failf("%s: read failed", who);
-  for (int b = 0; b < B; ++b) {  // a live row's tokens lie where its ancestors wrote them: token i in the row that owns position beam_begin + i
-    const int len = rows[b].count < 0 ? 0 : (rows[b].count < n ? rows[b].count : n);
-    live_sum[b] = rows[b].sum_logprob;
-    live_length[b] = len;
-    for (int i = 0; i < len; ++i) {
-      const int p = m->beam_begin + i;
-      int o = p < T ? own[(size_t)b * T + p] : b;
-      if (o < 0 || o >= B) o = b;
-      live_tokens[(size_t)b * cap + i] = tok[(size_t)o * T + i];
-    }
-  }
+  live_prefixes(B, T, n, cap, m->beam_begin, rows.data(), tok.data(), own.data(), [B](int o) { return o >= 0 && o < B ? o : -1; }, live_tokens, live_sum,
+                live_length);  // the window's table names batch rows
   return 0;
 }
 
@@ -848,6 +859,49 @@ int rows_check_row(const char* who, const kk_whisper_text* m, int row, bool admi
   if (admitted && !m->rows[row].admitted) return kk_failf("%s: row %d was never admitted", who, row);
   return 0;
 }
+// One admission, behind rows_admit (one row) and rows_admit_group (rows[0] leads).  The checks both make of what is admitted, and the workspace:
+int rows_admit_check(const char* who, const kk_whisper_text* m, int n, const kk_whisper_pick_params* params, void* workspace, size_t workspace_bytes, RowsWork& p) {
+  const kk_whisper_text_config& c = m->cfg;
+  if (n < 1 || n > c.n_text_ctx) return kk_failf("%s: %d initial tokens are outside [1, n_text_ctx = %d]", who, n, c.n_text_ctx);
+  KK_TRY(check_pick_params(who, c, params));
+  Workspace ws;
+  bind(ws, workspace, workspace_bytes);
+  plan_rows_work(c, 1, false, ws, p);
+  if (ws.oom) return kk_failf("%s: workspace too small", who);
+  return 0;
+}
+// and, everything checked, the admission: the window's cross K/V is projected ONCE (set_audio's launches with one window), into the leader's slices
+// -- the other rows name them; every row gets the initial tokens, the pick parameters and bitmask, a reset pick state and no draw (greedy until
+// rows_set_draw).  beam: the buffers of a beam group, whose tables are reset too, or null.  Synchronised once, at the end: the host arrays may go away.
+int rows_admit_body(const char* who, kk_whisper_text* m, void* stream, const RowsState& s, const RowsWork& p, const int32_t* rows, int n_rows,
+                    const float* audio_features, const int32_t* tokens, int n, const kk_whisper_pick_params* params, const uint32_t* suppress,
+                    const KKGroupBufs* beam) {
+  const kk_whisper_text_config& c = m->cfg;
+  hipStream_t st = (hipStream_t)stream;
+  for (int k = 0; k < n_rows; ++k) {  // a failure below leaves the rows unusable, not half new
+    m->rows[rows[k]].admitted = false;
+    m->rows[rows[k]].logit = -1;
+  }
+  KK_TRY(project_cross(m, st, audio_features, 1, p.t.feat, s.cross, (int)m->rows.size(), rows[0]));
+  KKGroupRows gr;
+  memset(&gr, 0, sizeof gr);
+  for (int k = 0; k < n_rows; ++k) {
+    const int row = gr.row[k] = rows[k];
+    if (hipMemcpyAsync(s.init + (size_t)row * c.n_text_ctx, tokens, (size_t)n * 4, hipMemcpyHostToDevice, st) != hipSuccess) return kk_failf("%s: upload failed", who);
+    KK_TRY(upload_pick_params(who, st, c, params, suppress, s.params + row, s.suppress + (size_t)row * mask_words(c)));
+    if (hipMemsetAsync(s.draws + row, 0, sizeof(PickDraw), st) != hipSuccess) return kk_failf("%s: clearing the draw failed", who);
+    KK_TRY(kk_op_whisper_pick_reset(stream, 1, s.rows + row, s.not_ended));
+  }
+  if (beam) KK_TRY(kk_launch_whisper_rows_group_reset(st, gr, n_rows, c.n_text_ctx, *beam));
+  if (hipStreamSynchronize(st) != hipSuccess) return kk_failf("%s: stream sync failed", who);
+  for (int k = 0; k < n_rows; ++k) {
+    kk_whisper_text::Row& r = m->rows[rows[k]];
+    r.admitted = true;
+    r.n_init = n;
+    r.at = 0;
+  }
+  return 0;
+}
 }  // namespace
 
 extern "C" size_t kk_whisper_text_rows_state_bytes(const kk_whisper_text* m, int max_rows) {
@@ -893,26 +947,10 @@ extern "C" int kk_whisper_text_rows_admit(kk_whisper_text* m, void* stream, int 
   KK_TRY(rows_bound(who, m, s));
   KK_TRY(rows_check_row(who, m, row, false));
   if (!audio_features || !tokens || !params || !workspace) return kk_failf("%s: null argument", who);
-  const kk_whisper_text_config& c = m->cfg;
-  if (n < 1 || n > c.n_text_ctx) return kk_failf("%s: %d initial tokens are outside [1, n_text_ctx = %d]", who, n, c.n_text_ctx);
-  KK_TRY(check_pick_params(who, c, params));
-  hipStream_t st = (hipStream_t)stream;
-  Workspace ws;
-  bind(ws, workspace, workspace_bytes);
   RowsWork p;
-  plan_rows_work(c, 1, false, ws, p);
-  if (ws.oom) return kk_failf("%s: workspace too small", who);
+  KK_TRY(rows_admit_check(who, m, n, params, workspace, workspace_bytes, p));
   if (m->rows[row].group >= 0) return kk_failf("%s: row %d belongs to the group led by row %d (kk_whisper_text_rows_group_release first)", who, row, m->rows[row].group);
-  m->rows[row].admitted = false;  // a failure below leaves the row unusable, not half new
-  m->rows[row].logit = -1;
-  KK_TRY(project_cross(m, st, audio_features, 1, p.t.feat, s.cross, (int)m->rows.size(), row));  // set_audio's launches with one window, into this row's slices
-  if (hipMemcpyAsync(s.init + (size_t)row * c.n_text_ctx, tokens, (size_t)n * 4, hipMemcpyHostToDevice, st) != hipSuccess) return kk_failf("%s: upload failed", who);
-  KK_TRY(upload_pick_params(who, st, c, params, suppress, s.params + row, s.suppress + (size_t)row * mask_words(c)));
-  KK_TRY(kk_op_whisper_pick_reset(stream, 1, s.rows + row, s.not_ended));
-  if (hipMemsetAsync(s.draws + row, 0, sizeof(PickDraw), st) != hipSuccess) return kk_failf("%s: clearing the draw failed", who);  // greedy until rows_set_draw
-  m->rows[row].admitted = true;
-  m->rows[row].n_init = n;
-  return 0;
+  return rows_admit_body(who, m, stream, s, p, &row, 1, audio_features, tokens, n, params, suppress, nullptr);  // a single row: no group, bound or not
 }
 
 extern "C" int kk_whisper_text_rows_forward(kk_whisper_text* m, void* stream, const kk_whisper_rows_item* items, int n_items, const int32_t* out_rows, int n_out,
@@ -1188,37 +1226,10 @@ extern "C" int kk_whisper_text_rows_admit_group(kk_whisper_text* m, void* stream
     seen |= 1u << rows[k];
     if (m->rows[rows[k]].group >= 0) return kk_failf("%s: row %d is already in the group led by row %d", who, rows[k], m->rows[rows[k]].group);
   }
-  const kk_whisper_text_config& c = m->cfg;
-  if (n < 1 || n > c.n_text_ctx) return kk_failf("%s: %d initial tokens are outside [1, n_text_ctx = %d]", who, n, c.n_text_ctx);
-  KK_TRY(check_pick_params(who, c, params));
-  hipStream_t st = (hipStream_t)stream;
-  Workspace ws;
-  bind(ws, workspace, workspace_bytes);
   RowsWork p;
-  plan_rows_work(c, 1, false, ws, p);
-  if (ws.oom) return kk_failf("%s: workspace too small", who);
+  KK_TRY(rows_admit_check(who, m, n, params, workspace, workspace_bytes, p));
+  KK_TRY(rows_admit_body(who, m, stream, s, p, rows, n_rows, audio_features, tokens, n, params, suppress, kind == KK_WHISPER_GROUP_BEAM ? &gb : nullptr));
   const int lead = rows[0];
-  for (int k = 0; k < n_rows; ++k) {  // a failure below leaves the rows unusable, not half new
-    m->rows[rows[k]].admitted = false;
-    m->rows[rows[k]].logit = -1;
-  }
-  KK_TRY(project_cross(m, st, audio_features, 1, p.t.feat, s.cross, (int)m->rows.size(), lead));  // ONCE, into the leader's slices: the others name them
-  const size_t words = mask_words(c);
-  KKGroupRows gr;
-  memset(&gr, 0, sizeof gr);
-  for (int k = 0; k < n_rows; ++k) {
-    const int row = rows[k];
-    gr.row[k] = row;
-    if (hipMemcpyAsync(s.init + (size_t)row * c.n_text_ctx, tokens, (size_t)n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(s.params + row, params, sizeof *params, hipMemcpyHostToDevice, st) != hipSuccess ||
-        (suppress ? hipMemcpyAsync(s.suppress + (size_t)row * words, suppress, words * 4, hipMemcpyHostToDevice, st)
-                  : hipMemsetAsync(s.suppress + (size_t)row * words, 0, words * 4, st)) != hipSuccess ||
-        hipMemsetAsync(s.draws + row, 0, sizeof(PickDraw), st) != hipSuccess)
-      return kk_failf("%s: upload failed", who);
-    KK_TRY(kk_op_whisper_pick_reset(stream, 1, s.rows + row, s.not_ended));
-  }
-  if (kind == KK_WHISPER_GROUP_BEAM) KK_TRY(kk_launch_whisper_rows_group_reset(st, gr, n_rows, c.n_text_ctx, gb));
-  if (hipStreamSynchronize(st) != hipSuccess) return kk_failf("%s: stream sync failed", who);  // once: the host arrays may go away
   kk_whisper_text::Group& g = m->groups[lead];
   g = kk_whisper_text::Group();
   g.live = true;
@@ -1226,13 +1237,9 @@ extern "C" int kk_whisper_text_rows_admit_group(kk_whisper_text* m, void* stream
   g.G = n_rows;
   g.max_candidates = kind == KK_WHISPER_GROUP_BEAM ? max_candidates : 0;
   for (int k = 0; k < n_rows; ++k) {
-    kk_whisper_text::Row& r = m->rows[rows[k]];
     g.rows[k] = rows[k];
-    r.admitted = true;
-    r.n_init = n;
-    r.group = lead;
-    r.slot = k;
-    r.at = 0;
+    m->rows[rows[k]].group = lead;
+    m->rows[rows[k]].slot = k;
   }
   return 0;
 }
@@ -1284,20 +1291,13 @@ extern "C" int kk_whisper_text_rows_group_read(kk_whisper_text* m, void* stream,
   }
   if (ok && kept) ok = hipMemcpyAsync(kept, s.kept + (size_t)leader * 2 * c.n_vocab, (size_t)2 * c.n_vocab * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
   if (!ok || hipStreamSynchronize(st) != hipSuccess) return kk_failf("%s: read failed", who);
-  for (int k = 0; k < G; ++k) {  // a live beam's tokens lie where its ancestors wrote them: token i in the row that owns position begin + i
-    const int len = rows[k].count < 0 ? 0 : (rows[k].count < n ? rows[k].count : n);
-    live_sum[k] = rows[k].sum_logprob;
-    live_length[k] = len;
-    for (int i = 0; i < len; ++i) {
-      int slot = k;
-      if (beam && g.picks > 0 && g.begin + i < T) {
-        const int o = own[(size_t)k * T + g.begin + i];
-        for (int q = 0; q < G; ++q)
-          if (g.rows[q] == o) slot = q;
-      }
-      live_tokens[(size_t)k * cap + i] = tok[(size_t)slot * T + i];
-    }
-  }
+  const auto slot_of = [&g](int o) {  // the group's table names decoder rows: the slot is the row's place in the group's list
+    int slot = -1;
+    for (int q = 0; q < g.G; ++q)
+      if (g.rows[q] == o) slot = q;
+    return slot;
+  };
+  live_prefixes(G, T, n, cap, g.begin, rows.data(), tok.data(), beam && g.picks > 0 ? own.data() : nullptr, slot_of, live_tokens, live_sum, live_length);
   return 0;
 }
 

@@ -23,12 +23,10 @@ from __future__ import annotations
 
 import math
 from dataclasses import replace
-from typing import Dict, List, Optional
-
-import numpy as np
+from typing import Optional
 
 from . import whisper_sampling
-from .whisper_decoding import DecodingOptions, _features, detect_language, initial_tokens, pick_params, special_tokens
+from .whisper_decoding import DecodingOptions, _features, window_loop, window_prologue
 from .whisper_sampling import MAX_GROUP, SampledWindows, fallback_loop, results
 
 
@@ -95,46 +93,16 @@ def beam_candidates(model, mel_or_features, options: DecodingOptions = DecodingO
     options = verify_beam_options(options)
     if eos_check_interval < 1:
         raise ValueError("eos_check_interval must be >= 1")
-    d, rt = model.dims, model._text
-    tok = special_tokens(d)
-    n_ctx = d.n_text_ctx
-    K = options.beam_size
-    sample_len = options.sample_len or n_ctx // 2
-    init = initial_tokens(tok, options, n_ctx, sample_len)
-    sample_begin, sot_index = len(init), init.index(tok.sot)
-    if sample_begin >= n_ctx:
-        raise ValueError(f"{sample_begin} initial tokens leave no room in n_text_ctx = {n_ctx}")
-    feats, single = _features(model, mel_or_features)
-    n_audio = feats.shape[0]
-    tokens = np.tile(np.asarray(init, np.int32), (n_audio * K, 1))
-
-    languages: List[Optional[int]] = [None if not tok.multilingual else init[sot_index + 1]] * n_audio
-    lang_probs: List[Optional[Dict[int, float]]] = [None] * n_audio
-    if options.language is None:  # _detect_language (:557-570)
-        lang_ids, lang_probs = detect_language(model, feats)
-        languages = [max(p, key=p.get) for p in lang_probs]
-        tokens[:, sot_index + 1] = np.repeat(lang_ids.cpu().numpy(), K)
-
-    params, bits = pick_params(d, tok, options)
+    rt, K = model._text, options.beam_size
+    w = window_prologue(model, mel_or_features, options, K)
     with torch.cuda.device(model.device):
-        rt.set_audio_groups(feats, K)
-        rt.pick_setup(params, bits)
-        rt.beam_setup(K, max_candidates(K, options.patience))
-        pre = rt.forward(torch.from_numpy(tokens).to(model.device), True)  # the prefill, (B, S, V)
-        no_speech = torch.softmax(pre[::K, sot_index], dim=-1)[:, tok.no_speech]  # the rows of a window share their prefill
-        rt.pick()
-        for i in range(1, sample_len):
-            if sample_begin + i > n_ctx:  # (:604)
-                break
-            rt.step()
-            rt.pick()
-            if i % eos_check_interval == 0 and rt.beam_not_complete() == 0:
-                break
+        no_speech = window_loop(model, w, options, K, eos_check_interval, lambda: rt.beam_setup(K, max_candidates(K, options.patience)),
+                                lambda: rt.beam_not_complete() == 0)
         finished, live = rt.beam_read()
         no_speech = no_speech.cpu().numpy()
-    cands = [finalize(finished[a], live[a], K) for a in range(n_audio)]
-    return SampledWindows(candidates=cands, languages=languages, language_probs=lang_probs, no_speech_probs=[float(p) for p in no_speech], audio_features=feats,
-                          single=single, temperature=0.0)
+    cands = [finalize(finished[a], live[a], K) for a in range(w.feats.shape[0])]
+    return SampledWindows(candidates=cands, languages=w.languages, language_probs=w.lang_probs, no_speech_probs=[float(p) for p in no_speech],
+                          audio_features=w.feats, single=w.single, temperature=0.0)
 
 
 def beam_search(model, mel_or_features, options: DecodingOptions = DecodingOptions(beam_size=5), eos_check_interval: int = 8, **kwargs):

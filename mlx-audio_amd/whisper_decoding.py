@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass, field, replace
-from typing import Dict, Iterable, List, Optional, Tuple, Union
+from typing import Dict, Iterable, List, NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 
@@ -499,6 +499,76 @@ def detect_language(model, mel_or_features):
     return ids, out
 
 
+class Windows(NamedTuple):
+    """what DecodingTask.run knows of a batch of windows before its loop (`window_prologue`)"""
+    tokens: np.ndarray  # int32 (rows, S): every row's initial tokens, the detected language written in
+    sample_len: int
+    sample_begin: int
+    sot_index: int
+    feats: object       # fp32 device (n_audio, n_audio_ctx, n_audio_state)
+    single: bool        # the input was 2-D
+    languages: List[Optional[int]]
+    lang_probs: List[Optional[Dict[int, float]]]  # per window; None where nothing was detected
+
+
+def window_prologue(model, mel_or_features, options: DecodingOptions, n_group: int = 1) -> Windows:
+    """DecodingTask.run up to its loop, behind the caller's option checks, for `n_group` decoder rows per window: the initial tokens (decoding.py:480-506),
+    the room check, the features, and _detect_language (:557-570) written into the tokens of every row of its window."""
+    d = model.dims
+    tok = special_tokens(d)
+    n_ctx = d.n_text_ctx
+    sample_len = options.sample_len or n_ctx // 2
+    init = initial_tokens(tok, options, n_ctx, sample_len)
+    sample_begin, sot_index = len(init), init.index(tok.sot)
+    if sample_begin >= n_ctx:
+        raise ValueError(f"{sample_begin} initial tokens leave no room in n_text_ctx = {n_ctx}")
+    feats, single = _features(model, mel_or_features)
+    n_audio = feats.shape[0]
+    tokens = np.tile(np.asarray(init, np.int32), (n_audio * n_group, 1))
+    languages: List[Optional[int]] = [None if not tok.multilingual else init[sot_index + 1]] * n_audio
+    lang_probs: List[Optional[Dict[int, float]]] = [None] * n_audio
+    if options.language is None or options.task == "lang_id":
+        ids, lang_probs = detect_language(model, feats)
+        languages = [max(p, key=p.get) for p in lang_probs]
+        if options.language is None:
+            tokens[:, sot_index + 1] = np.repeat(ids.cpu().numpy(), n_group)
+    return Windows(tokens, sample_len, sample_begin, sot_index, feats, single, languages, lang_probs)
+
+
+def window_loop(model, w: Windows, options: DecodingOptions, n_group: int, eos_check_interval: int, setup, done, audio_is_set: bool = False):
+    """The main loop of DecodingTask.run (:590-616, 641-669) on `n_group` rows per window: pick_setup and, behind it, the caller's `setup()` (None: greedy
+    picks); the prefill; then step and pick until `done()` -- asked every eos_check_interval steps --, sample_len or the text context ends it.  Called with
+    the model's device current.  audio_is_set: the windows' cross K/V is the state's already.  -> no_speech_prob per window, on the device"""
+    import torch
+
+    d, rt = model.dims, model._text
+    tok = special_tokens(d)
+    params, bits = pick_params(d, tok, options)
+    if audio_is_set:
+        rt.rewind(0)
+    else:
+        rt.set_audio_groups(w.feats, n_group)
+    rt.pick_setup(params, bits)
+    if setup is not None:
+        setup()
+    pre = rt.forward(torch.from_numpy(w.tokens).to(model.device), True)  # the prefill, (B, S, V)
+    no_speech = torch.softmax(pre[::n_group, w.sot_index], dim=-1)[:, tok.no_speech]  # the rows of a window share their prefill
+    rt.pick()
+    for i in range(1, w.sample_len):
+        if w.sample_begin + i > d.n_text_ctx:  # (:604)
+            break
+        rt.step()
+        rt.pick()
+        if i % eos_check_interval == 0 and done():
+            break
+    return no_speech
+
+
+def cut_at_eot(tokens, eot: int) -> List[int]:
+    seq = [int(t) for t in tokens]
+    return seq[: seq.index(eot)] if eot in seq else seq
+
+
 def decode(model, mel_or_features, options: DecodingOptions = DecodingOptions(), eos_check_interval: int = 8, **kwargs):
     """decoding.py:710-742 -> DecodingTask.run (:618-707), greedy at temperature 0"""
     import torch
@@ -508,58 +578,24 @@ def decode(model, mel_or_features, options: DecodingOptions = DecodingOptions(),
     options = verify_options(options)
     if eos_check_interval < 1:
         raise ValueError("eos_check_interval must be >= 1")
-    d, rt = model.dims, model._text
-    tok = special_tokens(d)
-    n_ctx = d.n_text_ctx
-    sample_len = options.sample_len or n_ctx // 2
-    init = initial_tokens(tok, options, n_ctx, sample_len)
-    sample_begin, sot_index = len(init), init.index(tok.sot)
-    if sample_begin >= n_ctx:
-        raise ValueError(f"{sample_begin} initial tokens leave no room in n_text_ctx = {n_ctx}")
-    feats, single = _features(model, mel_or_features)
-    B = feats.shape[0]
-    tokens = np.tile(np.asarray(init, np.int32), (B, 1))
-
-    # _detect_language (:557-570)
-    languages: List[Optional[int]] = [None if not tok.multilingual else init[sot_index + 1]] * B
-    lang_probs = None
-    if options.language is None or options.task == "lang_id":
-        ids, lang_probs = detect_language(model, feats)
-        languages = [max(p, key=p.get) for p in lang_probs]
-        if options.language is None:
-            tokens[:, sot_index + 1] = ids.cpu().numpy()
+    rt = model._text
+    w = window_prologue(model, mel_or_features, options)
+    B = w.feats.shape[0]
     if options.task == "lang_id":
-        res = [DecodingResult(audio_features=feats[b], language=languages[b], language_probs=lang_probs[b]) for b in range(B)]
-        return res[0] if single else res
-
-    params, bits = pick_params(d, tok, options)
-
+        res = [DecodingResult(audio_features=w.feats[b], language=w.languages[b], language_probs=w.lang_probs[b]) for b in range(B)]
+        return res[0] if w.single else res
     with torch.cuda.device(model.device):
-        if lang_probs is None:
-            rt.set_audio(feats)
-        else:
-            rt.rewind(0)  # detection has made this window's cross K/V already
-        rt.pick_setup(params, bits)
-        pre = rt.forward(torch.from_numpy(tokens).to(model.device), True)  # the prefill, (B, S, V)
-        no_speech = torch.softmax(pre[:, sot_index], dim=-1)[:, tok.no_speech]
-        rt.pick()
-        for i in range(1, sample_len):
-            if sample_begin + i > n_ctx:  # (:604)
-                break
-            rt.step()
-            rt.pick()
-            if i % eos_check_interval == 0 and rt.not_ended() == 0:
-                break
+        # (detection has made these windows' cross K/V already)
+        no_speech = window_loop(model, w, options, 1, eos_check_interval, None, lambda: rt.not_ended() == 0, audio_is_set=options.language is None)
         toks, rows = rt.read()
         no_speech = no_speech.cpu().numpy()
+    eot = special_tokens(model.dims).eot
     out = []
     for b in range(B):
-        seq = [int(t) for t in toks[b, : rows[b].count]]
-        if tok.eot in seq:
-            seq = seq[: seq.index(tok.eot)]
-        out.append(DecodingResult(audio_features=feats[b], language=languages[b], tokens=seq,
+        seq = cut_at_eot(toks[b, : rows[b].count], eot)
+        out.append(DecodingResult(audio_features=w.feats[b], language=w.languages[b], tokens=seq,
                                   avg_logprob=float(rows[b].sum_logprob) / (len(seq) + 1), no_speech_prob=float(no_speech[b]), temperature=options.temperature))
-    return out[0] if single else out
+    return out[0] if w.single else out
 
 
 # ---- row mode: decoder rows that join and leave one running batch (kk_whisper_text_rows_*) ------------------------------------------
@@ -595,6 +631,9 @@ class RowRuntime:
             self._ws = None
             _lib.check(self._lib.kk_whisper_text_rows_open(self._h, self._stream(), max_rows, C.c_void_p(self._state.data_ptr()), need),
                        "kk_whisper_text_rows_open")
+            need = int(self._lib.kk_whisper_text_rows_groups_state_bytes(self._h, max_rows))  # what groups keep beside the row state
+            self._gstate = torch.empty(need, dtype=torch.uint8, device=self.device)
+            _lib.check(self._lib.kk_whisper_text_rows_groups_bind(self._h, self._stream(), C.c_void_p(self._gstate.data_ptr()), need), "kk_whisper_text_rows_groups_bind")
         self._logits = None
 
     def _stream(self):
@@ -608,15 +647,30 @@ class RowRuntime:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return C.c_void_p(self._ws.data_ptr()), self._ws.numel()
 
-    def admit(self, row: int, features, tokens, params, suppress_bits: Optional[np.ndarray]):
-        """features: fp32 device (n_audio_ctx, n_audio_state), contiguous; tokens: the initial ids"""
-        from . import _lib
-
+    def _admission(self, features, tokens, params, suppress_bits: Optional[np.ndarray]):
+        """what both admission entries take of a window -- features: fp32 device (n_audio_ctx, n_audio_state), contiguous; tokens: the initial ids --
+        and, behind it, the workspace"""
         toks = np.ascontiguousarray(np.asarray(tokens, np.int32))
         sp = None if suppress_bits is None else suppress_bits.ctypes.data_as(C.c_void_p)
-        ws, wsn = self._workspace(1, 1)
-        _lib.check(self._lib.kk_whisper_text_rows_admit(self._h, self._stream(), row, C.c_void_p(features.data_ptr()), toks.ctypes.data_as(C.c_void_p), len(toks),
-                                                        C.byref(params), sp, ws, wsn), "kk_whisper_text_rows_admit")
+        return (C.c_void_p(features.data_ptr()), toks.ctypes.data_as(C.c_void_p), len(toks), C.byref(params), sp), self._workspace(1, 1)
+
+    def admit_group(self, rows, beam: bool, features, tokens, params, suppress_bits: Optional[np.ndarray], max_candidates: int = 1):
+        """rows: the group's decoder rows, the leader first, on ONE projection of the window's cross K/V; beam: a beam group of len(rows) =
+        beam_size, else a plain one (every row picks for itself; a single row is the plain group of one).  Read with group_read, left with group_release."""
+        from . import _lib
+
+        r = np.ascontiguousarray(np.asarray(rows, np.int32))
+        window, ws = self._admission(features, tokens, params, suppress_bits)
+        _lib.check(self._lib.kk_whisper_text_rows_admit_group(self._h, self._stream(), r.ctypes.data_as(C.c_void_p), len(r),
+                                                              _lib.WHISPER_GROUP_BEAM if beam else _lib.WHISPER_GROUP_PLAIN, *window, int(max_candidates), *ws),
+                   "kk_whisper_text_rows_admit_group")
+
+    def admit(self, row: int, features, tokens, params, suppress_bits: Optional[np.ndarray]):
+        """the one-row form on the raw entry: the row is in no group, is read with `read` and is admitted over without a release"""
+        from . import _lib
+
+        window, ws = self._admission(features, tokens, params, suppress_bits)
+        _lib.check(self._lib.kk_whisper_text_rows_admit(self._h, self._stream(), row, *window, *ws), "kk_whisper_text_rows_admit")
 
     def set_draw(self, row: int, temperature: float, seed: int, stream: int):
         """after admit (which leaves the row greedy): the row's picks draw at `temperature` on the Philox key `seed` and the stream id `stream`"""
@@ -674,32 +728,6 @@ class RowRuntime:
         from . import _lib
 
         _lib.check(self._lib.kk_whisper_text_rows_set_token(self._h, self._stream(), row, index, C.c_void_p(token.data_ptr())), "kk_whisper_text_rows_set_token")
-
-    # ---- groups: G rows on the leader's cross K/V (kk_whisper_text_rows_groups_bind ...) -----------------------------------------------
-    def _bind_groups(self):
-        """the groups buffer, bound at the first group's admission: until then row mode launches and sizes what it always did"""
-        import torch
-
-        from . import _lib
-
-        if getattr(self, "_gstate", None) is None:
-            need = int(self._lib.kk_whisper_text_rows_groups_state_bytes(self._h, self.max_rows))
-            self._gstate = torch.empty(need, dtype=torch.uint8, device=self.device)
-            _lib.check(self._lib.kk_whisper_text_rows_groups_bind(self._h, self._stream(), C.c_void_p(self._gstate.data_ptr()), need), "kk_whisper_text_rows_groups_bind")
-
-    def admit_group(self, rows, beam: bool, features, tokens, params, suppress_bits: Optional[np.ndarray], max_candidates: int = 1):
-        """rows: the group's decoder rows, the leader first; beam: a beam group of len(rows) = beam_size, else a plain one (every row picks for itself)"""
-        from . import _lib
-
-        self._bind_groups()
-        r = np.ascontiguousarray(np.asarray(rows, np.int32))
-        toks = np.ascontiguousarray(np.asarray(tokens, np.int32))
-        sp = None if suppress_bits is None else suppress_bits.ctypes.data_as(C.c_void_p)
-        ws, wsn = self._workspace(1, 1)
-        _lib.check(self._lib.kk_whisper_text_rows_admit_group(self._h, self._stream(), r.ctypes.data_as(C.c_void_p), len(r),
-                                                              _lib.WHISPER_GROUP_BEAM if beam else _lib.WHISPER_GROUP_PLAIN, C.c_void_p(features.data_ptr()),
-                                                              toks.ctypes.data_as(C.c_void_p), len(toks), C.byref(params), sp, int(max_candidates), ws, wsn),
-                   "kk_whisper_text_rows_admit_group")
 
     def group_read(self, leader: int, n_rows: int, kept: bool = True):
         """-> (finished [(tokens, sum)] in the order they finished, live [(tokens, sum)] by slot -- TextRuntime.beam_read for one window -- and the

@@ -17,7 +17,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .whisper_decoding import DecodingOptions, DecodingResult, _features, detect_language, initial_tokens, pick_params, special_tokens
+from .whisper_decoding import DecodingOptions, DecodingResult, _features, cut_at_eot, special_tokens, window_loop, window_prologue
 
 MAX_GROUP = 8  # KK_WHISPER_MAX_GROUP
 
@@ -91,57 +91,20 @@ def sample_candidates(model, mel_or_features, options: DecodingOptions = Decodin
     options = verify_sampling_options(options)
     if eos_check_interval < 1:
         raise ValueError("eos_check_interval must be >= 1")
-    d, rt = model.dims, model._text
-    tok = special_tokens(d)
-    n_ctx = d.n_text_ctx
+    rt = model._text
     n_group = options.best_of or 1
-    sample_len = options.sample_len or n_ctx // 2
-    init = initial_tokens(tok, options, n_ctx, sample_len)
-    sample_begin, sot_index = len(init), init.index(tok.sot)
-    if sample_begin >= n_ctx:
-        raise ValueError(f"{sample_begin} initial tokens leave no room in n_text_ctx = {n_ctx}")
-    feats, single = _features(model, mel_or_features)
-    n_audio = feats.shape[0]
-    B = n_audio * n_group
+    w = window_prologue(model, mel_or_features, options, n_group)
+    n_audio = w.feats.shape[0]
     ids = _row_streams(streams, n_audio, n_group)
-    tokens = np.tile(np.asarray(init, np.int32), (B, 1))
-
-    languages: List[Optional[int]] = [None if not tok.multilingual else init[sot_index + 1]] * n_audio
-    lang_probs: List[Optional[Dict[int, float]]] = [None] * n_audio
-    if options.language is None:  # _detect_language (:557-570)
-        lang_ids, lang_probs = detect_language(model, feats)
-        languages = [max(p, key=p.get) for p in lang_probs]
-        tokens[:, sot_index + 1] = np.repeat(lang_ids.cpu().numpy(), n_group)
-
-    params, bits = pick_params(d, tok, options)
     with torch.cuda.device(model.device):
-        rt.set_audio_groups(feats, n_group)
-        rt.pick_setup(params, bits)
-        rt.sample_setup(options.temperature, seed, ids)
-        pre = rt.forward(torch.from_numpy(tokens).to(model.device), True)  # the prefill, (B, S, V)
-        no_speech = torch.softmax(pre[::n_group, sot_index], dim=-1)[:, tok.no_speech]  # the rows of a window share their prefill
-        rt.pick()
-        for i in range(1, sample_len):
-            if sample_begin + i > n_ctx:  # (:604)
-                break
-            rt.step()
-            rt.pick()
-            if i % eos_check_interval == 0 and rt.not_ended() == 0:
-                break
+        no_speech = window_loop(model, w, options, n_group, eos_check_interval, lambda: rt.sample_setup(options.temperature, seed, ids),
+                                lambda: rt.not_ended() == 0)
         toks, rows = rt.read()
         no_speech = no_speech.cpu().numpy()
-    cands = []
-    for a in range(n_audio):
-        group = []
-        for g in range(n_group):
-            b = a * n_group + g
-            seq = [int(t) for t in toks[b, : rows[b].count]]
-            if tok.eot in seq:
-                seq = seq[: seq.index(tok.eot)]
-            group.append((seq, float(rows[b].sum_logprob)))
-        cands.append(group)
-    return SampledWindows(candidates=cands, languages=languages, language_probs=lang_probs, no_speech_probs=[float(p) for p in no_speech], audio_features=feats,
-                          single=single, temperature=float(options.temperature))
+    eot = special_tokens(model.dims).eot
+    cands = [[(cut_at_eot(toks[b, : rows[b].count], eot), float(rows[b].sum_logprob)) for b in range(a * n_group, (a + 1) * n_group)] for a in range(n_audio)]
+    return SampledWindows(candidates=cands, languages=w.languages, language_probs=w.lang_probs, no_speech_probs=[float(p) for p in no_speech],
+                          audio_features=w.feats, single=w.single, temperature=float(options.temperature))
 
 
 def rank(candidates: Sequence[Tuple[Sequence[int], float]], length_penalty: Optional[float]) -> int:

@@ -1,36 +1,38 @@
-"""Whisper serving: 30-second windows join and leave ONE running decoder batch (DESIGN 8i).  `Model.decode` is a static batch -- one set of options,
+"""Whisper serving: 30-second windows join and leave ONE running decoder batch (DESIGN 8i, 8o).  `Model.decode` is a static batch -- one set of options,
 one shared position, every row stepped until the last has ended; a voice service's listeners close utterances at different moments, each with its own
 language, prompt, prefix and length limit.  `WhisperBatcher` keeps `max_rows` decoder rows of the text handle's row mode (kk_whisper_text_rows_*,
-whisper_decoding.RowRuntime) busy: a request is admitted into a free row, prefilled in the round that steps the other rows, picked with its own
-parameters, and retired when it has ended or reached its own limit.
+whisper_decoding.RowRuntime) busy.
+
+One lifecycle.  Every request is a GROUP of G >= 1 rows on ONE projection of its window's cross K/V: a beam group (`submit_beam`, G = beam_size), or a plain
+one whose rows each pick for themselves -- `submit_group`'s `best_of` rows, and the one row of `submit` (greedy) and `submit_sampled` (its row carries a
+draw: 1 / T, Philox key, stream id).  A group is admitted when G rows are free (strictly FIFO: the head of the queue waits and nothing overtakes
+it), prefilled in the round that steps the other rows, picked with its own parameters in the round's ONE pick launch, and retired whole -- read back,
+released, all its rows free in that round -- when it has ended or reached its own limit.  The groups buffer of row mode is bound when the engine opens.
 
 The contract: every request's `DecodingResult` equals, field by field (`tokens`, `avg_logprob`, `no_speech_prob`, `language`, `language_probs`,
-`temperature`), what `model.decode(the same 2-D input, the same options)` returns alone -- whatever else the batch runs, in whatever order requests
-arrive, whichever row they land in.  The kernels give a row the bits of its solo run (a row's bits depend on that row's inputs alone); the two
-probabilities are the torch expressions of `decode` / `detect_language` on the same (1, V) / (1, n_languages) shapes of bit-identical logits.
+`temperature`), what the solo window-mode call returns for the same 2-D input and options alone -- `model.decode` (`submit`), `model.sample(...,
+streams=[stream])` (`submit_sampled`, `submit_group`), `model.beam_search` (`submit_beam`) -- whatever else the batch runs, in whatever order requests
+arrive, whichever rows they land in.  The kernels give a row the bits of its solo run (a row's bits depend on that row's inputs alone); the two
+probabilities are the torch expressions of `decode` / `detect_language` on the same (1, V) / (1, n_languages) shapes of bit-identical logits.  The result
+is formed from the one read-back record in the solo call's own way: `submit` and `submit_sampled` as `decode` forms it from the row (`language_probs`
+stays None but for `lang_id`), `submit_beam` and `submit_group` through whisper_beam.finalize, whisper_sampling.rank and results.
 
 One round (`step`):
-  1. rows that cannot go on are retired: a row at its own limit (its `sample_len` and decode's `sample_begin + i > n_ctx` rule -- a row is never picked
-     more often than its solo run), a `lang_id` row after its detection round and, every `eos_check_interval` rounds, the rows whose ended flag the
-     poll finds set.  Retiring reads the row back and synchronises; between polls the host reads nothing from the device.
-  2. queued requests are admitted FIFO into free rows, `max_round_tokens` of prefill per round at the most.
-  3. ONE rows_forward over every live row: a fresh row carries its initial tokens, a row in detection `[sot]` at position 0, the others one token.
+  1. requests that cannot go on are retired: one at its own limit (its `sample_len` and decode's `sample_begin + i > n_ctx` rule -- a row is never picked
+     more often than its solo run), a `lang_id` request after its detection round and, every `eos_check_interval` rounds, those the poll finds over: every
+     row's ended flag set (a beam group's rows all carry its complete flag).  Retiring reads the group back and synchronises; between polls the host
+     reads nothing from the device.
+  2. queued requests are admitted FIFO into free rows, `max_round_tokens` of prefill per round at the most (every row of a group prefills).
+  3. ONE rows_forward over every live row: a fresh row carries its initial tokens, a leader in detection `[sot]` at position 0, the others one token.
   4. ONE rows_pick over the rows that were prefilled or stepped.
 A row that has ended keeps stepping and emits eot until the next poll notices, as in `decode`.  A request with `language=None` (or `task="lang_id"`)
-spends one extra round first; the arg-maximum over the language tokens goes into its initial tokens on the device, with no synchronisation.
+spends one extra round first, on its leader alone; the arg-maximum over the language tokens goes into the initial tokens of every row of the group on the
+device, with no synchronisation.  `submit` keeps refusing a temperature and `submit_sampled` a `best_of` above 1, as their tests pin.
+`Model.transcribe` and `Model.beam_transcribe` (whisper_transcribe.py) are the long-form loops on top of this batcher.
 
-A request submitted with `submit_sampled` decodes at its own temperature: its row carries a draw (1 / T, Philox key, stream id) and the round's ONE
-pick launch samples it while it picks the greedy rows; its result is `model.sample`'s for that window alone.  `submit` itself keeps
-refusing a temperature.  `Model.transcribe` (whisper_transcribe.py) is the long-form loop on top of this batcher.
-
-Groups: `submit_beam` runs a window's beam search, and `submit_group` its `best_of` samples, on G rows of the same batch -- admitted together
-when G rows are free (strictly FIFO: the head of the queue waits and nothing overtakes it), on ONE projection of the window's cross K/V, stepped and
-picked in the rounds and the launches of the single rows beside them, and retired together at the poll that finds a beam group complete or every row
-of a plain group ended, or at the group's own limit.  The results are `model.beam_search`'s and `model.sample`'s for that window alone;
-`Model.beam_transcribe` is the long-form loop that uses them.
-
-The scheduler talks to the model through an engine (`ModelEngine`); a fake engine tests it without a GPU.  Out of scope: `generate` (see
-`Model.transcribe`), text-to-id encoding, hipGraph capture of the round, prefill on a side stream, prefilling a group's leader alone."""
+The scheduler talks to the model through an engine (`ModelEngine`: one entry per job, each taking the group's rows); a fake engine tests it without a
+GPU.  Out of scope: `generate` (see `Model.transcribe`), text-to-id encoding, hipGraph capture of the round, prefill on a side stream, prefilling a group's
+leader alone."""
 from __future__ import annotations
 
 import threading
@@ -39,28 +41,22 @@ from concurrent.futures import Future
 from dataclasses import dataclass, replace
 from typing import Deque, Dict, List, Optional, Sequence, Tuple
 
-from .whisper_decoding import (NOT_BUILT, DecodingOptions, DecodingResult, initial_tokens, special_tokens, verify_options)
+from .whisper_decoding import (NOT_BUILT, DecodingOptions, DecodingResult, cut_at_eot, initial_tokens, special_tokens, verify_options)
 
 NO_LANGUAGE_TOKENS = "This model doesn't have language tokens so it can't perform lang id"
 
 
 @dataclass
-class RowRead:
-    """what retiring a row reads back"""
-    tokens: Sequence[int]                 # the sampled tokens, `count` of them
-    count: int
-    sum_logprob: float
-    no_speech_prob: float = float("nan")
-    language_probs: Optional[Dict[int, float]] = None
-
-
-@dataclass
 class GroupRead:
-    """what retiring a group reads back: TextRuntime.beam_read's lists for one window (a plain group: nothing finished, its rows as the live ones)"""
+    """what retiring a request reads back: TextRuntime.beam_read's lists for one window.  A plain group has nothing finished and its rows as the live
+    ones, each with every token it sampled (eot and what it emitted behind it included) and its sum"""
     finished: List[Tuple[List[int], float]]
     live: List[Tuple[List[int], float]]
     no_speech_prob: float = float("nan")
     language_probs: Optional[Dict[int, float]] = None
+
+
+RowRead = GroupRead  # a single row's read-back is its group's: the row is live[0]
 
 
 @dataclass
@@ -99,9 +95,11 @@ class ModelEngine:
 
         self._rows = RowRuntime(self.model._text, max_rows)
 
-    def admit(self, row: int, x, init: Tuple[int, ...], options: DecodingOptions, draw: Optional[Tuple[float, int, int]] = None):
-        """-> the window's audio features (n_audio_ctx, n_audio_state); a mel goes through the encoder as the solo call's would.  draw: None (the row
-        picks greedily) or (temperature, seed, stream id) of a sampled row"""
+    def admit(self, rows: Sequence[int], x, init: Tuple[int, ...], options: DecodingOptions, beam: bool = False, max_candidates: int = 1,
+              draws: Optional[Sequence[Tuple[float, int, int]]] = None):
+        """The window into the group `rows` on rows[0]'s cross K/V -> its audio features (n_audio_ctx, n_audio_state); a mel goes through the encoder
+        as the solo call's would.  beam: a beam group (len(rows) = beam_size); else a plain one, whose row g picks greedily (draws None) or draws on
+        draws[g] = (temperature, seed, stream id)"""
         import torch
 
         from .whisper_decoding import _features, pick_params
@@ -109,8 +107,8 @@ class ModelEngine:
         feats, _ = _features(self.model, x)
         params, bits = pick_params(self.dims, self.tok, options)
         with torch.cuda.device(self.model.device):
-            self._rows.admit(row, feats[0], init, params, bits)
-            if draw is not None:
+            self._rows.admit_group(rows, beam, feats[0], init, params, bits, max_candidates)
+            for row, draw in zip(rows, draws or ()):
                 self._rows.set_draw(row, *draw)
         return feats[0]
 
@@ -120,16 +118,18 @@ class ModelEngine:
         with torch.cuda.device(self.model.device):
             self._rows.forward(items, out_rows)
 
-    def detect(self, row: int, out_index: int, token_index: Optional[int]) -> None:
-        """detect_language's arg-maximum on row `out_index` of the round's logits, written into the row's initial tokens on the device"""
+    def detect(self, rows: Sequence[int], out_index: int, token_index: Optional[int]) -> None:
+        """detect_language's arg-maximum on row `out_index` of the round's logits (the leader's), written into the initial tokens of EVERY row of the
+        group on the device"""
         import torch
 
         if token_index is None:
             return
         lo, hi = self.tok.language_tokens[0], self.tok.language_tokens[-1] + 1
         with torch.cuda.device(self.model.device):
-            ids = self._rows._logits[out_index:out_index + 1][:, lo:hi].argmax(dim=-1) + lo
-            self._rows.set_token(row, token_index, ids.to(torch.int32))
+            ids = (self._rows._logits[out_index:out_index + 1][:, lo:hi].argmax(dim=-1) + lo).to(torch.int32)
+            for row in rows:
+                self._rows.set_token(row, token_index, ids)
 
     def pick(self, rows: Sequence[int]) -> None:
         import torch
@@ -161,45 +161,8 @@ class ModelEngine:
             at_sot.copy_(kept[1:2])
             out.no_speech_prob = float(torch.softmax(at_sot, dim=-1)[:, tok.no_speech].cpu().numpy()[0])
 
-    def read(self, row: int, detected: bool, sot_index: Optional[int]) -> RowRead:
-        import torch
-
-        with torch.cuda.device(self.model.device):
-            toks, st, kept = self._rows.read(row, kept=True)
-            out = RowRead(tokens=[int(t) for t in toks[: st.count]], count=int(st.count), sum_logprob=float(st.sum_logprob))
-            self._probabilities(out, kept, detected, sot_index)
-        return out
-
-    # ---- groups ------------------------------------------------------------------------------------------------------------------
-    def admit_group(self, rows: Sequence[int], x, init: Tuple[int, ...], options: DecodingOptions, beam: bool, max_candidates: int = 1,
-                    draws: Optional[Sequence[Tuple[float, int, int]]] = None):
-        """`admit` for a group on rows[0]'s cross K/V.  beam: a beam group (len(rows) = beam_size); else a plain one whose row g draws on draws[g]"""
-        import torch
-
-        from .whisper_decoding import _features, pick_params
-
-        feats, _ = _features(self.model, x)
-        params, bits = pick_params(self.dims, self.tok, options)
-        with torch.cuda.device(self.model.device):
-            self._rows.admit_group(rows, beam, feats[0], init, params, bits, max_candidates)
-            for row, draw in zip(rows, draws or ()):
-                self._rows.set_draw(row, *draw)
-        return feats[0]
-
-    def detect_group(self, rows: Sequence[int], out_index: int, token_index: Optional[int]) -> None:
-        """`detect` on the leader's logits; the id goes into the initial tokens of EVERY row of the group, on the device"""
-        import torch
-
-        if token_index is None:
-            return
-        lo, hi = self.tok.language_tokens[0], self.tok.language_tokens[-1] + 1
-        with torch.cuda.device(self.model.device):
-            ids = (self._rows._logits[out_index:out_index + 1][:, lo:hi].argmax(dim=-1) + lo).to(torch.int32)
-            for row in rows:
-                self._rows.set_token(row, token_index, ids)
-
-    def read_group(self, rows: Sequence[int], detected: bool, sot_index: Optional[int]) -> GroupRead:
-        """reads the group back (the probabilities on the leader's kept rows, as `read` takes them) and releases its rows"""
+    def read(self, rows: Sequence[int], detected: bool, sot_index: Optional[int]) -> GroupRead:
+        """reads the group back (the probabilities on the leader's kept rows) and releases its rows"""
         import torch
 
         with torch.cuda.device(self.model.device):
@@ -213,15 +176,25 @@ class ModelEngine:
         self._rows = None
 
 
+def _checked(verify, options: DecodingOptions, overrides: dict) -> DecodingOptions:
+    return verify(replace(options, **overrides) if overrides else options)
+
+
+def _ints(*values) -> bool:
+    return all(isinstance(v, int) and not isinstance(v, bool) for v in values)
+
+
 class _Request:
-    def __init__(self, x, options: DecodingOptions, init: Tuple[int, ...], sot_index: int, limit: int, future: Future, draw=None):
+    """a group of G rows: "beam" (submit_beam), or "plain" -- every row picks for itself: submit_group's best_of rows, submit's and submit_sampled's one"""
+
+    def __init__(self, x, options: DecodingOptions, init: Tuple[int, ...], sot_index: int, limit: int, future: Future, kind: str, G: int, max_candidates: int,
+                 draws, ranked: bool):
         self.x, self.options, self.init, self.sot_index, self.limit, self.future = x, options, init, sot_index, limit, future
-        self.draw = draw  # None: greedy; (temperature, seed, stream id): submit_sampled
-        self.kind: Optional[str] = None  # "beam" (submit_beam) or "plain" (submit_group): a group of G rows; None: one row
-        self.G, self.max_candidates, self.draws = 1, 1, None
-        self.rows: List[int] = []
+        self.kind, self.G, self.max_candidates = kind, G, max_candidates
+        self.draws = draws    # None: the rows pick greedily; else row g draws on draws[g] = (temperature, seed, stream id)
+        self.ranked = ranked  # submit_beam, submit_group: the result is the ranker's choice among the group's candidates
+        self.rows: List[int] = []  # once admitted; rows[0] leads
         self.detect = options.language is None or options.task == "lang_id"
-        self.row: Optional[int] = None
         self.phase = "detect" if self.detect else "prefill"  # -> "prefill" -> "step" -> "retire"
         self.picks = 0
         self.features = None
@@ -249,9 +222,7 @@ class WhisperBatcher:
     # ---- submitting (any thread) ---------------------------------------------------------------------------------------------------------
     def submit(self, mel_or_features, options: DecodingOptions = DecodingOptions(), **overrides) -> Future:
         """One window (2-D) -> Future[DecodingResult].  The option checks of `decode` run here, in the caller's thread, with decode's exceptions."""
-        if overrides:
-            options = replace(options, **overrides)
-        return self._submit(mel_or_features, verify_options(options), None)
+        return self._submit(mel_or_features, _checked(verify_options, options, overrides))
 
     def submit_sampled(self, mel_or_features, options: DecodingOptions = DecodingOptions(temperature=1.0), seed: int = 0, stream: int = 0, **overrides) -> Future:
         """One window (2-D) decoded at temperature > 0 -> Future[DecodingResult]: what `model.sample(window, options, seed=seed, streams=[stream])` returns
@@ -260,14 +231,12 @@ class WhisperBatcher:
         DESIGN 8n).  The option checks are whisper_sampling.verify_sampling_options'; `best_of` must be None or 1: groups are not built here."""
         from .whisper_sampling import verify_sampling_options
 
-        if overrides:
-            options = replace(options, **overrides)
-        options = verify_sampling_options(options)
+        options = _checked(verify_sampling_options, options, overrides)
         if options.best_of not in (None, 1):
             raise NotImplementedError("best_of groups are not built in the batcher: submit_sampled takes best_of None or 1 (Model.sample runs groups)")
-        if isinstance(seed, bool) or not isinstance(seed, int) or isinstance(stream, bool) or not isinstance(stream, int) or not 0 <= stream <= 0xFFFFFFFF:
+        if not _ints(seed, stream) or not 0 <= stream <= 0xFFFFFFFF:
             raise ValueError("seed must be an int and stream an int in 0 .. 2**32 - 1")
-        return self._submit(mel_or_features, options, (float(options.temperature), seed, stream))
+        return self._submit(mel_or_features, options, draws=[(float(options.temperature), seed, stream)])
 
     def submit_beam(self, mel_or_features, options: DecodingOptions = DecodingOptions(beam_size=5), **overrides) -> Future:
         """One window (2-D) searched with a beam -> Future[DecodingResult]: what `model.beam_search(window, options)` returns for it alone, field by
@@ -277,15 +246,13 @@ class WhisperBatcher:
         is no one result to equal."""
         from .whisper_beam import max_candidates, verify_beam_options
 
-        if overrides:
-            options = replace(options, **overrides)
-        options = verify_beam_options(options)
+        options = _checked(verify_beam_options, options, overrides)
         mc = max_candidates(options.beam_size, options.patience)
         if mc < options.beam_size:
             raise ValueError(f"round(beam_size * patience) = {mc} finished sequences are fewer than beam_size = {options.beam_size}: the live prefixes that "
                              "top the candidates up change with every step after completion, so the result depends on when the poll runs "
                              "(Model.beam_search takes such a patience)")
-        return self._submit(mel_or_features, options, None, kind="beam", G=options.beam_size, max_candidates=mc)
+        return self._submit(mel_or_features, options, kind="beam", G=options.beam_size, max_candidates=mc, ranked=True)
 
     def submit_group(self, mel_or_features, options: DecodingOptions = DecodingOptions(temperature=1.0, best_of=5), seed: int = 0, stream: int = 0,
                      **overrides) -> Future:
@@ -294,20 +261,18 @@ class WhisperBatcher:
         bits.  The option checks are whisper_sampling.verify_sampling_options'."""
         from .whisper_sampling import verify_sampling_options
 
-        if overrides:
-            options = replace(options, **overrides)
-        options = verify_sampling_options(options)
+        options = _checked(verify_sampling_options, options, overrides)
         if options.best_of is None or options.best_of < 2:
             raise ValueError("submit_group takes best_of >= 2 (one sample per window is submit_sampled)")
-        if isinstance(seed, bool) or not isinstance(seed, int) or isinstance(stream, bool) or not isinstance(stream, int) or stream < 0:
+        if not _ints(seed, stream) or stream < 0:
             raise ValueError("seed must be an int and stream an int >= 0")
         G = options.best_of
         if stream * G + G - 1 > 0xFFFFFFFF:
             raise ValueError("a stream id times best_of must fit 32 bits")
         draws = [(float(options.temperature), seed, stream * G + g) for g in range(G)]
-        return self._submit(mel_or_features, options, None, kind="plain", G=G, draws=draws)
+        return self._submit(mel_or_features, options, G=G, draws=draws, ranked=True)
 
-    def _submit(self, mel_or_features, options: DecodingOptions, draw, kind=None, G: int = 1, max_candidates: int = 1, draws=None) -> Future:
+    def _submit(self, mel_or_features, options: DecodingOptions, kind: str = "plain", G: int = 1, max_candidates: int = 1, draws=None, ranked: bool = False) -> Future:
         if G > self.max_rows:
             raise ValueError(f"a group of {G} rows does not fit max_rows = {self.max_rows}")
         d = self.engine.dims
@@ -323,8 +288,7 @@ class WhisperBatcher:
             raise ValueError(NO_LANGUAGE_TOKENS)
         # decode picks once after the prefill and once per step i = 1 .. sample_len - 1 while sample_begin + i <= n_ctx
         limit = min(sample_len, n_ctx - sample_begin + 1)
-        req = _Request(mel_or_features, options, init, sot_index, limit, Future(), draw)
-        req.kind, req.G, req.max_candidates, req.draws = kind, G, max_candidates, draws
+        req = _Request(mel_or_features, options, init, sot_index, limit, Future(), kind, G, max_candidates, draws, ranked)
         with self._lock:
             if self.closed:
                 raise RuntimeError("WhisperBatcher is closed")
@@ -345,8 +309,9 @@ class WhisperBatcher:
         for row in r.rows:
             self._rows[row] = None
 
-    def _group_result(self, r: _Request, rd: GroupRead) -> DecodingResult:
-        """whisper_beam.finalize / whisper_sampling.rank and results on what the group read back: the solo calls' own host steps"""
+    def _result(self, r: _Request, rd: GroupRead) -> DecodingResult:
+        """The solo call's own host steps on what was read back.  A ranked request (submit_beam, submit_group): whisper_beam.finalize /
+        whisper_sampling.rank and results.  submit's and submit_sampled's: decode's result of the one row, or lang_id's three fields."""
         from .whisper_beam import finalize
         from .whisper_sampling import SampledWindows, results
 
@@ -354,51 +319,33 @@ class WhisperBatcher:
         language = None if not tok.multilingual else r.init[r.sot_index + 1]
         if r.detect:
             language = max(rd.language_probs, key=rd.language_probs.get)
+        if r.options.task == "lang_id":
+            return DecodingResult(audio_features=r.features, language=language, language_probs=rd.language_probs)
         if r.kind == "beam":
             cands = finalize(rd.finished, rd.live, r.G)
         else:
-            cands = [(seq[: seq.index(tok.eot)] if tok.eot in seq else list(seq), total) for seq, total in rd.live]
+            cands = [(cut_at_eot(seq, tok.eot), total) for seq, total in rd.live]
+        if not r.ranked:
+            seq, total = cands[0]
+            return DecodingResult(audio_features=r.features, language=language, tokens=seq, avg_logprob=total / (len(seq) + 1),
+                                  no_speech_prob=rd.no_speech_prob, temperature=r.options.temperature)
         win = SampledWindows(candidates=[cands], languages=[language], language_probs=[rd.language_probs], no_speech_probs=[rd.no_speech_prob],
                              audio_features=[r.features], single=True, temperature=float(r.options.temperature))
         return results(win, r.options.length_penalty)
 
-    def _result(self, r: _Request, rd: RowRead) -> DecodingResult:
-        tok = special_tokens(self.engine.dims)
-        language = None if not tok.multilingual else r.init[r.sot_index + 1]
-        if r.detect:
-            language = max(rd.language_probs, key=rd.language_probs.get)
-        if r.options.task == "lang_id":
-            return DecodingResult(audio_features=r.features, language=language, language_probs=rd.language_probs)
-        seq = list(rd.tokens)
-        if tok.eot in seq:
-            seq = seq[: seq.index(tok.eot)]
-        return DecodingResult(audio_features=r.features, language=language, tokens=seq, avg_logprob=rd.sum_logprob / (len(seq) + 1),
-                              no_speech_prob=rd.no_speech_prob, temperature=r.options.temperature)
-
-    def _retire_group(self, r: _Request) -> None:
-        try:
-            res = self._group_result(r, self.engine.read_group(r.rows, r.detect, r.sot_index))
-        except BaseException as e:  # noqa: BLE001  (the caller sits in Future.result())
-            r.future.set_exception(e)
-        else:
-            r.future.set_result(res)
-        self.stats.retired += 1
-        self.stats.groups_retired += 1
-        self._free(r)  # all its rows, in this round
-
     def _retire(self, r: _Request) -> None:
-        if r.kind is not None:
-            return self._retire_group(r)
         try:
-            rd = self.engine.read(r.row, r.detect, r.sot_index if r.options.task != "lang_id" else None)
+            rd = self.engine.read(r.rows, r.detect, r.sot_index if r.options.task != "lang_id" else None)
             res = self._result(r, rd)
         except BaseException as e:  # noqa: BLE001  (the caller sits in Future.result())
             r.future.set_exception(e)
         else:
-            self.stats.ended_row_rounds += max(0, rd.count - len(res.tokens) - 1)  # picks behind the row's eot
+            if not r.ranked:
+                self.stats.ended_row_rounds += max(0, len(rd.live[0][0]) - len(res.tokens) - 1)  # picks behind the row's eot
             r.future.set_result(res)
         self.stats.retired += 1
-        self._free(r)
+        self.stats.groups_retired += r.ranked
+        self._free(r)  # all its rows, in this round
 
     def _admit(self, busy_tokens: int) -> None:
         """FIFO into free rows.  A request costs its prefill in the round that runs it: this round, or the next after a detection round (which
@@ -425,20 +372,15 @@ class WhisperBatcher:
                 continue  # cancelled while it was queued
             rows = free[: r.G]
             try:
-                if r.kind is not None:
-                    r.features = self.engine.admit_group(rows, r.x, r.init, r.options, r.kind == "beam", r.max_candidates, r.draws)
-                elif r.draw is None:
-                    r.features = self.engine.admit(free[0], r.x, r.init, r.options)
-                else:
-                    r.features = self.engine.admit(free[0], r.x, r.init, r.options, draw=r.draw)
+                r.features = self.engine.admit(rows, r.x, r.init, r.options, r.kind == "beam", r.max_candidates, r.draws)
             except BaseException as e:  # noqa: BLE001
                 r.future.set_exception(e)
                 continue
-            r.row, r.rows, r.x = rows[0], list(rows), None
+            r.rows, r.x = list(rows), None
             for row in rows:
                 self._rows[row] = r
             self.stats.admissions += 1
-            if r.kind is not None:
+            if r.ranked:
                 self.stats.groups += 1
                 self.stats.group_rows += r.G
             now, nxt = now + cost_now, nxt + cost_next
@@ -468,13 +410,13 @@ class WhisperBatcher:
             for r in live:
                 n = len(r.init)
                 if r.phase == "detect":  # [sot] at position 0, its logits kept in slot 0
-                    items.append((r.row, 0, 1, r.sot_index, 0, 0))
+                    items.append((r.rows[0], 0, 1, r.sot_index, 0, 0))
                     detects.append((r, len(out_rows)))
                     out_rows.append(at)
                     at += 1
                 elif r.phase == "prefill":  # the initial tokens; the logits of the sot position kept in slot 1 (a group: of its leader)
                     for row in r.rows:
-                        lead = row == r.row
+                        lead = row == r.rows[0]
                         items.append((row, 0, n, 0, r.sot_index if lead else -1, 1 if lead else 0))
                         out_rows += ([at + r.sot_index] if lead else []) + ([at + n - 1] if r.sot_index != n - 1 or not lead else [])
                         at += n
@@ -488,10 +430,7 @@ class WhisperBatcher:
             self.engine.forward(items, out_rows)
             for r, j in detects:
                 token_index = r.sot_index + 1 if r.options.language is None else None
-                if r.kind is not None:
-                    self.engine.detect_group(r.rows, j, token_index)
-                else:
-                    self.engine.detect(r.row, j, token_index)
+                self.engine.detect(r.rows, j, token_index)
                 r.phase = "retire" if r.options.task == "lang_id" else "prefill"
                 self.stats.detections += 1
             if picks:
@@ -552,7 +491,7 @@ class WhisperBatcher:
             for r in pending + self._live():
                 if r.future.cancelled() or r.future.done():
                     continue
-                if r.row is None and not r.future.set_running_or_notify_cancel():
+                if not r.rows and not r.future.set_running_or_notify_cancel():
                     continue
                 r.future.set_exception(RuntimeError("WhisperBatcher is closed"))
             self._rows = [None] * self.max_rows

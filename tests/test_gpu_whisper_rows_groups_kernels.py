@@ -306,6 +306,40 @@ def test_a_beam_rows_step_reads_its_prefix_through_the_owner_table(n):
     assert [t for t, _ in live] == win.prefix
 
 
+@pytest.mark.parametrize("draw", [None, (0.7, 1234, 77)])
+def test_a_plain_group_of_one_is_a_single_row(draw):
+    """With the groups buffer bound, row 0 admitted by rows_admit and row 1 as the plain group (1,) carry the same window, initial tokens and pick
+    parameters (and, in the second case, the same draw): a prefill that keeps the sot position in slot 1, a pick, two steps with their picks.  The two
+    rows' logits are bit-equal in every round and are the request's window-mode bits; rows_read(0) and rows_group_read(1) give the same tokens, count,
+    sum and kept rows."""
+    d, rt = _runtime("a")
+    lib = rt._lib
+    tok = whisper.special_tokens(d)
+    _, params = _params(d, without_timestamps=True)
+    feats = T.features(d, 1, 5)[0]
+    init = [tok.sot, 11, 12]
+    rows = Groups(rt, 2)
+    rows.admit(0, feats, init, params)
+    rows.admit_group((1,), PLAIN, feats, init, params)
+    if draw is not None:
+        for r in (0, 1):
+            assert lib.kk_whisper_text_rows_set_draw(rows.h, _st(), r, C.c_float(draw[0]), draw[1], draw[2]) == 0, lib.kk_last_error()
+    got = [rows.forward([(0, 0, 3, 0, 0, 1), (1, 0, 3, 0, 0, 1)], [0, 2, 3, 5])]
+    assert rows.pick_rc([0, 1]) == 0, lib.kk_last_error()
+    for s in range(2):
+        got.append(rows.forward([(0, 3 + s, 1, -1), (1, 3 + s, 1, -1)], [0, 1]))
+        assert rows.pick_rc([0, 1]) == 0, lib.kk_last_error()
+    toks, st, kept = rows.read(0)
+    fin, live, gkept = rows.group_read(1, 1)
+    assert fin == [] and st.count == 3 and live[0] == ([int(t) for t in toks[:3]], float(st.sum_logprob))
+    assert np.array_equal(kept.view(np.uint32), gkept.view(np.uint32))
+    solo = _solo(rt, feats, init + [int(t) for t in toks[:2]])
+    same = lambda a, b: np.array_equal(a.view(np.uint32), b.view(np.uint32))  # noqa: E731
+    assert same(got[0][0], solo[0]) and same(got[0][2], solo[0]) and same(kept[1], solo[0])  # the sot position
+    for k, (a, b) in enumerate([(got[0][1], got[0][3]), (got[1][0], got[1][1]), (got[2][0], got[2][1])]):  # the prefill's last position, then the steps
+        assert np.isfinite(a).all() and same(a, solo[2 + k]) and same(b, solo[2 + k]), (draw, k)
+
+
 def test_group_refusals_are_error_returns_and_a_valid_round_follows():
     import torch
 
@@ -363,4 +397,33 @@ def test_group_refusals_are_error_returns_and_a_valid_round_follows():
     toks, _, _ = rows.read(0)
     assert np.array_equal(got[4], _solo(rt, feats, init + [int(toks[0])], all_positions=False))  # the single row beside the groups keeps its solo bits
     assert rows.release(4) == 0 and rows.release(4) != 0
-    rows.admit(1, feats, init, params)  # a released row is a free row
+    # Rows change kind across a release.  The beam group has selected: its owner rows are rewritten and its flip is 1.  Its former leader comes back as
+    # a single row and its former follower as a plain group of one; both prefill and step with the bits of the request alone
+    rows.admit(4, feats, init, params)
+    rows.admit_group((1,), PLAIN, feats, init, params)
+    solo = _solo(rt, feats, init)
+    got = rows.forward([(4, 0, 3, 0), (1, 0, 3, 0)], [2, 5])
+    assert np.array_equal(got[0].view(np.uint32), solo[2].view(np.uint32)) and np.array_equal(got[1].view(np.uint32), solo[2].view(np.uint32))
+    assert rows.pick_rc([4, 1]) == 0, lib.kk_last_error()
+    got = rows.forward([(4, 3, 1, -1), (1, 3, 1, -1)], [0, 1])
+    toks, _, _ = rows.read(4)
+    _, live, _ = rows.group_read(1, 1)
+    assert live[0][0] == [int(toks[0])]
+    want = _solo(rt, feats, init + [int(toks[0])], all_positions=False)
+    assert np.array_equal(got[0].view(np.uint32), want.view(np.uint32)) and np.array_equal(got[1].view(np.uint32), want.view(np.uint32))
+
+    # A row that was last a single row goes into a new beam group with no release between: the group's first round -- prefill, offers, select, the step
+    # through the owner table -- is that of the same group on a freshly opened state
+    def first_round(rows):
+        rows.admit_group((4, 3), BEAM, feats, init, params, maxc=2)
+        out = [rows.forward([(4, 0, 3, 0), (3, 0, 3, 0)], [2, 5])]
+        assert rows.pick_rc([4, 3]) == 0, lib.kk_last_error()
+        out += [a for r in (4, 3) for a in rows.offers(r, 3)]
+        out.append(rows.forward([(4, 3, 1, -1), (3, 3, 1, -1)], [0, 1]))
+        return out, rows.group_read(4, 2)[:2]
+
+    used, used_lists = first_round(rows)
+    fresh, fresh_lists = first_round(Groups(rt, 6))
+    assert used_lists == fresh_lists and len(used_lists[1][0][0]) == 1
+    for a, b in zip(used, fresh):
+        assert a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))

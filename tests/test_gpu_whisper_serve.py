@@ -73,9 +73,10 @@ def test_every_request_equals_its_solo_decode_in_any_order(name, opts, max_token
         with m.serve(max_rows=2, eos_check_interval=4) as s:
             admitted, admit = [], s.engine.admit
 
-            def spy(row, x, init, options, admit=admit, admitted=admitted):
-                admitted.append((row, next(i for i in order if x is feats_in[i])))
-                return admit(row, x, init, options)
+            def spy(rows, x, *more, admit=admit, admitted=admitted):
+                assert len(rows) == 1
+                admitted.append((rows[0], next(i for i in order if x is feats_in[i])))
+                return admit(rows, x, *more)
 
             s.engine.admit = spy
             feats_in = {i: feats[i] for i in order}

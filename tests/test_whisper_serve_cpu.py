@@ -17,7 +17,7 @@ import _whisper_text_ref as T  # noqa: E402
 
 from mlx_audio_amd import whisper  # noqa: E402
 from mlx_audio_amd import whisper_decoding as WD  # noqa: E402
-from mlx_audio_amd.whisper_serve import RowRead, WhisperBatcher  # noqa: E402
+from mlx_audio_amd.whisper_serve import GroupRead, WhisperBatcher  # noqa: E402
 
 DIMS = T.dims(128, 2, 2, 51865, 100)
 TOK = whisper.special_tokens(DIMS)
@@ -31,10 +31,13 @@ def window(end_at=0, tag=0):
 
 
 class FakeEngine:
-    """rows that sample 1000 + k at pick k and eot from pick `end_at` on; every call is logged"""
+    """Every request is a group of rows; a row samples 1000 + k at pick k and eot from pick `end_at` on.  A beam group is complete -- every row flagged --
+    from the pick `end_at` on, and its finished store then holds ONE sequence per beam: [1000 + 1 .. 1000 + end_at - 1] + [slot].  Every call is logged;
+    a plain group of one row is logged as that row ("admit", "detect", "read"), any other by its rows ("admit_group", "detect_group", "read_group")."""
 
     def __init__(self):
         self.dims, self.log, self.rows, self.counts = DIMS, [], {}, {}  # counts: request tag -> the picks it got
+        self.groups = {}  # leader -> dict(rows, beam, max_candidates, draws)
 
     def check_window(self, x):
         if len(x.shape) != 2:
@@ -43,10 +46,16 @@ class FakeEngine:
     def open(self, max_rows):
         self.max_rows = max_rows
 
-    def admit(self, row, x, init, options):
-        assert row not in self.rows, "a row is handed on only after it was read"
-        self.rows[row] = dict(end_at=int(x[0, 0]), tag=int(x[0, 1]), tokens=[], init=init)
-        self.log.append(("admit", row, int(x[0, 1])))
+    def _entry(self, what, rows, *more):
+        single = len(rows) == 1 and not self.groups[rows[0]]["beam"]
+        self.log.append((what, rows[0]) + more[:1] if single else (what + "_group", tuple(rows)) + more)
+
+    def admit(self, rows, x, init, options, beam=False, max_candidates=1, draws=None):
+        for r in rows:
+            assert r not in self.rows, "a row is handed on only after its group was read"
+            self.rows[r] = dict(end_at=int(x[0, 0]), tag=int(x[0, 1]), tokens=[], init=init)
+        self.groups[rows[0]] = dict(rows=tuple(rows), beam=beam, max_candidates=max_candidates, draws=draws)
+        self._entry("admit", rows, int(x[0, 1]), beam)
         return x
 
     def forward(self, items, out_rows):
@@ -54,8 +63,8 @@ class FakeEngine:
             assert row in self.rows and pos + count <= DIMS.n_text_ctx
         self.log.append(("forward", tuple(items), tuple(out_rows)))
 
-    def detect(self, row, out_index, token_index):
-        self.log.append(("detect", row, token_index))
+    def detect(self, rows, out_index, token_index):
+        self._entry("detect", rows, token_index)
 
     def pick(self, rows):
         for r in rows:
@@ -68,12 +77,21 @@ class FakeEngine:
         self.log.append(("flags",))
         return [r in self.rows and TOK.eot in self.rows[r]["tokens"] for r in range(self.max_rows)]
 
-    def read(self, row, detected, sot_index):
-        s = self.rows.pop(row)
-        self.log.append(("read", row, s["tag"]))
-        self.counts[s["tag"]] = len(s["tokens"])
-        return RowRead(tokens=s["tokens"], count=len(s["tokens"]), sum_logprob=-float(len(s["tokens"])), no_speech_prob=0.25,
-                       language_probs={t: (0.5 if t == TOK.language_tokens[3] else 0.0) for t in TOK.language_tokens} if detected else None)
+    def read(self, rows, detected, sot_index):
+        self._entry("read", rows, self.rows[rows[0]]["tag"])
+        g = self.groups.pop(rows[0])
+        assert tuple(rows) == g["rows"]
+        states = [self.rows.pop(r) for r in rows]
+        self.counts[states[0]["tag"]] = len(states[0]["tokens"])
+        live = [(list(s["tokens"]), -float(len(s["tokens"]) + k)) for k, s in enumerate(states)]
+        finished = []
+        if g["beam"]:
+            end = states[0]["end_at"]
+            if end and len(states[0]["tokens"]) >= end:
+                finished = [([1000 + i for i in range(1, end)] + [k], -float(k + 1)) for k in range(len(rows))]
+            live = [([t for t in s["tokens"] if t != TOK.eot], -10.0 - k) for k, s in enumerate(states)]
+        return GroupRead(finished=finished, live=live, no_speech_prob=0.25,
+                        language_probs={t: (0.5 if t == TOK.language_tokens[3] else 0.0) for t in TOK.language_tokens} if detected else None)
 
     def close(self):
         self.log.append(("close",))

@@ -13,52 +13,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from test_whisper_serve_cpu import DIMS, TOK, FakeEngine, window  # noqa: E402
+from test_whisper_serve_cpu import DIMS, TOK, serve, window  # noqa: E402
 
 from mlx_audio_amd import whisper_decoding as WD  # noqa: E402
 from mlx_audio_amd import whisper_transcribe as WT  # noqa: E402
-from mlx_audio_amd.whisper_serve import GroupRead, WhisperBatcher  # noqa: E402
-
-
-class GroupEngine(FakeEngine):
-    """FakeEngine plus the group seam.  A group's rows pick as single rows do (1000 + k, eot from pick `end_at` on); a beam group is complete -- every
-    row flagged -- from the pick `end_at` on, and its finished store then holds ONE sequence per beam: [1000 + 1 .. 1000 + end_at - 1] + [slot]."""
-
-    def __init__(self):
-        super().__init__()
-        self.groups = {}  # leader -> dict(rows, beam)
-
-    def admit_group(self, rows, x, init, options, beam, max_candidates=1, draws=None):
-        for r in rows:
-            assert r not in self.rows, "a row is handed on only after its group was read"
-            self.rows[r] = dict(end_at=int(x[0, 0]), tag=int(x[0, 1]), tokens=[], init=init)
-        self.groups[rows[0]] = dict(rows=tuple(rows), beam=beam, max_candidates=max_candidates, draws=draws)
-        self.log.append(("admit_group", tuple(rows), int(x[0, 1]), beam))
-        return x
-
-    def detect_group(self, rows, out_index, token_index):
-        self.log.append(("detect_group", tuple(rows), token_index))
-
-    def read_group(self, rows, detected, sot_index):
-        g = self.groups.pop(rows[0])
-        assert tuple(rows) == g["rows"]
-        states = [self.rows.pop(r) for r in rows]
-        self.log.append(("read_group", tuple(rows), states[0]["tag"]))
-        self.counts[states[0]["tag"]] = len(states[0]["tokens"])
-        live = [([t for t in s["tokens"]], -float(k + 1)) for k, s in enumerate(states)]
-        finished = []
-        if g["beam"]:
-            end = states[0]["end_at"]
-            if end and len(states[0]["tokens"]) >= end:
-                finished = [([1000 + i for i in range(1, end)] + [k], -float(k + 1)) for k in range(len(rows))]
-            live = [([t for t in s["tokens"] if t != TOK.eot], -10.0 - k) for k, s in enumerate(states)]
-        return GroupRead(finished=finished, live=live, no_speech_prob=0.25,
-                         language_probs={t: (0.5 if t == TOK.language_tokens[3] else 0.0) for t in TOK.language_tokens} if detected else None)
-
-
-def serve(**kw):
-    eng = GroupEngine()
-    return eng, WhisperBatcher(engine=eng, **kw)
 
 
 def test_a_group_waits_for_its_rows_and_nothing_overtakes_it():

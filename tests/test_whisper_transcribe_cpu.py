@@ -322,9 +322,9 @@ def test_the_driver_runs_five_files_on_two_rows_each_as_it_runs_alone():
 
 # ---- submit_sampled behind the engine seam ------------------------------------------------------------------------------------------------------
 class DrawEngine(FakeEngine):
-    def admit(self, row, x, init, options, draw=None):
-        self.log.append(("draw", row, draw))
-        return super().admit(row, x, init, options)
+    def admit(self, rows, x, init, options, beam=False, max_candidates=1, draws=None):
+        self.log.append(("draw", rows[0], draws[0] if draws else None))
+        return super().admit(rows, x, init, options, beam, max_candidates, draws)
 
 
 def test_submit_sampled_hands_the_draw_to_admit_and_submit_keeps_refusing():
@@ -346,7 +346,7 @@ def test_submit_sampled_hands_the_draw_to_admit_and_submit_keeps_refusing():
         s.submit_sampled(window(), language=0, temperature=0.5, stream=2 ** 32)
     with pytest.raises(NotImplementedError, match="temperature > 0 is not yet implemented"):
         s.submit(window(), temperature=0.5)
-    s2 = WhisperBatcher(engine=FakeEngine(), max_rows=1)  # an engine whose admit knows no draw still serves greedy requests
+    s2 = WhisperBatcher(engine=FakeEngine(), max_rows=1)  # a greedy request has no draws
     f = s2.submit(window(2, 0), language=0)
     s2.run_until_idle()
     assert len(f.result(1).tokens) == 1
