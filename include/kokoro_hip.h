@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 26  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 27  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -74,7 +74,9 @@ extern "C" {
                                (kk_whisper_text_rows_set_draw, kk_op_mel_windows);
                             26: groups of row mode: beam search and best_of in the running batch (kk_whisper_text_rows_groups_state_bytes,
                                kk_whisper_text_rows_groups_bind, kk_whisper_text_rows_admit_group, kk_whisper_text_rows_group_read,
-                               kk_whisper_text_rows_group_release, kk_whisper_text_rows_group_offers, KK_WHISPER_GROUP_PLAIN / _BEAM) */
+                               kk_whisper_text_rows_group_release, kk_whisper_text_rows_group_offers, KK_WHISPER_GROUP_PLAIN / _BEAM);
+                            27: a listener's utterance becomes a Whisper window: spans of sample buffers, resampled and log-mel'ed in one launch pair
+                               (kk_op_log_mel_spans) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -856,6 +858,18 @@ int kk_op_attention_long(void* stream, int B, const void* qkv, int ld, int T_row
  * 16-byte loads and stores, no arithmetic. */
 int kk_op_mel_windows(void* stream, int R, const float* const* src, const int32_t* frames, const int32_t* first, const int32_t* size, int W, int n_mels,
                       float* out);
+/* Spans of sample buffers as Whisper windows (ABI minor 27).  Row r is n[r] >= 1 fp32 samples at the source rate: elements
+ * pos[r] .. pos[r] + n[r] - 1 of the flat buffer buf[r] (ring_len[r] = 0), or samples (pos[r] + i) % ring_len[r] of a ring (n[r] <= ring_len[r]);
+ * buf_len[r] is the buffer's element count.  out[r] is, bit for bit, the first W frames of kk_op_log_mel with padding = 160 W over
+ * kk_op_resample(span, L, M) (L == M: over the span itself): the resampler's fmaf chain, the frame arithmetic and the row maximum over ALL frames
+ * of the padded clip are the ones of those two entry points.  Nothing outside a span is read.  buf, buf_len, ring_len, pos and n are HOST arrays of
+ * R entries that go to the kernel by value, 1 <= R <= KK_WHISPER_MAX_ROWS; a row whose ceil(n L / M) exceeds 160 W, a span outside its buffer and a
+ * ratio whose frame does not fit the workgroup's LDS (served: L (T | 1) <= 512 and 399 M / L + T + 2 <= 1536, which covers 8, 12, 24, 32 and
+ * 48 kHz) are refused before anything is launched.  tab: DEVICE fp32 [L][T], the phase table kk_resampler_set_row takes (unused when L == M);
+ * window, cos_sin, fbT as for kk_op_log_mel.  partial: scratch, R * (W + 2) floats.  out DEVICE fp32 [R][W][n_mels].  W >= 3.  Two launches. */
+int kk_op_log_mel_spans(void* stream, int R, const float* const* buf, const int64_t* buf_len, const int32_t* ring_len, const int64_t* pos,
+                        const int32_t* n, int W, int L, int M, const float* tab, int T, int n_mels, const float* window, const float* cos_sin,
+                        const float* fbT, float* partial, float* out);
 
 typedef struct kk_whisper kk_whisper;
 /* the audio fields of ModelDimensions (whisper.py:67-78); n_audio_state / n_audio_head must be 64, n_mels 80 or 128 */

@@ -305,6 +305,7 @@ SIGNATURES = {
     "kk_whisper_text_rows_group_release": (_i, [_vp, _i]),
     "kk_whisper_text_rows_group_offers": (_i, [_vp, _vp, _i, _vp, _vp]),
     "kk_op_mel_windows": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "kk_op_log_mel_spans": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "kk_op_whisper_qk_rows_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "kk_op_whisper_qk_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, C.c_longlong]),
     "kk_op_whisper_align_matrix_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
@@ -362,7 +363,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 26:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 27:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

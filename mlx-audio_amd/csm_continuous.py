@@ -28,7 +28,7 @@ import torch
 from . import pcm as PCM
 from . import resample as RS
 from . import vad as VAD
-from .csm_listen import ListenMixin, _claim, _fail_future, _Heard, _speech_span, _vacate
+from .csm_listen import ListenMixin, _claim, _drop_transcript, _fail_future, _Heard, _speech_span, _vacate
 
 _END = object()  # what the utterance queue holds behind the last utterance of a closed microphone
 
@@ -50,6 +50,8 @@ class CSMUtterance(_Heard):
         self.dropped = False
         self._start, self._stop, self._final = int(start), None, False
         self._done = False                    # resolved, dropped or failed: the scheduler has let go of it
+        if listener._topts is not None:       # a transcribing microphone: every utterance has its transcript
+            self._transcribes(listener._topts)
 
     def _took(self, codes: torch.Tensor, F: int) -> None:
         super()._took(codes, F)
@@ -73,9 +75,11 @@ class CSMContinuousListener:
     last utterance has resolved.  `cancel()` drops everything at once.  It holds one row of the batcher's streaming encoder, resampler,
     detector and device buffer from `listen` until then."""
 
-    def __init__(self, batcher, row: int, speaker: int, session, sample_rate: Optional[int], fmt: Optional[str], vad: VAD.VadConfig, barge_in: bool):
+    def __init__(self, batcher, row: int, speaker: int, session, sample_rate: Optional[int], fmt: Optional[str], vad: VAD.VadConfig, barge_in: bool,
+                 transcribe=None):
         self.batcher, self.row, self.speaker, self.session = batcher, int(row), int(speaker), session
         self.cfg, self.barge_in = vad, bool(barge_in)
+        self._topts = transcribe              # the checked whisper DecodingOptions of `listen(transcribe=)`, or None
         self._open = True                     # False once cancelled or freed: the row is someone else's
         self.spf = int(batcher.engine.samples_per_frame)
         self.rate, self.fmt = sample_rate, fmt
@@ -190,6 +194,7 @@ class CSMContinuousListener:
             u._done = True
             u.endpoint.cancel()
             _fail_future(u._future, e)
+            _drop_transcript(u, e)
         self._uq.put(_END)
 
 
@@ -205,9 +210,9 @@ class ContinuousMixin(ListenMixin):
         self._rvad_a = [0] * self.listen_rows   # ... the acked of its last step (a row no step takes is handed the same again)
         self._cont_out: Deque[tuple] = deque()  # (ticket, {row: (listener, the n24 covered)}): status and log on their way to the host
 
-    def _cont_listen(self, row, speaker, session, sample_rate, fmt, vad, barge_in) -> CSMContinuousListener:
+    def _cont_listen(self, row, speaker, session, sample_rate, fmt, vad, barge_in, **extra) -> CSMContinuousListener:
         """Under the lock."""
-        lis = CSMContinuousListener(self, row, speaker, session, sample_rate, fmt, vad, barge_in)
+        lis = CSMContinuousListener(self, row, speaker, session, sample_rate, fmt, vad, barge_in, **extra)
         self._cont_made = True
         return lis
 
@@ -266,7 +271,7 @@ class ContinuousMixin(ListenMixin):
         if left > 0:
             return ("tail", u, left)
         if u._future is not None:
-            return ("finish", u)
+            return ("finish", u) if u._text_ready(lis.session) else None  # (a session's `end()` without text waits for its transcript)
         nxt = lis._utts[1] if len(lis._utts) > 1 else None
         if nxt is not None and (nxt._final or self._cont_avail(lis, nxt) >= M):
             return ("drop", u)  # the next utterance needs the encoder row
@@ -309,6 +314,8 @@ class ContinuousMixin(ListenMixin):
                     self._cont_whole(lis)
                     did = True
             plans = [(lis, self._cont_plan(lis)) for lis in mics]
+        if self._stt is not None:
+            self._stt_mark_utts()  # (before anything of this round can finish or drop an utterance and hand its room in the ring on)
         full = [(lis, p[1]) for lis, p in plans if p is not None and p[0] == "full"]
         if full:
             self._cont_encode(full, self.listen_chunk)
@@ -335,6 +342,20 @@ class ContinuousMixin(ListenMixin):
             self._cont_free(lis)
             did = True
         return bool(did or full or tails)
+
+    def _stt_mark_utts(self) -> None:
+        """The utterances that became final (endpoints, forced ones and a closed microphone's last included): their spans of the ring, at
+        64-bit stream positions, join the round's cut (csm_listen.py).  An utterance stays in `_utts`, and so behind the upload
+        gate's `keep_from`, until this round's finish or drop at the earliest; nothing is written to the ring between here and the round's
+        cut, which is stream-ordered before every later write."""
+        spans = []
+        with self._lock:
+            for lis in self._cont_mics():
+                for u in lis._utts:
+                    if u.transcript is not None and not u._tcut and u._final:
+                        u._tcut = True
+                        spans.append((u, lis.row, lis.ring_len, u._start, u._stop - u._start))
+        self._stt_mark(spans)
 
     def _cont_whole(self, lis: CSMContinuousListener) -> None:
         """Under the lock: the closed microphone's stream is whole and classified: an utterance still open ends with it."""

@@ -31,7 +31,17 @@ Without `vad=` nothing of this exists: no detector is made and a listen round is
 
 Always-open microphones: `listen(vad=..., continuous=True)` (csm_continuous.py).  One listener yields utterance after
 utterance (`CSMUtterance`) from a ring on the device, a detector that re-arms behind every endpoint and a host queue that a silent microphone
-never fills.  Without `continuous=True` nothing of it exists."""
+never fills.  Without `continuous=True` nothing of it exists.
+
+Speech to text: `CSMBatcher(..., stt=whisper_model.serve(...))` and `listen(transcribe=True | DecodingOptions | dict)`.  In the round
+in which a transcribing listener's span becomes final -- a VAD endpoint, `end()` and the covering status, `end()` and the flush of a listener
+without a detector (its span is everything it heard), a continuous utterance's endpoint -- the scheduler cuts the Whisper windows of ALL the
+round's spans out of the device buffers in ONE launch pair (`engine.span_windows`: `_heard` rows for the one-shot listeners, the rings at their
+64-bit stream positions for the continuous ones), encodes them in ONE `embed_audio` call and submits each row's features to `stt` with the
+listener's options; `lis.transcript` / `utt.transcript` (a `Future[DecodingResult]`) resolves when Whisper's does, with what
+`whisper_model.decode(window, options)` returns for that window alone.  The scheduler steps `stt` itself, `stt_rounds_per_round` times per round
+at the most, so `stt` must not have a thread of its own.  With `stt_text=` (DecodingResult -> what `end(text)` takes) a session's listener may
+`end()` without text: the heard turn waits for the transcript.  Without `stt=` nothing of this exists."""
 from __future__ import annotations
 
 from collections import deque
@@ -112,6 +122,18 @@ class _Heard:
         self._fresh = True                    # the encoder row is reset before this stream's first step
         self._future: Optional[Future] = None
         self._text = None
+        # speech to text: None without `transcribe=`
+        self.transcript: Optional[Future] = None  # -> whisper DecodingResult of the span's window
+        self._topts = None                    # the checked DecodingOptions
+        self._tcut = False                    # the span's window has been cut (or the transcript has failed before)
+        self._twf: Optional[Future] = None    # the Whisper request's own future, once submitted
+
+    def _transcribes(self, options) -> None:
+        self.transcript, self._topts = Future(), options
+
+    def _text_ready(self, session) -> bool:
+        """Under the lock: an ended stream's text is there -- given, or (a session's `end()` without text) its transcript has resolved."""
+        return self._text is not None or session is None or self.transcript is None or self.transcript.done()
 
     def codes(self) -> torch.Tensor:
         """The codes encoded so far, [n_cb, frames] int32 on the host (a copy from the device)."""
@@ -135,7 +157,7 @@ class _Heard:
                 raise RuntimeError("CSMBatcher is closed")
             self._end_refused()
             if session is not None:
-                if text is None:
+                if text is None and (self.transcript is None or b._stt_text is None):
                     raise ValueError("end: a session's heard turn needs its text")
                 session._ready("end")
             fut: Future = Future()
@@ -160,9 +182,11 @@ class CSMListener(_Heard):
     streaming encoder from `listen` until the result (or `cancel`)."""
 
     def __init__(self, batcher, row: int, speaker: int, session=None, sample_rate: Optional[int] = None, fmt: Optional[str] = None,
-                 vad: Optional[VAD.VadConfig] = None, barge_in: bool = False):
+                 vad: Optional[VAD.VadConfig] = None, barge_in: bool = False, transcribe=None):
         super().__init__(batcher)
         self.row, self.speaker, self.session = int(row), int(speaker), session
+        if transcribe is not None:
+            self._transcribes(transcribe)
         # voice activity (DESIGN 8d-12): the detector's settings, or None -- then nothing below `barge_in` is ever touched
         self.vad, self.barge_in = vad, bool(barge_in)
         self.onset: Optional[Future] = Future() if vad is not None else None     # -> the first kept sample at the model's rate, once speech began
@@ -177,7 +201,8 @@ class CSMListener(_Heard):
         self.spf = int(batcher.engine.samples_per_frame)
         self.rate = sample_rate               # None: fed at the model's rate; else the scheduler resamples what is fed
         self.fmt = fmt                        # None: fed float32; else the samples are kept and uploaded in this format
-        self._dev = sample_rate is not None or fmt is not None or vad is not None  # the encoder reads this listener from its device buffer at the model's rate
+        # the encoder reads this listener from its device buffer at the model's rate (a transcribing one: the window is cut out of that buffer)
+        self._dev = sample_rate is not None or fmt is not None or vad is not None or transcribe is not None
         cap = batcher.listen_max_frames * self.spf
         if self.rate is not None:             # the most samples at `rate` whose out_len fits the row: N L <= cap M
             L, M = RS.ratio(self.rate, batcher.engine.sample_rate)
@@ -282,6 +307,16 @@ class CSMListener(_Heard):
         """The listener leaves before its result: a pending `end()` fails with `e` (None: it is cancelled), one that never ended just stops."""
         self._leave()
         _fail_future(self._future, e)
+        _drop_transcript(self, e)
+
+
+def _drop_transcript(h: _Heard, e: Optional[BaseException]) -> None:
+    """A transcript that is still owed fails with `e` (None: it is cancelled).  A Whisper request that is queued is cancelled with it; one in
+    flight runs out and its result is dropped."""
+    if h.transcript is not None and not h.transcript.done():
+        _fail_future(h.transcript, e)
+        if h._twf is not None:
+            h._twf.cancel()
 
 
 class ListenMixin:
@@ -307,6 +342,8 @@ class ListenMixin:
 
     def _listen_close(self) -> None:
         """`CSMBatcher.close`, the worker has stopped: every listener's row is taken, whoever waits on one is told, the objects are closed."""
+        if self._stt is not None:
+            self._stt_close()
         with self._lock:
             listeners = [lis for lis in self._listeners if lis is not None]
         self._vad_out.clear()
@@ -317,7 +354,7 @@ class ListenMixin:
                 obj.close()
 
     def listen(self, speaker: int = 0, session=None, sample_rate: Optional[int] = None,
-               format: Optional[str] = None, vad=None, barge_in: bool = False, continuous: bool = False):
+               format: Optional[str] = None, vad=None, barge_in: bool = False, continuous: bool = False, transcribe=None):
         """A microphone (`CSMListener`) on a free row of the batcher's streaming encoder; ValueError when all `listen_rows` are taken (or
         the batcher was made without any).  `session`: what `CSMSession.listen` passes.  `sample_rate`: the rate `feed` takes (None: the
         model's); ValueError for a rate the resampler does not take.  `format` (`pcm.FORMATS`; None or "f32": float32): what `feed` takes --
@@ -329,7 +366,11 @@ class ListenMixin:
         heard[speech_start:speech_stop] and ended, or fails with ValueError("no speech").  `barge_in` (a session's listener): the onset
         interrupts the session's queued or live turn in the round that sees it.
         `continuous` (needs `vad`): the microphone stays open -> a `CSMContinuousListener`: one `CSMUtterance` per detected
-        utterance, each with its own `onset`, `endpoint` and `end(text)`, until `close()`."""
+        utterance, each with its own `onset`, `endpoint` and `end(text)`, until `close()`.
+        `transcribe` (True, a whisper `DecodingOptions` or a dict of its fields; needs a batcher made with `stt=`):
+        `lis.transcript` (every utterance's `utt.transcript`) is a `Future[DecodingResult]` of the span's Whisper window, decoded greedily with
+        these options beside whatever else `stt` runs.  The options are checked here, with `whisper_decoding.verify_options`' exceptions."""
+        topts = self._stt_options(transcribe)
         if continuous and (vad is None or vad is False):
             raise ValueError("listen: continuous=True needs vad=")
         if self._enc is None:
@@ -356,9 +397,12 @@ class ListenMixin:
             if not free:
                 raise ValueError(f"all {self.listen_rows} listen rows are taken")
             if continuous:  # (csm_continuous.ContinuousMixin)
-                lis = self._listeners[free[0]] = self._cont_listen(free[0], speaker, session, sample_rate, fmt, vad, barge_in)
+                extra = {} if topts is None else {"transcribe": topts}
+                lis = self._listeners[free[0]] = self._cont_listen(free[0], speaker, session, sample_rate, fmt, vad, barge_in, **extra)
                 return lis
             extra = {} if vad is None else {"vad": vad, "barge_in": barge_in}
+            if topts is not None:
+                extra["transcribe"] = topts
             lis = self._listeners[free[0]] = CSMListener(self, free[0], speaker, session, sample_rate, fmt, **extra)
         return lis
 
@@ -456,7 +500,8 @@ class ListenMixin:
                 if lis.session._closed:
                     raise ValueError("end: the session is closed")
                 host = codes.cpu().numpy()  # (synchronises: the codes are the session's prompt frames from here on)
-                lis.session._hear(self.engine.heard_segment(lis.speaker, h._text, audio()), host)
+                text = h._text if h._text is not None else self._stt_text(h.transcript.result())  # (`end()` without text: a failed transcript fails the turn)
+                lis.session._hear(self.engine.heard_segment(lis.speaker, text, audio()), host)
             release()
             fut.set_result(ListenResult(codes=codes, frames=h.frames, steps=list(h.steps), **fields))
         except Exception as e:  # noqa: BLE001
@@ -483,7 +528,7 @@ class ListenMixin:
                 full.append(lis)
             elif whole and left > 0:
                 tails.setdefault(left, []).append(lis)
-            elif ended:
+            elif ended and lis._text_ready(lis.session):  # (a session's `end()` without text waits for its transcript)
                 done.append(lis)
         return full, tails, done
 
@@ -580,6 +625,8 @@ class ListenMixin:
         fresh = self._listen_resample()
         if self._vad is not None and (self._vad_step() or self._vad_out):
             fresh = True
+        if self._stt is not None:
+            self._stt_mark_shots()  # (before anything of this round can finish a listener and hand its row on)
         with self._lock:
             full, _, _ = self._listen_plan()
         if full:
@@ -634,6 +681,167 @@ class ListenMixin:
         fields = dict(samples=lis.samples, sample_rate=lis.rate if lis.rate is not None else int(self.engine.sample_rate),
                       **({"format": lis.fmt} if lis.fmt is not None else {}), **span)
         self._heard_turn(lis, lis, audio, fields, error="no speech" if lis.vad is not None and lis._vstart is None else None)
+
+    # ---- speech to text -------------------------------------------------------------------------------------------------------
+    def _stt_init(self, stt, rounds_per_round: int, stt_text) -> None:
+        self._stt, self._stt_text = None, None
+        self._stt_rounds = None
+        self._stt_due = None   # spans that became final in this round: (holder, listener row, ring length or 0, start, samples)
+        self._stt_owed = None  # holders whose Whisper request has been submitted and has not resolved
+        if stt is None:
+            if stt_text is not None:
+                raise ValueError("stt_text needs stt=")
+            return
+        if int(rounds_per_round) < 1:
+            raise ValueError("stt_rounds_per_round must be >= 1")
+        if stt_text is not None and not callable(stt_text):
+            raise ValueError("stt_text must be a callable: DecodingResult -> what end(text) takes")
+        if getattr(stt, "_thread", None) is not None:
+            raise ValueError("stt must not have been start()ed: the CSM scheduler steps it on its own thread and stream")
+        if getattr(stt, "closed", False):
+            raise ValueError("stt is closed")
+        self._stt, self._stt_text, self._stt_rounds = stt, stt_text, int(rounds_per_round)
+        self._stt_due, self._stt_owed = [], []
+        self.stats.update(stt_cuts=0, stt_windows=0, stt_rounds=0, stt_cut_seconds=0.0)
+        stt.on_submit = self._stt_poke  # a window the caller submits to `stt` directly wakes this scheduler, which steps it
+
+    def _stt_poke(self) -> None:
+        with self._lock:
+            self._wake.notify()
+
+    def _stt_options(self, transcribe):
+        """A caller's `transcribe` checked where it is given: None for None and False, else the DecodingOptions `submit` will take."""
+        if transcribe is None or transcribe is False:
+            return None
+        if self._stt is None:
+            raise ValueError("listen: transcribe= needs a batcher made with stt=")
+        from .whisper_decoding import DecodingOptions, verify_options
+
+        if transcribe is True:
+            transcribe = DecodingOptions()
+        elif isinstance(transcribe, dict):
+            transcribe = DecodingOptions(**transcribe)
+        elif not isinstance(transcribe, DecodingOptions):
+            raise ValueError("listen: transcribe takes True, a whisper DecodingOptions or a dict of its fields")
+        return verify_options(transcribe)
+
+    def _stt_has_work(self) -> bool:
+        """`stt` has queued or live requests, or spans wait for their cut: due work."""
+        if self._stt is None:
+            return False
+        with self._stt._lock:
+            queued = bool(self._stt._queue)
+        return queued or bool(self._stt_due) or any(r is not None for r in self._stt._rows)
+
+    def _stt_mark(self, spans) -> None:
+        """Spans that became final, (holder, listener row, ring length or 0, start or None, samples): their windows are cut by this round's
+        `_stt_round`; a span without speech fails its transcript like `end()`."""
+        for it in spans:
+            if it[3] is None or it[4] < 1:
+                _fail_future(it[0].transcript, ValueError("no speech"))
+            else:
+                with self._lock:
+                    self._stt_due.append(it)
+
+    def _stt_mark_shots(self) -> None:
+        """The one-shot listeners whose span became final: a detector's [start, stop), or all a listener without one has heard."""
+        spans = []
+        with self._lock:
+            for lis in self._shots():
+                if lis.transcript is None or lis._tcut:
+                    continue
+                if lis.vad is not None and lis._vclosed:
+                    spans.append((lis, lis.row, 0, lis._vstart, (lis._vstop or 0) - (lis._vstart or 0)))
+                elif lis.vad is None and lis.ended and lis._flushed:
+                    spans.append((lis, lis.row, 0, 0, lis._n24))
+            for it in spans:
+                it[0]._tcut = True
+        self._stt_mark(spans)
+
+    def _stt_round(self) -> bool:
+        """The scheduler's thread, once per scheduling round behind the listen round: the round's final spans become Whisper windows in ONE
+        `span_windows` launch pair and ONE `embed_audio` call and are submitted in row order; then `stt` is stepped, `stt_rounds_per_round`
+        times at the most, while it has queued or live requests.  False when there was nothing to do."""
+        with self._lock:
+            due, self._stt_due = self._stt_due, []
+        if due:
+            self._stt_cut(sorted(due, key=lambda it: it[1]))
+        n = 0
+        while n < self._stt_rounds and self._stt_has_work():
+            self._stt.step()
+            n += 1
+        self.stats["stt_rounds"] += n
+        self._stt_owed = [h for h in self._stt_owed if not h.transcript.done()]
+        return bool(due) or n > 0
+
+    def _stt_cut(self, due) -> None:
+        from . import whisper as WH
+        from ._lib import WHISPER_MAX_ROWS
+
+        stt = self._stt
+        d = stt.engine.dims
+        W, sr = 2 * int(d.n_audio_ctx), int(self.engine.sample_rate)
+        rows = []
+        for it in due:
+            h, row, _, _, n = it
+            try:
+                L, M = WH.span_ratio(sr)
+                if WH.span_len16(n, L, M) > W * WH.HOP_LENGTH:
+                    raise ValueError(f"transcribe: the utterance of listen row {row} is {WH.span_len16(n, L, M)} samples at 16 kHz, more than the "
+                                     f"{W * WH.HOP_LENGTH} of one Whisper window (long-form decoding of listeners is not built)")
+            except ValueError as e:
+                _fail_future(h.transcript, e)
+                continue
+            if not h.transcript.done():  # (cancelled meanwhile)
+                rows.append(it)
+        for at in range(0, len(rows), WHISPER_MAX_ROWS):
+            chunk = rows[at : at + WHISPER_MAX_ROWS]
+            try:
+                out: List[torch.Tensor] = []
+                spans = [(self._heard[row], ring_len, start, n) for _, row, ring_len, start, n in chunk]
+                self._timed("stt_cut", lambda: out.append(stt.engine.embed_audio(self.engine.span_windows(spans, W, int(d.n_mels)))))
+                feats = out[0]
+            except Exception as e:  # noqa: BLE001  (the shared launch: it fails the rows that took part in it)
+                for it in chunk:
+                    _fail_future(it[0].transcript, e)
+                continue
+            self.stats["stt_cuts"] += 1
+            self.stats["stt_windows"] += len(chunk)
+            for i, (h, _, _, _, _) in enumerate(chunk):
+                try:
+                    h._twf = stt.submit(feats[i], h._topts)
+                except Exception as e:  # noqa: BLE001  (this row's own refusal: the others go on)
+                    _fail_future(h.transcript, e)
+                    continue
+                self._stt_owed.append(h)
+                h._twf.add_done_callback(lambda wf, h=h: self._stt_done(h, wf))
+
+    def _stt_done(self, h: _Heard, wf: Future) -> None:
+        """Whisper's future has resolved (on the thread that stepped `stt`: this scheduler's): so does the transcript, unless it was dropped."""
+        if h.transcript.done():
+            return
+        if wf.cancelled():
+            h.transcript.cancel()
+            return
+        e = wf.exception()
+        try:
+            if e is not None:
+                h.transcript.set_exception(e)
+            else:
+                h.transcript.set_result(wf.result())
+        except InvalidStateError:
+            pass
+        with self._lock:
+            self._wake.notify()  # (a session's `end()` without text may be waiting for it)
+
+    def _stt_close(self) -> None:
+        """`CSMBatcher.close`: `stt` stays open and is the caller's again; the transcripts still owed fail."""
+        self._stt.on_submit = None
+        with self._lock:
+            due, self._stt_due = self._stt_due, []
+        for h in [it[0] for it in due] + self._stt_owed:
+            _drop_transcript(h, RuntimeError("CSMBatcher is closed"))
+        self._stt_owed = []
 
     # ---- voice activity (DESIGN 8d-12) -----------------------------------------------------------------------------------------------------
     def _vad_step(self) -> bool:

@@ -51,6 +51,8 @@ is conditioned on are those of a turn of k frames.  The other rows see a park an
 Listening: `CSMBatcher(..., listen_rows=K)` and `batcher.listen()` / `sess.listen(speaker)` (DESIGN 8d-9 ... 8d-13): microphones at any sample
 rate and in any PCM format, with endpointing and barge-in, one-shot or always open.  That edge touches no cache row and lives in csm_listen.py
 and csm_continuous.py; this module calls `_listen_init`, `_listen_consume`, `_listen_round`, `_listen_due` and `_listen_close` and re-exports its names.
+With `stt=` (a `whisper_serve.WhisperBatcher`) a listener made with `transcribe=` has its utterance transcribed: `_stt_init`, and `_stt_round`
+behind the listen round, which also steps `stt`; its work counts as due work (`_stt_has_work`).
 
 Audio out at other rates and in PCM formats: `submit(..., sample_rate=R, format="s16le")` / `submit_stream(...)` (`pcm.FORMATS`).
 Every chunk passes through the cache row's resampler row (`resample.RowResampler`), the last one flushes, and the chunks concatenate, bit for
@@ -262,18 +264,22 @@ class CSMSession:
         self.pending, self.history = _cat(self.pending, f), _cat(self.history, f)
 
     def listen(self, speaker: int = 0, sample_rate: Optional[int] = None, format: Optional[str] = None, vad=None, barge_in: bool = False,
-               continuous: bool = False):
+               continuous: bool = False, transcribe=None):
         """`CSMBatcher.listen` for this conversation: another speaker's microphone.  Allowed while the session's own turn is queued or live
         (a barge-in); the turn enters the history at the listener's `end(text)`, which waits for that turn as `hear` does.
         vad (`vad.VadConfig`, or True for the defaults): the scheduler finds the utterance itself.  barge_in (needs vad): the
         round that sees the speaker's onset interrupts this session's queued or live turn, which keeps what it has emitted.
         continuous (needs vad): the microphone stays open and yields one `CSMUtterance` per utterance (`CSMContinuousListener`, DESIGN
-        8d-13); each `utt.end(text)` enters the history as `hear` would, and with barge_in EVERY onset interrupts the queued or live turn."""
+        8d-13); each `utt.end(text)` enters the history as `hear` would, and with barge_in EVERY onset interrupts the queued or live turn.
+        transcribe (needs a batcher made with `stt=`): `lis.transcript` / `utt.transcript` resolves with Whisper's
+        `DecodingResult` of the utterance; with the batcher's `stt_text=`, `end()` may then be called without text."""
         if self._closed:
             raise ValueError("listen: the session is closed")
         kw = {} if format is None else {"format": format}
         if continuous:
             kw["continuous"] = True
+        if transcribe is not None and transcribe is not False:
+            kw["transcribe"] = transcribe
         if vad is not None and vad is not False:
             kw.update(vad=vad, barge_in=barge_in)
         elif barge_in:
@@ -545,6 +551,13 @@ class ModelEngine:
 
         return Segment(speaker=int(speaker), text=text, audio=audio)
 
+    def span_windows(self, spans, W: int, n_mels: int) -> torch.Tensor:
+        """Spans (buffer row, ring length or 0, start, samples) of the listeners' device buffers at the model's rate -> their Whisper windows
+        (R, W, n_mels) in one launch pair (whisper.span_windows)."""
+        from . import whisper as WH
+
+        return WH.span_windows(spans, W, n_mels, src_rate=int(self.sample_rate))
+
     def synchronize(self) -> None:
         torch.cuda.current_stream(self.device).synchronize()
 
@@ -643,7 +656,8 @@ class CSMBatcher(ContinuousMixin):
     def __init__(self, model, max_batch: int = 8, eos_check_interval: int = 8, rng: str = "device", sampler=None, seed: int = 0,
                  stop_on_eos: bool = True, decode: bool = True, profile: bool = False, engine=None, stream_chunk_frames: Optional[int] = None,
                  stream_max_frames: int = 1125, row_samplers: bool = False, overlap_admission: bool = False, prefill_lanes: int = 1,
-                 listen_rows: int = 0, listen_chunk_frames: int = 6, listen_max_frames: int = 375):
+                 listen_rows: int = 0, listen_chunk_frames: int = 6, listen_max_frames: int = 375, stt=None, stt_rounds_per_round: int = 4,
+                 stt_text=None):
         """model: a loaded sesame.Model (its frame generator's caches are taken over; use `model.share()` for a generator of its own).
         sampler: `make_sampler(...)` for every stream of the batch (default temp 0.9 / top_k 50; with `row_samplers` the default of a request).  seed: the device generator's seed (rng
         "device": one seed per batcher, streams differ by their ids).  profile: time admissions and shifts (one sync each) into `stats`.
@@ -660,7 +674,12 @@ class CSMBatcher(ContinuousMixin):
         listen_rows: K > 0 enables `listen` (up to K listeners at a time) on one row-mode streaming encoder of K rows; encoder rows are not
         cache rows, so listening never occupies a generation row.  listen_chunk_frames: M, the frames of one encode step (a listener's
         stream is always encoded in [M] * (T // M) + [T % M]).  listen_max_frames: the longest heard turn (the encoder's K / V cache holds
-        that many frames per row; 375 = 30 s).  0: no encoder is made and `step` is what it was."""
+        that many frames per row; 375 = 30 s).  0: no encoder is made and `step` is what it was.
+        stt: a `whisper_model.serve(...)` (whisper_serve.WhisperBatcher) that has NOT been started enables `listen(transcribe=...)` (DESIGN
+        8d-15): this scheduler cuts the listeners' utterances into Whisper windows on the device and steps `stt` itself, on its own thread and
+        stream -- up to `stt_rounds_per_round` of its rounds per scheduling round while it has queued or live requests.  The caller may still
+        `stt.submit(...)`; `close()` leaves `stt` open.  stt_text: a callable DecodingResult -> what `end(text)` takes (ids or str), which
+        lets a session's transcribing listener `end()` without text.  None: nothing of it is made and `step` is what it was."""
         if overlap_admission and int(prefill_lanes) < 1:
             raise ValueError("prefill_lanes must be >= 1")
         if rng not in ("host", "device"):
@@ -711,6 +730,7 @@ class CSMBatcher(ContinuousMixin):
             self.stats.update(chunks=0, chunk_rounds=0)
             self._dec = self.engine.row_decoder(self.max_batch, self.stream_max_frames, self.chunk)
         self._listen_init(listen_rows, listen_chunk_frames, listen_max_frames)  # (csm_listen.py: also the stateless PCM converter `_cvt`, which the output side shares)
+        self._stt_init(stt, stt_rounds_per_round, stt_text)  # (csm_listen.py)
         # other sample rates: made by the scheduler when the first request with a rate needs them, never before
         self._ors = None                       # the streaming requests' resampler, one row per cache row
         self._crs = None                       # one row for whole clips (a plain request's result): made once, so no allocation per result
@@ -1407,6 +1427,8 @@ class CSMBatcher(ContinuousMixin):
         self._listen_consume()  # (before the controls: a barge-in's interrupt is applied in the round that sees the onset)
         now = self._apply_controls()  # (before the admissions: a row a cancel has freed is refilled in this round)
         heard = self._listen_round()  # due listen rounds are work, with or without a live row
+        if self._stt is not None:
+            heard = self._stt_round() or heard  # (the round's final spans are cut and submitted, then `stt` is stepped: its work is due work)
         while True:
             self._admit()  # (rows a poll has just freed are refilled in the same round)
             live = self._live()
@@ -1448,7 +1470,7 @@ class CSMBatcher(ContinuousMixin):
         while True:
             with self._lock:
                 while (not self._closed and not self._queue and not self._live() and not self._inflight and not self._controls
-                       and not self._listen_due()):
+                       and not self._listen_due() and not self._stt_has_work()):
                     self._wake.wait()
                 if self._closed:
                     return

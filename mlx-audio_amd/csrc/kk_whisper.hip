@@ -10,6 +10,8 @@
 //   logmel_finish_kernel: every workgroup takes the maximum of the row's partials (a maximum does not depend on order), then clamps at
 //   max - 8 and maps (. + 4) / 4.  Rows of the output past the row's frame count are zeros.
 //   A row's bits depend on its own samples alone: no sum crosses a row, a frame or a workgroup.
+//   logmel_spans_kernel / logmel_spans_finish_kernel: the same frame body (logmel_frame) behind the resampler's fmaf chains, for spans
+//   of sample buffers at another rate -- see the comment above them.
 //
 // ---- attention (bf16, v_mfma_f32_16x16x32_bf16) ------------------------------------------------------------------------------------------
 //   One workgroup = 64 query rows of one (item, head), 4 waves of 16 query rows; keys walked in tiles of 64 through LDS in index order.
@@ -36,28 +38,12 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int NFFT = 400, HOP = 160, NBIN = 201, RPAD = 200;
 
 // ------------------------------------------------------------------------------------------------------------------------------ log-mel
-__global__ __launch_bounds__(256) void logmel_frames_kernel(const float* x, long long ldx, const int* n, int padding, int n_mels, const float* window,
-                                                            const float* cs, const float* fbT, float* partial, float* out, int F_rows) {
-  __shared__ float fr[NFFT];
-  __shared__ float tc[NFFT], ts[NFFT];
-  __shared__ float pw[NBIN + 3];
-  __shared__ float wmax[4];
-  const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const int nb = n[b], N = nb + padding, F = N / HOP;
-  float* orow = out + ((long long)b * F_rows + f) * n_mels;
-  if (f >= F) {  // (uniform) past the row's frames: zeros
-    if (tid < n_mels) orow[tid] = 0.f;
-    if (tid == 0) partial[(long long)b * F_rows + f] = -INFINITY;
-    return;
-  }
-  const float* xb = x + (long long)b * ldx;
+// The arithmetic of one frame, from its 400 windowed samples in fr (staged by the caller, no barrier yet) to its n_mels log values: the twiddles
+// go to LDS, the DFT, the filter bank and log10 run as described above.  orow: where the frame's values go, or null for a frame that only enters
+// the row's maximum.  Returns the frame's maximum (valid in thread 0).  Every thread of the workgroup calls it.
+__device__ static inline float logmel_frame(float* fr, float* tc, float* ts, float* pw, float* wmax, int n_mels, const float* cs, const float* fbT,
+                                            float* orow, int tid) {
   for (int i = tid; i < NFFT; i += 256) {
-    int j = f * HOP + i - RPAD;
-    j = j < 0 ? -j : j;
-    j = j >= N ? 2 * (N - 1) - j : j;
-    j = j < 0 ? 0 : j;  // (only a row shorter than the reflect padding, which the callers refuse)
-    const float v = j < nb ? xb[j] : 0.f;  // [n, N) is the zero padding: never read
-    fr[i] = v * window[i];
     tc[i] = cs[i];
     ts[i] = cs[NFFT + i];
   }
@@ -85,31 +71,163 @@ __global__ __launch_bounds__(256) void logmel_frames_kernel(const float* x, long
     float acc = 0.f;
     for (int k = 0; k < NBIN; ++k) acc = __builtin_fmaf(pw[k], fbT[k * n_mels + tid], acc);
     lg = acc > 1e-10f ? log10f(acc) : -10.0f;  // log10(max(mel, 1e-10)); the floor itself is exactly -10
-    orow[tid] = lg;
+    if (orow) orow[tid] = lg;
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) lg = fmaxf(lg, __shfl_xor(lg, o));
   if ((tid & 63) == 0) wmax[tid >> 6] = lg;
   __syncthreads();
-  if (tid == 0) partial[(long long)b * F_rows + f] = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+  return fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+}
+
+// max(., row maximum - 8), (. + 4) / 4
+__device__ static inline float logmel_scale(float v, float lo) { return (fmaxf(v, lo) + 4.0f) * 0.25f; }
+
+// the maximum of partial[0 .. F) in every thread of the workgroup
+__device__ static inline float logmel_row_max(const float* partial, int F, float* wmax, int tid) {
+  float mx = -INFINITY;
+  for (int f = tid; f < F; f += 256) mx = fmaxf(mx, partial[f]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  if ((tid & 63) == 0) wmax[tid >> 6] = mx;
+  __syncthreads();
+  return fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+}
+
+__global__ __launch_bounds__(256) void logmel_frames_kernel(const float* x, long long ldx, const int* n, int padding, int n_mels, const float* window,
+                                                            const float* cs, const float* fbT, float* partial, float* out, int F_rows) {
+  __shared__ float fr[NFFT];
+  __shared__ float tc[NFFT], ts[NFFT];
+  __shared__ float pw[NBIN + 3];
+  __shared__ float wmax[4];
+  const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int nb = n[b], N = nb + padding, F = N / HOP;
+  float* orow = out + ((long long)b * F_rows + f) * n_mels;
+  if (f >= F) {  // (uniform) past the row's frames: zeros
+    if (tid < n_mels) orow[tid] = 0.f;
+    if (tid == 0) partial[(long long)b * F_rows + f] = -INFINITY;
+    return;
+  }
+  const float* xb = x + (long long)b * ldx;
+  for (int i = tid; i < NFFT; i += 256) {
+    int j = f * HOP + i - RPAD;
+    j = j < 0 ? -j : j;
+    j = j >= N ? 2 * (N - 1) - j : j;
+    j = j < 0 ? 0 : j;  // (only a row shorter than the reflect padding, which the callers refuse)
+    const float v = j < nb ? xb[j] : 0.f;  // [n, N) is the zero padding: never read
+    fr[i] = v * window[i];
+  }
+  const float mx = logmel_frame(fr, tc, ts, pw, wmax, n_mels, cs, fbT, orow, tid);
+  if (tid == 0) partial[(long long)b * F_rows + f] = mx;
 }
 
 __global__ __launch_bounds__(256) void logmel_finish_kernel(const int* n, int padding, int n_mels, const float* partial, float* out, int F_rows) {
   __shared__ float wmax[4];
   const int b = blockIdx.y, tid = threadIdx.x;
   const int F = (n[b] + padding) / HOP;
-  float mx = -INFINITY;
-  for (int f = tid; f < F; f += 256) mx = fmaxf(mx, partial[(long long)b * F_rows + f]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-  if ((tid & 63) == 0) wmax[tid >> 6] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-  const float lo = mx - 8.0f;
+  const float lo = logmel_row_max(partial + (long long)b * F_rows, F, wmax, tid) - 8.0f;
   const long long total = (long long)F * n_mels;
   float* ob = out + (long long)b * F_rows * n_mels;
   for (long long e = (long long)blockIdx.x * 2048 + tid; e < (long long)(blockIdx.x + 1) * 2048 && e < total; e += 256)
-    ob[e] = (fmaxf(ob[e], lo) + 4.0f) * 0.25f;
+    ob[e] = logmel_scale(ob[e], lo);
+}
+
+// ---- a span of a sample buffer becomes a Whisper window --------------------------------------------------------------------
+//   Row r: the n samples of its span (a flat buffer from `pos` on, or the ring of kk_ring.hip, sample i at (pos + i) % ring_len) are resampled
+//   L / M to 16 kHz (n16 = ceil(n L / M) samples), log_mel with padding = 160 W runs over them and the first W frames are the window.
+//   logmel_spans_kernel: one workgroup per (frame, row).  The frame's 16 kHz samples q0 .. q1 (at most 400; reflected indices of frames 0 and 1
+//   fall inside the same run) are recomputed here: the source samples they read, (q0 M + half) / L - T + 1 .. (q1 M + half) / L, go to LDS with
+//   the ring's wrap resolved and ZEROS wherever the index is outside [0, n) -- the buffer is never read there -- and thread q runs kk_resample.hip's
+//   one fmaf chain from 0.0f over the T taps of its phase in ascending input order.  L == M: the samples are taken as they are.  Then the
+//   frame body above.  A frame whose 400 samples are all padding (160 f - 200 >= n16; with W >= 3 every frame that sees a sample exists and the reflection at the clip's end never
+//   reaches back to a sample) is the floor -10 in every bin: written, not computed.  Frames W and W + 1 may still see the clip's tail: they
+//   are computed for the maximum and not stored; later ones are silent, and a silent frame cannot raise a maximum that frame 0 already
+//   holds at >= -10.
+//   logmel_spans_finish_kernel: the maximum over the row's W + 2 partials, the clamp and the scale over its W stored frames.
+constexpr int SP_WIN = 1536, SP_TAB = 512, SP_EXTRA = 2;
+struct KKMelSpans {  // by value: the rows may lie in different allocations
+  const float* buf[KK_WHISPER_MAX_ROWS];
+  long long pos[KK_WHISPER_MAX_ROWS];  // flat: the span's first element; ring: its stream position
+  int ring_len[KK_WHISPER_MAX_ROWS], n[KK_WHISPER_MAX_ROWS], n16[KK_WHISPER_MAX_ROWS];
+};
+
+__global__ __launch_bounds__(256) void logmel_spans_kernel(KKMelSpans t, int W, int L, int M, int half, int T, const float* tab, int n_mels,
+                                                           const float* window, const float* cs, const float* fbT, float* partial, float* out) {
+  __shared__ float fr[NFFT];
+  __shared__ float tc[NFFT], ts[NFFT];
+  __shared__ float pw[NBIN + 3];
+  __shared__ float wmax[4];
+  __shared__ float seg[NFFT];
+  __shared__ float win_s[SP_WIN];
+  __shared__ float tab_s[SP_TAB];
+  const int f = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
+  const int n = t.n[r], n16 = t.n16[r];
+  float* orow = f < W ? out + ((long long)r * W + f) * n_mels : nullptr;
+  float* prow = partial + (long long)r * (W + SP_EXTRA);
+  const int lo = f * HOP - RPAD;
+  if (lo >= n16) {  // (uniform) all padding: the floor
+    if (orow && tid < n_mels) orow[tid] = -10.0f;
+    if (tid == 0) prow[f] = -10.0f;
+    return;
+  }
+  const int q0 = lo < 0 ? 0 : lo, q1 = min(max(lo + NFFT - 1, -lo), n16 - 1);  // the 16 kHz samples the frame reads (frame 0 reflects -200 to 200)
+  const int cnt = q1 - q0 + 1;
+  const long long s0 = L == M ? q0 : ((long long)q0 * M + half) / L - T + 1;  // source index of win_s[0]
+  const int sn = L == M ? cnt : (int)(((long long)q1 * M + half) / L - s0) + 1;  // <= SP_WIN: the host has checked the ratio
+  {
+    const float* buf = t.buf[r];
+    const long long pos = t.pos[r];
+    const int ring = t.ring_len[r];
+    const long long base = ring ? pos % ring : pos;
+    for (int e = tid; e < sn; e += 256) {
+      const long long i = s0 + e;
+      float v = 0.f;  // outside the span: a zero that is multiplied, from a slot that is never read
+      if (i >= 0 && i < n) {
+        long long a = base + i;
+        if (ring && a >= ring) a -= ring;  // i < n <= ring_len
+        v = buf[a];
+      }
+      win_s[e] = v;
+    }
+  }
+  const int Ts = T | 1;
+  if (L != M)
+    for (int e = tid; e < L * T; e += 256) {
+      const int p = e / T;
+      tab_s[p * Ts + (e - p * T)] = tab[e];
+    }
+  __syncthreads();
+  for (int e = tid; e < cnt; e += 256) {
+    if (L == M) {
+      seg[e] = win_s[e];
+    } else {
+      const long long num = (long long)(q0 + e) * M + half, j0 = num / L;
+      const float* tp = tab_s + (int)(num - j0 * L) * Ts;
+      const float* wp = win_s + (int)(j0 - T + 1 - s0);
+      float acc = 0.f;
+      for (int i = 0; i < T; ++i) acc = fmaf(tp[T - 1 - i], wp[i], acc);
+      seg[e] = acc;
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < NFFT; i += 256) {
+    int j = lo + i;
+    j = j < 0 ? -j : j;  // (the reflection at the padded clip's end stays inside the zero padding)
+    const float v = j < n16 ? seg[j - q0] : 0.f;
+    fr[i] = v * window[i];
+  }
+  const float mx = logmel_frame(fr, tc, ts, pw, wmax, n_mels, cs, fbT, orow, tid);
+  if (tid == 0) prow[f] = mx;
+}
+
+__global__ __launch_bounds__(256) void logmel_spans_finish_kernel(int W, int n_mels, const float* partial, float* out) {
+  __shared__ float wmax[4];
+  const int r = blockIdx.y, tid = threadIdx.x;
+  const float lo = logmel_row_max(partial + (long long)r * (W + SP_EXTRA), W + SP_EXTRA, wmax, tid) - 8.0f;
+  const long long total = (long long)W * n_mels;
+  float* ob = out + (long long)r * total;
+  for (long long e = (long long)blockIdx.x * 2048 + tid; e < (long long)(blockIdx.x + 1) * 2048 && e < total; e += 256)
+    ob[e] = logmel_scale(ob[e], lo);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------- attention
@@ -296,6 +414,51 @@ extern "C" int kk_op_mel_windows(void* stream, int R, const float* const* src, c
   }
   const long long total = (long long)W * (n_mels / 4);
   hipLaunchKernelGGL(mel_windows_kernel, dim3((unsigned)((total + 1023) / 1024), R), dim3(256), 0, (hipStream_t)stream, t, W, n_mels, out);
+  KK_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int kk_op_log_mel_spans(void* stream, int R, const float* const* buf, const int64_t* buf_len, const int32_t* ring_len, const int64_t* pos,
+                                   const int32_t* n, int W, int L, int M, const float* tab, int T, int n_mels, const float* window, const float* cos_sin,
+                                   const float* fbT, float* partial, float* out) {
+  const char* who = "kk_op_log_mel_spans";
+  if (!buf || !buf_len || !ring_len || !pos || !n || !window || !cos_sin || !fbT || !partial || !out) return kk_failf("%s: null argument", who);
+  if (R < 1 || R > KK_WHISPER_MAX_ROWS) return kk_failf("%s: R = %d is outside [1, %d]", who, R, KK_WHISPER_MAX_ROWS);
+  if (W < 3 || W > (1 << 20)) return kk_failf("%s: W = %d is outside [3, 2^20]", who, W);
+  if (n_mels != 80 && n_mels != 128) return kk_failf("%s: n_mels must be 80 or 128", who);
+  if (L < 1 || M < 1) return kk_failf("%s: L = %d, M = %d: both must be >= 1", who, L, M);
+  int half = 0;
+  if (L == M) {
+    L = M = 1, T = 0;
+  } else {
+    half = 10 * (L > M ? L : M);
+    if (!tab || T != (2 * half + L) / L) return kk_failf("%s: T = %d, the taps of %d / %d are [%d][%d]", who, T, L, M, L, (2 * half + L) / L);
+    if ((long long)L * (T | 1) > SP_TAB || ((long long)(NFFT - 1) * M) / L + T + 2 > SP_WIN)
+      return kk_failf("%s: the ratio %d / %d is not served: its phase table or a frame's source samples do not fit the workgroup's LDS", who, L, M);
+  }
+  KKMelSpans t;
+  memset(&t, 0, sizeof t);
+  for (int r = 0; r < R; ++r) {
+    if (!buf[r]) return kk_failf("%s: row %d: null buffer", who, r);
+    if (n[r] < 1) return kk_failf("%s: row %d: n = %d must be >= 1", who, r, n[r]);
+    const long long n16 = ((long long)n[r] * L + M - 1) / M;
+    if (n16 > (long long)W * HOP) return kk_failf("%s: row %d: %d samples are %lld at 16 kHz, a window holds %lld", who, r, n[r], n16, (long long)W * HOP);
+    if (pos[r] < 0) return kk_failf("%s: row %d: a negative position", who, r);
+    if (ring_len[r] < 0) return kk_failf("%s: row %d: a negative ring length", who, r);
+    if (ring_len[r] ? (n[r] > ring_len[r] || buf_len[r] < ring_len[r]) : (pos[r] + n[r] > buf_len[r]))
+      return kk_failf("%s: row %d: the span [%lld, + %d) does not lie in its buffer of %lld (ring %d)", who, r, (long long)pos[r], n[r], (long long)buf_len[r],
+                      ring_len[r]);
+    t.buf[r] = buf[r];
+    t.pos[r] = pos[r];
+    t.ring_len[r] = ring_len[r];
+    t.n[r] = n[r];
+    t.n16[r] = (int)n16;
+  }
+  hipLaunchKernelGGL(logmel_spans_kernel, dim3(W + SP_EXTRA, R), dim3(256), 0, (hipStream_t)stream, t, W, L, M, half, T, tab, n_mels, window, cos_sin, fbT,
+                     partial, out);
+  KK_CHECK_LAUNCH();
+  const long long total = (long long)W * n_mels;
+  hipLaunchKernelGGL(logmel_spans_finish_kernel, dim3((unsigned)((total + 2047) / 2048), R), dim3(256), 0, (hipStream_t)stream, W, n_mels, partial, out);
   KK_CHECK_LAUNCH();
   return 0;
 }

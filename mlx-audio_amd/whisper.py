@@ -13,6 +13,9 @@ Token timestamps (`Model.alignment_heads`, `set_alignment_heads`, `forward_with_
 `TokenTiming`, `WordTiming` of whisper_timing.py, re-exported here) run on kk_op_whisper_qk_rows / align_matrix / dtw and kk_whisper_text_forward_qk
 (csrc/kk_whisper_align.hip).
 
+`span_windows(spans, W, n_mels, src_rate)` (kk_op_log_mel_spans) turns spans of sample buffers at another rate -- flat, or rings at 64-bit stream
+positions -- into windows in one launch pair, bit-equal to `resample`, `log_mel_spectrogram` and `mel_windows` in turn: how a CSM listener's utterance gets here.
+
 `Model.serve(...)` returns a `whisper_serve.WhisperBatcher`: windows with their own options join and leave one running decoder batch (the row mode of the
 text handle, kk_whisper_text_rows_*), each with the result `decode` gives it alone."""
 from __future__ import annotations
@@ -24,7 +27,7 @@ import json
 import math
 from dataclasses import dataclass, fields
 from pathlib import Path
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import numpy as np
 
@@ -206,6 +209,102 @@ def mel_windows(mels, seeks, sizes, W: int):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(lib.kk_op_mel_windows(st, R, src, arr([m.shape[0] for m in mels]), arr(seeks), arr(sizes), W, n_mels, C.c_void_p(out.data_ptr())),
                    "kk_op_mel_windows")
+    return out
+
+
+class Span(NamedTuple):
+    """A row of `span_windows`: `n` >= 1 samples of the 1-D fp32 device tensor `buf`, from element `start` on when `ring_len` is 0, else samples
+    (start + i) % ring_len of a ring (`ring.py`; `start` is a 64-bit stream position)."""
+    buf: object
+    ring_len: int
+    start: int
+    n: int
+
+
+SPAN_LDS_WINDOW, SPAN_LDS_TABLE = 1536, 512  # floats of a frame's source samples and of the phase table that kk_op_log_mel_spans keeps in LDS
+
+_span_tabs: Dict[tuple, object] = {}
+
+
+def span_ratio(src_rate: int):
+    """(L, M) of `src_rate` -> 16 kHz, or ValueError naming a ratio that `span_windows` does not serve (`resample.ratio`'s bound, and a frame's
+    source samples and phase table must fit the kernel's LDS: 8, 12, 16, 24, 32 and 48 kHz do)."""
+    from . import resample as RS
+
+    L, M = RS.ratio(src_rate, SAMPLE_RATE)
+    if L != M:
+        T = RS.taps_per_output(L, M)
+        if L * (T | 1) > SPAN_LDS_TABLE or (N_FFT - 1) * M // L + T + 2 > SPAN_LDS_WINDOW:
+            raise ValueError(f"span_windows: {src_rate} -> {SAMPLE_RATE} Hz is {L} / {M}: a frame of that ratio does not fit the kernel's LDS "
+                             f"(phase table {L * (T | 1)} of {SPAN_LDS_TABLE} floats, source samples {(N_FFT - 1) * M // L + T + 2} of {SPAN_LDS_WINDOW})")
+    return L, M
+
+
+def span_len16(n: int, L: int, M: int) -> int:
+    """16 kHz samples of an n-sample span: `resample.out_len`."""
+    return -(-int(n) * int(L) // int(M))
+
+
+def check_spans(spans, W: int, src_rate: int = 24000):
+    """The host checks of `span_windows` without a device: -> (L, M).  ValueError names the row whose span is longer than one window."""
+    L, M = span_ratio(src_rate)
+    if W < 3:
+        raise ValueError("W must be >= 3")
+    for r, sp in enumerate(spans):
+        ring_len, start, n = int(sp[1]), int(sp[2]), int(sp[3])
+        if n < 1 or start < 0 or ring_len < 0 or (ring_len and n > ring_len):
+            raise ValueError(f"span_windows: row {r}: span [{start}, + {n}) of ring {ring_len}")
+        if span_len16(n, L, M) > W * HOP_LENGTH:
+            raise ValueError(f"span_windows: row {r}: {n} samples at {src_rate} Hz are {span_len16(n, L, M)} at 16 kHz, more than the "
+                             f"{W * HOP_LENGTH} of a window of {W} frames")
+    return L, M
+
+
+def span_windows(spans, W: int, n_mels: int = 80, src_rate: int = 24000):
+    """Utterances that lie on the device become Whisper windows in ONE launch pair (kk_op_log_mel_spans).  spans: 1 ..
+    WHISPER_MAX_ROWS `Span`s (or such tuples) at `src_rate`; the rows may name different allocations or the same one.  Row r is, bit for bit,
+    `mel_windows([log_mel_spectrogram(resample.resample(x, src_rate, 16000), n_mels, padding=W * 160)], [0], [W], W)[0]` for the span's samples
+    x; what lies outside a span is never read.  -> fp32 device (R, W, n_mels).  ValueError for a span longer than a window (it names the row)
+    and for a ratio that is not served (`span_ratio`)."""
+    import torch
+
+    from . import _lib
+    from . import resample as RS
+
+    if n_mels not in (80, 128):
+        raise ValueError("n_mels must be 80 or 128")
+    spans = [Span(*sp) for sp in spans]
+    R = len(spans)
+    if not 1 <= R <= _lib.WHISPER_MAX_ROWS:
+        raise ValueError(f"span_windows takes 1 .. {_lib.WHISPER_MAX_ROWS} spans")
+    L, M = check_spans(spans, W, src_rate)
+    dev = spans[0].buf.device
+    for r, sp in enumerate(spans):
+        b = sp.buf
+        if not _is_torch(b) or not b.is_cuda or b.dtype != torch.float32 or b.ndim != 1 or not b.is_contiguous() or b.device != dev:
+            raise ValueError("span_windows: every buffer must be a contiguous 1-D fp32 tensor on one device")
+        if (sp.ring_len > b.shape[0]) if sp.ring_len else (sp.start + sp.n > b.shape[0]):
+            raise ValueError(f"span_windows: row {r}: span [{sp.start}, + {sp.n}) of ring {sp.ring_len} does not lie in its buffer of {b.shape[0]}")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        window, cs, fbT = _logmel_tables(dev, n_mels)
+        tab, T = None, 0
+        if L != M:
+            key = (str(dev), L, M)
+            if key not in _span_tabs:
+                _span_tabs[key] = torch.from_numpy(np.array(RS.phase_table(L, M))).to(dev)
+            tab = _span_tabs[key]
+            T = int(tab.shape[1])
+        partial = torch.empty((R, W + 2), dtype=torch.float32, device=dev)
+        out = torch.empty((R, W, n_mels), dtype=torch.float32, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        i32 = lambda v: (C.c_int32 * R)(*[int(x) for x in v])  # noqa: E731
+        i64 = lambda v: (C.c_int64 * R)(*[int(x) for x in v])  # noqa: E731
+        _lib.check(lib.kk_op_log_mel_spans(st, R, (C.c_void_p * R)(*[sp.buf.data_ptr() for sp in spans]), i64([sp.buf.shape[0] for sp in spans]),
+                                           i32([sp.ring_len for sp in spans]), i64([sp.start for sp in spans]), i32([sp.n for sp in spans]), W, L, M,
+                                           C.c_void_p(tab.data_ptr() if tab is not None else None), T, n_mels, C.c_void_p(window.data_ptr()),
+                                           C.c_void_p(cs.data_ptr()), C.c_void_p(fbT.data_ptr()), C.c_void_p(partial.data_ptr()),
+                                           C.c_void_p(out.data_ptr())), "kk_op_log_mel_spans")
     return out
 
 

@@ -90,6 +90,11 @@ class ModelEngine:
         if tuple(x.shape) not in ((d.n_audio_ctx, d.n_audio_state), (2 * d.n_audio_ctx, d.n_mels)):
             raise ValueError(f"expected a mel ({2 * d.n_audio_ctx}, {d.n_mels}) or audio features ({d.n_audio_ctx}, {d.n_audio_state})")
 
+    def embed_audio(self, mel):
+        """Windows (R, 2 n_audio_ctx, n_mels) -> their audio features (R, n_audio_ctx, n_audio_state) in ONE encoder call; a row has the bits of
+        its own B = 1 call"""
+        return self.model.embed_audio(mel)
+
     def open(self, max_rows: int) -> None:
         from .whisper_decoding import RowRuntime
 
@@ -218,6 +223,7 @@ class WhisperBatcher:
         self._round = threading.RLock()     # one round at a time
         self._thread: Optional[threading.Thread] = None
         self.closed = False
+        self.on_submit = None  # a scheduler that steps this batcher itself (csm_serve.CSMBatcher(stt=...)) is told of every new request
 
     # ---- submitting (any thread) ---------------------------------------------------------------------------------------------------------
     def submit(self, mel_or_features, options: DecodingOptions = DecodingOptions(), **overrides) -> Future:
@@ -294,6 +300,9 @@ class WhisperBatcher:
                 raise RuntimeError("WhisperBatcher is closed")
             self._queue.append(req)
             self._wake.notify_all()
+            poke = self.on_submit
+        if poke is not None:
+            poke()
         return req.future
 
     # ---- one round -------------------------------------------------------------------------------------------------------------------------
