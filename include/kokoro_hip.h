@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 27  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 28  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -76,7 +76,9 @@ extern "C" {
                                kk_whisper_text_rows_groups_bind, kk_whisper_text_rows_admit_group, kk_whisper_text_rows_group_read,
                                kk_whisper_text_rows_group_release, kk_whisper_text_rows_group_offers, KK_WHISPER_GROUP_PLAIN / _BEAM);
                             27: a listener's utterance becomes a Whisper window: spans of sample buffers, resampled and log-mel'ed in one launch pair
-                               (kk_op_log_mel_spans) */
+                               (kk_op_log_mel_spans);
+                            28: the SNAC codec and its kernels on their own (kk_snac_*, kk_op_snac_dw_conv, kk_op_snac_residual_unit,
+                               kk_op_snac_from_codes, kk_op_snac_vq_search, kk_op_snac_conv_cout1) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -442,6 +444,78 @@ int kk_op_mimi_rvq_argmin(void* stream, int B, const float* dots, const float* c
  * The table ops need table_dev (nbuf * 32 bytes, device), active and pos; they upload the table to table_dev after synchronising `stream`. */
 int kk_op_mimi_carry(void* stream, int op, int B, int nbuf, float* const* bufs, const int* S, const int* n, const int* C, const long long* pitch,
                      void* table_dev, int32_t* active, int32_t* pos, int F, int pos_step, int row, unsigned long long mask);
+
+/* =====================================================================================================================
+ * SNAC codec (ABI minor 28): mlx_audio/codec/models/snac/{snac,layers,vq}.py, the tokeniser / vocoder of the reference's Llama
+ * TTS family.  Same conventions: device pointers, caller-owned buffers, work enqueued on `stream`, 0 = OK.  The reference's port is
+ * restated as written: transposed convs without output padding (an odd stride s turns L rows into L s - 1), NoiseBlock noise of shape
+ * [B][1][C] (one normal per item and channel), a no-op residual crop, snake(x) = x + sin^2(alpha x) / (alpha + 1e-9).
+ * ===================================================================================================================== */
+typedef struct kk_snac kk_snac;
+
+/* SNAC.__init__ (snac.py:16-65).  snac_24khz: encoder_dim 48, encoder_rates {2,4,8,8}, latent_dim 768, decoder_dim 1024, decoder_rates
+ * {8,8,4,2}, codebook_size 4096, codebook_dim 8, vq_strides {4,2,1}, noise 1, depthwise 1, attn_window_size 0 (None).
+ * A non-zero attn_window_size (LocalMHA) and depthwise 0 are refused by kk_snac_create. */
+typedef struct kk_snac_config {
+  int32_t sampling_rate, encoder_dim, n_encoder_rates, encoder_rates[8], latent_dim, decoder_dim, n_decoder_rates, decoder_rates[8];
+  int32_t attn_window_size, codebook_size, codebook_dim, n_vq, vq_strides[8], noise, depthwise;
+  int32_t compute_dtype; /* of DECODE: KK_DTYPE_F32 (parity path) or KK_DTYPE_BF16 (bf16 activations, matrix-core dense convs); encode is always fp32 */
+} kk_snac_config;
+
+int kk_snac_create(const kk_snac_config* cfg, kk_snac** out);
+void kk_snac_destroy(kk_snac* m);
+/* parameters by the reference's names and layouts, host fp32: WNConv1d weight_g [O][1][1] / weight_v [O][K][I / groups] / bias [O],
+ * WNConvTranspose1d weight_g [I][1][1] / weight_v [I][K][O], Snake alpha [1][C][1], codebook.weight [bins][dim] */
+int kk_snac_load_tensor(kk_snac* m, const char* name, const int64_t* shape, int ndim, const float* data);
+/* folds weight norm (g v / |v| over the axes except 0, float64), L2-normalises the code books for the search, makes the from_codes tables
+ * out_proj(codebook) [bins][latent_dim] and the summed out_proj biases, packs and uploads.  Fails with the name of a missing parameter. */
+int kk_snac_finalize(kk_snac* m, void* stream);
+int64_t kk_snac_hop_length(const kk_snac* m);          /* prod(encoder_rates): 512 for snac_24khz */
+int64_t kk_snac_decode_samples(const kk_snac* m, int T); /* samples per item of a decode of T latent frames (the chain of transposed-conv lengths) */
+size_t kk_snac_decode_workspace_bytes(kk_snac* m, int B, int T);
+/* SNAC.decode (snac.py:101-104).  codes: HOST array of n_vq device pointers, codes[i] int32 [B][T / vq_strides[i]] (clamped into range); T must be a
+ * multiple of every stride.  noise: HOST array of one device pointer per decoder block, noise[l] fp32 [B][C_l] with C_l = decoder_dim >> (l + 1);
+ * required when the model has NoiseBlocks, ignored otherwise.  pcm_out fp32 [B][kk_snac_decode_samples].  An item's samples do not depend on B
+ * or on its place in the batch. */
+int kk_snac_decode(kk_snac* m, void* stream, int B, int T, const int32_t* const* codes, const float* const* noise, void* workspace,
+                   size_t workspace_bytes, float* pcm_out);
+/* SNAC.encode (snac.py:95-99) after preprocess: pcm fp32 [B][N] -> codes_out (HOST array of n_vq device pointers) int32 [B][T / vq_strides[i]],
+ * T = kk_snac_encode_frames.  Always fp32.  N must give a T that is a multiple of every stride (the caller pads as SNAC.preprocess does). */
+int kk_snac_encode_frames(const kk_snac* m, int N);
+size_t kk_snac_encode_workspace_bytes(kk_snac* m, int B, int N);
+int kk_snac_encode(kk_snac* m, void* stream, int B, int N, const float* pcm, void* workspace, size_t workspace_bytes, int32_t* const* codes_out);
+/* intermediates of the last decode / encode (tests), [B][rows][channels] fp32: "z_q", "block0" .. (decode); "encoder", "residual0" .. (the
+ * residual after quantiser i) (encode) */
+int kk_snac_debug_info(kk_snac* m, const char* name, int64_t* rows, int64_t* channels);
+int kk_snac_debug_fetch(kk_snac* m, void* stream, const char* name, float* dst);
+
+/* ---- the codec's kernels on their own (single-kernel entry points as above; these call the launch functions the codec calls).  Tensors are
+ * frames-major [B][rows][ld]; dtypes are KK_DTYPE_F32 / KK_DTYPE_BF16 with fp32 arithmetic; pitches count elements. */
+enum { KK_SNAC_UNIT_GENERIC = 0, KK_SNAC_UNIT_MFMA = 1 }; /* *path_out of kk_op_snac_residual_unit: the kernel of its 1x1 conv */
+/* depth-wise dilated conv, 7 taps, pad 3 dil, 1 <= dil <= 9, a Snake on either side when its alpha [C] is given:
+ * out[t][c] = snake_out?(sum_k w[c][k] snake_in?(x[t - 3 dil + k dil][c]) + bias[c]); rows outside [0, L) are zeros and are never read.
+ * w [C][7], bias [C] fp32.  Columns [C, ldo) of out are not written. */
+int kk_op_snac_dw_conv(void* stream, int B, const void* x, long long xbs, int ldx, int dtype, int L, int C, int dil, const float* w, const float* bias,
+                       const float* alpha_in, const float* alpha_out, void* out, long long obs, int ldo);
+/* ResidualUnit (layers.py:208-231): out = x + W snake(dw7(snake(x))) + b on dense items x [B][L][ldx], out [B][L][ldo]; tmp [B][L][ldx] holds the
+ * depth-wise result between the two launches.  pw_packed [1][C][ldw] fp32; pw_frag (optional): the bf16 fragment pack [1][CoutP][CinP]
+ * (kk_op_pack_w_frag), used for bf16 tensors with an eligible shape (C % 8 == 0, C >= 16), pw_bias then has CoutP entries. */
+int kk_op_snac_residual_unit(void* stream, int B, const void* x, int ldx, int dtype, int L, int C, int dil, const float* dw_w, const float* dw_b,
+                             const float* alpha1, const float* alpha2, const float* pw_packed, int ldw, const void* pw_frag, int CinP, int CoutP,
+                             const float* pw_bias, void* tmp, void* out, int ldo, int* path_out);
+/* from_codes (vq.py:109-129): out[b][t][c] = sum_i tables[i][codes[i][b][t / strides[i]]][c] + bias_sum[c], quantisers in ascending order in fp32,
+ * codes clamped into [0, bins).  codes, strides, tables: HOST arrays of nq <= 8 entries (device pointers / ints); tables[i] fp32 [bins][D]. */
+int kk_op_snac_from_codes(void* stream, int B, int T, int D, int nq, const int32_t* const* codes, const int32_t* strides, const float* const* tables,
+                          int bins, const float* bias_sum, void* out, int ldo, int dtype);
+/* decode_latents (vq.py:62-77) + the straight-through line: e = ze / max(|ze|, 1e-12), dist_j = |e|^2 - 2 e . codebook_n[j] + c2[j] in fp32,
+ * codes[b][t] = the first index of the smallest distance, zq[b][t] = ze + (codebook[code] - ze).  ze [B][T][ldz], codebook / codebook_n
+ * [bins][cd] (cd <= 64), c2 [bins], zq [B][T][ldq]; all fp32. */
+int kk_op_snac_vq_search(void* stream, int B, int T, const float* ze, int ldz, int cd, const float* codebook, const float* codebook_n, const float* c2,
+                         int bins, int32_t* codes, float* zq, int ldq);
+/* the decoder's last conv, Cout = 1: out[b][t] = tanh?(sum_k sum_c snake?(x[b][t - pad + k][c]) w_packed[(k Cin + c) ldw] + bias[0]); rows outside
+ * [0, L) are zeros; x [B][L][ld] dense, out [B][L] fp32; Kw <= 16; alpha [Cin] or null (no Snake); bias may be null. */
+int kk_op_snac_conv_cout1(void* stream, int B, const void* x, int dtype, int ld, int L, int Cin, int Kw, int pad, const float* w_packed, int ldw,
+                          const float* bias, const float* alpha, int tanh_out, float* out);
 
 /* =====================================================================================================================
  * Row-mode polyphase FIR resampler (ABI minor 10): the sample-rate edge of CSM serving.  The reference resamples whole clips

@@ -40,6 +40,15 @@ class KKMimiConfig(C.Structure):
     ]
 
 
+class KKSnacConfig(C.Structure):  # kk_snac_config
+    _fields_ = [
+        ("sampling_rate", C.c_int32), ("encoder_dim", C.c_int32), ("n_encoder_rates", C.c_int32), ("encoder_rates", C.c_int32 * 8),
+        ("latent_dim", C.c_int32), ("decoder_dim", C.c_int32), ("n_decoder_rates", C.c_int32), ("decoder_rates", C.c_int32 * 8),
+        ("attn_window_size", C.c_int32), ("codebook_size", C.c_int32), ("codebook_dim", C.c_int32), ("n_vq", C.c_int32),
+        ("vq_strides", C.c_int32 * 8), ("noise", C.c_int32), ("depthwise", C.c_int32), ("compute_dtype", C.c_int32),
+    ]
+
+
 class KKWhisperConfig(C.Structure):
     _fields_ = [("n_mels", C.c_int32), ("n_audio_ctx", C.c_int32), ("n_audio_state", C.c_int32), ("n_audio_head", C.c_int32),
                 ("n_audio_layer", C.c_int32)]
@@ -315,6 +324,24 @@ SIGNATURES = {
     "kk_op_whisper_dtw": (_i, [_vp, _i, _vp, C.c_longlong, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz]),
     "kk_whisper_text_qk_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "kk_whisper_text_forward_qk": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz]),
+    "kk_snac_create": (_i, [C.POINTER(KKSnacConfig), C.POINTER(_vp)]),
+    "kk_snac_destroy": (None, [_vp]),
+    "kk_snac_load_tensor": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), _i, _vp]),
+    "kk_snac_finalize": (_i, [_vp, _vp]),
+    "kk_snac_hop_length": (C.c_int64, [_vp]),
+    "kk_snac_decode_samples": (C.c_int64, [_vp, _i]),
+    "kk_snac_decode_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "kk_snac_decode": (_i, [_vp, _vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _vp, _sz, _vp]),
+    "kk_snac_encode_frames": (_i, [_vp, _i]),
+    "kk_snac_encode_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "kk_snac_encode": (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, C.POINTER(_vp)]),
+    "kk_snac_debug_info": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "kk_snac_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
+    "kk_op_snac_dw_conv": (_i, [_vp, _i, _vp, C.c_longlong, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _i]),
+    "kk_op_snac_residual_unit": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, C.POINTER(C.c_int)]),
+    "kk_op_snac_from_codes": (_i, [_vp, _i, _i, _i, _i, C.POINTER(_vp), C.POINTER(C.c_int32), C.POINTER(_vp), _i, _vp, _vp, _i, _i]),
+    "kk_op_snac_vq_search": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i]),
+    "kk_op_snac_conv_cout1": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp]),
     "kk_mimi_debug_info": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "kk_mimi_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
     "kk_debug_set_op_wfrag": (None, [_vp]),
@@ -363,7 +390,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 27:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 28:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib
