@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 28  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 29  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -78,7 +78,11 @@ extern "C" {
                             27: a listener's utterance becomes a Whisper window: spans of sample buffers, resampled and log-mel'ed in one launch pair
                                (kk_op_log_mel_spans);
                             28: the SNAC codec and its kernels on their own (kk_snac_*, kk_op_snac_dw_conv, kk_op_snac_residual_unit,
-                               kk_op_snac_from_codes, kk_op_snac_vq_search, kk_op_snac_conv_cout1) */
+                               kk_op_snac_from_codes, kk_op_snac_vq_search, kk_op_snac_conv_cout1);
+                            29: the Kokoro forward's glue kernels, the Albert embedding and the ragged source / STFT on caller-owned buffers
+                               (kk_op_kokoro_style_fc, kk_op_kokoro_fill_style, kk_op_kokoro_embedding, kk_op_kokoro_duration, kk_op_kokoro_alignment,
+                               kk_op_kokoro_gather_rows, kk_op_kokoro_copy_slice, kk_op_kokoro_lens, kk_op_kokoro_convert, kk_op_albert_embed,
+                               kk_op_source_stft_ragged) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -245,6 +249,47 @@ int kk_op_attention(void* stream, int B, const void* qkv, int ld, int T_rows, co
 int kk_op_source_stft(void* stream, int B, const float* f0, int L2_rows, const int32_t* len2, const float* lin_w9, float lin_b,
                       int noise_mode, const float* noise, uint64_t seed, float* phase_scratch, float* har_source, void* har, int ldhar,
                       int dtype);
+/* The same two launches with ragged lengths (tests): len2 [B] valid F0 entries (<= L2_rows) and lenN [B] valid samples (<= 300 * L2_rows) are
+ * DEVICE pointers, each nullable (NULL = all of them).  The forward passes lenN = 300 * len2; here it is free, so the STFT's reflect padding can meet
+ * an edge at any sample.  phase_scratch fp32 [B][9][L2_rows], har_source fp32 [B][300 * L2_rows] (zero from 300 * len2 on), har [B][60 * L2_rows + 1]
+ * [ldhar >= 22]: magnitude at 0..10, angle at 11..21, rows from lenN / 5 + 1 on (all rows when lenN is 0) zero.  A signal shorter than the padding
+ * (0 < lenN < 11), which the reference refuses, is folded back into range as numpy's reflect mode does. */
+int kk_op_source_stft_ragged(void* stream, int B, const float* f0, int L2_rows, const int32_t* len2, const int32_t* lenN, const float* lin_w9,
+                             float lin_b, int noise_mode, const float* noise, uint64_t seed, float* phase_scratch, float* har_source, void* har,
+                             int ldhar, int dtype);
+/* The glue kernels of the Kokoro forward (csrc/kk_misc.hip) and the Albert embedding on caller-owned buffers (tests).  Every entry makes the call
+ * kk_forward makes.  Tensors are [B][rows][ld] with item pitch rows * ld; `len` [B] is a DEVICE pointer to the valid rows per item, NULL = all rows;
+ * dtype is KK_DTYPE_F32 or KK_DTYPE_BF16 and names the element type of the void* tensors.  Refused before any launch: a null tensor, B or a row /
+ * channel count < 1, a pitch smaller than the channels it must hold.
+ *   style_fc     out[b][o] = sum_j wT[j][o] ref_s[b][soff + j] + bias[o], j < 128, o < N; ref_s fp32 [B][256], wT fp32 [128][N], soff in [0, 128]
+ *   fill_style   out[b][t][coff + j] = ref_s[b][soff + j] for t < len[b], else 0; j < S, soff + S <= 256; other columns untouched
+ *   embedding    out[b][t][c] = table[ids[b][t]][c] for t < len[b], else 0; ids int32 [B][T_rows] (not read past len), table fp32 [*][C]
+ *   duration     d = sum_{o < nout} sigmoid(x[b][t][:Cin] . W[:, o] + bias[o]) / speed[b]; dur_f = d (nullable), dur = max(1, rint(d)) with ties to
+ *                even; both 0 for t >= len[b].  W fp32 [Cin][nout], speed fp32 [B], dur int32 [B][T_rows]
+ *   alignment    frame_idx[b][f] = the token t whose frames [sum_{u < t} max(dur_u, 0), + max(dur_t, 0)) hold f, over t < lenT[b]; lenF[b] =
+ *                min(sum, F_rows); frame_idx is 0 from lenF[b] on.  lenT is required (DEVICE, [B]); T_rows > 512 is refused
+ *   gather_rows  out[b][f][coff + c] = in[b][frame_idx[b][f]][c] for f < lenF[b], else 0; c < C; in [B][T_rows][ldi]; lenF is required
+ *   copy_slice   out[b][l][coff + c] = in[b][l][c] for l < len[b], else 0
+ *   lens         lens_out [4][B] = 2 F, 2 F up0, 2 F up0 up1 + 1 (0 when F = 0), 2 F up0 up1 hop, F = lenF[b] (required)
+ *   convert      dst[b][r][c] = (dst type) src[b][r][c]: fp32 -> fp32, fp32 -> bf16 (round to nearest even), bf16 -> fp32; bf16 -> bf16 is refused
+ *   albert_embed out[b][t][:E] = LayerNorm_eps(word[ids[b][t]] + pos[t] + type[0 row]) * ln_w + ln_b (modules.py:451-465) for t < len[b], else 0;
+ *                tables fp32 [*][E]; E > 512 is refused */
+int kk_op_kokoro_style_fc(void* stream, int B, const float* ref_s, int soff, const float* wT, const float* bias, float* out, int N);
+int kk_op_kokoro_fill_style(void* stream, int B, const float* ref_s, int soff, void* out, int ldo, int coff, int S, int L_rows, const int32_t* len,
+                            int dtype);
+int kk_op_kokoro_embedding(void* stream, int B, const int32_t* ids, const float* table, void* out, int ldo, int C, int T_rows, const int32_t* len,
+                           int dtype);
+int kk_op_kokoro_duration(void* stream, int B, const void* x, int ldx, const float* W, const float* bias, int Cin, int nout, const float* speed,
+                          int32_t* dur, float* dur_f, int T_rows, const int32_t* len, int dtype);
+int kk_op_kokoro_alignment(void* stream, int B, const int32_t* dur, int T_rows, const int32_t* lenT, int32_t* frame_idx, int32_t* lenF, int F_rows);
+int kk_op_kokoro_gather_rows(void* stream, int B, const void* in, int ldi, int T_rows, const int32_t* frame_idx, int F_rows, const int32_t* lenF,
+                             void* out, int ldo, int coff, int C, int dtype);
+int kk_op_kokoro_copy_slice(void* stream, int B, const void* in, int ldi, void* out, int ldo, int coff, int C, int L_rows, const int32_t* len,
+                            int dtype);
+int kk_op_kokoro_lens(void* stream, int B, const int32_t* lenF, int32_t* lens_out, int up0, int up1, int hop);
+int kk_op_kokoro_convert(void* stream, int B, const void* src, int src_dtype, int lds, void* dst, int dst_dtype, int ldd, int C, int rows);
+int kk_op_albert_embed(void* stream, int B, const int32_t* ids, const float* word, const float* pos, const float* type, const float* ln_w,
+                       const float* ln_b, float eps, void* out, int ldo, int E, int T_rows, const int32_t* len, int dtype);
 /* exp/sin + MLXSTFT.inverse + istft  --  istftnet.py:804-806,497-523; mlx_audio/utils.py:104-158 */
 int kk_op_istft_head(void* stream, int B, const void* x, int ldx, int Tf_rows, const int32_t* len_frames, float* wav, int dtype, int fast);
 /* The fused vocoder head of the bf16 mode: LeakyReLU(in_slope) -> conv_post (128 -> 22 channels, k = 7, pad 3) -> exp / sin -> inverse STFT ->

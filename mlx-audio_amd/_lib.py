@@ -139,6 +139,17 @@ SIGNATURES = {
     "kk_op_linear_rows": (_i, [_vp, _i, _vp, C.c_longlong, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, C.c_longlong, _i]),
     "kk_op_attention": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _i]),
     "kk_op_source_stft": (_i, [_vp, _i, _vp, _i, _vp, _vp, _f, _i, _vp, _u64, _vp, _vp, _vp, _i, _i]),
+    "kk_op_source_stft_ragged": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _f, _i, _vp, _u64, _vp, _vp, _vp, _i, _i]),
+    "kk_op_kokoro_style_fc": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i]),
+    "kk_op_kokoro_fill_style": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i]),
+    "kk_op_kokoro_embedding": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i]),
+    "kk_op_kokoro_duration": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i]),
+    "kk_op_kokoro_alignment": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i]),
+    "kk_op_kokoro_gather_rows": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i]),
+    "kk_op_kokoro_copy_slice": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i]),
+    "kk_op_kokoro_lens": (_i, [_vp, _i, _vp, _vp, _i, _i, _i]),
+    "kk_op_kokoro_convert": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i]),
+    "kk_op_albert_embed": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp, _i]),
     "kk_op_istft_head": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i]),
     "kk_op_pack_head_w": (_i, [_vp, _vp, _vp]),
     "kk_op_conv_post_istft": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _i]),
@@ -390,7 +401,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 28:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 29:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -1883,6 +1883,96 @@ extern "C" int kk_op_source_stft(void* stream, int B, const float* f0, int L2_ro
   return kk_launch_stft20(har_source, sa.Nmax, nullptr, har, (long long)Tf * ldhar, ldhar, Tf, B, dtype, (hipStream_t)stream);
 }
 
+// the ragged form (tests): len2 [B] valid F0 entries and lenN [B] valid samples, both device pointers and each nullable (NULL = every row / sample);
+// lenN is what the forward derives as 300 * len2 and is free here so that the reflect padding meets a ragged edge at any sample
+extern "C" int kk_op_source_stft_ragged(void* stream, int B, const float* f0, int L2_rows, const int32_t* len2, const int32_t* lenN,
+                                        const float* lin_w9, float lin_b, int noise_mode, const float* noise, uint64_t seed,
+                                        float* phase_scratch, float* har_source, void* har, int ldhar, int dtype) {
+  if (!f0 || !lin_w9 || !phase_scratch || !har_source || !har) return kk_fail("kk_op_source_stft_ragged: null argument");
+  if (B < 1 || L2_rows < 1 || ldhar < 22) return kk_fail("kk_op_source_stft_ragged: bad argument (need B, L2_rows >= 1 and ldhar >= 22)");
+  if (noise_mode == KK_NOISE_INJECTED && !noise) return kk_fail("kk_op_source_stft_ragged: injected noise needs the noise tensor");
+  KKSourceArgs sa;
+  memset(&sa, 0, sizeof sa);
+  sa.f0 = f0; sa.L2max = L2_rows; sa.len2 = len2; sa.phase = phase_scratch; sa.lin_w = lin_w9; sa.lin_b = lin_b; sa.noise = noise;
+  sa.seed = seed; sa.noise_mode = noise_mode; sa.har_source = har_source; sa.Nmax = 300 * L2_rows; sa.upsample = 300;
+  KK_TRY(kk_launch_source(sa, B, (hipStream_t)stream));
+  const int Tf = 60 * L2_rows + 1;
+  return kk_launch_stft20(har_source, sa.Nmax, lenN, har, (long long)Tf * ldhar, ldhar, Tf, B, dtype, (hipStream_t)stream);
+}
+
+// ---- the glue kernels of the forward (kk_misc.hip) and the Albert embedding on caller-owned buffers (tests): each entry is the call kk_forward makes
+#define KK_OP_LEN(len, rows) KKLen{len, (len) ? 1 : 0, (len) ? 0 : (rows)}
+extern "C" int kk_op_kokoro_style_fc(void* stream, int B, const float* ref_s, int soff, const float* wT, const float* bias, float* out, int N) {
+  if (!ref_s || !wT || !bias || !out) return kk_fail("kk_op_kokoro_style_fc: null argument");
+  if (B < 1 || N < 1 || soff < 0 || soff > 128) return kk_fail("kk_op_kokoro_style_fc: bad argument (need B, N >= 1 and 0 <= soff <= 128)");
+  return kk_launch_style_fc(ref_s, soff, wT, bias, out, N, B, (hipStream_t)stream);
+}
+extern "C" int kk_op_kokoro_fill_style(void* stream, int B, const float* ref_s, int soff, void* out, int ldo, int coff, int S, int L_rows,
+                                       const int32_t* len, int dtype) {
+  if (!ref_s || !out) return kk_fail("kk_op_kokoro_fill_style: null argument");
+  if (B < 1 || L_rows < 1 || S < 1 || soff < 0 || soff + S > 256 || coff < 0 || ldo < coff + S || (dtype != KK_F32 && dtype != KK_BF16))
+    return kk_fail("kk_op_kokoro_fill_style: bad argument");
+  return kk_launch_fill_style(ref_s, soff, out, (long long)L_rows * ldo, ldo, coff, S, L_rows, KK_OP_LEN(len, L_rows), B, dtype, (hipStream_t)stream);
+}
+extern "C" int kk_op_kokoro_embedding(void* stream, int B, const int32_t* ids, const float* table, void* out, int ldo, int C, int T_rows,
+                                      const int32_t* len, int dtype) {
+  if (!ids || !table || !out) return kk_fail("kk_op_kokoro_embedding: null argument");
+  if (B < 1 || T_rows < 1 || C < 1 || ldo < C || (dtype != KK_F32 && dtype != KK_BF16)) return kk_fail("kk_op_kokoro_embedding: bad argument");
+  return kk_launch_embedding(ids, table, out, (long long)T_rows * ldo, ldo, C, T_rows, KK_OP_LEN(len, T_rows), B, dtype, (hipStream_t)stream);
+}
+extern "C" int kk_op_kokoro_duration(void* stream, int B, const void* x, int ldx, const float* W, const float* bias, int Cin, int nout,
+                                     const float* speed, int32_t* dur, float* dur_f, int T_rows, const int32_t* len, int dtype) {
+  if (!x || !W || !bias || !speed || !dur) return kk_fail("kk_op_kokoro_duration: null argument");
+  if (B < 1 || T_rows < 1 || Cin < 1 || nout < 1 || ldx < Cin || (dtype != KK_F32 && dtype != KK_BF16))
+    return kk_fail("kk_op_kokoro_duration: bad argument");
+  return kk_launch_duration(x, (long long)T_rows * ldx, ldx, W, bias, Cin, nout, speed, dur, dur_f, T_rows, KK_OP_LEN(len, T_rows), B, dtype,
+                            (hipStream_t)stream);
+}
+extern "C" int kk_op_kokoro_alignment(void* stream, int B, const int32_t* dur, int T_rows, const int32_t* lenT, int32_t* frame_idx, int32_t* lenF,
+                                      int F_rows) {
+  if (!dur || !lenT || !frame_idx || !lenF) return kk_fail("kk_op_kokoro_alignment: null argument (the kernel reads lenT of every item)");
+  if (B < 1 || T_rows < 1 || F_rows < 1) return kk_fail("kk_op_kokoro_alignment: bad argument");
+  return kk_launch_alignment(dur, T_rows, lenT, frame_idx, lenF, F_rows, B, (hipStream_t)stream);
+}
+extern "C" int kk_op_kokoro_gather_rows(void* stream, int B, const void* in, int ldi, int T_rows, const int32_t* frame_idx, int F_rows,
+                                        const int32_t* lenF, void* out, int ldo, int coff, int C, int dtype) {
+  if (!in || !frame_idx || !lenF || !out) return kk_fail("kk_op_kokoro_gather_rows: null argument (the kernel reads lenF of every item)");
+  if (B < 1 || T_rows < 1 || F_rows < 1 || C < 1 || ldi < C || coff < 0 || ldo < coff + C || (dtype != KK_F32 && dtype != KK_BF16))
+    return kk_fail("kk_op_kokoro_gather_rows: bad argument");
+  return kk_launch_gather_rows(in, (long long)T_rows * ldi, ldi, frame_idx, F_rows, lenF, out, (long long)F_rows * ldo, ldo, coff, C, B, dtype,
+                               (hipStream_t)stream);
+}
+extern "C" int kk_op_kokoro_copy_slice(void* stream, int B, const void* in, int ldi, void* out, int ldo, int coff, int C, int L_rows,
+                                       const int32_t* len, int dtype) {
+  if (!in || !out) return kk_fail("kk_op_kokoro_copy_slice: null argument");
+  if (B < 1 || L_rows < 1 || C < 1 || ldi < C || coff < 0 || ldo < coff + C || (dtype != KK_F32 && dtype != KK_BF16))
+    return kk_fail("kk_op_kokoro_copy_slice: bad argument");
+  return kk_launch_copy_slice(in, (long long)L_rows * ldi, ldi, out, (long long)L_rows * ldo, ldo, coff, C, L_rows, KK_OP_LEN(len, L_rows), B, dtype,
+                              (hipStream_t)stream);
+}
+extern "C" int kk_op_kokoro_lens(void* stream, int B, const int32_t* lenF, int32_t* lens_out, int up0, int up1, int hop) {
+  if (!lenF || !lens_out || B < 1) return kk_fail("kk_op_kokoro_lens: bad argument");
+  return kk_launch_lens(lenF, lens_out, B, up0, up1, hop, (hipStream_t)stream);
+}
+extern "C" int kk_op_kokoro_convert(void* stream, int B, const void* src, int src_dtype, int lds, void* dst, int dst_dtype, int ldd, int C,
+                                    int rows) {
+  if (!src || !dst) return kk_fail("kk_op_kokoro_convert: null argument");
+  if (B < 1 || rows < 1 || C < 1 || lds < C || ldd < C) return kk_fail("kk_op_kokoro_convert: bad argument");
+  return kk_launch_convert(src, src_dtype, (long long)rows * lds, lds, dst, dst_dtype, (long long)rows * ldd, ldd, C, rows, B, (hipStream_t)stream);
+}
+extern "C" int kk_op_albert_embed(void* stream, int B, const int32_t* ids, const float* word, const float* pos, const float* type,
+                                  const float* ln_w, const float* ln_b, float eps, void* out, int ldo, int E, int T_rows, const int32_t* len,
+                                  int dtype) {
+  if (!ids || !word || !pos || !type || !ln_w || !ln_b || !out) return kk_fail("kk_op_albert_embed: null argument");
+  if (B < 1 || T_rows < 1 || E < 1 || ldo < E || (dtype != KK_F32 && dtype != KK_BF16)) return kk_fail("kk_op_albert_embed: bad argument");
+  KKEmbedArgs ea;
+  memset(&ea, 0, sizeof ea);
+  ea.ids = ids; ea.word = word; ea.pos = pos; ea.type = type; ea.ln_w = ln_w; ea.ln_b = ln_b;
+  ea.out = out; ea.obs = (long long)T_rows * ldo; ea.ldo = ldo; ea.E = E; ea.Tmax = T_rows; ea.len = KK_OP_LEN(len, T_rows); ea.eps = eps;
+  return kk_launch_albert_embed(ea, B, dtype, (hipStream_t)stream);
+}
+#undef KK_OP_LEN
+
 extern "C" int kk_op_istft_head(void* stream, int B, const void* x, int ldx, int Tf_rows, const int32_t* len_frames, float* wav, int dtype,
                                 int fast) {
   return kk_launch_istft_head(x, (long long)Tf_rows * ldx, ldx, len_frames, Tf_rows, wav, (long long)5 * (Tf_rows - 1), B, dtype, fast,

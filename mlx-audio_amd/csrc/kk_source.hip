@@ -157,7 +157,11 @@ __global__ __launch_bounds__(256) void stft20_kernel(const float* hs, int Nmax, 
   for (int j = 0; j < 20; ++j) {
     int m = 5 * t + j - 10;
     if (m < 0) m = -m;
-    if (m >= N) m = 2 * (N - 1) - m;
+    if (N < 11) {  // shorter than the padding (the reference refuses such a signal): fold until inside, as numpy's reflect mode does
+      const int p = 2 * (N - 1);
+      m = p ? m % p : 0;
+      if (m >= N) m = p - m;
+    } else if (m >= N) m = 2 * (N - 1) - m;
     fr[j] = x[m] * tb.hann_sym[j];
   }
 #pragma unroll
