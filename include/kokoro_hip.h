@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 29  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 30  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -82,7 +82,8 @@ extern "C" {
                             29: the Kokoro forward's glue kernels, the Albert embedding and the ragged source / STFT on caller-owned buffers
                                (kk_op_kokoro_style_fc, kk_op_kokoro_fill_style, kk_op_kokoro_embedding, kk_op_kokoro_duration, kk_op_kokoro_alignment,
                                kk_op_kokoro_gather_rows, kk_op_kokoro_copy_slice, kk_op_kokoro_lens, kk_op_kokoro_convert, kk_op_albert_embed,
-                               kk_op_source_stft_ragged) */
+                               kk_op_source_stft_ragged);
+                            30: SNAC with LocalMHA, the 32 / 44 kHz checkpoints (kk_snac_create_attn, kk_op_snac_local_attn) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -501,6 +502,8 @@ typedef struct kk_snac kk_snac;
 /* SNAC.__init__ (snac.py:16-65).  snac_24khz: encoder_dim 48, encoder_rates {2,4,8,8}, latent_dim 768, decoder_dim 1024, decoder_rates
  * {8,8,4,2}, codebook_size 4096, codebook_dim 8, vq_strides {4,2,1}, noise 1, depthwise 1, attn_window_size 0 (None).
  * A non-zero attn_window_size (LocalMHA) and depthwise 0 are refused by kk_snac_create. */
+/* snac_44khz (the reference's defaults): encoder_dim 64, encoder_rates {3,3,7,7}, latent_dim 1024, decoder_dim 1536, decoder_rates {7,7,3,3},
+ * vq_strides {8,4,2,1}, attn_window_size 32: kk_snac_create_attn. */
 typedef struct kk_snac_config {
   int32_t sampling_rate, encoder_dim, n_encoder_rates, encoder_rates[8], latent_dim, decoder_dim, n_decoder_rates, decoder_rates[8];
   int32_t attn_window_size, codebook_size, codebook_dim, n_vq, vq_strides[8], noise, depthwise;
@@ -508,6 +511,13 @@ typedef struct kk_snac_config {
 } kk_snac_config;
 
 int kk_snac_create(const kk_snac_config* cfg, kk_snac** out);
+/* (minor 30) as kk_snac_create, and accepts attn_window_size 32: a LocalMHA block (attention.py:6-43; LayerNorm, to_qkv, attention inside windows
+ * of 32 frames with a rotary embedding that restarts in every window, to_out, residual) as encoder.block.layers.{n + 1} (the last depth-wise conv
+ * moves to {n + 2}) and as decoder.model.layers.2 (every later layer moves up by one).  Heads have 64 channels: latent_dim and decoder_dim must be
+ * multiples of 64.  Any other non-zero window is refused with its value.  Parameters per block: .norm.weight [D], .norm.bias [D],
+ * .to_qkv.weight [3 D][D], .to_out.weight [D][D].  decode and encode then need T % 32 == 0.  rotate_half is NOT the reference's as written (its
+ * shapes do not broadcast): rot(u)[c] = -u[c + 32] for c < 32, u[c - 32] otherwise.  Intermediates: "decoder_attn", "encoder_attn" (the block's output). */
+int kk_snac_create_attn(const kk_snac_config* cfg, kk_snac** out);
 void kk_snac_destroy(kk_snac* m);
 /* parameters by the reference's names and layouts, host fp32: WNConv1d weight_g [O][1][1] / weight_v [O][K][I / groups] / bias [O],
  * WNConvTranspose1d weight_g [I][1][1] / weight_v [I][K][O], Snake alpha [1][C][1], codebook.weight [bins][dim] */
@@ -561,6 +571,12 @@ int kk_op_snac_vq_search(void* stream, int B, int T, const float* ze, int ldz, i
  * [0, L) are zeros; x [B][L][ld] dense, out [B][L] fp32; Kw <= 16; alpha [Cin] or null (no Snake); bias may be null. */
 int kk_op_snac_conv_cout1(void* stream, int B, const void* x, int dtype, int ld, int L, int Cin, int Kw, int pad, const float* w_packed, int ldw,
                           const float* bias, const float* alpha, int tanh_out, float* out);
+/* (minor 30) LocalMHA between its two Linears: qkv [B][T][ld] holds q | k | v, 64 H channels each, head h in channels [64 h, 64 h + 64) of its part;
+ * per window of 32 frames and head: u' = u cos + rot(u) sin on q and k with angle(i, c) = i 10000^(-2 (c mod 32) / 64), i the frame's place in its
+ * window; out = softmax(q' k'^T / 8) v over the window's 32 keys, heads concatenated, [B][T][ldo].  T % 32 == 0, ld >= 192 H, ldo >= 64 H; pitches
+ * are multiples of 4 (fp32) / 8 (bf16) elements, pointers 16-byte aligned.  fp32: fp32 operands and accumulation; bf16: bf16 matrix operands, fp32
+ * softmax and accumulation.  A frame's output depends on its own window alone. */
+int kk_op_snac_local_attn(void* stream, int B, int T, int H, const void* qkv, int ld, int dtype, void* out, int ldo);
 
 /* =====================================================================================================================
  * Row-mode polyphase FIR resampler (ABI minor 10): the sample-rate edge of CSM serving.  The reference resamples whole clips

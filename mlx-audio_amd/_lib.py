@@ -336,6 +336,7 @@ SIGNATURES = {
     "kk_whisper_text_qk_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "kk_whisper_text_forward_qk": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz]),
     "kk_snac_create": (_i, [C.POINTER(KKSnacConfig), C.POINTER(_vp)]),
+    "kk_snac_create_attn": (_i, [C.POINTER(KKSnacConfig), C.POINTER(_vp)]),
     "kk_snac_destroy": (None, [_vp]),
     "kk_snac_load_tensor": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), _i, _vp]),
     "kk_snac_finalize": (_i, [_vp, _vp]),
@@ -353,6 +354,7 @@ SIGNATURES = {
     "kk_op_snac_from_codes": (_i, [_vp, _i, _i, _i, _i, C.POINTER(_vp), C.POINTER(C.c_int32), C.POINTER(_vp), _i, _vp, _vp, _i, _i]),
     "kk_op_snac_vq_search": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i]),
     "kk_op_snac_conv_cout1": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp]),
+    "kk_op_snac_local_attn": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _i]),
     "kk_mimi_debug_info": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "kk_mimi_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
     "kk_debug_set_op_wfrag": (None, [_vp]),
@@ -401,7 +403,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 29:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 30:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

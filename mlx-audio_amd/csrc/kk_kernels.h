@@ -341,6 +341,11 @@ int kk_launch_rope_append_rows(float* qkv, int S, int H, int KV, int hd, const f
 int kk_launch_attn_cache_rows(const float* qkv, int S, int H, int KV, int hd, const int* row_pos, const int* active, const float* kc, const float* vc,
                               int max_pos, float scale, float* out, int ctx, int B, hipStream_t st);
 
+// ---- SNAC windowed attention (kk_snac_attn.hip), launched by the codec (kk_snac.hip): steps 3-6 of LocalMHA on the q | k | v tensor [B][T][ld >= 192 H],
+// windows of 32 frames, heads of 64 channels, the rotary embedding restarting in every window; out [B][T][ldo >= 64 H], the heads concatenated.
+// T % 32 == 0; fp32 tensors need pitches that are multiples of 4 and bf16 tensors of 8 elements, and 16-byte aligned pointers (the caller checks).
+int snac_launch_local_attn(const void* qkv, int ld, int dtype, int T, int H, void* out, int ldo, int B, hipStream_t st);
+
 // ---- Whisper alignment (kk_whisper_align.hip): raw cross-attention scores of selected heads, launched by the text handle's capturing forward
 struct KKQkSel {  // up to 32 heads of one layer per launch: head[j] goes to output slot slot[j]
   int n;

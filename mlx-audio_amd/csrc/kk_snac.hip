@@ -15,6 +15,14 @@
 //   layers.py:9-14,57   weight norm g v / |v| over the axes except 0 (folded at finalize in float64)
 //   vq.py:23-54,62-77   average pool, in_proj, L2-normalised search argmax(-dist), z_e + (z_q - z_e), out_proj, repeat-interleave
 //   vq.py:97-129        residual update and from_codes (quantisers added in ascending order)
+// NOT restated as written: attention.py:80-83 rotate_half.  Its mx.split keeps the split axis (the torch code it was translated from drops it with
+// unbind), so the rotated term has shape [b,h,w,n,1,d], does not broadcast against [b,h,w,n,d], and the reference's own LocalMHA cannot run.
+// Built instead: rot(u)[c] = -u[c + 32] for c < 32, u[c - 32] otherwise, u' = u cos + rot(u) sin, angle(i, c) = i 10000^(-2 (c mod 32) / 64), the
+// position i restarting in every window; xpos scale 1; a checkpoint's rel_pos.inv_freq is ignored.
+//
+// LocalMHA (attention.py:6-43; kk_snac_create_attn, window 32, heads of 64 channels), at the end of the encoder and the head of the decoder, is four
+// launches: kk_launch_layernorm, the to_qkv Linear as a bias-free 1x1 (snac_conv), the windowed attention (kk_snac_attn.hip), to_out with the
+// residual in its epilogue (snac_conv, res = x).
 #include <math.h>
 #include <string.h>
 
@@ -62,6 +70,11 @@ struct EncBlock {  // EncoderBlock (layers.py:234-253)
   PackedConv down;
   int stride = 1, Cin = 0, Cout = 0;
 };
+struct LocalAttn {  // LocalMHA (attention.py:6-43): LayerNorm, to_qkv [3 D][D], to_out [D][D], both bias-free
+  ArenaVec ln_w, ln_b;
+  PackedConv qkv, out;
+  int D = 0;
+};
 struct Quant {  // VectorQuantize (vq.py:10-77)
   PackedConv in_proj, out_proj;
   ArenaVec cb, cbn, c2, table;  // code book [bins][cd], its rows L2-normalised, their squared norms, out_proj(code book) [bins][D] without bias
@@ -82,6 +95,8 @@ struct kk_snac {
   std::vector<DecBlock> dec;
   std::vector<EncBlock> enc;
   std::vector<Quant> vq;
+  int attn = 0;  // window of the two LocalMHA blocks (32), 0: none
+  LocalAttn enc_attn, dec_attn;
   DebugNotes dbg;
   std::mutex dbg_mu;
 };
@@ -184,6 +199,21 @@ struct Run : Workspace {
     }
     return 0;
   }
+  // LocalMHA: y = to_out(attention(to_qkv(LayerNorm(x)))) + x.  qkv [rows][3 D] and y are tensors outside the slots; slots 0 and 1 are used.
+  int local_mha(const LocalAttn& a, const Act& x, const Act& qkv, const Act& y, const char* name) {
+    if (dry) return 0;
+    const Act n = view(0, x.rows, a.D, x.dtype), o = view(1, x.rows, a.D, x.dtype);
+    KKLnArgs ln;
+    memset(&ln, 0, sizeof ln);
+    ln.x = x.p; ln.xbs = x.bs(); ln.ldx = x.ld; ln.out = n.p; ln.obs = n.bs(); ln.ldo = n.ld; ln.C = a.D; ln.Lmax = x.rows;
+    ln.len = KKLen{nullptr, 0, x.rows}; ln.w = a.ln_w.p; ln.bias = a.ln_b.p; ln.eps = 1e-5f; ln.act = KK_ACT_NONE;
+    KK_TRY(kk_launch_layernorm(ln, B, x.dtype, st));
+    KK_TRY(snac_conv(st, B, a.qkv, n, qkv, 0, false, 1, nullptr, nullptr));
+    KK_TRY(snac_launch_local_attn(qkv.p, qkv.ld, qkv.dtype, x.rows, a.D / 64, o.p, o.ld, B, st));
+    KK_TRY(snac_conv(st, B, a.out, o, y, 0, false, 1, &x, nullptr));
+    note(name, y);
+    return 0;
+  }
 };
 
 int decode_samples(const kk_snac* m, int T) {
@@ -219,6 +249,12 @@ int run_decode(Run& r, int T, const int32_t* const* codes, const float* const* n
     const Act d0 = r.view(0, T, m->D, dt);
     KK_TRY(snac_launch_dw_conv(z.p, z.bs(), z.ld, dt, T, m->D, 1, m->dec_dw.w.p, m->dec_dw.b.p, nullptr, nullptr, d0.p, d0.bs(), d0.ld, B, r.st));
     KK_TRY(snac_conv(r.st, B, m->dec_pw, d0, y, 0, false, 1, nullptr, nullptr));
+  }
+  if (m->attn) {
+    const Act qkv = r.act(T, 3 * c.decoder_dim, dt), ya = r.act(T, c.decoder_dim, dt);
+    if (r.oom) return kk_fail("kk_snac_decode: workspace too small");
+    KK_TRY(r.local_mha(m->dec_attn, y, qkv, ya, "decoder_attn"));
+    y = ya;
   }
   int L = T;
   for (size_t l = 0; l < m->dec.size(); ++l) {
@@ -265,6 +301,7 @@ size_t encode_scratch_elems(const kk_snac* m, int B, int N) {
     mx = std::max(mx, (size_t)L * b.Cin);
     L = convs_len(L, b.stride);
   }
+  if (m->attn) mx = std::max(mx, (size_t)L * m->D);  // (LocalMHA's normalised input and its heads)
   return mx * B;
 }
 
@@ -275,6 +312,7 @@ int run_encode(Run& r, int N, const float* pcm, int32_t* const* codes) {
   if (T < 1) return kk_fail("kk_snac_encode: too few samples");
   for (const Quant& q : m->vq)
     if (T % q.stride != 0) return kk_failf("kk_snac_encode: %d latent frames are no multiple of the quantiser stride %d (preprocess pads the audio)", T, q.stride);
+  if (m->attn && T % m->attn != 0) return kk_failf("kk_snac_encode: %d latent frames are no multiple of the attention window %d (preprocess pads the audio)", T, m->attn);
   Act y = r.act(N, c.encoder_dim, KK_F32);
   r.scratch(encode_scratch_elems(m, B, N), KK_F32);
   if (r.oom) return kk_fail("kk_snac_encode: workspace too small");
@@ -299,6 +337,12 @@ int run_encode(Run& r, int N, const float* pcm, int32_t* const* codes) {
     }
     y = o;
     L = Lo;
+  }
+  if (m->attn) {
+    const Act qkv = r.act(T, 3 * D, KK_F32), ya = r.act(T, D, KK_F32);
+    if (r.oom) return kk_fail("kk_snac_encode: workspace too small");
+    KK_TRY(r.local_mha(m->enc_attn, y, qkv, ya, "encoder_attn"));
+    y = ya;
   }
   Act z = r.act(T, D, KK_F32);
   if (r.oom) return kk_fail("kk_snac_encode: workspace too small");
@@ -348,10 +392,19 @@ struct Packer {
   }
   // WNConv1d [O][K][I] or WNConvTranspose1d [I][K][O] -> [K][I][ldw] (+ the fragment pack when `mfma`)
   PackedConv conv(const std::string& p, int O, int K, int I, bool transposed, bool bias, bool mfma) {
-    PackedConv c;
     std::vector<double> w;
-    if (!folded(p, transposed ? I : O, K, transposed ? O : I, w)) return c;
-    auto at = [&](int o, int k, int i) { return (float)(transposed ? w[((size_t)i * K + k) * O + o] : w[((size_t)o * K + k) * I + i]); };
+    if (!folded(p, transposed ? I : O, K, transposed ? O : I, w)) return PackedConv();
+    return pack(p, O, K, I, bias, mfma, [&](int o, int k, int i) { return (float)(transposed ? w[((size_t)i * K + k) * O + o] : w[((size_t)o * K + k) * I + i]); });
+  }
+  // nn.Linear without bias, weight [O][I], as a 1x1 conv
+  PackedConv linear(const std::string& p, int O, int I, bool mfma) {
+    const HostTensor* w = a.get(p + ".weight", (size_t)O * I);
+    if (!w) return PackedConv();
+    return pack(p, O, 1, I, false, mfma, [&](int o, int, int i) { return w->d[(size_t)o * I + i]; });
+  }
+  template <typename At>
+  PackedConv pack(const std::string& p, int O, int K, int I, bool bias, bool mfma, At at) {
+    PackedConv c;
     c.Cin = I; c.Cout = O; c.K = K; c.ldw = rup(O, 64);
     c.w_off = a.alloc((size_t)K * I * c.ldw);
     float* dst = &a.pack[c.w_off];
@@ -391,6 +444,15 @@ struct Packer {
     d.b = a.vec(p + ".bias", C);
     return d;
   }
+  LocalAttn attn(const std::string& p, int D, bool mfma) {  // p.{norm, to_qkv, to_out}
+    LocalAttn t;
+    t.D = D;
+    t.ln_w = a.vec(p + ".norm.weight", D);
+    t.ln_b = a.vec(p + ".norm.bias", D);
+    t.qkv = linear(p + ".to_qkv", 3 * D, D, mfma);
+    t.out = linear(p + ".to_out", D, D, mfma);
+    return t;
+  }
   Unit unit(const std::string& p, int C, int dil, bool mfma) {  // p.block.layers.{0 Snake, 1 dw conv, 2 Snake, 3 1x1}
     Unit u;
     u.dil = dil;
@@ -409,11 +471,17 @@ void resolve(kk_snac* m, PackedConv& c) {
 }
 void resolve(kk_snac* m, ArenaVec& v) { m->arena.resolve(v); }
 void resolve(kk_snac* m, DwConv& d) { resolve(m, d.w); resolve(m, d.b); }
+void resolve(kk_snac* m, LocalAttn& t) { resolve(m, t.ln_w); resolve(m, t.ln_b); resolve(m, t.qkv); resolve(m, t.out); }
 void resolve(kk_snac* m, Unit& u) { resolve(m, u.a1); resolve(m, u.a2); resolve(m, u.dw); resolve(m, u.pw); }
 
-int check_cfg(const kk_snac_config& c) {
-  const char* who = "kk_snac_create";
-  if (c.attn_window_size != 0) return kk_failf("%s: attn_window_size: LocalMHA is not built (the 32 / 44 kHz checkpoints)", who);
+int check_cfg(const kk_snac_config& c, bool attn) {
+  const char* who = attn ? "kk_snac_create_attn" : "kk_snac_create";
+  if (c.attn_window_size != 0) {
+    if (!attn) return kk_failf("%s: attn_window_size: LocalMHA (the 32 / 44 kHz checkpoints) is served by kk_snac_create_attn", who);
+    if (c.attn_window_size != 32) return kk_failf("%s: attn_window_size %d is not built: only windows of 32 frames", who, c.attn_window_size);
+    if (c.latent_dim % 64 != 0 || c.decoder_dim % 64 != 0)
+      return kk_failf("%s: LocalMHA has heads of 64 channels: latent_dim %d and decoder_dim %d must be multiples of 64", who, c.latent_dim, c.decoder_dim);
+  }
   if (!c.depthwise) return kk_failf("%s: depthwise=False is not built", who);
   if (c.encoder_dim < 1 || c.decoder_dim < 1 || c.latent_dim < 1 || c.codebook_size < 1) return kk_failf("%s: bad dimension", who);
   if (c.codebook_dim < 1 || c.codebook_dim > SNAC_VQ_MAX_DIM) return kk_failf("%s: codebook_dim must be 1 .. %d", who, SNAC_VQ_MAX_DIM);
@@ -434,16 +502,22 @@ bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
-extern "C" int kk_snac_create(const kk_snac_config* cfg, kk_snac** out) {
-  if (!cfg || !out) return kk_fail("kk_snac_create: null argument");
-  KK_TRY(check_cfg(*cfg));
+namespace {
+int snac_create(const kk_snac_config* cfg, kk_snac** out, bool attn) {
+  if (!cfg || !out) return kk_failf("%s: null argument", attn ? "kk_snac_create_attn" : "kk_snac_create");
+  KK_TRY(check_cfg(*cfg, attn));
   kk_snac* m = new kk_snac();
   m->cfg = *cfg;
+  m->attn = cfg->attn_window_size;
   m->adt = cfg->compute_dtype == KK_BF16 ? KK_BF16 : KK_F32;
   m->D = cfg->latent_dim;
   *out = m;
   return 0;
 }
+}  // namespace
+
+extern "C" int kk_snac_create(const kk_snac_config* cfg, kk_snac** out) { return snac_create(cfg, out, false); }
+extern "C" int kk_snac_create_attn(const kk_snac_config* cfg, kk_snac** out) { return snac_create(cfg, out, true); }
 
 extern "C" void kk_snac_destroy(kk_snac* m) {
   if (!m) return;
@@ -479,7 +553,9 @@ extern "C" int kk_snac_finalize(kk_snac* m, void* stream) {
       d *= 2;
     }
     if (d != D) return kk_failf("kk_snac_finalize: latent_dim %d is not encoder_dim * 2^len(encoder_rates) = %d (the quantiser reads the encoder's channels)", D, d);
-    m->enc_last = P.dw(e + std::to_string(c.n_encoder_rates + 1), D);
+    // layers.py:147-152: with attention, LocalMHA is layer n + 1 and the last depth-wise conv moves to n + 2
+    if (m->attn) m->enc_attn = P.attn(e + std::to_string(c.n_encoder_rates + 1), D, false);
+    m->enc_last = P.dw(e + std::to_string(c.n_encoder_rates + (m->attn ? 2 : 1)), D);
   }
   // ---- quantiser (vq.py): packs, the normalised code book, the from_codes tables
   m->vq.resize(c.n_vq);
@@ -528,11 +604,14 @@ extern "C" int kk_snac_finalize(kk_snac* m, void* stream) {
     const std::string dp = "decoder.model.layers.";
     m->dec_dw = P.dw(dp + "0", D);
     m->dec_pw = P.conv(dp + "1", c.decoder_dim, 1, D, false, true, bf);
+    // layers.py:185-194: with attention, LocalMHA is layer 2 and everything after it moves up by one
+    const int sh = m->attn ? 1 : 0;
+    if (m->attn) m->dec_attn = P.attn(dp + "2", c.decoder_dim, bf);
     m->dec.resize(c.n_decoder_rates);
     int out_dim = c.decoder_dim;
     for (int l = 0; l < c.n_decoder_rates; ++l) {
       DecBlock& b = m->dec[l];
-      const std::string p = dp + std::to_string(l + 2) + ".block.layers.";
+      const std::string p = dp + std::to_string(l + 2 + sh) + ".block.layers.";
       b.Cin = c.decoder_dim >> l; b.Cout = c.decoder_dim >> (l + 1); b.stride = c.decoder_rates[l];
       b.alpha = P.a.vec(p + "0.alpha", b.Cin);
       b.up = P.conv(p + "1", b.Cout, 2 * b.stride, b.Cin, true, true, bf);
@@ -542,13 +621,14 @@ extern "C" int kk_snac_finalize(kk_snac* m, void* stream) {
       for (int i = 0; i < 3; ++i) b.u[i] = P.unit(p + std::to_string(at++), b.Cout, dils[i], bf);
       out_dim = b.Cout;
     }
-    m->dec_alpha = P.a.vec(dp + std::to_string(c.n_decoder_rates + 2) + ".alpha", out_dim);
-    m->dec_last = P.conv(dp + std::to_string(c.n_decoder_rates + 3), 1, SNAC_DW_K, out_dim, false, true, false);
+    m->dec_alpha = P.a.vec(dp + std::to_string(c.n_decoder_rates + 2 + sh) + ".alpha", out_dim);
+    m->dec_last = P.conv(dp + std::to_string(c.n_decoder_rates + 3 + sh), 1, SNAC_DW_K, out_dim, false, true, false);
   }
   if (!P.a.err.empty()) return kk_failf("kk_snac_finalize: %s", P.a.err.c_str());
   KK_TRY(m->arena.upload((hipStream_t)stream, "kk_snac_finalize"));
   resolve(m, m->enc_first); resolve(m, m->enc_last); resolve(m, m->dec_dw); resolve(m, m->dec_pw); resolve(m, m->dec_last);
   resolve(m, m->dec_alpha); resolve(m, m->bias_sum);
+  if (m->attn) { resolve(m, m->enc_attn); resolve(m, m->dec_attn); }
   for (auto& b : m->enc) {
     for (auto& u : b.u) resolve(m, u);
     resolve(m, b.alpha); resolve(m, b.down);
@@ -588,6 +668,7 @@ extern "C" int kk_snac_decode(kk_snac* m, void* stream, int B, int T, const int3
     if (!codes[i]) return kk_failf("%s: codes[%d] is null", who, i);
     if (T % m->cfg.vq_strides[i] != 0) return kk_failf("%s: %d latent frames are no multiple of the quantiser stride %d", who, T, m->cfg.vq_strides[i]);
   }
+  if (m->attn && T % m->attn != 0) return kk_failf("%s: %d latent frames are no multiple of the attention window %d", who, T, m->attn);
   if (m->cfg.noise) {
     if (!noise) return kk_failf("%s: the model has NoiseBlocks: noise must hold one [B][C] tensor per decoder block", who);
     for (int l = 0; l < m->cfg.n_decoder_rates; ++l)
@@ -708,4 +789,15 @@ extern "C" int kk_op_snac_conv_cout1(void* stream, int B, const void* x, int dty
   if (!dt_ok(dtype) || ld < Cin || ldw < 1 || pad < 0 || Kw < 1 || Kw > SNAC_C1_MAX_K || pad >= Kw || (tanh_out != 0 && tanh_out != 1))
     return kk_failf("%s: bad dtype, ld < Cin, ldw < 1, Kw outside 1 .. %d, pad outside [0, Kw) or tanh_out not 0 / 1", who, SNAC_C1_MAX_K);
   return snac_launch_conv_cout1(x, dtype, ld, L, Cin, Kw, pad, w_packed, ldw, bias, alpha, tanh_out, out, B, (hipStream_t)stream);
+}
+
+// (ABI minor 30) steps 3-6 of LocalMHA on caller-owned buffers: qkv [B][T][ld >= 192 H] -> out [B][T][ldo >= 64 H]
+extern "C" int kk_op_snac_local_attn(void* stream, int B, int T, int H, const void* qkv, int ld, int dtype, void* out, int ldo) {
+  const char* who = "kk_op_snac_local_attn";
+  if (B <= 0 || B > 65535 || T < 32 || T % 32 != 0 || H < 1 || !qkv || !out || qkv == out) return kk_failf("%s: B 1 .. 65535, T a positive multiple of 32, H positive, qkv / out two non-null tensors", who);
+  if (!dt_ok(dtype)) return kk_failf("%s: dtype is KK_DTYPE_F32 or KK_DTYPE_BF16", who);
+  if (H > (1 << 20) || ld < 192 * H || ldo < 64 * H) return kk_failf("%s: ld must cover 3 x 64 H channels and ldo 64 H", who);
+  const int q = dtype == KK_BF16 ? 8 : 4;
+  if (ld % q != 0 || ldo % q != 0 || !al16(qkv) || !al16(out)) return kk_failf("%s: pitches must be multiples of %d elements and the pointers 16-byte aligned", who, q);
+  return snac_launch_local_attn(qkv, ld, dtype, T, H, out, ldo, B, (hipStream_t)stream);
 }

@@ -5,8 +5,15 @@ and provides the stream.
 
 The reference's port is restated as written, not upstream PyTorch SNAC: transposed convs without output padding (an odd stride s gives
 L s - 1 rows), NoiseBlock noise of shape [B, 1, C] (one normal per item and channel, constant over time), a no-op residual crop.
-Not built (NotImplementedError names the field): `attn_window_size` (the LocalMHA of the 32 / 44 kHz checkpoints), `depthwise=False`, the
-ragged-batch form (`lengths=`), and `__call__` (the encode -> decode round trip)."""
+NOT restated as written: attention.py:80-83 rotate_half.  Its mx.split keeps the split axis (the torch code it was translated from drops it with
+unbind), so the rotated term has shape [b,h,w,n,1,d], does not broadcast against [b,h,w,n,d], and the reference's own LocalMHA cannot run.
+Built instead: rot(u)[c] = -u[c + 32] for c < 32, u[c - 32] otherwise, u' = u cos + rot(u) sin with angle(i, c) = i 10000^(-2 (c mod 32) / 64), the
+position i restarting in every window of 32 frames; the xpos scale is 1 and a checkpoint's `rel_pos.inv_freq` is ignored.
+
+LocalMHA (`attn_window_size=32`: the 32 / 44 kHz checkpoints, `snac_44khz()`) is opt-in: `SNAC(cfg, weights, local_attention=True)`, and the same
+keyword on `from_config`, `from_pretrained` and `param_shapes`.  Without the keyword a non-zero `attn_window_size` is refused as before.
+Not built (NotImplementedError names the field): windows other than 32, `depthwise=False`, the ragged-batch form (`lengths=`), and `__call__`
+(the encode -> decode round trip)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -54,17 +61,33 @@ def snac_24khz() -> SNACConfig:
                       attn_window_size=None, codebook_size=4096, codebook_dim=8, vq_strides=[4, 2, 1], noise=True, depthwise=True)
 
 
-def _refuse(cfg: SNACConfig) -> None:
+def snac_44khz() -> SNACConfig:
+    """The reference's constructor defaults: the 44 kHz checkpoint, with LocalMHA (`local_attention=True`)."""
+    return SNACConfig()
+
+
+def _refuse(cfg: SNACConfig, local_attention: bool = False) -> None:
     if cfg.attn_window_size is not None:
-        raise NotImplementedError("attn_window_size: LocalMHA (the 32 / 44 kHz checkpoints) is not built; only attn_window_size=None")
+        if not local_attention:
+            raise NotImplementedError("attn_window_size: LocalMHA (the 32 / 44 kHz checkpoints) is opt-in: pass local_attention=True")
+        if cfg.attn_window_size != 32:
+            raise NotImplementedError(f"attn_window_size={cfg.attn_window_size} is not built: only windows of 32 frames")
+        if cfg.latent_dim % 64 or cfg.decoder_dim % 64:
+            raise ValueError(f"LocalMHA has heads of 64 channels: latent_dim {cfg.latent_dim} and decoder_dim {cfg.decoder_dim} must be multiples of 64")
     if not cfg.depthwise:
         raise NotImplementedError("depthwise=False (dense residual convolutions) is not built")
 
 
-def param_shapes(cfg: SNACConfig) -> Dict[str, tuple]:
-    """Every parameter of the reference's module tree, by name, with its shape (layers.py, vq.py): what `load_weights` consumes."""
-    _refuse(cfg)
+def param_shapes(cfg: SNACConfig, local_attention: bool = False) -> Dict[str, tuple]:
+    """Every parameter of the reference's module tree, by name, with its shape (layers.py, vq.py): what `load_weights` consumes.  With
+    LocalMHA the module indices behind it shift by one (layers.py:147-152, 185-194)."""
+    _refuse(cfg, local_attention)
     out: Dict[str, tuple] = {}
+    sh = 1 if cfg.attn_window_size else 0
+
+    def mha(p, d):  # LocalMHA (attention.py:6-17); rel_pos.inv_freq is recomputed, not loaded
+        out[p + ".norm.weight"], out[p + ".norm.bias"] = (d,), (d,)
+        out[p + ".to_qkv.weight"], out[p + ".to_out.weight"] = (3 * d, d), (d, d)
 
     def conv(p, o, k, i, bias=True):  # WNConv1d (layers.py:17-47)
         out[p + ".weight_g"], out[p + ".weight_v"] = (o, 1, 1), (o, k, i)
@@ -90,7 +113,9 @@ def param_shapes(cfg: SNACConfig) -> Dict[str, tuple]:
         out[p + "3.alpha"] = (1, d, 1)
         conv(p + "4", 2 * d, 2 * s, d)
         d *= 2
-    conv(f"{e}{len(cfg.encoder_rates) + 1}", d, 7, 1)
+    if sh:
+        mha(f"{e}{len(cfg.encoder_rates) + 1}", d)
+    conv(f"{e}{len(cfg.encoder_rates) + 1 + sh}", d, 7, 1)
     D = cfg.latent_dim
     for i in range(len(cfg.vq_strides)):  # VectorQuantize (vq.py:11-21)
         p = f"quantizer.quantizers.{i}"
@@ -100,10 +125,12 @@ def param_shapes(cfg: SNACConfig) -> Dict[str, tuple]:
     m = "decoder.model.layers."
     conv(m + "0", D, 7, 1)
     conv(m + "1", cfg.decoder_dim, 1, D)
+    if sh:
+        mha(m + "2", cfg.decoder_dim)
     co = cfg.decoder_dim
     for l, s in enumerate(cfg.decoder_rates):  # DecoderBlock (layers.py:270-294)
         ci, co = cfg.decoder_dim // 2**l, cfg.decoder_dim // 2 ** (l + 1)
-        p = f"{m}{l + 2}.block.layers."
+        p = f"{m}{l + 2 + sh}.block.layers."
         out[p + "0.alpha"] = (1, ci, 1)
         convt(p + "1", ci, 2 * s, co)
         at = 2
@@ -113,8 +140,8 @@ def param_shapes(cfg: SNACConfig) -> Dict[str, tuple]:
         for i in range(3):
             unit(p + str(at + i), co)
     n = len(cfg.decoder_rates)
-    out[f"{m}{n + 2}.alpha"] = (1, co, 1)
-    conv(f"{m}{n + 3}", 1, 7, co)
+    out[f"{m}{n + 2 + sh}.alpha"] = (1, co, 1)
+    conv(f"{m}{n + 3 + sh}", 1, 7, co)
     return out
 
 
@@ -145,11 +172,13 @@ def codes_to_orpheus(codes: Sequence) -> List[int]:
 
 
 class SNAC:
-    def __init__(self, cfg: SNACConfig, weights: Dict[str, np.ndarray] | None = None, device: str = "cuda:0", compute_dtype: str = "float32"):
-        _refuse(cfg)  # (on the host, before the library is touched)
+    def __init__(self, cfg: SNACConfig, weights: Dict[str, np.ndarray] | None = None, device: str = "cuda:0", compute_dtype: str = "float32",
+                 local_attention: bool = False):
+        _refuse(cfg, local_attention)  # (on the host, before the library is touched)
         if compute_dtype not in ("float32", "bfloat16"):
             raise ValueError("compute_dtype must be float32 or bfloat16")
         self.cfg = cfg
+        self.window = int(cfg.attn_window_size or 0)  # 32 with LocalMHA, else 0
         self.compute_dtype = compute_dtype
         self.device = torch.device(device)
         self.lib = _lib.load()
@@ -162,10 +191,11 @@ class SNAC:
             for i, v in enumerate(vals):
                 getattr(kc, name)[i] = int(v)
         kc.n_encoder_rates, kc.n_decoder_rates, kc.n_vq = len(cfg.encoder_rates), len(cfg.decoder_rates), len(cfg.vq_strides)
-        kc.attn_window_size, kc.noise, kc.depthwise = 0, int(bool(cfg.noise)), 1
+        kc.attn_window_size, kc.noise, kc.depthwise = self.window, int(bool(cfg.noise)), 1
         kc.compute_dtype = _lib.KK_BF16 if compute_dtype == "bfloat16" else _lib.KK_F32
         h = C.c_void_p()
-        check(self.lib.kk_snac_create(C.byref(kc), C.byref(h)), "kk_snac_create")
+        create = "kk_snac_create_attn" if self.window else "kk_snac_create"
+        check(getattr(self.lib, create)(C.byref(kc), C.byref(h)), create)
         self._h = h
         self._final = False
         self._ws = None
@@ -238,7 +268,7 @@ class SNAC:
         """The reference's parameter names and layouts (`param_shapes`).  A missing name or a wrong shape fails with the name; names the
         module tree does not have are ignored the way `strict=False` would."""
         weights = dict(weights.items() if hasattr(weights, "items") else weights)
-        want = param_shapes(self.cfg)
+        want = param_shapes(self.cfg, bool(self.window))
         for name, shape in want.items():
             if name not in weights:
                 raise ValueError(f"SNAC.load_weights: missing parameter: {name}")
@@ -257,12 +287,12 @@ class SNAC:
 
     def pad_to(self) -> int:
         lcm = 1
-        for s in self.cfg.vq_strides:
+        for s in list(self.cfg.vq_strides) + ([self.window] if self.window else []):  # snac.py:77-78
             lcm = abs(lcm * s) // math.gcd(lcm, s)
         return self.hop_length * lcm
 
     def preprocess(self, audio):
-        """snac.py:67-85: right zero-pad [B, 1, N] to a multiple of hop_length * lcm(vq_strides)."""
+        """snac.py:67-85: right zero-pad [B, 1, N] to a multiple of hop_length * lcm(vq_strides..., attn_window_size)."""
         audio = torch.as_tensor(audio)
         n = audio.shape[-1]
         unit = self.pad_to()
@@ -323,6 +353,8 @@ class SNAC:
         strides = self.cfg.vq_strides
         if len(codes) != len(strides):
             raise ValueError(f"codes must hold {len(strides)} tensors, got {len(codes)}")
+        if self.window and (int(torch.as_tensor(codes[0]).shape[-1]) * strides[0]) % self.window:  # (the reference's rearrange would fail)
+            raise ValueError(f"{int(torch.as_tensor(codes[0]).shape[-1]) * strides[0]} latent frames are no multiple of the attention window {self.window}")
         cs = [torch.as_tensor(c).to(device=self.device, dtype=torch.int32).contiguous() for c in codes]
         if any(c.ndim != 2 or c.shape[0] != cs[0].shape[0] or c.shape[1] < 1 for c in cs):
             raise ValueError("every code tensor must be [B, T / stride_i] with one B")

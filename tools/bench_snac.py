@@ -1,7 +1,9 @@
 """SNAC codec timing at the snac_24khz shape on synthetic weights: SNAC.decode (fp32 and bf16) and SNAC.encode (fp32) at B = 1 and
 B = 8, 10 s of audio per item; the residual unit of every decoder block on its own (kk_op_snac_residual_unit: the depth-wise launch + the 1x1
 launch) with its bytes per second beside a device-to-device copy of the same size; launches per decode with and without a fused unit.
-python tools/bench_snac.py [--seconds 10] [--steps 5] [--out profiles/snac_bench.json]      prints one JSON line"""
+python tools/bench_snac.py [--seconds 10] [--steps 5] [--out profiles/snac_bench.json]      prints one JSON line
+--config 44khz: the reference's default configuration (LocalMHA, window 32) instead: decode and encode only, the same model without its two
+attention blocks beside it, and the attention kernel on its own at the decoder's width (--out profiles/snac_attn_bench.json)."""
 import argparse
 import ctypes as C
 import json
@@ -22,6 +24,7 @@ ap.add_argument("--seconds", type=float, default=10.0)
 ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--batches", type=int, nargs="+", default=[1, 8])
 ap.add_argument("--out", default="")
+ap.add_argument("--config", choices=["24khz", "44khz"], default="24khz")
 a = ap.parse_args()
 
 
@@ -37,6 +40,10 @@ def synth(shapes, seed=0):
             continue
         elif name.endswith(".bias"):
             v = 0.05 * rng.standard_normal(shape)
+        elif name.endswith((".to_qkv.weight", ".to_out.weight")):  # unit-variance q and k: a softmax neither flat nor one-hot
+            v = rng.standard_normal(shape) / math.sqrt(shape[1])
+        elif name.endswith(".norm.weight"):
+            v = rng.uniform(0.8, 1.2, shape)
         else:
             v = rng.standard_normal(shape)
         w[name] = v.astype(np.float32)
@@ -62,6 +69,61 @@ def timed(fn, steps):
     return e0.elapsed_time(e1) / steps
 
 
+def bench_44khz():
+    """decode / encode with LocalMHA and, on the same weights, without (the difference is what the two blocks' four launches each cost)"""
+    import dataclasses
+
+    cfg = snac.snac_44khz()
+    plain = dataclasses.replace(cfg, attn_window_size=None)
+    w = synth(snac.param_shapes(cfg, local_attention=True))
+    back = {"encoder.block.layers.6.": "encoder.block.layers.5.", **{f"decoder.model.layers.{i + 1}.": f"decoder.model.layers.{i}." for i in range(2, 8)}}
+    wp = {}
+    for name, v in w.items():  # the same parameters under the names of the model without attention
+        pre = next((k for k in back if name.startswith(k)), None)
+        if ".norm." not in name and ".to_qkv." not in name and ".to_out." not in name:
+            wp[back[pre] + name[len(pre):] if pre else name] = v
+    first = snac.SNAC(cfg, w, local_attention=True)
+    unit = first.pad_to()
+    N = math.ceil(a.seconds * cfg.sampling_rate / unit) * unit
+    T, H = N // first.hop_length, cfg.decoder_dim // 64
+    del first
+    out = {"metric": "ms per call, SNAC 44 kHz configuration (LocalMHA, window 32) on synthetic weights", "seconds_per_item": N / cfg.sampling_rate,
+           "latent_frames": T, "steps": a.steps, "decode": [], "encode": [], "attention_kernel": [], "data": "synthetic (random weights, random codes, noise audio)"}
+    rng = np.random.default_rng(0)
+    for dt in ("float32", "bfloat16"):
+        m, mp = snac.SNAC(cfg, w, compute_dtype=dt, local_attention=True), snac.SNAC(plain, wp, compute_dtype=dt)
+        for B in a.batches:
+            codes = [torch.tensor(rng.integers(0, cfg.codebook_size, (B, T // s)), device="cuda", dtype=torch.int32) for s in cfg.vq_strides]
+            noise = [n.cuda() for n in m.draw_noise(B, 0)]
+            ms, ms0 = timed(lambda: m.decode(codes, noise=noise), a.steps), timed(lambda: mp.decode(codes, noise=noise), a.steps)
+            out["decode"].append({"batch": B, "dtype": dt, "ms": ms, "ms_without_attention": ms0, "attention_share": (ms - ms0) / ms,
+                                  "xRT": B * N / cfg.sampling_rate / (ms * 1e-3)})
+            if dt == "float32":  # (encode always runs in fp32)
+                audio = torch.tensor((0.3 * rng.standard_normal((B, 1, N))).astype(np.float32), device="cuda")
+                ms, ms0 = timed(lambda: m.encode(audio), a.steps), timed(lambda: mp.encode(audio), a.steps)
+                out["encode"].append({"batch": B, "dtype": dt, "ms": ms, "ms_without_attention": ms0, "attention_share": (ms - ms0) / ms,
+                                      "xRT": B * N / cfg.sampling_rate / (ms * 1e-3)})
+                del audio
+            # the kernel alone at the decoder's width: reads q | k | v, writes o
+            tdt = torch.bfloat16 if dt == "bfloat16" else torch.float32
+            qkv, o = torch.randn(B, T, 192 * H, device="cuda").to(tdt), torch.empty(B, T, 64 * H, device="cuda", dtype=tdt)
+            run = lambda: _lib.check(_lib.load().kk_op_snac_local_attn(C.c_void_p(torch.cuda.current_stream().cuda_stream), B, T, H, C.c_void_p(qkv.data_ptr()),
+                                                                       192 * H, int(dt == "bfloat16"), C.c_void_p(o.data_ptr()), 64 * H), "kk_op_snac_local_attn")
+            ms = timed(run, 20 * a.steps)
+            out["attention_kernel"].append({"batch": B, "dtype": dt, "rows": T, "heads": H, "ms": ms, "gbs": (qkv.numel() + o.numel()) * qkv.element_size() / (ms * 1e-3) / 1e9})
+            del codes, qkv, o
+            torch.cuda.empty_cache()
+        del m, mp
+    print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+
+if a.config == "44khz":
+    bench_44khz()
+    sys.exit(0)
 cfg = snac.snac_24khz()
 w = synth(snac.param_shapes(cfg))
 models = {dt: snac.SNAC(cfg, w, compute_dtype=dt) for dt in ("float32", "bfloat16")}
