@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 30  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 31  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -83,7 +83,9 @@ extern "C" {
                                (kk_op_kokoro_style_fc, kk_op_kokoro_fill_style, kk_op_kokoro_embedding, kk_op_kokoro_duration, kk_op_kokoro_alignment,
                                kk_op_kokoro_gather_rows, kk_op_kokoro_copy_slice, kk_op_kokoro_lens, kk_op_kokoro_convert, kk_op_albert_embed,
                                kk_op_source_stft_ragged);
-                            30: SNAC with LocalMHA, the 32 / 44 kHz checkpoints (kk_snac_create_attn, kk_op_snac_local_attn) */
+                            30: SNAC with LocalMHA, the 32 / 44 kHz checkpoints (kk_snac_create_attn, kk_op_snac_local_attn);
+                            31: the Parakeet encoder's hot blocks on caller-owned buffers (kk_op_rel_pos_attention, kk_op_conformer_dwconv,
+                               kk_op_conv2d_s2), its features (kk_op_parakeet_log_mel) and its encoder behind a handle (kk_parakeet_*) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -1315,6 +1317,54 @@ int kk_op_whisper_dtw(void* stream, int B, const float* x, long long stride_b, i
 size_t kk_whisper_text_qk_bytes(const kk_whisper_text* m, int B, int S, int n_pairs, int n_keys);
 int kk_whisper_text_forward_qk(kk_whisper_text* m, void* stream, int B, int S, const int32_t* tokens, float* logits_out, const int32_t* pairs, int n_pairs,
                                int n_keys, float* qk_out, size_t qk_bytes, void* workspace, size_t workspace_bytes);
+
+/* =====================================================================================================================
+ * Parakeet (FastConformer), audio side: the encoder's three hot blocks on caller-owned buffers (csrc/kk_parakeet.hip).  Device pointers,
+ * work enqueued on `stream`, no device-to-host synchronisation, 0 = OK.
+ * ===================================================================================================================== */
+/* RelPositionMultiHeadAttention after its Linears (mlx_audio/stt/models/parakeet/attention.py:105-135) for heads of head_dim = 64 or 128 channels:
+ * qkv bf16 [B][T_rows][ld], q | k | v at channels 0, heads * head_dim and 2 * heads * head_dim (ld % 8 == 0); pos bf16 [2 T - 1][ldp], linear_pos of the
+ * positional table for positions T - 1 .. -(T - 1), shared by all items (ldp % 8 == 0); pos_bias_u, pos_bias_v fp32 [heads][head_dim]; out bf16
+ * [B][T_rows][ldo] (ldo % 4 == 0).  Over the first T rows: softmax_j(head_dim^-0.5 (bf16(q_i + u) . k_j + bf16(q_i + v) . pos[T - 1 - i + j])) v_j, the
+ * two sums taken in fp32 and rounded once; the index is what rel_shift selects.  The [T][2 T - 1] positional matrix is never stored.  Rows >= T are
+ * neither read nor written.  An item's bits do not depend on B. */
+int kk_op_rel_pos_attention(void* stream, int B, const void* qkv, int ld, int T_rows, int T, int heads, int head_dim, const void* pos, int ldp,
+                            const float* pos_bias_u, const float* pos_bias_v, void* out, int ldo);
+/* The core of the Conformer Convolution module (conformer.py:83-87): x bf16 [B][T][ld] holds pointwise_conv1's 2 D channels, out bf16 [B][T][ldo] gets
+ * silu(dwconv_k(x[:, :D] * sigmoid(x[:, D:])) + bias) on D channels: a depth-wise convolution over time with zero padding (k - 1) / 2, k odd and <= 31.
+ * w fp32 [k][D] (tap-major) and bias fp32 [D] are the caller's, with the inference-form BatchNorm folded in.  D, ld and ldo even.  fp32 arithmetic. */
+int kk_op_conformer_dwconv(void* stream, int B, const void* x, int ld, int T, int D, int k, const float* w, const float* bias, void* out, int ldo);
+/* A 3 x 3, stride 2, padding 1 Conv2d of DwStridingSubsampling (conformer.py:174-196) over channels-last data.  stem != 0: x fp32 [B][T][F] (one input
+ * channel), C output channels, ReLU.  stem == 0: x bf16 [B][T][F][C], depth-wise, no activation.  w fp32 [9][C] (tap ky * 3 + kx), bias fp32 [C], C even.
+ * out bf16 [B][(T - 1) / 2 + 1][(F - 1) / 2 + 1][C]. */
+int kk_op_conv2d_s2(void* stream, int B, const void* x, int stem, int T, int F, int C, const float* w, const float* bias, void* out);
+
+/* parakeet/audio.py:38-70 (log_mel_spectrogram; `dither` is unused there and here) for B rows x [B][ldx] fp32 of n samples each: samples up to pad_to are
+ * pad_value (pad_to <= n: none), reflect padding of n_fft / 2 at both ends (max(n, pad_to) > n_fft / 2), F = 1 + max(n, pad_to) / hop frames under the window
+ * [win] (zero from win to n_fft: never read; win % 4 == 0, win <= n_fft <= 512, n_fft even), |X|^2 of the n_fft / 2 + 1 bins, the filter bank
+ * fbT [n_fft / 2 + 1][features] (features <= 128), log(. + 1e-5), then (x - mean) / (std + 1e-5) with the population standard deviation over time per
+ * feature (per_feature != 0) or over the whole row.  window, cos_sin [2][n_fft] (cos | sin of 2 pi j / n_fft) and fbT are the caller's fp32 tables, made in
+ * float64 on the host.  out fp32 [B][F][features].  Two launches; the statistics are accumulated in float64 in index order. */
+int kk_op_parakeet_log_mel(void* stream, int B, const float* x, long long ldx, int n, int pad_to, float pad_value, int n_fft, int hop, int win, int features,
+                           int per_feature, const float* window, const float* cos_sin, const float* fbT, float* out);
+
+/* The FastConformer encoder (conformer.py:274-331: dw_striding pre_encode, rel_pos layers) behind a handle, in kk_whisper's pattern.  Parameters are
+ * loaded in the canonical form mlx-audio_amd/parakeet.py prepares in float64 (BatchNorm, the feed-forward 1/2, xscaling and the column order of pre_encode.out
+ * folded; q | k | v stacked; absent biases as zeros): see parakeet.canonical_tensors for names and shapes.  encode: mel fp32 [B][T_mel][feat_in] ->
+ * out fp32 [B][T'][d_model], T' = kk_parakeet_encode_frames(T_mel); pos_emb bf16 [2 T' - 1][d_model], the positional table for T', 16-byte aligned.  All
+ * items share T_mel; no mask is applied (the reference applies none).  Work is enqueued on `stream`. */
+typedef struct kk_parakeet kk_parakeet;
+typedef struct kk_parakeet_config {
+  int32_t feat_in, n_layers, d_model, n_heads, ff_expansion_factor, subsampling_factor, conv_kernel_size, subsampling_conv_channels;
+} kk_parakeet_config;
+int kk_parakeet_create(const kk_parakeet_config* cfg, kk_parakeet** out);
+void kk_parakeet_destroy(kk_parakeet* m);
+int kk_parakeet_load_tensor(kk_parakeet* m, const char* name, const int64_t* shape, int ndim, const float* data);
+int kk_parakeet_finalize(kk_parakeet* m, void* stream);
+int kk_parakeet_encode_frames(const kk_parakeet* m, int T_mel);
+size_t kk_parakeet_encode_workspace_bytes(const kk_parakeet* m, int B, int T_mel);
+int kk_parakeet_encode(kk_parakeet* m, void* stream, int B, int T_mel, const float* mel, const void* pos_emb, void* workspace, size_t workspace_bytes,
+                       float* out);
 
 #ifdef __cplusplus
 }

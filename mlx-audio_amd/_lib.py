@@ -54,6 +54,11 @@ class KKWhisperConfig(C.Structure):
                 ("n_audio_layer", C.c_int32)]
 
 
+class KKParakeetConfig(C.Structure):  # kk_parakeet_config
+    _fields_ = [(n, C.c_int32) for n in ("feat_in", "n_layers", "d_model", "n_heads", "ff_expansion_factor", "subsampling_factor", "conv_kernel_size",
+                                         "subsampling_conv_channels")]
+
+
 class KKWhisperTextConfig(C.Structure):
     _fields_ = [("n_vocab", C.c_int32), ("n_text_ctx", C.c_int32), ("n_text_state", C.c_int32), ("n_text_head", C.c_int32),
                 ("n_text_layer", C.c_int32), ("n_audio_ctx", C.c_int32), ("n_audio_state", C.c_int32)]
@@ -355,6 +360,17 @@ SIGNATURES = {
     "kk_op_snac_vq_search": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i]),
     "kk_op_snac_conv_cout1": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp]),
     "kk_op_snac_local_attn": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _i]),
+    "kk_op_rel_pos_attention": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i]),
+    "kk_op_conformer_dwconv": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i]),
+    "kk_op_conv2d_s2": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "kk_op_parakeet_log_mel": (_i, [_vp, _i, _vp, C.c_longlong, _i, _i, _f, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "kk_parakeet_create": (_i, [C.POINTER(KKParakeetConfig), C.POINTER(_vp)]),
+    "kk_parakeet_destroy": (None, [_vp]),
+    "kk_parakeet_load_tensor": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), _i, _vp]),
+    "kk_parakeet_finalize": (_i, [_vp, _vp]),
+    "kk_parakeet_encode_frames": (_i, [_vp, _i]),
+    "kk_parakeet_encode_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "kk_parakeet_encode": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "kk_mimi_debug_info": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "kk_mimi_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
     "kk_debug_set_op_wfrag": (None, [_vp]),
@@ -403,7 +419,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 30:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 31:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

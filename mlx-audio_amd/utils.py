@@ -81,6 +81,10 @@ def load_model(model_path, lazy: bool = False, strict: bool = True, compute_dtyp
 
     if whisper.is_whisper_config(config):  # stt/models/whisper: weights.safetensors / weights.npz + the ten ModelDimensions in config.json
         return whisper.load_model(path, kwargs.get("dtype"), weight_storage=weight_storage, **{k: v for k, v in kwargs.items() if k == "device"})
+    from . import parakeet
+
+    if parakeet.is_parakeet_config(config):  # stt/models/parakeet: the audio side (encoder) only
+        return parakeet.Model.from_pretrained(str(path))
     model_type = config.get("model_type") or (model_name[0] if model_name else None)
     weight_files = glob.glob(str(path / "*.safetensors"))
     if not weight_files:
