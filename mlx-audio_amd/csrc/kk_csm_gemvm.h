@@ -1,5 +1,5 @@
-// The matrix-core GEMV of the CSM single-token steps (kk_csm.hip) in its own header, so that tools/gridbar/gemvm_bench.hip can time the
-// SAME kernel in isolation.  Included inside kk_csm.hip's anonymous namespace.
+// The matrix-core GEMV of the CSM single-token steps (kk_csm_kernels.hip) in its own header, so that tools/gridbar/gemvm_bench.hip can time the
+// SAME kernel in isolation.  Included inside kk_csm_kernels.hip's anonymous namespace.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -16,7 +16,7 @@ typedef unsigned kk_u32x2 __attribute__((ext_vector_type(2)));
 // [block][K / group][sub-block][16 columns] float2: a lane's 8 values lie in one 32-row chunk, hence in one group (group % 32 == 0).  The lane
 // decodes them in registers to  bf16_rne(fp32(q) * scale + bias)  -- fp32 multiply, then fp32 add, no fma -- which is the bf16 rounding of the
 // dequantised matrix, i.e. bit for bit the fragment the bf16 pack of that matrix holds; everything behind the B operand is shared.
-enum { KK_WF_BF16 = 0, KK_WF_Q8 = 1, KK_WF_Q4 = 2 };
+#include "kk_csm_wf.h"  // enum { KK_WF_BF16, KK_WF_Q8, KK_WF_Q4 }
 template <int FMT> struct WFrag;
 template <> struct WFrag<KK_WF_BF16> { typedef kk_u32x4 Q; };
 template <> struct WFrag<KK_WF_Q8> { typedef kk_u32x2 Q; };

@@ -440,3 +440,85 @@ struct KKGroupRows {
 };
 // a beam group's admission: owner[0] of its K rows is identity, nothing finished, not complete
 int kk_launch_whisper_rows_group_reset(hipStream_t st, const KKGroupRows& rows, int K, int n_text_ctx, const KKGroupBufs& g);
+
+// ---- CSM generator (kk_csm_kernels.hip, kk_csm_sample.hip): the kernels of the frame step, launched by the handle (kk_csm.hip)
+#include "kk_csm_wf.h"  // KK_WF_BF16 / KK_WF_Q8 / KK_WF_Q4: what a fragment pack holds
+struct KKCsmWeight {  // one Linear x[Cin] -> out[Cout] as the launchers read it; the handle's Lin adds where its storage lives
+  int Cin = 0, Cout = 0, ldw = 0;
+  const float* w = nullptr;      // fp32 [Cin][ldw], or null (packed storage)
+  const uint16_t* wm = nullptr;  // fragment pack [Cout / (16 nsub)][Cin / 32][nsub][64 lanes][8]: bf16, or the quantised integers (fmt)
+  int nsub = 0;                  // 0 = no fragment pack
+  int ks = 1;                    // split-K slices of a deep projection
+  int fmt = KK_WF_BF16, group = 0;
+  const float2* wp = nullptr;    // quantised formats: the (scale, bias) pairs
+};
+int kk_launch_csm_embed_sum(hipStream_t st, const int* tokens, const float* mask, const float* audio, const float* text, int ncb, int V, int TV, int D, int rows,
+                            float* h);
+int kk_launch_csm_embed_audio(hipStream_t st, const int* codes, int cstride, const float* audio, int cb, int V, int D, float* out, int rows, int pos, int B);
+int kk_launch_csm_copy_rows(hipStream_t st, const float* src, long long sbs, float* dst, long long dbs, int D, int B);
+int kk_launch_csm_rmsnorm(hipStream_t st, const float* x, const float* w, int D, float eps, float* out, int rows);
+int kk_launch_csm_swiglu(hipStream_t st, const float* gu, int I, long long n, float* out);
+int kk_launch_csm_advance_pos(hipStream_t st, int* pos, int by);
+int kk_launch_csm_shift_cache(hipStream_t st, float* kc, float* vc, int maxB, int max_pos, int rowf4, int layers, const int* pos_dev, const int* pad, int delta);
+// one run of seg4 16-byte columns per (layer, K | V): layer l's run starts at src_k / src_v + l src_pitch4 columns and goes to dst_k / dst_v + l dst_pitch4
+int kk_launch_csm_kv_runs(const float* src_k, const float* src_v, long long src_pitch4, float* dst_k, float* dst_v, long long dst_pitch4, long long seg4,
+                          int layers, hipStream_t stream);
+// the skinny GEMM of <= 2 rows per item on fp32 weights: out[m] = x[m] W (+ res[m]), Mtot contiguous rows; part: kk_csm_skinny_floats(Cin, Cout) floats
+constexpr int KK_CSM_SKINNY_MAXM = 16;
+size_t kk_csm_skinny_floats(int K, int N);
+int kk_launch_csm_skinny(hipStream_t st, const KKCsmWeight& w, const float* x, int Mtot, const float* res, float* out, float* part);
+// the prompt GEMM of a fragment pack: out[m] = x[m] W (+ res[m]), M rows at the given pitches
+int kk_launch_csm_gemm_prompt(hipStream_t st, const KKCsmWeight& w, const float* x, long long xrs, int M, const float* res, long long rrs, float* out, long long ors);
+struct KKCsmGemv {  // what the caller of the matrix-core GEMV sets of its FGArgs (kk_csm_gemvm.h says what each prologue / epilogue reads)
+  const float* x = nullptr; long long xrs = 0;
+  const float* nw = nullptr; float eps = 0.f;
+  const int* codes = nullptr; int cstride = 0, cb = 0, V = 0, rows = 0; const float* emb = nullptr;
+  float* gather_out = nullptr;
+  const float* res = nullptr; long long rrs = 0;
+  float* out = nullptr; long long ors = 0;
+};
+int kk_launch_csm_gemv(hipStream_t st, const KKCsmWeight& w, int pro, int epi, const KKCsmGemv& a, int Mtot);
+// h[m][:] += x[m] W, in place or (w.ks > 1) through the slices in `part` ([ks][M][Cout]) and one combine
+int kk_launch_csm_gemv_accumulate(hipStream_t st, const KKCsmWeight& w, int pro, const KKCsmGemv& a, int M, float* h, float* part);
+// fp32 bits -> bf16 bits, round to nearest even (a NaN is truncated): the rounding of every bf16 pack, and of the fp32 pack beside it in bf16 weight mode
+inline uint32_t kk_csm_bf16_round(uint32_t u) {
+  if ((u & 0x7FFFFFFFu) <= 0x7F800000u) u += 0x7FFFu + ((u >> 16) & 1u);
+  return u >> 16;
+}
+// the packs (host): the plan of a K x N matrix (*nsub = 0: none), the bf16 fragment pack of w [K][ldw], the quantised packs part by part
+void kk_csm_frag_plan(int K, int N, bool split_ok, int* ks, int* nsub);
+size_t kk_csm_frag_elems(int K, int N, int nsub);
+void kk_csm_frag_pack_rows(const float* w, int K, int N, long long ldw, int nsub, uint16_t* out);
+bool kk_csm_group_ok(int K, int group);
+size_t kk_csm_qfrag_q_bytes(int K, int N, int nsub, int bits);
+size_t kk_csm_qfrag_pair_bytes(int K, int N, int nsub, int group);
+void kk_csm_qfrag_pack_part(const uint32_t* words, const float* scales, const float* biases, int O, int n0, int K, int nsub, int group, int bits, uint8_t* q,
+                            float* pairs);
+// kk_csm_debug_timestamps: the next launch's slot (null in production), and the buffer itself for a graph key
+unsigned long long* kk_csm_ts_slot();
+const void* kk_csm_ts_buffer();
+// the sampler (kk_csm_sample.hip).  Where a launch takes its uniforms from, and kk_csm_sampler as the kernels read it: the kernels' own argument
+// types derive from these two
+struct KKCsmSampleSrc {
+  const float* u = nullptr;  // [B] at pitch ustride, or null
+  int ustride = 0;
+  const unsigned long long* seed = nullptr;  // device; null = no device RNG
+  int seed_stride = 0;                       // 64-bit words between the seeds of two items: 0 = one word for the launch, 4 = the row's table entry
+  const int* sid = nullptr;                  // [B] stream ids, null = batch index
+  const int* pos = nullptr;                  // device position(s): pos[b * pos_stride]
+  int pos_stride = 0, pos_add = 0;
+  const int* pad = nullptr;                  // [B] left padding, or null
+  int cb = 0;
+};
+struct KKCsmSampleCfg {
+  float temp = 0.f;
+  int top_k = 0;
+  float top_p = 0.f, min_p = 0.f;
+  int min_keep = 1;
+};
+int kk_csm_sampler_cfg(const kk_csm_sampler* sp, KKCsmSampleCfg* c, const char* who);  // checks the ranges (the refusal names `who`)
+int kk_launch_csm_sample(hipStream_t st, const float* logits, int V, const KKCsmSampleCfg& cfg, const KKCsmSampleSrc& src, int* out, int ostride, int B);
+// row b's settings from entry b of a table of KK_CSM_ROW_SAMPLER_BYTES per row; src.seed non-null only says that the launch draws: the word is the entry's
+constexpr size_t KK_CSM_ROW_SAMPLER_BYTES = 32;
+int kk_launch_csm_sample_rows(hipStream_t st, const float* logits, int V, const void* table, KKCsmSampleSrc src, int* out, int ostride, int B);
+int kk_launch_csm_set_row_sampler(hipStream_t st, void* table, int row, const KKCsmSampleCfg& c, unsigned long long seed);

@@ -1,5 +1,5 @@
-// In-kernel wall-clock marks of the instrumented CSM kernels (kk_csm_debug_timestamps; layout of the 8 words per launch: kk_csm.hip, g_ts).
-// `ts` is null in production.  Included inside the anonymous namespace of each file that has such a kernel (kk_csm.hip through
+// In-kernel wall-clock marks of the instrumented CSM kernels (kk_csm_debug_timestamps; layout of the 8 words per launch: kk_csm_kernels.hip, g_ts).
+// `ts` is null in production.  Included inside the anonymous namespace of each file that has such a kernel (kk_csm_kernels.hip through
 // kk_csm_gemvm.h, kk_attn_cache.hip).
 #pragma once
 #include <hip/hip_runtime.h>
