@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 31  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 32  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -85,7 +85,10 @@ extern "C" {
                                kk_op_source_stft_ragged);
                             30: SNAC with LocalMHA, the 32 / 44 kHz checkpoints (kk_snac_create_attn, kk_op_snac_local_attn);
                             31: the Parakeet encoder's hot blocks on caller-owned buffers (kk_op_rel_pos_attention, kk_op_conformer_dwconv,
-                               kk_op_conv2d_s2), its features (kk_op_parakeet_log_mel) and its encoder behind a handle (kk_parakeet_*) */
+                               kk_op_conv2d_s2), its features (kk_op_parakeet_log_mel) and its encoder behind a handle (kk_parakeet_*);
+                            32: Parakeet's text side: the fused LSTM cell step and the joint with arg-maximum on caller-owned buffers
+                               (kk_op_lstm_pack, kk_op_lstm_cell_rows, kk_op_joint_argmax, kk_op_ctc_argmax) and TDT / RNNT / CTC greedy decoding
+                               behind a handle (kk_parakeet_text_*) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -1365,6 +1368,63 @@ int kk_parakeet_encode_frames(const kk_parakeet* m, int T_mel);
 size_t kk_parakeet_encode_workspace_bytes(const kk_parakeet* m, int B, int T_mel);
 int kk_parakeet_encode(kk_parakeet* m, void* stream, int B, int T_mel, const float* mel, const void* pos_emb, void* workspace, size_t workspace_bytes,
                        float* out);
+
+/* =====================================================================================================================
+ * Parakeet, text side (ABI minor 32; csrc/kk_parakeet_text.hip): the prediction network, the joint and the greedy loops of
+ * mlx_audio/stt/models/parakeet/rnnt.py and parakeet.py:307-599 for up to KK_PARAKEET_TEXT_MAX_ROWS rows in lock step.  Device pointers unless
+ * a parameter says HOST; work is enqueued on `stream`; every refusal is made before anything is launched.
+ * ===================================================================================================================== */
+#define KK_PARAKEET_TEXT_MAX_ROWS 16
+#define KK_PARAKEET_MAX_DURATIONS 16
+enum { KK_PARAKEET_TDT = 0, KK_PARAKEET_RNNT = 1, KK_PARAKEET_CTC = 2 };
+enum { KK_JOINT_RELU = 0, KK_JOINT_SIGMOID = 1, KK_JOINT_TANH = 2 };
+
+/* One LSTM layer, one time step, M <= 16 rows (rnnt.py:37-85 for a sequence of one).  kk_op_lstm_pack (host, no device work) turns MLX's Wx [4H][in],
+ * Wh [4H][H] and bias [4H] (gate order i, f, g, o; bias may be null) into the kernel's operands: w_out, kk_op_lstm_pack_elems(in, H) bf16 values --
+ * [Wx | Wh] with gate row g H + u moved to row 16 (u / 4) + 4 (u % 4) + g, in MFMA fragment order -- and bias_out [4H] in the same row order.
+ * The step: x is row token[m] of the bf16 table embed [n_embed][in] (zeros when token[m] == blank or is outside the table), or, with embed null,
+ * the fp32 row m of x at pitch ldx.  h and c hold two copies each, [2][..][H] with copy_stride elements between the copies and rows of H: row m
+ * reads copy idx[m] and writes copy 1 - idx[m].  Rows with mask[m] == 0 are neither computed nor written.  in and H are multiples of 32. */
+size_t kk_op_lstm_pack_elems(int in, int H);
+int kk_op_lstm_pack(const float* wx, const float* wh, const float* bias, int in, int H, void* w_out, float* bias_out);
+int kk_op_lstm_cell_rows(void* stream, int M, int in, int H, const void* w_packed, const float* bias_packed, const void* embed, int n_embed,
+                         const int32_t* token, int blank, const float* x, long long ldx, float* h, float* c, long long copy_stride, const int32_t* idx,
+                         const int32_t* mask);
+
+/* The joint's output Linear with both arg-maxima (rnnt.py:148-157 and the loop's mx.argmax calls): logits[m] = act(encp[m][t[m]] + predp[m]) W^T + bias for
+ * M <= 16 rows; encp fp32 [M][T_rows][Hj] (joint.enc of every frame, bias folded), predp fp32 [M][Hj], W bf16 [C][Hj] dense, act KK_JOINT_*.  tok[m] is the
+ * lowest arg-maximum over classes [0, V1), dur[m] (may be null) over [V1, C) counted from V1, or -1 for an empty range.  logits: fp32 [M][C] or null.
+ * kk_op_ctc_argmax is the same kernel over plain feature rows (fp32 or bf16, KK_DTYPE_*) [rows][ldf], any number of rows: ids[r] over all C classes.
+ * scratch: kk_op_joint_argmax_scratch_bytes(rows, C) bytes, 16-byte aligned.  Hj / K are multiples of 32. */
+size_t kk_op_joint_argmax_scratch_bytes(int rows, int C);
+int kk_op_joint_argmax(void* stream, int M, int Hj, int C, int V1, int act, const void* w, const float* bias, const float* encp, int T_rows, const int32_t* t,
+                       const float* predp, float* logits, void* scratch, size_t scratch_bytes, int32_t* tok, int32_t* dur);
+int kk_op_ctc_argmax(void* stream, int rows, int K, int C, const void* w, const float* bias, const void* feat, int feat_dtype, long long ldf, float* logits,
+                     void* scratch, size_t scratch_bytes, int32_t* ids);
+
+/* Greedy decoding behind a handle.  Tensors (fp32, rounded to bf16 once at finalize): embed [n_embed][H]; lstm.<i>.wx [4H][H], lstm.<i>.wh [4H][H],
+ * lstm.<i>.b [4H]; joint.pred.w [Hj][H], .b; joint.enc.w [Hj][encoder_hidden], .b; joint.out.w [C][Hj], .b with C = vocab + 1 + n_durations (RNNT: none);
+ * a CTC model has only ctc.w [vocab + 1][encoder_hidden] and ctc.b.  max_symbols < 0 means none; n_embed 0 means vocab + 1.
+ * begin: features fp32 [B][T][encoder_hidden], lengths HOST [B]; state is a caller-owned device buffer of kk_parakeet_text_state_bytes(m, B, T, cap) bytes
+ * that must live until the batch has been read.  A row ends when its frame index reaches its length (flag 1), or TRUNCATED (flag 2) when it holds `cap`
+ * tokens or has taken `step_cap` steps -- with max_symbols none the reference itself does not end on a blank of duration 0.  steps enqueues n steps
+ * (joint, decide, LSTM layers, joint.pred) with no host sync and then, with live non-null, reads the number of running rows (HOST), which waits for
+ * the stream.  read (waits): counts [B], flags [B], tokens [B][cap][3] = (token, frame, duration index), all HOST.  ctc: ids [rows] of fp32 features
+ * [rows][encoder_hidden]; workspace of kk_parakeet_text_state_bytes(m, rows, 1, 1) bytes. */
+typedef struct kk_parakeet_text kk_parakeet_text;
+typedef struct kk_parakeet_text_config {
+  int32_t kind, vocab, n_embed, pred_hidden, pred_layers, joint_hidden, encoder_hidden, activation, n_durations, durations[KK_PARAKEET_MAX_DURATIONS], max_symbols;
+} kk_parakeet_text_config;
+int kk_parakeet_text_create(const kk_parakeet_text_config* cfg, kk_parakeet_text** out);
+void kk_parakeet_text_destroy(kk_parakeet_text* m);
+int kk_parakeet_text_load_tensor(kk_parakeet_text* m, const char* name, const int64_t* shape, int ndim, const float* data);
+int kk_parakeet_text_finalize(kk_parakeet_text* m, void* stream);
+size_t kk_parakeet_text_state_bytes(kk_parakeet_text* m, int B, int T, int cap);
+int kk_parakeet_text_begin(kk_parakeet_text* m, void* stream, int B, int T, const float* features, const int32_t* lengths, int cap, int step_cap, void* state,
+                           size_t state_bytes);
+int kk_parakeet_text_steps(kk_parakeet_text* m, void* stream, int n, int32_t* live);
+int kk_parakeet_text_read(kk_parakeet_text* m, void* stream, int32_t* counts, int32_t* flags, int32_t* tokens);
+int kk_parakeet_text_ctc(kk_parakeet_text* m, void* stream, int rows, const float* features, int32_t* ids, void* workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

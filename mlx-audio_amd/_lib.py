@@ -59,6 +59,16 @@ class KKParakeetConfig(C.Structure):  # kk_parakeet_config
                                          "subsampling_conv_channels")]
 
 
+class KKParakeetTextConfig(C.Structure):  # kk_parakeet_text_config
+    _fields_ = [(n, C.c_int32) for n in ("kind", "vocab", "n_embed", "pred_hidden", "pred_layers", "joint_hidden", "encoder_hidden", "activation",
+                                         "n_durations")] + [("durations", C.c_int32 * 16), ("max_symbols", C.c_int32)]
+
+
+PARAKEET_TEXT_MAX_ROWS = 16  # KK_PARAKEET_TEXT_MAX_ROWS
+PARAKEET_TDT, PARAKEET_RNNT, PARAKEET_CTC = 0, 1, 2  # KK_PARAKEET_*
+JOINT_ACTIVATIONS = {"relu": 0, "sigmoid": 1, "tanh": 2}  # KK_JOINT_*
+
+
 class KKWhisperTextConfig(C.Structure):
     _fields_ = [("n_vocab", C.c_int32), ("n_text_ctx", C.c_int32), ("n_text_state", C.c_int32), ("n_text_head", C.c_int32),
                 ("n_text_layer", C.c_int32), ("n_audio_ctx", C.c_int32), ("n_audio_state", C.c_int32)]
@@ -371,6 +381,21 @@ SIGNATURES = {
     "kk_parakeet_encode_frames": (_i, [_vp, _i]),
     "kk_parakeet_encode_workspace_bytes": (_sz, [_vp, _i, _i]),
     "kk_parakeet_encode": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "kk_op_lstm_pack_elems": (_sz, [_i, _i]),
+    "kk_op_lstm_pack": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "kk_op_lstm_cell_rows": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, C.c_longlong, _vp, _vp, C.c_longlong, _vp, _vp]),
+    "kk_op_joint_argmax_scratch_bytes": (_sz, [_i, _i]),
+    "kk_op_joint_argmax": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "kk_op_ctc_argmax": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, C.c_longlong, _vp, _vp, _sz, _vp]),
+    "kk_parakeet_text_create": (_i, [C.POINTER(KKParakeetTextConfig), C.POINTER(_vp)]),
+    "kk_parakeet_text_destroy": (None, [_vp]),
+    "kk_parakeet_text_load_tensor": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), _i, _vp]),
+    "kk_parakeet_text_finalize": (_i, [_vp, _vp]),
+    "kk_parakeet_text_state_bytes": (_sz, [_vp, _i, _i, _i]),
+    "kk_parakeet_text_begin": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _sz]),
+    "kk_parakeet_text_steps": (_i, [_vp, _vp, _i, C.POINTER(C.c_int32)]),
+    "kk_parakeet_text_read": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "kk_parakeet_text_ctc": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _sz]),
     "kk_mimi_debug_info": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "kk_mimi_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
     "kk_debug_set_op_wfrag": (None, [_vp]),
@@ -419,7 +444,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 31:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 32:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -20,11 +20,11 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-std=c++17", "-Wall", "-Wno-unused-function"]
 
 
-# per-file extras.  kk_parakeet.hip, kk_snac_attn.hip: fp32 arithmetic written per element beside matrix instructions, kept on the scalar fp32 VALU
+# per-file extras.  kk_parakeet.hip, kk_parakeet_text.hip, kk_snac_attn.hip: fp32 arithmetic written per element beside matrix instructions, kept on the scalar fp32 VALU
 # forms (NO_PK_F32) so that no packed-fp32 instruction is formed from it.  kk_source.hip: the iSTFT head is written on explicit register pairs (v_pk_*_f32); hipcc's SLP vectoriser otherwise
 # re-pairs the scalar tail across outputs and pays two v_mov per packed op it creates
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]  # scalar fp32 VALU only: the arithmetic is written per element
-FILE_FLAGS = {"kk_snac_attn.hip": NO_PK_F32, "kk_parakeet.hip": NO_PK_F32, "kk_source.hip": ["-fno-slp-vectorize"], "kk_head.hip": ["-fno-slp-vectorize"], "kk_conv_mfma5.hip": ["-fno-slp-vectorize"], "kk_conv_mfma4.hip": ["-fno-slp-vectorize"], "kk_conv_mfma.hip": ["-fno-slp-vectorize"]}
+FILE_FLAGS = {"kk_snac_attn.hip": NO_PK_F32, "kk_parakeet.hip": NO_PK_F32, "kk_parakeet_text.hip": NO_PK_F32, "kk_source.hip": ["-fno-slp-vectorize"], "kk_head.hip": ["-fno-slp-vectorize"], "kk_conv_mfma5.hip": ["-fno-slp-vectorize"], "kk_conv_mfma4.hip": ["-fno-slp-vectorize"], "kk_conv_mfma.hip": ["-fno-slp-vectorize"]}
 
 
 def _sources():

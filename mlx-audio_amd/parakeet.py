@@ -1,5 +1,6 @@
-"""Parakeet (FastConformer) on the device, audio side: the encoder's hot blocks that no other kernel of the library serves
-(mlx_audio/stt/models/parakeet/attention.py, conformer.py).  The arithmetic runs in libkokoro_hip.so (csrc/kk_parakeet.hip); there is
+"""Parakeet (FastConformer) on the device: the encoder's hot blocks that no other kernel of the library serves
+(mlx_audio/stt/models/parakeet/attention.py, conformer.py; csrc/kk_parakeet.hip) and the text side -- prediction network, joint and TDT / RNNT /
+CTC greedy decoding (rnnt.py, ctc.py, parakeet.py:307-599; csrc/kk_parakeet_text.hip).  The arithmetic runs in libkokoro_hip.so; there is
 no PyTorch fallback.  Tensors are torch tensors on the device; work is enqueued on torch's current stream.
 
     rel_pos_attention(qkv, pos, pos_bias_u, pos_bias_v, heads)   RelPositionMultiHeadAttention after its Linears, rel_shift included
@@ -8,18 +9,25 @@ no PyTorch fallback.  Tensors are torch tensors on the device; work is enqueued 
     fold_batch_norm(...)                                         depth-wise taps and bias with the inference-form BatchNorm folded in (float64)
     rel_positions(T, d_model)                                    RelPositionalEncoding's table for positions T - 1 .. -(T - 1) (float64)
     subsampled_lengths(lengths, factor)                          DwStridingSubsampling's length formula
+    pack_lstm(wx, wh, bias) / lstm_cell_rows(...)                one LSTM layer, one step, <= 16 rows, the cell in the matrix kernel's epilogue
+    joint_argmax(...) / ctc_argmax(...)                          the joint's output Linear (or the CTC head) with its arg-maxima
 
-    Model(config).load_weights(w) / Model.from_pretrained(dir)   the FastConformer encoder behind one handle: encode(mel) -> (features, lengths)
+    Model(config).load_weights(w) / Model.from_pretrained(dir)   encode(mel) -> (features, lengths); with a complete text side in the checkpoint also
+                                                                 decode_features(features, lengths), decode(mel), decode_chunk(audio) -> AlignedResult
 
     PreprocessArgs, log_mel_spectrogram(audio, args)             parakeet/audio.py's features on the device; Model.encode_audio(audio) chains the two
+    AlignedToken, AlignedSentence, AlignedResult, tokens_to_sentences, sentences_to_result, decode_tokens: alignment.py / tokenizer.py on the host
 
-What is NOT built: the whole text side (TDT / RNNT / CTC decoding, alignment, chunked generate, streaming caches); ragged masking and sub-samplings
-other than dw_striding."""
+Decoding caps: a TDT / RNNT row holds at most ms * T + 16 tokens and takes at most 2 * ms * T + 32 steps, T its batch's frame count and ms = max_symbols
+(8 when the config has none); with max_symbols set the reference itself stays below both, without it a row that would loop for ever ends `truncated`.
+
+What is NOT built: generate (file loading, chunk merging), streaming caches, beam search; ragged masking in the encoder and sub-samplings other
+than dw_striding."""
 from __future__ import annotations
 
 import ctypes as C
 import math
-from dataclasses import dataclass, fields
+from dataclasses import dataclass, field, fields
 
 import numpy as np
 
@@ -218,9 +226,207 @@ def log_mel_spectrogram(audio, args: PreprocessArgs):
     return out
 
 
+# ------------------------------------------------------------------------------------------------------------------------------- text side
+def pack_lstm(wx, wh, bias=None):
+    """MLX's Wx [4H][in], Wh [4H][H], bias [4H] (gates i, f, g, o) -> (w bf16 device, bias fp32 device) as lstm_cell_rows takes them: [Wx | Wh] with
+    gate row g H + u at row 16 (u // 4) + 4 (u % 4) + g, in MFMA fragment order (kk_op_lstm_pack).  The packed matrix is also kept as int16 numpy in .host."""
+    import torch
+
+    wx, wh = np.ascontiguousarray(wx, dtype=np.float32), np.ascontiguousarray(wh, dtype=np.float32)
+    H, n_in = wh.shape[1], wx.shape[1]
+    if wx.shape[0] != 4 * H or wh.shape[0] != 4 * H:
+        raise ValueError(f"Wx {wx.shape} / Wh {wh.shape}: need [4H][in] and [4H][H]")
+    b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
+    lib = _lib.load()
+    w_out, b_out = np.zeros(max(int(lib.kk_op_lstm_pack_elems(n_in, H)), 1), dtype=np.int16), np.zeros(4 * H, dtype=np.float32)
+    _lib.check(lib.kk_op_lstm_pack(wx.ctypes.data, wh.ctypes.data, None if b is None else b.ctypes.data, n_in, H, w_out.ctypes.data, b_out.ctypes.data),
+               "kk_op_lstm_pack")
+    if not torch.cuda.is_available():
+        return w_out, b_out
+    return torch.from_numpy(w_out).cuda().view(torch.bfloat16), torch.from_numpy(b_out).cuda()
+
+
+def lstm_cell_rows(w, bias, h, c, idx, mask, x=None, embed=None, token=None, blank=-1):
+    """One LSTM step in place: w, bias from pack_lstm; h, c fp32 [2][M][H] (two copies); idx, mask int32 [M]; x fp32 [M][in], or embed bf16 [n][in] with
+    token int32 [M] (a blank token is a zero input).  Row m reads copy idx[m] and writes copy 1 - idx[m]; rows with mask 0 are left alone."""
+    M, H = h.shape[1], h.shape[2]
+    n_in = (x if embed is None else embed).shape[1]
+    _lib.check(_lib.load().kk_op_lstm_cell_rows(_stream(), M, n_in, H, _p(w), _p(bias), None if embed is None else _p(embed), 0 if embed is None else embed.shape[0],
+                                                None if token is None else _p(token), int(blank), None if x is None else _p(x), n_in, _p(h), _p(c), M * H,
+                                                _p(idx), _p(mask)), "kk_op_lstm_cell_rows")
+
+
+def joint_argmax(w, bias, encp, t, predp, n_token: int, activation: str = "relu", want_logits: bool = False):
+    """w bf16 [C][Hj], bias fp32 [C], encp fp32 [M][T][Hj], t int32 [M], predp fp32 [M][Hj] -> (tok int32 [M] over classes [0, n_token), dur int32 [M] over
+    [n_token, C) counted from n_token, logits fp32 [M][C] or None)"""
+    import torch
+
+    if activation not in _lib.JOINT_ACTIVATIONS:
+        raise ValueError(f"unknown activation {activation!r}: relu, sigmoid or tanh")
+    M, T, Hj = encp.shape
+    Cn = w.shape[0]
+    lib = _lib.load()
+    scratch = torch.empty(max(int(lib.kk_op_joint_argmax_scratch_bytes(M, Cn)), 16), dtype=torch.uint8, device="cuda")
+    tok, dur = torch.empty(M, dtype=torch.int32, device="cuda"), torch.empty(M, dtype=torch.int32, device="cuda")
+    logits = torch.empty((M, Cn), dtype=torch.float32, device="cuda") if want_logits else None
+    _lib.check(lib.kk_op_joint_argmax(_stream(), M, Hj, Cn, n_token, _lib.JOINT_ACTIVATIONS[activation], _p(w), _p(bias), _p(encp), T, _p(t), _p(predp),
+                                      None if logits is None else _p(logits), _p(scratch), scratch.numel(), _p(tok), _p(dur)), "kk_op_joint_argmax")
+    return tok, dur, logits
+
+
+def ctc_argmax(w, bias, feat, want_logits: bool = False):
+    """The CTC head: w bf16 [C][K], bias fp32 [C], feat fp32 or bf16 [rows][K] -> (ids int32 [rows], logits or None)"""
+    import torch
+
+    rows, K = feat.shape
+    Cn = w.shape[0]
+    lib = _lib.load()
+    scratch = torch.empty(max(int(lib.kk_op_joint_argmax_scratch_bytes(rows, Cn)), 16), dtype=torch.uint8, device="cuda")
+    ids = torch.empty(rows, dtype=torch.int32, device="cuda")
+    logits = torch.empty((rows, Cn), dtype=torch.float32, device="cuda") if want_logits else None
+    _lib.check(lib.kk_op_ctc_argmax(_stream(), rows, K, Cn, _p(w), _p(bias), _p(feat), _lib.KK_BF16 if feat.dtype == torch.bfloat16 else _lib.KK_F32, K,
+                                    None if logits is None else _p(logits), _p(scratch), scratch.numel(), _p(ids)), "kk_op_ctc_argmax")
+    return ids, logits
+
+
+@dataclass
+class AlignedToken:
+    id: int
+    text: str
+    start: float
+    duration: float
+    end: float = 0.0
+
+    def __post_init__(self):
+        self.end = self.start + self.duration
+
+
+@dataclass
+class AlignedSentence:
+    text: str
+    tokens: list
+    start: float = 0.0
+    end: float = 0.0
+    duration: float = 0.0
+
+    def __post_init__(self):
+        self.tokens = sorted(self.tokens, key=lambda t: t.start)
+        self.start, self.end = self.tokens[0].start, self.tokens[-1].end
+        self.duration = self.end - self.start
+
+
+@dataclass
+class AlignedResult:
+    text: str
+    sentences: list = field(default_factory=list)
+    truncated: bool = False  # the row ended at a cap of the device loop, not at its last frame
+
+    def __post_init__(self):
+        self.text = self.text.strip()
+
+
+SENTENCE_ENDS = "!?。？！"
+
+
+def decode_tokens(tokens, vocabulary) -> str:
+    """tokenizer.decode: the pieces joined, the word-start mark as a space"""
+    return "".join(vocabulary[t].replace("▁", " ") for t in tokens)
+
+
+def tokens_to_sentences(tokens) -> list:
+    """A sentence ends behind a token that holds one of ! ? and their CJK forms, or a full stop that is last or followed by a token with a space."""
+    out, cur = [], []
+    for i, tok in enumerate(tokens):
+        cur.append(tok)
+        if any(ch in tok.text for ch in SENTENCE_ENDS) or ("." in tok.text and (i + 1 == len(tokens) or " " in tokens[i + 1].text)):
+            out.append(AlignedSentence("".join(t.text for t in cur), cur))
+            cur = []
+    if cur:
+        out.append(AlignedSentence("".join(t.text for t in cur), cur))
+    return out
+
+
+def sentences_to_result(sentences, truncated: bool = False) -> AlignedResult:
+    return AlignedResult("".join(s.text for s in sentences), sentences, truncated)
+
+
+def ctc_collapse(ids, blank: int):
+    """parakeet.py:526-594 on one row's per-frame best ids: [(token, first frame, end frame)] with repeats and blanks dropped.  A token ends where the next one
+    starts; the last one ends behind the row's last non-blank frame."""
+    ids = np.asarray(ids)
+    out, prev = [], -1
+    for t in np.flatnonzero(ids != blank):
+        if ids[t] != prev:  # (prev survives blanks, as in the reference: a b _ b is one b)
+            out.append([int(ids[t]), int(t), 0])
+            prev = ids[t]
+    for i, e in enumerate(out):
+        e[2] = out[i + 1][1] if i + 1 < len(out) else 0
+    if out:  # the last non-blank frame behind the last token's first one; the row's last frame when there is none, as in the reference
+        later = np.flatnonzero(ids[out[-1][1] + 1:] != blank)
+        out[-1][2] = (out[-1][1] + 1 + int(later[-1]) if len(later) else len(ids) - 1) + 1
+    return [tuple(e) for e in out]
+
+
+def text_side_spec(config: dict, w: dict):
+    """None when the config or the checkpoint lacks a complete text side; else (KKParakeetTextConfig fields, canonical tensors, vocabulary, durations).
+    A complete set with a misshapen tensor raises ValueError naming the checkpoint's tensor."""
+    target, tdt = config.get("target", ""), (config.get("model_defaults") or {}).get("tdt_durations")
+    dec, joint, decoding = config.get("decoder"), config.get("joint"), config.get("decoding")
+    De = config["encoder"]["d_model"]
+    f32 = lambda name: np.asarray(w[name], dtype=np.float32)  # noqa: E731
+
+    def shaped(name, shape):
+        a = f32(name)
+        a = a.reshape(a.shape[0], -1) if a.ndim == 3 else a  # a 1-wide conv, MLX or PyTorch layout
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError(f"{name}: shape {tuple(np.shape(w[name]))} does not fit the config, need {tuple(shape)}")
+        return np.ascontiguousarray(a)
+
+    if target.endswith("EncDecCTCModelBPE"):
+        if not (isinstance(dec, dict) and "vocabulary" in dec and "feat_in" in dec):
+            return None
+        names = ["decoder.decoder_layers.0.weight", "decoder.decoder_layers.0.bias"]
+        if any(n not in w for n in names):
+            return None
+        vocab = list(dec["vocabulary"])
+        cfg = dict(kind=_lib.PARAKEET_CTC, vocab=len(vocab), encoder_hidden=int(dec["feat_in"]))
+        return cfg, {"ctc.w": shaped(names[0], (len(vocab) + 1, dec["feat_in"])), "ctc.b": shaped(names[1], (len(vocab) + 1,))}, vocab, []
+    if not (target.endswith("EncDecRNNTBPEModel") or (target.endswith("EncDecHybridRNNTCTCBPEModel") and tdt is not None)):
+        return None
+    if not (isinstance(dec, dict) and isinstance(joint, dict) and isinstance(decoding, dict)):
+        return None
+    net, jn = dec["prednet"], joint["jointnet"]
+    H, L, Hj = int(net["pred_hidden"]), int(net["pred_rnn_layers"]), int(jn["joint_hidden"])
+    pre = "decoder.prediction."
+    names = [pre + "embed.weight", "joint.pred.weight", "joint.pred.bias", "joint.enc.weight", "joint.enc.bias", "joint.joint_net.2.weight", "joint.joint_net.2.bias"]
+    names += [pre + f"dec_rnn.lstm.{i}.{n}" for i in range(L) for n in ("Wx", "Wh", "bias")]
+    if any(n not in w for n in names):
+        return None
+    if net.get("rnn_hidden_size") and int(net["rnn_hidden_size"]) != H:
+        raise NotImplementedError("decoder.prednet.rnn_hidden_size other than pred_hidden is not built")
+    if jn["activation"] not in _lib.JOINT_ACTIVATIONS:
+        raise ValueError(f"joint.jointnet.activation = {jn['activation']!r}: relu, sigmoid or tanh")
+    vocab = list(joint["vocabulary"])
+    durations = [int(d) for d in decoding.get("durations", [])] if tdt is not None else []
+    V, n_embed = len(vocab), int(dec["vocab_size"]) + (1 if dec.get("blank_as_pad", True) else 0)
+    Cn = V + 1 + len(durations)
+    ms = (decoding.get("greedy") or {}).get("max_symbols")
+    cfg = dict(kind=_lib.PARAKEET_TDT if tdt is not None else _lib.PARAKEET_RNNT, vocab=V, n_embed=n_embed, pred_hidden=H, pred_layers=L, joint_hidden=Hj,
+               encoder_hidden=int(jn.get("encoder_hidden", De)), activation=_lib.JOINT_ACTIVATIONS[jn["activation"]], n_durations=len(durations),
+               durations=durations, max_symbols=-1 if ms is None else int(ms))
+    t = {"embed": shaped(names[0], (n_embed, H)), "joint.pred.w": shaped(names[1], (Hj, H)), "joint.pred.b": shaped(names[2], (Hj,)),
+         "joint.enc.w": shaped(names[3], (Hj, cfg["encoder_hidden"])), "joint.enc.b": shaped(names[4], (Hj,)), "joint.out.w": shaped(names[5], (Cn, Hj)),
+         "joint.out.b": shaped(names[6], (Cn,))}
+    for i in range(L):
+        for src, dst, shape in (("Wx", "wx", (4 * H, H)), ("Wh", "wh", (4 * H, H)), ("bias", "b", (4 * H,))):
+            t[f"lstm.{i}.{dst}"] = shaped(pre + f"dec_rnn.lstm.{i}.{src}", shape)
+    return cfg, t, vocab, durations
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------- encoder
 CONFORMER_KEYS = ("feat_in", "n_layers", "d_model", "n_heads", "ff_expansion_factor", "subsampling_factor", "conv_kernel_size", "subsampling_conv_channels")
-TEXT_SIDE = "the text side (prediction network, joint, TDT / RNNT / CTC decoding, alignment, chunked generate) is not built: Model.encode gives the encoder states"
+TEXT_SIDE = "the text side of this model is not built (no complete decoder / joint tensor set in the checkpoint): Model.encode gives the encoder states"
+GENERATE = "generate (the text side's file loading and chunk merging) is not built: decode_chunk(audio) transcribes one clip"
 
 
 def is_parakeet_config(config: dict) -> bool:
@@ -296,13 +502,17 @@ class Model:
         check_conformer_args(self.enc)
         self.preprocessor = PreprocessArgs.from_dict(config["preprocessor"]) if config.get("preprocessor") else None
         self._h, self._pos, self._ws, self.text_side_weights = None, {}, {}, {}
+        self._text, self.vocabulary, self.durations, self.check_interval = None, [], [], 32
 
     def __del__(self):
         if getattr(self, "_h", None):
             _lib.load().kk_parakeet_destroy(self._h)
+        if getattr(self, "_text", None):
+            _lib.load().kk_parakeet_text_destroy(self._text)
 
     def load_weights(self, weights: dict):
-        """weights: name -> array (numpy, or anything np.asarray takes).  `decoder.*`, `joint.*` and `ctc.*` are kept aside for the text side."""
+        """weights: name -> array (numpy, or anything np.asarray takes).  `decoder.*`, `joint.*` and `ctc.*` are kept in text_side_weights; the text side is
+        built when the config has its blocks and the checkpoint its complete tensor set (text_side_spec), else the model stays encoder-only."""
         import torch
 
         lib = _lib.load()
@@ -316,6 +526,19 @@ class Model:
             _lib.check(lib.kk_parakeet_load_tensor(h, name.encode(), shape, a.ndim, a.ctypes.data_as(C.c_void_p)), "kk_parakeet_load_tensor")
         torch.cuda.init()
         _lib.check(lib.kk_parakeet_finalize(h, _stream()), "kk_parakeet_finalize")
+        spec = text_side_spec(self.config, w)
+        if spec is not None:
+            cfg, tensors, self.vocabulary, self.durations = spec
+            c = _lib.KKParakeetTextConfig()
+            for k, v in cfg.items():
+                setattr(c, k, (C.c_int32 * 16)(*v) if k == "durations" else v)
+            th = C.c_void_p()
+            _lib.check(lib.kk_parakeet_text_create(C.byref(c), C.byref(th)), "kk_parakeet_text_create")
+            self._text, self._text_cfg = th, cfg
+            for name, a in tensors.items():
+                shape = (C.c_int64 * a.ndim)(*a.shape)
+                _lib.check(lib.kk_parakeet_text_load_tensor(th, name.encode(), shape, a.ndim, a.ctypes.data_as(C.c_void_p)), "kk_parakeet_text_load_tensor")
+            _lib.check(lib.kk_parakeet_text_finalize(th, _stream()), "kk_parakeet_text_finalize")
         return self
 
     @classmethod
@@ -369,7 +592,76 @@ class Model:
             raise ValueError("the config has no preprocessor block")
         return self.encode(log_mel_spectrogram(audio, self.preprocessor))
 
-    def decode(self, *a, **k):
-        raise NotImplementedError(TEXT_SIDE)
+    def _seconds(self, frames):
+        """frame count -> seconds, as the reference writes it: frames * subsampling_factor / sample_rate * hop_length"""
+        return frames * self.enc["subsampling_factor"] / self.preprocessor.sample_rate * self.preprocessor.hop_length
 
-    decode_chunk = generate = decode
+    def _result(self, triples, truncated=False):
+        toks = [AlignedToken(tok, decode_tokens([tok], self.vocabulary), self._seconds(start), dur) for tok, start, dur in triples]
+        return sentences_to_result(tokens_to_sentences(toks), truncated)
+
+    def decode_features_raw(self, features, lengths):
+        """The device loop alone: per row ([(token, frame, duration index)], truncated) for TDT / RNNT, ([(token, first frame, end frame)], False) for CTC"""
+        import torch
+
+        if self._text is None:
+            raise NotImplementedError(TEXT_SIDE)
+        lib, cfg = _lib.load(), self._text_cfg
+        features = torch.as_tensor(features, dtype=torch.float32).cuda().contiguous()
+        B, T, D = features.shape
+        lengths = np.asarray(lengths, dtype=np.int32)
+        if D != cfg["encoder_hidden"] or lengths.shape != (B,) or lengths.min() < 0 or lengths.max() > T:
+            raise ValueError(f"features {tuple(features.shape)} / lengths {lengths.tolist()}: need [B][T][{cfg['encoder_hidden']}] and B lengths in [0, T]")
+        if cfg["kind"] == _lib.PARAKEET_CTC:
+            ws = torch.empty(lib.kk_parakeet_text_state_bytes(self._text, B * T, 1, 1), dtype=torch.uint8, device="cuda")
+            ids = torch.empty(B * T, dtype=torch.int32, device="cuda")
+            _lib.check(lib.kk_parakeet_text_ctc(self._text, _stream(), B * T, _p(features), _p(ids), _p(ws), ws.numel()), "kk_parakeet_text_ctc")
+            ids = ids.cpu().numpy().reshape(B, T)
+            return [(ctc_collapse(ids[b, :lengths[b]], cfg["vocab"]), False) for b in range(B)]
+        out = []
+        for b0 in range(0, B, _lib.PARAKEET_TEXT_MAX_ROWS):  # batches of up to 16 rows in lock step
+            n = min(_lib.PARAKEET_TEXT_MAX_ROWS, B - b0)
+            ms = cfg["max_symbols"] if cfg["max_symbols"] > 0 else 8
+            cap, step_cap = ms * T + 16, 2 * ms * T + 32
+            state = torch.empty(lib.kk_parakeet_text_state_bytes(self._text, n, T, cap), dtype=torch.uint8, device="cuda")
+            lens = np.ascontiguousarray(lengths[b0:b0 + n])
+            _lib.check(lib.kk_parakeet_text_begin(self._text, _stream(), n, T, _p(features[b0:b0 + n]), lens.ctypes.data, cap, step_cap, _p(state), state.numel()),
+                       "kk_parakeet_text_begin")
+            live = C.c_int32(1)
+            while live.value > 0:  # the only host reads inside the loop: one counter every check_interval steps
+                _lib.check(lib.kk_parakeet_text_steps(self._text, _stream(), self.check_interval, C.byref(live)), "kk_parakeet_text_steps")
+            counts, flags, toks = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, cap, 3), np.int32)
+            _lib.check(lib.kk_parakeet_text_read(self._text, _stream(), counts.ctypes.data, flags.ctypes.data, toks.ctypes.data), "kk_parakeet_text_read")
+            out += [([tuple(int(v) for v in toks[b, i]) for i in range(counts[b])], bool(flags[b] == 2)) for b in range(n)]
+        return out
+
+    def decode_features(self, features, lengths):
+        """features fp32 [B][T][d_model] on the device, lengths [B] (ragged) -> [AlignedResult]: greedy TDT / RNNT / CTC decoding (a hybrid TDT-CTC checkpoint
+        decodes with TDT, as in the reference)"""
+        if self._text is not None and self.preprocessor is None:
+            raise ValueError("the config has no preprocessor block: token times need its sample_rate and hop")
+        res, kind = [], self._text_cfg["kind"] if self._text is not None else None
+        for triples, truncated in self.decode_features_raw(features, lengths):
+            if kind == _lib.PARAKEET_CTC:
+                res.append(self._result([(tok, a, self._seconds(e) - self._seconds(a)) for tok, a, e in triples]))
+            else:
+                res.append(self._result([(tok, t, self._seconds(self.durations[d] if kind == _lib.PARAKEET_TDT else 1)) for tok, t, d in triples], truncated))
+        return res
+
+    def decode(self, mel):
+        """mel [B][T_mel][feat_in] or [T_mel][feat_in] -> [AlignedResult]"""
+        if self._text is None:
+            raise NotImplementedError(TEXT_SIDE)
+        return self.decode_features(*self.encode(mel))
+
+    def decode_chunk(self, audio, verbose: bool = False):
+        """samples [n] at preprocessor.sample_rate -> AlignedResult"""
+        if self._text is None:
+            raise NotImplementedError(TEXT_SIDE)
+        result = self.decode(log_mel_spectrogram(audio, self.preprocessor))[0]
+        if verbose:
+            print(result.text)
+        return result
+
+    def generate(self, *a, **k):
+        raise NotImplementedError(GENERATE if self._text is not None else TEXT_SIDE)

@@ -83,7 +83,7 @@ def load_model(model_path, lazy: bool = False, strict: bool = True, compute_dtyp
         return whisper.load_model(path, kwargs.get("dtype"), weight_storage=weight_storage, **{k: v for k, v in kwargs.items() if k == "device"})
     from . import parakeet
 
-    if parakeet.is_parakeet_config(config):  # stt/models/parakeet: the audio side (encoder) only
+    if parakeet.is_parakeet_config(config):  # stt/models/parakeet: the encoder, and the text side when the checkpoint holds its tensors
         return parakeet.Model.from_pretrained(str(path))
     model_type = config.get("model_type") or (model_name[0] if model_name else None)
     weight_files = glob.glob(str(path / "*.safetensors"))
