@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 32  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 33  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -88,7 +88,9 @@ extern "C" {
                                kk_op_conv2d_s2), its features (kk_op_parakeet_log_mel) and its encoder behind a handle (kk_parakeet_*);
                             32: Parakeet's text side: the fused LSTM cell step and the joint with arg-maximum on caller-owned buffers
                                (kk_op_lstm_pack, kk_op_lstm_cell_rows, kk_op_joint_argmax, kk_op_ctc_argmax) and TDT / RNNT / CTC greedy decoding
-                               behind a handle (kk_parakeet_text_*) */
+                               behind a handle (kk_parakeet_text_*);
+                            33: the BigVGAN vocoder behind a handle (kk_bigvgan_*) and its fused anti-aliased Snake activation on caller-owned
+                               buffers (kk_op_bigvgan_amp_act, kk_op_bigvgan_filter) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -1425,6 +1427,46 @@ int kk_parakeet_text_begin(kk_parakeet_text* m, void* stream, int B, int T, cons
 int kk_parakeet_text_steps(kk_parakeet_text* m, void* stream, int n, int32_t* live);
 int kk_parakeet_text_read(kk_parakeet_text* m, void* stream, int32_t* counts, int32_t* flags, int32_t* tokens);
 int kk_parakeet_text_ctc(kk_parakeet_text* m, void* stream, int rows, const float* features, int32_t* ids, void* workspace, size_t workspace_bytes);
+
+/* =====================================================================================================================
+ * BigVGAN vocoder (ABI minor 33; csrc/kk_bigvgan.hip): mlx_audio/codec/models/bigvgan, mel -> waveform.  Device pointers unless a
+ * parameter says HOST; work is enqueued on `stream`; every refusal is made before anything is launched.
+ * ===================================================================================================================== */
+typedef struct kk_bigvgan kk_bigvgan;
+/* BigVGANConfig (bigvgan.py:14-26) with activation "snakebeta".  resblock: 1 (AMPBlock1) or 2 (AMPBlock2); list j of resblock_dilation_sizes holds
+ * n_dilations[j] entries.  bigvgan_v2_24khz_100band_256x: num_mels 100, rates {4,4,2,2,2,2}, kernels {8,8,4,4,4,4}, initial channel 1536, resblock 1,
+ * kernel sizes {3,7,11}, dilations {1,3,5} each, snake_logscale 1. */
+typedef struct kk_bigvgan_config {
+  int32_t num_mels, upsample_initial_channel, n_upsamples, upsample_rates[8], upsample_kernel_sizes[8];
+  int32_t resblock, n_resblock_kernels, resblock_kernel_sizes[4], n_dilations[4], resblock_dilation_sizes[4][4];
+  int32_t snake_logscale, use_bias_at_final, use_tanh_at_final, compute_dtype; /* KK_DTYPE_F32 or KK_DTYPE_BF16: the activations between the convs */
+} kk_bigvgan_config;
+int kk_bigvgan_create(const kk_bigvgan_config* cfg, kk_bigvgan** out);
+void kk_bigvgan_destroy(kk_bigvgan* m);
+/* The reference's parameter names in MLX layout (HOST fp32): WNConv1d weight_v [O][K][I], weight_g [O][1][1]; WNConvTranspose1d (ups.<i>.0) weight_v
+ * [O][K][I], weight_g [1][1][I]; <activation>.act.alpha / .act.beta [C].  The filter tensors are not loaded: the taps are made on the host. */
+int kk_bigvgan_load_tensor(kk_bigvgan* m, const char* name, const int64_t* shape, int ndim, const float* data);
+/* folds the weight norm in float64 (WNConv1d over the axes except 0, WNConvTranspose1d except 2), packs, uploads; waits for the upload */
+int kk_bigvgan_finalize(kk_bigvgan* m, void* stream);
+int64_t kk_bigvgan_samples(const kk_bigvgan* m, int T); /* samples per item for T mel frames (T prod(upsample_rates) when every kernel - rate is even) */
+size_t kk_bigvgan_workspace_bytes(kk_bigvgan* m, int B, int T);
+/* BigVGAN.__call__ (bigvgan.py:97-122).  mel fp32 [B][T][num_mels] (frames-major, the layout after the reference's first transpose);
+ * pcm_out fp32 [B][kk_bigvgan_samples].  An item's samples do not depend on B or on its place in the batch. */
+int kk_bigvgan_forward(kk_bigvgan* m, void* stream, int B, int T, const float* mel, void* workspace, size_t workspace_bytes, float* pcm_out);
+/* intermediates of the last forward as dense fp32 [B][rows][channels]: conv_pre, stage<i> (the mean over the AMP blocks), activation_post */
+int kk_bigvgan_debug_info(kk_bigvgan* m, const char* name, int64_t* rows, int64_t* channels);
+int kk_bigvgan_debug_fetch(kk_bigvgan* m, void* stream, const char* name, float* dst);
+
+/* The 12 taps of kaiser_sinc_filter1d(0.25, 0.3, 12) (resample.py:17-46) as the library makes them (float64, rounded once), HOST; both filters of
+ * Activation1d(up_ratio 2, down_ratio 2, kernel 12) are these taps.  Any other ratio or kernel size is refused. */
+int kk_op_bigvgan_filter(int up_ratio, int down_ratio, int kernel_size, float* taps_out);
+/* Activation1d(SnakeBeta) (resample.py:157-177) in one launch, x and out [B][L][ld] fp32 or bf16 (KK_DTYPE_*), item strides xbs / obs elements:
+ *   out[b][t][c] = sum_{k < 12} fd[k] s(u[clamp(2 t - 5 + k, 0, 2 L - 1)]),  s(v) = v + inv_beta[c] sin^2(alpha[c] v),
+ *   u[2 t] = 2 sum_{d = -3 .. 2} fu[5 - 2 d] x[clamp(t + d, 0, L - 1)],  u[2 t + 1] = 2 sum_{d = -2 .. 3} fu[6 - 2 d] x[clamp(t + d, 0, L - 1)].
+ * alpha / inv_beta: fp32 [C] (exp already applied for snake_logscale; inv_beta = 1 / (beta + 1e-9)).  Columns of out beyond C are not written.
+ * seg_rows: rows per time segment of a lane, 0 = chosen by shape; a row's bits do not depend on it, nor on B. */
+int kk_op_bigvgan_amp_act(void* stream, int B, const void* x, long long xbs, int ldx, int dtype, int L, int C, const float* alpha, const float* inv_beta,
+                          void* out, long long obs, int ldo, int seg_rows);
 
 #ifdef __cplusplus
 }

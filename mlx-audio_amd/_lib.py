@@ -49,6 +49,13 @@ class KKSnacConfig(C.Structure):  # kk_snac_config
     ]
 
 
+class KKBigVGANConfig(C.Structure):  # kk_bigvgan_config
+    _fields_ = [("num_mels", C.c_int32), ("upsample_initial_channel", C.c_int32), ("n_upsamples", C.c_int32), ("upsample_rates", C.c_int32 * 8),
+                ("upsample_kernel_sizes", C.c_int32 * 8), ("resblock", C.c_int32), ("n_resblock_kernels", C.c_int32), ("resblock_kernel_sizes", C.c_int32 * 4),
+                ("n_dilations", C.c_int32 * 4), ("resblock_dilation_sizes", (C.c_int32 * 4) * 4), ("snake_logscale", C.c_int32),
+                ("use_bias_at_final", C.c_int32), ("use_tanh_at_final", C.c_int32), ("compute_dtype", C.c_int32)]
+
+
 class KKWhisperConfig(C.Structure):
     _fields_ = [("n_mels", C.c_int32), ("n_audio_ctx", C.c_int32), ("n_audio_state", C.c_int32), ("n_audio_head", C.c_int32),
                 ("n_audio_layer", C.c_int32)]
@@ -396,6 +403,17 @@ SIGNATURES = {
     "kk_parakeet_text_steps": (_i, [_vp, _vp, _i, C.POINTER(C.c_int32)]),
     "kk_parakeet_text_read": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "kk_parakeet_text_ctc": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _sz]),
+    "kk_bigvgan_create": (_i, [C.POINTER(KKBigVGANConfig), C.POINTER(_vp)]),
+    "kk_bigvgan_destroy": (None, [_vp]),
+    "kk_bigvgan_load_tensor": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), _i, _vp]),
+    "kk_bigvgan_finalize": (_i, [_vp, _vp]),
+    "kk_bigvgan_samples": (C.c_int64, [_vp, _i]),
+    "kk_bigvgan_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "kk_bigvgan_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "kk_bigvgan_debug_info": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "kk_bigvgan_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
+    "kk_op_bigvgan_filter": (_i, [_i, _i, _i, C.POINTER(C.c_float)]),
+    "kk_op_bigvgan_amp_act": (_i, [_vp, _i, _vp, C.c_longlong, _i, _i, _i, _i, _vp, _vp, _vp, C.c_longlong, _i, _i]),
     "kk_mimi_debug_info": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "kk_mimi_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
     "kk_debug_set_op_wfrag": (None, [_vp]),
@@ -444,7 +462,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 32:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 33:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib

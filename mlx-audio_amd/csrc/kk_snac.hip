@@ -36,18 +36,11 @@
 #include "kk_common.h"
 #include "kk_kernels.h"
 #include "kk_host.h"
+#include "kk_codec_conv.h"
 #include "kk_snac_kernels.h"
 
 namespace {
 
-struct PackedConv {  // generic-kernel pack [K][Cin][ldw] fp32 (+ bias); bf16 decode: the variant-4 fragment pack as well
-  size_t w_off = 0, b_off = 0, wf_off = 0;
-  bool has_bias = false, mfma = false;
-  int Cin = 0, Cout = 0, K = 0, ldw = 0, CinP = 0, CoutP = 0;
-  const float* w = nullptr;
-  const float* b = nullptr;  // [CoutP] when mfma (zero padded), else [Cout]
-  const bf16_t* wf = nullptr;
-};
 struct DwConv {  // depth-wise k7: w [C][7], b [C]
   ArenaVec w, b;
   int C = 0;
@@ -103,44 +96,9 @@ struct kk_snac {
 
 namespace {
 
-struct Act {  // an activation tensor [B][rows][ld], C valid channels, dense
-  void* p = nullptr;
-  int rows = 0, C = 0, ld = 0, dtype = KK_F32;
-  long long bs() const { return (long long)rows * ld; }
-};
-int pitch_of(int C, int dtype) { return dtype == KK_BF16 ? rup(C, 64) : C; }  // bf16 tensors can feed the matrix-core kernel
-size_t esize(int dtype) { return dtype == KK_BF16 ? 2 : 4; }
-
-// every dense convolution of the codec: the matrix-core kernel for bf16 tensors with a fragment pack and an eligible shape, else the generic one
+// every dense convolution of the codec (kk_codec_conv.h): dilation 1, no scale, no accumulate
 int snac_conv(hipStream_t st, int B, const PackedConv& w, const Act& x, const Act& out, int pad, bool transposed, int stride, const Act* res, int* path) {
-  const int Lin = x.rows, Lout = out.rows;
-  if (w.mfma && x.dtype == KK_BF16 && out.dtype == KK_BF16 && x.ld >= w.CinP && kk_mfma_eligible(w.Cin, w.Cout, w.K, transposed ? KK_CONVT : KK_CONV, stride, 1)) {
-    KKMfmaArgs g;
-    memset(&g, 0, sizeof g);
-    g.x = (const bf16_t*)x.p; g.xbs = x.bs(); g.ldx = x.ld; g.wf = w.wf; g.CinP = w.CinP; g.Cin = w.Cin; g.CoutP = w.CoutP; g.bias = w.b;
-    g.out = out.p; g.obs = out.bs(); g.ldo = out.ld;
-    if (res) { g.res = res->p; g.rbs = res->bs(); g.ldr = res->ld; }
-    g.Cout = w.Cout; g.Kw = w.K; g.mode = transposed ? KK_CONVT : KK_CONV; g.stride = stride; g.pad = pad; g.dil = 1;
-    g.Q = transposed ? kk_cdiv(Lout, stride) : Lout; g.Lo_rows = Lout;
-    g.lin = KKLen{nullptr, 0, Lin}; g.lout = KKLen{nullptr, 0, Lout};
-    g.in_slope = 1.f; g.scale = 1.f;
-    g.slabwise = 1;
-    if (path) *path = KK_SNAC_UNIT_MFMA;
-    return kk_launch_conv_mfma4(g, B, KK_BF16, st);
-  }
-  KKConvArgs a;
-  memset(&a, 0, sizeof a);
-  a.x = x.p; a.xbs = x.bs(); a.ldx = x.ld;
-  a.w = w.w; a.ldw = w.ldw; a.bias = w.b;
-  a.out = out.p; a.obs = out.bs(); a.ldo = out.ld;
-  if (res) { a.res = res->p; a.rbs = res->bs(); a.ldr = res->ld; }
-  a.Cin = w.Cin; a.Cout = w.Cout; a.Kw = w.K;
-  a.mode = transposed ? KK_CONVT : KK_CONV; a.stride = stride; a.pad = pad; a.dil = 1;
-  a.Q = transposed ? kk_cdiv(Lout, stride) : Lout; a.Lo_rows = Lout;
-  a.lin = KKLen{nullptr, 0, Lin}; a.lout = KKLen{nullptr, 0, Lout};
-  a.in_slope = 1.f; a.scale = 1.f;
-  if (path) *path = KK_SNAC_UNIT_GENERIC;
-  return kk_launch_conv_generic(a, B, x.dtype, out.dtype, st);
+  return codec_conv(st, B, w, x, out, pad, transposed, stride, 1, res, 1.f, 0, path);
 }
 
 // ResidualUnit: out = x + W snake(dw7(snake(x))) + b in two launches (tmp: [B][rows][x.ld], x's dtype).  out may not alias x or tmp.
@@ -404,35 +362,7 @@ struct Packer {
   }
   template <typename At>
   PackedConv pack(const std::string& p, int O, int K, int I, bool bias, bool mfma, At at) {
-    PackedConv c;
-    c.Cin = I; c.Cout = O; c.K = K; c.ldw = rup(O, 64);
-    c.w_off = a.alloc((size_t)K * I * c.ldw);
-    float* dst = &a.pack[c.w_off];
-    for (int o = 0; o < O; ++o)
-      for (int k = 0; k < K; ++k)
-        for (int i = 0; i < I; ++i) dst[((size_t)k * I + i) * c.ldw + o] = at(o, k, i);
-    c.mfma = mfma && O % 8 == 0 && O >= 16 && I >= 16;
-    if (c.mfma) {
-      c.CinP = rup(I, 64);
-      c.CoutP = rup(O, 128);
-      const size_t nel = (size_t)K * c.CoutP * c.CinP;
-      c.wf_off = a.alloc((nel + 1) / 2);
-      uint16_t* dfr = (uint16_t*)&a.pack[c.wf_off];
-      for (int o = 0; o < O; ++o)
-        for (int k = 0; k < K; ++k)
-          for (int i = 0; i < I; ++i) dfr[kk_mfma4_pack_index(k, o, i, c.CoutP, c.CinP)] = f32_to_bf16_rne(at(o, k, i));
-    }
-    const int nb = c.mfma ? c.CoutP : O;
-    if (bias || c.mfma) {
-      c.has_bias = true;
-      c.b_off = a.alloc(nb);
-      if (bias) {
-        const HostTensor* b = a.get(p + ".bias", (size_t)O);
-        if (!b) return c;
-        memcpy(&a.pack[c.b_off], b->d.data(), (size_t)O * 4);
-      }
-    }
-    return c;
+    return codec_pack(a, p, O, K, I, bias, mfma, at);
   }
   DwConv dw(const std::string& p, int C) {
     DwConv d;
@@ -464,11 +394,7 @@ struct Packer {
   }
 };
 
-void resolve(kk_snac* m, PackedConv& c) {
-  c.w = m->arena.dev + c.w_off;
-  c.b = c.has_bias ? m->arena.dev + c.b_off : nullptr;
-  c.wf = c.mfma ? (const bf16_t*)(m->arena.dev + c.wf_off) : nullptr;
-}
+void resolve(kk_snac* m, PackedConv& c) { codec_resolve(m->arena, c); }
 void resolve(kk_snac* m, ArenaVec& v) { m->arena.resolve(v); }
 void resolve(kk_snac* m, DwConv& d) { resolve(m, d.w); resolve(m, d.b); }
 void resolve(kk_snac* m, LocalAttn& t) { resolve(m, t.ln_w); resolve(m, t.ln_b); resolve(m, t.qkv); resolve(m, t.out); }
