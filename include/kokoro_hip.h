@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define KK_ABI_VERSION 2 /* 2: forward / graph / debug / profile entry points take a kk_context: round 3 */
-#define KK_ABI_MINOR 33  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
+#define KK_ABI_MINOR 34  /* additions that leave every entry point of the major version as it was; 1: quantised CSM checkpoints (kk_csm_load_quantized ...);
                             2: the full CSM sampler and its device RNG (kk_csm_sampler, kk_csm_generate_frame_ex, kk_op_csm_sample_ex, kk_op_csm_uniforms);
                             3: continuous batching of CSM streams (kk_csm_admit, kk_csm_park_row, kk_csm_shift_caches, kk_csm_row_state, kk_csm_reset_caches_parked);
                             4: shared voice prefixes of CSM streams (kk_csm_prefix_*, kk_csm_admit_prefixed);
@@ -90,7 +90,9 @@ extern "C" {
                                (kk_op_lstm_pack, kk_op_lstm_cell_rows, kk_op_joint_argmax, kk_op_ctc_argmax) and TDT / RNNT / CTC greedy decoding
                                behind a handle (kk_parakeet_text_*);
                             33: the BigVGAN vocoder behind a handle (kk_bigvgan_*) and its fused anti-aliased Snake activation on caller-owned
-                               buffers (kk_op_bigvgan_amp_act, kk_op_bigvgan_filter) */
+                               buffers (kk_op_bigvgan_amp_act, kk_op_bigvgan_filter);
+                            34: the Vocos vocoder behind a handle (kk_vocos_*), its fused depth-wise conv -> LayerNorm and its FFT iSTFT head on
+                               caller-owned buffers (kk_op_vocos_dwconv_ln, kk_op_vocos_dwconv_rows, kk_op_vocos_istft) */
 
 enum { KK_DTYPE_F32 = 0, KK_DTYPE_BF16 = 1, KK_DTYPE_I32 = 2, KK_DTYPE_F16 = 3 };
 enum { KK_NOISE_ZERO = 0, KK_NOISE_INJECTED = 1, KK_NOISE_PHILOX = 2 };
@@ -1467,6 +1469,54 @@ int kk_op_bigvgan_filter(int up_ratio, int down_ratio, int kernel_size, float* t
  * seg_rows: rows per time segment of a lane, 0 = chosen by shape; a row's bits do not depend on it, nor on B. */
 int kk_op_bigvgan_amp_act(void* stream, int B, const void* x, long long xbs, int ldx, int dtype, int L, int C, const float* alpha, const float* inv_beta,
                           void* out, long long obs, int ldo, int seg_rows);
+
+/* =====================================================================================================================
+ * Vocos vocoder (ABI minor 34; csrc/kk_vocos.hip): mlx_audio/codec/models/vocos, features -> waveform.  Device pointers unless a
+ * parameter says HOST; work is enqueued on `stream`; every refusal is made before anything is launched.
+ * ===================================================================================================================== */
+typedef struct kk_vocos kk_vocos;
+/* VocosBackbone + ISTFTHead (vocos.py:119-140,210-260).  adanorm_num_embeddings: 0 = LayerNorm, > 0 = AdaLayerNorm (forward then takes the scale / shift
+ * pairs); final_norm_bias: the backbone's `bias`; padding_same: ISTFTHead(padding="same"), refused.  dim 1 .. 1024; n_fft 2^a or 5 2^a in 256 .. 2048
+ * with hop_length n_fft / 4.  vocos-mel-24khz: 100, 512, 1536, 8 layers, 0, 1, 1024 / 256; vocos-encodec-24khz: 128, 384, 1152, 8, 4, 1, 1280 / 320. */
+typedef struct kk_vocos_config {
+  int32_t input_channels, dim, intermediate_dim, num_layers, adanorm_num_embeddings, final_norm_bias, n_fft, hop_length, padding_same;
+  int32_t compute_dtype; /* KK_DTYPE_F32: every matrix on the fp32 conv path; KK_DTYPE_BF16: embed, pwconv1 / pwconv2 and the head Linear on the bf16
+                            matrix-core kernel.  The residual stream and the iSTFT are fp32 in both. */
+} kk_vocos_config;
+int kk_vocos_create(const kk_vocos_config* cfg, kk_vocos** out);
+void kk_vocos_destroy(kk_vocos* m);
+/* The reference's parameter names in MLX layout (HOST fp32): backbone.embed.weight [dim][7][in], backbone.convnext.<i>.dwconv.weight [dim][7][1],
+ * .pwconv1.weight [intermediate][dim], .pwconv2.weight [dim][intermediate], .gamma [dim], the LayerNorms' weight / bias, head.out.weight [n_fft + 2][dim],
+ * every bias.  An AdaLayerNorm's two Linears are not loaded: the caller applies them and hands the result to kk_vocos_forward. */
+int kk_vocos_load_tensor(kk_vocos* m, const char* name, const int64_t* shape, int ndim, const float* data);
+/* folds gamma into pwconv2's weight and bias in float64, packs, uploads; waits for the upload */
+int kk_vocos_finalize(kk_vocos* m, void* stream);
+int64_t kk_vocos_samples(const kk_vocos* m, int T); /* (T - 1) hop_length; 0 for T < 2 */
+size_t kk_vocos_workspace_bytes(kk_vocos* m, int B, int T);
+/* Vocos.decode (vocos.py:351-354).  features fp32 [B][T][input_channels] (frames-major); cond: null for a LayerNorm model, else fp32
+ * [num_layers + 1][B][2][dim], (scale, shift) = (cond Ws^T + bs, cond Wh^T + bh) of backbone.norm and of every block's norm, in that order;
+ * pcm_out fp32 [B][(T - 1) hop_length].  T >= 2.  An item's samples do not depend on B or on its place in the batch. */
+int kk_vocos_forward(kk_vocos* m, void* stream, int B, int T, const float* features, const float* cond, void* workspace, size_t workspace_bytes,
+                     float* pcm_out);
+/* intermediates of the last forward as dense fp32 [B][rows][channels]: embed, block<i>, backbone (after final_layer_norm), head (the Linear's output) */
+int kk_vocos_debug_info(kk_vocos* m, const char* name, int64_t* rows, int64_t* channels);
+int kk_vocos_debug_fetch(kk_vocos* m, void* stream, const char* name, float* dst);
+
+/* ConvNeXtBlock's dwconv (k 7, padding 3, groups = C) -> LayerNorm / AdaLayerNorm (vocos.py:176-181,202-207) in one launch, 1 <= C <= 1024:
+ *   out[b][t][c] = LN_c(bias[c] + sum_{k < 7} w[c][k] x[b][t - 3 + k][c]) a[b as_stride + c] + s[b as_stride + c],
+ * rows outside [0, T) read as zero; the variance is biased, eps inside the root.  x fp32 [B][T][ldx]; w fp32 [C][7] and bias [C], or both null: the
+ * LayerNorm alone; a / s fp32 [C] (as_stride 0: the LayerNorm's weight / bias) or one pair per item (as_stride >= C: AdaLayerNorm's scale / shift), either
+ * may be null (1 / 0); out fp32 or bf16 (KK_DTYPE_*) [B][T][ldo], columns beyond C are not written.  rows: time rows per workgroup, 0 = chosen by
+ * shape (kk_op_vocos_dwconv_rows(C)); (rows + 6) C floats must fit the 160 KB of LDS.  A row's bits do not depend on rows, on B or on the item's place. */
+int kk_op_vocos_dwconv_rows(int C);
+int kk_op_vocos_dwconv_ln(void* stream, int B, const float* x, long long xbs, int ldx, int T, int C, const float* w, const float* bias, const float* a,
+                          const float* s, long long as_stride, float eps, void* out, long long obs, int ldo, int out_dtype, int rows);
+/* ISTFTHead after its Linear (vocos.py:128-140, utils.py:104-158): h fp32 [B][T][ldh >= n_fft + 2], log-magnitudes then phases of the n_fft / 2 + 1 bins
+ * of T frames; S = min(exp(mag), 100) (cos p + i sin p), irfft (the imaginary parts of bins 0 and n_fft / 2 ignored), the symmetric Hann window
+ * 0.5 (1 - cos(2 pi n / (n_fft - 1))), overlap-add at hop_length, division by the summed window where it is not zero, the centre cut:
+ * out fp32 [B][(T - 1) hop_length] at item stride obs.  n_fft 2^a or 5 2^a in 256 .. 2048, hop_length n_fft / 4, T >= 2.  group: output hops per
+ * workgroup, 0 = chosen by shape (5); group + 3 frames of 2 n_fft floats must fit the 160 KB of LDS.  A sample's bits do not depend on group or on B. */
+int kk_op_vocos_istft(void* stream, int B, int T, const float* h, long long hbs, int ldh, int n_fft, int hop_length, float* out, long long obs, int group);
 
 #ifdef __cplusplus
 }

@@ -56,6 +56,11 @@ class KKBigVGANConfig(C.Structure):  # kk_bigvgan_config
                 ("use_bias_at_final", C.c_int32), ("use_tanh_at_final", C.c_int32), ("compute_dtype", C.c_int32)]
 
 
+class KKVocosConfig(C.Structure):  # kk_vocos_config
+    _fields_ = [(n, C.c_int32) for n in ("input_channels", "dim", "intermediate_dim", "num_layers", "adanorm_num_embeddings", "final_norm_bias", "n_fft",
+                                         "hop_length", "padding_same", "compute_dtype")]
+
+
 class KKWhisperConfig(C.Structure):
     _fields_ = [("n_mels", C.c_int32), ("n_audio_ctx", C.c_int32), ("n_audio_state", C.c_int32), ("n_audio_head", C.c_int32),
                 ("n_audio_layer", C.c_int32)]
@@ -414,6 +419,18 @@ SIGNATURES = {
     "kk_bigvgan_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
     "kk_op_bigvgan_filter": (_i, [_i, _i, _i, C.POINTER(C.c_float)]),
     "kk_op_bigvgan_amp_act": (_i, [_vp, _i, _vp, C.c_longlong, _i, _i, _i, _i, _vp, _vp, _vp, C.c_longlong, _i, _i]),
+    "kk_vocos_create": (_i, [C.POINTER(KKVocosConfig), C.POINTER(_vp)]),
+    "kk_vocos_destroy": (None, [_vp]),
+    "kk_vocos_load_tensor": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), _i, _vp]),
+    "kk_vocos_finalize": (_i, [_vp, _vp]),
+    "kk_vocos_samples": (C.c_int64, [_vp, _i]),
+    "kk_vocos_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "kk_vocos_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "kk_vocos_debug_info": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "kk_vocos_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
+    "kk_op_vocos_dwconv_rows": (_i, [_i]),
+    "kk_op_vocos_dwconv_ln": (_i, [_vp, _i, _vp, C.c_longlong, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_longlong, _f, _vp, C.c_longlong, _i, _i, _i]),
+    "kk_op_vocos_istft": (_i, [_vp, _i, _i, _vp, C.c_longlong, _i, _i, _i, _vp, C.c_longlong, _i]),
     "kk_mimi_debug_info": (_i, [_vp, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "kk_mimi_debug_fetch": (_i, [_vp, _vp, C.c_char_p, _vp]),
     "kk_debug_set_op_wfrag": (None, [_vp]),
@@ -462,7 +479,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
-    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 33:
+    if lib.kk_abi_version() != 2 or lib.kk_abi_minor() < 34:
         raise KokoroHipError("libkokoro_hip.so ABI version mismatch")
     _lib = lib
     return lib
